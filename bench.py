@@ -6,7 +6,7 @@ already resident in HBM: im2patches (35 tiles of 256x256 per image) -> U-Net (fp
 quantise + argmax -> meta_inference clean-up -> connected-component ecDNA count, followed - when more than one
 rank runs - by the path's only exchange: an all-gather of the per-image result records (RCCL over xGMI).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--images B] [--base 64]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--images B] [--base 64] [--dump-outputs DIR] [--full]
 
 ``--gpus N`` with N > 1 starts the N ranks itself (one process per GPU, ``torch.distributed.run`` on 127.0.0.1) when
 it is not already running under a launcher; under ``torch.distributed.run`` (RANK / WORLD_SIZE set) it is one rank.
@@ -16,11 +16,16 @@ Rank 0 prints ONE JSON line.  The workload is BASELINE.json configs[1] (single-G
 canonical classic U-Net (base width 64, 23 conv layers, 96.2 GFLOP per 256x256 patch), random-initialised with a fixed
 seed because metaseg.h5 is not distributable.
 
-Order of work at N = 1: (1) the CPU-baseline worker processes are STARTED (idle) before this process touches the GPU - no
-process is ever created after HIP is initialised; (2) the timed GPU region; (3) a host-inclusive leg (host arrays in,
-labels + counts back on the host); (4) the CPU baseline legs on the waiting workers (after the GPU timing: 20 s of
-all-core CPU load right before it cost 1.5 - 3 % of the GPU number); (5) full-size parity of the device results against
-the CPU results of (4).
+A plain run sets up, runs W untimed and K timed steps, writes the outputs of the last timed step when ``--dump-outputs``
+is given, and prints the headline line (value, ms_per_step, stage_ms_per_image).  Everything else is behind ``--full``:
+per-launch kernel profiling of the timed steps (roofline, roofline_8d, --layer-table), and at N = 1 the legs below.
+
+Order of work of ``--full`` at N = 1: (1) the CPU-baseline worker processes are STARTED (idle) before this process touches
+the GPU - no process is ever created after HIP is initialised; (2) the timed GPU region; (3) a host-inclusive leg (host
+arrays in, labels + counts back on the host); (4) the bf16x3 split leg, the overlay / preprocess / realistic-CCL /
+all-gather legs, the single-image latency, the narrow and UpSampling2D models; (5) the CPU baseline legs on the waiting
+workers (after the GPU timing: 20 s of all-core CPU load right before it cost 1.5 - 3 % of the GPU number); (6) full-size
+parity of the device results against the CPU results of (5).
 """
 import argparse
 import json
@@ -600,6 +605,30 @@ def model_summary(run, m):
     return res
 
 
+DUMP_SAMPLE_PX = 1 << 22          # label pixels kept per label array by --dump-outputs (at most 2 x 16 MiB as float32)
+
+
+def dump_outputs(run, gathered, out_dir):
+    """What the timed path returned in its last step, as float32 / float64 .npy files under out_dir: the raw argmax and
+    the cleaned labels of this rank's images (all pixels when they fit DUMP_SAMPLE_PX, else the same seeded sample of flat
+    indices into (B, H, W) for both), n_ec per image, and the gathered per-image records in image order.  Inputs and weights
+    are seeded, so two builds run with the same arguments can be compared file for file."""
+    os.makedirs(out_dir, exist_ok=True)
+    raw = run.raw.cpu().numpy().reshape(-1)
+    post = run.post.cpu().numpy().reshape(-1)
+    if raw.size > DUMP_SAMPLE_PX:
+        idx = np.unique(np.random.default_rng(0).integers(0, raw.size, DUMP_SAMPLE_PX))
+        raw, post = raw[idx], post[idx]
+    else:
+        raw, post = raw.reshape(run.B, H, W), post.reshape(run.B, H, W)
+    from ecseg_amd import dist as edist
+    arrays = {'raw_labels': raw.astype(np.float32), 'labels': post.astype(np.float32),
+              'n_ec': run.nec.cpu().numpy().astype(np.float32),
+              'records': edist.compact_records(gathered).astype(np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -613,17 +642,26 @@ def main():
     ap.add_argument('--direct', action='store_true', help='direct implicit-GEMM 3x3 kernel instead of Winograd')
     ap.add_argument('--wino', type=int, default=None, help='3x3 kernel: 0 direct, 1 Winograd F(2x2,3x3), 2 F(4x4,3x3) where eligible (default: library default)')
     ap.add_argument('--opt', action='append', default=[], help='library tuning knob key=value (ecseg_set_option), repeatable')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-kernel-profile', action='store_true')
-    ap.add_argument('--no-host-inclusive', action='store_true')
-    ap.add_argument('--no-narrow', action='store_true', help='skip the base-32 / base-16 legs and the single-image latency (N = 1 only)')
-    ap.add_argument('--layer-table', default=None, help='write the per-layer roofline table (JSON) to this path')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps write the outputs of the last one to DIR/<name>.npy (float32 / float64, < 64 MB)')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what the headline does not need: per-launch kernel profiling of the timed steps (roofline, '
+                         'roofline_8d), and at N = 1 the host-inclusive, split, device-leg, latency, narrow-model and CPU-baseline legs')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='(--full) skip the CPU baseline and the parity check')
+    ap.add_argument('--no-kernel-profile', action='store_true', help='(--full) time the steps without per-launch kernel profiling')
+    ap.add_argument('--no-host-inclusive', action='store_true', help='(--full) skip the host-inclusive leg')
+    ap.add_argument('--no-narrow', action='store_true', help='(--full) skip the base-32 / base-16 legs and the single-image latency (N = 1 only)')
+    ap.add_argument('--layer-table', default=None, help='(--full) write the per-layer roofline table (JSON) to this path')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
+    if args.layer_table and not args.full:
+        ap.error('--layer-table needs --full (per-launch kernel profiling)')
 
     under_launcher = 'WORLD_SIZE' in os.environ and 'RANK' in os.environ
     if args.gpus > 1 and not under_launcher:
         self_launch(args)
-    want_cpu = args.gpus <= 1 and int(os.environ.get('WORLD_SIZE', '1')) == 1 and not args.no_cpu_baseline
+    want_cpu = args.full and args.gpus <= 1 and int(os.environ.get('WORLD_SIZE', '1')) == 1 and not args.no_cpu_baseline
     pools = cpu_pools_start() if want_cpu else None              # worker processes exist before this process initialises HIP
 
     import torch                      # first: libecseg_hip.so then binds to the HIP runtime torch already loaded
@@ -643,8 +681,10 @@ def main():
     B = args.images
 
     run = DeviceRun(args.base, B, args.group, local, rank, world, args)
-    m = run.timed(args.steps, args.warmup, profile=not args.no_kernel_profile)
+    m = run.timed(args.steps, args.warmup, profile=args.full and not args.no_kernel_profile)
     hnd, model = run.hnd, run.model
+    if rank == 0 and args.dump_outputs:                     # before any other leg reuses the step's buffers
+        dump_outputs(run, m['out'], args.dump_outputs)
 
     if rank == 0:
         counts = edist.compact_records(m['out'])[:, edist.F_NEC]
@@ -662,7 +702,7 @@ def main():
                        'parallelism': 'image-parallel x%d, all-gather of 128-B records' % world, 'allgather': run.allgather_via},
             'stage_ms_per_image': summ['stage_ms_per_image'], 'ccl_ms_per_image': summ['ccl_ms_per_image'],
         }
-        if m['conv_launches']:
+        if args.full and m['conv_launches']:
             conv_ms, conv_launches, conv_flops, conv_exec = m['conv_ms'], m['conv_launches'], m['conv_flops'], m['conv_exec']
             # HBM bytes per launch from a committed rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE summary (tools/profile_round.sh) - only
             # one of THIS configuration (base, up-sampler, 3x3 kernel) measured on THESE kernel sources; anything else is stale
@@ -716,7 +756,7 @@ def main():
                 rows = layer_table(model, m['recs'], args.steps)
                 json.dump({'command': ' '.join(sys.argv), 'patches_per_launch': B * 35, 'peak_tflops': PEAK_FP32_MFMA_TFLOPS,
                            'layers': rows}, open(args.layer_table, 'w'), indent=1)
-        if world == 1 and not args.no_host_inclusive:
+        if args.full and world == 1 and not args.no_host_inclusive:
             # host arrays in (pageable numpy), labels + counts back on the host: H2D + device pipeline + D2H per call
             n_hi = 2
             hnd.segment_images(run.host, want_raw=False)
@@ -728,11 +768,11 @@ def main():
                                      'what': 'ecseg_segment_images: %d uint8 images from pageable host memory (H2D), device '
                                              'pipeline, post-processed labels + counts back to host memory (D2H), synchronous'
                                              % B}
-        if world == 1 and not args.no_narrow and wino_mode == 2:
+        if args.full and world == 1 and not args.no_narrow and wino_mode == 2:
             r4 = DeviceRun(args.base, B, args.group, local, rank, world, args)
             res['split_bf16x3'] = split_leg(r4, args.steps, summ['value'], wino_mode)
             r4.close()
-        if world == 1 and not args.no_narrow:
+        if args.full and world == 1 and not args.no_narrow:
             res.update(aux_device_legs(hnd, local))
             res['single_image_latency_ms'] = run.single_image_latency()
             # "also run base 32 and 16" - the same pipeline on the narrower canonical models with the automatic

@@ -16,7 +16,6 @@ from PIL import Image
 from ecseg_amd import image_io
 
 CONDA = '/opt/conda/bin/python3.9'
-EXAMPLE = '/root/reference/example_ecSeg/dapi.jpeg'
 
 
 def _fixtures(golden_dir):
@@ -89,12 +88,15 @@ def test_written_files_decode_with_tifffile(tmp_path):
     assert out.returncode == 0 and 'ok' in out.stdout, out.stderr[-1500:]
 
 
-@pytest.mark.skipif(not os.path.exists(EXAMPLE), reason='reference tree not present (GPU box)')
 def test_reference_example_file_decodes_to_the_stored_pixels(golden_dir):
     """example_ecSeg/dapi.jpeg is an OpenCV-written TIFF (LZW, predictor 2, 5 rows per strip): the real thing the reader
-    must handle; its pixels as decoded by skimage.io.imread are in dapi_example.npz."""
+    must handle; its pixels as decoded by skimage.io.imread are in dapi_example.npz.  dapi_example.tif holds those pixels
+    written by libtiff in the same layout (tools/make_example_tiff.py)."""
     want = np.load(os.path.join(golden_dir, 'dapi_example.npz'))['dapi']
-    assert np.array_equal(image_io.imread(EXAMPLE), want)
+    path = os.path.join(golden_dir, 'dapi_example.tif')
+    tags = Image.open(path).tag_v2
+    assert tags[259] == 5 and tags[317] == 2 and tags[278] == 5 and tags[258] == (8,) and tags[262] == 1
+    assert np.array_equal(image_io.imread(path), want)
 
 
 def test_lzw_roundtrip_and_corrupt_streams_do_not_crash():

@@ -9,10 +9,10 @@ mkdir -p $OUT
 for lib in "$@"; do
   tag=$(echo $lib | tr -c 'A-Za-z0-9\n' '_')
   export ECSEG_HIP_LIB=$R/ecseg_amd/$lib
-  cd $R && timeout -k 10 200 python3 bench.py --no-cpu-baseline --no-host-inclusive --no-narrow --steps 4 --warmup 1 --layer-table $OUT/lt_$tag.json > $OUT/bench_$tag.json 2> $OUT/bench_$tag.err
+  cd $R && timeout -k 10 200 python3 bench.py --full --no-cpu-baseline --no-host-inclusive --no-narrow --steps 4 --warmup 1 --layer-table $OUT/lt_$tag.json > $OUT/bench_$tag.json 2> $OUT/bench_$tag.err
   cd /tmp && export TMPDIR=/tmp
   for c in FETCH_SIZE WRITE_SIZE; do
-    timeout -k 10 300 rocprofv3 --pmc $c --output-format csv -d $OUT/pmc_${c}_$tag -o bench -- python3 $R/bench.py --no-cpu-baseline --no-host-inclusive --no-narrow --steps 1 --warmup 1 > $OUT/pmc_${c}_$tag.log 2>&1
+    timeout -k 10 300 rocprofv3 --pmc $c --output-format csv -d $OUT/pmc_${c}_$tag -o bench -- python3 $R/bench.py --full --no-cpu-baseline --no-host-inclusive --no-narrow --steps 1 --warmup 1 > $OUT/pmc_${c}_$tag.log 2>&1
     echo "$tag $c rc $?"
   done
   cd $R
