@@ -1,4 +1,4 @@
-.PHONY: build metaseg meta_overlay test asan clean
+.PHONY: build metaseg meta_overlay interseg test asan clean
 
 # same targets and config.yaml surface as the reference (Makefile:6-10); `build` compiles the gfx950 library first
 build:
@@ -9,6 +9,9 @@ metaseg: build
 
 meta_overlay: build
 	python src/meta_overlay.py
+
+interseg: build
+	python src/interseg.py
 
 test:
 	python -m pytest tests -q -m "not gpu"

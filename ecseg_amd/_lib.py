@@ -16,7 +16,7 @@ EXPORTS = [
     'ecseg_segment_images', 'ecseg_segment_images_ex', 'ecseg_segment_images_dev', 'ecseg_set_images_per_group', 'ecseg_set_option', 'ecseg_preprocess', 'ecseg_u16_to_u8',
     'ecseg_meta_segment', 'ecseg_prefetch_input', 'ecseg_host_alloc', 'ecseg_host_free',
     'ecseg_stitch_argmax', 'ecseg_meta_inference', 'ecseg_meta_inference_dev', 'ecseg_count_cc', 'ecseg_ccl_labels',
-    'ecseg_count_colocalization', 'ecseg_count_hsr', 'ecseg_overlay', 'ecseg_get_timings',
+    'ecseg_count_colocalization', 'ecseg_count_hsr', 'ecseg_overlay', 'ecseg_nuclei_regions', 'ecseg_nucleus_crops', 'ecseg_get_timings',
     'ecseg_set_kernel_profiling', 'ecseg_get_conv_profile', 'ecseg_get_conv_executed_flops', 'ecseg_get_conv_launch_profile', 'ecseg_debug_peek', 'ecseg_lzw_decode', 'ecseg_lzw_encode',
     'ecseg_comm_unique_id', 'ecseg_comm_create', 'ecseg_comm_destroy', 'ecseg_comm_last_error', 'ecseg_allgather_records', 'ecseg_allgather_records_dev',
     'ecseg_npy_write_i64', 'ecseg_png_write_labels', 'ecseg_png_write', 'ecseg_png_write_channel', 'ecseg_npy_label_info', 'ecseg_npy_read_labels_u8', 'ecseg_tiff_write_gray8', 'ecseg_tiff_info', 'ecseg_tiff_read',
@@ -95,6 +95,8 @@ def load_library():
     lib.ecseg_count_colocalization.argtypes = [vp, u8p, u8p, i32, i32, i32, vp]
     lib.ecseg_count_hsr.argtypes = [vp, u8p, u8p, i32, i32, i32, i32, vp]
     lib.ecseg_overlay.argtypes = [vp, u8p, u8p, i32, i32, i32, i32, i32, i32, vp]
+    lib.ecseg_nuclei_regions.argtypes = [vp, u8p, i32, i32, u8p, i32, i32, i32, i32, i32, vp, C.POINTER(C.c_int32)]
+    lib.ecseg_nucleus_crops.argtypes = [vp, vp, i32, vp, vp, vp]
     lib.ecseg_get_timings.argtypes = [vp, vp]
     lib.ecseg_set_kernel_profiling.argtypes = [vp, i32]
     lib.ecseg_get_conv_profile.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double)]
@@ -421,6 +423,36 @@ class Handle:
         self._check(self.lib.ecseg_overlay(self.h, _ptr(a), _ptr(r), n, H, W, r.shape[3], int(sensitivity),
                                            int(hsr_size_threshold), _ptr(out)), 'ecseg_overlay')
         return out[0] if single else out
+
+    # ---- interSeg driver ------------------------------------------------------------------------------
+    def nuclei_regions(self, seg, img, channel0, capacity=4096):
+        """(H, W) uint8 nucleus mask + (>= H, >= W, C) uint8 image -> int64 (n_regions, 8) records (ecseg_nuclei_regions): area,
+        bbox (min row, min col, max row + 1, max col + 1), sum of rows, sum of columns, sum of channel ``channel0``.  The region
+        map stays on the handle for ``nucleus_crops``."""
+        s = _u8(seg)
+        im = _u8(img)
+        if s.ndim != 2 or im.ndim != 3:
+            raise ValueError('nuclei_regions takes a (H, W) mask and an (H, W, C) image')
+        H, W = s.shape
+        n = C.c_int32()
+        cap = int(capacity)
+        while True:
+            rec = np.empty((max(cap, 1), 8), np.int64)
+            self._check(self.lib.ecseg_nuclei_regions(self.h, _ptr(s), H, W, _ptr(im), im.shape[0], im.shape[1], im.shape[2],
+                                                      int(channel0), cap, _ptr(rec), C.byref(n)), 'ecseg_nuclei_regions')
+            if n.value <= cap:
+                return rec[:n.value]
+            cap = n.value
+
+    def nucleus_crops(self, crops, channel_order=(0, 1, 2)):
+        """(N, 5) int32 (region, y0, x0, h, w) windows of the last ``nuclei_regions`` image -> (uint8 (N, 256, 256, 3) crops,
+        int32 (N, 3) per-channel maxima) (ecseg_nucleus_crops)."""
+        d = np.ascontiguousarray(crops, np.int32).reshape(-1, 5)
+        order = np.ascontiguousarray(channel_order, np.int32)
+        out = np.empty((len(d), 256, 256, 3), np.uint8)
+        mx = np.zeros((len(d), 3), np.int32)
+        self._check(self.lib.ecseg_nucleus_crops(self.h, _ptr(d), len(d), _ptr(order), _ptr(out), _ptr(mx)), 'ecseg_nucleus_crops')
+        return out, mx
 
     # ---- timing ---------------------------------------------------------------------------------------
     def timings(self):

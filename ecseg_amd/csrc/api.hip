@@ -117,6 +117,19 @@ struct ecseg_ctx {
     uint32_t* d_hist = nullptr; size_t d_hist_cap = 0;
     PostWorkspace ws{};
     size_t ws_list_bytes = 0;
+    // interSeg driver (ecseg_nuclei_regions -> ecseg_nucleus_crops): the region label map and the image stay here between the calls
+    int32_t* d_iseg_lab = nullptr; size_t d_iseg_lab_cap = 0;
+    uint8_t* d_iseg_img = nullptr; size_t d_iseg_img_cap = 0;
+    int32_t* d_iseg_rid = nullptr; size_t d_iseg_rid_cap = 0;
+    int32_t* d_iseg_blk = nullptr; size_t d_iseg_blk_cap = 0;
+    int32_t* d_iseg_misc = nullptr; size_t d_iseg_misc_cap = 0;
+    unsigned long long* d_iseg_acc = nullptr; size_t d_iseg_acc_cap = 0;
+    int32_t* d_iseg_bb = nullptr; size_t d_iseg_bb_cap = 0;
+    int64_t* d_iseg_rec = nullptr; size_t d_iseg_rec_cap = 0;
+    int32_t* d_iseg_desc = nullptr; size_t d_iseg_desc_cap = 0;
+    uint8_t* d_iseg_crops = nullptr; size_t d_iseg_crops_cap = 0;
+    int32_t* d_iseg_max = nullptr; size_t d_iseg_max_cap = 0;
+    int iseg_H = 0, iseg_W = 0, iseg_img_w = 0, iseg_C = 0, iseg_n = -1;   // iseg_n < 0: no region map on the handle
     // meta_inference is ~60 short dependent kernels: captured once per (buffers, geometry) into a HIP graph and replayed
     struct PostGraph { uint8_t* img; int32_t* nec; int n, H, W; hipStream_t s; hipGraphExec_t exec; unsigned long long stamp; };
     std::vector<PostGraph> post_graphs;
@@ -1159,6 +1172,9 @@ void ecseg_destroy(ecseg_ctx* h) {
     void* ptrs[] = {h->d_tie, h->d_tie_sh, h->d_sprobs, h->d_gray, h->d_raw, h->d_post, h->d_aux8, h->d_u8in, h->d_i32, h->d_i64, h->d_probs_in, h->d_hist,
                     h->ws.L, h->ws.area, h->ws.sumy, h->ws.sumx, h->ws.flag, h->ws.tmpA, h->ws.tmpB, h->ws.list, h->ws.g, h->ws.tile_any, h->ws.own_bits, h->ws.binned, h->ws.binstart};
     for (void* p : ptrs) if (p) (void)hipFree(p);
+    void* iseg[] = {h->d_iseg_lab, h->d_iseg_img, h->d_iseg_rid, h->d_iseg_blk, h->d_iseg_misc, h->d_iseg_acc, h->d_iseg_bb, h->d_iseg_rec,
+                    h->d_iseg_desc, h->d_iseg_crops, h->d_iseg_max};
+    for (void* p : iseg) if (p) (void)hipFree(p);
     for (auto& ev : h->ev) if (ev) (void)hipEventDestroy(ev);
     if (h->ev_block) (void)hipEventDestroy(h->ev_block);
     if (h->stream_in) { (void)hipStreamSynchronize(h->stream_in); (void)hipStreamDestroy(h->stream_in); }
@@ -1963,6 +1979,100 @@ int ecseg_overlay(ecseg_ctx* h, const uint8_t* labels, const uint8_t* rgb, int n
         HIP_TRY(h, run_overlay(h->ws, h->d_gray, h->d_aux8, ni, H, W, C, sens, hsr_thr, h->d_i64, s));
         HIP_TRY(h, hipEventRecord(h->ev[1], s));
         HIP_TRY(h, hipMemcpyAsync(out + (size_t)i0 * 12, h->d_i64, (size_t)ni * 12 * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipStreamSynchronize(s));
+        h->stage_ms[ECSEG_T_COUNT] += stage_elapsed(h->ev[0], h->ev[1]);
+    }
+    return ECSEG_OK;
+}
+
+// ---- interSeg driver (src/interseg.py:113-235) ----------------------------------------------------------------------
+int ecseg_nuclei_regions(ecseg_ctx* h, const uint8_t* seg, int H, int W, const uint8_t* img, int img_h, int img_w, int C,
+                         int channel0, int capacity, int64_t* records, int32_t* n_regions) {
+    if (!h) return ECSEG_E_INVALID;
+    drop_sent_ahead(h);
+    h->iseg_n = -1;
+    if (!seg || !img || !n_regions || H <= 0 || W <= 0 || img_h < H || img_w < W || C < 1 || channel0 < 0 || channel0 >= C ||
+        capacity < 0 || (capacity > 0 && !records))
+        return fail(h, ECSEG_E_INVALID, "nuclei_regions: bad arguments (the segmentation must not be larger than the image)");
+    if ((long long)H * W >= (1ll << 31) || (long long)H * img_w * C >= (1ll << 40)) return fail(h, ECSEG_E_INVALID, "image too large");
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t px = (size_t)H * W, img_bytes = (size_t)H * img_w * C;
+    const size_t nb = (px + 1023) / 1024, cap = (size_t)capacity;
+    int rc;
+    if ((rc = ensure_post(h, 1, px))) return rc;
+    if ((rc = ensure(h, h->d_gray, h->d_gray_cap, px))) return rc;
+    if ((rc = ensure(h, h->d_iseg_lab, h->d_iseg_lab_cap, px))) return rc;
+    if ((rc = ensure(h, h->d_iseg_img, h->d_iseg_img_cap, img_bytes))) return rc;
+    if ((rc = ensure(h, h->d_iseg_rid, h->d_iseg_rid_cap, px))) return rc;
+    if ((rc = ensure(h, h->d_iseg_blk, h->d_iseg_blk_cap, nb))) return rc;
+    if ((rc = ensure(h, h->d_iseg_misc, h->d_iseg_misc_cap, 4))) return rc;
+    if ((rc = ensure(h, h->d_iseg_acc, h->d_iseg_acc_cap, cap * 4))) return rc;
+    if ((rc = ensure(h, h->d_iseg_bb, h->d_iseg_bb_cap, cap * 4))) return rc;
+    if ((rc = ensure(h, h->d_iseg_rec, h->d_iseg_rec_cap, cap * 8))) return rc;
+    hipStream_t s = h->stream;
+    for (float& v : h->stage_ms) v = 0.f;
+    HIP_TRY(h, hipMemcpyAsync(h->d_gray, seg, px, hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(h->d_iseg_img, img, img_bytes, hipMemcpyHostToDevice, s));   // the first H rows: I[:imheight, :imwidth]
+    HIP_TRY(h, hipEventRecord(h->ev[0], s));
+    HIP_TRY(h, run_ccl_labels(h->ws, h->d_gray, 1, H, W, 8, h->d_iseg_lab, s));
+    const RegionBufs b{h->d_iseg_rid, h->d_iseg_blk, h->d_iseg_misc, h->d_iseg_acc, h->d_iseg_bb, h->d_iseg_rec, capacity};
+    HIP_TRY(h, run_nuclei_regions(h->d_gray, h->d_iseg_img, H, W, img_w, C, channel0, h->d_iseg_lab, b, s));
+    HIP_TRY(h, hipEventRecord(h->ev[1], s));
+    int32_t misc[4];
+    HIP_TRY(h, hipMemcpyAsync(misc, h->d_iseg_misc, sizeof(misc), hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    h->stage_ms[ECSEG_T_COUNT] = stage_elapsed(h->ev[0], h->ev[1]);
+    const int n = misc[0], vmax = misc[1], vmin = 255 - misc[2];
+    if (n > 0 && vmin != vmax)
+        return fail(h, ECSEG_E_INVALID, "segmentation holds the non-zero values " + std::to_string(vmin) + " .. " + std::to_string(vmax) +
+                                            ": only 0 / non-zero nucleus masks are supported, not instance-id maps");
+    *n_regions = n;
+    if (n <= capacity && n > 0) {
+        HIP_TRY(h, hipMemcpyAsync(records, h->d_iseg_rec, (size_t)n * 8 * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipStreamSynchronize(s));
+    }
+    h->iseg_H = H; h->iseg_W = W; h->iseg_img_w = img_w; h->iseg_C = C; h->iseg_n = n;
+    return ECSEG_OK;
+}
+
+int ecseg_nucleus_crops(ecseg_ctx* h, const int32_t* crops, int n_crops, const int32_t* channel_order, uint8_t* out,
+                        int32_t* channel_max) {
+    if (!h) return ECSEG_E_INVALID;
+    drop_sent_ahead(h);
+    if (n_crops < 0 || (n_crops > 0 && (!crops || !channel_order || !out || !channel_max)))
+        return fail(h, ECSEG_E_INVALID, "nucleus_crops: bad arguments");
+    if (n_crops == 0) return ECSEG_OK;
+    if (h->iseg_n < 0) return fail(h, ECSEG_E_INVALID, "nucleus_crops: no region map on the handle (call ecseg_nuclei_regions first)");
+    int order[3];
+    for (int c = 0; c < 3; ++c) {
+        order[c] = channel_order[c];
+        if (order[c] < 0 || order[c] >= h->iseg_C) return fail(h, ECSEG_E_INVALID, "nucleus_crops: channel_order out of range");
+    }
+    for (int k = 0; k < n_crops; ++k) {
+        const int32_t* d = crops + (size_t)k * 5;
+        if (d[0] < 0 || d[0] >= h->iseg_n || d[1] < 0 || d[2] < 0 || d[3] < 1 || d[3] > 256 || d[4] < 1 || d[4] > 256 ||
+            d[1] > h->iseg_H - d[3] || d[2] > h->iseg_W - d[4])
+            return fail(h, ECSEG_E_INVALID, "nucleus_crops: crop " + std::to_string(k) + " is not a 1..256 x 1..256 window of a region");
+    }
+    HIP_TRY(h, hipSetDevice(h->device));
+    const int chunk = 256;                                   // 48 MiB of crops per launch
+    const size_t crop_bytes = (size_t)256 * 256 * 3;
+    const int nc = std::min(n_crops, chunk);
+    int rc;
+    if ((rc = ensure(h, h->d_iseg_desc, h->d_iseg_desc_cap, (size_t)nc * 5))) return rc;
+    if ((rc = ensure(h, h->d_iseg_crops, h->d_iseg_crops_cap, (size_t)nc * crop_bytes))) return rc;
+    if ((rc = ensure(h, h->d_iseg_max, h->d_iseg_max_cap, (size_t)nc * 3))) return rc;
+    hipStream_t s = h->stream;
+    for (float& v : h->stage_ms) v = 0.f;
+    for (int k0 = 0; k0 < n_crops; k0 += chunk) {
+        const int k = std::min(chunk, n_crops - k0);
+        HIP_TRY(h, hipMemcpyAsync(h->d_iseg_desc, crops + (size_t)k0 * 5, (size_t)k * 5 * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        HIP_TRY(h, hipEventRecord(h->ev[0], s));
+        HIP_TRY(h, run_nucleus_crops(h->d_iseg_lab, h->d_iseg_img, h->iseg_W, h->iseg_img_w, h->iseg_C, h->d_iseg_desc, k, order,
+                                     h->d_iseg_crops, h->d_iseg_max, s));
+        HIP_TRY(h, hipEventRecord(h->ev[1], s));
+        HIP_TRY(h, hipMemcpyAsync(out + (size_t)k0 * crop_bytes, h->d_iseg_crops, (size_t)k * crop_bytes, hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipMemcpyAsync(channel_max + (size_t)k0 * 3, h->d_iseg_max, (size_t)k * 3 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
         HIP_TRY(h, hipStreamSynchronize(s));
         h->stage_ms[ECSEG_T_COUNT] += stage_elapsed(h->ev[0], h->ev[1]);
     }

@@ -206,4 +206,18 @@ hipError_t launch_u16_to_u8(const uint16_t* in, uint8_t* out, size_t count, hipS
 hipError_t run_preprocess(const void* img, int n_img, int H, int W, int C, int bps, uint8_t* gray, int32_t* inverted,
                           uint32_t* hist_ws, hipStream_t s);
 
+// ---- launchers implemented in interseg_kernels.hip (the file-level driver of src/interseg.py) ------------------------------
+// Device buffers of run_nuclei_regions: rid (H*W int32), blk (ceil(H*W / 1024) int32), misc (4 int32), and `cap` regions' worth
+// of acc (4 u64), bb (4 int32) and rec (8 int64).
+struct RegionBufs { int32_t* rid; int32_t* blk; int32_t* misc; unsigned long long* acc; int32_t* bb; int64_t* rec; int cap; };
+// labels: in, run_ccl_labels' 8-connected labels of seg != 0 (one image); out, 1 + region index (skimage's order), 0 background.
+// img: (>= H, img_w, C) uint8, channel ch0 summed per region.  misc[0] = number of regions, misc[1] = largest non-zero value of
+// seg, misc[2] = 255 - smallest; rec: the first min(cap, misc[0]) region records (see ecseg_nuclei_regions).
+hipError_t run_nuclei_regions(const uint8_t* seg, const uint8_t* img, int H, int W, int img_w, int C, int ch0, int32_t* labels,
+                              const RegionBufs& b, hipStream_t s);
+// desc: n crops (region, y0, x0, h, w), 1 <= h, w <= 256, inside the H x W label map -> out (n, 256, 256, 3) uint8 with channels
+// order[0..2] of img, chmax (n, 3) int32
+hipError_t run_nucleus_crops(const int32_t* labels, const uint8_t* img, int W, int img_w, int C, const int32_t* desc, int n,
+                             const int order[3], uint8_t* out, int32_t* chmax, hipStream_t s);
+
 }  // namespace ecseg

@@ -1,0 +1,276 @@
+// interSeg's file-level driver on gfx950 (reference src/interseg.py:104-235): the nuclei of a segmentation image as
+// region records, and the per-nucleus 256 x 256 crops the classifiers read.
+//
+// Regions (src/interseg.py:121-134: measure.label(seg, connectivity=None) + regionprops + the brightness gate)
+//   * the 8-connected labels come from run_ccl_labels (label = 1 + raster index of the component's first pixel, the
+//     pixel skimage numbers components by); the first pixels ("roots") are the pixels with label == index + 1, so a
+//     per-chunk root count, one scan and a per-chunk rank give every component its skimage region index;
+//   * iseg_region_stats_kernel relabels the map in place to region + 1 and accumulates area, bbox, sum of rows, sum of
+//     columns and the sum of the reordered channel 0.  A wave handles one 64-pixel row segment at a time: lanes of one
+//     region are folded with one shuffle butterfly, the fold's leader lane adds into a 64-slot LDS table keyed by region,
+//     and the table is flushed with one global atomic per (region, field, workgroup).
+// Crops (src/interseg.py:131-133,150-152,193-194 and im2patches_overlap :27-46)
+//   * crop (region, y0, x0, h, w), h, w <= 256: the window of the image with every pixel outside THIS region zeroed,
+//     resized to 256 x 256 as skimage.transform.resize(order=1, mode='reflect', preserve_range=True).astype(uint8) does
+//     with the exact affine map (scale h/256, offset scale/2 - 1/2): output row i samples row
+//     (h (2i + 1) - 256) / 512, a multiple of 1/512, so the bilinear value is a multiple of 2^-18 and
+//     value * 2^18 = sum of 4 weights (512 - f)(512 - g) ... times uint8 samples < 2^26 is exact in int32; trunc = >> 18.
+//     No floating point on the value path.  Sample rows lie in [-1/2, h - 1/2]: the only out-of-window taps are -1 and
+//     h, reflected to 1 and h - 2 (h = 1: row 0).
+#include <climits>
+
+#include "common.h"
+
+namespace ecseg {
+
+typedef unsigned long long u64;
+
+static constexpr int ISEG_CHUNK = 1024;          // pixels per root-count chunk (256 threads x 4)
+static constexpr int ISEG_SLOTS = 64;            // LDS table entries of iseg_region_stats_kernel
+static constexpr int ISEG_ROWS_PER_WAVE = 8;     // stats kernel: a block covers 64 columns x 32 rows
+static constexpr int ISEG_CROP_ROWS = 16;        // crops kernel: output rows per block
+
+__global__ __launch_bounds__(256) void iseg_root_count_kernel(const int32_t* __restrict__ L, int px, int32_t* __restrict__ cnt) {
+    const int base = blockIdx.x * ISEG_CHUNK;
+    int c = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int p = base + k * 256 + (int)threadIdx.x;
+        c += __syncthreads_count(p < px && L[p] == p + 1);
+    }
+    if (threadIdx.x == 0) cnt[blockIdx.x] = c;
+}
+
+// exclusive prefix over the chunk counts (one workgroup); misc[0] = number of regions
+__global__ __launch_bounds__(256) void iseg_scan_kernel(int32_t* __restrict__ cnt, int nb, int32_t* __restrict__ misc) {
+    __shared__ int s[256];
+    __shared__ int carry;
+    const int t = threadIdx.x;
+    if (t == 0) carry = 0;
+    __syncthreads();
+    for (int b0 = 0; b0 < nb; b0 += 256) {
+        const int i = b0 + t;
+        const int v = i < nb ? cnt[i] : 0;
+        s[t] = v;
+        __syncthreads();
+        for (int d = 1; d < 256; d <<= 1) {
+            const int a = t >= d ? s[t - d] : 0;
+            __syncthreads();
+            s[t] += a;
+            __syncthreads();
+        }
+        if (i < nb) cnt[i] = carry + s[t] - v;
+        __syncthreads();
+        if (t == 255) carry += s[255];
+        __syncthreads();
+    }
+    if (t == 0) misc[0] = carry;
+}
+
+// rid[root pixel] = region index (raster order of the roots)
+__global__ __launch_bounds__(256) void iseg_root_id_kernel(const int32_t* __restrict__ L, int px, const int32_t* __restrict__ off,
+                                                           int32_t* __restrict__ rid) {
+    __shared__ int wsum[4];
+    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    int base_id = off[blockIdx.x];
+    for (int k = 0; k < 4; ++k) {
+        const int p = (int)blockIdx.x * ISEG_CHUNK + k * 256 + t;
+        const bool root = p < px && L[p] == p + 1;
+        const u64 m = __ballot(root);
+        if (lane == 0) wsum[wv] = __popcll(m);
+        __syncthreads();
+        int before = 0, tot = 0;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) { before += w < wv ? wsum[w] : 0; tot += wsum[w]; }
+        if (root) rid[p] = base_id + before + __popcll(m & ((1ull << lane) - 1ull));
+        base_id += tot;
+        __syncthreads();
+    }
+}
+
+// acc: per region (area, sum of rows, sum of columns, sum of channel 0) u64; bb: (min row, min col, -max row, -max col),
+// all atomicMin, preset to 0x7f7f7f7f.  misc[1] / misc[2]: largest non-zero segmentation value / 255 - smallest.
+__global__ __launch_bounds__(256) void iseg_region_stats_kernel(int32_t* __restrict__ L, const int32_t* __restrict__ rid,
+                                                                const uint8_t* __restrict__ seg, const uint8_t* __restrict__ img,
+                                                                int H, int W, int img_w, int C, int ch0, int cap,
+                                                                u64* __restrict__ acc, int32_t* __restrict__ bb,
+                                                                int32_t* __restrict__ misc) {
+    __shared__ int s_key[ISEG_SLOTS];
+    __shared__ unsigned s_area[ISEG_SLOTS], s_sv[ISEG_SLOTS];
+    __shared__ u64 s_sr[ISEG_SLOTS], s_sc[ISEG_SLOTS];
+    __shared__ int s_bb[4][ISEG_SLOTS];
+    __shared__ int s_vmax, s_vinv;
+    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    if (t < ISEG_SLOTS) {
+        s_key[t] = -1; s_area[t] = 0; s_sv[t] = 0; s_sr[t] = 0; s_sc[t] = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) s_bb[j][t] = INT_MAX;
+    }
+    if (t == 0) { s_vmax = 0; s_vinv = 0; }
+    __syncthreads();
+    const int xb = (int)blockIdx.x * 64, x = xb + lane;
+    const int ybeg = (int)blockIdx.y * (4 * ISEG_ROWS_PER_WAVE) + wv * ISEG_ROWS_PER_WAVE;
+    int vmax = 0, vinv = 0;
+    for (int r = 0; r < ISEG_ROWS_PER_WAVE; ++r) {
+        const int y = ybeg + r;
+        if (y >= H) break;                                   // wave-uniform
+        int reg = -1, v = 0;
+        if (x < W) {
+            const size_t p = (size_t)y * W + x;
+            const int l = L[p];
+            if (l > 0) {
+                reg = rid[l - 1];
+                L[p] = reg + 1;
+                const int sv = seg[p];
+                vmax = max(vmax, sv);
+                vinv = max(vinv, 255 - sv);
+                v = img[((size_t)y * img_w + x) * C + ch0];
+                if (reg >= cap) reg = -1;                    // counted, not accumulated: the caller's buffer is too small
+            }
+        }
+        u64 active = __ballot(reg >= 0);
+        while (active) {
+            const int leader = __ffsll((long long)active) - 1;
+            const int key = __shfl(reg, leader);
+            const bool mine = reg == key;
+            const u64 m = __ballot(mine);
+            unsigned packed = mine ? ((unsigned)lane << 16) | (unsigned)v : 0u;   // sum of lanes <= 2016, sum of v <= 16320
+#pragma unroll
+            for (int d = 32; d >= 1; d >>= 1) packed += __shfl_xor(packed, d);
+            if (lane == leader) {
+                const unsigned n = (unsigned)__popcll(m);
+                const int xl = xb + leader, xr = xb + 63 - __clzll((long long)m);
+                const u64 sr = (u64)y * n, sc = (u64)xb * n + (packed >> 16);
+                const unsigned sv = packed & 0xffffu;
+                int slot = key & (ISEG_SLOTS - 1), found = -1;
+                for (int probe = 0; probe < ISEG_SLOTS; ++probe) {
+                    const int old = atomicCAS(&s_key[slot], -1, key);
+                    if (old == -1 || old == key) { found = slot; break; }
+                    slot = (slot + 1) & (ISEG_SLOTS - 1);
+                }
+                if (found >= 0) {
+                    atomicAdd(&s_area[found], n); atomicAdd(&s_sr[found], sr); atomicAdd(&s_sc[found], sc); atomicAdd(&s_sv[found], sv);
+                    atomicMin(&s_bb[0][found], y); atomicMin(&s_bb[1][found], xl);
+                    atomicMin(&s_bb[2][found], -y); atomicMin(&s_bb[3][found], -xr);
+                } else {                                     // more than 64 regions in one 64 x 32 tile: straight to the region
+                    u64* a = acc + (size_t)key * 4;
+                    atomicAdd(a + 0, (u64)n); atomicAdd(a + 1, sr); atomicAdd(a + 2, sc); atomicAdd(a + 3, (u64)sv);
+                    int32_t* b = bb + (size_t)key * 4;
+                    atomicMin(b + 0, y); atomicMin(b + 1, xl); atomicMin(b + 2, -y); atomicMin(b + 3, -xr);
+                }
+            }
+            active &= ~m;
+        }
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) { vmax = max(vmax, __shfl_xor(vmax, d)); vinv = max(vinv, __shfl_xor(vinv, d)); }
+    if (lane == 0) { atomicMax(&s_vmax, vmax); atomicMax(&s_vinv, vinv); }
+    __syncthreads();
+    if (t < ISEG_SLOTS && s_key[t] >= 0) {
+        const int k = s_key[t];
+        u64* a = acc + (size_t)k * 4;
+        atomicAdd(a + 0, (u64)s_area[t]); atomicAdd(a + 1, s_sr[t]); atomicAdd(a + 2, s_sc[t]); atomicAdd(a + 3, (u64)s_sv[t]);
+        int32_t* b = bb + (size_t)k * 4;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) atomicMin(b + j, s_bb[j][t]);
+    }
+    if (t == 0) {
+        if (s_vmax) atomicMax(misc + 1, s_vmax);
+        if (s_vmax) atomicMax(misc + 2, s_vinv);
+    }
+}
+
+// rec (n, 8) int64: area, min row, min col, max row + 1, max col + 1, sum of rows, sum of columns, sum of channel 0
+__global__ __launch_bounds__(256) void iseg_finalize_kernel(const u64* __restrict__ acc, const int32_t* __restrict__ bb,
+                                                            const int32_t* __restrict__ misc, int cap, int64_t* __restrict__ rec) {
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= cap || r >= misc[0]) return;
+    const u64* a = acc + (size_t)r * 4;
+    const int32_t* b = bb + (size_t)r * 4;
+    int64_t* o = rec + (size_t)r * 8;
+    o[0] = (int64_t)a[0]; o[1] = b[0]; o[2] = b[1]; o[3] = 1 - (int64_t)b[2]; o[4] = 1 - (int64_t)b[3];
+    o[5] = (int64_t)a[1]; o[6] = (int64_t)a[2]; o[7] = (int64_t)a[3];
+}
+
+hipError_t run_nuclei_regions(const uint8_t* seg, const uint8_t* img, int H, int W, int img_w, int C, int ch0, int32_t* labels,
+                              const RegionBufs& b, hipStream_t s) {
+    const int px = H * W;
+    const int nb = (px + ISEG_CHUNK - 1) / ISEG_CHUNK;
+    hipError_t e;
+    if ((e = hipMemsetAsync(b.misc, 0, 4 * sizeof(int32_t), s)) != hipSuccess) return e;
+    if (b.cap > 0 && (e = hipMemsetAsync(b.acc, 0, (size_t)b.cap * 4 * sizeof(u64), s)) != hipSuccess) return e;
+    if (b.cap > 0 && (e = hipMemsetAsync(b.bb, 0x7f, (size_t)b.cap * 4 * sizeof(int32_t), s)) != hipSuccess) return e;
+    hipLaunchKernelGGL(iseg_root_count_kernel, dim3(nb), dim3(256), 0, s, labels, px, b.blk);
+    hipLaunchKernelGGL(iseg_scan_kernel, dim3(1), dim3(256), 0, s, b.blk, nb, b.misc);
+    hipLaunchKernelGGL(iseg_root_id_kernel, dim3(nb), dim3(256), 0, s, labels, px, b.blk, b.rid);
+    const dim3 g((W + 63) / 64, (H + 4 * ISEG_ROWS_PER_WAVE - 1) / (4 * ISEG_ROWS_PER_WAVE));
+    hipLaunchKernelGGL(iseg_region_stats_kernel, g, dim3(256), 0, s, labels, b.rid, seg, img, H, W, img_w, C, ch0, b.cap, b.acc,
+                       b.bb, b.misc);
+    if (b.cap > 0)
+        hipLaunchKernelGGL(iseg_finalize_kernel, dim3((b.cap + 255) / 256), dim3(256), 0, s, b.acc, b.bb, b.misc, b.cap, b.rec);
+    return hipGetLastError();
+}
+
+__device__ __forceinline__ int iseg_reflect(int c, int n) {   // c in [-1, n]
+    if (n == 1) return 0;
+    return c < 0 ? -c : (c >= n ? 2 * (n - 1) - c : c);
+}
+
+// one block = 16 output rows of one crop, thread = output column; out (n, 256, 256, 3); chmax (n, 3) preset to 0
+__global__ __launch_bounds__(256) void iseg_crops_kernel(const int32_t* __restrict__ L, const uint8_t* __restrict__ img, int W,
+                                                         int img_w, int C, const int32_t* __restrict__ desc, int c0, int c1, int c2,
+                                                         uint8_t* __restrict__ out, int32_t* __restrict__ chmax) {
+    const int n = blockIdx.x / (256 / ISEG_CROP_ROWS), rb = blockIdx.x % (256 / ISEG_CROP_ROWS);
+    const int32_t* d = desc + (size_t)n * 5;
+    const int label = d[0] + 1, y0 = d[1], x0 = d[2], h = d[3], w = d[4];
+    const int j = threadIdx.x;
+    const int cq = w * (2 * j + 1) - 256;                    // sample column * 512, > -512
+    const int ca = (cq + 512) / 512 - 1, fc = cq - ca * 512;
+    const int xa = x0 + iseg_reflect(ca, w), xb = x0 + iseg_reflect(ca + 1, w);
+    int m0 = 0, m1 = 0, m2 = 0;
+    for (int ii = 0; ii < ISEG_CROP_ROWS; ++ii) {
+        const int i = rb * ISEG_CROP_ROWS + ii;
+        const int rq = h * (2 * i + 1) - 256;
+        const int ra = (rq + 512) / 512 - 1, fr = rq - ra * 512;
+        const int ya = y0 + iseg_reflect(ra, h), yb = y0 + iseg_reflect(ra + 1, h);
+        const int ys[2] = {ya, yb}, xs[2] = {xa, xb};
+        const int wy[2] = {512 - fr, fr}, wx[2] = {512 - fc, fc};
+        int v0 = 0, v1 = 0, v2 = 0;
+#pragma unroll
+        for (int a = 0; a < 2; ++a) {
+#pragma unroll
+            for (int b = 0; b < 2; ++b) {
+                const size_t p = (size_t)ys[a] * W + xs[b];
+                if (L[p] != label) continue;
+                const uint8_t* q = img + ((size_t)ys[a] * img_w + xs[b]) * C;
+                const int wgt = wy[a] * wx[b];
+                v0 += wgt * q[c0]; v1 += wgt * q[c1]; v2 += wgt * q[c2];
+            }
+        }
+        v0 >>= 18; v1 >>= 18; v2 >>= 18;
+        uint8_t* o = out + (((size_t)n * 256 + i) * 256 + j) * 3;
+        o[0] = (uint8_t)v0; o[1] = (uint8_t)v1; o[2] = (uint8_t)v2;
+        m0 = max(m0, v0); m1 = max(m1, v1); m2 = max(m2, v2);
+    }
+#pragma unroll
+    for (int dd = 32; dd >= 1; dd >>= 1) {
+        m0 = max(m0, __shfl_xor(m0, dd)); m1 = max(m1, __shfl_xor(m1, dd)); m2 = max(m2, __shfl_xor(m2, dd));
+    }
+    if ((j & 63) == 0) {
+        if (m0) atomicMax(chmax + (size_t)n * 3 + 0, m0);
+        if (m1) atomicMax(chmax + (size_t)n * 3 + 1, m1);
+        if (m2) atomicMax(chmax + (size_t)n * 3 + 2, m2);
+    }
+}
+
+hipError_t run_nucleus_crops(const int32_t* labels, const uint8_t* img, int W, int img_w, int C, const int32_t* desc, int n,
+                             const int order[3], uint8_t* out, int32_t* chmax, hipStream_t s) {
+    if (n <= 0) return hipSuccess;
+    hipError_t e = hipMemsetAsync(chmax, 0, (size_t)n * 3 * sizeof(int32_t), s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(iseg_crops_kernel, dim3((unsigned)n * (256 / ISEG_CROP_ROWS)), dim3(256), 0, s, labels, img, W, img_w, C, desc,
+                       order[0], order[1], order[2], out, chmax);
+    return hipGetLastError();
+}
+
+}  // namespace ecseg

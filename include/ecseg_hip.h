@@ -40,6 +40,7 @@ extern "C" {
 /* (round 6, still 5 - additions a round-5 caller never triggers: option "winograd" = 3 and "wino4_rowpass"; ecseg_get_conv_launch_profile kinds 5 / 6
  * (the split kernels); CONV ops read their so far unused `mode` word as the horizontal stride / dilation rate (0 = as before); CONVT kernels larger than
  * their stride run phase by phase.) */
+/* (still 5 - additive: ecseg_nuclei_regions and ecseg_nucleus_crops, the file-level interSeg driver; nothing existing changed.) */
 #define ECSEG_ABI_VERSION 5
 
 #define ECSEG_OK             0
@@ -272,6 +273,30 @@ int ecseg_count_hsr(ecseg_ctx* h, const uint8_t* chrom, const uint8_t* fish, int
  *   [9]    coloc(ec, red' & green')   [10] HSR(red)   [11] HSR(green)          (x' = x & ~nuclei) */
 int ecseg_overlay(ecseg_ctx* h, const uint8_t* labels, const uint8_t* rgb, int n_img, int H, int W, int C,
                   int sensitivity, int hsr_size_threshold, int64_t* out);
+
+/* ---- interSeg: nuclei and their crops (src/interseg.py:113-235, im2patches_overlap :27-46) --------------------------- */
+/* Replaces measure.label(seg, connectivity=None) + measure.regionprops + the brightness gate (src/interseg.py:121-134) for
+ * ONE image.  seg: (H, W) uint8 nucleus mask (what stat_fish writes as annotated/<name>/<name>_segmentation.tif, 0 / 255);
+ * img: (img_h, img_w, C) uint8 with img_h >= H, img_w >= W - only I[:H, :W] is read (src/interseg.py:116-117).
+ * Regions are the 8-connected components of seg != 0 in skimage's order (raster order of their first pixel); a seg holding
+ * two different non-zero values (an instance-id map, which skimage would label by value) is refused with ECSEG_E_INVALID.
+ * *n_regions = the number of regions; records (capacity x 8 int64) receive, when n_regions <= capacity, per region:
+ *   [0] area  [1] min row  [2] min col  [3] max row + 1  [4] max col + 1   (regionprops' area and bbox)
+ *   [5] sum of rows  [6] sum of columns  (centroid = sum / area; nucleus_center = floor of both)
+ *   [7] sum of channel `channel0` of img inside the region (the gate of :134 is 4 * [7] < 51 * [0]).
+ * When n_regions > capacity nothing is written: call again with a buffer of n_regions records.  The region label map and
+ * I[:H] stay on the handle for ecseg_nucleus_crops until the next ecseg_nuclei_regions call. */
+int ecseg_nuclei_regions(ecseg_ctx* h, const uint8_t* seg, int H, int W, const uint8_t* img, int img_h, int img_w, int C,
+                         int channel0, int capacity, int64_t* records, int32_t* n_regions);
+/* The crops of src/interseg.py:131-133,150-152 (whole bbox) and :190-194 / :27-46 (256-stride tiles of a larger bbox):
+ * crops: n_crops x (region, y0, x0, h, w) int32, 1 <= h, w <= 256, inside the last ecseg_nuclei_regions image.  Crop k =
+ * the window with every pixel outside region `region` zeroed, channels channel_order[0..2] of img (the (fish, 1 - fish, 2)
+ * reorder of :119), resized to 256 x 256 like resize(.., (256, 256), preserve_range=True).astype('uint8') with the exact
+ * affine map (scale h / 256; bilinear, 'reflect' inside the window; integer arithmetic, truncated).
+ * out: (n_crops, 256, 256, 3) uint8; channel_max: (n_crops, 3) int32, the maximum of every output channel (the empty-tile
+ * test of :199 and the centromere gate of :160). */
+int ecseg_nucleus_crops(ecseg_ctx* h, const int32_t* crops, int n_crops, const int32_t* channel_order, uint8_t* out,
+                        int32_t* channel_max);
 
 /* ---- per-stage device timings of the last segment call (milliseconds, HIP events on the handle's stream) -- */
 /* ECSEG_T_COUNT: device time of the kernels of the last ecseg_overlay / ecseg_preprocess / ecseg_count_* call (inputs

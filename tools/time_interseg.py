@@ -1,0 +1,136 @@
+"""Throughput of the interSeg file-level driver (``make interseg``) on synthetic FISH images.
+
+    python tools/time_interseg.py [--images 16] [--nuclei 40] [--height 1040] [--width 1392] [--cpu-workers 16]
+
+Device side: per image ``Handle.nuclei_regions`` + ``Handle.nucleus_crops`` (regions + crops), the two classifiers
+(tests/golden/interseg_synth.h5 and ecseg_c_synth.h5, batched) and the host work around them (region rows, decisions).
+For comparison it restates the reference's per-nucleus loop (src/interseg.py:121-152) in numpy - a full-image mask and a
+full-image multiply per nucleus, then the crop and a bilinear resize - over the same images on a pool of CPU processes;
+the classifiers are not part of that restatement.  Prints one JSON line.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+from concurrent.futures import ProcessPoolExecutor
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def synth_image(seed, H, W, n_nuclei):
+    rng = np.random.default_rng(seed)
+    yy, xx = np.ogrid[:H, :W]
+    seg = np.zeros((H, W), np.uint8)
+    for k in range(n_nuclei):
+        ry, rx = (int(rng.integers(140, 200)),) * 2 if k == 0 else (int(rng.integers(15, 60)), int(rng.integers(15, 60)))
+        cy, cx = int(rng.integers(ry, H - ry)), int(rng.integers(rx, W - rx))
+        seg[((yy - cy) / ry) ** 2 + ((xx - cx) / rx) ** 2 <= 1.0] = 255
+    img = rng.integers(0, 60, (H, W, 3), dtype=np.uint8)
+    img[seg != 0] += rng.integers(0, 120, (int((seg != 0).sum()), 3), dtype=np.uint8)
+    return seg, img
+
+
+def _resize_bilinear(win):
+    """skimage's order-1 'reflect' resize to 256 x 256 restated in numpy float64 (exact affine parameters)."""
+    h, w = win.shape[:2]
+    i = np.arange(256)
+
+    def taps(n):
+        r = (i + 0.5) * n / 256.0 - 0.5
+        a = np.floor(r).astype(int)
+        f = r - a
+        refl = (lambda c: np.zeros_like(c)) if n == 1 else (lambda c: np.where(c < 0, -c, np.where(c >= n, 2 * (n - 1) - c, c)))
+        return refl(a), refl(a + 1), f
+    r0, r1, fr = taps(h)
+    c0, c1, fc = taps(w)
+    a = win.astype(np.float64)
+    top = a[r0][:, c0] * (1 - fc)[None, :, None] + a[r0][:, c1] * fc[None, :, None]
+    bot = a[r1][:, c0] * (1 - fc)[None, :, None] + a[r1][:, c1] * fc[None, :, None]
+    return (top * (1 - fr)[:, None, None] + bot * fr[:, None, None]).astype(np.uint8)
+
+
+def cpu_reference_loop(args):
+    """src/interseg.py:121-152,190-194 per image, numpy: the reference's O(nuclei x H x W) mask-and-multiply per nucleus."""
+    from scipy import ndimage as ndi
+
+    from ecseg_amd.interseg import crop_windows
+    seg, img = synth_image(*args)
+    lab, n = ndi.label(seg != 0, structure=np.ones((3, 3), int))
+    crops = 0
+    for r in range(1, n + 1):
+        mask = lab == r
+        temp = img * mask[..., None]
+        if temp[..., 0].sum() / mask.sum() < 12.75:
+            continue
+        ys, xs = np.nonzero(mask)
+        y0, x0, y1, x1 = ys.min(), xs.min(), ys.max() + 1, xs.max() + 1
+        for dy, dx, th, tw in crop_windows(y1 - y0, x1 - x0):
+            _resize_bilinear(temp[y0 + dy:y0 + dy + th, x0 + dx:x0 + dx + tw])
+            crops += 1
+    return crops
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--images', type=int, default=16)
+    ap.add_argument('--nuclei', type=int, default=40)
+    ap.add_argument('--height', type=int, default=1040)
+    ap.add_argument('--width', type=int, default=1392)
+    ap.add_argument('--cpu-workers', type=int, default=16)
+    ap.add_argument('--no-cpu', action='store_true')
+    a = ap.parse_args()
+    from ecseg_amd import hdf5_min, interseg
+    from ecseg_amd.model import MetasegModel
+    g = os.path.join(ROOT, 'tests', 'golden')
+    mi = MetasegModel(*hdf5_min.load_keras_h5(os.path.join(g, 'interseg_synth.h5')))
+    mc = MetasegModel(*hdf5_min.load_keras_h5(os.path.join(g, 'ecseg_c_synth.h5')))
+    h = mi.handle
+    jobs = [(1000 + k, a.height, a.width, a.nuclei) for k in range(a.images)]
+    data = [synth_image(*j) for j in jobs]
+    # warm-up: buffers, plans
+    seg, img = data[0]
+    rec = h.nuclei_regions(seg, img, 0)
+    _, _, desc, tiled, _ = interseg.region_rows(rec)
+    crops, cmax = h.nucleus_crops(desc)
+    interseg.classify_crops(mi, crops[:8], mc, True, from_patches=tiled[:8], channel_max=cmax[:8])
+    t = {'regions_crops': 0.0, 'classifiers': 0.0, 'host': 0.0}
+    n_crops = n_nuclei = 0
+    t_all = time.perf_counter()
+    for seg, img in data:
+        t0 = time.perf_counter()
+        rec = h.nuclei_regions(seg, img, 0)
+        t1 = time.perf_counter()
+        centers, low, desc, tiled, owner = interseg.region_rows(rec)
+        t2 = time.perf_counter()
+        crops, cmax = h.nucleus_crops(desc, (0, 1, 2))
+        t3 = time.perf_counter()
+        rows = []
+        for b0 in range(0, len(desc), interseg.CROP_BATCH):
+            sl = slice(b0, b0 + interseg.CROP_BATCH)
+            rows += interseg.classify_crops(mi, crops[sl], mc, True, from_patches=tiled[sl], channel_max=cmax[sl])
+        t4 = time.perf_counter()
+        t['regions_crops'] += (t1 - t0) + (t3 - t2)
+        t['host'] += t2 - t1
+        t['classifiers'] += t4 - t3
+        n_crops += len(desc)
+        n_nuclei += len(rec)
+    wall = time.perf_counter() - t_all
+    out = {'images': a.images, 'shape': [a.height, a.width], 'nuclei': n_nuclei, 'crops': n_crops,
+           'images_per_s': a.images / wall, 'seconds': {k: round(v, 4) for k, v in t.items()},
+           'ms_per_image': {k: round(1e3 * v / a.images, 3) for k, v in t.items()}}
+    if not a.no_cpu:
+        t0 = time.perf_counter()
+        with ProcessPoolExecutor(a.cpu_workers) as ex:
+            cpu_crops = sum(ex.map(cpu_reference_loop, jobs))
+        cw = time.perf_counter() - t0
+        out['cpu_restatement'] = {'workers': a.cpu_workers, 'images_per_s': a.images / cw, 'crops': cpu_crops,
+                                  'ms_per_nucleus_single_core': round(1e3 * cw * a.cpu_workers / max(n_nuclei, 1), 3)}
+    print(json.dumps(out))
+
+
+if __name__ == '__main__':
+    main()
