@@ -15,4 +15,7 @@ Parity status (see DESIGN.md "Oracle pinning"):
   Keras forward pass (TensorFlow 2.8): PARITY UNPINNED - OpenCV and TensorFlow are third-party wheels
   that are not vendored in the reference and not installed here; their published algorithms are
   restated and anchored on the reference's call sites (src/image_tools.py:86-101, src/utils.py:115).
+* interSeg region records and nucleus crops (``interseg.py``): PINNED - against scikit-image 0.18.3
+  fixtures (``tools/make_golden_interseg.py``, ``tests/test_interseg_driver.py``); exact integers, so skimage's
+  k - 1 at exact-integer pixels is the one documented difference.
 """

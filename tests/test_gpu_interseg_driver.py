@@ -14,31 +14,12 @@ from PIL import Image
 
 from ecseg_amd import hdf5_min, image_io, interseg
 from oracle import unet as oracle_unet
+from oracle.interseg import exact_resize
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SCENES = ['interseg_scene_small.npz', 'interseg_scene_large.npz']
 MARGIN = 1e-3
-
-
-def _exact_integer(win):
-    """Pixels of the 256 x 256 bilinear of an (h, w, 3) window whose exact value is an integer (multiple of 2^18 in units of
-    2^-18; the integer form of csrc/interseg_kernels.hip)."""
-    h, w = win.shape[:2]
-    i = np.arange(256)
-
-    def taps(n):
-        q = n * (2 * i + 1) - 256
-        a = (q + 512) // 512 - 1
-        refl = (lambda c: np.zeros_like(c)) if n == 1 else (lambda c: np.where(c < 0, -c, np.where(c >= n, 2 * (n - 1) - c, c)))
-        return refl(a), refl(a + 1), q - a * 512
-    r0, r1, fr = taps(h)
-    c0, c1, fc = taps(w)
-    a = win.astype(np.int64)
-    wy0, wy1 = (512 - fr)[:, None, None], fr[:, None, None]
-    wx0, wx1 = (512 - fc)[None, :, None], fc[None, :, None]
-    v = wy0 * (wx0 * a[r0][:, c0] + wx1 * a[r0][:, c1]) + wy1 * (wx0 * a[r1][:, c0] + wx1 * a[r1][:, c1])
-    return (v & (2 ** 18 - 1)) == 0
 
 
 @pytest.mark.parametrize('scene', SCENES)
@@ -87,7 +68,7 @@ def test_crops_match_skimage_resize(gpu, golden_dir, scene):
         assert crops.shape == (len(win), 256, 256, 3)
         km1 = 0
         for k, (r, y0, x0, h, w, _) in enumerate(win):
-            exact = _exact_integer(img[y0:y0 + h, x0:x0 + w] * (lab[y0:y0 + h, x0:x0 + w] == r + 1)[..., None])[..., list(order)]
+            exact = exact_resize(img[y0:y0 + h, x0:x0 + w] * (lab[y0:y0 + h, x0:x0 + w] == r + 1)[..., None])[1][..., list(order)]
             d = crops[k].astype(int) - z['crops'][k][..., list(order)]
             assert np.all((d == 0) | ((d == 1) & exact)), (scene, k, int((d != 0).sum()))
             km1 += int((d == 1).sum())

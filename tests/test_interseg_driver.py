@@ -1,7 +1,8 @@
 """`make interseg` without a GPU: the host half of the file-level driver (src/interseg.py:48-258) against fixtures written by
 skimage 0.18.3 / scipy / pandas (tools/make_golden_interseg.py) - crop windows and tiling, centroid strings and the
-brightness gate from region records, the centromeric quality score, the config and exit-code paths - and a numpy
-restatement of the integer bilinear the crops kernel computes (csrc/interseg_kernels.hip) against skimage's resize."""
+brightness gate from region records, the centromeric quality score, the config and exit-code paths - and the CPU
+reference of the region and crop kernels (oracle/interseg.py, csrc/interseg_kernels.hip) against skimage's regionprops and
+resize."""
 import json
 import os
 import re
@@ -12,6 +13,8 @@ import yaml
 from scipy import ndimage as ndi
 
 from ecseg_amd import interseg
+from oracle import interseg as oracle_interseg
+from oracle.interseg import exact_resize
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SCENES = ['interseg_scene_small.npz', 'interseg_scene_large.npz']
@@ -28,28 +31,6 @@ def region_records(seg, img, channel0):
         ys, xs = yy[m], xx[m]
         out[k] = [m.sum(), ys.min(), xs.min(), ys.max() + 1, xs.max() + 1, ys.sum(), xs.sum(), int(img[:H, :W, channel0][m].sum())]
     return out, lab
-
-
-def exact_resize(win):
-    """(h, w, 3) uint8 window, h, w <= 256 -> the 256 x 256 bilinear of the exact affine map in integers, and the mask of
-    the pixels whose value is an exact integer (value * 2^18 divisible by 2^18)."""
-    h, w = win.shape[:2]
-    i = np.arange(256)
-
-    def taps(n):
-        q = n * (2 * i + 1) - 256
-        a = (q + 512) // 512 - 1
-        f = q - a * 512
-        refl = (lambda c: np.zeros_like(c)) if n == 1 else (lambda c: np.where(c < 0, -c, np.where(c >= n, 2 * (n - 1) - c, c)))
-        return refl(a), refl(a + 1), f
-    r0, r1, fr = taps(h)
-    c0, c1, fc = taps(w)
-    a = win.astype(np.int64)
-    wy0, wy1 = (512 - fr)[:, None, None], fr[:, None, None]
-    wx0, wx1 = (512 - fc)[None, :, None], fc[None, :, None]
-    v = wy0 * (wx0 * a[r0][:, c0] + wx1 * a[r0][:, c1]) + wy1 * (wx0 * a[r1][:, c0] + wx1 * a[r1][:, c1])
-    assert v.max() < 2 ** 31
-    return (v >> 18).astype(np.uint8), (v & (2 ** 18 - 1)) == 0
 
 
 @pytest.mark.parametrize('shape,want', [
@@ -102,6 +83,46 @@ def test_integer_bilinear_equals_skimage_resize_but_for_exact_integers(golden_di
         assert np.all((d == 0) | ((d == 1) & exact)), (scene, k)
         km1 += int(((d == 1) & exact).sum())
     print('%s: %d pixels where skimage holds k - 1 for an exact integer k' % (scene, km1))
+
+
+@pytest.mark.parametrize('scene', SCENES)
+def test_oracle_matches_the_skimage_fixture(golden_dir, scene):
+    # oracle/interseg.py is the reference of the GPU kernel tests (tests/test_gpu_interseg_kernels.py): pin it to skimage
+    z = np.load(os.path.join(golden_dir, scene))
+    seg, img, want = z['seg'], z['image'], z['records']
+    for ch in (0, 1):
+        rec, lab = oracle_interseg.region_records(seg, img, ch)
+        assert rec.dtype == np.int64 and rec.shape == (len(want), 8)
+        assert np.array_equal(rec[:, :5], want[:, :5]) and np.array_equal(rec[:, 7], want[:, 5 + ch])
+        assert np.array_equal(rec, region_records(seg, img, ch)[0]) and np.array_equal(lab, region_records(seg, img, ch)[1])
+    assert interseg.region_rows(rec)[0] == [str(c) for c in z['centers']]    # centroids: the sums of rows and columns
+    for order in ((0, 1, 2), (1, 0, 2)):
+        for k, (r, y0, x0, h, w, _) in enumerate(z['windows']):
+            got = oracle_interseg.nucleus_crop(img, lab, r, y0, x0, h, w, order)
+            exact = exact_resize(img[y0:y0 + h, x0:x0 + w] * (lab[y0:y0 + h, x0:x0 + w] == r + 1)[..., None])[1][..., list(order)]
+            d = got.astype(int) - z['crops'][k][..., list(order)]
+            assert got.shape == (256, 256, 3) and np.all((d == 0) | ((d == 1) & exact)), (scene, order, k)
+
+
+@pytest.mark.parametrize('seed', range(20))
+def test_oracle_region_records_equal_the_loop_restatement(seed):
+    rng = np.random.default_rng(7000 + seed)
+    H, W = int(rng.integers(1, 70)), int(rng.integers(1, 90))
+    seg = (rng.random((H, W)) < rng.choice([0.05, 0.3, 0.5, 0.8])).astype(np.uint8) * int(rng.integers(1, 256))
+    C = int(rng.integers(1, 5))
+    img = rng.integers(0, 256, (H + int(rng.integers(0, 3)), W + int(rng.integers(0, 3)), C), dtype=np.uint8)
+    ch = int(rng.integers(0, C))
+    rec, lab = oracle_interseg.region_records(seg, img, ch)
+    want, want_lab = region_records(seg, img, ch)
+    assert np.array_equal(rec, want) and np.array_equal(lab, want_lab)
+    if len(rec):                                                                 # crops: any window, any channel order
+        r = int(rng.integers(0, len(rec)))
+        h, w = int(rng.integers(1, H + 1)), int(rng.integers(1, W + 1))
+        y0, x0 = int(rng.integers(0, H - h + 1)), int(rng.integers(0, W - w + 1))
+        order = [int(c) for c in rng.integers(0, C, 3)]
+        got = oracle_interseg.nucleus_crop(img, lab, r, y0, x0, h, w, order)
+        win = np.stack([img[y0:y0 + h, x0:x0 + w, c] for c in order], -1) * (lab[y0:y0 + h, x0:x0 + w] == r + 1)[..., None]
+        assert np.array_equal(got, exact_resize(win)[0])
 
 
 def _score_cases(golden_dir):
