@@ -16,7 +16,7 @@ EXPORTS = [
     'ecseg_segment_images', 'ecseg_segment_images_ex', 'ecseg_segment_images_dev', 'ecseg_set_images_per_group', 'ecseg_set_option', 'ecseg_preprocess', 'ecseg_u16_to_u8',
     'ecseg_meta_segment', 'ecseg_prefetch_input', 'ecseg_host_alloc', 'ecseg_host_free',
     'ecseg_stitch_argmax', 'ecseg_meta_inference', 'ecseg_meta_inference_dev', 'ecseg_count_cc', 'ecseg_ccl_labels',
-    'ecseg_count_colocalization', 'ecseg_count_hsr', 'ecseg_overlay', 'ecseg_nuclei_regions', 'ecseg_nucleus_crops', 'ecseg_get_timings',
+    'ecseg_count_colocalization', 'ecseg_count_hsr', 'ecseg_overlay', 'ecseg_nuclei_regions', 'ecseg_nucleus_crops', 'ecseg_fish_distances', 'ecseg_get_timings',
     'ecseg_set_kernel_profiling', 'ecseg_get_conv_profile', 'ecseg_get_conv_executed_flops', 'ecseg_get_conv_launch_profile', 'ecseg_debug_peek', 'ecseg_lzw_decode', 'ecseg_lzw_encode',
     'ecseg_comm_unique_id', 'ecseg_comm_create', 'ecseg_comm_destroy', 'ecseg_comm_last_error', 'ecseg_allgather_records', 'ecseg_allgather_records_dev',
     'ecseg_npy_write_i64', 'ecseg_png_write_labels', 'ecseg_png_write', 'ecseg_png_write_channel', 'ecseg_npy_label_info', 'ecseg_npy_read_labels_u8', 'ecseg_tiff_write_gray8', 'ecseg_tiff_info', 'ecseg_tiff_read',
@@ -97,6 +97,7 @@ def load_library():
     lib.ecseg_overlay.argtypes = [vp, u8p, u8p, i32, i32, i32, i32, i32, i32, vp]
     lib.ecseg_nuclei_regions.argtypes = [vp, u8p, i32, i32, u8p, i32, i32, i32, i32, i32, vp, C.POINTER(C.c_int32)]
     lib.ecseg_nucleus_crops.argtypes = [vp, vp, i32, vp, vp, vp]
+    lib.ecseg_fish_distances.argtypes = [vp, vp, i32, i32, u8p, i32, i32, i32, i32, vp, C.POINTER(C.c_int32)]
     lib.ecseg_get_timings.argtypes = [vp, vp]
     lib.ecseg_set_kernel_profiling.argtypes = [vp, i32]
     lib.ecseg_get_conv_profile.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double)]
@@ -453,6 +454,30 @@ class Handle:
         mx = np.zeros((len(d), 3), np.int32)
         self._check(self.lib.ecseg_nucleus_crops(self.h, _ptr(d), len(d), _ptr(order), _ptr(out), _ptr(mx)), 'ecseg_nucleus_crops')
         return out, mx
+
+    # ---- fish_distance_calculation -----------------------------------------------------------------------
+    def fish_distances(self, labels, lsq, fish_channel, centromere_channel, capacity=4096):
+        """(H, W) int32 instance labels (<= 0 background) + (H, W, C >= 2) uint8 lsq image -> int64 (n_cells, 8) records in
+        ascending label order (ecseg_fish_distances): label, area, gate bits, FISH pixels, centromere pixels, FISH components,
+        min squared FISH - centromere distance (-1: a set is empty), 0."""
+        lab = np.ascontiguousarray(labels)
+        if lab.dtype != np.int32:
+            if lab.dtype.kind not in 'iu' or (lab.size and (int(lab.max()) > 2 ** 31 - 1 or int(lab.min()) < -2 ** 31)):
+                raise ValueError('fish_distances takes integer labels that fit int32')
+            lab = lab.astype(np.int32)
+        im = _u8(lsq)
+        if lab.ndim != 2 or im.ndim != 3 or im.shape[:2] != lab.shape:
+            raise ValueError('fish_distances takes a (H, W) label map and an (H, W, C) image of the same extent')
+        H, W = lab.shape
+        n = C.c_int32()
+        cap = int(capacity)
+        while True:
+            rec = np.empty((max(cap, 1), 8), np.int64)
+            self._check(self.lib.ecseg_fish_distances(self.h, _ptr(lab), H, W, _ptr(im), im.shape[2], int(fish_channel),
+                                                      int(centromere_channel), cap, _ptr(rec), C.byref(n)), 'ecseg_fish_distances')
+            if n.value <= cap:
+                return rec[:n.value]
+            cap = n.value
 
     # ---- timing ---------------------------------------------------------------------------------------
     def timings(self):

@@ -130,6 +130,22 @@ struct ecseg_ctx {
     uint8_t* d_iseg_crops = nullptr; size_t d_iseg_crops_cap = 0;
     int32_t* d_iseg_max = nullptr; size_t d_iseg_max_cap = 0;
     int iseg_H = 0, iseg_W = 0, iseg_img_w = 0, iseg_C = 0, iseg_n = -1;   // iseg_n < 0: no region map on the handle
+    // ecseg_fish_distances: buffers of its own (a region map left by ecseg_nuclei_regions stays valid)
+    int32_t* d_fd_lab = nullptr; size_t d_fd_lab_cap = 0;
+    uint8_t* d_fd_lsq = nullptr; size_t d_fd_lsq_cap = 0;
+    int32_t* d_fd_rid = nullptr; size_t d_fd_rid_cap = 0;
+    int32_t* d_fd_par = nullptr; size_t d_fd_par_cap = 0;
+    int32_t* d_fd_blk = nullptr; size_t d_fd_blk_cap = 0;
+    int32_t* d_fd_misc = nullptr; size_t d_fd_misc_cap = 0;
+    int2* d_fd_flist = nullptr; size_t d_fd_flist_cap = 0;
+    int2* d_fd_clist = nullptr; size_t d_fd_clist_cap = 0;
+    unsigned* d_fd_acc = nullptr; size_t d_fd_acc_cap = 0;
+    int32_t* d_fd_val = nullptr; size_t d_fd_val_cap = 0;
+    int32_t* d_fd_off = nullptr; size_t d_fd_off_cap = 0;
+    int32_t* d_fd_cur = nullptr; size_t d_fd_cur_cap = 0;
+    int64_t* d_fd_rec = nullptr; size_t d_fd_rec_cap = 0;
+    unsigned long long* d_fd_pbest = nullptr; size_t d_fd_pbest_cap = 0;
+    int32_t* d_fd_proots = nullptr; size_t d_fd_proots_cap = 0;
     // meta_inference is ~60 short dependent kernels: captured once per (buffers, geometry) into a HIP graph and replayed
     struct PostGraph { uint8_t* img; int32_t* nec; int n, H, W; hipStream_t s; hipGraphExec_t exec; unsigned long long stamp; };
     std::vector<PostGraph> post_graphs;
@@ -1175,6 +1191,9 @@ void ecseg_destroy(ecseg_ctx* h) {
     void* iseg[] = {h->d_iseg_lab, h->d_iseg_img, h->d_iseg_rid, h->d_iseg_blk, h->d_iseg_misc, h->d_iseg_acc, h->d_iseg_bb, h->d_iseg_rec,
                     h->d_iseg_desc, h->d_iseg_crops, h->d_iseg_max};
     for (void* p : iseg) if (p) (void)hipFree(p);
+    void* fd[] = {h->d_fd_lab, h->d_fd_lsq, h->d_fd_rid, h->d_fd_par, h->d_fd_blk, h->d_fd_misc, h->d_fd_flist, h->d_fd_clist, h->d_fd_acc,
+                  h->d_fd_val, h->d_fd_off, h->d_fd_cur, h->d_fd_rec, h->d_fd_pbest, h->d_fd_proots};
+    for (void* p : fd) if (p) (void)hipFree(p);
     for (auto& ev : h->ev) if (ev) (void)hipEventDestroy(ev);
     if (h->ev_block) (void)hipEventDestroy(h->ev_block);
     if (h->stream_in) { (void)hipStreamSynchronize(h->stream_in); (void)hipStreamDestroy(h->stream_in); }
@@ -2076,6 +2095,69 @@ int ecseg_nucleus_crops(ecseg_ctx* h, const int32_t* crops, int n_crops, const i
         HIP_TRY(h, hipStreamSynchronize(s));
         h->stage_ms[ECSEG_T_COUNT] += stage_elapsed(h->ev[0], h->ev[1]);
     }
+    return ECSEG_OK;
+}
+
+// ---- fish_distance_calculation (src/fish_distance_calculation.py:16-46) ---------------------------------------------------
+int ecseg_fish_distances(ecseg_ctx* h, const int32_t* labels, int H, int W, const uint8_t* lsq, int C, int fish_channel,
+                         int centromere_channel, int capacity, int64_t* records, int32_t* n_cells) {
+    if (!h) return ECSEG_E_INVALID;
+    drop_sent_ahead(h);
+    if (n_cells) *n_cells = 0;
+    if (!labels || !lsq || !n_cells || H <= 0 || W <= 0 || capacity < 0 || (capacity > 0 && !records))
+        return fail(h, ECSEG_E_INVALID, "fish_distances: bad arguments");
+    if (C < 2) return fail(h, ECSEG_E_INVALID, "fish_distances: the lsq image needs at least 2 channels (the gate reads channels 0 and 1)");
+    if (fish_channel < 0 || fish_channel >= C || centromere_channel < 0 || centromere_channel >= C)
+        return fail(h, ECSEG_E_INVALID, "fish_distances: channel out of range (the lsq image has " + std::to_string(C) + " channels)");
+    if ((long long)H * W >= (1ll << 31) || (long long)H * W * C >= (1ll << 40))
+        return fail(h, ECSEG_E_INVALID, "fish_distances: image too large (H * W must be below 2^31, H * W * C below 2^40)");
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t px = (size_t)H * W;
+    int rc;
+    if ((rc = ensure(h, h->d_fd_lab, h->d_fd_lab_cap, px))) return rc;
+    if ((rc = ensure(h, h->d_fd_lsq, h->d_fd_lsq_cap, px * C))) return rc;
+    if ((rc = ensure(h, h->d_fd_rid, h->d_fd_rid_cap, px))) return rc;
+    if ((rc = ensure(h, h->d_fd_blk, h->d_fd_blk_cap, (px + 1023) / 1024))) return rc;
+    if ((rc = ensure(h, h->d_fd_misc, h->d_fd_misc_cap, 4))) return rc;
+    hipStream_t s = h->stream;
+    for (float& v : h->stage_ms) v = 0.f;
+    HIP_TRY(h, hipMemcpyAsync(h->d_fd_lab, labels, px * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(h->d_fd_lsq, lsq, px * C, hipMemcpyHostToDevice, s));
+    FishDistBufs b{h->d_fd_rid, nullptr, h->d_fd_blk, h->d_fd_misc, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    HIP_TRY(h, hipEventRecord(h->ev[0], s));
+    HIP_TRY(h, run_fishdist_cells(h->d_fd_lab, H, W, b, s));
+    HIP_TRY(h, hipEventRecord(h->ev[1], s));
+    int32_t misc[4];
+    HIP_TRY(h, hipMemcpyAsync(misc, h->d_fd_misc, sizeof(misc), hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    h->stage_ms[ECSEG_T_COUNT] = stage_elapsed(h->ev[0], h->ev[1]);
+    if (misc[3])
+        return fail(h, ECSEG_E_INVALID, "fish_distances: the label map holds a label larger than H * W = " + std::to_string(px) +
+                                            " (renumber the labels by rank first)");
+    const int n = misc[0];
+    *n_cells = n;
+    if (n == 0 || n > capacity) return ECSEG_OK;             // the cell count alone: the caller comes back with a larger buffer
+    // the rest is sized by the number of cells, which is known only now
+    const size_t nn = (size_t)n;
+    if ((rc = ensure(h, h->d_fd_par, h->d_fd_par_cap, px))) return rc;
+    if ((rc = ensure(h, h->d_fd_flist, h->d_fd_flist_cap, px))) return rc;
+    if ((rc = ensure(h, h->d_fd_clist, h->d_fd_clist_cap, px))) return rc;
+    if ((rc = ensure(h, h->d_fd_acc, h->d_fd_acc_cap, nn * 4))) return rc;
+    if ((rc = ensure(h, h->d_fd_val, h->d_fd_val_cap, nn))) return rc;
+    if ((rc = ensure(h, h->d_fd_off, h->d_fd_off_cap, nn * 2))) return rc;
+    if ((rc = ensure(h, h->d_fd_cur, h->d_fd_cur_cap, nn * 2))) return rc;
+    if ((rc = ensure(h, h->d_fd_rec, h->d_fd_rec_cap, nn * 8))) return rc;
+    const size_t parts = nn * (size_t)fishdist_slices(n);
+    if ((rc = ensure(h, h->d_fd_pbest, h->d_fd_pbest_cap, parts))) return rc;
+    if ((rc = ensure(h, h->d_fd_proots, h->d_fd_proots_cap, parts))) return rc;
+    b = FishDistBufs{h->d_fd_rid, h->d_fd_par, h->d_fd_blk, h->d_fd_misc, h->d_fd_flist, h->d_fd_clist, h->d_fd_acc, h->d_fd_val,
+                     h->d_fd_off, h->d_fd_cur, h->d_fd_rec, h->d_fd_pbest, h->d_fd_proots};
+    HIP_TRY(h, hipEventRecord(h->ev[2], s));
+    HIP_TRY(h, run_fishdist_records(h->d_fd_lab, h->d_fd_lsq, H, W, C, fish_channel, centromere_channel, n, b, s));
+    HIP_TRY(h, hipEventRecord(h->ev[3], s));
+    HIP_TRY(h, hipMemcpyAsync(records, h->d_fd_rec, nn * 8 * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    h->stage_ms[ECSEG_T_COUNT] += stage_elapsed(h->ev[2], h->ev[3]);
     return ECSEG_OK;
 }
 

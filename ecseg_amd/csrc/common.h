@@ -220,4 +220,19 @@ hipError_t run_nuclei_regions(const uint8_t* seg, const uint8_t* img, int H, int
 hipError_t run_nucleus_crops(const int32_t* labels, const uint8_t* img, int W, int img_w, int C, const int32_t* desc, int n,
                              const int order[3], uint8_t* out, int32_t* chmax, hipStream_t s);
 
+// ---- launchers implemented in fishdist_kernels.hip (src/fish_distance_calculation.py:16-46) ---------------------------------
+// Device buffers of one H x W image: rid and par (H*W int32), blk (ceil(H*W / 1024) int32), misc (4 int32), flist and clist
+// (H*W int2), and - sized by the number of cells n, which run_fishdist_cells reports - acc (4n uint32), val (n int32), off and
+// cur (2n int32), rec (8n int64), and pbest (uint64) and proots (int32) of n * fishdist_slices(n) entries each.
+struct FishDistBufs { int32_t* rid; int32_t* par; int32_t* blk; int32_t* misc; int2* flist; int2* clist; unsigned* acc; int32_t* val;
+                      int32_t* off; int32_t* cur; int64_t* rec; unsigned long long* pbest; int32_t* proots; };
+int fishdist_slices(int n);   // workgroups per cell of the distance search for n cells
+// labels: (H, W) int32 instance labels, <= 0 background.  Leaves rid[label - 1] = dense ascending cell index of every label that
+// occurs, misc[0] = number of cells, misc[3] = 1 when some label exceeds H * W (rid then misses it: do not go on).
+hipError_t run_fishdist_cells(const int32_t* labels, int H, int W, const FishDistBufs& b, hipStream_t s);
+// After run_fishdist_cells with n = misc[0] > 0 and misc[3] == 0: relabels `labels` in place to cell + 1 and writes the n records
+// of ecseg_fish_distances to rec.  lsq: (H, W, C) uint8; fi / ci: FISH and centromere channel.
+hipError_t run_fishdist_records(int32_t* labels, const uint8_t* lsq, int H, int W, int C, int fi, int ci, int n, const FishDistBufs& b,
+                                hipStream_t s);
+
 }  // namespace ecseg

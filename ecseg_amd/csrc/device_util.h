@@ -89,6 +89,28 @@ __device__ __forceinline__ unsigned xcd_remap(unsigned bid, unsigned nwg) {
     return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
 }
 
+// Union-find over an int32 parent array in global memory (post_kernels.hip: the binary labelling; fishdist_kernels.hip: the FISH
+// spots of one nucleus).  A root is its own parent.
+__device__ __forceinline__ int uf_load(const int32_t* L, int i) {
+    return __hip_atomic_load(L + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ int uf_find(const int32_t* L, int x) {
+    int n;
+    while ((n = uf_load(L, x)) != x) x = n;   // parents strictly decrease along a chain -> terminates
+    return x;
+}
+__device__ __forceinline__ void uf_unite(int32_t* L, int a, int b) {
+    for (;;) {
+        a = uf_find(L, a);
+        b = uf_find(L, b);
+        if (a == b) return;
+        if (a < b) { const int t = a; a = b; b = t; }
+        const int old = atomicMin(L + a, b);   // link the larger root under the smaller
+        if (old == a) return;
+        a = old;                                // a had just been linked elsewhere: keep merging from its old parent
+    }
+}
+
 // Host side: "do this once per device" latch for per-device function attributes (hipFuncSetAttribute applies to the
 // current device only; one process may drive several handles on different GPUs, from several threads).  `run(setup)`
 // holds the latch's mutex across check, setup and set, and marks the device only after `setup` has succeeded: a second

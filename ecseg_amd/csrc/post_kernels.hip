@@ -107,25 +107,7 @@ __device__ __forceinline__ size_t tile_index(const CclGeom& g, int img) {
 // ---------------------------------------------------------------------------------------------------------------
 // union-find
 // ---------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int uf_load(const int32_t* L, int i) {
-    return __hip_atomic_load(L + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ int uf_find(const int32_t* L, int x) {
-    int n;
-    while ((n = uf_load(L, x)) != x) x = n;   // parents strictly decrease along a chain -> terminates
-    return x;
-}
-__device__ __forceinline__ void uf_unite(int32_t* L, int a, int b) {
-    for (;;) {
-        a = uf_find(L, a);
-        b = uf_find(L, b);
-        if (a == b) return;
-        if (a < b) { const int t = a; a = b; b = t; }
-        const int old = atomicMin(L + a, b);   // link the larger root under the smaller
-        if (old == a) return;
-        a = old;                                // a had just been linked elsewhere: keep merging from its old parent
-    }
-}
+// uf_load / uf_find / uf_unite: device_util.h (shared with fishdist_kernels.hip)
 
 // ---- phase 1: label one 64 x 32 tile entirely in LDS ---------------------------------------------------------------
 // Every workgroup labels its tile as if it were a stand-alone image: run heads by ballot, one LDS atomicMin union per

@@ -41,6 +41,7 @@ extern "C" {
  * (the split kernels); CONV ops read their so far unused `mode` word as the horizontal stride / dilation rate (0 = as before); CONVT kernels larger than
  * their stride run phase by phase.) */
 /* (still 5 - additive: ecseg_nuclei_regions and ecseg_nucleus_crops, the file-level interSeg driver; nothing existing changed.) */
+/* (still 5 - additive: ecseg_fish_distances, the per-nucleus records of fish_distance_calculation; nothing existing changed.) */
 #define ECSEG_ABI_VERSION 5
 
 #define ECSEG_OK             0
@@ -297,6 +298,26 @@ int ecseg_nuclei_regions(ecseg_ctx* h, const uint8_t* seg, int H, int W, const u
  * test of :199 and the centromere gate of :160). */
 int ecseg_nucleus_crops(ecseg_ctx* h, const int32_t* crops, int n_crops, const int32_t* channel_order, uint8_t* out,
                         int32_t* channel_max);
+
+/* ---- fish_distance_calculation: per-nucleus FISH - centromere distances (src/fish_distance_calculation.py:16-46) --------- */
+/* Replaces, for ONE image, the loop over regionprops(segmentation) (:19), the gate on lsq channels 0 and 1 (:21), the spot
+ * count measure.label(fish_probe).max() (:30-32) and the pixel loop np.linalg.norm(centromere_coords - fish_coord).min()
+ * (:34-45).  labels: (H, W) int32 instance labels (what stat_fish saves as <name>__segmentation_min_cut.npy), values <= 0
+ * are background, a label's pixels need not be connected; a label larger than H * W is refused with ECSEG_E_INVALID
+ * (renumber by rank).  lsq: (H, W, C) uint8, C >= 2 (annotated/<name>/<name>_lsq*.tif: 0 red, 1 green, 2 boundaries).
+ * *n_cells = the number of different labels > 0; records (capacity x 8 int64) receive, when n_cells <= capacity, per label
+ * in ascending label order:
+ *   [0] label  [1] area  [2] gate bits: 1 = channel 0 non-zero somewhere in the cell, 2 = channel 1 (the gate of :21 is [2] == 3)
+ *   [3] FISH pixels (lsq[..., fish_channel] != 0 inside the cell)  [4] centromere pixels (centromere_channel)
+ *   [5] 8-connected components of the FISH pixels, joined only through pixels of this cell (the spot limit of :31 is [5] > max)
+ *   [6] min over FISH pixels f and centromere pixels c of the cell of |f - c|^2, exact; -1 when either set is empty
+ *   [7] 0 (reserved).
+ * The value of :39 is sqrt([6]) / sqrt([1]) in float64.  When n_cells > capacity nothing is written: call again with a buffer
+ * of n_cells records.  One image per call, synchronous; the call keeps buffers of its own (a region map left on the handle by
+ * ecseg_nuclei_regions stays valid); device time of the kernels in ECSEG_T_COUNT.  ECSEG_E_INVALID: C < 2, a channel outside
+ * 0 .. C - 1, H * W >= 2^31, H * W * C >= 2^40.  The distance search is brute force (FISH x centromere pixels per cell). */
+int ecseg_fish_distances(ecseg_ctx* h, const int32_t* labels, int H, int W, const uint8_t* lsq, int C, int fish_channel,
+                         int centromere_channel, int capacity, int64_t* records, int32_t* n_cells);
 
 /* ---- per-stage device timings of the last segment call (milliseconds, HIP events on the handle's stream) -- */
 /* ECSEG_T_COUNT: device time of the kernels of the last ecseg_overlay / ecseg_preprocess / ecseg_count_* call (inputs
