@@ -67,7 +67,7 @@ struct ConvParams {
 };
 
 // Winograd F(4x4,3x3) interpolation points {0, +-W4_PA, +-W4_PB, inf}, shared by the host filter transform (api.hip:
-// winograd4_filter) and the kernel's input / output transforms (wino4_kernel.hip).  The textbook set is {0, +-1, +-2, inf};
+// winograd4_filter) and the kernels' input / output transforms (wino4_consts.inc).  The textbook set is {0, +-1, +-2, inf};
 // the rounding error of the result is dominated by the float32 channel sum of the transformed products on the matrix cores,
 // whose magnitude the points set: tools/wino_points.py replays the kernel's arithmetic on the CPU and measures, against a
 // float64 convolution, 4.4x the error of a sequential float32 direct convolution for {1, 2} and 2.0x for {5/8, 3/2} (the
@@ -97,11 +97,14 @@ int        conv_wino_ntile(int cout);
 hipError_t launch_conv_wino16(const ConvParams& p, hipStream_t s);
 bool       conv_wino16_supported(const ConvParams& p);
 bool       conv_wino16_first_supported(const ConvParams& p);   // with ConvParams::first_w: the network's first layer computed into the halo
-// Winograd F(4x4,3x3) (wino4_kernel.hip); p.wt = image written by winograd4_filter (api.hip)
+// Winograd F(4x4,3x3), split-K kernel for a lone 32-channel output block (wino4_kernel.hip: out.c == 32, no fused head; anything else is
+// hipErrorInvalidValue); p.wt = image written by winograd4_filter (api.hip)
 hipError_t launch_conv_wino4(const ConvParams& p, hipStream_t s);
+// eligibility rules shared by the three F(4x4) kernels
 bool       conv_wino4_supported(const ConvParams& p);
 bool       conv_wino4_span_ok(const ConvParams& p, int windows);   // the halo's buffer descriptor reaches `windows` consecutive windows
-// F(4x4,3x3) on the fp32 matrix cores with the row transform done once per workgroup (wino4r_kernel.hip, round 6); p.wt as conv_wino4_kernel
+// F(4x4,3x3) on the fp32 matrix cores with the row transform done once per workgroup (wino4r_kernel.hip, round 6): every fp32 F(4x4) layer but
+// the lone 32-channel blocks that launch_conv_wino4 takes; p.wt as there
 hipError_t launch_conv_wino4r(const ConvParams& p, hipStream_t s);
 bool       conv_wino4r_supported(const ConvParams& p);
 // F(4x4,3x3) with 3-way bf16 split operands on the bf16 matrix pipe (wino4s_kernel.hip, round 6); p.wt = the stage image written

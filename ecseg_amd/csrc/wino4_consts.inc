@@ -1,4 +1,4 @@
-// Constants and small helpers shared by the F(4x4) kernels (wino4_kernel.hip, wino4s_kernel.hip); included inside namespace ecseg.
+// Constants and small helpers shared by the F(4x4) kernels (wino4_kernel.hip, wino4r_kernel.hip, wino4s_kernel.hip); included inside namespace ecseg.
 namespace {
 
 constexpr int W4_HS = 1536;          // halo slots per buffer: 2 regions x 18 rows x 36 = 1296 used, padded to 24 x 64

@@ -1,34 +1,30 @@
-// Winograd F(4x4, 3x3) convolution on the fp32 matrix cores (gfx950): 36 instead of 144 multiplies per 4x4 output
-// block, i.e. 4x fewer MFMAs than the direct convolution and 1.78x fewer than F(2x2,3x3), still exact-f32 fma chains
-// (v_mfma_f32_32x32x2_f32).
+// Split-K Winograd F(4x4, 3x3) kernel for a lone 32-channel output block (Cout == 32: the 64 -> 32 layers) on the fp32 matrix
+// cores (v_mfma_f32_32x32x2_f32).  The F(4x4) scheme itself - transforms, filter image, region pairs, output stage - is described in
+// wino4r_kernel.hip, whose conv_wino4r_kernel runs every other fp32 F(4x4) layer (and these, unsplit, under wino4_split = 0).
 //
-//   Y = A^T [ sum_cin (G g G^T) .* (B^T d B) ] A        d: 6x6 input tile, g: 3x3 filter, Y: 4x4 outputs
+// Workgroup = 12 waves = 2 regions of 16x16 output pixels (32 Winograd tiles = the MFMA M dimension) x 32 output channels.
+// Wave w = (input-channel half ch = w / 6, transform ROW xi = w % 6).  With 64-channel blocks ch is the output-channel half; for a
+// lone 32-channel block the ch = 1 waves would multiply zero padding.  Instead both waves of a row work on the SAME 32 outputs and
+// split the 8 input channels of a group: wave (ch, xi) runs only filter stage ch (channels 2 ch, 2 ch + 1 of both halo planes) of
+// every group, from the ch = 0 slot of the unchanged filter image; the partial sums meet in the exchange image of the output stage
+// (ch = 0 writes, ch = 1 adds).
 //
-// The filter transform U = G g G^T is done once at model load (float64 on the host, api.hip: winograd4_filter).
+// A wave reads the raw halo rows its row transform needs straight from LDS (8-byte reads: its two channels of every slot), forms
+// t[j] = B^T[xi,:] d[:,j] and the six column points V[xi][0..5] in registers and multiplies them with U[xi][nu] on the MFMA
+// (6 points x 16 accumulators = 96 registers); no transformed input ever touches LDS or HBM.
 //
-// Workgroup = 12 waves = 2 regions of 16x16 output pixels (32 Winograd tiles = the MFMA M dimension) x 64 output
-// channels.  Wave w = (channel half ch = w / 6, transform ROW xi = w % 6): it reads the raw halo rows its row transform
-// needs straight from LDS, forms t[j] = B^T[xi,:] d[:,j] and the six column points V[xi][0..5] in registers and
-// multiplies them with U[xi][nu] on the MFMA (6 points x 16 accumulators = 96 registers); no transformed input ever
-// touches LDS or HBM.  After the K loop every wave folds its own row (R = M[xi][:] A) in registers, the six rows
-// meet through LDS, and Y = A^T R + bias, activation is written as 16-byte stores (128-B segments per pixel).
-//
-// Pipeline: the halo arrives 8 input channels at a time by LDS-DMA into a 3-deep ring, two groups ahead of its use
-// (every wave issues two pieces per group, one at a time behind pinned MFMAs; nobody waits for a piece to land; ONE
-// s_barrier per 8 channels).  The filter fragments are private to a wave (nobody else reads them), so every wave
-// streams its own 3-KB stage (6 points x 4 input channels x 32 output channels) by LDS-DMA into a private double
-// buffer, ordered by its own counted vmcnt only - no barrier on the filter path.  All LDS-DMA goes through inline asm:
-// the compiler orders every ds_read behind a builtin LDS-DMA with vmcnt(0).  The barrier sits at a different
-// point of the phase sequence (transform, MFMA stage 0, MFMA stage 1) for the three waves of a SIMD (phase rotation).
-//
-// The output stage can also write the 2x2 max-pool of its result, finish a 1x1 head (<= 4 classes) and take its region
-// list from a look-up table (demand-driven cropping) - see ConvParams in common.h.
+// Pipeline: the halo arrives 8 input channels at a time by LDS-DMA into a 3-deep ring, two groups ahead of its use (every wave
+// issues two pieces per group, one at a time behind pinned MFMAs; nobody waits for a piece to land; ONE s_barrier per 8 channels).
+// The filter fragments are private to a wave (nobody else reads them), so every wave streams its own 3-KB stage (6 points x 4 input
+// channels x 32 output channels) by LDS-DMA into a private double buffer, ordered by its own counted vmcnt only - no barrier on the
+// filter path.  All LDS-DMA goes through inline asm (wino4_consts.inc).  Per group a wave has two phases, T (row transform) and
+// S (12 MFMAs); waves 4-11 run S one group late (phase rotation, see the K loop).
 //
 // LDS halo image, 16-byte slots (4 channels): slot(g, y, x, h) = (g * 18 + P(y)) * 36 + h * 18 + P(x), where
 // P(v) = {0, 5, 10, 14}[v % 4] + v / 4 regroups the 18 halo rows / columns by their phase modulo the tile stride 4.
-// For a fixed tile offset (i, j) the 16 lanes of a ds_read_b128 group then read slots 36 * ty + tx + const:
+// For a fixed tile offset (i, j) the 16 lanes of a ds_read group then read slots 36 * ty + tx + const:
 // 36 = 4 (mod 16), so all 16 land on different 16-byte bank groups: conflict-free without padding.  The A-operand
-// lane -> tile map follows the hardware's b128 lane groups (see gty below).
+// lane -> tile map follows the hardware's b128 lane groups (see tg / ty below).
 #include <cstdlib>
 #include <type_traits>
 
@@ -48,41 +44,16 @@ namespace ecseg {
 #define ECSEG_W4_TSLOTS 4
 #endif
 
-// Diagnostics (timing-only ablations, in-kernel cycle stamps) live in wino4_diag.inc and exist only in the -DECSEG_DIAG
-// build (tools/build_variants.sh diag); the product translation unit has ONE code path: every hook below is empty.
-#ifdef ECSEG_DIAG
-#include "wino4_diag.inc"
-#else
-#define W4_TEMPLATE template <bool HEAD = false, bool SPLIT = false>
-#define W4_DIAG_ENTRY()
-#define W4_DIAG_SKIP_HALO_DMA()
+#define W4_DIAG_SKIP_HALO_DMA()                              // (hooks of wino4_region.inc; only conv_wino4s_kernel's A/B builds fill them)
 #define W4_DIAG_HALO_OFFSET(off, a)
-#define W4_DIAG_SKIP_FILTER_DMA()
-#define W4_DIAG_FAKE_TRANSFORM(grp)
 #define W4_MFMA(ACC, A, B) ACC = __builtin_amdgcn_mfma_f32_32x32x2f32(A, B, ACC, 0, 0, 0)
 #define W4_WAIT(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
-#define W4_KSTAMP_BEGIN()
-#define WSTAMP(i)
-#define W4_KSTAMP_DUMP()
-#define W4_ESTAMP_BEGIN()
-#define ESTAMP(i)
-#define W4_ESTAMP_DUMP()
-#define W4_DIAG_SELECT(kern, p, lds)
-#endif
 
-// SPLIT (a lone 32-channel output block, Cout == 32): the two channel-half waves of a transform row would otherwise
-// multiply real channels (ch = 0) and zero padding (ch = 1).  Instead both work on the SAME 32 outputs and split the 8
-// input channels of a group: wave (ch, xi) runs only filter stage ch (channels 2 ch, 2 ch + 1 of both halo planes) of every
-// group, from the ch = 0 slot of the unchanged filter image; the partial sums meet in the exchange image of the output
-// stage (ch = 0 writes, ch = 1 adds).  Per group a wave has two phases (T, S) instead of three; waves 4-11 run S one
-// group late (phase rotation).
-W4_TEMPLATE
 __global__ __launch_bounds__(768) void conv_wino4_kernel(ConvParams p, int regs_x, int regs_y, int npairs) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     f32x4* Hs = reinterpret_cast<f32x4*>(smem);              // [3][W4_HS]        halo ring (group g -> buffer g % 3)
     f32x4* Bs = Hs + 3 * W4_HS;                              // [12][2][W4_BWS]   per-wave filter stages
 
-    W4_DIAG_ENTRY();
     const unsigned lds_base = (unsigned)(size_t)(lptr_t)smem;   // LDS byte address of the dynamic segment
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -92,11 +63,10 @@ __global__ __launch_bounds__(768) void conv_wino4_kernel(ConvParams p, int regs_
 #include "wino4_region.inc"
     // ---- filter DMA: wt4[nb][stage][wave][point pair nu / 2][lane = h * 32 + cout][nu % 2][k 2], 768 floats per wave and stage; the
     //      address is a scalar base (advanced per stage by scalar adds) + the lane's constant 16-byte offset ----
-    const unsigned long long w_base = (unsigned long long)(size_t)(p.wt + ((size_t)nb * nstages * 12 + (SPLIT ? xi : wave)) * 768);
+    const unsigned long long w_base = (unsigned long long)(size_t)(p.wt + ((size_t)nb * nstages * 12 + xi) * 768);      // (both channel halves: the ch = 0 slot)
     const unsigned lane16 = (unsigned)lane * 16u;
     f32x4* Bw = Bs + wave * 2 * W4_BWS;
     auto dma_filter_piece = [&](int stage, int buf, auto kk) __attribute__((always_inline)) {
-        W4_DIAG_SKIP_FILTER_DMA();
         constexpr int k = decltype(kk)::value;
         const unsigned long long g = w_base + (unsigned long long)stage * (12 * 768 * 4);
         const unsigned dst = lds_base + (unsigned)(3 * W4_HS + (wave * 2 + buf) * W4_BWS) * 16u;
@@ -133,42 +103,35 @@ __global__ __launch_bounds__(768) void conv_wino4_kernel(ConvParams p, int regs_
         for (int e = 0; e < 16; ++e) acc[v][e] = 0.f;
 
     f32x4 t[6];
-    if (SPLIT) {                                             // (components 2, 3 are never written in this mode: keep the vectors defined)
 #pragma unroll
-        for (int j = 0; j < 6; ++j) t[j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-    // ---- row transform of group grp: t[j] for the six halo columns of the lane's tile, 4 channels each ----
+    for (int j = 0; j < 6; ++j) t[j] = f32x4{0.f, 0.f, 0.f, 0.f};    // (a wave writes only its own two components: keep the vectors defined)
+    // ---- row transform of group grp: t[j] for the six halo columns of the lane's tile, the wave's two channels each ----
     // Rows 1-4 of B^T end in +1 (t = c0 d[r0] + c1 d[r1] + c2 d[r2] + d[r3]: three fmas), rows 0 and 5 have only three
     // terms, the last with +1 (t = c0 d[r0] + c1 d[r1] + d[r2]: three reads, two fmas) - for any point set of this shape.
     const bool inner_row = xi >= 1 && xi <= 4;
-    auto transform = [&](int grp, auto c_src, auto c_num) __attribute__((always_inline)) {   // t[j][k] = row transform of channel c_src + k of the lane's slot, k < c_num (SPLIT: the wave's two channels, in components 0 and 1)
-        constexpr int CS = decltype(c_src)::value, CN = decltype(c_num)::value;
+    auto transform = [&](int grp, auto c_src) __attribute__((always_inline)) {   // t[j][c_src + k] = row transform of channel c_src + k (k < 2, c_src = 2 ch) of the lane's slot
+        constexpr int CS = decltype(c_src)::value, CN = 2;
         const f32x4* A = Hs + (grp % 3) * W4_HS + a_lane;
         constexpr int cp[6] = {w4_cpos(0), w4_cpos(1), w4_cpos(2), w4_cpos(3), w4_cpos(4), w4_cpos(5)};
-        W4_DIAG_FAKE_TRANSFORM(grp);
         // scalar fmas on purpose (file is built with -fno-slp-vectorize): packed f32 VALU ops (v_pk_fma_f32) stall the
         // SIMD beside MFMAs, single v_fma_f32 hide in the matrix pipe's shadow
         // Software-pipelined (round 4): the phase used to be six LDS round trips behind each other (one per halo column:
         // 3 - 4 reads, wait, 12 fmas) and took 2200 - 3200 cycles per group - the three transforms of a SIMD's waves add up to the
         // group period (in-kernel stamps).  Now the LAST term of every column is read straight into t[j] (it enters the
         // chain with coefficient 1), the other reads go through NS rotating slots: each step waits for ONE read, accumulates it
-        // into its column (four fmas) and re-issues the slot, so NS reads are always in flight.  The fma chain of a column runs in
+        // into its column (two fmas) and re-issues the slot, so NS reads are always in flight.  The fma chain of a column runs in
         // the same order as before (innermost term first): results are bit-identical.
         constexpr int NS = ECSEG_W4_TSLOTS;
-        // CN == 4: the lane's whole 16-byte slots; CN == 2 (SPLIT, round 4): only the wave's two channels CS, CS + 1 of every slot
-        // (8-byte reads, half the fmas - a SPLIT wave multiplies half as often per group, so the row transform weighed twice as
-        // much per MFMA there: 64 -> 32 channels ran at 0.315 of the peak, half the rate of the unsplit layers)
-        static_assert((CN == 4 && CS == 0) || (CN == 2 && (CS == 0 || CS == 2)), "whole slots or one channel pair");
-        typedef typename std::conditional<CN == 4, f32x4, f32x2>::type vt;
-        auto rd = [&](int slot) __attribute__((always_inline)) -> vt {
-            if constexpr (CN == 4) return A[slot];
-            else return reinterpret_cast<const f32x2*>(A + slot)[CS / 2];
-        };
-        vt sl[NS];
+        // Only the wave's two channels CS, CS + 1 of every slot (round 4): 8-byte reads, half the fmas of a whole-slot transform - a
+        // split wave multiplies half as often per group, so the row transform weighed twice as much per MFMA: 64 -> 32 channels ran
+        // at 0.315 of the peak with whole slots, half the rate of the unsplit layers
+        static_assert(CS == 0 || CS == 2, "one channel pair of the slot");
+        auto rd = [&](int slot) __attribute__((always_inline)) -> f32x2 { return reinterpret_cast<const f32x2*>(A + slot)[CS / 2]; };
+        f32x2 sl[NS];
         if (inner_row) {
 #pragma unroll
             for (int j = 0; j < 6; ++j) {
-                const vt d = rd(ro3 + cp[j]);
+                const f32x2 d = rd(ro3 + cp[j]);
 #pragma unroll
                 for (int c = 0; c < CN; ++c) t[j][CS + c] = d[c];
             }
@@ -188,7 +151,7 @@ __global__ __launch_bounds__(768) void conv_wino4_kernel(ConvParams p, int regs_
         } else {
 #pragma unroll
             for (int j = 0; j < 6; ++j) {
-                const vt d = rd(ro2 + cp[j]);
+                const f32x2 d = rd(ro2 + cp[j]);
 #pragma unroll
                 for (int c = 0; c < CN; ++c) t[j][CS + c] = d[c];
             }
@@ -207,8 +170,8 @@ __global__ __launch_bounds__(768) void conv_wino4_kernel(ConvParams p, int regs_
 #undef W4_TRD
         }
     };
-    // ---- one filter stage (2 of the group's 4 channel pairs; buffer ss): column transform + 12 MFMAs ----
-    auto mfma_stage = [&](int ss, int fbuf, int next_stage, int halo_grp) __attribute__((always_inline)) {     // ss: channel pair of the group, fbuf: filter buffer; halo_grp: group to prefetch, < 0: none
+    // ---- one filter stage (channels 2 ss, 2 ss + 1 of both halo planes): column transform + 12 MFMAs ----
+    auto mfma_stage = [&](int ss, int fbuf, int next_stage, int halo_grp) __attribute__((always_inline)) {     // ss: the wave's channel pair (= ch), fbuf: filter buffer; halo_grp: group to prefetch, < 0: none
         const int nbuf = fbuf ^ 1;
         float V[6][2];
 #pragma unroll
@@ -258,151 +221,81 @@ __global__ __launch_bounds__(768) void conv_wino4_kernel(ConvParams p, int regs_
     };
 #define W4_BARRIER() asm volatile("s_barrier" ::: "memory")
 
-    W4_KSTAMP_BEGIN();
-    // Phase rotation.  Per 8-channel group a wave has three phases: T (halo LDS reads + row transform, latency-bound),
-    // S0 and S1 (12 MFMAs each).  The barrier would keep the three waves of a SIMD (w, w + 4, w + 8) in the same phase,
-    // with the matrix pipe idle while all of them transform.  So the barrier sits at a different point of each wave's
-    // phase sequence: class 0 (waves 0-3, also the halo loaders) runs T(g) S0(g) S1(g) after barrier g, class 1 runs
-    // S1(g-1) T(g) S0(g), class 2 runs S0(g-1) S1(g-1) T(g): at any time one wave of a SIMD transforms while the other
-    // two feed the matrix pipe.  t[] lives in registers across the barrier; every class executes ngroups barriers and
-    // reads halo group g only between barriers g and g+1.
+    // Phase rotation.  Per 8-channel group a wave has two phases: T (halo LDS reads + row transform of its two channels,
+    // latency-bound) and S (its one filter stage of the group: 12 MFMAs).  The barrier would keep the three waves of a SIMD
+    // (w, w + 4, w + 8) in the same phase, with the matrix pipe idle while all of them transform.  So the barrier sits at a
+    // different point of the phase sequence: waves 0-3 (one per SIMD) run T(g) S(g) after barrier g, waves 4-11 run S(g - 1) T(g):
+    // while one class transforms, the other feeds the matrix pipe.  t[] lives in registers across the barrier; every wave executes
+    // ngroups barriers and reads halo group g only between barriers g and g + 1.  The late waves' halo pieces of group g + 1 go
+    // out in period g (inside S(g - 1)) and are waited for before barrier g + 1.  (Three classes with the stage cut into two
+    // halves of 6 MFMAs: no gain, tools/experiments/wino4_split_three_classes.patch.)
 #define W4_SB() __builtin_amdgcn_sched_barrier(0)
-// T(g): raised priority for the few long-latency instructions of the transform; afterwards the MFMA phases run at a
-// priority that orders the three waves of a SIMD (class 2 first): the wave that is latest in the rotation gets the pipe
-// Priorities (round 4, A/B on one box, per-layer tables in gpurun_out/r04_ab1): the MATRIX phases run above the transform
-// (transform 0, matrix phases 1 / 2 / 3 by rotation class): 1024 -> 512 at 32x32 13.83 -> 13.35 ms, 512 -> 512 6.92-7.11 -> 6.73-6.78,
-// every other layer +-0.5 %; the transform is latency-bound on its LDS reads and loses nothing at priority 0, a ready MFMA
-// no longer waits behind another wave's burst of 12 transform fmas.  (Rounds 1-3: transform at 3, matrix phases 0 / 1 / 2; no
-// priorities at all: -6 %.)
+// Priorities (round 4, A/B on one box): the MATRIX phases run above the transform (transform 0, matrix phases 1 / 2 by class): the
+// transform is latency-bound on its LDS reads and loses nothing at priority 0, a ready MFMA no longer waits behind another wave's
+// burst of transform fmas.  (Rounds 1-3: transform above the matrix phases; no priorities at all: -6 %.)
 #define W4_PT 0
 #define W4_PS(PR) ((PR) + 1)
-#define W4_T(g, PR) do { __builtin_amdgcn_s_setprio(W4_PT); transform(g, std::integral_constant<int, 0>{}, std::integral_constant<int, 4>{}); __builtin_amdgcn_s_setprio(W4_PS(PR)); } while (0)
-    // S0(g): filter stage 2g has landed (it is the youngest thing this wave issued) -> vmcnt(0); streams stage 2g+1 and
-    // the halo of group g+2.  S1(g): only the two halo pieces issued after stage 2g+1 may still fly -> vmcnt(2).
-#define W4_S0(g) do { W4_SB(); W4_WAIT(0); W4_SB(); mfma_stage(0, 0, 2 * (g) + 1, (g) + 2 < ngroups ? (g) + 2 : -1); } while (0)
-#define W4_S1(g) do { W4_SB(); if ((g) + 2 < ngroups) W4_WAIT(2); else W4_WAIT(0); W4_SB(); \
-                      mfma_stage(1, 1, (g) + 1 < ngroups ? 2 * (g) + 2 : 2 * (g), -1); } while (0)
-// SPLIT: T(g) of the wave's two channels 2 ch, 2 ch + 1 only (round 4, in the slot-pipelined form; the column-by-column two-channel
-// transform of round 2 made the register allocator spill ~100 registers); S(g) = its one filter stage of group g (stage 2 g + ch of the image, private
-// buffer g & 1): everything this wave issued has landed (vmcnt(0): the filter of this group and its halo pieces of group
-// g + 1); streams the filter of group g + 1 and the halo of group g + 2
-#define W4_TS(g, PR) do { __builtin_amdgcn_s_setprio(W4_PT); \
-                          transform(g, std::integral_constant<int, 2 * CH>{}, std::integral_constant<int, 2>{}); \
+// T(g) in the slot-pipelined form (the column-by-column two-channel transform of round 2 made the register allocator spill ~100
+// registers).  S(g) = filter stage 2 g + CH of the image, private buffer g & 1: everything this wave issued has landed (vmcnt(0):
+// the filter of this group and its halo pieces of group g + 1); streams the filter of group g + 1 and the halo of group g + 2
+#define W4_TS(g, PR) do { __builtin_amdgcn_s_setprio(W4_PT); transform(g, std::integral_constant<int, 2 * CH>{}); \
                           __builtin_amdgcn_s_setprio(W4_PS(PR)); } while (0)
 #define W4_SS(g) do { W4_SB(); W4_WAIT(0); W4_SB(); \
                       mfma_stage(CH, (g) & 1, ((g) + 1 < ngroups ? 2 * (g) + 2 : 2 * (g)) + CH, (g) + 2 < ngroups ? (g) + 2 : -1); } while (0)
-    const int cls = wave >> 2;
     dma_halo_piece(0, std::integral_constant<int, 0>{});
     dma_halo_piece(0, std::integral_constant<int, 1>{});
     if (ngroups > 1) {
         dma_halo_piece(1, std::integral_constant<int, 0>{});
         dma_halo_piece(1, std::integral_constant<int, 1>{});
     }
-    dma_filter_piece(SPLIT ? ch : 0, 0, std::integral_constant<int, 0>{});
-    dma_filter_piece(SPLIT ? ch : 0, 0, std::integral_constant<int, 1>{});
-    dma_filter_piece(SPLIT ? ch : 0, 0, std::integral_constant<int, 2>{});
+    dma_filter_piece(ch, 0, std::integral_constant<int, 0>{});
+    dma_filter_piece(ch, 0, std::integral_constant<int, 1>{});
+    dma_filter_piece(ch, 0, std::integral_constant<int, 2>{});
     if (ngroups > 1) W4_WAIT(5); else W4_WAIT(3);            // halo group 0 has landed (group 1: before barrier 1, below)
-    if (SPLIT) {
-        // two phases per group.  Waves 0-3 run T(g) S(g) after barrier g; waves 4-11 run S(g - 1) T(g): while one class
-        // transforms, the other feeds the matrix pipe.  The late waves' halo pieces of group g + 1 go out in period g (inside
-        // S(g - 1)) and are waited for before barrier g + 1.
-        auto kloop = [&](auto chc) __attribute__((always_inline)) {      // (one copy of the loop per channel half: no branch inside)
-            constexpr int CH = decltype(chc)::value;
-            if (cls == 0) {
-                for (int grp = 0; grp < ngroups; ++grp) {
-                    W4_BARRIER();
-                    W4_TS(grp, 0);
-                    W4_SS(grp);
-                }
-            } else {
+    const int cls = wave >> 2;                               // waves 0-3: one per SIMD
+    auto kloop = [&](auto chc) __attribute__((always_inline)) {          // (one copy of the loop per channel half: no branch inside)
+        constexpr int CH = decltype(chc)::value;
+        if (cls == 0) {
+            for (int grp = 0; grp < ngroups; ++grp) {
                 W4_BARRIER();
-                W4_TS(0, 1);
-                for (int grp = 1; grp < ngroups; ++grp) {
-                    W4_WAIT(0);
-                    W4_BARRIER();
-                    W4_SS(grp - 1);
-                    W4_TS(grp, 1);
-                }
-                W4_SS(ngroups - 1);
+                W4_TS(grp, 0);
+                W4_SS(grp);
             }
-        };
-        if (ch == 0) kloop(std::integral_constant<int, 0>{}); else kloop(std::integral_constant<int, 1>{});
-    } else if (cls == 0) {
-        for (int grp = 0; grp < ngroups; ++grp) {
-            WSTAMP(0);
+        } else {
             W4_BARRIER();
-            WSTAMP(1);
-            W4_T(grp, 0);
-            WSTAMP(2);
-            W4_S0(grp);
-            WSTAMP(3);
-            W4_S1(grp);
-            WSTAMP(4);
+            W4_TS(0, 1);
+            for (int grp = 1; grp < ngroups; ++grp) {
+                W4_WAIT(0);
+                W4_BARRIER();
+                W4_SS(grp - 1);
+                W4_TS(grp, 1);
+            }
+            W4_SS(ngroups - 1);
         }
-    } else if (cls == 1) {
-        W4_BARRIER();
-        W4_T(0, 1);
-        W4_S0(0);
-        for (int grp = 1; grp < ngroups; ++grp) {
-            WSTAMP(0);
-            W4_BARRIER();
-            WSTAMP(1);
-            W4_S1(grp - 1);
-            WSTAMP(2);
-            W4_T(grp, 1);
-            WSTAMP(3);
-            W4_S0(grp);
-            WSTAMP(4);
-        }
-        W4_S1(ngroups - 1);
-    } else {
-        W4_BARRIER();
-        W4_T(0, 2);
-        for (int grp = 1; grp < ngroups; ++grp) {
-            W4_WAIT(3);                                      // own halo pieces of group grp + 0/1 landed (3 filter pieces may fly)
-            WSTAMP(0);
-            W4_BARRIER();
-            WSTAMP(1);
-            W4_S0(grp - 1);
-            WSTAMP(2);
-            W4_S1(grp - 1);
-            WSTAMP(3);
-            W4_T(grp, 2);
-            WSTAMP(4);
-        }
-        W4_S0(ngroups - 1);
-        W4_S1(ngroups - 1);
-    }
-#undef W4_T
-#undef W4_S0
-#undef W4_S1
+    };
+    if (ch == 0) kloop(std::integral_constant<int, 0>{}); else kloop(std::integral_constant<int, 1>{});
 #undef W4_TS
 #undef W4_SS
 #undef W4_SB
-    W4_KSTAMP_DUMP();
 #undef W4_BARRIER
 
-    // ---- output stage: two passes (channel halves) through a [xi][x][tile][32 couts] exchange image ----
+    // ---- output stage: one pass through a [xi][x][tile][32 couts] exchange image ----
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");         // the compiler does not see the asm LDS-DMAs
     float* Rs = reinterpret_cast<float*>(smem);
     const int Cout = p.out.c;
-    W4_ESTAMP_BEGIN();
-    // Work split of the combine step: wino4_combine.inc (1024 whole items per pass, a wave owns tile pairs).
-    float hl[2][4][4];                                       // fused 1x1 head: partial logits [round][row of the tile][class]
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 4; ++b)
-#pragma unroll
-            for (int c = 0; c < 4; ++c) hl[a][b][c] = 0.f;
-    // the bias quads of both passes are fetched here, under the K loop's drain and the first barrier: a global load inside
-    // the combine step would queue behind the previous pass's output stores (one in-order vmcnt)
+    // wino4_combine.inc is written for the 64-channel kernels (two passes of 32 channels, an optional fused 1x1 head): this kernel
+    // is its pass 0 without a head; hl is named only in the constant-false HEAD arm
+    constexpr bool HEAD = false;
+    constexpr int pass = 0;
+    float hl[2][4][4];
+    // the bias quads are fetched here, under the K loop's drain and the first barrier (a global load inside the combine step would
+    // queue behind output stores: one in-order vmcnt)
     f32x4 bvp[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
     if (p.bias != nullptr) {
         bvp[0] = *reinterpret_cast<const f32x4*>(p.bias + nb * 64 + 4 * (tid & 7));
         if (nb * 64 + 32 < Cout) bvp[1] = *reinterpret_cast<const f32x4*>(p.bias + nb * 64 + 32 + 4 * (tid & 7));
     }
-    // fold the wave's own row (R = M[xi][:] A) into the exchange image; `add` (SPLIT, ch = 1): onto the partner's partial sums
+    // fold the wave's own row (R = M[xi][:] A) into the exchange image; `add` (ch = 1): onto the partner's partial sums
     auto write_R = [&](auto add_c) __attribute__((always_inline)) {
         constexpr bool add = decltype(add_c)::value;
 #pragma unroll
@@ -420,24 +313,12 @@ __global__ __launch_bounds__(768) void conv_wino4_kernel(ConvParams p, int regs_
             }
         }
     };
-    for (int pass = 0; pass < (SPLIT ? 1 : 2); ++pass) {
-        __syncthreads();                                     // main-loop LDS reads / previous pass's combine are done
-        ESTAMP(0);                                           // [0] barrier (K-loop skew / previous combine)
-        if (SPLIT) {
-            if (ch == 0) write_R(std::false_type{});
-            __syncthreads();
-            if (ch == 1) write_R(std::true_type{});
-        } else if (ch == pass) {
-            write_R(std::false_type{});
-        }
-        ESTAMP(1);                                           // [1] fold own row + write R to LDS
-        __syncthreads();
-        ESTAMP(2);                                           // [2] barrier
+    __syncthreads();                                         // main-loop LDS reads are done
+    if (ch == 0) write_R(std::false_type{});
+    __syncthreads();
+    if (ch == 1) write_R(std::true_type{});
+    __syncthreads();
 #include "wino4_combine.inc"
-        ESTAMP(3);                                           // [3] combine + output stores issued
-    }
-#include "wino4_head.inc"
-    W4_ESTAMP_DUMP();
 }
 
 // Eligibility beyond "3x3, stride 1, pad 1, same size" (checked by the caller): extents multiples of 16, input channels
@@ -455,27 +336,22 @@ bool conv_wino4_supported(const ConvParams& p) {
 }
 
 hipError_t launch_conv_wino4(const ConvParams& p, hipStream_t s) {
+    if (p.out.c != 32 || p.head_w != nullptr) return hipErrorInvalidValue;    // (every other F(4x4) layer: launch_conv_wino4r / launch_conv_wino4s)
     const int regs_x = p.out.w / 16, regs_y = p.out.h / 16;
     const size_t nreg = p.lut != nullptr ? (size_t)(p.n / p.per_image) * p.lut_len : (size_t)p.n * regs_x * regs_y;
     const size_t npairs = (nreg + 1) / 2;
-    const size_t grid = npairs * (size_t)((p.out.c + 63) / 64);
+    const size_t grid = npairs;                              // one output-channel block
     if (grid == 0) return hipSuccess;
     if (grid > 0x7fffffffull || !conv_wino4_span_ok(p, p.lut != nullptr ? p.per_image : 2)) return hipErrorInvalidValue;
-    if (p.head_w != nullptr && (!p.head_only || p.pool.p != nullptr)) return hipErrorInvalidValue;     // (the HEAD kernels write neither the features nor a pool)
     size_t lds = (size_t)(3 * W4_HS + 12 * 2 * W4_BWS) * 16;
     const size_t lds_epi = (size_t)24 * W4_RPLANE * 4;
     if (lds_epi > lds) lds = lds_epi;
-    void (*kern)(ConvParams, int, int, int) = conv_wino4_kernel<false, false>;
-    if (p.head_w != nullptr) kern = conv_wino4_kernel<true, false>;
-    else if (p.out.c == 32 && p.w4_split) kern = conv_wino4_kernel<false, true>;   // a lone 32-channel block: split K
-    W4_DIAG_SELECT(kern, p, lds);
-    static DeviceOnce attr_set[3];                          // the attribute is per device
-    const int which = p.head_w != nullptr ? 1 : (p.out.c == 32 && p.w4_split) ? 2 : 0;
-    const hipError_t ea = attr_set[which].run([&] {
-        return hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    static DeviceOnce attr_set;                              // the attribute is per device
+    const hipError_t ea = attr_set.run([&] {
+        return hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wino4_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     });
     if (ea != hipSuccess) return ea;
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(768), lds, s, p, regs_x, regs_y, (int)npairs);
+    hipLaunchKernelGGL(conv_wino4_kernel, dim3((unsigned)grid), dim3(768), lds, s, p, regs_x, regs_y, (int)npairs);
     return hipGetLastError();
 }
 

@@ -1,4 +1,4 @@
-// Shared by conv_wino4_kernel (wino4_kernel.hip) and conv_wino4s_kernel (wino4s_kernel.hip), included inside the kernel body:
+// Shared by the three F(4x4) kernels (wino4_kernel.hip, wino4r_kernel.hip, wino4s_kernel.hip), included inside the kernel body:
 // block order, the two 16x16 regions of the workgroup, their input boxes, and the halo LDS-DMA (dma_halo_piece).
 // Expects: p, regs_x, regs_y, npairs, wave, lane, lds_base; defines bid, nb, pair, H, W, ngroups, tail4, r_img / r_y0 / r_x0 / r_win,
 // hrsrc, hoff[2], dma_halo_piece(grp, piece).  W4_HALO_RING: depth of the halo ring in LDS (buffers of W4_HS slots from lds_base on);

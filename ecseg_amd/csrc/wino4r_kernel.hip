@@ -1,10 +1,33 @@
-// Winograd F(4x4, 3x3) on the fp32 matrix cores with the ROW transform done once per workgroup (round 6): conv_wino4_kernel's arithmetic -
-// the same filter image, the same fma chains in the row and column transforms, MFMA order and output stage: results are BIT-IDENTICAL
-// (tools/w4r_time.py) - in the loop structure of conv_wino4s_kernel (wino4s_kernel.hip): per 8-channel group all 768 threads
-// turn the raw halo into a t image in LDS (row_pass: 576 half items, 24 fmas each), a wave reads the six 16-byte columns of ITS row instead
-// of 24 raw slots + 72 fmas; two barriers per group, raw halo double-buffered and fetched two groups ahead.  See DESIGN.md 5.1 for what
-// it measures against the kernel it came from.  (A SPLIT variant for lone 32-channel blocks was built and measured 2 - 6 % SLOWER than
-// conv_wino4_kernel<false, true>, which keeps those layers: tools/experiments/wino4r_split_variant.patch.)
+// Winograd F(4x4, 3x3) convolution on the fp32 matrix cores (gfx950): 36 instead of 144 multiplies per 4x4 output
+// block, i.e. 4x fewer MFMAs than the direct convolution and 1.78x fewer than F(2x2,3x3), still exact-f32 fma chains
+// (v_mfma_f32_32x32x2_f32).
+//
+//   Y = A^T [ sum_cin (G g G^T) .* (B^T d B) ] A        d: 6x6 input tile, g: 3x3 filter, Y: 4x4 outputs
+//
+// The filter transform U = G g G^T is done once at model load (float64 on the host, api.hip: winograd4_filter).
+//
+// Workgroup = 12 waves = 2 regions of 16x16 output pixels (32 Winograd tiles = the MFMA M dimension) x 64 output
+// channels.  Wave w = (channel half ch = w / 6, transform ROW xi = w % 6).  Per 8-channel group all 768 threads turn the raw
+// halo into a t image in LDS ONCE per workgroup (row_pass: 576 half items, 24 fmas each; t[j] = B^T[xi,:] d[:,j]); a wave reads
+// the six 16-byte columns of ITS row, forms the six column points V[xi][0..5] in registers and multiplies them with U[xi][nu]
+// on the MFMA (6 points x 16 accumulators = 96 registers); no transformed input ever touches HBM.  After the K loop every
+// wave folds its own row (R = M[xi][:] A) in registers, the six rows meet through LDS, and Y = A^T R + bias, activation is
+// written as 16-byte stores (128-B segments per pixel).
+//
+// Pipeline: the raw halo arrives 8 input channels at a time by LDS-DMA into a double buffer, two groups ahead of its use; two
+// barriers per group, the three waves of a SIMD rotated against them (see the K loop; the loop structure is conv_wino4s_kernel's,
+// wino4s_kernel.hip).  The filter fragments are private to a wave (nobody else reads them), so every wave streams its own 3-KB
+// stage (6 points x 4 input channels x 32 output channels) by LDS-DMA into a private double buffer, ordered by its own counted
+// vmcnt only - no barrier on the filter path.  All LDS-DMA goes through inline asm (wino4_consts.inc).
+//
+// The output stage can also write the 2x2 max-pool of its result, finish a 1x1 head (<= 4 classes) and take its region
+// list from a look-up table (demand-driven cropping) - see ConvParams in common.h.
+//
+// History (round 6): until then every wave read the raw halo rows of its transform row straight from LDS and ran
+// the row transform itself (24 raw slots + 72 fmas per group instead of six columns); this kernel replaced that one with
+// bit-identical results, 1 - 6 % faster per layer.  The per-wave scheme survives where it is faster: the split-K kernel for a lone
+// 32-channel output block, conv_wino4_kernel (wino4_kernel.hip; a split variant of THIS kernel measured 2 - 6 % slower there:
+// tools/experiments/wino4r_split_variant.patch).
 #include <cstdlib>
 #include <type_traits>
 
@@ -33,9 +56,6 @@ namespace ecseg {
 #define W4_MFMA(ACC, A, B) ACC = __builtin_amdgcn_mfma_f32_32x32x2f32(A, B, ACC, 0, 0, 0)
 #endif
 #define W4_WAIT(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
-#define ESTAMP(i)
-#define W4_ESTAMP_BEGIN()
-#define W4_ESTAMP_DUMP()
 
 namespace {
 constexpr int W4R_TS = 2 * 6 * 4 * 36;   // slots of the t image: 2 regions x 6 transform rows x 4 tile rows x (18 columns x 2 channel halves)
@@ -43,7 +63,6 @@ constexpr int W4R_TS = 2 * 6 * 4 * 36;   // slots of the t image: 2 regions x 6 
 
 template <bool HEAD>
 __global__ __launch_bounds__(768) void conv_wino4r_kernel(ConvParams p, int regs_x, int regs_y, int npairs) {
-    constexpr bool SPLIT = false;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     f32x4* Hs = reinterpret_cast<f32x4*>(smem);              // [2][W4_HS]        raw halo (group g -> buffer g & 1)
     f32x4* Ts = Hs + 2 * W4_HS;                              // [W4R_TS]          row-transformed halo of one group
@@ -58,7 +77,7 @@ __global__ __launch_bounds__(768) void conv_wino4r_kernel(ConvParams p, int regs
 #include "wino4_region.inc"
     // ---- filter DMA: wt4[nb][stage][wave][point pair nu / 2][lane = h * 32 + cout][nu % 2][k 2], 768 floats per wave and stage; the
     //      address is a scalar base (advanced per stage by scalar adds) + the lane's constant 16-byte offset ----
-    const unsigned long long w_base = (unsigned long long)(size_t)(p.wt + ((size_t)nb * nstages * 12 + (SPLIT ? xi : wave)) * 768);
+    const unsigned long long w_base = (unsigned long long)(size_t)(p.wt + ((size_t)nb * nstages * 12 + wave) * 768);
     const unsigned lane16 = (unsigned)lane * 16u;
     f32x4* Bw = Bs + wave * 2 * W4_BWS;
     auto dma_filter_piece = [&](int stage, int buf, auto kk) __attribute__((always_inline)) {
@@ -95,8 +114,9 @@ __global__ __launch_bounds__(768) void conv_wino4r_kernel(ConvParams p, int regs
         const f32x2* R = reinterpret_cast<const f32x2*>(Hs + (grp & 1) * W4_HS + (tgg * 18 + 4 * tyy) * 36 + 2 * x + h) + cpair;     // raw row 4 tyy + i: + 36 i slots
         const f32x2 d0 = R[2 * 36 * 0], d1 = R[2 * 36 * 1], d2 = R[2 * 36 * 2], d3 = R[2 * 36 * 3], d4 = R[2 * 36 * 4], d5 = R[2 * 36 * 5];
         f32x2* T = reinterpret_cast<f32x2*>(Ts + ((tgg * 6) * 4 + tyy) * 36 + h * 18 + w4_pos(x)) + cpair;                            // + xi * 144 slots
-        // t[xi] = c0 d[r0] + c1 d[r1] + c2 d[r2] + d[r3] as the SAME fma chains conv_wino4_kernel's per-wave row transform runs (innermost term
-        // first): bit-identical t, hence bit-identical results in the fp32 kernel.  (A first version shared the even / odd parts of the +- rows,
+        // t[xi] = c0 d[r0] + c1 d[r1] + c2 d[r2] + d[r3] as ONE fma chain per row, innermost term first: fma(c0, d[r0], fma(c1, d[r1],
+        // fma(c2, d[r2], d[r3]))) - the operation order of the per-wave row transform (wino4_kernel.hip), so every F(4x4) kernel forms
+        // bit-identical t.  (A first version shared the even / odd parts of the +- rows,
         // 12 instead of 16 fmas per channel: the smooth fixture model's wrong-pixel total rose from 11 to 19 of ~15 hard pixels per image.)
         f32x2 o;
 #define W4_ROW3(XI, A0, DA, A1, DB, DC) do { _Pragma("unroll") for (int c = 0; c < 2; ++c) o[c] = __builtin_fmaf(A0, DA[c], __builtin_fmaf(A1, DB[c], DC[c])); T[2 * (XI) * 144] = o; } while (0)
@@ -174,10 +194,9 @@ __global__ __launch_bounds__(768) void conv_wino4r_kernel(ConvParams p, int regs
     //   class 0:   Y(g-1) | t <- image, S0(g)        | X(g) | row_pass(g+1), S1(g)
     //   class 1:   Y(g-1) | S1(g-1), t <- image      | X(g) | row_pass(g+1), S0(g)
     //   class 2:   Y(g-1) | t <- image, S0(g)        | X(g) | S1(g), row_pass(g+1)
-    // Filter stage s = 2 g + ss lives in buffer ss and is streamed one stage ahead behind the MFMAs of the stage before (as in
-    // conv_wino4_kernel).  Waits: the phase right behind Y has the two halo pieces issued behind Y younger than its stage -> vmcnt(2);
+    // Filter stage s = 2 g + ss lives in buffer ss and is streamed one stage ahead behind the MFMAs of the stage before.  Waits: the phase right behind Y has the two halo pieces issued behind Y younger than its stage -> vmcnt(2);
     // the other phase's stage is the youngest thing the wave issued -> vmcnt(0).  (Two stages ahead, as the split kernel streams: -1 %,
-    // tools/experiments/wino4r_filter_two_stages_ahead.patch; s_setprio by rotation class as in conv_wino4_kernel: +-0.)
+    // tools/experiments/wino4r_filter_two_stages_ahead.patch; s_setprio by rotation class, matrix phases above the transform: +-0.)
 #define W4_S(ss, g, H) do { W4_SB(); if (H) W4_WAIT(2); else W4_WAIT(0); W4_SB(); \
                             mfma_stage(ss, ss, (ss) == 0 ? 2 * (g) + 1 : ((g) + 1 < ngroups ? 2 * (g) + 2 : 2 * (g)), -1); W4_SB(); } while (0)
 #define W4_Y() do { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); W4_BARRIER(); W4_SB(); } while (0)
@@ -247,7 +266,6 @@ __global__ __launch_bounds__(768) void conv_wino4r_kernel(ConvParams p, int regs
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");         // the compiler does not see the asm LDS-DMAs
     float* Rs = reinterpret_cast<float*>(smem);
     const int Cout = p.out.c;
-    W4_ESTAMP_BEGIN();
     // Work split of the combine step: wino4_combine.inc (1024 whole items per pass, a wave owns tile pairs).
     float hl[2][4][4];                                       // fused 1x1 head: partial logits [round][row of the tile][class]
 #pragma unroll
@@ -263,9 +281,8 @@ __global__ __launch_bounds__(768) void conv_wino4r_kernel(ConvParams p, int regs
         bvp[0] = *reinterpret_cast<const f32x4*>(p.bias + nb * 64 + 4 * (tid & 7));
         if (nb * 64 + 32 < Cout) bvp[1] = *reinterpret_cast<const f32x4*>(p.bias + nb * 64 + 32 + 4 * (tid & 7));
     }
-    // fold the wave's own row (R = M[xi][:] A) into the exchange image; `add` (SPLIT, ch = 1): onto the partner's partial sums
-    auto write_R = [&](auto add_c) __attribute__((always_inline)) {
-        constexpr bool add = decltype(add_c)::value;
+    // fold the wave's own row (R = M[xi][:] A) into the exchange image
+    auto write_R = [&]() __attribute__((always_inline)) {
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
             const int tl = (e & 3) + 8 * (e >> 2) + 4 * lh;               // accumulator row = tile slot
@@ -274,14 +291,10 @@ __global__ __launch_bounds__(768) void conv_wino4r_kernel(ConvParams p, int regs
             float* o = Rs + (xi * 4) * W4_RPLANE + tl * 32 + li;
             const float r0 = m0 + s12 + s34, r1 = __builtin_fmaf(KA, d12, KB * d34), r2 = __builtin_fmaf(KA2, s12, KB2 * s34),
                         r3 = __builtin_fmaf(KA3, d12, __builtin_fmaf(KB3, d34, m5));
-            if (add) {                                           // (this lane's four words: nobody else touches them in this phase)
-                o[0 * W4_RPLANE] += r0; o[1 * W4_RPLANE] += r1; o[2 * W4_RPLANE] += r2; o[3 * W4_RPLANE] += r3;
-            } else {
-                o[0 * W4_RPLANE] = r0; o[1 * W4_RPLANE] = r1; o[2 * W4_RPLANE] = r2; o[3 * W4_RPLANE] = r3;
-            }
+            o[0 * W4_RPLANE] = r0; o[1 * W4_RPLANE] = r1; o[2 * W4_RPLANE] = r2; o[3 * W4_RPLANE] = r3;
         }
     };
-    if constexpr (!HEAD && !SPLIT) {
+    if constexpr (!HEAD) {
         // Passes by TILE half instead of channel half (round 6): pass P takes the accumulator rows e = 8 P .. 8 P + 7 (tiles 16 P .. 16 P + 15) of ALL
         // 64 output channels, exchange image [xi][x][16 tiles][64 couts] - every wave folds and writes in BOTH passes (half as many rows each)
         // where the channel-half passes left six of the twelve waves waiting behind the other six's fold.  The same sums element by element:
@@ -371,24 +384,13 @@ __global__ __launch_bounds__(768) void conv_wino4r_kernel(ConvParams p, int regs
         tile_pass(std::integral_constant<int, 0>{});
         tile_pass(std::integral_constant<int, 1>{});
     } else
-    for (int pass = 0; pass < (SPLIT ? 1 : 2); ++pass) {
+    for (int pass = 0; pass < 2; ++pass) {                   // fused head: passes by channel half
         __syncthreads();                                     // main-loop LDS reads / previous pass's combine are done
-        ESTAMP(0);                                           // [0] barrier (K-loop skew / previous combine)
-        if (SPLIT) {
-            if (ch == 0) write_R(std::false_type{});
-            __syncthreads();
-            if (ch == 1) write_R(std::true_type{});
-        } else if (ch == pass) {
-            write_R(std::false_type{});
-        }
-        ESTAMP(1);                                           // [1] fold own row + write R to LDS
+        if (ch == pass) write_R();
         __syncthreads();
-        ESTAMP(2);                                           // [2] barrier
 #include "wino4_combine.inc"
-        ESTAMP(3);                                           // [3] combine + output stores issued
     }
 #include "wino4_head.inc"
-    W4_ESTAMP_DUMP();
 }
 
 

@@ -1,7 +1,7 @@
 // Winograd F(4x4, 3x3) convolution with the channel sum on the BF16 matrix pipe, float32-accurate: both operands are split
 // exactly into three bf16 pieces (x = x1 + x2 + x3, 8 significant bits each) and the six products above 2^-24 relative are
 // accumulated in float32 by v_mfma_f32_32x32x16_bf16 - 32 pipe cycles for K = 16 where v_mfma_f32_32x32x2_f32 needs 64 for K = 2
-// (round 6; option "winograd" = 3, `precision: split`; the fp32-MFMA kernel of wino4_kernel.hip stays the default).
+// (round 6; option "winograd" = 3, `precision: split`; the fp32-MFMA kernel of wino4r_kernel.hip stays the default).
 //
 //   sum_c V[c] U[c]  ~  sum_c  v1 u1 + (v1 u2 + v2 u1) + (v1 u3 + v2 u2 + v3 u1)        dropped: v2 u3 + v3 u2 + v3 u3 <= 3 x 2^-24 |V U|
 //
@@ -146,7 +146,7 @@ __global__ __launch_bounds__(768) void conv_wino4s_kernel(ConvParams p, int regs
         const f32x2* R = reinterpret_cast<const f32x2*>(Hs + (grp & 1) * W4_HS + (tgg * 18 + 4 * tyy) * 36 + 2 * x + h) + cpair;     // raw row 4 tyy + i: + 36 i slots
         const f32x2 d0 = R[2 * 36 * 0], d1 = R[2 * 36 * 1], d2 = R[2 * 36 * 2], d3 = R[2 * 36 * 3], d4 = R[2 * 36 * 4], d5 = R[2 * 36 * 5];
         f32x2* T = reinterpret_cast<f32x2*>(Ts + ((tgg * 6) * 4 + tyy) * 36 + h * 18 + w4_pos(x)) + cpair;                            // + xi * 144 slots
-        // t[xi] = c0 d[r0] + c1 d[r1] + c2 d[r2] + d[r3] as the SAME fma chains conv_wino4_kernel's per-wave row transform runs (innermost term
+        // t[xi] = c0 d[r0] + c1 d[r1] + c2 d[r2] + d[r3] as the SAME fma chains conv_wino4r_kernel's row_pass runs (one chain per row, innermost term
         // first): bit-identical t, hence bit-identical results in the fp32 kernel.  (A first version shared the even / odd parts of the +- rows,
         // 12 instead of 16 fmas per channel: the smooth fixture model's wrong-pixel total rose from 11 to 19 of ~15 hard pixels per image.)
         f32x2 o;

@@ -37,7 +37,7 @@ extern "C" {
  * ECSEG_COMM_TIMEOUT_S bounds ecseg_comm_create / ecseg_allgather_records*. */
 /* 5 (round 5): ecseg_meta_segment (pre-process + segment in one call), ecseg_prefetch_input, ecseg_host_alloc / ecseg_host_free
  * (page-locked host buffers); ecseg_create sets the device's scheduling flag to hipDeviceScheduleBlockingSync (see there). */
-/* (round 6, still 5 - additions a round-5 caller never triggers: option "winograd" = 3 and "wino4_rowpass"; ecseg_get_conv_launch_profile kinds 5 / 6
+/* (round 6, still 5 - additions a round-5 caller never triggers: option "winograd" = 3 (the round's second option, which selected the superseded F(4x4) kernel path, went with that path: the key fails as unknown); ecseg_get_conv_launch_profile kinds 5 / 6
  * (the split kernels); CONV ops read their so far unused `mode` word as the horizontal stride / dilation rate (0 = as before); CONVT kernels larger than
  * their stride run phase by phase.) */
 /* (still 5 - additive: ecseg_nuclei_regions and ecseg_nucleus_crops, the file-level interSeg driver; nothing existing changed.) */

@@ -451,21 +451,35 @@ def test_plan_of_classifier_graphs(kind, golden_dir):
 
 
 def test_shipped_library_has_no_diagnostic_kernels():
-    """the timing-only ablations and cycle stamps of conv_wino4_kernel live in csrc/wino4_diag.inc and exist
-    only in the -DECSEG_DIAG build; the product source contains one code path and the shipped library exactly the three
-    instantiations <HEAD, SPLIT> it launches."""
+    """VERDICT r02 #8, r06 "next round" 6: the shipped library holds exactly the F(4x4) kernels it launches - ONE conv_wino4_kernel (split-K
+    for a lone 32-channel output block, no template), conv_wino4r_kernel / conv_wino4s_kernel with and without the fused head - and
+    wino4_kernel.hip contains no timing-only ablation, cycle stamp or variant hook at all."""
     import re
     import shutil
     import subprocess
     from ecseg_amd._lib import LIB_PATH
     nm = shutil.which('nm') or '/opt/rocm/lib/llvm/bin/llvm-nm'
     out = subprocess.run([nm, '-C', LIB_PATH], capture_output=True, text=True, check=True).stdout
-    inst = sorted(set(re.findall(r' ecseg::conv_wino4_kernel<([^>]*)>\(', out)))
-    assert inst == ['false, false', 'false, true', 'true, false'], inst
+    w4 = sorted(set(re.findall(r' (?:void )?ecseg::(conv_wino4_kernel[^(]*)\(', out)))
+    assert w4 == ['conv_wino4_kernel'], w4
+    for name in ('conv_wino4r_kernel', 'conv_wino4s_kernel'):
+        inst = sorted(set(re.findall(r' ecseg::%s<([^>]*)>\(' % name, out)))
+        assert inst == ['false', 'true'], (name, inst)
     src = open(os.path.join(ROOT, 'ecseg_amd', 'csrc', 'wino4_kernel.hip')).read()
-    product = src.split('#ifdef ECSEG_DIAG')[0] + src.split('#endif', 1)[1]          # everything but the hook definitions
     for word in ('ABL', 'STAMP', 'W4_VARIANT', 's_memtime'):
-        assert word not in product.replace('W4_KSTAMP', '').replace('W4_ESTAMP', '').replace('WSTAMP', '').replace('ESTAMP', ''), word
+        assert word not in src, word
+
+
+def test_set_option_no_longer_knows_wino4_rowpass():
+    """The superseded non-split conv_wino4_kernel path went together with the option that selected it: ecseg_set_option has no
+    "wino4_rowpass" key any more (it fails like any unknown key) and no source of the library names the option."""
+    csrc = os.path.join(ROOT, 'ecseg_amd', 'csrc')
+    api = open(os.path.join(csrc, 'api.hip')).read()
+    body = api.split('int ecseg_set_option(', 1)[1].split('\n}\n', 1)[0]
+    assert '"wino4_split"' in body and 'unknown option or bad value' in body        # (the function this test means to read)
+    assert 'rowpass' not in body
+    for f in sorted(f for f in os.listdir(csrc) if f.endswith(('.hip', '.h', '.inc', '.cpp'))):
+        assert 'rowpass' not in open(os.path.join(csrc, f), errors='replace').read(), f
 
 
 def test_no_kernel_of_the_shipped_library_spills_registers():
