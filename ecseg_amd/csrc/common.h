@@ -16,7 +16,7 @@ struct TView {
 
 struct ConvParams {
     TView in, out;
-    const float* wt;    // re-laid-out kernel (see relayout_* in api.hip)
+    const float* wt;    // re-laid-out kernel (see relayout_* in filter_layout.hip)
     const float* bias;  // may be null
     int n;              // patches in the batch
     int R, S;           // taps
@@ -66,7 +66,7 @@ struct ConvParams {
     long wt_chunk_stride, wt_tap_stride;
 };
 
-// Winograd F(4x4,3x3) interpolation points {0, +-W4_PA, +-W4_PB, inf}, shared by the host filter transform (api.hip:
+// Winograd F(4x4,3x3) interpolation points {0, +-W4_PA, +-W4_PB, inf}, shared by the host filter transform (filter_layout.hip:
 // winograd4_filter) and the kernels' input / output transforms (wino4_consts.inc).  The textbook set is {0, +-1, +-2, inf};
 // the rounding error of the result is dominated by the float32 channel sum of the transformed products on the matrix cores,
 // whose magnitude the points set: tools/wino_points.py replays the kernel's arithmetic on the CPU and measures, against a
@@ -80,7 +80,7 @@ struct ConvParams {
 #endif
 constexpr double W4_PA = ECSEG_W4_PA, W4_PB = ECSEG_W4_PB;
 
-// pitches used by relayout_* (api.hip) and the kernels
+// pitches used by relayout_* (filter_layout.hip) and the kernels
 inline long wt_chunk_pitch(int np_total) { return (long)2 * np_total * 4 + 32; }
 inline long wt_tap_pitch(int np_total, int chunks) { return wt_chunk_pitch(np_total) * chunks + 96; }
 
@@ -93,12 +93,12 @@ int        conv_mfma_ntile(int cout);   // N tile (32 | 64 | 128) used for a giv
 hipError_t launch_conv_wino(const ConvParams& p, hipStream_t s);
 int        conv_wino_ntile(int cout);
 // Winograd F(2x2,3x3) for 16 / 32 input and output channels on 16x16x4 MFMAs (wino16_kernel.hip); p.wt = image written by
-// relayout_wino16 (api.hip)
+// relayout_wino16 (filter_layout.hip)
 hipError_t launch_conv_wino16(const ConvParams& p, hipStream_t s);
 bool       conv_wino16_supported(const ConvParams& p);
 bool       conv_wino16_first_supported(const ConvParams& p);   // with ConvParams::first_w: the network's first layer computed into the halo
 // Winograd F(4x4,3x3), split-K kernel for a lone 32-channel output block (wino4_kernel.hip: out.c == 32, no fused head; anything else is
-// hipErrorInvalidValue); p.wt = image written by winograd4_filter (api.hip)
+// hipErrorInvalidValue); p.wt = image written by winograd4_filter (filter_layout.hip)
 hipError_t launch_conv_wino4(const ConvParams& p, hipStream_t s);
 // eligibility rules shared by the three F(4x4) kernels
 bool       conv_wino4_supported(const ConvParams& p);

@@ -13,7 +13,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 // Activations of the Winograd kernels' output stages (conv_wino4 / conv_wino16: register-critical - the F(4x4) head variant
-// sits at its 168-VGPR ceiling): codes 0..6 with ELU's alpha = 1; api.hip sends anything else to the other kernels
+// sits at its 168-VGPR ceiling): codes 0..6 with ELU's alpha = 1; plan_run.hip sends anything else to the other kernels
 // (act_core_ok).
 __device__ __forceinline__ float apply_act_core(float v, int act, float alpha) {
     switch (act) {

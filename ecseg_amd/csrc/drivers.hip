@@ -1,0 +1,334 @@
+// The one-call drivers: each uploads its inputs, runs one family of kernels on the main stream and downloads the results
+// (u16_to_u8, stitch_argmax, meta_inference, the counts, overlay, the interSeg regions / crops, the FISH distances).
+#include "ctx.h"
+
+using namespace ecseg;
+
+extern "C" {
+
+int ecseg_u16_to_u8(ecseg_ctx* h, const uint16_t* in, long long count, uint8_t* out) {
+    if (!h) return ECSEG_E_INVALID;
+    drop_sent_ahead(h);
+    if (count < 0 || (count > 0 && (!in || !out))) return fail(h, ECSEG_E_INVALID, "u16_to_u8: bad arguments");
+    if (count == 0) return ECSEG_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    int rc;
+    if ((rc = h->d_aux8.ensure(h, (size_t)count * 2))) return rc;
+    if ((rc = h->d_gray.ensure(h, (size_t)count))) return rc;
+    hipStream_t s = h->stream;
+    HIP_TRY(h, hipMemcpyAsync(h->d_aux8, in, (size_t)count * 2, hipMemcpyHostToDevice, s));
+    HIP_TRY(h, launch_u16_to_u8(reinterpret_cast<const uint16_t*>(h->d_aux8.p), h->d_gray, (size_t)count, s));
+    HIP_TRY(h, hipMemcpyAsync(out, h->d_gray, (size_t)count, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    return ECSEG_OK;
+}
+
+int ecseg_stitch_argmax(ecseg_ctx* h, const float* probs, int n_img, int H, int W, uint8_t* labels_raw) {
+    if (!h) return ECSEG_E_INVALID;
+    drop_sent_ahead(h);
+    if (n_img < 0 || (n_img > 0 && (!probs || !labels_raw))) return fail(h, ECSEG_E_INVALID, "stitch_argmax: bad arguments");
+    if (n_img == 0) return ECSEG_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    StitchPlan* sp = nullptr;
+    int rc;
+    if ((rc = get_stitch(h, H, W, &sp))) return rc;
+    const size_t px = (size_t)H * W, nfl = (size_t)n_img * sp->n_pos * 65536 * 4;
+    if ((rc = h->d_probs_in.ensure(h, nfl))) return rc;
+    if ((rc = h->d_raw.ensure(h, px * n_img))) return rc;
+    hipStream_t s = h->stream;
+    HIP_TRY(h, hipMemcpyAsync(h->d_probs_in, probs, nfl * sizeof(float), hipMemcpyHostToDevice, s));
+    HIP_TRY(h, launch_stitch_argmax(h->d_probs_in, 4, sp->map_dev, n_img, sp->n_pos, H, W, h->d_raw, s));
+    HIP_TRY(h, hipMemcpyAsync(labels_raw, h->d_raw, px * n_img, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    return ECSEG_OK;
+}
+
+int ecseg_meta_inference_dev(ecseg_ctx* h, const uint8_t* in, int n_img, int H, int W, uint8_t* out, int32_t* n_ec) {
+    if (!h) return ECSEG_E_INVALID;
+    drop_sent_ahead(h);
+    if (n_img < 0 || H <= 0 || W <= 0 || (n_img > 0 && (!in || !out))) return fail(h, ECSEG_E_INVALID, "meta_inference: bad arguments");
+    if (n_img == 0) return ECSEG_OK;
+    if ((long long)H * W >= (1ll << 31)) return fail(h, ECSEG_E_INVALID, "image too large");
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t px = (size_t)H * W;
+    int rc;
+    if ((rc = ensure_post(h, std::min(n_img, h->post_chunk), px))) return rc;
+    hipStream_t s = h->stream;
+    if (out != in) HIP_TRY(h, hipMemcpyAsync(out, in, px * n_img, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(h, hipEventRecord(h->ev[0], s));
+    for (int i0 = 0; i0 < n_img; i0 += h->post_chunk) {
+        const int ni = std::min(h->post_chunk, n_img - i0);
+        HIP_TRY(h, run_meta_inference(h->ws, out + (size_t)i0 * px, ni, H, W, n_ec ? n_ec + i0 : nullptr, s));
+    }
+    HIP_TRY(h, hipEventRecord(h->ev[1], s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    for (float& v : h->stage_ms) v = 0.f;
+    h->stage_ms[ECSEG_T_POST] = stage_elapsed(h->ev[0], h->ev[1]);
+    return ECSEG_OK;
+}
+
+int ecseg_meta_inference(ecseg_ctx* h, const uint8_t* in, int n_img, int H, int W, uint8_t* out, int32_t* n_ec) {
+    if (!h) return ECSEG_E_INVALID;
+    drop_sent_ahead(h);
+    if (n_img < 0 || H <= 0 || W <= 0 || (n_img > 0 && (!in || !out))) return fail(h, ECSEG_E_INVALID, "meta_inference: bad arguments");
+    if (n_img == 0) return ECSEG_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t tot = (size_t)H * W * n_img;
+    int rc;
+    if ((rc = h->d_post.ensure(h, tot))) return rc;
+    if ((rc = h->d_i32.ensure(h, (size_t)n_img))) return rc;
+    HIP_TRY(h, hipMemcpyAsync(h->d_post, in, tot, hipMemcpyHostToDevice, h->stream));
+    if ((rc = ecseg_meta_inference_dev(h, h->d_post, n_img, H, W, h->d_post, h->d_i32))) return rc;
+    HIP_TRY(h, hipMemcpyAsync(out, h->d_post, tot, hipMemcpyDeviceToHost, h->stream));
+    if (n_ec) HIP_TRY(h, hipMemcpyAsync(n_ec, h->d_i32, (size_t)n_img * 4, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return ECSEG_OK;
+}
+
+// shared driver of the mask-counting entry points: uploads one or two mask stacks, chunks over images
+static int count_driver(ecseg_ctx* h, const uint8_t* a, const uint8_t* b, int n_img, int H, int W, int kind, int arg,
+                        int32_t* n_out, int64_t* px_out, int32_t* labels_out) {
+    if (!h) return ECSEG_E_INVALID;
+    drop_sent_ahead(h);
+    if (n_img < 0 || H <= 0 || W <= 0 || (n_img > 0 && !a)) return fail(h, ECSEG_E_INVALID, "count: bad arguments");
+    if (n_img == 0) return ECSEG_OK;
+    if ((long long)H * W >= (1ll << 31)) return fail(h, ECSEG_E_INVALID, "image too large");
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t px = (size_t)H * W;
+    const int chunk = h->post_chunk;
+    int rc;
+    if ((rc = ensure_post(h, std::min(n_img, chunk), px))) return rc;
+    if ((rc = h->d_gray.ensure(h, px * std::min(n_img, chunk)))) return rc;
+    if (b && (rc = h->d_aux8.ensure(h, px * std::min(n_img, chunk)))) return rc;
+    if ((rc = h->d_i32.ensure(h, labels_out ? px * std::min(n_img, chunk) : (size_t)chunk))) return rc;
+    if ((rc = h->d_i64.ensure(h, (size_t)chunk))) return rc;
+    hipStream_t s = h->stream;
+    for (float& v : h->stage_ms) v = 0.f;
+    for (int i0 = 0; i0 < n_img; i0 += chunk) {
+        const int ni = std::min(chunk, n_img - i0);
+        HIP_TRY(h, hipMemcpyAsync(h->d_gray, a + (size_t)i0 * px, px * ni, hipMemcpyHostToDevice, s));
+        if (b) HIP_TRY(h, hipMemcpyAsync(h->d_aux8, b + (size_t)i0 * px, px * ni, hipMemcpyHostToDevice, s));
+        hipError_t e = hipSuccess;
+        HIP_TRY(h, hipEventRecord(h->ev[0], s));
+        if (kind == 0) e = run_count_cc(h->ws, h->d_gray, ni, H, W, h->d_i32, h->d_i64, s);
+        else if (kind == 1) e = run_count_coloc(h->ws, h->d_gray, h->d_aux8, ni, H, W, h->d_i32, s);
+        else if (kind == 2) e = run_count_hsr(h->ws, h->d_gray, h->d_aux8, ni, H, W, arg, h->d_i32, s);
+        else e = run_ccl_labels(h->ws, h->d_gray, ni, H, W, arg, h->d_i32, s);
+        if (e != hipSuccess) return fail_hip(h, e, "count kernels");
+        HIP_TRY(h, hipEventRecord(h->ev[1], s));
+        if (labels_out) HIP_TRY(h, hipMemcpyAsync(labels_out + (size_t)i0 * px, h->d_i32, px * ni * 4, hipMemcpyDeviceToHost, s));
+        else if (n_out) HIP_TRY(h, hipMemcpyAsync(n_out + i0, h->d_i32, (size_t)ni * 4, hipMemcpyDeviceToHost, s));
+        if (px_out) HIP_TRY(h, hipMemcpyAsync(px_out + i0, h->d_i64, (size_t)ni * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipStreamSynchronize(s));
+        h->stage_ms[ECSEG_T_COUNT] += stage_elapsed(h->ev[0], h->ev[1]);
+    }
+    return ECSEG_OK;
+}
+
+int ecseg_count_cc(ecseg_ctx* h, const uint8_t* mask, int n_img, int H, int W, int32_t* n_out, int64_t* px_out) {
+    return count_driver(h, mask, nullptr, n_img, H, W, 0, 0, n_out, px_out, nullptr);
+}
+int ecseg_ccl_labels(ecseg_ctx* h, const uint8_t* mask, int n_img, int H, int W, int connectivity, int32_t* labels_out) {
+    if (h && connectivity != 4 && connectivity != 8) return fail(h, ECSEG_E_INVALID, "connectivity must be 4 or 8");
+    if (h && n_img > 0 && !labels_out) return fail(h, ECSEG_E_INVALID, "labels_out is NULL");
+    return count_driver(h, mask, nullptr, n_img, H, W, 3, connectivity, nullptr, nullptr, labels_out);
+}
+int ecseg_count_colocalization(ecseg_ctx* h, const uint8_t* ob1, const uint8_t* ob2, int n_img, int H, int W, int32_t* n_out) {
+    if (h && n_img > 0 && !ob2) return fail(h, ECSEG_E_INVALID, "ob2 is NULL");
+    return count_driver(h, ob1, ob2, n_img, H, W, 1, 0, n_out, nullptr, nullptr);
+}
+int ecseg_count_hsr(ecseg_ctx* h, const uint8_t* chrom, const uint8_t* fish, int n_img, int H, int W, int thr, int32_t* n_out) {
+    if (h && n_img > 0 && !fish) return fail(h, ECSEG_E_INVALID, "fish is NULL");
+    return count_driver(h, chrom, fish, n_img, H, W, 2, thr, n_out, nullptr, nullptr);
+}
+
+int ecseg_overlay(ecseg_ctx* h, const uint8_t* labels, const uint8_t* rgb, int n_img, int H, int W, int C, int sens, int hsr_thr,
+                  int64_t* out) {
+    if (!h) return ECSEG_E_INVALID;
+    drop_sent_ahead(h);
+    if (n_img < 0 || H <= 0 || W <= 0 || C < 2 || (n_img > 0 && (!labels || !rgb || !out)))
+        return fail(h, ECSEG_E_INVALID, "overlay: bad arguments");
+    if (n_img == 0) return ECSEG_OK;
+    if ((long long)H * W >= (1ll << 31)) return fail(h, ECSEG_E_INVALID, "image too large");
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t px = (size_t)H * W;
+    const int chunk = h->post_chunk;
+    int rc;
+    if ((rc = ensure_post(h, std::min(n_img, chunk), px))) return rc;
+    if ((rc = h->d_gray.ensure(h, px * std::min(n_img, chunk)))) return rc;
+    if ((rc = h->d_aux8.ensure(h, px * C * std::min(n_img, chunk)))) return rc;
+    if ((rc = h->d_i64.ensure(h, (size_t)chunk * 12))) return rc;
+    hipStream_t s = h->stream;
+    for (float& v : h->stage_ms) v = 0.f;
+    for (int i0 = 0; i0 < n_img; i0 += chunk) {
+        const int ni = std::min(chunk, n_img - i0);
+        HIP_TRY(h, hipMemcpyAsync(h->d_gray, labels + (size_t)i0 * px, px * ni, hipMemcpyHostToDevice, s));
+        HIP_TRY(h, hipMemcpyAsync(h->d_aux8, rgb + (size_t)i0 * px * C, px * C * ni, hipMemcpyHostToDevice, s));
+        HIP_TRY(h, hipEventRecord(h->ev[0], s));             // the kernels alone (inputs resident): ecseg_get_timings()[ECSEG_T_COUNT]
+        HIP_TRY(h, run_overlay(h->ws, h->d_gray, h->d_aux8, ni, H, W, C, sens, hsr_thr, h->d_i64, s));
+        HIP_TRY(h, hipEventRecord(h->ev[1], s));
+        HIP_TRY(h, hipMemcpyAsync(out + (size_t)i0 * 12, h->d_i64, (size_t)ni * 12 * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipStreamSynchronize(s));
+        h->stage_ms[ECSEG_T_COUNT] += stage_elapsed(h->ev[0], h->ev[1]);
+    }
+    return ECSEG_OK;
+}
+
+// ---- interSeg driver (src/interseg.py:113-235) ----------------------------------------------------------------------
+int ecseg_nuclei_regions(ecseg_ctx* h, const uint8_t* seg, int H, int W, const uint8_t* img, int img_h, int img_w, int C,
+                         int channel0, int capacity, int64_t* records, int32_t* n_regions) {
+    if (!h) return ECSEG_E_INVALID;
+    drop_sent_ahead(h);
+    h->iseg_n = -1;
+    if (!seg || !img || !n_regions || H <= 0 || W <= 0 || img_h < H || img_w < W || C < 1 || channel0 < 0 || channel0 >= C ||
+        capacity < 0 || (capacity > 0 && !records))
+        return fail(h, ECSEG_E_INVALID, "nuclei_regions: bad arguments (the segmentation must not be larger than the image)");
+    if ((long long)H * W >= (1ll << 31) || (long long)H * img_w * C >= (1ll << 40)) return fail(h, ECSEG_E_INVALID, "image too large");
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t px = (size_t)H * W, img_bytes = (size_t)H * img_w * C;
+    const size_t nb = (px + 1023) / 1024, cap = (size_t)capacity;
+    int rc;
+    if ((rc = ensure_post(h, 1, px))) return rc;
+    if ((rc = h->d_gray.ensure(h, px))) return rc;
+    if ((rc = h->d_iseg_lab.ensure(h, px))) return rc;
+    if ((rc = h->d_iseg_img.ensure(h, img_bytes))) return rc;
+    if ((rc = h->d_iseg_rid.ensure(h, px))) return rc;
+    if ((rc = h->d_iseg_blk.ensure(h, nb))) return rc;
+    if ((rc = h->d_iseg_misc.ensure(h, 4))) return rc;
+    if ((rc = h->d_iseg_acc.ensure(h, cap * 4))) return rc;
+    if ((rc = h->d_iseg_bb.ensure(h, cap * 4))) return rc;
+    if ((rc = h->d_iseg_rec.ensure(h, cap * 8))) return rc;
+    hipStream_t s = h->stream;
+    for (float& v : h->stage_ms) v = 0.f;
+    HIP_TRY(h, hipMemcpyAsync(h->d_gray, seg, px, hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(h->d_iseg_img, img, img_bytes, hipMemcpyHostToDevice, s));   // the first H rows: I[:imheight, :imwidth]
+    HIP_TRY(h, hipEventRecord(h->ev[0], s));
+    HIP_TRY(h, run_ccl_labels(h->ws, h->d_gray, 1, H, W, 8, h->d_iseg_lab, s));
+    const RegionBufs b{h->d_iseg_rid, h->d_iseg_blk, h->d_iseg_misc, h->d_iseg_acc, h->d_iseg_bb, h->d_iseg_rec, capacity};
+    HIP_TRY(h, run_nuclei_regions(h->d_gray, h->d_iseg_img, H, W, img_w, C, channel0, h->d_iseg_lab, b, s));
+    HIP_TRY(h, hipEventRecord(h->ev[1], s));
+    int32_t misc[4];
+    HIP_TRY(h, hipMemcpyAsync(misc, h->d_iseg_misc, sizeof(misc), hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    h->stage_ms[ECSEG_T_COUNT] = stage_elapsed(h->ev[0], h->ev[1]);
+    const int n = misc[0], vmax = misc[1], vmin = 255 - misc[2];
+    if (n > 0 && vmin != vmax)
+        return fail(h, ECSEG_E_INVALID, "segmentation holds the non-zero values " + std::to_string(vmin) + " .. " + std::to_string(vmax) +
+                                            ": only 0 / non-zero nucleus masks are supported, not instance-id maps");
+    *n_regions = n;
+    if (n <= capacity && n > 0) {
+        HIP_TRY(h, hipMemcpyAsync(records, h->d_iseg_rec, (size_t)n * 8 * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipStreamSynchronize(s));
+    }
+    h->iseg_H = H; h->iseg_W = W; h->iseg_img_w = img_w; h->iseg_C = C; h->iseg_n = n;
+    return ECSEG_OK;
+}
+
+int ecseg_nucleus_crops(ecseg_ctx* h, const int32_t* crops, int n_crops, const int32_t* channel_order, uint8_t* out,
+                        int32_t* channel_max) {
+    if (!h) return ECSEG_E_INVALID;
+    drop_sent_ahead(h);
+    if (n_crops < 0 || (n_crops > 0 && (!crops || !channel_order || !out || !channel_max)))
+        return fail(h, ECSEG_E_INVALID, "nucleus_crops: bad arguments");
+    if (n_crops == 0) return ECSEG_OK;
+    if (h->iseg_n < 0) return fail(h, ECSEG_E_INVALID, "nucleus_crops: no region map on the handle (call ecseg_nuclei_regions first)");
+    int order[3];
+    for (int c = 0; c < 3; ++c) {
+        order[c] = channel_order[c];
+        if (order[c] < 0 || order[c] >= h->iseg_C) return fail(h, ECSEG_E_INVALID, "nucleus_crops: channel_order out of range");
+    }
+    for (int k = 0; k < n_crops; ++k) {
+        const int32_t* d = crops + (size_t)k * 5;
+        if (d[0] < 0 || d[0] >= h->iseg_n || d[1] < 0 || d[2] < 0 || d[3] < 1 || d[3] > 256 || d[4] < 1 || d[4] > 256 ||
+            d[1] > h->iseg_H - d[3] || d[2] > h->iseg_W - d[4])
+            return fail(h, ECSEG_E_INVALID, "nucleus_crops: crop " + std::to_string(k) + " is not a 1..256 x 1..256 window of a region");
+    }
+    HIP_TRY(h, hipSetDevice(h->device));
+    const int chunk = 256;                                   // 48 MiB of crops per launch
+    const size_t crop_bytes = (size_t)256 * 256 * 3;
+    const int nc = std::min(n_crops, chunk);
+    int rc;
+    if ((rc = h->d_iseg_desc.ensure(h, (size_t)nc * 5))) return rc;
+    if ((rc = h->d_iseg_crops.ensure(h, (size_t)nc * crop_bytes))) return rc;
+    if ((rc = h->d_iseg_max.ensure(h, (size_t)nc * 3))) return rc;
+    hipStream_t s = h->stream;
+    for (float& v : h->stage_ms) v = 0.f;
+    for (int k0 = 0; k0 < n_crops; k0 += chunk) {
+        const int k = std::min(chunk, n_crops - k0);
+        HIP_TRY(h, hipMemcpyAsync(h->d_iseg_desc, crops + (size_t)k0 * 5, (size_t)k * 5 * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        HIP_TRY(h, hipEventRecord(h->ev[0], s));
+        HIP_TRY(h, run_nucleus_crops(h->d_iseg_lab, h->d_iseg_img, h->iseg_W, h->iseg_img_w, h->iseg_C, h->d_iseg_desc, k, order,
+                                     h->d_iseg_crops, h->d_iseg_max, s));
+        HIP_TRY(h, hipEventRecord(h->ev[1], s));
+        HIP_TRY(h, hipMemcpyAsync(out + (size_t)k0 * crop_bytes, h->d_iseg_crops, (size_t)k * crop_bytes, hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipMemcpyAsync(channel_max + (size_t)k0 * 3, h->d_iseg_max, (size_t)k * 3 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipStreamSynchronize(s));
+        h->stage_ms[ECSEG_T_COUNT] += stage_elapsed(h->ev[0], h->ev[1]);
+    }
+    return ECSEG_OK;
+}
+
+// ---- fish_distance_calculation (src/fish_distance_calculation.py:16-46) ---------------------------------------------------
+int ecseg_fish_distances(ecseg_ctx* h, const int32_t* labels, int H, int W, const uint8_t* lsq, int C, int fish_channel,
+                         int centromere_channel, int capacity, int64_t* records, int32_t* n_cells) {
+    if (!h) return ECSEG_E_INVALID;
+    drop_sent_ahead(h);
+    if (n_cells) *n_cells = 0;
+    if (!labels || !lsq || !n_cells || H <= 0 || W <= 0 || capacity < 0 || (capacity > 0 && !records))
+        return fail(h, ECSEG_E_INVALID, "fish_distances: bad arguments");
+    if (C < 2) return fail(h, ECSEG_E_INVALID, "fish_distances: the lsq image needs at least 2 channels (the gate reads channels 0 and 1)");
+    if (fish_channel < 0 || fish_channel >= C || centromere_channel < 0 || centromere_channel >= C)
+        return fail(h, ECSEG_E_INVALID, "fish_distances: channel out of range (the lsq image has " + std::to_string(C) + " channels)");
+    if ((long long)H * W >= (1ll << 31) || (long long)H * W * C >= (1ll << 40))
+        return fail(h, ECSEG_E_INVALID, "fish_distances: image too large (H * W must be below 2^31, H * W * C below 2^40)");
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t px = (size_t)H * W;
+    int rc;
+    if ((rc = h->d_fd_lab.ensure(h, px))) return rc;
+    if ((rc = h->d_fd_lsq.ensure(h, px * C))) return rc;
+    if ((rc = h->d_fd_rid.ensure(h, px))) return rc;
+    if ((rc = h->d_fd_blk.ensure(h, (px + 1023) / 1024))) return rc;
+    if ((rc = h->d_fd_misc.ensure(h, 4))) return rc;
+    hipStream_t s = h->stream;
+    for (float& v : h->stage_ms) v = 0.f;
+    HIP_TRY(h, hipMemcpyAsync(h->d_fd_lab, labels, px * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(h->d_fd_lsq, lsq, px * C, hipMemcpyHostToDevice, s));
+    FishDistBufs b{h->d_fd_rid, nullptr, h->d_fd_blk, h->d_fd_misc, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    HIP_TRY(h, hipEventRecord(h->ev[0], s));
+    HIP_TRY(h, run_fishdist_cells(h->d_fd_lab, H, W, b, s));
+    HIP_TRY(h, hipEventRecord(h->ev[1], s));
+    int32_t misc[4];
+    HIP_TRY(h, hipMemcpyAsync(misc, h->d_fd_misc, sizeof(misc), hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    h->stage_ms[ECSEG_T_COUNT] = stage_elapsed(h->ev[0], h->ev[1]);
+    if (misc[3])
+        return fail(h, ECSEG_E_INVALID, "fish_distances: the label map holds a label larger than H * W = " + std::to_string(px) +
+                                            " (renumber the labels by rank first)");
+    const int n = misc[0];
+    *n_cells = n;
+    if (n == 0 || n > capacity) return ECSEG_OK;             // the cell count alone: the caller comes back with a larger buffer
+    // the rest is sized by the number of cells, which is known only now
+    const size_t nn = (size_t)n;
+    if ((rc = h->d_fd_par.ensure(h, px))) return rc;
+    if ((rc = h->d_fd_flist.ensure(h, px))) return rc;
+    if ((rc = h->d_fd_clist.ensure(h, px))) return rc;
+    if ((rc = h->d_fd_acc.ensure(h, nn * 4))) return rc;
+    if ((rc = h->d_fd_val.ensure(h, nn))) return rc;
+    if ((rc = h->d_fd_off.ensure(h, nn * 2))) return rc;
+    if ((rc = h->d_fd_cur.ensure(h, nn * 2))) return rc;
+    if ((rc = h->d_fd_rec.ensure(h, nn * 8))) return rc;
+    const size_t parts = nn * (size_t)fishdist_slices(n);
+    if ((rc = h->d_fd_pbest.ensure(h, parts))) return rc;
+    if ((rc = h->d_fd_proots.ensure(h, parts))) return rc;
+    b = FishDistBufs{h->d_fd_rid, h->d_fd_par, h->d_fd_blk, h->d_fd_misc, h->d_fd_flist, h->d_fd_clist, h->d_fd_acc, h->d_fd_val,
+                     h->d_fd_off, h->d_fd_cur, h->d_fd_rec, h->d_fd_pbest, h->d_fd_proots};
+    HIP_TRY(h, hipEventRecord(h->ev[2], s));
+    HIP_TRY(h, run_fishdist_records(h->d_fd_lab, h->d_fd_lsq, H, W, C, fish_channel, centromere_channel, n, b, s));
+    HIP_TRY(h, hipEventRecord(h->ev[3], s));
+    HIP_TRY(h, hipMemcpyAsync(records, h->d_fd_rec, nn * 8 * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    h->stage_ms[ECSEG_T_COUNT] += stage_elapsed(h->ev[2], h->ev[3]);
+    return ECSEG_OK;
+}
+
+}  // extern "C"

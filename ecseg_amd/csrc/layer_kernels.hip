@@ -23,7 +23,7 @@ namespace ecseg {
 //
 //   M = output pixels (lane & 31 -> pixel of the wave's 32-pixel strip), N = output channels, K = (tap, input channel);
 //   one MFMA (v_mfma_f32_32x32x2_f32) consumes channels {e, 4 + e} of a chunk, so one ds_read_b128 per operand feeds four.
-// LDS: As[kc][half][128 pixels][4 ch], Bs[kc][half][BN][4 ch]; global filter layout = relayout_conv (api.hip):
+// LDS: As[kc][half][128 pixels][4 ch], Bs[kc][half][BN][4 ch]; global filter layout = relayout_conv (filter_layout.hip):
 // wt[tap][chunk][half][N padded][4].
 // ------------------------------------------------------------------------------------------------------------
 template <int NT, int TW>

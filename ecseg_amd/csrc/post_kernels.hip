@@ -1198,7 +1198,7 @@ hipError_t run_meta_inference(PostWorkspace& ws, uint8_t* img, int n_img, int H,
     const dim3 ig4 = img_grid(px / 4, n_img);
     hipError_t e;
     // one counter block per labelling that produces counters, all zeroed here: no zeroing / folding launches in between
-    // (a kernel, not hipMemsetAsync: replayed from a HIP graph - option post_graph - the memset node of ROCm 7.2 was not ordered
+    // (a kernel, not hipMemsetAsync: when these launches were replayed from a captured graph, the memset node of ROCm 7.2 was not ordered
     // before the kernels behind it and zeroed list counters in mid-use: a memory fault on speckled images, round 5)
     const size_t gslot = (size_t)ws.cap_img * G_IMG;
     {

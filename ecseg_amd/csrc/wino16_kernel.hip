@@ -337,7 +337,7 @@ __global__ __launch_bounds__(512, (NBUF == 1 ? 4 : 2)) void conv_wino16_kernel(C
                         f32x4 Y[2];
                         Y[0] = apply_act4_core(R[0] + R[1] + R[2] + bv[nb], p.act, p.alpha);
                         Y[1] = apply_act4_core(R[1] - R[2] - R[3] + bv[nb], p.act, p.alpha);
-                        if (!HEAD) {             // (a fused head is always the only reader: api.hip sets head_only with head_w; launch_conv_wino16 checks)
+                        if (!HEAD) {             // (a fused head is always the only reader: plan_run.hip sets head_only with head_w; launch_conv_wino16 checks)
 #pragma unroll
                             for (int yy = 0; yy < 2; ++yy)
                                 if (oy + yy < H && ox + x < W)
@@ -358,7 +358,7 @@ __global__ __launch_bounds__(512, (NBUF == 1 ? 4 : 2)) void conv_wino16_kernel(C
                         for (int c = 0; c < 4; ++c) mx[c] = x == 0 ? fmaxf(Y[0][c], Y[1][c]) : fmaxf(mx[c], fmaxf(Y[0][c], Y[1][c]));
                         if (HEAD) __builtin_amdgcn_sched_barrier(0);
                     }
-                    if (!HEAD && p.pool.p != nullptr && (oy >> 1) < p.pool.h && (ox >> 1) < p.pool.w)     // (never both: api.hip fuses a head only where no pool is)
+                    if (!HEAD && p.pool.p != nullptr && (oy >> 1) < p.pool.h && (ox >> 1) < p.pool.w)     // (never both: plan_run.hip fuses a head only where no pool is)
                         *reinterpret_cast<f32x4*>(p.pool.p + (((size_t)img * p.pool.h + (oy >> 1)) * p.pool.w + (ox >> 1)) * p.pool.cs + co) = mx;
                 }
                             if (HEAD) {

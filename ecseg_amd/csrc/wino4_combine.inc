@@ -76,7 +76,7 @@
                     for (int c = 0; c < 4; ++c)
                         hl[k][yy][c] += y[yy][0] * w0[c] + y[yy][1] * w1[c] + y[yy][2] * w2[c] + y[yy][3] * w3[c];
             }
-            if (!HEAD && p.pool.p != nullptr) {             // (never with a fused head: api.hip fuses a head only where no pool is)
+            if (!HEAD && p.pool.p != nullptr) {             // (never with a fused head: plan_run.hip fuses a head only where no pool is)
                 // fused MaxPooling2D(2x2, stride 2): the row pairs are in registers, the column partner (cx ^ 1) is lane ^ 8 of
                 // the same tile, hence of the same region: it is active whenever this lane is
                 float* pb = p.pool.p + (((size_t)img * p.pool.h + (oy >> 1)) * p.pool.w + (ox >> 1)) * p.pool.cs;

@@ -4,7 +4,7 @@
 //
 //   Y = A^T [ sum_cin (G g G^T) .* (B^T d B) ] A        d: 6x6 input tile, g: 3x3 filter, Y: 4x4 outputs
 //
-// The filter transform U = G g G^T is done once at model load (float64 on the host, api.hip: winograd4_filter).
+// The filter transform U = G g G^T is done once at model load (float64 on the host, filter_layout.hip: winograd4_filter).
 //
 // Workgroup = 12 waves = 2 regions of 16x16 output pixels (32 Winograd tiles = the MFMA M dimension) x 64 output
 // channels.  Wave w = (channel half ch = w / 6, transform ROW xi = w % 6).  Per 8-channel group all 768 threads turn the raw

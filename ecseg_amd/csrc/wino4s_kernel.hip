@@ -400,7 +400,7 @@ __global__ __launch_bounds__(768) void conv_wino4s_kernel(ConvParams p, int regs
 #include "wino4_head.inc"
 }
 
-// The fp32 image of winograd4_filter (api.hip) -> the bf16x3 stage image of conv_wino4s_kernel; one thread per (block, stage, wave,
+// The fp32 image of winograd4_filter (filter_layout.hip) -> the bf16x3 stage image of conv_wino4s_kernel; one thread per (block, stage, wave,
 // column block, lane): 4 channels x 3 pieces.
 __global__ __launch_bounds__(256) void wino4s_filter_kernel(const float* __restrict__ src, unsigned short* __restrict__ dst, int nblk, int ngroups) {
     const long long id = (long long)blockIdx.x * 256 + threadIdx.x;

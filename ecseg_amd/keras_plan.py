@@ -841,7 +841,7 @@ def build_plan(model_config, weights, input_hw=(256, 256), fuse=True, lambda_ove
         last_use[i] = max(last_use.get(i, i), last_use.get(j, j))
 
     # a 2x2 max-pool that directly follows its producing convolution may be written by that convolution's output stage
-    # (csrc/api.hip run_plan): the convolution's input must then still be alive when the pool's buffer is chosen
+    # (csrc/plan_run.hip run_plan): the convolution's input must then still be alive when the pool's buffer is chosen
     # ... and likewise a 1x1 convolution (the head) that directly follows a convolution may be finished by that
     # convolution's output stage: its output buffer must differ from the producing convolution's INPUT buffer, which other
     # workgroups are still reading
@@ -880,7 +880,7 @@ def build_plan(model_config, weights, input_hw=(256, 256), fuse=True, lambda_ove
         if j not in node_buf:
             h, w, c = nodes[j]['shape']
             # the model output gets a buffer of its own (and the input's is never re-used, below): the window lanes of
-            # csrc/api.hip run_plan address both in plain window order, whatever else a lane packs into shared buffers
+            # csrc/plan_run.hip run_plan address both in plain window order, whatever else a lane packs into shared buffers
             node_buf[j] = alloc(h * w * c, fresh=(j == out_node))
         return node_buf[j], 0, nodes[j]['shape'][2]
 

@@ -196,9 +196,7 @@ int ecseg_set_images_per_group(ecseg_ctx* h, int n);
  * a launch group of <= 70 windows (one or two 1040x1392 images) runs its U-Net as two window lanes on their own streams, which fills
  * the half-empty last round of workgroups of the deep layers (one image: 11.3 -> 10.4 ms); 1..8: that many lanes; results are
  * bit-identical for every value), "blocking_wait" (1 (default): the wait for a launch group sleeps on an event created
- * with hipEventBlockingSync; 0: hipStreamSynchronize), "post_graph" (1: the
- * ~60 short kernels of meta_inference + count are captured once per (buffers, geometry) into a HIP graph and replayed;
- * 0 (default): plain launches - measured equal, the asynchronous launch queue already hides the launch gaps). */
+ * with hipEventBlockingSync; 0: hipStreamSynchronize). */
 int ecseg_set_option(ecseg_ctx* h, const char* key, int value);
 
 /* ---- meta_preprocess (src/image_tools.py:86-101) ---------------------------------------------------------- */

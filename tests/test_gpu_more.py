@@ -222,7 +222,7 @@ def test_device_timers_of_overlay_and_preprocess(gpu):
 
 @pytest.mark.parametrize('base,up', [(16, 'transpose'), (32, 'transpose'), (64, 'transpose')])
 def test_window_lanes_do_not_change_results(gpu, base, up):
-    """Small batches run the U-Net as several window lanes on their own streams (api.hip: run_plan - a lane is whole images,
+    """Small batches run the U-Net as several window lanes on their own streams (plan_run.hip: run_plan - a lane is whole images,
     or a slice of ONE image's windows with the matching slice of every crop list); same kernels, same per-window arithmetic:
     raw labels, cleaned labels, counts and the stitched probabilities are bit-identical for every lane count."""
     cfg = synth.unet_config(base=base, up=up)

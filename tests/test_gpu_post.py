@@ -173,25 +173,21 @@ def test_preprocess_vs_oracle(gpu):
         assert np.array_equal(gray[i], preprocess.meta_preprocess(g16[i])), i
 
 
-def test_meta_inference_through_hip_graph_replay(gpu):
-    """Option post_graph=1: the kernels of meta_inference captured into a HIP graph and replayed must give the same labels
-    and counts as plain launches, also when the same buffers are used again with new contents."""
+def test_meta_inference_same_buffers_again_with_new_contents(gpu):
+    """meta_inference called again on the handle's same device buffers with new contents (the input rolled by 7 and 14 columns)
+    gives the oracle's labels and counts every time; the unrolled input gives what the first call gave.  (The option that replayed
+    these launches from a captured HIP graph is retired: the launches are plain.)"""
     labs = np.stack([synth.label_map(400 + i, 300, 420) for i in range(3)])
     plain, nec_plain = gpu.meta_inference(labs)
-    try:
-        gpu.set_option('post_graph', 1)
-        for rep in range(3):
-            x = np.roll(labs, rep * 7, axis=2)
-            got, nec = gpu.meta_inference(x)
-            want, wnec = (plain, nec_plain) if rep == 0 else (None, None)
-            for k in range(3):
-                w = postproc.meta_inference(x[k])
-                assert np.array_equal(got[k], w)
-                assert int(nec[k]) == postproc.count_cc(w == 3)[0]
-            if want is not None:
-                assert np.array_equal(got, want) and np.array_equal(nec, wnec)
-    finally:
-        gpu.set_option('post_graph', 0)
+    for rep in range(3):
+        x = np.roll(labs, rep * 7, axis=2)
+        got, nec = gpu.meta_inference(x)
+        for k in range(3):
+            w = postproc.meta_inference(x[k])
+            assert np.array_equal(got[k], w)
+            assert int(nec[k]) == postproc.count_cc(w == 3)[0]
+        if rep == 0:
+            assert np.array_equal(got, plain) and np.array_equal(nec, nec_plain)
 
 
 def test_nucleus_test_binned_and_pair_paths(gpu):

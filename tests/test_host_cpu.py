@@ -115,7 +115,7 @@ def test_plan_of_canonical_unet(base, up, bn):
                     assert np.allclose(k3[1, 1], k2.sum((0, 1)).T, atol=1e-6) and np.allclose(k3[0, 0], k2[1, 1].T) and np.allclose(k3[2, 1], (k2[0, 0] + k2[0, 1]).T, atol=1e-6)
         elif up == 'upsample':
             assert sum(1 for o in plan.ops if o['op'] == keras_plan.OP_UPSAMPLE) == 4
-        # window lanes (csrc/api.hip run_plan) address the model input and output in plain window order while every other
+        # window lanes (csrc/plan_run.hip run_plan) address the model input and output in plain window order while every other
         # tensor is packed into a lane's private slice of its buffer: the two must have buffers of their own
         for io in (plan.input_tensor, plan.output_tensor):
             b = plan.tensors[io]['buffer']
@@ -472,14 +472,16 @@ def test_shipped_library_has_no_diagnostic_kernels():
 
 def test_set_option_no_longer_knows_wino4_rowpass():
     """The superseded non-split conv_wino4_kernel path went together with the option that selected it: ecseg_set_option has no
-    "wino4_rowpass" key any more (it fails like any unknown key) and no source of the library names the option."""
+    "wino4_rowpass" key any more (it fails like any unknown key) and no source of the library names the option.  The same holds for
+    "post_graph" (meta_inference replayed from a captured HIP graph: measured +-0 %, retired with its graph cache)."""
     csrc = os.path.join(ROOT, 'ecseg_amd', 'csrc')
-    api = open(os.path.join(csrc, 'api.hip')).read()
+    api = open(os.path.join(csrc, 'api.hip')).read()          # (the handle's options live with its life cycle)
     body = api.split('int ecseg_set_option(', 1)[1].split('\n}\n', 1)[0]
     assert '"wino4_split"' in body and 'unknown option or bad value' in body        # (the function this test means to read)
-    assert 'rowpass' not in body
-    for f in sorted(f for f in os.listdir(csrc) if f.endswith(('.hip', '.h', '.inc', '.cpp'))):
-        assert 'rowpass' not in open(os.path.join(csrc, f), errors='replace').read(), f
+    for retired in ('rowpass', 'post_graph'):
+        assert retired not in body
+        for f in sorted(f for f in os.listdir(csrc) if f.endswith(('.hip', '.h', '.inc', '.cpp'))):
+            assert retired not in open(os.path.join(csrc, f), errors='replace').read(), (retired, f)
 
 
 def test_no_kernel_of_the_shipped_library_spills_registers():

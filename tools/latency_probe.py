@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Single-image latency (BASELINE configs[1] read literally) with its stage breakdown, for a few option sets, and the same
-for small batches (2, 3 images) - the window lanes of run_plan (api.hip) are what these measure.
+for small batches (2, 3 images) - the window lanes of run_plan (plan_run.hip) are what these measure.
     python tools/latency_probe.py [--base 64] [--lanes 1,2,3,4] [--images 1,2,3]"""
 import argparse
 import json
@@ -42,9 +42,9 @@ def main():
         ref = None
         variants = [('lanes%d' % int(x), {'unet_lanes': int(x)}) for x in a.lanes.split(',')]
         if n_img == 1:
-            variants += [('auto', {}), ('auto+post_graph', {'post_graph': 1}), ('auto+overlap_post', {'overlap_post': 1})]
+            variants += [('auto', {}), ('auto+overlap_post', {'overlap_post': 1})]
         for name, opts in variants:
-            for k in ('post_graph', 'overlap_post', 'unet_lanes'):
+            for k in ('overlap_post', 'unet_lanes'):
                 h.set_option(k, opts.get(k, 0))
             for _ in range(3):
                 call()

@@ -8,6 +8,6 @@ for v in "$@"; do n=${v%%:*}; f=${v#*:}; $HC $f -c wino4r_kernel.hip -o /tmp/w4r
 wait
 for v in "$@"; do
   n=${v%%:*}
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../libecseg_w4r_$n.so api.o unet_kernels.o layer_kernels.o wino4_kernel.o wino4s_kernel.o /tmp/w4r/w4r_$n.o convs_kernel.o wino16_kernel.o post_kernels.o host_codec.o host_io.o comm.o -lz -ldl
+  /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../libecseg_w4r_$n.so api.o filter_layout.o model_load.o plan_run.o segment.o drivers.o unet_kernels.o layer_kernels.o wino4_kernel.o wino4s_kernel.o /tmp/w4r/w4r_$n.o convs_kernel.o wino16_kernel.o post_kernels.o host_codec.o host_io.o comm.o -lz -ldl
 done
 ls -la ../libecseg_w4r_*.so
