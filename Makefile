@@ -1,4 +1,4 @@
-.PHONY: build metaseg meta_overlay interseg fish_distance_calculation test asan clean
+.PHONY: build metaseg meta_overlay interseg stat_fish fish_distance_calculation test asan clean
 
 # same targets and config.yaml surface as the reference (Makefile:6-10); `build` compiles the gfx950 library first
 build:
@@ -12,6 +12,9 @@ meta_overlay: build
 
 interseg: build
 	python src/interseg.py
+
+stat_fish: build
+	python src/stat_fish.py
 
 fish_distance_calculation: build
 	python src/fish_distance_calculation.py

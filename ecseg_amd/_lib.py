@@ -16,10 +16,11 @@ EXPORTS = [
     'ecseg_segment_images', 'ecseg_segment_images_ex', 'ecseg_segment_images_dev', 'ecseg_set_images_per_group', 'ecseg_set_option', 'ecseg_preprocess', 'ecseg_u16_to_u8',
     'ecseg_meta_segment', 'ecseg_prefetch_input', 'ecseg_host_alloc', 'ecseg_host_free',
     'ecseg_stitch_argmax', 'ecseg_meta_inference', 'ecseg_meta_inference_dev', 'ecseg_count_cc', 'ecseg_ccl_labels',
-    'ecseg_count_colocalization', 'ecseg_count_hsr', 'ecseg_overlay', 'ecseg_nuclei_regions', 'ecseg_nucleus_crops', 'ecseg_fish_distances', 'ecseg_get_timings',
+    'ecseg_count_colocalization', 'ecseg_count_hsr', 'ecseg_overlay', 'ecseg_nuclei_regions', 'ecseg_nucleus_crops', 'ecseg_fish_distances', 'ecseg_fish_spots', 'ecseg_get_timings',
     'ecseg_set_kernel_profiling', 'ecseg_get_conv_profile', 'ecseg_get_conv_executed_flops', 'ecseg_get_conv_launch_profile', 'ecseg_debug_peek', 'ecseg_lzw_decode', 'ecseg_lzw_encode',
     'ecseg_comm_unique_id', 'ecseg_comm_create', 'ecseg_comm_destroy', 'ecseg_comm_last_error', 'ecseg_allgather_records', 'ecseg_allgather_records_dev',
     'ecseg_npy_write_i64', 'ecseg_png_write_labels', 'ecseg_png_write', 'ecseg_png_write_channel', 'ecseg_npy_label_info', 'ecseg_npy_read_labels_u8', 'ecseg_tiff_write_gray8', 'ecseg_tiff_info', 'ecseg_tiff_read',
+    'ecseg_tiff_write_rgb8', 'ecseg_npy_write_i32_as_i64',
 ]
 
 
@@ -98,6 +99,8 @@ def load_library():
     lib.ecseg_nuclei_regions.argtypes = [vp, u8p, i32, i32, u8p, i32, i32, i32, i32, i32, vp, C.POINTER(C.c_int32)]
     lib.ecseg_nucleus_crops.argtypes = [vp, vp, i32, vp, vp, vp]
     lib.ecseg_fish_distances.argtypes = [vp, vp, i32, i32, u8p, i32, i32, i32, i32, vp, C.POINTER(C.c_int32)]
+    lib.ecseg_fish_spots.argtypes = [vp, vp, i32, i32, u8p, i32, vp, i32, vp, i32, C.c_double, vp, i32, i32, i32, vp, vp, vp,
+                                     C.POINTER(C.c_int32)]
     lib.ecseg_get_timings.argtypes = [vp, vp]
     lib.ecseg_set_kernel_profiling.argtypes = [vp, i32]
     lib.ecseg_get_conv_profile.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double)]
@@ -120,6 +123,8 @@ def load_library():
     lib.ecseg_npy_label_info.argtypes = [C.c_char_p, C.POINTER(i32), C.POINTER(i32)]
     lib.ecseg_npy_read_labels_u8.argtypes = [C.c_char_p, vp, i32, i32]
     lib.ecseg_tiff_write_gray8.argtypes = [C.c_char_p, vp, i32, i32, i32]
+    lib.ecseg_tiff_write_rgb8.argtypes = [C.c_char_p, vp, i32, i32]
+    lib.ecseg_npy_write_i32_as_i64.argtypes = [C.c_char_p, vp, i32, i32]
     lib.ecseg_tiff_info.argtypes = [C.c_char_p, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
     lib.ecseg_tiff_read.argtypes = [C.c_char_p, vp, C.c_longlong]
     for name in EXPORTS:
@@ -477,6 +482,43 @@ class Handle:
                                                       int(centromere_channel), cap, _ptr(rec), C.byref(n)), 'ecseg_fish_distances')
             if n.value <= cap:
                 return rec[:n.value]
+            cap = n.value
+
+    # ---- stat_fish -------------------------------------------------------------------------------------
+    FISH_SPOT_INT64 = 24
+
+    def fish_spots(self, labels, img, probe_channels, weights, normal_threshold, intensity_thresholds, min_cc_size, line_thickness,
+                   capacity=4096):
+        """(H, W) int32 instance labels (<= 0 background) + (H, W, C) uint8 image -> (int64 (n_cells, 24) records in ascending
+        label order, cleaned thresholded masks uint8 (H, W, n_probe), boundaries uint8 (H, W)) (ecseg_fish_spots; the record
+        layout is in include/ecseg_hip.h).  ``weights``: the K x K float64 projected Gaussian kernel, K odd."""
+        lab = np.ascontiguousarray(labels)
+        if lab.dtype != np.int32:
+            if lab.dtype.kind not in 'iu' or (lab.size and (int(lab.max()) > 2 ** 31 - 1 or int(lab.min()) < -2 ** 31)):
+                raise ValueError('fish_spots takes integer labels that fit int32')
+            lab = lab.astype(np.int32)
+        im = _u8(img)
+        if lab.ndim != 2 or im.ndim != 3 or im.shape[:2] != lab.shape:
+            raise ValueError('fish_spots takes a (H, W) label map and an (H, W, C) image of the same extent')
+        ch = np.ascontiguousarray(probe_channels, np.int32).reshape(-1)
+        thr_in = np.ascontiguousarray(intensity_thresholds, np.float64).reshape(-1)
+        w = np.ascontiguousarray(weights, np.float64)
+        if w.ndim != 2 or w.shape[0] != w.shape[1]:
+            raise ValueError('fish_spots takes a square K x K kernel')
+        if len(thr_in) != len(ch):
+            raise ValueError('fish_spots takes one intensity threshold per probe channel')
+        H, W = lab.shape
+        n = C.c_int32()
+        cap = int(capacity)
+        thr = np.empty((H, W, max(len(ch), 1)), np.uint8)
+        bnd = np.empty((H, W), np.uint8)
+        while True:
+            rec = np.empty((max(cap, 1), self.FISH_SPOT_INT64), np.int64)
+            self._check(self.lib.ecseg_fish_spots(self.h, _ptr(lab), H, W, _ptr(im), im.shape[2], _ptr(ch), len(ch), _ptr(w), w.shape[0],
+                                                  float(normal_threshold), _ptr(thr_in), int(min_cc_size), int(line_thickness), cap,
+                                                  _ptr(thr), _ptr(bnd), _ptr(rec), C.byref(n)), 'ecseg_fish_spots')
+            if n.value <= cap:
+                return rec[:n.value], thr, bnd
             cap = n.value
 
     # ---- timing ---------------------------------------------------------------------------------------

@@ -238,4 +238,15 @@ hipError_t run_fishdist_cells(const int32_t* labels, int H, int W, const FishDis
 hipError_t run_fishdist_records(int32_t* labels, const uint8_t* lsq, int H, int W, int C, int fi, int ci, int n, const FishDistBufs& b,
                                 hipStream_t s);
 
+// ---- launcher implemented in fishspot_kernels.hip (src/stat_fish.py:73-107,134-142,226-300) ---------------------------------
+// Device buffers of one H x W image with np probes: rid (H*W int32, as run_fishdist_cells left it), mx (4 int32), thr (H*W*np
+// uint8), bnd (H*W uint8), par and sz (4 planes of H*W int32 each: probes 0..2, the pair) and - sized by the number of cells n -
+// acc (12n uint64), cnt (8n uint32), val (n int32), rec (ECSEG_FISH_SPOT_INT64 x n int64).
+struct FishSpotBufs { int32_t* rid; int32_t* mx; uint8_t* thr; uint8_t* bnd; int32_t* par; int32_t* sz; unsigned long long* acc;
+                      unsigned* cnt; int32_t* val; int64_t* rec; };
+// After run_fishdist_cells with n = misc[0] > 0 and misc[3] == 0: relabels `labels` in place to cell + 1 and writes thr, bnd and the
+// n records of ecseg_fish_spots.  img: (H, W, C) uint8; ch: the np probe channels; wts: K x K float64 on the device.
+hipError_t run_fishspot(int32_t* labels, const uint8_t* img, int H, int W, int C, int np, const int ch[3], const double* wts, int K,
+                        double normal_thr, const double ithr[3], int min_cc, int line_t, int n, const FishSpotBufs& b, hipStream_t s);
+
 }  // namespace ecseg

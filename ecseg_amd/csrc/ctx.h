@@ -129,6 +129,13 @@ struct DevMem {
     DevBuf<unsigned> d_fd_acc;
     DevBuf<int64_t> d_fd_rec;
     DevBuf<unsigned long long> d_fd_pbest;
+    // ecseg_fish_spots: buffers of its own as well
+    DevBuf<int32_t> d_fs_lab, d_fs_rid, d_fs_blk, d_fs_misc, d_fs_mx, d_fs_par, d_fs_sz, d_fs_val;
+    DevBuf<uint8_t> d_fs_img, d_fs_thr, d_fs_bnd;
+    DevBuf<double> d_fs_w;
+    DevBuf<unsigned long long> d_fs_acc;
+    DevBuf<unsigned> d_fs_cnt;
+    DevBuf<int64_t> d_fs_rec;
 };
 
 }  // namespace ecseg

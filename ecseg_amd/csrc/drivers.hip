@@ -1,5 +1,5 @@
 // The one-call drivers: each uploads its inputs, runs one family of kernels on the main stream and downloads the results
-// (u16_to_u8, stitch_argmax, meta_inference, the counts, overlay, the interSeg regions / crops, the FISH distances).
+// (u16_to_u8, stitch_argmax, meta_inference, the counts, overlay, the interSeg regions / crops, the FISH distances, the FISH spots).
 #include "ctx.h"
 
 using namespace ecseg;
@@ -326,6 +326,89 @@ int ecseg_fish_distances(ecseg_ctx* h, const int32_t* labels, int H, int W, cons
     HIP_TRY(h, run_fishdist_records(h->d_fd_lab, h->d_fd_lsq, H, W, C, fish_channel, centromere_channel, n, b, s));
     HIP_TRY(h, hipEventRecord(h->ev[3], s));
     HIP_TRY(h, hipMemcpyAsync(records, h->d_fd_rec, nn * 8 * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    h->stage_ms[ECSEG_T_COUNT] += stage_elapsed(h->ev[2], h->ev[3]);
+    return ECSEG_OK;
+}
+
+// ---- stat_fish behind nuclei_segment (src/stat_fish.py:73-107,134-142,226-300) --------------------------------------------------
+int ecseg_fish_spots(ecseg_ctx* h, const int32_t* labels, int H, int W, const uint8_t* img, int C, const int32_t* probe_channels,
+                     int n_probe, const double* weights, int K, double normal_threshold, const double* intensity_thresholds,
+                     int min_cc_size, int line_thickness, int capacity, uint8_t* thresholded, uint8_t* boundaries,
+                     int64_t* records, int32_t* n_cells) {
+    if (!h) return ECSEG_E_INVALID;
+    drop_sent_ahead(h);
+    if (n_cells) *n_cells = 0;
+    if (!labels || !img || !probe_channels || !weights || !intensity_thresholds || !thresholded || !boundaries || !n_cells || H <= 0 ||
+        W <= 0 || C < 1 || capacity < 0 || (capacity > 0 && !records))
+        return fail(h, ECSEG_E_INVALID, "fish_spots: bad arguments");
+    if (n_probe < 1 || n_probe > 3) return fail(h, ECSEG_E_INVALID, "fish_spots: n_probe must be 1, 2 or 3");
+    int ch[3] = {0, 0, 0};
+    double ithr[3] = {0.0, 0.0, 0.0};
+    for (int j = 0; j < n_probe; ++j) {
+        ch[j] = probe_channels[j];
+        ithr[j] = intensity_thresholds[j];
+        if (ch[j] < 0 || ch[j] >= C)
+            return fail(h, ECSEG_E_INVALID, "fish_spots: probe channel out of range (the image has " + std::to_string(C) + " channels)");
+    }
+    if (K < 1 || K > ECSEG_FISH_SPOT_MAX_KERNEL || K % 2 == 0)
+        return fail(h, ECSEG_E_INVALID, "fish_spots: the kernel side must be odd and between 1 and " + std::to_string(ECSEG_FISH_SPOT_MAX_KERNEL));
+    if (line_thickness < 1 || line_thickness > ECSEG_FISH_SPOT_MAX_LINE)
+        return fail(h, ECSEG_E_INVALID, "fish_spots: line_thickness must be between 1 and " + std::to_string(ECSEG_FISH_SPOT_MAX_LINE));
+    if ((long long)H * W >= (1ll << 31) || (long long)H * W * C >= (1ll << 40))
+        return fail(h, ECSEG_E_INVALID, "fish_spots: image too large (H * W must be below 2^31, H * W * C below 2^40)");
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t px = (size_t)H * W, np = (size_t)n_probe;
+    int rc;
+    if ((rc = h->d_fs_lab.ensure(h, px))) return rc;
+    if ((rc = h->d_fs_img.ensure(h, px * C))) return rc;
+    if ((rc = h->d_fs_rid.ensure(h, px))) return rc;
+    if ((rc = h->d_fs_blk.ensure(h, (px + 1023) / 1024))) return rc;
+    if ((rc = h->d_fs_misc.ensure(h, 4))) return rc;
+    hipStream_t s = h->stream;
+    for (float& v : h->stage_ms) v = 0.f;
+    HIP_TRY(h, hipMemcpyAsync(h->d_fs_lab, labels, px * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(h->d_fs_img, img, px * C, hipMemcpyHostToDevice, s));
+    const FishDistBufs cb{h->d_fs_rid, nullptr, h->d_fs_blk, h->d_fs_misc, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    HIP_TRY(h, hipEventRecord(h->ev[0], s));
+    HIP_TRY(h, run_fishdist_cells(h->d_fs_lab, H, W, cb, s));
+    HIP_TRY(h, hipEventRecord(h->ev[1], s));
+    int32_t misc[4];
+    HIP_TRY(h, hipMemcpyAsync(misc, h->d_fs_misc, sizeof(misc), hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    h->stage_ms[ECSEG_T_COUNT] = stage_elapsed(h->ev[0], h->ev[1]);
+    if (misc[3])
+        return fail(h, ECSEG_E_INVALID, "fish_spots: the label map holds a label larger than H * W = " + std::to_string(px) +
+                                            " (renumber the labels by rank first)");
+    const int n = misc[0];
+    *n_cells = n;
+    if (n > capacity) return ECSEG_OK;                       // the cell count alone: the caller comes back with a larger buffer
+    if (n == 0) {                                            // no cell: nothing is thresholded and no rank differs from 0
+        std::fill(thresholded, thresholded + px * np, (uint8_t)0);
+        std::fill(boundaries, boundaries + px, (uint8_t)0);
+        return ECSEG_OK;
+    }
+    const size_t nn = (size_t)n;
+    if ((rc = h->d_fs_mx.ensure(h, 4))) return rc;
+    if ((rc = h->d_fs_w.ensure(h, (size_t)K * K))) return rc;
+    if ((rc = h->d_fs_thr.ensure(h, px * np))) return rc;
+    if ((rc = h->d_fs_bnd.ensure(h, px))) return rc;
+    if ((rc = h->d_fs_par.ensure(h, px * 4))) return rc;
+    if ((rc = h->d_fs_sz.ensure(h, px * 4))) return rc;
+    if ((rc = h->d_fs_acc.ensure(h, nn * 12))) return rc;
+    if ((rc = h->d_fs_cnt.ensure(h, nn * 8))) return rc;
+    if ((rc = h->d_fs_val.ensure(h, nn))) return rc;
+    if ((rc = h->d_fs_rec.ensure(h, nn * ECSEG_FISH_SPOT_INT64))) return rc;
+    HIP_TRY(h, hipMemcpyAsync(h->d_fs_w, weights, (size_t)K * K * sizeof(double), hipMemcpyHostToDevice, s));
+    const FishSpotBufs b{h->d_fs_rid, h->d_fs_mx, h->d_fs_thr, h->d_fs_bnd, h->d_fs_par, h->d_fs_sz, h->d_fs_acc, h->d_fs_cnt, h->d_fs_val,
+                         h->d_fs_rec};
+    HIP_TRY(h, hipEventRecord(h->ev[2], s));
+    HIP_TRY(h, run_fishspot(h->d_fs_lab, h->d_fs_img, H, W, C, n_probe, ch, h->d_fs_w, K, normal_threshold, ithr, min_cc_size,
+                            line_thickness, n, b, s));
+    HIP_TRY(h, hipEventRecord(h->ev[3], s));
+    HIP_TRY(h, hipMemcpyAsync(thresholded, h->d_fs_thr, px * np, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipMemcpyAsync(boundaries, h->d_fs_bnd, px, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipMemcpyAsync(records, h->d_fs_rec, nn * ECSEG_FISH_SPOT_INT64 * sizeof(int64_t), hipMemcpyDeviceToHost, s));
     HIP_TRY(h, hipStreamSynchronize(s));
     h->stage_ms[ECSEG_T_COUNT] += stage_elapsed(h->ev[2], h->ev[3]);
     return ECSEG_OK;

@@ -1,0 +1,311 @@
+// stat_fish behind nuclei_segment on gfx950 (reference src/stat_fish.py:73-107,134-142,226-300): per nucleus of an instance-label map
+// the FISH spot statistics of up to three probe channels, the cleaned spot masks and the boundary drawing.  Every integer field
+// is a sum, a maximum, an OR or a root count, so no result depends on the order of the atomics; the one float64 decision
+// (coefficient > normal_threshold) is evaluated in a fixed tap order, so two calls give identical bytes.
+//
+// Cells (regionprops(labeled_segmented_cells): every label > 0 that occurs, ascending)
+//   * run_fishdist_cells (fishdist_kernels.hip: mark + exclusive scan) gives rid[label - 1] = dense cell index, misc[0] = cells;
+//   * fs_cell_stats_kernel relabels the map in place to the dense rank cell + 1 and accumulates per cell the area, the sums of
+//     rows and columns and, per probe, sum / count / maximum of the non-zero raw pixels (:252,261-263).  A wave handles one
+//     64-pixel row segment: the lanes of one cell are reduced with shuffles and the segment's leader lane adds into the cell's
+//     64-bit accumulators, one atomic per (cell, field, segment).
+// Peak filter (get_thresholded, :73-88)
+//   * fs_channel_max_kernel: the maximum of every probe channel over the whole image (the "max brightness" centres of :82);
+//   * fs_threshold_kernel: a 64 x 16 pixel tile per workgroup; per probe the channel's zero-padded halo tile (uint8) and the K x K
+//     float64 weights sit in LDS; a pixel that passes "label > 0 and pixel > intensity threshold" sums weight * pixel over all
+//     K * K taps in float64, row-major tap order (padding taps are multiplied too: 0 * NaN = NaN as in the reference's
+//     convolution, so NaN weights give no normal centre).  thresholded = centre ? 255 : 0; the union-find parent of the probe
+//     is preset to the pixel itself on thresholded pixels and to -1 elsewhere.
+// Spots (count_blobs, :134-142: scipy.ndimage.label, 4-connected, of thresholded * cell)
+//   * fs_unite_kernel unites a thresholded pixel with its W / N neighbour when that is a thresholded pixel of the SAME cell;
+//   * fs_size_kernel flattens (parent = root) and counts the pixels of every root; fs_finalize_kernel clears the components
+//     below min_cc_size from `thresholded` (:140 clears through a view, so the cleaned mask is what the _lsq file shows) and
+//     counts pixels and roots of the rest per cell;
+//   * the pair of the first two probes (:270-275): fs_pair_init_kernel presets parents on the AND of the two CLEANED masks, then
+//     the same unite / size / finalize, which here only counts.
+// Boundaries (get_boundaries, :91-107) on the dense ranks: fs_boundary_kernel, 64-bit sums of the 2 t taps of either axis.
+// fs_records_kernel writes the ECSEG_FISH_SPOT_INT64 fields of every cell.
+#include "common.h"
+#include "device_util.h"
+
+namespace ecseg {
+
+typedef unsigned long long u64;
+
+static constexpr int FS_TW = 64, FS_TH = 16;                 // output tile of fs_threshold_kernel (256 threads x 4 rows)
+static constexpr int FS_KMAX = ECSEG_FISH_SPOT_MAX_KERNEL;
+static constexpr int FS_HALO_W = FS_TW + FS_KMAX - 1, FS_HALO_H = FS_TH + FS_KMAX - 1;
+static constexpr int FS_ROWS_PER_WAVE = 8;                   // stats kernel: a block covers 64 columns x 32 rows
+static constexpr int FS_SLOTS = 4;                           // union-find slots: probes 0..2, the pair
+
+struct FsChannels { int c[3]; };
+struct FsThresholds { double t[3]; };
+
+// mx[j] = max over the image of channel ch.c[j]
+__global__ __launch_bounds__(256) void fs_channel_max_kernel(const uint8_t* __restrict__ img, int px, int C, int np, FsChannels ch,
+                                                             int32_t* __restrict__ mx) {
+    int m[3] = {0, 0, 0};
+    for (unsigned p = blockIdx.x * 256u + threadIdx.x; p < (unsigned)px; p += gridDim.x * 256u) {
+        const uint8_t* q = img + (size_t)p * C;
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+            if (j < np) m[j] = max(m[j], (int)q[ch.c[j]]);
+    }
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) m[j] = max(m[j], __shfl_xor(m[j], d));
+        if ((threadIdx.x & 63) == 0 && j < np && m[j] > 0) atomicMax(mx + j, m[j]);
+    }
+}
+
+// acc: per cell 12 uint64: area, sum of rows, sum of columns, then per probe sum / count / maximum of the non-zero raw pixels.
+// val[cell] = the cell's label value.  L is relabelled in place to cell + 1.
+__global__ __launch_bounds__(256) void fs_cell_stats_kernel(int32_t* __restrict__ L, const int32_t* __restrict__ rid,
+                                                            const uint8_t* __restrict__ img, int H, int W, int C, int np, FsChannels ch,
+                                                            u64* __restrict__ acc, int32_t* __restrict__ val) {
+    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    const unsigned tiles_x = ((unsigned)W + 63u) / 64u;
+    const unsigned xb = (blockIdx.x % tiles_x) * 64u;
+    const unsigned x = xb + (unsigned)lane;                 // < W + 63: compared as unsigned
+    const int ybeg = (int)(blockIdx.x / tiles_x) * (4 * FS_ROWS_PER_WAVE) + wv * FS_ROWS_PER_WAVE;
+    for (int r = 0; r < FS_ROWS_PER_WAVE; ++r) {
+        const int y = ybeg + r;
+        if (y >= H) break;                                   // wave-uniform
+        int reg = -1, l = 0;
+        int raw[3] = {0, 0, 0};
+        if (x < (unsigned)W) {
+            const size_t p = (size_t)y * W + x;
+            l = L[p];
+            if (l > 0) {
+                reg = rid[l - 1];
+                L[p] = reg + 1;
+                const uint8_t* q = img + p * C;
+#pragma unroll
+                for (int j = 0; j < 3; ++j)
+                    if (j < np) raw[j] = q[ch.c[j]];
+            } else if (l < 0) {
+                L[p] = 0;                                    // background: the later kernels test > 0 / compare ranks
+            }
+        }
+        u64 active = __ballot(reg >= 0);
+        while (active) {
+            const int leader = __ffsll((long long)active) - 1;
+            const int key = __shfl(reg, leader);
+            const bool mine = reg == key;
+            const u64 m = __ballot(mine);
+            const unsigned n = (unsigned)__popcll(m);
+            int sl = mine ? lane : 0;                        // sum of the lane numbers: columns = n * xb + that
+            int s[3], mxv[3];
+            unsigned cnt[3];
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                s[j] = mine ? raw[j] : 0;
+                mxv[j] = s[j];
+                cnt[j] = (unsigned)__popcll(__ballot(mine && raw[j] != 0));
+            }
+#pragma unroll
+            for (int d = 32; d >= 1; d >>= 1) {
+                sl += __shfl_xor(sl, d);
+#pragma unroll
+                for (int j = 0; j < 3; ++j) {
+                    s[j] += __shfl_xor(s[j], d);
+                    mxv[j] = max(mxv[j], __shfl_xor(mxv[j], d));
+                }
+            }
+            if (lane == leader) {
+                u64* a = acc + (size_t)key * 12;
+                atomicAdd(a + 0, (u64)n);
+                atomicAdd(a + 1, (u64)n * (u64)y);
+                atomicAdd(a + 2, (u64)n * (u64)xb + (u64)sl);
+#pragma unroll
+                for (int j = 0; j < 3; ++j)
+                    if (j < np && cnt[j]) {
+                        atomicAdd(a + 3 + 3 * j, (u64)s[j]);
+                        atomicAdd(a + 4 + 3 * j, (u64)cnt[j]);
+                        atomicMax(a + 5 + 3 * j, (u64)mxv[j]);
+                    }
+                val[key] = l;                                // every writer of a cell stores the same label
+            }
+            active &= ~m;
+        }
+    }
+}
+
+// L: cell + 1 per pixel (0 background).  thr (H, W, np) uint8 0 / 255; par: np planes of H * W parents (pixel | -1).
+__global__ __launch_bounds__(256) void fs_threshold_kernel(const int32_t* __restrict__ L, const uint8_t* __restrict__ img, int H, int W, int C,
+                                                           int np, FsChannels ch, const double* __restrict__ wts, int K, double normal_thr,
+                                                           FsThresholds ithr, const int32_t* __restrict__ mx, uint8_t* __restrict__ thr,
+                                                           int32_t* __restrict__ par) {
+    __shared__ double s_w[FS_KMAX * FS_KMAX];
+    __shared__ uint8_t s_t[FS_HALO_H * FS_HALO_W];
+    const int t = threadIdx.x, lx = t & 63, ly = t >> 6;
+    const int r = K >> 1, hw = FS_TW + K - 1, hh = FS_TH + K - 1;
+    const unsigned tiles_x = ((unsigned)W + FS_TW - 1) / FS_TW;
+    const int x0 = (int)(blockIdx.x % tiles_x) * FS_TW, y0 = (int)(blockIdx.x / tiles_x) * FS_TH;
+    for (int i = t; i < K * K; i += 256) s_w[i] = wts[i];
+    const size_t px = (size_t)H * W;
+    for (int j = 0; j < np; ++j) {
+        const int c = ch.c[j];
+        __syncthreads();                                     // the previous probe's readers are done (and s_w is complete)
+        for (int i = t; i < hh * hw; i += 256) {
+            const int ty = i / hw, tx = i - ty * hw;
+            const int gy = y0 - r + ty, gx = x0 - r + tx;
+            s_t[ty * FS_HALO_W + tx] = (gy >= 0 && gy < H && gx >= 0 && gx < W) ? img[((size_t)gy * W + gx) * C + c] : (uint8_t)0;
+        }
+        __syncthreads();
+        const int cmax = mx[j];
+        const double it = ithr.t[j];
+#pragma unroll
+        for (int q = 0; q < FS_TH / 4; ++q) {
+            const int oy = ly + 4 * q, y = y0 + oy, x = x0 + lx;
+            if (y >= H || x >= W) continue;
+            const size_t p = (size_t)y * W + x;
+            const int v = s_t[(oy + r) * FS_HALO_W + lx + r];
+            bool on = false;
+            if (L[p] > 0 && (double)v > it) {
+                on = cmax != 0 && v == cmax;                 // :82
+                if (!on) {
+                    double sum = 0.0;
+                    for (int ky = 0; ky < K; ++ky) {
+                        const uint8_t* row = s_t + (oy + ky) * FS_HALO_W + lx;
+                        const double* wr = s_w + ky * K;
+                        for (int kx = 0; kx < K; ++kx) sum += wr[kx] * (double)row[kx];
+                    }
+                    on = sum > normal_thr;                   // :83 (NaN: false)
+                }
+            }
+            thr[p * np + j] = on ? 255 : 0;
+            par[(size_t)j * px + p] = on ? (int)p : -1;
+        }
+    }
+}
+
+// slot blockIdx.y: unite every mask pixel with its W / N neighbour when that is a mask pixel of the same cell
+__global__ __launch_bounds__(256) void fs_unite_kernel(const int32_t* __restrict__ L, int H, int W, int32_t* par_all) {
+    const unsigned pu = blockIdx.x * 256u + threadIdx.x;    // H * W < 2^31: no wrap
+    if (pu >= (unsigned)(H * W)) return;
+    const int p = (int)pu;
+    int32_t* par = par_all + (size_t)blockIdx.y * ((size_t)H * W);
+    if (uf_load(par, p) < 0) return;
+    const int cell = L[p];
+    const int y = p / W, x = p - y * W;
+    // parents only ever move to smaller pixel indices, so "was preset to a pixel" stays readable as >= 0 while others unite
+    if (x > 0 && L[p - 1] == cell && uf_load(par, p - 1) >= 0) uf_unite(par, p, p - 1);
+    if (y > 0 && L[p - W] == cell && uf_load(par, p - W) >= 0) uf_unite(par, p, p - W);
+}
+
+// parent = root for every mask pixel; sz[root] = pixels of the component
+__global__ __launch_bounds__(256) void fs_size_kernel(int px, int32_t* par_all, int32_t* __restrict__ sz_all) {
+    const unsigned pu = blockIdx.x * 256u + threadIdx.x;
+    if (pu >= (unsigned)px) return;
+    const int p = (int)pu;
+    int32_t* par = par_all + (size_t)blockIdx.y * (size_t)px;
+    if (uf_load(par, p) < 0) return;
+    const int root = uf_find(par, p);
+    __hip_atomic_store(par + p, root, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // a shortcut inside the same tree
+    atomicAdd(sz_all + (size_t)blockIdx.y * (size_t)px + root, 1);
+}
+
+// slot = slot0 + blockIdx.y.  Components below min_cc: cleared from thr when thr != null (probes), else just not counted (the pair).
+// cnt: per cell FS_SLOTS x (pixels, components) uint32.
+__global__ __launch_bounds__(256) void fs_finalize_kernel(const int32_t* __restrict__ L, int px, int np, int slot0, int min_cc,
+                                                          const int32_t* __restrict__ par_all, const int32_t* __restrict__ sz_all,
+                                                          uint8_t* __restrict__ thr, unsigned* __restrict__ cnt) {
+    const unsigned pu = blockIdx.x * 256u + threadIdx.x;
+    if (pu >= (unsigned)px) return;
+    const int p = (int)pu, slot = slot0 + (int)blockIdx.y;
+    const int32_t* par = par_all + (size_t)slot * (size_t)px;
+    const int q = par[p];
+    if (q < 0) return;
+    const int root = uf_find(par, q);
+    if (sz_all[(size_t)slot * (size_t)px + root] < min_cc) {
+        if (thr) thr[(size_t)p * np + slot] = 0;
+        return;
+    }
+    unsigned* c = cnt + ((size_t)(L[p] - 1) * FS_SLOTS + slot) * 2;
+    atomicAdd(c, 1u);
+    if (root == p) atomicAdd(c + 1, 1u);
+}
+
+// parents of the pair slot: the pixel itself where the cleaned masks of probes 0 and 1 are both set
+__global__ __launch_bounds__(256) void fs_pair_init_kernel(const uint8_t* __restrict__ thr, int px, int np, int32_t* __restrict__ par) {
+    const unsigned p = blockIdx.x * 256u + threadIdx.x;
+    if (p >= (unsigned)px) return;
+    const uint8_t* q = thr + (size_t)p * np;
+    par[p] = (q[0] && q[1]) ? (int)p : -1;
+}
+
+// b = 255 where sum L[y][x-t+1..x] != sum L[y][x+1..x+t] or the same along y (taps outside the image are 0): the "SAME" padding
+// of an even kernel, t - 1 before and t after.  Ranks are < 2^31 and t <= 16; the sums are 64-bit.
+__global__ __launch_bounds__(256) void fs_boundary_kernel(const int32_t* __restrict__ L, int H, int W, int t, uint8_t* __restrict__ out) {
+    const unsigned pu = blockIdx.x * 256u + threadIdx.x;
+    if (pu >= (unsigned)(H * W)) return;
+    const int p = (int)pu, y = p / W, x = p - y * W;
+    long long h = 0, v = 0;
+    for (int k = 0; k < t; ++k) {
+        if (x - k >= 0) h += L[p - k];
+        if (x + 1 + k < W) h -= L[p + 1 + k];
+        if (y - k >= 0) v += L[(size_t)(y - k) * W + x];
+        if (y + 1 + k < H) v -= L[(size_t)(y + 1 + k) * W + x];
+    }
+    out[p] = (h != 0 || v != 0) ? 255 : 0;
+}
+
+// rec (n, ECSEG_FISH_SPOT_INT64) int64: see ecseg_fish_spots
+__global__ __launch_bounds__(256) void fs_records_kernel(const u64* __restrict__ acc, const unsigned* __restrict__ cnt,
+                                                         const int32_t* __restrict__ val, int n, int np, int64_t* __restrict__ rec) {
+    const unsigned cell = blockIdx.x * 256u + threadIdx.x;
+    if (cell >= (unsigned)n) return;
+    const u64* a = acc + (size_t)cell * 12;
+    const unsigned* c = cnt + (size_t)cell * FS_SLOTS * 2;
+    int64_t* o = rec + (size_t)cell * ECSEG_FISH_SPOT_INT64;
+    o[0] = val[cell]; o[1] = (int64_t)a[0]; o[2] = (int64_t)a[1]; o[3] = (int64_t)a[2];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        const bool live = j < np;
+        o[4 + 5 * j] = live ? c[2 * j] : 0;
+        o[5 + 5 * j] = live ? c[2 * j + 1] : 0;
+        o[6 + 5 * j] = live ? (int64_t)a[3 + 3 * j] : 0;
+        o[7 + 5 * j] = live ? (int64_t)a[4 + 3 * j] : 0;
+        o[8 + 5 * j] = live ? (int64_t)a[5 + 3 * j] : 0;
+    }
+    o[19] = np >= 2 ? c[6] : 0;
+    o[20] = np >= 2 ? c[7] : 0;
+    o[21] = o[22] = o[23] = 0;
+}
+
+hipError_t run_fishspot(int32_t* labels, const uint8_t* img, int H, int W, int C, int np, const int ch[3], const double* wts, int K,
+                        double normal_thr, const double ithr[3], int min_cc, int line_t, int n, const FishSpotBufs& b, hipStream_t s) {
+    const int px = H * W;
+    const unsigned gpx = ((unsigned)px + 255u) / 256u;
+    FsChannels fc{{ch[0], ch[1], ch[2]}};
+    FsThresholds ft{{ithr[0], ithr[1], ithr[2]}};
+    hipError_t e;
+    if ((e = hipMemsetAsync(b.mx, 0, 4 * sizeof(int32_t), s)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(b.acc, 0, (size_t)n * 12 * sizeof(u64), s)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(b.cnt, 0, (size_t)n * FS_SLOTS * 2 * sizeof(unsigned), s)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(b.sz, 0, (size_t)px * FS_SLOTS * sizeof(int32_t), s)) != hipSuccess) return e;
+    hipLaunchKernelGGL(fs_channel_max_kernel, dim3(gpx < 2048u ? gpx : 2048u), dim3(256), 0, s, img, px, C, np, fc, b.mx);
+    const unsigned stat_tiles = (((unsigned)W + 63u) / 64u) * (((unsigned)H + 4 * FS_ROWS_PER_WAVE - 1) / (4 * FS_ROWS_PER_WAVE));
+    hipLaunchKernelGGL(fs_cell_stats_kernel, dim3(stat_tiles), dim3(256), 0, s, labels, b.rid, img, H, W, C, np, fc, b.acc, b.val);
+    const unsigned thr_tiles = (((unsigned)W + FS_TW - 1) / FS_TW) * (((unsigned)H + FS_TH - 1) / FS_TH);
+    hipLaunchKernelGGL(fs_threshold_kernel, dim3(thr_tiles), dim3(256), 0, s, labels, img, H, W, C, np, fc, wts, K, normal_thr, ft, b.mx, b.thr,
+                       b.par);
+    hipLaunchKernelGGL(fs_unite_kernel, dim3(gpx, (unsigned)np), dim3(256), 0, s, labels, H, W, b.par);
+    hipLaunchKernelGGL(fs_size_kernel, dim3(gpx, (unsigned)np), dim3(256), 0, s, px, b.par, b.sz);
+    hipLaunchKernelGGL(fs_finalize_kernel, dim3(gpx, (unsigned)np), dim3(256), 0, s, labels, px, np, 0, min_cc, b.par, b.sz, b.thr, b.cnt);
+    if (np >= 2) {
+        int32_t* pair_par = b.par + (size_t)(FS_SLOTS - 1) * px;
+        hipLaunchKernelGGL(fs_pair_init_kernel, dim3(gpx), dim3(256), 0, s, b.thr, px, np, pair_par);
+        hipLaunchKernelGGL(fs_unite_kernel, dim3(gpx, 1), dim3(256), 0, s, labels, H, W, pair_par);
+        hipLaunchKernelGGL(fs_size_kernel, dim3(gpx, 1), dim3(256), 0, s, px, pair_par, b.sz + (size_t)(FS_SLOTS - 1) * px);
+        hipLaunchKernelGGL(fs_finalize_kernel, dim3(gpx, 1), dim3(256), 0, s, labels, px, np, FS_SLOTS - 1, min_cc, b.par, b.sz,
+                           static_cast<uint8_t*>(nullptr), b.cnt);
+    }
+    hipLaunchKernelGGL(fs_boundary_kernel, dim3(gpx), dim3(256), 0, s, labels, H, W, line_t, b.bnd);
+    hipLaunchKernelGGL(fs_records_kernel, dim3(((unsigned)n + 255u) / 256u), dim3(256), 0, s, b.acc, b.cnt, b.val, n, np, b.rec);
+    return hipGetLastError();
+}
+
+}  // namespace ecseg

@@ -568,11 +568,10 @@ bool read_file(const char* path, std::vector<uint8_t>* out) {
 
 }  // namespace
 
-extern "C" {
-
 // labels/<stem>.npy: np.save(path, labels.astype('int64')) (src/metaseg.py:53), byte for byte what numpy's format 1.0
 // writer produces (header dict, padded with spaces to a multiple of 64 bytes, '\n' last).
-int ecseg_npy_write_i64(const char* path, const uint8_t* labels, int H, int W) {
+template <typename T>
+static int npy_write_as_i64(const char* path, const T* labels, int H, int W) {
     if (!path || !labels || H < 0 || W < 0) return ECSEG_E_INVALID;
     std::string hdr = "{'descr': '<i8', 'fortran_order': False, 'shape': (" + std::to_string(H) + ", " + std::to_string(W) + "), }";
     const size_t hlen = hdr.size() + 1;                                   // + '\n'
@@ -595,11 +594,17 @@ int ecseg_npy_write_i64(const char* path, const uint8_t* labels, int H, int W) {
     std::unique_ptr<uint64_t[]> buf(new uint64_t[CH]);
     for (size_t off = 0; off < npx; off += CH) {
         const size_t k = std::min(CH, npx - off);
-        for (size_t i = 0; i < k; ++i) buf[i] = labels[off + i];          // little-endian host: int64 of a value 0..255
+        for (size_t i = 0; i < k; ++i) buf[i] = (uint64_t)(int64_t)labels[off + i];   // little-endian host: the value widened to int64
         if (!out.put(buf.get(), k * 8)) return ECSEG_E_IO;
     }
     return out.close() ? ECSEG_OK : ECSEG_E_IO;
 }
+
+extern "C" {
+
+int ecseg_npy_write_i64(const char* path, const uint8_t* labels, int H, int W) { return npy_write_as_i64(path, labels, H, W); }
+// <name>__segmentation_min_cut.npy (src/stat_fish.py:302): the same file from int32 values
+int ecseg_npy_write_i32_as_i64(const char* path, const int32_t* labels, int H, int W) { return npy_write_as_i64(path, labels, H, W); }
 
 // labels/<stem>.png: plt.imsave(path, I.astype('uint8'), cmap=ListedColormap(['#386cb0', '#ffff99', '#7fc97f', '#f0027f']),
 // vmin=0, vmax=4) (src/metaseg.py:47-52): class k -> colour k (values above 3 clip to 3), 8-bit RGBA, filter type 0 on
@@ -681,28 +686,29 @@ int ecseg_npy_read_labels_u8(const char* path, uint8_t* dst, int H, int W) {
     return ECSEG_OK;
 }
 
-// dapi/<name>.tif: cv2.imwrite of an 8-bit gray image (src/utils.py:122-123): LZW + horizontal predictor, strips of
-// 8192 / width rows (the tags OpenCV 4.6 wrote into example_ecSeg/dapi.jpeg's sibling files).  invert != 0 writes 255 - img
-// (the caller holds the pre-processed image, the file holds cv2.bitwise_not of it: src/utils.py:112).
-int ecseg_tiff_write_gray8(const char* path, const uint8_t* img, int H, int W, int invert) {
-    if (!path || !img || H <= 0 || W <= 0) return ECSEG_E_INVALID;
-    int rps = 8192 / W; if (rps < 1) rps = 1; if (rps > H) rps = H;
+// cv2.imwrite of an 8-bit image with `spp` interleaved samples per pixel (1: gray, 3: RGB): LZW + horizontal predictor (per
+// sample: a byte minus the byte `spp` to its left), strips of 8192 / (W * spp) rows.
+static int tiff_write_u8(const char* path, const uint8_t* img, int H, int W, int spp, int invert) {
+    if (!path || !img || H <= 0 || W <= 0 || (long long)W * spp >= (1ll << 30)) return ECSEG_E_INVALID;
+    const size_t line = (size_t)W * spp;
+    int rps = (int)(8192 / line); if (rps < 1) rps = 1; if (rps > H) rps = H;
     const int nstrips = (H + rps - 1) / rps;
-    std::vector<uint8_t> diff((size_t)rps * W), enc((size_t)2 * rps * W + 64), data;
+    std::vector<uint8_t> diff((size_t)rps * line), enc((size_t)2 * rps * line + 64), data;
     std::vector<uint32_t> offs(nstrips), cnts(nstrips);
-    data.reserve((size_t)H * W / 2 + 4096);
+    data.reserve((size_t)H * line / 2 + 4096);
     const uint8_t flip = invert ? 0xff : 0;
     size_t pos = 8;
     for (int s = 0; s < nstrips; ++s) {
         const int r0 = s * rps, rows = r0 + rps <= H ? rps : H - r0;
         for (int y = 0; y < rows; ++y) {
-            const uint8_t* src = img + (size_t)(r0 + y) * W;
-            uint8_t* d = diff.data() + (size_t)y * W;
-            d[0] = src[0] ^ flip;
-            for (int x = 1; x < W; ++x) d[x] = (uint8_t)((src[x] ^ flip) - (src[x - 1] ^ flip));   // horizontal differencing (mod 256)
+            const uint8_t* src = img + (size_t)(r0 + y) * line;
+            uint8_t* d = diff.data() + (size_t)y * line;
+            for (size_t x = 0; x < (size_t)spp; ++x) d[x] = src[x] ^ flip;
+            for (size_t x = spp; x < line; ++x) d[x] = (uint8_t)((src[x] ^ flip) - (src[x - spp] ^ flip));   // horizontal differencing (mod 256)
         }
-        const long long m = ecseg_lzw_encode(diff.data(), (long long)rows * W, enc.data(), (long long)enc.size());
+        const long long m = ecseg_lzw_encode(diff.data(), (long long)rows * (long long)line, enc.data(), (long long)enc.size());
         if (m < 0) return ECSEG_E_INVALID;
+        if (pos + (size_t)m + 1 >= 0xffffffffull) return ECSEG_E_INVALID;   // classic TIFF: 32-bit offsets
         offs[s] = (uint32_t)pos; cnts[s] = (uint32_t)m;
         data.insert(data.end(), enc.begin(), enc.begin() + m);
         if (m & 1) data.push_back(0);
@@ -710,10 +716,14 @@ int ecseg_tiff_write_gray8(const char* path, const uint8_t* img, int H, int W, i
     }
     std::vector<uint8_t> extra;
     const size_t extra_off = pos;
-    uint32_t so = offs[0], sc = cnts[0];
+    uint32_t so = offs[0], sc = cnts[0], bps = 8;
     if (nstrips > 1) {
         so = (uint32_t)(extra_off + extra.size()); for (uint32_t v : offs) put_le32(extra, v);
         sc = (uint32_t)(extra_off + extra.size()); for (uint32_t v : cnts) put_le32(extra, v);
+    }
+    if (spp > 2) {                                           // more than two SHORTs do not fit the entry's value field
+        bps = (uint32_t)(extra_off + extra.size());
+        for (int c = 0; c < spp; ++c) put_le16(extra, 8);
     }
     size_t ifd_off = extra_off + extra.size();
     const bool pad = ifd_off & 1;
@@ -721,8 +731,8 @@ int ecseg_tiff_write_gray8(const char* path, const uint8_t* img, int H, int W, i
     std::vector<uint8_t> ifd;
     auto entry = [&](uint32_t tag, uint32_t typ, uint32_t count, uint32_t value) { put_le16(ifd, tag); put_le16(ifd, typ); put_le32(ifd, count); put_le32(ifd, value); };
     put_le16(ifd, 12);
-    entry(256, 4, 1, (uint32_t)W); entry(257, 4, 1, (uint32_t)H); entry(258, 3, 1, 8); entry(259, 3, 1, 5);
-    entry(262, 3, 1, 1); entry(273, 4, (uint32_t)nstrips, so); entry(277, 3, 1, 1); entry(278, 4, 1, (uint32_t)rps);
+    entry(256, 4, 1, (uint32_t)W); entry(257, 4, 1, (uint32_t)H); entry(258, 3, (uint32_t)spp, bps); entry(259, 3, 1, 5);
+    entry(262, 3, 1, spp == 1 ? 1 : 2); entry(273, 4, (uint32_t)nstrips, so); entry(277, 3, 1, (uint32_t)spp); entry(278, 4, 1, (uint32_t)rps);
     entry(279, 4, (uint32_t)nstrips, sc); entry(284, 3, 1, 1); entry(317, 3, 1, 2); entry(339, 3, 1, 1);
     put_le32(ifd, 0);
     std::vector<uint8_t> head = {'I', 'I'};
@@ -733,6 +743,18 @@ int ecseg_tiff_write_gray8(const char* path, const uint8_t* img, int H, int W, i
     const bool ok = out.put(head.data(), head.size()) && out.put(data.data(), data.size()) && out.put(extra.data(), extra.size()) &&
                     (!pad || out.put(&zero, 1)) && out.put(ifd.data(), ifd.size());
     return ok && out.close() ? ECSEG_OK : ECSEG_E_IO;
+}
+
+// dapi/<name>.tif: cv2.imwrite of an 8-bit gray image (src/utils.py:122-123): LZW + horizontal predictor, strips of
+// 8192 / width rows (the tags OpenCV 4.6 wrote into example_ecSeg/dapi.jpeg's sibling files).  invert != 0 writes 255 - img
+// (the caller holds the pre-processed image, the file holds cv2.bitwise_not of it: src/utils.py:112).
+int ecseg_tiff_write_gray8(const char* path, const uint8_t* img, int H, int W, int invert) {
+    return tiff_write_u8(path, img, H, W, 1, invert);
+}
+
+// The colour files of stat_fish (src/stat_fish.py:306-308): the same writer with three samples per pixel, stored as given.
+int ecseg_tiff_write_rgb8(const char* path, const uint8_t* img, int H, int W) {
+    return tiff_write_u8(path, img, H, W, 3, 0);
 }
 
 // imread of a baseline TIFF (src/utils.py:110): first image of the file; strips; 8 / 16-bit unsigned samples, gray or

@@ -296,6 +296,16 @@ def write_tiff_gray8(path, img, invert=False, native=True):
         f.write(struct.pack('<H', len(entries)) + b''.join(entries) + struct.pack('<I', 0))
 
 
+def write_tiff_rgb8(path, img):
+    """8-bit TIFF with three samples per pixel, stored in the order given (RGB), with the settings of ``write_tiff_gray8``: LZW +
+    horizontal predictor, strips of 8192 // (3 * width) rows - what ``cv2.imwrite('x.tif', bgr)`` produces for the colour files
+    of stat_fish (src/stat_fish.py:306-308) once the caller has turned the reference's BGR arrays into RGB (csrc/host_io.cpp)."""
+    img = np.ascontiguousarray(img, np.uint8)
+    if img.ndim != 3 or img.shape[2] != 3 or not img.size:
+        raise ValueError('write_tiff_rgb8 takes a non-empty (H, W, 3) uint8 image')
+    _check_write(load_library().ecseg_tiff_write_rgb8(os.fsencode(path), img.ctypes.data_as(C.c_void_p), img.shape[0], img.shape[1]), path)
+
+
 def write_png(path, img, level=6, native=True):
     """8-bit PNG: (H, W) gray, (H, W, 3) RGB or (H, W, 4) RGBA."""
     img = np.ascontiguousarray(img, np.uint8)
@@ -348,14 +358,14 @@ def write_label_png(path, labels, native=True):
 
 
 def write_npy_int64(path, labels):
-    """``np.save(path, labels.astype('int64'))`` (src/metaseg.py:53) for a uint8 label image: the widening and the write
-    happen in csrc/host_io.cpp, byte-identical to numpy's file (tests/test_io_fixtures.py).  ``path`` is taken as given (no
-    ``.npy`` is appended)."""
+    """``np.save(path, labels.astype('int64'))`` (src/metaseg.py:53; src/stat_fish.py:302) for a uint8 or int32 label image: the
+    widening and the write happen in csrc/host_io.cpp, byte-identical to numpy's file (tests/test_io_fixtures.py).  ``path`` is
+    taken as given (no ``.npy`` is appended)."""
     lab = np.asarray(labels)
-    if lab.dtype == np.uint8 and lab.ndim == 2:
+    if lab.dtype in (np.uint8, np.int32) and lab.ndim == 2:
         lab = np.ascontiguousarray(lab)
-        _check_write(load_library().ecseg_npy_write_i64(os.fsencode(path), lab.ctypes.data_as(C.c_void_p), lab.shape[0],
-                                                        lab.shape[1]), path)
+        write = load_library().ecseg_npy_write_i64 if lab.dtype == np.uint8 else load_library().ecseg_npy_write_i32_as_i64
+        _check_write(write(os.fsencode(path), lab.ctypes.data_as(C.c_void_p), lab.shape[0], lab.shape[1]), path)
         return
     with open(path, 'wb') as f:
         np.save(f, lab.astype(np.int64))

@@ -1,0 +1,367 @@
+#!/usr/bin/env python3
+"""``make stat_fish``: per-nucleus FISH spot statistics (reference src/stat_fish.py), everything behind ``nuclei_segment``.
+
+The nucleus mask of every image is read from ``<masks>/<name>.tif`` (config key ``masks``, default ``<inpath>/nuclei_masks``):
+NuSeT, whose TF1 checkpoints this project cannot load, stays out of scope, and any segmenter writing an 8-bit single-sample
+TIFF there, non-zero = nucleus, will do.  Per image the nuclei are labelled on the device (``Handle.ccl_labels``, 8-connected,
+skimage's order) and one more device call (``Handle.fish_spots`` -> ecseg_fish_spots, csrc/fishspot_kernels.hip) returns the
+per-nucleus integers, the cleaned spot masks and the boundary drawing; the host computes the projected Gaussian kernel
+(src/stat_fish.py:28-55) with numpy / scipy, forms the means as ``sum / count`` in float64 (exact: the sums are far below
+2^53) and writes the five files per image and ``stat_fish_lsq.csv``.  ``make interseg`` and ``make fish_distance_calculation``
+read the ``annotated/`` folder this leaves behind.
+
+The parameters of the reference's ``src/stat_fish_params.yaml`` are built in (``DEFAULT_PARAMS``); a ``src/stat_fish_params.yaml``
+in the working directory overrides them key by key.  The file, or the effective values when there is none, is copied into the
+output folder.
+
+The reference indexes its arrays as BGR (``cv2.imread``); the TIFF reader here returns RGB, so a TIFF's blue / green / red are
+channels 2 / 1 / 0 and the indices are mapped, the image is not copied.  A ``.npy`` image is indexed as the reference indexes
+it: channel 0 blue, 1 green, 2 red.
+
+The NaN-scale branch (:238-240; ``scale: auto`` on an image without nuclei) yields an all-zero ``thresholded``: the device is
+still called for regions, raw intensities and boundaries, with intensity thresholds of +infinity, which no pixel exceeds.
+
+Divergences from the reference, all on inputs it crashes on or leaves to chance: images are processed in sorted order; a
+per-image failure (missing mask, unreadable file, 4-channel image - the two-entry ``color_sensitivity`` cannot broadcast over
+three probes in the reference either -, 16-bit TIFF - ``cv2.imread``'s internal 16-to-8 conversion cannot be pinned without
+OpenCV -) is reported, skipped and turns the exit code to 1 while the other images' outputs are still written;
+configuration errors exit with code 2; ``use_min_cut: True`` is a configuration error (the min-cut splitter,
+src/max_flow_binary_mask.py, is not built); integer CSV columns are always written as integers (pandas promotes them to
+float when it concatenates an image without nuclei with others).  Kept as in the reference: with ``scale: auto`` the scale
+of the FIRST image is used for every later image (:228 overwrites the variable).
+"""
+import datetime
+import math
+import os
+import shutil
+import subprocess
+import sys
+
+import numpy as np
+
+from .interseg import ImageError
+
+DEFAULT_PARAMS = {
+    'normal_threshold': 15,
+    'color_sensitivity': [70, 70],
+    'line_thickness': 2,
+    'min_cc_size': 7,
+    'gaussian_sigma': 3,
+    'kernel_size': [7, 7],
+    'target_median_nuclei_size': 2500,
+}
+PARAMS_FILE = os.path.join('src', 'stat_fish_params.yaml')
+PROBE_NAMES = ('green', 'red')
+MAX_KERNEL = 63                # ECSEG_FISH_SPOT_MAX_KERNEL
+MAX_LINE = 16                  # ECSEG_FISH_SPOT_MAX_LINE
+
+
+class ConfigError(Exception):
+    pass
+
+
+def csv_columns():
+    """Column order of src/stat_fish.py:277-288."""
+    cols = ['image_name', 'nucleus_center']
+    for name in PROBE_NAMES:
+        cols += ['#_FISH_pixels (%s)' % name, '#_FISH_foci (%s)' % name, 'Avg fish intensity (%s)' % name,
+                 'Max fish intensity (%s)' % name]
+    return cols + ['#_DAPI_pixels', '#_FISH_pixels (green and red)', '#_FISH_foci (green and red)']
+
+
+def sampled_gaussian_kernel(kernel_shape, sigma):
+    """src/stat_fish.py:28-38: the normal density sampled at the distances from the kernel's centre, normalised to sum 1."""
+    import scipy.stats
+    shape = np.array(kernel_shape)
+    centers = (shape / 2) - 0.5
+    axis_y, axis_x = [np.arange(size) - center for size, center in zip(shape, centers)]
+    grid = np.linalg.norm(np.dstack(np.meshgrid(axis_x, axis_y)), axis=2).astype(np.float64)
+    gaussian = scipy.stats.norm.pdf(grid, scale=sigma)
+    return gaussian / gaussian.sum()
+
+
+def gaussian_proj_kernel(kernel_shape, sigma):
+    """src/stat_fish.py:41-55 without the two trailing axes: the Gaussian kernel minus its projection on the constant kernel,
+    scaled to unit norm.  A 1 x 1 kernel gives 0 / 0 = NaN (the device then finds no normal centre)."""
+    g = sampled_gaussian_kernel(kernel_shape, sigma)
+    c = np.ones(kernel_shape)
+    c = c / np.linalg.norm(c)
+    proj = np.dot(g.flatten(), c.flatten()) * c
+    perp = g - proj
+    with np.errstate(divide='ignore', invalid='ignore'):
+        perp = perp / np.linalg.norm(perp)
+    return perp
+
+
+def derived_parameters(scale, params):
+    """src/stat_fish.py:232-240 -> (gaussian_stdev, min_cc_size, kernel shape); three NaNs for a NaN scale."""
+    if isinstance(scale, float) and math.isnan(scale):
+        return float('nan'), float('nan'), float('nan')
+    stdev = params['gaussian_sigma'] / scale
+    min_cc = int(params['min_cc_size'] // (scale * scale))
+    shape = [int(dim // scale) if (dim // scale % 2) else int(dim // scale) + 1 for dim in params['kernel_size']]
+    return stdev, min_cc, shape
+
+
+def lsq_name(img_name, params, stdev, min_cc):
+    """src/stat_fish.py:291-292."""
+    abbreviation = '_'.join('%s%s' % (letter, format(x, '.1f')) for letter, x in zip(['g', 'r', 'aq'], params['color_sensitivity']))
+    return '%s_lsq_n%s_std%s_s%s_%s.tif' % (img_name, params['normal_threshold'], format(stdev, '.2f'), min_cc, abbreviation)
+
+
+def with_segmentation(img, boundaries, green):
+    """src/stat_fish.py:296, ``np.minimum(I + [b, -b, b], 255).astype(np.uint8)`` in BGR: on boundary pixels blue and red become
+    255 and green becomes I - 255 wrapped to uint8, i.e. (I + 1) & 255.  ``green``: the index of the green channel."""
+    out = np.array(img, np.uint8, copy=True)
+    on = np.asarray(boundaries) != 0
+    for c in range(3):
+        out[..., c][on] = (out[..., c][on] + np.uint8(1)) if c == green else np.uint8(255)
+    return out
+
+
+def get_scale(areas, target_median_nuclei_size):
+    """src/stat_fish.py:127-132; NaN without regions."""
+    if not len(areas):
+        return float('nan')
+    return float(np.sqrt(target_median_nuclei_size / np.median(areas)))
+
+
+def rows_from_records(img_name, records):
+    """CSV rows of one image from the records of ecseg_fish_spots (src/stat_fish.py:249-288)."""
+    rows = []
+    for r in np.asarray(records, np.int64).reshape(-1, 24).tolist():
+        row = [img_name, '%d_%d' % (r[2] // r[1], r[3] // r[1])]
+        for j in range(len(PROBE_NAMES)):
+            pixels, foci, total, count, peak = r[4 + 5 * j:9 + 5 * j]
+            row += [pixels, foci, (total / count) if count else 0.0, peak]
+        rows.append(row + [r[1], r[19], r[20]])
+    return rows
+
+
+def read_image(path, handle):
+    """-> ((H, W, 3) uint8 image, (blue, green, red) channel indices into it) (src/stat_fish.py:206-212)."""
+    from . import image_io
+    try:
+        I = image_io.imread(path)
+    except Exception as e:
+        raise ImageError('cannot be read (%s)' % e)
+    is_npy = path.lower().endswith('.npy')
+    if is_npy:
+        if I.ndim != 3 or I.shape[2] != 3 or I.dtype not in (np.uint8, np.uint16):
+            raise ImageError("isn't an (H, W, 3) uint8 / uint16 array (shape %s, %s); a fourth channel needs a third "
+                             "color_sensitivity entry, which the reference cannot take either" % (I.shape, I.dtype))
+        if I.dtype == np.uint16:
+            I = handle.u16_to_u8(np.ascontiguousarray(I))
+        return np.ascontiguousarray(I), (0, 1, 2)
+    if I.dtype != np.uint8:
+        raise ImageError('is a %s TIFF: only 8-bit TIFFs are read (the 16-to-8-bit conversion inside cv2.imread is not reproduced); '
+                         'convert it, or store it as a uint16 .npy' % I.dtype)
+    if I.ndim == 2:
+        I = np.repeat(I[..., None], 3, axis=2)               # cv2.imread turns a gray file into three equal channels
+    elif I.shape[2] == 1:
+        I = np.repeat(I, 3, axis=2)
+    elif I.shape[2] < 3:
+        raise ImageError('has %d samples per pixel' % I.shape[2])
+    elif I.shape[2] > 3:
+        I = I[..., :3]                                       # cv2.imread drops the samples beyond three
+    return np.ascontiguousarray(I), (2, 1, 0)
+
+
+def read_mask(path):
+    from . import image_io
+    if not os.path.exists(path):
+        raise ImageError('has no nucleus mask %s' % path)
+    try:
+        m = image_io.imread(path)
+    except Exception as e:
+        raise ImageError('nucleus mask %s cannot be read (%s)' % (path, e))
+    if m.ndim == 3 and m.shape[2] == 1:
+        m = m[..., 0]
+    if m.ndim != 2 or m.dtype != np.uint8:
+        raise ImageError('nucleus mask %s is not an 8-bit single-sample image (shape %s, %s)' % (path, m.shape, m.dtype))
+    return (m != 0).astype(np.uint8) * np.uint8(255)
+
+
+def process_image(path, mask_path, out_root, params, scale, handle, stats=None):
+    """One image of src/stat_fish.py:199-308 -> (CSV rows, the scale that was used)."""
+    import time
+    from . import image_io
+    t0 = time.perf_counter()
+    img_name = os.path.basename(path)[:-4]
+    I, (blue, green, red) = read_image(path, handle)
+    mask = read_mask(mask_path)
+    imheight, imwidth = mask.shape
+    I = np.ascontiguousarray(I[:imheight, :imwidth])
+    mask = np.ascontiguousarray(mask[:I.shape[0], :I.shape[1]])
+    if mask.size == 0:
+        raise ImageError('is empty')
+    t1 = time.perf_counter()
+    probes = [green, red]
+    line = params['line_thickness']
+    try:
+        labels = handle.ccl_labels(mask, 8)
+        off = ([[0.0]], float('inf'), [float('inf')] * len(probes), 1)     # a call for the regions alone
+        if scale == 'auto':
+            rec, _, _ = handle.fish_spots(labels, I, probes, off[0], off[1], off[2], off[3], line)
+            scale = get_scale(rec[:, 1], params['target_median_nuclei_size'])
+        stdev, min_cc, shape = derived_parameters(scale, params)
+        if isinstance(stdev, float) and math.isnan(stdev):
+            rec, thr, bnd = handle.fish_spots(labels, I, probes, off[0], off[1], off[2], off[3], line)
+        else:
+            if shape[0] != shape[1] or shape[0] > MAX_KERNEL or shape[0] < 1:
+                raise ImageError('needs a %s Gaussian kernel: the device takes square kernels up to %d x %d' % (shape, MAX_KERNEL, MAX_KERNEL))
+            weights = gaussian_proj_kernel(shape, stdev)
+            rec, thr, bnd = handle.fish_spots(labels, I, probes, weights, params['normal_threshold'], params['color_sensitivity'][:len(probes)],
+                                              min_cc, line)
+    except Exception as e:
+        if getattr(e, 'code', None) == -1:
+            raise ImageError(str(e))
+        raise
+    t2 = time.perf_counter()
+    lut = np.zeros(labels.size + 1, np.int32)                 # label value -> dense rank (1 .. n), what skimage numbers them
+    lut[rec[:, 0]] = np.arange(1, len(rec) + 1, dtype=np.int32)
+    ranks = lut[labels]
+    annotated_path = os.path.join(out_root, img_name)
+    os.makedirs(annotated_path, exist_ok=True)
+    rgb = (blue, green, red) == (2, 1, 0)
+    original = I if rgb else np.ascontiguousarray(I[..., ::-1])            # the writers store RGB; cv2 writes its BGR arrays as RGB
+    lsq = np.empty(I.shape[:2] + (3,), np.uint8)                           # BGR (boundaries, green, red) -> RGB (red, green, boundaries)
+    lsq[..., 0] = thr[..., 1]
+    lsq[..., 1] = thr[..., 0]
+    lsq[..., 2] = bnd
+    image_io.write_npy_int64(os.path.join(annotated_path, img_name + '__segmentation_min_cut.npy'), ranks)
+    image_io.write_tiff_gray8(os.path.join(annotated_path, img_name + '_segmentation.tif'), mask)
+    image_io.write_tiff_rgb8(os.path.join(annotated_path, img_name + '_original_with_segmentation.tif'), with_segmentation(original, bnd, 1))
+    image_io.write_tiff_rgb8(os.path.join(annotated_path, img_name + '_original.tif'), original)
+    image_io.write_tiff_rgb8(os.path.join(annotated_path, lsq_name(img_name, params, stdev, min_cc)), lsq)
+    if stats is not None:
+        for key, v in (('read', t1 - t0), ('device', t2 - t1), ('write', time.perf_counter() - t2)):
+            stats[key] = stats.get(key, 0.0) + v
+        stats['nuclei'] = stats.get('nuclei', 0) + len(rec)
+    return rows_from_records(img_name, rec), scale
+
+
+def load_params():
+    """DEFAULT_PARAMS overridden by a src/stat_fish_params.yaml in the working directory -> (params, path of that file or None)."""
+    import yaml
+    params = {k: (list(v) if isinstance(v, list) else v) for k, v in DEFAULT_PARAMS.items()}
+    source = None
+    if os.path.isfile(PARAMS_FILE):
+        with open(PARAMS_FILE) as f:
+            user = yaml.safe_load(f) or {}
+        if not isinstance(user, dict):
+            raise ConfigError('%s is not a mapping' % PARAMS_FILE)
+        params.update({k: v for k, v in user.items() if k in DEFAULT_PARAMS})
+        source = PARAMS_FILE
+
+    def number(v):
+        return isinstance(v, (int, float)) and not isinstance(v, bool)
+    for key in ('normal_threshold', 'gaussian_sigma', 'min_cc_size', 'target_median_nuclei_size'):
+        if not number(params[key]):
+            raise ConfigError('%s must be a number' % key)
+    cs = params['color_sensitivity']
+    if not isinstance(cs, list) or len(cs) < len(PROBE_NAMES) or not all(number(v) for v in cs):
+        raise ConfigError('color_sensitivity must be a list of at least %d numbers' % len(PROBE_NAMES))
+    ks = params['kernel_size']
+    if not isinstance(ks, list) or len(ks) != 2 or not all(number(v) and v > 0 for v in ks):
+        raise ConfigError('kernel_size must be a list of two positive numbers')
+    lt = params['line_thickness']
+    if isinstance(lt, bool) or not isinstance(lt, int) or not 1 <= lt <= MAX_LINE:
+        raise ConfigError('line_thickness must be an integer between 1 and %d' % MAX_LINE)
+    return params, source
+
+
+def current_commit():
+    """src/stat_fish.py:186: the last word of ``git log -1 | head -1``; empty without git."""
+    try:
+        out = subprocess.run('git log -1 | head -1', shell=True, capture_output=True).stdout.decode()
+    except OSError:
+        return ''
+    return out.strip().split(' ')[-1]
+
+
+def main(argv=None, handle=None):
+    """``make stat_fish``.  Like the reference's ``main`` it takes everything from section ``stat_fish`` of ``config.yaml`` in
+    the working directory; ``argv`` is accepted for the shim's sake and not read.  ``handle`` is an injection point for tests and
+    tools (anything with ``Handle.ccl_labels``, ``fish_spots`` and ``u16_to_u8``); without it the call opens a handle on device 0
+    and closes it at the end."""
+    import yaml
+    from . import csvio
+    from .utils import get_imgs
+    try:
+        with open('config.yaml') as infile:
+            var = (yaml.safe_load(infile) or {}).get('stat_fish')
+        if not isinstance(var, dict):
+            raise ConfigError('config.yaml has no stat_fish section')
+        for key in ('inpath', 'scale', 'use_min_cut', 'nuclei_size_T'):       # nuclei_size_T belongs to nuclei_segment: accepted, unused
+            if key not in var:
+                raise ConfigError('config.yaml: stat_fish has no key %s' % key)
+        inpath = str(var['inpath'])
+        if not os.path.isdir(inpath):
+            raise ConfigError('Input folder does not exist. Exiting...')
+        if var['use_min_cut']:
+            raise ConfigError('use_min_cut: True needs the min-cut splitter (src/max_flow_binary_mask.py), which is not built: '
+                              'set use_min_cut: False in config.yaml')
+        scale = var['scale']
+        if scale != 'auto' and (isinstance(scale, bool) or not isinstance(scale, (int, float)) or not scale > 0 or math.isinf(scale)):
+            raise ConfigError('scale must be a positive number or "auto"')
+        masks = str(var['masks']) if var.get('masks') is not None else os.path.join(inpath, 'nuclei_masks')
+        if not os.path.isdir(masks):
+            raise ConfigError('The folder of nucleus masks %s does not exist (config key masks): it holds one 8-bit <name>.tif per '
+                              'image, non-zero = nucleus' % masks)
+        params, params_source = load_params()
+        image_paths = get_imgs(inpath)
+        if not image_paths:
+            raise ConfigError('No .tif / .npy images in the input folder. Exiting...')    # the reference crashes in pd.concat
+    except ConfigError as e:
+        print(e)
+        sys.exit(2)
+
+    output_folder = 'tmp_' + datetime.datetime.now().strftime('%m-%d_%H:%M:%S')
+    out_root = os.path.join(inpath, output_folder)
+    os.makedirs(out_root, exist_ok=True)
+    shutil.copyfile('config.yaml', os.path.join(out_root, 'config_%s.yaml' % current_commit()))
+    if params_source:
+        shutil.copyfile(params_source, os.path.join(out_root, 'stat_fish_params.yaml'))
+    else:
+        with open(os.path.join(out_root, 'stat_fish_params.yaml'), 'w') as f:
+            yaml.safe_dump(params, f)
+
+    own = handle is None
+    if own:
+        from ._lib import Handle
+        handle = Handle(0)
+    rows, failed = [], []
+    try:
+        for p in image_paths:
+            print("Processing image: ", p)
+            try:
+                img_rows, scale = process_image(p, os.path.join(masks, os.path.basename(p)[:-4] + '.tif'), out_root, params, scale, handle)
+                rows += img_rows
+            except ImageError as e:
+                print(p, '-', e)
+                failed.append((p, str(e)))
+    finally:
+        if own:
+            handle.close()
+    with open(os.path.join(out_root, 'stat_fish_lsq.csv'), 'w') as f:
+        f.write(csvio.csv_text(csv_columns(), rows))
+
+    annotated = os.path.join(inpath, 'annotated')
+    if os.path.isdir(annotated):
+        old = annotated + '_' + str(datetime.datetime.now())[5:-10].replace(' ', '-')
+        k, target = 1, old
+        while os.path.exists(target):                        # a second run within the minute: the reference's rename fails here
+            k += 1
+            target = '%s_%d' % (old, k)
+        os.rename(annotated, target)
+    os.rename(out_root, annotated)
+    if failed:
+        print("%d image(s) were NOT processed and are missing from the CSV:" % len(failed))
+        for p, why in failed:
+            print("  ", p, "-", why)
+        sys.exit(1)             # the reference would have crashed on the first such image
+
+
+if __name__ == "__main__":
+    main(sys.argv[1:])

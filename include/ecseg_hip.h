@@ -42,6 +42,8 @@ extern "C" {
  * their stride run phase by phase.) */
 /* (still 5 - additive: ecseg_nuclei_regions and ecseg_nucleus_crops, the file-level interSeg driver; nothing existing changed.) */
 /* (still 5 - additive: ecseg_fish_distances, the per-nucleus records of fish_distance_calculation; nothing existing changed.) */
+/* (still 5 - additive: ecseg_fish_spots, the per-nucleus records, masks and boundaries of stat_fish, and ecseg_tiff_write_rgb8; ecseg_npy_write_i32_as_i64
+ * beside ecseg_npy_write_i64; nothing existing changed.) */
 #define ECSEG_ABI_VERSION 5
 
 #define ECSEG_OK             0
@@ -317,6 +319,42 @@ int ecseg_nucleus_crops(ecseg_ctx* h, const int32_t* crops, int n_crops, const i
 int ecseg_fish_distances(ecseg_ctx* h, const int32_t* labels, int H, int W, const uint8_t* lsq, int C, int fish_channel,
                          int centromere_channel, int capacity, int64_t* records, int32_t* n_cells);
 
+/* ---- stat_fish behind nuclei_segment: per-nucleus FISH spot statistics (src/stat_fish.py:73-107,134-142,226-300) ----------- */
+/* Replaces, for ONE image, get_thresholded (:73-88, the two TensorFlow convolutions included), the loop over
+ * regionprops(labeled_segmented_cells) with count_blobs and intensity_metrics (:134-142,249-275; src/image_tools.py:121-124) and
+ * get_boundaries (:91-107).  labels: (H, W) int32 instance labels as for ecseg_fish_distances (<= 0 background, <= H * W, need
+ * not be connected; cells = the labels that occur, ascending).  img: (H, W, C) uint8.  probe_channels: n_probe (1..3) channel
+ * indices into img, the reference's green then red (then aqua).  weights: K x K float64, K odd, 1 <= K <=
+ * ECSEG_FISH_SPOT_MAX_KERNEL - the projected Gaussian kernel of :28-55, computed by the caller (its bits are the host's).
+ *   Peak filter: per probe, coefficient = the zero-padded "SAME" correlation of the channel with weights, accumulated in float64
+ *     in row-major tap order; centre = coefficient > normal_threshold, or pixel == the channel's maximum over the whole image
+ *     when that maximum is non-zero; thresholded = centre && pixel > intensity_thresholds[probe] && label > 0.  NaN weights (K = 1
+ *     gives 0 / 0) yield no normal centre.  An intensity threshold of +infinity switches a probe's mask off altogether (the
+ *     reference's NaN-scale branch, :238-240).
+ *   Spots: per cell and probe the 4-connected components (scipy.ndimage.label's default) of thresholded, joined only through
+ *     pixels of the same cell; components of fewer than min_cc_size pixels are cleared from thresholded (:140 does so in place).
+ *   Boundaries: with R = the dense rank of the labels (cell index + 1, 0 background) and t = line_thickness (1 ..
+ *     ECSEG_FISH_SPOT_MAX_LINE), a pixel is 255 when sum R[y][x-t+1 .. x] != sum R[y][x+1 .. x+t] or the same along y, taps
+ *     outside the image counting 0 (TensorFlow's "SAME" for the even kernel: t - 1 before, t after); the sums are 64-bit.
+ * Outputs, written when n_cells <= capacity: thresholded (H, W, n_probe) uint8 0 / 255, cleaned; boundaries (H, W) uint8 0 / 255;
+ * records (capacity x ECSEG_FISH_SPOT_INT64 int64), per cell in ascending label order:
+ *   [0] label  [1] area  [2] sum of rows  [3] sum of columns   (nucleus centre = floor([2] / [1]), floor([3] / [1]))
+ *   per probe j at 4 + 5 j: [+0] pixels of the kept spots  [+1] kept spots (foci)  [+2] sum and [+3] count of the non-zero raw
+ *     pixels of the channel inside the cell (mean = sum / count, 0 without any)  [+4] their maximum      (0 for j >= n_probe)
+ *   [19] pixels and [20] components of (cleaned mask 0 AND cleaned mask 1) that reach min_cc_size (0 when n_probe < 2)
+ *   [21..23] 0 (reserved).
+ * When n_cells > capacity nothing is written: call again with a buffer of n_cells records.  One image per call, synchronous,
+ * buffers of its own; device time of the kernels in ECSEG_T_COUNT.  ECSEG_E_INVALID: n_probe outside 1..3, a channel outside
+ * 0 .. C - 1, K even or outside 1 .. ECSEG_FISH_SPOT_MAX_KERNEL, line_thickness outside 1 .. ECSEG_FISH_SPOT_MAX_LINE, a label
+ * above H * W, H * W >= 2^31, H * W * C >= 2^40. */
+#define ECSEG_FISH_SPOT_INT64      24
+#define ECSEG_FISH_SPOT_MAX_KERNEL 63
+#define ECSEG_FISH_SPOT_MAX_LINE   16
+int ecseg_fish_spots(ecseg_ctx* h, const int32_t* labels, int H, int W, const uint8_t* img, int C, const int32_t* probe_channels,
+                     int n_probe, const double* weights, int K, double normal_threshold, const double* intensity_thresholds,
+                     int min_cc_size, int line_thickness, int capacity, uint8_t* thresholded, uint8_t* boundaries,
+                     int64_t* records, int32_t* n_cells);
+
 /* ---- per-stage device timings of the last segment call (milliseconds, HIP events on the handle's stream) -- */
 /* ECSEG_T_COUNT: device time of the kernels of the last ecseg_overlay / ecseg_preprocess / ecseg_count_* call (inputs
  * already resident, copies excluded). */
@@ -368,6 +406,13 @@ int ecseg_npy_read_labels_u8(const char* path, uint8_t* dst, int H, int W);
 /* cv2.imwrite(dapi/<name>.tif, gray) (src/utils.py:122-123): LZW + predictor 2, strips of 8192 / W rows; invert != 0
  * stores 255 - img (cv2.bitwise_not, src/utils.py:112). */
 int ecseg_tiff_write_gray8(const char* path, const uint8_t* img, int H, int W, int invert);
+/* cv2.imwrite(x.tif, 8-bit 3-channel image) (src/stat_fish.py:306-308): 3 samples per pixel, RGB photometric interpretation, the
+ * samples stored in the order given (the caller hands over RGB; cv2 turns its BGR arrays into RGB files), LZW + predictor 2,
+ * strips of 8192 / (3 W) rows. */
+int ecseg_tiff_write_rgb8(const char* path, const uint8_t* img, int H, int W);
+/* np.save(path, labels) of an int64 (H, W) array whose values the caller holds as int32 (src/stat_fish.py:302,
+ * <name>__segmentation_min_cut.npy): byte-identical to numpy's file of labels.astype(int64). */
+int ecseg_npy_write_i32_as_i64(const char* path, const int32_t* labels, int H, int W);
 /* skimage.io.imread of a baseline TIFF (src/utils.py:110): shape first, then the samples as native-endian (H, W, spp). */
 int ecseg_tiff_info(const char* path, int* H, int* W, int* samples_per_pixel, int* bits_per_sample);
 int ecseg_tiff_read(const char* path, void* dst, long long dst_bytes);

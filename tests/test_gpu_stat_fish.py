@@ -1,0 +1,224 @@
+"""ecseg_fish_spots (csrc/fishspot_kernels.hip) and ``make stat_fish`` on the device.  Records, cleaned masks and boundaries
+are compared exactly with the oracle tests/stat_fish_ref.py (its vectorised producer; the cell-by-cell one on the small
+cases), never with the product's own Python.  The float64 decision of the peak filter may differ between two correct
+evaluations only inside the derived band |coefficient - threshold| <= 2 B (see the oracle): every committed case is asserted
+to hold no pixel inside it, so exact equality is required.  ``case_mismatches(seed)`` is also the check of
+tools/fuzz_stat_fish.py; a failing seed of that campaign becomes a case here."""
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import yaml
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import stat_fish_cases as cases              # noqa: E402
+import stat_fish_ref as ref                  # noqa: E402
+import fish_distance_ref as fd_ref           # noqa: E402
+from ecseg_amd import csvio, image_io        # noqa: E402
+from ecseg_amd import fish_distance_calculation as fdc   # noqa: E402
+from ecseg_amd import interseg               # noqa: E402
+
+pytestmark = pytest.mark.gpu
+HAND = cases.hand_cases()
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _run(gpu, case, capacity=4096):
+    return gpu.fish_spots(case['seg'], case['img'], case['probes'], case['weights'], case['normal'], case['ithr'], case['min_cc'],
+                          case['line'], capacity)
+
+
+def mismatches(gpu, case, capacity=4096, producer=ref.records):
+    """-> (list of differences, number of ambiguous pixels of the case)."""
+    want_rec, want_thr, want_bnd, ambiguous = producer(*cases.args(case))
+    rec, thr, bnd = _run(gpu, case, capacity)
+    bad = []
+    if rec.shape != want_rec.shape:
+        return ['%d cells, the oracle has %d' % (len(rec), len(want_rec))], ambiguous
+    rows = np.flatnonzero((rec != want_rec).any(axis=1))
+    if len(rows):
+        r = rows[0]
+        bad.append('%d of %d records differ, first cell %d: %s, oracle %s' % (len(rows), len(rec), r, rec[r].tolist(), want_rec[r].tolist()))
+    if thr.shape != want_thr.shape or not np.array_equal(thr, want_thr):
+        bad.append('cleaned masks differ in %d pixel(s)' % (int((thr != want_thr).sum()) if thr.shape == want_thr.shape else -1))
+    if not np.array_equal(bnd, want_bnd):
+        bad.append('boundaries differ in %d pixel(s)' % int((bnd != want_bnd).sum()))
+    return bad, ambiguous
+
+
+def case_mismatches(gpu, seed):
+    """The fuzz campaign's check of one generated scene -> (differences, ambiguous pixels)."""
+    rng = np.random.default_rng(seed + 31337)
+    size = None if seed % 3 else (int(rng.integers(1, 260)), int(rng.integers(1, 260)))
+    return mismatches(gpu, cases.scene(seed, size=size, n_probe=int(rng.choice([1, 2, 2, 2, 3]))))
+
+
+def _check(gpu, case, capacity=4096, producer=ref.records):
+    bad, ambiguous = mismatches(gpu, case, capacity, producer)
+    assert ambiguous == 0, 'the case holds %d pixel(s) inside the 2 B band: not a committed case' % ambiguous
+    assert not bad, '; '.join(bad)
+
+
+# ---- hand cases and seeds -----------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize('name', sorted(HAND))
+def test_hand_computed_cases(gpu, name):
+    case, expected = HAND[name]
+    _check(gpu, case, producer=ref.loop)
+    rec = _run(gpu, case)[0]
+    for col, values in expected.items():
+        assert rec[:, col].tolist() == values, (col, rec[:, col].tolist())
+
+
+def test_committed_seeds(gpu):
+    for seed in range(cases.N_SEEDS):
+        case = cases.scene(seed)
+        _check(gpu, case)
+        if seed % 4 == 0:
+            _check(gpu, case, producer=ref.loop)
+
+
+@pytest.mark.parametrize('size', [(1, 1), (1, 64), (64, 1), (2, 2), (63, 65), (33, 1025), (1025, 3), (129, 257), (16, 64), (17, 65)])
+def test_odd_sizes(gpu, size):
+    for seed in range(3):
+        _check(gpu, cases.scene(200 + seed, size=size, K=(7, 3, 23)[seed]))
+
+
+@pytest.mark.parametrize('K', [1, 3, 7, 23])
+@pytest.mark.parametrize('line', [1, 2, 3])
+def test_kernel_sizes_and_line_thickness(gpu, K, line):
+    _check(gpu, cases.scene(300 + K, size=(150, 190), K=K, line=line))
+
+
+@pytest.mark.parametrize('n_probe', [1, 2, 3])
+def test_one_two_and_three_probes(gpu, n_probe):
+    _check(gpu, cases.scene(400 + n_probe, size=(120, 140), K=7, n_probe=n_probe))
+
+
+def test_largest_kernel_and_thickest_line(gpu):
+    case = cases.scene(500, size=(90, 140), K=7, line=16)
+    case['weights'] = cases.proj_kernel(63, 27.0)
+    _check(gpu, case)
+
+
+def test_full_size_scene_with_300_nuclei(gpu):
+    img, mask = cases.full_size_scene()
+    seg = gpu.ccl_labels(mask, 8)
+    assert np.array_equal(ref.ranks(seg)[0], ref.nuclei(mask))          # ascending raster labels = skimage's order
+    case = cases._case(img, seg, (1, 0), cases.proj_kernel(7, 3.0), 15.0, (70.0, 70.0), 7, 2)
+    _check(gpu, case)
+    rec = _run(gpu, case)[0]
+    assert 280 <= len(rec) <= 300 and rec[:, 5].sum() > 200 and rec[:, 10].sum() > 200
+    print('full-size scene: %d nuclei, %.2f ms of kernels' % (len(rec), gpu.timings()['count']))
+
+
+# ---- the protocol ---------------------------------------------------------------------------------------------------------------
+def test_capacity_protocol(gpu):
+    rng = np.random.default_rng(8)
+    H, W = 90, 100
+    seg = (rng.permutation(H * W) + 1).reshape(H, W).astype(np.int32)       # 9000 one-pixel cells
+    img = rng.integers(0, 256, (H, W, 3)).astype(np.uint8)
+    case = cases._case(img, seg, (1, 0), cases.proj_kernel(3, 1.5), 15.0, (70.0, 70.0), 1, 1)
+    assert ref.records(*cases.args(case))[3] == 0
+    for capacity in (4096, 9000, 0):
+        _check(gpu, case, capacity=capacity)
+    from ecseg_amd._lib import C, _ptr
+    n = C.c_int32()
+    thr = np.full((H, W, 2), 7, np.uint8); bnd = np.full((H, W), 7, np.uint8); rec = np.full((10, 24), -5, np.int64)
+    ch = np.array([1, 0], np.int32); it = np.array([70.0, 70.0])
+    rc = gpu.lib.ecseg_fish_spots(gpu.h, _ptr(seg), H, W, _ptr(img), 3, _ptr(ch), 2, _ptr(case['weights']), 3, 15.0, _ptr(it), 1, 1, 10,
+                                  _ptr(thr), _ptr(bnd), _ptr(rec), C.byref(n))
+    assert rc == 0 and n.value == 9000
+    assert (thr == 7).all() and (bnd == 7).all() and (rec == -5).all()     # n_cells > capacity: nothing is written
+
+
+def test_two_calls_give_identical_bytes(gpu):
+    case = cases.scene(14)
+    a = _run(gpu, case)
+    _run(gpu, cases.scene(3))
+    b = _run(gpu, case)
+    for x, y in zip(a, b):
+        assert x.tobytes() == y.tobytes()
+
+
+def test_bad_arguments_leave_the_handle_usable(gpu):
+    from ecseg_amd._lib import EcsegError
+    case, _ = HAND['pair_overlap']
+    for change, text in ((dict(probes=(1, 3)), 'channel'), (dict(probes=(0, 1, 2, 0), ithr=(1.0,) * 4), 'n_probe'),
+                         (dict(weights=np.zeros((2, 2))), 'odd'), (dict(weights=np.zeros((65, 65))), 'odd'),
+                         (dict(line=0), 'line_thickness'), (dict(line=17), 'line_thickness')):
+        bad = dict(case); bad.update(change)
+        with pytest.raises(EcsegError) as e:
+            _run(gpu, bad)
+        assert e.value.code == -1 and text in str(e.value)
+        _check(gpu, case, producer=ref.loop)
+    too_big = dict(case); too_big['seg'] = case['seg'].copy(); too_big['seg'][0, 0] = case['seg'].size + 1
+    with pytest.raises(EcsegError, match='larger than H \\* W'):
+        _run(gpu, too_big)
+    _check(gpu, case, producer=ref.loop)
+    gpu.fish_spots(case['seg'], case['img'], (1, 0), cases.NAN1, 15.0, (70.0, 70.0), 1, 1)
+    assert 0 < gpu.timings()['count'] < 1000
+
+
+def test_infinite_thresholds_switch_the_masks_off(gpu):
+    case = dict(cases.scene(14)); case['ithr'] = (float('inf'), float('inf')); case['weights'] = np.zeros((1, 1))
+    rec, thr, bnd = _run(gpu, case)
+    assert not thr.any() and bnd.any() and not rec[:, [4, 5, 9, 10, 19, 20]].any() and rec[:, 6].all()
+    _check(gpu, case)
+
+
+# ---- file level: the three interphase targets chain ------------------------------------------------------------------------------
+def test_make_stat_fish_then_fish_distances_and_the_interseg_readers(tmp_path, monkeypatch, capsys):
+    inp = tmp_path / 'in'
+    (inp / 'nuclei_masks').mkdir(parents=True)
+    scenes = {}
+    for k, name in enumerate(('img_b', 'img_a')):
+        img, mask = cases.full_size_scene(seed=5 + k)
+        img, mask = np.ascontiguousarray(img[:400, :520]), np.ascontiguousarray(mask[:400, :520])
+        image_io.write_tiff_rgb8(str(inp / (name + '.tif')), img)
+        image_io.write_tiff_gray8(str(inp / 'nuclei_masks' / (name + '.tif')), mask)
+        scenes[name] = (img, mask)
+    cfg = yaml.safe_load(open(os.path.join(ROOT, 'config.yaml')))
+    cfg['stat_fish'].update(inpath=str(inp))
+    cfg['fish_distance_calculation'].update(inpath=str(inp))
+    yaml.safe_dump(cfg, open(tmp_path / 'config.yaml', 'w'))
+    os.symlink(os.path.join(ROOT, 'src'), tmp_path / 'src')
+    os.symlink(os.path.join(ROOT, 'ecseg_amd'), tmp_path / 'ecseg_amd')
+    out = subprocess.run(['make', '-f', os.path.join(ROOT, 'Makefile'), 'stat_fish'], cwd=tmp_path, capture_output=True, text=True, timeout=900)
+    assert out.returncode == 0, out.stdout + out.stderr
+    ann = inp / 'annotated'
+    rows, dist, unreadable = [], [], 0
+    w = cases.proj_kernel(7, 3.0)
+    for name in sorted(scenes):
+        img, mask = scenes[name]
+        lab = ref.nuclei(mask)
+        rec, thr, bnd, amb = ref.records(img, lab, (1, 0), w, 15, (70, 70), 7, 2)
+        # the product computes its kernel with scipy's normal density: the same decisions unless a pixel sits inside the band
+        assert amb == 0
+        for r in rec.tolist():
+            rows.append([name, '%d_%d' % (r[2] // r[1], r[3] // r[1]), r[4], r[5], r[6] / r[7] if r[7] else 0.0, r[8],
+                         r[9], r[10], r[11] / r[12] if r[12] else 0.0, r[13], r[1], r[19], r[20]])
+        lsq = image_io.imread(str(ann / name / (name + '_lsq_n15_std3.00_s7_g70.0_r70.0.tif')))
+        assert np.array_equal(lsq, np.dstack([thr[..., 1], thr[..., 0], bnd]))
+        assert np.array_equal(np.load(ann / name / (name + '__segmentation_min_cut.npy')), lab)
+        try:
+            dist += fd_ref.loop(lsq, lab, (1, 0, 3))
+        except ValueError:                                   # a nucleus with FISH but no centromere pixels: the reference stops there
+            unreadable += 1
+        # what make interseg reads: the mask and the table
+        I, seg = interseg._load_image(str(inp / (name + '.tif')), str(ann / name / (name + '_segmentation.tif')))
+        assert np.array_equal(seg, mask) and np.array_equal(I, img)
+    from ecseg_amd import stat_fish as sf
+    assert open(ann / 'stat_fish_lsq.csv').read() == csvio.csv_text(sf.csv_columns(), rows) and len(rows) > 30
+    table = interseg.read_stat_fish(str(ann / 'stat_fish_lsq.csv'))
+    want = interseg.kurtosis([r[8] for r in rows if r[0] == 'img_a'])
+    assert interseg.quality_score(table, 'img_a', 'red') == want
+    monkeypatch.chdir(tmp_path)
+    code = 0
+    try:
+        fdc.main([])
+    except SystemExit as e:
+        code = e.code
+    assert code == (1 if unreadable else 0) and unreadable < len(scenes)
+    assert open(inp / 'centromere_distances.csv').read() == csvio.csv_text(['normalized_distance'], [[v] for v in dist]) and len(dist) > 5
