@@ -16,7 +16,7 @@ EXPORTS = [
     'ecseg_segment_images', 'ecseg_segment_images_ex', 'ecseg_segment_images_dev', 'ecseg_set_images_per_group', 'ecseg_set_option', 'ecseg_preprocess', 'ecseg_u16_to_u8',
     'ecseg_meta_segment', 'ecseg_prefetch_input', 'ecseg_host_alloc', 'ecseg_host_free',
     'ecseg_stitch_argmax', 'ecseg_meta_inference', 'ecseg_meta_inference_dev', 'ecseg_count_cc', 'ecseg_ccl_labels',
-    'ecseg_count_colocalization', 'ecseg_count_hsr', 'ecseg_overlay', 'ecseg_nuclei_regions', 'ecseg_nucleus_crops', 'ecseg_fish_distances', 'ecseg_fish_spots', 'ecseg_get_timings',
+    'ecseg_count_colocalization', 'ecseg_count_hsr', 'ecseg_overlay', 'ecseg_nuclei_regions', 'ecseg_nucleus_crops', 'ecseg_fish_distances', 'ecseg_fish_spots', 'ecseg_min_cut', 'ecseg_get_timings',
     'ecseg_set_kernel_profiling', 'ecseg_get_conv_profile', 'ecseg_get_conv_executed_flops', 'ecseg_get_conv_launch_profile', 'ecseg_debug_peek', 'ecseg_lzw_decode', 'ecseg_lzw_encode',
     'ecseg_comm_unique_id', 'ecseg_comm_create', 'ecseg_comm_destroy', 'ecseg_comm_last_error', 'ecseg_allgather_records', 'ecseg_allgather_records_dev',
     'ecseg_npy_write_i64', 'ecseg_png_write_labels', 'ecseg_png_write', 'ecseg_png_write_channel', 'ecseg_npy_label_info', 'ecseg_npy_read_labels_u8', 'ecseg_tiff_write_gray8', 'ecseg_tiff_info', 'ecseg_tiff_read',
@@ -101,6 +101,7 @@ def load_library():
     lib.ecseg_fish_distances.argtypes = [vp, vp, i32, i32, u8p, i32, i32, i32, i32, vp, C.POINTER(C.c_int32)]
     lib.ecseg_fish_spots.argtypes = [vp, vp, i32, i32, u8p, i32, vp, i32, vp, i32, C.c_double, vp, i32, i32, i32, vp, vp, vp,
                                      C.POINTER(C.c_int32)]
+    lib.ecseg_min_cut.argtypes = [vp, vp, C.c_longlong, vp, i32, i32, vp, vp]
     lib.ecseg_get_timings.argtypes = [vp, vp]
     lib.ecseg_set_kernel_profiling.argtypes = [vp, i32]
     lib.ecseg_get_conv_profile.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double)]
@@ -520,6 +521,30 @@ class Handle:
             if n.value <= cap:
                 return rec[:n.value], thr, bnd
             cap = n.value
+
+    # ---- min-cut splitter -------------------------------------------------------------------------------
+    MIN_CUT_MAX_DIST = 32          # ECSEG_MIN_CUT_MAX_DIST
+    MIN_CUT_LDS_PIXELS = 10240     # ECSEG_MIN_CUT_LDS_PIXELS
+
+    def min_cut(self, tasks, dist):
+        """A batch of max-flow tasks (ecseg_min_cut; the network is in include/ecseg_hip.h).  ``tasks``: a sequence of
+        (window, source, sink) with window a 2-D uint8 / bool array, non-zero = pixel, and source / sink (row, column) pixels of
+        it -> (list of uint8 windows, 1 = on the source's side of the minimal minimum cut, int32 array of the max-flow values)."""
+        wins = [_u8(t[0]) for t in tasks]
+        if any(w.ndim != 2 for w in wins):
+            raise ValueError('min_cut takes 2-D windows')
+        desc = np.zeros((len(wins), 8), np.int32)
+        offs = np.concatenate([[0], np.cumsum([w.size for w in wins], dtype=np.int64)]).astype(np.int64)
+        if offs[-1] >= 2 ** 31:
+            raise ValueError('min_cut: the windows of one call must stay below 2^31 bytes')
+        for k, (w, t) in enumerate(zip(wins, tasks)):
+            desc[k, :7] = (offs[k], w.shape[0], w.shape[1], int(t[1][0]), int(t[1][1]), int(t[2][0]), int(t[2][1]))
+        packed = np.concatenate([w.reshape(-1) for w in wins]) if wins else np.zeros(0, np.uint8)
+        side = np.zeros(packed.size, np.uint8)
+        flow = np.zeros(len(wins), np.int32)
+        self._check(self.lib.ecseg_min_cut(self.h, _ptr(packed), packed.size, _ptr(desc), len(wins), int(dist), _ptr(side), _ptr(flow)),
+                    'ecseg_min_cut')
+        return [side[offs[k]:offs[k + 1]].reshape(w.shape) for k, w in enumerate(wins)], flow
 
     # ---- timing ---------------------------------------------------------------------------------------
     def timings(self):

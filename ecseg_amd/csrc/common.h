@@ -249,4 +249,13 @@ struct FishSpotBufs { int32_t* rid; int32_t* mx; uint8_t* thr; uint8_t* bnd; int
 hipError_t run_fishspot(int32_t* labels, const uint8_t* img, int H, int W, int C, int np, const int ch[3], const double* wts, int K,
                         double normal_thr, const double ithr[3], int min_cc, int line_t, int n, const FishSpotBufs& b, hipStream_t s);
 
+// ---- launcher implemented in mincut_kernels.hip (src/max_flow_binary_mask.py:59-116) -----------------------------------------
+// n_tasks tasks of ecseg_min_cut, one workgroup each.  desc: (n_tasks, 8) int32 as the entry point takes them, validated by the
+// caller; soff: per task the byte offset of its mincut_scratch_bytes(h, w) bytes in `scratch` (16-byte aligned), or < 0 for a
+// window of at most ECSEG_MIN_CUT_LDS_PIXELS pixels whose state stays in LDS.  side: as masks, written over every window.
+size_t mincut_scratch_bytes(int h, int w);
+// n_global: how many tasks have soff >= 0 (a kernel without tasks is not launched).
+hipError_t run_mincut(const uint8_t* masks, const int32_t* desc, const long long* soff, int n_tasks, int n_global, int d, uint8_t* scratch,
+                      uint8_t* side, int32_t* flow, hipStream_t s);
+
 }  // namespace ecseg

@@ -136,6 +136,10 @@ struct DevMem {
     DevBuf<unsigned long long> d_fs_acc;
     DevBuf<unsigned> d_fs_cnt;
     DevBuf<int64_t> d_fs_rec;
+    // ecseg_min_cut: the packed windows, their sides, the task table and the state of the windows too large for LDS
+    DevBuf<uint8_t> d_mc_mask, d_mc_side, d_mc_scratch;
+    DevBuf<int32_t> d_mc_desc, d_mc_flow;
+    DevBuf<long long> d_mc_soff;
 };
 
 }  // namespace ecseg
@@ -171,6 +175,7 @@ struct ecseg_ctx : ecseg::DevMem {
     const void* next_host = nullptr; size_t next_bytes = 0;   // registered by ecseg_prefetch_input for the coming call to send ahead
     hipStream_t stream_in = nullptr;
     hipEvent_t ev_pre = nullptr;
+    int min_cut_lds_pixels = ECSEG_MIN_CUT_LDS_PIXELS;   // windows above this many pixels keep their state in global memory (tests lower it)
     int iseg_H = 0, iseg_W = 0, iseg_img_w = 0, iseg_C = 0, iseg_n = -1;   // iseg_n < 0: no region map on the handle
     int post_chunk = 64;
     int overlap_post = 0;

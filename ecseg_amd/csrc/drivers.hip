@@ -1,5 +1,5 @@
 // The one-call drivers: each uploads its inputs, runs one family of kernels on the main stream and downloads the results
-// (u16_to_u8, stitch_argmax, meta_inference, the counts, overlay, the interSeg regions / crops, the FISH distances, the FISH spots).
+// (u16_to_u8, stitch_argmax, meta_inference, the counts, overlay, the interSeg regions / crops, the FISH distances, the FISH spots, the min-cut tasks).
 #include "ctx.h"
 
 using namespace ecseg;
@@ -411,6 +411,67 @@ int ecseg_fish_spots(ecseg_ctx* h, const int32_t* labels, int H, int W, const ui
     HIP_TRY(h, hipMemcpyAsync(records, h->d_fs_rec, nn * ECSEG_FISH_SPOT_INT64 * sizeof(int64_t), hipMemcpyDeviceToHost, s));
     HIP_TRY(h, hipStreamSynchronize(s));
     h->stage_ms[ECSEG_T_COUNT] += stage_elapsed(h->ev[2], h->ev[3]);
+    return ECSEG_OK;
+}
+
+// ---- the min-cut splitter's max-flow tasks (src/max_flow_binary_mask.py:59-116) ------------------------------------------------
+int ecseg_min_cut(ecseg_ctx* h, const uint8_t* masks, long long mask_bytes, const int32_t* tasks, int n_tasks, int dist, uint8_t* side,
+                  int32_t* flow) {
+    if (!h) return ECSEG_E_INVALID;
+    drop_sent_ahead(h);
+    if (n_tasks < 0 || mask_bytes < 0 || (n_tasks > 0 && (!masks || !tasks || !side || !flow)))
+        return fail(h, ECSEG_E_INVALID, "min_cut: bad arguments");
+    if (dist < 1 || dist > ECSEG_MIN_CUT_MAX_DIST)
+        return fail(h, ECSEG_E_INVALID, "min_cut: dist must be between 1 and " + std::to_string(ECSEG_MIN_CUT_MAX_DIST));
+    if (mask_bytes > ECSEG_MIN_CUT_MAX_BYTES)
+        return fail(h, ECSEG_E_INVALID, "min_cut: more than " + std::to_string(ECSEG_MIN_CUT_MAX_BYTES) + " bytes of windows in one call");
+    for (float& v : h->stage_ms) v = 0.f;
+    if (n_tasks == 0) return ECSEG_OK;
+    std::vector<long long> soff((size_t)n_tasks, -1);
+    long long end = 0;
+    size_t scratch = 0;
+    int n_global = 0;
+    for (int i = 0; i < n_tasks; ++i) {
+        const int32_t* t = tasks + 8 * (size_t)i;
+        const std::string who = "min_cut: task " + std::to_string(i);
+        const long long off = t[0], th = t[1], tw = t[2];
+        if (th < 1 || tw < 1 || th * tw > ECSEG_MIN_CUT_MAX_PIXELS)
+            return fail(h, ECSEG_E_INVALID, who + ": the window must hold between 1 and " + std::to_string(ECSEG_MIN_CUT_MAX_PIXELS) + " pixels");
+        if (off < end || off + th * tw > mask_bytes)
+            return fail(h, ECSEG_E_INVALID, who + ": the window overlaps the one in front or leaves the buffer");
+        end = off + th * tw;
+        if (t[3] < 0 || t[3] >= th || t[4] < 0 || t[4] >= tw || t[5] < 0 || t[5] >= th || t[6] < 0 || t[6] >= tw)
+            return fail(h, ECSEG_E_INVALID, who + ": source or sink outside the window");
+        if (t[3] == t[5] && t[4] == t[6]) return fail(h, ECSEG_E_INVALID, who + ": source and sink are the same pixel");
+        if (!masks[off + t[3] * tw + t[4]] || !masks[off + t[5] * tw + t[6]])
+            return fail(h, ECSEG_E_INVALID, who + ": source or sink on a zero pixel");
+        if (th * tw > h->min_cut_lds_pixels) {
+            soff[(size_t)i] = (long long)scratch;
+            ++n_global;
+            scratch += mincut_scratch_bytes((int)th, (int)tw);
+        }
+    }
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t nb = (size_t)mask_bytes, nt = (size_t)n_tasks;
+    int rc;
+    if ((rc = h->d_mc_mask.ensure(h, nb))) return rc;
+    if ((rc = h->d_mc_side.ensure(h, nb))) return rc;
+    if ((rc = h->d_mc_desc.ensure(h, nt * 8))) return rc;
+    if ((rc = h->d_mc_soff.ensure(h, nt))) return rc;
+    if ((rc = h->d_mc_flow.ensure(h, nt))) return rc;
+    if ((rc = h->d_mc_scratch.ensure(h, scratch))) return rc;
+    hipStream_t s = h->stream;
+    HIP_TRY(h, hipMemcpyAsync(h->d_mc_mask, masks, nb, hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(h->d_mc_desc, tasks, nt * 8 * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(h->d_mc_soff, soff.data(), nt * sizeof(long long), hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemsetAsync(h->d_mc_side, 0, nb, s));
+    HIP_TRY(h, hipEventRecord(h->ev[0], s));
+    HIP_TRY(h, run_mincut(h->d_mc_mask, h->d_mc_desc, h->d_mc_soff, n_tasks, n_global, dist, h->d_mc_scratch, h->d_mc_side, h->d_mc_flow, s));
+    HIP_TRY(h, hipEventRecord(h->ev[1], s));
+    HIP_TRY(h, hipMemcpyAsync(side, h->d_mc_side, nb, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipMemcpyAsync(flow, h->d_mc_flow, nt * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));                     // (soff is read by the copy above: it lives until here)
+    h->stage_ms[ECSEG_T_COUNT] = stage_elapsed(h->ev[0], h->ev[1]);
     return ECSEG_OK;
 }
 

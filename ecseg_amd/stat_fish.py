@@ -4,7 +4,9 @@
 The nucleus mask of every image is read from ``<masks>/<name>.tif`` (config key ``masks``, default ``<inpath>/nuclei_masks``):
 NuSeT, whose TF1 checkpoints this project cannot load, stays out of scope, and any segmenter writing an 8-bit single-sample
 TIFF there, non-zero = nucleus, will do.  Per image the nuclei are labelled on the device (``Handle.ccl_labels``, 8-connected,
-skimage's order) and one more device call (``Handle.fish_spots`` -> ecseg_fish_spots, csrc/fishspot_kernels.hip) returns the
+skimage's order) - or, with ``use_min_cut: True``, labelled 4-connected and split by the min-cut splitter (src/max_flow_binary_mask.py
+-> ecseg_amd/min_cut.py, whose maximum flows run on the device: ``Handle.min_cut``), which also adds the sixth file
+``<name>_segmentation_corrected_min_cut.tif`` - and one more device call (``Handle.fish_spots`` -> ecseg_fish_spots, csrc/fishspot_kernels.hip) returns the
 per-nucleus integers, the cleaned spot masks and the boundary drawing; the host computes the projected Gaussian kernel
 (src/stat_fish.py:28-55) with numpy / scipy, forms the means as ``sum / count`` in float64 (exact: the sums are far below
 2^53) and writes the five files per image and ``stat_fish_lsq.csv``.  ``make interseg`` and ``make fish_distance_calculation``
@@ -25,8 +27,8 @@ Divergences from the reference, all on inputs it crashes on or leaves to chance:
 per-image failure (missing mask, unreadable file, 4-channel image - the two-entry ``color_sensitivity`` cannot broadcast over
 three probes in the reference either -, 16-bit TIFF - ``cv2.imread``'s internal 16-to-8 conversion cannot be pinned without
 OpenCV -) is reported, skipped and turns the exit code to 1 while the other images' outputs are still written;
-configuration errors exit with code 2; ``use_min_cut: True`` is a configuration error (the min-cut splitter,
-src/max_flow_binary_mask.py, is not built); integer CSV columns are always written as integers (pandas promotes them to
+configuration errors exit with code 2; ``use_min_cut: True`` is one of them when the handle in use has no ``min_cut`` method (the
+library's own ``Handle`` has it; the max_flow_binary_mask splitter needs its device call); integer CSV columns are always written as integers (pandas promotes them to
 float when it concatenates an image without nuclei with others).  Kept as in the reference: with ``scale: auto`` the scale
 of the FIRST image is used for every later image (:228 overwrites the variable).
 """
@@ -49,11 +51,14 @@ DEFAULT_PARAMS = {
     'gaussian_sigma': 3,
     'kernel_size': [7, 7],
     'target_median_nuclei_size': 2500,
+    'cell_size_threshold_coeff': 1.25,
+    'flow_limit': 60,
 }
 PARAMS_FILE = os.path.join('src', 'stat_fish_params.yaml')
 PROBE_NAMES = ('green', 'red')
 MAX_KERNEL = 63                # ECSEG_FISH_SPOT_MAX_KERNEL
 MAX_LINE = 16                  # ECSEG_FISH_SPOT_MAX_LINE
+MAX_DIST = 32                  # ECSEG_MIN_CUT_MAX_DIST
 
 
 class ConfigError(Exception):
@@ -182,8 +187,9 @@ def read_mask(path):
     return (m != 0).astype(np.uint8) * np.uint8(255)
 
 
-def process_image(path, mask_path, out_root, params, scale, handle, stats=None):
-    """One image of src/stat_fish.py:199-308 -> (CSV rows, the scale that was used)."""
+def process_image(path, mask_path, out_root, params, scale, handle, stats=None, use_min_cut=False):
+    """One image of src/stat_fish.py:199-308 -> (CSV rows, the scale that was used).  ``use_min_cut`` (:221-224): the label map comes
+    from the min-cut splitter, already numbered 1..n (its cells need not be connected, which ecseg_fish_spots allows)."""
     import time
     from . import image_io
     t0 = time.perf_counter()
@@ -198,8 +204,13 @@ def process_image(path, mask_path, out_root, params, scale, handle, stats=None):
     t1 = time.perf_counter()
     probes = [green, red]
     line = params['line_thickness']
+    visualization = None
     try:
-        labels = handle.ccl_labels(mask, 8)
+        if use_min_cut:
+            from .min_cut import binary_seg_to_instance_min_cut
+            labels, visualization = binary_seg_to_instance_min_cut(mask, params['flow_limit'], params['cell_size_threshold_coeff'], handle=handle)
+        else:
+            labels = handle.ccl_labels(mask, 8)
         off = ([[0.0]], float('inf'), [float('inf')] * len(probes), 1)     # a call for the regions alone
         if scale == 'auto':
             rec, _, _ = handle.fish_spots(labels, I, probes, off[0], off[1], off[2], off[3], line)
@@ -234,6 +245,9 @@ def process_image(path, mask_path, out_root, params, scale, handle, stats=None):
     image_io.write_tiff_rgb8(os.path.join(annotated_path, img_name + '_original_with_segmentation.tif'), with_segmentation(original, bnd, 1))
     image_io.write_tiff_rgb8(os.path.join(annotated_path, img_name + '_original.tif'), original)
     image_io.write_tiff_rgb8(os.path.join(annotated_path, lsq_name(img_name, params, stdev, min_cc)), lsq)
+    if visualization is not None:                            # (:304-305) cv2 writes its (r, g, b) array as if it were BGR: the file holds (b, g, r)
+        image_io.write_tiff_rgb8(os.path.join(annotated_path, img_name + '_segmentation_corrected_min_cut.tif'),
+                                 np.ascontiguousarray(visualization[..., ::-1]))
     if stats is not None:
         for key, v in (('read', t1 - t0), ('device', t2 - t1), ('write', time.perf_counter() - t2)):
             stats[key] = stats.get(key, 0.0) + v
@@ -265,6 +279,12 @@ def load_params():
     ks = params['kernel_size']
     if not isinstance(ks, list) or len(ks) != 2 or not all(number(v) and v > 0 for v in ks):
         raise ConfigError('kernel_size must be a list of two positive numbers')
+    if not number(params['cell_size_threshold_coeff']) or not params['cell_size_threshold_coeff'] >= 0:
+        raise ConfigError('cell_size_threshold_coeff must be a non-negative number')
+    fl = params['flow_limit']
+    if not number(fl) or not fl >= 0 or math.isinf(fl) or not 1 <= (-1 + int(math.sqrt(1 + 2 * fl))) // 2 <= MAX_DIST:
+        raise ConfigError('flow_limit must give a distance (-1 + int(sqrt(1 + 2 * flow_limit))) // 2 between 1 and %d (flow_limit 4 .. 2243)'
+                          % MAX_DIST)
     lt = params['line_thickness']
     if isinstance(lt, bool) or not isinstance(lt, int) or not 1 <= lt <= MAX_LINE:
         raise ConfigError('line_thickness must be an integer between 1 and %d' % MAX_LINE)
@@ -283,7 +303,7 @@ def current_commit():
 def main(argv=None, handle=None):
     """``make stat_fish``.  Like the reference's ``main`` it takes everything from section ``stat_fish`` of ``config.yaml`` in
     the working directory; ``argv`` is accepted for the shim's sake and not read.  ``handle`` is an injection point for tests and
-    tools (anything with ``Handle.ccl_labels``, ``fish_spots`` and ``u16_to_u8``); without it the call opens a handle on device 0
+    tools (anything with ``Handle.ccl_labels``, ``fish_spots`` and ``u16_to_u8``, and ``min_cut`` for ``use_min_cut: True``); without it the call opens a handle on device 0
     and closes it at the end."""
     import yaml
     from . import csvio
@@ -299,9 +319,10 @@ def main(argv=None, handle=None):
         inpath = str(var['inpath'])
         if not os.path.isdir(inpath):
             raise ConfigError('Input folder does not exist. Exiting...')
-        if var['use_min_cut']:
-            raise ConfigError('use_min_cut: True needs the min-cut splitter (src/max_flow_binary_mask.py), which is not built: '
-                              'set use_min_cut: False in config.yaml')
+        use_min_cut = bool(var['use_min_cut'])
+        if use_min_cut and handle is not None and not hasattr(handle, 'min_cut'):
+            raise ConfigError('use_min_cut: True needs the min-cut splitter (src/max_flow_binary_mask.py), whose device call the handle in use '
+                              'does not have: set use_min_cut: False in config.yaml')
         scale = var['scale']
         if scale != 'auto' and (isinstance(scale, bool) or not isinstance(scale, (int, float)) or not scale > 0 or math.isinf(scale)):
             raise ConfigError('scale must be a positive number or "auto"')
@@ -336,7 +357,8 @@ def main(argv=None, handle=None):
         for p in image_paths:
             print("Processing image: ", p)
             try:
-                img_rows, scale = process_image(p, os.path.join(masks, os.path.basename(p)[:-4] + '.tif'), out_root, params, scale, handle)
+                img_rows, scale = process_image(p, os.path.join(masks, os.path.basename(p)[:-4] + '.tif'), out_root, params, scale, handle,
+                                                 use_min_cut=use_min_cut)
                 rows += img_rows
             except ImageError as e:
                 print(p, '-', e)

@@ -198,7 +198,8 @@ int ecseg_set_images_per_group(ecseg_ctx* h, int n);
  * a launch group of <= 70 windows (one or two 1040x1392 images) runs its U-Net as two window lanes on their own streams, which fills
  * the half-empty last round of workgroups of the deep layers (one image: 11.3 -> 10.4 ms); 1..8: that many lanes; results are
  * bit-identical for every value), "blocking_wait" (1 (default): the wait for a launch group sleeps on an event created
- * with hipEventBlockingSync; 0: hipStreamSynchronize). */
+ * with hipEventBlockingSync; 0: hipStreamSynchronize), "min_cut_lds_pixels" (0 .. ECSEG_MIN_CUT_LDS_PIXELS (default): windows of
+ * ecseg_min_cut with more pixels than this keep their state in global memory instead of LDS; the results do not depend on it). */
 int ecseg_set_option(ecseg_ctx* h, const char* key, int value);
 
 /* ---- meta_preprocess (src/image_tools.py:86-101) ---------------------------------------------------------- */
@@ -354,6 +355,35 @@ int ecseg_fish_spots(ecseg_ctx* h, const int32_t* labels, int H, int W, const ui
                      int n_probe, const double* weights, int K, double normal_threshold, const double* intensity_thresholds,
                      int min_cc_size, int line_thickness, int capacity, uint8_t* thresholded, uint8_t* boundaries,
                      int64_t* records, int32_t* n_cells);
+
+/* ---- the min-cut nucleus splitter: a batch of grid max-flows (src/max_flow_binary_mask.py:59-116) ------------------------- */
+/* Replaces get_graph + max_flow + partition_min_cut (:59-116) for a BATCH of independent tasks; segment_min_cut's recursion
+ * (:119-140) stays with the caller, who sends all tasks of one recursion depth over all nuclei of an image in one call.
+ * masks: mask_bytes bytes holding the windows back to back; tasks: (n_tasks, 8) int32 per task
+ *   [0] offset of the window in masks  [1] h  [2] w  [3] source row  [4] source column  [5] sink row  [6] sink column  [7] 0,
+ * the window M being h x w uint8 in row-major order, non-zero = pixel; windows lie in ascending order and do not overlap.
+ * dist (d) is shared by all tasks.  The network of one task, with s the source and t the sink pixel:
+ *   Body pixels: the pixels with M != 0 other than s and t.
+ *   Unit-capacity arcs:
+ *     s -> p for body pixels with |p - s|_1 <= d;
+ *     p -> t for body pixels with |p - t|_1 <= d that are NOT within d of s (the source ball wins: the reference uses `elif`);
+ *     p -> q for every body pixel p and each 4-neighbour q inside the window with M[q] != 0; q may be s or t.
+ *   A body pixel next to t and inside its ball therefore has capacity 2 into t: two parallel arcs, both kept.
+ *   s has no arcs except to its ball.  Nothing leaves t.
+ * Outputs: side (mask_bytes bytes, laid out as masks; bytes outside every window are 0): per window pixel 1 = reachable from s
+ * in the residual network of a maximum flow, s included, else 0 - the source side of the minimal minimum cut, which is the
+ * same set for every maximum flow, so no augmentation order can change it; flow (n_tasks int32): the max-flow value.
+ * One synchronous call, buffers of its own, device time of the kernel in ECSEG_T_COUNT; n_tasks = 0 is allowed and does
+ * nothing.  ECSEG_E_INVALID: s == t; s or t outside the window or on a zero pixel; d < 1 or d > ECSEG_MIN_CUT_MAX_DIST; h or
+ * w < 1 or h * w > ECSEG_MIN_CUT_MAX_PIXELS (2048 x 2048); mask_bytes > ECSEG_MIN_CUT_MAX_BYTES; a window that leaves masks or
+ * starts before the end of the one in front.  Windows of up to ECSEG_MIN_CUT_LDS_PIXELS pixels are solved in LDS, larger ones in a
+ * scratch region of 6 bytes per pixel (ECSEG_E_NOMEM when the device cannot hold it). */
+#define ECSEG_MIN_CUT_MAX_DIST   32
+#define ECSEG_MIN_CUT_MAX_PIXELS (1 << 22)
+#define ECSEG_MIN_CUT_MAX_BYTES  (1 << 28)
+#define ECSEG_MIN_CUT_LDS_PIXELS 10240
+int ecseg_min_cut(ecseg_ctx* h, const uint8_t* masks, long long mask_bytes, const int32_t* tasks, int n_tasks, int dist, uint8_t* side,
+                  int32_t* flow);
 
 /* ---- per-stage device timings of the last segment call (milliseconds, HIP events on the handle's stream) -- */
 /* ECSEG_T_COUNT: device time of the kernels of the last ecseg_overlay / ecseg_preprocess / ecseg_count_* call (inputs
