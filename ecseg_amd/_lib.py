@@ -16,7 +16,7 @@ EXPORTS = [
     'ecseg_segment_images', 'ecseg_segment_images_ex', 'ecseg_segment_images_dev', 'ecseg_set_images_per_group', 'ecseg_set_option', 'ecseg_preprocess', 'ecseg_u16_to_u8',
     'ecseg_meta_segment', 'ecseg_prefetch_input', 'ecseg_host_alloc', 'ecseg_host_free',
     'ecseg_stitch_argmax', 'ecseg_meta_inference', 'ecseg_meta_inference_dev', 'ecseg_count_cc', 'ecseg_ccl_labels',
-    'ecseg_count_colocalization', 'ecseg_count_hsr', 'ecseg_overlay', 'ecseg_nuclei_regions', 'ecseg_nucleus_crops', 'ecseg_fish_distances', 'ecseg_fish_spots', 'ecseg_min_cut', 'ecseg_get_timings',
+    'ecseg_count_colocalization', 'ecseg_count_hsr', 'ecseg_overlay', 'ecseg_nuclei_regions', 'ecseg_nucleus_crops', 'ecseg_fish_distances', 'ecseg_fish_spots', 'ecseg_min_cut', 'ecseg_nuset_forward', 'ecseg_rpn_proposals', 'ecseg_rpn_proposals_last', 'ecseg_get_timings',
     'ecseg_set_kernel_profiling', 'ecseg_get_conv_profile', 'ecseg_get_conv_executed_flops', 'ecseg_get_conv_launch_profile', 'ecseg_debug_peek', 'ecseg_lzw_decode', 'ecseg_lzw_encode',
     'ecseg_comm_unique_id', 'ecseg_comm_create', 'ecseg_comm_destroy', 'ecseg_comm_last_error', 'ecseg_allgather_records', 'ecseg_allgather_records_dev',
     'ecseg_npy_write_i64', 'ecseg_png_write_labels', 'ecseg_png_write', 'ecseg_png_write_channel', 'ecseg_npy_label_info', 'ecseg_npy_read_labels_u8', 'ecseg_tiff_write_gray8', 'ecseg_tiff_info', 'ecseg_tiff_read',
@@ -102,6 +102,9 @@ def load_library():
     lib.ecseg_fish_spots.argtypes = [vp, vp, i32, i32, u8p, i32, vp, i32, vp, i32, C.c_double, vp, i32, i32, i32, vp, vp, vp,
                                      C.POINTER(C.c_int32)]
     lib.ecseg_min_cut.argtypes = [vp, vp, C.c_longlong, vp, i32, i32, vp, vp]
+    lib.ecseg_nuset_forward.argtypes = [vp, vp, i32, i32, i32, i32, vp]
+    lib.ecseg_rpn_proposals.argtypes = [vp, vp, vp, i32, i32, i32, vp, i32, i32, i32, C.c_float, i32, i32, C.POINTER(C.c_int32), vp, vp, vp]
+    lib.ecseg_rpn_proposals_last.argtypes = [vp, i32, vp, i32, i32, i32, C.c_float, i32, i32, C.POINTER(C.c_int32), vp, vp, vp]
     lib.ecseg_get_timings.argtypes = [vp, vp]
     lib.ecseg_set_kernel_profiling.argtypes = [vp, i32]
     lib.ecseg_get_conv_profile.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double)]
@@ -545,6 +548,57 @@ class Handle:
         self._check(self.lib.ecseg_min_cut(self.h, _ptr(packed), packed.size, _ptr(desc), len(wins), int(dist), _ptr(side), _ptr(flow)),
                     'ecseg_min_cut')
         return [side[offs[k]:offs[k + 1]].reshape(w.shape) for k, w in enumerate(wins)], flow
+
+    # ---- NuSeT's network stage ---------------------------------------------------------------------------
+    RPN_MAX_CANDIDATES = 1 << 22   # ECSEG_RPN_MAX_CANDIDATES
+    RPN_MAX_PRE_NMS = 8192         # ECSEG_RPN_MAX_PRE_NMS
+
+    def nuset_forward(self, x, cls_tensor, bbox_tensor):
+        """(H, W) float32 normalised image -> uint8 (H, W) argmax mask of the loaded plan's 2-channel logits (ecseg_nuset_forward).
+        ``cls_tensor`` / ``bbox_tensor``: the plan's RPN tensors (``plan.layer_tensor``), which stay on the handle for
+        ``rpn_proposals_last``."""
+        if self.plan is None:
+            raise EcsegError('no model loaded')
+        a = np.ascontiguousarray(x, np.float32)
+        if a.ndim != 2:
+            raise ValueError('nuset_forward takes one (H, W) image')
+        mask = np.empty(a.shape, np.uint8)
+        self._check(self.lib.ecseg_nuset_forward(self.h, _ptr(a), a.shape[0], a.shape[1], int(cls_tensor), int(bbox_tensor), _ptr(mask)),
+                    'ecseg_nuset_forward')
+        return mask
+
+    @staticmethod
+    def _rpn_args(ref_anchors, pre_nms_top_n, post_nms_top_n):
+        ref = np.ascontiguousarray(ref_anchors, np.float64)
+        if ref.ndim != 2 or ref.shape[1] != 4:
+            raise ValueError('ref_anchors must be (A, 4) float64')
+        cap = max(min(int(post_nms_top_n), int(pre_nms_top_n)), 1)
+        return ref, np.empty(cap, np.float32), np.empty((cap, 4), np.float32), np.empty(cap, np.int32)
+
+    def rpn_proposals(self, cls_score, bbox_pred, ref_anchors, stride, im_h, im_w, nms_threshold, pre_nms_top_n=6000, post_nms_top_n=800):
+        """RPNProposal on host tensors (ecseg_rpn_proposals; the arithmetic is in include/ecseg_hip.h): ``cls_score`` (fh, fw, 2A) and
+        ``bbox_pred`` (fh, fw, 4A) float32, ``ref_anchors`` (A, 4) float64 -> (scores float32 (n,) descending, proposals float32 (n, 4)
+        as (x1, y1, x2, y2), int32 (n,) flat indices (y * fw + x) * A + a of the selected candidates)."""
+        ref, sc, pr, ix = self._rpn_args(ref_anchors, pre_nms_top_n, post_nms_top_n)
+        c = np.ascontiguousarray(cls_score, np.float32)
+        b = np.ascontiguousarray(bbox_pred, np.float32)
+        A = ref.shape[0]
+        if c.ndim != 3 or b.ndim != 3 or c.shape[2] != 2 * A or b.shape != c.shape[:2] + (4 * A,):
+            raise ValueError('rpn_proposals takes (fh, fw, 2A) scores and (fh, fw, 4A) deltas for (A, 4) reference anchors')
+        n = C.c_int32()
+        self._check(self.lib.ecseg_rpn_proposals(self.h, _ptr(c), _ptr(b), c.shape[0], c.shape[1], A, _ptr(ref), int(stride), int(im_h), int(im_w),
+                                                 float(nms_threshold), int(pre_nms_top_n), int(post_nms_top_n), C.byref(n), _ptr(sc), _ptr(pr),
+                                                 _ptr(ix)), 'ecseg_rpn_proposals')
+        return sc[:n.value], pr[:n.value], ix[:n.value]
+
+    def rpn_proposals_last(self, ref_anchors, stride, im_h, im_w, nms_threshold, pre_nms_top_n=6000, post_nms_top_n=800):
+        """The same on the RPN tensors the last ``nuset_forward`` left on the device (ecseg_rpn_proposals_last)."""
+        ref, sc, pr, ix = self._rpn_args(ref_anchors, pre_nms_top_n, post_nms_top_n)
+        n = C.c_int32()
+        self._check(self.lib.ecseg_rpn_proposals_last(self.h, ref.shape[0], _ptr(ref), int(stride), int(im_h), int(im_w), float(nms_threshold),
+                                                      int(pre_nms_top_n), int(post_nms_top_n), C.byref(n), _ptr(sc), _ptr(pr), _ptr(ix)),
+                    'ecseg_rpn_proposals_last')
+        return sc[:n.value], pr[:n.value], ix[:n.value]
 
     # ---- timing ---------------------------------------------------------------------------------------
     def timings(self):

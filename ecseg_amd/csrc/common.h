@@ -258,4 +258,18 @@ size_t mincut_scratch_bytes(int h, int w);
 hipError_t run_mincut(const uint8_t* masks, const int32_t* desc, const long long* soff, int n_tasks, int n_global, int d, uint8_t* scratch,
                       uint8_t* side, int32_t* flow, hipStream_t s);
 
+// ---- launchers implemented in nuset_kernels.hip (src/utils.py:53, src/model_layers/rpn_proposal.py) ---------------------------
+// mask (h * w uint8) = argmax over the 2 channels of `logits`, a tie giving 0.
+hipError_t launch_argmax2(const TView& logits, uint8_t* mask, hipStream_t s);
+// Device buffers of one proposal call over N = fh * fw * A candidates: boxes (N float4), scores (N float), keys (rpn_sort_len(N)
+// uint64), mat (K * ceil(K / 64) uint64 with K = min(pre_nms_top_n, N)), misc (2 int32: n_out, kept candidates) and the outputs
+// (post_nms_top_n entries each).
+struct RpnBufs { float4* boxes; float* scores; unsigned long long* keys; unsigned long long* mat; int32_t* misc; float* out_scores;
+                 float4* out_boxes; int32_t* out_idx; };
+int rpn_sort_len(int N);      // N padded to the power of two the sort works on
+// cls / bbox: (fh, fw, 2A) / (fh, fw, 4A) float32 on the device, consecutive pixels cls_cs / bbox_cs floats apart; ref: A x 4
+// float64 on the device.  The arguments are validated by the caller (ecseg_rpn_proposals).
+hipError_t run_rpn_proposals(const float* cls, int cls_cs, const float* bbox, int bbox_cs, const double* ref, int fh, int fw, int A, int stride,
+                             int im_h, int im_w, float nms_threshold, int pre, int post, const RpnBufs& b, hipStream_t s);
+
 }  // namespace ecseg

@@ -140,6 +140,13 @@ struct DevMem {
     DevBuf<uint8_t> d_mc_mask, d_mc_side, d_mc_scratch;
     DevBuf<int32_t> d_mc_desc, d_mc_flow;
     DevBuf<long long> d_mc_soff;
+    // ecseg_nuset_forward / ecseg_rpn_proposals: the mask, the host-given RPN tensors and reference anchors, and the proposal layer's state
+    DevBuf<uint8_t> d_nu_mask;
+    DevBuf<float> d_nu_cls, d_nu_bbox, d_nu_scores, d_nu_oscores;
+    DevBuf<double> d_nu_ref;
+    DevBuf<float4> d_nu_boxes, d_nu_oboxes;
+    DevBuf<unsigned long long> d_nu_keys, d_nu_mat;
+    DevBuf<int32_t> d_nu_misc, d_nu_oidx;
 };
 
 }  // namespace ecseg
@@ -177,6 +184,7 @@ struct ecseg_ctx : ecseg::DevMem {
     hipEvent_t ev_pre = nullptr;
     int min_cut_lds_pixels = ECSEG_MIN_CUT_LDS_PIXELS;   // windows above this many pixels keep their state in global memory (tests lower it)
     int iseg_H = 0, iseg_W = 0, iseg_img_w = 0, iseg_C = 0, iseg_n = -1;   // iseg_n < 0: no region map on the handle
+    int nuset_cls_t = -1, nuset_bbox_t = -1;   // the RPN tensors the last ecseg_nuset_forward left in the plan's buffers (-1: none)
     int post_chunk = 64;
     int overlap_post = 0;
     int blocking_wait = 1;    // the long waits (a whole launch group) sleep on a blocking event instead of spinning on the stream

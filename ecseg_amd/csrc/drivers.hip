@@ -1,5 +1,5 @@
 // The one-call drivers: each uploads its inputs, runs one family of kernels on the main stream and downloads the results
-// (u16_to_u8, stitch_argmax, meta_inference, the counts, overlay, the interSeg regions / crops, the FISH distances, the FISH spots, the min-cut tasks).
+// (u16_to_u8, stitch_argmax, meta_inference, the counts, overlay, the interSeg regions / crops, the FISH distances, the FISH spots, the min-cut tasks, NuSeT's mask and proposals).
 #include "ctx.h"
 
 using namespace ecseg;
@@ -473,6 +473,128 @@ int ecseg_min_cut(ecseg_ctx* h, const uint8_t* masks, long long mask_bytes, cons
     HIP_TRY(h, hipStreamSynchronize(s));                     // (soff is read by the copy above: it lives until here)
     h->stage_ms[ECSEG_T_COUNT] = stage_elapsed(h->ev[0], h->ev[1]);
     return ECSEG_OK;
+}
+
+// ---- NuSeT's network stage (src/utils.py:35-103) ---------------------------------------------------------------------------
+int ecseg_nuset_forward(ecseg_ctx* h, const float* x, int H, int W, int cls_tensor, int bbox_tensor, uint8_t* mask) {
+    if (h) drop_sent_ahead(h);
+    int rc = check_model(h);
+    if (rc) return rc;
+    h->nuset_cls_t = h->nuset_bbox_t = -1;
+    if (!x || !mask || H <= 0 || W <= 0) return fail(h, ECSEG_E_INVALID, "nuset_forward: bad arguments");
+    const int nt = (int)h->tensors.size();
+    if (cls_tensor < 0 || cls_tensor >= nt || bbox_tensor < 0 || bbox_tensor >= nt || cls_tensor == bbox_tensor)
+        return fail(h, ECSEG_E_INVALID, "nuset_forward: bad RPN tensor index");
+    const ecseg_tensor_desc& ti = h->tensors[h->input_tensor];
+    const ecseg_tensor_desc& to = h->tensors[h->output_tensor];
+    const ecseg_tensor_desc& tc = h->tensors[cls_tensor];
+    const ecseg_tensor_desc& tb = h->tensors[bbox_tensor];
+    if (ti.h != H || ti.w != W || ti.c != 1 || ti.c_stride != 1 || ti.c_offset != 0)
+        return fail(h, ECSEG_E_INVALID, "nuset_forward: the loaded plan takes (" + std::to_string(ti.h) + ", " + std::to_string(ti.w) + ", " +
+                                            std::to_string(ti.c) + ") inputs, not a (" + std::to_string(H) + ", " + std::to_string(W) + ") image");
+    if (to.h != H || to.w != W || to.c != 2) return fail(h, ECSEG_E_INVALID, "nuset_forward: the plan's output is not (H, W, 2) logits");
+    if (tc.c < 2 || tc.c % 2 || tb.c != 2 * tc.c || tb.h != tc.h || tb.w != tc.w)
+        return fail(h, ECSEG_E_INVALID, "nuset_forward: the RPN tensors are not (fh, fw, 2A) and (fh, fw, 4A)");
+    for (const ecseg_tensor_desc& t : h->tensors)
+        if (&t != &tc && &t != &tb && (t.buffer == tc.buffer || t.buffer == tb.buffer))
+            return fail(h, ECSEG_E_INVALID, "nuset_forward: an RPN tensor shares its buffer with another tensor (build the plan with keep=)");
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t px = (size_t)H * W;
+    if ((rc = ensure_patches(h, 1))) return rc;
+    if ((rc = h->d_nu_mask.ensure(h, px))) return rc;
+    hipStream_t s = h->stream;
+    for (float& v : h->stage_ms) v = 0.f;
+    prof_begin(h);
+    HIP_TRY(h, hipMemcpyAsync(view_of(h, h->input_tensor).p, x, px * sizeof(float), hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipEventRecord(h->ev[0], s));
+    if ((rc = run_plan(h, 1))) return rc;
+    HIP_TRY(h, launch_argmax2(view_of(h, h->output_tensor), h->d_nu_mask, s));
+    HIP_TRY(h, hipEventRecord(h->ev[1], s));
+    HIP_TRY(h, hipMemcpyAsync(mask, h->d_nu_mask, px, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    prof_end(h);
+    h->stage_ms[ECSEG_T_UNET] = stage_elapsed(h->ev[0], h->ev[1]);
+    h->nuset_cls_t = cls_tensor; h->nuset_bbox_t = bbox_tensor;
+    return ECSEG_OK;
+}
+
+// cls / bbox: on the device already (null: upload the host tensors first)
+static int rpn_driver(ecseg_ctx* h, const float* d_cls, int cls_cs, const float* d_bbox, int bbox_cs, const float* cls_host,
+                      const float* bbox_host, int fh, int fw, int A, const double* ref_anchors, int stride, int im_h, int im_w,
+                      float nms_threshold, int pre, int post, int32_t* n_out, float* scores, float* proposals, int32_t* indices) {
+    if (n_out) *n_out = 0;
+    if (!n_out || !scores || !proposals || !indices || !ref_anchors || fh <= 0 || fw <= 0 || A <= 0 || im_h <= 0 || im_w <= 0)
+        return fail(h, ECSEG_E_INVALID, "rpn_proposals: bad arguments");
+    if ((long long)fh * fw * A > ECSEG_RPN_MAX_CANDIDATES)
+        return fail(h, ECSEG_E_INVALID, "rpn_proposals: more than " + std::to_string(ECSEG_RPN_MAX_CANDIDATES) + " candidates");
+    if (pre < 1 || pre > ECSEG_RPN_MAX_PRE_NMS)
+        return fail(h, ECSEG_E_INVALID, "rpn_proposals: pre_nms_top_n must be between 1 and " + std::to_string(ECSEG_RPN_MAX_PRE_NMS));
+    if (post < 1 || stride < 1 || (long long)stride * std::max(fh, fw) >= (1ll << 31))
+        return fail(h, ECSEG_E_INVALID, "rpn_proposals: post_nms_top_n and stride must be positive");
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t N = (size_t)fh * fw * A, K = std::min<size_t>((size_t)pre, N), words = (K + 63) / 64, no = std::min<size_t>((size_t)post, K);
+    int rc;
+    if ((rc = h->d_nu_ref.ensure(h, (size_t)A * 4))) return rc;
+    if ((rc = h->d_nu_boxes.ensure(h, N))) return rc;
+    if ((rc = h->d_nu_scores.ensure(h, N))) return rc;
+    if ((rc = h->d_nu_keys.ensure(h, (size_t)rpn_sort_len((int)N)))) return rc;
+    if ((rc = h->d_nu_mat.ensure(h, K * words))) return rc;
+    if ((rc = h->d_nu_misc.ensure(h, 2))) return rc;
+    if ((rc = h->d_nu_oscores.ensure(h, no))) return rc;
+    if ((rc = h->d_nu_oboxes.ensure(h, no))) return rc;
+    if ((rc = h->d_nu_oidx.ensure(h, no))) return rc;
+    hipStream_t s = h->stream;
+    for (float& v : h->stage_ms) v = 0.f;
+    if (!d_cls) {
+        const size_t px = (size_t)fh * fw;
+        if ((rc = h->d_nu_cls.ensure(h, px * 2 * A))) return rc;
+        if ((rc = h->d_nu_bbox.ensure(h, px * 4 * A))) return rc;
+        HIP_TRY(h, hipMemcpyAsync(h->d_nu_cls, cls_host, px * 2 * A * sizeof(float), hipMemcpyHostToDevice, s));
+        HIP_TRY(h, hipMemcpyAsync(h->d_nu_bbox, bbox_host, px * 4 * A * sizeof(float), hipMemcpyHostToDevice, s));
+        d_cls = h->d_nu_cls; cls_cs = 2 * A; d_bbox = h->d_nu_bbox; bbox_cs = 4 * A;
+    }
+    HIP_TRY(h, hipMemcpyAsync(h->d_nu_ref, ref_anchors, (size_t)A * 4 * sizeof(double), hipMemcpyHostToDevice, s));
+    const RpnBufs b{h->d_nu_boxes, h->d_nu_scores, h->d_nu_keys, h->d_nu_mat, h->d_nu_misc, h->d_nu_oscores, h->d_nu_oboxes, h->d_nu_oidx};
+    HIP_TRY(h, hipEventRecord(h->ev[0], s));
+    HIP_TRY(h, run_rpn_proposals(d_cls, cls_cs, d_bbox, bbox_cs, h->d_nu_ref, fh, fw, A, stride, im_h, im_w, nms_threshold, pre, (int)no, b, s));
+    HIP_TRY(h, hipEventRecord(h->ev[1], s));
+    int32_t misc[2];
+    HIP_TRY(h, hipMemcpyAsync(misc, h->d_nu_misc, sizeof(misc), hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));                      // (ref_anchors is read by the copy above: it lives until here)
+    h->stage_ms[ECSEG_T_COUNT] = stage_elapsed(h->ev[0], h->ev[1]);
+    const int n = misc[0];
+    if (n < 0 || (size_t)n > no) return fail(h, ECSEG_E_HIP, "rpn_proposals: the device reported an impossible count");
+    *n_out = n;
+    if (n > 0) {
+        HIP_TRY(h, hipMemcpyAsync(scores, h->d_nu_oscores, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipMemcpyAsync(proposals, h->d_nu_oboxes, (size_t)n * 4 * sizeof(float), hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipMemcpyAsync(indices, h->d_nu_oidx, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipStreamSynchronize(s));
+    }
+    return ECSEG_OK;
+}
+
+int ecseg_rpn_proposals(ecseg_ctx* h, const float* cls_score, const float* bbox_pred, int fh, int fw, int A, const double* ref_anchors,
+                        int stride, int im_h, int im_w, float nms_threshold, int pre_nms_top_n, int post_nms_top_n, int32_t* n_out,
+                        float* scores, float* proposals, int32_t* indices) {
+    if (!h) return ECSEG_E_INVALID;
+    drop_sent_ahead(h);
+    if (!cls_score || !bbox_pred) return fail(h, ECSEG_E_INVALID, "rpn_proposals: bad arguments");
+    return rpn_driver(h, nullptr, 0, nullptr, 0, cls_score, bbox_pred, fh, fw, A, ref_anchors, stride, im_h, im_w, nms_threshold,
+                      pre_nms_top_n, post_nms_top_n, n_out, scores, proposals, indices);
+}
+
+int ecseg_rpn_proposals_last(ecseg_ctx* h, int A, const double* ref_anchors, int stride, int im_h, int im_w, float nms_threshold,
+                             int pre_nms_top_n, int post_nms_top_n, int32_t* n_out, float* scores, float* proposals, int32_t* indices) {
+    if (h) drop_sent_ahead(h);
+    int rc = check_model(h);
+    if (rc) return rc;
+    if (h->nuset_cls_t < 0 || h->cap_patches < 1)
+        return fail(h, ECSEG_E_INVALID, "rpn_proposals_last: no RPN tensors on the handle (call ecseg_nuset_forward first)");
+    const TView c = view_of(h, h->nuset_cls_t), b = view_of(h, h->nuset_bbox_t);
+    if (c.c != 2 * A) return fail(h, ECSEG_E_INVALID, "rpn_proposals_last: the RPN tensors hold " + std::to_string(c.c / 2) + " anchors per position");
+    return rpn_driver(h, c.p, c.cs, b.p, b.cs, nullptr, nullptr, c.h, c.w, A, ref_anchors, stride, im_h, im_w, nms_threshold, pre_nms_top_n,
+                      post_nms_top_n, n_out, scores, proposals, indices);
 }
 
 }  // extern "C"

@@ -13,6 +13,7 @@ void free_model(ecseg_ctx* h) {
     h->cap_patches = 0;
     h->ops.clear(); h->tensors.clear();
     h->has_model = false;
+    h->nuset_cls_t = h->nuset_bbox_t = -1;
 }
 
 int upload(ecseg_ctx* h, const std::vector<float>& host, float** dev) {

@@ -410,13 +410,16 @@ def _conv_geometry(cls, name, lc, h, w, aniso=None):
     return kh, kw, sh, dil, pt, pl, oh, ow
 
 
-def build_plan(model_config, weights, input_hw=(256, 256), fuse=True, lambda_overrides=None, output=0):
+def build_plan(model_config, weights, input_hw=(256, 256), fuse=True, lambda_overrides=None, output=0, keep=()):
     """``model_config``: dict or JSON text; ``weights``: {layer name: [arrays]} -> Plan.
     ``lambda_overrides``: {layer name: (scale, offset)} for ``Lambda`` layers (their Python bytecode cannot be
     interpreted; the common ``Lambda(lambda x: x / 255)`` input normalisation is ``(1/255, 0)``).
     ``output``: which output of a model with several (index into ``output_layers``, or a layer name): the plan computes that
     one (``predict_on_batch`` of such a Keras model returns a list; the callers of the reference read a single array,
-    src/utils.py:115, src/interseg.py:155,168)."""
+    src/utils.py:115, src/interseg.py:155,168).
+    ``keep``: names of further layers whose outputs stay readable after the plan has run (``Plan.layer_tensor[name]``,
+    ``Handle.read_tensor``): each gets a buffer of its own that nothing re-uses, and is neither fused away nor written into a
+    concatenation (NuSeT's RPN head beside the U-Net's logits, ecseg_amd/nuset.py)."""
     lambda_overrides = lambda_overrides or {}
     if isinstance(model_config, (str, bytes)):
         model_config = json.loads(model_config)
@@ -732,6 +735,11 @@ def build_plan(model_config, weights, input_hw=(256, 256), fuse=True, lambda_ove
             if not 0 <= int(output) < len(outs):
                 raise PlanError('output %r out of range: the model has %d output(s)' % (output, len(outs)))
             out_node = by_name[outs[int(output)][0]]
+    keep_nodes = set()
+    for nm in keep:
+        if nm not in by_name or nodes[by_name[nm]]['kind'] in ('input', 'reshape', 'slice', 'concat'):
+            raise PlanError('keep: %r is not a layer of the model that owns its output' % (nm,))
+        keep_nodes.add(by_name[nm])
     in_nodes = [i for i, n in enumerate(nodes) if n['kind'] == 'input']
     if len(in_nodes) != 1:
         raise PlanError('models with %d inputs are not supported' % len(in_nodes))
@@ -757,7 +765,7 @@ def build_plan(model_config, weights, input_hw=(256, 256), fuse=True, lambda_ove
                 continue
             i = n['inputs'][0]
             u = nodes[i]
-            if u['kind'] != 'upsample' or u['stride'] != 2 or u['mode'] != 0 or len(consumers(i)) != 1 or i == out_node:
+            if u['kind'] != 'upsample' or u['stride'] != 2 or u['mode'] != 0 or len(consumers(i)) != 1 or i == out_node or i in keep_nodes:
                 continue
             if (n['kh'], n['kw'], n.get('stride', 1), n.get('dilation', 1), n['pad_top'], n['pad_left'], n.get('aniso', 0)) != (2, 2, 1, 1, 0, 0, 0) or \
                     n['shape'][:2] != u['shape'][:2]:
@@ -777,7 +785,7 @@ def build_plan(model_config, weights, input_hw=(256, 256), fuse=True, lambda_ove
                 continue
             i = n['inputs'][0]
             p = nodes[i]
-            if p['kind'] not in ('conv', 'convt', 'dwconv') or len(consumers(i)) != 1 or i == out_node:
+            if p['kind'] not in ('conv', 'convt', 'dwconv') or len(consumers(i)) != 1 or i == out_node or i in keep_nodes or j in keep_nodes:
                 continue
             if n['kind'] == 'affine' and p['act'] == 0 and n['act'] == 0:
                 s, t = n['scale64'], n['shift64']
@@ -812,7 +820,7 @@ def build_plan(model_config, weights, input_hw=(256, 256), fuse=True, lambda_ove
         for pos, i in enumerate(n['inputs']):
             ci = nodes[i]['shape'][2]
             ok = (i not in view and nodes[i]['kind'] not in ('input', 'concat', 'reshape', 'slice') and n['inputs'].count(i) == 1
-                  and i != out_node)
+                  and i != out_node and i not in keep_nodes)
             if ok:
                 view[i] = (j, off)
             else:
@@ -828,6 +836,8 @@ def build_plan(model_config, weights, input_hw=(256, 256), fuse=True, lambda_ove
         for i in nodes[j]['inputs']:
             last_use[i] = j
     last_use[out_node] = len(nodes) + 1
+    for i in keep_nodes:
+        last_use[i] = len(nodes) + 1
     # Flatten / Reshape / channel slices (grouped convolutions) are views of their input's buffer: the owner lives as long as the
     # view is read
     for j in reversed(order):
@@ -881,7 +891,7 @@ def build_plan(model_config, weights, input_hw=(256, 256), fuse=True, lambda_ove
             h, w, c = nodes[j]['shape']
             # the model output gets a buffer of its own (and the input's is never re-used, below): the window lanes of
             # csrc/plan_run.hip run_plan address both in plain window order, whatever else a lane packs into shared buffers
-            node_buf[j] = alloc(h * w * c, fresh=(j == out_node))
+            node_buf[j] = alloc(h * w * c, fresh=(j == out_node or j in keep_nodes))
         return node_buf[j], 0, nodes[j]['shape'][2]
 
     def new_tensor(j):

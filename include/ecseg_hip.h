@@ -385,6 +385,40 @@ int ecseg_fish_spots(ecseg_ctx* h, const int32_t* labels, int H, int W, const ui
 int ecseg_min_cut(ecseg_ctx* h, const uint8_t* masks, long long mask_bytes, const int32_t* tasks, int n_tasks, int dist, uint8_t* side,
                   int32_t* flow);
 
+/* ---- NuSeT's network stage (src/utils.py:35-103): the U-Net mask and the RPN proposal layer ------------------------------ */
+/* Runs the loaded plan on ONE whole image and writes pred_masks (:53): x is the normalised (H, W) float32 image, the plan's input
+ * tensor must be (H, W, 1) and its output the 2-channel logits of the same extent; mask (H, W) uint8 = argmax over the logits, a
+ * tie giving 0 as tf.argmax does.  cls_tensor / bbox_tensor: the plan tensors of rpn_cls_score (fh, fw, 2A) and rpn_bbox_pred
+ * (fh, fw, 4A) (src/model_layers/model_RPN.py:26-37), which the plan must keep alive to its end (keras_plan.build_plan: keep);
+ * they stay on the handle for ecseg_rpn_proposals_last until the next forward call or model load (ecseg_read_tensor reads them
+ * and the logits back).  A plan is built for one image extent: another extent needs ecseg_model_load again.  Device time of the
+ * plan and the argmax in ECSEG_T_UNET. */
+int ecseg_nuset_forward(ecseg_ctx* h, const float* x, int H, int W, int cls_tensor, int bbox_tensor, uint8_t* mask);
+/* RPNProposal (src/model_layers/rpn_proposal.py) on the N = fh * fw * A candidates of cls_score (fh, fw, 2A) and bbox_pred
+ * (fh, fw, 4A), float32 on the host; candidate (y * fw + x) * A + a has the anchor float32(ref_anchors[a] + (x, y, x, y) *
+ * stride), the sum taken in float64 (src/nuset_utils/generate_anchors.py), ref_anchors being A x 4 float64 (x1, y1, x2, y2).
+ *   score  = the second of softmax(cls[2a], cls[2a + 1]) in float32 (model_RPN.py:30-32);
+ *   box    = decode(anchor, bbox[4a .. 4a + 3]) in float32 in the operation order of src/nuset_utils/bbox_transform_tf.py:41-66;
+ *            exp is the correctly rounded float32 exponential;
+ *   kept   where max(x2 - x1, 0) * max(y2 - y1, 0) > 0 and score >= 0 (NaN fails both);
+ *   top-k  k = min(pre_nms_top_n, kept) by descending score, equal scores in ascending candidate order (tf.nn.top_k);
+ *   NMS    greedy in that order as tf.image.non_max_suppression: corners min/max-normalised, a box of area <= 0 has IoU 0 with
+ *          everything, a candidate is suppressed by a selected one when IoU > nms_threshold (strictly), at most post_nms_top_n
+ *          are selected;
+ *   clip   of the selected boxes to [0, im_w - 1] x [0, im_h - 1], after NMS (rpn_proposal.py:166-168).
+ * Outputs, each with room for post_nms_top_n entries: scores (descending), proposals (x1, y1, x2, y2) and the selected candidates'
+ * indices; *n_out their number, 0 when nothing is kept.  ECSEG_E_INVALID: fh * fw * A > ECSEG_RPN_MAX_CANDIDATES, pre_nms_top_n
+ * outside 1 .. ECSEG_RPN_MAX_PRE_NMS, post_nms_top_n < 1, stride < 1.  Device time of the kernels in ECSEG_T_COUNT. */
+#define ECSEG_RPN_MAX_CANDIDATES (1 << 22)
+#define ECSEG_RPN_MAX_PRE_NMS    8192
+int ecseg_rpn_proposals(ecseg_ctx* h, const float* cls_score, const float* bbox_pred, int fh, int fw, int A, const double* ref_anchors,
+                        int stride, int im_h, int im_w, float nms_threshold, int pre_nms_top_n, int post_nms_top_n, int32_t* n_out,
+                        float* scores, float* proposals, int32_t* indices);
+/* The same on the two RPN tensors the last ecseg_nuset_forward left on the device (fh, fw and A are theirs; A x 4 reference
+ * anchors must match their channel counts). */
+int ecseg_rpn_proposals_last(ecseg_ctx* h, int A, const double* ref_anchors, int stride, int im_h, int im_w, float nms_threshold,
+                             int pre_nms_top_n, int post_nms_top_n, int32_t* n_out, float* scores, float* proposals, int32_t* indices);
+
 /* ---- per-stage device timings of the last segment call (milliseconds, HIP events on the handle's stream) -- */
 /* ECSEG_T_COUNT: device time of the kernels of the last ecseg_overlay / ecseg_preprocess / ecseg_count_* call (inputs
  * already resident, copies excluded). */

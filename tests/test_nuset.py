@@ -1,0 +1,316 @@
+"""NuSeT's network stage without a GPU: the restatement of the proposal layer (tests/nuset_ref.py) pinned on hand-computed answers,
+its float32 and float64 runs against each other on EVERY committed case (tests/nuset_cases.py) - which is what makes those cases fit
+for an exact comparison with the device in tests/test_gpu_nuset.py -, the host side of ecseg_amd/nuset.py (anchor size against the
+reference's own function, reference anchors, normalisations, the .npz loader) and ``nuclei_masks`` end to end on an oracle-backed
+handle."""
+import os
+import sys
+
+import numpy as np
+import pytest
+from scipy import ndimage
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import nuset_cases as cases                  # noqa: E402
+import nuset_ref as ref                      # noqa: E402
+
+from ecseg_amd import _lib, build, keras_plan, nuset          # noqa: E402
+from oracle import unet as oracle_unet       # noqa: E402
+
+ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), '..')
+
+
+def _run(c, dtype=np.float32, **over):
+    c = dict(c, **over)
+    return ref.proposals(c['cls'], c['bbox'], c['ref'], c['stride'], c['im_h'], c['im_w'], c['thr'], c['pre'], c['post'], dtype=dtype)
+
+
+# ---- the restatement on hand-computed answers ---------------------------------------------------------------------------------
+def test_decode_by_hand():
+    """Anchor (0, 0, 9, 9): width = height = 10, centre (5, 5).  dx = 0.1, dy = -0.2, dw = dh = 0 -> centre (6, 3), extent 10:
+    (1, -2, 10, 7) - the x2 / y2 of bbox_transform_tf.py:60-61 carry the extra -1.  dw = ln 2 doubles the width: (-4, ., 15, .)."""
+    a = np.array([[0, 0, 9, 9]], np.float32)
+    assert np.array_equal(ref.decode(a, np.array([[0.1, -0.2, 0, 0]], np.float32)), np.array([[1, -2, 10, 7]], np.float32))
+    got = ref.decode(a, np.array([[0.1, -0.2, np.log(2.0), 0]], np.float32))
+    np.testing.assert_allclose(got, [[-4, -2, 15, 7]], atol=1e-5)
+    assert got.dtype == np.float32 and ref.decode(a, np.zeros((1, 4)), np.float64).dtype == np.float64
+    # dw = -inf: width 0, x2 - x1 = -1
+    z = ref.decode(a, np.array([[0, 0, -np.inf, 0]], np.float32))
+    assert z[0, 2] - z[0, 0] == -1
+
+
+def test_anchors_are_float32_of_the_float64_sum():
+    r = np.array([[-0.1, -0.1, 0.1, 0.1 + 2.0 ** -30]])
+    a = ref.all_anchors(r, 16, 2, 3)
+    assert a.shape == (6, 4) and a.dtype == np.float32
+    assert np.array_equal(a[4], np.array([16 - 0.1, 16 - 0.1, 16.1, 16.1 + 2.0 ** -30]).astype(np.float32))      # (y 1, x 1)
+    assert np.array_equal(a[2], np.array([32 - 0.1, -0.1, 32.1, 0.1]).astype(np.float32))                           # (y 0, x 2)
+
+
+def _two_boxes(thr, c1=(0.0, 2.0), c2=(0.0, 1.0), refs=((0, 0, 9, 9), (0, 0, 9, 4))):
+    """One position, two anchors that decode to themselves (zero deltas).  (0, 0, 9, 9) and (0, 0, 9, 4) have areas 81 and 36 and
+    intersect in 36: IoU = 36 / 81 = 0.444..."""
+    cls = np.array([[list(c1) + list(c2)]], np.float32)
+    return ref.proposals(cls, np.zeros((1, 1, 8), np.float32), np.array(refs, np.float64), 16, 16, 16, thr, 10, 10)
+
+
+def test_nms_just_above_and_just_below_the_threshold():
+    below = _two_boxes(0.45)                                 # IoU 0.444 is not > 0.45: both stay
+    assert below['indices'].tolist() == [0, 1] and below['scores'][0] > below['scores'][1]
+    assert np.array_equal(below['proposals'], np.array([[0, 0, 9, 9], [0, 0, 9, 4]], np.float32))
+    above = _two_boxes(0.44)                                 # 0.444 > 0.44: the lower score goes
+    assert above['indices'].tolist() == [0]
+    exact = _two_boxes(np.float32(36.0) / np.float32(81.0))  # IoU == threshold: strictly greater is asked for
+    assert exact['indices'].tolist() == [0, 1]
+    swapped = _two_boxes(0.44, c1=(0.0, 1.0), c2=(0.0, 2.0))
+    assert swapped['indices'].tolist() == [1]
+    np.testing.assert_allclose(below['scores'], [1 / (1 + np.exp(-2.0)), 1 / (1 + np.exp(-1.0))], rtol=1e-6)
+
+
+def test_equal_scores_keep_the_candidate_order():
+    tie = _two_boxes(0.44, c1=(0.5, 1.5), c2=(0.5, 1.5))
+    assert tie['indices'].tolist() == [0] and tie['all_scores'][0] == tie['all_scores'][1]
+    apart = _two_boxes(0.44, c1=(0.5, 1.5), c2=(0.5, 1.5), refs=((0, 0, 4, 4), (8, 8, 12, 12)))
+    assert apart['indices'].tolist() == [0, 1]
+    c = cases.equal_scores()
+    r = _run(c)
+    s = r['all_scores'][r['order']]
+    assert len(np.unique(s)) < len(s)                        # the case really ties
+    for k in range(len(s) - 1):
+        assert s[k] > s[k + 1] or (s[k] == s[k + 1] and r['order'][k] < r['order'][k + 1])
+
+
+def test_filter_clip_and_caps():
+    r = _run(cases.bad_values())
+    assert r['kept'] == 22 and 5 not in r['order'] and 14 not in r['order']
+    assert np.isnan(r['all_scores'][5]) and not np.isnan(r['all_scores'][14])
+    e = _run(cases.all_filtered())
+    assert e['kept'] == 0 and len(e['scores']) == 0 and e['proposals'].shape == (0, 4)
+    c = cases.outside()
+    o = _run(c)
+    p = o['proposals']
+    assert p.min() == 0 and p[:, [0, 2]].max() == c['im_w'] - 1 and p[:, [1, 3]].max() == c['im_h'] - 1
+    assert ((p[:, 2] == p[:, 0]) | (p[:, 3] == p[:, 1])).any() and ((p[:, 2] > p[:, 0]) & (p[:, 3] > p[:, 1])).any()
+    k = _run(cases.top_k_cut())
+    assert k['kept'] == 6069 and len(k['order']) == 6000 and len(k['scores']) == 800
+    cap = _run(cases.cap())
+    assert cap['kept'] == 1200 and len(cap['scores']) == 800
+    assert np.array_equal(cap['indices'], cap['order'][:800])                      # nothing was suppressed
+    assert len(_run(cases.small())['scores']) < 20                                 # the NMS, not the cap, ended that one
+
+
+@pytest.mark.parametrize('make', cases.ALL, ids=[f.__name__ for f in cases.ALL])
+def test_every_case_is_decided_alike_in_float32_and_float64(make):
+    """What makes a case fit for an exact comparison with the device: the float32 run (the device's arithmetic) and the float64
+    adjudicator agree on the order of the kept candidates, scores that differ in float64 differ in float32 (ties are ties in both:
+    equal inputs), both select the same candidates, and no pair decision of either run comes closer to the threshold than
+    coordinate errors of ``coord_tol`` can move an IoU."""
+    c = make()
+    a, b = _run(c, np.float32), _run(c, np.float64)
+    assert a['all_scores'].dtype == np.float32 and b['all_scores'].dtype == np.float64
+    assert a['kept'] == b['kept'] and np.array_equal(a['order'], b['order'])
+    sa, sb = a['all_scores'][a['order']], b['all_scores'][b['order']]
+    assert np.array_equal(sa[:-1] == sa[1:], sb[:-1] == sb[1:])
+    assert np.array_equal(a['indices'], b['indices'])
+    assert a['min_gap'] > 0 and b['min_gap'] > 0, (a['min_gap'], b['min_gap'])
+    if len(a['scores']):
+        assert np.abs(a['proposals'].astype(np.float64) - b['proposals']).max() <= ref.coord_tol(c['im_h'], c['im_w'])
+        assert np.abs(a['scores'].astype(np.float64) - b['scores']).max() < 1e-6
+
+
+# ---- host side of ecseg_amd/nuset.py ------------------------------------------------------------------------------------------
+def _regions(seg, img, channel0, capacity=4096):
+    """``Handle.nuclei_regions`` by scipy: 8-connected regions in raster order of their first pixel."""
+    lab, n = ndimage.label(np.asarray(seg) != 0, structure=np.ones((3, 3)))
+    rec = np.zeros((n, 8), np.int64)
+    for k, sl in enumerate(ndimage.find_objects(lab)):
+        ys, xs = np.nonzero(lab == k + 1)
+        rec[k] = (len(ys), sl[0].start, sl[1].start, sl[0].stop, sl[1].stop, ys.sum(), xs.sum(), int(np.asarray(img)[ys, xs, channel0].sum()))
+    return rec
+
+
+class OracleHandle:
+    """What ``nuset.NuSeT`` needs of a ``_lib.Handle``, computed by oracle/unet.py, tests/nuset_ref.py and scipy."""
+
+    def __init__(self, weights, base):
+        self.weights, self.base, self.plan, self.loads, self.last = weights, base, None, 0, None
+
+    def load_plan(self, plan):
+        self.plan, self.last = plan, None
+        self.loads += 1
+
+    def outputs(self, x):
+        cfg = nuset.nuset_config(x.shape[0], x.shape[1], self.base)
+        return [oracle_unet.forward(cfg, self.weights, x[None, :, :, None], output=k)[0] for k in range(3)]
+
+    def nuset_forward(self, x, cls_tensor, bbox_tensor):
+        ti = self.plan.tensors[self.plan.input_tensor]
+        assert (ti['h'], ti['w']) == x.shape and x.dtype == np.float32
+        assert (cls_tensor, bbox_tensor) == tuple(self.plan.layer_tensor[n] for n in nuset.RPN_LAYERS[1:])
+        logits, cls, bbox = self.outputs(x)
+        self.last = (cls, bbox)
+        return (logits[..., 1] > logits[..., 0]).astype(np.uint8)
+
+    def rpn_proposals_last(self, ref_anchors, stride, im_h, im_w, nms_threshold, pre_nms_top_n=6000, post_nms_top_n=800):
+        r = ref.proposals(self.last[0], self.last[1], ref_anchors, stride, im_h, im_w, nms_threshold, pre_nms_top_n, post_nms_top_n)
+        return r['scores'], r['proposals'], r['indices']
+
+    nuclei_regions = staticmethod(_regions)
+
+
+def test_anchor_size_against_the_reference(golden_dir):
+    z = np.load(os.path.join(golden_dir, 'nuset_anchor_size.npz'))
+    names = [str(n) for n in z['names']]
+    assert len(names) >= 12 and {'empty', 'one_pixel', 'touching_diagonally', 'ring'} <= set(names)
+    h = OracleHandle(None, 0)
+    for k, (name, want) in enumerate(zip(names, z['sizes'])):
+        got = nuset.anchor_size(z['mask_%d' % k], h)
+        if np.isnan(want):
+            assert got is None, name                         # (the reference's median of nothing is NaN)
+        else:
+            assert got == want and isinstance(got, float), (name, got, want)
+    assert nuset.anchor_size(z['mask_%d' % names.index('ring')].astype(np.float32), h) == 16.0       # pred_masks is float32 in the reference
+
+
+def test_reference_anchors_by_hand():
+    """base_size 16.  Index = ratio index * 3 + scale index over ratios 0.125 .. 8 and scales 0.5, 1, 2.  Ratio 1, scale 1 (index
+    10): 16 x 16 -> +-7.5.  Ratio 4, scale 2 (index 17): sqrt 2, height 2 * 2 * 16 = 64, width 2 / 2 * 16 = 16 -> (-7.5, -31.5, 7.5,
+    31.5).  Ratio 0.25, scale 0.5 (index 3): sqrt 0.5, height 4, width 16 -> (-7.5, -1.5, 7.5, 1.5).  Ratio 0.125, scale 0.5 (index
+    0): sqrt(1/8), height 8 sqrt(1/8) = 2 sqrt 2 / ... = 2.8284..., width 8 sqrt 8 = 22.627..."""
+    a = nuset.reference_anchors(16)
+    assert a.shape == (21, 4) and a.dtype == np.float64
+    assert a[10].tolist() == [-7.5, -7.5, 7.5, 7.5]
+    assert a[17].tolist() == [-7.5, -31.5, 7.5, 31.5]
+    assert a[3].tolist() == [-7.5, -1.5, 7.5, 1.5]
+    np.testing.assert_allclose(a[0], [-(8 * np.sqrt(8) - 1) / 2, -(np.sqrt(8) - 1) / 2, (8 * np.sqrt(8) - 1) / 2, (np.sqrt(8) - 1) / 2], rtol=1e-15)
+    assert np.array_equal(a[:, :2], -a[:, 2:])
+    assert np.array_equal(nuset.reference_anchors(9.5), cases.ref_anchors(21, 9.5))          # the median of an even count is a half
+
+
+def test_normalisations():
+    rng = np.random.default_rng(3)
+    img = rng.integers(0, 4000, (16, 32)).astype(np.uint16)
+    w = nuset.whole_image_norm(img)
+    assert w.dtype == np.float32 and abs(float(w.mean())) < 1e-6 and abs(float(w.std()) - 1) < 1e-6
+    assert np.array_equal(w, ((img.astype(np.float64) - img.mean()) / img.std()).astype(np.float32))
+    mask = np.zeros((16, 32), np.uint8)
+    mask[4:9, 5:20] = 1
+    img[4, 5] = 0                                            # a zero inside the mask is not foreground (normalization.py:15)
+    nz = img[4:9, 5:20].astype(np.float64).reshape(-1)
+    nz = nz[nz != 0]
+    f = nuset.foreground_norm(img, mask)
+    assert f.dtype == np.float32 and len(nz) == 74
+    assert np.array_equal(f, ((img.astype(np.float64) - np.median(nz)) / (nz.std() + 1e-5)).astype(np.float32))
+    assert nuset.foreground_norm(img, np.zeros_like(mask)) is None
+
+
+def test_config_and_plan_keep_the_rpn_outputs():
+    cfg = nuset.nuset_config(32, 48, base=8)
+    assert [o[0] for o in cfg['config']['output_layers']] == ['final', 'rpn_cls_score', 'rpn_bbox_pred']
+    by = {L['name']: L for L in cfg['config']['layers']}
+    assert by['rpn_conv/3x3']['config']['filters'] == 64 and by['rpn_conv/3x3']['config']['activation'] == 'linear'
+    assert by['rpn_conv/3x3']['inbound_nodes'][0][0][0] == 'pool4' and by['rpn_cls_score']['config']['filters'] == 42
+    assert by['rpn_bbox_pred']['config']['filters'] == 84 and not by['final']['config']['use_bias']
+    assert nuset.nuset_config(16, 16)['config']['layers'][-3]['config']['filters'] == 512
+    assert [by[n]['config']['activation'] for n in ('up4', 'up3', 'up2', 'up1')] == ['relu', 'linear', 'linear', 'linear']   # models.py:78-124
+    for bad in ((30, 48), (32, 40), (0, 16)):
+        with pytest.raises(ValueError):
+            nuset.nuset_config(*bad)
+    w = nuset.synth_weights(cfg, seed=2)
+    plan = keras_plan.build_plan(cfg, w, keep=nuset.RPN_LAYERS[1:])
+    assert plan.tensors[plan.output_tensor] == dict(plan.tensors[plan.output_tensor], h=32, w=48, c=2)
+    kept = [plan.tensors[plan.layer_tensor[n]] for n in nuset.RPN_LAYERS[1:]]
+    assert [(t['h'], t['w'], t['c']) for t in kept] == [(2, 3, 42), (2, 3, 84)]
+    for t in kept:                                           # a buffer of its own that nothing else ever writes
+        assert sum(1 for u in plan.tensors if u['buffer'] == t['buffer']) == 1
+    # without `keep` the plan of the same model re-uses those buffers or not as before: the option changes nothing else
+    plain = keras_plan.build_plan(cfg, w)
+    assert [dict(o, out=0, in0=0, in1=0) for o in plain.ops] == [dict(o, out=0, in0=0, in1=0) for o in plan.ops]
+    with pytest.raises(keras_plan.PlanError):
+        keras_plan.build_plan(cfg, w, keep=('no_such_layer',))
+
+
+def test_npz_loader_and_its_error_paths(tmp_path):
+    base = 4
+    w = nuset.synth_weights(nuset.nuset_config(16, 16, base), seed=5)
+    entries = {}
+    for name, arrs in w.items():
+        for part, a in zip(('kernel', 'bias'), arrs):
+            entries['%s/%s' % (nuset.CHECKPOINT_SCOPE[name], part)] = a
+    assert 'model_U-Net/conv2d_transpose_3/kernel' in entries and 'model_U-Net/final/bias' not in entries
+    assert 'model_RPN/rpn_conv/3x3/bias' in entries and len(entries) == 2 * (18 + 4 + 1 + 3) - 1       # 18 convolutions, 4 up-samplers, final (no bias), 3 RPN layers
+    p = str(tmp_path / 'w.npz')
+    np.savez(p, **entries)
+    got = nuset.load_weights_npz(p, base=base)
+    assert list(got) == list(w) and all(np.array_equal(a, b) for n in w for a, b in zip(got[n], w[n]))
+    assert all(a.dtype == np.float32 for arrs in got.values() for a in arrs)
+    keras_plan.build_plan(nuset.nuset_config(32, 32, base), got, keep=nuset.RPN_LAYERS[1:])
+    missing = dict(entries)
+    del missing['model_RPN/rpn_bbox_pred/bias']
+    np.savez(p, **missing)
+    with pytest.raises(ValueError, match='model_RPN/rpn_bbox_pred/bias'):
+        nuset.load_weights_npz(p, base=base)
+    shaped = dict(entries)
+    shaped['model_U-Net/conv2d_transpose/kernel'] = np.transpose(shaped['model_U-Net/conv2d_transpose/kernel'], (0, 1, 3, 2))
+    np.savez(p, **shaped)
+    with pytest.raises(ValueError, match=r'model_U-Net/conv2d_transpose/kernel.*\(3, 3, 64, 32\).*\(3, 3, 32, 64\)'):
+        nuset.load_weights_npz(p, base=base)
+    with pytest.raises(ValueError, match='model_U-Net/conv1-1/kernel'):
+        nuset.load_weights_npz(p, base=8)                    # a file of another width
+
+
+def test_nuclei_masks_end_to_end_on_an_oracle_backed_handle():
+    base = 4
+    w = nuset.synth_weights(nuset.nuset_config(16, 16, base), seed=7)
+    rng = np.random.default_rng(7)
+    yy, xx = np.mgrid[:70, :53]
+    img = 200.0 + 30.0 * rng.random((70, 53))
+    for cy, cx, r in ((20, 15, 9), (40, 36, 11), (55, 12, 6)):
+        img += 2500.0 * np.exp(-((yy - cy) ** 2 + (xx - cx) ** 2) / (2.0 * r * r))
+    img = img.astype(np.uint16)
+    h = OracleHandle(w, base)
+    net = nuset.NuSeT(w, base=base, handle=h)
+    mask, scores, props = net.nuclei_masks(img, min_score=0.5, nms_threshold=0.3)
+    assert h.loads == 1                                      # both passes at 64 x 48: one plan
+    # the same by hand (src/utils.py:138-152)
+    a = img[:64, :48]
+    m1 = (lambda o: (o[0][..., 1] > o[0][..., 0]).astype(np.uint8))(h.outputs(nuset.whole_image_norm(a)))
+    assert 0 < m1.sum() < m1.size
+    logits, cls, bbox = h.outputs(nuset.foreground_norm(a, m1))
+    want_mask = (logits[..., 1] > logits[..., 0]).astype(np.uint8)
+    rec = _regions(want_mask, want_mask[..., None], 0)
+    size = float(np.median(np.maximum(rec[:, 3] - rec[:, 1], rec[:, 4] - rec[:, 2])))
+    r = ref.proposals(cls, bbox, cases.ref_anchors(21, size), 16, 64, 48, 0.3)
+    top = r['scores'] > 0.5
+    assert mask.dtype == np.uint8 and np.array_equal(mask, want_mask)
+    assert 0 < top.sum() < len(top)
+    assert np.array_equal(scores, r['scores'][top]) and np.array_equal(props, r['proposals'][top])
+    assert scores.dtype == props.dtype == np.float32 and props.shape == (top.sum(), 4) and np.all(np.diff(scores) <= 0)
+    # `run` alone returns every proposal; another extent loads another plan
+    m2, s2, p2 = net.run(nuset.whole_image_norm(img[:32, :32]), nms_threshold=0.3)
+    assert h.loads == 2 and m2.shape == (32, 32) and len(s2) == len(p2)
+    # no foreground in the first pass / no region in the second: empty results, not NaN
+    dark = nuset.NuSeT(w, base=base, handle=OracleHandle(w, base))
+    dark.mask = lambda x: np.zeros(x.shape, np.uint8)
+    m0, s0, p0 = dark.nuclei_masks(img)
+    assert m0.shape == (64, 48) and not m0.any() and s0.shape == (0,) and p0.shape == (0, 4)
+    m0, s0, p0 = dark.run(np.zeros((32, 32), np.float32))
+    assert not m0.any() and s0.shape == (0,) and p0.shape == (0, 4)
+    with pytest.raises(ValueError):
+        net.nuclei_masks(img[:10])
+
+
+def test_header_binding_and_build_agree():
+    header = open(os.path.join(ROOT, 'include', 'ecseg_hip.h')).read()
+    assert 'int ecseg_nuset_forward(ecseg_ctx* h, const float* x, int H, int W, int cls_tensor, int bbox_tensor, uint8_t* mask);' in header
+    assert 'int ecseg_rpn_proposals(ecseg_ctx* h, const float* cls_score, const float* bbox_pred, int fh, int fw, int A, const double* ref_anchors,' in header
+    assert 'int ecseg_rpn_proposals_last(ecseg_ctx* h, int A, const double* ref_anchors, int stride, int im_h, int im_w, float nms_threshold,' in header
+    assert '#define ECSEG_RPN_MAX_PRE_NMS    %d' % _lib.Handle.RPN_MAX_PRE_NMS in header
+    assert '#define ECSEG_RPN_MAX_CANDIDATES (1 << 22)' in header and _lib.Handle.RPN_MAX_CANDIDATES == 1 << 22
+    assert '#define ECSEG_ABI_VERSION 5' in header.replace('  ', ' ') and _lib.ABI_VERSION == 5
+    for name in ('ecseg_nuset_forward', 'ecseg_rpn_proposals', 'ecseg_rpn_proposals_last'):
+        assert name in _lib.EXPORTS
+    for name in ('nuset_forward', 'rpn_proposals', 'rpn_proposals_last'):
+        assert hasattr(_lib.Handle, name)
+    assert 'nuset_kernels.hip' in build.SOURCES and build.EXTRA_FLAGS['nuset_kernels.hip'] == ['-ffp-contract=off']
+    assert (nuset.PRE_NMS_TOP_N, nuset.POST_NMS_TOP_N, nuset.STRIDE, nuset.N_ANCHORS) == (6000, 800, 16, 21)
