@@ -95,9 +95,10 @@ def iou_bound(b, others, iou, ih, iw, ab, ao, tol):
 
 
 def proposals(cls_score, bbox_pred, ref_anchors, stride, im_h, im_w, nms_threshold, pre_nms_top_n=6000, post_nms_top_n=800,
-              dtype=np.float32):
+              dtype=np.float32, gaps=True):
     """-> dict(scores, proposals, indices: of the selected candidates, in selection order; all_scores, all_boxes: of every
-    candidate; kept: how many passed the filter; order: the top-k candidate indices; min_gap)."""
+    candidate; kept: how many passed the filter; order: the top-k candidate indices; min_gap).  ``gaps=False`` leaves ``min_gap``
+    out (None): the selection is the same and costs half as much, for a caller that already knows the case to be decided."""
     dtype = np.dtype(dtype).type
     cls_score = np.asarray(cls_score, np.float32)
     fh, fw = cls_score.shape[:2]
@@ -125,8 +126,9 @@ def proposals(cls_score, bbox_pred, ref_anchors, stride, im_h, im_w, nms_thresho
         if len(rest) == 0:
             continue
         iou, ih, iw, ab, ao = iou_row(b[i], b[rest])
-        bound = iou_bound(b[i], b[rest], iou, ih, iw, ab, ao, tol)
-        min_gap = min(min_gap, float(np.min(np.abs(iou.astype(np.float64) - float(thr)) - bound)))
+        if gaps:
+            bound = iou_bound(b[i], b[rest], iou, ih, iw, ab, ao, tol)
+            min_gap = min(min_gap, float(np.min(np.abs(iou.astype(np.float64) - float(thr)) - bound)))
         alive[rest[iou > thr]] = False
     sel = np.asarray(sel, np.int64)
     out = b[sel] if len(sel) else np.zeros((0, 4), dtype)
@@ -135,4 +137,78 @@ def proposals(cls_score, bbox_pred, ref_anchors, stride, im_h, im_w, nms_thresho
                         np.maximum(np.minimum(out[:, 2], wmax), zero), np.maximum(np.minimum(out[:, 3], hmax), zero)], axis=1)
     idx = order[sel] if len(sel) else np.zeros(0, np.int64)
     return dict(scores=sc[idx], proposals=clipped, indices=idx.astype(np.int32), all_scores=sc, all_boxes=bx, kept=len(cand),
-                order=order, min_gap=min_gap)
+                order=order, min_gap=min_gap if gaps else None)
+
+
+def run_case(c, dtype=np.float32, gaps=True):
+    """``proposals`` on a case dict of tests/nuset_cases.py."""
+    return proposals(c['cls'], c['bbox'], c['ref'], c['stride'], c['im_h'], c['im_w'], c['thr'], c['pre'], c['post'], dtype=dtype, gaps=gaps)
+
+
+def judge(c):
+    """What makes a case fit for an exact comparison with the device: the float32 run (the device's arithmetic) and the float64
+    adjudicator agree on the order of the kept candidates, scores that differ in float64 differ in float32 (ties are ties in both:
+    equal inputs), both select the same candidates, and no pair decision of either run comes closer to the threshold than
+    coordinate errors of ``coord_tol`` can move an IoU.  -> (None when all of that holds, else the first condition that fails as
+    a string; the float32 run)."""
+    a, b = run_case(c, np.float32), run_case(c, np.float64)
+    return _first_failure(c, a, b), a
+
+
+def undecided(c):
+    """None when case ``c`` is decided alike in float32 and float64 (``judge``), else the reason it is not."""
+    return judge(c)[0]
+
+
+def _first_failure(c, a, b):
+    if a['all_scores'].dtype != np.float32 or b['all_scores'].dtype != np.float64:
+        return 'the runs are not float32 and float64'
+    if a['kept'] != b['kept']:
+        return 'kept %d in float32, %d in float64' % (a['kept'], b['kept'])
+    if not np.array_equal(a['order'], b['order']):
+        return 'the top-k order differs at %d places' % int((a['order'] != b['order']).sum())
+    sa, sb = a['all_scores'][a['order']], b['all_scores'][b['order']]
+    if not np.array_equal(sa[:-1] == sa[1:], sb[:-1] == sb[1:]):
+        return 'scores tie in one precision only'
+    if not np.array_equal(a['indices'], b['indices']):
+        return 'the selections differ'
+    if not (a['min_gap'] > 0 and b['min_gap'] > 0):
+        return 'IoU gap %.3g (float32), %.3g (float64)' % (a['min_gap'], b['min_gap'])
+    if len(a['scores']):
+        err = float(np.abs(a['proposals'].astype(np.float64) - b['proposals']).max())
+        if not err <= coord_tol(c['im_h'], c['im_w']):
+            return 'coordinates differ by %.3g' % err
+        if not np.abs(a['scores'].astype(np.float64) - b['scores']).max() < 1e-6:
+            return 'scores differ by 1e-6 or more'
+    return None
+
+
+def case_mismatches(gpu, c, want, raw=False):
+    """One device call (``gpu``: a ``_lib.Handle``) on case ``c`` against the restatement's run ``want``, by the assertions of
+    tests/test_gpu_nuset.py ``test_proposals_from_given_tensors``; shared by that module and tools/fuzz_nuset.py -> (differences as strings, largest coordinate error, coordinates that are not
+    bit-equal[, the device's (scores, proposals, indices)])."""
+    scores, props, idx = gpu.rpn_proposals(c['cls'], c['bbox'], c['ref'], c['stride'], c['im_h'], c['im_w'], c['thr'], c['pre'], c['post'])
+    bad, err, unequal = [], 0.0, 0
+    if (scores.dtype, props.dtype, idx.dtype) != (np.float32, np.float32, np.int32):
+        bad.append('dtypes %s %s %s' % (scores.dtype, props.dtype, idx.dtype))
+    if not (len(scores) == len(props) == len(idx)) or props.shape != (len(idx), 4):
+        bad.append('shapes %s %s %s' % (scores.shape, props.shape, idx.shape))
+    elif idx.tolist() != want['indices'].tolist():
+        n = min(len(idx), len(want['indices']))
+        first = int(np.argmax(idx[:n] != want['indices'][:n])) if (idx[:n] != want['indices'][:n]).any() else n
+        bad.append('%d indices, %d expected, the first difference at %d' % (len(idx), len(want['indices']), first))
+    else:
+        if not np.array_equal(scores, want['scores']):
+            bad.append('%d scores differ' % int((scores != want['scores']).sum()))
+        if len(idx):
+            err = float(np.abs(props.astype(np.float64) - want['proposals'].astype(np.float64)).max())
+            unequal = int((props != want['proposals']).sum())
+            tol = 4 * float(np.spacing(np.float32(max(c['im_h'], c['im_w']))))
+            if not err <= tol:
+                bad.append('coordinate error %g above %g' % (err, tol))
+            if not np.all(np.diff(scores) <= 0):
+                bad.append('scores increase')
+            if not (props[:, [0, 2]].min() >= 0 and props[:, [0, 2]].max() <= c['im_w'] - 1 and props[:, [1, 3]].min() >= 0
+                    and props[:, [1, 3]].max() <= c['im_h'] - 1):
+                bad.append('a proposal outside the image')
+    return (bad, err, unequal, (scores, props, idx)) if raw else (bad, err, unequal)

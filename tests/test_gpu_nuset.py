@@ -1,7 +1,13 @@
 """NuSeT's network stage on the device (csrc/nuset_kernels.hip, ecseg_nuset_forward, ecseg_rpn_proposals[_last]): the three-output
 plan against the CPU oracle (oracle/unet.py), the argmax mask against the device's own logits, and the proposal layer against its
 float32 restatement (tests/nuset_ref.py) on the cases of tests/nuset_cases.py - selected candidates and scores exactly, coordinates
-within a few float32 ulp.  tests/test_nuset.py shows without a GPU that no decision of those cases hangs on a rounding."""
+within a few float32 ulp.  tests/test_nuset.py shows without a GPU that no decision of those cases hangs on a rounding.
+
+Beyond the hand-made cases: the boundary cases (sort lengths 2048 .. 32768 with none, one and thousands of padding keys, K = 8192,
+ties across sort blocks, cuts by pre_nms_top_n and post_nms_top_n, thousands of filtered candidates, and ``whole_order``, whose
+result is the device's entire sorted order), the decided seeds of the committed random range, one handle over calls of changing
+size, and the seeds that tools/fuzz_nuset.py once found failing.  ``case_mismatches`` is the comparison of all of them and of
+that campaign (tests/nuset_ref.py)."""
 import os
 import sys
 
@@ -149,3 +155,76 @@ def test_error_paths(gpu, weights):
         gpu.rpn_proposals(c['cls'], c['bbox'], c['ref'], 16, 32, 48, 0.3, pre_nms_top_n=_lib.Handle.RPN_MAX_PRE_NMS + 1)
     with pytest.raises(ValueError):
         gpu.rpn_proposals(c['cls'], c['bbox'][..., :8], c['ref'], 16, 32, 48, 0.3)
+
+
+# ---- boundary cases, the seeded range, handle reuse ---------------------------------------------------------------------------
+def _want(c):
+    return ref.run_case(c, gaps=False)                       # (decided already: tests/test_nuset.py)
+
+
+case_mismatches = ref.case_mismatches
+
+
+@pytest.fixture(scope='module')
+def boundary():
+    """name -> (case, float32 restatement), each computed when first asked for and then shared."""
+    made = {}
+
+    def get(name):
+        if name not in made:
+            c = getattr(cases, name)()
+            made[name] = (c, _want(c))
+        return made[name]
+    return get
+
+
+@pytest.mark.parametrize('name', [f.__name__ for f in cases.BOUNDARY])
+def test_boundary_cases(gpu, boundary, name):
+    c, want = boundary(name)
+    bad, err, unequal, (scores, props, idx) = case_mismatches(gpu, c, want, raw=True)
+    print(name, 'n_out', len(idx), 'expected', len(want['indices']), 'max coordinate error', err, 'coordinates not bit-equal', unequal)
+    assert not bad, (name, bad)
+    if name == 'whole_order':
+        assert len(idx) == 8192 and sorted(idx.tolist()) == list(range(8192))
+
+
+def test_random_cases(gpu):
+    decided = [s for s in cases.RANDOM_SEEDS if s not in cases.RANDOM_UNDECIDED]
+    assert 10 * len(decided) >= 9 * len(cases.RANDOM_SEEDS)
+    failing, worst, unequal, compared = {}, 0.0, 0, 0
+    for seed in decided:
+        c = cases.random_case(seed)
+        want = _want(c)
+        bad, err, ne = case_mismatches(gpu, c, want)
+        worst, unequal, compared = max(worst, err), unequal + ne, compared + len(want['indices'])
+        if bad:
+            failing[seed] = bad
+    print('seeds', len(decided), 'skipped as undecided', list(cases.RANDOM_UNDECIDED), 'proposals compared', compared,
+          'max coordinate error', worst, 'coordinates not bit-equal', unequal)
+    assert not failing, failing
+
+
+def test_handle_reuse_across_sizes(gpu, boundary):
+    """The key and matrix buffers only grow and are never cleared, and the row pitch of the matrix changes from call to call: a
+    large call, two smaller ones, and the large one again on one handle."""
+    out = []
+    for name, (c, want) in (('n21504', boundary('n21504')), ('small', (cases.small(), _want(cases.small()))), ('n2050', boundary('n2050')),
+                            ('n21504', boundary('n21504'))):
+        bad, err, unequal, got = case_mismatches(gpu, c, want, raw=True)
+        print(name, 'n_out', len(got[2]), 'max coordinate error', err)
+        assert not bad, (name, len(out), bad)
+        out.append([a.copy() for a in got])
+    assert all(a.tobytes() == b.tobytes() for a, b in zip(out[0], out[3]))
+
+
+# Seeds of tools/fuzz_nuset.py that once failed, as (seed, max_positions); none so far
+CAMPAIGN_REGRESSIONS = ()
+
+
+def test_regressions(gpu):
+    for seed, max_positions in CAMPAIGN_REGRESSIONS:
+        c = cases.random_case(seed, max_positions)
+        reason, want = ref.judge(c)
+        assert reason is None, (seed, max_positions, reason)
+        bad, err, unequal = case_mismatches(gpu, c, want)
+        assert not bad, (seed, max_positions, bad)
