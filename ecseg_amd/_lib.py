@@ -16,7 +16,7 @@ EXPORTS = [
     'ecseg_segment_images', 'ecseg_segment_images_ex', 'ecseg_segment_images_dev', 'ecseg_set_images_per_group', 'ecseg_set_option', 'ecseg_preprocess', 'ecseg_u16_to_u8',
     'ecseg_meta_segment', 'ecseg_prefetch_input', 'ecseg_host_alloc', 'ecseg_host_free',
     'ecseg_stitch_argmax', 'ecseg_meta_inference', 'ecseg_meta_inference_dev', 'ecseg_count_cc', 'ecseg_ccl_labels',
-    'ecseg_count_colocalization', 'ecseg_count_hsr', 'ecseg_overlay', 'ecseg_nuclei_regions', 'ecseg_nucleus_crops', 'ecseg_fish_distances', 'ecseg_fish_spots', 'ecseg_min_cut', 'ecseg_nuset_forward', 'ecseg_rpn_proposals', 'ecseg_rpn_proposals_last', 'ecseg_get_timings',
+    'ecseg_count_colocalization', 'ecseg_count_hsr', 'ecseg_overlay', 'ecseg_nuclei_regions', 'ecseg_nucleus_crops', 'ecseg_fish_distances', 'ecseg_fish_spots', 'ecseg_min_cut', 'ecseg_nuset_forward', 'ecseg_rpn_proposals', 'ecseg_rpn_proposals_last', 'ecseg_marker_watershed', 'ecseg_clean_nuclei', 'ecseg_get_timings',
     'ecseg_set_kernel_profiling', 'ecseg_get_conv_profile', 'ecseg_get_conv_executed_flops', 'ecseg_get_conv_launch_profile', 'ecseg_debug_peek', 'ecseg_lzw_decode', 'ecseg_lzw_encode',
     'ecseg_comm_unique_id', 'ecseg_comm_create', 'ecseg_comm_destroy', 'ecseg_comm_last_error', 'ecseg_allgather_records', 'ecseg_allgather_records_dev',
     'ecseg_npy_write_i64', 'ecseg_png_write_labels', 'ecseg_png_write', 'ecseg_png_write_channel', 'ecseg_npy_label_info', 'ecseg_npy_read_labels_u8', 'ecseg_tiff_write_gray8', 'ecseg_tiff_info', 'ecseg_tiff_read',
@@ -105,6 +105,8 @@ def load_library():
     lib.ecseg_nuset_forward.argtypes = [vp, vp, i32, i32, i32, i32, vp]
     lib.ecseg_rpn_proposals.argtypes = [vp, vp, vp, i32, i32, i32, vp, i32, i32, i32, C.c_float, i32, i32, C.POINTER(C.c_int32), vp, vp, vp]
     lib.ecseg_rpn_proposals_last.argtypes = [vp, i32, vp, i32, i32, i32, C.c_float, i32, i32, C.POINTER(C.c_int32), vp, vp, vp]
+    lib.ecseg_marker_watershed.argtypes = [vp, vp, i32, i32, vp, vp, vp, C.c_longlong, vp]
+    lib.ecseg_clean_nuclei.argtypes = [vp, vp, i32, i32, i32, vp, vp, C.POINTER(C.c_double)]
     lib.ecseg_get_timings.argtypes = [vp, vp]
     lib.ecseg_set_kernel_profiling.argtypes = [vp, i32]
     lib.ecseg_get_conv_profile.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double)]
@@ -599,6 +601,39 @@ class Handle:
                                                       int(pre_nms_top_n), int(post_nms_top_n), C.byref(n), _ptr(sc), _ptr(pr), _ptr(ix)),
                     'ecseg_rpn_proposals_last')
         return sc[:n.value], pr[:n.value], ix[:n.value]
+
+    @staticmethod
+    def _mask_u8(mask, what):
+        m = np.asarray(mask)
+        if m.ndim != 2:
+            raise ValueError('%s takes one (H, W) mask' % what)
+        if m.dtype.kind not in 'biu':
+            raise TypeError('%s: expected a bool / integer mask, got %s' % (what, m.dtype))
+        return np.ascontiguousarray(m != 0, np.uint8) if m.dtype != np.uint8 else np.ascontiguousarray(m)
+
+    def marker_watershed(self, mask, rows, cols, labels):
+        """(H, W) bool / integer mask + the ordered marker list (``nuset.watershed_markers``) -> uint8 (H, W): the mask where the
+        marker watershed with lines put a label, 0 on the lines and where no marker reaches (ecseg_marker_watershed)."""
+        m = self._mask_u8(mask, 'marker_watershed')
+        r, c, l = (np.ascontiguousarray(a, np.int32).reshape(-1) for a in (rows, cols, labels))
+        if not (len(r) == len(c) == len(l)):
+            raise ValueError('marker_watershed: rows, cols and labels differ in length')
+        out = np.empty(m.shape, np.uint8)
+        self._check(self.lib.ecseg_marker_watershed(self.h, _ptr(m), m.shape[0], m.shape[1], _ptr(r), _ptr(c), _ptr(l), len(r), _ptr(out)),
+                    'ecseg_marker_watershed')
+        return out
+
+    def clean_nuclei(self, mask, nuclei_size_T, want_cleaned=False):
+        """(H, W) bool / integer mask, != 0 foreground (``_watershed``'s output) -> (uint8 0 / 255 final mask, mean_area) (ecseg_clean_nuclei:
+        ``clean_image`` and the threshold of src/utils.py:159-162); ``want_cleaned``: ``clean_image``'s own 0 / 1 output as a third
+        value."""
+        m = self._mask_u8(mask, 'clean_nuclei')
+        out = np.empty(m.shape, np.uint8)
+        cleaned = np.empty(m.shape, np.uint8) if want_cleaned else None
+        mean = C.c_double()
+        self._check(self.lib.ecseg_clean_nuclei(self.h, _ptr(m), m.shape[0], m.shape[1], int(nuclei_size_T), _ptr(out), _ptr(cleaned),
+                                                C.byref(mean)), 'ecseg_clean_nuclei')
+        return (out, mean.value, cleaned) if want_cleaned else (out, mean.value)
 
     # ---- timing ---------------------------------------------------------------------------------------
     def timings(self):

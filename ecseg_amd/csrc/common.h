@@ -272,4 +272,20 @@ int rpn_sort_len(int N);      // N padded to the power of two the sort works on
 hipError_t run_rpn_proposals(const float* cls, int cls_cs, const float* bbox, int bbox_cs, const double* ref, int fh, int fw, int A, int stride,
                              int im_h, int im_w, float nms_threshold, int pre, int post, const RpnBufs& b, hipStream_t s);
 
+// ---- launcher implemented in watershed_kernels.hip (src/nuset_utils/normalization.py:25-37, src/utils.py:159-162) ------------
+// Device buffers of one H x W image: par and sz (H*W int32), tmp, cleaned and out (H*W uint8), misc (4 int32: cells, pixels, the
+// value flags of `cleaned`, 0) and dbl (2 float64: mean_area, mean_area / 5).
+struct CleanBufs { int32_t* par; int32_t* sz; uint8_t* tmp; uint8_t* cleaned; uint8_t* out; int32_t* misc; double* dbl; };
+// mask: (H, W) uint8 on the device, H * W < 2^31 -> cleaned (clean_image, 0 / 1), out (the final mask, 0 / 255), dbl[0] = mean_area.
+hipError_t run_clean_nuclei(const uint8_t* mask, int H, int W, int nuclei_size_t, const CleanBufs& b, hipStream_t s);
+
+// Device buffers of run_marker_watershed for one H x W image: idx, rw, g, d2, lab, par, sz (H*W int32), work, filled, out (H*W
+// uint8), misc (4 int32: [0] `filled` holds a zero, [1] heap overflow) and the heap (heap_cap keys and payloads).
+struct WatershedBufs { int32_t* idx; int32_t* rw; int32_t* g; int32_t* d2; int32_t* lab; int32_t* par; int32_t* sz; uint8_t* work;
+                       uint8_t* filled; uint8_t* out; int32_t* misc; unsigned long long* heap_k; int2* heap_p; };
+// mask (H, W) uint8 and the n ordered markers (validated by the caller) on the device -> out = mask * (flooded label != 0).
+// heap_cap >= 5 * (non-zero mask pixels) + 1: every marker pixel once, at most four pushes per expanded pixel.
+hipError_t run_marker_watershed(const uint8_t* mask, int H, int W, const int32_t* rows, const int32_t* cols, const int32_t* labels, int n,
+                                int heap_cap, const WatershedBufs& b, hipStream_t s);
+
 }  // namespace ecseg

@@ -147,6 +147,15 @@ struct DevMem {
     DevBuf<float4> d_nu_boxes, d_nu_oboxes;
     DevBuf<unsigned long long> d_nu_keys, d_nu_mat;
     DevBuf<int32_t> d_nu_misc, d_nu_oidx;
+    // ecseg_clean_nuclei
+    DevBuf<uint8_t> d_cl_mask, d_cl_tmp, d_cl_cleaned, d_cl_out;
+    DevBuf<int32_t> d_cl_par, d_cl_sz, d_cl_misc;
+    DevBuf<double> d_cl_dbl;
+    // ecseg_marker_watershed (par, sz, misc and the mask are those of ecseg_clean_nuclei)
+    DevBuf<int32_t> d_ws_idx, d_ws_rw, d_ws_g, d_ws_d2, d_ws_lab, d_ws_mk;
+    DevBuf<uint8_t> d_ws_work, d_ws_filled;
+    DevBuf<unsigned long long> d_ws_hk;
+    DevBuf<int2> d_ws_hp;
 };
 
 }  // namespace ecseg

@@ -597,4 +597,100 @@ int ecseg_rpn_proposals_last(ecseg_ctx* h, int A, const double* ref_anchors, int
                       post_nms_top_n, n_out, scores, proposals, indices);
 }
 
+// ---- NuSeT's marker watershed (src/model_layers/marker_watershed.py:82-91) ----------------------------------------------------
+int ecseg_marker_watershed(ecseg_ctx* h, const uint8_t* mask, int H, int W, const int32_t* marker_rows, const int32_t* marker_cols,
+                           const int32_t* marker_labels, long long n_markers, uint8_t* out) {
+    if (!h) return ECSEG_E_INVALID;
+    drop_sent_ahead(h);
+    if (!mask || !out || H <= 0 || W <= 0) return fail(h, ECSEG_E_INVALID, "marker_watershed: bad arguments");
+    if (H > ECSEG_WATERSHED_MAX_EXTENT || W > ECSEG_WATERSHED_MAX_EXTENT)
+        return fail(h, ECSEG_E_INVALID, "marker_watershed: an extent above " + std::to_string(ECSEG_WATERSHED_MAX_EXTENT));
+    if (n_markers < 0 || n_markers >= (1ll << 31) || (n_markers > 0 && (!marker_rows || !marker_cols || !marker_labels)))
+        return fail(h, ECSEG_E_INVALID, "marker_watershed: n_markers must be between 0 and 2^31 - 1, with the three lists");
+    const int n = (int)n_markers;
+    for (int i = 0; i < n; ++i) {
+        if (marker_rows[i] < 0 || marker_rows[i] >= H || marker_cols[i] < 0 || marker_cols[i] >= W)
+            return fail(h, ECSEG_E_INVALID, "marker_watershed: marker " + std::to_string(i) + " lies outside the image");
+        if (marker_labels[i] < 1) return fail(h, ECSEG_E_INVALID, "marker_watershed: marker " + std::to_string(i) + " has a label below 1");
+    }
+    const size_t px = (size_t)H * W;
+    size_t fg = 0;
+    for (size_t p = 0; p < px; ++p) fg += mask[p] != 0;
+    if (5 * fg + 1 >= (1ull << 31)) return fail(h, ECSEG_E_INVALID, "marker_watershed: the mask holds too many pixels for one heap");
+    const int cap = (int)(5 * fg + 1);
+    HIP_TRY(h, hipSetDevice(h->device));
+    int rc;
+    if ((rc = h->d_cl_mask.ensure(h, px))) return rc;
+    if ((rc = h->d_cl_out.ensure(h, px))) return rc;
+    if ((rc = h->d_cl_par.ensure(h, px))) return rc;
+    if ((rc = h->d_cl_sz.ensure(h, px))) return rc;
+    if ((rc = h->d_cl_misc.ensure(h, 4))) return rc;
+    if ((rc = h->d_ws_idx.ensure(h, px))) return rc;
+    if ((rc = h->d_ws_rw.ensure(h, px))) return rc;
+    if ((rc = h->d_ws_g.ensure(h, px))) return rc;
+    if ((rc = h->d_ws_d2.ensure(h, px))) return rc;
+    if ((rc = h->d_ws_lab.ensure(h, px))) return rc;
+    if ((rc = h->d_ws_work.ensure(h, px))) return rc;
+    if ((rc = h->d_ws_filled.ensure(h, px))) return rc;
+    if ((rc = h->d_ws_mk.ensure(h, 3 * (size_t)std::max(n, 1)))) return rc;
+    if ((rc = h->d_ws_hk.ensure(h, (size_t)cap))) return rc;
+    if ((rc = h->d_ws_hp.ensure(h, (size_t)cap))) return rc;
+    hipStream_t s = h->stream;
+    for (float& v : h->stage_ms) v = 0.f;
+    int32_t* d_rows = h->d_ws_mk; int32_t* d_cols = d_rows + n; int32_t* d_labels = d_cols + n;
+    HIP_TRY(h, hipMemcpyAsync(h->d_cl_mask, mask, px, hipMemcpyHostToDevice, s));
+    if (n > 0) {
+        HIP_TRY(h, hipMemcpyAsync(d_rows, marker_rows, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        HIP_TRY(h, hipMemcpyAsync(d_cols, marker_cols, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        HIP_TRY(h, hipMemcpyAsync(d_labels, marker_labels, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    }
+    const WatershedBufs b{h->d_ws_idx, h->d_ws_rw, h->d_ws_g, h->d_ws_d2, h->d_ws_lab, h->d_cl_par, h->d_cl_sz, h->d_ws_work, h->d_ws_filled,
+                          h->d_cl_out, h->d_cl_misc, h->d_ws_hk, h->d_ws_hp};
+    HIP_TRY(h, hipEventRecord(h->ev[0], s));
+    HIP_TRY(h, run_marker_watershed(h->d_cl_mask, H, W, d_rows, d_cols, d_labels, n, cap, b, s));
+    HIP_TRY(h, hipEventRecord(h->ev[1], s));
+    int32_t misc[4] = {0, 0, 0, 0};
+    HIP_TRY(h, hipMemcpyAsync(out, h->d_cl_out, px, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipMemcpyAsync(misc, h->d_cl_misc, sizeof(misc), hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    h->stage_ms[ECSEG_T_COUNT] = stage_elapsed(h->ev[0], h->ev[1]);
+    if (misc[1]) return fail(h, ECSEG_E_HIP, "marker_watershed: the heap overflowed its bound");
+    return ECSEG_OK;
+}
+
+// ---- NuSeT's clean-up behind the marker watershed (src/nuset_utils/normalization.py:25-37, src/utils.py:159-162) -----------------
+int ecseg_clean_nuclei(ecseg_ctx* h, const uint8_t* mask, int H, int W, int nuclei_size_t, uint8_t* out, uint8_t* cleaned, double* mean_area) {
+    if (!h) return ECSEG_E_INVALID;
+    drop_sent_ahead(h);
+    if (!mask || !out || H <= 0 || W <= 0) return fail(h, ECSEG_E_INVALID, "clean_nuclei: bad arguments");
+    if ((long long)H * W >= (1ll << 31)) return fail(h, ECSEG_E_INVALID, "clean_nuclei: the image must hold fewer than 2^31 pixels");
+    if (nuclei_size_t < 0) return fail(h, ECSEG_E_INVALID, "clean_nuclei: nuclei_size_T must not be negative");
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t px = (size_t)H * W;
+    int rc;
+    if ((rc = h->d_cl_mask.ensure(h, px))) return rc;
+    if ((rc = h->d_cl_tmp.ensure(h, px))) return rc;
+    if ((rc = h->d_cl_cleaned.ensure(h, px))) return rc;
+    if ((rc = h->d_cl_out.ensure(h, px))) return rc;
+    if ((rc = h->d_cl_par.ensure(h, px))) return rc;
+    if ((rc = h->d_cl_sz.ensure(h, px))) return rc;
+    if ((rc = h->d_cl_misc.ensure(h, 4))) return rc;
+    if ((rc = h->d_cl_dbl.ensure(h, 2))) return rc;
+    hipStream_t s = h->stream;
+    for (float& v : h->stage_ms) v = 0.f;
+    HIP_TRY(h, hipMemcpyAsync(h->d_cl_mask, mask, px, hipMemcpyHostToDevice, s));
+    const CleanBufs b{h->d_cl_par, h->d_cl_sz, h->d_cl_tmp, h->d_cl_cleaned, h->d_cl_out, h->d_cl_misc, h->d_cl_dbl};
+    HIP_TRY(h, hipEventRecord(h->ev[0], s));
+    HIP_TRY(h, run_clean_nuclei(h->d_cl_mask, H, W, nuclei_size_t, b, s));
+    HIP_TRY(h, hipEventRecord(h->ev[1], s));
+    double dbl[2] = {0.0, 0.0};
+    HIP_TRY(h, hipMemcpyAsync(out, h->d_cl_out, px, hipMemcpyDeviceToHost, s));
+    if (cleaned) HIP_TRY(h, hipMemcpyAsync(cleaned, h->d_cl_cleaned, px, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipMemcpyAsync(dbl, h->d_cl_dbl, sizeof(dbl), hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    if (mean_area) *mean_area = dbl[0];
+    h->stage_ms[ECSEG_T_COUNT] = stage_elapsed(h->ev[0], h->ev[1]);
+    return ECSEG_OK;
+}
+
 }  // extern "C"

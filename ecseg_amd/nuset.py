@@ -1,7 +1,9 @@
 """NuSeT's network stage (reference src/utils.py:35-103, ``load_nuset``): everything ``sess.run([pred_masks, scores, proposals])``
 computes - the U-Net's argmax mask, the RPN head on its pool-4 feature map and the proposal layer (decode, filter, top-k, NMS,
-clip) - on the device, behind one three-output plan.  The ``py_func`` half that follows it in the reference (``marker_watershed``,
-``clean_image``, ``rescale``) is not here.
+clip) - on the device, behind one three-output plan.  The ``py_func`` half that follows it in the reference is here too, at
+``resize_scale == 1`` (``NuSeT.segment``): the marker list of ``marker_watershed`` on the host (``watershed_markers``), the watershed
+(``Handle.marker_watershed``) and ``clean_image`` with the final threshold (``Handle.clean_nuclei``) on the device.  ``rescale`` is not
+(DESIGN.md 5.12, 10).
 
 Host side, as in the reference: ``whole_image_norm`` / ``foreground_norm`` (src/nuset_utils/normalization.py), ``anchor_size``
 (src/model_layers/anchor_size.py, from the region records of ``ecseg_nuclei_regions``) and ``reference_anchors``
@@ -149,6 +151,54 @@ def reference_anchors(base_size):
     return np.stack([0 - (widths - 1) / 2, 0 - (heights - 1) / 2, 0 + (widths - 1) / 2, 0 + (heights - 1) / 2], axis=-1)
 
 
+EDGE_LEN, MIN_REGION_AREA = 20, 10                     # src/model_layers/marker_watershed.py:16,65
+
+
+def _round_half_even(v):
+    return int(round(float(v)))                        # Python's round, as the reference calls it
+
+
+def watershed_markers(scores, proposals, mask, min_score, handle):
+    """The host part of ``_watershed`` (marker_watershed.py:22-80): the ordered marker list as int32 (rows, cols, labels), a later
+    entry overwriting an earlier one on the same pixel, or None for the two branches that leave the mask as it is (no score, or none
+    above ``min_score``).  Kept proposals ascending by score; centre = round-half-even of the float32 mean of the box's ends, the ROW
+    from ``bbox[1]`` and ``bbox[3]``; a marker only where the 20-pixel edge mask is 0; a negative centre wraps as numpy's index does
+    (-21 and below can land inside), one past the image raises IndexError as the reference does (the proposal layer clips its boxes
+    to the image, so neither happens behind it).  Then one marker at the centre of the clipped bounding box of
+    every 8-connected region of at least 10 pixels (the records of ``handle.nuclei_regions``, in skimage's order) whose box holds
+    no marker yet, possibly on a background pixel."""
+    scores = np.asarray(scores, np.float32).reshape(-1)
+    proposals = np.asarray(proposals, np.float32).reshape(-1, 4)
+    m = (np.asarray(mask) != 0).astype(np.uint8)
+    if m.ndim != 2 or len(scores) != len(proposals):
+        raise ValueError('watershed_markers takes n scores, (n, 4) proposals and one (H, W) mask')
+    H, W = m.shape
+    if scores.size == 0 or not scores.max() > min_score:
+        return None
+    top = scores > min_score
+    proposals = proposals[top][scores[top].argsort()]
+    placed = np.zeros((H, W), bool)
+    rows, cols = [], []
+    for b in proposals:
+        r = _round_half_even((b[3] + b[1]) / np.float32(2))
+        c = _round_half_even((b[2] + b[0]) / np.float32(2))
+        if not (-H <= r < H and -W <= c < W):
+            raise IndexError('watershed_markers: centre (%d, %d) lies outside the %d x %d image' % (r, c, H, W))
+        r, c = r % H, c % W
+        if EDGE_LEN <= r < H - EDGE_LEN and EDGE_LEN <= c < W - EDGE_LEN:
+            rows.append(r); cols.append(c)
+            placed[r, c] = True
+    for area, r0, c0, r1, c1 in np.asarray(handle.nuclei_regions(m, m[..., None], 0))[:, :5]:
+        if area < MIN_REGION_AREA:
+            continue
+        r0, r1, c0, c1 = (int(min(v, lim - 1)) for v, lim in ((r0, H), (r1, H), (c0, W), (c1, W)))
+        if not placed[r0:r1, c0:c1].any():
+            r, c = _round_half_even((r0 + r1) / 2), _round_half_even((c0 + c1) / 2)
+            rows.append(r); cols.append(c)
+            placed[r, c] = True
+    return np.asarray(rows, np.int32), np.asarray(cols, np.int32), np.arange(1, len(rows) + 1, dtype=np.int32)
+
+
 def _empty():
     return np.zeros(0, np.float32), np.zeros((0, 4), np.float32)
 
@@ -212,3 +262,11 @@ class NuSeT:
         m, scores, proposals = (second or self).run(fg, nms_threshold)
         top = scores > min_score
         return m, scores[top], proposals[top]
+
+    def segment(self, image, min_score=0.95, nms_threshold=0.01, nuclei_size_T=0, second=None):
+        """``nuclei_segment`` at ``resize_scale == 1`` (src/utils.py:134-163): ``nuclei_masks``, the markers, the marker watershed,
+        ``clean_image`` and the final threshold -> uint8 0 / 255 mask of the cropped extent (multiples of 16)."""
+        m, scores, proposals = self.nuclei_masks(image, min_score, nms_threshold, second)
+        mk = watershed_markers(scores, proposals, m, min_score, self.handle)
+        ws = m if mk is None else self.handle.marker_watershed(m, *mk)
+        return self.handle.clean_nuclei(ws, nuclei_size_T)[0]

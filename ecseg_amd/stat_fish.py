@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
 """``make stat_fish``: per-nucleus FISH spot statistics (reference src/stat_fish.py), everything behind ``nuclei_segment``.
 
-The nucleus mask of every image is read from ``<masks>/<name>.tif`` (config key ``masks``, default ``<inpath>/nuclei_masks``):
-NuSeT, whose TF1 checkpoints this project cannot load, stays out of scope, and any segmenter writing an 8-bit single-sample
-TIFF there, non-zero = nucleus, will do.  Per image the nuclei are labelled on the device (``Handle.ccl_labels``, 8-connected,
+The nucleus mask of every image comes from NuSeT on the device (config key ``nuset_weights``: ``NuSeT.segment`` on channel 0) or, without
+that key, is read from ``<masks>/<name>.tif`` (config key ``masks``, default ``<inpath>/nuclei_masks``):
+any segmenter writing an 8-bit single-sample TIFF there, non-zero = nucleus, will do (NuSeT's weights come as an ``.npz``: TF1
+checkpoints are not read).  Per image the nuclei are labelled on the device (``Handle.ccl_labels``, 8-connected,
 skimage's order) - or, with ``use_min_cut: True``, labelled 4-connected and split by the min-cut splitter (src/max_flow_binary_mask.py
 -> ecseg_amd/min_cut.py, whose maximum flows run on the device: ``Handle.min_cut``), which also adds the sixth file
 ``<name>_segmentation_corrected_min_cut.tif`` - and one more device call (``Handle.fish_spots`` -> ecseg_fish_spots, csrc/fishspot_kernels.hip) returns the
@@ -59,6 +60,11 @@ PROBE_NAMES = ('green', 'red')
 MAX_KERNEL = 63                # ECSEG_FISH_SPOT_MAX_KERNEL
 MAX_LINE = 16                  # ECSEG_FISH_SPOT_MAX_LINE
 MAX_DIST = 32                  # ECSEG_MIN_CUT_MAX_DIST
+
+
+# the parameters of nuclei_segment in src/stat_fish_params.yaml, read only with the config key nuset_weights; scale_ratio: the
+# reference's file says 0.3, but rescale is not built, so 1 is the only value taken
+NUSET_DEFAULT_PARAMS = {'min_score': 0.95, 'nms_threshold': 0.01, 'scale_ratio': 1}
 
 
 class ConfigError(Exception):
@@ -187,15 +193,16 @@ def read_mask(path):
     return (m != 0).astype(np.uint8) * np.uint8(255)
 
 
-def process_image(path, mask_path, out_root, params, scale, handle, stats=None, use_min_cut=False):
+def process_image(path, mask_path, out_root, params, scale, handle, stats=None, use_min_cut=False, segment=None):
     """One image of src/stat_fish.py:199-308 -> (CSV rows, the scale that was used).  ``use_min_cut`` (:221-224): the label map comes
-    from the min-cut splitter, already numbered 1..n (its cells need not be connected, which ecseg_fish_spots allows)."""
+    from the min-cut splitter, already numbered 1..n (its cells need not be connected, which ecseg_fish_spots allows).  ``segment``
+    (config key ``nuset_weights``): the mask is ``segment(blue channel)`` (:212-214) instead of the file ``mask_path``."""
     import time
     from . import image_io
     t0 = time.perf_counter()
     img_name = os.path.basename(path)[:-4]
     I, (blue, green, red) = read_image(path, handle)
-    mask = read_mask(mask_path)
+    mask = read_mask(mask_path) if segment is None else segment(I[:, :, blue])
     imheight, imwidth = mask.shape
     I = np.ascontiguousarray(I[:imheight, :imwidth])
     mask = np.ascontiguousarray(mask[:I.shape[0], :I.shape[1]])
@@ -291,6 +298,53 @@ def load_params():
     return params, source
 
 
+def load_nuset_segmenter(var, handle):
+    """The config key ``nuset_weights`` ([whole.npz, foreground.npz], or one path for both passes; optional ``nuset_base``, default
+    64) -> ``segment(blue)`` = ``NuSeT.segment`` with ``min_score`` / ``nms_threshold`` of src/stat_fish_params.yaml and
+    ``nuclei_size_T`` of the config.  Every problem is a ConfigError."""
+    import yaml
+    from . import nuset
+    paths = var['nuset_weights']
+    paths = [paths] if isinstance(paths, str) else paths
+    if not isinstance(paths, list) or len(paths) not in (1, 2) or not all(isinstance(p, str) for p in paths):
+        raise ConfigError('nuset_weights must be one .npz path or a list of two (whole-image and foreground checkpoint)')
+    prm = dict(NUSET_DEFAULT_PARAMS)
+    if os.path.isfile(PARAMS_FILE):
+        with open(PARAMS_FILE) as f:
+            user = yaml.safe_load(f) or {}
+        if isinstance(user, dict):
+            prm.update({k: v for k, v in user.items() if k in prm})
+    for k, v in prm.items():
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or math.isnan(v):
+            raise ConfigError('%s must be a number' % k)
+    if prm['scale_ratio'] != 1:
+        raise ConfigError('scale_ratio: %s with nuset_weights: the rescale step of nuclei_segment (scikit-image\'s anti-aliased rescale) is '
+                          'not built; only scale_ratio: 1 is' % prm['scale_ratio'])
+    size_t = var['nuclei_size_T']
+    if isinstance(size_t, bool) or not isinstance(size_t, int) or size_t < 0:
+        raise ConfigError('nuclei_size_T must be a non-negative integer')
+    base = var.get('nuset_base', 64)
+    if isinstance(base, bool) or not isinstance(base, int) or base < 1:
+        raise ConfigError('nuset_base must be a positive integer')
+    if handle is not None and not all(hasattr(handle, m) for m in ('marker_watershed', 'clean_nuclei', 'nuset_forward', 'rpn_proposals_last')):
+        raise ConfigError('nuset_weights needs NuSeT\'s device calls (nuset_forward, rpn_proposals_last, marker_watershed, clean_nuclei), which '
+                          'the handle in use does not have')
+    weights = []
+    for p in paths:
+        try:
+            weights.append(nuset.load_weights_npz(p, base))
+        except Exception as e:
+            raise ConfigError('nuset_weights: %s cannot be used (%s)' % (p, e))
+    state = {}
+
+    def segment(blue, handle):
+        if 'nets' not in state:
+            state['nets'] = [nuset.NuSeT(w, base, handle=handle) for w in weights]
+        nets = state['nets']
+        return nets[0].segment(blue, prm['min_score'], prm['nms_threshold'], size_t, second=nets[-1] if len(nets) > 1 else None)
+    return segment
+
+
 def current_commit():
     """src/stat_fish.py:186: the last word of ``git log -1 | head -1``; empty without git."""
     try:
@@ -327,7 +381,8 @@ def main(argv=None, handle=None):
         if scale != 'auto' and (isinstance(scale, bool) or not isinstance(scale, (int, float)) or not scale > 0 or math.isinf(scale)):
             raise ConfigError('scale must be a positive number or "auto"')
         masks = str(var['masks']) if var.get('masks') is not None else os.path.join(inpath, 'nuclei_masks')
-        if not os.path.isdir(masks):
+        segmenter = load_nuset_segmenter(var, handle) if var.get('nuset_weights') is not None else None
+        if segmenter is None and not os.path.isdir(masks):
             raise ConfigError('The folder of nucleus masks %s does not exist (config key masks): it holds one 8-bit <name>.tif per '
                               'image, non-zero = nucleus' % masks)
         params, params_source = load_params()
@@ -358,7 +413,8 @@ def main(argv=None, handle=None):
             print("Processing image: ", p)
             try:
                 img_rows, scale = process_image(p, os.path.join(masks, os.path.basename(p)[:-4] + '.tif'), out_root, params, scale, handle,
-                                                 use_min_cut=use_min_cut)
+                                                 use_min_cut=use_min_cut,
+                                                 segment=None if segmenter is None else (lambda blue: segmenter(blue, handle)))
                 rows += img_rows
             except ImageError as e:
                 print(p, '-', e)

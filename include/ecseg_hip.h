@@ -419,6 +419,40 @@ int ecseg_rpn_proposals(ecseg_ctx* h, const float* cls_score, const float* bbox_
 int ecseg_rpn_proposals_last(ecseg_ctx* h, int A, const double* ref_anchors, int stride, int im_h, int im_w, float nms_threshold,
                              int pre_nms_top_n, int post_nms_top_n, int32_t* n_out, float* scores, float* proposals, int32_t* indices);
 
+/* ---- NuSeT's marker watershed --------------------------------------------------------------------------------------------------
+ * Replaces, for ONE image, src/model_layers/marker_watershed.py:82-91 behind the marker loops.  mask: (H, W) uint8, != 0 is
+ * foreground; the n_markers markers (row, column, label >= 1) in the reference's order, a later one overwriting an earlier one on
+ * the same pixel (ecseg_amd/nuset.py: watershed_markers builds the list of :22-80 on the host).  On the device:
+ *   markers_rw = morphology.dilation(markers, disk(3)): the maximum label over the 29 offsets (:82), times the mask;
+ *   distance   = distance_transform_edt(binary_fill_holes(mask)) (:83) as the exact integer d^2 (holes: 4-connected background
+ *                components off the border; a filled mask without a zero gets scipy's answer, the distance to (-1, 0));
+ *   contour    = segmentation.watershed(-distance, markers_rw, mask=mask, watershed_line=True) of scikit-image 0.18 (:84): one
+ *                binary heap on (value, age) with that library's sift rules, replayed as one serial stream, because marker
+ *                pixels of equal d^2 carry equal keys and the heap's order among them shows in the result;
+ *   out (H, W) uint8 = mask where contour != 0, else 0 (:85,91).  A component no marker reaches stays 0; n_markers = 0 gives 0.
+ * One synchronous call, buffers of its own, no host work per component or pixel; device time in ECSEG_T_COUNT.  The flood is
+ * serial: its time grows with the foreground area (about five heap operations per pixel).  ECSEG_E_INVALID: null mask or out; H or
+ * W outside 1 .. ECSEG_WATERSHED_MAX_EXTENT; n_markers < 0 or >= 2^31; a marker outside the image or with a label < 1. */
+#define ECSEG_WATERSHED_MAX_EXTENT 16384
+int ecseg_marker_watershed(ecseg_ctx* h, const uint8_t* mask, int H, int W, const int32_t* marker_rows, const int32_t* marker_cols,
+                           const int32_t* marker_labels, long long n_markers, uint8_t* out);
+
+/* ---- NuSeT's clean-up behind the marker watershed ----------------------------------------------------------------------------
+ * Replaces, for ONE image, clean_image (src/nuset_utils/normalization.py:25-37) and the final threshold of nuclei_segment
+ * (src/utils.py:159-162).  mask: (H, W) uint8, != 0 is foreground (what _watershed returns).
+ *   mean_area = float32(foreground pixels) / number of 4-connected components, in float64 (:28-30; NaN without a component);
+ *   remove_small_objects(min_size = mean_area / 5, connectivity = 2), then remove_small_holes(area_threshold = mean_area / 5,
+ *   connectivity = 2), which also fills small background components at the border (:34-36); the areas are compared as
+ *   float64(area) < mean_area / 5, so a NaN removes nothing -> cleaned (H, W) uint8 0 / 1 (may be null);
+ *   the min-max scaling of utils.py:159 leaves an image of one value all zero (0 / 0), everything else becomes 0 / 255 (:160);
+ *   remove_small_objects(bool, nuclei_size_T) with its default connectivity of 1 (:161): 4-connected components below
+ *   nuclei_size_T pixels go, nuclei_size_T = 0 keeps all -> out (H, W) uint8 0 / 255.
+ * *mean_area (may be null) receives mean_area.  One synchronous call, buffers of its own, nothing per component on the host;
+ * device time of the kernels in ECSEG_T_COUNT.  ECSEG_E_INVALID: null mask or out, H or W < 1, H * W >= 2^31, nuclei_size_T < 0.
+ * The results do not depend on the order of the atomics: two calls give identical bytes. */
+int ecseg_clean_nuclei(ecseg_ctx* h, const uint8_t* mask, int H, int W, int nuclei_size_T, uint8_t* out, uint8_t* cleaned,
+                       double* mean_area);
+
 /* ---- per-stage device timings of the last segment call (milliseconds, HIP events on the handle's stream) -- */
 /* ECSEG_T_COUNT: device time of the kernels of the last ecseg_overlay / ecseg_preprocess / ecseg_count_* call (inputs
  * already resident, copies excluded). */
