@@ -50,13 +50,17 @@ __device__ __forceinline__ float apply_act(float v, int act, float alpha) {
     }
 }
 
-// Every activation code: the element-wise kernels (ACT / AFFINE / ADD ops, depthwise convolutions).
+// Every activation code: the element-wise kernels (ACT / AFFINE / ADD ops, depthwise convolutions).  ELU / SELU use expm1f here:
+// expf(v) - 1.f has an absolute error of 2^-24, i.e. no correct digit left at |v| ~ 1e-7 (tests/test_gpu_layers.py holds these two to
+// 3.5 / 5 ulp).  The convolution kernels' apply_act keeps expf(v) - 1.f: their output stages are register-critical, and an error of
+// 2^-24 alpha is below the rounding of the accumulated sum it is applied to.
 __device__ __forceinline__ float apply_act_ext(float v, int act, float alpha) {
     switch (act) {
+        case ECSEG_ACT_ELU: return v > 0.f ? v : alpha * expm1f(v);
         case ECSEG_ACT_SWISH: return v / (1.f + expf(-v));
         case ECSEG_ACT_HARD_SIGMOID: return fminf(fmaxf(0.2f * v + 0.5f, 0.f), 1.f);
         case ECSEG_ACT_SOFTPLUS: return fmaxf(v, 0.f) + log1pf(expf(-fabsf(v)));
-        case ECSEG_ACT_SELU: return 1.05070098735548f * (v > 0.f ? v : 1.67326324235438f * (expf(v) - 1.f));
+        case ECSEG_ACT_SELU: return 1.05070098735548f * (v > 0.f ? v : 1.67326324235438f * expm1f(v));
         case ECSEG_ACT_GELU: return 0.5f * v * (1.f + erff(v * 0.70710678118654752f));
         case ECSEG_ACT_EXP: return expf(v);
         case ECSEG_ACT_SOFTSIGN: return v / (1.f + fabsf(v));

@@ -278,6 +278,7 @@ def _F(layers, ins, outs, name='m'):
 
 
 def _check(gpu, cfg, weights, x, tol=1e-3, output=0, **okw):
+    """Whole chains within ``tol``; tests/test_gpu_layers.py holds each non-convolution kernel alone to a derived per-op bound."""
     want = oracle_unet.forward(cfg, weights, x, output=output, **okw)
     scale = max(1.0, float(np.abs(want).max()))
     for fuse in (True, False):
