@@ -180,6 +180,8 @@ int ecseg_model_load(ecseg_ctx* h, const ecseg_tensor_desc* tensors, int n_tenso
                 if (!rc2) h->mfma_flops_per_patch += o.flops;
                 return rc2;
             };
+            // (tests/conv_exact_cases.py: conv_paths restates the choice of kernel below, for the kernels the launch profile does not
+            // report; a change of these rules belongs there too)
             if (d.op == ECSEG_OP_CONV) {
                 const int dil = d.dilation > 1 ? d.dilation : 1;
                 // anisotropic strides / dilation rates (round 6): CONV's `mode` carries the HORIZONTAL stride (bits 0-7) and dilation rate (bits
