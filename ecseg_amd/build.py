@@ -11,7 +11,7 @@ SOURCES = ['api.hip', 'filter_layout.hip', 'model_load.hip', 'plan_run.hip', 'se
 EXTRA_FLAGS = {'wino4_kernel.hip': ['-fno-slp-vectorize'], 'wino4s_kernel.hip': ['-fno-slp-vectorize'], 'wino4r_kernel.hip': ['-fno-slp-vectorize']}
 # the proposal layer restates TensorFlow's float32 arithmetic op by op: a * b + c must round twice there
 EXTRA_FLAGS['nuset_kernels.hip'] = ['-ffp-contract=off']
-HEADERS = [os.path.join(CSRC, f) for f in ('common.h', 'ctx.h', 'device_util.h', 'wino4_consts.inc', 'wino4_region.inc', 'wino4_combine.inc', 'wino4_head.inc')] + \
+HEADERS = [os.path.join(CSRC, f) for f in ('common.h', 'ctx.h', 'device_util.h', 'cell_util.h', 'wino4_consts.inc', 'wino4_region.inc', 'wino4_combine.inc', 'wino4_head.inc')] + \
     [os.path.join(HERE, '..', 'include', 'ecseg_hip.h')]
 
 

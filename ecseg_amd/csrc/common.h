@@ -224,27 +224,30 @@ hipError_t run_nucleus_crops(const int32_t* labels, const uint8_t* img, int W, i
                              const int order[3], uint8_t* out, int32_t* chmax, hipStream_t s);
 
 // ---- launchers implemented in fishdist_kernels.hip (src/fish_distance_calculation.py:16-46) ---------------------------------
-// Device buffers of one H x W image: rid and par (H*W int32), blk (ceil(H*W / 1024) int32), misc (4 int32), flist and clist
-// (H*W int2), and - sized by the number of cells n, which run_fishdist_cells reports - acc (4n uint32), val (n int32), off and
-// cur (2n int32), rec (8n int64), and pbest (uint64) and proots (int32) of n * fishdist_slices(n) entries each.
+// The dense cell index of one H x W label map, shared with fishspot_kernels.hip: rid (H*W int32), blk (ceil(H*W / 1024) int32)
+// and misc (4 int32).
+struct CellIndexBufs { int32_t* rid; int32_t* blk; int32_t* misc; };
+// labels: (H, W) int32 instance labels, <= 0 background.  Leaves rid[label - 1] = dense ascending cell index of every label that
+// occurs, misc[0] = number of cells, misc[3] = 1 when some label exceeds H * W (rid then misses it: do not go on).
+hipError_t run_dense_cells(const int32_t* labels, int H, int W, const CellIndexBufs& b, hipStream_t s);
+// Device buffers of run_fishdist_records: rid, blk and misc as run_dense_cells left them, par (H*W int32), flist and clist
+// (H*W int2), and - sized by the number of cells n - acc (4n uint32), val (n int32), off and cur (2n int32), rec (8n int64), and
+// pbest (uint64) and proots (int32) of n * fishdist_slices(n) entries each.
 struct FishDistBufs { int32_t* rid; int32_t* par; int32_t* blk; int32_t* misc; int2* flist; int2* clist; unsigned* acc; int32_t* val;
                       int32_t* off; int32_t* cur; int64_t* rec; unsigned long long* pbest; int32_t* proots; };
 int fishdist_slices(int n);   // workgroups per cell of the distance search for n cells
-// labels: (H, W) int32 instance labels, <= 0 background.  Leaves rid[label - 1] = dense ascending cell index of every label that
-// occurs, misc[0] = number of cells, misc[3] = 1 when some label exceeds H * W (rid then misses it: do not go on).
-hipError_t run_fishdist_cells(const int32_t* labels, int H, int W, const FishDistBufs& b, hipStream_t s);
-// After run_fishdist_cells with n = misc[0] > 0 and misc[3] == 0: relabels `labels` in place to cell + 1 and writes the n records
+// After run_dense_cells with n = misc[0] > 0 and misc[3] == 0: relabels `labels` in place to cell + 1 and writes the n records
 // of ecseg_fish_distances to rec.  lsq: (H, W, C) uint8; fi / ci: FISH and centromere channel.
 hipError_t run_fishdist_records(int32_t* labels, const uint8_t* lsq, int H, int W, int C, int fi, int ci, int n, const FishDistBufs& b,
                                 hipStream_t s);
 
 // ---- launcher implemented in fishspot_kernels.hip (src/stat_fish.py:73-107,134-142,226-300) ---------------------------------
-// Device buffers of one H x W image with np probes: rid (H*W int32, as run_fishdist_cells left it), mx (4 int32), thr (H*W*np
+// Device buffers of one H x W image with np probes: rid (H*W int32, as run_dense_cells left it), mx (4 int32), thr (H*W*np
 // uint8), bnd (H*W uint8), par and sz (4 planes of H*W int32 each: probes 0..2, the pair) and - sized by the number of cells n -
 // acc (12n uint64), cnt (8n uint32), val (n int32), rec (ECSEG_FISH_SPOT_INT64 x n int64).
 struct FishSpotBufs { int32_t* rid; int32_t* mx; uint8_t* thr; uint8_t* bnd; int32_t* par; int32_t* sz; unsigned long long* acc;
                       unsigned* cnt; int32_t* val; int64_t* rec; };
-// After run_fishdist_cells with n = misc[0] > 0 and misc[3] == 0: relabels `labels` in place to cell + 1 and writes thr, bnd and the
+// After run_dense_cells with n = misc[0] > 0 and misc[3] == 0: relabels `labels` in place to cell + 1 and writes thr, bnd and the
 // n records of ecseg_fish_spots.  img: (H, W, C) uint8; ch: the np probe channels; wts: K x K float64 on the device.
 hipError_t run_fishspot(int32_t* labels, const uint8_t* img, int H, int W, int C, int np, const int ch[3], const double* wts, int K,
                         double normal_thr, const double ithr[3], int min_cc, int line_t, int n, const FishSpotBufs& b, hipStream_t s);

@@ -122,16 +122,19 @@ struct DevMem {
     DevBuf<uint8_t> d_iseg_img, d_iseg_crops;
     DevBuf<unsigned long long> d_iseg_acc;
     DevBuf<int64_t> d_iseg_rec;
-    // ecseg_fish_distances: buffers of its own (a region map left by ecseg_nuclei_regions stays valid)
-    DevBuf<int32_t> d_fd_lab, d_fd_rid, d_fd_par, d_fd_blk, d_fd_misc, d_fd_val, d_fd_off, d_fd_cur, d_fd_proots;
-    DevBuf<uint8_t> d_fd_lsq;
+    // ecseg_fish_distances and ecseg_fish_spots: the label map, the image and the dense cell index of the call (buffers of their
+    // own: a region map left by ecseg_nuclei_regions stays valid)
+    DevBuf<int32_t> d_cell_lab, d_cell_rid, d_cell_blk, d_cell_misc;
+    DevBuf<uint8_t> d_cell_img;
+    // ecseg_fish_distances
+    DevBuf<int32_t> d_fd_par, d_fd_val, d_fd_off, d_fd_cur, d_fd_proots;
     DevBuf<int2> d_fd_flist, d_fd_clist;
     DevBuf<unsigned> d_fd_acc;
     DevBuf<int64_t> d_fd_rec;
     DevBuf<unsigned long long> d_fd_pbest;
-    // ecseg_fish_spots: buffers of its own as well
-    DevBuf<int32_t> d_fs_lab, d_fs_rid, d_fs_blk, d_fs_misc, d_fs_mx, d_fs_par, d_fs_sz, d_fs_val;
-    DevBuf<uint8_t> d_fs_img, d_fs_thr, d_fs_bnd;
+    // ecseg_fish_spots
+    DevBuf<int32_t> d_fs_mx, d_fs_par, d_fs_sz, d_fs_val;
+    DevBuf<uint8_t> d_fs_thr, d_fs_bnd;
     DevBuf<double> d_fs_w;
     DevBuf<unsigned long long> d_fs_acc;
     DevBuf<unsigned> d_fs_cnt;

@@ -268,6 +268,34 @@ int ecseg_nucleus_crops(ecseg_ctx* h, const int32_t* crops, int n_crops, const i
     return ECSEG_OK;
 }
 
+// The opening phase of ecseg_fish_distances and ecseg_fish_spots: the label map and the image on the device, the dense cell index
+// (stage_ms[ECSEG_T_COUNT] = its device time) and the number of cells.  `who` prefixes the refusal of a label above H * W.
+static int open_dense_cells(ecseg_ctx* h, const char* who, const int32_t* labels, int H, int W, const uint8_t* img, int C, int32_t* n_cells) {
+    const size_t px = (size_t)H * W;
+    int rc;
+    if ((rc = h->d_cell_lab.ensure(h, px))) return rc;
+    if ((rc = h->d_cell_img.ensure(h, px * C))) return rc;
+    if ((rc = h->d_cell_rid.ensure(h, px))) return rc;
+    if ((rc = h->d_cell_blk.ensure(h, (px + 1023) / 1024))) return rc;
+    if ((rc = h->d_cell_misc.ensure(h, 4))) return rc;
+    hipStream_t s = h->stream;
+    for (float& v : h->stage_ms) v = 0.f;
+    HIP_TRY(h, hipMemcpyAsync(h->d_cell_lab, labels, px * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(h->d_cell_img, img, px * C, hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipEventRecord(h->ev[0], s));
+    HIP_TRY(h, run_dense_cells(h->d_cell_lab, H, W, CellIndexBufs{h->d_cell_rid, h->d_cell_blk, h->d_cell_misc}, s));
+    HIP_TRY(h, hipEventRecord(h->ev[1], s));
+    int32_t misc[4];
+    HIP_TRY(h, hipMemcpyAsync(misc, h->d_cell_misc, sizeof(misc), hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    h->stage_ms[ECSEG_T_COUNT] = stage_elapsed(h->ev[0], h->ev[1]);
+    if (misc[3])
+        return fail(h, ECSEG_E_INVALID, std::string(who) + ": the label map holds a label larger than H * W = " + std::to_string(px) +
+                                            " (renumber the labels by rank first)");
+    *n_cells = misc[0];
+    return ECSEG_OK;
+}
+
 // ---- fish_distance_calculation (src/fish_distance_calculation.py:16-46) ---------------------------------------------------
 int ecseg_fish_distances(ecseg_ctx* h, const int32_t* labels, int H, int W, const uint8_t* lsq, int C, int fish_channel,
                          int centromere_channel, int capacity, int64_t* records, int32_t* n_cells) {
@@ -284,28 +312,8 @@ int ecseg_fish_distances(ecseg_ctx* h, const int32_t* labels, int H, int W, cons
     HIP_TRY(h, hipSetDevice(h->device));
     const size_t px = (size_t)H * W;
     int rc;
-    if ((rc = h->d_fd_lab.ensure(h, px))) return rc;
-    if ((rc = h->d_fd_lsq.ensure(h, px * C))) return rc;
-    if ((rc = h->d_fd_rid.ensure(h, px))) return rc;
-    if ((rc = h->d_fd_blk.ensure(h, (px + 1023) / 1024))) return rc;
-    if ((rc = h->d_fd_misc.ensure(h, 4))) return rc;
-    hipStream_t s = h->stream;
-    for (float& v : h->stage_ms) v = 0.f;
-    HIP_TRY(h, hipMemcpyAsync(h->d_fd_lab, labels, px * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    HIP_TRY(h, hipMemcpyAsync(h->d_fd_lsq, lsq, px * C, hipMemcpyHostToDevice, s));
-    FishDistBufs b{h->d_fd_rid, nullptr, h->d_fd_blk, h->d_fd_misc, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    HIP_TRY(h, hipEventRecord(h->ev[0], s));
-    HIP_TRY(h, run_fishdist_cells(h->d_fd_lab, H, W, b, s));
-    HIP_TRY(h, hipEventRecord(h->ev[1], s));
-    int32_t misc[4];
-    HIP_TRY(h, hipMemcpyAsync(misc, h->d_fd_misc, sizeof(misc), hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipStreamSynchronize(s));
-    h->stage_ms[ECSEG_T_COUNT] = stage_elapsed(h->ev[0], h->ev[1]);
-    if (misc[3])
-        return fail(h, ECSEG_E_INVALID, "fish_distances: the label map holds a label larger than H * W = " + std::to_string(px) +
-                                            " (renumber the labels by rank first)");
-    const int n = misc[0];
-    *n_cells = n;
+    if ((rc = open_dense_cells(h, "fish_distances", labels, H, W, lsq, C, n_cells))) return rc;
+    const int n = *n_cells;
     if (n == 0 || n > capacity) return ECSEG_OK;             // the cell count alone: the caller comes back with a larger buffer
     // the rest is sized by the number of cells, which is known only now
     const size_t nn = (size_t)n;
@@ -320,10 +328,11 @@ int ecseg_fish_distances(ecseg_ctx* h, const int32_t* labels, int H, int W, cons
     const size_t parts = nn * (size_t)fishdist_slices(n);
     if ((rc = h->d_fd_pbest.ensure(h, parts))) return rc;
     if ((rc = h->d_fd_proots.ensure(h, parts))) return rc;
-    b = FishDistBufs{h->d_fd_rid, h->d_fd_par, h->d_fd_blk, h->d_fd_misc, h->d_fd_flist, h->d_fd_clist, h->d_fd_acc, h->d_fd_val,
-                     h->d_fd_off, h->d_fd_cur, h->d_fd_rec, h->d_fd_pbest, h->d_fd_proots};
+    hipStream_t s = h->stream;
+    const FishDistBufs b{h->d_cell_rid, h->d_fd_par, h->d_cell_blk, h->d_cell_misc, h->d_fd_flist, h->d_fd_clist, h->d_fd_acc, h->d_fd_val,
+                         h->d_fd_off, h->d_fd_cur, h->d_fd_rec, h->d_fd_pbest, h->d_fd_proots};
     HIP_TRY(h, hipEventRecord(h->ev[2], s));
-    HIP_TRY(h, run_fishdist_records(h->d_fd_lab, h->d_fd_lsq, H, W, C, fish_channel, centromere_channel, n, b, s));
+    HIP_TRY(h, run_fishdist_records(h->d_cell_lab, h->d_cell_img, H, W, C, fish_channel, centromere_channel, n, b, s));
     HIP_TRY(h, hipEventRecord(h->ev[3], s));
     HIP_TRY(h, hipMemcpyAsync(records, h->d_fd_rec, nn * 8 * sizeof(int64_t), hipMemcpyDeviceToHost, s));
     HIP_TRY(h, hipStreamSynchronize(s));
@@ -360,28 +369,8 @@ int ecseg_fish_spots(ecseg_ctx* h, const int32_t* labels, int H, int W, const ui
     HIP_TRY(h, hipSetDevice(h->device));
     const size_t px = (size_t)H * W, np = (size_t)n_probe;
     int rc;
-    if ((rc = h->d_fs_lab.ensure(h, px))) return rc;
-    if ((rc = h->d_fs_img.ensure(h, px * C))) return rc;
-    if ((rc = h->d_fs_rid.ensure(h, px))) return rc;
-    if ((rc = h->d_fs_blk.ensure(h, (px + 1023) / 1024))) return rc;
-    if ((rc = h->d_fs_misc.ensure(h, 4))) return rc;
-    hipStream_t s = h->stream;
-    for (float& v : h->stage_ms) v = 0.f;
-    HIP_TRY(h, hipMemcpyAsync(h->d_fs_lab, labels, px * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    HIP_TRY(h, hipMemcpyAsync(h->d_fs_img, img, px * C, hipMemcpyHostToDevice, s));
-    const FishDistBufs cb{h->d_fs_rid, nullptr, h->d_fs_blk, h->d_fs_misc, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    HIP_TRY(h, hipEventRecord(h->ev[0], s));
-    HIP_TRY(h, run_fishdist_cells(h->d_fs_lab, H, W, cb, s));
-    HIP_TRY(h, hipEventRecord(h->ev[1], s));
-    int32_t misc[4];
-    HIP_TRY(h, hipMemcpyAsync(misc, h->d_fs_misc, sizeof(misc), hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipStreamSynchronize(s));
-    h->stage_ms[ECSEG_T_COUNT] = stage_elapsed(h->ev[0], h->ev[1]);
-    if (misc[3])
-        return fail(h, ECSEG_E_INVALID, "fish_spots: the label map holds a label larger than H * W = " + std::to_string(px) +
-                                            " (renumber the labels by rank first)");
-    const int n = misc[0];
-    *n_cells = n;
+    if ((rc = open_dense_cells(h, "fish_spots", labels, H, W, img, C, n_cells))) return rc;
+    const int n = *n_cells;
     if (n > capacity) return ECSEG_OK;                       // the cell count alone: the caller comes back with a larger buffer
     if (n == 0) {                                            // no cell: nothing is thresholded and no rank differs from 0
         std::fill(thresholded, thresholded + px * np, (uint8_t)0);
@@ -399,11 +388,12 @@ int ecseg_fish_spots(ecseg_ctx* h, const int32_t* labels, int H, int W, const ui
     if ((rc = h->d_fs_cnt.ensure(h, nn * 8))) return rc;
     if ((rc = h->d_fs_val.ensure(h, nn))) return rc;
     if ((rc = h->d_fs_rec.ensure(h, nn * ECSEG_FISH_SPOT_INT64))) return rc;
+    hipStream_t s = h->stream;
     HIP_TRY(h, hipMemcpyAsync(h->d_fs_w, weights, (size_t)K * K * sizeof(double), hipMemcpyHostToDevice, s));
-    const FishSpotBufs b{h->d_fs_rid, h->d_fs_mx, h->d_fs_thr, h->d_fs_bnd, h->d_fs_par, h->d_fs_sz, h->d_fs_acc, h->d_fs_cnt, h->d_fs_val,
+    const FishSpotBufs b{h->d_cell_rid, h->d_fs_mx, h->d_fs_thr, h->d_fs_bnd, h->d_fs_par, h->d_fs_sz, h->d_fs_acc, h->d_fs_cnt, h->d_fs_val,
                          h->d_fs_rec};
     HIP_TRY(h, hipEventRecord(h->ev[2], s));
-    HIP_TRY(h, run_fishspot(h->d_fs_lab, h->d_fs_img, H, W, C, n_probe, ch, h->d_fs_w, K, normal_threshold, ithr, min_cc_size,
+    HIP_TRY(h, run_fishspot(h->d_cell_lab, h->d_cell_img, H, W, C, n_probe, ch, h->d_fs_w, K, normal_threshold, ithr, min_cc_size,
                             line_thickness, n, b, s));
     HIP_TRY(h, hipEventRecord(h->ev[3], s));
     HIP_TRY(h, hipMemcpyAsync(thresholded, h->d_fs_thr, px * np, hipMemcpyDeviceToHost, s));

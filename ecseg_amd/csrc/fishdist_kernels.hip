@@ -4,15 +4,15 @@
 // the atomics.
 //
 // Cells (regionprops(segmentation): every label > 0 that occurs, in ascending label order; a label's pixels need not touch)
-//   * fd_mark_kernel sets flag[label - 1]; an exclusive scan over the flags (chunk sums, one scan of the chunk sums, per-chunk
-//     prefix) turns them into the dense ascending cell index, misc[0] = number of cells;
+//   * run_dense_cells (also the opening of fishspot_kernels.hip): fd_mark_kernel sets flag[label - 1] and cell_util.h's exclusive
+//     scan over the flags, in place, turns them into the dense ascending cell index, misc[0] = number of cells;
 //   * fd_cell_stats_kernel relabels the map in place to cell + 1 and accumulates area, FISH pixels, centromere pixels and the
-//     gate bits.  A wave handles one 64-pixel row segment at a time: the lanes of one cell are counted with ballots, the
-//     segment's leader lane adds into a 64-slot LDS table keyed by cell, and the table is flushed with one global atomic per
+//     gate bits, on cell_util.h's statistics tile: the lanes of one cell (wave_key_groups) are counted with ballots, the leader
+//     lane adds into the LDS table keyed by cell (lds_key_claim), and the table is flushed with one global atomic per
 //     (cell, field, workgroup).  It also presets the union-find parents: par[p] = p on FISH pixels of a cell, -1 elsewhere.
 // Spots (skimage.measure.label(fish_probe) of the cut-out, :30-32: 8-connected, only through pixels of this cell)
-//   * fd_fill_unite_kernel unites every FISH pixel with its W / NW / N / NE neighbour when that neighbour is a FISH pixel of the
-//     SAME cell, and appends the pixel's (row, column) to its cell's FISH and / or centromere list (offsets = exclusive scans of
+//   * fd_fill_unite_kernel unites every FISH pixel with the FISH pixels of the SAME cell behind it (uf_unite_back, 8-connected),
+//     and appends the pixel's (row, column) to its cell's FISH and / or centromere list (offsets = exclusive scans of
 //     the per-cell counts; the order inside a list is arbitrary and irrelevant to a minimum and a count).
 // Distance (:34-45, a minimum over all FISH pixels of the minimum over all centromere pixels)
 //   * fd_distance_kernel, S workgroups per cell, each with a 256-strided slice of the cell's FISH list: counts the slice's roots
@@ -25,15 +25,10 @@
 //   1.7 x 10^11 pairs in 57 ms, i.e. 1.2 x 10^10 pairs per second and workgroup); the case left serial is one huge dense cell
 //   among more than 4096 others, whose search runs on a single workgroup at that rate.  Real spots are dozens of pixels.
 #include "common.h"
-#include "device_util.h"
+#include "cell_util.h"
 
 namespace ecseg {
 
-typedef unsigned long long u64;
-
-static constexpr int FD_CHUNK = 1024;            // elements per scan chunk (256 threads x 4)
-static constexpr int FD_SLOTS = 64;              // LDS table entries of fd_cell_stats_kernel
-static constexpr int FD_ROWS_PER_WAVE = 8;       // stats kernel: a block covers 64 columns x 32 rows
 static constexpr int FD_TILE = 1024;             // centromere pixels per LDS tile of fd_distance_kernel
 
 // flag[label - 1] = 1 for every label that occurs; misc[3] = 1 when a label exceeds px (the caller refuses the map)
@@ -47,99 +42,29 @@ __global__ __launch_bounds__(256) void fd_mark_kernel(const int32_t* __restrict_
     flag[l - 1] = 1;
 }
 
-// blk[chunk] = sum of v[i * stride] over the chunk's elements
-__global__ __launch_bounds__(256) void fd_chunk_sum_kernel(const int32_t* __restrict__ v, int stride, int n, int32_t* __restrict__ blk) {
-    __shared__ int wsum[4];
-    const int t = threadIdx.x;
-    const size_t i0 = (size_t)blockIdx.x * FD_CHUNK + (size_t)t * 4;
-    int s = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) s += i0 + k < (size_t)n ? v[(i0 + k) * stride] : 0;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) s += __shfl_xor(s, d);
-    if ((t & 63) == 0) wsum[t >> 6] = s;
-    __syncthreads();
-    if (t == 0) blk[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-}
-
-// exclusive prefix over the chunk sums (one workgroup); *total = their sum
-__global__ __launch_bounds__(256) void fd_scan_kernel(int32_t* __restrict__ blk, int nb, int32_t* __restrict__ total) {
-    __shared__ int s[256];
-    __shared__ int carry;
-    const int t = threadIdx.x;
-    if (t == 0) carry = 0;
-    __syncthreads();
-    for (int b0 = 0; b0 < nb; b0 += 256) {
-        const int i = b0 + t;
-        const int v = i < nb ? blk[i] : 0;
-        s[t] = v;
-        __syncthreads();
-        for (int d = 1; d < 256; d <<= 1) {
-            const int a = t >= d ? s[t - d] : 0;
-            __syncthreads();
-            s[t] += a;
-            __syncthreads();
-        }
-        if (i < nb) blk[i] = carry + s[t] - v;
-        __syncthreads();
-        if (t == 255) carry += s[255];
-        __syncthreads();
-    }
-    if (t == 0) *total = carry;
-}
-
-// out[i] = sum of v[j * stride] over j < i (out may be v itself when stride == 1: a thread reads its four elements first)
-__global__ __launch_bounds__(256) void fd_chunk_excl_kernel(const int32_t* v, int stride, int n, const int32_t* __restrict__ blk,
-                                                            int32_t* out) {
-    __shared__ int wsum[4];
-    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-    const size_t i0 = (size_t)blockIdx.x * FD_CHUNK + (size_t)t * 4;
-    int a[4], s = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) { a[k] = i0 + k < (size_t)n ? v[(i0 + k) * stride] : 0; s += a[k]; }
-    int incl = s;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int o = __shfl_up(incl, d);
-        if (lane >= d) incl += o;
-    }
-    if (lane == 63) wsum[wv] = incl;
-    __syncthreads();
-    int run = blk[blockIdx.x] + incl - s;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) run += w < wv ? wsum[w] : 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        if (i0 + k < (size_t)n) out[i0 + k] = run;
-        run += a[k];
-    }
-}
-
 // acc: per cell (area, FISH pixels, centromere pixels, bits) uint32; bits: 1 = channel 0 non-zero somewhere in the cell,
 // 2 = channel 1, 4 = some pixel is FISH and centromere at once.  val[cell] = the cell's label value.
 __global__ __launch_bounds__(256) void fd_cell_stats_kernel(int32_t* __restrict__ L, const int32_t* __restrict__ rid,
                                                             const uint8_t* __restrict__ lsq, int H, int W, int C, int fi, int ci,
                                                             unsigned* __restrict__ acc, int32_t* __restrict__ val,
                                                             int32_t* __restrict__ par) {
-    __shared__ int s_key[FD_SLOTS], s_val[FD_SLOTS];
-    __shared__ unsigned s_acc[4][FD_SLOTS];
-    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-    if (t < FD_SLOTS) {
+    __shared__ int s_key[CELL_SLOTS], s_val[CELL_SLOTS];
+    __shared__ unsigned s_acc[4][CELL_SLOTS];
+    const int t = threadIdx.x, lane = t & 63;
+    if (t < CELL_SLOTS) {
         s_key[t] = -1;
 #pragma unroll
         for (int j = 0; j < 4; ++j) s_acc[j][t] = 0;
     }
     __syncthreads();
-    const unsigned tiles_x = ((unsigned)W + 63u) / 64u;
-    const unsigned x = (blockIdx.x % tiles_x) * 64u + (unsigned)lane;   // < W + 63 <= 2^31 + 62: compared as unsigned
-    const int ybeg = (int)(blockIdx.x / tiles_x) * (4 * FD_ROWS_PER_WAVE) + wv * FD_ROWS_PER_WAVE;
-    for (int r = 0; r < FD_ROWS_PER_WAVE; ++r) {
-        const int y = ybeg + r;
+    const StatTile tile = stat_tile(W);
+    for (int r = 0; r < CELL_ROWS_PER_WAVE; ++r) {
+        const int y = tile.ybeg + r;
         if (y >= H) break;                                   // wave-uniform
         int reg = -1, l = 0;
         bool f = false, c = false, g0 = false, g1 = false;
-        if (x < (unsigned)W) {
-            const size_t p = (size_t)y * W + x;
+        if (tile.x < (unsigned)W) {
+            const size_t p = (size_t)y * W + tile.x;
             l = L[p];
             if (l > 0) {
                 reg = rid[l - 1];
@@ -149,37 +74,25 @@ __global__ __launch_bounds__(256) void fd_cell_stats_kernel(int32_t* __restrict_
             }
             par[p] = f ? (int)p : -1;
         }
-        u64 active = __ballot(reg >= 0);
-        while (active) {
-            const int leader = __ffsll((long long)active) - 1;
-            const int key = __shfl(reg, leader);
-            const bool mine = reg == key;
-            const u64 m = __ballot(mine);
+        wave_key_groups(reg, [&](int key, bool mine, u64 m, int leader) {
             const unsigned n = (unsigned)__popcll(m);
             const unsigned nf = (unsigned)__popcll(__ballot(mine && f)), nc = (unsigned)__popcll(__ballot(mine && c));
             const unsigned bits = (__ballot(mine && g0) ? 1u : 0u) | (__ballot(mine && g1) ? 2u : 0u) | (__ballot(mine && f && c) ? 4u : 0u);
-            if (lane == leader) {
-                int slot = key & (FD_SLOTS - 1), found = -1;
-                for (int probe = 0; probe < FD_SLOTS; ++probe) {
-                    const int old = atomicCAS(&s_key[slot], -1, key);
-                    if (old == -1 || old == key) { found = slot; break; }
-                    slot = (slot + 1) & (FD_SLOTS - 1);
-                }
-                if (found >= 0) {
-                    s_val[found] = l;                        // every writer of a slot stores the same label
-                    atomicAdd(&s_acc[0][found], n); atomicAdd(&s_acc[1][found], nf); atomicAdd(&s_acc[2][found], nc);
-                    atomicOr(&s_acc[3][found], bits);
-                } else {                                     // more than 64 cells in one 64 x 32 tile: straight to the cell
-                    unsigned* a = acc + (size_t)key * 4;
-                    atomicAdd(a + 0, n); atomicAdd(a + 1, nf); atomicAdd(a + 2, nc); atomicOr(a + 3, bits);
-                    val[key] = l;
-                }
+            if (lane != leader) return;
+            const int found = lds_key_claim(s_key, key);
+            if (found >= 0) {
+                s_val[found] = l;                            // every writer of a slot stores the same label
+                atomicAdd(&s_acc[0][found], n); atomicAdd(&s_acc[1][found], nf); atomicAdd(&s_acc[2][found], nc);
+                atomicOr(&s_acc[3][found], bits);
+            } else {                                         // more than 64 cells in one 64 x 32 tile: straight to the cell
+                unsigned* a = acc + (size_t)key * 4;
+                atomicAdd(a + 0, n); atomicAdd(a + 1, nf); atomicAdd(a + 2, nc); atomicOr(a + 3, bits);
+                val[key] = l;
             }
-            active &= ~m;
-        }
+        });
     }
     __syncthreads();
-    if (t < FD_SLOTS && s_key[t] >= 0) {
+    if (t < CELL_SLOTS && s_key[t] >= 0) {
         const int k = s_key[t];
         unsigned* a = acc + (size_t)k * 4;
         atomicAdd(a + 0, s_acc[0][t]); atomicAdd(a + 1, s_acc[1][t]); atomicAdd(a + 2, s_acc[2][t]); atomicOr(a + 3, s_acc[3][t]);
@@ -203,14 +116,8 @@ __global__ __launch_bounds__(256) void fd_fill_unite_kernel(const int32_t* __res
     if (c) clist[off[n + cell - 1] + atomicAdd(cur + n + cell - 1, 1)] = make_int2(y, x);
     if (!f) return;
     flist[off[cell - 1] + atomicAdd(cur + cell - 1, 1)] = make_int2(y, x);
-    // a neighbour is a FISH pixel of this cell exactly when its label matches and its preset parent is not -1; parents only
-    // ever move to smaller pixel indices, so "was preset to a pixel" stays readable as >= 0 while other threads unite
-    if (x > 0 && L[p - 1] == cell && uf_load(par, p - 1) >= 0) uf_unite(par, p, p - 1);
-    if (y > 0) {
-        if (x > 0 && L[p - W - 1] == cell && uf_load(par, p - W - 1) >= 0) uf_unite(par, p, p - W - 1);
-        if (L[p - W] == cell && uf_load(par, p - W) >= 0) uf_unite(par, p, p - W);
-        if (x + 1 < W && L[p - W + 1] == cell && uf_load(par, p - W + 1) >= 0) uf_unite(par, p, p - W + 1);
-    }
+    // a neighbour is a FISH pixel of this cell exactly when its label matches and its preset parent is not -1
+    uf_unite_back(par, p, y, x, W, 1, [&](int nb) { return L[nb] == cell; });
 }
 
 template <typename T>
@@ -306,20 +213,13 @@ __global__ __launch_bounds__(256) void fd_records_kernel(const unsigned* __restr
 // n * S <= 4096 + n workgroups in all
 int fishdist_slices(int n) { return n <= 0 ? 1 : (4096 / n < 1 ? 1 : (4096 / n > 256 ? 256 : 4096 / n)); }
 
-static void fd_exclusive_scan(const int32_t* v, int stride, int n, int32_t* blk, int32_t* out, int32_t* total, hipStream_t s) {
-    const int nb = (int)(((unsigned)n + FD_CHUNK - 1) / FD_CHUNK);
-    hipLaunchKernelGGL(fd_chunk_sum_kernel, dim3(nb), dim3(256), 0, s, v, stride, n, blk);
-    hipLaunchKernelGGL(fd_scan_kernel, dim3(1), dim3(256), 0, s, blk, nb, total);
-    hipLaunchKernelGGL(fd_chunk_excl_kernel, dim3(nb), dim3(256), 0, s, v, stride, n, blk, out);
-}
-
-hipError_t run_fishdist_cells(const int32_t* labels, int H, int W, const FishDistBufs& b, hipStream_t s) {
+hipError_t run_dense_cells(const int32_t* labels, int H, int W, const CellIndexBufs& b, hipStream_t s) {
     const int px = H * W;
     hipError_t e;
     if ((e = hipMemsetAsync(b.misc, 0, 4 * sizeof(int32_t), s)) != hipSuccess) return e;
     if ((e = hipMemsetAsync(b.rid, 0, (size_t)px * sizeof(int32_t), s)) != hipSuccess) return e;
     hipLaunchKernelGGL(fd_mark_kernel, dim3(((unsigned)px + 255u) / 256u), dim3(256), 0, s, labels, px, b.rid, b.misc);
-    fd_exclusive_scan(b.rid, 1, px, b.blk, b.rid, b.misc, s);
+    exclusive_scan(LoadStrided{b.rid, 1}, px, b.blk, b.rid, b.misc, s);
     return hipGetLastError();
 }
 
@@ -330,10 +230,9 @@ hipError_t run_fishdist_records(int32_t* labels, const uint8_t* lsq, int H, int 
     hipError_t e;
     if ((e = hipMemsetAsync(b.acc, 0, (size_t)n * 4 * sizeof(unsigned), s)) != hipSuccess) return e;
     if ((e = hipMemsetAsync(b.cur, 0, (size_t)n * 2 * sizeof(int32_t), s)) != hipSuccess) return e;
-    const unsigned tiles = (((unsigned)W + 63u) / 64u) * (((unsigned)H + 4 * FD_ROWS_PER_WAVE - 1) / (4 * FD_ROWS_PER_WAVE));
-    hipLaunchKernelGGL(fd_cell_stats_kernel, dim3(tiles), dim3(256), 0, s, labels, b.rid, lsq, H, W, C, fi, ci, b.acc, b.val, b.par);
-    fd_exclusive_scan(reinterpret_cast<const int32_t*>(b.acc) + 1, 4, n, b.blk, b.off, b.misc + 1, s);
-    fd_exclusive_scan(reinterpret_cast<const int32_t*>(b.acc) + 2, 4, n, b.blk, b.off + n, b.misc + 2, s);
+    hipLaunchKernelGGL(fd_cell_stats_kernel, dim3(stat_tiles(H, W)), dim3(256), 0, s, labels, b.rid, lsq, H, W, C, fi, ci, b.acc, b.val, b.par);
+    exclusive_scan(LoadStrided{reinterpret_cast<const int32_t*>(b.acc) + 1, 4}, n, b.blk, b.off, b.misc + 1, s);
+    exclusive_scan(LoadStrided{reinterpret_cast<const int32_t*>(b.acc) + 2, 4}, n, b.blk, b.off + n, b.misc + 2, s);
     hipLaunchKernelGGL(fd_fill_unite_kernel, dim3(((unsigned)px + 255u) / 256u), dim3(256), 0, s, labels, lsq, H, W, C, fi, ci, n, b.off, b.cur,
                        b.flist, b.clist, b.par);
     const int S = fishdist_slices(n);

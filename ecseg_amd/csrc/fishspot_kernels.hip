@@ -4,11 +4,11 @@
 // (coefficient > normal_threshold) is evaluated in a fixed tap order, so two calls give identical bytes.
 //
 // Cells (regionprops(labeled_segmented_cells): every label > 0 that occurs, ascending)
-//   * run_fishdist_cells (fishdist_kernels.hip: mark + exclusive scan) gives rid[label - 1] = dense cell index, misc[0] = cells;
+//   * run_dense_cells (fishdist_kernels.hip: mark + exclusive scan) gives rid[label - 1] = dense cell index, misc[0] = cells;
 //   * fs_cell_stats_kernel relabels the map in place to the dense rank cell + 1 and accumulates per cell the area, the sums of
-//     rows and columns and, per probe, sum / count / maximum of the non-zero raw pixels (:252,261-263).  A wave handles one
-//     64-pixel row segment: the lanes of one cell are reduced with shuffles and the segment's leader lane adds into the cell's
-//     64-bit accumulators, one atomic per (cell, field, segment).
+//     rows and columns and, per probe, sum / count / maximum of the non-zero raw pixels (:252,261-263), on cell_util.h's
+//     statistics tile: the lanes of one cell (wave_key_groups) are reduced with shuffles and the leader lane adds into the
+//     cell's 64-bit accumulators, one atomic per (cell, field, row segment).
 // Peak filter (get_thresholded, :73-88)
 //   * fs_channel_max_kernel: the maximum of every probe channel over the whole image (the "max brightness" centres of :82);
 //   * fs_threshold_kernel: a 64 x 16 pixel tile per workgroup; per probe the channel's zero-padded halo tile (uint8) and the K x K
@@ -17,8 +17,9 @@
 //     convolution, so NaN weights give no normal centre).  thresholded = centre ? 255 : 0; the union-find parent of the probe
 //     is preset to the pixel itself on thresholded pixels and to -1 elsewhere.
 // Spots (count_blobs, :134-142: scipy.ndimage.label, 4-connected, of thresholded * cell)
-//   * fs_unite_kernel unites a thresholded pixel with its W / N neighbour when that is a thresholded pixel of the SAME cell;
-//   * fs_size_kernel flattens (parent = root) and counts the pixels of every root; fs_finalize_kernel clears the components
+//   * fs_unite_kernel unites a thresholded pixel with the thresholded pixels of the SAME cell behind it (uf_unite_back,
+//     4-connected);
+//   * uf_size_kernel (cell_util.h) flattens (parent = root) and counts the pixels of every root; fs_finalize_kernel clears the components
 //     below min_cc_size from `thresholded` (:140 clears through a view, so the cleaned mask is what the _lsq file shows) and
 //     counts pixels and roots of the rest per cell;
 //   * the pair of the first two probes (:270-275): fs_pair_init_kernel presets parents on the AND of the two CLEANED masks, then
@@ -26,16 +27,13 @@
 // Boundaries (get_boundaries, :91-107) on the dense ranks: fs_boundary_kernel, 64-bit sums of the 2 t taps of either axis.
 // fs_records_kernel writes the ECSEG_FISH_SPOT_INT64 fields of every cell.
 #include "common.h"
-#include "device_util.h"
+#include "cell_util.h"
 
 namespace ecseg {
-
-typedef unsigned long long u64;
 
 static constexpr int FS_TW = 64, FS_TH = 16;                 // output tile of fs_threshold_kernel (256 threads x 4 rows)
 static constexpr int FS_KMAX = ECSEG_FISH_SPOT_MAX_KERNEL;
 static constexpr int FS_HALO_W = FS_TW + FS_KMAX - 1, FS_HALO_H = FS_TH + FS_KMAX - 1;
-static constexpr int FS_ROWS_PER_WAVE = 8;                   // stats kernel: a block covers 64 columns x 32 rows
 static constexpr int FS_SLOTS = 4;                           // union-find slots: probes 0..2, the pair
 
 struct FsChannels { int c[3]; };
@@ -64,18 +62,15 @@ __global__ __launch_bounds__(256) void fs_channel_max_kernel(const uint8_t* __re
 __global__ __launch_bounds__(256) void fs_cell_stats_kernel(int32_t* __restrict__ L, const int32_t* __restrict__ rid,
                                                             const uint8_t* __restrict__ img, int H, int W, int C, int np, FsChannels ch,
                                                             u64* __restrict__ acc, int32_t* __restrict__ val) {
-    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-    const unsigned tiles_x = ((unsigned)W + 63u) / 64u;
-    const unsigned xb = (blockIdx.x % tiles_x) * 64u;
-    const unsigned x = xb + (unsigned)lane;                 // < W + 63: compared as unsigned
-    const int ybeg = (int)(blockIdx.x / tiles_x) * (4 * FS_ROWS_PER_WAVE) + wv * FS_ROWS_PER_WAVE;
-    for (int r = 0; r < FS_ROWS_PER_WAVE; ++r) {
-        const int y = ybeg + r;
+    const int lane = threadIdx.x & 63;
+    const StatTile tile = stat_tile(W);
+    for (int r = 0; r < CELL_ROWS_PER_WAVE; ++r) {
+        const int y = tile.ybeg + r;
         if (y >= H) break;                                   // wave-uniform
         int reg = -1, l = 0;
         int raw[3] = {0, 0, 0};
-        if (x < (unsigned)W) {
-            const size_t p = (size_t)y * W + x;
+        if (tile.x < (unsigned)W) {
+            const size_t p = (size_t)y * W + tile.x;
             l = L[p];
             if (l > 0) {
                 reg = rid[l - 1];
@@ -88,12 +83,7 @@ __global__ __launch_bounds__(256) void fs_cell_stats_kernel(int32_t* __restrict_
                 L[p] = 0;                                    // background: the later kernels test > 0 / compare ranks
             }
         }
-        u64 active = __ballot(reg >= 0);
-        while (active) {
-            const int leader = __ffsll((long long)active) - 1;
-            const int key = __shfl(reg, leader);
-            const bool mine = reg == key;
-            const u64 m = __ballot(mine);
+        wave_key_groups(reg, [&](int key, bool mine, u64 m, int leader) {
             const unsigned n = (unsigned)__popcll(m);
             int sl = mine ? lane : 0;                        // sum of the lane numbers: columns = n * xb + that
             int s[3], mxv[3];
@@ -113,22 +103,20 @@ __global__ __launch_bounds__(256) void fs_cell_stats_kernel(int32_t* __restrict_
                     mxv[j] = max(mxv[j], __shfl_xor(mxv[j], d));
                 }
             }
-            if (lane == leader) {
-                u64* a = acc + (size_t)key * 12;
-                atomicAdd(a + 0, (u64)n);
-                atomicAdd(a + 1, (u64)n * (u64)y);
-                atomicAdd(a + 2, (u64)n * (u64)xb + (u64)sl);
+            if (lane != leader) return;
+            u64* a = acc + (size_t)key * 12;
+            atomicAdd(a + 0, (u64)n);
+            atomicAdd(a + 1, (u64)n * (u64)y);
+            atomicAdd(a + 2, (u64)n * (u64)tile.xb + (u64)sl);
 #pragma unroll
-                for (int j = 0; j < 3; ++j)
-                    if (j < np && cnt[j]) {
-                        atomicAdd(a + 3 + 3 * j, (u64)s[j]);
-                        atomicAdd(a + 4 + 3 * j, (u64)cnt[j]);
-                        atomicMax(a + 5 + 3 * j, (u64)mxv[j]);
-                    }
-                val[key] = l;                                // every writer of a cell stores the same label
-            }
-            active &= ~m;
-        }
+            for (int j = 0; j < 3; ++j)
+                if (j < np && cnt[j]) {
+                    atomicAdd(a + 3 + 3 * j, (u64)s[j]);
+                    atomicAdd(a + 4 + 3 * j, (u64)cnt[j]);
+                    atomicMax(a + 5 + 3 * j, (u64)mxv[j]);
+                }
+            val[key] = l;                                    // every writer of a cell stores the same label
+        });
     }
 }
 
@@ -190,21 +178,7 @@ __global__ __launch_bounds__(256) void fs_unite_kernel(const int32_t* __restrict
     if (uf_load(par, p) < 0) return;
     const int cell = L[p];
     const int y = p / W, x = p - y * W;
-    // parents only ever move to smaller pixel indices, so "was preset to a pixel" stays readable as >= 0 while others unite
-    if (x > 0 && L[p - 1] == cell && uf_load(par, p - 1) >= 0) uf_unite(par, p, p - 1);
-    if (y > 0 && L[p - W] == cell && uf_load(par, p - W) >= 0) uf_unite(par, p, p - W);
-}
-
-// parent = root for every mask pixel; sz[root] = pixels of the component
-__global__ __launch_bounds__(256) void fs_size_kernel(int px, int32_t* par_all, int32_t* __restrict__ sz_all) {
-    const unsigned pu = blockIdx.x * 256u + threadIdx.x;
-    if (pu >= (unsigned)px) return;
-    const int p = (int)pu;
-    int32_t* par = par_all + (size_t)blockIdx.y * (size_t)px;
-    if (uf_load(par, p) < 0) return;
-    const int root = uf_find(par, p);
-    __hip_atomic_store(par + p, root, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // a shortcut inside the same tree
-    atomicAdd(sz_all + (size_t)blockIdx.y * (size_t)px + root, 1);
+    uf_unite_back(par, p, y, x, W, 0, [&](int q) { return L[q] == cell; });
 }
 
 // slot = slot0 + blockIdx.y.  Components below min_cc: cleared from thr when thr != null (probes), else just not counted (the pair).
@@ -287,19 +261,19 @@ hipError_t run_fishspot(int32_t* labels, const uint8_t* img, int H, int W, int C
     if ((e = hipMemsetAsync(b.cnt, 0, (size_t)n * FS_SLOTS * 2 * sizeof(unsigned), s)) != hipSuccess) return e;
     if ((e = hipMemsetAsync(b.sz, 0, (size_t)px * FS_SLOTS * sizeof(int32_t), s)) != hipSuccess) return e;
     hipLaunchKernelGGL(fs_channel_max_kernel, dim3(gpx < 2048u ? gpx : 2048u), dim3(256), 0, s, img, px, C, np, fc, b.mx);
-    const unsigned stat_tiles = (((unsigned)W + 63u) / 64u) * (((unsigned)H + 4 * FS_ROWS_PER_WAVE - 1) / (4 * FS_ROWS_PER_WAVE));
-    hipLaunchKernelGGL(fs_cell_stats_kernel, dim3(stat_tiles), dim3(256), 0, s, labels, b.rid, img, H, W, C, np, fc, b.acc, b.val);
+    hipLaunchKernelGGL(fs_cell_stats_kernel, dim3(stat_tiles(H, W)), dim3(256), 0, s, labels, b.rid, img, H, W, C, np, fc, b.acc, b.val);
     const unsigned thr_tiles = (((unsigned)W + FS_TW - 1) / FS_TW) * (((unsigned)H + FS_TH - 1) / FS_TH);
     hipLaunchKernelGGL(fs_threshold_kernel, dim3(thr_tiles), dim3(256), 0, s, labels, img, H, W, C, np, fc, wts, K, normal_thr, ft, b.mx, b.thr,
                        b.par);
     hipLaunchKernelGGL(fs_unite_kernel, dim3(gpx, (unsigned)np), dim3(256), 0, s, labels, H, W, b.par);
-    hipLaunchKernelGGL(fs_size_kernel, dim3(gpx, (unsigned)np), dim3(256), 0, s, px, b.par, b.sz);
+    hipLaunchKernelGGL(uf_size_kernel, dim3(gpx, (unsigned)np), dim3(256), 0, s, px, b.par, b.sz, static_cast<int32_t*>(nullptr));
     hipLaunchKernelGGL(fs_finalize_kernel, dim3(gpx, (unsigned)np), dim3(256), 0, s, labels, px, np, 0, min_cc, b.par, b.sz, b.thr, b.cnt);
     if (np >= 2) {
         int32_t* pair_par = b.par + (size_t)(FS_SLOTS - 1) * px;
         hipLaunchKernelGGL(fs_pair_init_kernel, dim3(gpx), dim3(256), 0, s, b.thr, px, np, pair_par);
         hipLaunchKernelGGL(fs_unite_kernel, dim3(gpx, 1), dim3(256), 0, s, labels, H, W, pair_par);
-        hipLaunchKernelGGL(fs_size_kernel, dim3(gpx, 1), dim3(256), 0, s, px, pair_par, b.sz + (size_t)(FS_SLOTS - 1) * px);
+        hipLaunchKernelGGL(uf_size_kernel, dim3(gpx, 1), dim3(256), 0, s, px, pair_par, b.sz + (size_t)(FS_SLOTS - 1) * px,
+                           static_cast<int32_t*>(nullptr));
         hipLaunchKernelGGL(fs_finalize_kernel, dim3(gpx, 1), dim3(256), 0, s, labels, px, np, FS_SLOTS - 1, min_cc, b.par, b.sz,
                            static_cast<uint8_t*>(nullptr), b.cnt);
     }

@@ -3,12 +3,12 @@
 //
 // Regions (src/interseg.py:121-134: measure.label(seg, connectivity=None) + regionprops + the brightness gate)
 //   * the 8-connected labels come from run_ccl_labels (label = 1 + raster index of the component's first pixel, the
-//     pixel skimage numbers components by); the first pixels ("roots") are the pixels with label == index + 1, so a
-//     per-chunk root count, one scan and a per-chunk rank give every component its skimage region index;
+//     pixel skimage numbers components by); the first pixels ("roots") are the pixels with label == index + 1, so the
+//     exclusive scan of that flag (cell_util.h) read at a root is the component's skimage region index;
 //   * iseg_region_stats_kernel relabels the map in place to region + 1 and accumulates area, bbox, sum of rows, sum of
-//     columns and the sum of the reordered channel 0.  A wave handles one 64-pixel row segment at a time: lanes of one
-//     region are folded with one shuffle butterfly, the fold's leader lane adds into a 64-slot LDS table keyed by region,
-//     and the table is flushed with one global atomic per (region, field, workgroup).
+//     columns and the sum of the reordered channel 0, on cell_util.h's statistics tile: the lanes of one region
+//     (wave_key_groups) are folded with one shuffle butterfly, the fold's leader lane adds into the LDS table keyed by
+//     region (lds_key_claim), and the table is flushed with one global atomic per (region, field, workgroup).
 // Crops (src/interseg.py:131-133,150-152,193-194 and im2patches_overlap :27-46)
 //   * crop (region, y0, x0, h, w), h, w <= 256: the window of the image with every pixel outside THIS region zeroed,
 //     resized to 256 x 256 as skimage.transform.resize(order=1, mode='reflect', preserve_range=True).astype(uint8) does
@@ -20,73 +20,11 @@
 #include <climits>
 
 #include "common.h"
+#include "cell_util.h"
 
 namespace ecseg {
 
-typedef unsigned long long u64;
-
-static constexpr int ISEG_CHUNK = 1024;          // pixels per root-count chunk (256 threads x 4)
-static constexpr int ISEG_SLOTS = 64;            // LDS table entries of iseg_region_stats_kernel
-static constexpr int ISEG_ROWS_PER_WAVE = 8;     // stats kernel: a block covers 64 columns x 32 rows
 static constexpr int ISEG_CROP_ROWS = 16;        // crops kernel: output rows per block
-
-__global__ __launch_bounds__(256) void iseg_root_count_kernel(const int32_t* __restrict__ L, int px, int32_t* __restrict__ cnt) {
-    const int base = blockIdx.x * ISEG_CHUNK;
-    int c = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int p = base + k * 256 + (int)threadIdx.x;
-        c += __syncthreads_count(p < px && L[p] == p + 1);
-    }
-    if (threadIdx.x == 0) cnt[blockIdx.x] = c;
-}
-
-// exclusive prefix over the chunk counts (one workgroup); misc[0] = number of regions
-__global__ __launch_bounds__(256) void iseg_scan_kernel(int32_t* __restrict__ cnt, int nb, int32_t* __restrict__ misc) {
-    __shared__ int s[256];
-    __shared__ int carry;
-    const int t = threadIdx.x;
-    if (t == 0) carry = 0;
-    __syncthreads();
-    for (int b0 = 0; b0 < nb; b0 += 256) {
-        const int i = b0 + t;
-        const int v = i < nb ? cnt[i] : 0;
-        s[t] = v;
-        __syncthreads();
-        for (int d = 1; d < 256; d <<= 1) {
-            const int a = t >= d ? s[t - d] : 0;
-            __syncthreads();
-            s[t] += a;
-            __syncthreads();
-        }
-        if (i < nb) cnt[i] = carry + s[t] - v;
-        __syncthreads();
-        if (t == 255) carry += s[255];
-        __syncthreads();
-    }
-    if (t == 0) misc[0] = carry;
-}
-
-// rid[root pixel] = region index (raster order of the roots)
-__global__ __launch_bounds__(256) void iseg_root_id_kernel(const int32_t* __restrict__ L, int px, const int32_t* __restrict__ off,
-                                                           int32_t* __restrict__ rid) {
-    __shared__ int wsum[4];
-    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-    int base_id = off[blockIdx.x];
-    for (int k = 0; k < 4; ++k) {
-        const int p = (int)blockIdx.x * ISEG_CHUNK + k * 256 + t;
-        const bool root = p < px && L[p] == p + 1;
-        const u64 m = __ballot(root);
-        if (lane == 0) wsum[wv] = __popcll(m);
-        __syncthreads();
-        int before = 0, tot = 0;
-#pragma unroll
-        for (int w = 0; w < 4; ++w) { before += w < wv ? wsum[w] : 0; tot += wsum[w]; }
-        if (root) rid[p] = base_id + before + __popcll(m & ((1ull << lane) - 1ull));
-        base_id += tot;
-        __syncthreads();
-    }
-}
 
 // acc: per region (area, sum of rows, sum of columns, sum of channel 0) u64; bb: (min row, min col, -max row, -max col),
 // all atomicMin, preset to 0x7f7f7f7f.  misc[1] / misc[2]: largest non-zero segmentation value / 255 - smallest.
@@ -95,28 +33,28 @@ __global__ __launch_bounds__(256) void iseg_region_stats_kernel(int32_t* __restr
                                                                 int H, int W, int img_w, int C, int ch0, int cap,
                                                                 u64* __restrict__ acc, int32_t* __restrict__ bb,
                                                                 int32_t* __restrict__ misc) {
-    __shared__ int s_key[ISEG_SLOTS];
-    __shared__ unsigned s_area[ISEG_SLOTS], s_sv[ISEG_SLOTS];
-    __shared__ u64 s_sr[ISEG_SLOTS], s_sc[ISEG_SLOTS];
-    __shared__ int s_bb[4][ISEG_SLOTS];
+    __shared__ int s_key[CELL_SLOTS];
+    __shared__ unsigned s_area[CELL_SLOTS], s_sv[CELL_SLOTS];
+    __shared__ u64 s_sr[CELL_SLOTS], s_sc[CELL_SLOTS];
+    __shared__ int s_bb[4][CELL_SLOTS];
     __shared__ int s_vmax, s_vinv;
-    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-    if (t < ISEG_SLOTS) {
+    const int t = threadIdx.x, lane = t & 63;
+    if (t < CELL_SLOTS) {
         s_key[t] = -1; s_area[t] = 0; s_sv[t] = 0; s_sr[t] = 0; s_sc[t] = 0;
 #pragma unroll
         for (int j = 0; j < 4; ++j) s_bb[j][t] = INT_MAX;
     }
     if (t == 0) { s_vmax = 0; s_vinv = 0; }
     __syncthreads();
-    const int xb = (int)blockIdx.x * 64, x = xb + lane;
-    const int ybeg = (int)blockIdx.y * (4 * ISEG_ROWS_PER_WAVE) + wv * ISEG_ROWS_PER_WAVE;
+    const StatTile tile = stat_tile(W);
+    const int xb = (int)tile.xb;                             // < W
     int vmax = 0, vinv = 0;
-    for (int r = 0; r < ISEG_ROWS_PER_WAVE; ++r) {
-        const int y = ybeg + r;
+    for (int r = 0; r < CELL_ROWS_PER_WAVE; ++r) {
+        const int y = tile.ybeg + r;
         if (y >= H) break;                                   // wave-uniform
         int reg = -1, v = 0;
-        if (x < W) {
-            const size_t p = (size_t)y * W + x;
+        if (tile.x < (unsigned)W) {
+            const size_t p = (size_t)y * W + tile.x;
             const int l = L[p];
             if (l > 0) {
                 reg = rid[l - 1];
@@ -124,49 +62,37 @@ __global__ __launch_bounds__(256) void iseg_region_stats_kernel(int32_t* __restr
                 const int sv = seg[p];
                 vmax = max(vmax, sv);
                 vinv = max(vinv, 255 - sv);
-                v = img[((size_t)y * img_w + x) * C + ch0];
+                v = img[((size_t)y * img_w + tile.x) * C + ch0];
                 if (reg >= cap) reg = -1;                    // counted, not accumulated: the caller's buffer is too small
             }
         }
-        u64 active = __ballot(reg >= 0);
-        while (active) {
-            const int leader = __ffsll((long long)active) - 1;
-            const int key = __shfl(reg, leader);
-            const bool mine = reg == key;
-            const u64 m = __ballot(mine);
+        wave_key_groups(reg, [&](int key, bool mine, u64 m, int leader) {
             unsigned packed = mine ? ((unsigned)lane << 16) | (unsigned)v : 0u;   // sum of lanes <= 2016, sum of v <= 16320
 #pragma unroll
             for (int d = 32; d >= 1; d >>= 1) packed += __shfl_xor(packed, d);
-            if (lane == leader) {
-                const unsigned n = (unsigned)__popcll(m);
-                const int xl = xb + leader, xr = xb + 63 - __clzll((long long)m);
-                const u64 sr = (u64)y * n, sc = (u64)xb * n + (packed >> 16);
-                const unsigned sv = packed & 0xffffu;
-                int slot = key & (ISEG_SLOTS - 1), found = -1;
-                for (int probe = 0; probe < ISEG_SLOTS; ++probe) {
-                    const int old = atomicCAS(&s_key[slot], -1, key);
-                    if (old == -1 || old == key) { found = slot; break; }
-                    slot = (slot + 1) & (ISEG_SLOTS - 1);
-                }
-                if (found >= 0) {
-                    atomicAdd(&s_area[found], n); atomicAdd(&s_sr[found], sr); atomicAdd(&s_sc[found], sc); atomicAdd(&s_sv[found], sv);
-                    atomicMin(&s_bb[0][found], y); atomicMin(&s_bb[1][found], xl);
-                    atomicMin(&s_bb[2][found], -y); atomicMin(&s_bb[3][found], -xr);
-                } else {                                     // more than 64 regions in one 64 x 32 tile: straight to the region
-                    u64* a = acc + (size_t)key * 4;
-                    atomicAdd(a + 0, (u64)n); atomicAdd(a + 1, sr); atomicAdd(a + 2, sc); atomicAdd(a + 3, (u64)sv);
-                    int32_t* b = bb + (size_t)key * 4;
-                    atomicMin(b + 0, y); atomicMin(b + 1, xl); atomicMin(b + 2, -y); atomicMin(b + 3, -xr);
-                }
+            if (lane != leader) return;
+            const unsigned n = (unsigned)__popcll(m);
+            const int xl = xb + leader, xr = xb + 63 - __clzll((long long)m);
+            const u64 sr = (u64)y * n, sc = (u64)xb * n + (packed >> 16);
+            const unsigned sv = packed & 0xffffu;
+            const int found = lds_key_claim(s_key, key);
+            if (found >= 0) {
+                atomicAdd(&s_area[found], n); atomicAdd(&s_sr[found], sr); atomicAdd(&s_sc[found], sc); atomicAdd(&s_sv[found], sv);
+                atomicMin(&s_bb[0][found], y); atomicMin(&s_bb[1][found], xl);
+                atomicMin(&s_bb[2][found], -y); atomicMin(&s_bb[3][found], -xr);
+            } else {                                         // more than 64 regions in one 64 x 32 tile: straight to the region
+                u64* a = acc + (size_t)key * 4;
+                atomicAdd(a + 0, (u64)n); atomicAdd(a + 1, sr); atomicAdd(a + 2, sc); atomicAdd(a + 3, (u64)sv);
+                int32_t* b = bb + (size_t)key * 4;
+                atomicMin(b + 0, y); atomicMin(b + 1, xl); atomicMin(b + 2, -y); atomicMin(b + 3, -xr);
             }
-            active &= ~m;
-        }
+        });
     }
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) { vmax = max(vmax, __shfl_xor(vmax, d)); vinv = max(vinv, __shfl_xor(vinv, d)); }
     if (lane == 0) { atomicMax(&s_vmax, vmax); atomicMax(&s_vinv, vinv); }
     __syncthreads();
-    if (t < ISEG_SLOTS && s_key[t] >= 0) {
+    if (t < CELL_SLOTS && s_key[t] >= 0) {
         const int k = s_key[t];
         u64* a = acc + (size_t)k * 4;
         atomicAdd(a + 0, (u64)s_area[t]); atomicAdd(a + 1, s_sr[t]); atomicAdd(a + 2, s_sc[t]); atomicAdd(a + 3, (u64)s_sv[t]);
@@ -195,16 +121,12 @@ __global__ __launch_bounds__(256) void iseg_finalize_kernel(const u64* __restric
 hipError_t run_nuclei_regions(const uint8_t* seg, const uint8_t* img, int H, int W, int img_w, int C, int ch0, int32_t* labels,
                               const RegionBufs& b, hipStream_t s) {
     const int px = H * W;
-    const int nb = (px + ISEG_CHUNK - 1) / ISEG_CHUNK;
     hipError_t e;
     if ((e = hipMemsetAsync(b.misc, 0, 4 * sizeof(int32_t), s)) != hipSuccess) return e;
     if (b.cap > 0 && (e = hipMemsetAsync(b.acc, 0, (size_t)b.cap * 4 * sizeof(u64), s)) != hipSuccess) return e;
     if (b.cap > 0 && (e = hipMemsetAsync(b.bb, 0x7f, (size_t)b.cap * 4 * sizeof(int32_t), s)) != hipSuccess) return e;
-    hipLaunchKernelGGL(iseg_root_count_kernel, dim3(nb), dim3(256), 0, s, labels, px, b.blk);
-    hipLaunchKernelGGL(iseg_scan_kernel, dim3(1), dim3(256), 0, s, b.blk, nb, b.misc);
-    hipLaunchKernelGGL(iseg_root_id_kernel, dim3(nb), dim3(256), 0, s, labels, px, b.blk, b.rid);
-    const dim3 g((W + 63) / 64, (H + 4 * ISEG_ROWS_PER_WAVE - 1) / (4 * ISEG_ROWS_PER_WAVE));
-    hipLaunchKernelGGL(iseg_region_stats_kernel, g, dim3(256), 0, s, labels, b.rid, seg, img, H, W, img_w, C, ch0, b.cap, b.acc,
+    exclusive_scan(LoadRootFlag{labels}, px, b.blk, b.rid, b.misc, s);   // rid[root pixel] = region index, misc[0] = regions
+    hipLaunchKernelGGL(iseg_region_stats_kernel, dim3(stat_tiles(H, W)), dim3(256), 0, s, labels, b.rid, seg, img, H, W, img_w, C, ch0, b.cap, b.acc,
                        b.bb, b.misc);
     if (b.cap > 0)
         hipLaunchKernelGGL(iseg_finalize_kernel, dim3((b.cap + 255) / 256), dim3(256), 0, s, b.acc, b.bb, b.misc, b.cap, b.rec);

@@ -1,7 +1,7 @@
 // The clean-up behind NuSeT's marker watershed on gfx950: clean_image (reference src/nuset_utils/normalization.py:25-37) and the final
 // threshold of nuclei_segment (src/utils.py:159-162), one image, no host round trip.  Every step is a component labelling with
-// per-component areas (union-find over pixel indices, device_util.h) followed by a per-pixel decision, so no result depends on the
-// order of the atomics:
+// per-component areas (union-find over pixel indices: uf_unite_back and uf_size_kernel of cell_util.h) followed by a per-pixel
+// decision, so no result depends on the order of the atomics:
 //   1. 4-connected components of mask != 0 -> the number of cells n and the pixel sum s; mean_area = float32(s) / n in float64 and
 //      the size threshold t = mean_area / 5 (n = 0: NaN, every comparison below is false and nothing is removed);
 //   2. remove_small_objects(connectivity=2): 8-connected components of the mask with area < t go;
@@ -15,7 +15,7 @@
 // binary heap - marker pixels of equal d^2 carry equal (value, age) keys and leave the heap as its sift rules decide - so it runs
 // as one serial stream that replays that heap; everything around it is parallel.
 #include "common.h"
-#include "device_util.h"
+#include "cell_util.h"
 
 namespace ecseg {
 namespace {
@@ -36,34 +36,7 @@ __global__ __launch_bounds__(256) void wk_unite_kernel(int H, int W, int conn8, 
     const int p = (int)pu;
     if (uf_load(par, p) < 0) return;
     const int y = p / W, x = p - y * W;
-    // parents only ever move to smaller pixel indices, so "keyed" stays readable as >= 0 while others unite
-    if (x > 0 && uf_load(par, p - 1) >= 0) uf_unite(par, p, p - 1);
-    if (y > 0 && uf_load(par, p - W) >= 0) uf_unite(par, p, p - W);
-    if (conn8 && y > 0) {
-        if (x > 0 && uf_load(par, p - W - 1) >= 0) uf_unite(par, p, p - W - 1);
-        if (x + 1 < W && uf_load(par, p - W + 1) >= 0) uf_unite(par, p, p - W + 1);
-    }
-}
-
-// parent = root for every keyed pixel; sz[root] = pixels of the component; cnt (may be null): [0] += components, [1] += keyed pixels
-__global__ __launch_bounds__(256) void wk_size_kernel(int px, int32_t* par, int32_t* __restrict__ sz, int32_t* __restrict__ cnt) {
-    const unsigned pu = blockIdx.x * 256u + threadIdx.x;
-    const int p = (int)pu;
-    bool keyed = false, is_root = false;
-    if (pu < (unsigned)px && uf_load(par, p) >= 0) {
-        keyed = true;
-        const int root = uf_find(par, p);
-        __hip_atomic_store(par + p, root, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // a shortcut inside the same tree
-        atomicAdd(sz + root, 1);
-        is_root = root == p;
-    }
-    if (cnt) {                                               // one atomic per wave and counter
-        const int nk = __popcll(__ballot(keyed)), nr = __popcll(__ballot(is_root));
-        if ((threadIdx.x & 63) == 0) {
-            if (nr) atomicAdd(cnt + 0, nr);
-            if (nk) atomicAdd(cnt + 1, nk);
-        }
-    }
+    uf_unite_back(par, p, y, x, W, conn8, [](int) { return true; });
 }
 
 // dbl[0] = mean_area = float32(pixels) / cells in float64 (normalization.py:30), dbl[1] = mean_area / 5 (:34,36)
@@ -319,7 +292,7 @@ hipError_t run_clean_nuclei(const uint8_t* mask, int H, int W, int nuclei_size_t
     auto label = [&](const uint8_t* img, int want, int conn8, int32_t* cnt) {
         hipLaunchKernelGGL(wk_init_kernel, g, t, 0, s, img, px, want, b.par, b.sz);
         hipLaunchKernelGGL(wk_unite_kernel, g, t, 0, s, H, W, conn8, b.par);
-        hipLaunchKernelGGL(wk_size_kernel, g, t, 0, s, px, b.par, b.sz, cnt);
+        hipLaunchKernelGGL(uf_size_kernel, g, t, 0, s, px, b.par, b.sz, cnt);
     };
     label(mask, 1, 0, b.misc);                               // misc[0] cells, misc[1] pixels
     hipLaunchKernelGGL(wk_mean_kernel, dim3(1), dim3(64), 0, s, b.misc, b.dbl);

@@ -323,5 +323,6 @@ def test_the_new_kernels_are_in_the_shipped_library():
     """The unchanged spill test of test_host_cpu.py covers every kernel of the library; this pins that the new ones are among them."""
     from ecseg_amd._lib import LIB_PATH
     blob = open(LIB_PATH, 'rb').read()
-    for name in (b'fd_mark_kernel', b'fd_cell_stats_kernel', b'fd_fill_unite_kernel', b'fd_distance_kernel', b'fd_chunk_excl_kernel'):
+    for name in (b'fd_mark_kernel', b'fd_cell_stats_kernel', b'fd_fill_unite_kernel', b'fd_distance_kernel', b'scan_chunk_sum_kernel',
+                 b'scan_blocks_kernel', b'scan_chunk_excl_kernel'):
         assert name in blob, name

@@ -95,7 +95,7 @@ def test_fuzz_generator_cases(gpu):
         assert not bad, 'seed %d: %s' % (seed, '; '.join(bad))
 
 
-@pytest.mark.parametrize('size', [(1, 1), (1, 64), (64, 1), (1, 1000), (1000, 1), (2, 2), (63, 65), (33, 1025), (1025, 3)])
+@pytest.mark.parametrize('size', [(1, 1), (1, 64), (64, 1), (1, 1000), (1000, 1), (2, 2), (63, 65), (33, 1025), (1025, 3), (512, 512), (512, 514)])
 def test_degenerate_sizes(gpu, size):
     for seed in range(3):
         lsq, seg = cases.scene(100 + seed, size=size)

@@ -79,7 +79,7 @@ def test_committed_seeds(gpu):
             _check(gpu, case, producer=ref.loop)
 
 
-@pytest.mark.parametrize('size', [(1, 1), (1, 64), (64, 1), (2, 2), (63, 65), (33, 1025), (1025, 3), (129, 257), (16, 64), (17, 65)])
+@pytest.mark.parametrize('size', [(1, 1), (1, 64), (64, 1), (2, 2), (63, 65), (33, 1025), (1025, 3), (129, 257), (16, 64), (17, 65), (512, 512), (512, 514)])
 def test_odd_sizes(gpu, size):
     for seed in range(3):
         _check(gpu, cases.scene(200 + seed, size=size, K=(7, 3, 23)[seed]))
