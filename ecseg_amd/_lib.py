@@ -16,7 +16,7 @@ EXPORTS = [
     'ecseg_segment_images', 'ecseg_segment_images_ex', 'ecseg_segment_images_dev', 'ecseg_set_images_per_group', 'ecseg_set_option', 'ecseg_preprocess', 'ecseg_u16_to_u8',
     'ecseg_meta_segment', 'ecseg_prefetch_input', 'ecseg_host_alloc', 'ecseg_host_free',
     'ecseg_stitch_argmax', 'ecseg_meta_inference', 'ecseg_meta_inference_dev', 'ecseg_count_cc', 'ecseg_ccl_labels',
-    'ecseg_count_colocalization', 'ecseg_count_hsr', 'ecseg_overlay', 'ecseg_nuclei_regions', 'ecseg_nucleus_crops', 'ecseg_fish_distances', 'ecseg_fish_spots', 'ecseg_min_cut', 'ecseg_nuset_forward', 'ecseg_rpn_proposals', 'ecseg_rpn_proposals_last', 'ecseg_marker_watershed', 'ecseg_clean_nuclei', 'ecseg_get_timings',
+    'ecseg_count_colocalization', 'ecseg_count_hsr', 'ecseg_overlay', 'ecseg_nuclei_regions', 'ecseg_nucleus_crops', 'ecseg_fish_distances', 'ecseg_fish_spots', 'ecseg_min_cut', 'ecseg_nuset_forward', 'ecseg_rpn_proposals', 'ecseg_rpn_proposals_last', 'ecseg_marker_watershed', 'ecseg_clean_nuclei', 'ecseg_rescale_down', 'ecseg_rescale_mask_up', 'ecseg_get_timings',
     'ecseg_set_kernel_profiling', 'ecseg_get_conv_profile', 'ecseg_get_conv_executed_flops', 'ecseg_get_conv_launch_profile', 'ecseg_debug_peek', 'ecseg_lzw_decode', 'ecseg_lzw_encode',
     'ecseg_comm_unique_id', 'ecseg_comm_create', 'ecseg_comm_destroy', 'ecseg_comm_last_error', 'ecseg_allgather_records', 'ecseg_allgather_records_dev',
     'ecseg_npy_write_i64', 'ecseg_png_write_labels', 'ecseg_png_write', 'ecseg_png_write_channel', 'ecseg_npy_label_info', 'ecseg_npy_read_labels_u8', 'ecseg_tiff_write_gray8', 'ecseg_tiff_info', 'ecseg_tiff_read',
@@ -48,6 +48,26 @@ class OpDesc(C.Structure):
 
 
 _lib = None
+
+
+def rescale_extent(shape, scale):
+    """The output extent of scikit-image's ``rescale``: ``np.round(scale * shape)``, half to even -> (out_h, out_w)."""
+    out = np.round(scale * np.asarray(shape))
+    return int(out[0]), int(out[1])
+
+
+def rescale_weights(n_in, n_out):
+    """The float64 weights ``rescale(anti_aliasing=True)`` filters one axis with (scipy 1.7's ``gaussian_filter1d``):
+    sigma = max(0, (f - 1) / 2) with f = n_in / n_out, radius r = int(4 sigma + 0.5), exp(-0.5 / sigma^2 * x^2) over -r .. r divided by
+    its sum; [1.0] (r = 0) where scipy copies the axis (sigma <= 1e-15)."""
+    sigma = max(0.0, (float(np.float64(n_in) / np.float64(n_out)) - 1) / 2)
+    if not sigma > 1e-15:
+        return np.ones(1, np.float64)
+    radius = int(4.0 * sigma + 0.5)
+    sigma2 = sigma * sigma
+    x = np.arange(-radius, radius + 1)
+    phi = np.exp(-0.5 / sigma2 * x ** 2)
+    return np.ascontiguousarray(phi / phi.sum(), np.float64)
 
 
 def load_library():
@@ -107,6 +127,8 @@ def load_library():
     lib.ecseg_rpn_proposals_last.argtypes = [vp, i32, vp, i32, i32, i32, C.c_float, i32, i32, C.POINTER(C.c_int32), vp, vp, vp]
     lib.ecseg_marker_watershed.argtypes = [vp, vp, i32, i32, vp, vp, vp, C.c_longlong, vp]
     lib.ecseg_clean_nuclei.argtypes = [vp, vp, i32, i32, i32, vp, vp, C.POINTER(C.c_double)]
+    lib.ecseg_rescale_down.argtypes = [vp, vp, i32, i32, i32, i32, vp, i32, vp, i32, vp, vp]
+    lib.ecseg_rescale_mask_up.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp]
     lib.ecseg_get_timings.argtypes = [vp, vp]
     lib.ecseg_set_kernel_profiling.argtypes = [vp, i32]
     lib.ecseg_get_conv_profile.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double)]
@@ -634,6 +656,41 @@ class Handle:
         self._check(self.lib.ecseg_clean_nuclei(self.h, _ptr(m), m.shape[0], m.shape[1], int(nuclei_size_T), _ptr(out), _ptr(cleaned),
                                                 C.byref(mean)), 'ecseg_clean_nuclei')
         return (out, mean.value, cleaned) if want_cleaned else (out, mean.value)
+
+    @staticmethod
+    def _rescale_u8(a, what):
+        a = np.asarray(a)
+        if a.ndim != 2:
+            raise ValueError('%s takes one (H, W) image' % what)
+        if a.dtype != np.uint8:
+            raise ValueError('%s: expected uint8, got %s (scikit-image 0.18 filters in the input\'s dtype: another dtype is another '
+                             'result)' % (what, a.dtype))
+        return np.ascontiguousarray(a)
+
+    def rescale_down(self, image_u8, scale):
+        """``rescale(image, scale, anti_aliasing=True)`` of scikit-image 0.18 (src/utils.py:136) on a uint8 (H, W) image, 0 < scale <= 1 ->
+        (float64 (out_h, out_w) in [0, 1], the Gaussian-filtered uint8 (H, W) image) (ecseg_rescale_down; the extent and the weights
+        are computed here in float64: ``rescale_extent``, ``rescale_weights``)."""
+        a = self._rescale_u8(image_u8, 'rescale_down')
+        H, W = a.shape
+        oh, ow = rescale_extent(a.shape, scale)
+        wy, wx = rescale_weights(H, max(oh, 1)), rescale_weights(W, max(ow, 1))
+        out = np.empty((max(oh, 0), max(ow, 0)), np.float64)
+        filtered = np.empty((H, W), np.uint8)
+        self._check(self.lib.ecseg_rescale_down(self.h, _ptr(a), H, W, oh, ow, _ptr(wy), len(wy) // 2, _ptr(wx), len(wx) // 2, _ptr(filtered),
+                                                _ptr(out)), 'ecseg_rescale_down')
+        return out, filtered
+
+    def rescale_mask_up(self, cleaned, scale, nuclei_size_T):
+        """``rescale(cleaned, scale)`` (``scale`` = 1 / scale_ratio >= 1, as the caller computes it) of ``clean_image``'s uint8 0 / 1
+        output, the min-max scaling, the threshold and ``remove_small_objects(bool, nuclei_size_T)`` of src/utils.py:157-162 -> uint8
+        0 / 255 of extent ``np.round(scale * shape)`` (ecseg_rescale_mask_up)."""
+        c = self._rescale_u8(cleaned, 'rescale_mask_up')
+        oh, ow = rescale_extent(c.shape, scale)
+        out = np.empty((max(oh, 0), max(ow, 0)), np.uint8)
+        self._check(self.lib.ecseg_rescale_mask_up(self.h, _ptr(c), c.shape[0], c.shape[1], oh, ow, int(nuclei_size_T), _ptr(out)),
+                    'ecseg_rescale_mask_up')
+        return out
 
     # ---- timing ---------------------------------------------------------------------------------------
     def timings(self):

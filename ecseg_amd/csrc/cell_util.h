@@ -1,5 +1,5 @@
 // Per-cell device primitives shared by the interSeg regions, the FISH distances, the FISH spot statistics and the watershed
-// clean-up (interseg_kernels.hip, fishdist_kernels.hip, fishspot_kernels.hip, watershed_kernels.hip; gfx950 only).  Everything
+// clean-up and rescale (interseg_kernels.hip, fishdist_kernels.hip, fishspot_kernels.hip, watershed_kernels.hip, rescale_kernels.hip; gfx950 only).  Everything
 // built from them is an integer sum, OR, minimum, maximum or root count, so no result depends on the order of the atomics.
 #pragma once
 #include "device_util.h"

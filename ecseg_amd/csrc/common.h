@@ -291,4 +291,16 @@ struct WatershedBufs { int32_t* idx; int32_t* rw; int32_t* g; int32_t* d2; int32
 hipError_t run_marker_watershed(const uint8_t* mask, int H, int W, const int32_t* rows, const int32_t* cols, const int32_t* labels, int n,
                                 int heap_cap, const WatershedBufs& b, hipStream_t s);
 
+// ---- launchers implemented in rescale_kernels.hip (src/utils.py:136,157-162 on scikit-image 0.18 / scipy 1.7) ------------------
+// img (H, W) uint8 on the device -> filtered (H, W) uint8 (the two truncating Gaussian passes; tmp: H*W uint8 between them) and out
+// (oh, ow) float64 (the bilinear warp of filtered / 255).  wy / wx: 2 r + 1 float64 weights on the device, r = 0: that axis is
+// copied.  Validated by the caller: oh <= H, ow <= W, ry < H, rx < W, radii <= ECSEG_RESCALE_MAX_RADIUS.
+hipError_t run_rescale_down(const uint8_t* img, int H, int W, int oh, int ow, const double* wy, int ry, const double* wx, int rx,
+                            uint8_t* tmp, uint8_t* filtered, double* out, hipStream_t s);
+// Device buffers of one up-scaling to oh x ow: v (oh*ow float64), mm (2 uint64: ~min and max of v as bit patterns), par and sz
+// (oh*ow int32) and out (oh*ow uint8, the final 0 / 255 mask).
+struct RescaleUpBufs { double* v; unsigned long long* mm; int32_t* par; int32_t* sz; uint8_t* out; };
+// cleaned (H, W) uint8 on the device, oh >= H, ow >= W, oh * ow < 2^31.
+hipError_t run_rescale_mask_up(const uint8_t* cleaned, int H, int W, int oh, int ow, int nuclei_size_t, const RescaleUpBufs& b, hipStream_t s);
+
 }  // namespace ecseg

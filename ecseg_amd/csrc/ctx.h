@@ -159,6 +159,10 @@ struct DevMem {
     DevBuf<uint8_t> d_ws_work, d_ws_filled;
     DevBuf<unsigned long long> d_ws_hk;
     DevBuf<int2> d_ws_hp;
+    // ecseg_rescale_down and ecseg_rescale_mask_up (par, sz, out and the mask are those of ecseg_clean_nuclei)
+    DevBuf<uint8_t> d_rs_tmp, d_rs_filtered;
+    DevBuf<double> d_rs_w, d_rs_v;
+    DevBuf<unsigned long long> d_rs_mm;
 };
 
 }  // namespace ecseg

@@ -683,4 +683,69 @@ int ecseg_clean_nuclei(ecseg_ctx* h, const uint8_t* mask, int H, int W, int nucl
     return ECSEG_OK;
 }
 
+// ---- NuSeT's two rescale calls (src/utils.py:136,157-162) ----------------------------------------------------------------------
+int ecseg_rescale_down(ecseg_ctx* h, const uint8_t* img, int H, int W, int out_h, int out_w, const double* wy, int ry, const double* wx,
+                       int rx, uint8_t* filtered, double* out) {
+    if (!h) return ECSEG_E_INVALID;
+    drop_sent_ahead(h);
+    if (!img || !out || H <= 0 || W <= 0 || out_h <= 0 || out_w <= 0) return fail(h, ECSEG_E_INVALID, "rescale_down: bad arguments");
+    if ((long long)H * W >= (1ll << 31)) return fail(h, ECSEG_E_INVALID, "rescale_down: the image must hold fewer than 2^31 pixels");
+    if (out_h > H || out_w > W) return fail(h, ECSEG_E_INVALID, "rescale_down: the output extent exceeds the input's");
+    if (ry < 0 || rx < 0 || ry > ECSEG_RESCALE_MAX_RADIUS || rx > ECSEG_RESCALE_MAX_RADIUS)
+        return fail(h, ECSEG_E_INVALID, "rescale_down: a filter radius outside 0 .. " + std::to_string(ECSEG_RESCALE_MAX_RADIUS));
+    if (ry >= H || rx >= W) return fail(h, ECSEG_E_INVALID, "rescale_down: a filter radius reaches across the whole image");
+    if ((ry > 0 && !wy) || (rx > 0 && !wx)) return fail(h, ECSEG_E_INVALID, "rescale_down: no weights for a radius above 0");
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t px = (size_t)H * W, opx = (size_t)out_h * out_w;
+    int rc;
+    if ((rc = h->d_cl_mask.ensure(h, px))) return rc;
+    if ((rc = h->d_rs_tmp.ensure(h, px))) return rc;
+    if ((rc = h->d_rs_filtered.ensure(h, px))) return rc;
+    if ((rc = h->d_rs_v.ensure(h, opx))) return rc;
+    if ((rc = h->d_rs_w.ensure(h, 2 * (2 * ECSEG_RESCALE_MAX_RADIUS + 1)))) return rc;
+    hipStream_t s = h->stream;
+    for (float& v : h->stage_ms) v = 0.f;
+    double* d_wy = h->d_rs_w; double* d_wx = d_wy + (2 * ECSEG_RESCALE_MAX_RADIUS + 1);
+    HIP_TRY(h, hipMemcpyAsync(h->d_cl_mask, img, px, hipMemcpyHostToDevice, s));
+    if (ry > 0) HIP_TRY(h, hipMemcpyAsync(d_wy, wy, (size_t)(2 * ry + 1) * sizeof(double), hipMemcpyHostToDevice, s));
+    if (rx > 0) HIP_TRY(h, hipMemcpyAsync(d_wx, wx, (size_t)(2 * rx + 1) * sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipEventRecord(h->ev[0], s));
+    HIP_TRY(h, run_rescale_down(h->d_cl_mask, H, W, out_h, out_w, d_wy, ry, d_wx, rx, h->d_rs_tmp, h->d_rs_filtered, h->d_rs_v, s));
+    HIP_TRY(h, hipEventRecord(h->ev[1], s));
+    HIP_TRY(h, hipMemcpyAsync(out, h->d_rs_v, opx * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (filtered) HIP_TRY(h, hipMemcpyAsync(filtered, h->d_rs_filtered, px, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    h->stage_ms[ECSEG_T_COUNT] = stage_elapsed(h->ev[0], h->ev[1]);
+    return ECSEG_OK;
+}
+
+int ecseg_rescale_mask_up(ecseg_ctx* h, const uint8_t* cleaned, int H, int W, int out_h, int out_w, int nuclei_size_t, uint8_t* out) {
+    if (!h) return ECSEG_E_INVALID;
+    drop_sent_ahead(h);
+    if (!cleaned || !out || H <= 0 || W <= 0 || out_h <= 0 || out_w <= 0) return fail(h, ECSEG_E_INVALID, "rescale_mask_up: bad arguments");
+    if ((long long)out_h * out_w >= (1ll << 31)) return fail(h, ECSEG_E_INVALID, "rescale_mask_up: the output must hold fewer than 2^31 pixels");
+    if (nuclei_size_t < 0) return fail(h, ECSEG_E_INVALID, "rescale_mask_up: nuclei_size_T must not be negative");
+    if (out_h < H || out_w < W) return fail(h, ECSEG_E_INVALID, "rescale_mask_up: the output extent is below the input's");
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t px = (size_t)H * W, opx = (size_t)out_h * out_w;
+    int rc;
+    if ((rc = h->d_cl_mask.ensure(h, px))) return rc;
+    if ((rc = h->d_cl_out.ensure(h, opx))) return rc;
+    if ((rc = h->d_cl_par.ensure(h, opx))) return rc;
+    if ((rc = h->d_cl_sz.ensure(h, opx))) return rc;
+    if ((rc = h->d_rs_v.ensure(h, opx))) return rc;
+    if ((rc = h->d_rs_mm.ensure(h, 2))) return rc;
+    hipStream_t s = h->stream;
+    for (float& v : h->stage_ms) v = 0.f;
+    HIP_TRY(h, hipMemcpyAsync(h->d_cl_mask, cleaned, px, hipMemcpyHostToDevice, s));
+    const RescaleUpBufs b{h->d_rs_v, h->d_rs_mm, h->d_cl_par, h->d_cl_sz, h->d_cl_out};
+    HIP_TRY(h, hipEventRecord(h->ev[0], s));
+    HIP_TRY(h, run_rescale_mask_up(h->d_cl_mask, H, W, out_h, out_w, nuclei_size_t, b, s));
+    HIP_TRY(h, hipEventRecord(h->ev[1], s));
+    HIP_TRY(h, hipMemcpyAsync(out, h->d_cl_out, opx, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    h->stage_ms[ECSEG_T_COUNT] = stage_elapsed(h->ev[0], h->ev[1]);
+    return ECSEG_OK;
+}
+
 }  // extern "C"

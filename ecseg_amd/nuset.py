@@ -2,15 +2,16 @@
 computes - the U-Net's argmax mask, the RPN head on its pool-4 feature map and the proposal layer (decode, filter, top-k, NMS,
 clip) - on the device, behind one three-output plan.  The ``py_func`` half that follows it in the reference is here too, at
 ``resize_scale == 1`` (``NuSeT.segment``): the marker list of ``marker_watershed`` on the host (``watershed_markers``), the watershed
-(``Handle.marker_watershed``) and ``clean_image`` with the final threshold (``Handle.clean_nuclei``) on the device.  ``rescale`` is not
-(DESIGN.md 5.12, 10).
+(``Handle.marker_watershed``) and ``clean_image`` with the final threshold (``Handle.clean_nuclei``) on the device.  At
+``0 < resize_scale < 1`` the two ``rescale`` calls around them run on the device too (``Handle.rescale_down``,
+``Handle.rescale_mask_up``), as scikit-image 0.18.3 computes them; ``resize_scale > 1`` is not built.
 
 Host side, as in the reference: ``whole_image_norm`` / ``foreground_norm`` (src/nuset_utils/normalization.py), ``anchor_size``
 (src/model_layers/anchor_size.py, from the region records of ``ecseg_nuclei_regions``) and ``reference_anchors``
 (src/nuset_utils/anchors.py) in float64."""
 import numpy as np
 
-from . import keras_plan, synth
+from . import _lib, keras_plan, synth
 
 STRIDE = 16                                            # src/utils.py:64
 SCALES = (0.5, 1.0, 2.0)                               # :59
@@ -210,7 +211,6 @@ class NuSeT:
 
     def __init__(self, weights, base=64, handle=None, device=0):
         if handle is None:
-            from . import _lib
             handle = _lib.Handle(device)
         self.handle, self.weights, self.base = handle, weights, int(base)
         self.plan = None
@@ -263,10 +263,27 @@ class NuSeT:
         top = scores > min_score
         return m, scores[top], proposals[top]
 
-    def segment(self, image, min_score=0.95, nms_threshold=0.01, nuclei_size_T=0, second=None):
-        """``nuclei_segment`` at ``resize_scale == 1`` (src/utils.py:134-163): ``nuclei_masks``, the markers, the marker watershed,
-        ``clean_image`` and the final threshold -> uint8 0 / 255 mask of the cropped extent (multiples of 16)."""
+    def segment(self, image, min_score=0.95, nms_threshold=0.01, nuclei_size_T=0, second=None, scale_ratio=1):
+        """``nuclei_segment`` (src/utils.py:134-163): ``nuclei_masks``, the markers, the marker watershed, ``clean_image`` and the final
+        threshold -> uint8 0 / 255 mask of the cropped extent (multiples of 16).  ``scale_ratio`` (``resize_scale``) below 1: the uint8
+        image is shrunk first (``Handle.rescale_down``, :136), everything up to ``clean_image`` runs on the small float64 image, and the
+        cleaned mask is scaled back up before the threshold (``Handle.rescale_mask_up``, :157-162) -> a mask of
+        ``round(cropped small extent / scale_ratio)``, within a few pixels of the image's extent.  A scaled image below 16 x 16, or a
+        ``scale_ratio`` outside (0, 1], raises ``ValueError``."""
+        if scale_ratio != 1:
+            if not 0 < scale_ratio < 1:
+                raise ValueError('segment: scale_ratio must lie in (0, 1], got %r (above 1 the reference\'s second rescale Gaussian-filters the '
+                                 '0 / 1 uint8 mask into almost nothing: not built)' % (scale_ratio,))
+            image = np.asarray(image)
+            if image.ndim != 2:
+                raise ValueError('segment takes one (H, W) image')
+            if min(_lib.rescale_extent(image.shape, scale_ratio)) < 16:
+                raise ValueError('segment: the image scaled by %s is smaller than 16 x 16' % (scale_ratio,))
+            image = self.handle.rescale_down(image, scale_ratio)[0]
         m, scores, proposals = self.nuclei_masks(image, min_score, nms_threshold, second)
         mk = watershed_markers(scores, proposals, m, min_score, self.handle)
         ws = m if mk is None else self.handle.marker_watershed(m, *mk)
-        return self.handle.clean_nuclei(ws, nuclei_size_T)[0]
+        if scale_ratio == 1:
+            return self.handle.clean_nuclei(ws, nuclei_size_T)[0]
+        cleaned = self.handle.clean_nuclei(ws, 0, want_cleaned=True)[2]
+        return self.handle.rescale_mask_up(cleaned, 1 / scale_ratio, nuclei_size_T)

@@ -63,7 +63,7 @@ MAX_DIST = 32                  # ECSEG_MIN_CUT_MAX_DIST
 
 
 # the parameters of nuclei_segment in src/stat_fish_params.yaml, read only with the config key nuset_weights; scale_ratio: the
-# reference's file says 0.3, but rescale is not built, so 1 is the only value taken
+# reference's file says 0.3; the built-in default stays 1 (no rescale), any value in (0, 1] is taken from the file
 NUSET_DEFAULT_PARAMS = {'min_score': 0.95, 'nms_threshold': 0.01, 'scale_ratio': 1}
 
 
@@ -300,8 +300,10 @@ def load_params():
 
 def load_nuset_segmenter(var, handle):
     """The config key ``nuset_weights`` ([whole.npz, foreground.npz], or one path for both passes; optional ``nuset_base``, default
-    64) -> ``segment(blue)`` = ``NuSeT.segment`` with ``min_score`` / ``nms_threshold`` of src/stat_fish_params.yaml and
-    ``nuclei_size_T`` of the config.  Every problem is a ConfigError."""
+    64) -> ``segment(blue)`` = ``NuSeT.segment`` with ``min_score`` / ``nms_threshold`` / ``scale_ratio`` of src/stat_fish_params.yaml and
+    ``nuclei_size_T`` of the config.  ``scale_ratio`` other than 1 must lie in (0, 1) and needs a handle with ``rescale_down`` and
+    ``rescale_mask_up``; an image smaller than 16 x 16 after scaling is reported as that image's failure.  Every other problem is a
+    ConfigError."""
     import yaml
     from . import nuset
     paths = var['nuset_weights']
@@ -318,8 +320,12 @@ def load_nuset_segmenter(var, handle):
         if isinstance(v, bool) or not isinstance(v, (int, float)) or math.isnan(v):
             raise ConfigError('%s must be a number' % k)
     if prm['scale_ratio'] != 1:
-        raise ConfigError('scale_ratio: %s with nuset_weights: the rescale step of nuclei_segment (scikit-image\'s anti-aliased rescale) is '
-                          'not built; only scale_ratio: 1 is' % prm['scale_ratio'])
+        if not 0 < prm['scale_ratio'] <= 1 or math.isinf(prm['scale_ratio']):
+            raise ConfigError('scale_ratio: %s with nuset_weights: only values in (0, 1] are built (above 1 the second rescale of '
+                              'nuclei_segment Gaussian-filters the 0 / 1 uint8 mask into almost nothing)' % prm['scale_ratio'])
+        if handle is not None and not all(hasattr(handle, m) for m in ('rescale_down', 'rescale_mask_up')):
+            raise ConfigError('scale_ratio: %s with nuset_weights needs the rescale step of nuclei_segment (rescale_down, rescale_mask_up), '
+                              'which the handle in use does not have; only scale_ratio: 1 works on it' % prm['scale_ratio'])
     size_t = var['nuclei_size_T']
     if isinstance(size_t, bool) or not isinstance(size_t, int) or size_t < 0:
         raise ConfigError('nuclei_size_T must be a non-negative integer')
@@ -341,7 +347,13 @@ def load_nuset_segmenter(var, handle):
         if 'nets' not in state:
             state['nets'] = [nuset.NuSeT(w, base, handle=handle) for w in weights]
         nets = state['nets']
-        return nets[0].segment(blue, prm['min_score'], prm['nms_threshold'], size_t, second=nets[-1] if len(nets) > 1 else None)
+        second = nets[-1] if len(nets) > 1 else None
+        if prm['scale_ratio'] == 1:
+            return nets[0].segment(blue, prm['min_score'], prm['nms_threshold'], size_t, second=second)
+        try:
+            return nets[0].segment(blue, prm['min_score'], prm['nms_threshold'], size_t, second=second, scale_ratio=prm['scale_ratio'])
+        except ValueError as e:                              # e.g. smaller than 16 x 16 after scaling: this image only
+            raise ImageError(str(e))
     return segment
 
 

@@ -453,6 +453,36 @@ int ecseg_marker_watershed(ecseg_ctx* h, const uint8_t* mask, int H, int W, cons
 int ecseg_clean_nuclei(ecseg_ctx* h, const uint8_t* mask, int H, int W, int nuclei_size_T, uint8_t* out, uint8_t* cleaned,
                        double* mean_area);
 
+/* ---- NuSeT's two rescale calls (scale_ratio != 1) -------------------------------------------------------------------------------
+ * Replace, for ONE image, rescale(image, s, anti_aliasing=True) (src/utils.py:136) and rescale(masks, 1 / s) with the threshold
+ * behind it (:157-162) as scikit-image 0.18.3 / scipy 1.7.1 compute them.  All float64 arithmetic has the bits of the formulas below
+ * (no fused multiply-add, the libraries' order of operations).
+ *
+ * ecseg_rescale_down.  img: (H, W) uint8.  The host passes the output extent (np.round(s * shape)) and per axis the 2 r + 1
+ * float64 weights of scipy's gaussian_filter1d at sigma = max(0, (f - 1) / 2), f = extent / output extent, r = int(4 sigma + 0.5)
+ * (ecseg_amd/_lib.py: rescale_weights); r = 0 copies that axis and its weights are not read.  On the device:
+ *   the Gaussian on the uint8 image, axis 0 (wy, ry) first, then axis 1 (wx, rx), each pass writing uint8 by truncation; one
+ *   output is tmp = in[i] * w[0], then for j = -r .. -1 in that order tmp += (in[i + j] + in[i - j]) * w[j] (w indexed from the
+ *   centre), indices mirrored without repeating the edge sample (-1 -> 1) -> filtered (H, W) uint8 (may be null);
+ *   the order-1 warp of p = filtered / 255: per output row r, y = f_y * (r + 0.5) - 0.5, y0 = floor(y), y1 = ceil(y), dy = y - y0,
+ *   columns alike; top = (1 - dx) * p(y0, x0) + dx * p(y0, x1), bottom alike on y1, value = (1 - dy) * top + dy * bottom, indices
+ *   mirrored the same way -> out (out_h, out_w) float64.
+ * ECSEG_E_INVALID: null img, out or (r > 0) weights; an extent < 1; H * W >= 2^31; out_h > H or out_w > W; ry >= H or rx >= W (one
+ * reflection always suffices); a radius < 0 or above ECSEG_RESCALE_MAX_RADIUS (s = 0.05 needs 38).
+ *
+ * ecseg_rescale_mask_up.  cleaned: (H, W) uint8, clean_image's 0 / 1.  On the device: v = the same warp of cleaned / 255 to
+ * (out_h, out_w) (no filter: f < 1); vmin and vmax over the output; uint8(((v - vmin) / (vmax - vmin)) * 255) > 0 in float64 (an
+ * image of one value divides 0 by 0 and comes out all zero); remove_small_objects(bool, nuclei_size_T): 4-connected components
+ * below nuclei_size_T pixels go, 0 keeps all -> out (out_h, out_w) uint8 0 / 255.  ECSEG_E_INVALID: null cleaned or out, an extent
+ * < 1, out_h * out_w >= 2^31, nuclei_size_T < 0, out_h < H or out_w < W.
+ *
+ * Both: one synchronous call, buffers owned by the handle, nothing per pixel or component on the host; device time of the kernels in
+ * ECSEG_T_COUNT.  No result depends on the order of the atomics: two calls give identical bytes. */
+#define ECSEG_RESCALE_MAX_RADIUS 64
+int ecseg_rescale_down(ecseg_ctx* h, const uint8_t* img, int H, int W, int out_h, int out_w, const double* wy, int ry, const double* wx,
+                       int rx, uint8_t* filtered, double* out);
+int ecseg_rescale_mask_up(ecseg_ctx* h, const uint8_t* cleaned, int H, int W, int out_h, int out_w, int nuclei_size_T, uint8_t* out);
+
 /* ---- per-stage device timings of the last segment call (milliseconds, HIP events on the handle's stream) -- */
 /* ECSEG_T_COUNT: device time of the kernels of the last ecseg_overlay / ecseg_preprocess / ecseg_count_* call (inputs
  * already resident, copies excluded). */
