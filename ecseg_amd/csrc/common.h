@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "../../include/ecseg_hip.h"
+#include "scratch.h"
 
 namespace ecseg {
 
@@ -191,6 +192,24 @@ struct PostWorkspace {
 enum { G_STRIDE = 32, G_SHARDS = 16 };
 enum { G_SLOTS = 6 };                  // counter blocks in PostWorkspace::g: one per labelling of run_meta_inference that produces counters (zeroed by ONE memset)
 enum { NUCLEUS_BIN_EXTENT = 32768 };   // largest image extent for which the nucleus test runs on binned coordinates (LDS histogram)
+inline PostWorkspace post_workspace(Carver& c, int n_img, size_t px) {
+    PostWorkspace w{};
+    const size_t ni = (size_t)n_img, tot = ni * px;
+    // Root lists of the nucleus-in-metaphase test: run_meta_inference uses px/4 + (H+W)/2 + 4 entries per image
+    // (>= ceil(H/2)*ceil(W/2), the most 8-connected components an image can hold); (H+W)/2 <= px/2 + 1, and every
+    // entry costs 4 B (nucleus root) + 16 B (chromosome centroid).
+    const size_t list_cap = px / 4 + px / 2 + 8;
+    w.L = c.take<int32_t>(tot); w.area = c.take<uint32_t>(tot); w.sumy = c.take<unsigned long long>(tot); w.sumx = c.take<unsigned long long>(tot);
+    w.flag = c.take<uint32_t>(tot); w.tmpA = c.take<uint8_t>(tot); w.tmpB = c.take<uint8_t>(tot);
+    w.list = reinterpret_cast<int32_t*>(c.take<uint8_t>(ni * list_cap * 20 + 256)); w.g = c.take<int32_t>((size_t)G_SLOTS * ni * G_STRIDE * G_SHARDS);
+    w.tile_any = c.take<uint8_t>(ni * (px / 16 + 2));          // (W/64 + 1)(H/32 + 1) <= px/16 + 1 tiles per image
+    // owner bits: 256 B per 64 x 32 tile; ceil(W/64) ceil(H/32) <= px/2048 + W/64 + H/32 + 1 <= px/31 + 3 tiles for any H x W = px
+    w.own_bits = c.take<uint32_t>(ni * (px / 31 + 4) * 64);
+    w.binned_cap = list_cap < ((size_t)1 << 20) ? list_cap : (size_t)1 << 20;
+    w.binned = c.take<double>(ni * 2 * w.binned_cap); w.binstart = c.take<int32_t>(ni * 2 * (NUCLEUS_BIN_EXTENT + 2));
+    w.cap_img = n_img; w.cap_px = px;
+    return w;
+}
 
 // meta_inference on n_img uint8 label images, in place; n_ec receives count_cc(img==3)[0] per image
 hipError_t run_meta_inference(PostWorkspace& ws, uint8_t* img, int n_img, int H, int W, int32_t* n_ec_dev,
@@ -210,9 +229,31 @@ hipError_t run_preprocess(const void* img, int n_img, int H, int W, int C, int b
                           uint32_t* hist_ws, hipStream_t s);
 
 // ---- launchers implemented in interseg_kernels.hip (the file-level driver of src/interseg.py) ------------------------------
-// Device buffers of run_nuclei_regions: rid (H*W int32), blk (ceil(H*W / 1024) int32), misc (4 int32), and `cap` regions' worth
-// of acc (4 u64), bb (4 int32) and rec (8 int64).
+// What ecseg_nuclei_regions leaves for ecseg_nucleus_crops: the region label map (H, W) and the first H rows of the image.
+struct RegionMapBufs { int32_t* lab; uint8_t* img; };
+inline RegionMapBufs region_map_bufs(Carver& c, int H, int W, int img_w, int C) {
+    RegionMapBufs b;
+    b.lab = c.take<int32_t>((size_t)H * W); b.img = c.take<uint8_t>((size_t)H * img_w * C);
+    return b;
+}
+// Device buffers of run_nuclei_regions: the per-pixel index rid with its scan blocks blk, the counters misc, and `cap` regions'
+// worth of accumulators acc, bounding boxes bb and records rec.
 struct RegionBufs { int32_t* rid; int32_t* blk; int32_t* misc; unsigned long long* acc; int32_t* bb; int64_t* rec; int cap; };
+inline RegionBufs region_bufs(Carver& c, int H, int W, int cap) {
+    const size_t px = (size_t)H * W, n = (size_t)cap;
+    RegionBufs b;
+    b.rid = c.take<int32_t>(px); b.blk = c.take<int32_t>((px + 1023) / 1024); b.misc = c.take<int32_t>(4); b.acc = c.take<unsigned long long>(n * 4);
+    b.bb = c.take<int32_t>(n * 4); b.rec = c.take<int64_t>(n * 8);
+    b.cap = cap;
+    return b;
+}
+// Device buffers of run_nucleus_crops for n crops: the descriptors, the 256 x 256 x 3 crops and the channel maxima.
+struct CropBufs { int32_t* desc; uint8_t* crops; int32_t* max; };
+inline CropBufs crop_bufs(Carver& c, int n) {
+    CropBufs b;
+    b.desc = c.take<int32_t>((size_t)n * 5); b.crops = c.take<uint8_t>((size_t)n * 256 * 256 * 3); b.max = c.take<int32_t>((size_t)n * 3);
+    return b;
+}
 // labels: in, run_ccl_labels' 8-connected labels of seg != 0 (one image); out, 1 + region index (skimage's order), 0 background.
 // img: (>= H, img_w, C) uint8, channel ch0 summed per region.  misc[0] = number of regions, misc[1] = largest non-zero value of
 // seg, misc[2] = 255 - smallest; rec: the first min(cap, misc[0]) region records (see ecseg_nuclei_regions).
@@ -224,29 +265,54 @@ hipError_t run_nucleus_crops(const int32_t* labels, const uint8_t* img, int W, i
                              const int order[3], uint8_t* out, int32_t* chmax, hipStream_t s);
 
 // ---- launchers implemented in fishdist_kernels.hip (src/fish_distance_calculation.py:16-46) ---------------------------------
-// The dense cell index of one H x W label map, shared with fishspot_kernels.hip: rid (H*W int32), blk (ceil(H*W / 1024) int32)
-// and misc (4 int32).
-struct CellIndexBufs { int32_t* rid; int32_t* blk; int32_t* misc; };
+// The dense cell index of one H x W label map, shared with fishspot_kernels.hip: rid, its scan blocks blk and the counters misc,
+// with the label map lab and the C-channel image img they belong to.
+struct CellIndexBufs { int32_t* rid; int32_t* blk; int32_t* misc; int32_t* lab; uint8_t* img; };
+inline CellIndexBufs cell_index_bufs(Carver& c, int H, int W, int C) {
+    const size_t px = (size_t)H * W;
+    CellIndexBufs b;
+    b.lab = c.take<int32_t>(px); b.img = c.take<uint8_t>(px * C); b.rid = c.take<int32_t>(px); b.blk = c.take<int32_t>((px + 1023) / 1024);
+    b.misc = c.take<int32_t>(4);
+    return b;
+}
 // labels: (H, W) int32 instance labels, <= 0 background.  Leaves rid[label - 1] = dense ascending cell index of every label that
 // occurs, misc[0] = number of cells, misc[3] = 1 when some label exceeds H * W (rid then misses it: do not go on).
 hipError_t run_dense_cells(const int32_t* labels, int H, int W, const CellIndexBufs& b, hipStream_t s);
-// Device buffers of run_fishdist_records: rid, blk and misc as run_dense_cells left them, par (H*W int32), flist and clist
-// (H*W int2), and - sized by the number of cells n - acc (4n uint32), val (n int32), off and cur (2n int32), rec (8n int64), and
-// pbest (uint64) and proots (int32) of n * fishdist_slices(n) entries each.
+// Device buffers of run_fishdist_records: rid, blk and misc as run_dense_cells left them, the per-pixel par, flist and clist,
+// and - sized by the number of cells n - acc, val, off, cur and rec, and the per-slice pbest and proots.
 struct FishDistBufs { int32_t* rid; int32_t* par; int32_t* blk; int32_t* misc; int2* flist; int2* clist; unsigned* acc; int32_t* val;
                       int32_t* off; int32_t* cur; int64_t* rec; unsigned long long* pbest; int32_t* proots; };
 int fishdist_slices(int n);   // workgroups per cell of the distance search for n cells
+// slices: fishdist_slices(n)
+inline FishDistBufs fishdist_bufs(Carver& c, const CellIndexBufs& cells, int H, int W, int n, int slices) {
+    const size_t px = (size_t)H * W, nn = (size_t)n;
+    FishDistBufs b;
+    b.rid = cells.rid; b.blk = cells.blk; b.misc = cells.misc;
+    b.par = c.take<int32_t>(px); b.flist = c.take<int2>(px); b.clist = c.take<int2>(px); b.acc = c.take<unsigned>(nn * 4);
+    b.val = c.take<int32_t>(nn); b.off = c.take<int32_t>(nn * 2); b.cur = c.take<int32_t>(nn * 2); b.rec = c.take<int64_t>(nn * 8);
+    b.pbest = c.take<unsigned long long>(nn * slices); b.proots = c.take<int32_t>(nn * slices);
+    return b;
+}
 // After run_dense_cells with n = misc[0] > 0 and misc[3] == 0: relabels `labels` in place to cell + 1 and writes the n records
 // of ecseg_fish_distances to rec.  lsq: (H, W, C) uint8; fi / ci: FISH and centromere channel.
 hipError_t run_fishdist_records(int32_t* labels, const uint8_t* lsq, int H, int W, int C, int fi, int ci, int n, const FishDistBufs& b,
                                 hipStream_t s);
 
 // ---- launcher implemented in fishspot_kernels.hip (src/stat_fish.py:73-107,134-142,226-300) ---------------------------------
-// Device buffers of one H x W image with np probes: rid (H*W int32, as run_dense_cells left it), mx (4 int32), thr (H*W*np
-// uint8), bnd (H*W uint8), par and sz (4 planes of H*W int32 each: probes 0..2, the pair) and - sized by the number of cells n -
-// acc (12n uint64), cnt (8n uint32), val (n int32), rec (ECSEG_FISH_SPOT_INT64 x n int64).
+// Device buffers of one H x W image with np probes: rid as run_dense_cells left it, mx, the outputs thr (one plane per probe) and
+// bnd, par and sz (4 planes each: probes 0..2, the pair), the K x K filter weights w and - sized by the number of cells n - acc,
+// cnt, val and rec.
 struct FishSpotBufs { int32_t* rid; int32_t* mx; uint8_t* thr; uint8_t* bnd; int32_t* par; int32_t* sz; unsigned long long* acc;
-                      unsigned* cnt; int32_t* val; int64_t* rec; };
+                      unsigned* cnt; int32_t* val; int64_t* rec; double* w; };
+inline FishSpotBufs fishspot_bufs(Carver& c, const CellIndexBufs& cells, int H, int W, int np, int K, int n) {
+    const size_t px = (size_t)H * W, nn = (size_t)n;
+    FishSpotBufs b;
+    b.rid = cells.rid;
+    b.mx = c.take<int32_t>(4); b.w = c.take<double>((size_t)K * K); b.thr = c.take<uint8_t>(px * np); b.bnd = c.take<uint8_t>(px);
+    b.par = c.take<int32_t>(px * 4); b.sz = c.take<int32_t>(px * 4); b.acc = c.take<unsigned long long>(nn * 12); b.cnt = c.take<unsigned>(nn * 8);
+    b.val = c.take<int32_t>(nn); b.rec = c.take<int64_t>(nn * ECSEG_FISH_SPOT_INT64);
+    return b;
+}
 // After run_dense_cells with n = misc[0] > 0 and misc[3] == 0: relabels `labels` in place to cell + 1 and writes thr, bnd and the
 // n records of ecseg_fish_spots.  img: (H, W, C) uint8; ch: the np probe channels; wts: K x K float64 on the device.
 hipError_t run_fishspot(int32_t* labels, const uint8_t* img, int H, int W, int C, int np, const int ch[3], const double* wts, int K,
@@ -257,6 +323,15 @@ hipError_t run_fishspot(int32_t* labels, const uint8_t* img, int H, int W, int C
 // caller; soff: per task the byte offset of its mincut_scratch_bytes(h, w) bytes in `scratch` (16-byte aligned), or < 0 for a
 // window of at most ECSEG_MIN_CUT_LDS_PIXELS pixels whose state stays in LDS.  side: as masks, written over every window.
 size_t mincut_scratch_bytes(int h, int w);
+// Device buffers of one ecseg_min_cut call: the packed windows and their sides (mask_bytes each), the task table desc with the
+// offsets soff and the flows, and scratch_bytes = the sum of mincut_scratch_bytes over the windows too large for LDS.
+struct MinCutBufs { uint8_t* mask; uint8_t* side; int32_t* desc; long long* soff; int32_t* flow; uint8_t* scratch; };
+inline MinCutBufs mincut_bufs(Carver& c, size_t mask_bytes, int n_tasks, size_t scratch_bytes) {
+    MinCutBufs b;
+    b.mask = c.take<uint8_t>(mask_bytes); b.side = c.take<uint8_t>(mask_bytes); b.desc = c.take<int32_t>((size_t)n_tasks * 8);
+    b.soff = c.take<long long>((size_t)n_tasks); b.flow = c.take<int32_t>((size_t)n_tasks); b.scratch = c.take<uint8_t>(scratch_bytes);
+    return b;
+}
 // n_global: how many tasks have soff >= 0 (a kernel without tasks is not launched).
 hipError_t run_mincut(const uint8_t* masks, const int32_t* desc, const long long* soff, int n_tasks, int n_global, int d, uint8_t* scratch,
                       uint8_t* side, int32_t* flow, hipStream_t s);
@@ -264,28 +339,59 @@ hipError_t run_mincut(const uint8_t* masks, const int32_t* desc, const long long
 // ---- launchers implemented in nuset_kernels.hip (src/utils.py:53, src/model_layers/rpn_proposal.py) ---------------------------
 // mask (h * w uint8) = argmax over the 2 channels of `logits`, a tie giving 0.
 hipError_t launch_argmax2(const TView& logits, uint8_t* mask, hipStream_t s);
-// Device buffers of one proposal call over N = fh * fw * A candidates: boxes (N float4), scores (N float), keys (rpn_sort_len(N)
-// uint64), mat (K * ceil(K / 64) uint64 with K = min(pre_nms_top_n, N)), misc (2 int32: n_out, kept candidates) and the outputs
-// (post_nms_top_n entries each).
+struct NusetMaskBufs { uint8_t* mask; };
+inline NusetMaskBufs nuset_mask_bufs(Carver& c, int H, int W) { return NusetMaskBufs{c.take<uint8_t>((size_t)H * W)}; }
+// Device buffers of one proposal call over N = fh * fw * A candidates: boxes, scores, the sort keys, the suppression matrix mat
+// over the K = min(pre_nms_top_n, N) best, misc (n_out, kept candidates), the outputs (min(post_nms_top_n, K) entries each), the
+// A reference anchors ref and, where the host gives them, the RPN tensors cls and bbox.
 struct RpnBufs { float4* boxes; float* scores; unsigned long long* keys; unsigned long long* mat; int32_t* misc; float* out_scores;
-                 float4* out_boxes; int32_t* out_idx; };
+                 float4* out_boxes; int32_t* out_idx; double* ref; float* cls; float* bbox; };
 int rpn_sort_len(int N);      // N padded to the power of two the sort works on
+// sort_len: rpn_sort_len(fh * fw * A); upload: the RPN tensors come from the host (else cls and bbox are empty slots)
+inline RpnBufs rpn_bufs(Carver& c, int fh, int fw, int A, int sort_len, int pre, int post, bool upload) {
+    const size_t px = (size_t)fh * fw, N = px * A, K = (size_t)pre < N ? (size_t)pre : N, no = (size_t)post < K ? (size_t)post : K;
+    RpnBufs b;
+    b.ref = c.take<double>((size_t)A * 4); b.boxes = c.take<float4>(N); b.scores = c.take<float>(N);
+    b.keys = c.take<unsigned long long>((size_t)sort_len); b.mat = c.take<unsigned long long>(K * ((K + 63) / 64)); b.misc = c.take<int32_t>(2);
+    b.out_scores = c.take<float>(no); b.out_boxes = c.take<float4>(no); b.out_idx = c.take<int32_t>(no);
+    b.cls = c.take<float>(upload ? px * 2 * A : 0); b.bbox = c.take<float>(upload ? px * 4 * A : 0);
+    return b;
+}
 // cls / bbox: (fh, fw, 2A) / (fh, fw, 4A) float32 on the device, consecutive pixels cls_cs / bbox_cs floats apart; ref: A x 4
 // float64 on the device.  The arguments are validated by the caller (ecseg_rpn_proposals).
 hipError_t run_rpn_proposals(const float* cls, int cls_cs, const float* bbox, int bbox_cs, const double* ref, int fh, int fw, int A, int stride,
                              int im_h, int im_w, float nms_threshold, int pre, int post, const RpnBufs& b, hipStream_t s);
 
 // ---- launcher implemented in watershed_kernels.hip (src/nuset_utils/normalization.py:25-37, src/utils.py:159-162) ------------
-// Device buffers of one H x W image: par and sz (H*W int32), tmp, cleaned and out (H*W uint8), misc (4 int32: cells, pixels, the
-// value flags of `cleaned`, 0) and dbl (2 float64: mean_area, mean_area / 5).
-struct CleanBufs { int32_t* par; int32_t* sz; uint8_t* tmp; uint8_t* cleaned; uint8_t* out; int32_t* misc; double* dbl; };
+// Device buffers of one H x W image: the input mask, par and sz, tmp, cleaned and out, misc (cells, pixels, the value flags of
+// `cleaned`, 0) and dbl (mean_area, mean_area / 5).
+struct CleanBufs { int32_t* par; int32_t* sz; uint8_t* tmp; uint8_t* cleaned; uint8_t* out; int32_t* misc; double* dbl; uint8_t* mask; };
+inline CleanBufs clean_bufs(Carver& c, int H, int W) {
+    const size_t px = (size_t)H * W;
+    CleanBufs b;
+    b.mask = c.take<uint8_t>(px); b.tmp = c.take<uint8_t>(px); b.cleaned = c.take<uint8_t>(px); b.out = c.take<uint8_t>(px);
+    b.par = c.take<int32_t>(px); b.sz = c.take<int32_t>(px); b.misc = c.take<int32_t>(4); b.dbl = c.take<double>(2);
+    return b;
+}
 // mask: (H, W) uint8 on the device, H * W < 2^31 -> cleaned (clean_image, 0 / 1), out (the final mask, 0 / 255), dbl[0] = mean_area.
 hipError_t run_clean_nuclei(const uint8_t* mask, int H, int W, int nuclei_size_t, const CleanBufs& b, hipStream_t s);
 
-// Device buffers of run_marker_watershed for one H x W image: idx, rw, g, d2, lab, par, sz (H*W int32), work, filled, out (H*W
-// uint8), misc (4 int32: [0] `filled` holds a zero, [1] heap overflow) and the heap (heap_cap keys and payloads).
+// Device buffers of run_marker_watershed for one H x W image: the input mask, the per-pixel idx, rw, g, d2, lab, par, sz, work,
+// filled and out, misc ([0] `filled` holds a zero, [1] heap overflow), the heap (heap_cap keys and payloads) and the n_markers
+// markers' rows, cols and labels.
 struct WatershedBufs { int32_t* idx; int32_t* rw; int32_t* g; int32_t* d2; int32_t* lab; int32_t* par; int32_t* sz; uint8_t* work;
-                       uint8_t* filled; uint8_t* out; int32_t* misc; unsigned long long* heap_k; int2* heap_p; };
+                       uint8_t* filled; uint8_t* out; int32_t* misc; unsigned long long* heap_k; int2* heap_p; uint8_t* mask;
+                       int32_t* rows; int32_t* cols; int32_t* labels; };
+inline WatershedBufs watershed_bufs(Carver& c, int H, int W, int n_markers, int heap_cap) {
+    const size_t px = (size_t)H * W;
+    WatershedBufs b;
+    b.mask = c.take<uint8_t>(px); b.out = c.take<uint8_t>(px); b.par = c.take<int32_t>(px); b.sz = c.take<int32_t>(px); b.misc = c.take<int32_t>(4);
+    b.idx = c.take<int32_t>(px); b.rw = c.take<int32_t>(px); b.g = c.take<int32_t>(px); b.d2 = c.take<int32_t>(px); b.lab = c.take<int32_t>(px);
+    b.work = c.take<uint8_t>(px); b.filled = c.take<uint8_t>(px); b.rows = c.take<int32_t>((size_t)n_markers);
+    b.cols = c.take<int32_t>((size_t)n_markers); b.labels = c.take<int32_t>((size_t)n_markers);
+    b.heap_k = c.take<unsigned long long>((size_t)heap_cap); b.heap_p = c.take<int2>((size_t)heap_cap);
+    return b;
+}
 // mask (H, W) uint8 and the n ordered markers (validated by the caller) on the device -> out = mask * (flooded label != 0).
 // heap_cap >= 5 * (non-zero mask pixels) + 1: every marker pixel once, at most four pushes per expanded pixel.
 hipError_t run_marker_watershed(const uint8_t* mask, int H, int W, const int32_t* rows, const int32_t* cols, const int32_t* labels, int n,
@@ -297,9 +403,26 @@ hipError_t run_marker_watershed(const uint8_t* mask, int H, int W, const int32_t
 // copied.  Validated by the caller: oh <= H, ow <= W, ry < H, rx < W, radii <= ECSEG_RESCALE_MAX_RADIUS.
 hipError_t run_rescale_down(const uint8_t* img, int H, int W, int oh, int ow, const double* wy, int ry, const double* wx, int rx,
                             uint8_t* tmp, uint8_t* filtered, double* out, hipStream_t s);
-// Device buffers of one up-scaling to oh x ow: v (oh*ow float64), mm (2 uint64: ~min and max of v as bit patterns), par and sz
-// (oh*ow int32) and out (oh*ow uint8, the final 0 / 255 mask).
-struct RescaleUpBufs { double* v; unsigned long long* mm; int32_t* par; int32_t* sz; uint8_t* out; };
+// Device buffers of one down-scaling of an H x W image to oh x ow: run_rescale_down's arguments, wy and wx with room for the
+// largest radius.
+struct RescaleDownBufs { uint8_t* img; uint8_t* tmp; uint8_t* filtered; double* v; double* wy; double* wx; };
+inline RescaleDownBufs rescale_down_bufs(Carver& c, int H, int W, int oh, int ow) {
+    const size_t px = (size_t)H * W;
+    RescaleDownBufs b;
+    b.img = c.take<uint8_t>(px); b.tmp = c.take<uint8_t>(px); b.filtered = c.take<uint8_t>(px); b.v = c.take<double>((size_t)oh * ow);
+    b.wy = c.take<double>(2 * ECSEG_RESCALE_MAX_RADIUS + 1); b.wx = c.take<double>(2 * ECSEG_RESCALE_MAX_RADIUS + 1);
+    return b;
+}
+// Device buffers of one up-scaling of an H x W mask to oh x ow: the input `cleaned`, the warped values v, mm (~min and max of v as
+// bit patterns), par and sz and out (the final 0 / 255 mask).
+struct RescaleUpBufs { double* v; unsigned long long* mm; int32_t* par; int32_t* sz; uint8_t* out; uint8_t* cleaned; };
+inline RescaleUpBufs rescale_up_bufs(Carver& c, int H, int W, int oh, int ow) {
+    const size_t opx = (size_t)oh * ow;
+    RescaleUpBufs b;
+    b.cleaned = c.take<uint8_t>((size_t)H * W); b.out = c.take<uint8_t>(opx); b.par = c.take<int32_t>(opx); b.sz = c.take<int32_t>(opx);
+    b.v = c.take<double>(opx); b.mm = c.take<unsigned long long>(2);
+    return b;
+}
 // cleaned (H, W) uint8 on the device, oh >= H, ow >= W, oh * ow < 2^31.
 hipError_t run_rescale_mask_up(const uint8_t* cleaned, int H, int W, int oh, int ow, int nuclei_size_t, const RescaleUpBufs& b, hipStream_t s);
 

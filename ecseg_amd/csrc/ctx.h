@@ -30,12 +30,12 @@ struct DevBuf {
     ~DevBuf() { if (p) (void)hipFree(p); }
     void swap(DevBuf& o) { std::swap(p, o.p); std::swap(cap, o.cap); }
     operator T*() const { return p; }
-    int ensure(ecseg_ctx* h, size_t need_elems) {
+    int ensure(ecseg_ctx* h, size_t need_elems, const char* what = "hipMalloc") {
         if (need_elems <= cap && p) return ECSEG_OK;
         if (p) { hipError_t e = hipFree(p); p = nullptr; cap = 0; if (e != hipSuccess) return fail_hip(h, e, "hipFree"); }
         if (need_elems == 0) need_elems = 1;
         hipError_t e = hipMalloc(reinterpret_cast<void**>(&p), need_elems * sizeof(T));
-        if (e != hipSuccess) { p = nullptr; return fail(h, ECSEG_E_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e)); }
+        if (e != hipSuccess) { p = nullptr; return fail(h, ECSEG_E_NOMEM, std::string(what) + ": " + hipGetErrorString(e)); }
         cap = need_elems;
         return ECSEG_OK;
     }
@@ -92,14 +92,6 @@ struct StitchPlan {
 // Window lanes (round 4): windows [w0, w0 + cnt) of a batch on stream `s` (run_plan)
 struct LaneSpec { int w0, cnt; hipStream_t s; };
 
-// The clean-up workspace: the plain struct the kernels' launchers take, freed with the handle's device memory
-void free_post_workspace(PostWorkspace& w);        // the one place that lists its pointers
-struct OwnedPostWorkspace : PostWorkspace {
-    OwnedPostWorkspace() : PostWorkspace{} {}
-    OwnedPostWorkspace(OwnedPostWorkspace&& o) noexcept : PostWorkspace(o) { static_cast<PostWorkspace&>(o) = PostWorkspace{}; }
-    ~OwnedPostWorkspace() { free_post_workspace(*this); }
-};
-
 // Every device allocation of the handle that outlives a call, apart from the model's (free_model).  A base of ecseg_ctx, so
 // that the code says h->d_gray; ecseg_destroy moves it out and lets it die BEFORE the streams go.  A buffer added here is
 // released with the rest: there is no list of names to keep.
@@ -116,53 +108,12 @@ struct DevMem {
     DevBuf<long long> d_i64;
     DevBuf<float> d_probs_in;
     DevBuf<uint32_t> d_hist;
-    OwnedPostWorkspace ws;
-    // interSeg driver (ecseg_nuclei_regions -> ecseg_nucleus_crops): the region label map and the image stay here between the calls
-    DevBuf<int32_t> d_iseg_lab, d_iseg_rid, d_iseg_blk, d_iseg_misc, d_iseg_bb, d_iseg_desc, d_iseg_max;
-    DevBuf<uint8_t> d_iseg_img, d_iseg_crops;
-    DevBuf<unsigned long long> d_iseg_acc;
-    DevBuf<int64_t> d_iseg_rec;
-    // ecseg_fish_distances and ecseg_fish_spots: the label map, the image and the dense cell index of the call (buffers of their
-    // own: a region map left by ecseg_nuclei_regions stays valid)
-    DevBuf<int32_t> d_cell_lab, d_cell_rid, d_cell_blk, d_cell_misc;
-    DevBuf<uint8_t> d_cell_img;
-    // ecseg_fish_distances
-    DevBuf<int32_t> d_fd_par, d_fd_val, d_fd_off, d_fd_cur, d_fd_proots;
-    DevBuf<int2> d_fd_flist, d_fd_clist;
-    DevBuf<unsigned> d_fd_acc;
-    DevBuf<int64_t> d_fd_rec;
-    DevBuf<unsigned long long> d_fd_pbest;
-    // ecseg_fish_spots
-    DevBuf<int32_t> d_fs_mx, d_fs_par, d_fs_sz, d_fs_val;
-    DevBuf<uint8_t> d_fs_thr, d_fs_bnd;
-    DevBuf<double> d_fs_w;
-    DevBuf<unsigned long long> d_fs_acc;
-    DevBuf<unsigned> d_fs_cnt;
-    DevBuf<int64_t> d_fs_rec;
-    // ecseg_min_cut: the packed windows, their sides, the task table and the state of the windows too large for LDS
-    DevBuf<uint8_t> d_mc_mask, d_mc_side, d_mc_scratch;
-    DevBuf<int32_t> d_mc_desc, d_mc_flow;
-    DevBuf<long long> d_mc_soff;
-    // ecseg_nuset_forward / ecseg_rpn_proposals: the mask, the host-given RPN tensors and reference anchors, and the proposal layer's state
-    DevBuf<uint8_t> d_nu_mask;
-    DevBuf<float> d_nu_cls, d_nu_bbox, d_nu_scores, d_nu_oscores;
-    DevBuf<double> d_nu_ref;
-    DevBuf<float4> d_nu_boxes, d_nu_oboxes;
-    DevBuf<unsigned long long> d_nu_keys, d_nu_mat;
-    DevBuf<int32_t> d_nu_misc, d_nu_oidx;
-    // ecseg_clean_nuclei
-    DevBuf<uint8_t> d_cl_mask, d_cl_tmp, d_cl_cleaned, d_cl_out;
-    DevBuf<int32_t> d_cl_par, d_cl_sz, d_cl_misc;
-    DevBuf<double> d_cl_dbl;
-    // ecseg_marker_watershed (par, sz, misc and the mask are those of ecseg_clean_nuclei)
-    DevBuf<int32_t> d_ws_idx, d_ws_rw, d_ws_g, d_ws_d2, d_ws_lab, d_ws_mk;
-    DevBuf<uint8_t> d_ws_work, d_ws_filled;
-    DevBuf<unsigned long long> d_ws_hk;
-    DevBuf<int2> d_ws_hp;
-    // ecseg_rescale_down and ecseg_rescale_mask_up (par, sz, out and the mask are those of ecseg_clean_nuclei)
-    DevBuf<uint8_t> d_rs_tmp, d_rs_filtered;
-    DevBuf<double> d_rs_w, d_rs_v;
-    DevBuf<unsigned long long> d_rs_mm;
+    // The drivers' scratch: each call lays its buffers out in an arena with the layout functions of common.h (lay_out below) and relies
+    // on nothing an earlier call left there.  An arena grows to the largest need it has met and never shrinks.
+    DevBuf<uint8_t> post_arena;   // the clean-up workspace `ws` (ensure_post)
+    DevBuf<uint8_t> call_arena;   // everything a driver can size before its first launch
+    DevBuf<uint8_t> count_arena;  // the FISH drivers: what is sized by the cell count, read back while call_arena is in use
+    DevBuf<uint8_t> keep_arena;   // `iseg`, left by ecseg_nuclei_regions for ecseg_nucleus_crops: no other driver touches it
 };
 
 }  // namespace ecseg
@@ -199,6 +150,8 @@ struct ecseg_ctx : ecseg::DevMem {
     hipStream_t stream_in = nullptr;
     hipEvent_t ev_pre = nullptr;
     int min_cut_lds_pixels = ECSEG_MIN_CUT_LDS_PIXELS;   // windows above this many pixels keep their state in global memory (tests lower it)
+    ecseg::PostWorkspace ws{};       // carved from post_arena
+    ecseg::RegionMapBufs iseg{};     // carved from keep_arena
     int iseg_H = 0, iseg_W = 0, iseg_img_w = 0, iseg_C = 0, iseg_n = -1;   // iseg_n < 0: no region map on the handle
     int nuset_cls_t = -1, nuset_bbox_t = -1;   // the RPN tensors the last ecseg_nuset_forward left in the plan's buffers (-1: none)
     int post_chunk = 64;
@@ -241,6 +194,18 @@ inline TView view_of(const ecseg_ctx* h, int t) {
 inline float stage_elapsed(hipEvent_t a, hipEvent_t b) {
     float t = 0.f;
     return hipEventElapsedTime(&t, a, b) == hipSuccess ? t : 0.f;
+}
+
+// Measure, ensure, place: runs `layout` (which fills the caller's *Bufs through the layout functions of common.h) on a measuring
+// Carver, grows `arena` to that size if it holds less, and runs it again on the arena.  When the allocation fails the *Bufs are
+// left holding the measuring pass's bare offsets: a caller that keeps them on the handle (ws, iseg) marks them invalid itself.
+template <typename F>
+int lay_out(ecseg_ctx* h, DevBuf<uint8_t>& arena, F&& layout, const char* what = "hipMalloc") {
+    Carver measure, place;
+    layout(measure);
+    if (int rc = arena.ensure(h, measure.used, what)) return rc;
+    layout(place = Carver(arena.p));
+    return ECSEG_OK;
 }
 
 // Images named or sent ahead by ecseg_prefetch_input belong to the very next ecseg_meta_segment call: any other call on the handle

@@ -186,29 +186,22 @@ int ecseg_nuclei_regions(ecseg_ctx* h, const uint8_t* seg, int H, int W, const u
     if ((long long)H * W >= (1ll << 31) || (long long)H * img_w * C >= (1ll << 40)) return fail(h, ECSEG_E_INVALID, "image too large");
     HIP_TRY(h, hipSetDevice(h->device));
     const size_t px = (size_t)H * W, img_bytes = (size_t)H * img_w * C;
-    const size_t nb = (px + 1023) / 1024, cap = (size_t)capacity;
     int rc;
+    RegionBufs b{};
     if ((rc = ensure_post(h, 1, px))) return rc;
     if ((rc = h->d_gray.ensure(h, px))) return rc;
-    if ((rc = h->d_iseg_lab.ensure(h, px))) return rc;
-    if ((rc = h->d_iseg_img.ensure(h, img_bytes))) return rc;
-    if ((rc = h->d_iseg_rid.ensure(h, px))) return rc;
-    if ((rc = h->d_iseg_blk.ensure(h, nb))) return rc;
-    if ((rc = h->d_iseg_misc.ensure(h, 4))) return rc;
-    if ((rc = h->d_iseg_acc.ensure(h, cap * 4))) return rc;
-    if ((rc = h->d_iseg_bb.ensure(h, cap * 4))) return rc;
-    if ((rc = h->d_iseg_rec.ensure(h, cap * 8))) return rc;
+    if ((rc = lay_out(h, h->keep_arena, [&](Carver& c) { h->iseg = region_map_bufs(c, H, W, img_w, C); }))) return rc;
+    if ((rc = lay_out(h, h->call_arena, [&](Carver& c) { b = region_bufs(c, H, W, capacity); }))) return rc;
     hipStream_t s = h->stream;
     for (float& v : h->stage_ms) v = 0.f;
     HIP_TRY(h, hipMemcpyAsync(h->d_gray, seg, px, hipMemcpyHostToDevice, s));
-    HIP_TRY(h, hipMemcpyAsync(h->d_iseg_img, img, img_bytes, hipMemcpyHostToDevice, s));   // the first H rows: I[:imheight, :imwidth]
+    HIP_TRY(h, hipMemcpyAsync(h->iseg.img, img, img_bytes, hipMemcpyHostToDevice, s));   // the first H rows: I[:imheight, :imwidth]
     HIP_TRY(h, hipEventRecord(h->ev[0], s));
-    HIP_TRY(h, run_ccl_labels(h->ws, h->d_gray, 1, H, W, 8, h->d_iseg_lab, s));
-    const RegionBufs b{h->d_iseg_rid, h->d_iseg_blk, h->d_iseg_misc, h->d_iseg_acc, h->d_iseg_bb, h->d_iseg_rec, capacity};
-    HIP_TRY(h, run_nuclei_regions(h->d_gray, h->d_iseg_img, H, W, img_w, C, channel0, h->d_iseg_lab, b, s));
+    HIP_TRY(h, run_ccl_labels(h->ws, h->d_gray, 1, H, W, 8, h->iseg.lab, s));
+    HIP_TRY(h, run_nuclei_regions(h->d_gray, h->iseg.img, H, W, img_w, C, channel0, h->iseg.lab, b, s));
     HIP_TRY(h, hipEventRecord(h->ev[1], s));
     int32_t misc[4];
-    HIP_TRY(h, hipMemcpyAsync(misc, h->d_iseg_misc, sizeof(misc), hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipMemcpyAsync(misc, b.misc, sizeof(misc), hipMemcpyDeviceToHost, s));
     HIP_TRY(h, hipStreamSynchronize(s));
     h->stage_ms[ECSEG_T_COUNT] = stage_elapsed(h->ev[0], h->ev[1]);
     const int n = misc[0], vmax = misc[1], vmin = 255 - misc[2];
@@ -217,7 +210,7 @@ int ecseg_nuclei_regions(ecseg_ctx* h, const uint8_t* seg, int H, int W, const u
                                             ": only 0 / non-zero nucleus masks are supported, not instance-id maps");
     *n_regions = n;
     if (n <= capacity && n > 0) {
-        HIP_TRY(h, hipMemcpyAsync(records, h->d_iseg_rec, (size_t)n * 8 * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipMemcpyAsync(records, b.rec, (size_t)n * 8 * sizeof(int64_t), hipMemcpyDeviceToHost, s));
         HIP_TRY(h, hipStreamSynchronize(s));
     }
     h->iseg_H = H; h->iseg_W = W; h->iseg_img_w = img_w; h->iseg_C = C; h->iseg_n = n;
@@ -248,20 +241,18 @@ int ecseg_nucleus_crops(ecseg_ctx* h, const int32_t* crops, int n_crops, const i
     const size_t crop_bytes = (size_t)256 * 256 * 3;
     const int nc = std::min(n_crops, chunk);
     int rc;
-    if ((rc = h->d_iseg_desc.ensure(h, (size_t)nc * 5))) return rc;
-    if ((rc = h->d_iseg_crops.ensure(h, (size_t)nc * crop_bytes))) return rc;
-    if ((rc = h->d_iseg_max.ensure(h, (size_t)nc * 3))) return rc;
+    CropBufs b{};
+    if ((rc = lay_out(h, h->call_arena, [&](Carver& c) { b = crop_bufs(c, nc); }))) return rc;
     hipStream_t s = h->stream;
     for (float& v : h->stage_ms) v = 0.f;
     for (int k0 = 0; k0 < n_crops; k0 += chunk) {
         const int k = std::min(chunk, n_crops - k0);
-        HIP_TRY(h, hipMemcpyAsync(h->d_iseg_desc, crops + (size_t)k0 * 5, (size_t)k * 5 * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        HIP_TRY(h, hipMemcpyAsync(b.desc, crops + (size_t)k0 * 5, (size_t)k * 5 * sizeof(int32_t), hipMemcpyHostToDevice, s));
         HIP_TRY(h, hipEventRecord(h->ev[0], s));
-        HIP_TRY(h, run_nucleus_crops(h->d_iseg_lab, h->d_iseg_img, h->iseg_W, h->iseg_img_w, h->iseg_C, h->d_iseg_desc, k, order,
-                                     h->d_iseg_crops, h->d_iseg_max, s));
+        HIP_TRY(h, run_nucleus_crops(h->iseg.lab, h->iseg.img, h->iseg_W, h->iseg_img_w, h->iseg_C, b.desc, k, order, b.crops, b.max, s));
         HIP_TRY(h, hipEventRecord(h->ev[1], s));
-        HIP_TRY(h, hipMemcpyAsync(out + (size_t)k0 * crop_bytes, h->d_iseg_crops, (size_t)k * crop_bytes, hipMemcpyDeviceToHost, s));
-        HIP_TRY(h, hipMemcpyAsync(channel_max + (size_t)k0 * 3, h->d_iseg_max, (size_t)k * 3 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipMemcpyAsync(out + (size_t)k0 * crop_bytes, b.crops, (size_t)k * crop_bytes, hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipMemcpyAsync(channel_max + (size_t)k0 * 3, b.max, (size_t)k * 3 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
         HIP_TRY(h, hipStreamSynchronize(s));
         h->stage_ms[ECSEG_T_COUNT] += stage_elapsed(h->ev[0], h->ev[1]);
     }
@@ -269,24 +260,21 @@ int ecseg_nucleus_crops(ecseg_ctx* h, const int32_t* crops, int n_crops, const i
 }
 
 // The opening phase of ecseg_fish_distances and ecseg_fish_spots: the label map and the image on the device, the dense cell index
-// (stage_ms[ECSEG_T_COUNT] = its device time) and the number of cells.  `who` prefixes the refusal of a label above H * W.
-static int open_dense_cells(ecseg_ctx* h, const char* who, const int32_t* labels, int H, int W, const uint8_t* img, int C, int32_t* n_cells) {
+// (stage_ms[ECSEG_T_COUNT] = its device time) and the number of cells.  `who` prefixes the refusal of a label above H * W.  `b`
+// lies in the call arena: what the caller sizes by the cell count goes to the count arena.
+static int open_dense_cells(ecseg_ctx* h, const char* who, const int32_t* labels, int H, int W, const uint8_t* img, int C, CellIndexBufs& b,
+                            int32_t* n_cells) {
     const size_t px = (size_t)H * W;
-    int rc;
-    if ((rc = h->d_cell_lab.ensure(h, px))) return rc;
-    if ((rc = h->d_cell_img.ensure(h, px * C))) return rc;
-    if ((rc = h->d_cell_rid.ensure(h, px))) return rc;
-    if ((rc = h->d_cell_blk.ensure(h, (px + 1023) / 1024))) return rc;
-    if ((rc = h->d_cell_misc.ensure(h, 4))) return rc;
+    if (int rc = lay_out(h, h->call_arena, [&](Carver& c) { b = cell_index_bufs(c, H, W, C); })) return rc;
     hipStream_t s = h->stream;
     for (float& v : h->stage_ms) v = 0.f;
-    HIP_TRY(h, hipMemcpyAsync(h->d_cell_lab, labels, px * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    HIP_TRY(h, hipMemcpyAsync(h->d_cell_img, img, px * C, hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(b.lab, labels, px * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(b.img, img, px * C, hipMemcpyHostToDevice, s));
     HIP_TRY(h, hipEventRecord(h->ev[0], s));
-    HIP_TRY(h, run_dense_cells(h->d_cell_lab, H, W, CellIndexBufs{h->d_cell_rid, h->d_cell_blk, h->d_cell_misc}, s));
+    HIP_TRY(h, run_dense_cells(b.lab, H, W, b, s));
     HIP_TRY(h, hipEventRecord(h->ev[1], s));
     int32_t misc[4];
-    HIP_TRY(h, hipMemcpyAsync(misc, h->d_cell_misc, sizeof(misc), hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipMemcpyAsync(misc, b.misc, sizeof(misc), hipMemcpyDeviceToHost, s));
     HIP_TRY(h, hipStreamSynchronize(s));
     h->stage_ms[ECSEG_T_COUNT] = stage_elapsed(h->ev[0], h->ev[1]);
     if (misc[3])
@@ -310,31 +298,19 @@ int ecseg_fish_distances(ecseg_ctx* h, const int32_t* labels, int H, int W, cons
     if ((long long)H * W >= (1ll << 31) || (long long)H * W * C >= (1ll << 40))
         return fail(h, ECSEG_E_INVALID, "fish_distances: image too large (H * W must be below 2^31, H * W * C below 2^40)");
     HIP_TRY(h, hipSetDevice(h->device));
-    const size_t px = (size_t)H * W;
     int rc;
-    if ((rc = open_dense_cells(h, "fish_distances", labels, H, W, lsq, C, n_cells))) return rc;
+    CellIndexBufs cells{};
+    if ((rc = open_dense_cells(h, "fish_distances", labels, H, W, lsq, C, cells, n_cells))) return rc;
     const int n = *n_cells;
     if (n == 0 || n > capacity) return ECSEG_OK;             // the cell count alone: the caller comes back with a larger buffer
     // the rest is sized by the number of cells, which is known only now
-    const size_t nn = (size_t)n;
-    if ((rc = h->d_fd_par.ensure(h, px))) return rc;
-    if ((rc = h->d_fd_flist.ensure(h, px))) return rc;
-    if ((rc = h->d_fd_clist.ensure(h, px))) return rc;
-    if ((rc = h->d_fd_acc.ensure(h, nn * 4))) return rc;
-    if ((rc = h->d_fd_val.ensure(h, nn))) return rc;
-    if ((rc = h->d_fd_off.ensure(h, nn * 2))) return rc;
-    if ((rc = h->d_fd_cur.ensure(h, nn * 2))) return rc;
-    if ((rc = h->d_fd_rec.ensure(h, nn * 8))) return rc;
-    const size_t parts = nn * (size_t)fishdist_slices(n);
-    if ((rc = h->d_fd_pbest.ensure(h, parts))) return rc;
-    if ((rc = h->d_fd_proots.ensure(h, parts))) return rc;
+    FishDistBufs b{};
+    if ((rc = lay_out(h, h->count_arena, [&](Carver& c) { b = fishdist_bufs(c, cells, H, W, n, fishdist_slices(n)); }))) return rc;
     hipStream_t s = h->stream;
-    const FishDistBufs b{h->d_cell_rid, h->d_fd_par, h->d_cell_blk, h->d_cell_misc, h->d_fd_flist, h->d_fd_clist, h->d_fd_acc, h->d_fd_val,
-                         h->d_fd_off, h->d_fd_cur, h->d_fd_rec, h->d_fd_pbest, h->d_fd_proots};
     HIP_TRY(h, hipEventRecord(h->ev[2], s));
-    HIP_TRY(h, run_fishdist_records(h->d_cell_lab, h->d_cell_img, H, W, C, fish_channel, centromere_channel, n, b, s));
+    HIP_TRY(h, run_fishdist_records(cells.lab, cells.img, H, W, C, fish_channel, centromere_channel, n, b, s));
     HIP_TRY(h, hipEventRecord(h->ev[3], s));
-    HIP_TRY(h, hipMemcpyAsync(records, h->d_fd_rec, nn * 8 * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipMemcpyAsync(records, b.rec, (size_t)n * 8 * sizeof(int64_t), hipMemcpyDeviceToHost, s));
     HIP_TRY(h, hipStreamSynchronize(s));
     h->stage_ms[ECSEG_T_COUNT] += stage_elapsed(h->ev[2], h->ev[3]);
     return ECSEG_OK;
@@ -369,7 +345,8 @@ int ecseg_fish_spots(ecseg_ctx* h, const int32_t* labels, int H, int W, const ui
     HIP_TRY(h, hipSetDevice(h->device));
     const size_t px = (size_t)H * W, np = (size_t)n_probe;
     int rc;
-    if ((rc = open_dense_cells(h, "fish_spots", labels, H, W, img, C, n_cells))) return rc;
+    CellIndexBufs cells{};
+    if ((rc = open_dense_cells(h, "fish_spots", labels, H, W, img, C, cells, n_cells))) return rc;
     const int n = *n_cells;
     if (n > capacity) return ECSEG_OK;                       // the cell count alone: the caller comes back with a larger buffer
     if (n == 0) {                                            // no cell: nothing is thresholded and no rank differs from 0
@@ -377,28 +354,16 @@ int ecseg_fish_spots(ecseg_ctx* h, const int32_t* labels, int H, int W, const ui
         std::fill(boundaries, boundaries + px, (uint8_t)0);
         return ECSEG_OK;
     }
-    const size_t nn = (size_t)n;
-    if ((rc = h->d_fs_mx.ensure(h, 4))) return rc;
-    if ((rc = h->d_fs_w.ensure(h, (size_t)K * K))) return rc;
-    if ((rc = h->d_fs_thr.ensure(h, px * np))) return rc;
-    if ((rc = h->d_fs_bnd.ensure(h, px))) return rc;
-    if ((rc = h->d_fs_par.ensure(h, px * 4))) return rc;
-    if ((rc = h->d_fs_sz.ensure(h, px * 4))) return rc;
-    if ((rc = h->d_fs_acc.ensure(h, nn * 12))) return rc;
-    if ((rc = h->d_fs_cnt.ensure(h, nn * 8))) return rc;
-    if ((rc = h->d_fs_val.ensure(h, nn))) return rc;
-    if ((rc = h->d_fs_rec.ensure(h, nn * ECSEG_FISH_SPOT_INT64))) return rc;
+    FishSpotBufs b{};
+    if ((rc = lay_out(h, h->count_arena, [&](Carver& c) { b = fishspot_bufs(c, cells, H, W, n_probe, K, n); }))) return rc;
     hipStream_t s = h->stream;
-    HIP_TRY(h, hipMemcpyAsync(h->d_fs_w, weights, (size_t)K * K * sizeof(double), hipMemcpyHostToDevice, s));
-    const FishSpotBufs b{h->d_cell_rid, h->d_fs_mx, h->d_fs_thr, h->d_fs_bnd, h->d_fs_par, h->d_fs_sz, h->d_fs_acc, h->d_fs_cnt, h->d_fs_val,
-                         h->d_fs_rec};
+    HIP_TRY(h, hipMemcpyAsync(b.w, weights, (size_t)K * K * sizeof(double), hipMemcpyHostToDevice, s));
     HIP_TRY(h, hipEventRecord(h->ev[2], s));
-    HIP_TRY(h, run_fishspot(h->d_cell_lab, h->d_cell_img, H, W, C, n_probe, ch, h->d_fs_w, K, normal_threshold, ithr, min_cc_size,
-                            line_thickness, n, b, s));
+    HIP_TRY(h, run_fishspot(cells.lab, cells.img, H, W, C, n_probe, ch, b.w, K, normal_threshold, ithr, min_cc_size, line_thickness, n, b, s));
     HIP_TRY(h, hipEventRecord(h->ev[3], s));
-    HIP_TRY(h, hipMemcpyAsync(thresholded, h->d_fs_thr, px * np, hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipMemcpyAsync(boundaries, h->d_fs_bnd, px, hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipMemcpyAsync(records, h->d_fs_rec, nn * ECSEG_FISH_SPOT_INT64 * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipMemcpyAsync(thresholded, b.thr, px * np, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipMemcpyAsync(boundaries, b.bnd, px, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipMemcpyAsync(records, b.rec, (size_t)n * ECSEG_FISH_SPOT_INT64 * sizeof(int64_t), hipMemcpyDeviceToHost, s));
     HIP_TRY(h, hipStreamSynchronize(s));
     h->stage_ms[ECSEG_T_COUNT] += stage_elapsed(h->ev[2], h->ev[3]);
     return ECSEG_OK;
@@ -444,22 +409,18 @@ int ecseg_min_cut(ecseg_ctx* h, const uint8_t* masks, long long mask_bytes, cons
     HIP_TRY(h, hipSetDevice(h->device));
     const size_t nb = (size_t)mask_bytes, nt = (size_t)n_tasks;
     int rc;
-    if ((rc = h->d_mc_mask.ensure(h, nb))) return rc;
-    if ((rc = h->d_mc_side.ensure(h, nb))) return rc;
-    if ((rc = h->d_mc_desc.ensure(h, nt * 8))) return rc;
-    if ((rc = h->d_mc_soff.ensure(h, nt))) return rc;
-    if ((rc = h->d_mc_flow.ensure(h, nt))) return rc;
-    if ((rc = h->d_mc_scratch.ensure(h, scratch))) return rc;
+    MinCutBufs b{};
+    if ((rc = lay_out(h, h->call_arena, [&](Carver& c) { b = mincut_bufs(c, nb, n_tasks, scratch); }))) return rc;
     hipStream_t s = h->stream;
-    HIP_TRY(h, hipMemcpyAsync(h->d_mc_mask, masks, nb, hipMemcpyHostToDevice, s));
-    HIP_TRY(h, hipMemcpyAsync(h->d_mc_desc, tasks, nt * 8 * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    HIP_TRY(h, hipMemcpyAsync(h->d_mc_soff, soff.data(), nt * sizeof(long long), hipMemcpyHostToDevice, s));
-    HIP_TRY(h, hipMemsetAsync(h->d_mc_side, 0, nb, s));
+    HIP_TRY(h, hipMemcpyAsync(b.mask, masks, nb, hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(b.desc, tasks, nt * 8 * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(b.soff, soff.data(), nt * sizeof(long long), hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemsetAsync(b.side, 0, nb, s));
     HIP_TRY(h, hipEventRecord(h->ev[0], s));
-    HIP_TRY(h, run_mincut(h->d_mc_mask, h->d_mc_desc, h->d_mc_soff, n_tasks, n_global, dist, h->d_mc_scratch, h->d_mc_side, h->d_mc_flow, s));
+    HIP_TRY(h, run_mincut(b.mask, b.desc, b.soff, n_tasks, n_global, dist, b.scratch, b.side, b.flow, s));
     HIP_TRY(h, hipEventRecord(h->ev[1], s));
-    HIP_TRY(h, hipMemcpyAsync(side, h->d_mc_side, nb, hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipMemcpyAsync(flow, h->d_mc_flow, nt * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipMemcpyAsync(side, b.side, nb, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipMemcpyAsync(flow, b.flow, nt * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     HIP_TRY(h, hipStreamSynchronize(s));                     // (soff is read by the copy above: it lives until here)
     h->stage_ms[ECSEG_T_COUNT] = stage_elapsed(h->ev[0], h->ev[1]);
     return ECSEG_OK;
@@ -491,16 +452,17 @@ int ecseg_nuset_forward(ecseg_ctx* h, const float* x, int H, int W, int cls_tens
     HIP_TRY(h, hipSetDevice(h->device));
     const size_t px = (size_t)H * W;
     if ((rc = ensure_patches(h, 1))) return rc;
-    if ((rc = h->d_nu_mask.ensure(h, px))) return rc;
+    NusetMaskBufs b{};
+    if ((rc = lay_out(h, h->call_arena, [&](Carver& c) { b = nuset_mask_bufs(c, H, W); }))) return rc;
     hipStream_t s = h->stream;
     for (float& v : h->stage_ms) v = 0.f;
     prof_begin(h);
     HIP_TRY(h, hipMemcpyAsync(view_of(h, h->input_tensor).p, x, px * sizeof(float), hipMemcpyHostToDevice, s));
     HIP_TRY(h, hipEventRecord(h->ev[0], s));
     if ((rc = run_plan(h, 1))) return rc;
-    HIP_TRY(h, launch_argmax2(view_of(h, h->output_tensor), h->d_nu_mask, s));
+    HIP_TRY(h, launch_argmax2(view_of(h, h->output_tensor), b.mask, s));
     HIP_TRY(h, hipEventRecord(h->ev[1], s));
-    HIP_TRY(h, hipMemcpyAsync(mask, h->d_nu_mask, px, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipMemcpyAsync(mask, b.mask, px, hipMemcpyDeviceToHost, s));
     HIP_TRY(h, hipStreamSynchronize(s));
     prof_end(h);
     h->stage_ms[ECSEG_T_UNET] = stage_elapsed(h->ev[0], h->ev[1]);
@@ -522,43 +484,33 @@ static int rpn_driver(ecseg_ctx* h, const float* d_cls, int cls_cs, const float*
     if (post < 1 || stride < 1 || (long long)stride * std::max(fh, fw) >= (1ll << 31))
         return fail(h, ECSEG_E_INVALID, "rpn_proposals: post_nms_top_n and stride must be positive");
     HIP_TRY(h, hipSetDevice(h->device));
-    const size_t N = (size_t)fh * fw * A, K = std::min<size_t>((size_t)pre, N), words = (K + 63) / 64, no = std::min<size_t>((size_t)post, K);
+    const size_t N = (size_t)fh * fw * A, K = std::min<size_t>((size_t)pre, N), no = std::min<size_t>((size_t)post, K);
     int rc;
-    if ((rc = h->d_nu_ref.ensure(h, (size_t)A * 4))) return rc;
-    if ((rc = h->d_nu_boxes.ensure(h, N))) return rc;
-    if ((rc = h->d_nu_scores.ensure(h, N))) return rc;
-    if ((rc = h->d_nu_keys.ensure(h, (size_t)rpn_sort_len((int)N)))) return rc;
-    if ((rc = h->d_nu_mat.ensure(h, K * words))) return rc;
-    if ((rc = h->d_nu_misc.ensure(h, 2))) return rc;
-    if ((rc = h->d_nu_oscores.ensure(h, no))) return rc;
-    if ((rc = h->d_nu_oboxes.ensure(h, no))) return rc;
-    if ((rc = h->d_nu_oidx.ensure(h, no))) return rc;
+    RpnBufs b{};
+    if ((rc = lay_out(h, h->call_arena, [&](Carver& c) { b = rpn_bufs(c, fh, fw, A, rpn_sort_len((int)N), pre, post, !d_cls); }))) return rc;
     hipStream_t s = h->stream;
     for (float& v : h->stage_ms) v = 0.f;
     if (!d_cls) {
         const size_t px = (size_t)fh * fw;
-        if ((rc = h->d_nu_cls.ensure(h, px * 2 * A))) return rc;
-        if ((rc = h->d_nu_bbox.ensure(h, px * 4 * A))) return rc;
-        HIP_TRY(h, hipMemcpyAsync(h->d_nu_cls, cls_host, px * 2 * A * sizeof(float), hipMemcpyHostToDevice, s));
-        HIP_TRY(h, hipMemcpyAsync(h->d_nu_bbox, bbox_host, px * 4 * A * sizeof(float), hipMemcpyHostToDevice, s));
-        d_cls = h->d_nu_cls; cls_cs = 2 * A; d_bbox = h->d_nu_bbox; bbox_cs = 4 * A;
+        HIP_TRY(h, hipMemcpyAsync(b.cls, cls_host, px * 2 * A * sizeof(float), hipMemcpyHostToDevice, s));
+        HIP_TRY(h, hipMemcpyAsync(b.bbox, bbox_host, px * 4 * A * sizeof(float), hipMemcpyHostToDevice, s));
+        d_cls = b.cls; cls_cs = 2 * A; d_bbox = b.bbox; bbox_cs = 4 * A;
     }
-    HIP_TRY(h, hipMemcpyAsync(h->d_nu_ref, ref_anchors, (size_t)A * 4 * sizeof(double), hipMemcpyHostToDevice, s));
-    const RpnBufs b{h->d_nu_boxes, h->d_nu_scores, h->d_nu_keys, h->d_nu_mat, h->d_nu_misc, h->d_nu_oscores, h->d_nu_oboxes, h->d_nu_oidx};
+    HIP_TRY(h, hipMemcpyAsync(b.ref, ref_anchors, (size_t)A * 4 * sizeof(double), hipMemcpyHostToDevice, s));
     HIP_TRY(h, hipEventRecord(h->ev[0], s));
-    HIP_TRY(h, run_rpn_proposals(d_cls, cls_cs, d_bbox, bbox_cs, h->d_nu_ref, fh, fw, A, stride, im_h, im_w, nms_threshold, pre, (int)no, b, s));
+    HIP_TRY(h, run_rpn_proposals(d_cls, cls_cs, d_bbox, bbox_cs, b.ref, fh, fw, A, stride, im_h, im_w, nms_threshold, pre, (int)no, b, s));
     HIP_TRY(h, hipEventRecord(h->ev[1], s));
     int32_t misc[2];
-    HIP_TRY(h, hipMemcpyAsync(misc, h->d_nu_misc, sizeof(misc), hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipMemcpyAsync(misc, b.misc, sizeof(misc), hipMemcpyDeviceToHost, s));
     HIP_TRY(h, hipStreamSynchronize(s));                      // (ref_anchors is read by the copy above: it lives until here)
     h->stage_ms[ECSEG_T_COUNT] = stage_elapsed(h->ev[0], h->ev[1]);
     const int n = misc[0];
     if (n < 0 || (size_t)n > no) return fail(h, ECSEG_E_HIP, "rpn_proposals: the device reported an impossible count");
     *n_out = n;
     if (n > 0) {
-        HIP_TRY(h, hipMemcpyAsync(scores, h->d_nu_oscores, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, s));
-        HIP_TRY(h, hipMemcpyAsync(proposals, h->d_nu_oboxes, (size_t)n * 4 * sizeof(float), hipMemcpyDeviceToHost, s));
-        HIP_TRY(h, hipMemcpyAsync(indices, h->d_nu_oidx, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipMemcpyAsync(scores, b.out_scores, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipMemcpyAsync(proposals, b.out_boxes, (size_t)n * 4 * sizeof(float), hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipMemcpyAsync(indices, b.out_idx, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
         HIP_TRY(h, hipStreamSynchronize(s));
     }
     return ECSEG_OK;
@@ -610,38 +562,22 @@ int ecseg_marker_watershed(ecseg_ctx* h, const uint8_t* mask, int H, int W, cons
     const int cap = (int)(5 * fg + 1);
     HIP_TRY(h, hipSetDevice(h->device));
     int rc;
-    if ((rc = h->d_cl_mask.ensure(h, px))) return rc;
-    if ((rc = h->d_cl_out.ensure(h, px))) return rc;
-    if ((rc = h->d_cl_par.ensure(h, px))) return rc;
-    if ((rc = h->d_cl_sz.ensure(h, px))) return rc;
-    if ((rc = h->d_cl_misc.ensure(h, 4))) return rc;
-    if ((rc = h->d_ws_idx.ensure(h, px))) return rc;
-    if ((rc = h->d_ws_rw.ensure(h, px))) return rc;
-    if ((rc = h->d_ws_g.ensure(h, px))) return rc;
-    if ((rc = h->d_ws_d2.ensure(h, px))) return rc;
-    if ((rc = h->d_ws_lab.ensure(h, px))) return rc;
-    if ((rc = h->d_ws_work.ensure(h, px))) return rc;
-    if ((rc = h->d_ws_filled.ensure(h, px))) return rc;
-    if ((rc = h->d_ws_mk.ensure(h, 3 * (size_t)std::max(n, 1)))) return rc;
-    if ((rc = h->d_ws_hk.ensure(h, (size_t)cap))) return rc;
-    if ((rc = h->d_ws_hp.ensure(h, (size_t)cap))) return rc;
+    WatershedBufs b{};
+    if ((rc = lay_out(h, h->call_arena, [&](Carver& c) { b = watershed_bufs(c, H, W, n, cap); }))) return rc;
     hipStream_t s = h->stream;
     for (float& v : h->stage_ms) v = 0.f;
-    int32_t* d_rows = h->d_ws_mk; int32_t* d_cols = d_rows + n; int32_t* d_labels = d_cols + n;
-    HIP_TRY(h, hipMemcpyAsync(h->d_cl_mask, mask, px, hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(b.mask, mask, px, hipMemcpyHostToDevice, s));
     if (n > 0) {
-        HIP_TRY(h, hipMemcpyAsync(d_rows, marker_rows, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
-        HIP_TRY(h, hipMemcpyAsync(d_cols, marker_cols, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
-        HIP_TRY(h, hipMemcpyAsync(d_labels, marker_labels, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        HIP_TRY(h, hipMemcpyAsync(b.rows, marker_rows, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        HIP_TRY(h, hipMemcpyAsync(b.cols, marker_cols, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        HIP_TRY(h, hipMemcpyAsync(b.labels, marker_labels, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
     }
-    const WatershedBufs b{h->d_ws_idx, h->d_ws_rw, h->d_ws_g, h->d_ws_d2, h->d_ws_lab, h->d_cl_par, h->d_cl_sz, h->d_ws_work, h->d_ws_filled,
-                          h->d_cl_out, h->d_cl_misc, h->d_ws_hk, h->d_ws_hp};
     HIP_TRY(h, hipEventRecord(h->ev[0], s));
-    HIP_TRY(h, run_marker_watershed(h->d_cl_mask, H, W, d_rows, d_cols, d_labels, n, cap, b, s));
+    HIP_TRY(h, run_marker_watershed(b.mask, H, W, b.rows, b.cols, b.labels, n, cap, b, s));
     HIP_TRY(h, hipEventRecord(h->ev[1], s));
     int32_t misc[4] = {0, 0, 0, 0};
-    HIP_TRY(h, hipMemcpyAsync(out, h->d_cl_out, px, hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipMemcpyAsync(misc, h->d_cl_misc, sizeof(misc), hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipMemcpyAsync(out, b.out, px, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipMemcpyAsync(misc, b.misc, sizeof(misc), hipMemcpyDeviceToHost, s));
     HIP_TRY(h, hipStreamSynchronize(s));
     h->stage_ms[ECSEG_T_COUNT] = stage_elapsed(h->ev[0], h->ev[1]);
     if (misc[1]) return fail(h, ECSEG_E_HIP, "marker_watershed: the heap overflowed its bound");
@@ -658,25 +594,18 @@ int ecseg_clean_nuclei(ecseg_ctx* h, const uint8_t* mask, int H, int W, int nucl
     HIP_TRY(h, hipSetDevice(h->device));
     const size_t px = (size_t)H * W;
     int rc;
-    if ((rc = h->d_cl_mask.ensure(h, px))) return rc;
-    if ((rc = h->d_cl_tmp.ensure(h, px))) return rc;
-    if ((rc = h->d_cl_cleaned.ensure(h, px))) return rc;
-    if ((rc = h->d_cl_out.ensure(h, px))) return rc;
-    if ((rc = h->d_cl_par.ensure(h, px))) return rc;
-    if ((rc = h->d_cl_sz.ensure(h, px))) return rc;
-    if ((rc = h->d_cl_misc.ensure(h, 4))) return rc;
-    if ((rc = h->d_cl_dbl.ensure(h, 2))) return rc;
+    CleanBufs b{};
+    if ((rc = lay_out(h, h->call_arena, [&](Carver& c) { b = clean_bufs(c, H, W); }))) return rc;
     hipStream_t s = h->stream;
     for (float& v : h->stage_ms) v = 0.f;
-    HIP_TRY(h, hipMemcpyAsync(h->d_cl_mask, mask, px, hipMemcpyHostToDevice, s));
-    const CleanBufs b{h->d_cl_par, h->d_cl_sz, h->d_cl_tmp, h->d_cl_cleaned, h->d_cl_out, h->d_cl_misc, h->d_cl_dbl};
+    HIP_TRY(h, hipMemcpyAsync(b.mask, mask, px, hipMemcpyHostToDevice, s));
     HIP_TRY(h, hipEventRecord(h->ev[0], s));
-    HIP_TRY(h, run_clean_nuclei(h->d_cl_mask, H, W, nuclei_size_t, b, s));
+    HIP_TRY(h, run_clean_nuclei(b.mask, H, W, nuclei_size_t, b, s));
     HIP_TRY(h, hipEventRecord(h->ev[1], s));
     double dbl[2] = {0.0, 0.0};
-    HIP_TRY(h, hipMemcpyAsync(out, h->d_cl_out, px, hipMemcpyDeviceToHost, s));
-    if (cleaned) HIP_TRY(h, hipMemcpyAsync(cleaned, h->d_cl_cleaned, px, hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipMemcpyAsync(dbl, h->d_cl_dbl, sizeof(dbl), hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipMemcpyAsync(out, b.out, px, hipMemcpyDeviceToHost, s));
+    if (cleaned) HIP_TRY(h, hipMemcpyAsync(cleaned, b.cleaned, px, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipMemcpyAsync(dbl, b.dbl, sizeof(dbl), hipMemcpyDeviceToHost, s));
     HIP_TRY(h, hipStreamSynchronize(s));
     if (mean_area) *mean_area = dbl[0];
     h->stage_ms[ECSEG_T_COUNT] = stage_elapsed(h->ev[0], h->ev[1]);
@@ -698,22 +627,18 @@ int ecseg_rescale_down(ecseg_ctx* h, const uint8_t* img, int H, int W, int out_h
     HIP_TRY(h, hipSetDevice(h->device));
     const size_t px = (size_t)H * W, opx = (size_t)out_h * out_w;
     int rc;
-    if ((rc = h->d_cl_mask.ensure(h, px))) return rc;
-    if ((rc = h->d_rs_tmp.ensure(h, px))) return rc;
-    if ((rc = h->d_rs_filtered.ensure(h, px))) return rc;
-    if ((rc = h->d_rs_v.ensure(h, opx))) return rc;
-    if ((rc = h->d_rs_w.ensure(h, 2 * (2 * ECSEG_RESCALE_MAX_RADIUS + 1)))) return rc;
+    RescaleDownBufs b{};
+    if ((rc = lay_out(h, h->call_arena, [&](Carver& c) { b = rescale_down_bufs(c, H, W, out_h, out_w); }))) return rc;
     hipStream_t s = h->stream;
     for (float& v : h->stage_ms) v = 0.f;
-    double* d_wy = h->d_rs_w; double* d_wx = d_wy + (2 * ECSEG_RESCALE_MAX_RADIUS + 1);
-    HIP_TRY(h, hipMemcpyAsync(h->d_cl_mask, img, px, hipMemcpyHostToDevice, s));
-    if (ry > 0) HIP_TRY(h, hipMemcpyAsync(d_wy, wy, (size_t)(2 * ry + 1) * sizeof(double), hipMemcpyHostToDevice, s));
-    if (rx > 0) HIP_TRY(h, hipMemcpyAsync(d_wx, wx, (size_t)(2 * rx + 1) * sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(b.img, img, px, hipMemcpyHostToDevice, s));
+    if (ry > 0) HIP_TRY(h, hipMemcpyAsync(b.wy, wy, (size_t)(2 * ry + 1) * sizeof(double), hipMemcpyHostToDevice, s));
+    if (rx > 0) HIP_TRY(h, hipMemcpyAsync(b.wx, wx, (size_t)(2 * rx + 1) * sizeof(double), hipMemcpyHostToDevice, s));
     HIP_TRY(h, hipEventRecord(h->ev[0], s));
-    HIP_TRY(h, run_rescale_down(h->d_cl_mask, H, W, out_h, out_w, d_wy, ry, d_wx, rx, h->d_rs_tmp, h->d_rs_filtered, h->d_rs_v, s));
+    HIP_TRY(h, run_rescale_down(b.img, H, W, out_h, out_w, b.wy, ry, b.wx, rx, b.tmp, b.filtered, b.v, s));
     HIP_TRY(h, hipEventRecord(h->ev[1], s));
-    HIP_TRY(h, hipMemcpyAsync(out, h->d_rs_v, opx * sizeof(double), hipMemcpyDeviceToHost, s));
-    if (filtered) HIP_TRY(h, hipMemcpyAsync(filtered, h->d_rs_filtered, px, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipMemcpyAsync(out, b.v, opx * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (filtered) HIP_TRY(h, hipMemcpyAsync(filtered, b.filtered, px, hipMemcpyDeviceToHost, s));
     HIP_TRY(h, hipStreamSynchronize(s));
     h->stage_ms[ECSEG_T_COUNT] = stage_elapsed(h->ev[0], h->ev[1]);
     return ECSEG_OK;
@@ -729,20 +654,15 @@ int ecseg_rescale_mask_up(ecseg_ctx* h, const uint8_t* cleaned, int H, int W, in
     HIP_TRY(h, hipSetDevice(h->device));
     const size_t px = (size_t)H * W, opx = (size_t)out_h * out_w;
     int rc;
-    if ((rc = h->d_cl_mask.ensure(h, px))) return rc;
-    if ((rc = h->d_cl_out.ensure(h, opx))) return rc;
-    if ((rc = h->d_cl_par.ensure(h, opx))) return rc;
-    if ((rc = h->d_cl_sz.ensure(h, opx))) return rc;
-    if ((rc = h->d_rs_v.ensure(h, opx))) return rc;
-    if ((rc = h->d_rs_mm.ensure(h, 2))) return rc;
+    RescaleUpBufs b{};
+    if ((rc = lay_out(h, h->call_arena, [&](Carver& c) { b = rescale_up_bufs(c, H, W, out_h, out_w); }))) return rc;
     hipStream_t s = h->stream;
     for (float& v : h->stage_ms) v = 0.f;
-    HIP_TRY(h, hipMemcpyAsync(h->d_cl_mask, cleaned, px, hipMemcpyHostToDevice, s));
-    const RescaleUpBufs b{h->d_rs_v, h->d_rs_mm, h->d_cl_par, h->d_cl_sz, h->d_cl_out};
+    HIP_TRY(h, hipMemcpyAsync(b.cleaned, cleaned, px, hipMemcpyHostToDevice, s));
     HIP_TRY(h, hipEventRecord(h->ev[0], s));
-    HIP_TRY(h, run_rescale_mask_up(h->d_cl_mask, H, W, out_h, out_w, nuclei_size_t, b, s));
+    HIP_TRY(h, run_rescale_mask_up(b.cleaned, H, W, out_h, out_w, nuclei_size_t, b, s));
     HIP_TRY(h, hipEventRecord(h->ev[1], s));
-    HIP_TRY(h, hipMemcpyAsync(out, h->d_cl_out, opx, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipMemcpyAsync(out, b.out, opx, hipMemcpyDeviceToHost, s));
     HIP_TRY(h, hipStreamSynchronize(s));
     h->stage_ms[ECSEG_T_COUNT] = stage_elapsed(h->ev[0], h->ev[1]);
     return ECSEG_OK;

@@ -79,44 +79,14 @@ int get_stitch(ecseg_ctx* h, int H, int W, StitchPlan** out) {
     return ECSEG_OK;
 }
 
-void free_post_workspace(PostWorkspace& w) {
-    void* ptrs[] = {w.L, w.area, w.sumy, w.sumx, w.flag, w.tmpA, w.tmpB, w.list, w.g, w.tile_any, w.own_bits, w.binned, w.binstart};
-    for (void* p : ptrs) if (p) (void)hipFree(p);
-    w = PostWorkspace{};
-}
-
 int ensure_post(ecseg_ctx* h, int n_img, size_t px) {
     PostWorkspace& w = h->ws;
     if (n_img <= w.cap_img && px <= w.cap_px && w.L) return ECSEG_OK;
     const int ni = std::max(n_img, w.cap_img);
     const size_t np = std::max(px, w.cap_px);
-    free_post_workspace(w);
-    const size_t tot = (size_t)ni * np;
-    // Root lists of the nucleus-in-metaphase test: run_meta_inference uses px/4 + (H+W)/2 + 4 entries per image
-    // (>= ceil(H/2)*ceil(W/2), the most 8-connected components an image can hold); (H+W)/2 <= px/2 + 1, and every
-    // entry costs 4 B (nucleus root) + 16 B (chromosome centroid).
-    const size_t list_cap = np / 4 + np / 2 + 8;
-    const size_t list_bytes = (size_t)ni * list_cap * 20 + 256;
-    hipError_t e = hipSuccess;
-    auto A = [&](void** p, size_t bytes) { if (e == hipSuccess) e = hipMalloc(p, bytes ? bytes : 16); };
-    A(reinterpret_cast<void**>(&w.L), tot * 4);
-    A(reinterpret_cast<void**>(&w.area), tot * 4);
-    A(reinterpret_cast<void**>(&w.sumy), tot * 8);
-    A(reinterpret_cast<void**>(&w.sumx), tot * 8);
-    A(reinterpret_cast<void**>(&w.flag), tot * 4);
-    A(reinterpret_cast<void**>(&w.tmpA), tot);
-    A(reinterpret_cast<void**>(&w.tmpB), tot);
-    A(reinterpret_cast<void**>(&w.list), list_bytes);
-    A(reinterpret_cast<void**>(&w.g), (size_t)G_SLOTS * ni * G_STRIDE * G_SHARDS * 4);
-    A(reinterpret_cast<void**>(&w.tile_any), (size_t)ni * (np / 16 + 2));
-    // owner bits: 256 B per 64 x 32 tile; ceil(W/64) ceil(H/32) <= px/2048 + W/64 + H/32 + 1 <= px/31 + 3 tiles for any H x W = px
-    A(reinterpret_cast<void**>(&w.own_bits), (size_t)ni * (np / 31 + 4) * 256);
-    const size_t binned_cap = std::min(list_cap, (size_t)1 << 20);
-    A(reinterpret_cast<void**>(&w.binned), (size_t)ni * 2 * binned_cap * sizeof(double));
-    A(reinterpret_cast<void**>(&w.binstart), (size_t)ni * 2 * (NUCLEUS_BIN_EXTENT + 2) * sizeof(int32_t));   // (W/64 + 1)(H/32 + 1) <= px/16 + 1 tiles per image
-    if (e != hipSuccess) return fail(h, ECSEG_E_NOMEM, std::string("hipMalloc(post workspace): ") + hipGetErrorString(e));
-    w.cap_img = ni; w.cap_px = np; w.binned_cap = binned_cap;
-    return ECSEG_OK;
+    const int rc = lay_out(h, h->post_arena, [&](Carver& c) { w = post_workspace(c, ni, np); }, "hipMalloc(post workspace)");
+    if (rc) w = PostWorkspace{};
+    return rc;
 }
 
 namespace {
