@@ -13,7 +13,7 @@ EXTRA_FLAGS = {'wino4_kernel.hip': ['-fno-slp-vectorize'], 'wino4s_kernel.hip': 
 EXTRA_FLAGS['nuset_kernels.hip'] = ['-ffp-contract=off']
 # rescale restates scipy's and scikit-image's float64 arithmetic bit for bit: the same there
 EXTRA_FLAGS['rescale_kernels.hip'] = ['-ffp-contract=off']
-HEADERS = [os.path.join(CSRC, f) for f in ('common.h', 'ctx.h', 'scratch.h', 'device_util.h', 'cell_util.h', 'wino4_consts.inc', 'wino4_region.inc', 'wino4_combine.inc', 'wino4_head.inc')] + \
+HEADERS = [os.path.join(CSRC, f) for f in ('common.h', 'ctx.h', 'scratch.h', 'device_util.h', 'cell_util.h', 'wino4_consts.inc', 'wino4_lds_layout.h', 'wino4_region.inc', 'wino4_combine.inc', 'wino4_head.inc')] + \
     [os.path.join(HERE, '..', 'include', 'ecseg_hip.h')]
 
 

@@ -18,7 +18,7 @@
         const int cwave = __builtin_amdgcn_readfirstlane(tid >> 6);
         const int co = n0 + 4 * cq;
         const bool co_ok = co + 3 < Cout;
-        const float* rlane = Rs + cx * W4_RPLANE + nlo * 32 + 4 * cq;
+        const float* rlane = Rs + W4Lds::r_comb(cx, nlo, cq, 0);           // (the function is a sum of a lane part and a tile-pair part)
         const unsigned out_lane = (unsigned)((4 * nlo + cx) * p.out.cs + co);       // floats from the tile pair's first output pixel
         const unsigned out_row = (unsigned)(W * p.out.cs);
 #pragma unroll
@@ -29,13 +29,13 @@
             const int g = (0x96 >> nq8) & 1, nty = nq8 >> 1;
             const int img = g ? r_img[1] : r_img[0];
             if (img < 0) continue;
-            const float* r = rlane + nw * 64;
+            const float* r = rlane + W4Lds::r_comb(0, 0, 0, nw);
             const f32x4 q0 = *reinterpret_cast<const f32x4*>(r);
-            const f32x4 q1 = *reinterpret_cast<const f32x4*>(r + 1 * 4 * W4_RPLANE);
-            const f32x4 q2 = *reinterpret_cast<const f32x4*>(r + 2 * 4 * W4_RPLANE);
-            const f32x4 q3 = *reinterpret_cast<const f32x4*>(r + 3 * 4 * W4_RPLANE);
-            const f32x4 q4 = *reinterpret_cast<const f32x4*>(r + 4 * 4 * W4_RPLANE);
-            const f32x4 q5 = *reinterpret_cast<const f32x4*>(r + 5 * 4 * W4_RPLANE);
+            const f32x4 q1 = *reinterpret_cast<const f32x4*>(r + W4Lds::r_plane(4 * 1));
+            const f32x4 q2 = *reinterpret_cast<const f32x4*>(r + W4Lds::r_plane(4 * 2));
+            const f32x4 q3 = *reinterpret_cast<const f32x4*>(r + W4Lds::r_plane(4 * 3));
+            const f32x4 q4 = *reinterpret_cast<const f32x4*>(r + W4Lds::r_plane(4 * 4));
+            const f32x4 q5 = *reinterpret_cast<const f32x4*>(r + W4Lds::r_plane(4 * 5));
             const f32x4 s12 = q1 + q2, d12 = q1 - q2, s34 = q3 + q4, d34 = q3 - q4;
             f32x4 y[4];                                      // (the expressions of the half-item form, term for term: results are bit-identical)
             y[0] = q0 + s12 + s34 + bv;

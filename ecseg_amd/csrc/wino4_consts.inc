@@ -1,18 +1,11 @@
 // Constants and small helpers shared by the F(4x4) kernels (wino4_kernel.hip, wino4r_kernel.hip, wino4s_kernel.hip); included inside namespace ecseg.
 namespace {
 
-constexpr int W4_HS = 1536;          // halo slots per buffer: 2 regions x 18 rows x 36 = 1296 used, padded to 24 x 64
-constexpr int W4_BWS = 192;          // filter slots per wave and stage: 6 points x 2 halves x 32 couts x 2 k / 4
-constexpr int W4_RPLANE = 1056;      // floats per (xi, x) plane of the output exchange image: 32 tiles x 32 couts + 32
-
-__device__ __forceinline__ int w4_pos(int v) {           // 0..17 -> regrouped position
-    const int m = v & 3;
-    return (m == 0 ? 0 : m == 1 ? 5 : m == 2 ? 10 : 14) + (v >> 2);
-}
-__device__ __forceinline__ int w4_inv(int r) {           // regrouped position -> 0..17
-    return r < 5 ? 4 * r : r < 10 ? 4 * (r - 5) + 1 : r < 14 ? 4 * (r - 10) + 2 : 4 * (r - 14) + 3;
-}
-constexpr int w4_cpos(int v) { return ((v & 3) == 0 ? 0 : (v & 3) == 1 ? 5 : (v & 3) == 2 ? 10 : 14) + (v >> 2); }
+// Every LDS size and lane -> address function of these kernels lives in wino4_lds_layout.h (W4Lds), which the including file
+// includes at file scope; the names the launch functions use:
+constexpr int W4_HS = W4Lds::HS;             // halo slots per raw buffer
+constexpr int W4_BWS = W4Lds::BWS;           // filter slots per wave and stage (fp32 kernels)
+constexpr int W4_RPLANE = W4Lds::RPLANE;     // floats per (xi, x) plane of the output exchange image
 
 typedef __attribute__((address_space(3))) void* lptr_t;
 

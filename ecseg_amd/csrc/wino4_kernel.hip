@@ -20,24 +20,27 @@
 // filter path.  All LDS-DMA goes through inline asm (wino4_consts.inc).  Per group a wave has two phases, T (row transform) and
 // S (12 MFMAs); waves 4-11 run S one group late (phase rotation, see the K loop).
 //
-// LDS halo image, 16-byte slots (4 channels): slot(g, y, x, h) = (g * 18 + P(y)) * 36 + h * 18 + P(x), where
+// LDS halo image (W4Lds::a_lane / a_row / a_col, wino4_lds_layout.h), 16-byte slots (4 channels): slot(g, y, x, h) = (g * 18 + P(y)) * 36 + h * 18 + P(x), where
 // P(v) = {0, 5, 10, 14}[v % 4] + v / 4 regroups the 18 halo rows / columns by their phase modulo the tile stride 4.
 // For a fixed tile offset (i, j) the 16 lanes of a ds_read group then read slots 36 * ty + tx + const:
 // 36 = 4 (mod 16), so all 16 land on different 16-byte bank groups: conflict-free without padding.  The A-operand
-// lane -> tile map follows the hardware's b128 lane groups (see tg / ty below).
+// lane -> tile map follows the hardware's b128 lane groups (see tg / ty below).  (The row transform's 8-byte reads take half of every slot they touch:
+// two-way on the banks under any placement of whole slots - tools/lds_bank_model.cpp, Site::floor.)
 #include <cstdlib>
 #include <type_traits>
 
 #include "common.h"
 #include "device_util.h"
+#include "wino4_lds_layout.h"
 
 namespace ecseg {
 
 #include "wino4_consts.inc"
 #define W4_HALO_RING 3
 // raw image of this kernel: rows and columns regrouped by their phase modulo the tile stride (see the header), the two channel halves 18 slots apart
-#define W4_HALO_SLOT(r, cc) const int h = (cc) >= 18 ? 1 : 0, hy = w4_inv(r), hx = w4_inv((cc) - h * 18)
+#define W4_HALO_SLOT(r, cc) const int h = (cc) >= 18 ? 1 : 0, hy = W4Lds::inv(r), hx = W4Lds::inv((cc) - h * 18)
 #define W4_HALO_UPPER(cc) ((cc) >= 18)
+#define W4_HALO_L W4Lds::Ring
 
 // Row-transform pipeline depth (slots of in-flight halo reads beside the six direct ones; 0: rounds 1-3, column by column)
 #ifndef ECSEG_W4_TSLOTS
@@ -65,11 +68,11 @@ __global__ __launch_bounds__(768) void conv_wino4_kernel(ConvParams p, int regs_
     //      address is a scalar base (advanced per stage by scalar adds) + the lane's constant 16-byte offset ----
     const unsigned long long w_base = (unsigned long long)(size_t)(p.wt + ((size_t)nb * nstages * 12 + xi) * 768);      // (both channel halves: the ch = 0 slot)
     const unsigned lane16 = (unsigned)lane * 16u;
-    f32x4* Bw = Bs + wave * 2 * W4_BWS;
+    f32x4* Bw = Bs + W4Lds::bw_stage(wave, 0);
     auto dma_filter_piece = [&](int stage, int buf, auto kk) __attribute__((always_inline)) {
         constexpr int k = decltype(kk)::value;
         const unsigned long long g = w_base + (unsigned long long)stage * (12 * 768 * 4);
-        const unsigned dst = lds_base + (unsigned)(3 * W4_HS + (wave * 2 + buf) * W4_BWS) * 16u;
+        const unsigned dst = lds_base + (unsigned)(3 * W4_HS + W4Lds::bw_stage(wave, buf)) * 16u;
         const unsigned l16 = lane16;
         unsigned keep;
         // the instruction offset advances the global AND the LDS address: one M0 for the three pieces
@@ -82,7 +85,7 @@ __global__ __launch_bounds__(768) void conv_wino4_kernel(ConvParams p, int regs_
     const int q8 = li >> 2, tx = li & 3;
     const int tg = (0x96 >> q8) & 1;                              // region of lane quad q8: 0,1,1,0,1,0,0,1
     const int ty = (q8 == 0 || q8 == 1) ? 0 : (q8 == 2 || q8 == 3) ? 1 : (q8 == 4 || q8 == 5) ? 2 : 3;
-    const int a_lane = (tg * 18 + ty) * 36 + lh * 18 + tx;       // slot of halo pixel (4 ty, 4 tx) of the lane's tile
+    const int a_lane = W4Lds::a_lane(tg, ty, lh, tx);       // slot of halo pixel (4 ty, 4 tx) of the lane's tile
 
     // row transform of wave xi (row xi of B^T): t = c0 d[r0] + c1 d[r1] + c2 d[r2] + d[r3]  (rows 0 and 5: three terms)
     int rr0, rr1, rr2, rr3; float c0, c1, c2;
@@ -94,7 +97,7 @@ __global__ __launch_bounds__(768) void conv_wino4_kernel(ConvParams p, int regs_
         case 4:  rr0 = 1; rr1 = 2; rr2 = 3; rr3 = 4; c0 = KA2 * KB;  c1 = -KA2; c2 = -KB; break;
         default: rr0 = 1; rr1 = 3; rr2 = 5; rr3 = 5; c0 = KP;        c1 = KS;   c2 = 1.f; break;
     }
-    const int ro0 = 36 * w4_pos(rr0), ro1 = 36 * w4_pos(rr1), ro2 = 36 * w4_pos(rr2), ro3 = 36 * w4_pos(rr3);
+    const int ro0 = W4Lds::a_row(rr0), ro1 = W4Lds::a_row(rr1), ro2 = W4Lds::a_row(rr2), ro3 = W4Lds::a_row(rr3);
 
     f32x16 acc[6];
 #pragma unroll
@@ -112,7 +115,7 @@ __global__ __launch_bounds__(768) void conv_wino4_kernel(ConvParams p, int regs_
     auto transform = [&](int grp, auto c_src) __attribute__((always_inline)) {   // t[j][c_src + k] = row transform of channel c_src + k (k < 2, c_src = 2 ch) of the lane's slot
         constexpr int CS = decltype(c_src)::value, CN = 2;
         const f32x4* A = Hs + (grp % 3) * W4_HS + a_lane;
-        constexpr int cp[6] = {w4_cpos(0), w4_cpos(1), w4_cpos(2), w4_cpos(3), w4_cpos(4), w4_cpos(5)};
+        constexpr int cp[6] = {W4Lds::a_col(0), W4Lds::a_col(1), W4Lds::a_col(2), W4Lds::a_col(3), W4Lds::a_col(4), W4Lds::a_col(5)};
         // scalar fmas on purpose (file is built with -fno-slp-vectorize): packed f32 VALU ops (v_pk_fma_f32) stall the
         // SIMD beside MFMAs, single v_fma_f32 hide in the matrix pipe's shadow
         // Software-pipelined (round 4): the phase used to be six LDS round trips behind each other (one per halo column:
@@ -189,10 +192,10 @@ __global__ __launch_bounds__(768) void conv_wino4_kernel(ConvParams p, int regs_
             V[5][e] = __builtin_fmaf(KP, u1, __builtin_fmaf(KS, u3, u5));
         }
         f32x2 w2[6];
-        const f32x4* Bp = Bw + fbuf * W4_BWS + lane;        // three 16-byte reads: the fragments of point pairs (0, 1), (2, 3), (4, 5)
+        const f32x4* Bp = Bw + W4Lds::bw_stage(0, fbuf) + W4Lds::bw_read(lane, 0);        // three 16-byte reads: the fragments of point pairs (0, 1), (2, 3), (4, 5)
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
-            const f32x4 w4 = Bp[k * 64];
+            const f32x4 w4 = Bp[W4Lds::bw_read(0, k)];
             w2[2 * k] = f32x2{w4[0], w4[1]};
             w2[2 * k + 1] = f32x2{w4[2], w4[3]};
         }
@@ -303,13 +306,13 @@ __global__ __launch_bounds__(768) void conv_wino4_kernel(ConvParams p, int regs_
             const int tl = (e & 3) + 8 * (e >> 2) + 4 * lh;               // accumulator row = tile slot
             const float m0 = acc[0][e], m1 = acc[1][e], m2 = acc[2][e], m3 = acc[3][e], m4 = acc[4][e], m5 = acc[5][e];
             const float s12 = m1 + m2, d12 = m1 - m2, s34 = m3 + m4, d34 = m3 - m4;
-            float* o = Rs + (xi * 4) * W4_RPLANE + tl * 32 + li;
+            float* o = Rs + W4Lds::r_fold(xi, tl, li);
             const float r0 = m0 + s12 + s34, r1 = __builtin_fmaf(KA, d12, KB * d34), r2 = __builtin_fmaf(KA2, s12, KB2 * s34),
                         r3 = __builtin_fmaf(KA3, d12, __builtin_fmaf(KB3, d34, m5));
             if (add) {                                           // (this lane's four words: nobody else touches them in this phase)
-                o[0 * W4_RPLANE] += r0; o[1 * W4_RPLANE] += r1; o[2 * W4_RPLANE] += r2; o[3 * W4_RPLANE] += r3;
+                o[W4Lds::r_plane(0)] += r0; o[W4Lds::r_plane(1)] += r1; o[W4Lds::r_plane(2)] += r2; o[W4Lds::r_plane(3)] += r3;
             } else {
-                o[0 * W4_RPLANE] = r0; o[1 * W4_RPLANE] = r1; o[2 * W4_RPLANE] = r2; o[3 * W4_RPLANE] = r3;
+                o[W4Lds::r_plane(0)] = r0; o[W4Lds::r_plane(1)] = r1; o[W4Lds::r_plane(2)] = r2; o[W4Lds::r_plane(3)] = r3;
             }
         }
     };
@@ -344,7 +347,7 @@ hipError_t launch_conv_wino4(const ConvParams& p, hipStream_t s) {
     if (grid == 0) return hipSuccess;
     if (grid > 0x7fffffffull || !conv_wino4_span_ok(p, p.lut != nullptr ? p.per_image : 2)) return hipErrorInvalidValue;
     size_t lds = (size_t)(3 * W4_HS + 12 * 2 * W4_BWS) * 16;
-    const size_t lds_epi = (size_t)24 * W4_RPLANE * 4;
+    const size_t lds_epi = (size_t)W4Lds::EPI_FLOATS * 4;
     if (lds_epi > lds) lds = lds_epi;
     static DeviceOnce attr_set;                              // the attribute is per device
     const hipError_t ea = attr_set.run([&] {

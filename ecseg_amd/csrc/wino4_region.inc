@@ -2,7 +2,8 @@
 // block order, the two 16x16 regions of the workgroup, their input boxes, and the halo LDS-DMA (dma_halo_piece).
 // Expects: p, regs_x, regs_y, npairs, wave, lane, lds_base; defines bid, nb, pair, H, W, ngroups, tail4, r_img / r_y0 / r_x0 / r_win,
 // hrsrc, hoff[2], dma_halo_piece(grp, piece).  W4_HALO_RING: depth of the halo ring in LDS (buffers of W4_HS slots from lds_base on);
-// W4_HALO_SLOT(r, cc) / W4_HALO_UPPER(cc): the kernel's raw image - slot (region * 18 + r) * 36 + cc holds halo row hy, column hx, channel half h.
+// W4_HALO_L: the strides of the kernel's raw image (W4Lds::Raw / W4Lds::Ring, wino4_lds_layout.h) - slot REGION * region + ROW * r + cc, cc < COLS;
+// W4_HALO_SLOT(r, cc) / W4_HALO_UPPER(cc): what (r, cc) holds - halo row hy, column hx, channel half h.
     unsigned bid = xcd_remap(blockIdx.x, gridDim.x);
     // Block order: output-channel blocks in groups of G = 4 (2) next to each other, region pairs next, groups slowest.  The
     // workgroups running together on an XCD then share each input halo in L2 between G of them and keep only G filter
@@ -77,15 +78,17 @@
     for (int i = 0; i < 2; ++i) {
         const int a = 64 * (wave + 12 * i) + lane;
         unsigned off = 0xffffffffu;
-        if (a < 2 * 18 * 36) {
-            const int g = a >= 648 ? 1 : 0, rem = a - g * 648;
-            const int r = rem / 36, cc = rem - r * 36;
+        if (a < W4_HALO_L::USED) {
+            const int g = a >= W4_HALO_L::REGION ? 1 : 0, rem = a - g * W4_HALO_L::REGION;
+            const int r = rem / W4_HALO_L::ROW, cc = rem - r * W4_HALO_L::ROW;
+            if (W4_HALO_L::ROW == W4_HALO_L::COLS || cc < W4_HALO_L::COLS) {      // (not a pad slot)
             W4_HALO_SLOT(r, cc);                                 // -> h (channel half), hy / hx (halo row / column 0..17) of slot (r, cc) of the kernel's raw image
             const int img = g ? r_img[1] : r_img[0];
             const int iy = (g ? r_y0[1] : r_y0[0]) - 1 + hy, ix = (g ? r_x0[1] : r_x0[0]) - 1 + hx;
             if (img >= 0 && iy >= (g ? r_by0[1] : r_by0[0]) && iy <= (g ? r_by1[1] : r_by1[0]) && ix >= (g ? r_bx0[1] : r_bx0[0]) &&
                 ix <= (g ? r_bx1[1] : r_bx1[0]))                         // (two neighbouring windows: far below 2 GB)
                 off = (unsigned)(((((size_t)(img - img_lo) * H + iy) * W + ix) * p.in.cs + 4 * h) * 4);
+            }
         }
         hoff[i] = off;
         W4_DIAG_HALO_OFFSET(hoff[i], a);
@@ -96,7 +99,8 @@
         unsigned off = hoff[i];
         if (tail4 && grp == ngroups - 1) {                   // Cin % 8 == 4: the upper channel half of the last group does not exist
             const int a = 64 * (wave + 12 * i) + lane;
-            if (W4_HALO_UPPER(a % 36)) off = 0xffffffffu;
+            const int cc = W4_HALO_L::REGION % W4_HALO_L::ROW == 0 ? a % W4_HALO_L::ROW : (a - (a >= W4_HALO_L::REGION ? W4_HALO_L::REGION : 0)) % W4_HALO_L::ROW;
+            if (W4_HALO_UPPER(cc)) off = 0xffffffffu;
         }
         const unsigned dst = lds_base + (unsigned)((grp % W4_HALO_RING) * W4_HS + 64 * (wave + 12 * i)) * 16u;
         const i32x4 rs = hrsrc;                              // (local copies: asm operands do not capture in a generic lambda)

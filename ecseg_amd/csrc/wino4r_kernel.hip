@@ -23,6 +23,9 @@
 // The output stage can also write the 2x2 max-pool of its result, finish a 1x1 head (<= 4 classes) and take its region
 // list from a look-up table (demand-driven cropping) - see ConvParams in common.h.
 //
+// Where every value sits in LDS - raw image, t image, filter stages, exchange image - is decided in wino4_lds_layout.h (W4Lds): the kernel calls its
+// functions and holds no address arithmetic of its own; tools/lds_bank_model.cpp walks the same functions against the LDS bank rule (round 9).
+//
 // History (round 6): until then every wave read the raw halo rows of its transform row straight from LDS and ran
 // the row transform itself (24 raw slots + 72 fmas per group instead of six columns); this kernel replaced that one with
 // bit-identical results, 1 - 6 % faster per layer.  The per-wave scheme survives where it is faster: the split-K kernel for a lone
@@ -33,14 +36,16 @@
 
 #include "common.h"
 #include "device_util.h"
+#include "wino4_lds_layout.h"
 
 namespace ecseg {
 
 #include "wino4_consts.inc"
 #define W4_HALO_RING 2
-// raw image (only row_pass reads it): plain row / column order, the two 16-byte channel halves of a pixel next to each other
+// raw image (only row_pass reads it): plain row / column order (one pad slot per row: W4Lds::RAW_ROW), the two 16-byte channel halves of a pixel next to each other
 #define W4_HALO_SLOT(r, cc) const int h = (cc) & 1, hy = (r), hx = (cc) >> 1
 #define W4_HALO_UPPER(cc) ((cc) & 1)
+#define W4_HALO_L W4Lds::Raw
 // (timing-only ablations exist only in A/B builds, tools/w4r_variants.sh -DECSEG_W4R_ABL=<bits>: 1 no filter DMA, 2 no halo DMA, 4 no MFMAs)
 #ifdef ECSEG_W4R_ABL
 #define W4_DIAG_SKIP_HALO_DMA() do { if (ECSEG_W4R_ABL & 2) return; } while (0)
@@ -58,7 +63,7 @@ namespace ecseg {
 #define W4_WAIT(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
 
 namespace {
-constexpr int W4R_TS = 2 * 6 * 4 * 36;   // slots of the t image: 2 regions x 6 transform rows x 4 tile rows x (18 columns x 2 channel halves)
+constexpr int W4R_TS = W4Lds::TS;       // slots of the t image: 2 regions x 6 transform rows x 4 tile rows x (18 columns x 2 channel halves), padded (wino4_lds_layout.h)
 }
 
 template <bool HEAD>
@@ -79,12 +84,12 @@ __global__ __launch_bounds__(768) void conv_wino4r_kernel(ConvParams p, int regs
     //      address is a scalar base (advanced per stage by scalar adds) + the lane's constant 16-byte offset ----
     const unsigned long long w_base = (unsigned long long)(size_t)(p.wt + ((size_t)nb * nstages * 12 + wave) * 768);
     const unsigned lane16 = (unsigned)lane * 16u;
-    f32x4* Bw = Bs + wave * 2 * W4_BWS;
+    f32x4* Bw = Bs + W4Lds::bw_stage(wave, 0);
     auto dma_filter_piece = [&](int stage, int buf, auto kk) __attribute__((always_inline)) {
         W4_DIAG_SKIP_FILTER_DMA();
         constexpr int k = decltype(kk)::value;
         const unsigned long long g = w_base + (unsigned long long)stage * (12 * 768 * 4);
-        const unsigned dst = lds_base + (unsigned)(2 * W4_HS + W4R_TS + (wave * 2 + buf) * W4_BWS) * 16u;
+        const unsigned dst = lds_base + (unsigned)(2 * W4_HS + W4R_TS + W4Lds::bw_stage(wave, buf)) * 16u;
         const unsigned l16 = lane16;
         unsigned keep;
         // the instruction offset advances the global AND the LDS address: one M0 for the three pieces
@@ -96,7 +101,7 @@ __global__ __launch_bounds__(768) void conv_wino4r_kernel(ConvParams p, int regs
     const int q8 = li >> 2, tx = li & 3;
     const int tg = (0x96 >> q8) & 1;
     const int ty = (q8 == 0 || q8 == 1) ? 0 : (q8 == 2 || q8 == 3) ? 1 : (q8 == 4 || q8 == 5) ? 2 : 3;
-    const int t_lane = ((tg * 6 + xi) * 4 + ty) * 36 + lh * 18 + tx;      // the lane's tile in the t image (wino4s_kernel.hip)
+    const int t_lane = W4Lds::t_lane(tg, xi, ty, lh, tx);      // the lane's tile in the t image (wino4s_kernel.hip)
 
     f32x16 acc[6];
 #pragma unroll
@@ -104,24 +109,33 @@ __global__ __launch_bounds__(768) void conv_wino4r_kernel(ConvParams p, int regs
 #pragma unroll
         for (int e = 0; e < 16; ++e) acc[v][e] = 0.f;
 
+    // row_pass's item and its two LDS byte addresses (raw buffer 0, transform row 0) do not depend on the group: formed once and pinned - left alone the
+    // compiler rebuilds them (~20 vector instructions beside the MFMA stream) in every copy of the pass
+    unsigned rp_raw, rp_t;
+    {
+        const int item = wave * 48 + lane, cpair = item & 1, h = (item >> 1) & 1, k = item >> 2;
+        const int x = k % 18, r2 = k / 18, tyy = r2 & 3, tgg = r2 >> 2;
+        rp_raw = (unsigned)(W4Lds::raw_read(0, tgg, tyy, x, h) * 16 + cpair * 8);
+        rp_t = (unsigned)((2 * W4_HS + W4Lds::t_write(tgg, tyy, h, x)) * 16 + cpair * 8);
+        asm volatile("" : "+v"(rp_raw), "+v"(rp_t));
+    }
     auto row_pass = [&](int grp) __attribute__((always_inline)) {
         // 576 half items (region, tile row, channel half, column, channel PAIR) over the 12 waves x 48 lanes: every wave carries the
         // same share (a pass run by five waves alone left the other seven waiting at the barrier behind it), 8-byte accesses,
         // neighbouring lanes on neighbouring addresses
         if (lane >= 48) return;
-        const int item = wave * 48 + lane, cpair = item & 1, h = (item >> 1) & 1, k = item >> 2;
-        const int x = k % 18, r2 = k / 18, tyy = r2 & 3, tgg = r2 >> 2;
-        const f32x2* R = reinterpret_cast<const f32x2*>(Hs + (grp & 1) * W4_HS + (tgg * 18 + 4 * tyy) * 36 + 2 * x + h) + cpair;     // raw row 4 tyy + i: + 36 i slots
-        const f32x2 d0 = R[2 * 36 * 0], d1 = R[2 * 36 * 1], d2 = R[2 * 36 * 2], d3 = R[2 * 36 * 3], d4 = R[2 * 36 * 4], d5 = R[2 * 36 * 5];
-        f32x2* T = reinterpret_cast<f32x2*>(Ts + ((tgg * 6) * 4 + tyy) * 36 + h * 18 + w4_pos(x)) + cpair;                            // + xi * 144 slots
+        const f32x2* R = reinterpret_cast<const f32x2*>(smem + rp_raw + (unsigned)(W4Lds::raw_read(grp & 1, 0, 0, 0, 0) * 16));     // raw row 4 tyy + i: + i rows
+        constexpr int RR = 2 * W4Lds::raw_row();
+        const f32x2 d0 = R[RR * 0], d1 = R[RR * 1], d2 = R[RR * 2], d3 = R[RR * 3], d4 = R[RR * 4], d5 = R[RR * 5];
+        f32x2* T = reinterpret_cast<f32x2*>(smem + rp_t);                            // + xi transform rows
         // t[xi] = c0 d[r0] + c1 d[r1] + c2 d[r2] + d[r3] as ONE fma chain per row, innermost term first: fma(c0, d[r0], fma(c1, d[r1],
         // fma(c2, d[r2], d[r3]))) - the operation order of the per-wave row transform (wino4_kernel.hip), so every F(4x4) kernel forms
         // bit-identical t.  (A first version shared the even / odd parts of the +- rows,
         // 12 instead of 16 fmas per channel: the smooth fixture model's wrong-pixel total rose from 11 to 19 of ~15 hard pixels per image.)
         f32x2 o;
-#define W4_ROW3(XI, A0, DA, A1, DB, DC) do { _Pragma("unroll") for (int c = 0; c < 2; ++c) o[c] = __builtin_fmaf(A0, DA[c], __builtin_fmaf(A1, DB[c], DC[c])); T[2 * (XI) * 144] = o; } while (0)
+#define W4_ROW3(XI, A0, DA, A1, DB, DC) do { _Pragma("unroll") for (int c = 0; c < 2; ++c) o[c] = __builtin_fmaf(A0, DA[c], __builtin_fmaf(A1, DB[c], DC[c])); T[2 * (XI) * W4Lds::t_xi()] = o; } while (0)
 #define W4_ROW4(XI, A0, DA, A1, DB, A2, DC, DD) do { _Pragma("unroll") for (int c = 0; c < 2; ++c) \
-            o[c] = __builtin_fmaf(A0, DA[c], __builtin_fmaf(A1, DB[c], __builtin_fmaf(A2, DC[c], DD[c]))); T[2 * (XI) * 144] = o; } while (0)
+            o[c] = __builtin_fmaf(A0, DA[c], __builtin_fmaf(A1, DB[c], __builtin_fmaf(A2, DC[c], DD[c]))); T[2 * (XI) * W4Lds::t_xi()] = o; } while (0)
         W4_ROW3(0, KP, d0, KS, d2, d4);
         W4_ROW3(5, KP, d1, KS, d3, d5);
         W4_ROW4(1, -KA * KB2, d1, -KB2, d2, KA, d3, d4);
@@ -135,7 +149,7 @@ __global__ __launch_bounds__(768) void conv_wino4r_kernel(ConvParams p, int regs
     auto load_t = [&]() __attribute__((always_inline)) {
         const f32x4* A = Ts + t_lane;
 #pragma unroll
-        for (int j = 0; j < 6; ++j) t[j] = A[w4_cpos(j)];
+        for (int j = 0; j < 6; ++j) t[j] = A[W4Lds::t_col(j)];
     };
     // ---- one filter stage (2 of the group's 4 channel pairs; buffer ss): column transform + 12 MFMAs ----
     auto mfma_stage = [&](int ss, int fbuf, int next_stage, int halo_grp) __attribute__((always_inline)) {     // ss: channel pair of the group, fbuf: filter buffer; halo_grp: group to prefetch, < 0: none
@@ -156,10 +170,10 @@ __global__ __launch_bounds__(768) void conv_wino4r_kernel(ConvParams p, int regs
             V[5][e] = __builtin_fmaf(KP, u1, __builtin_fmaf(KS, u3, u5));
         }
         f32x2 w2[6];
-        const f32x4* Bp = Bw + fbuf * W4_BWS + lane;        // three 16-byte reads: the fragments of point pairs (0, 1), (2, 3), (4, 5)
+        const f32x4* Bp = Bw + W4Lds::bw_stage(0, fbuf) + W4Lds::bw_read(lane, 0);        // three 16-byte reads: the fragments of point pairs (0, 1), (2, 3), (4, 5)
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
-            const f32x4 w4 = Bp[k * 64];
+            const f32x4 w4 = Bp[W4Lds::bw_read(0, k)];
             w2[2 * k] = f32x2{w4[0], w4[1]};
             w2[2 * k + 1] = f32x2{w4[2], w4[3]};
         }
@@ -288,10 +302,10 @@ __global__ __launch_bounds__(768) void conv_wino4r_kernel(ConvParams p, int regs
             const int tl = (e & 3) + 8 * (e >> 2) + 4 * lh;               // accumulator row = tile slot
             const float m0 = acc[0][e], m1 = acc[1][e], m2 = acc[2][e], m3 = acc[3][e], m4 = acc[4][e], m5 = acc[5][e];
             const float s12 = m1 + m2, d12 = m1 - m2, s34 = m3 + m4, d34 = m3 - m4;
-            float* o = Rs + (xi * 4) * W4_RPLANE + tl * 32 + li;
+            float* o = Rs + W4Lds::r_fold(xi, tl, li);
             const float r0 = m0 + s12 + s34, r1 = __builtin_fmaf(KA, d12, KB * d34), r2 = __builtin_fmaf(KA2, s12, KB2 * s34),
                         r3 = __builtin_fmaf(KA3, d12, __builtin_fmaf(KB3, d34, m5));
-            o[0 * W4_RPLANE] = r0; o[1 * W4_RPLANE] = r1; o[2 * W4_RPLANE] = r2; o[3 * W4_RPLANE] = r3;
+            o[W4Lds::r_plane(0)] = r0; o[W4Lds::r_plane(1)] = r1; o[W4Lds::r_plane(2)] = r2; o[W4Lds::r_plane(3)] = r3;
         }
     };
     if constexpr (!HEAD) {
@@ -301,7 +315,7 @@ __global__ __launch_bounds__(768) void conv_wino4r_kernel(ConvParams p, int regs
         // bit-identical.  (Not for a fused head: its per-pixel class sums would then be spread over two waves.)
         const int cq = tid & 7, cx = (tid >> 3) & 3, nlo = (tid >> 5) & 1;          // channel quad, column of the tile, tile of the pair
         const int cwave = __builtin_amdgcn_readfirstlane(tid >> 6);
-        const float* rlane = Rs + cx * W4_RPLANE + nlo * 64 + 4 * cq;
+        const float* rlane = Rs + W4Lds::r_comb_tile(cx, nlo, cq, 0, 0);     // (the function is a sum of a lane part and a unit part)
         const unsigned out_row = (unsigned)(W * p.out.cs);
         auto tile_pass = [&](auto pc) __attribute__((always_inline)) {
             constexpr int P = decltype(pc)::value;
@@ -312,10 +326,10 @@ __global__ __launch_bounds__(768) void conv_wino4r_kernel(ConvParams p, int regs
                 const int tl = (e8 & 3) + 8 * (e8 >> 2) + 4 * lh;         // tile slot within the half: 0..15
                 const float m0 = acc[0][e], m1 = acc[1][e], m2 = acc[2][e], m3 = acc[3][e], m4 = acc[4][e], m5 = acc[5][e];
                 const float s12 = m1 + m2, d12 = m1 - m2, s34 = m3 + m4, d34 = m3 - m4;
-                float* o = Rs + (xi * 4) * W4_RPLANE + tl * 64 + ch * 32 + li;
+                float* o = Rs + W4Lds::r_fold_tile(xi, tl, ch, li);
                 const float r0 = m0 + s12 + s34, r1 = __builtin_fmaf(KA, d12, KB * d34), r2 = __builtin_fmaf(KA2, s12, KB2 * s34),
                             r3 = __builtin_fmaf(KA3, d12, __builtin_fmaf(KB3, d34, m5));
-                o[0 * W4_RPLANE] = r0; o[1 * W4_RPLANE] = r1; o[2 * W4_RPLANE] = r2; o[3 * W4_RPLANE] = r3;
+                o[W4Lds::r_plane(0)] = r0; o[W4Lds::r_plane(1)] = r1; o[W4Lds::r_plane(2)] = r2; o[W4Lds::r_plane(3)] = r3;
             }
             __syncthreads();
             if (P == 0) asm volatile("" :: "v"(bvp[0]), "v"(bvp[1]));      // (the bias wait in straight-line code: wino4_combine.inc)
@@ -331,13 +345,13 @@ __global__ __launch_bounds__(768) void conv_wino4r_kernel(ConvParams p, int regs
                 const int co = nb * 64 + chh * 32 + 4 * cq;
                 if (co + 3 >= Cout) continue;                // (the missing channel half of a Cout % 64 == 32 block; wave-uniform per lane group: co_ok is all or nothing for chh)
                 const f32x4 bv = chh ? bvp[1] : bvp[0];
-                const float* r = rlane + tp * 128 + chh * 32;
+                const float* r = rlane + W4Lds::r_comb_tile(0, 0, 0, tp, chh);
                 const f32x4 q0 = *reinterpret_cast<const f32x4*>(r);
-                const f32x4 q1 = *reinterpret_cast<const f32x4*>(r + 1 * 4 * W4_RPLANE);
-                const f32x4 q2 = *reinterpret_cast<const f32x4*>(r + 2 * 4 * W4_RPLANE);
-                const f32x4 q3 = *reinterpret_cast<const f32x4*>(r + 3 * 4 * W4_RPLANE);
-                const f32x4 q4 = *reinterpret_cast<const f32x4*>(r + 4 * 4 * W4_RPLANE);
-                const f32x4 q5 = *reinterpret_cast<const f32x4*>(r + 5 * 4 * W4_RPLANE);
+                const f32x4 q1 = *reinterpret_cast<const f32x4*>(r + W4Lds::r_plane(4 * 1));
+                const f32x4 q2 = *reinterpret_cast<const f32x4*>(r + W4Lds::r_plane(4 * 2));
+                const f32x4 q3 = *reinterpret_cast<const f32x4*>(r + W4Lds::r_plane(4 * 3));
+                const f32x4 q4 = *reinterpret_cast<const f32x4*>(r + W4Lds::r_plane(4 * 4));
+                const f32x4 q5 = *reinterpret_cast<const f32x4*>(r + W4Lds::r_plane(4 * 5));
                 const f32x4 s12 = q1 + q2, d12 = q1 - q2, s34 = q3 + q4, d34 = q3 - q4;
                 f32x4 y[4];                                  // (wino4_combine.inc's expressions, term for term)
                 y[0] = q0 + s12 + s34 + bv;
@@ -405,7 +419,7 @@ hipError_t launch_conv_wino4r(const ConvParams& p, hipStream_t s) {
     if (grid > 0x7fffffffull || !conv_wino4_span_ok(p, p.lut != nullptr ? p.per_image : 2)) return hipErrorInvalidValue;
     if (p.head_w != nullptr && (!p.head_only || p.pool.p != nullptr)) return hipErrorInvalidValue;
     size_t lds = (size_t)(2 * W4_HS + W4R_TS + 12 * 2 * W4_BWS) * 16;
-    const size_t lds_epi = (size_t)24 * W4_RPLANE * 4;
+    const size_t lds_epi = (size_t)W4Lds::EPI_FLOATS * 4;
     if (lds_epi > lds) lds = lds_epi;
     void (*kern)(ConvParams, int, int, int) = p.head_w != nullptr ? conv_wino4r_kernel<true> : conv_wino4r_kernel<false>;
     static DeviceOnce attr_set[2];

@@ -32,16 +32,18 @@
 
 #include "common.h"
 #include "device_util.h"
+#include "wino4_lds_layout.h"
 
 namespace ecseg {
 
 #include "wino4_consts.inc"
 #define W4_HALO_RING 2
-// raw image of this kernel (only row_pass reads it): plain row / column order, the two 16-byte channel halves of a pixel NEXT to each other -
+// raw image of this kernel (only row_pass reads it): plain row / column order (one pad slot per row: W4Lds::RAW_ROW), the two 16-byte channel halves of a pixel NEXT to each other -
 // neighbouring lanes of a halo LDS-DMA then read the 32 contiguous bytes of one pixel (the fp32 kernel's image, laid out for its MFMA
 // operand reads, puts them 18 lanes apart: 64 cache lines per instruction; measured on this kernel: -0.3 ms of 3.6 on 256 -> 256 at 64 x 64)
 #define W4_HALO_SLOT(r, cc) const int h = (cc) & 1, hy = (r), hx = (cc) >> 1
 #define W4_HALO_UPPER(cc) ((cc) & 1)
+#define W4_HALO_L W4Lds::Raw
 
 #ifndef ECSEG_W4_TSLOTS
 #define ECSEG_W4_TSLOTS 4
@@ -69,8 +71,8 @@ typedef unsigned u32x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef u32x4 __attribute__((aligned(8))) u32x4_a8;
 
-constexpr int W4S_STAGE = 3072;      // bytes of one filter stage: 2 column blocks x 64 lanes x 24
-constexpr int W4S_TS = 2 * 6 * 4 * 36;   // slots of the t image: 2 regions x 6 transform rows x 4 tile rows x (18 columns x 2 channel halves)
+constexpr int W4S_STAGE = W4Lds::S_STAGE;      // bytes of one filter stage: 2 column blocks x 64 lanes x 24
+constexpr int W4S_TS = W4Lds::TS;       // slots of the t image: 2 regions x 6 transform rows x 4 tile rows x (18 columns x 2 channel halves), padded (wino4_lds_layout.h)
 
 __device__ __forceinline__ unsigned fbits(float v) { return __builtin_bit_cast(unsigned, v); }
 __device__ __forceinline__ float bfloat(unsigned v) { return __builtin_bit_cast(float, v); }
@@ -100,7 +102,7 @@ __global__ __launch_bounds__(768) void conv_wino4s_kernel(ConvParams p, int regs
         constexpr int k = decltype(kk)::value;
         W4S_DIAG_SKIP_FILTER_DMA();
         const unsigned long long g = w_base + (unsigned long long)W4S_DIAG_STAGE(stage) * (12 * W4S_STAGE);
-        const unsigned dst = lds_base + (unsigned)((2 * W4_HS + W4S_TS) * 16 + (wave * 2 + buf) * W4S_STAGE);
+        const unsigned dst = lds_base + (unsigned)((2 * W4_HS + W4S_TS) * 16 + W4Lds::s_stage(wave, buf));
         const unsigned l16 = lane16;
         unsigned keep;
         asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %3 offset:%4\n\ts_mov_b32 m0, %0"
@@ -111,12 +113,12 @@ __global__ __launch_bounds__(768) void conv_wino4s_kernel(ConvParams p, int regs
     const int q8 = li >> 2, tx = li & 3;
     const int tg = (0x96 >> q8) & 1;
     const int ty = (q8 == 0 || q8 == 1) ? 0 : (q8 == 2 || q8 == 3) ? 1 : (q8 == 4 || q8 == 5) ? 2 : 3;
-    // t image: slot(region, xi, tile row, column, half) = ((region * 6 + xi) * 4 + tile row) * 36 + half * 18 + P(column): the row
-    // stride 36 = 4 (mod 16) and the regrouped columns make the 16 lanes of a b128 group hit 16 different bank groups, as in the raw halo
-    const int t_lane = ((tg * 6 + xi) * 4 + ty) * 36 + lh * 18 + tx;
+    // t image (W4Lds, wino4_lds_layout.h): the 16 lanes of a b128 group - 4 x 4 tiles of one region - hit 16 different slots of the bank row, and
+    // so do the 16-lane groups of row_pass's 8-byte writes (tools/lds_bank_model.cpp walks both)
+    const int t_lane = W4Lds::t_lane(tg, xi, ty, lh, tx);
     // halo columns of a half row: half 0 needs columns 0..4 (points 0, +-a), half 1 columns 1..5 (points +-b, inf).  Both keep
     // columns 1..4 in t[1..4]; t[0] is column 0 (half 0) or column 5 (half 1): ONE wave-uniform slot offset, no second code path
-    const int xcol = hr ? w4_cpos(5) : w4_cpos(0);
+    const int xcol = hr ? W4Lds::t_col(5) : W4Lds::t_col(0);
     // column transform of a half row, with wave-uniform constants: e = t4 - kq t2, o = t3 - kq t1, points e +- kr o;
     // the third point is 0 (half 0: KP t0 + KS t2 + t4) or infinity (half 1: KP t1 + KS t3 + t0): stage 0 of both halves
     const float kq = hr ? KA2 : KB2, kr = hr ? KB : KA;
@@ -136,23 +138,32 @@ __global__ __launch_bounds__(768) void conv_wino4s_kernel(ConvParams p, int regs
     //      (tools/experiments/w4s_ablate.sh).  Now 288 threads transform the group cooperatively: item = (region, tile row, column,
     //      channel half): six raw rows in, t[xi = 0..5] out (12 fmas per channel, the +- rows share their even / odd parts), written
     //      to the t image; a wave then reads the five columns of ITS row: raw 28 KB + t 28 KB written + 60 KB read. ----
+    // row_pass's item and its two LDS byte addresses (raw buffer 0, transform row 0) do not depend on the group: formed once and pinned - left alone the
+    // compiler rebuilds them (~20 vector instructions beside the MFMA stream) in every copy of the pass
+    unsigned rp_raw, rp_t;
+    {
+        const int item = wave * 48 + lane, cpair = item & 1, h = (item >> 1) & 1, k = item >> 2;
+        const int x = k % 18, r2 = k / 18, tyy = r2 & 3, tgg = r2 >> 2;
+        rp_raw = (unsigned)(W4Lds::raw_read(0, tgg, tyy, x, h) * 16 + cpair * 8);
+        rp_t = (unsigned)((2 * W4_HS + W4Lds::t_write(tgg, tyy, h, x)) * 16 + cpair * 8);
+        asm volatile("" : "+v"(rp_raw), "+v"(rp_t));
+    }
     auto row_pass = [&](int grp) __attribute__((always_inline)) {
         // 576 half items (region, tile row, channel half, column, channel PAIR) over the 12 waves x 48 lanes: every wave carries the
         // same share (a pass run by five waves alone left the other seven waiting at the barrier behind it), 8-byte accesses,
         // neighbouring lanes on neighbouring addresses
         if (lane >= 48) return;
-        const int item = wave * 48 + lane, cpair = item & 1, h = (item >> 1) & 1, k = item >> 2;
-        const int x = k % 18, r2 = k / 18, tyy = r2 & 3, tgg = r2 >> 2;
-        const f32x2* R = reinterpret_cast<const f32x2*>(Hs + (grp & 1) * W4_HS + (tgg * 18 + 4 * tyy) * 36 + 2 * x + h) + cpair;     // raw row 4 tyy + i: + 36 i slots
-        const f32x2 d0 = R[2 * 36 * 0], d1 = R[2 * 36 * 1], d2 = R[2 * 36 * 2], d3 = R[2 * 36 * 3], d4 = R[2 * 36 * 4], d5 = R[2 * 36 * 5];
-        f32x2* T = reinterpret_cast<f32x2*>(Ts + ((tgg * 6) * 4 + tyy) * 36 + h * 18 + w4_pos(x)) + cpair;                            // + xi * 144 slots
+        const f32x2* R = reinterpret_cast<const f32x2*>(smem + rp_raw + (unsigned)(W4Lds::raw_read(grp & 1, 0, 0, 0, 0) * 16));     // raw row 4 tyy + i: + i rows
+        constexpr int RR = 2 * W4Lds::raw_row();
+        const f32x2 d0 = R[RR * 0], d1 = R[RR * 1], d2 = R[RR * 2], d3 = R[RR * 3], d4 = R[RR * 4], d5 = R[RR * 5];
+        f32x2* T = reinterpret_cast<f32x2*>(smem + rp_t);                            // + xi transform rows
         // t[xi] = c0 d[r0] + c1 d[r1] + c2 d[r2] + d[r3] as the SAME fma chains conv_wino4r_kernel's row_pass runs (one chain per row, innermost term
         // first): bit-identical t, hence bit-identical results in the fp32 kernel.  (A first version shared the even / odd parts of the +- rows,
         // 12 instead of 16 fmas per channel: the smooth fixture model's wrong-pixel total rose from 11 to 19 of ~15 hard pixels per image.)
         f32x2 o;
-#define W4_ROW3(XI, A0, DA, A1, DB, DC) do { _Pragma("unroll") for (int c = 0; c < 2; ++c) o[c] = __builtin_fmaf(A0, DA[c], __builtin_fmaf(A1, DB[c], DC[c])); T[2 * (XI) * 144] = o; } while (0)
+#define W4_ROW3(XI, A0, DA, A1, DB, DC) do { _Pragma("unroll") for (int c = 0; c < 2; ++c) o[c] = __builtin_fmaf(A0, DA[c], __builtin_fmaf(A1, DB[c], DC[c])); T[2 * (XI) * W4Lds::t_xi()] = o; } while (0)
 #define W4_ROW4(XI, A0, DA, A1, DB, A2, DC, DD) do { _Pragma("unroll") for (int c = 0; c < 2; ++c) \
-            o[c] = __builtin_fmaf(A0, DA[c], __builtin_fmaf(A1, DB[c], __builtin_fmaf(A2, DC[c], DD[c]))); T[2 * (XI) * 144] = o; } while (0)
+            o[c] = __builtin_fmaf(A0, DA[c], __builtin_fmaf(A1, DB[c], __builtin_fmaf(A2, DC[c], DD[c]))); T[2 * (XI) * W4Lds::t_xi()] = o; } while (0)
         W4_ROW3(0, KP, d0, KS, d2, d4);
         W4_ROW3(5, KP, d1, KS, d3, d5);
         W4_ROW4(1, -KA * KB2, d1, -KB2, d2, KA, d3, d4);
@@ -166,7 +177,7 @@ __global__ __launch_bounds__(768) void conv_wino4s_kernel(ConvParams p, int regs
     auto load_t = [&]() __attribute__((always_inline)) {
         const f32x4* A = Ts + t_lane;
         t[0] = A[xcol];
-        t[1] = A[w4_cpos(1)]; t[2] = A[w4_cpos(2)]; t[3] = A[w4_cpos(3)]; t[4] = A[w4_cpos(4)];
+        t[1] = A[W4Lds::t_col(1)]; t[2] = A[W4Lds::t_col(2)]; t[3] = A[W4Lds::t_col(3)]; t[4] = A[W4Lds::t_col(4)];
     };
     // ---- one point: column transform of the lane's 4 channels, exact 3-way bf16 split, 6 MFMAs; the three pieces of the next
     //      filter stage go out behind the first MFMAs ----
@@ -178,9 +189,9 @@ __global__ __launch_bounds__(768) void conv_wino4s_kernel(ConvParams p, int regs
         // 16-byte windows: 32).  Register budget (168 at three waves per SIMD; 96 accumulators + 20 of t[] are always live): block 0's
         // fragments are read first, the split runs under their latency, block 1's are read when the split's temporaries are dead -
         // the order is pinned (sched_barrier): the compiler's own schedule hoists all reads and spills.
-        const char* fp = Bs + (wave * 2 + fbuf) * W4S_STAGE;
-        const u32x4 b12a = reinterpret_cast<const u32x4*>(fp)[lane];
-        const u32x2 u3a = reinterpret_cast<const u32x2*>(fp + 2048)[lane];
+        const char* fp = Bs + W4Lds::s_stage(wave, fbuf);
+        const u32x4 b12a = *reinterpret_cast<const u32x4*>(fp + W4Lds::s_read16(lane, 0));
+        const u32x2 u3a = *reinterpret_cast<const u32x2*>(fp + W4Lds::s_read8(lane, 0));
         __builtin_amdgcn_sched_barrier(0);
         float V[4];
         if (P == 0) {
@@ -223,8 +234,8 @@ __global__ __launch_bounds__(768) void conv_wino4s_kernel(ConvParams p, int regs
         const bf16x8 A2 = __builtin_bit_cast(bf16x8, __builtin_shufflevector(a8, a8, 2, 3, 4, 5));      // [v1|v2]
         const bf16x8 A1 = __builtin_bit_cast(bf16x8, __builtin_shufflevector(a8, a8, 4, 5, 6, 7));      // [v2|v1]
         __builtin_amdgcn_sched_barrier(0);
-        const u32x4 b12b = reinterpret_cast<const u32x4*>(fp + 1024)[lane];
-        const u32x2 u3b = reinterpret_cast<const u32x2*>(fp + 2048 + 512)[lane];
+        const u32x4 b12b = *reinterpret_cast<const u32x4*>(fp + W4Lds::s_read16(lane, 1));
+        const u32x2 u3b = *reinterpret_cast<const u32x2*>(fp + W4Lds::s_read8(lane, 1));
         __builtin_amdgcn_sched_barrier(0);
         const bf16x8 B12a = __builtin_bit_cast(bf16x8, b12a), B3a = __builtin_bit_cast(bf16x8, u32x4{b12a[2], b12a[3], u3a[0], u3a[1]});
         const bf16x8 B12b = __builtin_bit_cast(bf16x8, b12b), B3b = __builtin_bit_cast(bf16x8, u32x4{b12b[2], b12b[3], u3b[0], u3b[1]});
@@ -372,14 +383,14 @@ __global__ __launch_bounds__(768) void conv_wino4s_kernel(ConvParams p, int regs
             const int tl = (e & 3) + 8 * (e >> 2) + 4 * lh;
             const float me = acc[0][cb][e], mp = acc[1][cb][e], mm = acc[2][cb][e];
             const float sm = mp + mm, df = mp - mm;
-            float* o = Rs + (xi * 4) * W4_RPLANE + tl * 32 + li;
+            float* o = Rs + W4Lds::r_fold(xi, tl, li);
             const float r1 = k1 * df, r2 = k2 * sm;
             if (add) {
-                o[0 * W4_RPLANE] += sm; o[1 * W4_RPLANE] += r1; o[2 * W4_RPLANE] += r2; o[3 * W4_RPLANE] += __builtin_fmaf(k3, df, me);
+                o[W4Lds::r_plane(0)] += sm; o[W4Lds::r_plane(1)] += r1; o[W4Lds::r_plane(2)] += r2; o[W4Lds::r_plane(3)] += __builtin_fmaf(k3, df, me);
                 // (four accumulator rows at a time: left alone, the compiler reads all 64 words first and spills accumulators for them)
                 if ((e & 3) == 3) __builtin_amdgcn_sched_barrier(0);
             } else {
-                o[0 * W4_RPLANE] = me + sm; o[1 * W4_RPLANE] = r1; o[2 * W4_RPLANE] = r2; o[3 * W4_RPLANE] = k3 * df;
+                o[W4Lds::r_plane(0)] = me + sm; o[W4Lds::r_plane(1)] = r1; o[W4Lds::r_plane(2)] = r2; o[W4Lds::r_plane(3)] = k3 * df;
             }
         }
     };
@@ -455,7 +466,7 @@ hipError_t launch_conv_wino4s(const ConvParams& p, hipStream_t s) {
     if (grid > 0x7fffffffull || !conv_wino4_span_ok(p, p.lut != nullptr ? p.per_image : 2)) return hipErrorInvalidValue;
     if (p.head_w != nullptr && (!p.head_only || p.pool.p != nullptr)) return hipErrorInvalidValue;     // (the HEAD kernels write neither the features nor a pool)
     size_t lds = (size_t)(2 * W4_HS + W4S_TS) * 16 + (size_t)12 * 2 * W4S_STAGE;
-    const size_t lds_epi = (size_t)24 * W4_RPLANE * 4;
+    const size_t lds_epi = (size_t)W4Lds::EPI_FLOATS * 4;
     if (lds_epi > lds) lds = lds_epi;
     void (*kern)(ConvParams, int, int, int) = p.head_w != nullptr ? conv_wino4s_kernel<true> : conv_wino4s_kernel<false>;
     static DeviceOnce attr_set[2];
