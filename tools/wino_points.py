@@ -153,47 +153,11 @@ if __name__ == '__main__':
 # "import tools.wino_points as w; print(w.kernel_order_error(5/8, 3/2, 64))"
 # ---------------------------------------------------------------------------------------------------------------------
 def kernel_order_error(a, b, cin, cout=16, tiles=64, seed=0):
-    rng = np.random.default_rng(seed)
-    d = f32(np.maximum(rng.normal(0, 1, (tiles, cin, 6, 6)), 0))
-    g = f32(rng.normal(0, np.sqrt(2.0 / (9 * cin)), (cout, cin, 3, 3)))
-    truth = np.zeros((tiles, cout, 4, 4))
-    for ky in range(3):
-        for kx in range(3):
-            truth += np.einsum('tcyx,oc->toyx', d[:, :, ky:ky + 4, kx:kx + 4], g[:, :, ky, kx])
-    a2, b2 = a * a, b * b
-    G = np.array([[1 / (a2 * b2), 0, 0],
-                  [1 / (2 * a2 * (a2 - b2)), a / (2 * a2 * (a2 - b2)), a2 / (2 * a2 * (a2 - b2))],
-                  [1 / (2 * a2 * (a2 - b2)), -a / (2 * a2 * (a2 - b2)), a2 / (2 * a2 * (a2 - b2))],
-                  [1 / (2 * b2 * (b2 - a2)), b / (2 * b2 * (b2 - a2)), b2 / (2 * b2 * (b2 - a2))],
-                  [1 / (2 * b2 * (b2 - a2)), -b / (2 * b2 * (b2 - a2)), b2 / (2 * b2 * (b2 - a2))],
-                  [0, 0, 1]])
-    U = f32(np.einsum('ik,ockl,jl->ocij', G, g, G))
-    rows = [(0, 2, 4, None, a2 * b2, -(a2 + b2), None), (1, 2, 3, 4, -a * b2, -b2, a), (1, 2, 3, 4, a * b2, -b2, -a),
-            (1, 2, 3, 4, -a2 * b, -a2, b), (1, 2, 3, 4, a2 * b, -a2, -b), (1, 3, 5, None, a2 * b2, -(a2 + b2), None)]
-    t = []
-    for r0, r1, r2, r3, c0, c1, c2 in rows:                         # t[xi] = row transform, (tiles, cin, 6 columns)
-        if r3 is None:
-            t.append(fma(c0, d[:, :, r0, :], fma(c1, d[:, :, r1, :], d[:, :, r2, :])))
-        else:
-            t.append(fma(c0, d[:, :, r0, :], fma(c1, d[:, :, r1, :], fma(c2, d[:, :, r2, :], d[:, :, r3, :]))))
-    t = np.stack(t, axis=2)                                          # (tiles, cin, xi, j)
-    u = [t[..., j] for j in range(6)]
-    ea, oa = fma(-b2, u[2], u[4]), fma(-b2, u[1], u[3])
-    eb, ob = fma(-a2, u[2], u[4]), fma(-a2, u[1], u[3])
-    V = np.stack([fma(a2 * b2, u[0], fma(-(a2 + b2), u[2], u[4])), fma(a, oa, ea), fma(-a, oa, ea), fma(b, ob, eb), fma(-b, ob, eb),
-                  fma(a2 * b2, u[1], fma(-(a2 + b2), u[3], u[5]))], axis=-1)      # (tiles, cin, xi, nu)
-    M = np.zeros((tiles, cout, 6, 6))
-    for c in range(cin):
-        M = fma(V[:, None, c], U[None, :, c], M)
-
-    def fold(m):                                                     # m: list of 6 arrays -> 4 outputs
-        s12, d12, s34, d34 = f32(m[1] + m[2]), f32(m[1] - m[2]), f32(m[3] + m[4]), f32(m[3] - m[4])
-        r0 = f32(f32(m[0] + s12) + s34)
-        r1 = fma(a, d12, f32(b * d34))
-        r2 = fma(a2, s12, f32(b2 * s34))
-        r3 = f32(fma(a2 * a, d12, f32(b2 * b * d34)) + m[5])
-        return [r0, r1, r2, r3]
-    R = np.stack(fold([M[..., j] for j in range(6)]), axis=-1)       # (tiles, cout, xi, 4)
-    Y = np.stack(fold([R[:, :, j, :] for j in range(6)]), axis=2)    # (tiles, cout, 4, 4)
-    scale = np.sqrt((truth ** 2).mean())
-    return float(np.sqrt(((Y - truth) ** 2).mean()) / scale)
+    """The replay itself lives in tests/wino4_ref.py, where the accuracy tests of the F(4x4) kernels run it on whole layers."""
+    import os
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    if root not in sys.path:
+        sys.path.insert(0, root)
+    from tests import wino4_ref
+    return wino4_ref.kernel_order_error(a, b, cin, cout=cout, tiles=tiles, seed=seed)
