@@ -16,7 +16,7 @@ EXPORTS = [
     'ecseg_segment_images', 'ecseg_segment_images_ex', 'ecseg_segment_images_dev', 'ecseg_set_images_per_group', 'ecseg_set_option', 'ecseg_preprocess', 'ecseg_u16_to_u8',
     'ecseg_meta_segment', 'ecseg_prefetch_input', 'ecseg_host_alloc', 'ecseg_host_free',
     'ecseg_stitch_argmax', 'ecseg_meta_inference', 'ecseg_meta_inference_dev', 'ecseg_count_cc', 'ecseg_ccl_labels',
-    'ecseg_count_colocalization', 'ecseg_count_hsr', 'ecseg_overlay', 'ecseg_nuclei_regions', 'ecseg_nucleus_crops', 'ecseg_fish_distances', 'ecseg_fish_spots', 'ecseg_min_cut', 'ecseg_nuset_forward', 'ecseg_rpn_proposals', 'ecseg_rpn_proposals_last', 'ecseg_marker_watershed', 'ecseg_clean_nuclei', 'ecseg_rescale_down', 'ecseg_rescale_mask_up', 'ecseg_get_timings',
+    'ecseg_count_colocalization', 'ecseg_count_hsr', 'ecseg_overlay', 'ecseg_nuclei_regions', 'ecseg_nucleus_crops', 'ecseg_fish_distances', 'ecseg_fish_spots', 'ecseg_fish_render', 'ecseg_min_cut', 'ecseg_nuset_forward', 'ecseg_rpn_proposals', 'ecseg_rpn_proposals_last', 'ecseg_marker_watershed', 'ecseg_clean_nuclei', 'ecseg_rescale_down', 'ecseg_rescale_mask_up', 'ecseg_get_timings',
     'ecseg_set_kernel_profiling', 'ecseg_get_conv_profile', 'ecseg_get_conv_executed_flops', 'ecseg_get_conv_launch_profile', 'ecseg_debug_peek', 'ecseg_lzw_decode', 'ecseg_lzw_encode',
     'ecseg_comm_unique_id', 'ecseg_comm_create', 'ecseg_comm_destroy', 'ecseg_comm_last_error', 'ecseg_allgather_records', 'ecseg_allgather_records_dev',
     'ecseg_npy_write_i64', 'ecseg_png_write_labels', 'ecseg_png_write', 'ecseg_png_write_channel', 'ecseg_npy_label_info', 'ecseg_npy_read_labels_u8', 'ecseg_tiff_write_gray8', 'ecseg_tiff_info', 'ecseg_tiff_read',
@@ -121,6 +121,7 @@ def load_library():
     lib.ecseg_fish_distances.argtypes = [vp, vp, i32, i32, u8p, i32, i32, i32, i32, vp, C.POINTER(C.c_int32)]
     lib.ecseg_fish_spots.argtypes = [vp, vp, i32, i32, u8p, i32, vp, i32, vp, i32, C.c_double, vp, i32, i32, i32, vp, vp, vp,
                                      C.POINTER(C.c_int32)]
+    lib.ecseg_fish_render.argtypes = [vp, u8p, i32, i32, i32, vp, u8p, i32, u8p, vp, vp, vp]
     lib.ecseg_min_cut.argtypes = [vp, vp, C.c_longlong, vp, i32, i32, vp, vp]
     lib.ecseg_nuset_forward.argtypes = [vp, vp, i32, i32, i32, i32, vp]
     lib.ecseg_rpn_proposals.argtypes = [vp, vp, vp, i32, i32, i32, vp, i32, i32, i32, C.c_float, i32, i32, C.POINTER(C.c_int32), vp, vp, vp]
@@ -548,6 +549,22 @@ class Handle:
             if n.value <= cap:
                 return rec[:n.value], thr, bnd
             cap = n.value
+
+    def fish_render(self, img, channels, thresholded, boundaries):
+        """(H, W, C) uint8 image, C = 3 or 4, with ``channels`` = the indices of its blue, green, red (and aqua) channel + the
+        (H, W, C - 1) masks and (H, W) boundaries of ``fish_spots`` -> the three (H, W, 3) uint8 RGB rasters stat_fish writes:
+        ``_original``, ``_original_with_segmentation`` and ``_lsq_`` (ecseg_fish_render; the rules are in include/ecseg_hip.h)."""
+        im, thr, bnd = _u8(img), _u8(thresholded), _u8(boundaries)
+        if im.ndim != 3 or thr.ndim != 3 or bnd.ndim != 2 or thr.shape[:2] != im.shape[:2] or bnd.shape != im.shape[:2]:
+            raise ValueError('fish_render takes an (H, W, C) image, (H, W, n_probe) masks and (H, W) boundaries of one extent')
+        ch = np.ascontiguousarray(channels, np.int32).reshape(-1)
+        if len(ch) != im.shape[2]:
+            raise ValueError('fish_render takes one channel index per image channel (blue, green, red[, aqua])')
+        H, W = bnd.shape
+        out = [np.empty((H, W, 3), np.uint8) for _ in range(3)]
+        self._check(self.lib.ecseg_fish_render(self.h, _ptr(im), H, W, im.shape[2], _ptr(ch), _ptr(thr), thr.shape[2], _ptr(bnd),
+                                               _ptr(out[0]), _ptr(out[1]), _ptr(out[2])), 'ecseg_fish_render')
+        return tuple(out)
 
     # ---- min-cut splitter -------------------------------------------------------------------------------
     MIN_CUT_MAX_DIST = 32          # ECSEG_MIN_CUT_MAX_DIST

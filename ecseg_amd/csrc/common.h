@@ -318,6 +318,20 @@ inline FishSpotBufs fishspot_bufs(Carver& c, const CellIndexBufs& cells, int H, 
 hipError_t run_fishspot(int32_t* labels, const uint8_t* img, int H, int W, int C, int np, const int ch[3], const double* wts, int K,
                         double normal_thr, const double ithr[3], int min_cc, int line_t, int n, const FishSpotBufs& b, hipStream_t s);
 
+// Device buffers of ecseg_fish_render for one H x W image of C channels: the inputs img (C bytes per pixel), thr (C - 1) and bnd
+// (1), and the three (H, W, 3) outputs orig, seg and lsq.
+struct FishRenderBufs { uint8_t* img; uint8_t* thr; uint8_t* bnd; uint8_t* orig; uint8_t* seg; uint8_t* lsq; };
+inline FishRenderBufs fish_render_bufs(Carver& c, int H, int W, int C) {
+    const size_t px = (size_t)H * W;
+    FishRenderBufs b;
+    b.img = c.take<uint8_t>(px * C); b.thr = c.take<uint8_t>(px * (C - 1)); b.bnd = c.take<uint8_t>(px);
+    b.orig = c.take<uint8_t>(px * 3); b.seg = c.take<uint8_t>(px * 3); b.lsq = c.take<uint8_t>(px * 3);
+    return b;
+}
+// The three colour files of stat_fish (:110-115,295-300) from b.img, b.thr and b.bnd into b.orig, b.seg and b.lsq, RGB.  C: 3 or
+// 4; ch: the image's blue, green, red and (C = 4) aqua channel, each inside 0 .. C - 1.
+hipError_t run_fish_render(int H, int W, int C, const int ch[4], const FishRenderBufs& b, hipStream_t s);
+
 // ---- launcher implemented in mincut_kernels.hip (src/max_flow_binary_mask.py:59-116) -----------------------------------------
 // n_tasks tasks of ecseg_min_cut, one workgroup each.  desc: (n_tasks, 8) int32 as the entry point takes them, validated by the
 // caller; soff: per task the byte offset of its mincut_scratch_bytes(h, w) bytes in `scratch` (16-byte aligned), or < 0 for a

@@ -1,5 +1,5 @@
 // The one-call drivers: each uploads its inputs, runs one family of kernels on the main stream and downloads the results
-// (u16_to_u8, stitch_argmax, meta_inference, the counts, overlay, the interSeg regions / crops, the FISH distances, the FISH spots, the min-cut tasks, NuSeT's mask and proposals).
+// (u16_to_u8, stitch_argmax, meta_inference, the counts, overlay, the interSeg regions / crops, the FISH distances, the FISH spots and their three colour files, the min-cut tasks, NuSeT's mask and proposals).
 #include "ctx.h"
 
 using namespace ecseg;
@@ -366,6 +366,44 @@ int ecseg_fish_spots(ecseg_ctx* h, const int32_t* labels, int H, int W, const ui
     HIP_TRY(h, hipMemcpyAsync(records, b.rec, (size_t)n * ECSEG_FISH_SPOT_INT64 * sizeof(int64_t), hipMemcpyDeviceToHost, s));
     HIP_TRY(h, hipStreamSynchronize(s));
     h->stage_ms[ECSEG_T_COUNT] += stage_elapsed(h->ev[2], h->ev[3]);
+    return ECSEG_OK;
+}
+
+// ---- stat_fish's three colour files (src/stat_fish.py:110-115,295-300) ------------------------------------------------------------
+int ecseg_fish_render(ecseg_ctx* h, const uint8_t* img, int H, int W, int C, const int32_t* channels, const uint8_t* thresholded,
+                      int n_probe, const uint8_t* boundaries, uint8_t* original, uint8_t* with_segmentation, uint8_t* lsq) {
+    if (!h) return ECSEG_E_INVALID;
+    drop_sent_ahead(h);
+    if (!img || !channels || !thresholded || !boundaries || !original || !with_segmentation || !lsq || H <= 0 || W <= 0)
+        return fail(h, ECSEG_E_INVALID, "fish_render: bad arguments");
+    if (C < 3 || C > 4) return fail(h, ECSEG_E_INVALID, "fish_render: the image must have 3 or 4 channels, not " + std::to_string(C));
+    if (n_probe != C - 1)
+        return fail(h, ECSEG_E_INVALID, "fish_render: n_probe must be C - 1 = " + std::to_string(C - 1) + " (one mask per FISH channel)");
+    int ch[4] = {0, 0, 0, 0};
+    for (int j = 0; j < C; ++j) {
+        ch[j] = channels[j];
+        if (ch[j] < 0 || ch[j] >= C)
+            return fail(h, ECSEG_E_INVALID, "fish_render: channel index out of range (the image has " + std::to_string(C) + " channels)");
+    }
+    if ((long long)H * W >= (1ll << 31)) return fail(h, ECSEG_E_INVALID, "fish_render: image too large (H * W must be below 2^31)");
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t px = (size_t)H * W;
+    int rc;
+    FishRenderBufs b{};
+    if ((rc = lay_out(h, h->call_arena, [&](Carver& c) { b = fish_render_bufs(c, H, W, C); }))) return rc;
+    hipStream_t s = h->stream;
+    for (float& v : h->stage_ms) v = 0.f;
+    HIP_TRY(h, hipMemcpyAsync(b.img, img, px * C, hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(b.thr, thresholded, px * n_probe, hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(b.bnd, boundaries, px, hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipEventRecord(h->ev[0], s));
+    HIP_TRY(h, run_fish_render(H, W, C, ch, b, s));
+    HIP_TRY(h, hipEventRecord(h->ev[1], s));
+    HIP_TRY(h, hipMemcpyAsync(original, b.orig, px * 3, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipMemcpyAsync(with_segmentation, b.seg, px * 3, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipMemcpyAsync(lsq, b.lsq, px * 3, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    h->stage_ms[ECSEG_T_COUNT] = stage_elapsed(h->ev[0], h->ev[1]);
     return ECSEG_OK;
 }
 

@@ -26,6 +26,10 @@
 //     the same unite / size / finalize, which here only counts.
 // Boundaries (get_boundaries, :91-107) on the dense ranks: fs_boundary_kernel, 64-bit sums of the 2 t taps of either axis.
 // fs_records_kernel writes the ECSEG_FISH_SPOT_INT64 fields of every cell.
+//
+// The three colour files (ecseg_fish_render, :110-115,295-300): fs_render_kernel composes _original, _original_with_segmentation
+// and _lsq_ in one elementwise pass, four pixels per thread: the image, the masks and the boundaries are read once as dwords, the
+// three (H, W, 3) RGB rasters leave as three dwords each.  All of it is integer arithmetic on bytes held in registers.
 #include "common.h"
 #include "cell_util.h"
 
@@ -247,6 +251,107 @@ __global__ __launch_bounds__(256) void fs_records_kernel(const u64* __restrict__
     o[19] = np >= 2 ? c[6] : 0;
     o[20] = np >= 2 ? c[7] : 0;
     o[21] = o[22] = o[23] = 0;
+}
+
+// ---- ecseg_fish_render ---------------------------------------------------------------------------------------------------
+struct FsRenderChannels { int blue, green, red, aqua; };
+static constexpr unsigned FS_AQUA_B = 54, FS_AQUA_G = 137, FS_AQUA_R = 233;      // aqua_rgb = [233, 137, 54] (:163), per BGR channel
+
+// One pixel.  pix: its C image bytes, channel c in bits 8 c .. 8 c + 7; t: its C - 1 mask bytes likewise; b: its boundary byte.
+// -> the three RGB pixels, red in bits 0..7, green in 8..15, blue in 16..23.
+//   merge_channels on the uint8 image (:295): coeff * aqua wraps to uint8 before / 255, so a channel gains 1 exactly when
+//     (coeff * aqua) & 255 == 255, saturating at 255;
+//   img_with_segmentation (:296): on a boundary blue and red become 255 and green (I - 255) as uint8 = (I + 1) & 255;
+//   _lsq_ (:297-300): BGR = (boundaries, mask 0, mask 1), each plus coeff * mask 2 / 255 (the quotient's floor: the sum is cut to
+//     uint8 after min(., 255)), saturating at 255.
+template <int C>
+__device__ __forceinline__ void fs_render_pixel(unsigned pix, unsigned t, unsigned b, const FsRenderChannels& ch, unsigned& orig,
+                                                unsigned& seg, unsigned& lsq) {
+    unsigned vb = (pix >> (8 * ch.blue)) & 255u, vg = (pix >> (8 * ch.green)) & 255u, vr = (pix >> (8 * ch.red)) & 255u;
+    unsigned lb = b, lg = t & 255u, lr = (t >> 8) & 255u;
+    if (C == 4) {
+        const unsigned q = (pix >> (8 * ch.aqua)) & 255u, m = (t >> 16) & 255u;
+        vb = min(255u, vb + (((FS_AQUA_B * q) & 255u) == 255u));
+        vg = min(255u, vg + (((FS_AQUA_G * q) & 255u) == 255u));
+        vr = min(255u, vr + (((FS_AQUA_R * q) & 255u) == 255u));
+        lb = min(255u, lb + FS_AQUA_B * m / 255u);
+        lg = min(255u, lg + FS_AQUA_G * m / 255u);
+        lr = min(255u, lr + FS_AQUA_R * m / 255u);
+    }
+    orig = vr | (vg << 8) | (vb << 16);
+    seg = b ? (255u | (((vg + 1u) & 255u) << 8) | (255u << 16)) : orig;
+    lsq = lr | (lg << 8) | (lb << 16);
+}
+
+// pixel k (0..3) of four 3-byte pixels packed in three dwords, in bits 0..23
+__device__ __forceinline__ unsigned fs_unpack3(const unsigned w[3], int k) {
+    return (k == 0 ? w[0] : k == 1 ? (w[0] >> 24) | (w[1] << 8) : k == 2 ? (w[1] >> 16) | (w[2] << 16) : w[2] >> 8) & 0xffffffu;
+}
+struct alignas(4) FsDword3 { unsigned x, y, z; };
+__device__ __forceinline__ FsDword3 fs_pack3(const unsigned p[4]) {
+    return FsDword3{p[0] | (p[1] << 24), (p[1] >> 8) | (p[2] << 16), (p[2] >> 16) | (p[3] << 8)};
+}
+
+// img (px, C), thr (px, C - 1), bnd (px) -> orig, seg, lsq (px, 3).  Thread g owns pixels 4 g .. 4 g + 3; every array starts on a
+// 256-byte boundary, so its group starts on a dword (C = 4: the image on 16 bytes).  The last group, when px % 4 != 0, goes byte by byte.
+template <int C>
+__global__ __launch_bounds__(256) void fs_render_kernel(const uint8_t* __restrict__ img, const uint8_t* __restrict__ thr,
+                                                        const uint8_t* __restrict__ bnd, unsigned px, FsRenderChannels ch,
+                                                        uint8_t* __restrict__ orig, uint8_t* __restrict__ seg, uint8_t* __restrict__ lsq) {
+    constexpr int NP = C - 1;
+    const unsigned g = blockIdx.x * 256u + threadIdx.x;      // px < 2^31: 4 g < 2^31 + 1024
+    const size_t p0 = (size_t)g * 4;
+    if (p0 >= px) return;
+    unsigned pix[4], t[4], b[4], o[4], s[4], l[4];
+    if (p0 + 4 <= px) {
+        if (C == 4) {
+            const uint4 v = *reinterpret_cast<const uint4*>(img + p0 * 4);
+            pix[0] = v.x; pix[1] = v.y; pix[2] = v.z; pix[3] = v.w;
+            const FsDword3 m = *reinterpret_cast<const FsDword3*>(thr + p0 * 3);
+            const unsigned mw[3] = {m.x, m.y, m.z};
+#pragma unroll
+            for (int k = 0; k < 4; ++k) t[k] = fs_unpack3(mw, k);
+        } else {
+            const FsDword3 v = *reinterpret_cast<const FsDword3*>(img + p0 * 3);
+            const unsigned vw[3] = {v.x, v.y, v.z};
+#pragma unroll
+            for (int k = 0; k < 4; ++k) pix[k] = fs_unpack3(vw, k);
+            const uint2 m = *reinterpret_cast<const uint2*>(thr + p0 * 2);
+            t[0] = m.x & 0xffffu; t[1] = m.x >> 16; t[2] = m.y & 0xffffu; t[3] = m.y >> 16;
+        }
+        const unsigned bw = *reinterpret_cast<const unsigned*>(bnd + p0);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            b[k] = (bw >> (8 * k)) & 255u;
+            fs_render_pixel<C>(pix[k], t[k], b[k], ch, o[k], s[k], l[k]);
+        }
+        *reinterpret_cast<FsDword3*>(orig + p0 * 3) = fs_pack3(o);
+        *reinterpret_cast<FsDword3*>(seg + p0 * 3) = fs_pack3(s);
+        *reinterpret_cast<FsDword3*>(lsq + p0 * 3) = fs_pack3(l);
+        return;
+    }
+    for (size_t p = p0; p < px; ++p) {
+        unsigned v = 0, m = 0, po, ps, pl;
+#pragma unroll
+        for (int c = 0; c < C; ++c) v |= (unsigned)img[p * C + c] << (8 * c);
+#pragma unroll
+        for (int c = 0; c < NP; ++c) m |= (unsigned)thr[p * NP + c] << (8 * c);
+        fs_render_pixel<C>(v, m, bnd[p], ch, po, ps, pl);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            orig[p * 3 + c] = (uint8_t)(po >> (8 * c));
+            seg[p * 3 + c] = (uint8_t)(ps >> (8 * c));
+            lsq[p * 3 + c] = (uint8_t)(pl >> (8 * c));
+        }
+    }
+}
+
+hipError_t run_fish_render(int H, int W, int C, const int ch[4], const FishRenderBufs& b, hipStream_t s) {
+    const unsigned px = (unsigned)H * (unsigned)W, groups = (px + 3u) / 4u, grid = (groups + 255u) / 256u;
+    const FsRenderChannels fc{ch[0], ch[1], ch[2], ch[3]};
+    if (C == 4) hipLaunchKernelGGL(fs_render_kernel<4>, dim3(grid), dim3(256), 0, s, b.img, b.thr, b.bnd, px, fc, b.orig, b.seg, b.lsq);
+    else hipLaunchKernelGGL(fs_render_kernel<3>, dim3(grid), dim3(256), 0, s, b.img, b.thr, b.bnd, px, fc, b.orig, b.seg, b.lsq);
+    return hipGetLastError();
 }
 
 hipError_t run_fishspot(int32_t* labels, const uint8_t* img, int H, int W, int C, int np, const int ch[3], const double* wts, int K,

@@ -10,7 +10,9 @@ skimage's order) - or, with ``use_min_cut: True``, labelled 4-connected and spli
 ``<name>_segmentation_corrected_min_cut.tif`` - and one more device call (``Handle.fish_spots`` -> ecseg_fish_spots, csrc/fishspot_kernels.hip) returns the
 per-nucleus integers, the cleaned spot masks and the boundary drawing; the host computes the projected Gaussian kernel
 (src/stat_fish.py:28-55) with numpy / scipy, forms the means as ``sum / count`` in float64 (exact: the sums are far below
-2^53) and writes the five files per image and ``stat_fish_lsq.csv``.  ``make interseg`` and ``make fish_distance_calculation``
+2^53) and writes the five files per image and ``stat_fish_lsq.csv``; the three colour files of every image (``_original``,
+``_original_with_segmentation``, ``_lsq_``) are composed by a third device call (``Handle.fish_render`` -> ecseg_fish_render), or by
+``render`` in numpy on a handle without it - the same bytes.  ``make interseg`` and ``make fish_distance_calculation``
 read the ``annotated/`` folder this leaves behind.
 
 The parameters of the reference's ``src/stat_fish_params.yaml`` are built in (``DEFAULT_PARAMS``); a ``src/stat_fish_params.yaml``
@@ -21,17 +23,36 @@ The reference indexes its arrays as BGR (``cv2.imread``); the TIFF reader here r
 channels 2 / 1 / 0 and the indices are mapped, the image is not copied.  A ``.npy`` image is indexed as the reference indexes
 it: channel 0 blue, 1 green, 2 red.
 
+The third probe, aqua (:193): an ``(H, W, 4)`` uint8 / uint16 ``.npy`` image (blue, green, red, aqua) is taken when
+``color_sensitivity`` has at least three entries.  Its probes are green, red and aqua, the "green and red" pair stays probes 0 and
+1, the CSV gains the four aqua columns after red's (:280-284) and the ``_lsq_`` name its ``aq`` part (:291).  ``merge_channels``
+(:110-115) folds the aqua channel into the colour files twice, with ``aqua_rgb = [233, 137, 54]``: into the image (:295), where
+``coeff * I[..., -1]`` is a Python int times a uint8 array and wraps modulo 256 before ``/ 255``, so that a colour channel gains 1
+where ``(coeff * aqua) & 255 == 255`` and the merge is almost a no-op (aqua 255 leaves blue 3 at 3; on an int copy it would become 57) -
+the reference's behaviour, reproduced and not corrected, and ``_original.tif`` holds that merged image (:307); and into the ``_lsq_``
+array (:297-299), an int array, where nothing wraps: an aqua spot adds (54, 137, 233) to (boundaries, green, red), lights all three
+channels, and ``make fish_distance_calculation`` then reads it as green and red FISH - the reference's behaviour too, kept.  A
+4-sample TIFF keeps losing its fourth sample, as ``cv2.imread`` drops it.
+
 The NaN-scale branch (:238-240; ``scale: auto`` on an image without nuclei) yields an all-zero ``thresholded``: the device is
 still called for regions, raw intensities and boundaries, with intensity thresholds of +infinity, which no pixel exceeds.
 
 Divergences from the reference, all on inputs it crashes on or leaves to chance: images are processed in sorted order; a
-per-image failure (missing mask, unreadable file, 4-channel image - the two-entry ``color_sensitivity`` cannot broadcast over
-three probes in the reference either -, 16-bit TIFF - ``cv2.imread``'s internal 16-to-8 conversion cannot be pinned without
+per-image failure (missing mask, unreadable file, 4-channel image under a ``color_sensitivity`` of fewer than three entries - two entries cannot
+broadcast over three probes in the reference either (:85) -, 16-bit TIFF - ``cv2.imread``'s internal 16-to-8 conversion cannot be pinned without
 OpenCV -) is reported, skipped and turns the exit code to 1 while the other images' outputs are still written;
 configuration errors exit with code 2; ``use_min_cut: True`` is one of them when the handle in use has no ``min_cut`` method (the
 library's own ``Handle`` has it; the max_flow_binary_mask splitter needs its device call); integer CSV columns are always written as integers (pandas promotes them to
-float when it concatenates an image without nuclei with others).  Kept as in the reference: with ``scale: auto`` the scale
+float when it concatenates an image without nuclei with others); in a folder that mixes 3- and 4-channel images the CSV has the aqua
+columns as soon as one processed image had four channels, always after red's, and the rows of the 3-channel images leave those four
+fields empty (the reference cannot run such a folder at all - three entries do not broadcast over a 3-channel image's two probes,
+which here take the first two -; ``pd.concat`` puts the columns in order of first appearance, so that a leading 3-channel image moves the aqua columns
+to the end, and would promote the aqua integer columns to float beside the missing values).  Kept as in the reference: with ``scale: auto`` the scale
 of the FIRST image is used for every later image (:228 overwrites the variable).
+
+A side effect on the process: ``main`` calls ``keep_freed_memory`` (glibc's ``mallopt``), so that the multi-megabyte arrays of one
+image are recycled for the next instead of going back to the kernel between the device calls; ``ECSEG_MALLOC_DEFAULT=1`` switches
+that off.
 """
 import datetime
 import math
@@ -56,7 +77,9 @@ DEFAULT_PARAMS = {
     'flow_limit': 60,
 }
 PARAMS_FILE = os.path.join('src', 'stat_fish_params.yaml')
-PROBE_NAMES = ('green', 'red')
+PROBE_NAMES = ('green', 'red')                   # the probes every image has; a fourth channel adds THIRD_PROBE (:191-193)
+THIRD_PROBE = 'aqua'
+AQUA_BGR = (54, 137, 233)                        # aqua_rgb = [233, 137, 54] (:163) as merge_channels applies it, reversed
 MAX_KERNEL = 63                # ECSEG_FISH_SPOT_MAX_KERNEL
 MAX_LINE = 16                  # ECSEG_FISH_SPOT_MAX_LINE
 MAX_DIST = 32                  # ECSEG_MIN_CUT_MAX_DIST
@@ -71,10 +94,10 @@ class ConfigError(Exception):
     pass
 
 
-def csv_columns():
-    """Column order of src/stat_fish.py:277-288."""
+def csv_columns(n_probe=2):
+    """Column order of src/stat_fish.py:277-288; with ``n_probe=3`` the four aqua columns stand after red's (:280-284)."""
     cols = ['image_name', 'nucleus_center']
-    for name in PROBE_NAMES:
+    for name in (PROBE_NAMES + (THIRD_PROBE,))[:n_probe]:
         cols += ['#_FISH_pixels (%s)' % name, '#_FISH_foci (%s)' % name, 'Avg fish intensity (%s)' % name,
                  'Max fish intensity (%s)' % name]
     return cols + ['#_DAPI_pixels', '#_FISH_pixels (green and red)', '#_FISH_foci (green and red)']
@@ -137,20 +160,70 @@ def get_scale(areas, target_median_nuclei_size):
     return float(np.sqrt(target_median_nuclei_size / np.median(areas)))
 
 
-def rows_from_records(img_name, records):
-    """CSV rows of one image from the records of ecseg_fish_spots (src/stat_fish.py:249-288)."""
+def rows_from_records(img_name, records, n_probe=2):
+    """CSV rows of one image from the records of ecseg_fish_spots (src/stat_fish.py:249-288), laid out as ``csv_columns(n_probe)``."""
     rows = []
     for r in np.asarray(records, np.int64).reshape(-1, 24).tolist():
         row = [img_name, '%d_%d' % (r[2] // r[1], r[3] // r[1])]
-        for j in range(len(PROBE_NAMES)):
+        for j in range(n_probe):
             pixels, foci, total, count, peak = r[4 + 5 * j:9 + 5 * j]
             row += [pixels, foci, (total / count) if count else 0.0, peak]
         rows.append(row + [r[1], r[19], r[20]])
     return rows
 
 
-def read_image(path, handle):
-    """-> ((H, W, 3) uint8 image, (blue, green, red) channel indices into it) (src/stat_fish.py:206-212)."""
+def widen_rows(rows):
+    """Rows laid out as ``csv_columns(2)`` -> as ``csv_columns(3)``, the four aqua fields empty; rows that have them pass."""
+    at, wide = 2 + 4 * len(PROBE_NAMES), len(csv_columns(3))
+    return [r if len(r) == wide else r[:at] + [''] * 4 + r[at:] for r in rows]
+
+
+def keep_freed_memory():
+    """Tells glibc's allocator to keep what the process frees (``mallopt``: no trimming of the heap top, no ``mmap`` below 32 MiB, 256
+    MiB of top padding) -> True when that was done.  Every image allocates and frees a dozen arrays of 1.4 - 6 MB around its device
+    calls; with the default policy they come from and go back to the kernel each time, and unmapping memory the GPU runtime has just
+    copied from or to makes the driver take the process's queues off the GPU and put them back about 10 ms later, which the next device
+    call waits for (DESIGN.md 5.9 has the measurements).  With the arrays recycled inside the process that does not happen, and
+    the page faults of fresh memory go as well.  The cost is that the process keeps its peak of freed memory (about 100 MB at 1040 x
+    1392).  ``ECSEG_MALLOC_DEFAULT=1`` in the environment leaves the allocator alone; so does a C library without ``mallopt``."""
+    import ctypes
+    if os.environ.get('ECSEG_MALLOC_DEFAULT', '0') not in ('', '0'):
+        return False
+    try:
+        mallopt = ctypes.CDLL(None).mallopt
+    except (OSError, AttributeError):
+        return False
+    M_TRIM_THRESHOLD, M_TOP_PAD, M_MMAP_THRESHOLD = -1, -2, -3
+    ok = [mallopt(M_TRIM_THRESHOLD, 2 ** 31 - 1), mallopt(M_TOP_PAD, 256 << 20), mallopt(M_MMAP_THRESHOLD, 32 << 20)]
+    return all(v == 1 for v in ok)
+
+
+def merge_aqua(bgr, aqua):
+    """``merge_channels`` (:110-115) on the uint8 image as :295 calls it, in integers: ``coeff * aqua`` is a Python int times a uint8
+    array and wraps modulo 256 before ``/ 255``, so a channel gains 1 where ``(coeff * aqua) & 255 == 255`` and nothing elsewhere,
+    saturating at 255.  ``bgr``: the three (H, W) uint8 planes blue, green, red -> the three merged planes."""
+    q = np.asarray(aqua).astype(np.int32)
+    return [np.minimum(np.asarray(a).astype(np.int32) + (((k * q) & 255) == 255), 255).astype(np.uint8) for a, k in zip(bgr, AQUA_BGR)]
+
+
+def render(img, channels, thresholded, boundaries):
+    """The three colour files of :295-300,306-308 in numpy, what ``Handle.fish_render`` computes on the device: (H, W, C) uint8 image
+    with ``channels`` = its (blue, green, red[, aqua]) indices, the (H, W, C - 1) masks and the (H, W) boundaries -> the RGB rasters
+    (_original, _original_with_segmentation, _lsq_).  The _lsq_ merge runs on an int array in the reference and does not wrap:
+    ``min(255, x + coeff * mask / 255)``."""
+    bgr = [img[..., c] for c in channels[:3]]
+    lsq = [boundaries, thresholded[..., 0], thresholded[..., 1]]
+    if len(channels) > 3:
+        bgr = merge_aqua(bgr, img[..., channels[3]])
+        m = thresholded[..., 2].astype(np.int32)
+        lsq = [np.minimum(x.astype(np.int32) + k * m // 255, 255).astype(np.uint8) for x, k in zip(lsq, AQUA_BGR)]
+    original = np.stack(bgr[::-1], axis=-1)                  # the writers store RGB; cv2 writes its BGR arrays as RGB
+    return original, with_segmentation(original, boundaries, 1), np.stack(lsq[::-1], axis=-1)
+
+
+def read_image(path, handle, max_probes=2):
+    """-> ((H, W, C) uint8 image, its (blue, green, red[, aqua]) channel indices) (src/stat_fish.py:206-212).  C is 3, or 4 for a
+    four-channel ``.npy`` when ``max_probes`` (the entries of ``color_sensitivity``) is at least 3."""
     from . import image_io
     try:
         I = image_io.imread(path)
@@ -158,6 +231,10 @@ def read_image(path, handle):
         raise ImageError('cannot be read (%s)' % e)
     is_npy = path.lower().endswith('.npy')
     if is_npy:
+        if I.ndim == 3 and I.shape[2] == 4 and I.dtype in (np.uint8, np.uint16) and max_probes >= 3:
+            if I.dtype == np.uint16:
+                I = handle.u16_to_u8(np.ascontiguousarray(I))
+            return np.ascontiguousarray(I), (0, 1, 2, 3)
         if I.ndim != 3 or I.shape[2] != 3 or I.dtype not in (np.uint8, np.uint16):
             raise ImageError("isn't an (H, W, 3) uint8 / uint16 array (shape %s, %s); a fourth channel needs a third "
                              "color_sensitivity entry, which the reference cannot take either" % (I.shape, I.dtype))
@@ -194,14 +271,17 @@ def read_mask(path):
 
 
 def process_image(path, mask_path, out_root, params, scale, handle, stats=None, use_min_cut=False, segment=None):
-    """One image of src/stat_fish.py:199-308 -> (CSV rows, the scale that was used).  ``use_min_cut`` (:221-224): the label map comes
+    """One image of src/stat_fish.py:199-308 -> (CSV rows, the scale that was used); the rows of a four-channel image carry the aqua
+    fields of ``csv_columns(3)``, and ``stats['probes']`` becomes 3 once such an image was seen (it may have no nucleus and no row).  The three colour files come from ``handle.fish_render`` when the handle has it, else from
+    ``render``, which writes the same bytes.  ``use_min_cut`` (:221-224): the label map comes
     from the min-cut splitter, already numbered 1..n (its cells need not be connected, which ecseg_fish_spots allows).  ``segment``
     (config key ``nuset_weights``): the mask is ``segment(blue channel)`` (:212-214) instead of the file ``mask_path``."""
     import time
     from . import image_io
     t0 = time.perf_counter()
     img_name = os.path.basename(path)[:-4]
-    I, (blue, green, red) = read_image(path, handle)
+    I, channels = read_image(path, handle, len(params['color_sensitivity']))
+    blue = channels[0]
     mask = read_mask(mask_path) if segment is None else segment(I[:, :, blue])
     imheight, imwidth = mask.shape
     I = np.ascontiguousarray(I[:imheight, :imwidth])
@@ -209,7 +289,7 @@ def process_image(path, mask_path, out_root, params, scale, handle, stats=None, 
     if mask.size == 0:
         raise ImageError('is empty')
     t1 = time.perf_counter()
-    probes = [green, red]
+    probes = list(channels[1:])                              # green, red[, aqua]
     line = params['line_thickness']
     visualization = None
     try:
@@ -241,15 +321,10 @@ def process_image(path, mask_path, out_root, params, scale, handle, stats=None, 
     ranks = lut[labels]
     annotated_path = os.path.join(out_root, img_name)
     os.makedirs(annotated_path, exist_ok=True)
-    rgb = (blue, green, red) == (2, 1, 0)
-    original = I if rgb else np.ascontiguousarray(I[..., ::-1])            # the writers store RGB; cv2 writes its BGR arrays as RGB
-    lsq = np.empty(I.shape[:2] + (3,), np.uint8)                           # BGR (boundaries, green, red) -> RGB (red, green, boundaries)
-    lsq[..., 0] = thr[..., 1]
-    lsq[..., 1] = thr[..., 0]
-    lsq[..., 2] = bnd
+    original, segmented, lsq = (handle.fish_render if hasattr(handle, 'fish_render') else render)(I, channels, thr, bnd)
     image_io.write_npy_int64(os.path.join(annotated_path, img_name + '__segmentation_min_cut.npy'), ranks)
     image_io.write_tiff_gray8(os.path.join(annotated_path, img_name + '_segmentation.tif'), mask)
-    image_io.write_tiff_rgb8(os.path.join(annotated_path, img_name + '_original_with_segmentation.tif'), with_segmentation(original, bnd, 1))
+    image_io.write_tiff_rgb8(os.path.join(annotated_path, img_name + '_original_with_segmentation.tif'), segmented)
     image_io.write_tiff_rgb8(os.path.join(annotated_path, img_name + '_original.tif'), original)
     image_io.write_tiff_rgb8(os.path.join(annotated_path, lsq_name(img_name, params, stdev, min_cc)), lsq)
     if visualization is not None:                            # (:304-305) cv2 writes its (r, g, b) array as if it were BGR: the file holds (b, g, r)
@@ -259,7 +334,8 @@ def process_image(path, mask_path, out_root, params, scale, handle, stats=None, 
         for key, v in (('read', t1 - t0), ('device', t2 - t1), ('write', time.perf_counter() - t2)):
             stats[key] = stats.get(key, 0.0) + v
         stats['nuclei'] = stats.get('nuclei', 0) + len(rec)
-    return rows_from_records(img_name, rec), scale
+        stats['probes'] = max(stats.get('probes', len(PROBE_NAMES)), len(probes))
+    return rows_from_records(img_name, rec, len(probes)), scale
 
 
 def load_params():
@@ -369,7 +445,8 @@ def current_commit():
 def main(argv=None, handle=None):
     """``make stat_fish``.  Like the reference's ``main`` it takes everything from section ``stat_fish`` of ``config.yaml`` in
     the working directory; ``argv`` is accepted for the shim's sake and not read.  ``handle`` is an injection point for tests and
-    tools (anything with ``Handle.ccl_labels``, ``fish_spots`` and ``u16_to_u8``, and ``min_cut`` for ``use_min_cut: True``); without it the call opens a handle on device 0
+    tools (anything with ``Handle.ccl_labels``, ``fish_spots`` and ``u16_to_u8``, and ``min_cut`` for ``use_min_cut: True``; ``fish_render``
+    is used when it is there); without it the call opens a handle on device 0
     and closes it at the end."""
     import yaml
     from . import csvio
@@ -419,13 +496,14 @@ def main(argv=None, handle=None):
     if own:
         from ._lib import Handle
         handle = Handle(0)
-    rows, failed = [], []
+    keep_freed_memory()
+    rows, failed, seen = [], [], {}
     try:
         for p in image_paths:
             print("Processing image: ", p)
             try:
                 img_rows, scale = process_image(p, os.path.join(masks, os.path.basename(p)[:-4] + '.tif'), out_root, params, scale, handle,
-                                                 use_min_cut=use_min_cut,
+                                                 stats=seen, use_min_cut=use_min_cut,
                                                  segment=None if segmenter is None else (lambda blue: segmenter(blue, handle)))
                 rows += img_rows
             except ImageError as e:
@@ -435,7 +513,8 @@ def main(argv=None, handle=None):
         if own:
             handle.close()
     with open(os.path.join(out_root, 'stat_fish_lsq.csv'), 'w') as f:
-        f.write(csvio.csv_text(csv_columns(), rows))
+        n_probe = seen.get('probes', len(PROBE_NAMES))
+        f.write(csvio.csv_text(csv_columns(n_probe), widen_rows(rows) if n_probe == 3 else rows))
 
     annotated = os.path.join(inpath, 'annotated')
     if os.path.isdir(annotated):

@@ -44,6 +44,7 @@ extern "C" {
 /* (still 5 - additive: ecseg_fish_distances, the per-nucleus records of fish_distance_calculation; nothing existing changed.) */
 /* (still 5 - additive: ecseg_fish_spots, the per-nucleus records, masks and boundaries of stat_fish, and ecseg_tiff_write_rgb8; ecseg_npy_write_i32_as_i64
  * beside ecseg_npy_write_i64; nothing existing changed.) */
+/* (still 5 - additive: ecseg_fish_render, the three colour files of stat_fish for 3- and 4-channel images; nothing existing changed.) */
 #define ECSEG_ABI_VERSION 5
 
 #define ECSEG_OK             0
@@ -355,6 +356,26 @@ int ecseg_fish_spots(ecseg_ctx* h, const int32_t* labels, int H, int W, const ui
                      int n_probe, const double* weights, int K, double normal_threshold, const double* intensity_thresholds,
                      int min_cc_size, int line_thickness, int capacity, uint8_t* thresholded, uint8_t* boundaries,
                      int64_t* records, int32_t* n_cells);
+
+/* Composes, for ONE image, the three colour files stat_fish writes beside the label map and the mask (:110-115,295-300,306-308):
+ * merge_channels on the image, img_with_segmentation, and blob_labeled_img with its merge_channels.  img: (H, W, C) uint8, C = 3
+ * or 4.  channels: C indices into img - its blue, green, red and (C = 4) aqua channel; the reference's arrays are BGR(A), a TIFF
+ * read as RGB passes (2, 1, 0).  thresholded (H, W, n_probe) uint8 with n_probe = C - 1 and boundaries (H, W) uint8 as
+ * ecseg_fish_spots returned them for the probes (green, red[, aqua]).  With k = (54, 137, 233) for (blue, green, red) - aqua_rgb
+ * of :163 reversed - and q the aqua byte of a pixel, in integers:
+ *   merged    c = min(255, img c + [((k_c * q) & 255) == 255]) for C = 4, img c for C = 3.  (:114 multiplies a Python int with a
+ *             uint8 array: the product wraps modulo 256 BEFORE "/ 255", so the merge adds at most 1.  Reproduced, not corrected.)
+ *   original  = merged                                                                        (:307 writes the merged image)
+ *   with_segmentation = merged, and on boundaries != 0: blue = red = 255, green = (merged green + 1) & 255             (:296)
+ *   lsq       blue = min(255, boundaries + k_b * m / 255), green = min(255, thresholded[0] + k_g * m / 255), red = min(255,
+ *             thresholded[1] + k_r * m / 255), "/" flooring, m = thresholded[2] for C = 4 and 0 for C = 3 (:297-300, no wrap: that
+ *             array is int).  An aqua spot lights all three channels, which fish_distance_calculation then reads as green and red
+ *             FISH: the reference's behaviour, kept.
+ * Outputs: three (H, W, 3) uint8 rasters in the order the TIFF writers store, RGB (cv2.imwrite stores its BGR arrays so).  One
+ * elementwise kernel; one image per call, synchronous, buffers of its own; its device time in ECSEG_T_COUNT.  ECSEG_E_INVALID: C
+ * outside 3..4, n_probe != C - 1, a channel index outside 0 .. C - 1, H * W >= 2^31. */
+int ecseg_fish_render(ecseg_ctx* h, const uint8_t* img, int H, int W, int C, const int32_t* channels, const uint8_t* thresholded,
+                      int n_probe, const uint8_t* boundaries, uint8_t* original, uint8_t* with_segmentation, uint8_t* lsq);
 
 /* ---- the min-cut nucleus splitter: a batch of grid max-flows (src/max_flow_binary_mask.py:59-116) ------------------------- */
 /* Replaces get_graph + max_flow + partition_min_cut (:59-116) for a BATCH of independent tasks; segment_min_cut's recursion
