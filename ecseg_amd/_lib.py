@@ -16,7 +16,7 @@ EXPORTS = [
     'ecseg_segment_images', 'ecseg_segment_images_ex', 'ecseg_segment_images_dev', 'ecseg_set_images_per_group', 'ecseg_set_option', 'ecseg_preprocess', 'ecseg_u16_to_u8',
     'ecseg_meta_segment', 'ecseg_prefetch_input', 'ecseg_host_alloc', 'ecseg_host_free',
     'ecseg_stitch_argmax', 'ecseg_meta_inference', 'ecseg_meta_inference_dev', 'ecseg_count_cc', 'ecseg_ccl_labels',
-    'ecseg_count_colocalization', 'ecseg_count_hsr', 'ecseg_overlay', 'ecseg_nuclei_regions', 'ecseg_nucleus_crops', 'ecseg_fish_distances', 'ecseg_fish_spots', 'ecseg_fish_render', 'ecseg_min_cut', 'ecseg_nuset_forward', 'ecseg_rpn_proposals', 'ecseg_rpn_proposals_last', 'ecseg_marker_watershed', 'ecseg_clean_nuclei', 'ecseg_rescale_down', 'ecseg_rescale_mask_up', 'ecseg_get_timings',
+    'ecseg_count_colocalization', 'ecseg_count_hsr', 'ecseg_overlay', 'ecseg_nuclei_regions', 'ecseg_nucleus_crops', 'ecseg_fish_distances', 'ecseg_fish_spots', 'ecseg_fish_render', 'ecseg_min_cut', 'ecseg_nuset_forward', 'ecseg_rpn_proposals', 'ecseg_rpn_proposals_last', 'ecseg_marker_watershed', 'ecseg_marker_watershed_batch', 'ecseg_marker_watershed_batch_bytes', 'ecseg_clean_nuclei', 'ecseg_rescale_down', 'ecseg_rescale_mask_up', 'ecseg_get_timings',
     'ecseg_set_kernel_profiling', 'ecseg_get_conv_profile', 'ecseg_get_conv_executed_flops', 'ecseg_get_conv_launch_profile', 'ecseg_debug_peek', 'ecseg_lzw_decode', 'ecseg_lzw_encode',
     'ecseg_comm_unique_id', 'ecseg_comm_create', 'ecseg_comm_destroy', 'ecseg_comm_last_error', 'ecseg_allgather_records', 'ecseg_allgather_records_dev',
     'ecseg_npy_write_i64', 'ecseg_png_write_labels', 'ecseg_png_write', 'ecseg_png_write_channel', 'ecseg_npy_label_info', 'ecseg_npy_read_labels_u8', 'ecseg_tiff_write_gray8', 'ecseg_tiff_info', 'ecseg_tiff_read',
@@ -127,6 +127,8 @@ def load_library():
     lib.ecseg_rpn_proposals.argtypes = [vp, vp, vp, i32, i32, i32, vp, i32, i32, i32, C.c_float, i32, i32, C.POINTER(C.c_int32), vp, vp, vp]
     lib.ecseg_rpn_proposals_last.argtypes = [vp, i32, vp, i32, i32, i32, C.c_float, i32, i32, C.POINTER(C.c_int32), vp, vp, vp]
     lib.ecseg_marker_watershed.argtypes = [vp, vp, i32, i32, vp, vp, vp, C.c_longlong, vp]
+    lib.ecseg_marker_watershed_batch.argtypes = [vp, vp, C.c_longlong, vp, i32, vp, vp, vp, C.c_longlong, vp]
+    lib.ecseg_marker_watershed_batch_bytes.argtypes = [vp, i32, vp]; lib.ecseg_marker_watershed_batch_bytes.restype = C.c_longlong
     lib.ecseg_clean_nuclei.argtypes = [vp, vp, i32, i32, i32, vp, vp, C.POINTER(C.c_double)]
     lib.ecseg_rescale_down.argtypes = [vp, vp, i32, i32, i32, i32, vp, i32, vp, i32, vp, vp]
     lib.ecseg_rescale_mask_up.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp]
@@ -660,6 +662,74 @@ class Handle:
         out = np.empty(m.shape, np.uint8)
         self._check(self.lib.ecseg_marker_watershed(self.h, _ptr(m), m.shape[0], m.shape[1], _ptr(r), _ptr(c), _ptr(l), len(r), _ptr(out)),
                     'ecseg_marker_watershed')
+        return out
+
+    WATERSHED_BATCH_MAX_IMAGES = 1024     # ECSEG_WATERSHED_BATCH_MAX_IMAGES
+
+    def marker_watershed_packed(self, masks, images, rows, cols, labels):
+        """ecseg_marker_watershed_batch as it is: ``masks`` a 1-D uint8 buffer, ``images`` (n, 5) int64 rows (byte offset, H, W, first
+        marker, markers), the three int32 marker lists of all images -> the uint8 buffer of the results, laid out as ``masks`` and 0
+        outside every image."""
+        buf = np.ascontiguousarray(masks, np.uint8).reshape(-1)
+        tab = np.ascontiguousarray(images, np.int64).reshape(-1, 5)
+        r, c, l = (np.ascontiguousarray(a, np.int32).reshape(-1) for a in (rows, cols, labels))
+        if not (len(r) == len(c) == len(l)):
+            raise ValueError('marker_watershed_packed: rows, cols and labels differ in length')
+        out = np.empty(buf.size, np.uint8)
+        self._check(self.lib.ecseg_marker_watershed_batch(self.h, _ptr(buf), buf.size, _ptr(tab), len(tab), _ptr(r), _ptr(c), _ptr(l), len(r),
+                                                          _ptr(out)), 'ecseg_marker_watershed_batch')
+        return out
+
+    def marker_watershed_batch(self, masks, markers, budget_bytes=8 << 30):
+        """``marker_watershed`` over a list of images at once (ecseg_marker_watershed_batch: one flood wave per image, side by side).
+        ``masks``: a list of (H, W) bool / integer masks of any extents; ``markers``: per mask its ``(rows, cols, labels)``, or None
+        for "leave the mask as it is" (what ``nuset.watershed_markers`` returns for its two early branches): such an image does not go
+        to the device and comes back as given.  -> the list of uint8 (H, W) results, each the bytes ``marker_watershed`` gives that image
+        alone.  The images are packed back to back and go in one call while ecseg_marker_watershed_batch_bytes stays within
+        ``budget_bytes`` of device scratch (and WATERSHED_BATCH_MAX_IMAGES images), else in several calls over consecutive images;
+        an image that exceeds the budget alone goes alone."""
+        if len(masks) != len(markers):
+            raise ValueError('marker_watershed_batch takes one marker entry (or None) per mask')
+        out = [None] * len(masks)
+        todo = []                                              # (position, mask, rows, cols, labels, foreground pixels)
+        for k, (mask, mk) in enumerate(zip(masks, markers)):
+            if mk is None:
+                out[k] = mask
+                continue
+            m = self._mask_u8(mask, 'marker_watershed_batch')
+            r, c, l = (np.ascontiguousarray(a, np.int32).reshape(-1) for a in mk)
+            if not (len(r) == len(c) == len(l)):
+                raise ValueError('marker_watershed_batch: rows, cols and labels of image %d differ in length' % k)
+            todo.append((k, m, r, c, l, int(np.count_nonzero(m))))
+
+        def table(chunk):
+            tab, off, first = np.zeros((len(chunk), 5), np.int64), 0, 0
+            for j, (_, m, r, _, _, _) in enumerate(chunk):
+                tab[j] = (off, m.shape[0], m.shape[1], first, len(r))
+                off += m.size
+                first += len(r)
+            return tab
+
+        def need(chunk):
+            tab = table(chunk)
+            fg = np.array([e[5] for e in chunk], np.int64)
+            return self.lib.ecseg_marker_watershed_batch_bytes(_ptr(tab), len(tab), _ptr(fg))
+
+        chunks, cur = [], []
+        for entry in todo:
+            if cur and (len(cur) >= self.WATERSHED_BATCH_MAX_IMAGES or not 0 <= need(cur + [entry]) <= budget_bytes):
+                chunks.append(cur)
+                cur = []
+            cur.append(entry)
+        if cur:
+            chunks.append(cur)
+        for chunk in chunks:
+            tab = table(chunk)
+            cat = lambda arrs, dt: np.concatenate([a.reshape(-1) for a in arrs]) if arrs else np.zeros(0, dt)
+            res = self.marker_watershed_packed(cat([e[1] for e in chunk], np.uint8), tab, cat([e[2] for e in chunk], np.int32),
+                                               cat([e[3] for e in chunk], np.int32), cat([e[4] for e in chunk], np.int32))
+            for (k, m, _, _, _, _), row in zip(chunk, tab):
+                out[k] = res[row[0]:row[0] + m.size].reshape(m.shape)
         return out
 
     def clean_nuclei(self, mask, nuclei_size_T, want_cleaned=False):

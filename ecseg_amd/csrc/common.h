@@ -411,6 +411,31 @@ inline WatershedBufs watershed_bufs(Carver& c, int H, int W, int n_markers, int 
 hipError_t run_marker_watershed(const uint8_t* mask, int H, int W, const int32_t* rows, const int32_t* cols, const int32_t* labels, int n,
                                 int heap_cap, const WatershedBufs& b, hipStream_t s);
 
+// One image of a batched marker watershed, as the device reads it: its H x W bytes start `off` bytes into the packed masks (and its
+// per-pixel int32 values `off` elements into theirs), its n_markers markers at entry first_marker of the lists, its heap of heap_cap
+// elements at element heap_off of the batch's keys and payloads.
+struct WsImage { long long off; long long heap_off; int H, W, first_marker, n_markers, heap_cap, pad; };
+// Device buffers of run_marker_watershed_batch over n_images images inside `span` packed bytes: what WatershedBufs holds per pixel,
+// `span` elements each and every image's part at its own offset; misc with 4 words per image ([0] `filled` holds a zero, [1] heap
+// overflow); the table; the first n_markers entries of the lists; heap_total = the sum of the heap capacities.  The heaps are typed
+// arrays indexed by element, so a slice starts on a multiple of 8 bytes wherever its image's bytes start.
+struct WatershedBatchBufs { uint8_t* mask; uint8_t* out; uint8_t* work; uint8_t* filled; int32_t* idx; int32_t* rw; int32_t* g; int32_t* d2;
+                            int32_t* lab; int32_t* par; int32_t* sz; int32_t* misc; WsImage* tab; int32_t* rows; int32_t* cols; int32_t* labels;
+                            unsigned long long* heap_k; int2* heap_p; };
+inline WatershedBatchBufs watershed_batch_bufs(Carver& c, size_t span, int n_images, size_t n_markers, size_t heap_total) {
+    WatershedBatchBufs b;
+    b.mask = c.take<uint8_t>(span); b.out = c.take<uint8_t>(span); b.work = c.take<uint8_t>(span); b.filled = c.take<uint8_t>(span);
+    b.idx = c.take<int32_t>(span); b.rw = c.take<int32_t>(span); b.g = c.take<int32_t>(span); b.d2 = c.take<int32_t>(span);
+    b.lab = c.take<int32_t>(span); b.par = c.take<int32_t>(span); b.sz = c.take<int32_t>(span); b.misc = c.take<int32_t>((size_t)n_images * 4);
+    b.tab = c.take<WsImage>((size_t)n_images); b.rows = c.take<int32_t>(n_markers); b.cols = c.take<int32_t>(n_markers);
+    b.labels = c.take<int32_t>(n_markers); b.heap_k = c.take<unsigned long long>(heap_total); b.heap_p = c.take<int2>(heap_total);
+    return b;
+}
+// b.mask, b.tab and the lists filled and validated by the caller; max_px / max_w / max_markers: the largest pixel count, width and
+// marker count of one image (they size the grids) -> b.out = per image what run_marker_watershed gives it, 0 outside every image.
+hipError_t run_marker_watershed_batch(int n_images, size_t span, int max_px, int max_w, int max_markers, const WatershedBatchBufs& b,
+                                      hipStream_t s);
+
 // ---- launchers implemented in rescale_kernels.hip (src/utils.py:136,157-162 on scikit-image 0.18 / scipy 1.7) ------------------
 // img (H, W) uint8 on the device -> filtered (H, W) uint8 (the two truncating Gaussian passes; tmp: H*W uint8 between them) and out
 // (oh, ow) float64 (the bilinear warp of filtered / 255).  wy / wx: 2 r + 1 float64 weights on the device, r = 0: that axis is

@@ -1,5 +1,5 @@
 // The one-call drivers: each uploads its inputs, runs one family of kernels on the main stream and downloads the results
-// (u16_to_u8, stitch_argmax, meta_inference, the counts, overlay, the interSeg regions / crops, the FISH distances, the FISH spots and their three colour files, the min-cut tasks, NuSeT's mask and proposals).
+// (u16_to_u8, stitch_argmax, meta_inference, the counts, overlay, the interSeg regions / crops, the FISH distances, the FISH spots and their three colour files, the min-cut tasks, NuSeT's mask and proposals, its marker watershed for one image and for a batch, clean-up and rescale).
 #include "ctx.h"
 
 using namespace ecseg;
@@ -619,6 +619,116 @@ int ecseg_marker_watershed(ecseg_ctx* h, const uint8_t* mask, int H, int W, cons
     HIP_TRY(h, hipStreamSynchronize(s));
     h->stage_ms[ECSEG_T_COUNT] = stage_elapsed(h->ev[0], h->ev[1]);
     if (misc[1]) return fail(h, ECSEG_E_HIP, "marker_watershed: the heap overflowed its bound");
+    return ECSEG_OK;
+}
+
+// ---- the same over a batch of images, one flood wave per image -----------------------------------------------------------------
+// What a batch needs, from its table (n x 5: offset, H, W, first marker, markers) and the foreground count of every image: the device
+// table with the heap slices laid end to end, the packed bytes up to the end of the last image, the list entries in use, the heap
+// elements and the largest image.  Empty string, or what is wrong with image `i`.
+struct WsBatchPlan { std::vector<WsImage> tab; size_t span = 0, n_markers = 0, heap_total = 0; int max_px = 0, max_w = 0, max_markers = 0; };
+static std::string ws_batch_plan(const int64_t* images, int n_images, const long long* foreground, WsBatchPlan& pl) {
+    pl = WsBatchPlan();
+    pl.tab.resize((size_t)n_images);
+    long long end = 0;
+    for (int i = 0; i < n_images; ++i) {
+        const int64_t* d = images + 5 * (size_t)i;
+        const std::string who = "image " + std::to_string(i);
+        const long long off = d[0], H = d[1], W = d[2], first = d[3], n = d[4], fg = foreground[i];
+        if (H < 1 || W < 1 || H > ECSEG_WATERSHED_MAX_EXTENT || W > ECSEG_WATERSHED_MAX_EXTENT)
+            return who + ": an extent outside 1 .. " + std::to_string(ECSEG_WATERSHED_MAX_EXTENT);
+        if (off < end) return who + " overlaps the one in front";
+        if (off > (1ll << 62)) return who + ": offset out of range";
+        end = off + H * W;
+        if (first < 0 || n < 0 || first >= (1ll << 31) || n >= (1ll << 31)) return who + ": a negative or oversized marker range";
+        if (fg < 0 || fg > H * W) return who + ": a foreground count outside its pixel count";
+        if (5 * fg + 1 >= (1ll << 31)) return who + " holds too many foreground pixels for one heap";
+        WsImage& w = pl.tab[(size_t)i];
+        w.off = off; w.heap_off = (long long)pl.heap_total; w.H = (int)H; w.W = (int)W; w.first_marker = (int)first; w.n_markers = (int)n;
+        w.heap_cap = (int)(5 * fg + 1); w.pad = 0;
+        pl.heap_total += (size_t)w.heap_cap;
+        pl.n_markers = std::max(pl.n_markers, (size_t)(first + n));
+        pl.max_px = std::max(pl.max_px, (int)(H * W)); pl.max_w = std::max(pl.max_w, (int)W); pl.max_markers = std::max(pl.max_markers, (int)n);
+    }
+    pl.span = (size_t)end;
+    return std::string();
+}
+
+long long ecseg_marker_watershed_batch_bytes(const int64_t* images, int n_images, const long long* foreground) {
+    if (n_images == 0) return 0;
+    if (n_images < 0 || n_images > ECSEG_WATERSHED_BATCH_MAX_IMAGES || !images || !foreground) return -1;
+    WsBatchPlan pl;
+    if (!ws_batch_plan(images, n_images, foreground, pl).empty()) return -1;
+    Carver c;
+    (void)watershed_batch_bufs(c, pl.span, n_images, pl.n_markers, pl.heap_total);
+    return (long long)c.used;
+}
+
+int ecseg_marker_watershed_batch(ecseg_ctx* h, const uint8_t* masks, long long mask_bytes, const int64_t* images, int n_images,
+                                 const int32_t* marker_rows, const int32_t* marker_cols, const int32_t* marker_labels, long long n_markers,
+                                 uint8_t* out) {
+    if (!h) return ECSEG_E_INVALID;
+    drop_sent_ahead(h);
+    const std::string me = "marker_watershed_batch: ";
+    if (n_images < 0 || n_images > ECSEG_WATERSHED_BATCH_MAX_IMAGES)
+        return fail(h, ECSEG_E_INVALID, me + "n_images must be between 0 and " + std::to_string(ECSEG_WATERSHED_BATCH_MAX_IMAGES));
+    if (mask_bytes < 0 || n_markers < 0 || n_markers >= (1ll << 31) || (n_images > 0 && (!masks || !images || !out)) ||
+        (n_markers > 0 && (!marker_rows || !marker_cols || !marker_labels)))
+        return fail(h, ECSEG_E_INVALID, me + "bad arguments");
+    for (float& v : h->stage_ms) v = 0.f;
+    if (n_images == 0) return ECSEG_OK;
+    std::vector<long long> fg((size_t)n_images, 0);
+    WsBatchPlan pl;
+    std::string bad = ws_batch_plan(images, n_images, fg.data(), pl);         // the geometry first: nothing is read through a bad offset
+    if (!bad.empty()) return fail(h, ECSEG_E_INVALID, me + bad);
+    if ((long long)pl.span > mask_bytes) {
+        int i = 0;
+        while (pl.tab[(size_t)i].off + (long long)pl.tab[(size_t)i].H * pl.tab[(size_t)i].W <= mask_bytes) ++i;
+        return fail(h, ECSEG_E_INVALID, me + "image " + std::to_string(i) + " leaves the " + std::to_string(mask_bytes) + " bytes of masks");
+    }
+    for (int i = 0; i < n_images; ++i) {
+        const WsImage& w = pl.tab[(size_t)i];
+        if ((long long)w.first_marker + w.n_markers > n_markers)
+            return fail(h, ECSEG_E_INVALID, me + "image " + std::to_string(i) + ": its marker range leaves the " + std::to_string(n_markers) + " entries of the lists");
+        for (long long k = w.first_marker; k < (long long)w.first_marker + w.n_markers; ++k) {
+            const std::string who = me + "image " + std::to_string(i) + ": marker " + std::to_string(k);
+            if (marker_rows[k] < 0 || marker_rows[k] >= w.H || marker_cols[k] < 0 || marker_cols[k] >= w.W)
+                return fail(h, ECSEG_E_INVALID, who + " lies outside the image");
+            if (marker_labels[k] < 1) return fail(h, ECSEG_E_INVALID, who + " has a label below 1");
+        }
+        const uint8_t* m = masks + w.off;
+        const size_t px = (size_t)w.H * w.W;
+        size_t n = 0;
+        for (size_t p = 0; p < px; ++p) n += m[p] != 0;
+        fg[(size_t)i] = (long long)n;
+    }
+    bad = ws_batch_plan(images, n_images, fg.data(), pl);                     // now with the heaps
+    if (!bad.empty()) return fail(h, ECSEG_E_INVALID, me + bad);
+    HIP_TRY(h, hipSetDevice(h->device));
+    int rc;
+    WatershedBatchBufs b{};
+    if ((rc = lay_out(h, h->call_arena, [&](Carver& c) { b = watershed_batch_bufs(c, pl.span, n_images, pl.n_markers, pl.heap_total); })))
+        return rc;
+    hipStream_t s = h->stream;
+    const size_t nm = pl.n_markers, ni = (size_t)n_images;
+    HIP_TRY(h, hipMemcpyAsync(b.mask, masks, pl.span, hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(b.tab, pl.tab.data(), ni * sizeof(WsImage), hipMemcpyHostToDevice, s));
+    if (nm > 0) {
+        HIP_TRY(h, hipMemcpyAsync(b.rows, marker_rows, nm * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        HIP_TRY(h, hipMemcpyAsync(b.cols, marker_cols, nm * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        HIP_TRY(h, hipMemcpyAsync(b.labels, marker_labels, nm * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    }
+    HIP_TRY(h, hipEventRecord(h->ev[0], s));
+    HIP_TRY(h, run_marker_watershed_batch(n_images, pl.span, pl.max_px, pl.max_w, pl.max_markers, b, s));
+    HIP_TRY(h, hipEventRecord(h->ev[1], s));
+    std::vector<int32_t> misc(ni * 4, 0);
+    HIP_TRY(h, hipMemcpyAsync(out, b.out, pl.span, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipMemcpyAsync(misc.data(), b.misc, misc.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));                     // (pl.tab and misc are read and written by the copies above: they live until here)
+    std::fill(out + pl.span, out + mask_bytes, (uint8_t)0);  // behind the last image
+    h->stage_ms[ECSEG_T_COUNT] = stage_elapsed(h->ev[0], h->ev[1]);
+    for (int i = 0; i < n_images; ++i)
+        if (misc[(size_t)i * 4 + 1]) return fail(h, ECSEG_E_HIP, me + "the heap of image " + std::to_string(i) + " overflowed its bound");
     return ECSEG_OK;
 }
 

@@ -13,7 +13,8 @@
 // maximum, binary_fill_holes (4-connected background components off the border), the exact squared Euclidean distance transform
 // in int32 (column pass, then the row minimum), and scikit-image 0.18's flood with lines.  The flood's result IS the order of its
 // binary heap - marker pixels of equal d^2 carry equal (value, age) keys and leave the heap as its sift rules decide - so it runs
-// as one serial stream that replays that heap; everything around it is parallel.
+// as one serial stream that replays that heap; everything around it is parallel.  A batch of images
+// (run_marker_watershed_batch) gives every image such a stream of its own, side by side: the floods of different images share nothing.
 #include "common.h"
 #include "cell_util.h"
 
@@ -21,22 +22,27 @@ namespace ecseg {
 namespace {
 
 // par[p] = p where (img[p] != 0) == (want != 0), else -1
-__global__ __launch_bounds__(256) void wk_init_kernel(const uint8_t* __restrict__ img, int px, int want, int32_t* __restrict__ par,
-                                                      int32_t* __restrict__ sz) {
-    const unsigned p = blockIdx.x * 256u + threadIdx.x;      // H * W < 2^31: no wrap
-    if (p >= (unsigned)px) return;
+__device__ __forceinline__ void wk_init_px(const uint8_t* __restrict__ img, int px, int want, int32_t* __restrict__ par, int32_t* __restrict__ sz,
+                                           unsigned p) {
+    if (p >= (unsigned)px) return;                           // H * W < 2^31: no wrap
     par[p] = ((img[p] != 0) == (want != 0)) ? (int)p : -1;
     sz[p] = 0;
 }
+__global__ __launch_bounds__(256) void wk_init_kernel(const uint8_t* __restrict__ img, int px, int want, int32_t* __restrict__ par,
+                                                      int32_t* __restrict__ sz) {
+    wk_init_px(img, px, want, par, sz, blockIdx.x * 256u + threadIdx.x);
+}
 
 // unite every keyed pixel with its W / N (and, conn8, NW / NE) neighbour when that is keyed too
-__global__ __launch_bounds__(256) void wk_unite_kernel(int H, int W, int conn8, int32_t* par) {
-    const unsigned pu = blockIdx.x * 256u + threadIdx.x;
+__device__ __forceinline__ void wk_unite_px(int H, int W, int conn8, int32_t* par, unsigned pu) {
     if (pu >= (unsigned)(H * W)) return;
     const int p = (int)pu;
     if (uf_load(par, p) < 0) return;
     const int y = p / W, x = p - y * W;
     uf_unite_back(par, p, y, x, W, conn8, [](int) { return true; });
+}
+__global__ __launch_bounds__(256) void wk_unite_kernel(int H, int W, int conn8, int32_t* par) {
+    wk_unite_px(H, W, conn8, par, blockIdx.x * 256u + threadIdx.x);
 }
 
 // dbl[0] = mean_area = float32(pixels) / cells in float64 (normalization.py:30), dbl[1] = mean_area / 5 (:34,36)
@@ -79,18 +85,19 @@ __global__ __launch_bounds__(256) void wk_final_kernel(int px, int min_size, con
 // ---- the marker watershed (src/model_layers/marker_watershed.py:82-91) ----------------------------------------------------------
 constexpr int WS_INF = 1 << 30;
 
+// Every stage below is stated once, as a function of the thread's pixel (marker, column) index over ONE image's buffers; the
+// single-image kernels and the batched ones (blockIdx.y = the image, the pointers moved to its offset) are wrappers around it.
+
 // idx[pixel] = 1 + the LAST list entry on that pixel (later markers overwrite earlier ones)
-__global__ __launch_bounds__(256) void ws_scatter_kernel(const int32_t* __restrict__ rows, const int32_t* __restrict__ cols, int n, int W,
-                                                         int32_t* __restrict__ idx) {
-    const unsigned i = blockIdx.x * 256u + threadIdx.x;
+__device__ __forceinline__ void ws_scatter_px(const int32_t* __restrict__ rows, const int32_t* __restrict__ cols, int n, int W,
+                                              int32_t* __restrict__ idx, unsigned i) {
     if (i >= (unsigned)n) return;
     atomicMax(idx + (size_t)rows[i] * W + cols[i], (int)i + 1);   // coordinates validated by the caller
 }
 
 // rw = morphology.dilation(markers, disk(3)) * mask: the maximum label over the 29 offsets with dy^2 + dx^2 <= 9
-__global__ __launch_bounds__(256) void ws_dilate_kernel(const int32_t* __restrict__ idx, const int32_t* __restrict__ labels,
-                                                        const uint8_t* __restrict__ mask, int H, int W, int32_t* __restrict__ rw) {
-    const unsigned pu = blockIdx.x * 256u + threadIdx.x;
+__device__ __forceinline__ void ws_dilate_px(const int32_t* __restrict__ idx, const int32_t* __restrict__ labels, const uint8_t* __restrict__ mask,
+                                             int H, int W, int32_t* __restrict__ rw, unsigned pu) {
     if (pu >= (unsigned)(H * W)) return;
     const int p = (int)pu, y = p / W, x = p - y * W;
     int best = 0;
@@ -106,17 +113,16 @@ __global__ __launch_bounds__(256) void ws_dilate_kernel(const int32_t* __restric
 }
 
 // after the 4-connected labelling of the background: sz[root] = 1 for every background component on the border
-__global__ __launch_bounds__(256) void ws_border_kernel(int H, int W, const int32_t* __restrict__ par, int32_t* __restrict__ sz) {
-    const unsigned pu = blockIdx.x * 256u + threadIdx.x;
+__device__ __forceinline__ void ws_border_px(int H, int W, const int32_t* __restrict__ par, int32_t* __restrict__ sz, unsigned pu) {
     if (pu >= (unsigned)(H * W)) return;
     const int p = (int)pu, y = p / W, x = p - y * W;
     if ((y == 0 || y == H - 1 || x == 0 || x == W - 1) && par[p] >= 0) sz[uf_find(par, p)] = 1;
 }
 
-// filled = binary_fill_holes(mask): the mask plus the background components that do not reach the border; *anyzero |= 1 when a 0 is left
-__global__ __launch_bounds__(256) void ws_filled_kernel(const uint8_t* __restrict__ mask, int px, const int32_t* __restrict__ par,
-                                                        const int32_t* __restrict__ sz, uint8_t* __restrict__ filled, int32_t* __restrict__ anyzero) {
-    const unsigned pu = blockIdx.x * 256u + threadIdx.x;
+// filled = binary_fill_holes(mask): the mask plus the background components that do not reach the border; *anyzero |= 1 when a 0 is
+// left.  Whole waves call it (the ballot).
+__device__ __forceinline__ void ws_filled_px(const uint8_t* __restrict__ mask, int px, const int32_t* __restrict__ par, const int32_t* __restrict__ sz,
+                                             uint8_t* __restrict__ filled, int32_t* __restrict__ anyzero, unsigned pu) {
     int v = 1;
     if (pu < (unsigned)px) {
         const int p = (int)pu;
@@ -128,8 +134,7 @@ __global__ __launch_bounds__(256) void ws_filled_kernel(const uint8_t* __restric
 }
 
 // g[y][x] = distance along the column to the nearest zero of `filled`, WS_INF when the column holds none
-__global__ __launch_bounds__(64) void ws_edt_cols_kernel(const uint8_t* __restrict__ filled, int H, int W, int32_t* __restrict__ g) {
-    const unsigned x = blockIdx.x * 64u + threadIdx.x;
+__device__ __forceinline__ void ws_edt_col(const uint8_t* __restrict__ filled, int H, int W, int32_t* __restrict__ g, unsigned x) {
     if (x >= (unsigned)W) return;
     int d = WS_INF;
     for (int y = 0; y < H; ++y) {
@@ -147,9 +152,8 @@ __global__ __launch_bounds__(64) void ws_edt_cols_kernel(const uint8_t* __restri
 
 // d2 = the exact squared Euclidean distance to the nearest zero of `filled` on the mask's pixels (0 elsewhere): the minimum over
 // the row of dx^2 + g^2, scanned outwards until dx^2 reaches the best.  No zero at all: scipy's answer, the distance to (-1, 0).
-__global__ __launch_bounds__(256) void ws_edt_rows_kernel(const uint8_t* __restrict__ mask, const int32_t* __restrict__ g, int H, int W,
-                                                          const int32_t* __restrict__ anyzero, int32_t* __restrict__ d2) {
-    const unsigned pu = blockIdx.x * 256u + threadIdx.x;
+__device__ __forceinline__ void ws_edt_row_px(const uint8_t* __restrict__ mask, const int32_t* __restrict__ g, int H, int W,
+                                              const int32_t* __restrict__ anyzero, int32_t* __restrict__ d2, unsigned pu) {
     if (pu >= (unsigned)(H * W)) return;
     const int p = (int)pu, y = p / W, x = p - y * W;
     if (!mask[p]) { d2[p] = 0; return; }
@@ -162,6 +166,40 @@ __global__ __launch_bounds__(256) void ws_edt_rows_kernel(const uint8_t* __restr
         if (x + dx < W) { const int v = row[x + dx]; if (v < WS_INF) best = min(best, dx * dx + v * v); }
     }
     d2[p] = best;
+}
+
+// out = pred_mask * (contour != 0)
+__device__ __forceinline__ void ws_result_px(const uint8_t* __restrict__ mask, const int32_t* __restrict__ lab, int px, uint8_t* __restrict__ out,
+                                             unsigned p) {
+    if (p >= (unsigned)px) return;
+    out[p] = lab[p] != 0 ? mask[p] : (uint8_t)0;
+}
+
+__global__ __launch_bounds__(256) void ws_scatter_kernel(const int32_t* __restrict__ rows, const int32_t* __restrict__ cols, int n, int W,
+                                                         int32_t* __restrict__ idx) {
+    ws_scatter_px(rows, cols, n, W, idx, blockIdx.x * 256u + threadIdx.x);
+}
+__global__ __launch_bounds__(256) void ws_dilate_kernel(const int32_t* __restrict__ idx, const int32_t* __restrict__ labels,
+                                                        const uint8_t* __restrict__ mask, int H, int W, int32_t* __restrict__ rw) {
+    ws_dilate_px(idx, labels, mask, H, W, rw, blockIdx.x * 256u + threadIdx.x);
+}
+__global__ __launch_bounds__(256) void ws_border_kernel(int H, int W, const int32_t* __restrict__ par, int32_t* __restrict__ sz) {
+    ws_border_px(H, W, par, sz, blockIdx.x * 256u + threadIdx.x);
+}
+__global__ __launch_bounds__(256) void ws_filled_kernel(const uint8_t* __restrict__ mask, int px, const int32_t* __restrict__ par,
+                                                        const int32_t* __restrict__ sz, uint8_t* __restrict__ filled, int32_t* __restrict__ anyzero) {
+    ws_filled_px(mask, px, par, sz, filled, anyzero, blockIdx.x * 256u + threadIdx.x);
+}
+__global__ __launch_bounds__(64) void ws_edt_cols_kernel(const uint8_t* __restrict__ filled, int H, int W, int32_t* __restrict__ g) {
+    ws_edt_col(filled, H, W, g, blockIdx.x * 64u + threadIdx.x);
+}
+__global__ __launch_bounds__(256) void ws_edt_rows_kernel(const uint8_t* __restrict__ mask, const int32_t* __restrict__ g, int H, int W,
+                                                          const int32_t* __restrict__ anyzero, int32_t* __restrict__ d2) {
+    ws_edt_row_px(mask, g, H, W, anyzero, d2, blockIdx.x * 256u + threadIdx.x);
+}
+__global__ __launch_bounds__(256) void ws_result_kernel(const uint8_t* __restrict__ mask, const int32_t* __restrict__ lab, int px,
+                                                        uint8_t* __restrict__ out) {
+    ws_result_px(mask, lab, px, out, blockIdx.x * 256u + threadIdx.x);
 }
 
 // scikit-image 0.18's binary heap on (value, age) as ONE 64-bit key: push swims up while strictly smaller, pop moves the last
@@ -208,8 +246,8 @@ __device__ __forceinline__ int2 ws_pop(WsHeap& h) {
 
 // The flood, one serial stream (lane 0 of one wave; the other lanes only help to find the marker pixels): the order of the heap is
 // the result.  m: working copy of the mask (line pixels leave it); lab: labels, zeroed by the caller; misc[1] = 1 on a heap overflow.
-__global__ __launch_bounds__(64) void ws_flood_kernel(uint8_t* m, const int32_t* __restrict__ rw, const int32_t* __restrict__ d2, int H, int W,
-                                                      unsigned long long* K, int2* P, int cap, int32_t* lab, int32_t* misc) {
+__device__ __forceinline__ void ws_flood(uint8_t* m, const int32_t* __restrict__ rw, const int32_t* __restrict__ d2, int H, int W,
+                                         unsigned long long* K, int2* P, int cap, int32_t* lab, int32_t* misc) {
     const int lane = threadIdx.x, px = H * W;
     WsHeap h{K, P, 0, cap, 0};
     for (int base = 0; base < px; base += 64) {              // markers in raster order, age 0
@@ -252,13 +290,61 @@ __global__ __launch_bounds__(64) void ws_flood_kernel(uint8_t* m, const int32_t*
     if (h.overflow) misc[1] = 1;
 }
 
-// out = pred_mask * (contour != 0)
-__global__ __launch_bounds__(256) void ws_result_kernel(const uint8_t* __restrict__ mask, const int32_t* __restrict__ lab, int px,
-                                                        uint8_t* __restrict__ out) {
-    const unsigned p = blockIdx.x * 256u + threadIdx.x;
-    if (p >= (unsigned)px) return;
-    out[p] = lab[p] != 0 ? mask[p] : (uint8_t)0;
+__global__ __launch_bounds__(64) void ws_flood_kernel(uint8_t* m, const int32_t* __restrict__ rw, const int32_t* __restrict__ d2, int H, int W,
+                                                      unsigned long long* K, int2* P, int cap, int32_t* lab, int32_t* misc) {
+    ws_flood(m, rw, d2, H, W, K, P, cap, lab, misc);
 }
+
+// ---- the batch: blockIdx.y (the flood: blockIdx.x) is the image, every pointer moves to the image's own offset -------------------
+// A block past its image's pixels (markers, columns) returns at once; the union-find parents are indices INSIDE the image.
+#define WSB_IMAGE(count)                                                   \
+    const WsImage im = b.tab[blockIdx.y];                                  \
+    const int px = im.H * im.W;                                            \
+    if (blockIdx.x * blockDim.x >= (unsigned)(count)) return;              \
+    const unsigned t = blockIdx.x * blockDim.x + threadIdx.x;              \
+    (void)px
+__global__ __launch_bounds__(256) void wsb_scatter_kernel(WatershedBatchBufs b) {
+    WSB_IMAGE(im.n_markers);
+    ws_scatter_px(b.rows + im.first_marker, b.cols + im.first_marker, im.n_markers, im.W, b.idx + im.off, t);
+}
+__global__ __launch_bounds__(256) void wsb_dilate_kernel(WatershedBatchBufs b) {
+    WSB_IMAGE(px);
+    ws_dilate_px(b.idx + im.off, b.labels + im.first_marker, b.mask + im.off, im.H, im.W, b.rw + im.off, t);
+}
+__global__ __launch_bounds__(256) void wsb_init_kernel(WatershedBatchBufs b) {                // the background, 4-connected
+    WSB_IMAGE(px);
+    wk_init_px(b.mask + im.off, px, 0, b.par + im.off, b.sz + im.off, t);
+}
+__global__ __launch_bounds__(256) void wsb_unite_kernel(WatershedBatchBufs b) {
+    WSB_IMAGE(px);
+    wk_unite_px(im.H, im.W, 0, b.par + im.off, t);
+}
+__global__ __launch_bounds__(256) void wsb_border_kernel(WatershedBatchBufs b) {
+    WSB_IMAGE(px);
+    ws_border_px(im.H, im.W, b.par + im.off, b.sz + im.off, t);
+}
+__global__ __launch_bounds__(256) void wsb_filled_kernel(WatershedBatchBufs b) {
+    WSB_IMAGE(px);
+    ws_filled_px(b.mask + im.off, px, b.par + im.off, b.sz + im.off, b.filled + im.off, b.misc + 4 * blockIdx.y, t);
+}
+__global__ __launch_bounds__(64) void wsb_edt_cols_kernel(WatershedBatchBufs b) {
+    WSB_IMAGE(im.W);
+    ws_edt_col(b.filled + im.off, im.H, im.W, b.g + im.off, t);
+}
+__global__ __launch_bounds__(256) void wsb_edt_rows_kernel(WatershedBatchBufs b) {
+    WSB_IMAGE(px);
+    ws_edt_row_px(b.mask + im.off, b.g + im.off, im.H, im.W, b.misc + 4 * blockIdx.y, b.d2 + im.off, t);
+}
+__global__ __launch_bounds__(64) void wsb_flood_kernel(WatershedBatchBufs b) {               // one wave per image
+    const WsImage im = b.tab[blockIdx.x];
+    ws_flood(b.work + im.off, b.rw + im.off, b.d2 + im.off, im.H, im.W, b.heap_k + im.heap_off, b.heap_p + im.heap_off, im.heap_cap,
+             b.lab + im.off, b.misc + 4 * blockIdx.x);
+}
+__global__ __launch_bounds__(256) void wsb_result_kernel(WatershedBatchBufs b) {
+    WSB_IMAGE(px);
+    ws_result_px(b.mask + im.off, b.lab + im.off, px, b.out + im.off, t);
+}
+#undef WSB_IMAGE
 
 }  // namespace
 
@@ -281,6 +367,29 @@ hipError_t run_marker_watershed(const uint8_t* mask, int H, int W, const int32_t
     hipLaunchKernelGGL(ws_edt_rows_kernel, g, t, 0, s, mask, b.g, H, W, b.misc, b.d2);
     hipLaunchKernelGGL(ws_flood_kernel, dim3(1), dim3(64), 0, s, b.work, b.rw, b.d2, H, W, b.heap_k, b.heap_p, heap_cap, b.lab, b.misc);
     hipLaunchKernelGGL(ws_result_kernel, g, t, 0, s, mask, b.lab, px, b.out);
+    return hipGetLastError();
+}
+
+hipError_t run_marker_watershed_batch(int n_images, size_t span, int max_px, int max_w, int max_markers, const WatershedBatchBufs& b,
+                                      hipStream_t s) {
+    const unsigned N = (unsigned)n_images;
+    const dim3 g(((unsigned)max_px + 255u) / 256u, N), t(256);
+    hipError_t e;
+    if ((e = hipMemsetAsync(b.misc, 0, (size_t)N * 4 * sizeof(int32_t), s)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(b.idx, 0, span * sizeof(int32_t), s)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(b.lab, 0, span * sizeof(int32_t), s)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(b.out, 0, span, s)) != hipSuccess) return e;         // the bytes between the images stay 0
+    if ((e = hipMemcpyAsync(b.work, b.mask, span, hipMemcpyDeviceToDevice, s)) != hipSuccess) return e;
+    if (max_markers > 0) hipLaunchKernelGGL(wsb_scatter_kernel, dim3(((unsigned)max_markers + 255u) / 256u, N), t, 0, s, b);
+    hipLaunchKernelGGL(wsb_dilate_kernel, g, t, 0, s, b);
+    hipLaunchKernelGGL(wsb_init_kernel, g, t, 0, s, b);
+    hipLaunchKernelGGL(wsb_unite_kernel, g, t, 0, s, b);
+    hipLaunchKernelGGL(wsb_border_kernel, g, t, 0, s, b);
+    hipLaunchKernelGGL(wsb_filled_kernel, g, t, 0, s, b);
+    hipLaunchKernelGGL(wsb_edt_cols_kernel, dim3(((unsigned)max_w + 63u) / 64u, N), dim3(64), 0, s, b);
+    hipLaunchKernelGGL(wsb_edt_rows_kernel, g, t, 0, s, b);
+    hipLaunchKernelGGL(wsb_flood_kernel, dim3(N), dim3(64), 0, s, b);
+    hipLaunchKernelGGL(wsb_result_kernel, g, t, 0, s, b);
     return hipGetLastError();
 }
 

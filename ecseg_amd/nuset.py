@@ -270,10 +270,20 @@ class NuSeT:
         cleaned mask is scaled back up before the threshold (``Handle.rescale_mask_up``, :157-162) -> a mask of
         ``round(cropped small extent / scale_ratio)``, within a few pixels of the image's extent.  A scaled image below 16 x 16, or a
         ``scale_ratio`` outside (0, 1], raises ``ValueError``."""
+        m, mk = self._segment_head(image, min_score, nms_threshold, second, scale_ratio)
+        ws = m if mk is None else self.handle.marker_watershed(m, *mk)
+        return self._segment_tail(ws, nuclei_size_T, scale_ratio)
+
+    @staticmethod
+    def _check_scale(scale_ratio):
+        if scale_ratio != 1 and not 0 < scale_ratio < 1:
+            raise ValueError('segment: scale_ratio must lie in (0, 1], got %r (above 1 the reference\'s second rescale Gaussian-filters the '
+                             '0 / 1 uint8 mask into almost nothing: not built)' % (scale_ratio,))
+
+    def _segment_head(self, image, min_score, nms_threshold, second, scale_ratio):
+        """``segment`` up to the watershed: -> (mask, the marker list of ``watershed_markers`` or None)."""
+        self._check_scale(scale_ratio)
         if scale_ratio != 1:
-            if not 0 < scale_ratio < 1:
-                raise ValueError('segment: scale_ratio must lie in (0, 1], got %r (above 1 the reference\'s second rescale Gaussian-filters the '
-                                 '0 / 1 uint8 mask into almost nothing: not built)' % (scale_ratio,))
             image = np.asarray(image)
             if image.ndim != 2:
                 raise ValueError('segment takes one (H, W) image')
@@ -281,9 +291,32 @@ class NuSeT:
                 raise ValueError('segment: the image scaled by %s is smaller than 16 x 16' % (scale_ratio,))
             image = self.handle.rescale_down(image, scale_ratio)[0]
         m, scores, proposals = self.nuclei_masks(image, min_score, nms_threshold, second)
-        mk = watershed_markers(scores, proposals, m, min_score, self.handle)
-        ws = m if mk is None else self.handle.marker_watershed(m, *mk)
+        return m, watershed_markers(scores, proposals, m, min_score, self.handle)
+
+    def _segment_tail(self, ws, nuclei_size_T, scale_ratio):
+        """``segment`` behind the watershed: ``clean_image``, the rescale back up and the final threshold."""
         if scale_ratio == 1:
             return self.handle.clean_nuclei(ws, nuclei_size_T)[0]
         cleaned = self.handle.clean_nuclei(ws, 0, want_cleaned=True)[2]
         return self.handle.rescale_mask_up(cleaned, 1 / scale_ratio, nuclei_size_T)
+
+    def segment_many(self, images, min_score=0.95, nms_threshold=0.01, nuclei_size_T=0, second=None, scale_ratio=1):
+        """``[segment(im, ...) for im in images]``, byte for byte, with the marker watersheds of all images in ONE device call
+        (``Handle.marker_watershed_batch``: the flood is one serial wave per image, and the waves of different images run side by
+        side).  Everything else runs image after image as in ``segment``: the rescale, the network and the marker list first, the
+        clean-up and the rescale back up after the batch; the plan is re-loaded when the extent changes, so images of one extent
+        are best kept together.  A ``ValueError`` that ``segment`` would raise for one image (one below 16 x 16 after scaling) is
+        RETURNED in that image's place and the others are not disturbed; a ``scale_ratio`` outside (0, 1] raises at once."""
+        self._check_scale(scale_ratio)
+        heads = []
+        for image in images:
+            try:
+                heads.append(self._segment_head(image, min_score, nms_threshold, second, scale_ratio))
+            except ValueError as e:
+                heads.append(e)
+        good = [k for k, v in enumerate(heads) if not isinstance(v, ValueError)]
+        flooded = self.handle.marker_watershed_batch([heads[k][0] for k in good], [heads[k][1] for k in good])
+        out = list(heads)
+        for k, ws in zip(good, flooded):
+            out[k] = self._segment_tail(ws, nuclei_size_T, scale_ratio)
+        return out

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """``make stat_fish``: per-nucleus FISH spot statistics (reference src/stat_fish.py), everything behind ``nuclei_segment``.
 
-The nucleus mask of every image comes from NuSeT on the device (config key ``nuset_weights``: ``NuSeT.segment`` on channel 0) or, without
+The nucleus mask of every image comes from NuSeT on the device (config key ``nuset_weights``: ``NuSeT.segment`` on channel 0; with
+``nuset_batch: k`` the sorted images are taken k at a time and their marker watersheds share one device call, ``NuSeT.segment_many`` -
+the same files, k blue channels held at once) or, without
 that key, is read from ``<masks>/<name>.tif`` (config key ``masks``, default ``<inpath>/nuclei_masks``):
 any segmenter writing an 8-bit single-sample TIFF there, non-zero = nucleus, will do (NuSeT's weights come as an ``.npz``: TF1
 checkpoints are not read).  Per image the nuclei are labelled on the device (``Handle.ccl_labels``, 8-connected,
@@ -430,6 +432,17 @@ def load_nuset_segmenter(var, handle):
             return nets[0].segment(blue, prm['min_score'], prm['nms_threshold'], size_t, second=second, scale_ratio=prm['scale_ratio'])
         except ValueError as e:                              # e.g. smaller than 16 x 16 after scaling: this image only
             raise ImageError(str(e))
+
+    def segment_many(blues, handle):
+        """``[segment(b, handle) for b in blues]`` through ``NuSeT.segment_many`` (config key ``nuset_batch``); what ``segment`` would
+        raise for one image stands in its place, as the exception ``segment`` raises."""
+        if 'nets' not in state:
+            state['nets'] = [nuset.NuSeT(w, base, handle=handle) for w in weights]
+        nets = state['nets']
+        out = nets[0].segment_many(blues, prm['min_score'], prm['nms_threshold'], size_t, second=nets[-1] if len(nets) > 1 else None,
+                                   scale_ratio=prm['scale_ratio'])
+        return [ImageError(str(m)) if isinstance(m, ValueError) and prm['scale_ratio'] != 1 else m for m in out]
+    segment.many = segment_many
     return segment
 
 
@@ -471,6 +484,12 @@ def main(argv=None, handle=None):
             raise ConfigError('scale must be a positive number or "auto"')
         masks = str(var['masks']) if var.get('masks') is not None else os.path.join(inpath, 'nuclei_masks')
         segmenter = load_nuset_segmenter(var, handle) if var.get('nuset_weights') is not None else None
+        batch = var.get('nuset_batch', 1) if segmenter is not None else 1
+        if isinstance(batch, bool) or not isinstance(batch, int) or batch < 1:
+            raise ConfigError('nuset_batch must be a positive integer (how many images share one marker-watershed call; 1: one by one)')
+        if batch > 1 and handle is not None and not hasattr(handle, 'marker_watershed_batch'):
+            raise ConfigError('nuset_batch: %d needs the batched marker watershed (marker_watershed_batch), which the handle in use does not '
+                              'have; only nuset_batch: 1 works on it' % batch)
         if segmenter is None and not os.path.isdir(masks):
             raise ConfigError('The folder of nucleus masks %s does not exist (config key masks): it holds one 8-bit <name>.tif per '
                               'image, non-zero = nucleus' % masks)
@@ -498,17 +517,40 @@ def main(argv=None, handle=None):
         handle = Handle(0)
     keep_freed_memory()
     rows, failed, seen = [], [], {}
+
+    def handed_in(mask):                                     # the `segment` hook of process_image for a mask computed with its chunk
+        def segment(blue):
+            if isinstance(mask, Exception):
+                raise mask
+            return mask
+        return segment
     try:
-        for p in image_paths:
-            print("Processing image: ", p)
-            try:
-                img_rows, scale = process_image(p, os.path.join(masks, os.path.basename(p)[:-4] + '.tif'), out_root, params, scale, handle,
-                                                 stats=seen, use_min_cut=use_min_cut,
-                                                 segment=None if segmenter is None else (lambda blue: segmenter(blue, handle)))
-                rows += img_rows
-            except ImageError as e:
-                print(p, '-', e)
-                failed.append((p, str(e)))
+        for at in range(0, len(image_paths), batch):
+            chunk = image_paths[at:at + batch]
+            hooks = {}
+            if segmenter is not None and batch == 1:
+                hooks[chunk[0]] = lambda blue: segmenter(blue, handle)
+            elif segmenter is not None:                      # nuset_batch: the chunk's blue channels (and nothing else of them) are held at once
+                blues = []
+                for p in chunk:
+                    try:
+                        I, channels = read_image(p, handle, len(params['color_sensitivity']))
+                        blues.append((p, np.ascontiguousarray(I[:, :, channels[0]])))
+                    except ImageError as e:
+                        hooks[p] = handed_in(e)              # (process_image meets and reports it at the image's turn)
+                    I = None
+                for (p, _), m in zip(blues, segmenter.many([b for _, b in blues], handle)):
+                    hooks[p] = handed_in(m)
+                blues = None
+            for p in chunk:
+                print("Processing image: ", p)
+                try:
+                    img_rows, scale = process_image(p, os.path.join(masks, os.path.basename(p)[:-4] + '.tif'), out_root, params, scale, handle,
+                                                     stats=seen, use_min_cut=use_min_cut, segment=hooks.get(p))
+                    rows += img_rows
+                except ImageError as e:
+                    print(p, '-', e)
+                    failed.append((p, str(e)))
     finally:
         if own:
             handle.close()

@@ -457,6 +457,31 @@ int ecseg_rpn_proposals_last(ecseg_ctx* h, int A, const double* ref_anchors, int
 #define ECSEG_WATERSHED_MAX_EXTENT 16384
 int ecseg_marker_watershed(ecseg_ctx* h, const uint8_t* mask, int H, int W, const int32_t* marker_rows, const int32_t* marker_cols,
                            const int32_t* marker_labels, long long n_markers, uint8_t* out);
+/* The same for n_images images in ONE call: the flood of one image cannot be split, but the floods of different images do not know
+ * of each other, so every image gets a wave of its own and they run side by side; every other step runs over all images at once.
+ * masks: mask_bytes bytes holding the images, image i being the H x W bytes from byte `offset` on; images: n_images x 5 int64 rows
+ * (offset, H, W, first_marker, n_markers), the image's markers being entries first_marker .. first_marker + n_markers - 1 of the
+ * three lists (n_markers entries in all), rows and columns counted inside the image.  Images must not overlap: each starts at or
+ * after the end of the one in front (ecseg_min_cut's rule for its windows); gaps are allowed.  out: mask_bytes bytes laid out as
+ * masks.  Per image the call writes exactly the bytes ecseg_marker_watershed writes for that image alone; bytes of `out` outside
+ * every image are 0; an image without a marker or without foreground gives zeros; n_images = 0 does nothing.  One synchronous
+ * call, scratch from the handle's call arena (ecseg_marker_watershed_batch_bytes says how much), device time of the kernels in
+ * ECSEG_T_COUNT: about that of the slowest image's flood, while there are no more images than the device runs waves at once.
+ * ECSEG_E_INVALID: a null masks, images or out, or null lists with n_markers > 0; n_images outside 0 ..
+ * ECSEG_WATERSHED_BATCH_MAX_IMAGES; mask_bytes < 0; n_markers < 0 or >= 2^31; H or W outside 1 .. ECSEG_WATERSHED_MAX_EXTENT; an
+ * image that leaves masks or overlaps the one in front; a marker range that leaves the lists; a marker outside ITS image or with a
+ * label < 1 (the message names the image and the list entry); an image with 5 * foreground + 1 >= 2^31.  ECSEG_E_NOMEM: the arena
+ * cannot be had.  A heap that overflows its bound (5 * foreground + 1 elements, counted on the host per image) is reported as
+ * ECSEG_E_HIP with the image's index. */
+#define ECSEG_WATERSHED_BATCH_MAX_IMAGES 1024
+int ecseg_marker_watershed_batch(ecseg_ctx* h, const uint8_t* masks, long long mask_bytes, const int64_t* images, int n_images,
+                                 const int32_t* marker_rows, const int32_t* marker_cols, const int32_t* marker_labels, long long n_markers,
+                                 uint8_t* out);
+/* Host arithmetic only, no handle: the bytes of call arena ecseg_marker_watershed_batch needs for these images (as above; the marker
+ * columns count too) when image i has foreground[i] non-zero pixels: 4 uint8 and 7 int32 values per byte up to the end of the last
+ * image, 16 bytes per heap element (5 * foreground + 1 per image), 16 bytes of flags and a 40-byte table row per image, 12 bytes
+ * per list entry in use, every buffer rounded up to 256 bytes.  0 for n_images = 0; -1 for arguments the call would refuse. */
+long long ecseg_marker_watershed_batch_bytes(const int64_t* images, int n_images, const long long* foreground);
 
 /* ---- NuSeT's clean-up behind the marker watershed ----------------------------------------------------------------------------
  * Replaces, for ONE image, clean_image (src/nuset_utils/normalization.py:25-37) and the final threshold of nuclei_segment
