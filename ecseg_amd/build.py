@@ -13,8 +13,7 @@ EXTRA_FLAGS = {'wino4_kernel.hip': ['-fno-slp-vectorize'], 'wino4s_kernel.hip': 
 EXTRA_FLAGS['nuset_kernels.hip'] = ['-ffp-contract=off']
 # rescale restates scipy's and scikit-image's float64 arithmetic bit for bit: the same there
 EXTRA_FLAGS['rescale_kernels.hip'] = ['-ffp-contract=off']
-HEADERS = [os.path.join(CSRC, f) for f in ('common.h', 'ctx.h', 'scratch.h', 'device_util.h', 'cell_util.h', 'wino4_consts.inc', 'wino4_lds_layout.h', 'wino4_region.inc', 'wino4_combine.inc', 'wino4_head.inc')] + \
-    [os.path.join(HERE, '..', 'include', 'ecseg_hip.h')]
+PUBLIC_HEADER = os.path.join(HERE, '..', 'include', 'ecseg_hip.h')
 
 
 def source_hash():
@@ -41,7 +40,8 @@ def needs_build():
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    deps = [os.path.join(CSRC, s) for s in SOURCES] + HEADERS
+    # every header and textual include under csrc/ (what source_hash reads too): a new shared file is a dependency without being listed
+    deps = [os.path.join(CSRC, s) for s in SOURCES] + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(('.h', '.inc'))] + [PUBLIC_HEADER]
     return any(os.path.getmtime(d) > t for d in deps if os.path.exists(d))
 
 

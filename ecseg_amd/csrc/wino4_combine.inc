@@ -26,7 +26,7 @@
             const int nw = cwave + 12 * k;                   // tile pair: tiles 2 nw, 2 nw + 1 (columns 0 / 1 or 2 / 3 of tile row nw >> 1)
             if (nw >= 16) break;
             const int nq8 = nw >> 1;
-            const int g = (0x96 >> nq8) & 1, nty = nq8 >> 1;
+            const int g = W4_QUAD_REGION(nq8), nty = nq8 >> 1;
             const int img = g ? r_img[1] : r_img[0];
             if (img < 0) continue;
             const float* r = rlane + W4Lds::r_comb(0, 0, 0, nw);

@@ -8,7 +8,7 @@
             const int nw = __builtin_amdgcn_readfirstlane(tid >> 6) + 12 * k;          // the item order of wino4_combine.inc
             if (nw >= 16) break;
             const int nq8 = nw >> 1, ntx = 2 * (nw & 1) + nlo;
-            const int g = (0x96 >> nq8) & 1, nty = nq8 >> 1;
+            const int g = W4_QUAD_REGION(nq8), nty = nq8 >> 1;
             const int img = g ? r_img[1] : r_img[0];
             if (img < 0) continue;
             f32x4 mine = {0.f, 0.f, 0.f, 0.f};

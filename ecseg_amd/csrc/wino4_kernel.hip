@@ -47,10 +47,9 @@ namespace ecseg {
 #define ECSEG_W4_TSLOTS 4
 #endif
 
-#define W4_DIAG_SKIP_HALO_DMA()                              // (hooks of wino4_region.inc; only conv_wino4s_kernel's A/B builds fill them)
-#define W4_DIAG_HALO_OFFSET(off, a)
-#define W4_MFMA(ACC, A, B) ACC = __builtin_amdgcn_mfma_f32_32x32x2f32(A, B, ACC, 0, 0, 0)
-#define W4_WAIT(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
+// filter stages (wino4_filter_dma.inc): wt4[nb][stage][wave] is 768 floats, the wave's double buffer follows the ring
+#define W4_FILTER_STRIDE (12 * 768 * 4)
+#define W4_FILTER_LDS(buf) ((3 * W4_HS + W4Lds::bw_stage(wave, buf)) * 16u)
 
 __global__ __launch_bounds__(768) void conv_wino4_kernel(ConvParams p, int regs_x, int regs_y, int npairs) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -64,27 +63,12 @@ __global__ __launch_bounds__(768) void conv_wino4_kernel(ConvParams p, int regs_
     const int li = lane & 31, lh = lane >> 5;
 
 #include "wino4_region.inc"
-    // ---- filter DMA: wt4[nb][stage][wave][point pair nu / 2][lane = h * 32 + cout][nu % 2][k 2], 768 floats per wave and stage; the
-    //      address is a scalar base (advanced per stage by scalar adds) + the lane's constant 16-byte offset ----
+    // ---- filter DMA: wt4[nb][stage][wave][point pair nu / 2][lane = h * 32 + cout][nu % 2][k 2], 768 floats per wave and stage ----
     const unsigned long long w_base = (unsigned long long)(size_t)(p.wt + ((size_t)nb * nstages * 12 + xi) * 768);      // (both channel halves: the ch = 0 slot)
-    const unsigned lane16 = (unsigned)lane * 16u;
     f32x4* Bw = Bs + W4Lds::bw_stage(wave, 0);
-    auto dma_filter_piece = [&](int stage, int buf, auto kk) __attribute__((always_inline)) {
-        constexpr int k = decltype(kk)::value;
-        const unsigned long long g = w_base + (unsigned long long)stage * (12 * 768 * 4);
-        const unsigned dst = lds_base + (unsigned)(3 * W4_HS + W4Lds::bw_stage(wave, buf)) * 16u;
-        const unsigned l16 = lane16;
-        unsigned keep;
-        // the instruction offset advances the global AND the LDS address: one M0 for the three pieces
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %3 offset:%4\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep) : "v"(l16), "s"(dst), "s"(g), "n"(k * 1024) : "memory");
-    };
+#include "wino4_filter_dma.inc"
 
-    // ---- A-operand lane -> tile.  ds_read_b128 serves lanes {0-3,12-15,20-27} and {4-11,16-19,28-31} of each half
-    //      in separate LDS cycles; give each of those groups the 16 tiles of ONE region ----
-    const int q8 = li >> 2, tx = li & 3;
-    const int tg = (0x96 >> q8) & 1;                              // region of lane quad q8: 0,1,1,0,1,0,0,1
-    const int ty = (q8 == 0 || q8 == 1) ? 0 : (q8 == 2 || q8 == 3) ? 1 : (q8 == 4 || q8 == 5) ? 2 : 3;
+#include "wino4_lane_tile.inc"
     const int a_lane = W4Lds::a_lane(tg, ty, lh, tx);       // slot of halo pixel (4 ty, 4 tx) of the lane's tile
 
     // row transform of wave xi (row xi of B^T): t = c0 d[r0] + c1 d[r1] + c2 d[r2] + d[r3]  (rows 0 and 5: three terms)
@@ -173,56 +157,7 @@ __global__ __launch_bounds__(768) void conv_wino4_kernel(ConvParams p, int regs_
 #undef W4_TRD
         }
     };
-    // ---- one filter stage (channels 2 ss, 2 ss + 1 of both halo planes): column transform + 12 MFMAs ----
-    auto mfma_stage = [&](int ss, int fbuf, int next_stage, int halo_grp) __attribute__((always_inline)) {     // ss: the wave's channel pair (= ch), fbuf: filter buffer; halo_grp: group to prefetch, < 0: none
-        const int nbuf = fbuf ^ 1;
-        float V[6][2];
-#pragma unroll
-        for (int e = 0; e < 2; ++e) {   // V[nu] = sum_j B^T[nu][j] t[j], scalar ops (see transform)
-            const int c = 2 * ss + e;
-            const float u0 = t[0][c], u1 = t[1][c], u2 = t[2][c], u3 = t[3][c], u4 = t[4][c], u5 = t[5][c];
-            // points +-a share an even part (u4 - b2 u2) and an odd part (u3 - b2 u1), points +-b likewise with a2
-            const float ea = __builtin_fmaf(-KB2, u2, u4), oa = __builtin_fmaf(-KB2, u1, u3);
-            const float eb = __builtin_fmaf(-KA2, u2, u4), ob = __builtin_fmaf(-KA2, u1, u3);
-            V[0][e] = __builtin_fmaf(KP, u0, __builtin_fmaf(KS, u2, u4));
-            V[1][e] = __builtin_fmaf(KA, oa, ea);
-            V[2][e] = __builtin_fmaf(-KA, oa, ea);
-            V[3][e] = __builtin_fmaf(KB, ob, eb);
-            V[4][e] = __builtin_fmaf(-KB, ob, eb);
-            V[5][e] = __builtin_fmaf(KP, u1, __builtin_fmaf(KS, u3, u5));
-        }
-        f32x2 w2[6];
-        const f32x4* Bp = Bw + W4Lds::bw_stage(0, fbuf) + W4Lds::bw_read(lane, 0);        // three 16-byte reads: the fragments of point pairs (0, 1), (2, 3), (4, 5)
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const f32x4 w4 = Bp[W4Lds::bw_read(0, k)];
-            w2[2 * k] = f32x2{w4[0], w4[1]};
-            w2[2 * k + 1] = f32x2{w4[2], w4[3]};
-        }
-        // 12 MFMAs, channel-major: consecutive MFMAs hit different accumulators (dependency distance 6), so even a lone
-        // wave keeps the matrix pipe full.  The next stage's three filter pieces go out one at a time behind MFMAs 2, 4
-        // and 6 (pinned): the wave's issue slot is free while the pipe works, and the load path never sees a burst.
-#pragma unroll
-        for (int e = 0; e < 2; ++e)
-#pragma unroll
-            for (int v = 0; v < 6; ++v) {
-                W4_MFMA(acc[v], V[v][e], w2[v][e]);
-                if (e == 0 && (v == 1 || v == 3 || v == 5)) {
-                    __builtin_amdgcn_sched_barrier(0);
-                    if (v == 1) dma_filter_piece(next_stage, nbuf, std::integral_constant<int, 0>{});
-                    if (v == 3) dma_filter_piece(next_stage, nbuf, std::integral_constant<int, 1>{});
-                    if (v == 5) dma_filter_piece(next_stage, nbuf, std::integral_constant<int, 2>{});
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-                if (e == 1 && (v == 1 || v == 3) && halo_grp >= 0) {       // behind MFMAs 8 and 10
-                    __builtin_amdgcn_sched_barrier(0);
-                    if (v == 1) dma_halo_piece(halo_grp, std::integral_constant<int, 0>{});
-                    if (v == 3) dma_halo_piece(halo_grp, std::integral_constant<int, 1>{});
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
-    };
-#define W4_BARRIER() asm volatile("s_barrier" ::: "memory")
+#include "wino4_mfma_stage.inc"
 
     // Phase rotation.  Per 8-channel group a wave has two phases: T (halo LDS reads + row transform of its two channels,
     // latency-bound) and S (its one filter stage of the group: 12 MFMAs).  The barrier would keep the three waves of a SIMD
@@ -232,7 +167,6 @@ __global__ __launch_bounds__(768) void conv_wino4_kernel(ConvParams p, int regs_
     // ngroups barriers and reads halo group g only between barriers g and g + 1.  The late waves' halo pieces of group g + 1 go
     // out in period g (inside S(g - 1)) and are waited for before barrier g + 1.  (Three classes with the stage cut into two
     // halves of 6 MFMAs: no gain, tools/experiments/wino4_split_three_classes.patch.)
-#define W4_SB() __builtin_amdgcn_sched_barrier(0)
 // Priorities (round 4, A/B on one box): the MATRIX phases run above the transform (transform 0, matrix phases 1 / 2 by class): the
 // transform is latency-bound on its LDS reads and loses nothing at priority 0, a ready MFMA no longer waits behind another wave's
 // burst of transform fmas.  (Rounds 1-3: transform above the matrix phases; no priorities at all: -6 %.)
@@ -279,36 +213,21 @@ __global__ __launch_bounds__(768) void conv_wino4_kernel(ConvParams p, int regs_
     if (ch == 0) kloop(std::integral_constant<int, 0>{}); else kloop(std::integral_constant<int, 1>{});
 #undef W4_TS
 #undef W4_SS
-#undef W4_SB
-#undef W4_BARRIER
 
     // ---- output stage: one pass through a [xi][x][tile][32 couts] exchange image ----
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");         // the compiler does not see the asm LDS-DMAs
-    float* Rs = reinterpret_cast<float*>(smem);
-    const int Cout = p.out.c;
     // wino4_combine.inc is written for the 64-channel kernels (two passes of 32 channels, an optional fused 1x1 head): this kernel
-    // is its pass 0 without a head; hl is named only in the constant-false HEAD arm
+    // is its pass 0 without a head
     constexpr bool HEAD = false;
     constexpr int pass = 0;
-    float hl[2][4][4];
-    // the bias quads are fetched here, under the K loop's drain and the first barrier (a global load inside the combine step would
-    // queue behind output stores: one in-order vmcnt)
-    f32x4 bvp[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-    if (p.bias != nullptr) {
-        bvp[0] = *reinterpret_cast<const f32x4*>(p.bias + nb * 64 + 4 * (tid & 7));
-        if (nb * 64 + 32 < Cout) bvp[1] = *reinterpret_cast<const f32x4*>(p.bias + nb * 64 + 32 + 4 * (tid & 7));
-    }
+#include "wino4_out_begin.inc"
     // fold the wave's own row (R = M[xi][:] A) into the exchange image; `add` (ch = 1): onto the partner's partial sums
     auto write_R = [&](auto add_c) __attribute__((always_inline)) {
         constexpr bool add = decltype(add_c)::value;
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
             const int tl = (e & 3) + 8 * (e >> 2) + 4 * lh;               // accumulator row = tile slot
-            const float m0 = acc[0][e], m1 = acc[1][e], m2 = acc[2][e], m3 = acc[3][e], m4 = acc[4][e], m5 = acc[5][e];
-            const float s12 = m1 + m2, d12 = m1 - m2, s34 = m3 + m4, d34 = m3 - m4;
-            float* o = Rs + W4Lds::r_fold(xi, tl, li);
-            const float r0 = m0 + s12 + s34, r1 = __builtin_fmaf(KA, d12, KB * d34), r2 = __builtin_fmaf(KA2, s12, KB2 * s34),
-                        r3 = __builtin_fmaf(KA3, d12, __builtin_fmaf(KB3, d34, m5));
+            const int fold_at = W4Lds::r_fold(xi, tl, li);
+#include "wino4_fold.inc"
             if (add) {                                           // (this lane's four words: nobody else touches them in this phase)
                 o[W4Lds::r_plane(0)] += r0; o[W4Lds::r_plane(1)] += r1; o[W4Lds::r_plane(2)] += r2; o[W4Lds::r_plane(3)] += r3;
             } else {
@@ -338,24 +257,27 @@ bool conv_wino4_supported(const ConvParams& p) {
            p.in.c >= 8 && p.out.c % 32 == 0 && p.in.cs % 4 == 0 && p.out.cs % 4 == 0 && p.zero != nullptr && conv_wino4_span_ok(p, 2);
 }
 
-hipError_t launch_conv_wino4(const ConvParams& p, hipStream_t s) {
-    if (p.out.c != 32 || p.head_w != nullptr) return hipErrorInvalidValue;    // (every other F(4x4) layer: launch_conv_wino4r / launch_conv_wino4s)
+hipError_t launch_wino4_grid(const ConvParams& p, hipStream_t s, W4Kernel kern, DeviceOnce& attr_set, size_t kloop_lds, int nblocks) {
     const int regs_x = p.out.w / 16, regs_y = p.out.h / 16;
     const size_t nreg = p.lut != nullptr ? (size_t)(p.n / p.per_image) * p.lut_len : (size_t)p.n * regs_x * regs_y;
     const size_t npairs = (nreg + 1) / 2;
-    const size_t grid = npairs;                              // one output-channel block
+    const size_t grid = npairs * (size_t)nblocks;
     if (grid == 0) return hipSuccess;
     if (grid > 0x7fffffffull || !conv_wino4_span_ok(p, p.lut != nullptr ? p.per_image : 2)) return hipErrorInvalidValue;
-    size_t lds = (size_t)(3 * W4_HS + 12 * 2 * W4_BWS) * 16;
-    const size_t lds_epi = (size_t)W4Lds::EPI_FLOATS * 4;
-    if (lds_epi > lds) lds = lds_epi;
-    static DeviceOnce attr_set;                              // the attribute is per device
-    const hipError_t ea = attr_set.run([&] {
-        return hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wino4_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    const size_t lds_epi = (size_t)W4Lds::EPI_FLOATS * 4;    // the output stage's exchange image lies over the K loop's buffers
+    const size_t lds = lds_epi > kloop_lds ? lds_epi : kloop_lds;
+    const hipError_t ea = attr_set.run([&] {                 // the attribute is per device
+        return hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     });
     if (ea != hipSuccess) return ea;
-    hipLaunchKernelGGL(conv_wino4_kernel, dim3((unsigned)grid), dim3(768), lds, s, p, regs_x, regs_y, (int)npairs);
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(768), lds, s, p, regs_x, regs_y, (int)npairs);
     return hipGetLastError();
+}
+
+hipError_t launch_conv_wino4(const ConvParams& p, hipStream_t s) {
+    if (p.out.c != 32 || p.head_w != nullptr) return hipErrorInvalidValue;    // (every other F(4x4) layer: launch_conv_wino4r / launch_conv_wino4s)
+    static DeviceOnce attr_set;
+    return launch_wino4_grid(p, s, conv_wino4_kernel, attr_set, (size_t)(3 * W4_HS + 12 * 2 * W4_BWS) * 16, 1);      // one output-channel block
 }
 
 }  // namespace ecseg

@@ -17,6 +17,12 @@
 #define W4L_HD inline
 #endif
 
+// The region rule of the A-operand lane -> tile map (wino4_lane_tile.inc).  ds_read_b128 serves lanes {0-3,12-15,20-27} and {4-11,16-19,28-31} of
+// each wave half in separate LDS cycles; each of those groups gets the 16 tiles of ONE region: lane quad q8 = (lane & 31) >> 2 belongs to region
+// 0, 1, 1, 0, 1, 0, 0, 1.  The output stage applies the same rule to its tile-row pairs (two per tile row of the 32 tiles).  (A macro: as a
+// function the rule compiles to other device code in the output stages of conv_wino4_kernel and conv_wino4r_kernel, EXPERIMENTS.md round 11.)
+#define W4_QUAD_REGION(q8) ((0x96 >> (q8)) & 1)
+
 namespace ecseg {
 
 struct W4Lds {

@@ -40,27 +40,24 @@
 
 namespace ecseg {
 
+// (timing-only ablations exist only in A/B builds, tools/w4r_variants.sh -DECSEG_W4R_ABL=<bits>: 1 no filter DMA, 2 no halo DMA, 4 no MFMAs;
+// the hooks and their empty defaults: wino4_consts.inc, wino4_mfma_stage.inc)
+#ifdef ECSEG_W4R_ABL
+#define W4_DIAG_SKIP_HALO_DMA() do { if (ECSEG_W4R_ABL & 2) return; } while (0)
+#define W4_DIAG_SKIP_FILTER_DMA() do { if (ECSEG_W4R_ABL & 1) return; } while (0)
+#if ECSEG_W4R_ABL & 4
+#define W4_MFMA(ACC, A, B) asm volatile("" :: "v"(A), "v"(B))
+#endif
+#endif
 #include "wino4_consts.inc"
 #define W4_HALO_RING 2
 // raw image (only row_pass reads it): plain row / column order (one pad slot per row: W4Lds::RAW_ROW), the two 16-byte channel halves of a pixel next to each other
 #define W4_HALO_SLOT(r, cc) const int h = (cc) & 1, hy = (r), hx = (cc) >> 1
 #define W4_HALO_UPPER(cc) ((cc) & 1)
 #define W4_HALO_L W4Lds::Raw
-// (timing-only ablations exist only in A/B builds, tools/w4r_variants.sh -DECSEG_W4R_ABL=<bits>: 1 no filter DMA, 2 no halo DMA, 4 no MFMAs)
-#ifdef ECSEG_W4R_ABL
-#define W4_DIAG_SKIP_HALO_DMA() do { if (ECSEG_W4R_ABL & 2) return; } while (0)
-#define W4_DIAG_SKIP_FILTER_DMA() do { if (ECSEG_W4R_ABL & 1) return; } while (0)
-#else
-#define W4_DIAG_SKIP_HALO_DMA()
-#define W4_DIAG_SKIP_FILTER_DMA()
-#endif
-#define W4_DIAG_HALO_OFFSET(off, a)
-#if defined(ECSEG_W4R_ABL) && (ECSEG_W4R_ABL & 4)
-#define W4_MFMA(ACC, A, B) asm volatile("" :: "v"(A), "v"(B))
-#else
-#define W4_MFMA(ACC, A, B) ACC = __builtin_amdgcn_mfma_f32_32x32x2f32(A, B, ACC, 0, 0, 0)
-#endif
-#define W4_WAIT(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
+// filter stages (wino4_filter_dma.inc): wt4[nb][stage][wave] is 768 floats, the wave's double buffer follows the raw buffers and the t image
+#define W4_FILTER_STRIDE (12 * 768 * 4)
+#define W4_FILTER_LDS(buf) ((2 * W4_HS + W4R_TS + W4Lds::bw_stage(wave, buf)) * 16u)
 
 namespace {
 constexpr int W4R_TS = W4Lds::TS;       // slots of the t image: 2 regions x 6 transform rows x 4 tile rows x (18 columns x 2 channel halves), padded (wino4_lds_layout.h)
@@ -80,28 +77,13 @@ __global__ __launch_bounds__(768) void conv_wino4r_kernel(ConvParams p, int regs
     const int li = lane & 31, lh = lane >> 5;
 
 #include "wino4_region.inc"
-    // ---- filter DMA: wt4[nb][stage][wave][point pair nu / 2][lane = h * 32 + cout][nu % 2][k 2], 768 floats per wave and stage; the
-    //      address is a scalar base (advanced per stage by scalar adds) + the lane's constant 16-byte offset ----
+    // ---- filter DMA: wt4[nb][stage][wave][point pair nu / 2][lane = h * 32 + cout][nu % 2][k 2], 768 floats per wave and stage ----
     const unsigned long long w_base = (unsigned long long)(size_t)(p.wt + ((size_t)nb * nstages * 12 + wave) * 768);
-    const unsigned lane16 = (unsigned)lane * 16u;
     f32x4* Bw = Bs + W4Lds::bw_stage(wave, 0);
-    auto dma_filter_piece = [&](int stage, int buf, auto kk) __attribute__((always_inline)) {
-        W4_DIAG_SKIP_FILTER_DMA();
-        constexpr int k = decltype(kk)::value;
-        const unsigned long long g = w_base + (unsigned long long)stage * (12 * 768 * 4);
-        const unsigned dst = lds_base + (unsigned)(2 * W4_HS + W4R_TS + W4Lds::bw_stage(wave, buf)) * 16u;
-        const unsigned l16 = lane16;
-        unsigned keep;
-        // the instruction offset advances the global AND the LDS address: one M0 for the three pieces
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %3 offset:%4\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep) : "v"(l16), "s"(dst), "s"(g), "n"(k * 1024) : "memory");
-    };
+#include "wino4_filter_dma.inc"
 
-
-    const int q8 = li >> 2, tx = li & 3;
-    const int tg = (0x96 >> q8) & 1;
-    const int ty = (q8 == 0 || q8 == 1) ? 0 : (q8 == 2 || q8 == 3) ? 1 : (q8 == 4 || q8 == 5) ? 2 : 3;
-    const int t_lane = W4Lds::t_lane(tg, xi, ty, lh, tx);      // the lane's tile in the t image (wino4s_kernel.hip)
+#include "wino4_lane_tile.inc"
+    const int t_lane = W4Lds::t_lane(tg, xi, ty, lh, tx);      // the lane's tile in the t image
 
     f32x16 acc[6];
 #pragma unroll
@@ -109,99 +91,14 @@ __global__ __launch_bounds__(768) void conv_wino4r_kernel(ConvParams p, int regs
 #pragma unroll
         for (int e = 0; e < 16; ++e) acc[v][e] = 0.f;
 
-    // row_pass's item and its two LDS byte addresses (raw buffer 0, transform row 0) do not depend on the group: formed once and pinned - left alone the
-    // compiler rebuilds them (~20 vector instructions beside the MFMA stream) in every copy of the pass
-    unsigned rp_raw, rp_t;
-    {
-        const int item = wave * 48 + lane, cpair = item & 1, h = (item >> 1) & 1, k = item >> 2;
-        const int x = k % 18, r2 = k / 18, tyy = r2 & 3, tgg = r2 >> 2;
-        rp_raw = (unsigned)(W4Lds::raw_read(0, tgg, tyy, x, h) * 16 + cpair * 8);
-        rp_t = (unsigned)((2 * W4_HS + W4Lds::t_write(tgg, tyy, h, x)) * 16 + cpair * 8);
-        asm volatile("" : "+v"(rp_raw), "+v"(rp_t));
-    }
-    auto row_pass = [&](int grp) __attribute__((always_inline)) {
-        // 576 half items (region, tile row, channel half, column, channel PAIR) over the 12 waves x 48 lanes: every wave carries the
-        // same share (a pass run by five waves alone left the other seven waiting at the barrier behind it), 8-byte accesses,
-        // neighbouring lanes on neighbouring addresses
-        if (lane >= 48) return;
-        const f32x2* R = reinterpret_cast<const f32x2*>(smem + rp_raw + (unsigned)(W4Lds::raw_read(grp & 1, 0, 0, 0, 0) * 16));     // raw row 4 tyy + i: + i rows
-        constexpr int RR = 2 * W4Lds::raw_row();
-        const f32x2 d0 = R[RR * 0], d1 = R[RR * 1], d2 = R[RR * 2], d3 = R[RR * 3], d4 = R[RR * 4], d5 = R[RR * 5];
-        f32x2* T = reinterpret_cast<f32x2*>(smem + rp_t);                            // + xi transform rows
-        // t[xi] = c0 d[r0] + c1 d[r1] + c2 d[r2] + d[r3] as ONE fma chain per row, innermost term first: fma(c0, d[r0], fma(c1, d[r1],
-        // fma(c2, d[r2], d[r3]))) - the operation order of the per-wave row transform (wino4_kernel.hip), so every F(4x4) kernel forms
-        // bit-identical t.  (A first version shared the even / odd parts of the +- rows,
-        // 12 instead of 16 fmas per channel: the smooth fixture model's wrong-pixel total rose from 11 to 19 of ~15 hard pixels per image.)
-        f32x2 o;
-#define W4_ROW3(XI, A0, DA, A1, DB, DC) do { _Pragma("unroll") for (int c = 0; c < 2; ++c) o[c] = __builtin_fmaf(A0, DA[c], __builtin_fmaf(A1, DB[c], DC[c])); T[2 * (XI) * W4Lds::t_xi()] = o; } while (0)
-#define W4_ROW4(XI, A0, DA, A1, DB, A2, DC, DD) do { _Pragma("unroll") for (int c = 0; c < 2; ++c) \
-            o[c] = __builtin_fmaf(A0, DA[c], __builtin_fmaf(A1, DB[c], __builtin_fmaf(A2, DC[c], DD[c]))); T[2 * (XI) * W4Lds::t_xi()] = o; } while (0)
-        W4_ROW3(0, KP, d0, KS, d2, d4);
-        W4_ROW3(5, KP, d1, KS, d3, d5);
-        W4_ROW4(1, -KA * KB2, d1, -KB2, d2, KA, d3, d4);
-        W4_ROW4(2, KA * KB2, d1, -KB2, d2, -KA, d3, d4);
-        W4_ROW4(3, -KA2 * KB, d1, -KA2, d2, KB, d3, d4);
-        W4_ROW4(4, KA2 * KB, d1, -KA2, d2, -KB, d3, d4);
-#undef W4_ROW3
-#undef W4_ROW4
-    };
+#include "wino4_row_pass.inc"
     f32x4 t[6];
     auto load_t = [&]() __attribute__((always_inline)) {
         const f32x4* A = Ts + t_lane;
 #pragma unroll
         for (int j = 0; j < 6; ++j) t[j] = A[W4Lds::t_col(j)];
     };
-    // ---- one filter stage (2 of the group's 4 channel pairs; buffer ss): column transform + 12 MFMAs ----
-    auto mfma_stage = [&](int ss, int fbuf, int next_stage, int halo_grp) __attribute__((always_inline)) {     // ss: channel pair of the group, fbuf: filter buffer; halo_grp: group to prefetch, < 0: none
-        const int nbuf = fbuf ^ 1;
-        float V[6][2];
-#pragma unroll
-        for (int e = 0; e < 2; ++e) {   // V[nu] = sum_j B^T[nu][j] t[j], scalar ops (see transform)
-            const int c = 2 * ss + e;
-            const float u0 = t[0][c], u1 = t[1][c], u2 = t[2][c], u3 = t[3][c], u4 = t[4][c], u5 = t[5][c];
-            // points +-a share an even part (u4 - b2 u2) and an odd part (u3 - b2 u1), points +-b likewise with a2
-            const float ea = __builtin_fmaf(-KB2, u2, u4), oa = __builtin_fmaf(-KB2, u1, u3);
-            const float eb = __builtin_fmaf(-KA2, u2, u4), ob = __builtin_fmaf(-KA2, u1, u3);
-            V[0][e] = __builtin_fmaf(KP, u0, __builtin_fmaf(KS, u2, u4));
-            V[1][e] = __builtin_fmaf(KA, oa, ea);
-            V[2][e] = __builtin_fmaf(-KA, oa, ea);
-            V[3][e] = __builtin_fmaf(KB, ob, eb);
-            V[4][e] = __builtin_fmaf(-KB, ob, eb);
-            V[5][e] = __builtin_fmaf(KP, u1, __builtin_fmaf(KS, u3, u5));
-        }
-        f32x2 w2[6];
-        const f32x4* Bp = Bw + W4Lds::bw_stage(0, fbuf) + W4Lds::bw_read(lane, 0);        // three 16-byte reads: the fragments of point pairs (0, 1), (2, 3), (4, 5)
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const f32x4 w4 = Bp[W4Lds::bw_read(0, k)];
-            w2[2 * k] = f32x2{w4[0], w4[1]};
-            w2[2 * k + 1] = f32x2{w4[2], w4[3]};
-        }
-        // 12 MFMAs, channel-major: consecutive MFMAs hit different accumulators (dependency distance 6), so even a lone
-        // wave keeps the matrix pipe full.  The next stage's three filter pieces go out one at a time behind MFMAs 2, 4
-        // and 6 (pinned): the wave's issue slot is free while the pipe works, and the load path never sees a burst.
-#pragma unroll
-        for (int e = 0; e < 2; ++e)
-#pragma unroll
-            for (int v = 0; v < 6; ++v) {
-                W4_MFMA(acc[v], V[v][e], w2[v][e]);
-                if (e == 0 && (v == 1 || v == 3 || v == 5)) {
-                    __builtin_amdgcn_sched_barrier(0);
-                    if (v == 1) dma_filter_piece(next_stage, nbuf, std::integral_constant<int, 0>{});
-                    if (v == 3) dma_filter_piece(next_stage, nbuf, std::integral_constant<int, 1>{});
-                    if (v == 5) dma_filter_piece(next_stage, nbuf, std::integral_constant<int, 2>{});
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-                if (e == 1 && (v == 1 || v == 3) && halo_grp >= 0) {       // behind MFMAs 8 and 10
-                    __builtin_amdgcn_sched_barrier(0);
-                    if (v == 1) dma_halo_piece(halo_grp, std::integral_constant<int, 0>{});
-                    if (v == 3) dma_halo_piece(halo_grp, std::integral_constant<int, 1>{});
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
-    };
-#define W4_BARRIER() asm volatile("s_barrier" ::: "memory")
-#define W4_SB() __builtin_amdgcn_sched_barrier(0)
+#include "wino4_mfma_stage.inc"
     // Per group g: barrier Y(g-1) (the t image holds group g, raw buffer g & 1 is free: this wave's two halo pieces of group g + 2 go out) and
     // barrier X(g) (nobody needs the t image of group g any more, the raw halo of group g + 1 has landed: row_pass(g + 1) follows).  The
     // three waves of a SIMD sit at different points of the sequence:
@@ -213,9 +110,6 @@ __global__ __launch_bounds__(768) void conv_wino4r_kernel(ConvParams p, int regs
     // tools/experiments/wino4r_filter_two_stages_ahead.patch; s_setprio by rotation class, matrix phases above the transform: +-0.)
 #define W4_S(ss, g, H) do { W4_SB(); if (H) W4_WAIT(2); else W4_WAIT(0); W4_SB(); \
                             mfma_stage(ss, ss, (ss) == 0 ? 2 * (g) + 1 : ((g) + 1 < ngroups ? 2 * (g) + 2 : 2 * (g)), -1); W4_SB(); } while (0)
-#define W4_Y() do { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); W4_BARRIER(); W4_SB(); } while (0)
-#define W4_X() do { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); W4_BARRIER(); W4_SB(); } while (0)
-#define W4_HALO(g) do { dma_halo_piece((g), std::integral_constant<int, 0>{}); dma_halo_piece((g), std::integral_constant<int, 1>{}); } while (0)
     const int cls = wave >> 2;
     W4_HALO(0);
     if (ngroups > 1) W4_HALO(1);
@@ -270,41 +164,16 @@ __global__ __launch_bounds__(768) void conv_wino4r_kernel(ConvParams p, int regs
         }
     }
 #undef W4_S
-#undef W4_Y
-#undef W4_X
-#undef W4_HALO
-#undef W4_SB
-#undef W4_BARRIER
 
     // ---- output stage: two passes (channel halves) through a [xi][x][tile][32 couts] exchange image ----
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");         // the compiler does not see the asm LDS-DMAs
-    float* Rs = reinterpret_cast<float*>(smem);
-    const int Cout = p.out.c;
-    // Work split of the combine step: wino4_combine.inc (1024 whole items per pass, a wave owns tile pairs).
-    float hl[2][4][4];                                       // fused 1x1 head: partial logits [round][row of the tile][class]
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 4; ++b)
-#pragma unroll
-            for (int c = 0; c < 4; ++c) hl[a][b][c] = 0.f;
-    // the bias quads of both passes are fetched here, under the K loop's drain and the first barrier: a global load inside
-    // the combine step would queue behind the previous pass's output stores (one in-order vmcnt)
-    f32x4 bvp[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-    if (p.bias != nullptr) {
-        bvp[0] = *reinterpret_cast<const f32x4*>(p.bias + nb * 64 + 4 * (tid & 7));
-        if (nb * 64 + 32 < Cout) bvp[1] = *reinterpret_cast<const f32x4*>(p.bias + nb * 64 + 32 + 4 * (tid & 7));
-    }
+#include "wino4_out_begin.inc"
     // fold the wave's own row (R = M[xi][:] A) into the exchange image
     auto write_R = [&]() __attribute__((always_inline)) {
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
             const int tl = (e & 3) + 8 * (e >> 2) + 4 * lh;               // accumulator row = tile slot
-            const float m0 = acc[0][e], m1 = acc[1][e], m2 = acc[2][e], m3 = acc[3][e], m4 = acc[4][e], m5 = acc[5][e];
-            const float s12 = m1 + m2, d12 = m1 - m2, s34 = m3 + m4, d34 = m3 - m4;
-            float* o = Rs + W4Lds::r_fold(xi, tl, li);
-            const float r0 = m0 + s12 + s34, r1 = __builtin_fmaf(KA, d12, KB * d34), r2 = __builtin_fmaf(KA2, s12, KB2 * s34),
-                        r3 = __builtin_fmaf(KA3, d12, __builtin_fmaf(KB3, d34, m5));
+            const int fold_at = W4Lds::r_fold(xi, tl, li);
+#include "wino4_fold.inc"
             o[W4Lds::r_plane(0)] = r0; o[W4Lds::r_plane(1)] = r1; o[W4Lds::r_plane(2)] = r2; o[W4Lds::r_plane(3)] = r3;
         }
     };
@@ -324,11 +193,8 @@ __global__ __launch_bounds__(768) void conv_wino4r_kernel(ConvParams p, int regs
             for (int e8 = 0; e8 < 8; ++e8) {
                 const int e = 8 * P + e8;
                 const int tl = (e8 & 3) + 8 * (e8 >> 2) + 4 * lh;         // tile slot within the half: 0..15
-                const float m0 = acc[0][e], m1 = acc[1][e], m2 = acc[2][e], m3 = acc[3][e], m4 = acc[4][e], m5 = acc[5][e];
-                const float s12 = m1 + m2, d12 = m1 - m2, s34 = m3 + m4, d34 = m3 - m4;
-                float* o = Rs + W4Lds::r_fold_tile(xi, tl, ch, li);
-                const float r0 = m0 + s12 + s34, r1 = __builtin_fmaf(KA, d12, KB * d34), r2 = __builtin_fmaf(KA2, s12, KB2 * s34),
-                            r3 = __builtin_fmaf(KA3, d12, __builtin_fmaf(KB3, d34, m5));
+                const int fold_at = W4Lds::r_fold_tile(xi, tl, ch, li);
+#include "wino4_fold.inc"
                 o[W4Lds::r_plane(0)] = r0; o[W4Lds::r_plane(1)] = r1; o[W4Lds::r_plane(2)] = r2; o[W4Lds::r_plane(3)] = r3;
             }
             __syncthreads();
@@ -339,7 +205,7 @@ __global__ __launch_bounds__(768) void conv_wino4r_kernel(ConvParams p, int regs
                 if (u >= 16) break;
                 const int tp = u & 7, chh = u >> 3;
                 const int nq8 = 4 * P + (tp >> 1);           // tile row pair index of the 32 tiles
-                const int g = (0x96 >> nq8) & 1, nty = nq8 >> 1;
+                const int g = W4_QUAD_REGION(nq8), nty = nq8 >> 1;
                 const int img = g ? r_img[1] : r_img[0];
                 if (img < 0) continue;
                 const int co = nb * 64 + chh * 32 + 4 * cq;
@@ -353,7 +219,9 @@ __global__ __launch_bounds__(768) void conv_wino4r_kernel(ConvParams p, int regs
                 const f32x4 q4 = *reinterpret_cast<const f32x4*>(r + W4Lds::r_plane(4 * 4));
                 const f32x4 q5 = *reinterpret_cast<const f32x4*>(r + W4Lds::r_plane(4 * 5));
                 const f32x4 s12 = q1 + q2, d12 = q1 - q2, s34 = q3 + q4, d34 = q3 - q4;
-                f32x4 y[4];                                  // (wino4_combine.inc's expressions, term for term)
+                // From here to the pool stores the item is wino4_combine.inc's, term for term.  It stays written out: one body included by both forms
+                // is not byte-identical device code in this kernel (EXPERIMENTS.md round 11, tools/experiments/wino4_item_body.patch)
+                f32x4 y[4];
                 y[0] = q0 + s12 + s34 + bv;
                 y[1] = KA * d12 + KB * d34 + bv;
                 y[2] = KA2 * s12 + KB2 * s34 + bv;
@@ -411,24 +279,11 @@ __global__ __launch_bounds__(768) void conv_wino4r_kernel(ConvParams p, int regs
 bool conv_wino4r_supported(const ConvParams& p) { return conv_wino4_supported(p) && !(p.out.c == 32 && p.w4_split); }
 
 hipError_t launch_conv_wino4r(const ConvParams& p, hipStream_t s) {
-    const int regs_x = p.out.w / 16, regs_y = p.out.h / 16;
-    const size_t nreg = p.lut != nullptr ? (size_t)(p.n / p.per_image) * p.lut_len : (size_t)p.n * regs_x * regs_y;
-    const size_t npairs = (nreg + 1) / 2;
-    const size_t grid = npairs * (size_t)((p.out.c + 63) / 64);
-    if (grid == 0) return hipSuccess;
-    if (grid > 0x7fffffffull || !conv_wino4_span_ok(p, p.lut != nullptr ? p.per_image : 2)) return hipErrorInvalidValue;
-    if (p.head_w != nullptr && (!p.head_only || p.pool.p != nullptr)) return hipErrorInvalidValue;
-    size_t lds = (size_t)(2 * W4_HS + W4R_TS + 12 * 2 * W4_BWS) * 16;
-    const size_t lds_epi = (size_t)W4Lds::EPI_FLOATS * 4;
-    if (lds_epi > lds) lds = lds_epi;
-    void (*kern)(ConvParams, int, int, int) = p.head_w != nullptr ? conv_wino4r_kernel<true> : conv_wino4r_kernel<false>;
-    static DeviceOnce attr_set[2];
-    const hipError_t ea = attr_set[p.head_w != nullptr ? 1 : 0].run([&] {
-        return hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    });
-    if (ea != hipSuccess) return ea;
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(768), lds, s, p, regs_x, regs_y, (int)npairs);
-    return hipGetLastError();
+    if (p.head_w != nullptr && (!p.head_only || p.pool.p != nullptr)) return hipErrorInvalidValue;     // (the HEAD kernels write neither the features nor a pool)
+    static DeviceOnce attr_set[2];                           // (per template instance)
+    const int head = p.head_w != nullptr ? 1 : 0;
+    return launch_wino4_grid(p, s, head ? conv_wino4r_kernel<true> : conv_wino4r_kernel<false>, attr_set[head],
+                             (size_t)(2 * W4_HS + W4R_TS + 12 * 2 * W4_BWS) * 16, (p.out.c + 63) / 64);
 }
 
 }  // namespace ecseg

@@ -3,8 +3,8 @@
 //   cache)   32 every halo piece one contiguous KB.  Numbers: EXPERIMENTS.md (round 6), gpurun_out/r06_w4s_*ablate*.log.
 #define W4_DIAG_SKIP_HALO_DMA() do { if (ECSEG_W4S_ABL & 2) return; } while (0)
 #define W4_DIAG_HALO_OFFSET(off, a) do { if (ECSEG_W4S_ABL & 32) off = (unsigned)(a) * 16u; } while (0)
-#define W4S_DIAG_SKIP_FILTER_DMA() do { if (ECSEG_W4S_ABL & 1) return; } while (0)
-#define W4S_DIAG_STAGE(stage) ((ECSEG_W4S_ABL & 16) ? 0 : (stage))
+#define W4_DIAG_SKIP_FILTER_DMA() do { if (ECSEG_W4S_ABL & 1) return; } while (0)
+#define W4_DIAG_FILTER_STAGE(stage) ((ECSEG_W4S_ABL & 16) ? 0 : (stage))
 #define W4S_DIAG_NO_SPLIT ((ECSEG_W4S_ABL & 8) != 0)
 #if ECSEG_W4S_ABL & 4
 #define W4S_MFMA(CB, A, B) asm volatile("" :: "v"(A), "v"(B))

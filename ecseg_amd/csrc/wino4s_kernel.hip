@@ -36,6 +36,15 @@
 
 namespace ecseg {
 
+// Timing-only ablations (no filter DMA, no halo DMA, no MFMAs, no split arithmetic, hot / contiguous sources) exist only in A/B builds
+// with -DECSEG_W4S_ABL=<bits> (tools/w4s_variants.sh, csrc/wino4s_diag.inc); the product translation unit has ONE code path: every
+// hook is empty (the shared ones: wino4_consts.inc).
+#ifdef ECSEG_W4S_ABL
+#include "wino4s_diag.inc"
+#else
+#define W4S_DIAG_NO_SPLIT 0
+#define W4S_MFMA(CB, A, B) acc[P][CB] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A, B, acc[P][CB], 0, 0, 0)
+#endif
 #include "wino4_consts.inc"
 #define W4_HALO_RING 2
 // raw image of this kernel (only row_pass reads it): plain row / column order (one pad slot per row: W4Lds::RAW_ROW), the two 16-byte channel halves of a pixel NEXT to each other -
@@ -44,25 +53,9 @@ namespace ecseg {
 #define W4_HALO_SLOT(r, cc) const int h = (cc) & 1, hy = (r), hx = (cc) >> 1
 #define W4_HALO_UPPER(cc) ((cc) & 1)
 #define W4_HALO_L W4Lds::Raw
-
-#ifndef ECSEG_W4_TSLOTS
-#define ECSEG_W4_TSLOTS 4
-#endif
-// Timing-only ablations (no filter DMA, no halo DMA, no MFMAs, no split arithmetic, hot / contiguous sources) exist only in A/B builds
-// with -DECSEG_W4S_ABL=<bits> (tools/w4s_variants.sh, csrc/wino4s_diag.inc); the product translation unit has ONE code path: every
-// hook below is empty.
-#ifdef ECSEG_W4S_ABL
-#include "wino4s_diag.inc"
-#else
-#define W4_DIAG_SKIP_HALO_DMA()
-#define W4_DIAG_HALO_OFFSET(off, a)
-#define W4S_DIAG_SKIP_FILTER_DMA()
-#define W4S_DIAG_STAGE(stage) (stage)
-#define W4S_DIAG_NO_SPLIT 0
-#define W4S_MFMA(CB, A, B) acc[P][CB] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A, B, acc[P][CB], 0, 0, 0)
-#endif
-#define ESTAMP(i)
-#define W4_WAIT(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
+// filter stages (wino4_filter_dma.inc): image [nb][group][point slot][wave][3072 B], the wave's double buffer follows the raw buffers and the t image
+#define W4_FILTER_STRIDE (12 * W4S_STAGE)
+#define W4_FILTER_LDS(buf) ((2 * W4_HS + W4S_TS) * 16 + W4Lds::s_stage(wave, buf))
 
 namespace {
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
@@ -95,24 +88,12 @@ __global__ __launch_bounds__(768) void conv_wino4s_kernel(ConvParams p, int regs
 
 #include "wino4_region.inc"
     (void)nstages;
-    // ---- filter DMA: image [nb][group][point slot][wave][3072 B]; scalar base + the lane's constant 16-byte offset ----
+    // ---- filter DMA: image [nb][group][point slot][wave][3072 B] ----
     const unsigned long long w_base = (unsigned long long)(size_t)p.wt + ((size_t)nb * (3 * ngroups) * 12 + wave) * W4S_STAGE;
-    const unsigned lane16 = (unsigned)lane * 16u;
-    auto dma_filter_piece = [&](int stage, int buf, auto kk) __attribute__((always_inline)) {
-        constexpr int k = decltype(kk)::value;
-        W4S_DIAG_SKIP_FILTER_DMA();
-        const unsigned long long g = w_base + (unsigned long long)W4S_DIAG_STAGE(stage) * (12 * W4S_STAGE);
-        const unsigned dst = lds_base + (unsigned)((2 * W4_HS + W4S_TS) * 16 + W4Lds::s_stage(wave, buf));
-        const unsigned l16 = lane16;
-        unsigned keep;
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %3 offset:%4\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep) : "v"(l16), "s"(dst), "s"(g), "n"(k * 1024) : "memory");
-    };
+#include "wino4_filter_dma.inc"
 
     // ---- the lane's tile (as in the fp32 kernel: the b128 lane groups of a region read conflict-free) and its slot in the t image ----
-    const int q8 = li >> 2, tx = li & 3;
-    const int tg = (0x96 >> q8) & 1;
-    const int ty = (q8 == 0 || q8 == 1) ? 0 : (q8 == 2 || q8 == 3) ? 1 : (q8 == 4 || q8 == 5) ? 2 : 3;
+#include "wino4_lane_tile.inc"
     // t image (W4Lds, wino4_lds_layout.h): the 16 lanes of a b128 group - 4 x 4 tiles of one region - hit 16 different slots of the bank row, and
     // so do the 16-lane groups of row_pass's 8-byte writes (tools/lds_bank_model.cpp walks both)
     const int t_lane = W4Lds::t_lane(tg, xi, ty, lh, tx);
@@ -131,48 +112,7 @@ __global__ __launch_bounds__(768) void conv_wino4s_kernel(ConvParams p, int regs
 #pragma unroll
             for (int e = 0; e < 16; ++e) acc[v][cb][e] = 0.f;
 
-    // ---- the row transform, ONCE per workgroup and group (round 6, second version).  In the fp32 kernel - and in this kernel's first
-    //      version - every wave reads the raw halo rows of its transform row itself: 20 ds_read_b128 per wave and group, 240 KB of LDS
-    //      reads per group for 21 KB of data, and with the channel sum three times faster that traffic (+ 144 KB of filter reads +
-    //      134 KB of LDS-DMA writes = 518 KB at 128 B / clock) - not the matrix pipe, not the vector pipe - set the pace
-    //      (tools/experiments/w4s_ablate.sh).  Now 288 threads transform the group cooperatively: item = (region, tile row, column,
-    //      channel half): six raw rows in, t[xi = 0..5] out (12 fmas per channel, the +- rows share their even / odd parts), written
-    //      to the t image; a wave then reads the five columns of ITS row: raw 28 KB + t 28 KB written + 60 KB read. ----
-    // row_pass's item and its two LDS byte addresses (raw buffer 0, transform row 0) do not depend on the group: formed once and pinned - left alone the
-    // compiler rebuilds them (~20 vector instructions beside the MFMA stream) in every copy of the pass
-    unsigned rp_raw, rp_t;
-    {
-        const int item = wave * 48 + lane, cpair = item & 1, h = (item >> 1) & 1, k = item >> 2;
-        const int x = k % 18, r2 = k / 18, tyy = r2 & 3, tgg = r2 >> 2;
-        rp_raw = (unsigned)(W4Lds::raw_read(0, tgg, tyy, x, h) * 16 + cpair * 8);
-        rp_t = (unsigned)((2 * W4_HS + W4Lds::t_write(tgg, tyy, h, x)) * 16 + cpair * 8);
-        asm volatile("" : "+v"(rp_raw), "+v"(rp_t));
-    }
-    auto row_pass = [&](int grp) __attribute__((always_inline)) {
-        // 576 half items (region, tile row, channel half, column, channel PAIR) over the 12 waves x 48 lanes: every wave carries the
-        // same share (a pass run by five waves alone left the other seven waiting at the barrier behind it), 8-byte accesses,
-        // neighbouring lanes on neighbouring addresses
-        if (lane >= 48) return;
-        const f32x2* R = reinterpret_cast<const f32x2*>(smem + rp_raw + (unsigned)(W4Lds::raw_read(grp & 1, 0, 0, 0, 0) * 16));     // raw row 4 tyy + i: + i rows
-        constexpr int RR = 2 * W4Lds::raw_row();
-        const f32x2 d0 = R[RR * 0], d1 = R[RR * 1], d2 = R[RR * 2], d3 = R[RR * 3], d4 = R[RR * 4], d5 = R[RR * 5];
-        f32x2* T = reinterpret_cast<f32x2*>(smem + rp_t);                            // + xi transform rows
-        // t[xi] = c0 d[r0] + c1 d[r1] + c2 d[r2] + d[r3] as the SAME fma chains conv_wino4r_kernel's row_pass runs (one chain per row, innermost term
-        // first): bit-identical t, hence bit-identical results in the fp32 kernel.  (A first version shared the even / odd parts of the +- rows,
-        // 12 instead of 16 fmas per channel: the smooth fixture model's wrong-pixel total rose from 11 to 19 of ~15 hard pixels per image.)
-        f32x2 o;
-#define W4_ROW3(XI, A0, DA, A1, DB, DC) do { _Pragma("unroll") for (int c = 0; c < 2; ++c) o[c] = __builtin_fmaf(A0, DA[c], __builtin_fmaf(A1, DB[c], DC[c])); T[2 * (XI) * W4Lds::t_xi()] = o; } while (0)
-#define W4_ROW4(XI, A0, DA, A1, DB, A2, DC, DD) do { _Pragma("unroll") for (int c = 0; c < 2; ++c) \
-            o[c] = __builtin_fmaf(A0, DA[c], __builtin_fmaf(A1, DB[c], __builtin_fmaf(A2, DC[c], DD[c]))); T[2 * (XI) * W4Lds::t_xi()] = o; } while (0)
-        W4_ROW3(0, KP, d0, KS, d2, d4);
-        W4_ROW3(5, KP, d1, KS, d3, d5);
-        W4_ROW4(1, -KA * KB2, d1, -KB2, d2, KA, d3, d4);
-        W4_ROW4(2, KA * KB2, d1, -KB2, d2, -KA, d3, d4);
-        W4_ROW4(3, -KA2 * KB, d1, -KA2, d2, KB, d3, d4);
-        W4_ROW4(4, KA2 * KB, d1, -KA2, d2, -KB, d3, d4);
-#undef W4_ROW3
-#undef W4_ROW4
-    };
+#include "wino4_row_pass.inc"
     f32x4 t[5];
     auto load_t = [&]() __attribute__((always_inline)) {
         const f32x4* A = Ts + t_lane;
@@ -259,8 +199,6 @@ __global__ __launch_bounds__(768) void conv_wino4s_kernel(ConvParams p, int regs
         W4S_MFMA(1, A1, B12b);
         __builtin_amdgcn_sched_barrier(0);                   // (MFMAs are no memory operations: without this they sink below the s_barrier that follows)
     };
-#define W4_BARRIER() asm volatile("s_barrier" ::: "memory")
-#define W4_SB() __builtin_amdgcn_sched_barrier(0)
     // Barriers and phases.  Per group g: barrier Y(g-1) - the t image holds group g and raw buffer g & 1 is free (this wave's halo pieces
     // of group g + 2 go out right behind it) - and barrier X(g) - nobody needs the t image of group g any more and the raw halo of
     // group g + 1 has landed: row_pass(g + 1) follows it.  Between them every wave runs its three point phases, but the three waves
@@ -275,9 +213,6 @@ __global__ __launch_bounds__(768) void conv_wino4s_kernel(ConvParams p, int regs
     // the two phases that follow Y, vmcnt(3) for the third (and for all of them once no halo is left to fetch).
 #define W4_PH(PP, s, H) do { W4_SB(); if (H) W4_WAIT(5); else W4_WAIT(3); W4_SB(); \
                              point(std::integral_constant<int, PP>{}, (s) & 1, (s) + 2 < 3 * ngroups ? (s) + 2 : 3 * ngroups - 1); } while (0)
-#define W4_Y() do { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); W4_BARRIER(); W4_SB(); } while (0)      /* (own share of the row pass is written) */
-#define W4_X() do { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); W4_BARRIER(); W4_SB(); } while (0)      /* (own t[] is loaded) */
-#define W4_HALO(g) do { dma_halo_piece((g), std::integral_constant<int, 0>{}); dma_halo_piece((g), std::integral_constant<int, 1>{}); } while (0)
     const int cls = wave >> 2;
     W4_HALO(0);
     if (ngroups > 1) W4_HALO(1);
@@ -349,28 +284,9 @@ __global__ __launch_bounds__(768) void conv_wino4s_kernel(ConvParams p, int regs
         W4_PH(2, 3 * ngroups - 1, false);
     }
 #undef W4_PH
-#undef W4_Y
-#undef W4_X
-#undef W4_HALO
-#undef W4_SB
-#undef W4_BARRIER
 
     // ---- output stage: two passes (column blocks) through the [xi][x][tile][32 couts] exchange image ----
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");         // the compiler does not see the asm LDS-DMAs
-    float* Rs = reinterpret_cast<float*>(smem);
-    const int Cout = p.out.c;
-    float hl[2][4][4];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 4; ++b)
-#pragma unroll
-            for (int c = 0; c < 4; ++c) hl[a][b][c] = 0.f;
-    f32x4 bvp[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-    if (p.bias != nullptr) {
-        bvp[0] = *reinterpret_cast<const f32x4*>(p.bias + nb * 64 + 4 * (tid & 7));
-        if (nb * 64 + 32 < Cout) bvp[1] = *reinterpret_cast<const f32x4*>(p.bias + nb * 64 + 32 + 4 * (tid & 7));
-    }
+#include "wino4_out_begin.inc"
     // R = M[xi][:] A of a HALF row (A^T = [1 1 1 1 1 0; 0 a -a b -b 0; 0 a2 a2 b2 b2 0; 0 a3 -a3 b3 -b3 1]):
     //   half 0 (m0, m+a, m-a):   r0 = m0 + s, r1 = a d, r2 = a2 s, r3 = a3 d            s = m+ + m-, d = m+ - m-
     //   half 1 (minf, m+b, m-b): r0 = s, r1 = b d, r2 = b2 s, r3 = b3 d + minf
@@ -458,24 +374,11 @@ hipError_t launch_wino4s_filter(const float* wt_wino4, void* dst, int cin, int c
 bool conv_wino4s_supported(const ConvParams& p) { return conv_wino4_supported(p) && p.out.c % 64 == 0; }
 
 hipError_t launch_conv_wino4s(const ConvParams& p, hipStream_t s) {
-    const int regs_x = p.out.w / 16, regs_y = p.out.h / 16;
-    const size_t nreg = p.lut != nullptr ? (size_t)(p.n / p.per_image) * p.lut_len : (size_t)p.n * regs_x * regs_y;
-    const size_t npairs = (nreg + 1) / 2;
-    const size_t grid = npairs * (size_t)(p.out.c / 64);
-    if (grid == 0) return hipSuccess;
-    if (grid > 0x7fffffffull || !conv_wino4_span_ok(p, p.lut != nullptr ? p.per_image : 2)) return hipErrorInvalidValue;
     if (p.head_w != nullptr && (!p.head_only || p.pool.p != nullptr)) return hipErrorInvalidValue;     // (the HEAD kernels write neither the features nor a pool)
-    size_t lds = (size_t)(2 * W4_HS + W4S_TS) * 16 + (size_t)12 * 2 * W4S_STAGE;
-    const size_t lds_epi = (size_t)W4Lds::EPI_FLOATS * 4;
-    if (lds_epi > lds) lds = lds_epi;
-    void (*kern)(ConvParams, int, int, int) = p.head_w != nullptr ? conv_wino4s_kernel<true> : conv_wino4s_kernel<false>;
-    static DeviceOnce attr_set[2];
-    const hipError_t ea = attr_set[p.head_w != nullptr ? 1 : 0].run([&] {
-        return hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    });
-    if (ea != hipSuccess) return ea;
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(768), lds, s, p, regs_x, regs_y, (int)npairs);
-    return hipGetLastError();
+    static DeviceOnce attr_set[2];                           // (per template instance)
+    const int head = p.head_w != nullptr ? 1 : 0;
+    return launch_wino4_grid(p, s, head ? conv_wino4s_kernel<true> : conv_wino4s_kernel<false>, attr_set[head],
+                             (size_t)(2 * W4_HS + W4S_TS) * 16 + (size_t)12 * 2 * W4S_STAGE, p.out.c / 64);
 }
 
 }  // namespace ecseg

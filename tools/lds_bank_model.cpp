@@ -141,11 +141,11 @@ struct Model {
     }
 };
 
-// the lane -> tile map of the MFMA A operand (the kernels' q8 / tg / ty / tx)
-void lane_tile(int lane, int& li, int& lh, int& tg, int& ty, int& tx) {
-    li = lane & 31; lh = lane >> 5;
-    const int q8 = li >> 2;
-    tx = li & 3; tg = (0x96 >> q8) & 1; ty = q8 >> 1;
+// the lane -> tile map of the MFMA A operand: the text the kernels compile (csrc/wino4_lane_tile.inc)
+void lane_tile(int lane, int& li_, int& lh_, int& tg_, int& ty_, int& tx_) {
+    const int li = lane & 31;
+#include "wino4_lane_tile.inc"
+    li_ = li; lh_ = lane >> 5; tg_ = tg; ty_ = ty; tx_ = tx;
 }
 
 template <class L>
@@ -155,7 +155,7 @@ std::vector<Site> sites() {
     const long T0 = 2L * L::HS * 16, B0 = T0 + (long)L::TS * 16;      // conv_wino4r / conv_wino4s: t image, filter stages (bytes from the segment's start)
     const long B0K = 3L * L::HS * 16;                                  // conv_wino4: filter stages behind the 3-deep ring
 
-    // ---- row_pass (wino4r_kernel.hip, wino4s_kernel.hip): item = wave * 48 + lane, lanes >= 48 idle ----
+    // ---- row_pass (wino4_row_pass.inc): item = wave * 48 + lane, lanes >= 48 idle ----
     // disassembly: ds_read2_b64 x 3 (raw rows 0|1, 2|3, 4|5), ds_write_b64 x 6
     auto item = [](int wave, int lane, int& cpair, int& h, int& x, int& tyy, int& tgg) {
         const int it = wave * 48 + lane, k = it >> 2;
