@@ -283,9 +283,92 @@ def kernel_order_error(a, b, cin, cout=16, tiles=64, seed=0):
 
 
 # ---- tails -----------------------------------------------------------------------------------------------------------------------------
+def _spec(act):
+    """An activation as (name, alpha): a plain name, or (name, alpha) with LeakyReLU's slope, ELU's alpha or ReLU's max_value."""
+    return (act, None) if isinstance(act, str) else (act[0], act[1])
+
+
 def act64(y, act):
-    assert act in ('linear', 'relu'), act
-    return np.maximum(y, 0) if act == 'relu' else y
+    """The activation in float64, each in the form that does not cancel.  ``act``: a name (linear, relu, sigmoid, tanh, elu, swish) or
+    (name, alpha) for leaky_relu / elu / relu_clip."""
+    name, alpha = _spec(act)
+    y = np.asarray(y, np.float64)
+    with np.errstate(over='ignore', under='ignore'):
+        if name == 'linear':
+            return y
+        if name == 'relu':
+            return np.maximum(y, 0)
+        if name == 'relu_clip':
+            return np.clip(y, 0.0, alpha)
+        if name == 'leaky_relu':
+            return np.where(y > 0, y, alpha * y)
+        if name in ('sigmoid', 'swish'):
+            e = np.exp(-np.abs(y))
+            s = np.where(y >= 0, 1.0 / (1.0 + e), e / (1.0 + e))
+            return s if name == 'sigmoid' else y * s
+        if name == 'tanh':
+            return np.tanh(y)
+        if name == 'elu':
+            return np.where(y > 0, y, (1.0 if alpha is None else alpha) * np.expm1(np.minimum(y, 0.0)))
+    raise AssertionError('no activation %r' % (act,))
+
+
+FLT_MIN, DENORMAL = 2.0 ** -126, 2.0 ** -149
+SECOND = 1.0 + 2.0 ** -10          # the products of errors that a first-order count leaves out (as in tests/test_gpu_layers.py)
+
+
+def act_lip(act):
+    """The largest |act'| anywhere: what an error of the argument is multiplied by at most."""
+    name, alpha = _spec(act)
+    if name in ('linear', 'relu', 'relu_clip', 'tanh'):
+        return 1.0
+    if name == 'sigmoid':
+        return 0.25
+    if name == 'elu':
+        return max(1.0, 1.0 if alpha is None else abs(alpha))     # alpha e^v for v <= 0
+    if name == 'leaky_relu':
+        return max(1.0, abs(alpha))
+    raise AssertionError('no Lipschitz constant for %r' % (act,))
+
+
+def act_own(v, act, expm1=False):
+    """-> (bound, exact): the error of the convolution kernels' own float32 evaluation of act at the float32 argument v, as an absolute
+    bound per element (derived in tests/test_gpu_conv_tails.py from OCML's documented ceilings, as tests/test_gpu_layers.py's table is);
+    ``exact``: the result is one of the inputs or a constant (the select class: bound 0).  ``expm1``: the element-wise kernels' ELU
+    (dwconv_kernel, apply_act_ext: alpha * expm1f(v)) instead of the convolution kernels' alpha * (expf(v) - 1.f)."""
+    name, alpha = _spec(act)
+    v = np.asarray(v, np.float64)
+    want = np.abs(act64(v, act))
+    if name in ('linear', 'relu', 'relu_clip'):
+        return np.zeros_like(v), True
+    if name == 'leaky_relu':
+        return U32 * want + DENORMAL, False
+    if name in ('sigmoid', 'swish'):
+        floor = FLT_MIN
+        if name == 'swish':
+            floor = np.where(-v > np.log(float(np.finfo(np.float32).max)), np.abs(v) / float(np.finfo(np.float32).max), FLT_MIN)
+        return 8 * U32 * want * SECOND + floor, False
+    if name == 'tanh':
+        return 10 * U32 * want * SECOND + FLT_MIN, False
+    if name == 'elu':
+        a = 1.0 if alpha is None else abs(alpha)
+        if expm1:
+            return 7 * U32 * want * SECOND + FLT_MIN, False
+        ev = np.exp(np.minimum(v, 0.0))
+        return np.where(v > 0, 0.0, a * U32 * (6 * ev + 2 * np.abs(ev - 1.0)) * SECOND + FLT_MIN), False
+    raise AssertionError('no bound for %r' % (act,))
+
+
+def act32(y, act):
+    """The convolution kernels' float32 evaluation of act on float32 values, as float64 arrays of float32 values (the replay's tail): the
+    float64 function rounded once, except ELU, which follows the kernels' alpha * (expf(v) - 1.f)."""
+    name, alpha = _spec(act)
+    y = f32(y)
+    if name == 'elu':
+        a = 1.0 if alpha is None else alpha
+        with np.errstate(under='ignore'):
+            return np.where(y > 0, y, f32(a * f32(f32(np.exp(np.minimum(y, 0.0))) - 1.0)))
+    return f32(act64(y, act))
 
 
 def pool2(y, how=np.max):
@@ -298,12 +381,13 @@ def softmax64(l):
     return e / e.sum(axis=-1, keepdims=True)
 
 
-def head_replay(y, hw, hb):
-    """The fused 1 x 1 softmax head (wino4_combine.inc, wino4_head.inc) in float32: per pass of 32 channels a lane adds the products of its
-    channel quad onto its partial logits, a butterfly over the eight lanes of a pixel, the bias, softmax with float32 exp."""
+def head_replay(y, hw, hb, act='softmax'):
+    """The fused 1 x 1 head (wino4_combine.inc, wino4_head.inc) in float32: per pass of 32 channels a lane adds the products of its
+    channel quad onto its partial logits, a butterfly over the eight lanes of a pixel, the bias, then softmax over the k <= 4 classes with
+    float32 exp, or the head's activation (``act32``)."""
     hw, hb = np.asarray(hw, np.float64).reshape(-1, np.asarray(hw).shape[-1]), np.asarray(hb, np.float64)
     cout, k = hw.shape
-    assert cout == 64
+    assert cout == 64 and 1 <= k <= 4
     part = [np.zeros(y.shape[:-1] + (k,)) for _ in range(8)]
     for p in range(2):
         for q in range(8):
@@ -315,6 +399,8 @@ def head_replay(y, hw, hb):
     for step in (1, 2, 4):
         part = [f32(part[q] + part[q ^ step]) for q in range(8)]
     l = f32(part[0] + hb)
+    if _spec(act)[0] != 'softmax':
+        return act32(l, act)
     e = f32(np.exp(f32(l - l.max(axis=-1, keepdims=True))))
     s = e[..., 0]
     for c in range(1, k):
@@ -353,20 +439,31 @@ def pool_scale(q):
     return pool2(q)
 
 
-def head_scale(q, y, head):
-    """-> (S, own) of the head's outputs, both (N, H, W, k), equal over the classes of a pixel: S = max_k sum_o |h_ok| Q_o, the convolution's
-    scale carried through the 1 x 1 layer (softmax is 1-Lipschitz in the max norm, so every class moves by at most the largest move of a
-    logit); ``own`` = the head's own roundings as an absolute bound: HEAD_OWN u (sum_o |h_ok| |y_o| + |hb_k|) on the logits, and
-    SOFTMAX_OWN u + 2 u (max l - min l) on the softmax itself (outputs <= 1; the float32 difference l - max carries u |l - max| into the
-    exponent)."""
+def head_scale(q, y, head, act='softmax', feat_own=None):
+    """-> (S, own) of the head's outputs, both (N, H, W, k), k <= 4 classes.  Per class S_k = sum_o |h_ok| Q_o, the convolution's scale
+    carried through the 1 x 1 layer, and own_k = HEAD_OWN u (sum_o |h_ok| |y_o| + |hb_k|), the head's own roundings on the logit, plus
+    sum_o |h_ok| feat_own_o where the features carry an error of their own (``feat_own``: the convolution's activation).
+
+    softmax   is 1-Lipschitz in the max norm, so every class moves by at most the largest move of a logit: S and own are the maxima over the
+              classes, and own gains SOFTMAX_OWN u + 2 u (max l - min l) for the softmax itself (outputs <= 1; the float32 difference
+              l - max carries u |l - max| into the exponent).  One class: the output is e^0 / e^0 = 1 whatever the logit.
+    other     S_k and own_k times the head activation's Lipschitz constant (``act_lip``), plus its own bound at the logit (``act_own``).
+              SECOND on the L own term: the device evaluates the activation at its own logit, not at l, and act_own is at most 10 u times
+              a function of slope <= L, so it moves by at most 10 u L own."""
     hw, hb = head
     hw, hb = np.abs(np.asarray(hw, np.float64).reshape(q.shape[-1], -1)), np.asarray(hb, np.float64)
-    S = (q @ hw).max(axis=-1, keepdims=True)
-    l = y @ np.asarray(head[0], np.float64).reshape(q.shape[-1], -1) + hb
-    own = (HEAD_OWN * U32 * (np.abs(y) @ hw + np.abs(hb))).max(axis=-1, keepdims=True)
-    own = own + U32 * (SOFTMAX_OWN + 2 * (l.max(axis=-1, keepdims=True) - l.min(axis=-1, keepdims=True)))
     k = hw.shape[1]
-    return np.repeat(S, k, axis=-1), np.repeat(own, k, axis=-1)
+    S = q @ hw
+    l = y @ np.asarray(head[0], np.float64).reshape(q.shape[-1], -1) + hb
+    own = HEAD_OWN * U32 * (np.abs(y) @ hw + np.abs(hb))
+    if feat_own is not None:
+        own = own + feat_own @ hw
+    if _spec(act)[0] == 'softmax':
+        S, own = S.max(axis=-1, keepdims=True), own.max(axis=-1, keepdims=True)
+        own = own + U32 * (SOFTMAX_OWN + 2 * (l.max(axis=-1, keepdims=True) - l.min(axis=-1, keepdims=True)))
+        return np.repeat(S, k, axis=-1), np.repeat(own, k, axis=-1)
+    L = act_lip(act)
+    return L * S, L * own * SECOND + act_own(l, act)[0]
 
 
 def replay(x, w, b=None, mode='fp32', act='linear', tail=None, head=None):
