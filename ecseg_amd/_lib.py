@@ -21,6 +21,7 @@ EXPORTS = [
     'ecseg_comm_unique_id', 'ecseg_comm_create', 'ecseg_comm_destroy', 'ecseg_comm_last_error', 'ecseg_allgather_records', 'ecseg_allgather_records_dev',
     'ecseg_npy_write_i64', 'ecseg_png_write_labels', 'ecseg_png_write', 'ecseg_png_write_channel', 'ecseg_npy_label_info', 'ecseg_npy_read_labels_u8', 'ecseg_tiff_write_gray8', 'ecseg_tiff_info', 'ecseg_tiff_read',
     'ecseg_tiff_write_rgb8', 'ecseg_npy_write_i32_as_i64',
+    'ecseg_tiff_encode_bound', 'ecseg_tiff_encode', 'ecseg_fish_render_tiff',
 ]
 
 
@@ -122,6 +123,9 @@ def load_library():
     lib.ecseg_fish_spots.argtypes = [vp, vp, i32, i32, u8p, i32, vp, i32, vp, i32, C.c_double, vp, i32, i32, i32, vp, vp, vp,
                                      C.POINTER(C.c_int32)]
     lib.ecseg_fish_render.argtypes = [vp, u8p, i32, i32, i32, vp, u8p, i32, u8p, vp, vp, vp]
+    lib.ecseg_tiff_encode_bound.argtypes = [i32, i32, i32]; lib.ecseg_tiff_encode_bound.restype = C.c_longlong
+    lib.ecseg_tiff_encode.argtypes = [vp, u8p, i32, i32, i32, i32, vp, C.c_longlong, C.POINTER(C.c_longlong)]
+    lib.ecseg_fish_render_tiff.argtypes = [vp, u8p, i32, i32, i32, vp, u8p, i32, u8p, C.POINTER(vp), C.c_longlong, C.POINTER(C.c_longlong), vp, vp, vp]
     lib.ecseg_min_cut.argtypes = [vp, vp, C.c_longlong, vp, i32, i32, vp, vp]
     lib.ecseg_nuset_forward.argtypes = [vp, vp, i32, i32, i32, i32, vp]
     lib.ecseg_rpn_proposals.argtypes = [vp, vp, vp, i32, i32, i32, vp, i32, i32, i32, C.c_float, i32, i32, C.POINTER(C.c_int32), vp, vp, vp]
@@ -567,6 +571,48 @@ class Handle:
         self._check(self.lib.ecseg_fish_render(self.h, _ptr(im), H, W, im.shape[2], _ptr(ch), _ptr(thr), thr.shape[2], _ptr(bnd),
                                                _ptr(out[0]), _ptr(out[1]), _ptr(out[2])), 'ecseg_fish_render')
         return tuple(out)
+
+    def tiff_encode(self, img, invert=False, capacity=None):
+        """(H, W) or (H, W, 3) uint8 image -> the bytes of the file ``image_io.write_tiff_gray8(path, img, invert)`` /
+        ``write_tiff_rgb8(path, img)`` writes, with every LZW strip encoded on the device (ecseg_tiff_encode).  ``capacity``: bytes
+        of the buffer the file is built in, by default ecseg_tiff_encode_bound; a file that does not fit raises, with code -1."""
+        im = _u8(img)
+        if im.ndim == 3 and im.shape[2] == 1:
+            im = im[..., 0]
+        if im.ndim not in (2, 3) or (im.ndim == 3 and im.shape[2] != 3) or not im.size:
+            raise ValueError('tiff_encode takes a non-empty (H, W) or (H, W, 3) uint8 image')
+        H, W = im.shape[:2]
+        spp = 1 if im.ndim == 2 else 3
+        cap = self.lib.ecseg_tiff_encode_bound(H, W, spp) if capacity is None else int(capacity)
+        if cap < 0:
+            raise ValueError('tiff_encode: an image of %d x %d x %d samples cannot be written as a TIFF' % (H, W, spp))
+        out = np.empty(max(cap, 1), np.uint8)
+        n = C.c_longlong()
+        self._check(self.lib.ecseg_tiff_encode(self.h, _ptr(im), H, W, spp, int(bool(invert)), _ptr(out), cap, C.byref(n)), 'ecseg_tiff_encode')
+        return out[:n.value].tobytes()
+
+    def fish_render_tiff(self, img, channels, thresholded, boundaries, want_rasters=False):
+        """``fish_render``'s inputs -> the bytes of the three files ``image_io.write_tiff_rgb8`` writes for its rasters (``_original``,
+        ``_original_with_segmentation``, ``_lsq_``): rendered and LZW-encoded without leaving the device (ecseg_fish_render_tiff).
+        ``want_rasters``: return (files, rasters), the rasters as ``fish_render`` returns them."""
+        im, thr, bnd = _u8(img), _u8(thresholded), _u8(boundaries)
+        if im.ndim != 3 or thr.ndim != 3 or bnd.ndim != 2 or thr.shape[:2] != im.shape[:2] or bnd.shape != im.shape[:2]:
+            raise ValueError('fish_render_tiff takes an (H, W, C) image, (H, W, n_probe) masks and (H, W) boundaries of one extent')
+        ch = np.ascontiguousarray(channels, np.int32).reshape(-1)
+        if len(ch) != im.shape[2]:
+            raise ValueError('fish_render_tiff takes one channel index per image channel (blue, green, red[, aqua])')
+        H, W = bnd.shape
+        cap = self.lib.ecseg_tiff_encode_bound(H, W, 3)
+        if cap < 0:
+            raise ValueError('fish_render_tiff: an image of %d x %d pixels cannot be written as a TIFF' % (H, W))
+        files = [np.empty(cap, np.uint8) for _ in range(3)]
+        ptrs = (C.c_void_p * 3)(*[f.ctypes.data for f in files])
+        n = (C.c_longlong * 3)()
+        rasters = [np.empty((H, W, 3), np.uint8) for _ in range(3)] if want_rasters else [None] * 3
+        self._check(self.lib.ecseg_fish_render_tiff(self.h, _ptr(im), H, W, im.shape[2], _ptr(ch), _ptr(thr), thr.shape[2], _ptr(bnd), ptrs, cap, n,
+                                                    *[_ptr(r) if r is not None else None for r in rasters]), 'ecseg_fish_render_tiff')
+        out = tuple(f[:k].tobytes() for f, k in zip(files, n))
+        return (out, tuple(rasters)) if want_rasters else out
 
     # ---- min-cut splitter -------------------------------------------------------------------------------
     MIN_CUT_MAX_DIST = 32          # ECSEG_MIN_CUT_MAX_DIST

@@ -5,6 +5,7 @@
 
 #include "../../include/ecseg_hip.h"
 #include "scratch.h"
+#include "tiff_frame.h"
 
 namespace ecseg {
 
@@ -331,6 +332,32 @@ inline FishRenderBufs fish_render_bufs(Carver& c, int H, int W, int C) {
 // The three colour files of stat_fish (:110-115,295-300) from b.img, b.thr and b.bnd into b.orig, b.seg and b.lsq, RGB.  C: 3 or
 // 4; ch: the image's blue, green, red and (C = 4) aqua channel, each inside 0 .. C - 1.
 hipError_t run_fish_render(int H, int W, int C, const int ch[4], const FishRenderBufs& b, hipStream_t s);
+
+// ---- launcher implemented in tiff_kernels.hip (the LZW strips of tiff_write_u8, host_io.cpp) -----------------------------------
+// Device buffers of one encode of n_files H x W rasters of spp samples (one extent, so one strip plan: strips of rps rows,
+// nstrips per file).  img: the upload of ecseg_tiff_encode (zero bytes when the rasters are on the device already); slots: per
+// (file, strip) slot_stride bytes = the host's bound 2 * strip bytes + 64, rounded up to 16; cnt: the encoded length of every
+// strip; off: per file nstrips + 1 offsets of the packed strips, counted from the first strip, the last one their total; packed:
+// per file file_stride bytes, room for every strip at its bound.
+struct TiffEncodeBufs { uint8_t* img; uint8_t* slots; uint32_t* cnt; unsigned long long* off; uint8_t* packed;
+                        size_t slot_stride, file_stride; int rps, nstrips; };
+inline TiffEncodeBufs tiff_encode_bufs(Carver& c, int H, int W, int spp, int n_files, bool upload) {
+    const size_t line = (size_t)W * spp;
+    TiffEncodeBufs b;
+    b.rps = tiff_rows_per_strip(H, W, spp);
+    b.nstrips = (H + b.rps - 1) / b.rps;
+    b.slot_stride = (tiff_strip_bound((size_t)b.rps * line) + 15) / 16 * 16;
+    b.file_stride = (size_t)b.nstrips * b.slot_stride;
+    const size_t nf = (size_t)n_files;
+    b.img = c.take<uint8_t>(upload ? (size_t)H * line * nf : 0); b.slots = c.take<uint8_t>(nf * b.file_stride);
+    b.cnt = c.take<uint32_t>(nf * b.nstrips); b.off = c.take<unsigned long long>(nf * ((size_t)b.nstrips + 1));
+    b.packed = c.take<uint8_t>(nf * b.file_stride);
+    return b;
+}
+// Encodes n_files (1..3) rasters that lie on the device: the strips (horizontal predictor, `invert`, LZW) into b.slots and b.cnt,
+// the scan into b.off, the gather into b.packed.  nstrips must be below 2^26.
+struct TiffSources { const uint8_t* img[3]; };
+hipError_t run_tiff_encode(const TiffSources& src, int n_files, int H, int W, int spp, int invert, const TiffEncodeBufs& b, hipStream_t s);
 
 // ---- launcher implemented in mincut_kernels.hip (src/max_flow_binary_mask.py:59-116) -----------------------------------------
 // n_tasks tasks of ecseg_min_cut, one workgroup each.  desc: (n_tasks, 8) int32 as the entry point takes them, validated by the

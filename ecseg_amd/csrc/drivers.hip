@@ -1,5 +1,7 @@
 // The one-call drivers: each uploads its inputs, runs one family of kernels on the main stream and downloads the results
-// (u16_to_u8, stitch_argmax, meta_inference, the counts, overlay, the interSeg regions / crops, the FISH distances, the FISH spots and their three colour files, the min-cut tasks, NuSeT's mask and proposals, its marker watershed for one image and for a batch, clean-up and rescale).
+// (u16_to_u8, stitch_argmax, meta_inference, the counts, overlay, the interSeg regions / crops, the FISH distances, the FISH spots and their three colour files, TIFF files encoded on the device, the min-cut tasks, NuSeT's mask and proposals, its marker watershed for one image and for a batch, clean-up and rescale).
+#include <cstring>
+
 #include "ctx.h"
 
 using namespace ecseg;
@@ -370,25 +372,32 @@ int ecseg_fish_spots(ecseg_ctx* h, const int32_t* labels, int H, int W, const ui
 }
 
 // ---- stat_fish's three colour files (src/stat_fish.py:110-115,295-300) ------------------------------------------------------------
-int ecseg_fish_render(ecseg_ctx* h, const uint8_t* img, int H, int W, int C, const int32_t* channels, const uint8_t* thresholded,
-                      int n_probe, const uint8_t* boundaries, uint8_t* original, uint8_t* with_segmentation, uint8_t* lsq) {
-    if (!h) return ECSEG_E_INVALID;
-    drop_sent_ahead(h);
-    if (!img || !channels || !thresholded || !boundaries || !original || !with_segmentation || !lsq || H <= 0 || W <= 0)
-        return fail(h, ECSEG_E_INVALID, "fish_render: bad arguments");
+// the argument rules the two entry points share; ch: the validated channel indices
+static int fish_render_check(ecseg_ctx* h, const uint8_t* img, int H, int W, int C, const int32_t* channels, const uint8_t* thresholded,
+                             int n_probe, const uint8_t* boundaries, int ch[4]) {
+    if (!img || !channels || !thresholded || !boundaries || H <= 0 || W <= 0) return fail(h, ECSEG_E_INVALID, "fish_render: bad arguments");
     if (C < 3 || C > 4) return fail(h, ECSEG_E_INVALID, "fish_render: the image must have 3 or 4 channels, not " + std::to_string(C));
     if (n_probe != C - 1)
         return fail(h, ECSEG_E_INVALID, "fish_render: n_probe must be C - 1 = " + std::to_string(C - 1) + " (one mask per FISH channel)");
-    int ch[4] = {0, 0, 0, 0};
+    for (int j = 0; j < 4; ++j) ch[j] = 0;
     for (int j = 0; j < C; ++j) {
         ch[j] = channels[j];
         if (ch[j] < 0 || ch[j] >= C)
             return fail(h, ECSEG_E_INVALID, "fish_render: channel index out of range (the image has " + std::to_string(C) + " channels)");
     }
     if ((long long)H * W >= (1ll << 31)) return fail(h, ECSEG_E_INVALID, "fish_render: image too large (H * W must be below 2^31)");
+    return ECSEG_OK;
+}
+
+int ecseg_fish_render(ecseg_ctx* h, const uint8_t* img, int H, int W, int C, const int32_t* channels, const uint8_t* thresholded,
+                      int n_probe, const uint8_t* boundaries, uint8_t* original, uint8_t* with_segmentation, uint8_t* lsq) {
+    if (!h) return ECSEG_E_INVALID;
+    drop_sent_ahead(h);
+    if (!original || !with_segmentation || !lsq) return fail(h, ECSEG_E_INVALID, "fish_render: bad arguments");
+    int ch[4], rc;
+    if ((rc = fish_render_check(h, img, H, W, C, channels, thresholded, n_probe, boundaries, ch))) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
     const size_t px = (size_t)H * W;
-    int rc;
     FishRenderBufs b{};
     if ((rc = lay_out(h, h->call_arena, [&](Carver& c) { b = fish_render_bufs(c, H, W, C); }))) return rc;
     hipStream_t s = h->stream;
@@ -403,6 +412,108 @@ int ecseg_fish_render(ecseg_ctx* h, const uint8_t* img, int H, int W, int C, con
     HIP_TRY(h, hipMemcpyAsync(with_segmentation, b.seg, px * 3, hipMemcpyDeviceToHost, s));
     HIP_TRY(h, hipMemcpyAsync(lsq, b.lsq, px * 3, hipMemcpyDeviceToHost, s));
     HIP_TRY(h, hipStreamSynchronize(s));
+    h->stage_ms[ECSEG_T_COUNT] = stage_elapsed(h->ev[0], h->ev[1]);
+    return ECSEG_OK;
+}
+
+// ---- TIFF files encoded on the device (tiff_kernels.hip; the host writer is tiff_write_u8, host_io.cpp) -----------------------------
+static bool tiff_args_ok(int H, int W, int spp) {            // what tiff_write_u8 accepts
+    return H > 0 && W > 0 && (spp == 1 || spp == 3) && (long long)W * spp < (1ll << 30);
+}
+
+long long ecseg_tiff_encode_bound(int H, int W, int spp) {
+    if (!tiff_args_ok(H, W, spp)) return -1;
+    const int rps = tiff_rows_per_strip(H, W, spp), nstrips = (H + rps - 1) / rps;
+    return (long long)(8 + (size_t)nstrips * (tiff_strip_bound((size_t)rps * W * spp) + 1) + tiff_tail_bound(nstrips, spp));
+}
+
+// The strips of n_files rasters are encoded and packed (run_tiff_encode is on the stream): brings the tables over, puts head and
+// tail around every file's strips and copies the strips into the caller's buffers.  Nothing is written when any file does not fit.
+static int tiff_collect(ecseg_ctx* h, const char* who, int n_files, int H, int W, int spp, const TiffEncodeBufs& b, uint8_t* const* files,
+                        long long file_cap, long long* file_bytes) {
+    hipStream_t s = h->stream;
+    const size_t ns = (size_t)b.nstrips;
+    std::vector<uint32_t> cnt(ns * n_files);
+    std::vector<unsigned long long> off((ns + 1) * n_files);
+    HIP_TRY(h, hipMemcpyAsync(cnt.data(), b.cnt, cnt.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipMemcpyAsync(off.data(), b.off, off.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    std::vector<uint8_t> head[3], tail[3];
+    std::vector<uint32_t> offs(ns);
+    for (int f = 0; f < n_files; ++f) {
+        const unsigned long long* o = off.data() + (ns + 1) * f;
+        const uint32_t* m = cnt.data() + ns * f;
+        for (size_t k = 0; k < ns; ++k) {
+            if (8 + o[k] + m[k] + 1 >= 0xffffffffull) return fail(h, ECSEG_E_INVALID, std::string(who) + ": the file would pass 4 GiB (classic TIFF has 32-bit offsets)");
+            offs[k] = (uint32_t)(8 + o[k]);
+        }
+        tiff_frame(H, W, spp, b.rps, offs.data(), m, b.nstrips, (size_t)(8 + o[ns]), &head[f], &tail[f]);
+        const unsigned long long total = 8 + o[ns] + tail[f].size();
+        if (total > (unsigned long long)file_cap)
+            return fail(h, ECSEG_E_INVALID, std::string(who) + ": a file of " + std::to_string(total) + " bytes does not fit the capacity of " +
+                                                std::to_string(file_cap) + " (ecseg_tiff_encode_bound says what always does)");
+        file_bytes[f] = (long long)total;
+    }
+    for (int f = 0; f < n_files; ++f) {
+        const size_t data = (size_t)off[(ns + 1) * f + ns];
+        std::memcpy(files[f], head[f].data(), 8);
+        HIP_TRY(h, hipMemcpyAsync(files[f] + 8, b.packed + b.file_stride * f, data, hipMemcpyDeviceToHost, s));
+        std::memcpy(files[f] + 8 + data, tail[f].data(), tail[f].size());
+    }
+    HIP_TRY(h, hipStreamSynchronize(s));
+    return ECSEG_OK;
+}
+
+int ecseg_tiff_encode(ecseg_ctx* h, const uint8_t* img, int H, int W, int spp, int invert, uint8_t* out, long long out_cap, long long* out_bytes) {
+    if (!h) return ECSEG_E_INVALID;
+    drop_sent_ahead(h);
+    if (!img || !out || !out_bytes || out_cap < 0 || !tiff_args_ok(H, W, spp)) return fail(h, ECSEG_E_INVALID, "tiff_encode: bad arguments");
+    *out_bytes = 0;
+    const int rps = tiff_rows_per_strip(H, W, spp);
+    if ((H + rps - 1) / rps >= (1 << 26)) return fail(h, ECSEG_E_INVALID, "tiff_encode: 2^26 strips or more (such a file would pass 4 GiB)");
+    HIP_TRY(h, hipSetDevice(h->device));
+    int rc;
+    TiffEncodeBufs b{};
+    if ((rc = lay_out(h, h->call_arena, [&](Carver& c) { b = tiff_encode_bufs(c, H, W, spp, 1, true); }))) return rc;
+    hipStream_t s = h->stream;
+    for (float& v : h->stage_ms) v = 0.f;
+    HIP_TRY(h, hipMemcpyAsync(b.img, img, (size_t)H * W * spp, hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipEventRecord(h->ev[0], s));
+    HIP_TRY(h, run_tiff_encode(TiffSources{{b.img, nullptr, nullptr}}, 1, H, W, spp, invert, b, s));
+    HIP_TRY(h, hipEventRecord(h->ev[1], s));
+    if ((rc = tiff_collect(h, "tiff_encode", 1, H, W, spp, b, &out, out_cap, out_bytes))) return rc;
+    h->stage_ms[ECSEG_T_COUNT] = stage_elapsed(h->ev[0], h->ev[1]);
+    return ECSEG_OK;
+}
+
+int ecseg_fish_render_tiff(ecseg_ctx* h, const uint8_t* img, int H, int W, int C, const int32_t* channels, const uint8_t* thresholded,
+                           int n_probe, const uint8_t* boundaries, uint8_t* const* files, long long file_cap, long long* file_bytes,
+                           uint8_t* original, uint8_t* with_segmentation, uint8_t* lsq) {
+    if (!h) return ECSEG_E_INVALID;
+    drop_sent_ahead(h);
+    if (!files || !files[0] || !files[1] || !files[2] || !file_bytes || file_cap < 0) return fail(h, ECSEG_E_INVALID, "fish_render_tiff: bad arguments");
+    int ch[4], rc;
+    if ((rc = fish_render_check(h, img, H, W, C, channels, thresholded, n_probe, boundaries, ch))) return rc;
+    if (!tiff_args_ok(H, W, 3)) return fail(h, ECSEG_E_INVALID, "fish_render_tiff: the TIFF writer takes lines below 2^30 bytes");
+    file_bytes[0] = file_bytes[1] = file_bytes[2] = 0;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t px = (size_t)H * W;
+    FishRenderBufs b{};
+    TiffEncodeBufs t{};
+    if ((rc = lay_out(h, h->call_arena, [&](Carver& c) { b = fish_render_bufs(c, H, W, C); t = tiff_encode_bufs(c, H, W, 3, 3, false); }))) return rc;
+    hipStream_t s = h->stream;
+    for (float& v : h->stage_ms) v = 0.f;
+    HIP_TRY(h, hipMemcpyAsync(b.img, img, px * C, hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(b.thr, thresholded, px * n_probe, hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(b.bnd, boundaries, px, hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipEventRecord(h->ev[0], s));
+    HIP_TRY(h, run_fish_render(H, W, C, ch, b, s));
+    HIP_TRY(h, run_tiff_encode(TiffSources{{b.orig, b.seg, b.lsq}}, 3, H, W, 3, 0, t, s));
+    HIP_TRY(h, hipEventRecord(h->ev[1], s));
+    if (original) HIP_TRY(h, hipMemcpyAsync(original, b.orig, px * 3, hipMemcpyDeviceToHost, s));
+    if (with_segmentation) HIP_TRY(h, hipMemcpyAsync(with_segmentation, b.seg, px * 3, hipMemcpyDeviceToHost, s));
+    if (lsq) HIP_TRY(h, hipMemcpyAsync(lsq, b.lsq, px * 3, hipMemcpyDeviceToHost, s));
+    if ((rc = tiff_collect(h, "fish_render_tiff", 3, H, W, 3, t, files, file_cap, file_bytes))) return rc;
     h->stage_ms[ECSEG_T_COUNT] = stage_elapsed(h->ev[0], h->ev[1]);
     return ECSEG_OK;
 }

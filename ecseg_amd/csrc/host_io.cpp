@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "../../include/ecseg_hip.h"
+#include "tiff_frame.h"
 
 namespace {
 
@@ -600,6 +601,38 @@ static int npy_write_as_i64(const char* path, const T* labels, int H, int W) {
     return out.close() ? ECSEG_OK : ECSEG_E_IO;
 }
 
+// The file around its strips (tiff_frame.h): the tags OpenCV 4.6 writes, in its order.
+void ecseg::tiff_frame(int H, int W, int spp, int rps, const uint32_t* offs, const uint32_t* cnts, int nstrips, size_t data_end,
+                       std::vector<uint8_t>* head_out, std::vector<uint8_t>* tail) {
+    std::vector<uint8_t> extra;
+    const size_t extra_off = data_end;
+    uint32_t so = offs[0], sc = cnts[0], bps = 8;
+    if (nstrips > 1) {
+        so = (uint32_t)(extra_off + extra.size()); for (int s = 0; s < nstrips; ++s) put_le32(extra, offs[s]);
+        sc = (uint32_t)(extra_off + extra.size()); for (int s = 0; s < nstrips; ++s) put_le32(extra, cnts[s]);
+    }
+    if (spp > 2) {                                           // more than two SHORTs do not fit the entry's value field
+        bps = (uint32_t)(extra_off + extra.size());
+        for (int c = 0; c < spp; ++c) put_le16(extra, 8);
+    }
+    size_t ifd_off = extra_off + extra.size();
+    const bool pad = ifd_off & 1;
+    ifd_off += pad;
+    std::vector<uint8_t> ifd;
+    auto entry = [&](uint32_t tag, uint32_t typ, uint32_t count, uint32_t value) { put_le16(ifd, tag); put_le16(ifd, typ); put_le32(ifd, count); put_le32(ifd, value); };
+    put_le16(ifd, 12);
+    entry(256, 4, 1, (uint32_t)W); entry(257, 4, 1, (uint32_t)H); entry(258, 3, (uint32_t)spp, bps); entry(259, 3, 1, 5);
+    entry(262, 3, 1, spp == 1 ? 1 : 2); entry(273, 4, (uint32_t)nstrips, so); entry(277, 3, 1, (uint32_t)spp); entry(278, 4, 1, (uint32_t)rps);
+    entry(279, 4, (uint32_t)nstrips, sc); entry(284, 3, 1, 1); entry(317, 3, 1, 2); entry(339, 3, 1, 1);
+    put_le32(ifd, 0);
+    std::vector<uint8_t> head = {'I', 'I'};
+    put_le16(head, 42); put_le32(head, (uint32_t)ifd_off);
+    *head_out = head;
+    *tail = extra;
+    if (pad) tail->push_back(0);
+    tail->insert(tail->end(), ifd.begin(), ifd.end());
+}
+
 extern "C" {
 
 int ecseg_npy_write_i64(const char* path, const uint8_t* labels, int H, int W) { return npy_write_as_i64(path, labels, H, W); }
@@ -691,9 +724,9 @@ int ecseg_npy_read_labels_u8(const char* path, uint8_t* dst, int H, int W) {
 static int tiff_write_u8(const char* path, const uint8_t* img, int H, int W, int spp, int invert) {
     if (!path || !img || H <= 0 || W <= 0 || (long long)W * spp >= (1ll << 30)) return ECSEG_E_INVALID;
     const size_t line = (size_t)W * spp;
-    int rps = (int)(8192 / line); if (rps < 1) rps = 1; if (rps > H) rps = H;
+    const int rps = ecseg::tiff_rows_per_strip(H, W, spp);
     const int nstrips = (H + rps - 1) / rps;
-    std::vector<uint8_t> diff((size_t)rps * line), enc((size_t)2 * rps * line + 64), data;
+    std::vector<uint8_t> diff((size_t)rps * line), enc(ecseg::tiff_strip_bound((size_t)rps * line)), data;
     std::vector<uint32_t> offs(nstrips), cnts(nstrips);
     data.reserve((size_t)H * line / 2 + 4096);
     const uint8_t flip = invert ? 0xff : 0;
@@ -714,34 +747,11 @@ static int tiff_write_u8(const char* path, const uint8_t* img, int H, int W, int
         if (m & 1) data.push_back(0);
         pos += (size_t)m + (m & 1);
     }
-    std::vector<uint8_t> extra;
-    const size_t extra_off = pos;
-    uint32_t so = offs[0], sc = cnts[0], bps = 8;
-    if (nstrips > 1) {
-        so = (uint32_t)(extra_off + extra.size()); for (uint32_t v : offs) put_le32(extra, v);
-        sc = (uint32_t)(extra_off + extra.size()); for (uint32_t v : cnts) put_le32(extra, v);
-    }
-    if (spp > 2) {                                           // more than two SHORTs do not fit the entry's value field
-        bps = (uint32_t)(extra_off + extra.size());
-        for (int c = 0; c < spp; ++c) put_le16(extra, 8);
-    }
-    size_t ifd_off = extra_off + extra.size();
-    const bool pad = ifd_off & 1;
-    ifd_off += pad;
-    std::vector<uint8_t> ifd;
-    auto entry = [&](uint32_t tag, uint32_t typ, uint32_t count, uint32_t value) { put_le16(ifd, tag); put_le16(ifd, typ); put_le32(ifd, count); put_le32(ifd, value); };
-    put_le16(ifd, 12);
-    entry(256, 4, 1, (uint32_t)W); entry(257, 4, 1, (uint32_t)H); entry(258, 3, (uint32_t)spp, bps); entry(259, 3, 1, 5);
-    entry(262, 3, 1, spp == 1 ? 1 : 2); entry(273, 4, (uint32_t)nstrips, so); entry(277, 3, 1, (uint32_t)spp); entry(278, 4, 1, (uint32_t)rps);
-    entry(279, 4, (uint32_t)nstrips, sc); entry(284, 3, 1, 1); entry(317, 3, 1, 2); entry(339, 3, 1, 1);
-    put_le32(ifd, 0);
-    std::vector<uint8_t> head = {'I', 'I'};
-    put_le16(head, 42); put_le32(head, (uint32_t)ifd_off);
+    std::vector<uint8_t> head, tail;
+    ecseg::tiff_frame(H, W, spp, rps, offs.data(), cnts.data(), nstrips, pos, &head, &tail);
     File out(path, "wb");
     if (!out.f) return ECSEG_E_IO;
-    const uint8_t zero = 0;
-    const bool ok = out.put(head.data(), head.size()) && out.put(data.data(), data.size()) && out.put(extra.data(), extra.size()) &&
-                    (!pad || out.put(&zero, 1)) && out.put(ifd.data(), ifd.size());
+    const bool ok = out.put(head.data(), head.size()) && out.put(data.data(), data.size()) && out.put(tail.data(), tail.size());
     return ok && out.close() ? ECSEG_OK : ECSEG_E_IO;
 }
 

@@ -306,6 +306,13 @@ def write_tiff_rgb8(path, img):
     _check_write(load_library().ecseg_tiff_write_rgb8(os.fsencode(path), img.ctypes.data_as(C.c_void_p), img.shape[0], img.shape[1]), path)
 
 
+def write_file_image(path, data):
+    """A file image built in memory (``Handle.tiff_encode``, ``Handle.fish_render_tiff``) -> the file, opened and written as the
+    native writers of this module do it."""
+    with open(path, 'wb') as f:
+        f.write(data)
+
+
 def write_png(path, img, level=6, native=True):
     """8-bit PNG: (H, W) gray, (H, W, 3) RGB or (H, W, 4) RGBA."""
     img = np.ascontiguousarray(img, np.uint8)

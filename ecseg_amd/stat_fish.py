@@ -272,12 +272,15 @@ def read_mask(path):
     return (m != 0).astype(np.uint8) * np.uint8(255)
 
 
-def process_image(path, mask_path, out_root, params, scale, handle, stats=None, use_min_cut=False, segment=None):
+def process_image(path, mask_path, out_root, params, scale, handle, stats=None, use_min_cut=False, segment=None, tiff_on_device=False):
     """One image of src/stat_fish.py:199-308 -> (CSV rows, the scale that was used); the rows of a four-channel image carry the aqua
     fields of ``csv_columns(3)``, and ``stats['probes']`` becomes 3 once such an image was seen (it may have no nucleus and no row).  The three colour files come from ``handle.fish_render`` when the handle has it, else from
     ``render``, which writes the same bytes.  ``use_min_cut`` (:221-224): the label map comes
     from the min-cut splitter, already numbered 1..n (its cells need not be connected, which ecseg_fish_spots allows).  ``segment``
-    (config key ``nuset_weights``): the mask is ``segment(blue channel)`` (:212-214) instead of the file ``mask_path``."""
+    (config key ``nuset_weights``): the mask is ``segment(blue channel)`` (:212-214) instead of the file ``mask_path``.
+    ``tiff_on_device`` (the config key of that name): every TIFF of the image is LZW-encoded on the device - the colour files by
+    ``handle.fish_render_tiff``, which renders them there too, the mask and the min-cut picture by ``handle.tiff_encode`` - and
+    reaches the disk as the file image these return; the bytes are those of the host writers."""
     import time
     from . import image_io
     t0 = time.perf_counter()
@@ -323,15 +326,23 @@ def process_image(path, mask_path, out_root, params, scale, handle, stats=None, 
     ranks = lut[labels]
     annotated_path = os.path.join(out_root, img_name)
     os.makedirs(annotated_path, exist_ok=True)
-    original, segmented, lsq = (handle.fish_render if hasattr(handle, 'fish_render') else render)(I, channels, thr, bnd)
-    image_io.write_npy_int64(os.path.join(annotated_path, img_name + '__segmentation_min_cut.npy'), ranks)
-    image_io.write_tiff_gray8(os.path.join(annotated_path, img_name + '_segmentation.tif'), mask)
-    image_io.write_tiff_rgb8(os.path.join(annotated_path, img_name + '_original_with_segmentation.tif'), segmented)
-    image_io.write_tiff_rgb8(os.path.join(annotated_path, img_name + '_original.tif'), original)
-    image_io.write_tiff_rgb8(os.path.join(annotated_path, lsq_name(img_name, params, stdev, min_cc)), lsq)
+    if tiff_on_device:                                       # three file images instead of three rasters
+        original, segmented, lsq = handle.fish_render_tiff(I, channels, thr, bnd)
+    else:
+        original, segmented, lsq = (handle.fish_render if hasattr(handle, 'fish_render') else render)(I, channels, thr, bnd)
+    tiffs = [(img_name + '_segmentation.tif', mask), (img_name + '_original_with_segmentation.tif', segmented),
+             (img_name + '_original.tif', original), (lsq_name(img_name, params, stdev, min_cc), lsq)]
     if visualization is not None:                            # (:304-305) cv2 writes its (r, g, b) array as if it were BGR: the file holds (b, g, r)
-        image_io.write_tiff_rgb8(os.path.join(annotated_path, img_name + '_segmentation_corrected_min_cut.tif'),
-                                 np.ascontiguousarray(visualization[..., ::-1]))
+        tiffs.append((img_name + '_segmentation_corrected_min_cut.tif', np.ascontiguousarray(visualization[..., ::-1])))
+    image_io.write_npy_int64(os.path.join(annotated_path, img_name + '__segmentation_min_cut.npy'), ranks)
+    for name, what in tiffs:
+        out = os.path.join(annotated_path, name)
+        if tiff_on_device:
+            image_io.write_file_image(out, what if isinstance(what, bytes) else handle.tiff_encode(what))
+        elif what.ndim == 2:
+            image_io.write_tiff_gray8(out, what)
+        else:
+            image_io.write_tiff_rgb8(out, what)
     if stats is not None:
         for key, v in (('read', t1 - t0), ('device', t2 - t1), ('write', time.perf_counter() - t2)):
             stats[key] = stats.get(key, 0.0) + v
@@ -459,7 +470,7 @@ def main(argv=None, handle=None):
     """``make stat_fish``.  Like the reference's ``main`` it takes everything from section ``stat_fish`` of ``config.yaml`` in
     the working directory; ``argv`` is accepted for the shim's sake and not read.  ``handle`` is an injection point for tests and
     tools (anything with ``Handle.ccl_labels``, ``fish_spots`` and ``u16_to_u8``, and ``min_cut`` for ``use_min_cut: True``; ``fish_render``
-    is used when it is there); without it the call opens a handle on device 0
+    is used when it is there, ``tiff_encode`` and ``fish_render_tiff`` are needed for ``tiff_on_device: true``); without it the call opens a handle on device 0
     and closes it at the end."""
     import yaml
     from . import csvio
@@ -490,6 +501,12 @@ def main(argv=None, handle=None):
         if batch > 1 and handle is not None and not hasattr(handle, 'marker_watershed_batch'):
             raise ConfigError('nuset_batch: %d needs the batched marker watershed (marker_watershed_batch), which the handle in use does not '
                               'have; only nuset_batch: 1 works on it' % batch)
+        tiff_on_device = var.get('tiff_on_device', False)
+        if not isinstance(tiff_on_device, bool):
+            raise ConfigError('tiff_on_device must be true or false (true: the LZW strips of every TIFF are encoded on the device)')
+        if tiff_on_device and handle is not None and not all(hasattr(handle, m) for m in ('tiff_encode', 'fish_render_tiff')):
+            raise ConfigError('tiff_on_device: true needs the device TIFF encoder (tiff_encode, fish_render_tiff), which the handle in use '
+                              'does not have; only tiff_on_device: false works on it')
         if segmenter is None and not os.path.isdir(masks):
             raise ConfigError('The folder of nucleus masks %s does not exist (config key masks): it holds one 8-bit <name>.tif per '
                               'image, non-zero = nucleus' % masks)
@@ -546,7 +563,7 @@ def main(argv=None, handle=None):
                 print("Processing image: ", p)
                 try:
                     img_rows, scale = process_image(p, os.path.join(masks, os.path.basename(p)[:-4] + '.tif'), out_root, params, scale, handle,
-                                                     stats=seen, use_min_cut=use_min_cut, segment=hooks.get(p))
+                                                     stats=seen, use_min_cut=use_min_cut, segment=hooks.get(p), tiff_on_device=tiff_on_device)
                     rows += img_rows
                 except ImageError as e:
                     print(p, '-', e)

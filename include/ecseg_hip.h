@@ -45,6 +45,8 @@ extern "C" {
 /* (still 5 - additive: ecseg_fish_spots, the per-nucleus records, masks and boundaries of stat_fish, and ecseg_tiff_write_rgb8; ecseg_npy_write_i32_as_i64
  * beside ecseg_npy_write_i64; nothing existing changed.) */
 /* (still 5 - additive: ecseg_fish_render, the three colour files of stat_fish for 3- and 4-channel images; nothing existing changed.) */
+/* (still 5 - additive: ecseg_tiff_encode_bound, ecseg_tiff_encode and ecseg_fish_render_tiff, stat_fish's LZW TIFF files encoded on the
+ * device; nothing existing changed.) */
 #define ECSEG_ABI_VERSION 5
 
 #define ECSEG_OK             0
@@ -376,6 +378,27 @@ int ecseg_fish_spots(ecseg_ctx* h, const int32_t* labels, int H, int W, const ui
  * outside 3..4, n_probe != C - 1, a channel index outside 0 .. C - 1, H * W >= 2^31. */
 int ecseg_fish_render(ecseg_ctx* h, const uint8_t* img, int H, int W, int C, const int32_t* channels, const uint8_t* thresholded,
                       int n_probe, const uint8_t* boundaries, uint8_t* original, uint8_t* with_segmentation, uint8_t* lsq);
+
+/* ---- TIFF files encoded on the device ---------------------------------------------------------------------------------------- */
+/* The file ecseg_tiff_write_gray8 (spp = 1) / ecseg_tiff_write_rgb8 (spp = 3) would write for img, byte for byte, as a file image in
+ * memory: the horizontal predictor, `invert` and the LZW coding of every strip run on the device, one wave per strip, the
+ * strips are packed there, and only the packed bytes and the strip tables come back (csrc/tiff_kernels.hip).  img: (H, W, spp)
+ * uint8 in host memory, uploaded by the call.  out receives *out_bytes bytes; a capacity of ecseg_tiff_encode_bound(H, W, spp)
+ * (-1 for extents the writers refuse) always suffices, and a file that does not fit out_cap is ECSEG_E_INVALID with nothing
+ * written, never a truncated file.  One synchronous call, scratch from the handle's call arena; device time of the kernels in
+ * ECSEG_T_COUNT.  ECSEG_E_INVALID where the file writers return it - a null pointer, H or W < 1, W * spp >= 2^30, a file that would
+ * pass 4 GiB - and for spp outside {1, 3}. */
+long long ecseg_tiff_encode_bound(int H, int W, int spp);
+int ecseg_tiff_encode(ecseg_ctx* h, const uint8_t* img, int H, int W, int spp, int invert, uint8_t* out, long long out_cap,
+                      long long* out_bytes);
+/* ecseg_fish_render followed by ecseg_tiff_encode of its three rasters, without their leaving the device: files[0..2] receive
+ * the file images of _original, _original_with_segmentation and _lsq_ (file_bytes[0..2] their lengths), each with room for
+ * file_cap bytes (ecseg_tiff_encode_bound(H, W, 3) always suffices; too little is ECSEG_E_INVALID with no file written).
+ * original, with_segmentation and lsq: each null, or room for the (H, W, 3) raster as ecseg_fish_render returns it.  Inputs and
+ * their rules are ecseg_fish_render's.  Device time of all kernels, render and encode, in ECSEG_T_COUNT. */
+int ecseg_fish_render_tiff(ecseg_ctx* h, const uint8_t* img, int H, int W, int C, const int32_t* channels, const uint8_t* thresholded,
+                           int n_probe, const uint8_t* boundaries, uint8_t* const* files, long long file_cap, long long* file_bytes,
+                           uint8_t* original, uint8_t* with_segmentation, uint8_t* lsq);
 
 /* ---- the min-cut nucleus splitter: a batch of grid max-flows (src/max_flow_binary_mask.py:59-116) ------------------------- */
 /* Replaces get_graph + max_flow + partition_min_cut (:59-116) for a BATCH of independent tasks; segment_min_cut's recursion

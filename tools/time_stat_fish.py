@@ -1,6 +1,7 @@
 """Timing of ``make stat_fish`` on synthetic full-size scenes.
 
     python tools/time_stat_fish.py [--images 16] [--reps 5] [--cpu-workers 16] [--channels 4] [--main-passes 3]
+                                   [--tiff-on-device off|on|alternate] [--no-cpu-baseline]
 
 Per 1040 x 1392 scene with 300 nuclei (tests/stat_fish_cases.py ``full_size_scene``) it reports
   * device milliseconds per image of ecseg_fish_spots (ECSEG_T_COUNT: the kernels alone), of the nucleus labelling in front of
@@ -8,7 +9,10 @@ Per 1040 x 1392 scene with 300 nuclei (tests/stat_fish_cases.py ``full_size_scen
   * the time to read that image's two input files (the LZW RGB image and the mask TIFF);
   * device milliseconds and wall time of ecseg_fish_render, the call that composes the three colour files;
   * the files-in / files-out rate of ``main()`` on the folder: one warm-up pass, then the median with min and max of --main-passes
-    passes;
+    passes, and the write stage of ``process_image`` per image over those passes;
+  * with ``--tiff-on-device on`` the same under the config key ``tiff_on_device: true`` (every TIFF LZW-encoded on the device), with
+    ``alternate`` key off and key on in turn, twice, each with its own warm-up pass (``main_by_key``); either way the device
+    milliseconds (render + encode for the first) and the wall time of ecseg_fish_render_tiff and of ecseg_tiff_encode of the mask;
   * the same scenes through the vectorised numpy / scipy restatement tests/stat_fish_ref.py ``records`` on one core and on a
     pool of --cpu-workers processes, as the baseline.
 With ``--channels 4`` the scenes are four-channel ``.npy`` images (blue, green, red and an aqua channel made of the green one shifted
@@ -47,6 +51,8 @@ def main():
     ap.add_argument('--cpu-workers', type=int, default=16)
     ap.add_argument('--channels', type=int, default=3, choices=(3, 4))
     ap.add_argument('--main-passes', type=int, default=3)
+    ap.add_argument('--tiff-on-device', choices=('off', 'on', 'alternate'), default='off')
+    ap.add_argument('--no-cpu-baseline', action='store_true')
     a = ap.parse_args()
     import yaml
     import stat_fish_cases as cases
@@ -70,6 +76,8 @@ def main():
             image_io.write_tiff_gray8(os.path.join(inp, 'nuclei_masks', 'img%03d.tif' % k), mask)
         w = stat_fish.gaussian_proj_kernel([7, 7], 3.0)
         kern, label, wall, nuclei, render_kern, render_wall = [], [], [], 0, [], []
+        tiff = {k: [] for k in ('render_tiff_kernel_ms', 'render_tiff_wall_ms', 'mask_tiff_kernel_ms', 'mask_tiff_wall_ms')}
+        with_tiff = a.tiff_on_device != 'off'
         for rep in range(a.reps + 1):
             for img, mask in scenes:
                 t0 = time.perf_counter()
@@ -80,15 +88,28 @@ def main():
                 t_spots = gpu.timings()['count']
                 gpu.fish_render(img, order, thr, bnd)
                 t2 = time.perf_counter()
+                t_render = gpu.timings()['count']
+                if with_tiff:
+                    gpu.fish_render_tiff(img, order, thr, bnd)
+                    t3 = time.perf_counter()
+                    t_files = gpu.timings()['count']
+                    gpu.tiff_encode(mask)
+                    t4 = time.perf_counter()
+                    if rep:
+                        tiff['render_tiff_kernel_ms'].append(t_files); tiff['render_tiff_wall_ms'].append((t3 - t2) * 1e3)
+                        tiff['mask_tiff_kernel_ms'].append(gpu.timings()['count']); tiff['mask_tiff_wall_ms'].append((t4 - t3) * 1e3)
                 if rep:
                     kern.append(t_spots); label.append(t_label); wall.append((t1 - t0) * 1e3)
-                    render_kern.append(gpu.timings()['count']); render_wall.append((t2 - t1) * 1e3)
+                    render_kern.append(t_render); render_wall.append((t2 - t1) * 1e3)
                 else:
                     nuclei += len(rec)
         out.update(nuclei_per_image=nuclei / a.images, kernel_ms_median=statistics.median(kern), kernel_ms_min=min(kern), kernel_ms_max=max(kern),
                    labelling_ms_median=statistics.median(label), call_wall_ms_median=statistics.median(wall),
                    render_kernel_ms_median=statistics.median(render_kern), render_kernel_ms_min=min(render_kern),
                    render_kernel_ms_max=max(render_kern), render_call_wall_ms_median=statistics.median(render_wall))
+        for k, v in tiff.items():
+            if v:
+                out.update({k + '_median': statistics.median(v), k + '_min': min(v), k + '_max': max(v)})
         reads = []
         for rep in range(a.reps):
             for k in range(a.images):
@@ -97,26 +118,56 @@ def main():
                 image_io.imread(os.path.join(inp, 'nuclei_masks', 'img%03d.tif' % k))
                 reads.append((time.perf_counter() - t0) * 1e3)
         out['read_ms_median'] = statistics.median(reads)
-        cfg = {'stat_fish': {'inpath': inp, 'scale': 1, 'use_min_cut': False, 'nuclei_size_T': 5000}}
-        with open(os.path.join(tmp, 'config.yaml'), 'w') as f:
-            yaml.safe_dump(cfg, f)
         if a.channels == 4:
             os.makedirs(os.path.join(tmp, 'src'))
             with open(os.path.join(tmp, 'src', 'stat_fish_params.yaml'), 'w') as f:
                 f.write('color_sensitivity: [70, 70, 70]\n')
-        cwd = os.getcwd()
-        os.chdir(tmp)
-        try:
-            rates = []
+        seen = {}
+        process_image = stat_fish.process_image
+
+        def spy(*args, **kw):                                # main()'s stage times: it hands every image the same dict
+            r = process_image(*args, **kw)
+            seen.update(kw['stats'])
+            return r
+
+        def passes(key):
+            """One warm-up pass (arenas, page cache) and --main-passes timed ones -> images/s of each, write stage ms per image."""
+            cfg = {'stat_fish': {'inpath': inp, 'scale': 1, 'use_min_cut': False, 'nuclei_size_T': 5000}}
+            if key:
+                cfg['stat_fish']['tiff_on_device'] = True
+            with open(os.path.join(tmp, 'config.yaml'), 'w') as f:
+                yaml.safe_dump(cfg, f)
+            rates, writes = [], []
             for rep in range(a.main_passes + 1):
                 t0 = time.perf_counter()
                 stat_fish.main([], handle=gpu)
-                if rep:                                      # the first pass warms the arenas and the page cache
+                if rep:
                     rates.append(a.images / (time.perf_counter() - t0))
+                    writes.append(seen['write'] * 1e3 / a.images)
+            return rates, writes
+
+        def summary(rates, writes):
+            return dict(main_images_per_s=statistics.median(rates), main_images_per_s_min=min(rates), main_images_per_s_max=max(rates),
+                        write_stage_ms_per_image=statistics.median(writes))
+        cwd = os.getcwd()
+        os.chdir(tmp)
+        stat_fish.process_image = spy
+        try:
+            if a.tiff_on_device == 'alternate':
+                out['main_by_key'] = [dict(tiff_on_device=key, **summary(*passes(key))) for key in (False, True, False, True)]
+                offs = [r for r in out['main_by_key'] if not r['tiff_on_device']]
+                ons = [r for r in out['main_by_key'] if r['tiff_on_device']]
+                out['max_off_below_min_on'] = max(r['main_images_per_s_max'] for r in offs) < min(r['main_images_per_s_min'] for r in ons)
+                out.update(offs[0])
+            else:
+                out.update(tiff_on_device=a.tiff_on_device == 'on', **summary(*passes(a.tiff_on_device == 'on')))
         finally:
+            stat_fish.process_image = process_image
             os.chdir(cwd)
-        out.update(main_images_per_s=statistics.median(rates), main_images_per_s_min=min(rates), main_images_per_s_max=max(rates))
     gpu.close()
+    if a.no_cpu_baseline:
+        print(json.dumps(out))
+        return
     n_cpu = min(a.images, 4)
     one = [_cpu_records(100 + k) for k in range(n_cpu)]
     out['cpu_records_s_per_image_one_core'] = statistics.median(one)
