@@ -22,6 +22,7 @@ EXPORTS = [
     'ecseg_npy_write_i64', 'ecseg_png_write_labels', 'ecseg_png_write', 'ecseg_png_write_channel', 'ecseg_npy_label_info', 'ecseg_npy_read_labels_u8', 'ecseg_tiff_write_gray8', 'ecseg_tiff_info', 'ecseg_tiff_read',
     'ecseg_tiff_write_rgb8', 'ecseg_npy_write_i32_as_i64',
     'ecseg_tiff_encode_bound', 'ecseg_tiff_encode', 'ecseg_fish_render_tiff',
+    'ecseg_png_labels_encode', 'ecseg_meta_segment_files', 'ecseg_get_file_timings', 'ecseg_png_labels_stream_size',
 ]
 
 
@@ -153,6 +154,11 @@ def load_library():
     lib.ecseg_allgather_records_dev.argtypes = [vp, vp, i32, vp, vp]
     lib.ecseg_npy_write_i64.argtypes = [C.c_char_p, vp, i32, i32]
     lib.ecseg_png_write_labels.argtypes = [C.c_char_p, vp, i32, i32]
+    lib.ecseg_png_labels_stream_size.argtypes = [vp, i32, i32, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
+    lib.ecseg_png_labels_encode.argtypes = [vp, vp, i32, i32, i32, C.POINTER(vp), C.c_longlong, C.POINTER(C.c_longlong)]
+    lib.ecseg_meta_segment_files.argtypes = [vp, vp, i32, i32, i32, i32, i32, C.POINTER(vp), C.c_longlong, C.POINTER(C.c_longlong),
+                                             C.POINTER(vp), C.c_longlong, C.POINTER(C.c_longlong), vp, vp, vp, vp]
+    lib.ecseg_get_file_timings.argtypes = [vp, C.POINTER(C.c_float)]
     lib.ecseg_png_write.argtypes = [C.c_char_p, vp, i32, i32, i32, i32]
     lib.ecseg_png_write_channel.argtypes = [C.c_char_p, vp, i32, i32, i32, i32, i32]
     lib.ecseg_npy_label_info.argtypes = [C.c_char_p, C.POINTER(i32), C.POINTER(i32)]
@@ -352,6 +358,83 @@ class Handle:
         self.native_seconds += time.perf_counter() - t0    # (inside the library, GIL released: `make metaseg`'s stage report)
         self._check(rc, 'ecseg_meta_segment')
         return outs[0], outs[1], nec, tie
+
+    @staticmethod
+    def _file_slots(buf, n, cap):
+        """n slots of cap bytes in ``buf`` (a flat uint8 array, or None: a fresh one) -> the array and the table of their addresses"""
+        if buf is None:
+            buf = np.empty(n * cap, np.uint8)
+        elif buf.dtype != np.uint8 or buf.ndim != 1 or buf.size < n * cap or not buf.flags.c_contiguous:
+            raise ValueError('a file buffer must be a flat C-contiguous uint8 array of at least %d bytes' % (n * cap))
+        return buf, (C.c_void_p * max(n, 1))(*[buf.ctypes.data + i * cap for i in range(n)])
+
+    @staticmethod
+    def _files_of(buf, sizes, cap, copy):
+        """per slot the file (``bytes``, or with copy = False a view of the slot) or None for a file that did not fit"""
+        out = []
+        for i, k in enumerate(sizes):
+            out.append(None if k <= 0 else buf[i * cap:i * cap + k].tobytes() if copy else buf[i * cap:i * cap + k])
+        return out
+
+    def png_labels_encode(self, labels, capacity=None):
+        """(n, H, W) or (H, W) uint8 labels -> per image the bytes of the file ``image_io.write_label_png`` writes, run-length and
+        Huffman coded on the device (ecseg_png_labels_encode); a list for a batch.  ``capacity``: bytes of each file's buffer, by
+        default more than any label image needs; a file that does not fit is None, and ``last_file_bytes`` holds minus the size
+        it needs (the lengths of the others)."""
+        lab = np.ascontiguousarray(labels, np.uint8)
+        single = lab.ndim == 2
+        if single:
+            lab = lab[None]
+        if lab.ndim != 3 or lab.size == 0:
+            raise ValueError('png_labels_encode takes non-empty (n, H, W) or (H, W) uint8 labels')
+        n, H, W = lab.shape
+        cap = 11 * H * W + 2 * H + 4096 if capacity is None else int(capacity)      # (a run costs at most 81 bits, a scan line 15 more)
+        buf, ptrs = self._file_slots(None, n, max(cap, 1))
+        sizes = (C.c_longlong * n)()
+        self._check(self.lib.ecseg_png_labels_encode(self.h, _ptr(lab), n, H, W, ptrs, cap, sizes), 'ecseg_png_labels_encode')
+        self.last_file_bytes = list(sizes)
+        files = self._files_of(buf, self.last_file_bytes, max(cap, 1), True)
+        return files[0] if single else files
+
+    def meta_segment_files(self, imgs, gray_out=None, post_out=None, dapi_capacity=None, png_capacity=None, file_bufs=None):
+        """``meta_segment`` plus, per image, the file images of ``dapi/<name>.tif`` (``write_tiff_gray8(gray, invert=True)``) and
+        of ``labels/<stem>.png`` (``write_label_png(post)``), encoded on the device (ecseg_meta_segment_files) ->
+        (gray, post, n_ec, tie_risk, dapi_files, png_files).  A file is ``bytes``, or None when it did not fit its capacity
+        (defaults: H * W + 65536 and H * W // 2 + 65536 bytes; the caller then writes it from gray / post).  ``file_bufs``: two
+        flat uint8 arrays of n * capacity bytes (e.g. page-locked ones) to build the files in; the files are then views of them."""
+        a = np.ascontiguousarray(imgs)
+        if a.dtype not in (np.uint8, np.uint16):
+            raise TypeError('meta_preprocess takes uint8 or uint16 images, got %s' % a.dtype)
+        if a.ndim == 3:
+            a = a[..., None]
+        n, H, W, Cc = a.shape
+        outs = []
+        for o in (gray_out, post_out):
+            if o is None:
+                o = np.empty((n, H, W), np.uint8)
+            elif o.shape != (n, H, W) or o.dtype != np.uint8 or not o.flags.c_contiguous:
+                raise ValueError('output buffers must be C-contiguous uint8 arrays of shape %s' % ((n, H, W),))
+            outs.append(o)
+        dcap = H * W + 65536 if dapi_capacity is None else int(dapi_capacity)
+        pcap = H * W // 2 + 65536 if png_capacity is None else int(png_capacity)
+        dbuf, dptr = self._file_slots(file_bufs[0] if file_bufs else None, n, max(dcap, 1))
+        pbuf, pptr = self._file_slots(file_bufs[1] if file_bufs else None, n, max(pcap, 1))
+        dn, pn = (C.c_longlong * max(n, 1))(), (C.c_longlong * max(n, 1))()
+        nec = np.zeros(n, np.int32); tie = np.zeros(n, np.int32)
+        t0 = time.perf_counter()
+        rc = self.lib.ecseg_meta_segment_files(self.h, _ptr(a), n, H, W, Cc, a.dtype.itemsize, dptr, dcap, dn, pptr, pcap, pn,
+                                               _ptr(outs[0]), _ptr(outs[1]), _ptr(nec), _ptr(tie))
+        self.native_seconds += time.perf_counter() - t0
+        self._check(rc, 'ecseg_meta_segment_files')
+        self.last_file_bytes = list(dn)[:n] + list(pn)[:n]
+        copy = not file_bufs
+        return (outs[0], outs[1], nec, tie, self._files_of(dbuf, list(dn)[:n], max(dcap, 1), copy), self._files_of(pbuf, list(pn)[:n], max(pcap, 1), copy))
+
+    def file_timings(self):
+        """Device milliseconds of the last ``meta_segment_files`` call's dapi encode and PNG kernels."""
+        ms = (C.c_float * 2)()
+        self._check(self.lib.ecseg_get_file_timings(self.h, ms), 'ecseg_get_file_timings')
+        return {'dapi': float(ms[0]), 'png': float(ms[1])}
 
     def prefetch_input(self, imgs):
         """Name the raw images (a C-contiguous array in page-locked memory) of the meta_segment call AFTER the coming one: the

@@ -354,10 +354,46 @@ inline TiffEncodeBufs tiff_encode_bufs(Carver& c, int H, int W, int spp, int n_f
     b.packed = c.take<uint8_t>(nf * b.file_stride);
     return b;
 }
-// Encodes n_files (1..3) rasters that lie on the device: the strips (horizontal predictor, `invert`, LZW) into b.slots and b.cnt,
-// the scan into b.off, the gather into b.packed.  nstrips must be below 2^26.
-struct TiffSources { const uint8_t* img[3]; };
+// Encodes n_files rasters that lie on the device: the strips (horizontal predictor, `invert`, LZW) into b.slots and b.cnt, the
+// scan into b.off, the gather into b.packed.  nstrips must be below 2^26.  The rasters: stride == 0: img[0 .. n_files - 1], at
+// most three of them; stride > 0: a batch, raster f at img[0] + f * stride (n_files below 65536: grid dimension y is the file).
+struct TiffSources { const uint8_t* img[3]; size_t stride; };
 hipError_t run_tiff_encode(const TiffSources& src, int n_files, int H, int W, int spp, int invert, const TiffEncodeBufs& b, hipStream_t s);
+
+// ---- launchers implemented in png_kernels.hip (the label PNG of ecseg_png_write_labels, host_io.cpp) ------------------------------
+// The token counts of one image, as deflate_labels' pass 1 takes them: [0..3] runs per colour, [4 + m] matches of 4 m bytes for
+// m = 1..64 (m = 64 with the whole-64 parts of long runs; m = 0 counts the runs without a remainder match and is not used).
+constexpr int PNG_NCOUNT = 4 + 65;
+// One image's code on the device (LabelPngCode, png_label_code.h, in dwords): cbits / cn per colour, mbits / mn per match of 4 m
+// bytes, head the first head_bits bits of the stream as little-endian dwords (1540 at most), the codes of the filter byte and
+// of the end of the block; z_off / z_words: where in the stream buffer the image's stream lies (in dwords) and the dwords it owns.
+struct PngDevCode {
+    unsigned long long cbits[4];
+    unsigned long long z_off;
+    uint32_t cn[4], mbits[65], mn[65], head[64];
+    uint32_t head_bits, filt, filt_n, eob, eob_n, z_words;
+};
+static_assert(sizeof(PngDevCode) % 8 == 0, "copied to LDS dword by dword, laid out as an array");
+// Device buffers of one encode of n H x W label images: labels (the upload of ecseg_png_labels_encode; zero bytes when the labels
+// are on the device already), the counts, per scan line its Adler terms, its bits and its bit offset in the stream, per image its
+// code and the stream's length as the device found it.
+struct PngEncodeBufs { uint8_t* labels; uint32_t* counts; uint32_t* row_a; uint32_t* row_b; unsigned long long* row_bits;
+                       unsigned long long* row_off; PngDevCode* codes; unsigned long long* z_bytes; };
+inline PngEncodeBufs png_encode_bufs(Carver& c, int H, int W, int n, bool upload) {
+    const size_t rows = (size_t)n * H;
+    PngEncodeBufs b;
+    b.labels = c.take<uint8_t>(upload ? rows * W : 0); b.counts = c.take<uint32_t>((size_t)n * PNG_NCOUNT);
+    b.row_a = c.take<uint32_t>(rows); b.row_b = c.take<uint32_t>(rows);
+    b.row_bits = c.take<unsigned long long>(rows); b.row_off = c.take<unsigned long long>(rows);
+    b.codes = c.take<PngDevCode>((size_t)n); b.z_bytes = c.take<unsigned long long>((size_t)n);
+    return b;
+}
+// labels: n images of H x W, image i at labels + i * img_stride, on the device.  run_png_count clears and fills b.counts, b.row_a
+// and b.row_b; run_png_emit, with b.codes in place, clears z (z_bytes bytes, a multiple of 4) and writes every stream and b.z_bytes.
+// n below 65536 (grid dimension y is the image), W below 2^30.
+hipError_t run_png_count(const uint8_t* labels, size_t img_stride, int n, int H, int W, const PngEncodeBufs& b, hipStream_t s);
+hipError_t run_png_emit(const uint8_t* labels, size_t img_stride, int n, int H, int W, const PngEncodeBufs& b, uint32_t* z, size_t z_bytes,
+                        hipStream_t s);
 
 // ---- launcher implemented in mincut_kernels.hip (src/max_flow_binary_mask.py:59-116) -----------------------------------------
 // n_tasks tasks of ecseg_min_cut, one workgroup each.  desc: (n_tasks, 8) int32 as the entry point takes them, validated by the

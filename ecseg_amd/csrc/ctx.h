@@ -171,6 +171,8 @@ struct ecseg_ctx : ecseg::DevMem {
     // timing
     hipEvent_t ev[ECSEG_T_N + 1] = {};
     float stage_ms[ECSEG_T_N] = {};
+    hipEvent_t ev_files[6] = {};     // the device file coders: [0, 1] the batched dapi strips, [2, 3] the PNG count, [4, 5] the PNG emit
+    float file_ms[2] = {};           // device time of the last ecseg_meta_segment_files call's dapi encode and PNG kernels
     bool profile_kernels = false;
     std::vector<hipEvent_t> prof_events;   // pairs
     std::vector<hipEvent_t> grp_events;    // 6 per image group of segment_dev
@@ -218,6 +220,16 @@ inline void drop_sent_ahead(ecseg_ctx* h) {
 
 // api.hip
 int check_model(ecseg_ctx* h);
+
+// drivers.hip: the file coders' tails, shared with ecseg_meta_segment_files (segment.hip).  Both bring the tables over, wait, and
+// copy every file that fits file_cap into files[i] (file_bytes[i]: its length); a file that does not fit is not produced.
+// tiff_collect, strict: that is an error and nothing is written; else file_bytes[i] = -(the bytes it needs) and the call goes on.
+int tiff_collect(ecseg_ctx* h, const char* who, int n_files, int H, int W, int spp, const TiffEncodeBufs& b, uint8_t* const* files,
+                 long long file_cap, long long* file_bytes, bool strict);
+// The label PNGs of n images that lie on the device (image i at d_labels + i * H * W), on the main stream: count, code build on the
+// host, emit into count_arena, frame.  *ms: device time of the kernels.
+int png_encode_files(ecseg_ctx* h, const char* who, const uint8_t* d_labels, int n, int H, int W, const PngEncodeBufs& b,
+                     uint8_t* const* files, long long file_cap, long long* file_bytes, float* ms);
 
 // filter_layout.hip: host arrays to host arrays
 std::vector<float> relayout_conv(const float* w, int R, int S, int cin, int cout, int chunks, int np);

@@ -4,7 +4,102 @@
 
 #include "ctx.h"
 
+#include "png_label_code.h"
+
 using namespace ecseg;
+
+// The strips of n_files rasters are encoded and packed (run_tiff_encode is done or on a stream that the main stream's end waits
+// for): brings the tables over, puts head and tail around every file's strips and copies the strips into the caller's buffers.
+int ecseg::tiff_collect(ecseg_ctx* h, const char* who, int n_files, int H, int W, int spp, const TiffEncodeBufs& b, uint8_t* const* files,
+                        long long file_cap, long long* file_bytes, bool strict) {
+    hipStream_t s = h->stream;
+    const size_t ns = (size_t)b.nstrips;
+    std::vector<uint32_t> cnt(ns * n_files);
+    std::vector<unsigned long long> off((ns + 1) * n_files);
+    HIP_TRY(h, hipMemcpyAsync(cnt.data(), b.cnt, cnt.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipMemcpyAsync(off.data(), b.off, off.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    std::vector<std::vector<uint8_t>> head(n_files), tail(n_files);
+    std::vector<uint32_t> offs(ns);
+    for (int f = 0; f < n_files; ++f) {
+        const unsigned long long* o = off.data() + (ns + 1) * f;
+        const uint32_t* m = cnt.data() + ns * f;
+        for (size_t k = 0; k < ns; ++k) {
+            if (8 + o[k] + m[k] + 1 >= 0xffffffffull) return fail(h, ECSEG_E_INVALID, std::string(who) + ": the file would pass 4 GiB (classic TIFF has 32-bit offsets)");
+            offs[k] = (uint32_t)(8 + o[k]);
+        }
+        tiff_frame(H, W, spp, b.rps, offs.data(), m, b.nstrips, (size_t)(8 + o[ns]), &head[f], &tail[f]);
+        const unsigned long long total = 8 + o[ns] + tail[f].size();
+        if (total > (unsigned long long)file_cap && strict)
+            return fail(h, ECSEG_E_INVALID, std::string(who) + ": a file of " + std::to_string(total) + " bytes does not fit the capacity of " +
+                                                std::to_string(file_cap) + " (ecseg_tiff_encode_bound says what always does)");
+        file_bytes[f] = total > (unsigned long long)file_cap ? -(long long)total : (long long)total;
+    }
+    for (int f = 0; f < n_files; ++f) {
+        if (file_bytes[f] < 0) continue;
+        const size_t data = (size_t)off[(ns + 1) * f + ns];
+        std::memcpy(files[f], head[f].data(), 8);
+        HIP_TRY(h, hipMemcpyAsync(files[f] + 8, b.packed + b.file_stride * f, data, hipMemcpyDeviceToHost, s));
+        std::memcpy(files[f] + 8 + data, tail[f].data(), tail[f].size());
+    }
+    HIP_TRY(h, hipStreamSynchronize(s));
+    return ECSEG_OK;
+}
+
+int ecseg::png_encode_files(ecseg_ctx* h, const char* who, const uint8_t* d_labels, int n, int H, int W, const PngEncodeBufs& b,
+                            uint8_t* const* files, long long file_cap, long long* file_bytes, float* ms) {
+    hipStream_t s = h->stream;
+    const size_t px = (size_t)H * W;
+    HIP_TRY(h, hipEventRecord(h->ev_files[2], s));
+    HIP_TRY(h, run_png_count(d_labels, px, n, H, W, b, s));
+    HIP_TRY(h, hipEventRecord(h->ev_files[3], s));
+    std::vector<uint32_t> counts((size_t)n * PNG_NCOUNT);
+    HIP_TRY(h, hipMemcpyAsync(counts.data(), b.counts, counts.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    // the code of every image and with it the exact size of its stream: the stream buffer holds just that, in whole dwords
+    std::vector<PngDevCode> codes((size_t)n);
+    std::vector<size_t> zb((size_t)n);
+    size_t words = 0;
+    for (int i = 0; i < n; ++i) {
+        const uint32_t* c = counts.data() + (size_t)i * PNG_NCOUNT;
+        LabelPngCode k;
+        label_png_code(c, c + 4, (uint32_t)H, LABEL_PNG_PALETTE, &k);
+        zb[i] = label_png_stream_bytes(k, c, c + 4, (uint32_t)H);
+        if (zb[i] >= 0x7fffffffull) return fail(h, ECSEG_E_INVALID, std::string(who) + ": a stream of 2 GiB or more does not fit a PNG chunk");
+        PngDevCode& d = codes[i];
+        std::memset(&d, 0, sizeof d);
+        for (int q = 0; q < 4; ++q) { d.cbits[q] = k.cbits[q]; d.cn[q] = (uint32_t)k.cn[q]; }
+        for (int m = 0; m <= 64; ++m) { d.mbits[m] = k.mbits[m]; d.mn[m] = (uint32_t)k.mn[m]; }
+        std::memcpy(d.head, k.head, sizeof d.head);
+        d.head_bits = k.head_bits; d.filt = k.filt; d.filt_n = (uint32_t)k.filt_n; d.eob = k.eob; d.eob_n = (uint32_t)k.eob_n;
+        d.z_off = words; d.z_words = (uint32_t)((zb[i] + 3) / 4);
+        words += d.z_words;
+    }
+    int rc;
+    if ((rc = h->count_arena.ensure(h, words * 4, "hipMalloc(png streams)"))) return rc;
+    uint32_t* z = reinterpret_cast<uint32_t*>(h->count_arena.p);
+    HIP_TRY(h, hipMemcpyAsync(b.codes, codes.data(), codes.size() * sizeof(PngDevCode), hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipEventRecord(h->ev_files[4], s));
+    HIP_TRY(h, run_png_emit(d_labels, px, n, H, W, b, z, words * 4, s));
+    HIP_TRY(h, hipEventRecord(h->ev_files[5], s));
+    std::vector<unsigned long long> dz((size_t)n);
+    HIP_TRY(h, hipMemcpyAsync(dz.data(), b.z_bytes, dz.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    for (int i = 0; i < n; ++i) {
+        const size_t total = label_png_file_bytes(zb[i]);
+        file_bytes[i] = total > (unsigned long long)file_cap ? -(long long)total : (long long)total;
+        if (file_bytes[i] > 0)
+            HIP_TRY(h, hipMemcpyAsync(files[i] + LABEL_PNG_Z_OFFSET, z + codes[i].z_off, zb[i], hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(h, hipStreamSynchronize(s));
+    for (int i = 0; i < n; ++i) {
+        if (dz[i] != zb[i])
+            return fail(h, ECSEG_E_HIP, std::string(who) + ": image " + std::to_string(i) + ": the device wrote a stream of " + std::to_string(dz[i]) +
+                                            " bytes where the counts give " + std::to_string(zb[i]));
+        if (file_bytes[i] > 0) label_png_frame(files[i], zb[i], H, W);
+    }
+    *ms = stage_elapsed(h->ev_files[2], h->ev_files[3]) + stage_elapsed(h->ev_files[4], h->ev_files[5]);
+    return ECSEG_OK;
+}
 
 extern "C" {
 
@@ -427,43 +522,6 @@ long long ecseg_tiff_encode_bound(int H, int W, int spp) {
     return (long long)(8 + (size_t)nstrips * (tiff_strip_bound((size_t)rps * W * spp) + 1) + tiff_tail_bound(nstrips, spp));
 }
 
-// The strips of n_files rasters are encoded and packed (run_tiff_encode is on the stream): brings the tables over, puts head and
-// tail around every file's strips and copies the strips into the caller's buffers.  Nothing is written when any file does not fit.
-static int tiff_collect(ecseg_ctx* h, const char* who, int n_files, int H, int W, int spp, const TiffEncodeBufs& b, uint8_t* const* files,
-                        long long file_cap, long long* file_bytes) {
-    hipStream_t s = h->stream;
-    const size_t ns = (size_t)b.nstrips;
-    std::vector<uint32_t> cnt(ns * n_files);
-    std::vector<unsigned long long> off((ns + 1) * n_files);
-    HIP_TRY(h, hipMemcpyAsync(cnt.data(), b.cnt, cnt.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipMemcpyAsync(off.data(), b.off, off.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipStreamSynchronize(s));
-    std::vector<uint8_t> head[3], tail[3];
-    std::vector<uint32_t> offs(ns);
-    for (int f = 0; f < n_files; ++f) {
-        const unsigned long long* o = off.data() + (ns + 1) * f;
-        const uint32_t* m = cnt.data() + ns * f;
-        for (size_t k = 0; k < ns; ++k) {
-            if (8 + o[k] + m[k] + 1 >= 0xffffffffull) return fail(h, ECSEG_E_INVALID, std::string(who) + ": the file would pass 4 GiB (classic TIFF has 32-bit offsets)");
-            offs[k] = (uint32_t)(8 + o[k]);
-        }
-        tiff_frame(H, W, spp, b.rps, offs.data(), m, b.nstrips, (size_t)(8 + o[ns]), &head[f], &tail[f]);
-        const unsigned long long total = 8 + o[ns] + tail[f].size();
-        if (total > (unsigned long long)file_cap)
-            return fail(h, ECSEG_E_INVALID, std::string(who) + ": a file of " + std::to_string(total) + " bytes does not fit the capacity of " +
-                                                std::to_string(file_cap) + " (ecseg_tiff_encode_bound says what always does)");
-        file_bytes[f] = (long long)total;
-    }
-    for (int f = 0; f < n_files; ++f) {
-        const size_t data = (size_t)off[(ns + 1) * f + ns];
-        std::memcpy(files[f], head[f].data(), 8);
-        HIP_TRY(h, hipMemcpyAsync(files[f] + 8, b.packed + b.file_stride * f, data, hipMemcpyDeviceToHost, s));
-        std::memcpy(files[f] + 8 + data, tail[f].data(), tail[f].size());
-    }
-    HIP_TRY(h, hipStreamSynchronize(s));
-    return ECSEG_OK;
-}
-
 int ecseg_tiff_encode(ecseg_ctx* h, const uint8_t* img, int H, int W, int spp, int invert, uint8_t* out, long long out_cap, long long* out_bytes) {
     if (!h) return ECSEG_E_INVALID;
     drop_sent_ahead(h);
@@ -479,9 +537,9 @@ int ecseg_tiff_encode(ecseg_ctx* h, const uint8_t* img, int H, int W, int spp, i
     for (float& v : h->stage_ms) v = 0.f;
     HIP_TRY(h, hipMemcpyAsync(b.img, img, (size_t)H * W * spp, hipMemcpyHostToDevice, s));
     HIP_TRY(h, hipEventRecord(h->ev[0], s));
-    HIP_TRY(h, run_tiff_encode(TiffSources{{b.img, nullptr, nullptr}}, 1, H, W, spp, invert, b, s));
+    HIP_TRY(h, run_tiff_encode(TiffSources{{b.img, nullptr, nullptr}, 0}, 1, H, W, spp, invert, b, s));
     HIP_TRY(h, hipEventRecord(h->ev[1], s));
-    if ((rc = tiff_collect(h, "tiff_encode", 1, H, W, spp, b, &out, out_cap, out_bytes))) return rc;
+    if ((rc = tiff_collect(h, "tiff_encode", 1, H, W, spp, b, &out, out_cap, out_bytes, true))) return rc;
     h->stage_ms[ECSEG_T_COUNT] = stage_elapsed(h->ev[0], h->ev[1]);
     return ECSEG_OK;
 }
@@ -508,14 +566,33 @@ int ecseg_fish_render_tiff(ecseg_ctx* h, const uint8_t* img, int H, int W, int C
     HIP_TRY(h, hipMemcpyAsync(b.bnd, boundaries, px, hipMemcpyHostToDevice, s));
     HIP_TRY(h, hipEventRecord(h->ev[0], s));
     HIP_TRY(h, run_fish_render(H, W, C, ch, b, s));
-    HIP_TRY(h, run_tiff_encode(TiffSources{{b.orig, b.seg, b.lsq}}, 3, H, W, 3, 0, t, s));
+    HIP_TRY(h, run_tiff_encode(TiffSources{{b.orig, b.seg, b.lsq}, 0}, 3, H, W, 3, 0, t, s));
     HIP_TRY(h, hipEventRecord(h->ev[1], s));
     if (original) HIP_TRY(h, hipMemcpyAsync(original, b.orig, px * 3, hipMemcpyDeviceToHost, s));
     if (with_segmentation) HIP_TRY(h, hipMemcpyAsync(with_segmentation, b.seg, px * 3, hipMemcpyDeviceToHost, s));
     if (lsq) HIP_TRY(h, hipMemcpyAsync(lsq, b.lsq, px * 3, hipMemcpyDeviceToHost, s));
-    if ((rc = tiff_collect(h, "fish_render_tiff", 3, H, W, 3, t, files, file_cap, file_bytes))) return rc;
+    if ((rc = tiff_collect(h, "fish_render_tiff", 3, H, W, 3, t, files, file_cap, file_bytes, true))) return rc;
     h->stage_ms[ECSEG_T_COUNT] = stage_elapsed(h->ev[0], h->ev[1]);
     return ECSEG_OK;
+}
+
+// ---- label PNG files encoded on the device (png_kernels.hip; the host writer is ecseg_png_write_labels, host_io.cpp) ---------------
+int ecseg_png_labels_encode(ecseg_ctx* h, const uint8_t* labels, int n_img, int H, int W, uint8_t* const* files, long long file_cap,
+                            long long* file_bytes) {
+    if (!h) return ECSEG_E_INVALID;
+    drop_sent_ahead(h);
+    if (n_img < 0 || n_img >= 65536 || H <= 0 || W <= 0 || W >= (1 << 30) || file_cap < 1 || (n_img > 0 && (!labels || !files || !file_bytes)))
+        return fail(h, ECSEG_E_INVALID, "png_labels_encode: bad arguments");
+    for (int i = 0; i < n_img; ++i) if (!files[i]) return fail(h, ECSEG_E_INVALID, "png_labels_encode: a null file buffer");
+    for (float& v : h->stage_ms) v = 0.f;
+    if (n_img == 0) return ECSEG_OK;
+    for (int i = 0; i < n_img; ++i) file_bytes[i] = 0;
+    HIP_TRY(h, hipSetDevice(h->device));
+    int rc;
+    PngEncodeBufs b{};
+    if ((rc = lay_out(h, h->call_arena, [&](Carver& c) { b = png_encode_bufs(c, H, W, n_img, true); }))) return rc;
+    HIP_TRY(h, hipMemcpyAsync(b.labels, labels, (size_t)n_img * H * W, hipMemcpyHostToDevice, h->stream));
+    return png_encode_files(h, "png_labels_encode", b.labels, n_img, H, W, b, files, file_cap, file_bytes, &h->stage_ms[ECSEG_T_COUNT]);
 }
 
 // ---- the min-cut splitter's max-flow tasks (src/max_flow_binary_mask.py:59-116) ------------------------------------------------

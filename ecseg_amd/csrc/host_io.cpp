@@ -22,9 +22,12 @@
 #include <vector>
 
 #include "../../include/ecseg_hip.h"
+#include "png_label_code.h"
 #include "tiff_frame.h"
 
 namespace {
+
+using namespace ecseg;
 
 struct File {
     FILE* f = nullptr;
@@ -93,87 +96,9 @@ int png_write_rows(const char* path, const std::vector<uint8_t>& rows, int H, in
 // the never-materialised RGBA rows is advanced in closed form per run.  Any inflate reproduces the rows exactly (the
 // pixels are the contract); realistic label maps come out as small as zlib's, speckled ones ~2.5x larger, both in a
 // fraction of zlib's time.
-struct BitWriter {                                        // branch-free: speckled label maps make every data-dependent branch a coin flip
-    uint8_t* p;                                           // into a buffer sized for the worst case (+ 8 bytes of slack) by the caller
-    uint64_t acc = 0;
-    int n = 0;                                            // < 8 between calls
-    explicit BitWriter(uint8_t* dst) : p(dst) {}
-    inline void put(uint64_t bits, int len) {             // LSB-first; len <= 56
-        acc |= bits << n;
-        n += len;
-        std::memcpy(p, &acc, 8);                          // little-endian host (x86-64 / the GPU boxes); whole bytes are kept below
-        p += n >> 3;
-        acc >>= (n & ~7);
-        n &= 7;
-    }
-    uint8_t* finish() {
-        if (n > 0) { *p++ = (uint8_t)acc; }
-        acc = 0; n = 0;
-        return p;
-    }
-};
-
-// code lengths (<= 15) of a Huffman code for the given counts; symbols with count 0 get length 0; a lone used symbol gets 1
-void huffman_lengths(const uint32_t* freq, int nsym, uint8_t* len) {
-    std::vector<uint64_t> f(freq, freq + nsym);
-    for (;;) {
-        struct Node { uint64_t w; int l, r; };
-        std::vector<Node> nodes;
-        std::vector<int> live;
-        for (int i = 0; i < nsym; ++i) { len[i] = 0; if (f[i]) { nodes.push_back({f[i], -1 - i, 0}); live.push_back((int)nodes.size() - 1); } }
-        if (live.empty()) return;
-        if (live.size() == 1) { len[-1 - nodes[live[0]].l] = 1; return; }
-        while (live.size() > 1) {                             // (tens of symbols: a quadratic merge is fine)
-            int a = 0, b = 1;
-            if (nodes[live[b]].w < nodes[live[a]].w) std::swap(a, b);
-            for (int k = 2; k < (int)live.size(); ++k) {
-                if (nodes[live[k]].w < nodes[live[a]].w) { b = a; a = k; }
-                else if (nodes[live[k]].w < nodes[live[b]].w) b = k;
-            }
-            nodes.push_back({nodes[live[a]].w + nodes[live[b]].w, live[a], live[b]});
-            const int hi = std::max(a, b), lo = std::min(a, b);
-            live.erase(live.begin() + hi);
-            live[lo] = (int)nodes.size() - 1;
-        }
-        int maxlen = 0;
-        std::vector<std::pair<int, int>> stack{{live[0], 0}};
-        while (!stack.empty()) {
-            const auto [id, d] = stack.back();
-            stack.pop_back();
-            if (nodes[id].l < 0) { len[-1 - nodes[id].l] = (uint8_t)d; maxlen = std::max(maxlen, d); }
-            else { stack.push_back({nodes[id].l, d + 1}); stack.push_back({nodes[id].r, d + 1}); }
-        }
-        if (maxlen <= 15) return;
-        for (auto& v : f) if (v) v = (v + 1) / 2;              // flatten the distribution and try again
-    }
-}
-
-// canonical codes, bit-reversed for deflate's LSB-first packing
-void canonical_codes(const uint8_t* len, int nsym, uint16_t* code) {
-    int count[16] = {0}, next[16] = {0};
-    for (int i = 0; i < nsym; ++i) ++count[len[i]];
-    count[0] = 0;
-    int c = 0;
-    for (int b = 1; b < 16; ++b) { c = (c + count[b - 1]) << 1; next[b] = c; }
-    for (int i = 0; i < nsym; ++i) {
-        if (!len[i]) { code[i] = 0; continue; }
-        int v = next[len[i]]++, r = 0;
-        for (int k = 0; k < len[i]; ++k) { r = (r << 1) | (v & 1); v >>= 1; }
-        code[i] = (uint16_t)r;
-    }
-}
-
-struct LenCode { uint16_t sym; uint8_t extra_bits; uint8_t extra; };
-inline LenCode length_code(int L) {                          // deflate length 3..258 -> symbol 257.. + extra bits
-    static const int base[29] = {3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 15, 17, 19, 23, 27, 31, 35, 43, 51, 59, 67, 83, 99, 115, 131, 163, 195, 227, 258};
-    static const int ebits[29] = {0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 4, 5, 5, 5, 5, 0};
-    int i = 28;
-    while (base[i] > L) --i;
-    return LenCode{(uint16_t)(257 + i), (uint8_t)ebits[i], (uint8_t)(L - base[i])};
-}
-
 // zlib stream (header, one dynamic block, Adler-32) of the RGBA scan lines (filter byte 0 each) of an H x W label image
-void deflate_labels(const uint8_t* labels, int H, int W, const uint8_t pal[4][4], std::vector<uint8_t>* z) {
+// stream_bytes (optional): the size label_png_stream_bytes works out from the counts alone
+void deflate_labels(const uint8_t* labels, int H, int W, const uint8_t pal[4][4], std::vector<uint8_t>* z, size_t* stream_bytes = nullptr) {
     // pass 1: run-length tokens (colour in the top 2 bits, run length below; 0xffffffff = start of a scan line) + counts
     uint32_t flit[4] = {0, 0, 0, 0};                          // runs per colour (each contributes its 4 literal bytes)
     uint32_t flen[65] = {0};                                  // matches of 4 m bytes, m = 1..64
@@ -229,47 +154,19 @@ void deflate_labels(const uint8_t* labels, int H, int W, const uint8_t pal[4][4]
         flen[64] += (uint32_t)((k - 1) >> 6);
         ++flen[(k - 1) & 63];
     }
-    uint32_t freq[286] = {0};
-    freq[0] += (uint32_t)H;                                   // filter bytes
-    for (int c = 0; c < 4; ++c) for (int k = 0; k < 4; ++k) freq[pal[c][k]] += flit[c];
-    freq[256] = 1;
-    bool any_match = false;
-    for (int m = 1; m <= 64; ++m) if (flen[m]) { freq[length_code(4 * m).sym] += flen[m]; any_match = true; }
-    uint8_t llen[286], dlen[4] = {0, 0, 0, 0};
-    uint16_t lcode[286];
-    huffman_lengths(freq, 286, llen);
-    canonical_codes(llen, 286, lcode);
-    if (any_match) dlen[3] = 1;                               // distance 4 = distance code 3, the only one: a single 1-bit code (bit 0)
-    // code-length alphabet: a fixed complete code (13 symbols of 4 bits, 6 of 5 bits); lengths are sent one by one
-    uint8_t cl_len[19];
-    uint16_t cl_code[19];
-    for (int i = 0; i < 19; ++i) cl_len[i] = i < 13 ? 4 : 5;
-    canonical_codes(cl_len, 19, cl_code);
+    LabelPngCode code;
+    label_png_code(flit, flen, (uint32_t)H, pal, &code);
+    if (stream_bytes) *stream_bytes = label_png_stream_bytes(code, flit, flen, (uint32_t)H);
+    const uint64_t* cbits = code.cbits; const int* cn = code.cn;
+    const uint32_t* mbits = code.mbits; const int* mn = code.mn;
     // worst case: every run costs its four literals (<= 60 bits) plus one match code (<= 21 bits) per started 64 pixels
     // (in closed form: at most nt runs, and W / 64 + 1 further match codes per scan line)
     const size_t worst_bits = 4096 + 16 * (size_t)H + 64 + (60 + 21) * nt + 21 * (size_t)H * ((size_t)W / 64 + 1);
     std::unique_ptr<uint8_t[]> buf(new uint8_t[worst_bits / 8 + 32]);
-    buf[0] = 0x78; buf[1] = 0x01;
-    BitWriter bw(buf.get() + 2);
-    bw.put(1, 1); bw.put(2, 2);                               // BFINAL, BTYPE = dynamic
-    bw.put(286 - 257, 5); bw.put(4 - 1, 5); bw.put(19 - 4, 4);
-    static const int order[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
-    for (int i = 0; i < 19; ++i) bw.put(cl_len[order[i]], 3);
-    for (int i = 0; i < 286; ++i) bw.put(cl_code[llen[i]], cl_len[llen[i]]);
-    for (int i = 0; i < 4; ++i) bw.put(cl_code[dlen[i]], cl_len[dlen[i]]);
-    // per colour: the bit string of its four literals; per match length 4 m: length code + extra bits + the 1-bit distance code
-    uint64_t cbits[4]; int cn[4];
-    for (int c = 0; c < 4; ++c) {
-        cbits[c] = 0; cn[c] = 0;
-        for (int k = 0; k < 4; ++k) { cbits[c] |= (uint64_t)lcode[pal[c][k]] << cn[c]; cn[c] += llen[pal[c][k]]; }
-    }
-    uint32_t mbits[65]; int mn[65];
-    mbits[0] = 0; mn[0] = 0;                                  // "no remainder match": zero bits
-    for (int m = 1; m <= 64; ++m) {
-        const LenCode lc = length_code(4 * m);
-        mbits[m] = (uint32_t)lcode[lc.sym] | ((uint32_t)lc.extra << llen[lc.sym]);
-        mn[m] = llen[lc.sym] + lc.extra_bits + 1;             // + distance code "0"
-    }
+    std::memcpy(buf.get(), code.head, (code.head_bits + 7) / 8);
+    BitWriter bw(buf.get() + code.head_bits / 8);             // goes on behind the block header, inside its last byte
+    bw.n = (int)(code.head_bits & 7);
+    bw.acc = bw.n ? code.head[code.head_bits / 8] : 0;
     // pass 2: bits + Adler-32 in closed form (per run of k pixels with byte sum S and weighted sum T = 4 p0 + 3 p1 + 2 p2 + p3:
     // b += 4 k a + 2 k (k - 1) S + k T; a += k S)
     uint64_t S[4], T[4];
@@ -289,7 +186,7 @@ void deflate_labels(const uint8_t* labels, int H, int W, const uint8_t pal[4][4]
     const uint64_t M = 65521;
     for (size_t i = 0; i < nt; ++i) {
         const uint32_t t = tok[i];
-        if (t == 0xffffffffu) { bw.put(lcode[0], llen[0]); b += a; continue; }
+        if (t == 0xffffffffu) { bw.put(code.filt, code.filt_n); b += a; continue; }
         const int c = (int)(t >> 30);
         const uint64_t k = t & 0x3fffffffu;
         if (k <= 64 && comb_n[c][k]) {
@@ -315,7 +212,7 @@ void deflate_labels(const uint8_t* labels, int H, int W, const uint8_t pal[4][4]
         a += k * S[c];
     }
     a %= M; b %= M;
-    bw.put(lcode[256], llen[256]);
+    bw.put(code.eob, code.eob_n);
     uint8_t* end = bw.finish();
     const uint32_t adler = (uint32_t)((b << 16) | a);
     *end++ = (uint8_t)(adler >> 24); *end++ = (uint8_t)(adler >> 16); *end++ = (uint8_t)(adler >> 8); *end++ = (uint8_t)adler;
@@ -633,6 +530,26 @@ void ecseg::tiff_frame(int H, int W, int spp, int rps, const uint32_t* offs, con
     tail->insert(tail->end(), ifd.begin(), ifd.end());
 }
 
+// The file around a label PNG's stream (png_label_code.h): what png_write_stream puts around it, in memory.
+void ecseg::label_png_frame(uint8_t* file, size_t z, int H, int W) {
+    static const uint8_t sig[8] = {0x89, 'P', 'N', 'G', '\r', '\n', 0x1a, '\n'};
+    auto chunk = [](uint8_t* p, const char tag[4], size_t n) {     // the data lies at p + 8 already; returns the chunk's end
+        put_be32(p, (uint32_t)n);
+        std::memcpy(p + 4, tag, 4);
+        uLong c = crc32(0L, p + 4, 4);
+        for (size_t off = 0; off < n; off += (1u << 30)) c = crc32(c, p + 8 + off, (uInt)std::min<size_t>(n - off, 1u << 30));
+        put_be32(p + 8 + n, (uint32_t)c);
+        return p + 12 + n;
+    };
+    std::memcpy(file, sig, 8);
+    uint8_t* ihdr = file + 16;
+    put_be32(ihdr, (uint32_t)W); put_be32(ihdr + 4, (uint32_t)H);
+    ihdr[8] = 8; ihdr[9] = 6; ihdr[10] = 0; ihdr[11] = 0; ihdr[12] = 0;
+    uint8_t* p = chunk(file + 8, "IHDR", 13);
+    p = chunk(p, "IDAT", z);
+    chunk(p, "IEND", 0);
+}
+
 extern "C" {
 
 int ecseg_npy_write_i64(const char* path, const uint8_t* labels, int H, int W) { return npy_write_as_i64(path, labels, H, W); }
@@ -644,11 +561,21 @@ int ecseg_npy_write_i32_as_i64(const char* path, const int32_t* labels, int H, i
 // every scan line, compressed by deflate_labels above (the pixels are the contract, not the compressed bytes).
 int ecseg_png_write_labels(const char* path, const uint8_t* labels, int H, int W) {
     if (!path || !labels || H <= 0 || W <= 0) return ECSEG_E_INVALID;
-    static const uint8_t pal[4][4] = {{0x38, 0x6c, 0xb0, 255}, {0xff, 0xff, 0x99, 255}, {0x7f, 0xc9, 0x7f, 255}, {0xf0, 0x02, 0x7f, 255}};
     if (W >= (1 << 30)) return ECSEG_E_INVALID;
     std::vector<uint8_t> z;
-    deflate_labels(labels, H, W, pal, &z);
+    deflate_labels(labels, H, W, LABEL_PNG_PALETTE, &z);
     return png_write_stream(path, z, H, W, 6);
+}
+
+// The zlib stream of that file: *stream_bytes its length as written, *formula_bytes the length label_png_stream_bytes works out
+// from the token counts before a bit is written (the device coder sizes its buffers by it: the two must agree).
+int ecseg_png_labels_stream_size(const uint8_t* labels, int H, int W, long long* formula_bytes, long long* stream_bytes) {
+    if (!labels || !formula_bytes || !stream_bytes || H <= 0 || W <= 0 || W >= (1 << 30)) return ECSEG_E_INVALID;
+    std::vector<uint8_t> z;
+    size_t f = 0;
+    deflate_labels(labels, H, W, LABEL_PNG_PALETTE, &z, &f);
+    *formula_bytes = (long long)f; *stream_bytes = (long long)z.size();
+    return ECSEG_OK;
 }
 
 // 8-bit PNG of a (H, W, channels) image, channels 1 (gray), 3 (RGB) or 4 (RGBA): the red/ green/ channel images of

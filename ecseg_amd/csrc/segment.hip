@@ -307,16 +307,19 @@ int ecseg_preprocess(ecseg_ctx* h, const void* img, int n_img, int H, int W, int
 // once, the pre-processed images never leave the device between meta_preprocess and the U-Net (the two-call sequence
 // ecseg_preprocess + ecseg_segment_images_ex downloads them, synchronises and uploads them again), and their copy back
 // to the host (dapi/<name> is written from it) travels on the second stream under the U-Net.
-int ecseg_meta_segment(ecseg_ctx* h, const void* img, int n_img, int H, int W, int C, int bps, uint8_t* gray_out, uint8_t* post,
-                       int32_t* n_ec, int32_t* tie_risk) {
-    if (!h) return ECSEG_E_INVALID;
-    if (n_img < 0 || H <= 0 || W <= 0 || (C != 1 && C != 3 && C != 4) || (bps != 1 && bps != 2) || (n_img > 0 && (!img || !post)))
-        return fail(h, ECSEG_E_INVALID, "meta_segment: bad arguments");
-    if (n_img == 0) return ECSEG_OK;
+// files (ecseg_meta_segment_files): the two file images per image, the dapi strips encoded on the second stream beside the copy
+// of gray_out, the label PNGs behind the clean-up
+struct MetaFiles { uint8_t* const* dapi; long long dapi_cap; long long* dapi_bytes; uint8_t* const* png; long long png_cap; long long* png_bytes; };
+static int meta_segment_run(ecseg_ctx* h, const void* img, int n_img, int H, int W, int C, int bps, uint8_t* gray_out, uint8_t* post,
+                            int32_t* n_ec, int32_t* tie_risk, const MetaFiles* files) {
     int rc = check_model(h);
     if (rc) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
     const size_t px = (size_t)H * W, tot = px * n_img, in_bytes = tot * C * bps;
+    TiffEncodeBufs tb{};
+    PngEncodeBufs pb{};
+    if (files && (rc = lay_out(h, h->call_arena, [&](Carver& c) { tb = tiff_encode_bufs(c, H, W, 1, n_img, false); pb = png_encode_bufs(c, H, W, n_img, false); })))
+        return rc;
     if ((rc = h->d_aux8.ensure(h, in_bytes))) return rc;
     if ((rc = h->d_gray.ensure(h, tot))) return rc;
     if ((rc = h->d_raw.ensure(h, tot))) return rc;
@@ -338,11 +341,16 @@ int ecseg_meta_segment(ecseg_ctx* h, const void* img, int n_img, int H, int W, i
     }
     const double t1 = dbg_now();
     HIP_TRY(h, run_preprocess(h->d_aux8, n_img, H, W, C, bps, h->d_gray, h->d_i32 + n_img, h->d_hist, s));
-    if (gray_out) {
+    if (gray_out || files) {
         HIP_TRY(h, hipEventRecord(h->ev[2], s));
         HIP_TRY(h, hipStreamWaitEvent(sc, h->ev[2], 0));
-        HIP_TRY(h, hipMemcpyAsync(gray_out, h->d_gray, tot, hipMemcpyDeviceToHost, sc));
     }
+    if (files) {                                           // dapi/<name>.tif holds cv2.bitwise_not of the pre-processed image
+        HIP_TRY(h, hipEventRecord(h->ev_files[0], sc));
+        HIP_TRY(h, run_tiff_encode(TiffSources{{h->d_gray, nullptr, nullptr}, px}, n_img, H, W, 1, 1, tb, sc));
+        HIP_TRY(h, hipEventRecord(h->ev_files[1], sc));
+    }
+    if (gray_out) HIP_TRY(h, hipMemcpyAsync(gray_out, h->d_gray, tot, hipMemcpyDeviceToHost, sc));
     if (h->next_host) {                                    // the next call's images, registered by ecseg_prefetch_input
         const void* nx = h->next_host; const size_t nb = h->next_bytes;
         h->next_host = nullptr; h->next_bytes = 0;
@@ -364,9 +372,49 @@ int ecseg_meta_segment(ecseg_ctx* h, const void* img, int n_img, int H, int W, i
     const double t4 = dbg_now();
     HIP_TRY(h, wait_stream(h, sc));
     if (h->pre_host) HIP_TRY(h, wait_stream(h, h->stream_in));     // (long done: the caller's buffer is not read after this call)
+    if (files) {                                           // (both streams are idle: the tables, then the files that fit)
+        if ((rc = tiff_collect(h, "meta_segment_files", n_img, H, W, 1, tb, files->dapi, files->dapi_cap, files->dapi_bytes, false))) return rc;
+        h->file_ms[0] = stage_elapsed(h->ev_files[0], h->ev_files[1]);
+        if ((rc = png_encode_files(h, "meta_segment_files", h->d_post, n_img, H, W, pb, files->png, files->png_cap, files->png_bytes, &h->file_ms[1])))
+            return rc;
+    }
     const double t5 = dbg_now();
     if (debug_calls()) fprintf(stderr, "[meta_segment n=%d] upload enqueue %.2f preprocess + gray copy enqueue %.2f segment_dev %.2f (stage timers %.2f) labels down %.2f gray wait %.2f total %.2f ms\n",
                      n_img, t1 - t0, t2 - t1, t3 - t2, h->stage_ms[0] + h->stage_ms[1] + h->stage_ms[2] + h->stage_ms[3], t4 - t3, t5 - t4, t5 - t0);
+    return ECSEG_OK;
+}
+
+int ecseg_meta_segment(ecseg_ctx* h, const void* img, int n_img, int H, int W, int C, int bps, uint8_t* gray_out, uint8_t* post,
+                       int32_t* n_ec, int32_t* tie_risk) {
+    if (!h) return ECSEG_E_INVALID;
+    if (n_img < 0 || H <= 0 || W <= 0 || (C != 1 && C != 3 && C != 4) || (bps != 1 && bps != 2) || (n_img > 0 && (!img || !post)))
+        return fail(h, ECSEG_E_INVALID, "meta_segment: bad arguments");
+    if (n_img == 0) return ECSEG_OK;
+    return meta_segment_run(h, img, n_img, H, W, C, bps, gray_out, post, n_ec, tie_risk, nullptr);
+}
+
+int ecseg_meta_segment_files(ecseg_ctx* h, const void* img, int n_img, int H, int W, int C, int bps, uint8_t* const* dapi_files,
+                             long long dapi_cap, long long* dapi_bytes, uint8_t* const* png_files, long long png_cap, long long* png_bytes,
+                             uint8_t* gray_out, uint8_t* labels_post, int32_t* n_ec, int32_t* tie_risk) {
+    if (!h) return ECSEG_E_INVALID;
+    if (n_img < 0 || H <= 0 || W <= 0 || (C != 1 && C != 3 && C != 4) || (bps != 1 && bps != 2) || (n_img > 0 && (!img || !labels_post)))
+        return fail(h, ECSEG_E_INVALID, "meta_segment_files: bad arguments");
+    if (!dapi_files || !dapi_bytes || !png_files || !png_bytes || dapi_cap < 1 || png_cap < 1)
+        return fail(h, ECSEG_E_INVALID, "meta_segment_files: a null file table or a capacity below 1");
+    for (int i = 0; i < n_img; ++i)
+        if (!dapi_files[i] || !png_files[i]) return fail(h, ECSEG_E_INVALID, "meta_segment_files: a null file buffer");
+    if (n_img >= 65536 || W >= (1 << 30)) return fail(h, ECSEG_E_INVALID, "meta_segment_files: 65536 images or more, or lines of 2^30 pixels or more");
+    h->file_ms[0] = h->file_ms[1] = 0.f;
+    if (n_img == 0) return ECSEG_OK;
+    const int rps = tiff_rows_per_strip(H, W, 1);
+    if ((H + rps - 1) / rps >= (1 << 26)) return fail(h, ECSEG_E_INVALID, "meta_segment_files: 2^26 strips or more (such a file would pass 4 GiB)");
+    const MetaFiles files{dapi_files, dapi_cap, dapi_bytes, png_files, png_cap, png_bytes};
+    return meta_segment_run(h, img, n_img, H, W, C, bps, gray_out, labels_post, n_ec, tie_risk, &files);
+}
+
+int ecseg_get_file_timings(ecseg_ctx* h, float* ms_out) {
+    if (!h || !ms_out) return ECSEG_E_INVALID;
+    ms_out[0] = h->file_ms[0]; ms_out[1] = h->file_ms[1];
     return ECSEG_OK;
 }
 

@@ -16,6 +16,9 @@
 // reaches 4094; the width step of last() before EOI; the last bits zero-padded to a byte.  The final dword is zero-padded too: the
 // byte behind a strip of odd length is the 0 the file wants there, which the gather copies with it.
 //
+// A launch takes up to three rasters by pointer (stat_fish's colour files) or a batch at one stride (`make metaseg`'s dapi images):
+// grid dimension y is the file.
+//
 // tiff_scan_kernel: the strip offsets, an exclusive scan over m + (m & 1) in 64 bits (one workgroup per file).
 // tiff_gather_kernel: the strips back to back, two bytes per lane and store (every strip starts on an even offset).
 #include "common.h"
@@ -57,7 +60,7 @@ __global__ __launch_bounds__(64) void tiff_lzw_strip_kernel(TiffSources srcs, in
     const size_t strip = blockIdx.x, file = blockIdx.y, slot = file * gridDim.x + strip;
     const int r0 = (int)strip * rps, rows = r0 + rps <= H ? rps : H - r0;
     const uint32_t n = (uint32_t)rows * line;                // <= 8192 with more than one row, else one line < 2^30
-    const uint8_t* __restrict__ src = srcs.img[file] + (size_t)r0 * line;
+    const uint8_t* __restrict__ src = srcs.img[srcs.stride ? 0 : file] + file * srcs.stride + (size_t)r0 * line;
     uint32_t* __restrict__ dst = reinterpret_cast<uint32_t*>(slots + slot * slot_stride);
     const uint32_t slot_words = (uint32_t)(slot_stride / 4);
     uint32_t written = 0;                                    // words of the slot that hold output

@@ -11,7 +11,9 @@ of the per-image records (the reference's analogue is the implicit all-device Mi
 
 Optional config keys (defaults keep the reference's behaviour): ``batch_images`` (8), ``io_threads``, ``device_ids``,
 ``resume`` (false; true: images whose ``labels/<stem>.npy``, ``.png`` and ``dapi/<name>`` exist are not segmented again),
-``device_workers`` (1), ``pinned_mb`` (2048: page-locked host memory for the batch buffers; 0: none).
+``device_workers`` (1), ``pinned_mb`` (2048: page-locked host memory for the batch buffers; 0: none), ``files_on_device`` (false;
+true: ``dapi/<name>.tif`` and ``labels/<stem>.png`` are encoded on the GPU by the batch's device call and the writer threads only
+put the bytes on disk - the same bytes; a file the device did not produce is written by the host writer as before).
 """
 import concurrent.futures as cf
 import json
@@ -80,18 +82,27 @@ def _replace_into(path, write):
         raise
 
 
-def _write_outputs(p, gray, post, log, probs=None):
+def _write_outputs(p, gray, post, log, probs=None, files=None):
     """gray: the pre-processed image; dapi/<name> holds cv2.bitwise_not of it (src/utils.py:112,122-123).  probs (config key
-    ``emit_probs``): the stitched float32 probabilities -> labels/<stem>_probs.npy, written before the resume marker."""
+    ``emit_probs``): the stitched float32 probabilities -> labels/<stem>_probs.npy, written before the resume marker.  files (config
+    key ``files_on_device``): the file images (dapi TIFF, label PNG) the device encoded, each None where it produced none - that
+    file is encoded here, as are all without the key."""
+    dapi_file, png_file = files or (None, None)
     path_split = os.path.split(p)
     dapi = os.path.join(path_split[0], 'dapi', path_split[1])
     if dapi.lower().endswith(('.tif', '.tiff')):
-        _replace_into(dapi, lambda t: image_io.write_tiff_gray8(t, gray, invert=True))
+        if dapi_file is not None:
+            _replace_into(dapi, lambda t: image_io.write_file_image(t, dapi_file))
+        else:
+            _replace_into(dapi, lambda t: image_io.write_tiff_gray8(t, gray, invert=True))
     else:
         save_img(~gray, path_split, 'dapi')
     outpath = os.path.join(path_split[0], 'labels', path_split[1][:-4])
     log("Saving labels: ", p, " to ", outpath)
-    _replace_into(outpath + '.png', lambda t: image_io.write_label_png(t, post))
+    if png_file is not None:
+        _replace_into(outpath + '.png', lambda t: image_io.write_file_image(t, png_file))
+    else:
+        _replace_into(outpath + '.png', lambda t: image_io.write_label_png(t, post))
     if probs is not None:
         def save_probs(t):
             with open(t, 'wb') as f:                        # (np.save would append ".npy" to the temporary name)
@@ -209,8 +220,22 @@ def _view(buf, shape, dtype=np.uint8):
     return buf[:n].view(dtype).reshape(shape)
 
 
-def _segment_group(model, imgs, emit_probs=False, outs=None):
-    """-> gray, post, n_ec, tie_risk, probs | None (arrays over the batch).  ``outs``: (gray, post) arrays to fill."""
+def file_capacities(H, W):
+    """Bytes per dapi TIFF and per label PNG that ``files_on_device`` gives the device call: realistic images need a fraction (a
+    1040 x 1392 dapi file is ~0.6 bytes per pixel, its PNG a few per cent of that, a speckled one ~0.3 bytes per pixel); an image
+    that needs more - noise compresses to ~1.4 bytes per pixel under LZW - is encoded by the host writer, so any choice is safe."""
+    return H * W + 65536, H * W // 2 + 65536
+
+
+def _segment_group(model, imgs, emit_probs=False, outs=None, files=None):
+    """-> gray, post, n_ec, tie_risk, probs | None (arrays over the batch).  ``outs``: (gray, post) arrays to fill.
+    ``files`` (the key ``files_on_device``; not with ``emit_probs``, whose device call is another): (dapi capacity, PNG capacity,
+    the two buffers to build the files in | None) -> a sixth value, per image its (dapi file | None, PNG file | None)."""
+    if files is not None and not emit_probs:
+        dcap, pcap, bufs = files
+        gray, post, nec, tie, dapi, png = model.handle.meta_segment_files(imgs, *(outs or (None, None)), dapi_capacity=dcap,
+                                                                          png_capacity=pcap, file_bufs=bufs)
+        return gray, post, nec, tie, None, list(zip(dapi, png))
     fused = getattr(model.handle, 'meta_segment', None)
     if fused is not None and not emit_probs:               # one device call: the pre-processed images stay on the GPU
         gray, post, nec, tie = fused(imgs, *(outs or (None, None)))
@@ -224,7 +249,15 @@ def _segment_group(model, imgs, emit_probs=False, outs=None):
     return (gray, out[0], out[1], out[2], out[3] if emit_probs else None)
 
 
-def _segment_with_retry(model, imgs, log, emit_probs=False, outs=None):
+def _split_files(files, half):
+    """the file buffers of a batch for its first ``half`` images and for the rest"""
+    if files is None or files[2] is None:
+        return files, files
+    dcap, pcap, (d, p) = files
+    return (dcap, pcap, (d[:half * dcap], p[:half * pcap])), (dcap, pcap, (d[half * dcap:], p[half * pcap:]))
+
+
+def _segment_with_retry(model, imgs, log, emit_probs=False, outs=None, files=None):
     """GPU part of one batch.  On an out-of-memory status the internal launch group is halved, starting below what the failed
     attempt used (down to one image per launch); if that still does not fit, the batch itself is split by images (allocations
     that scale with the batch: post-processing workspace, input staging).  The handle's setting is restored afterwards, so
@@ -235,7 +268,7 @@ def _segment_with_retry(model, imgs, log, emit_probs=False, outs=None):
         group = min(before, len(imgs)) if before > 0 else len(imgs)
         while True:
             try:
-                return _segment_group(model, imgs, emit_probs, outs)
+                return _segment_group(model, imgs, emit_probs, outs, files)
             except EcsegError as e:
                 if e.code != E_NOMEM:
                     raise
@@ -249,20 +282,24 @@ def _segment_with_retry(model, imgs, log, emit_probs=False, outs=None):
         half = len(imgs) // 2
         log("Out of device memory for a batch of shape %s: splitting it into %d + %d image(s)" % (imgs.shape, half, len(imgs) - half))
         lo, hi = (tuple(o[:half] for o in outs), tuple(o[half:] for o in outs)) if outs else (None, None)
-        a, b = _segment_with_retry(model, imgs[:half], log, emit_probs, lo), _segment_with_retry(model, imgs[half:], log, emit_probs, hi)
-        return tuple(None if x is None else np.concatenate([x, y]) for x, y in zip(a, b))
+        flo, fhi = _split_files(files, half)
+        a, b = _segment_with_retry(model, imgs[:half], log, emit_probs, lo, flo), _segment_with_retry(model, imgs[half:], log, emit_probs, hi, fhi)
+        return tuple(None if x is None else x + y if isinstance(x, list) else np.concatenate([x, y]) for x, y in zip(a, b))
     finally:
         h.set_images_per_group(before)
 
 
-def _segment_isolating(model, imgs, log, emit_probs=False, outs=None):
+def _segment_isolating(model, imgs, log, emit_probs=False, outs=None, files=None):
     """GPU part of one batch with per-image failure isolation (a per-image status): a batch that fails for any reason
     other than memory (_segment_with_retry deals with that) is bisected until the failing image(s) stand alone - one bad image
-    costs one status-2 row, not the whole batch.  -> list of (index in batch, gray, post, n_ec, tie_risk, probs | None) for the
-    images that went through, list of (index, exception) for those that did not."""
+    costs one status-2 row, not the whole batch.  -> list of (index in batch, gray, post, n_ec, tie_risk, probs | None, files | None)
+    for the images that went through, list of (index, exception) for those that did not.  (A bisected batch builds its files in
+    memory of its own: the halves do not share the batch's buffers.)"""
     try:
-        gray, post, nec, tie, probs = _segment_with_retry(model, imgs, log, emit_probs, outs)
-        return [(j, gray[j], post[j], int(nec[j]), int(tie[j]), None if probs is None else probs[j]) for j in range(len(imgs))], []
+        gray, post, nec, tie, probs, *made = _segment_with_retry(model, imgs, log, emit_probs, outs, files)
+        made = made[0] if made else None
+        return [(j, gray[j], post[j], int(nec[j]), int(tie[j]), None if probs is None else probs[j], None if made is None else made[j])
+                for j in range(len(imgs))], []
     except EcsegError as e:
         # only failures that can belong to ONE input are bisected (a bad argument / shape, an unsupported layout, memory for a single
         # giant image).  A HIP runtime error is sticky - after a device fault or a lost context every sub-batch would fail again,
@@ -275,14 +312,17 @@ def _segment_isolating(model, imgs, log, emit_probs=False, outs=None):
         half = len(imgs) // 2
         log("A batch of %d image(s) of shape %s failed on the device (%s): retrying it as %d + %d"
             % (len(imgs), imgs.shape[1:], e, half, len(imgs) - half))
-        ok_a, bad_a = _segment_isolating(model, imgs[:half], log, emit_probs)
-        ok_b, bad_b = _segment_isolating(model, imgs[half:], log, emit_probs)
+        own = None if files is None else (files[0], files[1], None)
+        ok_a, bad_a = _segment_isolating(model, imgs[:half], log, emit_probs, None, own)
+        ok_b, bad_b = _segment_isolating(model, imgs[half:], log, emit_probs, None, own)
         return (ok_a + [(r[0] + half,) + r[1:] for r in ok_b], bad_a + [(j + half, e2) for j, e2 in bad_b])
 
 
 def run(inpath, model, image_paths, rank=0, world=1, batch_images=8, io_threads=None, log=print, stats=None, resume=False,
-        emit_probs=False, pinned_mb=2048, pinned_min_images=None):
+        emit_probs=False, pinned_mb=2048, pinned_min_images=None, files_on_device=False):
     """Segment this rank's shard; returns records (one row per image of the WHOLE job after the all-gather)."""
+    if files_on_device and not all(hasattr(m.handle, 'meta_segment_files') for m in (model if isinstance(model, (list, tuple)) else [model])):
+        raise ValueError('files_on_device needs the device file coders (meta_segment_files), which the handle in use does not have')
     start, stop, per = dist.shard_bounds(len(image_paths), rank, world)
     mine = image_paths[start:stop]
     n_ec = np.zeros(len(mine), np.int64)
@@ -304,14 +344,14 @@ def run(inpath, model, image_paths, rank=0, world=1, batch_images=8, io_threads=
         pool.start()
     try:
         return _run_threads(model, mine, start, per, rank, world, batch_images, io_threads, window, pending_writes, n_ec,
-                            status, log, stats, resume, tie, emit_probs, pool)
+                            status, log, stats, resume, tie, emit_probs, pool, files_on_device)
     finally:
         pool.stop()
         sys.setswitchinterval(old_switch)
 
 
 def _run_threads(model, mine, start, per, rank, world, batch_images, io_threads, window, pending_writes, n_ec, status, log, stats,
-                 resume=False, tie=None, emit_probs=False, pool=None):
+                 resume=False, tie=None, emit_probs=False, pool=None, files_on_device=False):
     # `model`: one model, or a list of models on the same GPU (config key device_workers): one device thread per model takes
     # batches from the common queue, so the host <-> device copies and the per-call synchronisation of one overlap the kernels of
     # the other (a narrow model spends a third of a call outside its kernels: EXPERIMENTS.md 6)
@@ -321,7 +361,9 @@ def _run_threads(model, mine, start, per, rank, world, batch_images, io_threads,
     t_lock = threading.Lock()
     # per-stage host timers (thread-seconds summed over the worker threads): where a slow `make metaseg` spends its CPU
     # (device_kernels: the library's stage timers; device_native: inside the library call, the rest of gpu_seconds is Python)
-    t_stage = {'read': 0.0, 'write': 0.0, 'pack': 0.0, 'device_kernels': 0.0, 'device_native': 0.0}
+    # (device_dapi_encode / device_png_encode: the file coders of files_on_device, the first as it ran beside the U-Net)
+    t_stage = {'read': 0.0, 'write': 0.0, 'pack': 0.0, 'device_kernels': 0.0, 'device_native': 0.0, 'device_dapi_encode': 0.0,
+               'device_png_encode': 0.0}
 
     def timed(stage, fn):
         def wrapped(*a, **kw):
@@ -366,8 +408,19 @@ def _run_threads(model, mine, start, per, rank, world, batch_images, io_threads,
             full = max(n, batch_images) * H * W
             bufs = [pool.get(n * H * W, full) for _ in range(2)] if not emit_probs else [None, None]
             outs = tuple(_view(b, (n, H, W)) for b in bufs) if all(b is not None for b in bufs) else None
+            files, keep = None, list(bufs) if outs is not None else []     # keep: what goes back to the pool after the last file
+            if files_on_device and not emit_probs:         # page-locked buffers for the file images too, else memory of the call's own
+                dcap, pcap = file_capacities(H, W)
+                fbufs = [pool.get(n * cap, max(n, batch_images) * cap) for cap in (dcap, pcap)]
+                if all(b is not None for b in fbufs):
+                    files = (dcap, pcap, tuple(fbufs))
+                    keep += fbufs
+                else:
+                    files = (dcap, pcap, None)
+                    for b in fbufs:
+                        pool.put(b)
             try:
-                done, bad = _segment_isolating(model, imgs, log, emit_probs, outs)
+                done, bad = _segment_isolating(model, imgs, log, emit_probs, outs, files)
             finally:
                 pool.put(in_buf)                           # (the call has returned: the upload is over)
                 if outs is None:
@@ -376,9 +429,13 @@ def _run_threads(model, mine, start, per, rank, world, batch_images, io_threads,
             dt = time.perf_counter() - t0
             tm = getattr(model.handle, 'timings', None)
             kern = 1e-3 * sum(tm().values()) if tm is not None else 0.0
+            ft = getattr(model.handle, 'file_timings', None) if files is not None and not bad else None
+            fms = ft() if ft is not None else {'dapi': 0.0, 'png': 0.0}
             with t_lock:
                 t_gpu += dt
                 t_stage['device_kernels'] += kern
+                t_stage['device_dapi_encode'] += 1e-3 * fms['dapi']
+                t_stage['device_png_encode'] += 1e-3 * fms['png']
                 t_stage['device_native'] += getattr(model.handle, 'native_seconds', 0.0) - nat0
             for j, e in bad:                               # a failing image must not take its batch or the shard down
                 log("Skipping %s (shape %s): %s" % (mine[group[j]], imgs.shape[1:], e))
@@ -390,20 +447,20 @@ def _run_threads(model, mine, start, per, rank, world, batch_images, io_threads,
                 with t_lock:
                     left[0] -= 1
                     last = left[0] == 0
-                if last and outs is not None:
-                    for b in bufs:
+                if last:
+                    for b in keep:
                         pool.put(b)
 
-            if not done and outs is not None:
-                for b in bufs:
+            if not done:
+                for b in keep:
                     pool.put(b)
-            for j, gray_j, post_j, nec_j, tie_j, probs_j in done:
+            for j, gray_j, post_j, nec_j, tie_j, probs_j, files_j in done:
                 k = group[j]
                 n_ec[k] = nec_j
                 if tie is not None:
                     tie[k] = tie_j
                 pending_writes.acquire()
-                f = writers.submit(write_fn, mine[k], gray_j, post_j, log, probs_j)
+                f = writers.submit(write_fn, mine[k], gray_j, post_j, log, probs_j, files_j)
                 f.add_done_callback(written)
                 write_futs.append((k, f))
 
@@ -484,7 +541,8 @@ def _run_threads(model, mine, start, per, rank, world, batch_images, io_threads,
                     # (three inputs in flight - being packed, queued, on the device - and three output pairs being written)
                     reserved = True
                     b_in, b_out = batch_images * img.nbytes, batch_images * img.shape[0] * img.shape[1]
-                    pool.reserve([b_in, b_out, b_out, b_in, b_out, b_out, b_in, b_out, b_out])
+                    f_out = [batch_images * cap for cap in file_capacities(*img.shape[:2])] if files_on_device and not emit_probs else []
+                    pool.reserve(([b_in, b_out, b_out] + f_out) * 3)
                 if group and (kk != key or len(group) >= batch_images):
                     batches.put(pack(group))
                     group = []
@@ -634,6 +692,10 @@ def main(argv=None):
         print("metaseg.precision must be 'fast', 'exact' or 'split'. Exiting...")
         sys.exit(2)
     emit_probs = bool(var.get('emit_probs', False))
+    files_on_device = var.get('files_on_device', False)
+    if not isinstance(files_on_device, bool):
+        print("metaseg.files_on_device must be true or false (true: dapi TIFFs and label PNGs are encoded on the device). Exiting...")
+        sys.exit(2)
     for sub in ('dapi', 'labels'):
         os.makedirs(os.path.join(inpath, sub), exist_ok=True)
 
@@ -661,13 +723,16 @@ def main(argv=None):
     print(model.handle.device_name)
     for m in models:
         m.handle.set_option('winograd', {'exact': 1, 'fast': 2, 'split': 3}[precision])
+    if files_on_device and not all(hasattr(m.handle, 'meta_segment_files') for m in models):
+        print("metaseg.files_on_device: true needs the device file coders (meta_segment_files), which the handle in use does not have. Exiting...")
+        sys.exit(2)
     image_paths = get_imgs(inpath)
     print("Reading from: ", inpath)
     t0 = time.perf_counter()
     stats = {}
     rec = run(inpath, models if workers > 1 else model, image_paths, rank, world, batch_images=int(var.get('batch_images', 8)),
               io_threads=var.get('io_threads'), stats=stats, resume=bool(var.get('resume', False)), emit_probs=emit_probs,
-              pinned_mb=int(var.get('pinned_mb', 2048)))
+              pinned_mb=int(var.get('pinned_mb', 2048)), files_on_device=files_on_device)
     failed = finish(inpath, image_paths, rec, rank, seconds=time.perf_counter() - t0, gpu_seconds=stats.get('gpu_seconds', 0.0))
     if native:
         dist.native_close(os.environ['ECSEG_RDZV'], rank)          # (the all-gather was the last thing every rank waited for)

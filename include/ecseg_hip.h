@@ -47,6 +47,8 @@ extern "C" {
 /* (still 5 - additive: ecseg_fish_render, the three colour files of stat_fish for 3- and 4-channel images; nothing existing changed.) */
 /* (still 5 - additive: ecseg_tiff_encode_bound, ecseg_tiff_encode and ecseg_fish_render_tiff, stat_fish's LZW TIFF files encoded on the
  * device; nothing existing changed.) */
+/* (still 5 - additive: ecseg_png_labels_encode, ecseg_meta_segment_files with ecseg_get_file_timings, and ecseg_png_labels_stream_size:
+ * `make metaseg`'s dapi TIFFs and label PNGs encoded on the device; nothing existing changed.) */
 #define ECSEG_ABI_VERSION 5
 
 #define ECSEG_OK             0
@@ -400,6 +402,30 @@ int ecseg_fish_render_tiff(ecseg_ctx* h, const uint8_t* img, int H, int W, int C
                            int n_probe, const uint8_t* boundaries, uint8_t* const* files, long long file_cap, long long* file_bytes,
                            uint8_t* original, uint8_t* with_segmentation, uint8_t* lsq);
 
+/* ---- label PNG files encoded on the device ----------------------------------------------------------------------------------- */
+/* The file ecseg_png_write_labels would write for each of n_img label images, byte for byte (signature, IHDR, one IDAT, IEND), as
+ * file images in memory (csrc/png_kernels.hip: the runs of every scan line are counted on the device, the Huffman code is built
+ * on the host from the 68 counts by the host writer's own functions, the device writes the bits and the Adler-32; the chunk
+ * CRCs are the host's).  labels: (n_img, H, W) uint8 in host memory, uploaded by the call; values above 3 count as 3.  files[i]:
+ * room for file_cap bytes.  A file that fits receives its bytes and file_bytes[i] = its length; one that does not is not
+ * produced - file_bytes[i] = -(the bytes it needs), nothing of it is written, the call still returns ECSEG_OK and the other
+ * files are whole.  One synchronous call, scratch from the handle's arenas; device time of the kernels in ECSEG_T_COUNT.
+ * ECSEG_E_INVALID: a null pointer (n_img > 0), H or W < 1, W >= 2^30, n_img < 0 or >= 65536, file_cap < 1. */
+int ecseg_png_labels_encode(ecseg_ctx* h, const uint8_t* labels, int n_img, int H, int W, uint8_t* const* files, long long file_cap,
+                            long long* file_bytes);
+/* ecseg_meta_segment plus the two files `make metaseg` writes per image, as file images: dapi_files[i] receives what
+ * ecseg_tiff_write_gray8(gray_i, invert = 1) writes, png_files[i] what ecseg_png_write_labels(labels_post_i) writes, byte for
+ * byte.  The dapi strips of the whole batch are encoded on the second stream as soon as the pre-processing is done, under the
+ * U-Net; the PNGs behind the clean-up.  Capacities and lengths follow ecseg_png_labels_encode's protocol for both kinds of file
+ * (a file that does not fit: its *_bytes[i] = -(the bytes it needs), the caller writes it from gray_out / labels_post).
+ * labels_post, n_ec and tie_risk are ecseg_meta_segment's; gray_out may be null.  Argument errors are ecseg_meta_segment's, and a
+ * null file table or buffer, a capacity below 1, 65536 images or more.  ecseg_get_file_timings: ms_out[0] the device time of the
+ * last call's dapi encode (as it ran beside the U-Net), ms_out[1] that of its PNG kernels. */
+int ecseg_meta_segment_files(ecseg_ctx* h, const void* img, int n_img, int H, int W, int C, int bytes_per_sample, uint8_t* const* dapi_files,
+                             long long dapi_cap, long long* dapi_bytes, uint8_t* const* png_files, long long png_cap, long long* png_bytes,
+                             uint8_t* gray_out, uint8_t* labels_post, int32_t* n_ec, int32_t* tie_risk);
+int ecseg_get_file_timings(ecseg_ctx* h, float* ms_out /* [2] */);
+
 /* ---- the min-cut nucleus splitter: a batch of grid max-flows (src/max_flow_binary_mask.py:59-116) ------------------------- */
 /* Replaces get_graph + max_flow + partition_min_cut (:59-116) for a BATCH of independent tasks; segment_min_cut's recursion
  * (:119-140) stays with the caller, who sends all tasks of one recursion depth over all nuclei of an image in one call.
@@ -590,6 +616,9 @@ long long ecseg_lzw_encode(const uint8_t* src, long long n, uint8_t* dst, long l
 int ecseg_npy_write_i64(const char* path, const uint8_t* labels, int H, int W);
 /* plt.imsave(labels/<stem>.png, I, cmap=ListedColormap([4 colours]), vmin=0, vmax=4) (src/metaseg.py:47-52): RGBA. */
 int ecseg_png_write_labels(const char* path, const uint8_t* labels, int H, int W);
+/* The zlib stream of that file: *stream_bytes its length as written, *formula_bytes the length worked out from the 68 token counts
+ * before a bit is written (what ecseg_png_labels_encode sizes its device buffer by): always equal. */
+int ecseg_png_labels_stream_size(const uint8_t* labels, int H, int W, long long* formula_bytes, long long* stream_bytes);
 /* 8-bit gray / RGB / RGBA PNG (channels 1 / 3 / 4; zlib level 0..9, or -1: the settings of cv2.imwrite without parameters -
  * SUB filter, Z_BEST_SPEED, Z_RLE strategy): red/ and green/ of split_FISH_channels (src/image_tools.py:136-146). */
 int ecseg_png_write(const char* path, const uint8_t* pixels, int H, int W, int channels, int level);

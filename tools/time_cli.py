@@ -2,7 +2,11 @@
 """User-visible rate of `make metaseg`: N generated 1040x1392 RGB LZW TIFF files in, labels/*.npy + *.png, dapi/*.tif and
 ec_quantification.csv out ("time `make metaseg` on 256 generated files").  Prints one JSON line.
 
-    python tools/time_cli.py [--n 256] [--base 64] [--batch 16] [--io-threads 32] [--keep DIR]
+    python tools/time_cli.py [--n 256] [--base 64] [--batch 16] [--io-threads 32] [--keep DIR] [--files-on-device off|on|alternate]
+
+``--files-on-device on``: the run under the config key ``files_on_device: true`` (dapi TIFFs and label PNGs encoded on the device);
+``alternate``: off, on, off, on in this one process over the same files, each pass reported under ``main_by_key`` with the device
+milliseconds per image of the two file coders, and ``verdict`` = the minimum on above the maximum off.
 """
 import argparse
 import json
@@ -42,6 +46,7 @@ def main():
     ap.add_argument('--weights', default='random', choices=('random', 'smooth'),
                     help="random: seeded random weights (speckled labels: the slowest case for the label PNG coder); smooth: the fitted base-16 "
                          "stand-in for a trained model (tests/golden/smooth_b16_f16.npz: blobs, as real label maps)")
+    ap.add_argument('--files-on-device', default='off', choices=('off', 'on', 'alternate'), help='config key files_on_device; alternate: off, on, off, on in one process')
     ap.add_argument('--warm-one', dest='warm_full', action='store_false', help='warm up with ONE image (rounds 1-4) instead of a full batch per handle')
     a = ap.parse_args()
     from PIL import Image
@@ -96,12 +101,26 @@ def main():
         for mdl in [model] + extra:
             metaseg.run(warm, mdl, utils.get_imgs(warm), batch_images=a.batch, log=lambda *x: None, stats=stats, pinned_mb=a.pinned_mb,
                         pinned_min_images=0)    # (one batch would not start the page-locked pool by itself)
-        cg0 = cgroup_cpu()
-        t0 = time.perf_counter()
-        rec = metaseg.run(inp, [model] + extra if extra else model, utils.get_imgs(inp), batch_images=a.batch, io_threads=a.io_threads, log=lambda *x: None, stats=stats,
-                          pinned_mb=a.pinned_mb)
-        dt = time.perf_counter() - t0
-        cg1 = cgroup_cpu()
+        def one_pass(key):
+            for sub in ('dapi', 'labels'):               # (every pass creates its files: overwriting is slower)
+                shutil.rmtree(os.path.join(inp, sub), ignore_errors=True)
+                os.makedirs(os.path.join(inp, sub))
+            st = {}
+            c0, t0 = cgroup_cpu(), time.perf_counter()
+            r = metaseg.run(inp, [model] + extra if extra else model, utils.get_imgs(inp), batch_images=a.batch, io_threads=a.io_threads,
+                            log=lambda *x: None, stats=st, pinned_mb=a.pinned_mb, files_on_device=key)
+            return r, time.perf_counter() - t0, c0, cgroup_cpu(), st
+
+        by_key = []
+        for key in {'off': (False,), 'on': (True,), 'alternate': (False, True, False, True)}[a.files_on_device]:
+            if key:                                          # (the file coders' arenas and page-locked buffers: first use is not the rate)
+                metaseg.run(warm, model, utils.get_imgs(warm), batch_images=a.batch, log=lambda *x: None, pinned_mb=a.pinned_mb,
+                            pinned_min_images=0, files_on_device=True)
+            rec, dt, cg0, cg1, stats = one_pass(key)
+            by_key.append({'files_on_device': key, 'seconds': round(dt, 3), 'images_per_s': round(a.n / dt, 2),
+                           'cpu_ms_per_image': None if not (cg0 and cg1) else round(1e3 * (cg1['usage_s'] - cg0['usage_s']) / a.n, 2),
+                           'device_ms_per_image': {k[len('device_'):-len('_thread_seconds')]: round(1e3 * v / a.n, 4)
+                                                   for k, v in stats.items() if k.startswith('device_') and k.endswith('_thread_seconds')}})
     finally:
         metaseg.load_model = real_load
     # `make meta_overlay` over the same files (labels/*.npy from the run above): decode + labels in, red / green PNGs +
@@ -115,7 +134,11 @@ def main():
                             stats=ov_stats)
     dt_ov = time.perf_counter() - t0
     out_bytes = sum(os.path.getsize(os.path.join(dp, f)) for dp, _, fs in os.walk(inp) for f in fs) - in_bytes
-    print(json.dumps({'what': '`make metaseg` loop: %d RGB %s TIFF files (1040x1392) -> dapi/*.tif, labels/*.png, labels/*.npy (int64), records'
+    offs = [r['images_per_s'] for r in by_key if not r['files_on_device']]
+    ons = [r['images_per_s'] for r in by_key if r['files_on_device']]
+    print(json.dumps({'files_on_device': a.files_on_device, 'main_by_key': by_key,
+                      'verdict': None if not (offs and ons) else {'off_max': max(offs), 'on_min': min(ons), 'on_wins': min(ons) > max(offs)},
+                      'what': '`make metaseg` loop: %d RGB %s TIFF files (1040x1392) -> dapi/*.tif, labels/*.png, labels/*.npy (int64), records'
                               % (a.n, 'LZW' if a.input_compression == 'tiff_lzw' else 'uncompressed'), 'images': a.n, 'unet_base': a.base, 'weights': a.weights, 'batch_images': a.batch, 'device_workers': a.workers, 'pinned_mb': a.pinned_mb,
                       'pinned_pool': stats.get('pinned_pool'), 'warmup': 'one full batch per handle' if a.warm_full else 'one image',
                       'io_threads': a.io_threads or 'default', 'cpu_count': os.cpu_count(),
