@@ -29,5 +29,13 @@ asan:
 	    ecseg_amd/csrc/host_codec.cpp ecseg_amd/csrc/host_io.cpp tools/asan/codec_fuzz.cpp -lz -o /tmp/ecseg_codec_fuzz
 	/tmp/ecseg_codec_fuzz
 
+# the same for the device TIFF reader: its per-strip routine (csrc/tiff_decode_strip.h) compiled for the host, lanes as a loop, against
+# the host decoder on built-in streams; tests/test_tiff_decode.py runs it on the tests' corpus too
+.PHONY: asan_tiff_decode
+asan_tiff_decode:
+	g++ -std=c++17 -O1 -g -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=all \
+	    ecseg_amd/csrc/host_codec.cpp tools/asan/tiff_decode_fuzz.cpp -o /tmp/ecseg_tiff_decode_fuzz
+	/tmp/ecseg_tiff_decode_fuzz
+
 clean:
 	rm -rf __pycache__ ecseg_amd/csrc/*.o ecseg_amd/libecseg_*.so

@@ -21,7 +21,7 @@ EXPORTS = [
     'ecseg_comm_unique_id', 'ecseg_comm_create', 'ecseg_comm_destroy', 'ecseg_comm_last_error', 'ecseg_allgather_records', 'ecseg_allgather_records_dev',
     'ecseg_npy_write_i64', 'ecseg_png_write_labels', 'ecseg_png_write', 'ecseg_png_write_channel', 'ecseg_npy_label_info', 'ecseg_npy_read_labels_u8', 'ecseg_tiff_write_gray8', 'ecseg_tiff_info', 'ecseg_tiff_read',
     'ecseg_tiff_write_rgb8', 'ecseg_npy_write_i32_as_i64',
-    'ecseg_tiff_encode_bound', 'ecseg_tiff_encode', 'ecseg_fish_render_tiff',
+    'ecseg_tiff_encode_bound', 'ecseg_tiff_encode', 'ecseg_fish_render_tiff', 'ecseg_tiff_decode', 'ecseg_tiff_decode_routes',
     'ecseg_png_labels_encode', 'ecseg_meta_segment_files', 'ecseg_get_file_timings', 'ecseg_png_labels_stream_size',
 ]
 
@@ -127,6 +127,8 @@ def load_library():
     lib.ecseg_tiff_encode_bound.argtypes = [i32, i32, i32]; lib.ecseg_tiff_encode_bound.restype = C.c_longlong
     lib.ecseg_tiff_encode.argtypes = [vp, u8p, i32, i32, i32, i32, vp, C.c_longlong, C.POINTER(C.c_longlong)]
     lib.ecseg_fish_render_tiff.argtypes = [vp, u8p, i32, i32, i32, vp, u8p, i32, u8p, C.POINTER(vp), C.c_longlong, C.POINTER(C.c_longlong), vp, vp, vp]
+    lib.ecseg_tiff_decode.argtypes = [vp, vp, C.c_longlong, vp, C.c_longlong, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
+    lib.ecseg_tiff_decode_routes.argtypes = [vp, C.c_longlong]
     lib.ecseg_min_cut.argtypes = [vp, vp, C.c_longlong, vp, i32, i32, vp, vp]
     lib.ecseg_nuset_forward.argtypes = [vp, vp, i32, i32, i32, i32, vp]
     lib.ecseg_rpn_proposals.argtypes = [vp, vp, vp, i32, i32, i32, vp, i32, i32, i32, C.c_float, i32, i32, C.POINTER(C.c_int32), vp, vp, vp]
@@ -673,6 +675,26 @@ class Handle:
         n = C.c_longlong()
         self._check(self.lib.ecseg_tiff_encode(self.h, _ptr(im), H, W, spp, int(bool(invert)), _ptr(out), cap, C.byref(n)), 'ecseg_tiff_encode')
         return out[:n.value].tobytes()
+
+    def tiff_decode(self, data):
+        """The bytes of a TIFF file -> what ``image_io.read_tiff`` returns for that file, (H, W) or (H, W, spp) uint8 / uint16, with
+        every strip decoded on the device (ecseg_tiff_decode); None for a file that is left to the host readers (ECSEG_E_UNSUPPORTED:
+        tiles, BigTIFF, PackBits, Deflate).  Whether a file is worth sending here is ``image_io.imread``'s question (ecseg_tiff_decode_routes).  A corrupt file raises, with code -1."""
+        buf = np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else _u8(data).reshape(-1)
+        if not buf.size:
+            raise ValueError('tiff_decode takes the bytes of a file')
+        H, W, spp, bits = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        shape = (C.byref(H), C.byref(W), C.byref(spp), C.byref(bits))
+        rc = self.lib.ecseg_tiff_decode(self.h, _ptr(buf), buf.size, None, 0, *shape)
+        if rc == E_UNSUPPORTED:
+            return None
+        self._check(rc, 'ecseg_tiff_decode')
+        out = np.empty((H.value, W.value, spp.value), np.uint8 if bits.value == 8 else np.uint16)
+        rc = self.lib.ecseg_tiff_decode(self.h, _ptr(buf), buf.size, _ptr(out), out.nbytes, *shape)
+        if rc == E_UNSUPPORTED:
+            return None
+        self._check(rc, 'ecseg_tiff_decode')
+        return out[..., 0] if spp.value == 1 else out
 
     def fish_render_tiff(self, img, channels, thresholded, boundaries, want_rasters=False):
         """``fish_render``'s inputs -> the bytes of the three files ``image_io.write_tiff_rgb8`` writes for its rasters (``_original``,

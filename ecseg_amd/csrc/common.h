@@ -360,6 +360,22 @@ inline TiffEncodeBufs tiff_encode_bufs(Carver& c, int H, int W, int spp, int n_f
 struct TiffSources { const uint8_t* img[3]; size_t stride; };
 hipError_t run_tiff_encode(const TiffSources& src, int n_files, int H, int W, int spp, int invert, const TiffEncodeBufs& b, hipStream_t s);
 
+// ---- launcher implemented in tiff_decode_kernels.hip (the strips of ecseg_tiff_read, host_io.cpp) -------------------------------
+// Device buffers of one decode: file: the file image as uploaded; offs / cnts: the first n_table entries of its strip tables (the
+// strips the image has rows for); raster: H lines; status: one word per strip of the image (nstrips = ceil(H / rps) >= n_table).
+struct TiffDecodeBufs { uint8_t* file; uint32_t* offs; uint32_t* cnts; uint8_t* raster; uint32_t* status; int n_table, nstrips; };
+inline TiffDecodeBufs tiff_decode_bufs(Carver& c, size_t n_bytes, int n_table, size_t raster_bytes, int nstrips) {
+    TiffDecodeBufs b;
+    b.n_table = n_table; b.nstrips = nstrips;
+    b.file = c.take<uint8_t>(n_bytes); b.offs = c.take<uint32_t>((size_t)n_table); b.cnts = c.take<uint32_t>((size_t)n_table);
+    b.raster = c.take<uint8_t>(raster_bytes); b.status = c.take<uint32_t>((size_t)nstrips);
+    return b;
+}
+// Decodes the strips (lzw: LZW, else uncompressed) into b.raster and b.status (0, or 1: corrupt), then swaps 16-bit samples
+// (`swap`) and undoes the horizontal predictor (`predictor`) row by row.  A strip holds less than 2^31 bytes.
+hipError_t run_tiff_decode(const TiffDecodeBufs& b, unsigned long long n_bytes, int H, int W, int spp, int bytes_per_sample, int rps, int lzw,
+                           int swap, int predictor, hipStream_t s);
+
 // ---- launchers implemented in png_kernels.hip (the label PNG of ecseg_png_write_labels, host_io.cpp) ------------------------------
 // The token counts of one image, as deflate_labels' pass 1 takes them: [0..3] runs per colour, [4 + m] matches of 4 m bytes for
 // m = 1..64 (m = 64 with the whole-64 parts of long runs; m = 0 counts the runs without a remainder match and is not used).

@@ -1,10 +1,11 @@
 // The one-call drivers: each uploads its inputs, runs one family of kernels on the main stream and downloads the results
-// (u16_to_u8, stitch_argmax, meta_inference, the counts, overlay, the interSeg regions / crops, the FISH distances, the FISH spots and their three colour files, TIFF files encoded on the device, the min-cut tasks, NuSeT's mask and proposals, its marker watershed for one image and for a batch, clean-up and rescale).
+// (u16_to_u8, stitch_argmax, meta_inference, the counts, overlay, the interSeg regions / crops, the FISH distances, the FISH spots and their three colour files, TIFF files encoded and decoded on the device, the min-cut tasks, NuSeT's mask and proposals, its marker watershed for one image and for a batch, clean-up and rescale).
 #include <cstring>
 
 #include "ctx.h"
 
 #include "png_label_code.h"
+#include "tiff_parse.h"
 
 using namespace ecseg;
 
@@ -573,6 +574,55 @@ int ecseg_fish_render_tiff(ecseg_ctx* h, const uint8_t* img, int H, int W, int C
     if (lsq) HIP_TRY(h, hipMemcpyAsync(lsq, b.lsq, px * 3, hipMemcpyDeviceToHost, s));
     if ((rc = tiff_collect(h, "fish_render_tiff", 3, H, W, 3, t, files, file_cap, file_bytes, true))) return rc;
     h->stage_ms[ECSEG_T_COUNT] = stage_elapsed(h->ev[0], h->ev[1]);
+    return ECSEG_OK;
+}
+
+// ---- TIFF files decoded on the device (tiff_decode_kernels.hip; the host reader is ecseg_tiff_read, host_io.cpp) -------------------
+int ecseg_tiff_decode_routes(const uint8_t* file, long long n_bytes) {
+    TiffInfo t;
+    return file && n_bytes >= 0 && parse_tiff(file, (size_t)n_bytes, &t) == ECSEG_OK && tiff_goes_to_device(t) ? 1 : 0;
+}
+
+int ecseg_tiff_decode(ecseg_ctx* h, const uint8_t* file, long long n_bytes, void* dst, long long dst_bytes, int* H, int* W, int* samples_per_pixel,
+                      int* bits_per_sample) {
+    if (!h) return ECSEG_E_INVALID;
+    drop_sent_ahead(h);
+    if (!file || n_bytes < 0 || !H || !W || !samples_per_pixel || !bits_per_sample || (dst && dst_bytes < 0))
+        return fail(h, ECSEG_E_INVALID, "tiff_decode: bad arguments");
+    for (float& v : h->stage_ms) v = 0.f;
+    TiffInfo t;
+    const size_t n = (size_t)n_bytes;
+    int rc = parse_tiff(file, n, &t);
+    if (rc == ECSEG_E_UNSUPPORTED) return fail(h, rc, "tiff_decode: a layout the native readers leave to the Python reader");
+    if (rc != ECSEG_OK) return fail(h, rc, "tiff_decode: not a TIFF file, or a corrupt one");
+    *H = (int)t.H; *W = (int)t.W; *samples_per_pixel = (int)t.spp; *bits_per_sample = (int)t.bits;
+    const unsigned long long bpp = t.bits / 8, line = (unsigned long long)t.W * t.spp * bpp, total = line * t.H;
+    if (t.comp != 1 && t.comp != 5) return fail(h, ECSEG_E_UNSUPPORTED, "tiff_decode: Deflate strips are decoded by the host reader");
+    if ((unsigned long long)t.rps * line >= (1ull << 31) || total >= (1ull << 40))
+        return fail(h, ECSEG_E_UNSUPPORTED, "tiff_decode: strips of 2 GiB or more, or an image of 1 TiB or more");
+    if (!dst) return ECSEG_OK;
+    if ((unsigned long long)dst_bytes < total) return fail(h, ECSEG_E_INVALID, "tiff_decode: the destination holds fewer bytes than the image");
+    const size_t nstrips = ((size_t)t.H + t.rps - 1) / t.rps, n_table = std::min(t.off.size(), nstrips);
+    for (size_t k = 0; k < n_table; ++k)
+        if (t.off[k] > n) return fail(h, ECSEG_E_INVALID, "tiff_decode: strip " + std::to_string(k) + " starts behind the end of the file");
+    HIP_TRY(h, hipSetDevice(h->device));
+    TiffDecodeBufs b{};
+    if ((rc = lay_out(h, h->call_arena, [&](Carver& c) { b = tiff_decode_bufs(c, n, (int)n_table, (size_t)total, (int)nstrips); }))) return rc;
+    hipStream_t s = h->stream;
+    HIP_TRY(h, hipMemcpyAsync(b.file, file, n, hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(b.offs, t.off.data(), n_table * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(b.cnts, t.cnt.data(), n_table * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipEventRecord(h->ev[0], s));
+    HIP_TRY(h, run_tiff_decode(b, (unsigned long long)n, (int)t.H, (int)t.W, (int)t.spp, (int)bpp, (int)t.rps, t.comp == 5, bpp == 2 && !t.le, t.pred == 2, s));
+    HIP_TRY(h, hipEventRecord(h->ev[1], s));
+    std::vector<uint32_t> status(nstrips);
+    HIP_TRY(h, hipMemcpyAsync(status.data(), b.status, nstrips * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    h->stage_ms[ECSEG_T_COUNT] = stage_elapsed(h->ev[0], h->ev[1]);
+    for (size_t k = 0; k < nstrips; ++k)
+        if (status[k]) return fail(h, ECSEG_E_INVALID, "tiff_decode: strip " + std::to_string(k) + " holds a corrupt LZW stream");
+    HIP_TRY(h, hipMemcpyAsync(dst, b.raster, (size_t)total, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
     return ECSEG_OK;
 }
 

@@ -24,6 +24,7 @@
 #include "../../include/ecseg_hip.h"
 #include "png_label_code.h"
 #include "tiff_frame.h"
+#include "tiff_parse.h"
 
 namespace {
 
@@ -378,12 +379,6 @@ struct Reader {
     }
 };
 
-struct TiffInfo {
-    uint32_t W = 0, H = 0, bits = 8, spp = 1, comp = 1, planar = 1, pred = 1, fmt = 1, rps = 0;
-    std::vector<uint32_t> off, cnt;
-    bool le = true;
-};
-
 // values of one IFD entry (types BYTE / SHORT / LONG only) -> vector; ECSEG_E_INVALID when the entry is malformed,
 // ECSEG_E_UNSUPPORTED for a structurally valid entry of another TIFF 6.0 / BigTIFF type (RATIONAL, LONG8, ...): the Python
 // reader decodes those (image_io._TYPE_FMT)
@@ -400,8 +395,11 @@ int entry_values(const Reader& r, size_t e, std::vector<uint32_t>* out) {
     return ECSEG_OK;
 }
 
-// ECSEG_OK, ECSEG_E_UNSUPPORTED (a valid layout this reader leaves to the Python one) or ECSEG_E_INVALID (corrupt)
-int parse_tiff(const uint8_t* buf, size_t n, TiffInfo* t) {
+}  // namespace
+
+// ECSEG_OK, ECSEG_E_UNSUPPORTED (a valid layout this reader leaves to the Python one) or ECSEG_E_INVALID (corrupt); TiffInfo and
+// the declaration are in tiff_parse.h, for the device reader's driver
+int ecseg::parse_tiff(const uint8_t* buf, size_t n, TiffInfo* t) {
     if (n < 8) return ECSEG_E_INVALID;
     if (buf[0] == 'I' && buf[1] == 'I') t->le = true;
     else if (buf[0] == 'M' && buf[1] == 'M') t->le = false;
@@ -453,6 +451,8 @@ int parse_tiff(const uint8_t* buf, size_t n, TiffInfo* t) {
     if (t->rps == 0 || t->rps > t->H) t->rps = t->H;
     return ECSEG_OK;
 }
+
+namespace {
 
 bool read_file(const char* path, std::vector<uint8_t>* out) {
     File f(path, "rb");

@@ -1,0 +1,135 @@
+// One LZW strip decoded by one wave: the routine of tiff_lzw_unstrip_kernel (tiff_decode_kernels.hip), written so that the host
+// compiler takes it too - tools/asan/tiff_decode_fuzz.cpp runs it under ASan + UBSan against ecseg_lzw_decode (host_codec.cpp),
+// which is its specification, tolerances included.  Under hipcc a lane is a thread of the wave, td_first is a read of lane 0 and
+// td_stores_done the fence + barrier that completes the wave's stores; under the host compiler the lanes are a loop, and the other
+// two do nothing.
+//
+// Lane 0 is the decoder, a serial walk over the codes in plain C++ (as lane 0 of the encoder, tiff_kernels.hip); it stores the
+// literals itself.  Every longer string is a copy from the strip's own earlier output (an entry is (offset, length) of an earlier
+// occurrence, as on the host) that all 64 lanes make, 64 bytes per step, straight in the raster: output is not held in LDS, one
+// table epoch of a constant image covers megabytes.  The table (4096 x offset, length: 24 KB) and TD_IN staged bytes of the
+// stream are in LDS.  The table is never cleared: an entry is read only below `next`, as on the host.
+//   Lanes read global bytes that other lanes (and lane 0's literal stores) have written.  The wave keeps a watermark `fenced`: the
+// output offset below which every store is known to have completed.  A copy whose source reaches beyond it first runs
+// td_stores_done (workgroup-scope release + acquire around a barrier, which drains the wave's stores: vmcnt(0)) and moves the
+// watermark to its own destination; a copy from older output - most of them: an entry points anywhere into its epoch - pays nothing.
+//   An overlapping copy (KwKwK: the previous string + its own first byte, distance = the previous length) never reads what it
+// writes: byte k >= distance is byte k - distance of the source, which is byte 0.
+//   Every index is checked where it is used: into the staged bytes against the staged count, into the stream against `have`,
+// into the table by the code's 12 bits and `next`, into the output against `want`.
+#pragma once
+#include <stdint.h>
+
+#ifdef __HIPCC__
+#define TD_FN __device__ __forceinline__
+#define TD_FOR_LANES(lane) for (int lane = (int)threadIdx.x, td_once_ = 1; td_once_; td_once_ = 0)
+#define TD_CONTROL_LANE if (threadIdx.x == 0)
+TD_FN uint32_t td_first(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+TD_FN void td_stores_done() { __syncthreads(); }
+#else
+#define TD_FN inline
+#define TD_FOR_LANES(lane) for (int lane = 0; lane < 64; ++lane)
+#define TD_CONTROL_LANE
+inline uint32_t td_first(uint32_t v) { return v; }
+inline void td_stores_done() {}
+#endif
+
+namespace ecseg {
+
+constexpr uint32_t TD_IN = 1024;                             // staged bytes of the code stream
+struct TdLds { uint32_t pos[4096]; uint16_t len[4096]; uint8_t in[TD_IN]; };   // (a string is at most 3839 bytes: one more than an earlier one per entry)
+
+enum { TD_REFILL = 0, TD_COPY = 1, TD_END = 2, TD_CORRUPT = 3 };
+// lane 0's registers: the host decoder's state (careful form) and the copy it asks the wave for
+struct TdWalk { uint32_t racc; int nbits, width, next, old; uint32_t ipos, out, old_pos, old_len, c_src, c_len, c_dst; int full; };
+
+// Walks the codes until the wave has something to do: stage the next bytes (TD_REFILL), copy a string (TD_COPY), or stop.  The staged
+// bytes are those of [c0, c0 + cn) of the stream.
+TD_FN int td_walk(TdWalk& s, TdLds& L, uint32_t have, uint32_t c0, uint32_t cn, uint8_t* dst, uint32_t want) {
+    if (s.full) return TD_END;                               // the copy before filled the destination
+    for (;;) {
+        while (s.nbits < s.width) {
+            if (s.ipos >= have) return TD_END;               // stream ended without EOI: accept what we have
+            if (s.ipos - c0 >= cn) return TD_REFILL;         // (unsigned: an ipos below c0 asks for a refill too)
+            s.racc = (s.racc << 8) | L.in[s.ipos - c0];
+            ++s.ipos;
+            s.nbits += 8;
+        }
+        const int code = (int)((s.racc >> (s.nbits - s.width)) & ((1u << s.width) - 1));
+        s.nbits -= s.width;
+        if (code == 257) return TD_END;
+        if (code == 256) { s.next = 258; s.width = 9; s.old = -1; continue; }
+        if (s.old < 0) {                                     // behind a ClearCode, or the first code of a stream without one: a literal, no entry
+            if (code >= 256) return TD_CORRUPT;
+            if (s.out >= want) return TD_END;
+            s.old_pos = s.out; s.old_len = 1; s.old = code;
+            dst[s.out++] = (uint8_t)code;
+            continue;
+        }
+        uint32_t cpos = 0, clen = 1;                         // the string of `code`
+        if (code < s.next) {
+            if (code >= 256) { cpos = L.pos[code]; clen = L.len[code]; }
+        } else if (code == s.next && s.next < 4096) {       // KwKwK: previous string + its own first byte
+            cpos = s.old_pos; clen = s.old_len + 1;
+        } else {
+            return TD_CORRUPT;
+        }
+        const uint32_t start = s.out, room = want - s.out;
+        const uint32_t ncopy = clen <= room ? clen : room;
+        const bool wave = code >= 256 && ncopy > 0;
+        if (code < 256) { if (ncopy) dst[s.out] = (uint8_t)code; }
+        else { s.c_src = cpos; s.c_len = ncopy; s.c_dst = start; }
+        s.out += ncopy;
+        if (s.next < 4096) { L.pos[s.next] = s.old_pos; L.len[s.next] = (uint16_t)(s.old_len + 1); ++s.next; }
+        if (ncopy < clen) {                                  // destination full
+            if (!wave) return TD_END;
+            s.full = 1;
+            return TD_COPY;
+        }
+        s.old = code; s.old_pos = start; s.old_len = clen;
+        if (s.next >= (1 << s.width) - 1 && s.width < 12) ++s.width;     // early change
+        if (wave) return TD_COPY;
+    }
+}
+
+// src: the strip's `have` bytes; dst: its `want` bytes of the raster (want below 2^31).  Returns 0, or 1 for a corrupt stream
+// (the same value in every lane); bytes the stream does not give are zero.
+TD_FN uint32_t td_lzw_strip(const uint8_t* src, uint32_t have, uint8_t* dst, uint32_t want, TdLds& L) {
+    TdWalk s{0u, 0, 9, 258, -1, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0};
+    uint32_t c0 = 0, cn = 0, fenced = 0;
+    int cmd;
+    for (;;) {
+        cmd = TD_END;
+        TD_CONTROL_LANE { cmd = td_walk(s, L, have, c0, cn, dst, want); }
+        cmd = (int)td_first((uint32_t)cmd);
+        if (cmd == TD_REFILL) {
+            c0 = td_first(s.ipos);
+            cn = c0 < have ? (have - c0 < TD_IN ? have - c0 : TD_IN) : 0u;
+            TD_FOR_LANES(lane) {
+                for (uint32_t k = (uint32_t)lane; k < cn; k += 64) L.in[k] = src[c0 + k];
+            }
+            td_stores_done();                                // (the barrier the staged bytes need completes the output stores too)
+            fenced = td_first(s.out);
+        } else if (cmd == TD_COPY) {
+            const uint32_t c_src = td_first(s.c_src), c_len = td_first(s.c_len), c_dst = td_first(s.c_dst);
+            const uint32_t dist = c_dst - c_src;             // >= 1: a string lies before the place it is copied to
+            const uint32_t reach = c_len < dist ? c_len : dist;
+            if (c_src + reach > fenced) { td_stores_done(); fenced = c_dst; }
+            TD_FOR_LANES(lane) {
+                for (uint32_t k = (uint32_t)lane; k < c_len; k += 64) {
+                    const uint32_t from = c_src + (k >= dist ? k - dist : k), to = c_dst + k;
+                    if (from < want && to < want) dst[to] = dst[from];
+                }
+            }
+        } else {
+            break;
+        }
+    }
+    const uint32_t got = td_first(s.out);
+    TD_FOR_LANES(lane) {
+        for (uint32_t k = got + (uint32_t)lane; k < want; k += 64) dst[k] = 0;
+    }
+    return cmd == TD_CORRUPT ? 1u : 0u;
+}
+
+}  // namespace ecseg

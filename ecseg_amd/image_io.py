@@ -224,10 +224,33 @@ def image_shape(path):
     return read_tiff(path).shape
 
 
-def imread(path):
-    """``skimage.io.imread`` stand-in for the inputs ``get_imgs`` globs (``*.tif`` and ``*.npy``, src/utils.py:105-110)."""
+def tiff_goes_to_device(data):
+    """The routing rule of the device reader (csrc/tiff_parse.h, the one place that states it) on the bytes of a file."""
+    buf = np.frombuffer(data, np.uint8)
+    return bool(buf.size) and load_library().ecseg_tiff_decode_routes(buf.ctypes.data_as(C.c_void_p), buf.size) == 1
+
+
+def imread(path, handle=None):
+    """``skimage.io.imread`` stand-in for the inputs ``get_imgs`` globs (``*.tif`` and ``*.npy``, src/utils.py:105-110).
+    ``handle``: anything with ``Handle.tiff_decode``: a ``.tif`` that the routing rule sends to the device (ecseg_tiff_decode_routes:
+    LZW files of many strips) is decoded there, and by the readers of this module when that returns None (a layout it leaves to them)
+    or finds the file corrupt or unreadable, so that the error raised is theirs."""
     if str(path).lower().endswith('.npy'):
         return np.load(path)
+    if handle is not None and hasattr(handle, 'tiff_decode') and str(path).lower().endswith(('.tif', '.tiff')):
+        a = None
+        try:
+            with open(path, 'rb') as f:
+                data = f.read()
+            if tiff_goes_to_device(data):
+                a = handle.tiff_decode(data)
+        except OSError:
+            pass
+        except RuntimeError as e:
+            if getattr(e, 'code', None) != -1:
+                raise
+        if a is not None:
+            return a
     return read_tiff(path)
 
 

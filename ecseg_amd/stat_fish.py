@@ -223,12 +223,13 @@ def render(img, channels, thresholded, boundaries):
     return original, with_segmentation(original, boundaries, 1), np.stack(lsq[::-1], axis=-1)
 
 
-def read_image(path, handle, max_probes=2):
+def read_image(path, handle, max_probes=2, tiff_read_on_device=False):
     """-> ((H, W, C) uint8 image, its (blue, green, red[, aqua]) channel indices) (src/stat_fish.py:206-212).  C is 3, or 4 for a
-    four-channel ``.npy`` when ``max_probes`` (the entries of ``color_sensitivity``) is at least 3."""
+    four-channel ``.npy`` when ``max_probes`` (the entries of ``color_sensitivity``) is at least 3.  ``tiff_read_on_device``: a TIFF's
+    strips are decoded by ``handle.tiff_decode`` (``image_io.imread(path, handle=handle)``)."""
     from . import image_io
     try:
-        I = image_io.imread(path)
+        I = image_io.imread(path, handle=handle if tiff_read_on_device else None)
     except Exception as e:
         raise ImageError('cannot be read (%s)' % e)
     is_npy = path.lower().endswith('.npy')
@@ -257,12 +258,13 @@ def read_image(path, handle, max_probes=2):
     return np.ascontiguousarray(I), (2, 1, 0)
 
 
-def read_mask(path):
+def read_mask(path, handle=None):
+    """``handle``: the mask's strips are decoded by ``handle.tiff_decode`` (config key ``tiff_read_on_device``)."""
     from . import image_io
     if not os.path.exists(path):
         raise ImageError('has no nucleus mask %s' % path)
     try:
-        m = image_io.imread(path)
+        m = image_io.imread(path, handle=handle)
     except Exception as e:
         raise ImageError('nucleus mask %s cannot be read (%s)' % (path, e))
     if m.ndim == 3 and m.shape[2] == 1:
@@ -272,7 +274,8 @@ def read_mask(path):
     return (m != 0).astype(np.uint8) * np.uint8(255)
 
 
-def process_image(path, mask_path, out_root, params, scale, handle, stats=None, use_min_cut=False, segment=None, tiff_on_device=False):
+def process_image(path, mask_path, out_root, params, scale, handle, stats=None, use_min_cut=False, segment=None, tiff_on_device=False,
+                  tiff_read_on_device=False):
     """One image of src/stat_fish.py:199-308 -> (CSV rows, the scale that was used); the rows of a four-channel image carry the aqua
     fields of ``csv_columns(3)``, and ``stats['probes']`` becomes 3 once such an image was seen (it may have no nucleus and no row).  The three colour files come from ``handle.fish_render`` when the handle has it, else from
     ``render``, which writes the same bytes.  ``use_min_cut`` (:221-224): the label map comes
@@ -280,14 +283,16 @@ def process_image(path, mask_path, out_root, params, scale, handle, stats=None, 
     (config key ``nuset_weights``): the mask is ``segment(blue channel)`` (:212-214) instead of the file ``mask_path``.
     ``tiff_on_device`` (the config key of that name): every TIFF of the image is LZW-encoded on the device - the colour files by
     ``handle.fish_render_tiff``, which renders them there too, the mask and the min-cut picture by ``handle.tiff_encode`` - and
-    reaches the disk as the file image these return; the bytes are those of the host writers."""
+    reaches the disk as the file image these return; the bytes are those of the host writers.  ``tiff_read_on_device`` (the config key
+    of that name): the image and the mask are read with ``handle.tiff_decode`` where the device reader takes the file; the samples are
+    those of the host readers."""
     import time
     from . import image_io
     t0 = time.perf_counter()
     img_name = os.path.basename(path)[:-4]
-    I, channels = read_image(path, handle, len(params['color_sensitivity']))
+    I, channels = read_image(path, handle, len(params['color_sensitivity']), tiff_read_on_device)
     blue = channels[0]
-    mask = read_mask(mask_path) if segment is None else segment(I[:, :, blue])
+    mask = read_mask(mask_path, handle if tiff_read_on_device else None) if segment is None else segment(I[:, :, blue])
     imheight, imwidth = mask.shape
     I = np.ascontiguousarray(I[:imheight, :imwidth])
     mask = np.ascontiguousarray(mask[:I.shape[0], :I.shape[1]])
@@ -470,7 +475,8 @@ def main(argv=None, handle=None):
     """``make stat_fish``.  Like the reference's ``main`` it takes everything from section ``stat_fish`` of ``config.yaml`` in
     the working directory; ``argv`` is accepted for the shim's sake and not read.  ``handle`` is an injection point for tests and
     tools (anything with ``Handle.ccl_labels``, ``fish_spots`` and ``u16_to_u8``, and ``min_cut`` for ``use_min_cut: True``; ``fish_render``
-    is used when it is there, ``tiff_encode`` and ``fish_render_tiff`` are needed for ``tiff_on_device: true``); without it the call opens a handle on device 0
+    is used when it is there, ``tiff_encode`` and ``fish_render_tiff`` are needed for ``tiff_on_device: true``, ``tiff_decode`` for
+    ``tiff_read_on_device: true``); without it the call opens a handle on device 0
     and closes it at the end."""
     import yaml
     from . import csvio
@@ -507,6 +513,12 @@ def main(argv=None, handle=None):
         if tiff_on_device and handle is not None and not all(hasattr(handle, m) for m in ('tiff_encode', 'fish_render_tiff')):
             raise ConfigError('tiff_on_device: true needs the device TIFF encoder (tiff_encode, fish_render_tiff), which the handle in use '
                               'does not have; only tiff_on_device: false works on it')
+        tiff_read_on_device = var.get('tiff_read_on_device', False)
+        if not isinstance(tiff_read_on_device, bool):
+            raise ConfigError('tiff_read_on_device must be true or false (true: the strips of every input TIFF are decoded on the device)')
+        if tiff_read_on_device and handle is not None and not hasattr(handle, 'tiff_decode'):
+            raise ConfigError('tiff_read_on_device: true needs the device TIFF reader (tiff_decode), which the handle in use '
+                              'does not have; only tiff_read_on_device: false works on it')
         if segmenter is None and not os.path.isdir(masks):
             raise ConfigError('The folder of nucleus masks %s does not exist (config key masks): it holds one 8-bit <name>.tif per '
                               'image, non-zero = nucleus' % masks)
@@ -551,7 +563,7 @@ def main(argv=None, handle=None):
                 blues = []
                 for p in chunk:
                     try:
-                        I, channels = read_image(p, handle, len(params['color_sensitivity']))
+                        I, channels = read_image(p, handle, len(params['color_sensitivity']), tiff_read_on_device)
                         blues.append((p, np.ascontiguousarray(I[:, :, channels[0]])))
                     except ImageError as e:
                         hooks[p] = handed_in(e)              # (process_image meets and reports it at the image's turn)
@@ -563,7 +575,8 @@ def main(argv=None, handle=None):
                 print("Processing image: ", p)
                 try:
                     img_rows, scale = process_image(p, os.path.join(masks, os.path.basename(p)[:-4] + '.tif'), out_root, params, scale, handle,
-                                                     stats=seen, use_min_cut=use_min_cut, segment=hooks.get(p), tiff_on_device=tiff_on_device)
+                                                     stats=seen, use_min_cut=use_min_cut, segment=hooks.get(p), tiff_on_device=tiff_on_device,
+                                                     tiff_read_on_device=tiff_read_on_device)
                     rows += img_rows
                 except ImageError as e:
                     print(p, '-', e)

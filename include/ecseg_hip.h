@@ -49,6 +49,8 @@ extern "C" {
  * device; nothing existing changed.) */
 /* (still 5 - additive: ecseg_png_labels_encode, ecseg_meta_segment_files with ecseg_get_file_timings, and ecseg_png_labels_stream_size:
  * `make metaseg`'s dapi TIFFs and label PNGs encoded on the device; nothing existing changed.) */
+/* (still 5 - additive: ecseg_tiff_decode and ecseg_tiff_decode_routes, stat_fish's input TIFFs decoded on the device; nothing existing
+ * changed.) */
 #define ECSEG_ABI_VERSION 5
 
 #define ECSEG_OK             0
@@ -401,6 +403,26 @@ int ecseg_tiff_encode(ecseg_ctx* h, const uint8_t* img, int H, int W, int spp, i
 int ecseg_fish_render_tiff(ecseg_ctx* h, const uint8_t* img, int H, int W, int C, const int32_t* channels, const uint8_t* thresholded,
                            int n_probe, const uint8_t* boundaries, uint8_t* const* files, long long file_cap, long long* file_bytes,
                            uint8_t* original, uint8_t* with_segmentation, uint8_t* lsq);
+
+/* ---- TIFF files decoded on the device ---------------------------------------------------------------------------------------- */
+/* skimage.io.imread of a baseline TIFF (src/utils.py:110) from a file image in memory, with every strip decoded on the device
+ * (csrc/tiff_decode_kernels.hip: one wave per LZW strip, then byte order and the horizontal predictor row by row): what
+ * ecseg_tiff_info plus ecseg_tiff_read return for the same bytes - ECSEG_OK, the shape in *H, *W, *samples_per_pixel,
+ * *bits_per_sample and the samples in dst as native-endian (H, W, spp), strips that end early or are missing zero-filled - or
+ * ECSEG_E_INVALID (not a TIFF, a corrupt IFD, a strip offset behind the file, a corrupt LZW stream in any strip: dst is not
+ * written).  ECSEG_E_UNSUPPORTED: everything ecseg_tiff_info leaves to the Python reader, and Deflate strips, which stay on the
+ * host (also strips of 2 GiB or more); the shape is reported then too
+ * when the file has one.  dst == NULL: only the shape (and the ECSEG_E_UNSUPPORTED verdict).  dst_bytes below H * W * spp *
+ * bits / 8: ECSEG_E_INVALID with nothing written.  file: n_bytes of host memory, uploaded by the call; one synchronous call,
+ * scratch (file image, strip tables, raster, status words) from the handle's call arena; device time of the kernels in
+ * ECSEG_T_COUNT. */
+int ecseg_tiff_decode(ecseg_ctx* h, const uint8_t* file, long long n_bytes, void* dst, long long dst_bytes,
+                      int* H, int* W, int* samples_per_pixel, int* bits_per_sample);
+/* The one rule that says whether a file is worth sending to ecseg_tiff_decode (image_io.imread(path, handle) asks it): 1 for an
+ * LZW file of at least 1040 strips, 0 for everything else, unreadable files included.  A strip is one serial stream on one wave,
+ * so the device is faster than a host core only where many strips decode at once; the measurement behind the threshold is in
+ * DESIGN.md 5.9.  No device work. */
+int ecseg_tiff_decode_routes(const uint8_t* file, long long n_bytes);
 
 /* ---- label PNG files encoded on the device ----------------------------------------------------------------------------------- */
 /* The file ecseg_png_write_labels would write for each of n_img label images, byte for byte (signature, IHDR, one IDAT, IEND), as

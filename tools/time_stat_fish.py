@@ -1,7 +1,7 @@
 """Timing of ``make stat_fish`` on synthetic full-size scenes.
 
     python tools/time_stat_fish.py [--images 16] [--reps 5] [--cpu-workers 16] [--channels 4] [--main-passes 3]
-                                   [--tiff-on-device off|on|alternate] [--no-cpu-baseline]
+                                   [--tiff-on-device off|on|alternate] [--tiff-read-on-device off|on|alternate] [--no-cpu-baseline]
 
 Per 1040 x 1392 scene with 300 nuclei (tests/stat_fish_cases.py ``full_size_scene``) it reports
   * device milliseconds per image of ecseg_fish_spots (ECSEG_T_COUNT: the kernels alone), of the nucleus labelling in front of
@@ -13,6 +13,9 @@ Per 1040 x 1392 scene with 300 nuclei (tests/stat_fish_cases.py ``full_size_scen
   * with ``--tiff-on-device on`` the same under the config key ``tiff_on_device: true`` (every TIFF LZW-encoded on the device), with
     ``alternate`` key off and key on in turn, twice, each with its own warm-up pass (``main_by_key``); either way the device
     milliseconds (render + encode for the first) and the wall time of ecseg_fish_render_tiff and of ecseg_tiff_encode of the mask;
+  * with ``--tiff-read-on-device on`` ``main()`` runs under ``tiff_read_on_device: true`` (the input TIFFs decoded on the device), with
+    ``alternate`` that key off and on in turn, twice (``main_by_read_key``; ``--tiff-on-device on`` then holds in all four), and the read
+    stage of ``process_image`` per image is reported beside the write stage;
   * the same scenes through the vectorised numpy / scipy restatement tests/stat_fish_ref.py ``records`` on one core and on a
     pool of --cpu-workers processes, as the baseline.
 With ``--channels 4`` the scenes are four-channel ``.npy`` images (blue, green, red and an aqua channel made of the green one shifted
@@ -52,6 +55,7 @@ def main():
     ap.add_argument('--channels', type=int, default=3, choices=(3, 4))
     ap.add_argument('--main-passes', type=int, default=3)
     ap.add_argument('--tiff-on-device', choices=('off', 'on', 'alternate'), default='off')
+    ap.add_argument('--tiff-read-on-device', choices=('off', 'on', 'alternate'), default='off')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     a = ap.parse_args()
     import yaml
@@ -130,37 +134,49 @@ def main():
             seen.update(kw['stats'])
             return r
 
-        def passes(key):
+        def passes(key, read_key=False):
             """One warm-up pass (arenas, page cache) and --main-passes timed ones -> images/s of each, write stage ms per image."""
             cfg = {'stat_fish': {'inpath': inp, 'scale': 1, 'use_min_cut': False, 'nuclei_size_T': 5000}}
             if key:
                 cfg['stat_fish']['tiff_on_device'] = True
+            if read_key:
+                cfg['stat_fish']['tiff_read_on_device'] = True
             with open(os.path.join(tmp, 'config.yaml'), 'w') as f:
                 yaml.safe_dump(cfg, f)
-            rates, writes = [], []
+            rates, writes, stage_reads = [], [], []
             for rep in range(a.main_passes + 1):
                 t0 = time.perf_counter()
                 stat_fish.main([], handle=gpu)
                 if rep:
                     rates.append(a.images / (time.perf_counter() - t0))
                     writes.append(seen['write'] * 1e3 / a.images)
-            return rates, writes
+                    stage_reads.append(seen['read'] * 1e3 / a.images)
+                seen.clear()
+            return rates, writes, stage_reads
 
-        def summary(rates, writes):
+        def summary(rates, writes, stage_reads):
             return dict(main_images_per_s=statistics.median(rates), main_images_per_s_min=min(rates), main_images_per_s_max=max(rates),
-                        write_stage_ms_per_image=statistics.median(writes))
+                        write_stage_ms_per_image=statistics.median(writes), read_stage_ms_per_image=statistics.median(stage_reads))
         cwd = os.getcwd()
         os.chdir(tmp)
         stat_fish.process_image = spy
         try:
-            if a.tiff_on_device == 'alternate':
+            if a.tiff_read_on_device == 'alternate':
+                w = a.tiff_on_device == 'on'
+                out['main_by_read_key'] = [dict(tiff_on_device=w, tiff_read_on_device=key, **summary(*passes(w, key))) for key in (False, True, False, True)]
+                offs = [r for r in out['main_by_read_key'] if not r['tiff_read_on_device']]
+                ons = [r for r in out['main_by_read_key'] if r['tiff_read_on_device']]
+                out['max_off_below_min_on'] = max(r['main_images_per_s_max'] for r in offs) < min(r['main_images_per_s_min'] for r in ons)
+                out.update(offs[0])
+            elif a.tiff_on_device == 'alternate':
                 out['main_by_key'] = [dict(tiff_on_device=key, **summary(*passes(key))) for key in (False, True, False, True)]
                 offs = [r for r in out['main_by_key'] if not r['tiff_on_device']]
                 ons = [r for r in out['main_by_key'] if r['tiff_on_device']]
                 out['max_off_below_min_on'] = max(r['main_images_per_s_max'] for r in offs) < min(r['main_images_per_s_min'] for r in ons)
                 out.update(offs[0])
             else:
-                out.update(tiff_on_device=a.tiff_on_device == 'on', **summary(*passes(a.tiff_on_device == 'on')))
+                out.update(tiff_on_device=a.tiff_on_device == 'on', tiff_read_on_device=a.tiff_read_on_device == 'on',
+                           **summary(*passes(a.tiff_on_device == 'on', a.tiff_read_on_device == 'on')))
         finally:
             stat_fish.process_image = process_image
             os.chdir(cwd)
