@@ -223,7 +223,8 @@ hipError_t run_count_coloc(PostWorkspace& ws, const uint8_t* ob1, const uint8_t*
                            int32_t* n_dev, hipStream_t s);
 hipError_t run_count_hsr(PostWorkspace& ws, const uint8_t* chrom, const uint8_t* fish, int n_img, int H, int W,
                          int thr, int32_t* n_dev, hipStream_t s);
-hipError_t run_overlay(PostWorkspace& ws, const uint8_t* labels, const uint8_t* rgb, int n_img, int H, int W, int C,
+// labels: the driver's device copy; label bytes above 3 are folded to 0 in it (they are no class of the reference)
+hipError_t run_overlay(PostWorkspace& ws, uint8_t* labels, const uint8_t* rgb, int n_img, int H, int W, int C,
                        int sens, int hsr_thr, long long* out_dev, hipStream_t s);
 hipError_t launch_u16_to_u8(const uint16_t* in, uint8_t* out, size_t count, hipStream_t s);
 hipError_t run_preprocess(const void* img, int n_img, int H, int W, int C, int bps, uint8_t* gray, int32_t* inverted,

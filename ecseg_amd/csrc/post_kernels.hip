@@ -1464,12 +1464,17 @@ __global__ __launch_bounds__(256) void overlay_mask_kernel(const uint8_t* __rest
 
 // aux bits for the (chromosome, ecDNA) labelling: bit0 fish, bit1 fish2, bit2 fish & fish2 (ecDNA colocalisation);
 // bits 3 / 4 (size-filtered fish2 / fish, for HSR) are OR-ed in afterwards by keep_large_kernel.
-__global__ __launch_bounds__(256) void overlay_aux_kernel(const uint8_t* __restrict__ labels, const uint8_t* __restrict__ rgb,
+// The first kernel of the row also folds label bytes above 3 to 0 in the driver's copy of the labels: the reference takes
+// nuclei / chromosomes / ecDNA as labels == 1 / 2 / 3, so such a byte is background, while key_of looks at the low two
+// bits only (6 would be labelled as a chromosome, 7 and 255 as ecDNA).  A store happens only for such a byte, and it comes
+// last: in front of the colour loads it made them wait for the label byte (two memory round trips per pixel instead of one).
+__global__ __launch_bounds__(256) void overlay_aux_kernel(uint8_t* __restrict__ labels, const uint8_t* __restrict__ rgb,
                                                           int C, int sens, uint8_t* __restrict__ aux, size_t total) {
     PX_LOOP(total) {
         const uint8_t v = labels[t];
         const bool fish2 = rgb[t * C + 0] > sens && v != 1, fish = rgb[t * C + 1] > sens && v != 1;
         aux[t] = (uint8_t)((fish ? 1 : 0) | (fish2 ? 2 : 0) | ((fish && fish2) ? 4 : 0));
+        if (v > 3) labels[t] = 0;
     }
 }
 
@@ -1483,7 +1488,7 @@ __global__ void overlay_cc_gather_kernel(const int32_t* __restrict__ G_all, int 
     out[(size_t)i * 12 + off + 1] = (n == 0 || px == full_px) ? -1 : px;
 }
 
-hipError_t run_overlay(PostWorkspace& ws, const uint8_t* labels, const uint8_t* rgb, int n_img, int H, int W, int C, int sens,
+hipError_t run_overlay(PostWorkspace& ws, uint8_t* labels, const uint8_t* rgb, int n_img, int H, int W, int C, int sens,
                        int hsr_thr, long long* out, hipStream_t s) {
     if (n_img <= 0) return hipSuccess;
     const CclGeom g = make_geom(n_img, H, W);

@@ -272,7 +272,8 @@ int ecseg_count_hsr(ecseg_ctx* h, const uint8_t* chrom, const uint8_t* fish, int
                     int size_threshold, int32_t* n_out);
 
 /* ---- meta_overlay row (src/meta_overlay.py:59-95, src/image_tools.py:136-146) ----------------------------- */
-/* labels: (n_img, H, W) uint8 post-processed labels (what read_seg loads, src/utils.py:125-132);
+/* labels: (n_img, H, W) uint8 post-processed labels (what read_seg loads, src/utils.py:125-132): 1 nucleus, 2 chromosome,
+ * 3 ecDNA; every other byte, those above 3 included, is background, as with the reference's labels == 1 / 2 / 3;
  * rgb: (n_img, H, W, C>=2) uint8, channel 0 red, channel 1 green; sensitivity: color_sensitivity.
  * out: n_img rows of 12 int64, in final CSV column order (src/meta_overlay.py:98-100):
  *   [0,1]  count_cc(ec)                 (n, px)   px = -1 stands for the reference's float 0.0

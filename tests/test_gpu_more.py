@@ -6,7 +6,8 @@ import os
 import numpy as np
 import pytest
 
-from ecseg_amd import keras_plan, synth
+from ecseg_amd import csvio, keras_plan, synth
+from oracle import overlay as oracle_overlay
 from oracle import postproc
 from oracle import unet as oracle_unet
 
@@ -261,12 +262,14 @@ def test_clean_up_and_counts_for_every_batch_remainder(gpu, n_img):
     labs = np.stack([synth.label_map(300 + i, H, W) if i % 3 else rng.integers(0, 4, size=(H, W)).astype(np.uint8) for i in range(n_img)])
     post, nec = gpu.meta_inference(labs)
     cnt, px = gpu.count_cc(labs == 3)
-    rows = gpu.overlay(labs, np.stack([synth.dapi_image(500 + i, H, W, rgb=True) for i in range(n_img)]), 85)
+    rgbs = np.stack([synth.dapi_image(500 + i, H, W, rgb=True) for i in range(n_img)])
+    rows = gpu.overlay(labs, rgbs, 85)
     for i in range(n_img):
         want = postproc.meta_inference(labs[i])
         assert np.array_equal(post[i], want), i
         assert nec[i] == postproc.count_cc(want == 3)[0]
         assert (cnt[i], px[i]) == tuple(postproc.count_cc(labs[i] == 3)), i
+        assert csvio.overlay_cells(rows[i]) == oracle_overlay.overlay_row(labs[i], rgbs[i], 85), i
     one = gpu.overlay(labs[-1], synth.dapi_image(500 + n_img - 1, H, W, rgb=True), 85)
     assert np.array_equal(np.asarray(one).reshape(-1), np.asarray(rows[-1]).reshape(-1))
 
