@@ -23,6 +23,7 @@ EXPORTS = [
     'ecseg_tiff_write_rgb8', 'ecseg_npy_write_i32_as_i64',
     'ecseg_tiff_encode_bound', 'ecseg_tiff_encode', 'ecseg_fish_render_tiff', 'ecseg_tiff_decode', 'ecseg_tiff_decode_routes',
     'ecseg_png_labels_encode', 'ecseg_meta_segment_files', 'ecseg_get_file_timings', 'ecseg_png_labels_stream_size',
+    'ecseg_ccl_pass_debug',
 ]
 
 
@@ -47,6 +48,16 @@ class OpDesc(C.Structure):
                 ('kh', C.c_int32), ('kw', C.c_int32), ('stride', C.c_int32),
                 ('pad_top', C.c_int32), ('pad_left', C.c_int32), ('act', C.c_int32), ('mode', C.c_int32),
                 ('w0', C.c_int32), ('w1', C.c_int32), ('alpha', C.c_float), ('dilation', C.c_int32)]
+
+
+class CclPassDesc(C.Structure):
+    _fields_ = [('lut', C.c_uint32), ('conn', C.c_int32), ('stat', C.c_int32), ('aux_mode', C.c_int32), ('aux_c', C.c_int32),
+                ('need', C.c_int32), ('count_only', C.c_int32), ('sparse', C.c_int32), ('allow_full', C.c_int32),
+                ('n_queries', C.c_int32), ('query_key', C.c_int32 * 5), ('query_need', C.c_uint32 * 5)]
+
+
+class CclPassOut(C.Structure):
+    _fields_ = [(name, C.c_void_p) for name in ('root', 'area', 'sumy', 'sumx', 'flag', 'counters', 'list1', 'list2', 'tile_any')]
 
 
 _lib = None
@@ -115,6 +126,7 @@ def load_library():
     lib.ecseg_meta_inference_dev.argtypes = [vp, u8p, i32, i32, i32, vp, vp]
     lib.ecseg_count_cc.argtypes = [vp, u8p, i32, i32, i32, vp, vp]
     lib.ecseg_ccl_labels.argtypes = [vp, u8p, i32, i32, i32, i32, vp]
+    lib.ecseg_ccl_pass_debug.argtypes = [vp, u8p, u8p, i32, i32, i32, C.POINTER(CclPassDesc), C.POINTER(CclPassOut)]
     lib.ecseg_count_colocalization.argtypes = [vp, u8p, u8p, i32, i32, i32, vp]
     lib.ecseg_count_hsr.argtypes = [vp, u8p, u8p, i32, i32, i32, i32, vp]
     lib.ecseg_overlay.argtypes = [vp, u8p, u8p, i32, i32, i32, i32, i32, i32, vp]
@@ -518,6 +530,44 @@ class Handle:
         out = np.empty((n, H, W), np.int32)
         self._check(self.lib.ecseg_ccl_labels(self.h, _ptr(a), n, H, W, int(connectivity), _ptr(out)), 'ecseg_ccl_labels')
         return out[0] if single else out
+
+    def ccl_pass(self, key, aux=None, lut=0xffffffff, conn=8, stat=0, aux_mode=0, aux_c=0, need=0, count_only=False, sparse=False,
+                 allow_full=False, queries=()):
+        """Test-only (ecseg_ccl_pass_debug): ONE labelling pass on (n, H, W) uint8 keys, described as the drivers of
+        csrc/post_kernels.hip describe theirs, with everything it produced -> dict: ``root`` int32 (-1 unkeyed, else the pixel
+        index of the component's first pixel; after a count_only pass the pixel's own index where it was counted as a root),
+        ``area`` uint32 / ``sumy`` / ``sumx`` uint64 / ``flag`` uint32 at root pixels (0 elsewhere), ``ncomp`` / ``npx`` (n, 3) for
+        keys 1..3, ``last_root`` (last root + 1), ``cnt`` (n, 5) answers to ``queries`` [(key, need_bits)], ``list1`` / ``list2``
+        (per image the roots of value 1 / 2, in the device's order) and ``tile_any`` (n, ceil(H/32), ceil(W/64))."""
+        a, _ = self._stack(key)
+        n, H, W = a.shape
+        x = None
+        if aux is not None:
+            x, _ = self._stack(aux)
+            if x.shape != a.shape:
+                raise ValueError('aux must have the shape of key')
+        queries = list(queries)
+        if len(queries) > 5:
+            raise ValueError('at most 5 flag queries')
+        d = CclPassDesc(lut=int(lut), conn=int(conn), stat=int(stat), aux_mode=int(aux_mode), aux_c=int(aux_c), need=int(need),
+                        count_only=int(bool(count_only)), sparse=int(bool(sparse)), allow_full=int(bool(allow_full)), n_queries=len(queries))
+        for k, (qk, qn) in enumerate(queries):
+            d.query_key[k] = int(qk)
+            d.query_need[k] = int(qn)
+        cap = H * W // 4 + (H + W) // 2 + 4
+        bufs = dict(root=np.empty((n, H, W), np.int32), area=np.empty((n, H, W), np.uint32), sumy=np.empty((n, H, W), np.uint64),
+                    sumx=np.empty((n, H, W), np.uint64), flag=np.empty((n, H, W), np.uint32), counters=np.empty((n, 16), np.int32),
+                    list1=np.empty((n, cap), np.int32), list2=np.empty((n, cap), np.int32),
+                    tile_any=np.empty((n, (H + 31) // 32, (W + 63) // 64), np.uint8))
+        o = CclPassOut(**{k: v.ctypes.data for k, v in bufs.items()})
+        self._check(self.lib.ecseg_ccl_pass_debug(self.h, _ptr(a), _ptr(x), n, H, W, C.byref(d), C.byref(o)), 'ecseg_ccl_pass_debug')
+        cnt = bufs.pop('counters')
+        l1, l2 = bufs.pop('list1'), bufs.pop('list2')
+        bufs.update(ncomp=cnt[:, 0:3].copy(), npx=cnt[:, 3:6].copy(), last_root=cnt[:, 6].copy(), nlist1=cnt[:, 7].copy(),
+                    nlist2=cnt[:, 8].copy(), cnt=cnt[:, 9:14].copy(),
+                    list1=[l1[i, :max(0, min(cap, int(cnt[i, 7])))].copy() for i in range(n)],
+                    list2=[l2[i, :max(0, min(cap, int(cnt[i, 8])))].copy() for i in range(n)])
+        return bufs
 
     def count_colocalization(self, ob1, ob2):
         a, single = self._stack(ob1)

@@ -219,6 +219,39 @@ hipError_t run_count_cc(PostWorkspace& ws, const uint8_t* mask, int n_img, int H
                         long long* px_dev, hipStream_t s);
 hipError_t run_ccl_labels(PostWorkspace& ws, const uint8_t* mask, int n_img, int H, int W, int conn,
                           int32_t* labels_dev, hipStream_t s);
+// Test-only: ONE labelling pass (the CclPass of post_kernels.hip, field by field) alone, with everything it produced exported.
+// q_key / q_need: up to 5 queries of count_flagged_owner_roots_kernel (roots with key == q_key, 0 = any, whose flag word holds all
+// bits of q_need), answered in counters 9 .. 13.
+struct CclPassDesc {
+    uint32_t lut;
+    int conn, stat, aux_mode, aux_c, need;
+    bool count_only, sparse, allow_full;
+    int n_q, q_key[5];
+    uint32_t q_need[5];
+};
+enum { CCL_DEBUG_COUNTERS = 16 };      // per image: NCOMP[1..3], NPX[1..3], LAST_ROOT, NLIST1, NLIST2, CNT0..4, two spare
+// entries per image in each root list of a NEED_LISTS pass (run_meta_inference's formula: >= ceil(H/2) ceil(W/2), the most
+// 8-connected components an image can hold)
+inline size_t ccl_list_cap(int H, int W) { return (size_t)H * W / 4 + (size_t)(H + W) / 2 + 4; }
+// root: per pixel, -1 unkeyed, else the component's root (pixel index in the image) read as consumers do, pixel -> owner -> root
+// (-2: a parent out of range); count_only passes: the pixel's own index where count_roots_kernel counts it, else -1.
+// area / sumy / sumx / flag: the root's slots at root pixels, 0 elsewhere.  list1 / list2: (n_img, ccl_list_cap) entries, -1 beyond
+// the counts.
+struct CclPassExport {
+    int32_t* root; uint32_t* area; unsigned long long* sumy; unsigned long long* sumx; uint32_t* flag;
+    int32_t* counters; int32_t* list1; int32_t* list2;
+};
+inline CclPassExport ccl_pass_export_bufs(Carver& c, int n_img, size_t px, size_t list_cap) {
+    CclPassExport b;
+    const size_t tot = (size_t)n_img * px;
+    b.root = c.take<int32_t>(tot); b.area = c.take<uint32_t>(tot); b.sumy = c.take<unsigned long long>(tot);
+    b.sumx = c.take<unsigned long long>(tot); b.flag = c.take<uint32_t>(tot);
+    b.counters = c.take<int32_t>((size_t)n_img * CCL_DEBUG_COUNTERS);
+    b.list1 = c.take<int32_t>((size_t)n_img * list_cap); b.list2 = c.take<int32_t>((size_t)n_img * list_cap);
+    return b;
+}
+hipError_t run_ccl_pass_debug(PostWorkspace& ws, const uint8_t* key_img, const uint8_t* aux_img, int n_img, int H, int W,
+                              const CclPassDesc& d, const CclPassExport& out, hipStream_t s);
 hipError_t run_count_coloc(PostWorkspace& ws, const uint8_t* ob1, const uint8_t* ob2, int n_img, int H, int W,
                            int32_t* n_dev, hipStream_t s);
 hipError_t run_count_hsr(PostWorkspace& ws, const uint8_t* chrom, const uint8_t* fish, int n_img, int H, int W,

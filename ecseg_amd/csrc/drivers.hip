@@ -231,6 +231,57 @@ int ecseg_ccl_labels(ecseg_ctx* h, const uint8_t* mask, int n_img, int H, int W,
     if (h && n_img > 0 && !labels_out) return fail(h, ECSEG_E_INVALID, "labels_out is NULL");
     return count_driver(h, mask, nullptr, n_img, H, W, 3, connectivity, nullptr, nullptr, labels_out);
 }
+// Test-only: one labelling pass alone (run_ccl_pass_debug), uploaded and chunked as count_driver does it, every export brought back.
+int ecseg_ccl_pass_debug(ecseg_ctx* h, const uint8_t* key_img, const uint8_t* aux_img, int n_img, int H, int W,
+                         const ecseg_ccl_pass_desc* pass, const ecseg_ccl_pass_out* out) {
+    if (!h) return ECSEG_E_INVALID;
+    drop_sent_ahead(h);
+    if (n_img < 0 || H <= 0 || W <= 0 || !pass || (n_img > 0 && (!key_img || !out))) return fail(h, ECSEG_E_INVALID, "ccl_pass_debug: bad arguments");
+    if (n_img == 0) return ECSEG_OK;
+    if (!out->root || !out->area || !out->sumy || !out->sumx || !out->flag || !out->counters || !out->list1 || !out->list2 || !out->tile_any)
+        return fail(h, ECSEG_E_INVALID, "ccl_pass_debug: every output is required");
+    if (pass->conn != 4 && pass->conn != 8) return fail(h, ECSEG_E_INVALID, "connectivity must be 4 or 8");
+    if (pass->aux_mode == 3 && !aux_img) return fail(h, ECSEG_E_INVALID, "ccl_pass_debug: aux_mode 3 needs aux_img");
+    if (pass->n_queries < 0 || pass->n_queries > 5) return fail(h, ECSEG_E_INVALID, "ccl_pass_debug: at most 5 flag queries");
+    if ((pass->need & 8) && pass->conn != 8) return fail(h, ECSEG_E_INVALID, "ccl_pass_debug: the root lists are sized for 8-connected components");
+    if (pass->n_queries > 0 && pass->count_only) return fail(h, ECSEG_E_INVALID, "ccl_pass_debug: a count_only pass writes no flag words to query");
+    if ((long long)H * W >= (1ll << 31)) return fail(h, ECSEG_E_INVALID, "image too large");
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t px = (size_t)H * W, cap = ccl_list_cap(H, W);
+    const size_t tiles = (size_t)((H + 31) / 32) * (size_t)((W + 63) / 64);
+    const int chunk = std::min(n_img, h->post_chunk);
+    int rc;
+    CclPassExport b{};
+    if ((rc = ensure_post(h, chunk, px))) return rc;
+    if ((rc = h->d_gray.ensure(h, px * chunk))) return rc;
+    if (aux_img && (rc = h->d_aux8.ensure(h, px * chunk))) return rc;
+    if ((rc = lay_out(h, h->call_arena, [&](Carver& c) { b = ccl_pass_export_bufs(c, chunk, px, cap); }))) return rc;
+    CclPassDesc d{};
+    d.lut = pass->lut; d.conn = pass->conn; d.stat = pass->stat; d.aux_mode = pass->aux_mode; d.aux_c = pass->aux_c; d.need = pass->need;
+    d.count_only = pass->count_only != 0; d.sparse = pass->sparse != 0; d.allow_full = pass->allow_full != 0;
+    d.n_q = pass->n_queries;
+    for (int k = 0; k < 5; ++k) { d.q_key[k] = pass->query_key[k]; d.q_need[k] = pass->query_need[k]; }
+    hipStream_t s = h->stream;
+    for (int i0 = 0; i0 < n_img; i0 += chunk) {
+        const int ni = std::min(chunk, n_img - i0);
+        const size_t o = (size_t)i0 * px, nb = px * ni;
+        HIP_TRY(h, hipMemcpyAsync(h->d_gray, key_img + o, nb, hipMemcpyHostToDevice, s));
+        if (aux_img) HIP_TRY(h, hipMemcpyAsync(h->d_aux8, aux_img + o, nb, hipMemcpyHostToDevice, s));
+        const hipError_t e = run_ccl_pass_debug(h->ws, h->d_gray, aux_img ? h->d_aux8.p : nullptr, ni, H, W, d, b, s);
+        if (e != hipSuccess) return fail_hip(h, e, "ccl_pass_debug kernels");
+        HIP_TRY(h, hipMemcpyAsync(out->root + o, b.root, nb * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipMemcpyAsync(out->area + o, b.area, nb * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipMemcpyAsync(out->sumy + o, b.sumy, nb * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipMemcpyAsync(out->sumx + o, b.sumx, nb * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipMemcpyAsync(out->flag + o, b.flag, nb * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipMemcpyAsync(out->counters + (size_t)i0 * CCL_DEBUG_COUNTERS, b.counters, (size_t)ni * CCL_DEBUG_COUNTERS * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipMemcpyAsync(out->list1 + (size_t)i0 * cap, b.list1, (size_t)ni * cap * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipMemcpyAsync(out->list2 + (size_t)i0 * cap, b.list2, (size_t)ni * cap * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipMemcpyAsync(out->tile_any + (size_t)i0 * tiles, h->ws.tile_any, (size_t)ni * tiles, hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipStreamSynchronize(s));
+    }
+    return ECSEG_OK;
+}
 int ecseg_count_colocalization(ecseg_ctx* h, const uint8_t* ob1, const uint8_t* ob2, int n_img, int H, int W, int32_t* n_out) {
     if (h && n_img > 0 && !ob2) return fail(h, ECSEG_E_INVALID, "ob2 is NULL");
     return count_driver(h, ob1, ob2, n_img, H, W, 1, 0, n_out, nullptr, nullptr);

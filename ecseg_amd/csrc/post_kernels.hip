@@ -675,6 +675,9 @@ struct CclPass {
     bool allow_full = false;   // binary keys, 4-connectivity, no statistics / counters: tiles without an unkeyed pixel are one node (tile_any == 2)
     int32_t* list1 = nullptr;  // NEED_LISTS: per-image lists of class-1 roots / class-2 roots (first word of 16-byte slots)
     int32_t* list2 = nullptr;
+    // ccl_resolve appends without looking at list_cap: NEED_LISTS is for conn == 8 only, where ceil(H/2) ceil(W/2) <= list_cap bounds
+    // the roots of an image (a 4-connected checkerboard has twice as many); run_ccl_pass_debug's callers reject conn == 4 with lists.
+    // The flag words of a count_only pass are not written (no slots): flag queries after one read stale words, rejected there too.
     size_t list_cap = 0;
     // counter block of this pass (null: ws.g, zeroed by a launch of its own and folded by reduce_g_kernel).  run_meta_inference
     // gives every labelling its own block, zeroes them all with ONE memset and lets the consumers fold the replicas themselves
@@ -1375,6 +1378,107 @@ static void launch_flagged_counts(PostWorkspace& ws, const CclGeom& g, const uin
     hipLaunchKernelGGL(count_flagged_owner_roots_kernel, dim3(geom_grid(g)), dim3(256), 0, s, g, key_img, lut, ws.L, ws.flag, ws.g,
                        ws.tile_any, ws.own_bits, Q);
     hipLaunchKernelGGL(reduce_g_kernel, dim3(g.n_img), dim3(G_STRIDE), 0, s, ws.g, g.n_img);
+}
+
+// ---- test-only: one pass alone, everything it produced read back (run_ccl_pass_debug) --------------------------------------
+// One thread per pixel.  A keyed pixel's root is read as every consumer reads it: pixel -> owner -> root; in a full tile
+// (tile_any == 2) the tile's first pixel stands in for the owner (apply_fill_tile_kernel).  The key comes first: a sparse pass
+// leaves stale parents on background.  Root pixels carry their slots, every other pixel 0.  A count_only pass has no resolved
+// roots: the pixels count_roots_kernel counts (owners that point at themselves) are exported as their own roots, the rest as -1.
+__global__ __launch_bounds__(256) void export_pass_px_kernel(CclGeom g, const uint8_t* __restrict__ img_all, uint32_t lut,
+                                                             const int32_t* __restrict__ L_all, const uint32_t* __restrict__ area_all,
+                                                             const u64* __restrict__ sumy_all, const u64* __restrict__ sumx_all,
+                                                             const uint32_t* __restrict__ flag_all, const uint8_t* __restrict__ tile_any,
+                                                             const uint32_t* __restrict__ own_bits, int stat, int count_only,
+                                                             int32_t* __restrict__ root_out, uint32_t* __restrict__ area_out,
+                                                             u64* __restrict__ sumy_out, u64* __restrict__ sumx_out,
+                                                             uint32_t* __restrict__ flag_out) {
+    const size_t px = (size_t)g.H * g.W;
+    IMG_PX_LOOP(g.n_img, px) {
+        const int p = (int)(t - ib), y = p / g.W, x = p % g.W;
+        const int ty = y / CCL_BLOCK_ROWS, tx = x / 64;
+        const size_t ti = (size_t)im * g.blocks_per_img + (size_t)ty * g.chunks_x + tx;
+        const int ta = tile_any[ti];
+        const int p0 = ty * CCL_BLOCK_ROWS * g.W + tx * 64;            // the tile's first pixel
+        int root = -1;
+        uint32_t a = 0, f = 0;
+        u64 sy = 0, sx = 0;
+        if (key_of(img_all[t], lut)) {
+            if (count_only) {
+                const int li = (y - ty * CCL_BLOCK_ROWS) * 64 + (x - tx * 64);
+                const bool owner = ta == 2 ? p == p0 : ((own_bits[ti * 64 + (li >> 5)] >> (li & 31)) & 1u) != 0;
+                if (owner && L_all[t] == p) root = p;
+            } else {
+                const int o = ta == 2 ? p0 : L_all[t];
+                root = (o >= 0 && (size_t)o < px) ? L_all[ib + o] : -2;
+                if (root < 0 || (size_t)root >= px) root = -2;
+                if (root == p) {
+                    f = flag_all[t];
+                    if (stat & STAT_AREA) a = area_all[t];
+                    if (stat & STAT_SUMS) { sy = sumy_all[t]; sx = sumx_all[t]; }
+                }
+            }
+        }
+        root_out[t] = root; area_out[t] = a; sumy_out[t] = sy; sumx_out[t] = sx; flag_out[t] = f;
+    }
+}
+
+// one thread per image: the folded counters (replica 0 after reduce_g_kernel)
+__global__ void export_pass_counters_kernel(const int32_t* __restrict__ G_all, int n_img, int32_t* __restrict__ out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_img) return;
+    const int32_t* G = G_all + (size_t)i * G_IMG;
+    int32_t* o = out + (size_t)i * CCL_DEBUG_COUNTERS;
+    for (int k = 0; k < 3; ++k) { o[k] = G[G_NCOMP + 1 + k]; o[3 + k] = G[G_NPX + 1 + k]; }
+    o[6] = G[G_LAST_ROOT]; o[7] = G[G_NLIST1]; o[8] = G[G_NLIST2];
+    for (int k = 0; k < 5; ++k) o[9 + k] = G[G_CNT0 + k];
+    o[14] = 0; o[15] = 0;
+}
+
+// one thread per list entry: the class-1 roots and the first word of every class-2 slot up to their counts, -1 beyond
+__global__ __launch_bounds__(256) void export_pass_lists_kernel(const int32_t* __restrict__ G_all, const int32_t* __restrict__ list1,
+                                                                const int32_t* __restrict__ list2, int n_img, size_t cap,
+                                                                int32_t* __restrict__ out1, int32_t* __restrict__ out2) {
+    IMG_PX_LOOP(n_img, cap) {
+        const int k = (int)(t - ib);
+        const int32_t* G = G_all + (size_t)im * G_IMG;
+        out1[t] = (list1 && k < G[G_NLIST1]) ? list1[t] : -1;
+        out2[t] = (list2 && k < G[G_NLIST2]) ? list2[t * 4] : -1;
+    }
+}
+
+hipError_t run_ccl_pass_debug(PostWorkspace& ws, const uint8_t* key_img, const uint8_t* aux_img, int n_img, int H, int W,
+                              const CclPassDesc& d, const CclPassExport& out, hipStream_t s) {
+    if (n_img <= 0) return hipSuccess;
+    // (ecseg_ccl_pass_debug says which: ECSEG_E_INVALID; see struct CclPass for the last two)
+    if ((d.conn != 4 && d.conn != 8) || (d.aux_mode == AUX_IMAGE && !aux_img) || d.n_q < 0 || d.n_q > 5 ||
+        ((d.need & NEED_LISTS) && d.conn != 8) || (d.n_q > 0 && d.count_only))
+        return hipErrorInvalidValue;
+    const CclGeom g = make_geom(n_img, H, W);
+    const size_t px = (size_t)H * W, cap = ccl_list_cap(H, W);
+    CclPass p{key_img, d.lut, d.conn, d.stat, d.aux_mode, d.aux_c, aux_img, d.need, d.count_only};
+    p.sparse = d.sparse;
+    p.allow_full = d.allow_full;
+    if (d.need & NEED_LISTS) {                                 // carved as run_meta_inference carves them
+        p.list1 = ws.list;
+        p.list2 = reinterpret_cast<int32_t*>(reinterpret_cast<double2*>(ws.list + (((size_t)n_img * cap + 3) & ~(size_t)3)));
+        p.list_cap = cap;
+    }
+    // a pass without counters zeroes none: the export and the flag queries below read them all the same
+    if (!d.need) hipLaunchKernelGGL(zero_g_kernel, dim3((n_img * G_IMG + 255) / 256), dim3(256), 0, s, ws.g, n_img * G_IMG);
+    hipError_t e = run_ccl_pass(ws, g, p, s);
+    if (e != hipSuccess) return e;
+    if (d.n_q > 0) {
+        FlagQueries Q{d.n_q, {}, {}, {}};
+        for (int k = 0; k < d.n_q; ++k) { Q.key[k] = d.q_key[k]; Q.need[k] = d.q_need[k]; Q.slot[k] = k; }
+        launch_flagged_counts(ws, g, key_img, d.lut, Q, s);
+    }
+    hipLaunchKernelGGL(export_pass_px_kernel, img_grid(px, n_img), dim3(256), 0, s, g, key_img, d.lut, ws.L, ws.area, ws.sumy, ws.sumx,
+                       ws.flag, ws.tile_any, ws.own_bits, d.stat, d.count_only ? 1 : 0, out.root, out.area, out.sumy, out.sumx, out.flag);
+    hipLaunchKernelGGL(export_pass_counters_kernel, dim3((n_img + 63) / 64), dim3(64), 0, s, ws.g, n_img, out.counters);
+    hipLaunchKernelGGL(export_pass_lists_kernel, img_grid(cap, n_img), dim3(256), 0, s, ws.g, p.list1, p.list2, n_img, cap, out.list1,
+                       out.list2);
+    return hipGetLastError();
 }
 
 __global__ void gather_slot_kernel(const int32_t* __restrict__ G_all, int n_img, int slot, int key_for_quirk,

@@ -51,6 +51,8 @@ extern "C" {
  * `make metaseg`'s dapi TIFFs and label PNGs encoded on the device; nothing existing changed.) */
 /* (still 5 - additive: ecseg_tiff_decode and ecseg_tiff_decode_routes, stat_fish's input TIFFs decoded on the device; nothing existing
  * changed.) */
+/* (still 5 - additive: ecseg_ccl_pass_debug, one connected-component labelling pass alone with everything it produced read back, for
+ * the tests of the labelling kernels; nothing existing changed.) */
 #define ECSEG_ABI_VERSION 5
 
 #define ECSEG_OK             0
@@ -264,6 +266,31 @@ int ecseg_count_cc(ecseg_ctx* h, const uint8_t* mask, int n_img, int H, int W, i
  * (connectivity 4 or 8); used by the parity tests of the union-find kernels. */
 int ecseg_ccl_labels(ecseg_ctx* h, const uint8_t* mask, int n_img, int H, int W, int connectivity,
                      int32_t* labels_out);
+/* Test-only: ONE labelling pass of the post-processing (struct CclPass of csrc/post_kernels.hip, field by field) run alone, and
+ * everything it produced read back whole.  lut: key of a pixel = byte (value & 3) of it, or value != 0 when it is 0xffffffff;
+ * conn 4 | 8; stat bit 0 area, bit 1 coordinate sums; aux_mode 0 none, 1 image border, 2 value == aux_c, 3 bits 0-4 of aux_img;
+ * need bit 0 components per key, 1 pixels per key, 2 last root + 1, 3 the two root lists; n_queries <= 5 flag queries (roots with
+ * key == query_key, 0 = any, whose flag word holds all bits of query_need).
+ * ECSEG_E_INVALID: conn not 4 / 8, aux_mode 3 without aux_img, lists with conn 4 (their capacity bounds 8-connected components only),
+ * queries after a count_only pass (it writes no flag words). */
+typedef struct ecseg_ccl_pass_desc {
+    uint32_t lut;
+    int32_t conn, stat, aux_mode, aux_c, need, count_only, sparse, allow_full;
+    int32_t n_queries, query_key[5];
+    uint32_t query_need[5];
+} ecseg_ccl_pass_desc;
+/* All of them required, (n_img, H, W) unless said otherwise.  root: -1 where the key is 0, else the pixel index (in the image) of the
+ * component's root = its first pixel in raster order; after a count_only pass the pixel's own index where it was counted as a
+ * root, else -1.  area / sumy / sumx / flag: the component's at its root pixel, 0 elsewhere.  counters: (n_img, 16) components
+ * per key 1..3, pixels per key 1..3, last root + 1, entries of list1 / list2, the 5 query answers, 2 spare.  list1 / list2:
+ * (n_img, H*W/4 + (H+W)/2 + 4) roots of value 1 / 2 in no particular order, -1 beyond their counts.  tile_any: (n_img,
+ * ceil(H/32), ceil(W/64)) 0 no keyed pixel, 1 some, 2 a full tile treated as one node. */
+typedef struct ecseg_ccl_pass_out {
+    int32_t* root; uint32_t* area; uint64_t* sumy; uint64_t* sumx; uint32_t* flag;
+    int32_t* counters; int32_t* list1; int32_t* list2; uint8_t* tile_any;
+} ecseg_ccl_pass_out;
+int ecseg_ccl_pass_debug(ecseg_ctx* h, const uint8_t* key_img, const uint8_t* aux_img, int n_img, int H, int W,
+                         const ecseg_ccl_pass_desc* pass, const ecseg_ccl_pass_out* out);
 /* count_colocalization (:126-134) */
 int ecseg_count_colocalization(ecseg_ctx* h, const uint8_t* ob1, const uint8_t* ob2, int n_img, int H, int W,
                                int32_t* n_out);
