@@ -37,5 +37,13 @@ asan_tiff_decode:
 	    ecseg_amd/csrc/host_codec.cpp tools/asan/tiff_decode_fuzz.cpp -o /tmp/ecseg_tiff_decode_fuzz
 	/tmp/ecseg_tiff_decode_fuzz
 
+# and for the batched reader: the layout function (csrc/tiff_decode_batch.h) and the batched strip walk over packed batches with
+# corrupt and truncated files; tests/test_tiff_decode_batch.py builds and runs it
+.PHONY: asan_tiff_decode_batch
+asan_tiff_decode_batch:
+	g++ -std=c++17 -O1 -g -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=all \
+	    ecseg_amd/csrc/host_codec.cpp tools/asan/tiff_decode_batch_fuzz.cpp -o /tmp/ecseg_tiff_decode_batch_fuzz
+	/tmp/ecseg_tiff_decode_batch_fuzz
+
 clean:
 	rm -rf __pycache__ ecseg_amd/csrc/*.o ecseg_amd/libecseg_*.so

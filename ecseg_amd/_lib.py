@@ -24,6 +24,7 @@ EXPORTS = [
     'ecseg_tiff_encode_bound', 'ecseg_tiff_encode', 'ecseg_fish_render_tiff', 'ecseg_tiff_decode', 'ecseg_tiff_decode_routes',
     'ecseg_png_labels_encode', 'ecseg_meta_segment_files', 'ecseg_get_file_timings', 'ecseg_png_labels_stream_size',
     'ecseg_ccl_pass_debug',
+    'ecseg_tiff_decode_batch', 'ecseg_tiff_decode_batch_bytes', 'ecseg_tiff_decode_batch_routes', 'ecseg_tiff_decode_batch_counts',
 ]
 
 
@@ -141,6 +142,10 @@ def load_library():
     lib.ecseg_fish_render_tiff.argtypes = [vp, u8p, i32, i32, i32, vp, u8p, i32, u8p, C.POINTER(vp), C.c_longlong, C.POINTER(C.c_longlong), vp, vp, vp]
     lib.ecseg_tiff_decode.argtypes = [vp, vp, C.c_longlong, vp, C.c_longlong, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
     lib.ecseg_tiff_decode_routes.argtypes = [vp, C.c_longlong]
+    lib.ecseg_tiff_decode_batch.argtypes = [vp, vp, C.c_longlong, vp, i32, vp, C.c_longlong, vp, vp, vp]
+    lib.ecseg_tiff_decode_batch_bytes.argtypes = [vp, C.c_longlong, vp, i32]; lib.ecseg_tiff_decode_batch_bytes.restype = C.c_longlong
+    lib.ecseg_tiff_decode_batch_routes.argtypes = [vp, C.c_longlong, vp, i32]
+    lib.ecseg_tiff_decode_batch_counts.argtypes = [vp, C.c_longlong]
     lib.ecseg_min_cut.argtypes = [vp, vp, C.c_longlong, vp, i32, i32, vp, vp]
     lib.ecseg_nuset_forward.argtypes = [vp, vp, i32, i32, i32, i32, vp]
     lib.ecseg_rpn_proposals.argtypes = [vp, vp, vp, i32, i32, i32, vp, i32, i32, i32, C.c_float, i32, i32, C.POINTER(C.c_int32), vp, vp, vp]
@@ -188,6 +193,19 @@ def load_library():
             fn.restype = C.c_int
     _lib = lib
     return lib
+
+
+def pack_file_images(bufs):
+    """1-D uint8 arrays -> (one buffer, (n, 2) int64 rows of byte offset and length): as ecseg_tiff_decode_batch takes its files.
+    Views of one buffer in ascending order, clear of each other (how ``image_io.imread_many`` reads its files), are not copied."""
+    sizes = np.array([b.size for b in bufs], np.int64)
+    base = bufs[0].base if bufs else None
+    if isinstance(base, np.ndarray) and base.dtype == np.uint8 and base.ndim == 1 and base.flags.c_contiguous and all(b.base is base for b in bufs):
+        offs = np.array([b.ctypes.data - base.ctypes.data for b in bufs], np.int64)
+        if (offs >= 0).all() and (offs + sizes <= base.size).all() and (offs[1:] >= (offs + sizes)[:-1]).all():
+            return base, np.ascontiguousarray(np.stack([offs, sizes], axis=1))
+    buf = np.concatenate(bufs) if bufs else np.zeros(0, np.uint8)
+    return buf, np.ascontiguousarray(np.stack([np.cumsum(sizes) - sizes, sizes], axis=1))
 
 
 def _ptr(a):
@@ -745,6 +763,73 @@ class Handle:
             return None
         self._check(rc, 'ecseg_tiff_decode')
         return out[..., 0] if spp.value == 1 else out
+
+    def tiff_decode_packed(self, files, ranges, dst=None, dst_offsets=None):
+        """ecseg_tiff_decode_batch as it is: ``files`` a 1-D uint8 buffer, ``ranges`` (n, 2) int64 rows (byte offset, bytes) -> (shapes
+        (n, 4) int32: H, W, samples per pixel, bits; status (n,) int32).  ``dst``: a 1-D uint8 buffer that receives the raster of file i
+        at ``dst_offsets[i]``; without it only shapes and status are filled."""
+        buf = np.ascontiguousarray(files, np.uint8).reshape(-1)
+        tab = np.ascontiguousarray(ranges, np.int64).reshape(-1, 2)
+        shapes, status = np.zeros((len(tab), 4), np.int32), np.zeros(len(tab), np.int32)
+        offs = None if dst_offsets is None else np.ascontiguousarray(dst_offsets, np.int64).reshape(-1)
+        if dst is not None and (offs is None or len(offs) != len(tab) or dst.dtype != np.uint8 or dst.ndim != 1 or not dst.flags.c_contiguous):
+            raise ValueError('tiff_decode_packed takes a 1-D uint8 destination and one offset per file')
+        self._check(self.lib.ecseg_tiff_decode_batch(self.h, _ptr(buf), buf.size, _ptr(tab), len(tab), _ptr(dst), 0 if dst is None else dst.size,
+                                                     _ptr(offs), _ptr(shapes), _ptr(status)), 'ecseg_tiff_decode_batch')
+        return shapes, status
+
+    def tiff_decode_many(self, datas, budget_bytes=8 << 30):
+        """``tiff_decode`` over a list of files at once (ecseg_tiff_decode_batch: a wave per strip, the strips of all files side by side).
+        -> a list with, per file, the array ``tiff_decode`` returns for it alone, None where it returns None, or the error it raises -
+        returned in its place, not raised (``segment_many``'s rule), so that one bad file costs the others nothing.  The files are packed
+        back to back (``pack_file_images``) and go in one call while the sum of what ecseg_tiff_decode_batch_bytes says each needs
+        stays within ``budget_bytes`` of device scratch, else in several calls over consecutive files; a file that exceeds the budget
+        alone goes alone."""
+        out = [None] * len(datas)
+        todo = []                                              # (position, bytes as uint8)
+        for k, data in enumerate(datas):
+            try:
+                buf = np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else _u8(data).reshape(-1)
+                if not buf.size:
+                    raise ValueError('tiff_decode takes the bytes of a file')
+                todo.append((k, buf))
+            except (TypeError, ValueError) as e:
+                out[k] = e
+
+        if not todo:
+            return out
+        buf, ranges = pack_file_images([b for _, b in todo])     # packed once: every call reads its files through its rows of the table
+        # what each file needs alone, asked once per file: their sum is at least what a call over them needs (every slot rounds up alone)
+        needs = [self.lib.ecseg_tiff_decode_batch_bytes(_ptr(buf), buf.size, _ptr(np.ascontiguousarray(ranges[k:k + 1])), 1) for k in range(len(todo))]
+        chunks, lo, held = [], 0, 0
+        for hi, need in enumerate(needs):
+            if hi > lo and (need < 0 or held < 0 or held + need > budget_bytes):
+                chunks.append((lo, hi))
+                lo, held = hi, 0
+            held = -1 if need < 0 or held < 0 else held + need
+        chunks.append((lo, len(todo)))
+        for lo, hi in chunks:
+            chunk, tab = todo[lo:hi], ranges[lo:hi]
+            shapes, status = self.tiff_decode_packed(buf, tab)
+            sizes = [int(H) * W * spp * (bits // 8) if st == 0 else 0 for (H, W, spp, bits), st in zip(shapes.tolist(), status.tolist())]
+            offs, end = [], 0
+            for (H, W, spp, bits), n in zip(shapes.tolist(), sizes):
+                end += end & 1 if bits == 16 else 0                # a 16-bit raster starts on an even byte
+                offs.append(end)
+                end += n
+            dst = np.empty(max(end, 1), np.uint8)
+            if end:
+                _, status = self.tiff_decode_packed(buf, tab, dst, offs)
+            for (k, _), (H, W, spp, bits), st, off, n in zip(chunk, shapes.tolist(), status.tolist(), offs, sizes):
+                if st == E_UNSUPPORTED:
+                    out[k] = None
+                elif st != 0:
+                    out[k] = EcsegError('ecseg_tiff_decode failed (%d): file %d of the batch is not a TIFF file, or a corrupt one' % (st, k))
+                    out[k].code = st
+                else:
+                    a = dst[off:off + n].view(np.uint8 if bits == 8 else np.uint16).reshape(H, W, spp)
+                    out[k] = a[..., 0] if spp == 1 else a
+        return out
 
     def fish_render_tiff(self, img, channels, thresholded, boundaries, want_rasters=False):
         """``fish_render``'s inputs -> the bytes of the three files ``image_io.write_tiff_rgb8`` writes for its rasters (``_original``,

@@ -5,6 +5,7 @@
 
 #include "../../include/ecseg_hip.h"
 #include "scratch.h"
+#include "tiff_decode_batch.h"
 #include "tiff_frame.h"
 
 namespace ecseg {
@@ -409,6 +410,10 @@ inline TiffDecodeBufs tiff_decode_bufs(Carver& c, size_t n_bytes, int n_table, s
 // (`swap`) and undoes the horizontal predictor (`predictor`) row by row.  A strip holds less than 2^31 bytes.
 hipError_t run_tiff_decode(const TiffDecodeBufs& b, unsigned long long n_bytes, int H, int W, int spp, int bytes_per_sample, int rps, int lzw,
                            int swap, int predictor, hipStream_t s);
+// The same for a batch of files laid out by td_batch_layout (tiff_decode_batch.h), in one launch per kernel: every strip of every
+// file into b.rasters and b.strip_status, the row pass once per sample size that needs it, then b.file_status (0, or 1: some strip of
+// the file is corrupt).  b.tab, b.files and b.tables are in place.
+hipError_t run_tiff_decode_batch(const TiffDecodeBatchBufs& b, const TdBatchLayout& L, hipStream_t s);
 
 // ---- launchers implemented in png_kernels.hip (the label PNG of ecseg_png_write_labels, host_io.cpp) ------------------------------
 // The token counts of one image, as deflate_labels' pass 1 takes them: [0..3] runs per colour, [4 + m] matches of 4 m bytes for

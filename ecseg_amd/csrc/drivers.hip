@@ -634,6 +634,33 @@ int ecseg_tiff_decode_routes(const uint8_t* file, long long n_bytes) {
     return file && n_bytes >= 0 && parse_tiff(file, (size_t)n_bytes, &t) == ECSEG_OK && tiff_goes_to_device(t) ? 1 : 0;
 }
 
+// The strips of a parsed file that is to be decoded lie in the file: ECSEG_OK, or ECSEG_E_INVALID and which one does not.
+static int tiff_strips_in_file(const TiffInfo& t, size_t n, std::string& why) {
+    const size_t nstrips = ((size_t)t.H + t.rps - 1) / t.rps, n_table = std::min(t.off.size(), nstrips);
+    for (size_t k = 0; k < n_table; ++k)
+        if (t.off[k] > n) { why = "strip " + std::to_string(k) + " starts behind the end of the file"; return ECSEG_E_INVALID; }
+    return ECSEG_OK;
+}
+
+// What ecseg_tiff_decode makes of a file before any device work, for itself and for every file of a batch: the tags in t, *parsed
+// (the file has a shape), and ECSEG_OK or the status with its reason.  with_strips: the file is to be decoded, not only measured.
+static int tiff_decode_verdict(const uint8_t* file, size_t n, bool with_strips, TiffInfo& t, bool* parsed, std::string& why) {
+    t = TiffInfo();
+    int rc = parse_tiff(file, n, &t);
+    *parsed = rc == ECSEG_OK;
+    if (rc != ECSEG_OK) {
+        why = rc == ECSEG_E_UNSUPPORTED ? "a layout the native readers leave to the Python reader" : "not a TIFF file, or a corrupt one";
+        return rc;
+    }
+    const unsigned long long bpp = t.bits / 8, line = (unsigned long long)t.W * t.spp * bpp, total = line * t.H;
+    if (t.comp != 1 && t.comp != 5) { why = "Deflate strips are decoded by the host reader"; return ECSEG_E_UNSUPPORTED; }
+    if ((unsigned long long)t.rps * line >= (1ull << 31) || total >= (1ull << 40)) {
+        why = "strips of 2 GiB or more, or an image of 1 TiB or more";
+        return ECSEG_E_UNSUPPORTED;
+    }
+    return with_strips ? tiff_strips_in_file(t, n, why) : ECSEG_OK;
+}
+
 int ecseg_tiff_decode(ecseg_ctx* h, const uint8_t* file, long long n_bytes, void* dst, long long dst_bytes, int* H, int* W, int* samples_per_pixel,
                       int* bits_per_sample) {
     if (!h) return ECSEG_E_INVALID;
@@ -642,20 +669,17 @@ int ecseg_tiff_decode(ecseg_ctx* h, const uint8_t* file, long long n_bytes, void
         return fail(h, ECSEG_E_INVALID, "tiff_decode: bad arguments");
     for (float& v : h->stage_ms) v = 0.f;
     TiffInfo t;
+    std::string why;
     const size_t n = (size_t)n_bytes;
-    int rc = parse_tiff(file, n, &t);
-    if (rc == ECSEG_E_UNSUPPORTED) return fail(h, rc, "tiff_decode: a layout the native readers leave to the Python reader");
-    if (rc != ECSEG_OK) return fail(h, rc, "tiff_decode: not a TIFF file, or a corrupt one");
-    *H = (int)t.H; *W = (int)t.W; *samples_per_pixel = (int)t.spp; *bits_per_sample = (int)t.bits;
+    bool parsed = false;
+    int rc = tiff_decode_verdict(file, n, false, t, &parsed, why);
+    if (parsed) { *H = (int)t.H; *W = (int)t.W; *samples_per_pixel = (int)t.spp; *bits_per_sample = (int)t.bits; }
+    if (rc != ECSEG_OK) return fail(h, rc, "tiff_decode: " + why);
     const unsigned long long bpp = t.bits / 8, line = (unsigned long long)t.W * t.spp * bpp, total = line * t.H;
-    if (t.comp != 1 && t.comp != 5) return fail(h, ECSEG_E_UNSUPPORTED, "tiff_decode: Deflate strips are decoded by the host reader");
-    if ((unsigned long long)t.rps * line >= (1ull << 31) || total >= (1ull << 40))
-        return fail(h, ECSEG_E_UNSUPPORTED, "tiff_decode: strips of 2 GiB or more, or an image of 1 TiB or more");
     if (!dst) return ECSEG_OK;
     if ((unsigned long long)dst_bytes < total) return fail(h, ECSEG_E_INVALID, "tiff_decode: the destination holds fewer bytes than the image");
+    if ((rc = tiff_strips_in_file(t, n, why)) != ECSEG_OK) return fail(h, rc, "tiff_decode: " + why);
     const size_t nstrips = ((size_t)t.H + t.rps - 1) / t.rps, n_table = std::min(t.off.size(), nstrips);
-    for (size_t k = 0; k < n_table; ++k)
-        if (t.off[k] > n) return fail(h, ECSEG_E_INVALID, "tiff_decode: strip " + std::to_string(k) + " starts behind the end of the file");
     HIP_TRY(h, hipSetDevice(h->device));
     TiffDecodeBufs b{};
     if ((rc = lay_out(h, h->call_arena, [&](Carver& c) { b = tiff_decode_bufs(c, n, (int)n_table, (size_t)total, (int)nstrips); }))) return rc;
@@ -673,6 +697,151 @@ int ecseg_tiff_decode(ecseg_ctx* h, const uint8_t* file, long long n_bytes, void
     for (size_t k = 0; k < nstrips; ++k)
         if (status[k]) return fail(h, ECSEG_E_INVALID, "tiff_decode: strip " + std::to_string(k) + " holds a corrupt LZW stream");
     HIP_TRY(h, hipMemcpyAsync(dst, b.raster, (size_t)total, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    return ECSEG_OK;
+}
+
+// ---- the same over a batch of files: every strip of every file is a wave of one launch ----------------------------------------------
+// The files of a batch as ecseg_tiff_decode judges each alone: info[i] and status[i] (with_strips as there), and the rows of the
+// layout for the files that are ECSEG_OK (dst_offsets may be null: the rasters back to back, 16-bit ones on even offsets).  Empty
+// string, or which argument is wrong.
+static std::string tiff_batch_plan(const uint8_t* files, long long files_bytes, const int64_t* ranges, int n_files, const int64_t* dst_offsets,
+                                   bool with_strips, std::vector<TiffInfo>& info, std::vector<int>& status, std::vector<TdFileIn>& in) {
+    info.assign((size_t)n_files, TiffInfo()); status.assign((size_t)n_files, ECSEG_OK); in.assign((size_t)n_files, TdFileIn());
+    long long end = 0;
+    for (int i = 0; i < n_files; ++i) {                      // the geometry first: nothing is read through a bad range
+        const long long off = ranges[2 * (size_t)i], nb = ranges[2 * (size_t)i + 1];
+        if (nb < 0 || off < end || off > files_bytes || nb > files_bytes - off)
+            return "file " + std::to_string(i) + ": its range overlaps the one in front or leaves the " + std::to_string(files_bytes) + " bytes of files";
+        end = off + nb;
+    }
+    unsigned long long packed = 0;
+    std::string why;
+    for (int i = 0; i < n_files; ++i) {
+        const size_t off = (size_t)ranges[2 * (size_t)i], nb = (size_t)ranges[2 * (size_t)i + 1];
+        TiffInfo& t = info[(size_t)i];
+        bool parsed = false;
+        status[(size_t)i] = tiff_decode_verdict(files + off, nb, with_strips, t, &parsed, why);
+        if (!parsed) t.H = t.W = 0;                          // (no shape to report)
+        if (status[(size_t)i] != ECSEG_OK) continue;
+        TdFileIn& f = in[(size_t)i];
+        const size_t nstrips = ((size_t)t.H + t.rps - 1) / t.rps;
+        f.in_batch = true; f.src_off = off; f.n_bytes = nb;
+        f.n_table = (uint32_t)std::min(t.off.size(), nstrips); f.H = t.H; f.W = t.W; f.spp = t.spp; f.bps = t.bits / 8; f.rps = t.rps;
+        f.lzw = t.comp == 5; f.swap = f.bps == 2 && !t.le; f.predictor = t.pred == 2;
+        if (dst_offsets) {
+            if (dst_offsets[i] < 0) return "file " + std::to_string(i) + ": a negative destination offset";
+            f.dst_off = (uint64_t)dst_offsets[i];
+        } else {
+            packed += packed & (f.bps - 1);
+            f.dst_off = packed;
+            packed += (unsigned long long)f.W * f.spp * f.bps * f.H;
+        }
+    }
+    return std::string();
+}
+
+int ecseg_tiff_decode_batch_counts(const uint8_t* file, long long n_bytes) {
+    TiffInfo t;
+    std::string why;
+    bool parsed = false;
+    return file && n_bytes >= 0 && tiff_decode_verdict(file, (size_t)n_bytes, true, t, &parsed, why) == ECSEG_OK && tiff_batch_counts(t) ? 1 : 0;
+}
+
+int ecseg_tiff_decode_batch_routes(const uint8_t* files, long long files_bytes, const int64_t* file_ranges, int n_files) {
+    if (n_files <= 0 || !files || !file_ranges || files_bytes < 0) return 0;
+    std::vector<TiffInfo> info; std::vector<int> status; std::vector<TdFileIn> in;
+    if (!tiff_batch_plan(files, files_bytes, file_ranges, n_files, nullptr, true, info, status, in).empty()) return 0;
+    std::vector<const TiffInfo*> ok;
+    for (int i = 0; i < n_files; ++i) if (status[(size_t)i] == ECSEG_OK) ok.push_back(&info[(size_t)i]);
+    return tiff_batch_goes_to_device(ok.data(), ok.size()) ? 1 : 0;
+}
+
+long long ecseg_tiff_decode_batch_bytes(const uint8_t* files, long long files_bytes, const int64_t* file_ranges, int n_files) {
+    if (n_files == 0) return 0;
+    if (n_files < 0 || !files || !file_ranges || files_bytes < 0) return -1;
+    std::vector<TiffInfo> info; std::vector<int> status; std::vector<TdFileIn> in;
+    if (!tiff_batch_plan(files, files_bytes, file_ranges, n_files, nullptr, true, info, status, in).empty()) return -1;
+    TdBatchLayout L;
+    if (!td_batch_layout(in, L).empty()) return -1;
+    Carver c;
+    (void)tiff_decode_batch_bufs(c, L);
+    return (long long)c.used;
+}
+
+int ecseg_tiff_decode_batch(ecseg_ctx* h, const uint8_t* files, long long files_bytes, const int64_t* file_ranges, int n_files, void* dst,
+                            long long dst_bytes, const int64_t* dst_offsets, int32_t* shapes, int32_t* status) {
+    if (!h) return ECSEG_E_INVALID;
+    drop_sent_ahead(h);
+    const std::string me = "tiff_decode_batch: ";
+    if (n_files < 0 || files_bytes < 0 || (n_files > 0 && (!files || !file_ranges || !shapes || !status)) ||
+        (dst && (dst_bytes < 0 || (n_files > 0 && !dst_offsets))))
+        return fail(h, ECSEG_E_INVALID, me + "bad arguments");
+    for (float& v : h->stage_ms) v = 0.f;
+    if (n_files == 0) return ECSEG_OK;
+    const size_t nf = (size_t)n_files;
+    std::vector<TiffInfo> info; std::vector<int> verdict; std::vector<TdFileIn> in;
+    std::string bad = tiff_batch_plan(files, files_bytes, file_ranges, n_files, dst ? dst_offsets : nullptr, dst != nullptr, info, verdict, in);
+    if (!bad.empty()) return fail(h, ECSEG_E_INVALID, me + bad);
+    if (dst) {                                               // every raster inside the destination and clear of the others
+        std::vector<std::pair<uint64_t, uint64_t>> spans;   // (offset, end) of the files that are decoded
+        for (size_t i = 0; i < nf; ++i) {
+            if (!in[i].in_batch) continue;
+            const uint64_t total = (uint64_t)in[i].W * in[i].spp * in[i].bps * in[i].H;
+            if (in[i].dst_off > (uint64_t)dst_bytes || total > (uint64_t)dst_bytes - in[i].dst_off)
+                return fail(h, ECSEG_E_INVALID, me + "file " + std::to_string(i) + ": its raster leaves the " + std::to_string(dst_bytes) + " bytes of the destination");
+            spans.emplace_back(in[i].dst_off, in[i].dst_off + total);
+        }
+        std::sort(spans.begin(), spans.end());
+        for (size_t k = 1; k < spans.size(); ++k)
+            if (spans[k].first < spans[k - 1].second) return fail(h, ECSEG_E_INVALID, me + "two rasters overlap in the destination");
+    }
+    TdBatchLayout L;
+    if (dst && !(bad = td_batch_layout(in, L)).empty()) return fail(h, ECSEG_E_INVALID, me + bad);
+    for (size_t i = 0; i < nf; ++i) {
+        const TiffInfo& t = info[i];
+        int32_t* q = shapes + 4 * i;
+        q[0] = (int32_t)t.H; q[1] = (int32_t)t.W; q[2] = t.H ? (int32_t)t.spp : 0; q[3] = t.H ? (int32_t)t.bits : 0;
+        status[i] = verdict[i];
+    }
+    if (!dst || L.n_strips == 0) return ECSEG_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    int rc;
+    TiffDecodeBatchBufs b{};
+    if ((rc = lay_out(h, h->call_arena, [&](Carver& c) { b = tiff_decode_batch_bufs(c, L); }))) return rc;
+    std::vector<uint32_t> tables((size_t)L.table_words);
+    for (size_t i = 0; i < nf; ++i) {
+        const TdFile& f = L.tab[i];
+        std::copy(info[i].off.begin(), info[i].off.begin() + f.n_table, tables.begin() + (size_t)f.table_off);
+        std::copy(info[i].cnt.begin(), info[i].cnt.begin() + f.n_table, tables.begin() + (size_t)f.table_off + f.n_table);
+    }
+    hipStream_t s = h->stream;
+    HIP_TRY(h, hipMemcpyAsync(b.files, files + L.src_base, (size_t)L.src_span, hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(b.tab, L.tab.data(), nf * sizeof(TdFile), hipMemcpyHostToDevice, s));
+    if (!tables.empty()) HIP_TRY(h, hipMemcpyAsync(b.tables, tables.data(), tables.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipEventRecord(h->ev[0], s));
+    HIP_TRY(h, run_tiff_decode_batch(b, L, s));
+    HIP_TRY(h, hipEventRecord(h->ev[1], s));
+    std::vector<uint32_t> corrupt(nf, 0);
+    HIP_TRY(h, hipMemcpyAsync(corrupt.data(), b.file_status, nf * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));                     // (L.tab and tables are read by the copies above: they live until here)
+    h->stage_ms[ECSEG_T_COUNT] = stage_elapsed(h->ev[0], h->ev[1]);
+    // the rasters of the clean files, a run without a gap in one copy: all of them at once where the caller packed them
+    std::vector<std::pair<uint64_t, uint64_t>> runs;
+    for (size_t i = 0; i < nf; ++i) {
+        if (!L.tab[i].in_batch) continue;
+        if (corrupt[i]) { status[i] = ECSEG_E_INVALID; continue; }
+        runs.emplace_back(L.tab[i].raster_off, L.tab[i].raster_off + td_file_raster_bytes(L.tab[i]));
+    }
+    std::sort(runs.begin(), runs.end());
+    for (size_t k = 0; k < runs.size();) {
+        size_t e = k + 1;
+        uint64_t end = runs[k].second;
+        while (e < runs.size() && runs[e].first == end) end = runs[e++].second;
+        HIP_TRY(h, hipMemcpyAsync(static_cast<uint8_t*>(dst) + L.dst_base + runs[k].first, b.rasters + runs[k].first, (size_t)(end - runs[k].first),
+                                  hipMemcpyDeviceToHost, s));
+        k = e;
+    }
     HIP_TRY(h, hipStreamSynchronize(s));
     return ECSEG_OK;
 }

@@ -1,0 +1,108 @@
+// A batch of TIFF files for one decode (ecseg_tiff_decode_batch, drivers.hip; the tiffb_* kernels, tiff_decode_kernels.hip): the
+// device table, one TdFile row per file, and the one function that lays a batch out - where every file image, strip table and
+// raster lies in the packed buffers, the prefix sums over strips and rows that give every workgroup its file, and the arena the
+// call carves.  Plain C++: the driver includes it, and so does tools/asan/tiff_decode_batch_fuzz.cpp, which walks the same table on
+// the host (as watershed_batch_bufs runs on a measuring Carver).
+//   The files are uploaded as the caller holds them, one span from the first file's first byte to the last file's last, and the
+// rasters lie on the device as they will in the caller's destination, relative to `dst_base`: a run of rasters without a gap is one
+// copy back.  A 16-bit raster is read and written as uint16_t: its offset must be even (dst_base is, and the buffers start on 256
+// bytes).  A file of zero strips (one the call leaves out: not OK, or a shape alone) owns nothing and no workgroup finds it.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+#include <string>
+#include <vector>
+
+#include "scratch.h"
+
+namespace ecseg {
+
+struct TdFile {
+    uint64_t file_off;       // of the file image in the packed upload
+    uint64_t n_bytes;
+    uint64_t table_off;      // in uint32_t: n_table strip offsets, then n_table byte counts, in the packed tables
+    uint64_t raster_off;     // of the raster in the packed output
+    uint64_t line;           // bytes of a row: W * spp * bps
+    uint32_t n_table;        // entries of the strip tables the image has rows for
+    uint32_t H, rps, W, spp, bps;
+    uint32_t first_strip;    // global index of strip 0 (grid x of tiffb_unstrip_kernel); the file has ceil(H / rps) strips
+    uint32_t first_row;      // global index of row 0 (grid x of tiffb_unpredict_kernel); the file has H rows
+    uint8_t lzw, swap, predictor, in_batch;      // LZW or uncompressed strips; 16-bit samples in the other byte order; horizontal predictor; 0: a file of zero strips
+    uint32_t pad;
+};
+static_assert(sizeof(TdFile) == 80, "the device table is an array of 80-byte rows, copied as it is");
+
+// What the layout is made from, per file: the tags (parse_tiff), where the caller keeps the file and wants the raster.
+struct TdFileIn {
+    uint64_t src_off = 0, n_bytes = 0, dst_off = 0;
+    uint32_t n_table = 0, H = 0, W = 0, spp = 1, bps = 1, rps = 1;
+    bool lzw = false, swap = false, predictor = false;
+    bool in_batch = false;   // false: the file takes no part (zero strips, zero rows, nothing uploaded for it)
+};
+
+struct TdBatchLayout {
+    std::vector<TdFile> tab;                     // one row per file, the files left out included
+    uint64_t src_base = 0, src_span = 0;         // the upload: bytes [src_base, src_base + src_span) of the caller's files
+    uint64_t dst_base = 0, dst_span = 0;         // the rasters: bytes [dst_base, dst_base + dst_span) of the caller's destination (dst_base even)
+    uint64_t table_words = 0;                    // uint32_t of all strip tables
+    uint64_t n_strips = 0, n_rows = 0;           // the two grids
+    bool any_u8_predictor = false, any_u16_pass = false;     // which tiffb_unpredict_kernel launches the batch needs
+};
+
+constexpr uint64_t TD_BATCH_MAX_GRID = (1ull << 31) - 1;     // grid dimension x
+
+inline uint64_t td_file_strips(const TdFile& f) { return f.in_batch ? ((uint64_t)f.H + f.rps - 1) / f.rps : 0; }
+inline uint64_t td_file_raster_bytes(const TdFile& f) { return f.in_batch ? f.line * f.H : 0; }
+
+// Empty string, or what is wrong: a 16-bit raster at an odd offset, or more strips or rows than a grid has.  The caller has made
+// sure that ranges do not overlap.
+inline std::string td_batch_layout(const std::vector<TdFileIn>& in, TdBatchLayout& L) {
+    L = TdBatchLayout();
+    L.tab.resize(in.size());
+    uint64_t src_lo = UINT64_MAX, src_hi = 0, dst_lo = UINT64_MAX, dst_hi = 0;
+    for (const TdFileIn& f : in) {
+        if (!f.in_batch) continue;
+        const uint64_t raster = (uint64_t)f.W * f.spp * f.bps * f.H;
+        src_lo = f.src_off < src_lo ? f.src_off : src_lo;
+        src_hi = f.src_off + f.n_bytes > src_hi ? f.src_off + f.n_bytes : src_hi;
+        dst_lo = f.dst_off < dst_lo ? f.dst_off : dst_lo;
+        dst_hi = f.dst_off + raster > dst_hi ? f.dst_off + raster : dst_hi;
+    }
+    if (src_lo == UINT64_MAX) src_lo = src_hi = dst_lo = dst_hi = 0;
+    L.src_base = src_lo; L.src_span = src_hi - src_lo;
+    L.dst_base = dst_lo & ~1ull; L.dst_span = dst_hi - L.dst_base;
+    for (size_t i = 0; i < in.size(); ++i) {
+        const TdFileIn& f = in[i];
+        TdFile& t = L.tab[i];
+        t = TdFile();
+        t.first_strip = (uint32_t)L.n_strips; t.first_row = (uint32_t)L.n_rows; t.table_off = L.table_words;
+        t.rps = 1;
+        if (!f.in_batch) continue;
+        if (f.bps == 2 && (f.dst_off & 1)) return "file " + std::to_string(i) + ": a 16-bit raster at an odd offset";
+        t.in_batch = 1;
+        t.file_off = f.src_off - L.src_base; t.n_bytes = f.n_bytes; t.raster_off = f.dst_off - L.dst_base;
+        t.line = (uint64_t)f.W * f.spp * f.bps;
+        t.n_table = f.n_table; t.H = f.H; t.rps = f.rps; t.W = f.W; t.spp = f.spp; t.bps = f.bps;
+        t.lzw = f.lzw; t.swap = f.swap && f.bps == 2; t.predictor = f.predictor;
+        L.table_words += 2ull * f.n_table;
+        L.n_strips += td_file_strips(t);
+        L.n_rows += f.H;
+        if (L.n_strips > TD_BATCH_MAX_GRID || L.n_rows > TD_BATCH_MAX_GRID) return "the batch holds 2^31 strips or rows, or more";
+        L.any_u16_pass = L.any_u16_pass || (t.bps == 2 && (t.swap || t.predictor));
+        L.any_u8_predictor = L.any_u8_predictor || (t.bps == 1 && t.predictor);
+    }
+    return std::string();
+}
+
+// Device buffers of one batch: the table, the file images, the strip tables, the rasters, one status word per strip and one per file.
+struct TiffDecodeBatchBufs { TdFile* tab; uint8_t* files; uint32_t* tables; uint8_t* rasters; uint32_t* strip_status; uint32_t* file_status; };
+inline TiffDecodeBatchBufs tiff_decode_batch_bufs(Carver& c, const TdBatchLayout& L) {
+    TiffDecodeBatchBufs b;
+    b.tab = c.take<TdFile>(L.tab.size()); b.files = c.take<uint8_t>((size_t)L.src_span); b.tables = c.take<uint32_t>((size_t)L.table_words);
+    b.rasters = c.take<uint8_t>((size_t)L.dst_span); b.strip_status = c.take<uint32_t>((size_t)L.n_strips);
+    b.file_status = c.take<uint32_t>(L.tab.size());
+    return b;
+}
+
+}  // namespace ecseg

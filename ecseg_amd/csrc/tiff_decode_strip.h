@@ -20,6 +20,8 @@
 #pragma once
 #include <stdint.h>
 
+#include "tiff_decode_batch.h"
+
 #ifdef __HIPCC__
 #define TD_FN __device__ __forceinline__
 #define TD_FOR_LANES(lane) for (int lane = (int)threadIdx.x, td_once_ = 1; td_once_; td_once_ = 0)
@@ -130,6 +132,62 @@ TD_FN uint32_t td_lzw_strip(const uint8_t* src, uint32_t have, uint8_t* dst, uin
         for (uint32_t k = got + (uint32_t)lane; k < want; k += 64) dst[k] = 0;
     }
     return cmd == TD_CORRUPT ? 1u : 0u;
+}
+
+// ---- a strip's place in its file and its raster; the uncompressed strip; the same for a strip of a batch --------------------------
+struct TdStrip { const uint8_t* src; uint8_t* dst; uint32_t have, want; bool in_table, behind_file; };
+
+// Strip `strip` of a file: rows [strip * rps, ...) of the raster, bytes [off, off + min(cnt, n - off)) of the file.
+TD_FN TdStrip td_strip(uint32_t strip, const uint8_t* file, unsigned long long n, const uint32_t* offs, const uint32_t* cnts, uint32_t n_table,
+                       uint32_t H, unsigned long long line, uint32_t rps, uint8_t* raster) {
+    const unsigned long long r0 = (unsigned long long)strip * rps;
+    TdStrip t{file, raster, 0u, 0u, false, false};
+    if (r0 >= H) return t;                                   // (the grid has ceil(H / rps) strips: never)
+    const unsigned long long rows = r0 + rps <= H ? rps : H - r0;
+    t.want = (uint32_t)(rows * line);                        // (below 2^31: the driver refuses longer strips)
+    t.dst = raster + r0 * line;
+    if (strip >= n_table) return t;
+    t.in_table = true;
+    const unsigned long long off = offs[strip], cnt = cnts[strip];
+    if (off > n) { t.behind_file = true; return t; }
+    t.src = file + off;
+    t.have = (uint32_t)(cnt < n - off ? cnt : n - off);
+    return t;
+}
+
+// An uncompressed strip: a clamped copy and the zero fill, by `nlanes` lanes (the threads of the workgroup).
+TD_FN void td_raw_strip(const TdStrip& t, uint32_t nlanes) {
+    const uint32_t got = t.have < t.want ? t.have : t.want;
+    TD_FOR_LANES(lane) {
+        for (uint32_t k = (uint32_t)lane; k < t.want; k += nlanes) t.dst[k] = k < got ? t.src[k] : (uint8_t)0;
+    }
+}
+
+// The file of global strip (rows == false) or row (rows == true) `idx` of a batch: the last row of the table that starts at or
+// before it.  Files of zero strips share their start with the file behind them and are never the last such row, except at the
+// table's end, which no index reaches.  n >= 1.
+TD_FN uint32_t td_find_file(const TdFile* tab, uint32_t n, uint32_t idx, bool rows) {
+    uint32_t lo = 0, hi = n;
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if ((rows ? tab[mid].first_row : tab[mid].first_strip) <= idx) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+// Global strip `strip` of a batch, by one wave: td_lzw_strip or td_raw_strip on the strip's file.  Returns its status word (0, or 1:
+// corrupt stream / offset behind the file), the same in every lane.
+TD_FN uint32_t tdb_unstrip(const TdFile* tab, uint32_t n_files, const uint8_t* files, const uint32_t* tables, uint8_t* rasters, uint32_t strip,
+                           TdLds& L) {
+    const TdFile& f = tab[td_first(td_find_file(tab, n_files, strip, false))];
+    const uint32_t k = strip - f.first_strip;
+    if (!f.in_batch || (unsigned long long)k * f.rps >= f.H) return 0u;      // (the grid has the strips of the table: never)
+    const uint32_t* offs = tables + f.table_off;
+    const TdStrip t = td_strip(k, files + f.file_off, f.n_bytes, offs, offs + f.n_table, f.n_table, f.H, f.line, f.rps, rasters + f.raster_off);
+    uint32_t st = 0;
+    if (f.lzw) st = td_lzw_strip(t.src, t.have, t.dst, t.want, L);           // (have == 0: nothing is read, the strip is zeros)
+    else td_raw_strip(t, 64u);
+    return t.behind_file ? 1u : st;
 }
 
 }  // namespace ecseg

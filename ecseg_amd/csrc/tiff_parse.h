@@ -32,4 +32,31 @@ inline bool tiff_goes_to_device(const TiffInfo& t) {
     return nstrips >= TIFF_DEVICE_MIN_STRIPS && t.off.size() >= nstrips;
 }
 
+// The routing rule for a set of files that would go in one ecseg_tiff_decode_batch call, the only place that decides it
+// (ecseg_tiff_decode_batch_routes asks it for image_io.imread_many).  The strips of different files decode side by side as the strips
+// of one file do, so what counts is their sum: the set goes when the LZW strips of its files - those ecseg_tiff_decode accepts,
+// whatever their own strip count - are at least TIFF_BATCH_DEVICE_MIN_STRIPS together.  Uncompressed and Deflate files are never
+// counted (and never sent: tiff_batch_counts is false for them), for the reasons above.  The measurement is the batch table of
+// DESIGN.md 5.9 (tools/time_tiff_decode.py --batch: 1 to 32 files of the 1040 x 1392 RGB scene at 1, 5 and 15 rows per strip, and the
+// stat_fish pair): every measured set of 1040 strips or more is read faster through the device than by ecseg_tiff_read on one core
+// (the batch's maximum below the host's minimum), at each of the three plans; so is every measured set from 416 strips up, and the
+// sets of 280 strips or fewer lose - the threshold stays at the single-file 1040 here, and lowering it to 416 is the follow-up that
+// table supports.  Nothing was measured above 15 rows of 4176 bytes per strip, where a single wave takes 174 ms and more for its
+// strip: a file whose strips decode to more than TIFF_BATCH_DEVICE_MAX_STRIP_BYTES is not counted either.  files: the parsed files that
+// ecseg_tiff_decode accepts.
+constexpr size_t TIFF_BATCH_DEVICE_MIN_STRIPS = 1040;
+constexpr unsigned long long TIFF_BATCH_DEVICE_MAX_STRIP_BYTES = 15ull * 1392 * 3;
+inline bool tiff_batch_counts(const TiffInfo& t) {
+    if (t.comp != 5 || t.rps == 0 || t.H == 0) return false;
+    const size_t nstrips = ((size_t)t.H + t.rps - 1) / t.rps;
+    return t.off.size() >= nstrips &&                        // (a strip table shorter than the image stays on the host, as in the single-file rule)
+           (unsigned long long)(t.rps < t.H ? t.rps : t.H) * t.W * t.spp * (t.bits / 8) <= TIFF_BATCH_DEVICE_MAX_STRIP_BYTES;
+}
+inline bool tiff_batch_goes_to_device(const TiffInfo* const* files, size_t n) {
+    size_t strips = 0;
+    for (size_t i = 0; i < n; ++i)
+        if (tiff_batch_counts(*files[i])) strips += ((size_t)files[i]->H + files[i]->rps - 1) / files[i]->rps;
+    return strips >= TIFF_BATCH_DEVICE_MIN_STRIPS;
+}
+
 }  // namespace ecseg

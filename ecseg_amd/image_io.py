@@ -15,7 +15,7 @@ import zlib
 
 import numpy as np
 
-from ._lib import E_IO, E_UNSUPPORTED, load_library
+from ._lib import E_IO, E_UNSUPPORTED, load_library, pack_file_images
 
 # class k -> RGBA of ListedColormap(['#386cb0', '#ffff99', '#7fc97f', '#f0027f']) with vmin=0, vmax=4
 # (reference src/metaseg.py:47,52)
@@ -252,6 +252,62 @@ def imread(path, handle=None):
         if a is not None:
             return a
     return read_tiff(path)
+
+
+def tiff_batch_goes_to_device(datas):
+    """The routing rule for a set of files (csrc/tiff_parse.h, the one place that states it) on their bytes -> (whether the set goes to
+    the device in one ``Handle.tiff_decode_many``, per file whether the rule counts it: the files that are sent when it goes)."""
+    lib = load_library()
+    bufs = [d if isinstance(d, np.ndarray) else np.frombuffer(d, np.uint8) for d in datas]
+    counts = [bool(b.size) and lib.ecseg_tiff_decode_batch_counts(b.ctypes.data_as(C.c_void_p), b.size) == 1 for b in bufs]
+    sent = [b for b, c in zip(bufs, counts) if c]
+    if not sent:
+        return False, counts
+    buf, ranges = pack_file_images(sent)                     # (no copy where the files lie in one buffer, as imread_many reads them)
+    goes = lib.ecseg_tiff_decode_batch_routes(buf.ctypes.data_as(C.c_void_p), buf.size, ranges.ctypes.data_as(C.c_void_p), len(ranges)) == 1
+    return goes, counts
+
+
+def imread_many(paths, handle=None):
+    """``imread`` over a list of paths -> a list with, per path, the array ``imread(path)`` returns or the exception it raises, in its
+    place.  ``handle``: anything with ``Handle.tiff_decode_many``: the ``.tif`` / ``.tiff`` files the routing rule for a set counts
+    (ecseg_tiff_decode_batch_routes: LZW files, whatever their strip count) are decoded in one call when together they are worth it;
+    every other file, and every file that call answers with None or an error, is read by ``imread(path)``, so that the samples and
+    the errors are always its own."""
+    out = [None] * len(paths)
+    if handle is not None and hasattr(handle, 'tiff_decode_many'):
+        tiffs = [(k, str(path)) for k, path in enumerate(paths) if str(path).lower().endswith(('.tif', '.tiff'))]
+        sizes = []
+        for _, path in tiffs:
+            try:
+                sizes.append(os.path.getsize(path))
+            except OSError:
+                sizes.append(-1)
+        pool = np.empty(sum(n for n in sizes if n > 0), np.uint8)   # the file images in one buffer: the rule and the device call read them where they lie
+        held, at = [], 0                                         # (position, bytes)
+        for (k, path), n in zip(tiffs, sizes):
+            if n <= 0:
+                continue
+            try:
+                with open(path, 'rb') as f:
+                    got = f.readinto(memoryview(pool[at:at + n]))
+            except OSError:
+                continue
+            held.append((k, pool[at:at + got]))
+            at += n
+        goes, counts = tiff_batch_goes_to_device([d for _, d in held])
+        if goes:
+            sent = [e for e, c in zip(held, counts) if c]
+            for (k, _), a in zip(sent, handle.tiff_decode_many([d for _, d in sent])):
+                if isinstance(a, np.ndarray):
+                    out[k] = a
+    for k, path in enumerate(paths):
+        if out[k] is None:
+            try:
+                out[k] = imread(path)
+            except Exception as e:
+                out[k] = e
+    return out
 
 
 def _ifd_entry(tag, typ, count, value):

@@ -223,13 +223,16 @@ def render(img, channels, thresholded, boundaries):
     return original, with_segmentation(original, boundaries, 1), np.stack(lsq[::-1], axis=-1)
 
 
-def read_image(path, handle, max_probes=2, tiff_read_on_device=False):
+def read_image(path, handle, max_probes=2, tiff_read_on_device=False, pre=None):
     """-> ((H, W, C) uint8 image, its (blue, green, red[, aqua]) channel indices) (src/stat_fish.py:206-212).  C is 3, or 4 for a
     four-channel ``.npy`` when ``max_probes`` (the entries of ``color_sensitivity``) is at least 3.  ``tiff_read_on_device``: a TIFF's
-    strips are decoded by ``handle.tiff_decode`` (``image_io.imread(path, handle=handle)``)."""
+    strips are decoded by ``handle.tiff_decode`` (``image_io.imread(path, handle=handle)``).  ``pre``: what ``image_io.imread_many``
+    returned for the file, an array or the exception, when it was read ahead with its chunk (config key ``tiff_read_batch``)."""
     from . import image_io
     try:
-        I = image_io.imread(path, handle=handle if tiff_read_on_device else None)
+        if isinstance(pre, Exception):
+            raise pre
+        I = pre if pre is not None else image_io.imread(path, handle=handle if tiff_read_on_device else None)
     except Exception as e:
         raise ImageError('cannot be read (%s)' % e)
     is_npy = path.lower().endswith('.npy')
@@ -258,13 +261,16 @@ def read_image(path, handle, max_probes=2, tiff_read_on_device=False):
     return np.ascontiguousarray(I), (2, 1, 0)
 
 
-def read_mask(path, handle=None):
-    """``handle``: the mask's strips are decoded by ``handle.tiff_decode`` (config key ``tiff_read_on_device``)."""
+def read_mask(path, handle=None, pre=None):
+    """``handle``: the mask's strips are decoded by ``handle.tiff_decode`` (config key ``tiff_read_on_device``).  ``pre``: as
+    ``read_image``'s."""
     from . import image_io
     if not os.path.exists(path):
         raise ImageError('has no nucleus mask %s' % path)
     try:
-        m = image_io.imread(path, handle=handle)
+        if isinstance(pre, Exception):
+            raise pre
+        m = pre if pre is not None else image_io.imread(path, handle=handle)
     except Exception as e:
         raise ImageError('nucleus mask %s cannot be read (%s)' % (path, e))
     if m.ndim == 3 and m.shape[2] == 1:
@@ -275,7 +281,7 @@ def read_mask(path, handle=None):
 
 
 def process_image(path, mask_path, out_root, params, scale, handle, stats=None, use_min_cut=False, segment=None, tiff_on_device=False,
-                  tiff_read_on_device=False):
+                  tiff_read_on_device=False, pre_read=None):
     """One image of src/stat_fish.py:199-308 -> (CSV rows, the scale that was used); the rows of a four-channel image carry the aqua
     fields of ``csv_columns(3)``, and ``stats['probes']`` becomes 3 once such an image was seen (it may have no nucleus and no row).  The three colour files come from ``handle.fish_render`` when the handle has it, else from
     ``render``, which writes the same bytes.  ``use_min_cut`` (:221-224): the label map comes
@@ -285,14 +291,16 @@ def process_image(path, mask_path, out_root, params, scale, handle, stats=None, 
     ``handle.fish_render_tiff``, which renders them there too, the mask and the min-cut picture by ``handle.tiff_encode`` - and
     reaches the disk as the file image these return; the bytes are those of the host writers.  ``tiff_read_on_device`` (the config key
     of that name): the image and the mask are read with ``handle.tiff_decode`` where the device reader takes the file; the samples are
-    those of the host readers."""
+    those of the host readers.  ``pre_read`` (config key ``tiff_read_batch``): ``(image, mask)`` as ``image_io.imread_many`` returned them
+    for ``path`` and ``mask_path`` - an array, the exception, or None for "read it here" - when the files were read ahead with their chunk."""
     import time
     from . import image_io
     t0 = time.perf_counter()
     img_name = os.path.basename(path)[:-4]
-    I, channels = read_image(path, handle, len(params['color_sensitivity']), tiff_read_on_device)
+    pre_image, pre_mask = pre_read if pre_read is not None else (None, None)
+    I, channels = read_image(path, handle, len(params['color_sensitivity']), tiff_read_on_device, pre_image)
     blue = channels[0]
-    mask = read_mask(mask_path, handle if tiff_read_on_device else None) if segment is None else segment(I[:, :, blue])
+    mask = read_mask(mask_path, handle if tiff_read_on_device else None, pre_mask) if segment is None else segment(I[:, :, blue])
     imheight, imwidth = mask.shape
     I = np.ascontiguousarray(I[:imheight, :imwidth])
     mask = np.ascontiguousarray(mask[:I.shape[0], :I.shape[1]])
@@ -476,7 +484,7 @@ def main(argv=None, handle=None):
     the working directory; ``argv`` is accepted for the shim's sake and not read.  ``handle`` is an injection point for tests and
     tools (anything with ``Handle.ccl_labels``, ``fish_spots`` and ``u16_to_u8``, and ``min_cut`` for ``use_min_cut: True``; ``fish_render``
     is used when it is there, ``tiff_encode`` and ``fish_render_tiff`` are needed for ``tiff_on_device: true``, ``tiff_decode`` for
-    ``tiff_read_on_device: true``); without it the call opens a handle on device 0
+    ``tiff_read_on_device: true``, ``tiff_decode_many`` too for ``tiff_read_batch`` above 1); without it the call opens a handle on device 0
     and closes it at the end."""
     import yaml
     from . import csvio
@@ -519,6 +527,15 @@ def main(argv=None, handle=None):
         if tiff_read_on_device and handle is not None and not hasattr(handle, 'tiff_decode'):
             raise ConfigError('tiff_read_on_device: true needs the device TIFF reader (tiff_decode), which the handle in use '
                               'does not have; only tiff_read_on_device: false works on it')
+        read_batch = var.get('tiff_read_batch', 1)
+        if isinstance(read_batch, bool) or not isinstance(read_batch, int) or read_batch < 1:
+            raise ConfigError('tiff_read_batch must be a positive integer (how many images, with their masks, are read in one call of the '
+                              'device TIFF reader; 1: one by one)')
+        if not tiff_read_on_device:
+            read_batch = 1                                   # the key belongs to the device reader
+        if read_batch > 1 and handle is not None and not hasattr(handle, 'tiff_decode_many'):
+            raise ConfigError('tiff_read_batch: %d needs the batched device TIFF reader (tiff_decode_many), which the handle in use does not '
+                              'have; only tiff_read_batch: 1 works on it' % read_batch)
         if segmenter is None and not os.path.isdir(masks):
             raise ConfigError('The folder of nucleus masks %s does not exist (config key masks): it holds one 8-bit <name>.tif per '
                               'image, non-zero = nucleus' % masks)
@@ -546,6 +563,21 @@ def main(argv=None, handle=None):
         handle = Handle(0)
     keep_freed_memory()
     rows, failed, seen = [], [], {}
+    mask_of = lambda p: os.path.join(masks, os.path.basename(p)[:-4] + '.tif')
+    ahead = {}                                               # tiff_read_batch: image path -> (image, mask) read with its chunk, until the image is done
+
+    def read_ahead(k):                                       # image k opens a chunk of read_batch images: their files, and their masks where those are files, in one call
+        if read_batch == 1 or k % read_batch:
+            return
+        import time
+        from . import image_io
+        chunk = image_paths[k:k + read_batch]
+        files = chunk + ([mask_of(p) for p in chunk if os.path.exists(mask_of(p))] if segmenter is None else [])
+        t0 = time.perf_counter()
+        got = dict(zip(files, image_io.imread_many(files, handle=handle)))
+        seen['read'] = seen.get('read', 0.0) + time.perf_counter() - t0
+        for p in chunk:
+            ahead[p] = (got[p], got.get(mask_of(p)) if segmenter is None else None)
 
     def handed_in(mask):                                     # the `segment` hook of process_image for a mask computed with its chunk
         def segment(blue):
@@ -561,9 +593,10 @@ def main(argv=None, handle=None):
                 hooks[chunk[0]] = lambda blue: segmenter(blue, handle)
             elif segmenter is not None:                      # nuset_batch: the chunk's blue channels (and nothing else of them) are held at once
                 blues = []
-                for p in chunk:
+                for k, p in enumerate(chunk, at):
                     try:
-                        I, channels = read_image(p, handle, len(params['color_sensitivity']), tiff_read_on_device)
+                        read_ahead(k)
+                        I, channels = read_image(p, handle, len(params['color_sensitivity']), tiff_read_on_device, ahead.get(p, (None, None))[0])
                         blues.append((p, np.ascontiguousarray(I[:, :, channels[0]])))
                     except ImageError as e:
                         hooks[p] = handed_in(e)              # (process_image meets and reports it at the image's turn)
@@ -571,12 +604,14 @@ def main(argv=None, handle=None):
                 for (p, _), m in zip(blues, segmenter.many([b for _, b in blues], handle)):
                     hooks[p] = handed_in(m)
                 blues = None
-            for p in chunk:
+            for k, p in enumerate(chunk, at):
                 print("Processing image: ", p)
                 try:
-                    img_rows, scale = process_image(p, os.path.join(masks, os.path.basename(p)[:-4] + '.tif'), out_root, params, scale, handle,
+                    if p not in ahead:
+                        read_ahead(k)
+                    img_rows, scale = process_image(p, mask_of(p), out_root, params, scale, handle,
                                                      stats=seen, use_min_cut=use_min_cut, segment=hooks.get(p), tiff_on_device=tiff_on_device,
-                                                     tiff_read_on_device=tiff_read_on_device)
+                                                     tiff_read_on_device=tiff_read_on_device, pre_read=ahead.pop(p, None))
                     rows += img_rows
                 except ImageError as e:
                     print(p, '-', e)

@@ -51,6 +51,8 @@ extern "C" {
  * `make metaseg`'s dapi TIFFs and label PNGs encoded on the device; nothing existing changed.) */
 /* (still 5 - additive: ecseg_tiff_decode and ecseg_tiff_decode_routes, stat_fish's input TIFFs decoded on the device; nothing existing
  * changed.) */
+/* (still 5 - additive: ecseg_tiff_decode_batch, ecseg_tiff_decode_batch_bytes, ecseg_tiff_decode_batch_routes and
+ * ecseg_tiff_decode_batch_counts, many TIFF files decoded in one device call, a wave per strip of any file; nothing existing changed.) */
 /* (still 5 - additive: ecseg_ccl_pass_debug, one connected-component labelling pass alone with everything it produced read back, for
  * the tests of the labelling kernels; nothing existing changed.) */
 #define ECSEG_ABI_VERSION 5
@@ -451,6 +453,36 @@ int ecseg_tiff_decode(ecseg_ctx* h, const uint8_t* file, long long n_bytes, void
  * so the device is faster than a host core only where many strips decode at once; the measurement behind the threshold is in
  * DESIGN.md 5.9.  No device work. */
 int ecseg_tiff_decode_routes(const uint8_t* file, long long n_bytes);
+/* ecseg_tiff_decode over n_files files in one call (csrc/tiff_decode_kernels.hip, the tiffb_* kernels): the strips of all files are
+ * one grid, a wave per strip, so files of few strips find in each other the parallelism one of them lacks.  files: files_bytes of
+ * host memory; file i is bytes [file_ranges[2 i], file_ranges[2 i] + file_ranges[2 i + 1]) of it, the ranges in ascending order
+ * and clear of each other.  status[i] is what ecseg_tiff_decode returns for file i alone (ECSEG_OK, ECSEG_E_INVALID,
+ * ECSEG_E_UNSUPPORTED), shapes[4 i ..] its H, W, samples per pixel and bits per sample (zeros where the file has no shape).  A file
+ * that is not ECSEG_OK is left out of the launch: its raster is not written - a corrupt LZW stream is found on the device, and that
+ * file's raster is not copied back - and it disturbs no other file.  The raster of file i goes to dst + dst_offsets[i], native-endian
+ * (H, W, spp) as there; dst_offsets of files that are not decoded are not read.  dst == NULL: only shapes and status, without the
+ * verdicts that need the strips (an offset behind the file, a corrupt stream), as ecseg_tiff_decode's own first pass.
+ * Returns ECSEG_OK when it ran, whatever the status words say; ECSEG_E_INVALID only for bad arguments: n_files < 0, a null pointer,
+ * a range that starts before the end of the one in front or leaves files_bytes, a raster that leaves dst_bytes or overlaps another
+ * file's, a 16-bit raster at an odd offset, 2^31 strips or rows or more in all.  n_files == 0 is ECSEG_OK and does nothing.
+ * One synchronous call: the files are uploaded as one span (first decoded file's first byte to the last one's last), the table and
+ * the strip tables beside it; the rasters lie on the device as in dst and come back in one copy per run of rasters without a gap - one
+ * copy where the caller packed them.  Scratch from the handle's call arena; device time of the kernels in ECSEG_T_COUNT. */
+int ecseg_tiff_decode_batch(ecseg_ctx* h, const uint8_t* files, long long files_bytes, const int64_t* file_ranges /* [n][2] offset, n_bytes */,
+                            int n_files, void* dst, long long dst_bytes, const int64_t* dst_offsets /* [n] */,
+                            int32_t* shapes /* [n][4] H, W, spp, bits */, int32_t* status /* [n] */);
+/* The bytes of the call arena ecseg_tiff_decode_batch needs for these files with their rasters back to back (16-bit ones on even
+ * offsets), for a caller that splits a large set into several calls; -1 for bad arguments, 0 for no files.  No device work. */
+long long ecseg_tiff_decode_batch_bytes(const uint8_t* files, long long files_bytes, const int64_t* file_ranges, int n_files);
+/* The one rule that says whether a set of files is worth sending to ecseg_tiff_decode_batch (image_io.imread_many asks it): 1 when
+ * the LZW strips of the files ecseg_tiff_decode accepts, whatever their own strip count, are at least 1040 together; uncompressed
+ * and Deflate files are never counted, nor files whose strips decode to more than 62640 bytes (nothing was measured there) or whose
+ * strip table is shorter than the image (as in the single-file rule).  0 for
+ * everything else, bad arguments included.  ecseg_tiff_decode_batch_counts: 1 for a
+ * file that the rule counts - the files of a set that goes which are sent -, 0 for any other.  The measurement behind the threshold
+ * is the batch table of DESIGN.md 5.9.  No device work. */
+int ecseg_tiff_decode_batch_routes(const uint8_t* files, long long files_bytes, const int64_t* file_ranges, int n_files);
+int ecseg_tiff_decode_batch_counts(const uint8_t* file, long long n_bytes);
 
 /* ---- label PNG files encoded on the device ----------------------------------------------------------------------------------- */
 /* The file ecseg_png_write_labels would write for each of n_img label images, byte for byte (signature, IHDR, one IDAT, IEND), as

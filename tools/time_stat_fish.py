@@ -1,7 +1,7 @@
 """Timing of ``make stat_fish`` on synthetic full-size scenes.
 
     python tools/time_stat_fish.py [--images 16] [--reps 5] [--cpu-workers 16] [--channels 4] [--main-passes 3]
-                                   [--tiff-on-device off|on|alternate] [--tiff-read-on-device off|on|alternate] [--no-cpu-baseline]
+                                   [--tiff-on-device off|on|alternate] [--tiff-read-on-device off|on|alternate] [--tiff-read-batch K] [--no-cpu-baseline]
 
 Per 1040 x 1392 scene with 300 nuclei (tests/stat_fish_cases.py ``full_size_scene``) it reports
   * device milliseconds per image of ecseg_fish_spots (ECSEG_T_COUNT: the kernels alone), of the nucleus labelling in front of
@@ -16,6 +16,8 @@ Per 1040 x 1392 scene with 300 nuclei (tests/stat_fish_cases.py ``full_size_scen
   * with ``--tiff-read-on-device on`` ``main()`` runs under ``tiff_read_on_device: true`` (the input TIFFs decoded on the device), with
     ``alternate`` that key off and on in turn, twice (``main_by_read_key``; ``--tiff-on-device on`` then holds in all four), and the read
     stage of ``process_image`` per image is reported beside the write stage;
+  * with ``--tiff-read-batch K`` (K above 1) ``tiff_read_on_device: true`` holds throughout and ``tiff_read_batch`` 1 and K alternate,
+    twice (``main_by_read_batch``); the read stage then includes the chunks that ``main()`` reads ahead;
   * the same scenes through the vectorised numpy / scipy restatement tests/stat_fish_ref.py ``records`` on one core and on a
     pool of --cpu-workers processes, as the baseline.
 With ``--channels 4`` the scenes are four-channel ``.npy`` images (blue, green, red and an aqua channel made of the green one shifted
@@ -56,6 +58,7 @@ def main():
     ap.add_argument('--main-passes', type=int, default=3)
     ap.add_argument('--tiff-on-device', choices=('off', 'on', 'alternate'), default='off')
     ap.add_argument('--tiff-read-on-device', choices=('off', 'on', 'alternate'), default='off')
+    ap.add_argument('--tiff-read-batch', type=int, default=1, help='with --tiff-read-on-device on: tiff_read_batch 1 and this value alternate, twice')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     a = ap.parse_args()
     import yaml
@@ -134,13 +137,15 @@ def main():
             seen.update(kw['stats'])
             return r
 
-        def passes(key, read_key=False):
+        def passes(key, read_key=False, read_batch=1):
             """One warm-up pass (arenas, page cache) and --main-passes timed ones -> images/s of each, write stage ms per image."""
             cfg = {'stat_fish': {'inpath': inp, 'scale': 1, 'use_min_cut': False, 'nuclei_size_T': 5000}}
             if key:
                 cfg['stat_fish']['tiff_on_device'] = True
             if read_key:
                 cfg['stat_fish']['tiff_read_on_device'] = True
+            if read_batch > 1:
+                cfg['stat_fish']['tiff_read_batch'] = read_batch
             with open(os.path.join(tmp, 'config.yaml'), 'w') as f:
                 yaml.safe_dump(cfg, f)
             rates, writes, stage_reads = [], [], []
@@ -161,7 +166,16 @@ def main():
         os.chdir(tmp)
         stat_fish.process_image = spy
         try:
-            if a.tiff_read_on_device == 'alternate':
+            if a.tiff_read_batch > 1:                             # the read key on throughout, tiff_read_batch 1 and K alternating, twice
+                w = a.tiff_on_device == 'on'
+                out['main_by_read_batch'] = [dict(tiff_on_device=w, tiff_read_on_device=True, tiff_read_batch=k, **summary(*passes(w, True, k)))
+                                             for k in (1, a.tiff_read_batch, 1, a.tiff_read_batch)]
+                ones = [r for r in out['main_by_read_batch'] if r['tiff_read_batch'] == 1]
+                many = [r for r in out['main_by_read_batch'] if r['tiff_read_batch'] > 1]
+                out['max_1_below_min_k'] = max(r['main_images_per_s_max'] for r in ones) < min(r['main_images_per_s_min'] for r in many)
+                out['max_k_below_min_1'] = max(r['main_images_per_s_max'] for r in many) < min(r['main_images_per_s_min'] for r in ones)
+                out.update(ones[0])
+            elif a.tiff_read_on_device == 'alternate':
                 w = a.tiff_on_device == 'on'
                 out['main_by_read_key'] = [dict(tiff_on_device=w, tiff_read_on_device=key, **summary(*passes(w, key))) for key in (False, True, False, True)]
                 offs = [r for r in out['main_by_read_key'] if not r['tiff_read_on_device']]

@@ -1,6 +1,7 @@
 """Timing of the device TIFF reader (ecseg_tiff_decode) against the host reader (ecseg_tiff_read) on one core.
 
     python tools/time_tiff_decode.py [--passes 5] [--limit 120]
+    python tools/time_tiff_decode.py --batch [--passes 5] [--limit 300] [--ks 1,2,4,8,16,32]
 
 A 1040 x 1392 RGB scene of the stat_fish generator (tests/stat_fish_cases.py ``full_size_scene``) is written with LZW and the
 horizontal predictor at 1, 5, 15, 64 and 1040 rows per strip, and once uncompressed.  Per file: the host reader from the page
@@ -10,6 +11,15 @@ seconds, so that a file that keeps a wave too long ends that run and no other.  
 file it is given; the routing rule that image_io.imread asks (csrc/tiff_parse.h, TIFF_DEVICE_MIN_STRIPS) takes its threshold from
 this table.  Prints one JSON line per file and a last line
 with the smallest strip count at which the device call is faster than the host reader.
+
+--batch: the batched reader (ecseg_tiff_decode_batch through image_io.imread_many) on k = 1, 2, 4, 8, 16, 32 such scenes of
+different seeds at 1, 5 and 15 rows per strip, and on the stat_fish pair (the RGB file at 1 row per strip with its 208-strip mask,
+k images of them).  Every (plan, k) cell is a child process of its own under --limit seconds: it writes its files, reads them one
+after another with ecseg_tiff_read on one host thread (the yardstick), then through imread_many as it is - reading the files, both
+questions of the routing rule, one Handle.tiff_decode_many - with only the rule's verdict replaced, so that every set is sent (the
+verdict is reported beside the times) - one warm-up and --passes passes each, median, minimum
+and maximum.  A cell counts as a win only when the batch's maximum is below the host's minimum; the last line lists the cells that
+win, and nothing is claimed between cells.
 """
 import argparse
 import json
@@ -94,14 +104,109 @@ def one(path, passes):
     print(json.dumps(out), flush=True)
 
 
+BATCH_PLANS = ('rps1', 'rps5', 'rps15', 'pair')
+
+
+def write_batch(folder, plan, k):
+    """k scenes of seeds 100 .. 100 + k - 1 at the plan's rows per strip ('pair': 1, each with its mask as write_tiff_gray8 writes
+    it) -> the paths."""
+    import ctypes as C
+    import stat_fish_cases as cases
+    import tiff_decode_cases as dc
+    from ecseg_amd import image_io
+    from ecseg_amd._lib import load_library
+    lib = load_library()
+    rps = 1 if plan == 'pair' else int(plan[3:])
+    paths = []
+    for j in range(k):
+        img, seg = cases.full_size_scene(100 + j)
+        H, W = img.shape[:2]
+        flat = np.ascontiguousarray(img).reshape(H, W * 3)
+        pred = flat.copy()
+        pred[:, 3:] = flat[:, 3:] - flat[:, :-3]
+        strips = []
+        for r in range(0, H, rps):
+            src = np.ascontiguousarray(pred[r:r + rps]).reshape(-1)
+            dst = np.empty(2 * src.size + 64, np.uint8)
+            m = lib.ecseg_lzw_encode(src.ctypes.data_as(C.c_void_p), src.size, dst.ctypes.data_as(C.c_void_p), dst.size)
+            assert m > 0
+            strips.append(dst[:m].tobytes())
+        paths.append(os.path.join(folder, 'scene_%02d.tif' % j))
+        with open(paths[-1], 'wb') as f:
+            f.write(dc.tiff_file(strips, H, W, rps, spp=3, predictor=2))
+        if plan == 'pair':
+            paths.append(os.path.join(folder, 'mask_%02d.tif' % j))
+            image_io.write_tiff_gray8(paths[-1], (np.asarray(seg) > 0).astype(np.uint8) * np.uint8(255))
+    return paths
+
+
+def batch_one(plan, k, passes):
+    """The child: one (plan, k) cell on the host reader and through imread_many -> one JSON line."""
+    from ecseg_amd import image_io
+    from ecseg_amd._lib import Handle
+    with tempfile.TemporaryDirectory() as tmp:
+        paths = write_batch(tmp, plan, k)
+        datas = [open(p, 'rb').read() for p in paths]
+        goes, counts = image_io.tiff_batch_goes_to_device(datas)
+        host = []
+        for rep in range(passes + 1):
+            t0 = time.perf_counter()
+            want = [image_io._native_tiff(p) for p in paths]
+            if rep:
+                host.append((time.perf_counter() - t0) * 1e3)
+        out = dict(plan=plan, k=k, files=len(paths), bytes=sum(len(d) for d in datas), rule_sends_the_set=bool(goes), host_read_ms=stats(host))
+        rule = image_io.tiff_batch_goes_to_device                # the measurement sends every set: the rule's questions are asked and
+        image_io.tiff_batch_goes_to_device = lambda datas: (True, rule(datas)[1])       # timed as ever, only the verdict is replaced
+        gpu = Handle(0)
+        call = []
+        for rep in range(passes + 1):
+            t0 = time.perf_counter()
+            got = image_io.imread_many(paths, handle=gpu)
+            if rep:
+                call.append((time.perf_counter() - t0) * 1e3)
+        assert all(isinstance(g, np.ndarray) and g.dtype == w.dtype and np.array_equal(g, w) for g, w in zip(got, want))
+        out.update(imread_many_ms=stats(call), device_kernel_ms_last_call=gpu.timings()['count'])
+        out['wins'] = out['imread_many_ms']['max'] < out['host_read_ms']['min']
+        gpu.close()
+    print(json.dumps(out), flush=True)
+
+
+def batch_main(a):
+    rows = []
+    for plan in BATCH_PLANS:
+        for k in a.ks:
+            cell = dict(plan=plan, k=k)
+            try:
+                r = subprocess.run([sys.executable, os.path.abspath(__file__), '--batch-one', '%s:%d' % (plan, k), '--passes', str(a.passes)],
+                                   capture_output=True, text=True, timeout=a.limit)
+            except subprocess.TimeoutExpired:
+                print(json.dumps(dict(cell, device='ended at the time limit of %g s' % a.limit)), flush=True)
+                return                                       # a hung device run: nothing more is started on the device
+            if r.returncode != 0:
+                print(json.dumps(dict(cell, failed=r.returncode, stderr=r.stderr[-2000:])), flush=True)
+                return
+            line = r.stdout.strip().splitlines()[-1]
+            print(line, flush=True)
+            rows.append(json.loads(line))
+    print(json.dumps(dict(cells_where_the_batch_maximum_is_below_the_host_minimum=[[r['plan'], r['k']] for r in rows if r['wins']])))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--passes', type=int, default=5)
     ap.add_argument('--limit', type=float, default=120.0)
     ap.add_argument('--one')
+    ap.add_argument('--batch', action='store_true')
+    ap.add_argument('--batch-one')
+    ap.add_argument('--ks', type=lambda v: [int(x) for x in v.split(',')], default=[1, 2, 4, 8, 16, 32])
     a = ap.parse_args()
     if a.one:
         return one(a.one, a.passes)
+    if a.batch_one:
+        plan, k = a.batch_one.split(':')
+        return batch_one(plan, int(k), a.passes)
+    if a.batch:
+        return batch_main(a)
     rows = []
     with tempfile.TemporaryDirectory() as tmp:
         for name in write_files(tmp):
