@@ -1,5 +1,5 @@
 // C ABI of libecseg_hip.so (see include/ecseg_hip.h): the handle's life cycle, errors, options, page-locked host memory and the
-// timing / profile getters.  The rest of the host side: model_load.hip, plan_run.hip, segment.hip, drivers.hip (ctx.h: what they share).
+// timing / profile getters.  The rest of the host side: model_load.hip, plan_run.hip, segment.hip, drivers_*.hip (ctx.h: what they share).
 #include <cstdio>
 #include <cstdlib>
 #include "ctx.h"

@@ -1,5 +1,5 @@
 // Internal header of the library's host side: the handle (ecseg_ctx), the device memory it owns and what the host-side files
-// (api, filter_layout, model_load, plan_run, segment, drivers) share.  No kernel includes this.
+// (api, filter_layout, model_load, plan_run, segment, drivers_*) share.  No kernel includes this.
 #pragma once
 #include <algorithm>
 #include <array>
@@ -221,9 +221,13 @@ inline void drop_sent_ahead(ecseg_ctx* h) {
 // api.hip
 int check_model(ecseg_ctx* h);
 
-// drivers.hip: the file coders' tails, shared with ecseg_meta_segment_files (segment.hip).  Both bring the tables over, wait, and
-// copy every file that fits file_cap into files[i] (file_bytes[i]: its length); a file that does not fit is not produced.
+// drivers_files.hip: the file coders' tails, shared with ecseg_meta_segment_files (segment.hip) and ecseg_fish_render_tiff
+// (drivers_fish.hip).  Both bring the tables over, wait, and copy every file that fits file_cap into files[i] (file_bytes[i]: its
+// length); a file that does not fit is not produced.
 // tiff_collect, strict: that is an error and nothing is written; else file_bytes[i] = -(the bytes it needs) and the call goes on.
+inline bool tiff_args_ok(int H, int W, int spp) {            // what tiff_write_u8 (host_io.cpp) and with it the device encoder accepts
+    return H > 0 && W > 0 && (spp == 1 || spp == 3) && (long long)W * spp < (1ll << 30);
+}
 int tiff_collect(ecseg_ctx* h, const char* who, int n_files, int H, int W, int spp, const TiffEncodeBufs& b, uint8_t* const* files,
                  long long file_cap, long long* file_bytes, bool strict);
 // The label PNGs of n images that lie on the device (image i at d_labels + i * H * W), on the main stream: count, code build on the

@@ -1,0 +1,233 @@
+// The FISH drivers: the per-nucleus distances (fishdist_kernels.hip), stat_fish's spots and its three colour files
+// (fishspot_kernels.hip; as TIFF files through tiff_collect of drivers_files.hip) and the min-cut tasks (mincut_kernels.hip).
+#include "driver_util.h"
+
+using namespace ecseg;
+
+// The opening phase of ecseg_fish_distances and ecseg_fish_spots: the label map and the image on the device, the dense cell index
+// (stage_ms[ECSEG_T_COUNT] = its device time) and the number of cells.  `who` prefixes the refusal of a label above H * W.  `b`
+// lies in the call arena: what the caller sizes by the cell count goes to the count arena.
+static int open_dense_cells(ecseg_ctx* h, const char* who, const int32_t* labels, int H, int W, const uint8_t* img, int C, CellIndexBufs& b,
+                            int32_t* n_cells) {
+    const size_t px = (size_t)H * W;
+    if (int rc = lay_out(h, h->call_arena, [&](Carver& c) { b = cell_index_bufs(c, H, W, C); })) return rc;
+    hipStream_t s = h->stream;
+    clear_timings(h);
+    HIP_TRY(h, hipMemcpyAsync(b.lab, labels, px * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(b.img, img, px * C, hipMemcpyHostToDevice, s));
+    TIMED(h, s, 0, 1, HIP_TRY(h, run_dense_cells(b.lab, H, W, b, s)));
+    int32_t misc[4];
+    HIP_TRY(h, hipMemcpyAsync(misc, b.misc, sizeof(misc), hipMemcpyDeviceToHost, s));
+    WAIT_SET(h, s, 0, 1);
+    if (misc[3])
+        return fail(h, ECSEG_E_INVALID, std::string(who) + ": the label map holds a label larger than H * W = " + std::to_string(px) +
+                                            " (renumber the labels by rank first)");
+    *n_cells = misc[0];
+    return ECSEG_OK;
+}
+
+// the argument rules ecseg_fish_render and ecseg_fish_render_tiff share; ch: the validated channel indices
+static int fish_render_check(ecseg_ctx* h, const uint8_t* img, int H, int W, int C, const int32_t* channels, const uint8_t* thresholded,
+                             int n_probe, const uint8_t* boundaries, int ch[4]) {
+    if (!img || !channels || !thresholded || !boundaries || H <= 0 || W <= 0) return fail(h, ECSEG_E_INVALID, "fish_render: bad arguments");
+    if (C < 3 || C > 4) return fail(h, ECSEG_E_INVALID, "fish_render: the image must have 3 or 4 channels, not " + std::to_string(C));
+    if (n_probe != C - 1)
+        return fail(h, ECSEG_E_INVALID, "fish_render: n_probe must be C - 1 = " + std::to_string(C - 1) + " (one mask per FISH channel)");
+    for (int j = 0; j < 4; ++j) ch[j] = 0;
+    for (int j = 0; j < C; ++j) {
+        ch[j] = channels[j];
+        if (ch[j] < 0 || ch[j] >= C)
+            return fail(h, ECSEG_E_INVALID, "fish_render: channel index out of range (the image has " + std::to_string(C) + " channels)");
+    }
+    if (!px_below_2_31(H, W)) return fail(h, ECSEG_E_INVALID, "fish_render: image too large (H * W must be below 2^31)");
+    return ECSEG_OK;
+}
+
+extern "C" {
+
+// ---- fish_distance_calculation (src/fish_distance_calculation.py:16-46) ---------------------------------------------------
+int ecseg_fish_distances(ecseg_ctx* h, const int32_t* labels, int H, int W, const uint8_t* lsq, int C, int fish_channel,
+                         int centromere_channel, int capacity, int64_t* records, int32_t* n_cells) {
+    DRIVER_OPEN(h);
+    if (n_cells) *n_cells = 0;
+    if (!labels || !lsq || !n_cells || H <= 0 || W <= 0 || capacity < 0 || (capacity > 0 && !records))
+        return fail(h, ECSEG_E_INVALID, "fish_distances: bad arguments");
+    if (C < 2) return fail(h, ECSEG_E_INVALID, "fish_distances: the lsq image needs at least 2 channels (the gate reads channels 0 and 1)");
+    if (fish_channel < 0 || fish_channel >= C || centromere_channel < 0 || centromere_channel >= C)
+        return fail(h, ECSEG_E_INVALID, "fish_distances: channel out of range (the lsq image has " + std::to_string(C) + " channels)");
+    if (!px_below_2_31(H, W) || (long long)H * W * C >= (1ll << 40))
+        return fail(h, ECSEG_E_INVALID, "fish_distances: image too large (H * W must be below 2^31, H * W * C below 2^40)");
+    USE_DEVICE(h);
+    int rc;
+    CellIndexBufs cells{};
+    if ((rc = open_dense_cells(h, "fish_distances", labels, H, W, lsq, C, cells, n_cells))) return rc;
+    const int n = *n_cells;
+    if (n == 0 || n > capacity) return ECSEG_OK;             // the cell count alone: the caller comes back with a larger buffer
+    // the rest is sized by the number of cells, which is known only now
+    FishDistBufs b{};
+    if ((rc = lay_out(h, h->count_arena, [&](Carver& c) { b = fishdist_bufs(c, cells, H, W, n, fishdist_slices(n)); }))) return rc;
+    hipStream_t s = h->stream;
+    TIMED(h, s, 2, 3, HIP_TRY(h, run_fishdist_records(cells.lab, cells.img, H, W, C, fish_channel, centromere_channel, n, b, s)));
+    HIP_TRY(h, hipMemcpyAsync(records, b.rec, (size_t)n * 8 * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    WAIT_ADD(h, s, 2, 3);
+    return ECSEG_OK;
+}
+
+// ---- stat_fish behind nuclei_segment (src/stat_fish.py:73-107,134-142,226-300) --------------------------------------------------
+int ecseg_fish_spots(ecseg_ctx* h, const int32_t* labels, int H, int W, const uint8_t* img, int C, const int32_t* probe_channels,
+                     int n_probe, const double* weights, int K, double normal_threshold, const double* intensity_thresholds,
+                     int min_cc_size, int line_thickness, int capacity, uint8_t* thresholded, uint8_t* boundaries,
+                     int64_t* records, int32_t* n_cells) {
+    DRIVER_OPEN(h);
+    if (n_cells) *n_cells = 0;
+    if (!labels || !img || !probe_channels || !weights || !intensity_thresholds || !thresholded || !boundaries || !n_cells || H <= 0 ||
+        W <= 0 || C < 1 || capacity < 0 || (capacity > 0 && !records))
+        return fail(h, ECSEG_E_INVALID, "fish_spots: bad arguments");
+    if (n_probe < 1 || n_probe > 3) return fail(h, ECSEG_E_INVALID, "fish_spots: n_probe must be 1, 2 or 3");
+    int ch[3] = {0, 0, 0};
+    double ithr[3] = {0.0, 0.0, 0.0};
+    for (int j = 0; j < n_probe; ++j) {
+        ch[j] = probe_channels[j];
+        ithr[j] = intensity_thresholds[j];
+        if (ch[j] < 0 || ch[j] >= C)
+            return fail(h, ECSEG_E_INVALID, "fish_spots: probe channel out of range (the image has " + std::to_string(C) + " channels)");
+    }
+    if (K < 1 || K > ECSEG_FISH_SPOT_MAX_KERNEL || K % 2 == 0)
+        return fail(h, ECSEG_E_INVALID, "fish_spots: the kernel side must be odd and between 1 and " + std::to_string(ECSEG_FISH_SPOT_MAX_KERNEL));
+    if (line_thickness < 1 || line_thickness > ECSEG_FISH_SPOT_MAX_LINE)
+        return fail(h, ECSEG_E_INVALID, "fish_spots: line_thickness must be between 1 and " + std::to_string(ECSEG_FISH_SPOT_MAX_LINE));
+    if (!px_below_2_31(H, W) || (long long)H * W * C >= (1ll << 40))
+        return fail(h, ECSEG_E_INVALID, "fish_spots: image too large (H * W must be below 2^31, H * W * C below 2^40)");
+    USE_DEVICE(h);
+    const size_t px = (size_t)H * W, np = (size_t)n_probe;
+    int rc;
+    CellIndexBufs cells{};
+    if ((rc = open_dense_cells(h, "fish_spots", labels, H, W, img, C, cells, n_cells))) return rc;
+    const int n = *n_cells;
+    if (n > capacity) return ECSEG_OK;                       // the cell count alone: the caller comes back with a larger buffer
+    if (n == 0) {                                            // no cell: nothing is thresholded and no rank differs from 0
+        std::fill(thresholded, thresholded + px * np, (uint8_t)0);
+        std::fill(boundaries, boundaries + px, (uint8_t)0);
+        return ECSEG_OK;
+    }
+    FishSpotBufs b{};
+    if ((rc = lay_out(h, h->count_arena, [&](Carver& c) { b = fishspot_bufs(c, cells, H, W, n_probe, K, n); }))) return rc;
+    hipStream_t s = h->stream;
+    HIP_TRY(h, hipMemcpyAsync(b.w, weights, (size_t)K * K * sizeof(double), hipMemcpyHostToDevice, s));
+    TIMED(h, s, 2, 3, HIP_TRY(h, run_fishspot(cells.lab, cells.img, H, W, C, n_probe, ch, b.w, K, normal_threshold, ithr, min_cc_size, line_thickness, n, b, s)));
+    HIP_TRY(h, hipMemcpyAsync(thresholded, b.thr, px * np, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipMemcpyAsync(boundaries, b.bnd, px, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipMemcpyAsync(records, b.rec, (size_t)n * ECSEG_FISH_SPOT_INT64 * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    WAIT_ADD(h, s, 2, 3);
+    return ECSEG_OK;
+}
+
+// ---- stat_fish's three colour files (src/stat_fish.py:110-115,295-300) ------------------------------------------------------------
+int ecseg_fish_render(ecseg_ctx* h, const uint8_t* img, int H, int W, int C, const int32_t* channels, const uint8_t* thresholded,
+                      int n_probe, const uint8_t* boundaries, uint8_t* original, uint8_t* with_segmentation, uint8_t* lsq) {
+    DRIVER_OPEN(h);
+    if (!original || !with_segmentation || !lsq) return fail(h, ECSEG_E_INVALID, "fish_render: bad arguments");
+    int ch[4], rc;
+    if ((rc = fish_render_check(h, img, H, W, C, channels, thresholded, n_probe, boundaries, ch))) return rc;
+    USE_DEVICE(h);
+    const size_t px = (size_t)H * W;
+    FishRenderBufs b{};
+    if ((rc = lay_out(h, h->call_arena, [&](Carver& c) { b = fish_render_bufs(c, H, W, C); }))) return rc;
+    hipStream_t s = h->stream;
+    clear_timings(h);
+    HIP_TRY(h, hipMemcpyAsync(b.img, img, px * C, hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(b.thr, thresholded, px * n_probe, hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(b.bnd, boundaries, px, hipMemcpyHostToDevice, s));
+    TIMED(h, s, 0, 1, HIP_TRY(h, run_fish_render(H, W, C, ch, b, s)));
+    HIP_TRY(h, hipMemcpyAsync(original, b.orig, px * 3, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipMemcpyAsync(with_segmentation, b.seg, px * 3, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipMemcpyAsync(lsq, b.lsq, px * 3, hipMemcpyDeviceToHost, s));
+    WAIT_SET(h, s, 0, 1);
+    return ECSEG_OK;
+}
+
+// the same, and the three images as TIFF files encoded on the device: here the raw images are optional
+int ecseg_fish_render_tiff(ecseg_ctx* h, const uint8_t* img, int H, int W, int C, const int32_t* channels, const uint8_t* thresholded,
+                           int n_probe, const uint8_t* boundaries, uint8_t* const* files, long long file_cap, long long* file_bytes,
+                           uint8_t* original, uint8_t* with_segmentation, uint8_t* lsq) {
+    DRIVER_OPEN(h);
+    if (!files || !files[0] || !files[1] || !files[2] || !file_bytes || file_cap < 0) return fail(h, ECSEG_E_INVALID, "fish_render_tiff: bad arguments");
+    int ch[4], rc;
+    if ((rc = fish_render_check(h, img, H, W, C, channels, thresholded, n_probe, boundaries, ch))) return rc;
+    if (!tiff_args_ok(H, W, 3)) return fail(h, ECSEG_E_INVALID, "fish_render_tiff: the TIFF writer takes lines below 2^30 bytes");
+    file_bytes[0] = file_bytes[1] = file_bytes[2] = 0;
+    USE_DEVICE(h);
+    const size_t px = (size_t)H * W;
+    FishRenderBufs b{};
+    TiffEncodeBufs t{};
+    if ((rc = lay_out(h, h->call_arena, [&](Carver& c) { b = fish_render_bufs(c, H, W, C); t = tiff_encode_bufs(c, H, W, 3, 3, false); }))) return rc;
+    hipStream_t s = h->stream;
+    clear_timings(h);
+    HIP_TRY(h, hipMemcpyAsync(b.img, img, px * C, hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(b.thr, thresholded, px * n_probe, hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(b.bnd, boundaries, px, hipMemcpyHostToDevice, s));
+    TIMED(h, s, 0, 1,
+          HIP_TRY(h, run_fish_render(H, W, C, ch, b, s));
+          HIP_TRY(h, run_tiff_encode(TiffSources{{b.orig, b.seg, b.lsq}, 0}, 3, H, W, 3, 0, t, s)));
+    if (original) HIP_TRY(h, hipMemcpyAsync(original, b.orig, px * 3, hipMemcpyDeviceToHost, s));
+    if (with_segmentation) HIP_TRY(h, hipMemcpyAsync(with_segmentation, b.seg, px * 3, hipMemcpyDeviceToHost, s));
+    if (lsq) HIP_TRY(h, hipMemcpyAsync(lsq, b.lsq, px * 3, hipMemcpyDeviceToHost, s));
+    if ((rc = tiff_collect(h, "fish_render_tiff", 3, H, W, 3, t, files, file_cap, file_bytes, true))) return rc;   // (waits for the stream)
+    timed_set(h, 0, 1);
+    return ECSEG_OK;
+}
+
+// ---- the min-cut splitter's max-flow tasks (src/max_flow_binary_mask.py:59-116) ------------------------------------------------
+int ecseg_min_cut(ecseg_ctx* h, const uint8_t* masks, long long mask_bytes, const int32_t* tasks, int n_tasks, int dist, uint8_t* side,
+                  int32_t* flow) {
+    DRIVER_OPEN(h);
+    if (n_tasks < 0 || mask_bytes < 0 || (n_tasks > 0 && (!masks || !tasks || !side || !flow)))
+        return fail(h, ECSEG_E_INVALID, "min_cut: bad arguments");
+    if (dist < 1 || dist > ECSEG_MIN_CUT_MAX_DIST)
+        return fail(h, ECSEG_E_INVALID, "min_cut: dist must be between 1 and " + std::to_string(ECSEG_MIN_CUT_MAX_DIST));
+    if (mask_bytes > ECSEG_MIN_CUT_MAX_BYTES)
+        return fail(h, ECSEG_E_INVALID, "min_cut: more than " + std::to_string(ECSEG_MIN_CUT_MAX_BYTES) + " bytes of windows in one call");
+    clear_timings(h);                                        // (before the tasks are checked: a refused task leaves zeros)
+    if (n_tasks == 0) return ECSEG_OK;
+    std::vector<long long> soff((size_t)n_tasks, -1);
+    long long end = 0;
+    size_t scratch = 0;
+    int n_global = 0;
+    for (int i = 0; i < n_tasks; ++i) {
+        const int32_t* t = tasks + 8 * (size_t)i;
+        const std::string who = "min_cut: task " + std::to_string(i);
+        const long long off = t[0], th = t[1], tw = t[2];
+        if (th < 1 || tw < 1 || th * tw > ECSEG_MIN_CUT_MAX_PIXELS)
+            return fail(h, ECSEG_E_INVALID, who + ": the window must hold between 1 and " + std::to_string(ECSEG_MIN_CUT_MAX_PIXELS) + " pixels");
+        if (off < end || off + th * tw > mask_bytes)
+            return fail(h, ECSEG_E_INVALID, who + ": the window overlaps the one in front or leaves the buffer");
+        end = off + th * tw;
+        if (t[3] < 0 || t[3] >= th || t[4] < 0 || t[4] >= tw || t[5] < 0 || t[5] >= th || t[6] < 0 || t[6] >= tw)
+            return fail(h, ECSEG_E_INVALID, who + ": source or sink outside the window");
+        if (t[3] == t[5] && t[4] == t[6]) return fail(h, ECSEG_E_INVALID, who + ": source and sink are the same pixel");
+        if (!masks[off + t[3] * tw + t[4]] || !masks[off + t[5] * tw + t[6]])
+            return fail(h, ECSEG_E_INVALID, who + ": source or sink on a zero pixel");
+        if (th * tw > h->min_cut_lds_pixels) {
+            soff[(size_t)i] = (long long)scratch;
+            ++n_global;
+            scratch += mincut_scratch_bytes((int)th, (int)tw);
+        }
+    }
+    USE_DEVICE(h);
+    const size_t nb = (size_t)mask_bytes, nt = (size_t)n_tasks;
+    int rc;
+    MinCutBufs b{};
+    if ((rc = lay_out(h, h->call_arena, [&](Carver& c) { b = mincut_bufs(c, nb, n_tasks, scratch); }))) return rc;
+    hipStream_t s = h->stream;
+    HIP_TRY(h, hipMemcpyAsync(b.mask, masks, nb, hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(b.desc, tasks, nt * 8 * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(b.soff, soff.data(), nt * sizeof(long long), hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemsetAsync(b.side, 0, nb, s));
+    TIMED(h, s, 0, 1, HIP_TRY(h, run_mincut(b.mask, b.desc, b.soff, n_tasks, n_global, dist, b.scratch, b.side, b.flow, s)));
+    HIP_TRY(h, hipMemcpyAsync(side, b.side, nb, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipMemcpyAsync(flow, b.flow, nt * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    WAIT_SET(h, s, 0, 1);                     // (soff is read by the copy above: it lives until here)
+    return ECSEG_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,218 @@
+// The one-call drivers of the clean-up and counting kernels (post_kernels.hip): each uploads its inputs, runs its kernels on the main
+// stream and downloads the results (u16_to_u8, stitch_argmax, meta_inference, the counts, one labelling pass alone, overlay).
+#include "driver_util.h"
+
+using namespace ecseg;
+
+extern "C" {
+
+int ecseg_u16_to_u8(ecseg_ctx* h, const uint16_t* in, long long count, uint8_t* out) {
+    DRIVER_OPEN(h);
+    if (count < 0 || (count > 0 && (!in || !out))) return fail(h, ECSEG_E_INVALID, "u16_to_u8: bad arguments");
+    if (count == 0) return ECSEG_OK;
+    USE_DEVICE(h);
+    int rc;
+    if ((rc = h->d_aux8.ensure(h, (size_t)count * 2))) return rc;
+    if ((rc = h->d_gray.ensure(h, (size_t)count))) return rc;
+    hipStream_t s = h->stream;
+    HIP_TRY(h, hipMemcpyAsync(h->d_aux8, in, (size_t)count * 2, hipMemcpyHostToDevice, s));
+    HIP_TRY(h, launch_u16_to_u8(reinterpret_cast<const uint16_t*>(h->d_aux8.p), h->d_gray, (size_t)count, s));
+    HIP_TRY(h, hipMemcpyAsync(out, h->d_gray, (size_t)count, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    return ECSEG_OK;                                         // (untimed, as ecseg_stitch_argmax: stage_ms keeps the call before's)
+}
+
+int ecseg_stitch_argmax(ecseg_ctx* h, const float* probs, int n_img, int H, int W, uint8_t* labels_raw) {
+    DRIVER_OPEN(h);
+    if (n_img < 0 || (n_img > 0 && (!probs || !labels_raw))) return fail(h, ECSEG_E_INVALID, "stitch_argmax: bad arguments");
+    if (n_img == 0) return ECSEG_OK;
+    USE_DEVICE(h);
+    StitchPlan* sp = nullptr;
+    int rc;
+    if ((rc = get_stitch(h, H, W, &sp))) return rc;
+    const size_t px = (size_t)H * W, nfl = (size_t)n_img * sp->n_pos * 65536 * 4;
+    if ((rc = h->d_probs_in.ensure(h, nfl))) return rc;
+    if ((rc = h->d_raw.ensure(h, px * n_img))) return rc;
+    hipStream_t s = h->stream;
+    HIP_TRY(h, hipMemcpyAsync(h->d_probs_in, probs, nfl * sizeof(float), hipMemcpyHostToDevice, s));
+    HIP_TRY(h, launch_stitch_argmax(h->d_probs_in, 4, sp->map_dev, n_img, sp->n_pos, H, W, h->d_raw, s));
+    HIP_TRY(h, hipMemcpyAsync(labels_raw, h->d_raw, px * n_img, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    return ECSEG_OK;
+}
+
+int ecseg_meta_inference_dev(ecseg_ctx* h, const uint8_t* in, int n_img, int H, int W, uint8_t* out, int32_t* n_ec) {
+    DRIVER_OPEN(h);
+    if (n_img < 0 || H <= 0 || W <= 0 || (n_img > 0 && (!in || !out))) return fail(h, ECSEG_E_INVALID, "meta_inference: bad arguments");
+    if (n_img == 0) return ECSEG_OK;
+    if (!px_below_2_31(H, W)) return fail(h, ECSEG_E_INVALID, "image too large");
+    USE_DEVICE(h);
+    const size_t px = (size_t)H * W;
+    int rc;
+    if ((rc = ensure_post(h, std::min(n_img, h->post_chunk), px))) return rc;
+    hipStream_t s = h->stream;
+    if (out != in) HIP_TRY(h, hipMemcpyAsync(out, in, px * n_img, hipMemcpyDeviceToDevice, s));
+    TIMED(h, s, 0, 1,
+          for (int i0 = 0; i0 < n_img; i0 += h->post_chunk) {
+              const int ni = std::min(h->post_chunk, n_img - i0);
+              HIP_TRY(h, run_meta_inference(h->ws, out + (size_t)i0 * px, ni, H, W, n_ec ? n_ec + i0 : nullptr, s));
+          });
+    HIP_TRY(h, hipStreamSynchronize(s));
+    clear_timings(h);                                        // (behind the wait, where every other driver clears before its upload: a failed call keeps the timings of the one before)
+    timed_set(h, 0, 1, ECSEG_T_POST);
+    return ECSEG_OK;
+}
+
+int ecseg_meta_inference(ecseg_ctx* h, const uint8_t* in, int n_img, int H, int W, uint8_t* out, int32_t* n_ec) {
+    DRIVER_OPEN(h);
+    if (n_img < 0 || H <= 0 || W <= 0 || (n_img > 0 && (!in || !out))) return fail(h, ECSEG_E_INVALID, "meta_inference: bad arguments");
+    if (n_img == 0) return ECSEG_OK;
+    USE_DEVICE(h);
+    const size_t tot = (size_t)H * W * n_img;
+    int rc;
+    if ((rc = h->d_post.ensure(h, tot))) return rc;
+    if ((rc = h->d_i32.ensure(h, (size_t)n_img))) return rc;
+    HIP_TRY(h, hipMemcpyAsync(h->d_post, in, tot, hipMemcpyHostToDevice, h->stream));
+    if ((rc = ecseg_meta_inference_dev(h, h->d_post, n_img, H, W, h->d_post, h->d_i32))) return rc;
+    HIP_TRY(h, hipMemcpyAsync(out, h->d_post, tot, hipMemcpyDeviceToHost, h->stream));
+    if (n_ec) HIP_TRY(h, hipMemcpyAsync(n_ec, h->d_i32, (size_t)n_img * 4, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return ECSEG_OK;
+}
+
+enum CountKind { COUNT_CC, COUNT_COLOC, COUNT_HSR, COUNT_LABELS };
+
+// shared driver of the mask-counting entry points: uploads one or two mask stacks, chunks over images
+static int count_driver(ecseg_ctx* h, const uint8_t* a, const uint8_t* b, int n_img, int H, int W, CountKind kind, int arg,
+                        int32_t* n_out, int64_t* px_out, int32_t* labels_out) {
+    DRIVER_OPEN(h);
+    if (n_img < 0 || H <= 0 || W <= 0 || (n_img > 0 && !a)) return fail(h, ECSEG_E_INVALID, "count: bad arguments");
+    if (n_img == 0) return ECSEG_OK;
+    if (!px_below_2_31(H, W)) return fail(h, ECSEG_E_INVALID, "image too large");
+    USE_DEVICE(h);
+    const size_t px = (size_t)H * W;
+    const int chunk = h->post_chunk;
+    int rc;
+    if ((rc = ensure_post(h, std::min(n_img, chunk), px))) return rc;
+    if ((rc = h->d_gray.ensure(h, px * std::min(n_img, chunk)))) return rc;
+    if (b && (rc = h->d_aux8.ensure(h, px * std::min(n_img, chunk)))) return rc;
+    if ((rc = h->d_i32.ensure(h, labels_out ? px * std::min(n_img, chunk) : (size_t)chunk))) return rc;
+    if ((rc = h->d_i64.ensure(h, (size_t)chunk))) return rc;
+    hipStream_t s = h->stream;
+    clear_timings(h);
+    for (int i0 = 0; i0 < n_img; i0 += chunk) {
+        const int ni = std::min(chunk, n_img - i0);
+        HIP_TRY(h, hipMemcpyAsync(h->d_gray, a + (size_t)i0 * px, px * ni, hipMemcpyHostToDevice, s));
+        if (b) HIP_TRY(h, hipMemcpyAsync(h->d_aux8, b + (size_t)i0 * px, px * ni, hipMemcpyHostToDevice, s));
+        hipError_t e = hipSuccess;
+        TIMED(h, s, 0, 1,
+              if (kind == COUNT_CC) e = run_count_cc(h->ws, h->d_gray, ni, H, W, h->d_i32, h->d_i64, s);
+              else if (kind == COUNT_COLOC) e = run_count_coloc(h->ws, h->d_gray, h->d_aux8, ni, H, W, h->d_i32, s);
+              else if (kind == COUNT_HSR) e = run_count_hsr(h->ws, h->d_gray, h->d_aux8, ni, H, W, arg, h->d_i32, s);
+              else e = run_ccl_labels(h->ws, h->d_gray, ni, H, W, arg, h->d_i32, s);
+              if (e != hipSuccess) return fail_hip(h, e, "count kernels"));
+        if (labels_out) HIP_TRY(h, hipMemcpyAsync(labels_out + (size_t)i0 * px, h->d_i32, px * ni * 4, hipMemcpyDeviceToHost, s));
+        else if (n_out) HIP_TRY(h, hipMemcpyAsync(n_out + i0, h->d_i32, (size_t)ni * 4, hipMemcpyDeviceToHost, s));
+        if (px_out) HIP_TRY(h, hipMemcpyAsync(px_out + i0, h->d_i64, (size_t)ni * 8, hipMemcpyDeviceToHost, s));
+        WAIT_ADD(h, s, 0, 1);
+    }
+    return ECSEG_OK;
+}
+
+int ecseg_count_cc(ecseg_ctx* h, const uint8_t* mask, int n_img, int H, int W, int32_t* n_out, int64_t* px_out) {
+    return count_driver(h, mask, nullptr, n_img, H, W, COUNT_CC, 0, n_out, px_out, nullptr);
+}
+int ecseg_ccl_labels(ecseg_ctx* h, const uint8_t* mask, int n_img, int H, int W, int connectivity, int32_t* labels_out) {
+    if (h && connectivity != 4 && connectivity != 8) return fail(h, ECSEG_E_INVALID, "connectivity must be 4 or 8");
+    if (h && n_img > 0 && !labels_out) return fail(h, ECSEG_E_INVALID, "labels_out is NULL");
+    return count_driver(h, mask, nullptr, n_img, H, W, COUNT_LABELS, connectivity, nullptr, nullptr, labels_out);
+}
+int ecseg_count_colocalization(ecseg_ctx* h, const uint8_t* ob1, const uint8_t* ob2, int n_img, int H, int W, int32_t* n_out) {
+    if (h && n_img > 0 && !ob2) return fail(h, ECSEG_E_INVALID, "ob2 is NULL");
+    return count_driver(h, ob1, ob2, n_img, H, W, COUNT_COLOC, 0, n_out, nullptr, nullptr);
+}
+int ecseg_count_hsr(ecseg_ctx* h, const uint8_t* chrom, const uint8_t* fish, int n_img, int H, int W, int thr, int32_t* n_out) {
+    if (h && n_img > 0 && !fish) return fail(h, ECSEG_E_INVALID, "fish is NULL");
+    return count_driver(h, chrom, fish, n_img, H, W, COUNT_HSR, thr, n_out, nullptr, nullptr);
+}
+
+// Test-only: one labelling pass alone (run_ccl_pass_debug), uploaded and chunked as count_driver does it, every export brought back.
+int ecseg_ccl_pass_debug(ecseg_ctx* h, const uint8_t* key_img, const uint8_t* aux_img, int n_img, int H, int W,
+                         const ecseg_ccl_pass_desc* pass, const ecseg_ccl_pass_out* out) {
+    DRIVER_OPEN(h);
+    if (n_img < 0 || H <= 0 || W <= 0 || !pass || (n_img > 0 && (!key_img || !out))) return fail(h, ECSEG_E_INVALID, "ccl_pass_debug: bad arguments");
+    if (n_img == 0) return ECSEG_OK;
+    if (!out->root || !out->area || !out->sumy || !out->sumx || !out->flag || !out->counters || !out->list1 || !out->list2 || !out->tile_any)
+        return fail(h, ECSEG_E_INVALID, "ccl_pass_debug: every output is required");
+    if (pass->conn != 4 && pass->conn != 8) return fail(h, ECSEG_E_INVALID, "connectivity must be 4 or 8");
+    if (pass->aux_mode == 3 && !aux_img) return fail(h, ECSEG_E_INVALID, "ccl_pass_debug: aux_mode 3 needs aux_img");
+    if (pass->n_queries < 0 || pass->n_queries > 5) return fail(h, ECSEG_E_INVALID, "ccl_pass_debug: at most 5 flag queries");
+    if ((pass->need & 8) && pass->conn != 8) return fail(h, ECSEG_E_INVALID, "ccl_pass_debug: the root lists are sized for 8-connected components");
+    if (pass->n_queries > 0 && pass->count_only) return fail(h, ECSEG_E_INVALID, "ccl_pass_debug: a count_only pass writes no flag words to query");
+    if (!px_below_2_31(H, W)) return fail(h, ECSEG_E_INVALID, "image too large");
+    USE_DEVICE(h);
+    const size_t px = (size_t)H * W, cap = ccl_list_cap(H, W);
+    const size_t tiles = (size_t)((H + 31) / 32) * (size_t)((W + 63) / 64);
+    const int chunk = std::min(n_img, h->post_chunk);
+    int rc;
+    CclPassExport b{};
+    if ((rc = ensure_post(h, chunk, px))) return rc;
+    if ((rc = h->d_gray.ensure(h, px * chunk))) return rc;
+    if (aux_img && (rc = h->d_aux8.ensure(h, px * chunk))) return rc;
+    if ((rc = lay_out(h, h->call_arena, [&](Carver& c) { b = ccl_pass_export_bufs(c, chunk, px, cap); }))) return rc;
+    CclPassDesc d{};
+    d.lut = pass->lut; d.conn = pass->conn; d.stat = pass->stat; d.aux_mode = pass->aux_mode; d.aux_c = pass->aux_c; d.need = pass->need;
+    d.count_only = pass->count_only != 0; d.sparse = pass->sparse != 0; d.allow_full = pass->allow_full != 0;
+    d.n_q = pass->n_queries;
+    for (int k = 0; k < 5; ++k) { d.q_key[k] = pass->query_key[k]; d.q_need[k] = pass->query_need[k]; }
+    hipStream_t s = h->stream;
+    for (int i0 = 0; i0 < n_img; i0 += chunk) {              // (untimed: stage_ms keeps the call before's)
+        const int ni = std::min(chunk, n_img - i0);
+        const size_t o = (size_t)i0 * px, nb = px * ni;
+        HIP_TRY(h, hipMemcpyAsync(h->d_gray, key_img + o, nb, hipMemcpyHostToDevice, s));
+        if (aux_img) HIP_TRY(h, hipMemcpyAsync(h->d_aux8, aux_img + o, nb, hipMemcpyHostToDevice, s));
+        const hipError_t e = run_ccl_pass_debug(h->ws, h->d_gray, aux_img ? h->d_aux8.p : nullptr, ni, H, W, d, b, s);
+        if (e != hipSuccess) return fail_hip(h, e, "ccl_pass_debug kernels");
+        HIP_TRY(h, hipMemcpyAsync(out->root + o, b.root, nb * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipMemcpyAsync(out->area + o, b.area, nb * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipMemcpyAsync(out->sumy + o, b.sumy, nb * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipMemcpyAsync(out->sumx + o, b.sumx, nb * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipMemcpyAsync(out->flag + o, b.flag, nb * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipMemcpyAsync(out->counters + (size_t)i0 * CCL_DEBUG_COUNTERS, b.counters, (size_t)ni * CCL_DEBUG_COUNTERS * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipMemcpyAsync(out->list1 + (size_t)i0 * cap, b.list1, (size_t)ni * cap * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipMemcpyAsync(out->list2 + (size_t)i0 * cap, b.list2, (size_t)ni * cap * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipMemcpyAsync(out->tile_any + (size_t)i0 * tiles, h->ws.tile_any, (size_t)ni * tiles, hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipStreamSynchronize(s));
+    }
+    return ECSEG_OK;
+}
+
+int ecseg_overlay(ecseg_ctx* h, const uint8_t* labels, const uint8_t* rgb, int n_img, int H, int W, int C, int sens, int hsr_thr,
+                  int64_t* out) {
+    DRIVER_OPEN(h);
+    if (n_img < 0 || H <= 0 || W <= 0 || C < 2 || (n_img > 0 && (!labels || !rgb || !out)))
+        return fail(h, ECSEG_E_INVALID, "overlay: bad arguments");
+    if (n_img == 0) return ECSEG_OK;
+    if (!px_below_2_31(H, W)) return fail(h, ECSEG_E_INVALID, "image too large");
+    USE_DEVICE(h);
+    const size_t px = (size_t)H * W;
+    const int chunk = h->post_chunk;
+    int rc;
+    if ((rc = ensure_post(h, std::min(n_img, chunk), px))) return rc;
+    if ((rc = h->d_gray.ensure(h, px * std::min(n_img, chunk)))) return rc;
+    if ((rc = h->d_aux8.ensure(h, px * C * std::min(n_img, chunk)))) return rc;
+    if ((rc = h->d_i64.ensure(h, (size_t)chunk * 12))) return rc;
+    hipStream_t s = h->stream;
+    clear_timings(h);
+    for (int i0 = 0; i0 < n_img; i0 += chunk) {
+        const int ni = std::min(chunk, n_img - i0);
+        HIP_TRY(h, hipMemcpyAsync(h->d_gray, labels + (size_t)i0 * px, px * ni, hipMemcpyHostToDevice, s));
+        HIP_TRY(h, hipMemcpyAsync(h->d_aux8, rgb + (size_t)i0 * px * C, px * C * ni, hipMemcpyHostToDevice, s));
+        TIMED(h, s, 0, 1, HIP_TRY(h, run_overlay(h->ws, h->d_gray, h->d_aux8, ni, H, W, C, sens, hsr_thr, h->d_i64, s)));
+        HIP_TRY(h, hipMemcpyAsync(out + (size_t)i0 * 12, h->d_i64, (size_t)ni * 12 * 8, hipMemcpyDeviceToHost, s));
+        WAIT_ADD(h, s, 0, 1);
+    }
+    return ECSEG_OK;
+}
+
+}  // extern "C"

@@ -1,5 +1,5 @@
 // Host-only: the Huffman code of a label PNG's one dynamic block, built from the image's 68 token counts, shared by the host coder
-// (deflate_labels, host_io.cpp) and the device coder's driver (ecseg_png_labels_encode, drivers.hip; kernels in png_kernels.hip).
+// (deflate_labels, host_io.cpp) and the device coder's driver (ecseg_png_labels_encode, drivers_files.hip; kernels in png_kernels.hip).
 // Tie-breaking has this one definition.  The stream is
 //   78 01 | block header | per scan line: the literal 0 (filter byte), then per run of k pixels of one colour its four palette
 //   literals, (k - 1) / 64 matches of 256 bytes, one match of 4 ((k - 1) % 64) bytes if that is not zero | end of block | zero bits

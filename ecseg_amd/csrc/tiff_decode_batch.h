@@ -1,4 +1,4 @@
-// A batch of TIFF files for one decode (ecseg_tiff_decode_batch, drivers.hip; the tiffb_* kernels, tiff_decode_kernels.hip): the
+// A batch of TIFF files for one decode (ecseg_tiff_decode_batch, drivers_files.hip; the tiffb_* kernels, tiff_decode_kernels.hip): the
 // device table, one TdFile row per file, and the one function that lays a batch out - where every file image, strip table and
 // raster lies in the packed buffers, the prefix sums over strips and rows that give every workgroup its file, and the arena the
 // call carves.  Plain C++: the driver includes it, and so does tools/asan/tiff_decode_batch_fuzz.cpp, which walks the same table on

@@ -1,5 +1,5 @@
 // Host-only: everything of an 8-bit LZW TIFF but its strips, shared by the host writer (tiff_write_u8, host_io.cpp) and the device
-// encoder's drivers (ecseg_tiff_encode, ecseg_fish_render_tiff; drivers.hip).  A file is
+// encoder's drivers (ecseg_tiff_encode, drivers_files.hip; ecseg_fish_render_tiff, drivers_fish.hip).  A file is
 //   head (8 bytes) | the strips back to back, a 0 after every strip of odd length | tail
 // and the tail is: the strip offset and count tables (more than one strip), BitsPerSample (more than two samples), a pad byte to an
 // even offset, the IFD.

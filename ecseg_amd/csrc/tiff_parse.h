@@ -1,5 +1,5 @@
 // Host-only: the TIFF parser of the native reader (parse_tiff, host_io.cpp) for the drivers, as tiff_frame.h serves the encoder: the
-// device reader (ecseg_tiff_decode, drivers.hip) reads the same tags by the same rules as ecseg_tiff_info / ecseg_tiff_read, and
+// device reader (ecseg_tiff_decode, drivers_files.hip) reads the same tags by the same rules as ecseg_tiff_info / ecseg_tiff_read, and
 // the one rule that says which files it takes.
 #pragma once
 #include <stddef.h>

@@ -11,7 +11,7 @@ set -e
 cd "$(dirname "$0")/../ecseg_amd/csrc"
 mkdir -p /tmp/w4
 HC="/opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 -fPIC"
-HOSTSRC="api filter_layout model_load plan_run segment drivers"
+HOSTSRC="api filter_layout model_load plan_run segment drivers_post drivers_interseg drivers_fish drivers_files drivers_nuset"
 for v in "$@"; do
   if [ "$v" = diag ]; then
     $HC -DECSEG_DIAG -c api.hip -o /tmp/w4/api_diag.o &
@@ -29,7 +29,7 @@ for v in "$@"; do
 done
 wait
 LK="/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC"
-HOST="model_load.o plan_run.o segment.o drivers.o"   # host objects no variant flag concerns
+HOST="model_load.o plan_run.o segment.o drivers_post.o drivers_interseg.o drivers_fish.o drivers_files.o drivers_nuset.o"   # host objects no variant flag concerns
 REST="layer_kernels.o convs_kernel.o post_kernels.o interseg_kernels.o fishdist_kernels.o host_codec.o host_io.o comm.o -lz -ldl"   # objects of the product build
 W4RS="wino4r_kernel.o wino4s_kernel.o"
 for v in "$@"; do
