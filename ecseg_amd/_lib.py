@@ -23,7 +23,7 @@ EXPORTS = [
     'ecseg_tiff_write_rgb8', 'ecseg_npy_write_i32_as_i64',
     'ecseg_tiff_encode_bound', 'ecseg_tiff_encode', 'ecseg_fish_render_tiff', 'ecseg_tiff_decode', 'ecseg_tiff_decode_routes',
     'ecseg_png_labels_encode', 'ecseg_meta_segment_files', 'ecseg_get_file_timings', 'ecseg_png_labels_stream_size',
-    'ecseg_ccl_pass_debug',
+    'ecseg_ccl_pass_debug', 'ecseg_meta_inference_stages_debug',
     'ecseg_tiff_decode_batch', 'ecseg_tiff_decode_batch_bytes', 'ecseg_tiff_decode_batch_routes', 'ecseg_tiff_decode_batch_counts',
 ]
 
@@ -125,6 +125,7 @@ def load_library():
     lib.ecseg_stitch_argmax.argtypes = [vp, vp, i32, i32, i32, vp]
     lib.ecseg_meta_inference.argtypes = [vp, u8p, i32, i32, i32, vp, vp]
     lib.ecseg_meta_inference_dev.argtypes = [vp, u8p, i32, i32, i32, vp, vp]
+    lib.ecseg_meta_inference_stages_debug.argtypes = [vp, u8p, i32, i32, i32, i32, i32, vp, vp]
     lib.ecseg_count_cc.argtypes = [vp, u8p, i32, i32, i32, vp, vp]
     lib.ecseg_ccl_labels.argtypes = [vp, u8p, i32, i32, i32, i32, vp]
     lib.ecseg_ccl_pass_debug.argtypes = [vp, u8p, u8p, i32, i32, i32, C.POINTER(CclPassDesc), C.POINTER(CclPassOut)]
@@ -528,6 +529,24 @@ class Handle:
     def meta_inference_dev(self, in_ptr, n, H, W, out_ptr, nec_ptr):
         self._check(self.lib.ecseg_meta_inference_dev(self.h, C.c_void_p(in_ptr), n, H, W, C.c_void_p(out_ptr),
                                                       C.c_void_p(nec_ptr) if nec_ptr else None), 'ecseg_meta_inference_dev')
+
+    def meta_inference_stages(self, labels, first, last, want_kill=False):
+        """Test-only (ecseg_meta_inference_stages_debug): stages ``first`` .. ``last`` of meta_inference alone on (n, H, W) or
+        (H, W) uint8 labels, the input of stage ``first`` -> the image after stage ``last`` (1 fill_holes(1), 2 fill_holes(2),
+        3 size_thresh + ec_band_removal, 4 nucleus_in_metaphase, 5 merge_comp(1), 6 merge_comp(2) + the final dilation).
+        ``want_kill``: -> (image, kill), kill = 1 at the pixels of the nuclei stage 4 erases (zeros when the range has no stage 4)."""
+        a = _u8(labels)
+        single = a.ndim == 2
+        if single:
+            a = a[None]
+        n, H, W = a.shape
+        out = np.empty_like(a)
+        kill = np.zeros_like(a) if want_kill else None
+        self._check(self.lib.ecseg_meta_inference_stages_debug(self.h, _ptr(a), n, H, W, int(first), int(last), _ptr(out), _ptr(kill)),
+                    'ecseg_meta_inference_stages_debug')
+        if single:
+            out, kill = out[0], (kill[0] if want_kill else None)
+        return (out, kill) if want_kill else out
 
     # ---- counting -----------------------------------------------------------------------------------
     @staticmethod

@@ -213,9 +213,11 @@ inline PostWorkspace post_workspace(Carver& c, int n_img, size_t px) {
     return w;
 }
 
-// meta_inference on n_img uint8 label images, in place; n_ec receives count_cc(img==3)[0] per image
+// meta_inference on n_img uint8 label images, in place; n_ec receives count_cc(img==3)[0] per image (when last == 6).
+// first..last: the stages to run, 1..6 in production (the whole schedule); a partial range is test-only, as is kill_dev
+// (n_img * H * W bytes, written when the range holds stage 4: 1 where the nucleus test erases the pixel).
 hipError_t run_meta_inference(PostWorkspace& ws, uint8_t* img, int n_img, int H, int W, int32_t* n_ec_dev,
-                              hipStream_t s);
+                              hipStream_t s, int first, int last, uint8_t* kill_dev = nullptr);
 hipError_t run_count_cc(PostWorkspace& ws, const uint8_t* mask, int n_img, int H, int W, int32_t* n_dev,
                         long long* px_dev, hipStream_t s);
 hipError_t run_ccl_labels(PostWorkspace& ws, const uint8_t* mask, int n_img, int H, int W, int conn,

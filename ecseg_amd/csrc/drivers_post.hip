@@ -55,7 +55,7 @@ int ecseg_meta_inference_dev(ecseg_ctx* h, const uint8_t* in, int n_img, int H, 
     TIMED(h, s, 0, 1,
           for (int i0 = 0; i0 < n_img; i0 += h->post_chunk) {
               const int ni = std::min(h->post_chunk, n_img - i0);
-              HIP_TRY(h, run_meta_inference(h->ws, out + (size_t)i0 * px, ni, H, W, n_ec ? n_ec + i0 : nullptr, s));
+              HIP_TRY(h, run_meta_inference(h->ws, out + (size_t)i0 * px, ni, H, W, n_ec ? n_ec + i0 : nullptr, s, 1, 6));
           });
     HIP_TRY(h, hipStreamSynchronize(s));
     clear_timings(h);                                        // (behind the wait, where every other driver clears before its upload: a failed call keeps the timings of the one before)
@@ -77,6 +77,37 @@ int ecseg_meta_inference(ecseg_ctx* h, const uint8_t* in, int n_img, int H, int 
     HIP_TRY(h, hipMemcpyAsync(out, h->d_post, tot, hipMemcpyDeviceToHost, h->stream));
     if (n_ec) HIP_TRY(h, hipMemcpyAsync(n_ec, h->d_i32, (size_t)n_img * 4, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return ECSEG_OK;
+}
+
+// Test-only: stages first..last of the clean-up alone (run_meta_inference with a partial range), uploaded and chunked as
+// ecseg_meta_inference does it; kill_out (may be null): the nucleus test's per-pixel decision when the range holds stage 4.
+int ecseg_meta_inference_stages_debug(ecseg_ctx* h, const uint8_t* in, int n_img, int H, int W, int first, int last, uint8_t* out,
+                                      uint8_t* kill_out) {
+    DRIVER_OPEN(h);
+    if (n_img < 0 || H <= 0 || W <= 0 || (n_img > 0 && (!in || !out))) return fail(h, ECSEG_E_INVALID, "meta_inference_stages: bad arguments");
+    if (first < 1 || last > 6 || first > last) return fail(h, ECSEG_E_INVALID, "meta_inference_stages: stages are 1..6, first <= last");
+    if (n_img == 0) return ECSEG_OK;
+    if (!px_below_2_31(H, W)) return fail(h, ECSEG_E_INVALID, "image too large");
+    USE_DEVICE(h);
+    const size_t px = (size_t)H * W, tot = px * n_img;
+    const int chunk = std::min(n_img, h->post_chunk);
+    const bool kill = kill_out && first <= 4 && last >= 4;
+    int rc;
+    if ((rc = h->d_post.ensure(h, tot))) return rc;
+    if ((rc = ensure_post(h, chunk, px))) return rc;
+    if (kill && (rc = h->d_gray.ensure(h, px * chunk))) return rc;
+    hipStream_t s = h->stream;
+    HIP_TRY(h, hipMemcpyAsync(h->d_post, in, tot, hipMemcpyHostToDevice, s));
+    for (int i0 = 0; i0 < n_img; i0 += chunk) {              // (untimed: stage_ms keeps the call before's)
+        const int ni = std::min(chunk, n_img - i0);
+        const hipError_t e = run_meta_inference(h->ws, h->d_post.p + (size_t)i0 * px, ni, H, W, nullptr, s, first, last,
+                                                kill ? h->d_gray.p : nullptr);
+        if (e != hipSuccess) return fail_hip(h, e, "meta_inference_stages kernels");
+        if (kill) HIP_TRY(h, hipMemcpyAsync(kill_out + (size_t)i0 * px, h->d_gray, px * ni, hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(h, hipMemcpyAsync(out, h->d_post, tot, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
     return ECSEG_OK;
 }
 

@@ -1189,8 +1189,21 @@ __global__ __launch_bounds__(256) void merge_open_kernel(CclGeom g, const uint8_
     }
 }
 
-hipError_t run_meta_inference(PostWorkspace& ws, uint8_t* img, int n_img, int H, int W, int32_t* n_ec_dev, hipStream_t s) {
+// test-only (stages_debug): which nucleus pixels the metaphase test erases, read from the flag words before the kill kernel runs
+__global__ __launch_bounds__(256) void export_nucleus_kill_kernel(const uint8_t* __restrict__ img, const int32_t* __restrict__ L,
+                                                                  const uint32_t* __restrict__ flag, int n_img, size_t px,
+                                                                  uint8_t* __restrict__ kill) {
+    IMG_PX_LOOP(n_img, px) kill[t] = (img[t] == 1 && (flag[ib + L[ib + L[t]]] & 2u)) ? 1 : 0;
+}
+
+// Stages first..last of the clean-up (1 fill_holes(1), 2 fill_holes(2), 3 size_thresh + band, 4 nucleus test, 5 merge_comp(1),
+// 6 merge_comp(2) + final dilation): `img` holds the input of stage `first` and receives the image after stage `last`.  1..6 is
+// the production schedule, launch for launch; a partial range (test-only) adds the copies into the buffer a stage expects
+// (ws.tmpA from stage 4 on) and out of the one it leaves its result in.  kill_dev (test-only, with stage 4): see above.
+hipError_t run_meta_inference(PostWorkspace& ws, uint8_t* img, int n_img, int H, int W, int32_t* n_ec_dev, hipStream_t s,
+                              int first, int last, uint8_t* kill_dev) {
     if (n_img <= 0) return hipSuccess;
+    if (first < 1 || last > 6 || first > last) return hipErrorInvalidValue;
     const CclGeom g = make_geom(n_img, H, W);
     const size_t px = (size_t)H * W;
     const dim3 ig = img_grid(px, n_img);
@@ -1210,6 +1223,7 @@ hipError_t run_meta_inference(PostWorkspace& ws, uint8_t* img, int n_img, int H,
     }
     // 1. fill_holes(1), fill_holes(2)
     for (int c = 1; c <= 2; ++c) {
+        if (c < first || c > last) continue;
         CclPass p{img, lut_ne(c), 4, 0, AUX_BORDER, 0, nullptr, 0};
         p.sparse = true;
         p.allow_full = true;
@@ -1220,7 +1234,9 @@ hipError_t run_meta_inference(PostWorkspace& ws, uint8_t* img, int n_img, int H,
     // result into it)
     uint8_t* cur = ws.tmpA;
     uint8_t* nxt = ws.tmpB;
-    {
+    const size_t tot = px * (size_t)n_img;
+    if (first > 3 && (e = hipMemcpyAsync(cur, img, tot, hipMemcpyDeviceToDevice, s)) != hipSuccess) return e;    // (partial range)
+    if (first <= 3 && last >= 3) {
         CclPass p{img, LUT_MULTI, 8, STAT_AREA, AUX_NONE, 0, nullptr, NEED_NCOMP | NEED_NPX};
         p.sparse = true;
         p.g = ws.g + 0 * gslot;
@@ -1229,7 +1245,7 @@ hipError_t run_meta_inference(PostWorkspace& ws, uint8_t* img, int n_img, int H,
         else hipLaunchKernelGGL(thresh_band_kernel<false>, dim3(tg), dim3(256), 0, s, g, img, cur, ws.L, ws.area, p.g, 15);
     }
     // 6. nucleus-in-metaphase test
-    {
+    if (first <= 4 && last >= 4) {
         const size_t cap = px / 4 + (size_t)(H + W) / 2 + 4;
         int32_t* list1 = ws.list;
         double2* list2 = reinterpret_cast<double2*>(ws.list + (((size_t)n_img * cap + 3) & ~(size_t)3));
@@ -1261,11 +1277,13 @@ hipError_t run_meta_inference(PostWorkspace& ws, uint8_t* img, int n_img, int H,
             hipLaunchKernelGGL(nucleus_test_kernel, dim3(n_img * bpi), dim3(256), 0, s, ws.area, ws.sumy, ws.sumx, p.g, list1,
                                list2, ws.flag, px, cap, bpi, 70.0, 5, H, W, ws.binned_cap);
         }
+        if (kill_dev) hipLaunchKernelGGL(export_nucleus_kill_kernel, ig, dim3(256), 0, s, cur, ws.L, ws.flag, n_img, px, kill_dev);
         if (v4) hipLaunchKernelGGL(nucleus_kill4_kernel, ig4, dim3(256), 0, s, cur, ws.L, ws.flag, n_img, px / 4);
         else hipLaunchKernelGGL(apply_nucleus_kill_kernel, ig, dim3(256), 0, s, cur, ws.L, ws.flag, n_img, px);
     }
     // 7-8. merge_comp(1), merge_comp(2); 9. the final ecDNA dilation rides on the second one, which writes the caller's buffer
     for (int c = 1; c <= 2; ++c) {
+        if (c + 4 < first || c + 4 > last) continue;
         const int m = (c == 1) ? 2 : 1;
         const uint32_t lut = lut_nonzero_except(m);
         CclPass p{cur, lut, 8, 0, AUX_VALUE_EQ, c, nullptr, NEED_LAST};
@@ -1281,8 +1299,9 @@ hipError_t run_meta_inference(PostWorkspace& ws, uint8_t* img, int n_img, int H,
             else hipLaunchKernelGGL((merge_open_kernel<true, false>), dim3(tg), dim3(256), 0, s, g, cur, img, ws.L, ws.flag, p.g, c, m, lut);
         }
     }
+    if (last >= 3 && last <= 5 && (e = hipMemcpyAsync(img, cur, tot, hipMemcpyDeviceToDevice, s)) != hipSuccess) return e;   // (partial range)
     // 10. count_cc(img == 3)[0]
-    if (n_ec_dev) {
+    if (n_ec_dev && last == 6) {
         CclPass p{img, lut_eq(3), 8, 0, AUX_NONE, 0, nullptr, NEED_NCOMP | NEED_NPX, true};
         p.sparse = true;
         p.g = ws.g + 4 * gslot;

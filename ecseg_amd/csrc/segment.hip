@@ -205,7 +205,7 @@ int segment_dev(ecseg_ctx* h, const uint8_t* gray, int n_img, int H, int W, uint
         HIP_TRY(h, hipEventRecord(e6[4], s2));
         if (post != raw)
             HIP_TRY(h, hipMemcpyAsync(post + (size_t)i0 * px, raw + (size_t)i0 * px, px * ni, hipMemcpyDeviceToDevice, s2));
-        HIP_TRY(h, run_meta_inference(h->ws, post + (size_t)i0 * px, ni, H, W, n_ec ? n_ec + i0 : nullptr, s2));
+        HIP_TRY(h, run_meta_inference(h->ws, post + (size_t)i0 * px, ni, H, W, n_ec ? n_ec + i0 : nullptr, s2, 1, 6));
         HIP_TRY(h, hipEventRecord(e6[5], s2));
     }
     const double tq1 = dbg_now();

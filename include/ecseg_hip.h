@@ -55,6 +55,8 @@ extern "C" {
  * ecseg_tiff_decode_batch_counts, many TIFF files decoded in one device call, a wave per strip of any file; nothing existing changed.) */
 /* (still 5 - additive: ecseg_ccl_pass_debug, one connected-component labelling pass alone with everything it produced read back, for
  * the tests of the labelling kernels; nothing existing changed.) */
+/* (still 5 - additive: ecseg_meta_inference_stages_debug, a range of the six clean-up stages of meta_inference alone on given images, for
+ * the tests of the kernels between the labelling passes; nothing existing changed.) */
 #define ECSEG_ABI_VERSION 5
 
 #define ECSEG_OK             0
@@ -258,6 +260,13 @@ int ecseg_meta_inference(ecseg_ctx* h, const uint8_t* labels_in, int n_img, int 
                          uint8_t* labels_out, int32_t* n_ec);
 int ecseg_meta_inference_dev(ecseg_ctx* h, const uint8_t* labels_in_dev, int n_img, int H, int W,
                              uint8_t* labels_out_dev, int32_t* n_ec_dev);
+/* Test-only: stages first..last of meta_inference alone.  labels_in is the input of stage `first`, labels_out the image after stage
+ * `last`: 1 fill_holes(1), 2 fill_holes(2), 3 size_thresh + ec_band_removal (:41-64), 4 the nucleus-in-metaphase test (:66-81),
+ * 5 merge_comp(1), 6 merge_comp(2) + the final ecDNA dilation (:83).  1..6 is ecseg_meta_inference without the count.  kill_out (may
+ * be NULL; (n_img, H, W), written when the range holds stage 4): 1 at the pixels of the nuclei the test erases, 0 elsewhere.
+ * ECSEG_E_INVALID: a range outside 1..6 or first > last. */
+int ecseg_meta_inference_stages_debug(ecseg_ctx* h, const uint8_t* labels_in, int n_img, int H, int W, int first, int last,
+                                      uint8_t* labels_out, uint8_t* kill_out);
 
 /* ---- counting (src/image_tools.py:103-134) ---------------------------------------------------------------- */
 /* masks are uint8 (non-zero = True), (n_img, H, W). */
