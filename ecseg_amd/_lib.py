@@ -25,6 +25,7 @@ EXPORTS = [
     'ecseg_png_labels_encode', 'ecseg_meta_segment_files', 'ecseg_get_file_timings', 'ecseg_png_labels_stream_size',
     'ecseg_ccl_pass_debug', 'ecseg_meta_inference_stages_debug',
     'ecseg_tiff_decode_batch', 'ecseg_tiff_decode_batch_bytes', 'ecseg_tiff_decode_batch_routes', 'ecseg_tiff_decode_batch_counts',
+    'ecseg_meta_segment_tiffs', 'ecseg_meta_segment_tiffs_files', 'ecseg_prefetch_tiffs', 'ecseg_get_read_timings',
 ]
 
 
@@ -179,6 +180,11 @@ def load_library():
     lib.ecseg_meta_segment_files.argtypes = [vp, vp, i32, i32, i32, i32, i32, C.POINTER(vp), C.c_longlong, C.POINTER(C.c_longlong),
                                              C.POINTER(vp), C.c_longlong, C.POINTER(C.c_longlong), vp, vp, vp, vp]
     lib.ecseg_get_file_timings.argtypes = [vp, C.POINTER(C.c_float)]
+    lib.ecseg_meta_segment_tiffs.argtypes = [vp, vp, C.c_longlong, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp]
+    lib.ecseg_meta_segment_tiffs_files.argtypes = [vp, vp, C.c_longlong, vp, i32, i32, i32, i32, i32, vp, C.POINTER(vp), C.c_longlong,
+                                                   C.POINTER(C.c_longlong), C.POINTER(vp), C.c_longlong, C.POINTER(C.c_longlong), vp, vp, vp, vp]
+    lib.ecseg_prefetch_tiffs.argtypes = [vp, vp, C.c_longlong, vp, i32, i32, i32, i32, i32]
+    lib.ecseg_get_read_timings.argtypes = [vp, C.POINTER(C.c_float)]
     lib.ecseg_png_write.argtypes = [C.c_char_p, vp, i32, i32, i32, i32]
     lib.ecseg_png_write_channel.argtypes = [C.c_char_p, vp, i32, i32, i32, i32, i32]
     lib.ecseg_npy_label_info.argtypes = [C.c_char_p, C.POINTER(i32), C.POINTER(i32)]
@@ -468,6 +474,82 @@ class Handle:
         ms = (C.c_float * 2)()
         self._check(self.lib.ecseg_get_file_timings(self.h, ms), 'ecseg_get_file_timings')
         return {'dapi': float(ms[0]), 'png': float(ms[1])}
+
+    @staticmethod
+    def _tiffs_packed(datas, shape):
+        """the files of one ``meta_segment_tiffs`` call -> (buffer, ranges, n, H, W, C, bytes per sample); ``shape``: the batch's common
+        (H, W, samples per pixel, bits per sample), a row of ``tiff_decode_packed``'s shapes"""
+        bufs = [np.frombuffer(d, np.uint8) if isinstance(d, (bytes, bytearray, memoryview)) else _u8(d).reshape(-1) for d in datas]
+        buf, ranges = pack_file_images(bufs)
+        H, W, Cc, bits = (int(v) for v in shape)
+        if bits not in (8, 16):
+            raise ValueError('meta_segment_tiffs takes 8- or 16-bit samples, got %d bits' % bits)
+        return buf, ranges, len(bufs), H, W, Cc, bits // 8
+
+    def meta_segment_tiffs(self, datas, shape, gray_out=None, post_out=None):
+        """``meta_segment`` on the bytes of n TIFF files of one ``shape`` (H, W, samples per pixel, bits per sample), decoded on the
+        device straight into the batch (ecseg_meta_segment_tiffs) -> (gray, post, n_ec, tie_risk, status).  status[i] is 0, or the
+        code ``tiff_decode`` fails with for file i alone (a file of another shape: -1); such an image is the all-zero image and its
+        n_ec is -1.  Files that are views of one buffer in ascending order (``pack_file_images``) are not copied: with
+        ``prefetch_tiffs`` that buffer is page-locked."""
+        buf, ranges, n, H, W, Cc, bps = self._tiffs_packed(datas, shape)
+        outs = self._gray_post(gray_out, post_out, n, H, W)
+        nec = np.zeros(n, np.int32); tie = np.zeros(n, np.int32); status = np.zeros(n, np.int32)
+        t0 = time.perf_counter()
+        rc = self.lib.ecseg_meta_segment_tiffs(self.h, _ptr(buf), buf.size, _ptr(ranges), n, H, W, Cc, bps, _ptr(status), _ptr(outs[0]), _ptr(outs[1]),
+                                               _ptr(nec), _ptr(tie))
+        self.native_seconds += time.perf_counter() - t0
+        self._check(rc, 'ecseg_meta_segment_tiffs')
+        return outs[0], outs[1], nec, tie, status.tolist()
+
+    def meta_segment_tiffs_files(self, datas, shape, gray_out=None, post_out=None, dapi_capacity=None, png_capacity=None, file_bufs=None):
+        """``meta_segment_files`` on the bytes of n TIFF files (ecseg_meta_segment_tiffs_files) -> (gray, post, n_ec, tie_risk, dapi_files,
+        png_files, status); the arguments behind ``shape`` and the files are ``meta_segment_files``'s, status is ``meta_segment_tiffs``'s.
+        An image whose status is not 0 has no files (None)."""
+        buf, ranges, n, H, W, Cc, bps = self._tiffs_packed(datas, shape)
+        outs = self._gray_post(gray_out, post_out, n, H, W)
+        dcap = H * W + 65536 if dapi_capacity is None else int(dapi_capacity)
+        pcap = H * W // 2 + 65536 if png_capacity is None else int(png_capacity)
+        dbuf, dptr = self._file_slots(file_bufs[0] if file_bufs else None, n, max(dcap, 1))
+        pbuf, pptr = self._file_slots(file_bufs[1] if file_bufs else None, n, max(pcap, 1))
+        dn, pn = (C.c_longlong * max(n, 1))(), (C.c_longlong * max(n, 1))()
+        nec = np.zeros(n, np.int32); tie = np.zeros(n, np.int32); status = np.zeros(n, np.int32)
+        t0 = time.perf_counter()
+        rc = self.lib.ecseg_meta_segment_tiffs_files(self.h, _ptr(buf), buf.size, _ptr(ranges), n, H, W, Cc, bps, _ptr(status), dptr, dcap, dn,
+                                                     pptr, pcap, pn, _ptr(outs[0]), _ptr(outs[1]), _ptr(nec), _ptr(tie))
+        self.native_seconds += time.perf_counter() - t0
+        self._check(rc, 'ecseg_meta_segment_tiffs_files')
+        self.last_file_bytes = list(dn)[:n] + list(pn)[:n]
+        copy = not file_bufs
+        return (outs[0], outs[1], nec, tie, self._files_of(dbuf, list(dn)[:n], max(dcap, 1), copy), self._files_of(pbuf, list(pn)[:n], max(pcap, 1), copy),
+                status.tolist())
+
+    @staticmethod
+    def _gray_post(gray_out, post_out, n, H, W):
+        outs = []
+        for o in (gray_out, post_out):
+            if o is None:
+                o = np.empty((n, H, W), np.uint8)
+            elif o.shape != (n, H, W) or o.dtype != np.uint8 or not o.flags.c_contiguous:
+                raise ValueError('output buffers must be C-contiguous uint8 arrays of shape %s' % ((n, H, W),))
+            outs.append(o)
+        return outs
+
+    def prefetch_tiffs(self, datas, shape=None):
+        """Name the files of the ``meta_segment_tiffs[_files]`` call AFTER the coming one, as that call will pass them (views of one
+        page-locked buffer, unchanged until then): the coming call uploads and decodes them under its kernels
+        (ecseg_prefetch_tiffs).  None withdraws."""
+        if datas is None:
+            self._check(self.lib.ecseg_prefetch_tiffs(self.h, None, 0, None, 0, 0, 0, 0, 0), 'ecseg_prefetch_tiffs')
+            return
+        buf, ranges, n, H, W, Cc, bps = self._tiffs_packed(datas, shape)
+        self._check(self.lib.ecseg_prefetch_tiffs(self.h, _ptr(buf), buf.size, _ptr(ranges), n, H, W, Cc, bps), 'ecseg_prefetch_tiffs')
+
+    def read_timings(self):
+        """Device milliseconds of the TIFF decode kernels that served the last ``meta_segment_tiffs[_files]`` call."""
+        ms = (C.c_float * 1)()
+        self._check(self.lib.ecseg_get_read_timings(self.h, ms), 'ecseg_get_read_timings')
+        return {'decode': float(ms[0])}
 
     def prefetch_input(self, imgs):
         """Name the raw images (a C-contiguous array in page-locked memory) of the meta_segment call AFTER the coming one: the

@@ -66,6 +66,7 @@ int ecseg_create(ecseg_ctx** out, int device_id) {
     }
     for (auto& ev : h->ev) (void)hipEventCreate(&ev);
     for (auto& ev : h->ev_files) (void)hipEventCreate(&ev);
+    for (auto& ev : h->ev_read) (void)hipEventCreate(&ev);
     if (hipMalloc(reinterpret_cast<void**>(&h->zero_page), 1024) == hipSuccess) (void)hipMemset(h->zero_page, 0, 1024);
     else h->zero_page = nullptr;
     *out = h;
@@ -84,6 +85,7 @@ void ecseg_destroy(ecseg_ctx* h) {
     { DevMem dying(std::move(static_cast<DevMem&>(*h))); }
     for (auto& ev : h->ev) if (ev) (void)hipEventDestroy(ev);
     for (auto& ev : h->ev_files) if (ev) (void)hipEventDestroy(ev);
+    for (auto& ev : h->ev_read) if (ev) (void)hipEventDestroy(ev);
     if (h->ev_block) (void)hipEventDestroy(h->ev_block);
     if (h->stream_in) { (void)hipStreamSynchronize(h->stream_in); (void)hipStreamDestroy(h->stream_in); }
     if (h->ev_pre) (void)hipEventDestroy(h->ev_pre);

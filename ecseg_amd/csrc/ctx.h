@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "common.h"
+#include "tiff_parse.h"
 
 namespace ecseg {
 
@@ -114,6 +115,22 @@ struct DevMem {
     DevBuf<uint8_t> call_arena;   // everything a driver can size before its first launch
     DevBuf<uint8_t> count_arena;  // the FISH drivers: what is sized by the cell count, read back while call_arena is in use
     DevBuf<uint8_t> keep_arena;   // `iseg`, left by ecseg_nuclei_regions for ecseg_nucleus_crops: no other driver touches it
+    DevBuf<uint8_t> pre_arena;    // ecseg_prefetch_tiffs: the decode-ahead's file images, tables and status words; they outlive the call that launched it, which call_arena does not
+};
+
+// A batch of TIFF files that decode into the input slots of one ecseg_meta_segment_tiffs call (segment.hip): the key the call after
+// recognises them by, what the host made of every file, and the layout with raster i at i * H * W * C * bytes_per_sample.
+struct TiffsKey {
+    const uint8_t* files = nullptr; long long bytes = 0; int n = 0, H = 0, W = 0, C = 0, bps = 0;
+    std::vector<int64_t> ranges;
+    bool same(const TiffsKey& o) const {
+        return files && files == o.files && bytes == o.bytes && n == o.n && H == o.H && W == o.W && C == o.C && bps == o.bps && ranges == o.ranges;
+    }
+};
+struct TiffsPlan {
+    std::vector<int> verdict;        // per file: ecseg_tiff_decode's status before any device work, or ECSEG_E_INVALID for another shape
+    TdBatchLayout L;
+    std::vector<uint32_t> tables;    // the strip tables as the device takes them
 };
 
 }  // namespace ecseg
@@ -149,6 +166,10 @@ struct ecseg_ctx : ecseg::DevMem {
     const void* next_host = nullptr; size_t next_bytes = 0;   // registered by ecseg_prefetch_input for the coming call to send ahead
     hipStream_t stream_in = nullptr;
     hipEvent_t ev_pre = nullptr;
+    ecseg::TiffsKey next_tiffs;      // registered by ecseg_prefetch_tiffs for the coming call to decode ahead
+    ecseg::TiffsKey pre_tiffs;       // what d_pre holds decoded (files == nullptr: nothing), with pre_plan and the status words at pre_file_status
+    ecseg::TiffsPlan pre_plan;
+    uint32_t* pre_file_status = nullptr;   // in pre_arena: read by the call that takes the rasters, after ev_pre
     int min_cut_lds_pixels = ECSEG_MIN_CUT_LDS_PIXELS;   // windows above this many pixels keep their state in global memory (tests lower it)
     ecseg::PostWorkspace ws{};       // carved from post_arena
     ecseg::RegionMapBufs iseg{};     // carved from keep_arena
@@ -173,6 +194,8 @@ struct ecseg_ctx : ecseg::DevMem {
     float stage_ms[ECSEG_T_N] = {};
     hipEvent_t ev_files[6] = {};     // the device file coders: [0, 1] the batched dapi strips, [2, 3] the PNG count, [4, 5] the PNG emit
     float file_ms[2] = {};           // device time of the last ecseg_meta_segment_files call's dapi encode and PNG kernels
+    hipEvent_t ev_read[4] = {};      // the TIFF decode kernels: [0, 1] of the call itself, [2, 3] of the decode-ahead on stream_in
+    float read_ms = 0.f, pre_read_ms = 0.f;   // device time of the decode that served the last ecseg_meta_segment_tiffs call / of the decode-ahead in d_pre
     bool profile_kernels = false;
     std::vector<hipEvent_t> prof_events;   // pairs
     std::vector<hipEvent_t> grp_events;    // 6 per image group of segment_dev
@@ -216,6 +239,7 @@ int lay_out(ecseg_ctx* h, DevBuf<uint8_t>& arena, F&& layout, const char* what =
 inline void drop_sent_ahead(ecseg_ctx* h) {
     h->next_host = nullptr; h->next_bytes = 0;
     h->pre_host = nullptr; h->pre_bytes = 0;
+    h->next_tiffs.files = nullptr; h->pre_tiffs.files = nullptr;     // (ecseg_prefetch_tiffs: the same rule)
 }
 
 // api.hip
@@ -234,6 +258,12 @@ int tiff_collect(ecseg_ctx* h, const char* who, int n_files, int H, int W, int s
 // host, emit into count_arena, frame.  *ms: device time of the kernels.
 int png_encode_files(ecseg_ctx* h, const char* who, const uint8_t* d_labels, int n, int H, int W, const PngEncodeBufs& b,
                      uint8_t* const* files, long long file_cap, long long* file_bytes, float* ms);
+
+// The files of a batch as ecseg_tiff_decode judges each alone: info[i] and status[i] (with_strips: the file is to be decoded, not only
+// measured), and the rows of the layout for the files that are ECSEG_OK (dst_offsets may be null: the rasters back to back, 16-bit
+// ones on even offsets).  Empty string, or which argument is wrong.
+std::string tiff_batch_plan(const uint8_t* files, long long files_bytes, const int64_t* ranges, int n_files, const int64_t* dst_offsets,
+                            bool with_strips, std::vector<TiffInfo>& info, std::vector<int>& status, std::vector<TdFileIn>& in);
 
 // filter_layout.hip: host arrays to host arrays
 std::vector<float> relayout_conv(const float* w, int R, int S, int cin, int cout, int chunks, int np);

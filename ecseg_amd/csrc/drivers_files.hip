@@ -130,10 +130,8 @@ static int tiff_decode_verdict(const uint8_t* file, size_t n, bool with_strips, 
     return with_strips ? tiff_strips_in_file(t, n, why) : ECSEG_OK;
 }
 
-// The files of a batch as ecseg_tiff_decode judges each alone: info[i] and status[i] (with_strips as there), and the rows of the
-// layout for the files that are ECSEG_OK (dst_offsets may be null: the rasters back to back, 16-bit ones on even offsets).  Empty
-// string, or which argument is wrong.
-static std::string tiff_batch_plan(const uint8_t* files, long long files_bytes, const int64_t* ranges, int n_files, const int64_t* dst_offsets,
+// The files of a batch as ecseg_tiff_decode judges each alone (ctx.h says what comes back).
+std::string ecseg::tiff_batch_plan(const uint8_t* files, long long files_bytes, const int64_t* ranges, int n_files, const int64_t* dst_offsets,
                                    bool with_strips, std::vector<TiffInfo>& info, std::vector<int>& status, std::vector<TdFileIn>& in) {
     info.assign((size_t)n_files, TiffInfo()); status.assign((size_t)n_files, ECSEG_OK); in.assign((size_t)n_files, TdFileIn());
     long long end = 0;

@@ -1,5 +1,6 @@
 // The image pipeline: stitch geometry per image size, the clean-up workspace, segment_dev (tile -> U-Net -> stitch / argmax ->
-// meta_inference -> count, group by group) and the entry points around it, ecseg_meta_segment with its send-ahead buffer included.
+// meta_inference -> count, group by group) and the entry points around it, ecseg_meta_segment with its send-ahead buffer and
+// ecseg_meta_segment_tiffs, whose input files decode on the device into that buffer, included.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -310,17 +311,90 @@ int ecseg_preprocess(ecseg_ctx* h, const void* img, int n_img, int H, int W, int
 // files (ecseg_meta_segment_files): the two file images per image, the dapi strips encoded on the second stream beside the copy
 // of gray_out, the label PNGs behind the clean-up
 struct MetaFiles { uint8_t* const* dapi; long long dapi_cap; long long* dapi_bytes; uint8_t* const* png; long long png_cap; long long* png_bytes; };
+// tiffs (ecseg_meta_segment_tiffs): the input is the files themselves.  Their strips decode on the device straight into the input
+// slots (raster i at i * H * W * C * bps of d_aux8, or of d_pre for the call after: ecseg_prefetch_tiffs), and the host never sees a sample.
+struct MetaTiffs { const uint8_t* files; long long files_bytes; const int64_t* ranges; int32_t* status; };
+
+// What the host makes of the files of one such call: every file judged as ecseg_tiff_decode judges it alone, a file of another shape
+// than the call's refused, the rest laid out on the slots.  ECSEG_OK, or the argument error.
+static int tiffs_plan(ecseg_ctx* h, const uint8_t* files, long long files_bytes, const int64_t* ranges, int n, int H, int W, int C, int bps, TiffsPlan& p) {
+    const std::string me = "meta_segment_tiffs: ";
+    std::vector<TiffInfo> info; std::vector<TdFileIn> in;
+    std::string bad = tiff_batch_plan(files, files_bytes, ranges, n, nullptr, true, info, p.verdict, in);
+    if (!bad.empty()) return fail(h, ECSEG_E_INVALID, me + bad);
+    const uint64_t slot = (uint64_t)H * W * C * bps;
+    for (size_t i = 0; i < (size_t)n; ++i) {
+        TdFileIn& f = in[i];
+        if (!f.in_batch) continue;
+        if (f.H != (uint32_t)H || f.W != (uint32_t)W || f.spp != (uint32_t)C || f.bps != (uint32_t)bps) {     // (a raster of another size must not reach the slots)
+            f = TdFileIn();
+            p.verdict[i] = ECSEG_E_INVALID;
+            continue;
+        }
+        f.dst_off = i * slot;
+    }
+    if (!(bad = td_batch_layout(in, p.L)).empty()) return fail(h, ECSEG_E_INVALID, me + bad);
+    p.tables.assign((size_t)p.L.table_words, 0u);
+    for (size_t i = 0; i < (size_t)n; ++i) {
+        const TdFile& f = p.L.tab[i];
+        std::copy(info[i].off.begin(), info[i].off.begin() + f.n_table, p.tables.begin() + (size_t)f.table_off);
+        std::copy(info[i].cnt.begin(), info[i].cnt.begin() + f.n_table, p.tables.begin() + (size_t)f.table_off + f.n_table);
+    }
+    return ECSEG_OK;
+}
+
+// The decode's scratch beside the rasters, which are the input slots at `slots`: tiff_decode_batch_bufs without a raster buffer.
+static TiffDecodeBatchBufs tiffs_bufs(Carver& c, const TdBatchLayout& L, uint8_t* slots) {
+    TiffDecodeBatchBufs b;
+    b.tab = c.take<TdFile>(L.tab.size()); b.files = c.take<uint8_t>((size_t)L.src_span); b.tables = c.take<uint32_t>((size_t)L.table_words);
+    b.rasters = slots + L.dst_base; b.strip_status = c.take<uint32_t>((size_t)L.n_strips);
+    b.file_status = c.take<uint32_t>(L.tab.size());
+    return b;
+}
+
+// Upload and decode on stream s, the kernels between events e0 and e1.  p and the caller's files are read until s has been waited for.
+static int tiffs_launch(ecseg_ctx* h, const uint8_t* files, const TiffsPlan& p, const TiffDecodeBatchBufs& b, hipStream_t s, hipEvent_t e0, hipEvent_t e1) {
+    const TdBatchLayout& L = p.L;
+    if (L.src_span) HIP_TRY(h, hipMemcpyAsync(b.files, files + L.src_base, (size_t)L.src_span, hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(b.tab, L.tab.data(), L.tab.size() * sizeof(TdFile), hipMemcpyHostToDevice, s));
+    if (!p.tables.empty()) HIP_TRY(h, hipMemcpyAsync(b.tables, p.tables.data(), p.tables.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipEventRecord(e0, s));
+    HIP_TRY(h, run_tiff_decode_batch(b, L, s));
+    HIP_TRY(h, hipEventRecord(e1, s));
+    return ECSEG_OK;
+}
+
 static int meta_segment_run(ecseg_ctx* h, const void* img, int n_img, int H, int W, int C, int bps, uint8_t* gray_out, uint8_t* post,
-                            int32_t* n_ec, int32_t* tie_risk, const MetaFiles* files) {
+                            int32_t* n_ec, int32_t* tie_risk, const MetaFiles* files, const MetaTiffs* tiffs = nullptr) {
     int rc = check_model(h);
     if (rc) return rc;
+    const size_t px = (size_t)H * W, tot = px * n_img, slot = px * C * bps, in_bytes = tot * C * bps;
+    // what was named or sent ahead for the other kind of input is for nobody
+    if (tiffs) { h->next_host = nullptr; h->next_bytes = 0; h->pre_host = nullptr; h->pre_bytes = 0; }
+    else { h->next_tiffs.files = nullptr; h->pre_tiffs.files = nullptr; }
+    TiffsKey me;
+    TiffsPlan plan;
+    bool ahead = false;                                    // this call's rasters lie decoded in d_pre
+    if (tiffs) {
+        me.files = tiffs->files; me.bytes = tiffs->files_bytes; me.n = n_img; me.H = H; me.W = W; me.C = C; me.bps = bps;
+        me.ranges.assign(tiffs->ranges, tiffs->ranges + 2 * (size_t)n_img);
+        if (h->next_tiffs.same(me)) h->next_tiffs.files = nullptr;     // (registered for a call that never came: it names THIS call's files)
+        ahead = h->pre_tiffs.same(me) && h->d_pre && h->pre_file_status;
+        h->pre_tiffs.files = nullptr;                      // (files decoded ahead are for the very next call or for nobody)
+        h->read_ms = 0.f;
+        if (!ahead && (rc = tiffs_plan(h, tiffs->files, tiffs->files_bytes, tiffs->ranges, n_img, H, W, C, bps, plan))) return rc;
+    }
+    const TiffsPlan& my_plan = ahead ? h->pre_plan : plan;
     HIP_TRY(h, hipSetDevice(h->device));
-    const size_t px = (size_t)H * W, tot = px * n_img, in_bytes = tot * C * bps;
+    if ((rc = h->d_aux8.ensure(h, in_bytes))) return rc;
     TiffEncodeBufs tb{};
     PngEncodeBufs pb{};
-    if (files && (rc = lay_out(h, h->call_arena, [&](Carver& c) { tb = tiff_encode_bufs(c, H, W, 1, n_img, false); pb = png_encode_bufs(c, H, W, n_img, false); })))
+    TiffDecodeBatchBufs db{};
+    if ((files || (tiffs && !ahead)) && (rc = lay_out(h, h->call_arena, [&](Carver& c) {
+            if (files) { tb = tiff_encode_bufs(c, H, W, 1, n_img, false); pb = png_encode_bufs(c, H, W, n_img, false); }
+            if (tiffs && !ahead) db = tiffs_bufs(c, plan.L, h->d_aux8);
+        })))
         return rc;
-    if ((rc = h->d_aux8.ensure(h, in_bytes))) return rc;
     if ((rc = h->d_gray.ensure(h, tot))) return rc;
     if ((rc = h->d_raw.ensure(h, tot))) return rc;
     if ((rc = h->d_post.ensure(h, tot))) return rc;
@@ -328,8 +402,32 @@ static int meta_segment_run(ecseg_ctx* h, const void* img, int n_img, int H, int
     if ((rc = h->d_hist.ensure(h, (size_t)n_img * 256))) return rc;
     hipStream_t s = h->stream, sc = h->stream2;
     const double t0 = dbg_now();
-    if (h->next_host == img) { h->next_host = nullptr; h->next_bytes = 0; }     // (registered for a call that never came: it names THIS call's images)
-    if (h->pre_host == img && h->pre_bytes == in_bytes && h->d_pre) {
+    std::vector<int> st;                                   // tiffs: the status of every file
+    if (!tiffs && h->next_host == img) { h->next_host = nullptr; h->next_bytes = 0; }     // (registered for a call that never came: it names THIS call's images)
+    if (tiffs) {
+        const uint32_t* d_status = db.file_status;
+        if (ahead) {
+            // decoded ahead (ecseg_prefetch_tiffs) while the call before this one computed: the two input buffers change places, and
+            // the status words the decode left in pre_arena are read here, behind ev_pre
+            HIP_TRY(h, hipStreamWaitEvent(s, h->ev_pre, 0));
+            h->d_aux8.swap(h->d_pre);
+            d_status = h->pre_file_status;
+            h->read_ms = h->pre_read_ms;
+        } else if ((rc = tiffs_launch(h, tiffs->files, plan, db, s, h->ev_read[0], h->ev_read[1]))) {
+            return rc;
+        }
+        std::vector<uint32_t> corrupt((size_t)n_img, 0);
+        HIP_TRY(h, hipMemcpyAsync(corrupt.data(), d_status, (size_t)n_img * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipStreamSynchronize(s));               // (plan and the caller's files are read by the copies above: until here)
+        if (!ahead) h->read_ms = stage_elapsed(h->ev_read[0], h->ev_read[1]);
+        st = my_plan.verdict;
+        for (int i = 0; i < n_img; ++i) {
+            if (st[(size_t)i] == ECSEG_OK && corrupt[(size_t)i]) st[(size_t)i] = ECSEG_E_INVALID;
+            tiffs->status[i] = st[(size_t)i];
+            // an image that did not decode is the all-zero image: nothing an earlier call left in the slot reaches an output
+            if (st[(size_t)i] != ECSEG_OK) HIP_TRY(h, hipMemsetAsync(h->d_aux8 + (size_t)i * slot, 0, slot, s));
+        }
+    } else if (h->pre_host == img && h->pre_bytes == in_bytes && h->d_pre) {
         // these images were sent ahead (ecseg_prefetch_input) while the call before this one computed: the two input buffers
         // change places (the one given up last held the images of the call before, whose pre-processing is long over)
         HIP_TRY(h, hipStreamWaitEvent(s, h->ev_pre, 0));
@@ -362,6 +460,27 @@ static int meta_segment_run(ecseg_ctx* h, const void* img, int n_img, int H, int
         HIP_TRY(h, hipEventRecord(h->ev_pre, h->stream_in));
         h->pre_host = nx; h->pre_bytes = nb;
     }
+    bool sent_tiffs = false;
+    if (tiffs && h->next_tiffs.files) {                    // the next call's files, registered by ecseg_prefetch_tiffs: uploaded and decoded on
+        TiffsKey nx;                                       // stream_in into the spare input buffer, under this call's kernels
+        std::swap(nx, h->next_tiffs);
+        h->next_tiffs.files = nullptr;
+        // a set with an argument error is not decoded ahead: the call it was named for reports it
+        if (tiffs_plan(h, nx.files, nx.bytes, nx.ranges.data(), nx.n, nx.H, nx.W, nx.C, nx.bps, h->pre_plan) == ECSEG_OK) {
+            if (!h->stream_in) HIP_TRY(h, hipStreamCreateWithFlags(&h->stream_in, hipStreamNonBlocking));
+            if (!h->ev_pre) HIP_TRY(h, hipEventCreateWithFlags(&h->ev_pre, hipEventDisableTiming));
+            if ((rc = h->d_pre.ensure(h, (size_t)nx.n * nx.H * nx.W * nx.C * nx.bps))) return rc;
+            TiffDecodeBatchBufs ab{};
+            if ((rc = lay_out(h, h->pre_arena, [&](Carver& c) { ab = tiffs_bufs(c, h->pre_plan.L, h->d_pre); }, "hipMalloc(decode-ahead)"))) return rc;
+            if ((rc = tiffs_launch(h, nx.files, h->pre_plan, ab, h->stream_in, h->ev_read[2], h->ev_read[3]))) return rc;
+            HIP_TRY(h, hipEventRecord(h->ev_pre, h->stream_in));
+            h->pre_file_status = ab.file_status;
+            std::swap(h->pre_tiffs, nx);
+            sent_tiffs = true;
+        } else {
+            h->err.clear();
+        }
+    }
     const double t2 = dbg_now();
     if ((rc = segment_dev(h, h->d_gray, n_img, H, W, h->d_raw, h->d_post, h->d_i32))) return rc;
     const double t3 = dbg_now();
@@ -372,11 +491,20 @@ static int meta_segment_run(ecseg_ctx* h, const void* img, int n_img, int H, int
     const double t4 = dbg_now();
     HIP_TRY(h, wait_stream(h, sc));
     if (h->pre_host) HIP_TRY(h, wait_stream(h, h->stream_in));     // (long done: the caller's buffer is not read after this call)
+    if (sent_tiffs) {                                      // (the same; pre_plan's tables have been copied, the status words stay on the device)
+        HIP_TRY(h, wait_stream(h, h->stream_in));
+        h->pre_read_ms = stage_elapsed(h->ev_read[2], h->ev_read[3]);
+    }
     if (files) {                                           // (both streams are idle: the tables, then the files that fit)
         if ((rc = tiff_collect(h, "meta_segment_files", n_img, H, W, 1, tb, files->dapi, files->dapi_cap, files->dapi_bytes, false))) return rc;
         h->file_ms[0] = stage_elapsed(h->ev_files[0], h->ev_files[1]);
         if ((rc = png_encode_files(h, "meta_segment_files", h->d_post, n_img, H, W, pb, files->png, files->png_cap, files->png_bytes, &h->file_ms[1])))
             return rc;
+    }
+    for (size_t i = 0; i < st.size(); ++i) {               // a file that did not decode has no count and no files
+        if (st[i] == ECSEG_OK) continue;
+        if (n_ec) n_ec[i] = -1;
+        if (files) files->dapi_bytes[i] = files->png_bytes[i] = 0;
     }
     const double t5 = dbg_now();
     if (debug_calls()) fprintf(stderr, "[meta_segment n=%d] upload enqueue %.2f preprocess + gray copy enqueue %.2f segment_dev %.2f (stage timers %.2f) labels down %.2f gray wait %.2f total %.2f ms\n",
@@ -410,6 +538,73 @@ int ecseg_meta_segment_files(ecseg_ctx* h, const void* img, int n_img, int H, in
     if ((H + rps - 1) / rps >= (1 << 26)) return fail(h, ECSEG_E_INVALID, "meta_segment_files: 2^26 strips or more (such a file would pass 4 GiB)");
     const MetaFiles files{dapi_files, dapi_cap, dapi_bytes, png_files, png_cap, png_bytes};
     return meta_segment_run(h, img, n_img, H, W, C, bps, gray_out, labels_post, n_ec, tie_risk, &files);
+}
+
+// ecseg_meta_segment with the files themselves as its input: what both entry points refuse before any work
+static int tiffs_args(ecseg_ctx* h, const char* who, const uint8_t* files, long long files_bytes, const int64_t* file_ranges, int n_files, int H, int W,
+                      int C, int bps, bool outputs) {
+    if (n_files < 0 || files_bytes < 0 || H <= 0 || W <= 0 || (C != 1 && C != 3 && C != 4) || (bps != 1 && bps != 2) ||
+        (n_files > 0 && (!files || !file_ranges || !outputs)))
+        return fail(h, ECSEG_E_INVALID, std::string(who) + ": bad arguments");
+    if (n_files >= 65536) return fail(h, ECSEG_E_INVALID, std::string(who) + ": 65536 images or more");
+    return ECSEG_OK;
+}
+
+int ecseg_meta_segment_tiffs(ecseg_ctx* h, const uint8_t* files, long long files_bytes, const int64_t* file_ranges, int n_files, int H, int W, int C,
+                             int bps, int32_t* status, uint8_t* gray_out, uint8_t* labels_post, int32_t* n_ec, int32_t* tie_risk) {
+    if (!h) return ECSEG_E_INVALID;
+    if (int rc = tiffs_args(h, "meta_segment_tiffs", files, files_bytes, file_ranges, n_files, H, W, C, bps, status && labels_post)) {
+        drop_sent_ahead(h);
+        return rc;
+    }
+    if (n_files == 0) { drop_sent_ahead(h); return ECSEG_OK; }
+    const MetaTiffs tiffs{files, files_bytes, file_ranges, status};
+    return meta_segment_run(h, nullptr, n_files, H, W, C, bps, gray_out, labels_post, n_ec, tie_risk, nullptr, &tiffs);
+}
+
+int ecseg_meta_segment_tiffs_files(ecseg_ctx* h, const uint8_t* files, long long files_bytes, const int64_t* file_ranges, int n_files, int H, int W,
+                                   int C, int bps, int32_t* status, uint8_t* const* dapi_files, long long dapi_cap, long long* dapi_bytes,
+                                   uint8_t* const* png_files, long long png_cap, long long* png_bytes, uint8_t* gray_out, uint8_t* labels_post,
+                                   int32_t* n_ec, int32_t* tie_risk) {
+    if (!h) return ECSEG_E_INVALID;
+    const char* who = "meta_segment_tiffs_files";
+    int rc = tiffs_args(h, who, files, files_bytes, file_ranges, n_files, H, W, C, bps, status && labels_post);
+    if (!rc && (!dapi_files || !dapi_bytes || !png_files || !png_bytes || dapi_cap < 1 || png_cap < 1))
+        rc = fail(h, ECSEG_E_INVALID, std::string(who) + ": a null file table or a capacity below 1");
+    for (int i = 0; !rc && i < n_files; ++i)
+        if (!dapi_files[i] || !png_files[i]) rc = fail(h, ECSEG_E_INVALID, std::string(who) + ": a null file buffer");
+    if (!rc && W >= (1 << 30)) rc = fail(h, ECSEG_E_INVALID, std::string(who) + ": lines of 2^30 pixels or more");
+    const int rps = rc ? 1 : tiff_rows_per_strip(H, W, 1);
+    if (!rc && (H + rps - 1) / rps >= (1 << 26)) rc = fail(h, ECSEG_E_INVALID, std::string(who) + ": 2^26 strips or more (such a file would pass 4 GiB)");
+    if (rc || n_files == 0) { drop_sent_ahead(h); if (!rc) h->file_ms[0] = h->file_ms[1] = 0.f; return rc; }
+    h->file_ms[0] = h->file_ms[1] = 0.f;
+    const MetaFiles out{dapi_files, dapi_cap, dapi_bytes, png_files, png_cap, png_bytes};
+    const MetaTiffs tiffs{files, files_bytes, file_ranges, status};
+    return meta_segment_run(h, nullptr, n_files, H, W, C, bps, gray_out, labels_post, n_ec, tie_risk, &out, &tiffs);
+}
+
+int ecseg_get_read_timings(ecseg_ctx* h, float* ms_out) {
+    if (!h || !ms_out) return ECSEG_E_INVALID;
+    ms_out[0] = h->read_ms;
+    return ECSEG_OK;
+}
+
+// Names the files of the ecseg_meta_segment_tiffs call AFTER the coming one, as that call will pass them (page-locked memory, unchanged
+// until then).  The coming ecseg_meta_segment_tiffs call uploads them on the input stream and decodes them there into the spare input
+// buffer, under its own kernels, with scratch of its own (pre_arena: the status words are read by the call that takes the rasters); the
+// call after it recognises them by (pointer, bytes, ranges, n, shape), waits, swaps the buffers and skips upload and decode.  Any other
+// call withdraws them.  files == null or n_files == 0 withdraws.
+int ecseg_prefetch_tiffs(ecseg_ctx* h, const uint8_t* files, long long files_bytes, const int64_t* file_ranges, int n_files, int H, int W, int C,
+                         int bytes_per_sample) {
+    if (!h) return ECSEG_E_INVALID;
+    h->next_tiffs = TiffsKey();
+    if (!files || !file_ranges || n_files <= 0) return ECSEG_OK;
+    if (tiffs_args(h, "prefetch_tiffs", files, files_bytes, file_ranges, n_files, H, W, C, bytes_per_sample, true))
+        return ECSEG_E_INVALID;
+    TiffsKey& k = h->next_tiffs;
+    k.files = files; k.bytes = files_bytes; k.n = n_files; k.H = H; k.W = W; k.C = C; k.bps = bytes_per_sample;
+    k.ranges.assign(file_ranges, file_ranges + 2 * (size_t)n_files);
+    return ECSEG_OK;
 }
 
 int ecseg_get_file_timings(ecseg_ctx* h, float* ms_out) {

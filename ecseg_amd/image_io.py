@@ -268,6 +268,20 @@ def tiff_batch_goes_to_device(datas):
     return goes, counts
 
 
+def tiff_batch_counts(data):
+    """Whether the rule for a set counts this file (ecseg_tiff_decode_batch_counts: an LZW file that ecseg_tiff_decode accepts), on its
+    bytes as a uint8 array.  Touches no handle: `make metaseg`'s reader threads ask it."""
+    return bool(data.size) and load_library().ecseg_tiff_decode_batch_counts(data.ctypes.data_as(C.c_void_p), data.size) == 1
+
+
+def tiff_shape(data):
+    """(H, W, samples per pixel, bits per sample) of a classic TIFF file that ``tiff_batch_counts`` accepts, from its first directory."""
+    buf = memoryview(data)
+    bo = '<' if bytes(buf[:2]) == b'II' else '>'
+    t = _read_ifd(buf, struct.unpack_from(bo + 'I', buf, 4)[0], bo, False)
+    return int(t[257][0]), int(t[256][0]), int(t.get(277, (1,))[0]), int(t.get(258, (1,))[0])
+
+
 def imread_many(paths, handle=None):
     """``imread`` over a list of paths -> a list with, per path, the array ``imread(path)`` returns or the exception it raises, in its
     place.  ``handle``: anything with ``Handle.tiff_decode_many``: the ``.tif`` / ``.tiff`` files the routing rule for a set counts

@@ -13,7 +13,11 @@ Optional config keys (defaults keep the reference's behaviour): ``batch_images``
 ``resume`` (false; true: images whose ``labels/<stem>.npy``, ``.png`` and ``dapi/<name>`` exist are not segmented again),
 ``device_workers`` (1), ``pinned_mb`` (2048: page-locked host memory for the batch buffers; 0: none), ``files_on_device`` (false;
 true: ``dapi/<name>.tif`` and ``labels/<stem>.png`` are encoded on the GPU by the batch's device call and the writer threads only
-put the bytes on disk - the same bytes; a file the device did not produce is written by the host writer as before).
+put the bytes on disk - the same bytes; a file the device did not produce is written by the host writer as before), ``tiff_read_on_device`` (false; true: a reader thread
+only reads the bytes of a ``.tif`` file, and a batch of LZW files that the routing rule for a set accepts
+(ecseg_tiff_decode_batch_routes) is decoded on the GPU straight into the batch of the device call that segments it - the same
+samples; ``.npy`` inputs, Deflate, PackBits, tiled, planar and uncompressed files, sets the rule refuses and every file the device
+leaves to the host are read by the host reader as before; not with ``emit_probs``, whose device call takes decoded images).
 """
 import concurrent.futures as cf
 import json
@@ -57,11 +61,56 @@ def _resume_probe(p):
         return None
 
 
-def _read(p, resume=False):
+class _TiffFile:
+    """The bytes of a ``.tif`` file that the device may decode (config key ``tiff_read_on_device``) and the image they hold: what a
+    reader thread returns in place of the decoded array.  shape / dtype / nbytes: those of the array ``image_io.imread`` returns."""
+
+    def __init__(self, path, data, tshape):
+        self.path, self.data, self.tshape = path, data, tuple(int(v) for v in tshape)      # tshape: (H, W, samples per pixel, bits)
+        H, W, spp, bits = self.tshape
+        self.shape = (H, W) if spp == 1 else (H, W, spp)
+        self.dtype = np.dtype(np.uint8 if bits == 8 else np.uint16)
+        self.nbytes = H * W * spp * (bits // 8)
+
+
+class _TiffBatch:
+    """The files of one ``meta_segment_tiffs`` call where the other batches have their image array: ``datas`` (views of one buffer, in
+    order), the common ``tshape``, and ``status``, which the device call fills (a slice shares it)."""
+
+    def __init__(self, datas, tshape, status=None):
+        self.datas, self.tshape = list(datas), tshape
+        self.status = np.full(len(self.datas), -1, np.int32) if status is None else status
+        H, W, spp, bits = tshape
+        self.shape = (len(self.datas), H, W) + ((spp,) if spp > 1 else ())
+        self.dtype = np.dtype(np.uint8 if bits == 8 else np.uint16)
+
+    def __len__(self):
+        return len(self.datas)
+
+    def __getitem__(self, sl):
+        return _TiffBatch(self.datas[sl], self.tshape, self.status[sl])
+
+
+def _tiff_file(p):
+    """-> _TiffFile when the rule for a set counts the file (an LZW file ecseg_tiff_decode accepts), else None: the host reader's"""
+    try:
+        data = np.fromfile(p, np.uint8)
+        if not image_io.tiff_batch_counts(data):
+            return None
+        return _TiffFile(p, data, image_io.tiff_shape(data))
+    except Exception:
+        return None
+
+
+def _read(p, resume=False, device_tiffs=False):
     if resume:
         done = _resume_probe(p)
         if done is not None:
             return done
+    if device_tiffs and str(p).lower().endswith(('.tif', '.tiff')):
+        f = _tiff_file(p)
+        if f is not None:
+            return f
     img = image_io.imread(p)
     if img.dtype not in (np.uint8, np.uint16) or img.ndim not in (2, 3):
         raise ValueError('unsupported image array %s %s' % (img.dtype, img.shape))
@@ -231,6 +280,17 @@ def _segment_group(model, imgs, emit_probs=False, outs=None, files=None):
     """-> gray, post, n_ec, tie_risk, probs | None (arrays over the batch).  ``outs``: (gray, post) arrays to fill.
     ``files`` (the key ``files_on_device``; not with ``emit_probs``, whose device call is another): (dapi capacity, PNG capacity,
     the two buffers to build the files in | None) -> a sixth value, per image its (dapi file | None, PNG file | None)."""
+    if isinstance(imgs, _TiffBatch):                        # the files themselves: decoded by the device call (tiff_read_on_device)
+        h, o = model.handle, outs or (None, None)
+        if files is not None:
+            dcap, pcap, bufs = files
+            gray, post, nec, tie, dapi, png, st = h.meta_segment_tiffs_files(imgs.datas, imgs.tshape, *o, dapi_capacity=dcap, png_capacity=pcap,
+                                                                             file_bufs=bufs)
+            imgs.status[:] = st
+            return gray, post, nec, tie, None, list(zip(dapi, png))
+        gray, post, nec, tie, st = h.meta_segment_tiffs(imgs.datas, imgs.tshape, *o)
+        imgs.status[:] = st
+        return gray, post, nec, tie, None
     if files is not None and not emit_probs:
         dcap, pcap, bufs = files
         gray, post, nec, tie, dapi, png = model.handle.meta_segment_files(imgs, *(outs or (None, None)), dapi_capacity=dcap,
@@ -319,8 +379,12 @@ def _segment_isolating(model, imgs, log, emit_probs=False, outs=None, files=None
 
 
 def run(inpath, model, image_paths, rank=0, world=1, batch_images=8, io_threads=None, log=print, stats=None, resume=False,
-        emit_probs=False, pinned_mb=2048, pinned_min_images=None, files_on_device=False):
-    """Segment this rank's shard; returns records (one row per image of the WHOLE job after the all-gather)."""
+        emit_probs=False, pinned_mb=2048, pinned_min_images=None, files_on_device=False, tiff_read_on_device=False):
+    """Segment this rank's shard; returns records (one row per image of the WHOLE job after the all-gather).
+    ``tiff_read_on_device``: LZW ``.tif`` inputs are decoded by the device call of their batch (host path only with ``emit_probs``:
+    the key is then without effect)."""
+    if tiff_read_on_device and not all(hasattr(m.handle, 'meta_segment_tiffs') for m in (model if isinstance(model, (list, tuple)) else [model])):
+        raise ValueError('tiff_read_on_device needs the device TIFF reader (meta_segment_tiffs), which the handle in use does not have')
     if files_on_device and not all(hasattr(m.handle, 'meta_segment_files') for m in (model if isinstance(model, (list, tuple)) else [model])):
         raise ValueError('files_on_device needs the device file coders (meta_segment_files), which the handle in use does not have')
     start, stop, per = dist.shard_bounds(len(image_paths), rank, world)
@@ -344,14 +408,14 @@ def run(inpath, model, image_paths, rank=0, world=1, batch_images=8, io_threads=
         pool.start()
     try:
         return _run_threads(model, mine, start, per, rank, world, batch_images, io_threads, window, pending_writes, n_ec,
-                            status, log, stats, resume, tie, emit_probs, pool, files_on_device)
+                            status, log, stats, resume, tie, emit_probs, pool, files_on_device, tiff_read_on_device and not emit_probs)
     finally:
         pool.stop()
         sys.setswitchinterval(old_switch)
 
 
 def _run_threads(model, mine, start, per, rank, world, batch_images, io_threads, window, pending_writes, n_ec, status, log, stats,
-                 resume=False, tie=None, emit_probs=False, pool=None, files_on_device=False):
+                 resume=False, tie=None, emit_probs=False, pool=None, files_on_device=False, device_tiffs=False):
     # `model`: one model, or a list of models on the same GPU (config key device_workers): one device thread per model takes
     # batches from the common queue, so the host <-> device copies and the per-call synchronisation of one overlap the kernels of
     # the other (a narrow model spends a third of a call outside its kernels: EXPERIMENTS.md 6)
@@ -362,8 +426,10 @@ def _run_threads(model, mine, start, per, rank, world, batch_images, io_threads,
     # per-stage host timers (thread-seconds summed over the worker threads): where a slow `make metaseg` spends its CPU
     # (device_kernels: the library's stage timers; device_native: inside the library call, the rest of gpu_seconds is Python)
     # (device_dapi_encode / device_png_encode: the file coders of files_on_device, the first as it ran beside the U-Net)
+    # (device_tiff_decode: the decode kernels of tiff_read_on_device, as they ran in front of or under the U-Net)
     t_stage = {'read': 0.0, 'write': 0.0, 'pack': 0.0, 'device_kernels': 0.0, 'device_native': 0.0, 'device_dapi_encode': 0.0,
-               'device_png_encode': 0.0}
+               'device_png_encode': 0.0, 'device_tiff_decode': 0.0}
+    n_device_tiffs = [0]                                   # images whose samples the device decoded
 
     def timed(stage, fn):
         def wrapped(*a, **kw):
@@ -386,7 +452,7 @@ def _run_threads(model, mine, start, per, rank, world, batch_images, io_threads,
             nonlocal next_submit
             while next_submit < min(len(mine), upto):
                 log("Processing image: ", mine[next_submit])
-                reads[next_submit] = readers.submit(read_fn, mine[next_submit], resume)
+                reads[next_submit] = readers.submit(read_fn, mine[next_submit], resume, device_tiffs)
                 next_submit += 1
 
         write_futs = []
@@ -431,9 +497,28 @@ def _run_threads(model, mine, start, per, rank, world, batch_images, io_threads,
             kern = 1e-3 * sum(tm().values()) if tm is not None else 0.0
             ft = getattr(model.handle, 'file_timings', None) if files is not None and not bad else None
             fms = ft() if ft is not None else {'dapi': 0.0, 'png': 0.0}
+            rms = model.handle.read_timings()['decode'] if isinstance(imgs, _TiffBatch) and not bad else 0.0
+            if isinstance(imgs, _TiffBatch):
+                # a file the device left to the host (another layout after all) or found corrupt goes to the host reader, alone: its
+                # samples, or its message for an unreadable file
+                redo = [r[0] for r in done if imgs.status[r[0]] != 0]
+                done = [r for r in done if imgs.status[r[0]] == 0]
+                n_device_tiffs[0] += len(done)
+                own = None if files is None else (files[0], files[1], None)
+                for j in redo:
+                    try:
+                        one = read_fn(mine[group[j]])
+                    except Exception as e:
+                        log("Skipping %s: %s" % (mine[group[j]], e))
+                        status[group[j]] = 1
+                        continue
+                    ok1, bad1 = _segment_isolating(model, one[None], log, emit_probs, None, own)
+                    done += [(j,) + r[1:] for r in ok1]
+                    bad += [(j, e) for _, e in bad1]
             with t_lock:
                 t_gpu += dt
                 t_stage['device_kernels'] += kern
+                t_stage['device_tiff_decode'] += 1e-3 * rms
                 t_stage['device_dapi_encode'] += 1e-3 * fms['dapi']
                 t_stage['device_png_encode'] += 1e-3 * fms['png']
                 t_stage['device_native'] += getattr(model.handle, 'native_seconds', 0.0) - nat0
@@ -472,6 +557,7 @@ def _run_threads(model, mine, start, per, rank, world, batch_images, io_threads,
 
         def gpu_loop(m):
             prefetch = None if emit_probs else getattr(m.handle, 'prefetch_input', None)
+            prefetch_tiffs = getattr(m.handle, 'prefetch_tiffs', None) if device_tiffs else None
             ahead = []                                     # the batch taken from the queue while looking ahead
             while True:
                 g = ahead.pop() if ahead else batches.get()
@@ -487,7 +573,11 @@ def _run_threads(model, mine, start, per, rank, world, batch_images, io_threads,
                         ahead.append(batches.get_nowait())
                         nxt = ahead[0]
                         to_device = g[0] and g[1].dtype != np.bool_
-                        if nxt is not None and nxt[2] is not None and nxt[1].dtype != np.bool_ and to_device and not fatal:
+                        send = nxt is not None and nxt[2] is not None and nxt[1].dtype != np.bool_ and to_device and not fatal
+                        if send and isinstance(nxt[1], _TiffBatch):        # (named for a call on files: one on images withdraws them)
+                            if prefetch_tiffs is not None and isinstance(g[1], _TiffBatch):
+                                prefetch_tiffs(nxt[1].datas, nxt[1].tshape)
+                        elif send and not isinstance(g[1], _TiffBatch):
                             prefetch(nxt[1])
                         else:
                             prefetch(None)
@@ -519,6 +609,35 @@ def _run_threads(model, mine, start, per, rank, world, batch_images, io_threads,
             t_stage['pack'] += time.perf_counter() - t0
             return [k for k, _ in group], arr, buf
 
+        def pack_tiffs(group):
+            """the batches of a group of _TiffFile: one of files where the rule for a set sends them, else one of images read by the host"""
+            t0 = time.perf_counter()
+            files = [f for _, f in group]
+            if image_io.tiff_batch_goes_to_device([f.data for f in files])[0]:
+                total, most = sum(f.data.size for f in files), max(f.data.size for f in files)
+                buf = pool.get(total, max(len(group), batch_images) * most)
+                flat, datas, at = buf if buf is not None else np.empty(total, np.uint8), [], 0
+                for f in files:
+                    datas.append(flat[at:at + f.data.size])
+                    np.copyto(datas[-1], f.data)
+                    at += f.data.size
+                t_stage['pack'] += time.perf_counter() - t0
+                return [([k for k, _ in group], _TiffBatch(datas, files[0].tshape), buf)]
+            decoded = []                                   # (the set stays on the host: read again, decoded on the reader threads)
+
+            def host(f):
+                try:
+                    return read_fn(f.path)
+                except Exception as e:
+                    return e
+            for (k, f), img in zip(group, list(readers.map(host, files))):
+                if isinstance(img, Exception):
+                    log("Skipping %s: %s" % (f.path, img))
+                    status[k] = 1
+                else:
+                    decoded.append((k, img))
+            return [pack(decoded)] if decoded else []
+
         gpu_threads = [threading.Thread(target=gpu_loop, args=(m,), name='ecseg-gpu%d' % i) for i, m in enumerate(models)]
         for th in gpu_threads:
             th.start()
@@ -535,7 +654,7 @@ def _run_threads(model, mine, start, per, rank, world, batch_images, io_threads,
                 if isinstance(img, tuple):                 # ('done', ecDNA mask of the stored labels)
                     img = img[1]
                     log("Keeping existing outputs of ", mine[k])
-                kk = (img.shape, img.dtype.str)
+                kk = (img.shape, img.dtype.str, isinstance(img, _TiffFile))     # (the route is part of the key: files and images do not mix)
                 if not reserved and img.dtype != np.bool_:
                     # the shape of the run is known with its first image: order the page-locked buffers of the first batches now
                     # (three inputs in flight - being packed, queued, on the device - and three output pairs being written)
@@ -544,12 +663,14 @@ def _run_threads(model, mine, start, per, rank, world, batch_images, io_threads,
                     f_out = [batch_images * cap for cap in file_capacities(*img.shape[:2])] if files_on_device and not emit_probs else []
                     pool.reserve(([b_in, b_out, b_out] + f_out) * 3)
                 if group and (kk != key or len(group) >= batch_images):
-                    batches.put(pack(group))
+                    for b in (pack_tiffs(group) if key[2] else [pack(group)]):
+                        batches.put(b)
                     group = []
                 group.append((k, img))
                 key = kk
             if group:
-                batches.put(pack(group))
+                for b in (pack_tiffs(group) if key[2] else [pack(group)]):
+                    batches.put(b)
         finally:
             for _ in gpu_threads:
                 batches.put(None)
@@ -569,6 +690,7 @@ def _run_threads(model, mine, start, per, rank, world, batch_images, io_threads,
                 status[k] = 3
     if stats is not None:
         stats['gpu_seconds'] = t_gpu
+        stats['tiff_device_images'] = n_device_tiffs[0]
         stats['pinned_pool'] = {'hits': pool.hits, 'misses': pool.misses, 'free_MB': round(sum(b.size for b in pool.free) / 1e6, 1)}
         stats.update({'%s_thread_seconds' % k: v for k, v in t_stage.items()})
     rec = dist.make_records(start, len(mine), per, n_ec=n_ec, status=status, tie_risk=tie)
@@ -696,6 +818,10 @@ def main(argv=None):
     if not isinstance(files_on_device, bool):
         print("metaseg.files_on_device must be true or false (true: dapi TIFFs and label PNGs are encoded on the device). Exiting...")
         sys.exit(2)
+    tiff_read_on_device = var.get('tiff_read_on_device', False)
+    if not isinstance(tiff_read_on_device, bool):
+        print("metaseg.tiff_read_on_device must be true or false (true: LZW input TIFFs are decoded on the device, into the batch). Exiting...")
+        sys.exit(2)
     for sub in ('dapi', 'labels'):
         os.makedirs(os.path.join(inpath, sub), exist_ok=True)
 
@@ -726,13 +852,16 @@ def main(argv=None):
     if files_on_device and not all(hasattr(m.handle, 'meta_segment_files') for m in models):
         print("metaseg.files_on_device: true needs the device file coders (meta_segment_files), which the handle in use does not have. Exiting...")
         sys.exit(2)
+    if tiff_read_on_device and not all(hasattr(m.handle, 'meta_segment_tiffs') for m in models):
+        print("metaseg.tiff_read_on_device: true needs the device TIFF reader (meta_segment_tiffs), which the handle in use does not have. Exiting...")
+        sys.exit(2)
     image_paths = get_imgs(inpath)
     print("Reading from: ", inpath)
     t0 = time.perf_counter()
     stats = {}
     rec = run(inpath, models if workers > 1 else model, image_paths, rank, world, batch_images=int(var.get('batch_images', 8)),
               io_threads=var.get('io_threads'), stats=stats, resume=bool(var.get('resume', False)), emit_probs=emit_probs,
-              pinned_mb=int(var.get('pinned_mb', 2048)), files_on_device=files_on_device)
+              pinned_mb=int(var.get('pinned_mb', 2048)), files_on_device=files_on_device, tiff_read_on_device=tiff_read_on_device)
     failed = finish(inpath, image_paths, rec, rank, seconds=time.perf_counter() - t0, gpu_seconds=stats.get('gpu_seconds', 0.0))
     if native:
         dist.native_close(os.environ['ECSEG_RDZV'], rank)          # (the all-gather was the last thing every rank waited for)

@@ -53,6 +53,8 @@ extern "C" {
  * changed.) */
 /* (still 5 - additive: ecseg_tiff_decode_batch, ecseg_tiff_decode_batch_bytes, ecseg_tiff_decode_batch_routes and
  * ecseg_tiff_decode_batch_counts, many TIFF files decoded in one device call, a wave per strip of any file; nothing existing changed.) */
+/* (still 5 - additive: ecseg_meta_segment_tiffs, ecseg_meta_segment_tiffs_files, ecseg_prefetch_tiffs and ecseg_get_read_timings,
+ * `make metaseg`'s input TIFFs decoded on the device into the U-Net's batch; nothing existing changed.) */
 /* (still 5 - additive: ecseg_ccl_pass_debug, one connected-component labelling pass alone with everything it produced read back, for
  * the tests of the labelling kernels; nothing existing changed.) */
 /* (still 5 - additive: ecseg_meta_inference_stages_debug, a range of the six clean-up stages of meta_inference alone on given images, for
@@ -516,6 +518,34 @@ int ecseg_meta_segment_files(ecseg_ctx* h, const void* img, int n_img, int H, in
                              long long dapi_cap, long long* dapi_bytes, uint8_t* const* png_files, long long png_cap, long long* png_bytes,
                              uint8_t* gray_out, uint8_t* labels_post, int32_t* n_ec, int32_t* tie_risk);
 int ecseg_get_file_timings(ecseg_ctx* h, float* ms_out /* [2] */);
+/* ecseg_meta_segment with the input files themselves as its input: the packed file table of ecseg_tiff_decode_batch (files, files_bytes,
+ * file_ranges, n_files) and the batch's common shape.  The strips of every file decode on the device, a wave per strip, straight into
+ * the call's input buffer (raster i at i * H * W * C * bytes_per_sample); pre-processing, U-Net, clean-up and count run behind them as
+ * in ecseg_meta_segment, and the host decodes nothing.  status[i] is what ecseg_tiff_decode returns for file i alone (ECSEG_OK,
+ * ECSEG_E_INVALID, ECSEG_E_UNSUPPORTED); a file that decodes but whose H, W, samples per pixel or bits are not the call's has
+ * ECSEG_E_INVALID.  An image whose status is not ECSEG_OK is the all-zero image - its input slot is cleared on the device before the
+ * pre-processing, so that nothing of an earlier call reaches an output -, its n_ec is -1 and (_files) its two file lengths are 0;
+ * every other image has exactly what ecseg_meta_segment gives for the samples ecseg_tiff_read returns, byte for byte.  The call
+ * returns ECSEG_OK when it ran, whatever the status words say.  ECSEG_E_INVALID: the argument errors of ecseg_meta_segment and of
+ * ecseg_tiff_decode_batch (a null table, a range that overlaps the one in front or leaves the files), 65536 images or more, 2^31
+ * strips or rows or more.  ecseg_meta_segment_tiffs_files: the same with the two file tables, the capacity protocol and the timings
+ * of ecseg_meta_segment_files.  ecseg_get_read_timings: ms_out[0] the device time of the decode kernels that served the last such
+ * call (those of the decode-ahead, where it took its rasters from one). */
+int ecseg_meta_segment_tiffs(ecseg_ctx* h, const uint8_t* files, long long files_bytes, const int64_t* file_ranges /* [n][2] offset, n_bytes */,
+                             int n_files, int H, int W, int C, int bytes_per_sample, int32_t* status /* [n] */, uint8_t* gray_out,
+                             uint8_t* labels_post, int32_t* n_ec, int32_t* tie_risk);
+int ecseg_meta_segment_tiffs_files(ecseg_ctx* h, const uint8_t* files, long long files_bytes, const int64_t* file_ranges, int n_files, int H, int W,
+                                   int C, int bytes_per_sample, int32_t* status /* [n] */, uint8_t* const* dapi_files, long long dapi_cap,
+                                   long long* dapi_bytes, uint8_t* const* png_files, long long png_cap, long long* png_bytes, uint8_t* gray_out,
+                                   uint8_t* labels_post, int32_t* n_ec, int32_t* tie_risk);
+int ecseg_get_read_timings(ecseg_ctx* h, float* ms_out /* [1] */);
+/* The analogue of ecseg_prefetch_input: names the files of the ecseg_meta_segment_tiffs[_files] call AFTER the coming one, as that call
+ * will pass them (page-locked memory, unchanged until then).  The coming ecseg_meta_segment_tiffs[_files] call uploads them on the
+ * input stream and decodes them there into the spare input buffer, under its own kernels; the call after it recognises them by
+ * (pointer, bytes, ranges, n, shape) and skips upload and decode.  Any other call on the handle withdraws them, as does files == null
+ * or n_files == 0.  Results are those of calls without it. */
+int ecseg_prefetch_tiffs(ecseg_ctx* h, const uint8_t* files, long long files_bytes, const int64_t* file_ranges, int n_files, int H, int W, int C,
+                         int bytes_per_sample);
 
 /* ---- the min-cut nucleus splitter: a batch of grid max-flows (src/max_flow_binary_mask.py:59-116) ------------------------- */
 /* Replaces get_graph + max_flow + partition_min_cut (:59-116) for a BATCH of independent tasks; segment_min_cut's recursion

@@ -3,10 +3,14 @@
 ec_quantification.csv out ("time `make metaseg` on 256 generated files").  Prints one JSON line.
 
     python tools/time_cli.py [--n 256] [--base 64] [--batch 16] [--io-threads 32] [--keep DIR] [--files-on-device off|on|alternate]
+                             [--tiff-read-on-device off|on|alternate]
 
 ``--files-on-device on``: the run under the config key ``files_on_device: true`` (dapi TIFFs and label PNGs encoded on the device);
 ``alternate``: off, on, off, on in this one process over the same files, each pass reported under ``main_by_key`` with the device
 milliseconds per image of the two file coders, and ``verdict`` = the minimum on above the maximum off.
+``--tiff-read-on-device``: the same for the config key ``tiff_read_on_device`` (batches of LZW input files decoded on the device, into the
+U-Net's batch); ``alternate`` alternates this key with ``--files-on-device`` held at off or on, ``verdict`` is then this key's, and
+every pass reports ``tiff_device_images`` and the decode's device milliseconds per image (``device_ms_per_image['tiff_decode']``).
 """
 import argparse
 import json
@@ -47,8 +51,12 @@ def main():
                     help="random: seeded random weights (speckled labels: the slowest case for the label PNG coder); smooth: the fitted base-16 "
                          "stand-in for a trained model (tests/golden/smooth_b16_f16.npz: blobs, as real label maps)")
     ap.add_argument('--files-on-device', default='off', choices=('off', 'on', 'alternate'), help='config key files_on_device; alternate: off, on, off, on in one process')
+    ap.add_argument('--tiff-read-on-device', default='off', choices=('off', 'on', 'alternate'),
+                    help='config key tiff_read_on_device; alternate: off, on, off, on in one process (--files-on-device then off or on)')
     ap.add_argument('--warm-one', dest='warm_full', action='store_false', help='warm up with ONE image (rounds 1-4) instead of a full batch per handle')
     a = ap.parse_args()
+    if a.tiff_read_on_device == 'alternate' and a.files_on_device == 'alternate':
+        ap.error('one key alternates at a time')
     from PIL import Image
     import yaml
     from ecseg_amd import metaseg, synth, utils
@@ -101,23 +109,24 @@ def main():
         for mdl in [model] + extra:
             metaseg.run(warm, mdl, utils.get_imgs(warm), batch_images=a.batch, log=lambda *x: None, stats=stats, pinned_mb=a.pinned_mb,
                         pinned_min_images=0)    # (one batch would not start the page-locked pool by itself)
-        def one_pass(key):
+        def one_pass(key, tkey):
             for sub in ('dapi', 'labels'):               # (every pass creates its files: overwriting is slower)
                 shutil.rmtree(os.path.join(inp, sub), ignore_errors=True)
                 os.makedirs(os.path.join(inp, sub))
             st = {}
             c0, t0 = cgroup_cpu(), time.perf_counter()
             r = metaseg.run(inp, [model] + extra if extra else model, utils.get_imgs(inp), batch_images=a.batch, io_threads=a.io_threads,
-                            log=lambda *x: None, stats=st, pinned_mb=a.pinned_mb, files_on_device=key)
+                            log=lambda *x: None, stats=st, pinned_mb=a.pinned_mb, files_on_device=key, tiff_read_on_device=tkey)
             return r, time.perf_counter() - t0, c0, cgroup_cpu(), st
 
         by_key = []
-        for key in {'off': (False,), 'on': (True,), 'alternate': (False, True, False, True)}[a.files_on_device]:
-            if key:                                          # (the file coders' arenas and page-locked buffers: first use is not the rate)
+        values = {'off': (False,), 'on': (True,), 'alternate': (False, True, False, True)}
+        for key, tkey in [(k, t) for k in values[a.files_on_device] for t in values[a.tiff_read_on_device]]:
+            if key or tkey:                                  # (the file coders' and the decoder's arenas and page-locked buffers: first use is not the rate)
                 metaseg.run(warm, model, utils.get_imgs(warm), batch_images=a.batch, log=lambda *x: None, pinned_mb=a.pinned_mb,
-                            pinned_min_images=0, files_on_device=True)
-            rec, dt, cg0, cg1, stats = one_pass(key)
-            by_key.append({'files_on_device': key, 'seconds': round(dt, 3), 'images_per_s': round(a.n / dt, 2),
+                            pinned_min_images=0, files_on_device=key, tiff_read_on_device=tkey)
+            rec, dt, cg0, cg1, stats = one_pass(key, tkey)
+            by_key.append({'files_on_device': key, 'tiff_read_on_device': tkey, 'tiff_device_images': stats.get('tiff_device_images', 0), 'seconds': round(dt, 3), 'images_per_s': round(a.n / dt, 2),
                            'cpu_ms_per_image': None if not (cg0 and cg1) else round(1e3 * (cg1['usage_s'] - cg0['usage_s']) / a.n, 2),
                            'device_ms_per_image': {k[len('device_'):-len('_thread_seconds')]: round(1e3 * v / a.n, 4)
                                                    for k, v in stats.items() if k.startswith('device_') and k.endswith('_thread_seconds')}})
@@ -134,9 +143,10 @@ def main():
                             stats=ov_stats)
     dt_ov = time.perf_counter() - t0
     out_bytes = sum(os.path.getsize(os.path.join(dp, f)) for dp, _, fs in os.walk(inp) for f in fs) - in_bytes
-    offs = [r['images_per_s'] for r in by_key if not r['files_on_device']]
-    ons = [r['images_per_s'] for r in by_key if r['files_on_device']]
-    print(json.dumps({'files_on_device': a.files_on_device, 'main_by_key': by_key,
+    judged = 'tiff_read_on_device' if a.tiff_read_on_device == 'alternate' else 'files_on_device'
+    offs = [r['images_per_s'] for r in by_key if not r[judged]]
+    ons = [r['images_per_s'] for r in by_key if r[judged]]
+    print(json.dumps({'files_on_device': a.files_on_device, 'tiff_read_on_device': a.tiff_read_on_device, 'verdict_on': judged, 'main_by_key': by_key,
                       'verdict': None if not (offs and ons) else {'off_max': max(offs), 'on_min': min(ons), 'on_wins': min(ons) > max(offs)},
                       'what': '`make metaseg` loop: %d RGB %s TIFF files (1040x1392) -> dapi/*.tif, labels/*.png, labels/*.npy (int64), records'
                               % (a.n, 'LZW' if a.input_compression == 'tiff_lzw' else 'uncompressed'), 'images': a.n, 'unet_base': a.base, 'weights': a.weights, 'batch_images': a.batch, 'device_workers': a.workers, 'pinned_mb': a.pinned_mb,
