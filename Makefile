@@ -45,5 +45,14 @@ asan_tiff_decode_batch:
 	    ecseg_amd/csrc/host_codec.cpp tools/asan/tiff_decode_batch_fuzz.cpp -o /tmp/ecseg_tiff_decode_batch_fuzz
 	/tmp/ecseg_tiff_decode_batch_fuzz
 
+# and for the device gray PNG coder: the per-block pieces of its kernels (csrc/png_gray_tokens.h) and the host parts of its code
+# (csrc/png_gray_code.h) walked as the kernels walk them, against rle_scan and the host writer's file; tests/test_png_gray.py builds
+# and runs it
+.PHONY: asan_png_gray
+asan_png_gray:
+	g++ -std=c++17 -O1 -g -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=all \
+	    ecseg_amd/csrc/host_codec.cpp ecseg_amd/csrc/host_io.cpp tools/asan/png_gray_fuzz.cpp -lz -o /tmp/ecseg_png_gray_fuzz
+	/tmp/ecseg_png_gray_fuzz
+
 clean:
 	rm -rf __pycache__ ecseg_amd/csrc/*.o ecseg_amd/libecseg_*.so

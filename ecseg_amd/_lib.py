@@ -26,6 +26,7 @@ EXPORTS = [
     'ecseg_ccl_pass_debug', 'ecseg_meta_inference_stages_debug',
     'ecseg_tiff_decode_batch', 'ecseg_tiff_decode_batch_bytes', 'ecseg_tiff_decode_batch_routes', 'ecseg_tiff_decode_batch_counts',
     'ecseg_meta_segment_tiffs', 'ecseg_meta_segment_tiffs_files', 'ecseg_prefetch_tiffs', 'ecseg_get_read_timings',
+    'ecseg_png_channel_bound', 'ecseg_png_channel_encode', 'ecseg_overlay_files',
 ]
 
 
@@ -180,6 +181,10 @@ def load_library():
     lib.ecseg_meta_segment_files.argtypes = [vp, vp, i32, i32, i32, i32, i32, C.POINTER(vp), C.c_longlong, C.POINTER(C.c_longlong),
                                              C.POINTER(vp), C.c_longlong, C.POINTER(C.c_longlong), vp, vp, vp, vp]
     lib.ecseg_get_file_timings.argtypes = [vp, C.POINTER(C.c_float)]
+    lib.ecseg_png_channel_bound.argtypes = [i32, i32]; lib.ecseg_png_channel_bound.restype = C.c_longlong
+    lib.ecseg_png_channel_encode.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, C.POINTER(vp), C.c_longlong, C.POINTER(C.c_longlong)]
+    lib.ecseg_overlay_files.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, C.POINTER(vp), C.POINTER(vp), C.c_longlong,
+                                        C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
     lib.ecseg_meta_segment_tiffs.argtypes = [vp, vp, C.c_longlong, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp]
     lib.ecseg_meta_segment_tiffs_files.argtypes = [vp, vp, C.c_longlong, vp, i32, i32, i32, i32, i32, vp, C.POINTER(vp), C.c_longlong,
                                                    C.POINTER(C.c_longlong), C.POINTER(vp), C.c_longlong, C.POINTER(C.c_longlong), vp, vp, vp, vp]
@@ -434,6 +439,52 @@ class Handle:
         self.last_file_bytes = list(sizes)
         files = self._files_of(buf, self.last_file_bytes, max(cap, 1), True)
         return files[0] if single else files
+
+    def png_channel_encode(self, pixels, channel, invert=False, capacity=None):
+        """(n, H, W, C) or (H, W, C) uint8 pixels -> per image the bytes of the file ``image_io.write_png_channel(path, pixels_i, channel,
+        invert)`` writes, coded on the device (ecseg_png_channel_encode); a list for a batch.  ``capacity``: bytes of each file's buffer,
+        by default ecseg_png_channel_bound, which every file fits; a file that does not fit is None, and ``last_file_bytes`` holds
+        minus the size it needs (the lengths of the others)."""
+        a = np.ascontiguousarray(pixels, np.uint8)
+        single = a.ndim == 3
+        if single:
+            a = a[None]
+        if a.ndim != 4 or a.size == 0:
+            raise ValueError('png_channel_encode takes non-empty (n, H, W, C) or (H, W, C) uint8 pixels')
+        n, H, W, Cc = a.shape
+        cap = int(self.lib.ecseg_png_channel_bound(H, W)) if capacity is None else int(capacity)
+        buf, ptrs = self._file_slots(None, n, max(cap, 1))
+        sizes = (C.c_longlong * n)()
+        self._check(self.lib.ecseg_png_channel_encode(self.h, _ptr(a), n, H, W, Cc, int(channel), int(bool(invert)), ptrs, cap, sizes),
+                    'ecseg_png_channel_encode')
+        self.last_file_bytes = list(sizes)
+        files = self._files_of(buf, self.last_file_bytes, max(cap, 1), True)
+        return files[0] if single else files
+
+    def overlay_files(self, labels, img, sensitivity, hsr_size_threshold=20):
+        """``overlay(labels, u16_to_u8(img))`` and the red / green files of `make meta_overlay` from one upload (ecseg_overlay_files) ->
+        (records, red_files, green_files): ``img`` is (n, H, W, C >= 2) uint8 or uint16 (or one image), the files are the bytes
+        ``image_io.write_png_channel(path, I8_i, 0 / 1, invert=True)`` writes for the 8-bit image, which stays on the device.  Every
+        file fits its buffer (ecseg_png_channel_bound), so none is None."""
+        a, single = self._stack(labels)
+        r = np.ascontiguousarray(img)
+        if r.dtype not in (np.uint8, np.uint16):
+            raise TypeError('overlay_files takes uint8 or uint16 images, got %s' % r.dtype)
+        if r.ndim == 3:
+            r = r[None]
+        n, H, W = a.shape
+        if r.ndim != 4 or r.shape[:3] != (n, H, W) or r.shape[3] < 2:
+            raise ValueError('img must be (n, H, W, C>=2) matching labels')
+        out = np.zeros((n, 12), np.int64)
+        cap = int(self.lib.ecseg_png_channel_bound(H, W))
+        rbuf, rptr = self._file_slots(None, n, cap)
+        gbuf, gptr = self._file_slots(None, n, cap)
+        rn, gn = (C.c_longlong * max(n, 1))(), (C.c_longlong * max(n, 1))()
+        self._check(self.lib.ecseg_overlay_files(self.h, _ptr(a), _ptr(r), n, H, W, r.shape[3], r.dtype.itemsize, int(sensitivity),
+                                                 int(hsr_size_threshold), _ptr(out), rptr, gptr, cap, rn, gn), 'ecseg_overlay_files')
+        self.last_file_bytes = list(rn)[:n] + list(gn)[:n]
+        red, green = self._files_of(rbuf, list(rn)[:n], cap, True), self._files_of(gbuf, list(gn)[:n], cap, True)
+        return (out[0], red[0], green[0]) if single else (out, red, green)
 
     def meta_segment_files(self, imgs, gray_out=None, post_out=None, dapi_capacity=None, png_capacity=None, file_bufs=None):
         """``meta_segment`` plus, per image, the file images of ``dapi/<name>.tif`` (``write_tiff_gray8(gray, invert=True)``) and

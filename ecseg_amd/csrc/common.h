@@ -452,6 +452,46 @@ hipError_t run_png_count(const uint8_t* labels, size_t img_stride, int n, int H,
 hipError_t run_png_emit(const uint8_t* labels, size_t img_stride, int n, int H, int W, const PngEncodeBufs& b, uint32_t* z, size_t z_bytes,
                         hipStream_t s);
 
+// ---- launchers implemented in png_gray_kernels.hip (the gray PNG of ecseg_png_write_channel, host_io.cpp) ------------------------
+// A plane is one (image, channel) pair; plane p is channel (chans >> 8 (p % n_ch)) & 255 of image p / n_ch.  Its filtered stream has
+// n = H (W + 1) bytes (below 2^31) and is walked in spans of PGRAY_SPAN bytes, a wave each.  The counts of one plane: the 286
+// literal / length symbols as deflate_gray_sub's first scan takes them (the end of the block not counted), [286]: runs with a match.
+constexpr int PGRAY_NCOUNT = 287;
+constexpr uint32_t PGRAY_SPAN = 1024;
+struct GraySource { const uint8_t* px; size_t img_stride; uint32_t W, C, n, n_ch, chans, invert; };
+// One plane's code on the device (GrayPngCode, png_gray_code.h): lit[b] = code | length << 16; match[L] = bits | length << 24 for a
+// match of L = 3..258 bytes; head the first head_bits bits of the stream as little-endian dwords (1525 at most); z_off / z_words:
+// where in the stream buffer the plane's stream lies (in dwords) and the dwords it owns - none for a file that does not fit.
+struct GrayDevCode {
+    unsigned long long z_off;
+    uint32_t lit[256], match[260], head[64];
+    uint32_t head_bits, eob, eob_n, z_words;
+};
+static_assert(sizeof(GrayDevCode) % 8 == 0, "copied to LDS dword by dword, laid out as an array");
+// Device buffers of one encode of n_planes planes of n_img H x W x C images: px (the upload of ecseg_png_channel_encode; zero bytes
+// when the pixels are on the device already), the counts, per span the start of the run that reaches into it, its Adler terms, its
+// bits and its bit offset, per plane its code and the stream's length as the device found it, and the streams: z_stride bytes per
+// plane, sized as the host writer sizes its own buffer (2 n + 4096), the streams packed from its front by their exact sizes.
+struct GrayEncodeBufs { uint8_t* px; uint32_t* counts; uint32_t* span_carry; uint32_t* span_a; uint32_t* span_b; unsigned long long* span_bits;
+                        unsigned long long* span_off; GrayDevCode* codes; unsigned long long* z_bytes; uint32_t* z; uint32_t n_spans; size_t z_stride; };
+inline GrayEncodeBufs gray_encode_bufs(Carver& c, int H, int W, int C, int n_img, int n_planes, bool upload) {
+    const size_t n = (size_t)H * ((size_t)W + 1), np = (size_t)n_planes;
+    GrayEncodeBufs b;
+    b.n_spans = (uint32_t)((n + PGRAY_SPAN - 1) / PGRAY_SPAN);
+    b.z_stride = (2 * n + 4096 + 3) / 4 * 4;
+    const size_t spans = np * b.n_spans;
+    b.px = c.take<uint8_t>(upload ? (size_t)n_img * H * W * C : 0); b.counts = c.take<uint32_t>(np * PGRAY_NCOUNT);
+    b.span_carry = c.take<uint32_t>(spans); b.span_a = c.take<uint32_t>(spans); b.span_b = c.take<uint32_t>(spans);
+    b.span_bits = c.take<unsigned long long>(spans); b.span_off = c.take<unsigned long long>(spans);
+    b.codes = c.take<GrayDevCode>(np); b.z_bytes = c.take<unsigned long long>(np); b.z = c.take<uint32_t>(np * (b.z_stride / 4));
+    return b;
+}
+// run_pgray_count clears and fills b.counts, b.span_carry, b.span_a and b.span_b; run_pgray_emit, with b.codes in place, clears the
+// first z_bytes bytes of b.z (a multiple of 4) and writes every stream that has dwords, and b.z_bytes.  n_planes below 65536 (grid
+// dimension y is the plane).
+hipError_t run_pgray_count(const GraySource& src, int n_planes, const GrayEncodeBufs& b, hipStream_t s);
+hipError_t run_pgray_emit(const GraySource& src, int n_planes, const GrayEncodeBufs& b, size_t z_bytes, hipStream_t s);
+
 // ---- launcher implemented in mincut_kernels.hip (src/max_flow_binary_mask.py:59-116) -----------------------------------------
 // n_tasks tasks of ecseg_min_cut, one workgroup each.  desc: (n_tasks, 8) int32 as the entry point takes them, validated by the
 // caller; soff: per task the byte offset of its mincut_scratch_bytes(h, w) bytes in `scratch` (16-byte aligned), or < 0 for a

@@ -259,6 +259,11 @@ int tiff_collect(ecseg_ctx* h, const char* who, int n_files, int H, int W, int s
 int png_encode_files(ecseg_ctx* h, const char* who, const uint8_t* d_labels, int n, int H, int W, const PngEncodeBufs& b,
                      uint8_t* const* files, long long file_cap, long long* file_bytes, float* ms);
 
+// The gray PNGs (ecseg_png_write_channel's files) of n_planes planes of images that lie on the device, on the main stream: count, code
+// build and capacity verdict on the host, emit of the files that fit, frame.  files / file_bytes: per plane.  *ms: as above.
+int png_gray_encode(ecseg_ctx* h, const char* who, const GraySource& src, int n_planes, int H, int W, const GrayEncodeBufs& b,
+                    uint8_t* const* files, long long file_cap, long long* file_bytes, float* ms);
+
 // The files of a batch as ecseg_tiff_decode judges each alone: info[i] and status[i] (with_strips: the file is to be decoded, not only
 // measured), and the rows of the layout for the files that are ECSEG_OK (dst_offsets may be null: the rasters back to back, 16-bit
 // ones on even offsets).  Empty string, or which argument is wrong.

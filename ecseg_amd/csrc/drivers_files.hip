@@ -1,10 +1,12 @@
 // Files coded on the device: the TIFF encoder (tiff_kernels.hip; the host writer is tiff_write_u8, host_io.cpp), the TIFF decoder for
-// one file and for a batch (tiff_decode_kernels.hip; the host reader is ecseg_tiff_read) and the label PNG encoder (png_kernels.hip;
-// the host writer is ecseg_png_write_labels), with the two tails that ecseg_meta_segment_files and ecseg_fish_render_tiff share.
+// one file and for a batch (tiff_decode_kernels.hip; the host reader is ecseg_tiff_read), the label PNG encoder (png_kernels.hip;
+// the host writer is ecseg_png_write_labels) and the gray PNG encoder (png_gray_kernels.hip; the host writer is
+// ecseg_png_write_channel), with the tails that ecseg_meta_segment_files and ecseg_fish_render_tiff share.
 #include <cstring>
 
 #include "driver_util.h"
 
+#include "png_gray_code.h"
 #include "png_label_code.h"
 #include "tiff_parse.h"
 
@@ -98,6 +100,58 @@ int ecseg::png_encode_files(ecseg_ctx* h, const char* who, const uint8_t* d_labe
             return fail(h, ECSEG_E_HIP, std::string(who) + ": image " + std::to_string(i) + ": the device wrote a stream of " + std::to_string(dz[i]) +
                                             " bytes where the counts give " + std::to_string(zb[i]));
         if (file_bytes[i] > 0) label_png_frame(files[i], zb[i], H, W);
+    }
+    *ms = stage_elapsed(h->ev_files[2], h->ev_files[3]) + stage_elapsed(h->ev_files[4], h->ev_files[5]);
+    return ECSEG_OK;
+}
+
+int ecseg::png_gray_encode(ecseg_ctx* h, const char* who, const GraySource& src, int n_planes, int H, int W, const GrayEncodeBufs& b,
+                           uint8_t* const* files, long long file_cap, long long* file_bytes, float* ms) {
+    hipStream_t s = h->stream;
+    const size_t np = (size_t)n_planes;
+    HIP_TRY(h, hipEventRecord(h->ev_files[2], s));
+    HIP_TRY(h, run_pgray_count(src, n_planes, b, s));
+    HIP_TRY(h, hipEventRecord(h->ev_files[3], s));
+    std::vector<uint32_t> counts(np * PGRAY_NCOUNT);
+    HIP_TRY(h, hipMemcpyAsync(counts.data(), b.counts, counts.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    // the code of every plane, with it the exact size of its stream and of its file, and so the verdict before a bit is written
+    std::vector<GrayDevCode> codes(np);
+    std::vector<size_t> zb(np);
+    size_t words = 0;
+    for (size_t i = 0; i < np; ++i) {
+        const uint32_t* c = counts.data() + i * PGRAY_NCOUNT;
+        GrayPngCode k;
+        gray_png_code(c, c[286] != 0, &k);
+        zb[i] = gray_png_stream_bytes(k, c);
+        if (zb[i] > b.z_stride) return fail(h, ECSEG_E_HIP, std::string(who) + ": plane " + std::to_string(i) + ": the counts give a stream of " +
+                                                                 std::to_string(zb[i]) + " bytes, above the bound of any stream");
+        const size_t total = label_png_file_bytes(zb[i]);
+        file_bytes[i] = total > (unsigned long long)file_cap ? -(long long)total : (long long)total;
+        GrayDevCode& d = codes[i];
+        std::memset(&d, 0, sizeof d);
+        for (int q = 0; q < 256; ++q) d.lit[q] = (uint32_t)k.lcode[q] | ((uint32_t)k.llen[q] << 16);
+        for (int L = 3; L <= 258; ++L) d.match[L] = k.mbits[L] | ((uint32_t)k.mn[L] << 24);
+        std::memcpy(d.head, k.head, sizeof d.head);
+        d.head_bits = k.head_bits; d.eob = k.lcode[256]; d.eob_n = k.llen[256];
+        d.z_off = words; d.z_words = file_bytes[i] > 0 ? (uint32_t)((zb[i] + 3) / 4) : 0u;
+        words += d.z_words;
+    }
+    HIP_TRY(h, hipMemcpyAsync(b.codes, codes.data(), codes.size() * sizeof(GrayDevCode), hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipEventRecord(h->ev_files[4], s));
+    HIP_TRY(h, run_pgray_emit(src, n_planes, b, words * 4, s));
+    HIP_TRY(h, hipEventRecord(h->ev_files[5], s));
+    std::vector<unsigned long long> dz(np);
+    HIP_TRY(h, hipMemcpyAsync(dz.data(), b.z_bytes, dz.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    for (size_t i = 0; i < np; ++i)
+        if (file_bytes[i] > 0) HIP_TRY(h, hipMemcpyAsync(files[i] + LABEL_PNG_Z_OFFSET, b.z + codes[i].z_off, zb[i], hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    for (size_t i = 0; i < np; ++i) {
+        if (file_bytes[i] <= 0) continue;
+        if (dz[i] != zb[i])
+            return fail(h, ECSEG_E_HIP, std::string(who) + ": plane " + std::to_string(i) + ": the device wrote a stream of " + std::to_string(dz[i]) +
+                                            " bytes where the counts give " + std::to_string(zb[i]));
+        gray_png_frame(files[i], zb[i], H, W);
     }
     *ms = stage_elapsed(h->ev_files[2], h->ev_files[3]) + stage_elapsed(h->ev_files[4], h->ev_files[5]);
     return ECSEG_OK;
@@ -355,6 +409,32 @@ int ecseg_png_labels_encode(ecseg_ctx* h, const uint8_t* labels, int n_img, int 
     if ((rc = lay_out(h, h->call_arena, [&](Carver& c) { b = png_encode_bufs(c, H, W, n_img, true); }))) return rc;
     HIP_TRY(h, hipMemcpyAsync(b.labels, labels, (size_t)n_img * H * W, hipMemcpyHostToDevice, h->stream));
     return png_encode_files(h, "png_labels_encode", b.labels, n_img, H, W, b, files, file_cap, file_bytes, &h->stage_ms[ECSEG_T_COUNT]);
+}
+
+// ---- gray PNG files (one channel of an interleaved image) encoded on the device ---------------------------------------------------
+long long ecseg_png_channel_bound(int H, int W) {
+    if (H < 1 || W < 1) return -1;
+    return (long long)label_png_file_bytes(gray_png_stream_bound((size_t)H * ((size_t)W + 1)));
+}
+
+int ecseg_png_channel_encode(ecseg_ctx* h, const uint8_t* pixels, int n_img, int H, int W, int C, int channel, int invert, uint8_t* const* files,
+                             long long file_cap, long long* file_bytes) {
+    DRIVER_OPEN(h);
+    if (n_img < 0 || n_img >= 65536 || H <= 0 || W <= 0 || C <= 0 || C > 256 || channel < 0 || channel >= C || file_cap < 1 ||
+        ((size_t)W + 1) * (size_t)H >= 0x7fffffffull || (n_img > 0 && (!pixels || !files || !file_bytes)))
+        return fail(h, ECSEG_E_INVALID, "png_channel_encode: bad arguments");
+    for (int i = 0; i < n_img; ++i) if (!files[i]) return fail(h, ECSEG_E_INVALID, "png_channel_encode: a null file buffer");
+    clear_timings(h);
+    if (n_img == 0) return ECSEG_OK;
+    for (int i = 0; i < n_img; ++i) file_bytes[i] = 0;
+    USE_DEVICE(h);
+    int rc;
+    GrayEncodeBufs b{};
+    if ((rc = lay_out(h, h->call_arena, [&](Carver& c) { b = gray_encode_bufs(c, H, W, C, n_img, n_img, true); }))) return rc;
+    const size_t img_bytes = (size_t)H * W * C;
+    HIP_TRY(h, hipMemcpyAsync(b.px, pixels, (size_t)n_img * img_bytes, hipMemcpyHostToDevice, h->stream));
+    const GraySource src{b.px, img_bytes, (uint32_t)W, (uint32_t)C, (uint32_t)(((size_t)W + 1) * (size_t)H), 1u, (uint32_t)channel, invert ? 1u : 0u};
+    return png_gray_encode(h, "png_channel_encode", src, n_img, H, W, b, files, file_cap, file_bytes, &h->stage_ms[ECSEG_T_COUNT]);
 }
 
 }  // extern "C"

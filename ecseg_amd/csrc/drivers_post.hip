@@ -246,4 +246,57 @@ int ecseg_overlay(ecseg_ctx* h, const uint8_t* labels, const uint8_t* rgb, int n
     return ECSEG_OK;
 }
 
+// ecseg_overlay's rows and the red / green PNGs of meta_overlay from one upload: the 8-bit image (u16_to_u8 of 16-bit samples, on the
+// device) is counted and then coded channel by channel where it lies (png_gray_encode, drivers_files.hip) and never comes back.
+int ecseg_overlay_files(ecseg_ctx* h, const uint8_t* labels, const void* img, int n_img, int H, int W, int C, int bytes_per_sample, int sens,
+                        int hsr_thr, int64_t* out, uint8_t* const* red_files, uint8_t* const* green_files, long long file_cap, long long* red_bytes,
+                        long long* green_bytes) {
+    DRIVER_OPEN(h);
+    if (n_img < 0 || n_img >= 65536 || H <= 0 || W <= 0 || C < 2 || C > 256 || (bytes_per_sample != 1 && bytes_per_sample != 2) || file_cap < 1 ||
+        ((size_t)W + 1) * (size_t)H >= 0x7fffffffull ||
+        (n_img > 0 && (!labels || !img || !out || !red_files || !green_files || !red_bytes || !green_bytes)))
+        return fail(h, ECSEG_E_INVALID, "overlay_files: bad arguments");
+    for (int i = 0; i < n_img; ++i) if (!red_files[i] || !green_files[i]) return fail(h, ECSEG_E_INVALID, "overlay_files: a null file buffer");
+    clear_timings(h);
+    h->file_ms[0] = h->file_ms[1] = 0.f;
+    if (n_img == 0) return ECSEG_OK;
+    for (int i = 0; i < n_img; ++i) red_bytes[i] = green_bytes[i] = 0;
+    if (!px_below_2_31(H, W)) return fail(h, ECSEG_E_INVALID, "image too large");
+    USE_DEVICE(h);
+    const size_t px = (size_t)H * W, bps = (size_t)bytes_per_sample;
+    const int chunk = std::min(h->post_chunk, n_img);
+    int rc;
+    if ((rc = ensure_post(h, chunk, px))) return rc;
+    if ((rc = h->d_gray.ensure(h, px * chunk))) return rc;
+    if ((rc = h->d_aux8.ensure(h, px * C * bps * chunk))) return rc;
+    if ((rc = h->d_i64.ensure(h, (size_t)chunk * 12))) return rc;
+    uint8_t* i8 = nullptr;
+    GrayEncodeBufs b{};
+    if ((rc = lay_out(h, h->call_arena, [&](Carver& c) {
+            i8 = c.take<uint8_t>(bps == 2 ? px * C * chunk : 0);
+            b = gray_encode_bufs(c, H, W, C, chunk, 2 * chunk, false);
+        }))) return rc;
+    if (bps == 1) i8 = h->d_aux8.p;
+    hipStream_t s = h->stream;
+    std::vector<uint8_t*> files((size_t)2 * chunk);
+    std::vector<long long> bytes((size_t)2 * chunk);
+    for (int i0 = 0; i0 < n_img; i0 += chunk) {
+        const int ni = std::min(chunk, n_img - i0);
+        HIP_TRY(h, hipMemcpyAsync(h->d_gray, labels + (size_t)i0 * px, px * ni, hipMemcpyHostToDevice, s));
+        HIP_TRY(h, hipMemcpyAsync(h->d_aux8, static_cast<const uint8_t*>(img) + (size_t)i0 * px * C * bps, px * C * bps * ni, hipMemcpyHostToDevice, s));
+        if (bps == 2) HIP_TRY(h, launch_u16_to_u8(reinterpret_cast<const uint16_t*>(h->d_aux8.p), i8, px * C * ni, s));
+        TIMED(h, s, 0, 1, HIP_TRY(h, run_overlay(h->ws, h->d_gray, i8, ni, H, W, C, sens, hsr_thr, h->d_i64, s)));
+        HIP_TRY(h, hipMemcpyAsync(out + (size_t)i0 * 12, h->d_i64, (size_t)ni * 12 * 8, hipMemcpyDeviceToHost, s));
+        for (int i = 0; i < ni; ++i) { files[2 * (size_t)i] = red_files[i0 + i]; files[2 * (size_t)i + 1] = green_files[i0 + i]; }
+        const GraySource src{i8, px * C, (uint32_t)W, (uint32_t)C, (uint32_t)(((size_t)W + 1) * (size_t)H), 2u, 0u | (1u << 8), 1u};
+        float ms = 0.f;
+        if ((rc = png_gray_encode(h, "overlay_files", src, 2 * ni, H, W, b, files.data(), file_cap, bytes.data(), &ms))) return rc;   // (waits for the stream)
+        for (int i = 0; i < ni; ++i) { red_bytes[i0 + i] = bytes[2 * (size_t)i]; green_bytes[i0 + i] = bytes[2 * (size_t)i + 1]; }
+        timed_add(h, 0, 1);
+        h->file_ms[1] += ms;
+        h->stage_ms[ECSEG_T_COUNT] += ms;
+    }
+    return ECSEG_OK;
+}
+
 }  // extern "C"

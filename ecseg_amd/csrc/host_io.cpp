@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "../../include/ecseg_hip.h"
+#include "png_gray_code.h"
 #include "png_label_code.h"
 #include "tiff_frame.h"
 #include "tiff_parse.h"
@@ -227,28 +228,6 @@ void deflate_labels(const uint8_t* labels, int H, int W, const uint8_t pal[4][4]
 // a byte repeated four times or more becomes one literal + distance-1 matches, everything goes out as ONE dynamic-Huffman block
 // built from the image's own symbol counts (two scans of the filtered bytes: count, then emit).  zlib's deflate_rle takes 16 ms
 // for a 1040 x 1392 noisy FISH channel, its level-1 deflate 43 ms; any inflate reproduces the rows exactly.
-template <typename Emit>
-inline void rle_scan(const uint8_t* f, size_t n, Emit&& emit) {      // emit(literal) / emit(-length) for a distance-1 match
-    size_t i = 0;
-    while (i < n) {
-        const uint8_t b = f[i];
-        emit((int)b);
-        ++i;
-        if (i + 2 < n && f[i] == b && f[i + 1] == b && f[i + 2] == b) {      // a run worth a match (>= 3 more of the same byte)
-            size_t j = i + 3;
-            while (j < n && f[j] == b) ++j;
-            size_t r = j - i;
-            while (r >= 3) {
-                size_t L = r > 258 ? 258 : r;
-                if (r - L > 0 && r - L < 3) L = r - 3;                       // never leave a tail shorter than a match
-                emit(-(int)L);
-                r -= L;
-            }
-            i = j - r;                                                      // (r == 0 here by construction)
-        }
-    }
-}
-
 void deflate_gray_sub(const uint8_t* px, int H, int W, size_t pixel_stride, size_t row_stride, bool invert, std::vector<uint8_t>* z) {
     const size_t line = (size_t)W + 1, n = (size_t)H * line;
     std::unique_ptr<uint8_t[]> f(new uint8_t[n + 8]);
@@ -266,32 +245,15 @@ void deflate_gray_sub(const uint8_t* px, int H, int W, size_t pixel_stride, size
         if (t >= 0) ++freq[t];
         else { ++freq[length_code(-t).sym]; any_match = true; }
     });
-    freq[256] = 1;
-    uint8_t llen[286];
-    uint16_t lcode[286];
-    huffman_lengths(freq, 286, llen);
-    canonical_codes(llen, 286, lcode);
-    uint8_t cl_len[19];
-    uint16_t cl_code[19];
-    for (int i = 0; i < 19; ++i) cl_len[i] = i < 13 ? 4 : 5;                 // a fixed complete code for the code lengths, sent one by one
-    canonical_codes(cl_len, 19, cl_code);
+    GrayPngCode code;                                                       // (png_gray_code.h: the device coder builds the same)
+    gray_png_code(freq, any_match, &code);
+    const uint16_t* lcode = code.lcode; const uint8_t* llen = code.llen;
+    const uint32_t* mbits = code.mbits; const uint8_t* mn = code.mn;
     std::unique_ptr<uint8_t[]> buf(new uint8_t[n * 2 + 4096]);             // <= 15 bits per literal
-    buf[0] = 0x78; buf[1] = 0x01;
-    BitWriter bw(buf.get() + 2);
-    bw.put(1, 1); bw.put(2, 2);                                             // BFINAL, BTYPE = dynamic
-    bw.put(286 - 257, 5); bw.put(1 - 1, 5); bw.put(19 - 4, 4);              // 286 literal / length codes, ONE distance code
-    static const int order[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
-    for (int i = 0; i < 19; ++i) bw.put(cl_len[order[i]], 3);
-    for (int i = 0; i < 286; ++i) bw.put(cl_code[llen[i]], cl_len[llen[i]]);
-    const int d0 = any_match ? 1 : 0;                                       // distance code 0 (distance 1): a 1-bit code, bit 0
-    bw.put(cl_code[d0], cl_len[d0]);
-    // match bit strings by length: length code + extra bits + the distance code "0"
-    uint32_t mbits[259]; uint8_t mn[259];
-    for (int L = 3; L <= 258; ++L) {
-        const LenCode lc = length_code(L);
-        mbits[L] = (uint32_t)lcode[lc.sym] | ((uint32_t)lc.extra << llen[lc.sym]);
-        mn[L] = (uint8_t)(llen[lc.sym] + lc.extra_bits + 1);
-    }
+    std::memcpy(buf.get(), code.head, (code.head_bits + 7) / 8);
+    BitWriter bw(buf.get() + code.head_bits / 8);                           // goes on behind the block header, inside its last byte
+    bw.n = (int)(code.head_bits & 7);
+    bw.acc = bw.n ? code.head[code.head_bits / 8] : 0;
     rle_scan(f.get(), n, [&](int t) {
         if (t >= 0) bw.put(lcode[t], llen[t]);
         else bw.put(mbits[-t], mn[-t]);
@@ -530,8 +492,8 @@ void ecseg::tiff_frame(int H, int W, int spp, int rps, const uint32_t* offs, con
     tail->insert(tail->end(), ifd.begin(), ifd.end());
 }
 
-// The file around a label PNG's stream (png_label_code.h): what png_write_stream puts around it, in memory.
-void ecseg::label_png_frame(uint8_t* file, size_t z, int H, int W) {
+// The file around a PNG stream that lies at file + LABEL_PNG_Z_OFFSET already: what png_write_stream puts around it, in memory.
+static void png_frame(uint8_t* file, size_t z, int H, int W, int color_type) {
     static const uint8_t sig[8] = {0x89, 'P', 'N', 'G', '\r', '\n', 0x1a, '\n'};
     auto chunk = [](uint8_t* p, const char tag[4], size_t n) {     // the data lies at p + 8 already; returns the chunk's end
         put_be32(p, (uint32_t)n);
@@ -544,11 +506,13 @@ void ecseg::label_png_frame(uint8_t* file, size_t z, int H, int W) {
     std::memcpy(file, sig, 8);
     uint8_t* ihdr = file + 16;
     put_be32(ihdr, (uint32_t)W); put_be32(ihdr + 4, (uint32_t)H);
-    ihdr[8] = 8; ihdr[9] = 6; ihdr[10] = 0; ihdr[11] = 0; ihdr[12] = 0;
+    ihdr[8] = 8; ihdr[9] = (uint8_t)color_type; ihdr[10] = 0; ihdr[11] = 0; ihdr[12] = 0;
     uint8_t* p = chunk(file + 8, "IHDR", 13);
     p = chunk(p, "IDAT", z);
     chunk(p, "IEND", 0);
 }
+void ecseg::label_png_frame(uint8_t* file, size_t z, int H, int W) { png_frame(file, z, H, W, 6); }     // (png_label_code.h)
+void ecseg::gray_png_frame(uint8_t* file, size_t z, int H, int W) { png_frame(file, z, H, W, 0); }      // (png_gray_code.h)
 
 extern "C" {
 

@@ -20,13 +20,13 @@
 // a run of k pixels whose first byte is byte p of its n-byte scan line, with byte sum S and U = p1 + 2 p2 + 3 p3, adds
 // k S to a and k (n - p) S - 2 k (k - 1) S - k U to b.
 #include "common.h"
+#include "png_device.h"
 #include "png_label_code.h"
 
 namespace ecseg {
 
 namespace {
 
-constexpr unsigned long long ADLER_M = 65521;
 constexpr int PNG_ROWS = 4;                                  // scan lines (waves) per workgroup
 
 constexpr uint32_t pal_s(int c) { return LABEL_PNG_PALETTE[c][0] + LABEL_PNG_PALETTE[c][1] + LABEL_PNG_PALETTE[c][2] + LABEL_PNG_PALETTE[c][3]; }
@@ -54,12 +54,6 @@ __device__ __forceinline__ RunEnd run_end(const uint8_t* __restrict__ row, uint3
     r.k = x - r.xs + 1;
     if (starts) carry = x0 + 63u - (uint32_t)__clzll((long long)starts);
     return r;
-}
-
-__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-    return v;
 }
 
 __global__ __launch_bounds__(64 * PNG_ROWS) void png_count_kernel(const uint8_t* __restrict__ labels, size_t img_stride, int H, uint32_t W,
@@ -145,18 +139,6 @@ __global__ __launch_bounds__(64 * PNG_ROWS) void png_rowbits_kernel(const uint8_
     }
     bits = wave_sum(bits);
     if (lane == 0) row_bits[img * H + y] = bits + code.filt_n;
-}
-
-// ORs the low n (<= 64) bits of `bits` into the stream at bit `pos`; dwords at or behind `words` are left alone
-__device__ __forceinline__ void put_bits(uint32_t* __restrict__ z, uint32_t words, unsigned long long pos, unsigned long long bits, uint32_t n) {
-    if (n == 0) return;
-    const unsigned long long w = pos >> 5;
-    const uint32_t sh = (uint32_t)pos & 31u;
-    const unsigned long long lo = bits << sh;
-    const uint32_t hi = sh ? (uint32_t)(bits >> (64 - sh)) : 0u;
-    if ((uint32_t)lo && w < words) atomicOr(z + w, (uint32_t)lo);
-    if ((uint32_t)(lo >> 32) && w + 1 < words) atomicOr(z + w + 1, (uint32_t)(lo >> 32));
-    if (hi && w + 2 < words) atomicOr(z + w + 2, hi);
 }
 
 __global__ __launch_bounds__(256) void png_scan_kernel(const unsigned long long* __restrict__ row_bits, const uint32_t* __restrict__ row_a,

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """``make meta_overlay``: drop-in for the reference's ``src/meta_overlay.py`` (config section, checks, exit codes,
-``red/`` ``green/`` images and ``fish_quantification.csv``), with the nine counts computed on MI355X."""
+``red/`` ``green/`` images and ``fish_quantification.csv``), with the nine counts computed on MI355X.  One key of its own:
+``files_on_device`` (false; true: the red / green PNGs are encoded on the device too, one call per group, the same bytes)."""
 import os
 import sys
 
@@ -34,12 +35,19 @@ def main(argv=None):
         if (sensitivity < 0) | (sensitivity > 255):
             print("color_sensitivity can only be between 0 and 255. Please update the config.yaml file accordingly.")
             sys.exit(2)
+    files_on_device = var.get('files_on_device', False)
+    if not isinstance(files_on_device, bool):
+        print("meta_overlay.files_on_device must be true or false (true: the red and green PNGs are encoded on the device). Exiting...")
+        sys.exit(2)
     for sub in ('red', 'green'):
         os.makedirs(os.path.join(inpath, sub), exist_ok=True)
 
     handle = image_tools.default_handle()
+    if files_on_device and not hasattr(handle, 'overlay_files'):
+        print("meta_overlay.files_on_device: true needs the device PNG coder (overlay_files), which the handle in use does not have. Exiting...")
+        sys.exit(2)
     rows = run(inpath, handle, get_imgs(inpath), int(sensitivity), batch_images=int(var.get('batch_images', 8)),
-               io_threads=var.get('io_threads'))
+               io_threads=var.get('io_threads'), files_on_device=files_on_device)
     with open(os.path.join(inpath, 'fish_quantification.csv'), 'w') as f:
         f.write(csvio.csv_text(csvio.OVERLAY_COLUMNS, rows))
 
@@ -59,10 +67,21 @@ def _write_channels(p, I8):
     image_io.write_png_channel(os.path.join(path_split[0], 'green', path_split[1] + '.png'), I8, 1, invert=True)
 
 
-def run(inpath, handle, image_paths, sensitivity, batch_images=8, io_threads=None, log=print, stats=None):
+def _write_channel_files(p, red, green):
+    """The same two files from file images the device encoded (``files_on_device``)."""
+    path_split = os.path.split(p)
+    image_io.write_file_image(os.path.join(path_split[0], 'red', path_split[1] + '.png'), red)
+    image_io.write_file_image(os.path.join(path_split[0], 'green', path_split[1] + '.png'), green)
+
+
+def run(inpath, handle, image_paths, sensitivity, batch_images=8, io_threads=None, log=print, stats=None, files_on_device=False):
     """The per-image loop of src/meta_overlay.py:56-95 with the decoding (TIFF + labels/*.npy) and the red / green PNG
     encoders on worker threads and the nine counts of consecutive same-shaped images computed in one device call.  Rows
-    come back in the order of ``image_paths``."""
+    come back in the order of ``image_paths``.  ``files_on_device`` (the config key): a group's stacked images (uint8 or uint16) go
+    up once, ``handle.overlay_files`` returns the rows and the red / green file images, and the writer threads only write them -
+    the same bytes; a group of another dtype takes the host path."""
+    if files_on_device and not hasattr(handle, 'overlay_files'):
+        raise ValueError('files_on_device needs the device PNG coder (overlay_files), which the handle in use does not have')
     import concurrent.futures as cf
     import threading
     import time
@@ -80,7 +99,7 @@ def run(inpath, handle, image_paths, sensitivity, batch_images=8, io_threads=Non
                     t_stage[stage] += dt
         return wrapped
 
-    load_fn, write_fn = timed('read', _load), timed('write', _write_channels)
+    load_fn, write_fn, write_files_fn = timed('read', _load), timed('write', _write_channels), timed('write', _write_channel_files)
     io_threads = io_threads or default_io_threads(1)
     window = max(2 * batch_images, io_threads)
     rows = [None] * len(image_paths)
@@ -95,12 +114,17 @@ def run(inpath, handle, image_paths, sensitivity, batch_images=8, io_threads=Non
             rgb = np.stack([g[1] for g in group])
             seg = np.stack([g[2] for g in group])
             t1 = time.perf_counter()
-            I8 = image_tools.u16_to_u8(rgb, handle=handle)   # src/image_tools.py:142
-            rec = handle.overlay(seg, np.ascontiguousarray(I8), sensitivity, HSR_SIZE_THRESHOLD)
+            if files_on_device and rgb.dtype in (np.uint8, np.uint16):
+                rec, red, green = handle.overlay_files(seg, rgb, sensitivity, HSR_SIZE_THRESHOLD)
+                writer, payload = write_files_fn, list(zip(red, green))
+            else:
+                I8 = image_tools.u16_to_u8(rgb, handle=handle)   # src/image_tools.py:142
+                rec = handle.overlay(seg, np.ascontiguousarray(I8), sensitivity, HSR_SIZE_THRESHOLD)
+                writer, payload = write_fn, [(im,) for im in I8]
             t_stage['pack'] += t1 - t0
             t_stage['device'] += time.perf_counter() - t1
             for j, (k, _, _) in enumerate(group):
-                writes.append(writers.submit(write_fn, image_paths[k], I8[j]))
+                writes.append(writers.submit(writer, image_paths[k], *payload[j]))
                 rows[k] = [os.path.split(image_paths[k])[1]] + csvio.overlay_cells(rec[j])
 
         group, key = [], None

@@ -59,6 +59,8 @@ extern "C" {
  * the tests of the labelling kernels; nothing existing changed.) */
 /* (still 5 - additive: ecseg_meta_inference_stages_debug, a range of the six clean-up stages of meta_inference alone on given images, for
  * the tests of the kernels between the labelling passes; nothing existing changed.) */
+/* (still 5 - additive: ecseg_png_channel_encode, ecseg_png_channel_bound and ecseg_overlay_files, `make meta_overlay`'s red and green
+ * PNGs encoded on the device; nothing existing changed.) */
 #define ECSEG_ABI_VERSION 5
 
 #define ECSEG_OK             0
@@ -506,6 +508,31 @@ int ecseg_tiff_decode_batch_counts(const uint8_t* file, long long n_bytes);
  * ECSEG_E_INVALID: a null pointer (n_img > 0), H or W < 1, W >= 2^30, n_img < 0 or >= 65536, file_cap < 1. */
 int ecseg_png_labels_encode(ecseg_ctx* h, const uint8_t* labels, int n_img, int H, int W, uint8_t* const* files, long long file_cap,
                             long long* file_bytes);
+/* ---- gray PNG files (one channel of an interleaved image) encoded on the device ------------------------------------------------ */
+/* A size no file of ecseg_png_write_channel for an H x W image can exceed: signature, IHDR, IDAT framing, the worst stream (15 bits
+ * per filtered byte, header, end of block, Adler-32), IEND.  No device work.  -1 for H or W < 1. */
+long long ecseg_png_channel_bound(int H, int W);
+/* The file ecseg_png_write_channel would write for channel `channel` of each of n_img interleaved 8-bit images, inverted when
+ * invert != 0, byte for byte, as file images in memory (csrc/png_gray_kernels.hip: the maximal runs of the SUB-filtered stream are
+ * counted on the device, a wave per span of the flat stream; the Huffman code is built on the host from the 286 counts by the
+ * host writer's own functions, which also give every stream's exact size; the device writes the bits and the Adler-32; the chunk
+ * CRCs are the host's).  pixels: (n_img, H, W, C) uint8 in host memory, uploaded by the call.  files[i]: room for file_cap bytes;
+ * capacities and lengths follow ecseg_png_labels_encode's protocol, and the verdict falls before a bit is written.  One synchronous
+ * call, scratch from the handle's call arena; device time of the kernels in ECSEG_T_COUNT.
+ * ECSEG_E_INVALID: a null pointer (n_img > 0), H or W < 1, H (W + 1) >= 2^31 - 1, C < 1 or > 256, channel outside [0, C), n_img < 0
+ * or >= 65536, file_cap < 1. */
+int ecseg_png_channel_encode(ecseg_ctx* h, const uint8_t* pixels /* (n_img,H,W,C) host */, int n_img, int H, int W, int C, int channel, int invert,
+                             uint8_t* const* files, long long file_cap, long long* file_bytes);
+/* `make meta_overlay`'s device work in one call: one upload of the labels (n_img, H, W) and of the image (n_img, H, W, C) of 8- or
+ * 16-bit samples; 16-bit samples become 8-bit on the device as ecseg_u16_to_u8 makes them; `out` receives exactly ecseg_overlay's
+ * rows on that 8-bit image; red_files[i] and green_files[i] receive what ecseg_png_write_channel writes for its channels 0 and 1 with
+ * invert = 1, byte for byte, under ecseg_png_channel_encode's capacity protocol (one file_cap for both).  The 8-bit image never
+ * returns to the host.  ecseg_get_file_timings then gives ms_out[0] = 0 and in ms_out[1] the device time of the PNG kernels;
+ * ECSEG_T_COUNT holds that plus the counting kernels'.  Argument errors are ecseg_overlay's and ecseg_png_channel_encode's, and
+ * bytes_per_sample other than 1 or 2. */
+int ecseg_overlay_files(ecseg_ctx* h, const uint8_t* labels, const void* img, int n_img, int H, int W, int C, int bytes_per_sample /* 1 | 2 */,
+                        int sensitivity, int hsr_size_threshold, int64_t* out /* [n][12] */, uint8_t* const* red_files,
+                        uint8_t* const* green_files, long long file_cap, long long* red_bytes, long long* green_bytes);
 /* ecseg_meta_segment plus the two files `make metaseg` writes per image, as file images: dapi_files[i] receives what
  * ecseg_tiff_write_gray8(gray_i, invert = 1) writes, png_files[i] what ecseg_png_write_labels(labels_post_i) writes, byte for
  * byte.  The dapi strips of the whole batch are encoded on the second stream as soon as the pre-processing is done, under the
