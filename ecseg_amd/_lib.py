@@ -233,6 +233,14 @@ def _u8(a, shape_tail=None):
     return a
 
 
+def _file_u8(data):
+    """the bytes of a file (``bytes``, ``bytearray``, ``memoryview`` or a uint8 array) -> a 1-D uint8 view of them"""
+    buf = np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else _u8(data).reshape(-1)
+    if not buf.size:
+        raise ValueError('tiff_decode takes the bytes of a file')
+    return buf
+
+
 class Handle:
     """One per GPU.  Owns the device context, its stream and all device buffers."""
 
@@ -498,13 +506,13 @@ class Handle:
         if a.ndim == 3:
             a = a[..., None]
         n, H, W, Cc = a.shape
-        outs = []
-        for o in (gray_out, post_out):
-            if o is None:
-                o = np.empty((n, H, W), np.uint8)
-            elif o.shape != (n, H, W) or o.dtype != np.uint8 or not o.flags.c_contiguous:
-                raise ValueError('output buffers must be C-contiguous uint8 arrays of shape %s' % ((n, H, W),))
-            outs.append(o)
+        return self._segment_to_files('ecseg_meta_segment_files', (_ptr(a), n, H, W, Cc, a.dtype.itemsize), n, H, W, gray_out, post_out,
+                                      dapi_capacity, png_capacity, file_bufs)
+
+    def _segment_to_files(self, entry, head, n, H, W, gray_out, post_out, dapi_capacity, png_capacity, file_bufs):
+        """what ``meta_segment_files`` and ``meta_segment_tiffs_files`` share: ``entry`` called with its own arguments (``head``, the
+        input), then the file slots and the outputs -> (gray, post, n_ec, tie_risk, dapi_files, png_files)"""
+        outs = self._gray_post(gray_out, post_out, n, H, W)
         dcap = H * W + 65536 if dapi_capacity is None else int(dapi_capacity)
         pcap = H * W // 2 + 65536 if png_capacity is None else int(png_capacity)
         dbuf, dptr = self._file_slots(file_bufs[0] if file_bufs else None, n, max(dcap, 1))
@@ -512,10 +520,9 @@ class Handle:
         dn, pn = (C.c_longlong * max(n, 1))(), (C.c_longlong * max(n, 1))()
         nec = np.zeros(n, np.int32); tie = np.zeros(n, np.int32)
         t0 = time.perf_counter()
-        rc = self.lib.ecseg_meta_segment_files(self.h, _ptr(a), n, H, W, Cc, a.dtype.itemsize, dptr, dcap, dn, pptr, pcap, pn,
-                                               _ptr(outs[0]), _ptr(outs[1]), _ptr(nec), _ptr(tie))
+        rc = getattr(self.lib, entry)(self.h, *head, dptr, dcap, dn, pptr, pcap, pn, _ptr(outs[0]), _ptr(outs[1]), _ptr(nec), _ptr(tie))
         self.native_seconds += time.perf_counter() - t0
-        self._check(rc, 'ecseg_meta_segment_files')
+        self._check(rc, entry)
         self.last_file_bytes = list(dn)[:n] + list(pn)[:n]
         copy = not file_bufs
         return (outs[0], outs[1], nec, tie, self._files_of(dbuf, list(dn)[:n], max(dcap, 1), copy), self._files_of(pbuf, list(pn)[:n], max(pcap, 1), copy))
@@ -530,7 +537,7 @@ class Handle:
     def _tiffs_packed(datas, shape):
         """the files of one ``meta_segment_tiffs`` call -> (buffer, ranges, n, H, W, C, bytes per sample); ``shape``: the batch's common
         (H, W, samples per pixel, bits per sample), a row of ``tiff_decode_packed``'s shapes"""
-        bufs = [np.frombuffer(d, np.uint8) if isinstance(d, (bytes, bytearray, memoryview)) else _u8(d).reshape(-1) for d in datas]
+        bufs = [_file_u8(d) for d in datas]
         buf, ranges = pack_file_images(bufs)
         H, W, Cc, bits = (int(v) for v in shape)
         if bits not in (8, 16):
@@ -558,22 +565,9 @@ class Handle:
         png_files, status); the arguments behind ``shape`` and the files are ``meta_segment_files``'s, status is ``meta_segment_tiffs``'s.
         An image whose status is not 0 has no files (None)."""
         buf, ranges, n, H, W, Cc, bps = self._tiffs_packed(datas, shape)
-        outs = self._gray_post(gray_out, post_out, n, H, W)
-        dcap = H * W + 65536 if dapi_capacity is None else int(dapi_capacity)
-        pcap = H * W // 2 + 65536 if png_capacity is None else int(png_capacity)
-        dbuf, dptr = self._file_slots(file_bufs[0] if file_bufs else None, n, max(dcap, 1))
-        pbuf, pptr = self._file_slots(file_bufs[1] if file_bufs else None, n, max(pcap, 1))
-        dn, pn = (C.c_longlong * max(n, 1))(), (C.c_longlong * max(n, 1))()
-        nec = np.zeros(n, np.int32); tie = np.zeros(n, np.int32); status = np.zeros(n, np.int32)
-        t0 = time.perf_counter()
-        rc = self.lib.ecseg_meta_segment_tiffs_files(self.h, _ptr(buf), buf.size, _ptr(ranges), n, H, W, Cc, bps, _ptr(status), dptr, dcap, dn,
-                                                     pptr, pcap, pn, _ptr(outs[0]), _ptr(outs[1]), _ptr(nec), _ptr(tie))
-        self.native_seconds += time.perf_counter() - t0
-        self._check(rc, 'ecseg_meta_segment_tiffs_files')
-        self.last_file_bytes = list(dn)[:n] + list(pn)[:n]
-        copy = not file_bufs
-        return (outs[0], outs[1], nec, tie, self._files_of(dbuf, list(dn)[:n], max(dcap, 1), copy), self._files_of(pbuf, list(pn)[:n], max(pcap, 1), copy),
-                status.tolist())
+        status = np.zeros(n, np.int32)
+        return self._segment_to_files('ecseg_meta_segment_tiffs_files', (_ptr(buf), buf.size, _ptr(ranges), n, H, W, Cc, bps, _ptr(status)), n, H, W,
+                                      gray_out, post_out, dapi_capacity, png_capacity, file_bufs) + (status.tolist(),)
 
     @staticmethod
     def _gray_post(gray_out, post_out, n, H, W):
@@ -900,9 +894,7 @@ class Handle:
         """The bytes of a TIFF file -> what ``image_io.read_tiff`` returns for that file, (H, W) or (H, W, spp) uint8 / uint16, with
         every strip decoded on the device (ecseg_tiff_decode); None for a file that is left to the host readers (ECSEG_E_UNSUPPORTED:
         tiles, BigTIFF, PackBits, Deflate).  Whether a file is worth sending here is ``image_io.imread``'s question (ecseg_tiff_decode_routes).  A corrupt file raises, with code -1."""
-        buf = np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else _u8(data).reshape(-1)
-        if not buf.size:
-            raise ValueError('tiff_decode takes the bytes of a file')
+        buf = _file_u8(data)
         H, W, spp, bits = C.c_int(), C.c_int(), C.c_int(), C.c_int()
         shape = (C.byref(H), C.byref(W), C.byref(spp), C.byref(bits))
         rc = self.lib.ecseg_tiff_decode(self.h, _ptr(buf), buf.size, None, 0, *shape)
@@ -941,10 +933,7 @@ class Handle:
         todo = []                                              # (position, bytes as uint8)
         for k, data in enumerate(datas):
             try:
-                buf = np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else _u8(data).reshape(-1)
-                if not buf.size:
-                    raise ValueError('tiff_decode takes the bytes of a file')
-                todo.append((k, buf))
+                todo.append((k, _file_u8(data)))
             except (TypeError, ValueError) as e:
                 out[k] = e
 

@@ -398,23 +398,10 @@ struct TiffSources { const uint8_t* img[3]; size_t stride; };
 hipError_t run_tiff_encode(const TiffSources& src, int n_files, int H, int W, int spp, int invert, const TiffEncodeBufs& b, hipStream_t s);
 
 // ---- launcher implemented in tiff_decode_kernels.hip (the strips of ecseg_tiff_read, host_io.cpp) -------------------------------
-// Device buffers of one decode: file: the file image as uploaded; offs / cnts: the first n_table entries of its strip tables (the
-// strips the image has rows for); raster: H lines; status: one word per strip of the image (nstrips = ceil(H / rps) >= n_table).
-struct TiffDecodeBufs { uint8_t* file; uint32_t* offs; uint32_t* cnts; uint8_t* raster; uint32_t* status; int n_table, nstrips; };
-inline TiffDecodeBufs tiff_decode_bufs(Carver& c, size_t n_bytes, int n_table, size_t raster_bytes, int nstrips) {
-    TiffDecodeBufs b;
-    b.n_table = n_table; b.nstrips = nstrips;
-    b.file = c.take<uint8_t>(n_bytes); b.offs = c.take<uint32_t>((size_t)n_table); b.cnts = c.take<uint32_t>((size_t)n_table);
-    b.raster = c.take<uint8_t>(raster_bytes); b.status = c.take<uint32_t>((size_t)nstrips);
-    return b;
-}
-// Decodes the strips (lzw: LZW, else uncompressed) into b.raster and b.status (0, or 1: corrupt), then swaps 16-bit samples
-// (`swap`) and undoes the horizontal predictor (`predictor`) row by row.  A strip holds less than 2^31 bytes.
-hipError_t run_tiff_decode(const TiffDecodeBufs& b, unsigned long long n_bytes, int H, int W, int spp, int bytes_per_sample, int rps, int lzw,
-                           int swap, int predictor, hipStream_t s);
-// The same for a batch of files laid out by td_batch_layout (tiff_decode_batch.h), in one launch per kernel: every strip of every
-// file into b.rasters and b.strip_status, the row pass once per sample size that needs it, then b.file_status (0, or 1: some strip of
-// the file is corrupt).  b.tab, b.files and b.tables are in place.
+// Decodes a batch of files laid out by td_batch_layout (tiff_decode_batch.h; a lone file is a batch of one), in one launch per kernel:
+// every strip of every file (LZW or uncompressed, a strip holds less than 2^31 bytes) into b.rasters and b.strip_status (0, or 1:
+// corrupt), the row pass - 16-bit samples swapped, the horizontal predictor undone - once per sample size that needs it, then
+// b.file_status (0, or 1: some strip of the file is corrupt).  b.tab, b.files and b.tables are in place.
 hipError_t run_tiff_decode_batch(const TiffDecodeBatchBufs& b, const TdBatchLayout& L, hipStream_t s);
 
 // ---- launchers implemented in png_kernels.hip (the label PNG of ecseg_png_write_labels, host_io.cpp) ------------------------------

@@ -269,6 +269,12 @@ int png_gray_encode(ecseg_ctx* h, const char* who, const GraySource& src, int n_
 // ones on even offsets).  Empty string, or which argument is wrong.
 std::string tiff_batch_plan(const uint8_t* files, long long files_bytes, const int64_t* ranges, int n_files, const int64_t* dst_offsets,
                             bool with_strips, std::vector<TiffInfo>& info, std::vector<int>& status, std::vector<TdFileIn>& in);
+// The rest of the way, one statement for ecseg_tiff_decode (a batch of one), ecseg_tiff_decode_batch and ecseg_meta_segment_tiffs:
+// p.tables from the files' parsed tags and p.L; then, with the buffers of tiff_decode_batch_bufs(p.L), the upload of the file span,
+// the table and the tables and the decode on stream s, the kernels between events e0 and e1.  p and the caller's files are read until
+// s has been waited for; the status words (b.file_status) are the caller's to read.
+void tiff_plan_tables(const std::vector<TiffInfo>& info, TiffsPlan& p);
+int tiff_batch_launch(ecseg_ctx* h, const uint8_t* files, const TiffsPlan& p, const TiffDecodeBatchBufs& b, hipStream_t s, hipEvent_t e0, hipEvent_t e1);
 
 // filter_layout.hip: host arrays to host arrays
 std::vector<float> relayout_conv(const float* w, int R, int S, int cin, int cout, int chunks, int np);

@@ -184,6 +184,16 @@ static int tiff_decode_verdict(const uint8_t* file, size_t n, bool with_strips, 
     return with_strips ? tiff_strips_in_file(t, n, why) : ECSEG_OK;
 }
 
+// The layout row of a file that passed tiff_decode_verdict with its strips: n bytes at src_off of the caller's files; dst_off is the caller's.
+static TdFileIn td_file_in(const TiffInfo& t, size_t src_off, size_t n) {
+    TdFileIn f;
+    const size_t nstrips = ((size_t)t.H + t.rps - 1) / t.rps;
+    f.in_batch = true; f.src_off = src_off; f.n_bytes = n;
+    f.n_table = (uint32_t)std::min(t.off.size(), nstrips); f.H = t.H; f.W = t.W; f.spp = t.spp; f.bps = t.bits / 8; f.rps = t.rps;
+    f.lzw = t.comp == 5; f.swap = f.bps == 2 && !t.le; f.predictor = t.pred == 2;
+    return f;
+}
+
 // The files of a batch as ecseg_tiff_decode judges each alone (ctx.h says what comes back).
 std::string ecseg::tiff_batch_plan(const uint8_t* files, long long files_bytes, const int64_t* ranges, int n_files, const int64_t* dst_offsets,
                                    bool with_strips, std::vector<TiffInfo>& info, std::vector<int>& status, std::vector<TdFileIn>& in) {
@@ -204,11 +214,7 @@ std::string ecseg::tiff_batch_plan(const uint8_t* files, long long files_bytes, 
         status[(size_t)i] = tiff_decode_verdict(files + off, nb, with_strips, t, &parsed, why);
         if (!parsed) t.H = t.W = 0;                          // (no shape to report)
         if (status[(size_t)i] != ECSEG_OK) continue;
-        TdFileIn& f = in[(size_t)i];
-        const size_t nstrips = ((size_t)t.H + t.rps - 1) / t.rps;
-        f.in_batch = true; f.src_off = off; f.n_bytes = nb;
-        f.n_table = (uint32_t)std::min(t.off.size(), nstrips); f.H = t.H; f.W = t.W; f.spp = t.spp; f.bps = t.bits / 8; f.rps = t.rps;
-        f.lzw = t.comp == 5; f.swap = f.bps == 2 && !t.le; f.predictor = t.pred == 2;
+        TdFileIn& f = in[(size_t)i] = td_file_in(t, off, nb);
         if (dst_offsets) {
             if (dst_offsets[i] < 0) return "file " + std::to_string(i) + ": a negative destination offset";
             f.dst_off = (uint64_t)dst_offsets[i];
@@ -219,6 +225,27 @@ std::string ecseg::tiff_batch_plan(const uint8_t* files, long long files_bytes, 
         }
     }
     return std::string();
+}
+
+void ecseg::tiff_plan_tables(const std::vector<TiffInfo>& info, TiffsPlan& p) {
+    p.tables.assign((size_t)p.L.table_words, 0u);
+    for (size_t i = 0; i < p.L.tab.size(); ++i) {
+        const TdFile& f = p.L.tab[i];
+        std::copy(info[i].off.begin(), info[i].off.begin() + f.n_table, p.tables.begin() + (size_t)f.table_off);
+        std::copy(info[i].cnt.begin(), info[i].cnt.begin() + f.n_table, p.tables.begin() + (size_t)f.table_off + f.n_table);
+    }
+}
+
+int ecseg::tiff_batch_launch(ecseg_ctx* h, const uint8_t* files, const TiffsPlan& p, const TiffDecodeBatchBufs& b, hipStream_t s, hipEvent_t e0,
+                             hipEvent_t e1) {
+    const TdBatchLayout& L = p.L;
+    if (L.src_span) HIP_TRY(h, hipMemcpyAsync(b.files, files + L.src_base, (size_t)L.src_span, hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(b.tab, L.tab.data(), L.tab.size() * sizeof(TdFile), hipMemcpyHostToDevice, s));
+    if (!p.tables.empty()) HIP_TRY(h, hipMemcpyAsync(b.tables, p.tables.data(), p.tables.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipEventRecord(e0, s));
+    HIP_TRY(h, run_tiff_decode_batch(b, L, s));
+    HIP_TRY(h, hipEventRecord(e1, s));
+    return ECSEG_OK;
 }
 
 extern "C" {
@@ -272,21 +299,26 @@ int ecseg_tiff_decode(ecseg_ctx* h, const uint8_t* file, long long n_bytes, void
     if (!dst) return ECSEG_OK;
     if ((unsigned long long)dst_bytes < total) return fail(h, ECSEG_E_INVALID, "tiff_decode: the destination holds fewer bytes than the image");
     if ((rc = tiff_strips_in_file(t, n, why)) != ECSEG_OK) return fail(h, rc, "tiff_decode: " + why);
-    const size_t nstrips = ((size_t)t.H + t.rps - 1) / t.rps, n_table = std::min(t.off.size(), nstrips);
+    TiffsPlan p;                                             // a batch of one: the file at the head of the upload, its raster at the head of dst
+    const std::string bad = td_batch_layout({td_file_in(t, 0, n)}, p.L);
+    if (!bad.empty()) return fail(h, ECSEG_E_INVALID, "tiff_decode: " + bad);
+    tiff_plan_tables({t}, p);
     USE_DEVICE(h);
-    TiffDecodeBufs b{};
-    if ((rc = lay_out(h, h->call_arena, [&](Carver& c) { b = tiff_decode_bufs(c, n, (int)n_table, (size_t)total, (int)nstrips); }))) return rc;
+    TiffDecodeBatchBufs b{};
+    if ((rc = lay_out(h, h->call_arena, [&](Carver& c) { b = tiff_decode_batch_bufs(c, p.L); }))) return rc;
     hipStream_t s = h->stream;
-    HIP_TRY(h, hipMemcpyAsync(b.file, file, n, hipMemcpyHostToDevice, s));
-    HIP_TRY(h, hipMemcpyAsync(b.offs, t.off.data(), n_table * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-    HIP_TRY(h, hipMemcpyAsync(b.cnts, t.cnt.data(), n_table * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-    TIMED(h, s, 0, 1, HIP_TRY(h, run_tiff_decode(b, (unsigned long long)n, (int)t.H, (int)t.W, (int)t.spp, (int)bpp, (int)t.rps, t.comp == 5, bpp == 2 && !t.le, t.pred == 2, s)));
-    std::vector<uint32_t> status(nstrips);
-    HIP_TRY(h, hipMemcpyAsync(status.data(), b.status, nstrips * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    WAIT_SET(h, s, 0, 1);
-    for (size_t k = 0; k < nstrips; ++k)
-        if (status[k]) return fail(h, ECSEG_E_INVALID, "tiff_decode: strip " + std::to_string(k) + " holds a corrupt LZW stream");
-    HIP_TRY(h, hipMemcpyAsync(dst, b.raster, (size_t)total, hipMemcpyDeviceToHost, s));
+    if ((rc = tiff_batch_launch(h, file, p, b, s, h->ev[0], h->ev[1]))) return rc;
+    uint32_t corrupt = 0;
+    HIP_TRY(h, hipMemcpyAsync(&corrupt, b.file_status, sizeof corrupt, hipMemcpyDeviceToHost, s));
+    WAIT_SET(h, s, 0, 1);                                    // (p and the caller's file are read by the copies above: they live until here)
+    if (corrupt) {                                           // the batch folds the strips into one word per file: which strip it was
+        std::vector<uint32_t> status((size_t)p.L.n_strips);
+        HIP_TRY(h, hipMemcpyAsync(status.data(), b.strip_status, status.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipStreamSynchronize(s));
+        const size_t k = std::find_if(status.begin(), status.end(), [](uint32_t v) { return v != 0; }) - status.begin();
+        return fail(h, ECSEG_E_INVALID, "tiff_decode: strip " + std::to_string(k) + " holds a corrupt LZW stream");
+    }
+    HIP_TRY(h, hipMemcpyAsync(dst, b.rasters, (size_t)total, hipMemcpyDeviceToHost, s));
     HIP_TRY(h, hipStreamSynchronize(s));
     return ECSEG_OK;
 }
@@ -330,7 +362,10 @@ int ecseg_tiff_decode_batch(ecseg_ctx* h, const uint8_t* files, long long files_
     clear_timings(h);                                        // (as ecseg_tiff_decode)
     if (n_files == 0) return ECSEG_OK;
     const size_t nf = (size_t)n_files;
-    std::vector<TiffInfo> info; std::vector<int> verdict; std::vector<TdFileIn> in;
+    std::vector<TiffInfo> info; std::vector<TdFileIn> in;
+    TiffsPlan p;
+    std::vector<int>& verdict = p.verdict;
+    TdBatchLayout& L = p.L;
     std::string bad = tiff_batch_plan(files, files_bytes, file_ranges, n_files, dst ? dst_offsets : nullptr, dst != nullptr, info, verdict, in);
     if (!bad.empty()) return fail(h, ECSEG_E_INVALID, me + bad);
     if (dst) {                                               // every raster inside the destination and clear of the others
@@ -346,7 +381,6 @@ int ecseg_tiff_decode_batch(ecseg_ctx* h, const uint8_t* files, long long files_
         for (size_t k = 1; k < spans.size(); ++k)
             if (spans[k].first < spans[k - 1].second) return fail(h, ECSEG_E_INVALID, me + "two rasters overlap in the destination");
     }
-    TdBatchLayout L;
     if (dst && !(bad = td_batch_layout(in, L)).empty()) return fail(h, ECSEG_E_INVALID, me + bad);
     for (size_t i = 0; i < nf; ++i) {
         const TiffInfo& t = info[i];
@@ -359,20 +393,12 @@ int ecseg_tiff_decode_batch(ecseg_ctx* h, const uint8_t* files, long long files_
     int rc;
     TiffDecodeBatchBufs b{};
     if ((rc = lay_out(h, h->call_arena, [&](Carver& c) { b = tiff_decode_batch_bufs(c, L); }))) return rc;
-    std::vector<uint32_t> tables((size_t)L.table_words);
-    for (size_t i = 0; i < nf; ++i) {
-        const TdFile& f = L.tab[i];
-        std::copy(info[i].off.begin(), info[i].off.begin() + f.n_table, tables.begin() + (size_t)f.table_off);
-        std::copy(info[i].cnt.begin(), info[i].cnt.begin() + f.n_table, tables.begin() + (size_t)f.table_off + f.n_table);
-    }
+    tiff_plan_tables(info, p);
     hipStream_t s = h->stream;
-    HIP_TRY(h, hipMemcpyAsync(b.files, files + L.src_base, (size_t)L.src_span, hipMemcpyHostToDevice, s));
-    HIP_TRY(h, hipMemcpyAsync(b.tab, L.tab.data(), nf * sizeof(TdFile), hipMemcpyHostToDevice, s));
-    if (!tables.empty()) HIP_TRY(h, hipMemcpyAsync(b.tables, tables.data(), tables.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-    TIMED(h, s, 0, 1, HIP_TRY(h, run_tiff_decode_batch(b, L, s)));
+    if ((rc = tiff_batch_launch(h, files, p, b, s, h->ev[0], h->ev[1]))) return rc;
     std::vector<uint32_t> corrupt(nf, 0);
     HIP_TRY(h, hipMemcpyAsync(corrupt.data(), b.file_status, nf * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    WAIT_SET(h, s, 0, 1);                     // (L.tab and tables are read by the copies above: they live until here)
+    WAIT_SET(h, s, 0, 1);                     // (p is read by the copies above: it lives until here)
     // the rasters of the clean files, a run without a gap in one copy: all of them at once where the caller packed them
     std::vector<std::pair<uint64_t, uint64_t>> runs;
     for (size_t i = 0; i < nf; ++i) {

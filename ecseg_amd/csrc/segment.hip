@@ -334,33 +334,14 @@ static int tiffs_plan(ecseg_ctx* h, const uint8_t* files, long long files_bytes,
         f.dst_off = i * slot;
     }
     if (!(bad = td_batch_layout(in, p.L)).empty()) return fail(h, ECSEG_E_INVALID, me + bad);
-    p.tables.assign((size_t)p.L.table_words, 0u);
-    for (size_t i = 0; i < (size_t)n; ++i) {
-        const TdFile& f = p.L.tab[i];
-        std::copy(info[i].off.begin(), info[i].off.begin() + f.n_table, p.tables.begin() + (size_t)f.table_off);
-        std::copy(info[i].cnt.begin(), info[i].cnt.begin() + f.n_table, p.tables.begin() + (size_t)f.table_off + f.n_table);
-    }
+    tiff_plan_tables(info, p);
     return ECSEG_OK;
 }
 
-// The decode's scratch beside the rasters, which are the input slots at `slots`: tiff_decode_batch_bufs without a raster buffer.
-static TiffDecodeBatchBufs tiffs_bufs(Carver& c, const TdBatchLayout& L, uint8_t* slots) {
-    TiffDecodeBatchBufs b;
-    b.tab = c.take<TdFile>(L.tab.size()); b.files = c.take<uint8_t>((size_t)L.src_span); b.tables = c.take<uint32_t>((size_t)L.table_words);
-    b.rasters = slots + L.dst_base; b.strip_status = c.take<uint32_t>((size_t)L.n_strips);
-    b.file_status = c.take<uint32_t>(L.tab.size());
-    return b;
-}
-
-// Upload and decode on stream s, the kernels between events e0 and e1.  p and the caller's files are read until s has been waited for.
-static int tiffs_launch(ecseg_ctx* h, const uint8_t* files, const TiffsPlan& p, const TiffDecodeBatchBufs& b, hipStream_t s, hipEvent_t e0, hipEvent_t e1) {
-    const TdBatchLayout& L = p.L;
-    if (L.src_span) HIP_TRY(h, hipMemcpyAsync(b.files, files + L.src_base, (size_t)L.src_span, hipMemcpyHostToDevice, s));
-    HIP_TRY(h, hipMemcpyAsync(b.tab, L.tab.data(), L.tab.size() * sizeof(TdFile), hipMemcpyHostToDevice, s));
-    if (!p.tables.empty()) HIP_TRY(h, hipMemcpyAsync(b.tables, p.tables.data(), p.tables.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-    HIP_TRY(h, hipEventRecord(e0, s));
-    HIP_TRY(h, run_tiff_decode_batch(b, L, s));
-    HIP_TRY(h, hipEventRecord(e1, s));
+// The stream and the event of what is sent ahead (images or files), made when the first call sends something.
+static int ensure_stream_in(ecseg_ctx* h) {
+    if (!h->stream_in) HIP_TRY(h, hipStreamCreateWithFlags(&h->stream_in, hipStreamNonBlocking));
+    if (!h->ev_pre) HIP_TRY(h, hipEventCreateWithFlags(&h->ev_pre, hipEventDisableTiming));
     return ECSEG_OK;
 }
 
@@ -392,7 +373,7 @@ static int meta_segment_run(ecseg_ctx* h, const void* img, int n_img, int H, int
     TiffDecodeBatchBufs db{};
     if ((files || (tiffs && !ahead)) && (rc = lay_out(h, h->call_arena, [&](Carver& c) {
             if (files) { tb = tiff_encode_bufs(c, H, W, 1, n_img, false); pb = png_encode_bufs(c, H, W, n_img, false); }
-            if (tiffs && !ahead) db = tiffs_bufs(c, plan.L, h->d_aux8);
+            if (tiffs && !ahead) db = tiff_decode_batch_bufs(c, plan.L, h->d_aux8);
         })))
         return rc;
     if ((rc = h->d_gray.ensure(h, tot))) return rc;
@@ -413,7 +394,7 @@ static int meta_segment_run(ecseg_ctx* h, const void* img, int n_img, int H, int
             h->d_aux8.swap(h->d_pre);
             d_status = h->pre_file_status;
             h->read_ms = h->pre_read_ms;
-        } else if ((rc = tiffs_launch(h, tiffs->files, plan, db, s, h->ev_read[0], h->ev_read[1]))) {
+        } else if ((rc = tiff_batch_launch(h, tiffs->files, plan, db, s, h->ev_read[0], h->ev_read[1]))) {
             return rc;
         }
         std::vector<uint32_t> corrupt((size_t)n_img, 0);
@@ -453,8 +434,7 @@ static int meta_segment_run(ecseg_ctx* h, const void* img, int n_img, int H, int
         const void* nx = h->next_host; const size_t nb = h->next_bytes;
         h->next_host = nullptr; h->next_bytes = 0;
         h->pre_host = nullptr; h->pre_bytes = 0;
-        if (!h->stream_in) HIP_TRY(h, hipStreamCreateWithFlags(&h->stream_in, hipStreamNonBlocking));
-        if (!h->ev_pre) HIP_TRY(h, hipEventCreateWithFlags(&h->ev_pre, hipEventDisableTiming));
+        if ((rc = ensure_stream_in(h))) return rc;
         if ((rc = h->d_pre.ensure(h, nb))) return rc;
         HIP_TRY(h, hipMemcpyAsync(h->d_pre, nx, nb, hipMemcpyHostToDevice, h->stream_in));
         HIP_TRY(h, hipEventRecord(h->ev_pre, h->stream_in));
@@ -467,12 +447,11 @@ static int meta_segment_run(ecseg_ctx* h, const void* img, int n_img, int H, int
         h->next_tiffs.files = nullptr;
         // a set with an argument error is not decoded ahead: the call it was named for reports it
         if (tiffs_plan(h, nx.files, nx.bytes, nx.ranges.data(), nx.n, nx.H, nx.W, nx.C, nx.bps, h->pre_plan) == ECSEG_OK) {
-            if (!h->stream_in) HIP_TRY(h, hipStreamCreateWithFlags(&h->stream_in, hipStreamNonBlocking));
-            if (!h->ev_pre) HIP_TRY(h, hipEventCreateWithFlags(&h->ev_pre, hipEventDisableTiming));
+            if ((rc = ensure_stream_in(h))) return rc;
             if ((rc = h->d_pre.ensure(h, (size_t)nx.n * nx.H * nx.W * nx.C * nx.bps))) return rc;
             TiffDecodeBatchBufs ab{};
-            if ((rc = lay_out(h, h->pre_arena, [&](Carver& c) { ab = tiffs_bufs(c, h->pre_plan.L, h->d_pre); }, "hipMalloc(decode-ahead)"))) return rc;
-            if ((rc = tiffs_launch(h, nx.files, h->pre_plan, ab, h->stream_in, h->ev_read[2], h->ev_read[3]))) return rc;
+            if ((rc = lay_out(h, h->pre_arena, [&](Carver& c) { ab = tiff_decode_batch_bufs(c, h->pre_plan.L, h->d_pre); }, "hipMalloc(decode-ahead)"))) return rc;
+            if ((rc = tiff_batch_launch(h, nx.files, h->pre_plan, ab, h->stream_in, h->ev_read[2], h->ev_read[3]))) return rc;
             HIP_TRY(h, hipEventRecord(h->ev_pre, h->stream_in));
             h->pre_file_status = ab.file_status;
             std::swap(h->pre_tiffs, nx);

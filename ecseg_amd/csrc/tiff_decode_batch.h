@@ -96,11 +96,13 @@ inline std::string td_batch_layout(const std::vector<TdFileIn>& in, TdBatchLayou
 }
 
 // Device buffers of one batch: the table, the file images, the strip tables, the rasters, one status word per strip and one per file.
+// `rasters`: where the caller's destination lies on the device already (the input slots of ecseg_meta_segment_tiffs): the rasters are
+// written there, from dst_base on, and the arena holds none.
 struct TiffDecodeBatchBufs { TdFile* tab; uint8_t* files; uint32_t* tables; uint8_t* rasters; uint32_t* strip_status; uint32_t* file_status; };
-inline TiffDecodeBatchBufs tiff_decode_batch_bufs(Carver& c, const TdBatchLayout& L) {
+inline TiffDecodeBatchBufs tiff_decode_batch_bufs(Carver& c, const TdBatchLayout& L, uint8_t* rasters = nullptr) {
     TiffDecodeBatchBufs b;
     b.tab = c.take<TdFile>(L.tab.size()); b.files = c.take<uint8_t>((size_t)L.src_span); b.tables = c.take<uint32_t>((size_t)L.table_words);
-    b.rasters = c.take<uint8_t>((size_t)L.dst_span); b.strip_status = c.take<uint32_t>((size_t)L.n_strips);
+    b.rasters = rasters ? rasters + L.dst_base : c.take<uint8_t>((size_t)L.dst_span); b.strip_status = c.take<uint32_t>((size_t)L.n_strips);
     b.file_status = c.take<uint32_t>(L.tab.size());
     return b;
 }

@@ -1,4 +1,4 @@
-// One LZW strip decoded by one wave: the routine of tiff_lzw_unstrip_kernel (tiff_decode_kernels.hip), written so that the host
+// One LZW strip decoded by one wave: the routine of tiffb_unstrip_kernel (tiff_decode_kernels.hip), written so that the host
 // compiler takes it too - tools/asan/tiff_decode_fuzz.cpp runs it under ASan + UBSan against ecseg_lzw_decode (host_codec.cpp),
 // which is its specification, tolerances included.  Under hipcc a lane is a thread of the wave, td_first is a read of lane 0 and
 // td_stores_done the fence + barrier that completes the wave's stores; under the host compiler the lanes are a loop, and the other

@@ -180,6 +180,50 @@ def test_the_c_entry_point_reports_the_shape_and_refuses_a_short_destination(gpu
         assert lib.ecseg_tiff_decode(gpu.h, vp(buf), 7, vp(out), want.size, *shape) == -1       # not a TIFF
 
 
+def _three_strips_one_flipped(k, at=9):
+    """An 8-pixel-wide LZW file of three one-row strips, bit ``at`` of strip k flipped as the corrupt corpus flips one: bit 9 is the
+    top bit of the first code behind the ClearCode, which then names an entry the fresh table does not have."""
+    rows = np.random.default_rng(9).integers(0, 256, (3, 8), dtype=np.uint8)
+    strips = [bytearray(dc.pack(dc.lzw_codes(r.tobytes()))) for r in rows]
+    strips[k][at >> 3] ^= 0x80 >> (at & 7)
+    return dc.tiff_file([bytes(s) for s in strips], 3, 8, 1)
+
+
+@pytest.mark.parametrize('k', (1, 2))
+def test_a_corrupt_strip_is_named_and_the_destination_is_not_written(gpu, tmp_path, k):
+    data = _three_strips_one_flipped(k)
+    assert host_read(data, tmp_path) == 'invalid'
+    with pytest.raises(EcsegError) as e:
+        gpu.tiff_decode(data)
+    assert e.value.code == -1 and 'strip %d holds a corrupt LZW stream' % k in str(e.value)
+    lib = load_library()
+    buf = np.frombuffer(data, np.uint8)
+    H, W, spp, bits = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+    out = np.full(24 + 16, 0xa5, np.uint8)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)
+    assert lib.ecseg_tiff_decode(gpu.h, vp(buf), buf.size, vp(out), 24, C.byref(H), C.byref(W), C.byref(spp), C.byref(bits)) == -1
+    assert 'tiff_decode: strip %d holds a corrupt LZW stream' % k in lib.ecseg_last_error(gpu.h).decode()
+    assert (H.value, W.value, spp.value, bits.value) == (3, 8, 1, 8) and (out == 0xa5).all(), 'a corrupt file reached the destination'
+
+
+def test_a_call_that_only_measures_or_refuses_leaves_every_stage_timer_at_zero(gpu, tmp_path_factory):
+    lib = load_library()
+    data, want = case_file(_case('gray_3x1'), tmp_path_factory)
+    buf = np.frombuffer(data, np.uint8)
+    H, W, spp, bits = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+    shape = (C.byref(H), C.byref(W), C.byref(spp), C.byref(bits))
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)
+    out = np.zeros(want.size, np.uint8)
+    for refusing in (False, True):
+        assert same(gpu.tiff_decode(data), want) and gpu.timings()['count'] > 0
+        if refusing:
+            assert lib.ecseg_tiff_decode(gpu.h, vp(buf), 7, vp(out), out.size, *shape) == -1       # not a TIFF
+        else:
+            assert lib.ecseg_tiff_decode(gpu.h, vp(buf), buf.size, None, 0, *shape) == 0
+            assert (H.value, W.value, spp.value, bits.value) == (want.shape[0], want.shape[1], 1, 8)
+        assert all(v == 0 for v in gpu.timings().values()), (refusing, gpu.timings())
+
+
 def test_make_stat_fish_writes_the_same_bytes_with_the_key_absent_on_and_off(gpu, tmp_path, monkeypatch, capsys):
     """Three- and four-channel images, the min-cut picture included: every file and the CSV; then both device keys at once."""
     inp, _ = cpu.make_folder(tmp_path, size=(67, 93))

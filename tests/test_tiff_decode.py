@@ -1,6 +1,6 @@
 """The device TIFF reader without a GPU: the new symbols, the ``tiff_read_on_device`` key of ``make stat_fish`` on injected handles,
-``image_io.imread(path, handle=...)``, the routing rule on hand-made strip tables, and the per-strip routine of
-tiff_lzw_unstrip_kernel compiled for the host under ASan + UBSan on the tolerated and the corrupt streams of
+``image_io.imread(path, handle=...)``, the routing rule on hand-made strip tables, and the per-strip LZW routine of
+tiffb_unstrip_kernel (td_lzw_strip) compiled for the host under ASan + UBSan on the tolerated and the corrupt streams of
 tests/tiff_decode_cases.py."""
 import os
 import shutil

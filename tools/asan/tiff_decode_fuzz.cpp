@@ -1,5 +1,5 @@
 // AddressSanitizer / UBSan driver for the device TIFF reader's per-strip routine (csrc/tiff_decode_strip.h, the body of
-// tiff_lzw_unstrip_kernel) compiled for the host: the 64 lanes are a loop, the read of lane 0 and the store fence do nothing.  CPU
+// tiffb_unstrip_kernel for an LZW strip) compiled for the host: the 64 lanes are a loop, the read of lane 0 and the store fence do nothing.  CPU
 // build only (`make asan_tiff_decode`).  Every stream is decoded by the routine and by ecseg_lzw_decode (csrc/host_codec.cpp), its
 // specification: the status must agree, and where it is OK every byte of the strip (zero fill included).  Source and destination
 // are heap blocks of exactly `have` and `want` bytes, so a read or write outside them is the sanitizer's finding.
