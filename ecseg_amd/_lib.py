@@ -698,7 +698,7 @@ class Handle:
     def ccl_pass(self, key, aux=None, lut=0xffffffff, conn=8, stat=0, aux_mode=0, aux_c=0, need=0, count_only=False, sparse=False,
                  allow_full=False, queries=()):
         """Test-only (ecseg_ccl_pass_debug): ONE labelling pass on (n, H, W) uint8 keys, described as the drivers of
-        csrc/post_kernels.hip describe theirs, with everything it produced -> dict: ``root`` int32 (-1 unkeyed, else the pixel
+        csrc/meta_inference_kernels.hip and csrc/overlay_kernels.hip describe theirs, with everything it produced -> dict: ``root`` int32 (-1 unkeyed, else the pixel
         index of the component's first pixel; after a count_only pass the pixel's own index where it was counted as a root),
         ``area`` uint32 / ``sumy`` / ``sumx`` uint64 / ``flag`` uint32 at root pixels (0 elsewhere), ``ncomp`` / ``npx`` (n, 3) for
         keys 1..3, ``last_root`` (last root + 1), ``cnt`` (n, 5) answers to ``queries`` [(key, need_bits)], ``list1`` / ``list2``

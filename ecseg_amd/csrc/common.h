@@ -162,7 +162,9 @@ hipError_t launch_pool_pad(const TView& in, const TView& out, int n, int kh, int
 hipError_t launch_tile_patches(const uint8_t* gray, int n_img, int H, int W, const int32_t* pos_yx, int n_pos,
                                float* out, hipStream_t s);
 
-// ---- launchers implemented in post_kernels.hip -----------------------------------------------------------------
+// ---- post-processing launchers: stitch_preprocess_kernels.hip (launch_stitch_*, launch_u16_to_u8, run_preprocess),
+// ---- meta_inference_kernels.hip (run_meta_inference), ccl_kernels.hip (run_count_cc, run_ccl_labels, run_ccl_pass_debug),
+// ---- overlay_kernels.hip (run_count_coloc, run_count_hsr, run_overlay); the labelling engine they share: ccl.h -------------
 // stitch + img_as_ubyte + argmax; src_map: (H*W) int32 = (patch << 16) | (y << 8) | x, or -1 when never written
 // tie_risk (may be null): per image, the pixels whose two largest quantised values differ by at most 1; tie_shards: scratch of
 // n_img * G_SHARDS * G_STRIDE ints (replicated counters, one 128-B line each)
@@ -222,7 +224,7 @@ hipError_t run_count_cc(PostWorkspace& ws, const uint8_t* mask, int n_img, int H
                         long long* px_dev, hipStream_t s);
 hipError_t run_ccl_labels(PostWorkspace& ws, const uint8_t* mask, int n_img, int H, int W, int conn,
                           int32_t* labels_dev, hipStream_t s);
-// Test-only: ONE labelling pass (the CclPass of post_kernels.hip, field by field) alone, with everything it produced exported.
+// Test-only: ONE labelling pass (the CclPass of ccl.h, field by field) alone, with everything it produced exported.
 // q_key / q_need: up to 5 queries of count_flagged_owner_roots_kernel (roots with key == q_key, 0 = any, whose flag word holds all
 // bits of q_need), answered in counters 9 .. 13.
 struct CclPassDesc {

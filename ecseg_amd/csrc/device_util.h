@@ -93,7 +93,7 @@ __device__ __forceinline__ unsigned xcd_remap(unsigned bid, unsigned nwg) {
     return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
 }
 
-// Union-find over an int32 parent array in global memory (post_kernels.hip: the binary labelling; fishdist_kernels.hip: the FISH
+// Union-find over an int32 parent array in global memory (ccl_kernels.hip: the binary labelling; fishdist_kernels.hip: the FISH
 // spots of one nucleus).  A root is its own parent.
 __device__ __forceinline__ int uf_load(const int32_t* L, int i) {
     return __hip_atomic_load(L + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

@@ -1,4 +1,4 @@
-// The one-call drivers of the clean-up and counting kernels (post_kernels.hip): each uploads its inputs, runs its kernels on the main
+// The one-call drivers of the clean-up and counting kernels (ccl_kernels.hip, meta_inference_kernels.hip, overlay_kernels.hip, stitch_preprocess_kernels.hip): each uploads its inputs, runs its kernels on the main
 // stream and downloads the results (u16_to_u8, stitch_argmax, meta_inference, the counts, one labelling pass alone, overlay).
 #include "driver_util.h"
 

@@ -281,7 +281,7 @@ int ecseg_count_cc(ecseg_ctx* h, const uint8_t* mask, int n_img, int H, int W, i
  * (connectivity 4 or 8); used by the parity tests of the union-find kernels. */
 int ecseg_ccl_labels(ecseg_ctx* h, const uint8_t* mask, int n_img, int H, int W, int connectivity,
                      int32_t* labels_out);
-/* Test-only: ONE labelling pass of the post-processing (struct CclPass of csrc/post_kernels.hip, field by field) run alone, and
+/* Test-only: ONE labelling pass of the post-processing (struct CclPass of csrc/ccl.h, field by field) run alone, and
  * everything it produced read back whole.  lut: key of a pixel = byte (value & 3) of it, or value != 0 when it is 0xffffffff;
  * conn 4 | 8; stat bit 0 area, bit 1 coordinate sums; aux_mode 0 none, 1 image border, 2 value == aux_c, 3 bits 0-4 of aux_img;
  * need bit 0 components per key, 1 pixels per key, 2 last root + 1, 3 the two root lists; n_queries <= 5 flag queries (roots with

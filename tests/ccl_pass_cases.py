@@ -249,7 +249,7 @@ def _mode(name, src, lut, conn, stat=0, aux_mode=AUX_NONE, aux_c=0, need=0, coun
     return Mode(name, src, lut, conn, stat, aux_mode, aux_c, need, count_only, sparse, allow_full)
 
 
-# every CclPass a driver of csrc/post_kernels.hip builds, verbatim (src: the label images or their mask variant)
+# every CclPass a driver of csrc/meta_inference_kernels.hip, ccl_kernels.hip or overlay_kernels.hip builds, verbatim (src: the label images or their mask variant)
 DRIVER_MODES = [
     _mode('fill_holes_1', 'labels', ref.lut_ne(1), 4, 0, AUX_BORDER, sparse=True, allow_full=True),
     _mode('fill_holes_2', 'labels', ref.lut_ne(2), 4, 0, AUX_BORDER, sparse=True, allow_full=True),

@@ -1,4 +1,4 @@
-"""Reference of ONE connected-component labelling pass of csrc/post_kernels.hip (what ``Handle.ccl_pass`` exports), in numpy and
+"""Reference of ONE connected-component labelling pass of csrc/ccl_kernels.hip (what ``Handle.ccl_pass`` exports), in numpy and
 ``scipy.ndimage.label`` alone: the key of a pixel, the components of every key, their root (first pixel in raster order), area,
 coordinate sums and flag word, the per-image counters, the two root lists, the answers to the flag queries, and a host model of the
 64 x 32 labelling tiles (``tile_any``).  Nothing here knows how the device gets there."""

@@ -1,4 +1,4 @@
-"""One connected-component labelling pass on the device (``Handle.ccl_pass``: run_ccl_pass of csrc/post_kernels.hip alone, every
+"""One connected-component labelling pass on the device (``Handle.ccl_pass``: run_ccl_pass of csrc/ccl_kernels.hip alone, every
 product exported) against the reference of ccl_pass_ref.py, bit for bit: roots, areas, coordinate sums, flag words, counters, root
 lists, flag queries and the tile votes, for every pass a driver builds and the cross of connectivity x statistics x aux mode x
 sparse, on every image of ccl_pass_cases.py (test_ccl_pass.py holds the reference and the case list themselves on the host)."""

@@ -1,5 +1,5 @@
 """The clean-up stages of meta_inference on the device one at a time (``Handle.meta_inference_stages``: run_meta_inference of
-csrc/post_kernels.hip with a range of stages) against the stage references of meta_stage_ref.py, byte for byte, on every image of
+csrc/meta_inference_kernels.hip with a range of stages) against the stage references of meta_stage_ref.py, byte for byte, on every image of
 meta_stage_cases.py fed DIRECTLY to the stage: the final image of the whole chain, which test_gpu_post.py and test_gpu_fuzz.py
 compare, can hide a stage's error behind the stages after it (test_meta_stages.py shows that it does)."""
 import functools

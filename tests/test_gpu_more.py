@@ -255,7 +255,7 @@ def test_window_lanes_do_not_change_results(gpu, base, up):
 @pytest.mark.parametrize('n_img', [1, 7, 8, 9, 13, 16, 19])
 def test_clean_up_and_counts_for_every_batch_remainder(gpu, n_img):
     """The CCL kernels map complete groups of 8 images to one XCD per image and deal the tiles of the remaining images (all of them
-    below 8) over all XCDs (post_kernels.hip: decode_block): every image of every batch size gets the same answer as alone, and
+    below 8) over all XCDs (ccl.h: decode_block): every image of every batch size gets the same answer as alone, and
     that answer is the oracle's."""
     rng = np.random.default_rng(100 + n_img)
     H, W = 150, 333                                             # 5 x 6 tiles, the last ones partial

@@ -1,4 +1,4 @@
-"""ecseg_overlay (run_overlay in csrc/post_kernels.hip) on the device: the nine counts of a ``meta_overlay`` row against the hand
+"""ecseg_overlay (run_overlay in csrc/overlay_kernels.hip) on the device: the nine counts of a ``meta_overlay`` row against the hand
 rows and the oracle of tests/overlay_cases.py (oracle/overlay.py with oracle/postproc.py), never against the product's own
 Python.  The 12 int64 fields go through ``csvio.overlay_cells`` and every comparison is exact.  ``case_mismatches(gpu, seed)``
 is also the check of tools/fuzz_overlay.py; a failing seed of that campaign becomes a case here.

@@ -30,7 +30,7 @@ done
 wait
 LK="/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC"
 HOST="model_load.o plan_run.o segment.o drivers_post.o drivers_interseg.o drivers_fish.o drivers_files.o drivers_nuset.o"   # host objects no variant flag concerns
-REST="layer_kernels.o convs_kernel.o post_kernels.o interseg_kernels.o fishdist_kernels.o host_codec.o host_io.o comm.o -lz -ldl"   # objects of the product build
+REST="layer_kernels.o convs_kernel.o ccl_kernels.o meta_inference_kernels.o overlay_kernels.o stitch_preprocess_kernels.o interseg_kernels.o fishdist_kernels.o host_codec.o host_io.o comm.o -lz -ldl"   # objects of the product build
 W4RS="wino4r_kernel.o wino4s_kernel.o"
 for v in "$@"; do
   if [ "$v" = diag ]; then

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Randomised parity campaign of ecseg_overlay (run_overlay in csrc/post_kernels.hip) against the CPU oracle
+"""Randomised parity campaign of ecseg_overlay (run_overlay in csrc/overlay_kernels.hip) against the CPU oracle
 (oracle/overlay.py with oracle/postproc.py) - the nine cells of the ``meta_overlay`` row, exactly - beyond the fixed seeds of
 tests/test_gpu_overlay.py: cases come from that module's ``case_mismatches(gpu, seed)`` (label maps of seven kinds, bytes
 above 3 and whole tiles of one class among them; fish blobs around the size threshold on, beside and diagonal to the
