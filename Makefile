@@ -45,6 +45,15 @@ asan_tiff_decode_batch:
 	    ecseg_amd/csrc/host_codec.cpp tools/asan/tiff_decode_batch_fuzz.cpp -o /tmp/ecseg_tiff_decode_batch_fuzz
 	/tmp/ecseg_tiff_decode_batch_fuzz
 
+# and for the batched writer: the layout function (csrc/tiff_encode_batch.h) over seeded file lists and the strip routine of the
+# encode kernels (csrc/tiff_encode_strip.h) compiled for the host, lanes as a loop, against the host encoder;
+# tests/test_tiff_encode_batch.py builds and runs it
+.PHONY: asan_tiff_encode_batch
+asan_tiff_encode_batch:
+	g++ -std=c++17 -O1 -g -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=all \
+	    ecseg_amd/csrc/host_codec.cpp tools/asan/tiff_encode_batch_fuzz.cpp -o /tmp/ecseg_tiff_encode_batch_fuzz
+	/tmp/ecseg_tiff_encode_batch_fuzz
+
 # and for the device gray PNG coder: the per-block pieces of its kernels (csrc/png_gray_tokens.h) and the host parts of its code
 # (csrc/png_gray_code.h) walked as the kernels walk them, against rle_scan and the host writer's file; tests/test_png_gray.py builds
 # and runs it

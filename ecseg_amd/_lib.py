@@ -27,6 +27,7 @@ EXPORTS = [
     'ecseg_tiff_decode_batch', 'ecseg_tiff_decode_batch_bytes', 'ecseg_tiff_decode_batch_routes', 'ecseg_tiff_decode_batch_counts',
     'ecseg_meta_segment_tiffs', 'ecseg_meta_segment_tiffs_files', 'ecseg_prefetch_tiffs', 'ecseg_get_read_timings',
     'ecseg_png_channel_bound', 'ecseg_png_channel_encode', 'ecseg_overlay_files',
+    'ecseg_tiff_encode_batch', 'ecseg_tiff_encode_batch_bytes', 'ecseg_fish_render_tiff_batch',
 ]
 
 
@@ -143,6 +144,10 @@ def load_library():
     lib.ecseg_tiff_encode_bound.argtypes = [i32, i32, i32]; lib.ecseg_tiff_encode_bound.restype = C.c_longlong
     lib.ecseg_tiff_encode.argtypes = [vp, u8p, i32, i32, i32, i32, vp, C.c_longlong, C.POINTER(C.c_longlong)]
     lib.ecseg_fish_render_tiff.argtypes = [vp, u8p, i32, i32, i32, vp, u8p, i32, u8p, C.POINTER(vp), C.c_longlong, C.POINTER(C.c_longlong), vp, vp, vp]
+    lib.ecseg_tiff_encode_batch.argtypes = [vp, vp, C.c_longlong, vp, i32, vp, C.c_longlong, vp]
+    lib.ecseg_tiff_encode_batch_bytes.argtypes = [vp, i32]; lib.ecseg_tiff_encode_batch_bytes.restype = C.c_longlong
+    lib.ecseg_fish_render_tiff_batch.argtypes = [vp, i32, C.POINTER(vp), vp, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp,
+                                                 C.c_longlong, vp]
     lib.ecseg_tiff_decode.argtypes = [vp, vp, C.c_longlong, vp, C.c_longlong, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
     lib.ecseg_tiff_decode_routes.argtypes = [vp, C.c_longlong]
     lib.ecseg_tiff_decode_batch.argtypes = [vp, vp, C.c_longlong, vp, i32, vp, C.c_longlong, vp, vp, vp]
@@ -995,8 +1000,122 @@ class Handle:
         out = tuple(f[:k].tobytes() for f, k in zip(files, n))
         return (out, tuple(rasters)) if want_rasters else out
 
+    def tiff_encode_packed(self, rasters, table, capacity=None):
+        """ecseg_tiff_encode_batch as it is: ``rasters`` a 1-D uint8 buffer, ``table`` (n, 5) int64 rows (byte offset, H, W, spp,
+        invert) -> (out, ranges): a 1-D uint8 buffer with the file images back to back and (n, 2) int64 rows (offset, bytes) into it.
+        ``capacity``: bytes of ``out``, by default the sum of ecseg_tiff_encode_bound over the rows (rows the bound refuses count as
+        nothing: the call refuses them itself)."""
+        buf = np.ascontiguousarray(rasters, np.uint8).reshape(-1)
+        tab = np.ascontiguousarray(table, np.int64).reshape(-1, 5)
+        if capacity is None:
+            i32 = lambda v: int(min(max(v, -1), 2 ** 31 - 1))
+            capacity = sum(max(self.lib.ecseg_tiff_encode_bound(i32(H), i32(W), i32(spp)), 0) for _, H, W, spp, _ in tab.tolist())
+        out = np.empty(max(int(capacity), 1), np.uint8)
+        ranges = np.zeros((len(tab), 2), np.int64)
+        self._check(self.lib.ecseg_tiff_encode_batch(self.h, _ptr(buf), buf.size, _ptr(tab), len(tab), _ptr(out), int(capacity), _ptr(ranges)),
+                    'ecseg_tiff_encode_batch')
+        return out, ranges
+
+    @staticmethod
+    def _split_by_budget(needs, budget_bytes):
+        """Consecutive (lo, hi) chunks of a list whose needs stay within the budget; an item that exceeds it alone goes alone
+        (``tiff_decode_many``'s rule; a negative need - an item its call will refuse - goes alone too)."""
+        chunks, lo, held = [], 0, 0
+        for hi, need in enumerate(needs):
+            if hi > lo and (need < 0 or held < 0 or held + need > budget_bytes):
+                chunks.append((lo, hi))
+                lo, held = hi, 0
+            held = -1 if need < 0 or held < 0 else held + need
+        if needs:
+            chunks.append((lo, len(needs)))
+        return chunks
+
+    def tiff_encode_many(self, rasters, inverts=None, budget_bytes=8 << 30):
+        """``tiff_encode`` over a list of (H, W) / (H, W, 3) uint8 images at once (ecseg_tiff_encode_batch: a wave per strip, the
+        strips of all files side by side) -> the list of their files as ``bytes``, in input order, each what ``tiff_encode`` returns
+        for that image alone.  ``inverts``: one flag per image (default: none inverted).  The images go in one call while the sum of
+        what ecseg_tiff_encode_batch_bytes says each needs stays within ``budget_bytes`` of device scratch, else in several calls over
+        consecutive images; an image that exceeds the budget alone goes alone."""
+        ims = []
+        for img in rasters:
+            im = _u8(img)
+            if im.ndim == 3 and im.shape[2] == 1:
+                im = im[..., 0]
+            if im.ndim not in (2, 3) or (im.ndim == 3 and im.shape[2] != 3) or not im.size:
+                raise ValueError('tiff_encode_many takes non-empty (H, W) or (H, W, 3) uint8 images')
+            ims.append(im)
+        inverts = [False] * len(ims) if inverts is None else [bool(v) for v in inverts]
+        if len(inverts) != len(ims):
+            raise ValueError('tiff_encode_many takes one invert flag per image')
+        rows = [[0, im.shape[0], im.shape[1], 1 if im.ndim == 2 else 3, int(v)] for im, v in zip(ims, inverts)]
+        needs = [self.lib.ecseg_tiff_encode_batch_bytes(_ptr(np.array(r, np.int64)), 1) for r in rows]
+        out = []
+        for lo, hi in self._split_by_budget(needs, budget_bytes):
+            tab, end = np.array(rows[lo:hi], np.int64), 0
+            for k, im in enumerate(ims[lo:hi]):
+                tab[k, 0] = end
+                end += im.size
+            buf = np.empty(end, np.uint8)
+            for k, im in enumerate(ims[lo:hi]):
+                buf[tab[k, 0]:tab[k, 0] + im.size] = im.reshape(-1)
+            files, ranges = self.tiff_encode_packed(buf, tab)
+            out += [files[o:o + n].tobytes() for o, n in ranges.tolist()]
+        return out
+
+    def fish_render_tiff_many(self, items, budget_bytes=8 << 30):
+        """``fish_render_tiff`` over a list of images at once, with the other TIFF files of each image (ecseg_fish_render_tiff_batch):
+        ``items`` is a list of (img, channels, thresholded, boundaries, mask, picture) - the first four as ``fish_render_tiff`` takes
+        them, ``mask`` an (H, W) uint8 raster or None, ``picture`` an (H, W, 3) uint8 raster or None - -> per item the tuple (original,
+        with_segmentation, lsq, mask file or None, picture file or None) of ``bytes``, each what ``fish_render_tiff`` and
+        ``tiff_encode`` return for it alone.  All files of all items of a call go through one batched encode; the items are split
+        into consecutive calls by ``budget_bytes`` of device scratch as ``tiff_encode_many`` splits its list."""
+        prepared, needs = [], []
+        for item in items:
+            img, channels, thresholded, boundaries, mask, picture = item
+            im, thr, bnd = _u8(img), _u8(thresholded), _u8(boundaries)
+            if im.ndim != 3 or thr.ndim != 3 or bnd.ndim != 2 or thr.shape[:2] != im.shape[:2] or bnd.shape != im.shape[:2]:
+                raise ValueError('fish_render_tiff_many takes (H, W, C) images, (H, W, n_probe) masks and (H, W) boundaries of one extent')
+            ch = np.ascontiguousarray(channels, np.int32).reshape(-1)
+            if len(ch) != im.shape[2] or thr.shape[2] != im.shape[2] - 1 or not 3 <= len(ch) <= 4:
+                raise ValueError('fish_render_tiff_many takes one channel index per image channel (blue, green, red[, aqua]) and one mask per probe')
+            H, W = bnd.shape
+            m = None if mask is None else _u8(mask)
+            p = None if picture is None else _u8(picture)
+            if (m is not None and m.shape != (H, W)) or (p is not None and p.shape != (H, W, 3)):
+                raise ValueError('fish_render_tiff_many takes an (H, W) mask and an (H, W, 3) picture of the image\'s extent, or None')
+            prepared.append((im, np.concatenate([ch, np.zeros(4 - len(ch), np.int32)]), thr, bnd, m, p))
+            spps = [3, 3, 3] + ([1] if m is not None else []) + ([3] if p is not None else [])
+            tab, end = [], 0
+            for spp in spps:                                   # as the call places them: every raster on a multiple of 256 bytes
+                tab.append([end, H, W, spp, 0])
+                end += (H * W * spp + 255) // 256 * 256
+            need = self.lib.ecseg_tiff_encode_batch_bytes(_ptr(np.array(tab, np.int64)), len(tab))
+            needs.append(need if need < 0 else need + end + 2 * H * W * im.shape[2] + 3 * 256)
+        out = []
+        for lo, hi in self._split_by_budget(needs, budget_bytes):
+            chunk = prepared[lo:hi]
+            n = len(chunk)
+            shapes = np.array([[c[0].shape[0], c[0].shape[1], c[0].shape[2]] for c in chunk], np.int32)
+            chans = np.ascontiguousarray(np.stack([c[1] for c in chunk]), np.int32)
+            ptrs = lambda col: (C.c_void_p * n)(*[None if c[col] is None else c[col].ctypes.data for c in chunk])
+            cap = 0
+            for c in chunk:
+                H, W = c[3].shape
+                cap += 3 * self.lib.ecseg_tiff_encode_bound(H, W, 3) + (self.lib.ecseg_tiff_encode_bound(H, W, 1) if c[4] is not None else 0) + \
+                    (self.lib.ecseg_tiff_encode_bound(H, W, 3) if c[5] is not None else 0)
+            if cap < 0:
+                raise ValueError('fish_render_tiff_many: an image that cannot be written as a TIFF')
+            files = np.empty(max(cap, 1), np.uint8)
+            ranges = np.zeros((n, 5, 2), np.int64)
+            self._check(self.lib.ecseg_fish_render_tiff_batch(self.h, n, ptrs(0), _ptr(shapes), _ptr(chans), ptrs(2), ptrs(3), ptrs(4), ptrs(5),
+                                                              _ptr(files), cap, _ptr(ranges)), 'ecseg_fish_render_tiff_batch')
+            for i, c in enumerate(chunk):
+                have = (True, True, True, c[4] is not None, c[5] is not None)
+                out.append(tuple(files[o:o + k].tobytes() if h else None for (o, k), h in zip(ranges[i].tolist(), have)))
+        return out
+
     # ---- min-cut splitter -------------------------------------------------------------------------------
-    MIN_CUT_MAX_DIST = 32          # ECSEG_MIN_CUT_MAX_DIST
+    MIN_CUT_MAX_DIST = 32         # ECSEG_MIN_CUT_MAX_DIST
     MIN_CUT_LDS_PIXELS = 10240     # ECSEG_MIN_CUT_LDS_PIXELS
 
     def min_cut(self, tasks, dist):

@@ -6,6 +6,7 @@
 #include "../../include/ecseg_hip.h"
 #include "scratch.h"
 #include "tiff_decode_batch.h"
+#include "tiff_encode_batch.h"
 #include "tiff_frame.h"
 
 namespace ecseg {
@@ -398,6 +399,10 @@ inline TiffEncodeBufs tiff_encode_bufs(Carver& c, int H, int W, int spp, int n_f
 // most three of them; stride > 0: a batch, raster f at img[0] + f * stride (n_files below 65536: grid dimension y is the file).
 struct TiffSources { const uint8_t* img[3]; size_t stride; };
 hipError_t run_tiff_encode(const TiffSources& src, int n_files, int H, int W, int spp, int invert, const TiffEncodeBufs& b, hipStream_t s);
+// Encodes a batch of rasters laid out by te_batch_layout (tiff_encode_batch.h), in one launch per kernel: the strips of all files
+// into b.slots and b.cnt, per file its strip offsets into b.off, where every file image starts into b.base, and the strips into
+// b.packed at base[f] + 8 + off, the gaps for heads and tails left as they are.  b.tab is in place and b.src holds the rasters.
+hipError_t run_tiff_encode_batch(const TiffEncodeBatchBufs& b, const TeBatchLayout& L, hipStream_t s);
 
 // ---- launcher implemented in tiff_decode_kernels.hip (the strips of ecseg_tiff_read, host_io.cpp) -------------------------------
 // Decodes a batch of files laid out by td_batch_layout (tiff_decode_batch.h; a lone file is a batch of one), in one launch per kernel:

@@ -254,6 +254,12 @@ inline bool tiff_args_ok(int H, int W, int spp) {            // what tiff_write_
 }
 int tiff_collect(ecseg_ctx* h, const char* who, int n_files, int H, int W, int spp, const TiffEncodeBufs& b, uint8_t* const* files,
                  long long file_cap, long long* file_bytes, bool strict);
+// The batched encoder's two ends, shared by ecseg_tiff_encode_batch and ecseg_fish_render_tiff_batch (drivers_fish.hip): the table
+// rows ([n][5]: byte offset, H, W, spp, invert) checked and turned into the layout's input, and - behind run_tiff_encode_batch - the
+// file images, back to back in out, with out_ranges[f] = (offset, bytes); too small an out_cap is ECSEG_E_INVALID with nothing written.
+std::string tiff_encode_batch_plan(const int64_t* files, int n_files, long long raster_bytes, std::vector<TeFileIn>& in);
+int tiff_batch_collect(ecseg_ctx* h, const char* who, const TeBatchLayout& L, const TiffEncodeBatchBufs& b, uint8_t* out, long long out_cap,
+                       int64_t* out_ranges);
 // The label PNGs of n images that lie on the device (image i at d_labels + i * H * W), on the main stream: count, code build on the
 // host, emit into count_arena, frame.  *ms: device time of the kernels.
 int png_encode_files(ecseg_ctx* h, const char* who, const uint8_t* d_labels, int n, int H, int W, const PngEncodeBufs& b,

@@ -1,4 +1,4 @@
-// Files coded on the device: the TIFF encoder (tiff_kernels.hip; the host writer is tiff_write_u8, host_io.cpp), the TIFF decoder for
+// Files coded on the device: the TIFF encoder for one raster and for a batch (tiff_kernels.hip; the host writer is tiff_write_u8, host_io.cpp), the TIFF decoder for
 // one file and for a batch (tiff_decode_kernels.hip; the host reader is ecseg_tiff_read), the label PNG encoder (png_kernels.hip;
 // the host writer is ecseg_png_write_labels) and the gray PNG encoder (png_gray_kernels.hip; the host writer is
 // ecseg_png_write_channel), with the tails that ecseg_meta_segment_files and ecseg_fish_render_tiff share.
@@ -47,6 +47,73 @@ int ecseg::tiff_collect(ecseg_ctx* h, const char* who, int n_files, int H, int W
         std::memcpy(files[f] + 8 + data, tail[f].data(), tail[f].size());
     }
     HIP_TRY(h, hipStreamSynchronize(s));
+    return ECSEG_OK;
+}
+
+// The rows of an encode batch's table ([n][5]: byte offset, H, W, spp, invert) as ecseg_tiff_encode judges each raster alone, the
+// ranges by ecseg_min_cut's rule: in order, clear of each other, inside the raster_bytes bytes of the buffer (raster_bytes < 0: no
+// buffer to hold them to).  Empty string and `in`, or what is wrong.
+std::string ecseg::tiff_encode_batch_plan(const int64_t* files, int n_files, long long raster_bytes, std::vector<TeFileIn>& in) {
+    in.assign((size_t)n_files, TeFileIn());
+    long long end = 0;
+    for (int i = 0; i < n_files; ++i) {
+        const int64_t* f = files + 5 * (size_t)i;
+        const std::string who = "file " + std::to_string(i);
+        if (f[1] <= 0 || f[2] <= 0 || f[1] > INT32_MAX || f[2] > INT32_MAX || (f[3] != 1 && f[3] != 3) || !tiff_args_ok((int)f[1], (int)f[2], (int)f[3]))
+            return who + ": the extents must be positive, the samples per pixel 1 or 3 and a line below 2^30 bytes";
+        const long long nb = f[1] * f[2] * f[3];             // (below 2^31 * 2^30)
+        if (f[0] < end || (raster_bytes >= 0 && (f[0] > raster_bytes || nb > raster_bytes - f[0])))
+            return who + ": its raster overlaps the one in front or leaves the " + std::to_string(raster_bytes) + " bytes of rasters";
+        if (f[0] > INT64_MAX - nb) return who + ": its raster ends behind 2^63";
+        end = f[0] + nb;
+        TeFileIn& d = in[(size_t)i];
+        d.src_off = (uint64_t)f[0]; d.H = (uint32_t)f[1]; d.W = (uint32_t)f[2]; d.spp = (uint32_t)f[3]; d.invert = f[4] != 0;
+    }
+    return std::string();
+}
+
+// The strips of a batch are encoded and packed (run_tiff_encode_batch is on the stream): brings the counts, the strip offsets and the
+// files' places over, frames every file and - once it is known that all of them fit out_cap - brings the packed output over in one
+// copy and writes heads and tails into its gaps.  Nothing of out or out_ranges is written before that verdict.
+int ecseg::tiff_batch_collect(ecseg_ctx* h, const char* who, const TeBatchLayout& L, const TiffEncodeBatchBufs& b, uint8_t* out, long long out_cap,
+                              int64_t* out_ranges) {
+    hipStream_t s = h->stream;
+    const size_t nf = L.tab.size();
+    std::vector<uint32_t> cnt((size_t)L.n_strips);
+    std::vector<unsigned long long> off((size_t)L.off_entries), base(nf + 1);
+    HIP_TRY(h, hipMemcpyAsync(cnt.data(), b.cnt, cnt.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipMemcpyAsync(off.data(), b.off, off.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipMemcpyAsync(base.data(), b.base, base.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    std::vector<std::vector<uint8_t>> head(nf), tail(nf);
+    std::vector<uint32_t> offs;
+    for (size_t f = 0; f < nf; ++f) {
+        const TeFile& t = L.tab[f];
+        const unsigned long long* o = off.data() + t.off_off;
+        const uint32_t* m = cnt.data() + t.first_strip;
+        offs.resize(t.n_strips);
+        for (uint32_t k = 0; k < t.n_strips; ++k) {
+            if (8 + o[k] + m[k] + 1 >= 0xffffffffull)
+                return fail(h, ECSEG_E_INVALID, std::string(who) + ": file " + std::to_string(f) + " would pass 4 GiB (classic TIFF has 32-bit offsets)");
+            offs[k] = (uint32_t)(8 + o[k]);
+        }
+        tiff_frame((int)t.H, (int)t.W, (int)t.spp, (int)t.rps, offs.data(), m, (int)t.n_strips, (size_t)(8 + o[t.n_strips]), &head[f], &tail[f]);
+        if (head[f].size() + tail[f].size() != t.frame_bytes || base[f + 1] - base[f] != t.frame_bytes + o[t.n_strips])
+            return fail(h, ECSEG_E_HIP, std::string(who) + ": file " + std::to_string(f) + ": the device placed the file for a frame of another size");
+    }
+    if (base[nf] > (unsigned long long)out_cap)
+        return fail(h, ECSEG_E_INVALID, std::string(who) + ": files of " + std::to_string(base[nf]) + " bytes do not fit the capacity of " +
+                                            std::to_string(out_cap) + " (the sum of ecseg_tiff_encode_bound says what always does)");
+    HIP_TRY(h, hipMemcpyAsync(out, b.packed, (size_t)base[nf], hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    for (size_t f = 0; f < nf; ++f) {
+        uint8_t* file = out + base[f];
+        const size_t data = (size_t)off[L.tab[f].off_off + L.tab[f].n_strips];
+        std::memcpy(file, head[f].data(), 8);
+        std::memcpy(file + 8 + data, tail[f].data(), tail[f].size());
+        out_ranges[2 * f] = (int64_t)base[f];
+        out_ranges[2 * f + 1] = (int64_t)(base[f + 1] - base[f]);
+    }
     return ECSEG_OK;
 }
 
@@ -272,6 +339,45 @@ int ecseg_tiff_encode(ecseg_ctx* h, const uint8_t* img, int H, int W, int spp, i
     HIP_TRY(h, hipMemcpyAsync(b.img, img, (size_t)H * W * spp, hipMemcpyHostToDevice, s));
     TIMED(h, s, 0, 1, HIP_TRY(h, run_tiff_encode(TiffSources{{b.img, nullptr, nullptr}, 0}, 1, H, W, spp, invert, b, s)));
     if ((rc = tiff_collect(h, "tiff_encode", 1, H, W, spp, b, &out, out_cap, out_bytes, true))) return rc;   // (waits for the stream)
+    timed_set(h, 0, 1);
+    return ECSEG_OK;
+}
+
+// ---- the same over a batch of rasters: every strip of every file is a wave of one launch -------------------------------------------
+long long ecseg_tiff_encode_batch_bytes(const int64_t* files, int n_files) {
+    if (n_files == 0) return 0;
+    if (n_files < 0 || n_files >= 65536 || !files) return -1;
+    std::vector<TeFileIn> in;
+    TeBatchLayout L;
+    if (!tiff_encode_batch_plan(files, n_files, -1, in).empty() || !te_batch_layout(in, L).empty()) return -1;
+    Carver c;
+    (void)tiff_encode_batch_bufs(c, L, true);
+    return (long long)c.used;
+}
+
+int ecseg_tiff_encode_batch(ecseg_ctx* h, const uint8_t* rasters, long long raster_bytes, const int64_t* files, int n_files, uint8_t* out,
+                            long long out_cap, int64_t* out_ranges) {
+    DRIVER_OPEN(h);
+    const std::string me = "tiff_encode_batch: ";
+    if (n_files < 0 || raster_bytes < 0 || out_cap < 0 || (n_files > 0 && (!rasters || !files || !out || !out_ranges)))
+        return fail(h, ECSEG_E_INVALID, me + "bad arguments");
+    if (n_files >= 65536) return fail(h, ECSEG_E_INVALID, me + "65536 files or more");
+    clear_timings(h);
+    if (n_files == 0) return ECSEG_OK;
+    std::vector<TeFileIn> in;
+    TeBatchLayout L;
+    std::string bad = tiff_encode_batch_plan(files, n_files, raster_bytes, in);
+    if (bad.empty()) bad = te_batch_layout(in, L);
+    if (!bad.empty()) return fail(h, ECSEG_E_INVALID, me + bad);
+    USE_DEVICE(h);
+    int rc;
+    TiffEncodeBatchBufs b{};
+    if ((rc = lay_out(h, h->call_arena, [&](Carver& c) { b = tiff_encode_batch_bufs(c, L, true); }))) return rc;
+    hipStream_t s = h->stream;
+    HIP_TRY(h, hipMemcpyAsync(b.src, rasters + L.src_base, (size_t)L.src_span, hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(b.tab, L.tab.data(), L.tab.size() * sizeof(TeFile), hipMemcpyHostToDevice, s));
+    TIMED(h, s, 0, 1, HIP_TRY(h, run_tiff_encode_batch(b, L, s)));
+    if ((rc = tiff_batch_collect(h, "tiff_encode_batch", L, b, out, out_cap, out_ranges))) return rc;   // (waits for the stream: L lives until here)
     timed_set(h, 0, 1);
     return ECSEG_OK;
 }

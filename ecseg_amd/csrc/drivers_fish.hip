@@ -177,6 +177,84 @@ int ecseg_fish_render_tiff(ecseg_ctx* h, const uint8_t* img, int H, int W, int C
     return ECSEG_OK;
 }
 
+// the same for n images, with up to two further rasters per image (the mask, (H, W); the min-cut picture, (H, W, 3)) encoded beside the
+// three rendered ones: every file of every image goes through ONE batched encode (tiff_encode_batch.h)
+int ecseg_fish_render_tiff_batch(ecseg_ctx* h, int n_images, const uint8_t* const* imgs, const int32_t* shapes, const int32_t* channels,
+                                 const uint8_t* const* thresholded, const uint8_t* const* boundaries, const uint8_t* const* masks,
+                                 const uint8_t* const* pictures, uint8_t* out, long long out_cap, int64_t* out_ranges) {
+    DRIVER_OPEN(h);
+    const std::string me = "fish_render_tiff_batch: ";
+    if (n_images < 0 || out_cap < 0 || (n_images > 0 && (!imgs || !shapes || !channels || !thresholded || !boundaries || !out || !out_ranges)))
+        return fail(h, ECSEG_E_INVALID, me + "bad arguments");
+    if ((long long)n_images * 5 >= 65536) return fail(h, ECSEG_E_INVALID, me + "65536 files or more");
+    clear_timings(h);
+    if (n_images == 0) return ECSEG_OK;
+    const size_t n = (size_t)n_images;
+    // one device buffer holds, per image, the inputs and the rasters that are encoded, every one on a multiple of 256 bytes
+    struct Place { size_t img, thr, bnd, file[5]; bool has[5]; int ch[4]; };
+    std::vector<Place> at(n);
+    std::vector<int64_t> rows;
+    size_t work = 0;
+    auto take = [&](size_t bytes) { const size_t o = work; work += (bytes + 255) / 256 * 256; return o; };
+    int rc;
+    for (size_t i = 0; i < n; ++i) {
+        const int H = shapes[3 * i], W = shapes[3 * i + 1], C = shapes[3 * i + 2];
+        Place& p = at[i];
+        if ((rc = fish_render_check(h, imgs[i], H, W, C, channels + 4 * i, thresholded[i], C - 1, boundaries[i], p.ch))) return rc;
+        if (!tiff_args_ok(H, W, 3)) return fail(h, ECSEG_E_INVALID, me + "the TIFF writer takes lines below 2^30 bytes");
+        const size_t px = (size_t)H * W;
+        p.img = take(px * C); p.thr = take(px * (C - 1)); p.bnd = take(px);
+        for (int k = 0; k < 5; ++k) {
+            const int spp = k == 3 ? 1 : 3;
+            p.has[k] = k < 3 || (k == 3 ? masks && masks[i] : pictures && pictures[i]);
+            if (!p.has[k]) continue;
+            p.file[k] = take(px * spp);
+            const int64_t row[5] = {(int64_t)p.file[k], H, W, spp, 0};
+            rows.insert(rows.end(), row, row + 5);
+        }
+    }
+    const int n_files = (int)(rows.size() / 5);
+    std::vector<TeFileIn> in;
+    TeBatchLayout L;
+    std::string bad = tiff_encode_batch_plan(rows.data(), n_files, (long long)work, in);
+    if (bad.empty()) bad = te_batch_layout(in, L);
+    if (!bad.empty()) return fail(h, ECSEG_E_INVALID, me + bad);
+    USE_DEVICE(h);
+    uint8_t* d = nullptr;
+    TiffEncodeBatchBufs b{};
+    if ((rc = lay_out(h, h->call_arena, [&](Carver& c) { d = c.take<uint8_t>(work); b = tiff_encode_batch_bufs(c, L, false); }))) return rc;
+    b.src = d + L.src_base;                                  // (the table's offsets count from the first raster)
+    hipStream_t s = h->stream;
+    for (size_t i = 0; i < n; ++i) {
+        const size_t px = (size_t)shapes[3 * i] * shapes[3 * i + 1], C = (size_t)shapes[3 * i + 2];
+        HIP_TRY(h, hipMemcpyAsync(d + at[i].img, imgs[i], px * C, hipMemcpyHostToDevice, s));
+        HIP_TRY(h, hipMemcpyAsync(d + at[i].thr, thresholded[i], px * (C - 1), hipMemcpyHostToDevice, s));
+        HIP_TRY(h, hipMemcpyAsync(d + at[i].bnd, boundaries[i], px, hipMemcpyHostToDevice, s));
+        if (at[i].has[3]) HIP_TRY(h, hipMemcpyAsync(d + at[i].file[3], masks[i], px, hipMemcpyHostToDevice, s));
+        if (at[i].has[4]) HIP_TRY(h, hipMemcpyAsync(d + at[i].file[4], pictures[i], px * 3, hipMemcpyHostToDevice, s));
+    }
+    HIP_TRY(h, hipMemcpyAsync(b.tab, L.tab.data(), L.tab.size() * sizeof(TeFile), hipMemcpyHostToDevice, s));
+    TIMED(h, s, 0, 1,
+          for (size_t i = 0; i < n; ++i) {
+              const Place& p = at[i];
+              const FishRenderBufs r{d + p.img, d + p.thr, d + p.bnd, d + p.file[0], d + p.file[1], d + p.file[2]};
+              HIP_TRY(h, run_fish_render(shapes[3 * i], shapes[3 * i + 1], shapes[3 * i + 2], p.ch, r, s));
+          }
+          HIP_TRY(h, run_tiff_encode_batch(b, L, s)));
+    std::vector<int64_t> ranges(2 * (size_t)n_files);
+    if ((rc = tiff_batch_collect(h, "fish_render_tiff_batch", L, b, out, out_cap, ranges.data()))) return rc;   // (waits for the stream)
+    timed_set(h, 0, 1);
+    size_t f = 0;
+    for (size_t i = 0; i < n; ++i)
+        for (int k = 0; k < 5; ++k) {
+            int64_t* q = out_ranges + 2 * (5 * i + k);
+            q[0] = at[i].has[k] ? ranges[2 * f] : 0;
+            q[1] = at[i].has[k] ? ranges[2 * f + 1] : 0;
+            f += at[i].has[k];
+        }
+    return ECSEG_OK;
+}
+
 // ---- the min-cut splitter's max-flow tasks (src/max_flow_binary_mask.py:59-116) ------------------------------------------------
 int ecseg_min_cut(ecseg_ctx* h, const uint8_t* masks, long long mask_bytes, const int32_t* tasks, int n_tasks, int dist, uint8_t* side,
                   int32_t* flow) {

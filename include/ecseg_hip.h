@@ -61,6 +61,8 @@ extern "C" {
  * the tests of the kernels between the labelling passes; nothing existing changed.) */
 /* (still 5 - additive: ecseg_png_channel_encode, ecseg_png_channel_bound and ecseg_overlay_files, `make meta_overlay`'s red and green
  * PNGs encoded on the device; nothing existing changed.) */
+/* (still 5 - additive: ecseg_tiff_encode_batch, ecseg_tiff_encode_batch_bytes and ecseg_fish_render_tiff_batch, the TIFF files of many
+ * stat_fish images encoded in one device call, a wave per strip of any file; nothing existing changed.) */
 #define ECSEG_ABI_VERSION 5
 
 #define ECSEG_OK             0
@@ -446,6 +448,32 @@ int ecseg_tiff_encode(ecseg_ctx* h, const uint8_t* img, int H, int W, int spp, i
 int ecseg_fish_render_tiff(ecseg_ctx* h, const uint8_t* img, int H, int W, int C, const int32_t* channels, const uint8_t* thresholded,
                            int n_probe, const uint8_t* boundaries, uint8_t* const* files, long long file_cap, long long* file_bytes,
                            uint8_t* original, uint8_t* with_segmentation, uint8_t* lsq);
+/* ecseg_tiff_encode over n_files rasters in one call (csrc/tiff_kernels.hip, the tiffb_* kernels; csrc/tiff_encode_batch.h): the
+ * strips of all files are one grid, a wave per strip, so a file of few strips runs beside the others instead of leaving the device
+ * idle.  rasters: raster_bytes of host memory; files[5 i ..] = byte offset, H, W, spp, invert of raster i, the rasters in ascending
+ * order and clear of each other (gaps are allowed).  The files may differ in extent, spp (1 or 3) and invert.  out receives the file
+ * images back to back, file i at out + out_ranges[2 i] with out_ranges[2 i + 1] bytes, each byte for byte what ecseg_tiff_encode
+ * returns for that raster alone.  The sum of ecseg_tiff_encode_bound over the files always suffices as out_cap.  ECSEG_E_INVALID,
+ * with no byte of out or out_ranges written: a null pointer, n_files < 0 or >= 65536, a row ecseg_tiff_encode refuses, a raster that
+ * overlaps the one in front or leaves raster_bytes, 2^31 strips or more in all, files that do not fit out_cap.  n_files == 0 is
+ * ECSEG_OK and does nothing.  One synchronous call: one upload of the span of the rasters, the table beside it, one copy back of all
+ * file images; scratch from the handle's call arena (ecseg_tiff_encode_batch_bytes: its size for such a table, negative for a table
+ * the call refuses; no device work); device time of the kernels in ECSEG_T_COUNT. */
+int ecseg_tiff_encode_batch(ecseg_ctx* h, const uint8_t* rasters, long long raster_bytes, const int64_t* files /* [n][5] offset, H, W, spp, invert */,
+                            int n_files, uint8_t* out, long long out_cap, int64_t* out_ranges /* [n][2] offset, n_bytes */);
+long long ecseg_tiff_encode_batch_bytes(const int64_t* files, int n_files);
+/* ecseg_fish_render_tiff over n_images images in one call, with up to two further rasters per image encoded beside the three rendered
+ * ones: image i has shapes[3 i ..] = H, W, C, channels[4 i ..] (C of them read), imgs[i], thresholded[i] ((H, W, C - 1)) and
+ * boundaries[i] as ecseg_fish_render takes them, masks[i] ((H, W), one sample) and pictures[i] ((H, W, 3)), each null for "none"
+ * (masks or pictures itself null: none for any image).  The rendered rasters never leave the device and ALL files of all images go
+ * through one batched encode.  out receives the file images back to back; out_ranges[10 i + 2 k ..] = offset, bytes of file k of
+ * image i, k = 0 .. 4: _original, _original_with_segmentation, _lsq_, the mask, the picture ((0, 0) for a raster that was not given),
+ * each what ecseg_fish_render_tiff and ecseg_tiff_encode return for it alone.  Argument rules are those calls'; ECSEG_E_INVALID leaves
+ * out and out_ranges unwritten, n_images == 0 is ECSEG_OK and does nothing.  Device time of all kernels in ECSEG_T_COUNT. */
+int ecseg_fish_render_tiff_batch(ecseg_ctx* h, int n_images, const uint8_t* const* imgs, const int32_t* shapes /* [n][3] H, W, C */,
+                                 const int32_t* channels /* [n][4] */, const uint8_t* const* thresholded, const uint8_t* const* boundaries,
+                                 const uint8_t* const* masks, const uint8_t* const* pictures, uint8_t* out, long long out_cap,
+                                 int64_t* out_ranges /* [n][5][2] offset, n_bytes */);
 
 /* ---- TIFF files decoded on the device ---------------------------------------------------------------------------------------- */
 /* skimage.io.imread of a baseline TIFF (src/utils.py:110) from a file image in memory, with every strip decoded on the device

@@ -1,7 +1,7 @@
 """Timing of ``make stat_fish`` on synthetic full-size scenes.
 
     python tools/time_stat_fish.py [--images 16] [--reps 5] [--cpu-workers 16] [--channels 4] [--main-passes 3]
-                                   [--tiff-on-device off|on|alternate] [--tiff-read-on-device off|on|alternate] [--tiff-read-batch K] [--no-cpu-baseline]
+                                   [--tiff-on-device off|on|alternate] [--tiff-read-on-device off|on|alternate] [--tiff-read-batch K] [--tiff-write-batch K] [--no-cpu-baseline]
 
 Per 1040 x 1392 scene with 300 nuclei (tests/stat_fish_cases.py ``full_size_scene``) it reports
   * device milliseconds per image of ecseg_fish_spots (ECSEG_T_COUNT: the kernels alone), of the nucleus labelling in front of
@@ -18,6 +18,10 @@ Per 1040 x 1392 scene with 300 nuclei (tests/stat_fish_cases.py ``full_size_scen
     stage of ``process_image`` per image is reported beside the write stage;
   * with ``--tiff-read-batch K`` (K above 1) ``tiff_read_on_device: true`` holds throughout and ``tiff_read_batch`` 1 and K alternate,
     twice (``main_by_read_batch``); the read stage then includes the chunks that ``main()`` reads ahead;
+  * with ``--tiff-write-batch K`` (K above 1) ``tiff_on_device: true`` holds throughout - and the read keys as given, ``--tiff-read-batch``
+    as a fixed value - and ``tiff_write_batch`` 1 and K alternate, twice (``main_by_write_batch``); the write stage then includes the
+    chunks that ``main()`` writes, and ``encode_kernel_ms_per_image`` is ECSEG_T_COUNT of the encoding calls (``fish_render_tiff`` and
+    ``tiff_encode``, or ``fish_render_tiff_many``) per image;
   * the same scenes through the vectorised numpy / scipy restatement tests/stat_fish_ref.py ``records`` on one core and on a
     pool of --cpu-workers processes, as the baseline.
 With ``--channels 4`` the scenes are four-channel ``.npy`` images (blue, green, red and an aqua channel made of the green one shifted
@@ -59,6 +63,7 @@ def main():
     ap.add_argument('--tiff-on-device', choices=('off', 'on', 'alternate'), default='off')
     ap.add_argument('--tiff-read-on-device', choices=('off', 'on', 'alternate'), default='off')
     ap.add_argument('--tiff-read-batch', type=int, default=1, help='with --tiff-read-on-device on: tiff_read_batch 1 and this value alternate, twice')
+    ap.add_argument('--tiff-write-batch', type=int, default=1, help='with tiff_on_device on: tiff_write_batch 1 and this value alternate, twice')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     a = ap.parse_args()
     import yaml
@@ -132,12 +137,19 @@ def main():
         seen = {}
         process_image = stat_fish.process_image
 
-        def spy(*args, **kw):                                # main()'s stage times: it hands every image the same dict
-            r = process_image(*args, **kw)
-            seen.update(kw['stats'])
-            return r
+        def spy(*args, **kw):                                # main()'s stage times: it hands every image the same dict, and adds its flushes to it
+            seen['stats'] = kw['stats']
+            return process_image(*args, **kw)
 
-        def passes(key, read_key=False, read_batch=1):
+        encode_ms = []
+        for name in ('fish_render_tiff', 'tiff_encode', 'fish_render_tiff_many'):     # ECSEG_T_COUNT of every encoding call of main()
+            def timed(*args, _call=getattr(gpu, name), **kw):
+                r = _call(*args, **kw)
+                encode_ms.append(gpu.timings()['count'])
+                return r
+            setattr(gpu, name, timed)
+
+        def passes(key, read_key=False, read_batch=1, write_batch=1):
             """One warm-up pass (arenas, page cache) and --main-passes timed ones -> images/s of each, write stage ms per image."""
             cfg = {'stat_fish': {'inpath': inp, 'scale': 1, 'use_min_cut': False, 'nuclei_size_T': 5000}}
             if key:
@@ -146,27 +158,42 @@ def main():
                 cfg['stat_fish']['tiff_read_on_device'] = True
             if read_batch > 1:
                 cfg['stat_fish']['tiff_read_batch'] = read_batch
+            if write_batch > 1:
+                cfg['stat_fish']['tiff_write_batch'] = write_batch
             with open(os.path.join(tmp, 'config.yaml'), 'w') as f:
                 yaml.safe_dump(cfg, f)
-            rates, writes, stage_reads = [], [], []
+            rates, writes, stage_reads, encodes = [], [], [], []
             for rep in range(a.main_passes + 1):
                 t0 = time.perf_counter()
+                del encode_ms[:]
                 stat_fish.main([], handle=gpu)
                 if rep:
                     rates.append(a.images / (time.perf_counter() - t0))
-                    writes.append(seen['write'] * 1e3 / a.images)
-                    stage_reads.append(seen['read'] * 1e3 / a.images)
+                    writes.append(seen['stats']['write'] * 1e3 / a.images)
+                    stage_reads.append(seen['stats']['read'] * 1e3 / a.images)
+                    encodes.append(sum(encode_ms) / a.images)
                 seen.clear()
-            return rates, writes, stage_reads
+            return rates, writes, stage_reads, encodes
 
-        def summary(rates, writes, stage_reads):
+        def summary(rates, writes, stage_reads, encodes):
             return dict(main_images_per_s=statistics.median(rates), main_images_per_s_min=min(rates), main_images_per_s_max=max(rates),
-                        write_stage_ms_per_image=statistics.median(writes), read_stage_ms_per_image=statistics.median(stage_reads))
+                        write_stage_ms_per_image=statistics.median(writes), read_stage_ms_per_image=statistics.median(stage_reads),
+                        encode_kernel_ms_per_image=statistics.median(encodes))
         cwd = os.getcwd()
         os.chdir(tmp)
         stat_fish.process_image = spy
         try:
-            if a.tiff_read_batch > 1:                             # the read key on throughout, tiff_read_batch 1 and K alternating, twice
+            if a.tiff_write_batch > 1:                            # tiff_on_device on throughout, tiff_write_batch 1 and K alternating, twice
+                r_on = a.tiff_read_on_device == 'on'
+                out['main_by_write_batch'] = [dict(tiff_on_device=True, tiff_read_on_device=r_on, tiff_read_batch=a.tiff_read_batch if r_on else 1,
+                                                   tiff_write_batch=k, **summary(*passes(True, r_on, a.tiff_read_batch if r_on else 1, k)))
+                                              for k in (1, a.tiff_write_batch, 1, a.tiff_write_batch)]
+                ones = [r for r in out['main_by_write_batch'] if r['tiff_write_batch'] == 1]
+                many = [r for r in out['main_by_write_batch'] if r['tiff_write_batch'] > 1]
+                out['max_1_below_min_k'] = max(r['main_images_per_s_max'] for r in ones) < min(r['main_images_per_s_min'] for r in many)
+                out['max_k_below_min_1'] = max(r['main_images_per_s_max'] for r in many) < min(r['main_images_per_s_min'] for r in ones)
+                out.update(ones[0])
+            elif a.tiff_read_batch > 1:                           # the read key on throughout, tiff_read_batch 1 and K alternating, twice
                 w = a.tiff_on_device == 'on'
                 out['main_by_read_batch'] = [dict(tiff_on_device=w, tiff_read_on_device=True, tiff_read_batch=k, **summary(*passes(w, True, k)))
                                              for k in (1, a.tiff_read_batch, 1, a.tiff_read_batch)]
