@@ -63,5 +63,15 @@ asan_png_gray:
 	    ecseg_amd/csrc/host_codec.cpp ecseg_amd/csrc/host_io.cpp tools/asan/png_gray_fuzz.cpp -lz -o /tmp/ecseg_png_gray_fuzz
 	/tmp/ecseg_png_gray_fuzz
 
+# and for interSeg's classifiers on the device: the per-element function of the ecSeg-c input and the selection and chunk planning
+# of ecseg_classify_nucleus_crops (csrc/iseg_classify.h, the text the kernel and the driver compile); tests/test_iseg_classify.py
+# builds and runs it, and holds its output to numpy and to classify_crops' rules.  ISEG_CHECK: where the program is put
+ISEG_CHECK ?= /tmp/ecseg_iseg_classify_check
+.PHONY: asan_iseg_classify
+asan_iseg_classify:
+	g++ -std=c++17 -O1 -g -fno-omit-frame-pointer -ffp-contract=off -fsanitize=address,undefined -fno-sanitize-recover=all \
+	    tools/asan/iseg_classify_check.cpp -o $(ISEG_CHECK)
+	$(ISEG_CHECK)
+
 clean:
 	rm -rf __pycache__ ecseg_amd/csrc/*.o ecseg_amd/libecseg_*.so

@@ -28,6 +28,7 @@ EXPORTS = [
     'ecseg_meta_segment_tiffs', 'ecseg_meta_segment_tiffs_files', 'ecseg_prefetch_tiffs', 'ecseg_get_read_timings',
     'ecseg_png_channel_bound', 'ecseg_png_channel_encode', 'ecseg_overlay_files',
     'ecseg_tiff_encode_batch', 'ecseg_tiff_encode_batch_bytes', 'ecseg_fish_render_tiff_batch',
+    'ecseg_classify_nucleus_crops', 'ecseg_iseg_classifier_inputs_debug',
 ]
 
 
@@ -137,6 +138,8 @@ def load_library():
     lib.ecseg_overlay.argtypes = [vp, u8p, u8p, i32, i32, i32, i32, i32, i32, vp]
     lib.ecseg_nuclei_regions.argtypes = [vp, u8p, i32, i32, u8p, i32, i32, i32, i32, i32, vp, C.POINTER(C.c_int32)]
     lib.ecseg_nucleus_crops.argtypes = [vp, vp, i32, vp, vp, vp]
+    lib.ecseg_classify_nucleus_crops.argtypes = [vp, vp, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp]
+    lib.ecseg_iseg_classifier_inputs_debug.argtypes = [vp, vp, i32, vp, vp, i32, vp, i32, vp, vp]
     lib.ecseg_fish_distances.argtypes = [vp, vp, i32, i32, u8p, i32, i32, i32, i32, vp, C.POINTER(C.c_int32)]
     lib.ecseg_fish_spots.argtypes = [vp, vp, i32, i32, u8p, i32, vp, i32, vp, i32, C.c_double, vp, i32, i32, i32, vp, vp, vp,
                                      C.POINTER(C.c_int32)]
@@ -798,6 +801,50 @@ class Handle:
         mx = np.zeros((len(d), 3), np.int32)
         self._check(self.lib.ecseg_nucleus_crops(self.h, _ptr(d), len(d), _ptr(order), _ptr(out), _ptr(mx)), 'ecseg_nucleus_crops')
         return out, mx
+
+    def classify_nucleus_crops(self, desc, order, from_patches, centromeric, model_i, model_c=None, want_crops=False, pred_i=None,
+                               pred_c=None):
+        """The crops of ``nucleus_crops`` through the two classifiers without leaving the device (ecseg_classify_nucleus_crops).
+        ``from_patches``: a bool or one per crop; ``centromeric``: ecSeg-c applies to this image; ``model_i`` / ``model_c``: a
+        ``Handle`` with the plan loaded, or an object holding one as ``.handle`` (``model_i`` may be this handle's own).  Returns
+        (channel_max int32 (N, 3), pred_i float32 (N, 3), ran_i bool (N), pred_c float32 (N), ran_c bool (N)[, crops uint8
+        (N, 256, 256, 3) with ``want_crops``]); the rows of ``pred_i`` / ``pred_c`` whose ``ran_*`` is false are not written - zeros,
+        or what the arrays given as ``pred_i`` / ``pred_c`` held."""
+        d = np.ascontiguousarray(desc, np.int32).reshape(-1, 5)
+        n = len(d)
+        order = np.ascontiguousarray(order, np.int32)
+        if order.shape != (3,):
+            raise ValueError('channel order must hold 3 channels')
+        fp = np.ascontiguousarray(np.broadcast_to(np.asarray(from_patches, bool), (n,))).view(np.uint8)
+        hi = getattr(model_i, 'handle', model_i)
+        hc = getattr(model_c, 'handle', model_c)
+        mx = np.zeros((n, 3), np.int32)
+        pi = np.zeros((n, 3), np.float32) if pred_i is None else pred_i
+        pc = np.zeros(n, np.float32) if pred_c is None else pred_c
+        for a, shape in ((pi, (n, 3)), (pc, (n,))):
+            if a.dtype != np.float32 or a.shape != shape or not a.flags.c_contiguous:
+                raise ValueError('pred_i / pred_c must be C-contiguous float32 arrays of shape (N, 3) / (N,)')
+        ri, rc = np.zeros(n, np.uint8), np.zeros(n, np.uint8)
+        crops = np.empty((n, 256, 256, 3), np.uint8) if want_crops else None
+        self._check(self.lib.ecseg_classify_nucleus_crops(self.h, hi.h, hc.h if hc is not None else None, _ptr(d), n, _ptr(order), _ptr(fp),
+                                                          int(bool(centromeric)), _ptr(mx), _ptr(pi), _ptr(ri), _ptr(pc), _ptr(rc), _ptr(crops)),
+                    'ecseg_classify_nucleus_crops')
+        out = (mx, pi, ri.view(bool), pc, rc.view(bool))
+        return out + (crops,) if want_crops else out
+
+    def iseg_classifier_inputs(self, crops, channel_max, sel_i, sel_c):
+        """The input kernel of ``classify_nucleus_crops`` alone, for its tests (ecseg_iseg_classifier_inputs_debug): uint8 (k, 256, 256, 3)
+        crops with their (k, 3) maxima and two lists of crop indices -> (float32 (len(sel_i), 256, 256, 1), float32 (len(sel_c), 256,
+        256, 3))."""
+        c = _u8(crops)
+        if c.ndim != 4 or c.shape[1:] != (256, 256, 3):
+            raise ValueError('crops must be (k, 256, 256, 3) uint8')
+        mx = np.ascontiguousarray(channel_max, np.int32).reshape(len(c), 3)
+        si, sc = np.ascontiguousarray(sel_i, np.int32).reshape(-1), np.ascontiguousarray(sel_c, np.int32).reshape(-1)
+        oi, oc = np.empty((len(si), 256, 256, 1), np.float32), np.empty((len(sc), 256, 256, 3), np.float32)
+        self._check(self.lib.ecseg_iseg_classifier_inputs_debug(self.h, _ptr(c), len(c), _ptr(mx), _ptr(si), len(si), _ptr(sc), len(sc), _ptr(oi),
+                                                                _ptr(oc)), 'ecseg_iseg_classifier_inputs_debug')
+        return oi, oc
 
     # ---- fish_distance_calculation -----------------------------------------------------------------------
     def fish_distances(self, labels, lsq, fish_channel, centromere_channel, capacity=4096):

@@ -305,6 +305,20 @@ hipError_t run_nuclei_regions(const uint8_t* seg, const uint8_t* img, int H, int
 hipError_t run_nucleus_crops(const int32_t* labels, const uint8_t* img, int W, int img_w, int C, const int32_t* desc, int n,
                              const int order[3], uint8_t* out, int32_t* chmax, hipStream_t s);
 
+// ---- launcher implemented in iseg_classify_kernels.hip (the classifiers' inputs; arithmetic and selection rules in iseg_classify.h) ----
+// Device buffers of ecseg_classify_nucleus_crops for chunks of n crops: run_nucleus_crops' own and the two lists of chosen crops.
+struct ClassifyBufs { CropBufs crop; int32_t* sel_i; int32_t* sel_c; };
+inline ClassifyBufs classify_bufs(Carver& c, int n) {
+    ClassifyBufs b;
+    b.crop = crop_bufs(c, n); b.sel_i = c.take<int32_t>((size_t)n); b.sel_c = c.take<int32_t>((size_t)n);
+    return b;
+}
+// crops: (k, 256, 256, 3) uint8 with chmax (k, 3); sel_i / sel_c: n_i / n_c crop indices in [0, k), in any order, repeats allowed.
+// out_i (n_i, 256, 256, 1) float32 = (float) of channel 0 of crop sel_i[j]; out_c (n_c, 256, 256, 3) float32 = preprocess_ecseg_c of
+// crop sel_c[j] (iseg_c_value with the crop's own maxima).  Both 16-byte aligned; either list may be empty (its pointers unused).
+hipError_t run_iseg_classifier_inputs(const uint8_t* crops, const int32_t* chmax, const int32_t* sel_i, int n_i, const int32_t* sel_c,
+                                      int n_c, float* out_i, float* out_c, hipStream_t s);
+
 // ---- launchers implemented in fishdist_kernels.hip (src/fish_distance_calculation.py:16-46) ---------------------------------
 // The dense cell index of one H x W label map, shared with fishspot_kernels.hip: rid, its scan blocks blk and the counters misc,
 // with the label map lab and the C-channel image img they belong to.

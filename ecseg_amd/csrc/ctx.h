@@ -300,6 +300,7 @@ int ensure_split_images(ecseg_ctx* h);
 int ensure_patches(ecseg_ctx* h, int n);
 int windows_per_group(const ecseg_ctx* h);
 int run_plan(ecseg_ctx* h, int n_all, StitchPlan* crop = nullptr, const std::vector<LaneSpec>* lanes = nullptr);
+int run_plan_to_host(ecseg_ctx* h, int ni, float* out);   // run_plan on a filled input tensor + the outputs' copy, stream not waited for
 void prof_begin(ecseg_ctx* h);
 void prof_end(ecseg_ctx* h);    // stream must be idle
 

@@ -1,6 +1,7 @@
 // The interSeg drivers (src/interseg.py:113-235; kernels in interseg_kernels.hip): the regions of a nucleus mask, which leave their
 // label map and image on the handle, and the crops cut from those.
 #include "driver_util.h"
+#include "iseg_classify.h"
 
 using namespace ecseg;
 
@@ -45,26 +46,46 @@ int ecseg_nuclei_regions(ecseg_ctx* h, const uint8_t* seg, int H, int W, const u
     return ECSEG_OK;
 }
 
+// The descriptors and the channel order of ecseg_nucleus_crops / ecseg_classify_nucleus_crops (`who`) against the region map on the
+// handle; order: channel_order, checked.
+static int check_crops(ecseg_ctx* h, const std::string& who, const int32_t* crops, int n_crops, const int32_t* channel_order, int order[3]) {
+    if (h->iseg_n < 0) return fail(h, ECSEG_E_INVALID, who + ": no region map on the handle (call ecseg_nuclei_regions first)");
+    for (int c = 0; c < 3; ++c) {
+        order[c] = channel_order[c];
+        if (order[c] < 0 || order[c] >= h->iseg_C) return fail(h, ECSEG_E_INVALID, who + ": channel_order out of range");
+    }
+    for (int k = 0; k < n_crops; ++k) {
+        const int32_t* d = crops + (size_t)k * 5;
+        if (d[0] < 0 || d[0] >= h->iseg_n || d[1] < 0 || d[2] < 0 || d[3] < 1 || d[3] > 256 || d[4] < 1 || d[4] > 256 ||
+            d[1] > h->iseg_H - d[3] || d[2] > h->iseg_W - d[4])
+            return fail(h, ECSEG_E_INVALID, who + ": crop " + std::to_string(k) + " is not a 1..256 x 1..256 window of a region");
+    }
+    return ECSEG_OK;
+}
+
+// Empty, or why `m` cannot serve as the classifier `name`: a loaded plan from compact (256, 256, c_in) patches to n_out values.
+static std::string classifier_plan_error(const ecseg_ctx* m, const char* name, int c_in, int n_out) {
+    const std::string who = std::string("classify_nucleus_crops: the ") + name + " handle ";
+    if (!m->has_model) return who + "has no model loaded";
+    const ecseg_tensor_desc& ti = m->tensors[m->input_tensor];
+    const ecseg_tensor_desc& to = m->tensors[m->output_tensor];
+    if (ti.h != 256 || ti.w != 256 || ti.c != c_in || ti.c_stride != ti.c || ti.c_offset != 0 || to.h != 1 || to.w != 1 || to.c != n_out)
+        return who + "holds a plan from (" + std::to_string(ti.h) + ", " + std::to_string(ti.w) + ", " + std::to_string(ti.c) + ") to " +
+               std::to_string((long long)to.h * to.w * to.c) + " values; " + name + " takes (256, 256, " + std::to_string(c_in) + ") and yields " +
+               std::to_string(n_out);
+    return std::string();
+}
+
 int ecseg_nucleus_crops(ecseg_ctx* h, const int32_t* crops, int n_crops, const int32_t* channel_order, uint8_t* out,
                         int32_t* channel_max) {
     DRIVER_OPEN(h);
     if (n_crops < 0 || (n_crops > 0 && (!crops || !channel_order || !out || !channel_max)))
         return fail(h, ECSEG_E_INVALID, "nucleus_crops: bad arguments");
     if (n_crops == 0) return ECSEG_OK;
-    if (h->iseg_n < 0) return fail(h, ECSEG_E_INVALID, "nucleus_crops: no region map on the handle (call ecseg_nuclei_regions first)");
     int order[3];
-    for (int c = 0; c < 3; ++c) {
-        order[c] = channel_order[c];
-        if (order[c] < 0 || order[c] >= h->iseg_C) return fail(h, ECSEG_E_INVALID, "nucleus_crops: channel_order out of range");
-    }
-    for (int k = 0; k < n_crops; ++k) {
-        const int32_t* d = crops + (size_t)k * 5;
-        if (d[0] < 0 || d[0] >= h->iseg_n || d[1] < 0 || d[2] < 0 || d[3] < 1 || d[3] > 256 || d[4] < 1 || d[4] > 256 ||
-            d[1] > h->iseg_H - d[3] || d[2] > h->iseg_W - d[4])
-            return fail(h, ECSEG_E_INVALID, "nucleus_crops: crop " + std::to_string(k) + " is not a 1..256 x 1..256 window of a region");
-    }
+    if (int rc = check_crops(h, "nucleus_crops", crops, n_crops, channel_order, order)) return rc;
     USE_DEVICE(h);
-    const int chunk = 256;                                   // 48 MiB of crops per launch
+    const int chunk = ISEG_CHUNK;                            // 48 MiB of crops per launch
     const size_t crop_bytes = (size_t)256 * 256 * 3;
     const int nc = std::min(n_crops, chunk);
     int rc;
@@ -80,6 +101,128 @@ int ecseg_nucleus_crops(ecseg_ctx* h, const int32_t* crops, int n_crops, const i
         HIP_TRY(h, hipMemcpyAsync(channel_max + (size_t)k0 * 3, b.max, (size_t)k * 3 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
         WAIT_ADD(h, s, 0, 1);
     }
+    return ECSEG_OK;
+}
+
+int ecseg_classify_nucleus_crops(ecseg_ctx* h, ecseg_ctx* model_i, ecseg_ctx* model_c, const int32_t* crops, int n_crops,
+                                 const int32_t* channel_order, const uint8_t* from_patches, int centromeric, int32_t* channel_max,
+                                 float* pred_i, uint8_t* ran_i, float* pred_c, uint8_t* ran_c, uint8_t* crops_out) {
+    DRIVER_OPEN(h);
+    if (!model_i) return fail(h, ECSEG_E_INVALID, "classify_nucleus_crops: bad arguments (no ecSeg-i handle)");
+    drop_sent_ahead(model_i);
+    if (model_c) drop_sent_ahead(model_c);
+    if (n_crops < 0 || (n_crops > 0 && (!crops || !channel_order || !from_patches || !channel_max || !pred_i || !ran_i || !ran_c ||
+                                        (model_c && !pred_c))))
+        return fail(h, ECSEG_E_INVALID, "classify_nucleus_crops: bad arguments");
+    std::string why = classifier_plan_error(model_i, "ecSeg-i", 1, 3);
+    if (why.empty() && model_c) why = classifier_plan_error(model_c, "ecSeg-c", 3, 1);
+    if (!why.empty()) return fail(h, ECSEG_E_INVALID, why);
+    if (model_i->device != h->device || (model_c && model_c->device != h->device))
+        return fail(h, ECSEG_E_INVALID, "classify_nucleus_crops: the crops handle and the model handles are not on one device");
+    if (n_crops == 0) return ECSEG_OK;
+    int order[3];
+    int rc;
+    if ((rc = check_crops(h, "classify_nucleus_crops", crops, n_crops, channel_order, order))) return rc;
+    USE_DEVICE(h);
+    const size_t crop_bytes = (size_t)256 * 256 * 3;
+    const int nc = std::min(n_crops, ISEG_CHUNK);
+    // a model's share of the call: its handle, the crops it takes per run, what one run leaves per crop, and where the rows go
+    struct Side { ecseg_ctx* m = nullptr; int per_group = 1, n_out = 0; float* pred = nullptr; std::vector<int32_t> sel; int n_sel = 0; std::vector<float> stage; };
+    Side side[2];
+    side[0].m = model_i; side[0].n_out = 3; side[0].pred = pred_i;
+    side[1].m = model_c; side[1].n_out = 1; side[1].pred = pred_c;
+    for (Side& sd : side) {
+        if (!sd.m) continue;
+        sd.per_group = std::max(1, windows_per_group(sd.m));
+        sd.sel.resize(nc);
+        sd.stage.resize((size_t)std::min(nc, sd.per_group) * sd.n_out);       // the rows of one run, compact
+        if ((rc = ensure_patches(sd.m, std::min(nc, sd.per_group)))) return fail(h, rc, sd.m->err);
+        if (sd.m != h) clear_timings(sd.m);
+        prof_begin(sd.m);
+    }
+    if (!model_c) side[1].sel.resize(nc);                    // (iseg_select writes no entry there: centromeric is off)
+    ClassifyBufs b{};
+    if ((rc = lay_out(h, h->call_arena, [&](Carver& c) { b = classify_bufs(c, nc); }))) return rc;
+    hipStream_t s = h->stream;
+    clear_timings(h);
+    for (int k0 = 0; k0 < n_crops; k0 += ISEG_CHUNK) {
+        const int k = std::min(ISEG_CHUNK, n_crops - k0);
+        HIP_TRY(h, hipMemcpyAsync(b.crop.desc, crops + (size_t)k0 * 5, (size_t)k * 5 * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        TIMED(h, s, 0, 1, HIP_TRY(h, run_nucleus_crops(h->iseg.lab, h->iseg.img, h->iseg_W, h->iseg_img_w, h->iseg_C, b.crop.desc, k, order, b.crop.crops, b.crop.max, s)));
+        if (crops_out) HIP_TRY(h, hipMemcpyAsync(crops_out + (size_t)k0 * crop_bytes, b.crop.crops, (size_t)k * crop_bytes, hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipMemcpyAsync(channel_max + (size_t)k0 * 3, b.crop.max, (size_t)k * 3 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        WAIT_ADD(h, s, 0, 1);
+        iseg_select(channel_max + (size_t)k0 * 3, from_patches + k0, k, centromeric && model_c, side[0].sel.data(), &side[0].n_sel,
+                    side[1].sel.data(), &side[1].n_sel, ran_i + k0, ran_c + k0);
+        if (side[0].n_sel) HIP_TRY(h, hipMemcpyAsync(b.sel_i, side[0].sel.data(), (size_t)side[0].n_sel * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        if (side[1].n_sel) HIP_TRY(h, hipMemcpyAsync(b.sel_c, side[1].sel.data(), (size_t)side[1].n_sel * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        const int rounds = std::max(iseg_sub_count(side[0].n_sel, side[0].per_group), side[1].m ? iseg_sub_count(side[1].n_sel, side[1].per_group) : 0);
+        // Round r: sub-chunk r of either list (a list that has run out takes no part).  The crops handle's stream is idle but for
+        // the input kernel, whose end (ev[3]) the model streams wait for; the crop buffer, the lists and the input tensors are not
+        // written again before both models' rows have arrived.
+        for (int r = 0; r < rounds; ++r) {
+            int at[2] = {0, 0}, cnt[2] = {0, 0};
+            for (int q = 0; q < 2; ++q)
+                if (side[q].m && r < iseg_sub_count(side[q].n_sel, side[q].per_group)) {
+                    at[q] = r * side[q].per_group;
+                    cnt[q] = iseg_sub_len(side[q].n_sel, side[q].per_group, r);
+                }
+            float* in_i = view_of(model_i, model_i->input_tensor).p;
+            float* in_c = model_c ? view_of(model_c, model_c->input_tensor).p : nullptr;
+            TIMED(h, s, 2, 3, HIP_TRY(h, run_iseg_classifier_inputs(b.crop.crops, b.crop.max, b.sel_i + at[0], cnt[0], b.sel_c + at[1], cnt[1], in_i, in_c, s)));
+            for (int q = 0; q < 2; ++q) {
+                Side& sd = side[q];
+                if (!cnt[q]) continue;
+                hipStream_t ms = sd.m->stream;
+                if (ms != s) HIP_TRY(h, hipStreamWaitEvent(ms, h->ev[3], 0));
+                HIP_TRY(h, hipEventRecord(sd.m->ev[4], ms));
+                if ((rc = run_plan_to_host(sd.m, cnt[q], sd.stage.data()))) return sd.m == h ? rc : fail(h, rc, sd.m->err);
+                HIP_TRY(h, hipEventRecord(sd.m->ev[5], ms));
+            }
+            for (int q = 0; q < 2; ++q) {
+                Side& sd = side[q];
+                if (!cnt[q]) continue;
+                HIP_TRY(h, hipStreamSynchronize(sd.m->stream));
+                timed_add(sd.m, 4, 5, ECSEG_T_UNET);
+                for (int j = 0; j < cnt[q]; ++j)
+                    std::copy_n(sd.stage.data() + (size_t)j * sd.n_out, sd.n_out, sd.pred + (size_t)(k0 + sd.sel[at[q] + j]) * sd.n_out);
+            }
+            HIP_TRY(h, hipStreamSynchronize(s));
+            timed_add(h, 2, 3, ECSEG_T_TILE);
+        }
+    }
+    for (Side& sd : side) if (sd.m) prof_end(sd.m);
+    return ECSEG_OK;
+}
+
+int ecseg_iseg_classifier_inputs_debug(ecseg_ctx* h, const uint8_t* crops, int k, const int32_t* channel_max, const int32_t* sel_i,
+                                       int n_i, const int32_t* sel_c, int n_c, float* out_i, float* out_c) {
+    DRIVER_OPEN(h);
+    if (!crops || !channel_max || k < 1 || k > ISEG_CHUNK || n_i < 0 || n_i > ISEG_CHUNK || n_c < 0 || n_c > ISEG_CHUNK ||
+        (n_i > 0 && (!sel_i || !out_i)) || (n_c > 0 && (!sel_c || !out_c)))
+        return fail(h, ECSEG_E_INVALID, "iseg_classifier_inputs_debug: bad arguments");
+    for (int j = 0; j < n_i; ++j) if (sel_i[j] < 0 || sel_i[j] >= k) return fail(h, ECSEG_E_INVALID, "iseg_classifier_inputs_debug: sel_i out of range");
+    for (int j = 0; j < n_c; ++j) if (sel_c[j] < 0 || sel_c[j] >= k) return fail(h, ECSEG_E_INVALID, "iseg_classifier_inputs_debug: sel_c out of range");
+    USE_DEVICE(h);
+    const size_t crop_bytes = (size_t)256 * 256 * 3, px = (size_t)256 * 256;
+    ClassifyBufs b{};
+    float* d_i = nullptr;
+    float* d_c = nullptr;
+    int rc;
+    if ((rc = lay_out(h, h->call_arena, [&](Carver& c) {
+            b = classify_bufs(c, ISEG_CHUNK); d_i = c.take<float>((size_t)n_i * px); d_c = c.take<float>((size_t)n_c * px * 3); })))
+        return rc;
+    hipStream_t s = h->stream;
+    clear_timings(h);
+    HIP_TRY(h, hipMemcpyAsync(b.crop.crops, crops, (size_t)k * crop_bytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(b.crop.max, channel_max, (size_t)k * 3 * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    if (n_i) HIP_TRY(h, hipMemcpyAsync(b.sel_i, sel_i, (size_t)n_i * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    if (n_c) HIP_TRY(h, hipMemcpyAsync(b.sel_c, sel_c, (size_t)n_c * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    TIMED(h, s, 2, 3, HIP_TRY(h, run_iseg_classifier_inputs(b.crop.crops, b.crop.max, b.sel_i, n_i, b.sel_c, n_c, d_i, d_c, s)));
+    if (n_i) HIP_TRY(h, hipMemcpyAsync(out_i, d_i, (size_t)n_i * px * sizeof(float), hipMemcpyDeviceToHost, s));
+    if (n_c) HIP_TRY(h, hipMemcpyAsync(out_c, d_c, (size_t)n_c * px * 3 * sizeof(float), hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    timed_set(h, 2, 3, ECSEG_T_TILE);
     return ECSEG_OK;
 }
 

@@ -464,6 +464,17 @@ int run_plan(ecseg_ctx* h, int n_all, StitchPlan* crop, const std::vector<LaneSp
     return ECSEG_OK;
 }
 
+// The plan on ni patches whose input tensor has been filled, then their rows of the output tensor on the way to `out` (compact), all on
+// the handle's stream: the caller waits for it.  Shared by forward_host and ecseg_classify_nucleus_crops (drivers_interseg.hip).
+int run_plan_to_host(ecseg_ctx* h, int ni, float* out) {
+    if (int rc = run_plan(h, ni)) return rc;
+    const ecseg_tensor_desc& to = h->tensors[h->output_tensor];
+    const TView ov = view_of(h, h->output_tensor);
+    HIP_TRY(h, hipMemcpy2DAsync(out, (size_t)to.c * sizeof(float), ov.p, (size_t)ov.cs * sizeof(float), (size_t)to.c * sizeof(float),
+                                (size_t)to.h * to.w * ni, hipMemcpyDeviceToHost, h->stream));
+    return ECSEG_OK;
+}
+
 void prof_begin(ecseg_ctx* h) { h->prof_used = 0; h->prof_flops = 0.0; h->prof_exec_flops = 0.0; h->prof_recs.clear(); }
 void prof_end(ecseg_ctx* h) {   // stream must be idle
     double ms = 0.0;
@@ -505,10 +516,7 @@ static int forward_host(ecseg_ctx* h, const void* patches, bool is_f32, int n, f
             HIP_TRY(h, hipMemcpyAsync(h->d_u8in, static_cast<const uint8_t*>(patches) + (size_t)i0 * in_per, in_per * ni, hipMemcpyHostToDevice, s));
             HIP_TRY(h, launch_u8_to_f32(h->d_u8in, view_of(h, h->input_tensor).p, in_per * ni, s));
         }
-        if ((rc = run_plan(h, ni))) return rc;
-        const TView ov = view_of(h, h->output_tensor);
-        HIP_TRY(h, hipMemcpy2DAsync(out + (size_t)i0 * out_per, (size_t)to.c * sizeof(float), ov.p, (size_t)ov.cs * sizeof(float),
-                                    (size_t)to.c * sizeof(float), (size_t)to.h * to.w * ni, hipMemcpyDeviceToHost, s));
+        if ((rc = run_plan_to_host(h, ni, out + (size_t)i0 * out_per))) return rc;
         HIP_TRY(h, hipStreamSynchronize(s));
     }
     prof_end(h);

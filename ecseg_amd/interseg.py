@@ -4,7 +4,9 @@
 (``Handle.nuclei_regions`` / ``Handle.nucleus_crops``, csrc/interseg_kernels.hip); the two Keras classifiers
 ``interseg_models/interseg`` (3 classes: No-amp / EC-amp / HSR-amp) and ``interseg_models/ecseg_c`` (focal amplification,
 one sigmoid unit) run batched through the same plan interpreter and HIP kernels as the metaseg U-Net, and the per-nucleus
-decision logic of src/interseg.py:131-190 is applied to their outputs (``classify_crops``).
+decision logic of src/interseg.py:131-190 is applied to their outputs (``classify_crops``).  One key of its own:
+``classify_on_device`` (false; true: one ``Handle.classify_nucleus_crops`` call per image builds the crops, writes both classifiers'
+inputs from them on the device and runs the plans - no crop crosses the bus; the same CSV).
 """
 import csv
 import os
@@ -52,7 +54,6 @@ def classify_crops(ecseg_i_model, crops, ecseg_c_model=None, centromeric_quality
         raise ValueError('crops must be (N, 256, 256, 3) uint8')
     n = len(crops)
     has_c = ecseg_c_model is not None
-    rows = [dict() for _ in range(n)]
     from_patches = np.broadcast_to(np.asarray(from_patches, bool), (n,))
     cmax = np.asarray(channel_max).reshape(n, 3) if channel_max is not None else None
     if cmax is not None:
@@ -60,38 +61,47 @@ def classify_crops(ecseg_i_model, crops, ecseg_c_model=None, centromeric_quality
     else:
         empty = np.array([from_patches[k] and not crops[k].any() for k in range(n)], bool)
     live = np.flatnonzero(~empty)
-    for k in np.flatnonzero(empty):
-        rows[k] = {'interSeg_label': EMPTY, 'ecSeg-i_label': EMPTY, 'pred_no_amp': EMPTY, 'pred_ec': EMPTY, 'pred_hsr': EMPTY}
-        if has_c:
-            rows[k].update({'ecSeg-c_label': EMPTY, 'pred_no_focal_amp': EMPTY, 'pred_focal_amp': EMPTY})
+    pred_i, pred_c, ran_c = np.zeros((n, 3), np.float32), np.zeros(n, np.float32), np.zeros(n, bool)
     if len(live):
-        pi = ecseg_i_model.predict(crops[live][..., 0])                        # (n, 3): src/interseg.py:155
-        run_c = np.array([has_c and centromeric_quality_score_pass and
-                          (cmax[k, 1] if cmax is not None else crops[k][..., 1].max()) > 10 for k in live], bool)
-        pc = None
-        if run_c.any():
-            xc = np.stack([preprocess_ecseg_c(crops[k]) for k in live[run_c]])
-            pc = ecseg_c_model.predict(xc).reshape(-1)                          # (n,): src/interseg.py:168
-        j = 0
-        for a, k in enumerate(live):
-            r = rows[k]
-            # np.float32 scalars, as the reference keeps them (src/interseg.py:156-158,169-170): a CSV written from these
-            # rows prints 0.3, not float64(float32(0.3)) = 0.30000001192092896
-            r['pred_no_amp'], r['pred_ec'], r['pred_hsr'] = (np.float32(v) for v in pi[a])
-            i_label = ECSEG_I_LABEL_MAP[int(np.argmax(pi[a]))]
-            r['ecSeg-i_label'] = i_label
-            if run_c[a]:
-                v = np.float32(pc[j]); j += 1
-                r['pred_no_focal_amp'], r['pred_focal_amp'] = np.float32(1) - v, v        # float32 complement
-                c_label = ECSEG_C_LABEL_MAP[int(v > 0.5)]
-                r['ecSeg-c_label'] = c_label
-                r['interSeg_label'] = INTERSEG_LABEL_MAP[(c_label, i_label)]
-            else:
-                if has_c and not centromeric_quality_score_pass:
-                    r['ecSeg-c_label'] = r['pred_no_focal_amp'] = r['pred_focal_amp'] = FAILED_QUALITY
-                elif has_c:
-                    r['ecSeg-c_label'] = r['pred_no_focal_amp'] = r['pred_focal_amp'] = LOW_CENT
-                r['interSeg_label'] = i_label
+        pred_i[live] = ecseg_i_model.predict(crops[live][..., 0])              # (n, 3): src/interseg.py:155
+        ran_c[live] = [has_c and centromeric_quality_score_pass and
+                       (cmax[k, 1] if cmax is not None else crops[k][..., 1].max()) > 10 for k in live]
+        if ran_c.any():
+            xc = np.stack([preprocess_ecseg_c(crops[k]) for k in np.flatnonzero(ran_c)])
+            pred_c[ran_c] = ecseg_c_model.predict(xc).reshape(-1)               # (n,): src/interseg.py:168
+    return rows_from_predictions(has_c, centromeric_quality_score_pass, ~empty, pred_i, ran_c, pred_c)
+
+
+def rows_from_predictions(has_c, centromeric_quality_score_pass, ran_i, pred_i, ran_c, pred_c):
+    """The rows of ``classify_crops`` from what the classifiers gave, wherever they ran (the host path above,
+    ``Handle.classify_nucleus_crops``): ``ran_i`` (N) bool and ``pred_i`` (N, 3) float32 of ecSeg-i - a crop it did not run for is
+    an empty tile of an oversized nucleus; ``ran_c`` (N) bool and ``pred_c`` (N) float32 of ecSeg-c.  ``has_c``: there is a
+    centromeric-probe model, so the rows carry its columns."""
+    ran_i, ran_c = np.asarray(ran_i, bool), np.asarray(ran_c, bool)
+    rows = [dict() for _ in range(len(ran_i))]
+    for k, r in enumerate(rows):
+        if not ran_i[k]:
+            r.update({'interSeg_label': EMPTY, 'ecSeg-i_label': EMPTY, 'pred_no_amp': EMPTY, 'pred_ec': EMPTY, 'pred_hsr': EMPTY})
+            if has_c:
+                r.update({'ecSeg-c_label': EMPTY, 'pred_no_focal_amp': EMPTY, 'pred_focal_amp': EMPTY})
+            continue
+        # np.float32 scalars, as the reference keeps them (src/interseg.py:156-158,169-170): a CSV written from these
+        # rows prints 0.3, not float64(float32(0.3)) = 0.30000001192092896
+        r['pred_no_amp'], r['pred_ec'], r['pred_hsr'] = (np.float32(v) for v in pred_i[k])
+        i_label = ECSEG_I_LABEL_MAP[int(np.argmax(pred_i[k]))]
+        r['ecSeg-i_label'] = i_label
+        if ran_c[k]:
+            v = np.float32(pred_c[k])
+            r['pred_no_focal_amp'], r['pred_focal_amp'] = np.float32(1) - v, v        # float32 complement
+            c_label = ECSEG_C_LABEL_MAP[int(v > 0.5)]
+            r['ecSeg-c_label'] = c_label
+            r['interSeg_label'] = INTERSEG_LABEL_MAP[(c_label, i_label)]
+        else:
+            if has_c and not centromeric_quality_score_pass:
+                r['ecSeg-c_label'] = r['pred_no_focal_amp'] = r['pred_focal_amp'] = FAILED_QUALITY
+            elif has_c:
+                r['ecSeg-c_label'] = r['pred_no_focal_amp'] = r['pred_focal_amp'] = LOW_CENT
+            r['interSeg_label'] = i_label
     return rows
 
 
@@ -203,8 +213,10 @@ def _load_image(p, seg_path):
     return I, seg
 
 
-def process_image(p, handle, ecseg_i_model, ecseg_c_model, fish_index, quality_pass, stats=None):
-    """CSV rows of one image (src/interseg.py:105-235): [name, nucleus_center, interSeg_label, (ecSeg-c_label,) ecSeg-i_label]."""
+def process_image(p, handle, ecseg_i_model, ecseg_c_model, fish_index, quality_pass, stats=None, classify_on_device=False):
+    """CSV rows of one image (src/interseg.py:105-235): [name, nucleus_center, interSeg_label, (ecSeg-c_label,) ecSeg-i_label].
+    ``classify_on_device`` (the config key): one ``handle.classify_nucleus_crops`` call takes the crop descriptors and returns the
+    classifiers' outputs - the crops never reach the host; the same rows."""
     import time
     from . import image_tools
     path_split = os.path.split(p)
@@ -219,21 +231,29 @@ def process_image(p, handle, ecseg_i_model, ecseg_c_model, fish_index, quality_p
             raise ImageError('segmentation %s holds several non-zero values: only 0 / non-zero nucleus masks are supported' % seg_path)
         seg = (seg != 0).astype(np.uint8) * np.uint8(255)
     t1 = time.perf_counter()
+    has_c = ecseg_c_model is not None
+    crop_rows = []
     try:
         rec = handle.nuclei_regions(seg, I, fish_index)
         centers, low, desc, tiled, owner = region_rows(rec)
         order = (fish_index, 1 - fish_index, 2)
-        crops, cmax = handle.nucleus_crops(desc, order) if len(desc) else (np.zeros((0, 256, 256, 3), np.uint8), np.zeros((0, 3), np.int32))
+        if classify_on_device:
+            t2 = time.perf_counter()
+            if len(desc):
+                _, pred_i, ran_i, pred_c, ran_c = handle.classify_nucleus_crops(desc, order, tiled, has_c and quality_pass, ecseg_i_model,
+                                                                               ecseg_c_model)
+                crop_rows = rows_from_predictions(has_c, quality_pass, ran_i, pred_i, ran_c, pred_c)
+        else:
+            crops, cmax = handle.nucleus_crops(desc, order) if len(desc) else (np.zeros((0, 256, 256, 3), np.uint8), np.zeros((0, 3), np.int32))
+            t2 = time.perf_counter()
     except Exception as e:
         if getattr(e, 'code', None) == -1:
             raise ImageError(str(e))
         raise
-    t2 = time.perf_counter()
-    has_c = ecseg_c_model is not None
-    crop_rows = []
-    for b0 in range(0, len(desc), CROP_BATCH):
-        sl = slice(b0, b0 + CROP_BATCH)
-        crop_rows += classify_crops(ecseg_i_model, crops[sl], ecseg_c_model, quality_pass, from_patches=tiled[sl], channel_max=cmax[sl])
+    if not classify_on_device:
+        for b0 in range(0, len(desc), CROP_BATCH):
+            sl = slice(b0, b0 + CROP_BATCH)
+            crop_rows += classify_crops(ecseg_i_model, crops[sl], ecseg_c_model, quality_pass, from_patches=tiled[sl], channel_max=cmax[sl])
     t3 = time.perf_counter()
     by_region = {}
     for k, r in zip(owner.tolist(), crop_rows):
@@ -274,6 +294,10 @@ def main(argv=None):
         if (fish_color != 'green') & (fish_color != 'red'):
             print("FISH_color can only be \"green\" or \"red\". Please update the config.yaml file accordingly.")
             sys.exit(2)
+    classify_on_device = var.get('classify_on_device', False)
+    if not isinstance(classify_on_device, bool):
+        print("interseg.classify_on_device must be true or false (true: the nucleus crops go through the classifiers without leaving the device). Exiting...")
+        sys.exit(2)
     fish_index = 1 if fish_color == 'green' else 0
     os.makedirs(os.path.join(inpath, 'annotated'), exist_ok=True)
 
@@ -286,6 +310,9 @@ def main(argv=None):
     ecseg_i_model = load_model(ECSEG_I_MODEL)
     ecseg_c_model = load_model(ECSEG_C_MODEL) if has_centromeric_probe else None
     handle = ecseg_i_model.handle
+    if classify_on_device and not hasattr(handle, 'classify_nucleus_crops'):
+        print("interseg.classify_on_device: true needs the device classifier path (classify_nucleus_crops), which the handle in use does not have. Exiting...")
+        sys.exit(2)
     table, table_error = None, None
     if has_centromeric_probe:
         # the reference reads the table even without a centromeric probe, where it is never used (src/interseg.py:101)
@@ -307,7 +334,7 @@ def main(argv=None):
                     quality_pass = bool(quality_score(table, path_split[1][:-4], ['red', 'green'][1 - fish_index]) <= 3)
                 except ValueError as e:
                     raise ImageError(str(e))
-            rows += process_image(p, handle, ecseg_i_model, ecseg_c_model, fish_index, quality_pass)
+            rows += process_image(p, handle, ecseg_i_model, ecseg_c_model, fish_index, quality_pass, classify_on_device=classify_on_device)
         except ImageError as e:
             print(p, '-', e)
             failed.append((p, str(e)))

@@ -63,6 +63,8 @@ extern "C" {
  * PNGs encoded on the device; nothing existing changed.) */
 /* (still 5 - additive: ecseg_tiff_encode_batch, ecseg_tiff_encode_batch_bytes and ecseg_fish_render_tiff_batch, the TIFF files of many
  * stat_fish images encoded in one device call, a wave per strip of any file; nothing existing changed.) */
+/* (still 5 - additive: ecseg_classify_nucleus_crops and ecseg_iseg_classifier_inputs_debug, interSeg's crops through both classifiers
+ * without a host round trip; nothing existing changed.) */
 #define ECSEG_ABI_VERSION 5
 
 #define ECSEG_OK             0
@@ -351,6 +353,30 @@ int ecseg_nuclei_regions(ecseg_ctx* h, const uint8_t* seg, int H, int W, const u
  * test of :199 and the centromere gate of :160). */
 int ecseg_nucleus_crops(ecseg_ctx* h, const int32_t* crops, int n_crops, const int32_t* channel_order, uint8_t* out,
                         int32_t* channel_max);
+/* The crops of ecseg_nucleus_crops through the two classifiers without leaving the device (src/interseg.py:153-170,199-210).
+ * h: the handle that holds the region map; model_i: the handle with the ecSeg-i plan ((256, 256, 1) -> 3 values; may be h itself);
+ * model_c: the handle with the ecSeg-c plan ((256, 256, 3) -> 1 value), or NULL.  All on one device.  crops, n_crops, channel_order:
+ * as ecseg_nucleus_crops, with its checks and its chunks of 256 crops; from_patches: one byte per crop, non-zero for a tile of a
+ * nucleus larger than 256 px; centromeric: non-zero when ecSeg-c applies to this image (a centromeric probe and a passed quality
+ * score).  Per chunk the maxima come back (the call's one wait per chunk before the models run), and the host chooses: ecSeg-i
+ * runs for every crop but a from_patches crop whose three maxima are 0; ecSeg-c for a crop ecSeg-i runs for when centromeric is
+ * set, model_c is given and channel_max[1] > 10.  One kernel then writes (float)channel 0 of the chosen crops into the ecSeg-i
+ * plan's input and round(x / max_c * 255) / 255 (float32, half to even, x / 0 = NaN) of every channel into the ecSeg-c plan's
+ * (src/utils.py:166-173), and each plan runs on its own handle's stream in runs of at most that handle's windows per group.
+ * channel_max (n_crops, 3) int32; pred_i (n_crops, 3) float32 and ran_i (n_crops) bytes; pred_c (n_crops) float32 (may be NULL
+ * without model_c) and ran_c (n_crops) bytes: ran_* is 1 where that model ran, and the rows of pred_* where it did not are left as
+ * they were.  crops_out: NULL, or (n_crops, 256, 256, 3) uint8 filled as ecseg_nucleus_crops fills `out`.
+ * Device time (ecseg_get_timings): on h, ECSEG_T_COUNT the crop kernels and ECSEG_T_TILE the input kernel; on each model handle,
+ * ECSEG_T_UNET its plan runs (h's own when it is model_i).  ECSEG_E_INVALID: the argument errors of ecseg_nucleus_crops, a model
+ * handle without a plan or with one of another shape (the message names the model), handles on different devices. */
+int ecseg_classify_nucleus_crops(ecseg_ctx* h, ecseg_ctx* model_i, ecseg_ctx* model_c, const int32_t* crops, int n_crops,
+                                 const int32_t* channel_order, const uint8_t* from_patches, int centromeric, int32_t* channel_max,
+                                 float* pred_i, uint8_t* ran_i, float* pred_c, uint8_t* ran_c, uint8_t* crops_out);
+/* For the tests of the input kernel alone: crops (k, 256, 256, 3) uint8 and channel_max (k, 3) as given, 1 <= k <= 256; sel_i / sel_c:
+ * n_i / n_c <= 256 crop indices in [0, k), any order, repeats allowed -> out_i (n_i, 256, 256) float32, out_c (n_c, 256, 256, 3)
+ * float32, what ecseg_classify_nucleus_crops would write into the two plans' inputs.  Device time in ECSEG_T_TILE. */
+int ecseg_iseg_classifier_inputs_debug(ecseg_ctx* h, const uint8_t* crops, int k, const int32_t* channel_max, const int32_t* sel_i,
+                                       int n_i, const int32_t* sel_c, int n_c, float* out_i, float* out_c);
 
 /* ---- fish_distance_calculation: per-nucleus FISH - centromere distances (src/fish_distance_calculation.py:16-46) --------- */
 /* Replaces, for ONE image, the loop over regionprops(segmentation) (:19), the gate on lsq channels 0 and 1 (:21), the spot

@@ -1,6 +1,8 @@
 """Throughput of the interSeg file-level driver (``make interseg``) on synthetic FISH images.
 
     python tools/time_interseg.py [--images 16] [--nuclei 40] [--height 1040] [--width 1392] [--cpu-workers 16]
+    python tools/time_interseg.py --classify-on-device off|on|alternate     # the classifier stage with interseg.classify_on_device
+                                                                            # off / on (alternate: off, on, off, on in one process)
 
 Device side: per image ``Handle.nuclei_regions`` + ``Handle.nucleus_crops`` (regions + crops), the two classifiers
 (tests/golden/interseg_synth.h5 and ecseg_c_synth.h5, batched) and the host work around them (region rows, decisions).
@@ -74,6 +76,94 @@ def cpu_reference_loop(args):
     return crops
 
 
+def classify_pass(data, h, mi, mc, on, split=False):
+    """One pass over the images as process_image runs them (regions, crops, classifiers, rows) with the key off or on.  Returns
+    (seconds of the pass, per-stage seconds, device milliseconds: crop kernels, input kernel, each plan).  ``split`` (key off): the
+    classifier stage again, piece by piece - crop slicing, ecSeg-i predict, preprocess_ecseg_c, ecSeg-c predict, rows."""
+    from ecseg_amd import interseg
+    st = {'regions': 0.0, 'crops': 0.0, 'classifiers': 0.0, 'rows': 0.0}
+    dev = {'crop_kernels': 0.0, 'input_kernel': 0.0, 'plan_i': 0.0, 'plan_c': 0.0}
+    parts = {'slice_u8': 0.0, 'predict_i': 0.0, 'preprocess_numpy': 0.0, 'predict_c': 0.0}
+    t_all = time.perf_counter()
+    for seg, img in data:
+        t0 = time.perf_counter()
+        rec = h.nuclei_regions(seg, img, 0)
+        centers, low, desc, tiled, owner = interseg.region_rows(rec)
+        t1 = time.perf_counter()
+        if on:
+            _, pi, ri, pc, rc = h.classify_nucleus_crops(desc, (0, 1, 2), tiled, True, mi, mc)
+            t2 = t3 = time.perf_counter()
+            rows = interseg.rows_from_predictions(True, True, ri, pi, rc, pc)
+            t4 = time.perf_counter()
+            tm = h.timings()
+            dev['crop_kernels'] += tm['count']
+            dev['input_kernel'] += tm['tile']
+            dev['plan_i'] += mi.handle.timings()['unet']
+            dev['plan_c'] += mc.handle.timings()['unet']
+            st['classifiers'] += t2 - t1
+            st['rows'] += t4 - t3
+        else:
+            crops, cmax = h.nucleus_crops(desc, (0, 1, 2))
+            t2 = time.perf_counter()
+            dev['crop_kernels'] += h.timings()['count']
+            rows = []
+            for b0 in range(0, len(desc), interseg.CROP_BATCH):
+                sl = slice(b0, b0 + interseg.CROP_BATCH)
+                rows += interseg.classify_crops(mi, crops[sl], mc, True, from_patches=tiled[sl], channel_max=cmax[sl])
+            t3 = time.perf_counter()
+            st['crops'] += t2 - t1
+            st['classifiers'] += t3 - t2
+            if split:
+                for b0 in range(0, len(desc), interseg.CROP_BATCH):
+                    c, m, tl = crops[b0:b0 + interseg.CROP_BATCH], cmax[b0:b0 + interseg.CROP_BATCH], tiled[b0:b0 + interseg.CROP_BATCH]
+                    live = np.flatnonzero(~(tl & (m.max(axis=1) == 0)))
+                    q0 = time.perf_counter()
+                    x = c[live][..., 0]
+                    q1 = time.perf_counter()
+                    mi.predict(x)
+                    q2 = time.perf_counter()
+                    xc = [interseg.preprocess_ecseg_c(c[k]) for k in live if m[k, 1] > 10]
+                    xc = np.stack(xc) if xc else np.zeros((0, 256, 256, 3), np.float32)
+                    q3 = time.perf_counter()
+                    mc.predict(xc)
+                    q4 = time.perf_counter()
+                    for key, v in zip(parts, (q1 - q0, q2 - q1, q3 - q2, q4 - q3)):
+                        parts[key] += v
+        st['regions'] += t1 - t0
+    return time.perf_counter() - t_all, st, dev, parts
+
+
+def classify_report(a):
+    """--classify-on-device: images/s as median (min - max) of 3 passes after a warm-up pass, per mode visit; per-stage seconds and device
+    milliseconds per image; for the key off, the split of the classifier stage into plan calls (upload + network + download), crop slicing
+    and numpy."""
+    from ecseg_amd import hdf5_min
+    from ecseg_amd.model import MetasegModel
+    g = os.path.join(ROOT, 'tests', 'golden')
+    mi = MetasegModel(*hdf5_min.load_keras_h5(os.path.join(g, 'interseg_synth.h5')))
+    mc = MetasegModel(*hdf5_min.load_keras_h5(os.path.join(g, 'ecseg_c_synth.h5')))
+    h = mi.handle
+    data = [synth_image(1000 + k, a.height, a.width, a.nuclei) for k in range(a.images)]
+    visits = {'off': [False], 'on': [True], 'alternate': [False, True, False, True]}[a.classify_on_device]
+    n = len(data)
+    out = {'images': n, 'shape': [a.height, a.width], 'visits': []}
+    for on in visits:
+        classify_pass(data, h, mi, mc, on)                                   # warm-up: buffers of this mode
+        rates, last = [], None
+        for _ in range(3):
+            wall, st, dev, _ = last = classify_pass(data, h, mi, mc, on)
+            rates.append(n / wall)
+        rec = {'classify_on_device': on, 'images_per_s': {'median': round(float(np.median(rates)), 3), 'min': round(min(rates), 3), 'max': round(max(rates), 3)},
+               'stage_ms_per_image': {k: round(1e3 * v / n, 3) for k, v in last[1].items()},
+               'device_ms_per_image': {k: round(v / n, 4) for k, v in last[2].items()}}
+        if not on:
+            _, _, _, parts = classify_pass(data, h, mi, mc, False, split=True)
+            # predict_* = upload + plan + download as the host path pays them; the plans' own device time is plan_i / plan_c of an `on` visit
+            rec['classifier_stage_split_ms_per_image'] = {k: round(1e3 * v / n, 3) for k, v in parts.items()}
+        out['visits'].append(rec)
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--images', type=int, default=16)
@@ -82,7 +172,11 @@ def main():
     ap.add_argument('--width', type=int, default=1392)
     ap.add_argument('--cpu-workers', type=int, default=16)
     ap.add_argument('--no-cpu', action='store_true')
+    ap.add_argument('--classify-on-device', choices=['off', 'on', 'alternate'], default=None,
+                    help='time the classifier stage of `make interseg` with interseg.classify_on_device off, on, or off, on, off, on over the same images')
     a = ap.parse_args()
+    if a.classify_on_device:
+        return classify_report(a)
     from ecseg_amd import hdf5_min, interseg
     from ecseg_amd.model import MetasegModel
     g = os.path.join(ROOT, 'tests', 'golden')
