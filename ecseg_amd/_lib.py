@@ -29,6 +29,7 @@ EXPORTS = [
     'ecseg_png_channel_bound', 'ecseg_png_channel_encode', 'ecseg_overlay_files',
     'ecseg_tiff_encode_batch', 'ecseg_tiff_encode_batch_bytes', 'ecseg_fish_render_tiff_batch',
     'ecseg_classify_nucleus_crops', 'ecseg_iseg_classifier_inputs_debug',
+    'ecseg_marker_watershed_stages_debug', 'ecseg_marker_watershed_batch_stages_debug',
 ]
 
 
@@ -163,6 +164,8 @@ def load_library():
     lib.ecseg_rpn_proposals_last.argtypes = [vp, i32, vp, i32, i32, i32, C.c_float, i32, i32, C.POINTER(C.c_int32), vp, vp, vp]
     lib.ecseg_marker_watershed.argtypes = [vp, vp, i32, i32, vp, vp, vp, C.c_longlong, vp]
     lib.ecseg_marker_watershed_batch.argtypes = [vp, vp, C.c_longlong, vp, i32, vp, vp, vp, C.c_longlong, vp]
+    lib.ecseg_marker_watershed_stages_debug.argtypes = [vp, vp, i32, i32, vp, vp, vp, C.c_longlong, vp, vp, vp, vp, vp]
+    lib.ecseg_marker_watershed_batch_stages_debug.argtypes = [vp, vp, C.c_longlong, vp, i32, vp, vp, vp, C.c_longlong, vp, vp, vp, vp, vp]
     lib.ecseg_marker_watershed_batch_bytes.argtypes = [vp, i32, vp]; lib.ecseg_marker_watershed_batch_bytes.restype = C.c_longlong
     lib.ecseg_clean_nuclei.argtypes = [vp, vp, i32, i32, i32, vp, vp, C.POINTER(C.c_double)]
     lib.ecseg_rescale_down.argtypes = [vp, vp, i32, i32, i32, i32, vp, i32, vp, i32, vp, vp]
@@ -1257,7 +1260,37 @@ class Handle:
                     'ecseg_marker_watershed')
         return out
 
+    def marker_watershed_stages(self, mask, rows, cols, labels):
+        """Test-only (ecseg_marker_watershed_stages_debug): ``marker_watershed`` with what its stages left on the device ->
+        dict(rw int32, filled uint8, d2 int32, lab int32, out uint8), each (H, W).  ``rw`` and ``d2`` are 0 off the mask."""
+        m = self._mask_u8(mask, 'marker_watershed_stages')
+        r, c, l = (np.ascontiguousarray(a, np.int32).reshape(-1) for a in (rows, cols, labels))
+        if not (len(r) == len(c) == len(l)):
+            raise ValueError('marker_watershed_stages: rows, cols and labels differ in length')
+        res = dict(rw=np.empty(m.shape, np.int32), filled=np.empty(m.shape, np.uint8), d2=np.empty(m.shape, np.int32),
+                   lab=np.empty(m.shape, np.int32), out=np.empty(m.shape, np.uint8))
+        self._check(self.lib.ecseg_marker_watershed_stages_debug(self.h, _ptr(m), m.shape[0], m.shape[1], _ptr(r), _ptr(c), _ptr(l), len(r),
+                                                                 _ptr(res['out']), _ptr(res['rw']), _ptr(res['filled']), _ptr(res['d2']),
+                                                                 _ptr(res['lab'])), 'ecseg_marker_watershed_stages_debug')
+        return res
+
     WATERSHED_BATCH_MAX_IMAGES = 1024     # ECSEG_WATERSHED_BATCH_MAX_IMAGES
+
+    def marker_watershed_batch_stages(self, masks, images, rows, cols, labels):
+        """Test-only (ecseg_marker_watershed_batch_stages_debug): ``marker_watershed_packed`` with the stage products -> one dict per
+        image as ``marker_watershed_stages`` returns it, cut out of the packed buffers at the image's offset."""
+        buf = np.ascontiguousarray(masks, np.uint8).reshape(-1)
+        tab = np.ascontiguousarray(images, np.int64).reshape(-1, 5)
+        r, c, l = (np.ascontiguousarray(a, np.int32).reshape(-1) for a in (rows, cols, labels))
+        if not (len(r) == len(c) == len(l)):
+            raise ValueError('marker_watershed_batch_stages: rows, cols and labels differ in length')
+        res = dict(rw=np.zeros(buf.size, np.int32), filled=np.zeros(buf.size, np.uint8), d2=np.zeros(buf.size, np.int32),
+                   lab=np.zeros(buf.size, np.int32), out=np.zeros(buf.size, np.uint8))
+        self._check(self.lib.ecseg_marker_watershed_batch_stages_debug(self.h, _ptr(buf), buf.size, _ptr(tab), len(tab), _ptr(r), _ptr(c), _ptr(l),
+                                                                       len(r), _ptr(res['out']), _ptr(res['rw']), _ptr(res['filled']),
+                                                                       _ptr(res['d2']), _ptr(res['lab'])),
+                    'ecseg_marker_watershed_batch_stages_debug')
+        return [{k: v[o:o + H * W].reshape(H, W).copy() for k, v in res.items()} for o, H, W, _, _ in tab.tolist()]
 
     def marker_watershed_packed(self, masks, images, rows, cols, labels):
         """ecseg_marker_watershed_batch as it is: ``masks`` a 1-D uint8 buffer, ``images`` (n, 5) int64 rows (byte offset, H, W, first

@@ -78,6 +78,128 @@ static std::string ws_batch_plan(const int64_t* images, int n_images, const long
     return std::string();
 }
 
+// The stage products of a marker watershed that the *_stages_debug entries hand back, as host pointers (each may be null: not copied):
+// rw, filled, d2 and lab of WatershedBufs / WatershedBatchBufs, `count` elements each.  The plain entries pass four nulls.
+struct WsStages { int32_t* rw; uint8_t* filled; int32_t* d2; int32_t* lab; };
+static hipError_t ws_read_stages(const WsStages& st, const int32_t* rw, const uint8_t* filled, const int32_t* d2, const int32_t* lab, size_t count,
+                                 hipStream_t s) {
+    hipError_t e = hipSuccess;
+    if (st.rw && (e = hipMemcpyAsync(st.rw, rw, count * sizeof(int32_t), hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
+    if (st.filled && (e = hipMemcpyAsync(st.filled, filled, count, hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
+    if (st.d2 && (e = hipMemcpyAsync(st.d2, d2, count * sizeof(int32_t), hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
+    if (st.lab && (e = hipMemcpyAsync(st.lab, lab, count * sizeof(int32_t), hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
+    return e;
+}
+
+// ecseg_marker_watershed and ecseg_marker_watershed_stages_debug: one driver, the second with somewhere to put the stage products
+static int marker_watershed_driver(ecseg_ctx* h, const uint8_t* mask, int H, int W, const int32_t* marker_rows, const int32_t* marker_cols,
+                                   const int32_t* marker_labels, long long n_markers, uint8_t* out, const WsStages& st) {
+    DRIVER_OPEN(h);
+    if (!mask || !out || H <= 0 || W <= 0) return fail(h, ECSEG_E_INVALID, "marker_watershed: bad arguments");
+    if (H > ECSEG_WATERSHED_MAX_EXTENT || W > ECSEG_WATERSHED_MAX_EXTENT)
+        return fail(h, ECSEG_E_INVALID, "marker_watershed: an extent above " + std::to_string(ECSEG_WATERSHED_MAX_EXTENT));
+    if (n_markers < 0 || n_markers >= (1ll << 31) || (n_markers > 0 && (!marker_rows || !marker_cols || !marker_labels)))
+        return fail(h, ECSEG_E_INVALID, "marker_watershed: n_markers must be between 0 and 2^31 - 1, with the three lists");
+    const int n = (int)n_markers;
+    for (int i = 0; i < n; ++i) {
+        if (marker_rows[i] < 0 || marker_rows[i] >= H || marker_cols[i] < 0 || marker_cols[i] >= W)
+            return fail(h, ECSEG_E_INVALID, "marker_watershed: marker " + std::to_string(i) + " lies outside the image");
+        if (marker_labels[i] < 1) return fail(h, ECSEG_E_INVALID, "marker_watershed: marker " + std::to_string(i) + " has a label below 1");
+    }
+    const size_t px = (size_t)H * W;
+    size_t fg = 0;
+    for (size_t p = 0; p < px; ++p) fg += mask[p] != 0;
+    if (5 * fg + 1 >= (1ull << 31)) return fail(h, ECSEG_E_INVALID, "marker_watershed: the mask holds too many pixels for one heap");
+    const int cap = (int)(5 * fg + 1);
+    USE_DEVICE(h);
+    int rc;
+    WatershedBufs b{};
+    if ((rc = lay_out(h, h->call_arena, [&](Carver& c) { b = watershed_bufs(c, H, W, n, cap); }))) return rc;
+    hipStream_t s = h->stream;
+    clear_timings(h);
+    HIP_TRY(h, hipMemcpyAsync(b.mask, mask, px, hipMemcpyHostToDevice, s));
+    if (n > 0) {
+        HIP_TRY(h, hipMemcpyAsync(b.rows, marker_rows, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        HIP_TRY(h, hipMemcpyAsync(b.cols, marker_cols, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        HIP_TRY(h, hipMemcpyAsync(b.labels, marker_labels, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    }
+    TIMED(h, s, 0, 1, HIP_TRY(h, run_marker_watershed(b.mask, H, W, b.rows, b.cols, b.labels, n, cap, b, s)));
+    int32_t misc[4] = {0, 0, 0, 0};
+    HIP_TRY(h, hipMemcpyAsync(out, b.out, px, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, ws_read_stages(st, b.rw, b.filled, b.d2, b.lab, px, s));
+    HIP_TRY(h, hipMemcpyAsync(misc, b.misc, sizeof(misc), hipMemcpyDeviceToHost, s));
+    WAIT_SET(h, s, 0, 1);
+    if (misc[1]) return fail(h, ECSEG_E_HIP, "marker_watershed: the heap overflowed its bound");
+    return ECSEG_OK;
+}
+
+// ecseg_marker_watershed_batch and ecseg_marker_watershed_batch_stages_debug, in the same way
+static int marker_watershed_batch_driver(ecseg_ctx* h, const uint8_t* masks, long long mask_bytes, const int64_t* images, int n_images,
+                                         const int32_t* marker_rows, const int32_t* marker_cols, const int32_t* marker_labels,
+                                         long long n_markers, uint8_t* out, const WsStages& st) {
+    DRIVER_OPEN(h);
+    const std::string me = "marker_watershed_batch: ";
+    if (n_images < 0 || n_images > ECSEG_WATERSHED_BATCH_MAX_IMAGES)
+        return fail(h, ECSEG_E_INVALID, me + "n_images must be between 0 and " + std::to_string(ECSEG_WATERSHED_BATCH_MAX_IMAGES));
+    if (mask_bytes < 0 || n_markers < 0 || n_markers >= (1ll << 31) || (n_images > 0 && (!masks || !images || !out)) ||
+        (n_markers > 0 && (!marker_rows || !marker_cols || !marker_labels)))
+        return fail(h, ECSEG_E_INVALID, me + "bad arguments");
+    clear_timings(h);                                        // (before the images are checked, where ecseg_marker_watershed clears behind its checks)
+    if (n_images == 0) return ECSEG_OK;
+    std::vector<long long> fg((size_t)n_images, 0);
+    WsBatchPlan pl;
+    std::string bad = ws_batch_plan(images, n_images, fg.data(), pl);         // the geometry first: nothing is read through a bad offset
+    if (!bad.empty()) return fail(h, ECSEG_E_INVALID, me + bad);
+    if ((long long)pl.span > mask_bytes) {
+        int i = 0;
+        while (pl.tab[(size_t)i].off + (long long)pl.tab[(size_t)i].H * pl.tab[(size_t)i].W <= mask_bytes) ++i;
+        return fail(h, ECSEG_E_INVALID, me + "image " + std::to_string(i) + " leaves the " + std::to_string(mask_bytes) + " bytes of masks");
+    }
+    for (int i = 0; i < n_images; ++i) {
+        const WsImage& w = pl.tab[(size_t)i];
+        if ((long long)w.first_marker + w.n_markers > n_markers)
+            return fail(h, ECSEG_E_INVALID, me + "image " + std::to_string(i) + ": its marker range leaves the " + std::to_string(n_markers) + " entries of the lists");
+        for (long long k = w.first_marker; k < (long long)w.first_marker + w.n_markers; ++k) {
+            const std::string who = me + "image " + std::to_string(i) + ": marker " + std::to_string(k);
+            if (marker_rows[k] < 0 || marker_rows[k] >= w.H || marker_cols[k] < 0 || marker_cols[k] >= w.W)
+                return fail(h, ECSEG_E_INVALID, who + " lies outside the image");
+            if (marker_labels[k] < 1) return fail(h, ECSEG_E_INVALID, who + " has a label below 1");
+        }
+        const uint8_t* m = masks + w.off;
+        const size_t px = (size_t)w.H * w.W;
+        size_t n = 0;
+        for (size_t p = 0; p < px; ++p) n += m[p] != 0;
+        fg[(size_t)i] = (long long)n;
+    }
+    bad = ws_batch_plan(images, n_images, fg.data(), pl);                     // now with the heaps
+    if (!bad.empty()) return fail(h, ECSEG_E_INVALID, me + bad);
+    USE_DEVICE(h);
+    int rc;
+    WatershedBatchBufs b{};
+    if ((rc = lay_out(h, h->call_arena, [&](Carver& c) { b = watershed_batch_bufs(c, pl.span, n_images, pl.n_markers, pl.heap_total); })))
+        return rc;
+    hipStream_t s = h->stream;
+    const size_t nm = pl.n_markers, ni = (size_t)n_images;
+    HIP_TRY(h, hipMemcpyAsync(b.mask, masks, pl.span, hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(b.tab, pl.tab.data(), ni * sizeof(WsImage), hipMemcpyHostToDevice, s));
+    if (nm > 0) {
+        HIP_TRY(h, hipMemcpyAsync(b.rows, marker_rows, nm * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        HIP_TRY(h, hipMemcpyAsync(b.cols, marker_cols, nm * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        HIP_TRY(h, hipMemcpyAsync(b.labels, marker_labels, nm * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    }
+    TIMED(h, s, 0, 1, HIP_TRY(h, run_marker_watershed_batch(n_images, pl.span, pl.max_px, pl.max_w, pl.max_markers, b, s)));
+    std::vector<int32_t> misc(ni * 4, 0);
+    HIP_TRY(h, hipMemcpyAsync(out, b.out, pl.span, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, ws_read_stages(st, b.rw, b.filled, b.d2, b.lab, pl.span, s));
+    HIP_TRY(h, hipMemcpyAsync(misc.data(), b.misc, misc.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));                     // (pl.tab and misc are read and written by the copies above: they live until here)
+    std::fill(out + pl.span, out + mask_bytes, (uint8_t)0);  // behind the last image
+    timed_set(h, 0, 1);
+    for (int i = 0; i < n_images; ++i)
+        if (misc[(size_t)i * 4 + 1]) return fail(h, ECSEG_E_HIP, me + "the heap of image " + std::to_string(i) + " overflowed its bound");
+    return ECSEG_OK;
+}
+
 extern "C" {
 
 // ---- NuSeT's network stage (src/utils.py:35-103) ---------------------------------------------------------------------------
@@ -148,42 +270,13 @@ int ecseg_rpn_proposals_last(ecseg_ctx* h, int A, const double* ref_anchors, int
 // ---- NuSeT's marker watershed (src/model_layers/marker_watershed.py:82-91) ----------------------------------------------------
 int ecseg_marker_watershed(ecseg_ctx* h, const uint8_t* mask, int H, int W, const int32_t* marker_rows, const int32_t* marker_cols,
                            const int32_t* marker_labels, long long n_markers, uint8_t* out) {
-    DRIVER_OPEN(h);
-    if (!mask || !out || H <= 0 || W <= 0) return fail(h, ECSEG_E_INVALID, "marker_watershed: bad arguments");
-    if (H > ECSEG_WATERSHED_MAX_EXTENT || W > ECSEG_WATERSHED_MAX_EXTENT)
-        return fail(h, ECSEG_E_INVALID, "marker_watershed: an extent above " + std::to_string(ECSEG_WATERSHED_MAX_EXTENT));
-    if (n_markers < 0 || n_markers >= (1ll << 31) || (n_markers > 0 && (!marker_rows || !marker_cols || !marker_labels)))
-        return fail(h, ECSEG_E_INVALID, "marker_watershed: n_markers must be between 0 and 2^31 - 1, with the three lists");
-    const int n = (int)n_markers;
-    for (int i = 0; i < n; ++i) {
-        if (marker_rows[i] < 0 || marker_rows[i] >= H || marker_cols[i] < 0 || marker_cols[i] >= W)
-            return fail(h, ECSEG_E_INVALID, "marker_watershed: marker " + std::to_string(i) + " lies outside the image");
-        if (marker_labels[i] < 1) return fail(h, ECSEG_E_INVALID, "marker_watershed: marker " + std::to_string(i) + " has a label below 1");
-    }
-    const size_t px = (size_t)H * W;
-    size_t fg = 0;
-    for (size_t p = 0; p < px; ++p) fg += mask[p] != 0;
-    if (5 * fg + 1 >= (1ull << 31)) return fail(h, ECSEG_E_INVALID, "marker_watershed: the mask holds too many pixels for one heap");
-    const int cap = (int)(5 * fg + 1);
-    USE_DEVICE(h);
-    int rc;
-    WatershedBufs b{};
-    if ((rc = lay_out(h, h->call_arena, [&](Carver& c) { b = watershed_bufs(c, H, W, n, cap); }))) return rc;
-    hipStream_t s = h->stream;
-    clear_timings(h);
-    HIP_TRY(h, hipMemcpyAsync(b.mask, mask, px, hipMemcpyHostToDevice, s));
-    if (n > 0) {
-        HIP_TRY(h, hipMemcpyAsync(b.rows, marker_rows, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
-        HIP_TRY(h, hipMemcpyAsync(b.cols, marker_cols, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
-        HIP_TRY(h, hipMemcpyAsync(b.labels, marker_labels, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    }
-    TIMED(h, s, 0, 1, HIP_TRY(h, run_marker_watershed(b.mask, H, W, b.rows, b.cols, b.labels, n, cap, b, s)));
-    int32_t misc[4] = {0, 0, 0, 0};
-    HIP_TRY(h, hipMemcpyAsync(out, b.out, px, hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipMemcpyAsync(misc, b.misc, sizeof(misc), hipMemcpyDeviceToHost, s));
-    WAIT_SET(h, s, 0, 1);
-    if (misc[1]) return fail(h, ECSEG_E_HIP, "marker_watershed: the heap overflowed its bound");
-    return ECSEG_OK;
+    return marker_watershed_driver(h, mask, H, W, marker_rows, marker_cols, marker_labels, n_markers, out, WsStages{});
+}
+
+int ecseg_marker_watershed_stages_debug(ecseg_ctx* h, const uint8_t* mask, int H, int W, const int32_t* marker_rows, const int32_t* marker_cols,
+                                        const int32_t* marker_labels, long long n_markers, uint8_t* out, int32_t* rw, uint8_t* filled,
+                                        int32_t* d2, int32_t* lab) {
+    return marker_watershed_driver(h, mask, H, W, marker_rows, marker_cols, marker_labels, n_markers, out, WsStages{rw, filled, d2, lab});
 }
 
 // ---- the same over a batch of images, one flood wave per image -----------------------------------------------------------------
@@ -200,66 +293,15 @@ long long ecseg_marker_watershed_batch_bytes(const int64_t* images, int n_images
 int ecseg_marker_watershed_batch(ecseg_ctx* h, const uint8_t* masks, long long mask_bytes, const int64_t* images, int n_images,
                                  const int32_t* marker_rows, const int32_t* marker_cols, const int32_t* marker_labels, long long n_markers,
                                  uint8_t* out) {
-    DRIVER_OPEN(h);
-    const std::string me = "marker_watershed_batch: ";
-    if (n_images < 0 || n_images > ECSEG_WATERSHED_BATCH_MAX_IMAGES)
-        return fail(h, ECSEG_E_INVALID, me + "n_images must be between 0 and " + std::to_string(ECSEG_WATERSHED_BATCH_MAX_IMAGES));
-    if (mask_bytes < 0 || n_markers < 0 || n_markers >= (1ll << 31) || (n_images > 0 && (!masks || !images || !out)) ||
-        (n_markers > 0 && (!marker_rows || !marker_cols || !marker_labels)))
-        return fail(h, ECSEG_E_INVALID, me + "bad arguments");
-    clear_timings(h);                                        // (before the images are checked, where ecseg_marker_watershed clears behind its checks)
-    if (n_images == 0) return ECSEG_OK;
-    std::vector<long long> fg((size_t)n_images, 0);
-    WsBatchPlan pl;
-    std::string bad = ws_batch_plan(images, n_images, fg.data(), pl);         // the geometry first: nothing is read through a bad offset
-    if (!bad.empty()) return fail(h, ECSEG_E_INVALID, me + bad);
-    if ((long long)pl.span > mask_bytes) {
-        int i = 0;
-        while (pl.tab[(size_t)i].off + (long long)pl.tab[(size_t)i].H * pl.tab[(size_t)i].W <= mask_bytes) ++i;
-        return fail(h, ECSEG_E_INVALID, me + "image " + std::to_string(i) + " leaves the " + std::to_string(mask_bytes) + " bytes of masks");
-    }
-    for (int i = 0; i < n_images; ++i) {
-        const WsImage& w = pl.tab[(size_t)i];
-        if ((long long)w.first_marker + w.n_markers > n_markers)
-            return fail(h, ECSEG_E_INVALID, me + "image " + std::to_string(i) + ": its marker range leaves the " + std::to_string(n_markers) + " entries of the lists");
-        for (long long k = w.first_marker; k < (long long)w.first_marker + w.n_markers; ++k) {
-            const std::string who = me + "image " + std::to_string(i) + ": marker " + std::to_string(k);
-            if (marker_rows[k] < 0 || marker_rows[k] >= w.H || marker_cols[k] < 0 || marker_cols[k] >= w.W)
-                return fail(h, ECSEG_E_INVALID, who + " lies outside the image");
-            if (marker_labels[k] < 1) return fail(h, ECSEG_E_INVALID, who + " has a label below 1");
-        }
-        const uint8_t* m = masks + w.off;
-        const size_t px = (size_t)w.H * w.W;
-        size_t n = 0;
-        for (size_t p = 0; p < px; ++p) n += m[p] != 0;
-        fg[(size_t)i] = (long long)n;
-    }
-    bad = ws_batch_plan(images, n_images, fg.data(), pl);                     // now with the heaps
-    if (!bad.empty()) return fail(h, ECSEG_E_INVALID, me + bad);
-    USE_DEVICE(h);
-    int rc;
-    WatershedBatchBufs b{};
-    if ((rc = lay_out(h, h->call_arena, [&](Carver& c) { b = watershed_batch_bufs(c, pl.span, n_images, pl.n_markers, pl.heap_total); })))
-        return rc;
-    hipStream_t s = h->stream;
-    const size_t nm = pl.n_markers, ni = (size_t)n_images;
-    HIP_TRY(h, hipMemcpyAsync(b.mask, masks, pl.span, hipMemcpyHostToDevice, s));
-    HIP_TRY(h, hipMemcpyAsync(b.tab, pl.tab.data(), ni * sizeof(WsImage), hipMemcpyHostToDevice, s));
-    if (nm > 0) {
-        HIP_TRY(h, hipMemcpyAsync(b.rows, marker_rows, nm * sizeof(int32_t), hipMemcpyHostToDevice, s));
-        HIP_TRY(h, hipMemcpyAsync(b.cols, marker_cols, nm * sizeof(int32_t), hipMemcpyHostToDevice, s));
-        HIP_TRY(h, hipMemcpyAsync(b.labels, marker_labels, nm * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    }
-    TIMED(h, s, 0, 1, HIP_TRY(h, run_marker_watershed_batch(n_images, pl.span, pl.max_px, pl.max_w, pl.max_markers, b, s)));
-    std::vector<int32_t> misc(ni * 4, 0);
-    HIP_TRY(h, hipMemcpyAsync(out, b.out, pl.span, hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipMemcpyAsync(misc.data(), b.misc, misc.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipStreamSynchronize(s));                     // (pl.tab and misc are read and written by the copies above: they live until here)
-    std::fill(out + pl.span, out + mask_bytes, (uint8_t)0);  // behind the last image
-    timed_set(h, 0, 1);
-    for (int i = 0; i < n_images; ++i)
-        if (misc[(size_t)i * 4 + 1]) return fail(h, ECSEG_E_HIP, me + "the heap of image " + std::to_string(i) + " overflowed its bound");
-    return ECSEG_OK;
+    return marker_watershed_batch_driver(h, masks, mask_bytes, images, n_images, marker_rows, marker_cols, marker_labels, n_markers, out,
+                                         WsStages{});
+}
+
+int ecseg_marker_watershed_batch_stages_debug(ecseg_ctx* h, const uint8_t* masks, long long mask_bytes, const int64_t* images, int n_images,
+                                              const int32_t* marker_rows, const int32_t* marker_cols, const int32_t* marker_labels,
+                                              long long n_markers, uint8_t* out, int32_t* rw, uint8_t* filled, int32_t* d2, int32_t* lab) {
+    return marker_watershed_batch_driver(h, masks, mask_bytes, images, n_images, marker_rows, marker_cols, marker_labels, n_markers, out,
+                                         WsStages{rw, filled, d2, lab});
 }
 
 // ---- NuSeT's clean-up behind the marker watershed (src/nuset_utils/normalization.py:25-37, src/utils.py:159-162) -----------------

@@ -65,6 +65,8 @@ extern "C" {
  * stat_fish images encoded in one device call, a wave per strip of any file; nothing existing changed.) */
 /* (still 5 - additive: ecseg_classify_nucleus_crops and ecseg_iseg_classifier_inputs_debug, interSeg's crops through both classifiers
  * without a host round trip; nothing existing changed.) */
+/* (still 5 - additive: ecseg_marker_watershed_stages_debug and ecseg_marker_watershed_batch_stages_debug, the marker watershed with its
+ * stage products (rw, filled, d2, lab) read back, for the tests of its kernels; nothing existing changed.) */
 #define ECSEG_ABI_VERSION 5
 
 #define ECSEG_OK             0
@@ -733,6 +735,23 @@ int ecseg_marker_watershed_batch(ecseg_ctx* h, const uint8_t* masks, long long m
  * image, 16 bytes per heap element (5 * foreground + 1 per image), 16 bytes of flags and a 40-byte table row per image, 12 bytes
  * per list entry in use, every buffer rounded up to 256 bytes.  0 for n_images = 0; -1 for arguments the call would refuse. */
 long long ecseg_marker_watershed_batch_bytes(const int64_t* images, int n_images, const long long* foreground);
+/* Test-only: ecseg_marker_watershed, the same driver and the same kernels in the same order, which also reads back what the stages
+ * left on the device, each (H, W) and each pointer optional (null: not copied):
+ *   rw     int32: markers_rw times the mask, the largest label over the disc's 29 offsets and 0 off the mask;
+ *   filled uint8: binary_fill_holes(mask), 0 / 1;
+ *   d2     int32: the squared distance to the nearest zero of `filled` on the mask's pixels and 0 off the mask (the flood reads it
+ *                 nowhere else); (row + 1)^2 + column^2 when `filled` holds no zero;
+ *   lab    int32: the flood's labels: 0 off the mask, where no marker reaches and on the lines, except that a marker pixel which
+ *                 becomes a line keeps its label.
+ * `out`, the status codes and the messages are ecseg_marker_watershed's; with four nulls the call is ecseg_marker_watershed. */
+int ecseg_marker_watershed_stages_debug(ecseg_ctx* h, const uint8_t* mask, int H, int W, const int32_t* marker_rows, const int32_t* marker_cols,
+                                        const int32_t* marker_labels, long long n_markers, uint8_t* out, int32_t* rw, uint8_t* filled,
+                                        int32_t* d2, int32_t* lab);
+/* Test-only: ecseg_marker_watershed_batch in the same way.  rw, filled, d2, lab: mask_bytes elements each (may be null), image i's
+ * H x W values from element `offset` on, as its bytes lie in masks; the elements outside every image are not defined. */
+int ecseg_marker_watershed_batch_stages_debug(ecseg_ctx* h, const uint8_t* masks, long long mask_bytes, const int64_t* images, int n_images,
+                                              const int32_t* marker_rows, const int32_t* marker_cols, const int32_t* marker_labels,
+                                              long long n_markers, uint8_t* out, int32_t* rw, uint8_t* filled, int32_t* d2, int32_t* lab);
 
 /* ---- NuSeT's clean-up behind the marker watershed ----------------------------------------------------------------------------
  * Replaces, for ONE image, clean_image (src/nuset_utils/normalization.py:25-37) and the final threshold of nuclei_segment

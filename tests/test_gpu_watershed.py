@@ -131,6 +131,13 @@ def test_marker_watershed_labels_and_order(gpu):
         assert np.array_equal(gpu.marker_watershed(c['mask'], r, cc, l), ref.watershed_from_markers(c['mask'], r, cc, l)), labels
     r2, c2, l2 = np.append(r, r[0]).astype(np.int32), np.append(cc, cc[0]).astype(np.int32), np.array([1, 2, 3, 9], np.int32)
     assert np.array_equal(gpu.marker_watershed(c['mask'], r2, c2, l2), ref.watershed_from_markers(c['mask'], r2, c2, l2))
+    # a later entry with a SMALLER label on the shared pixel (9 over 1 above: "the last wins" and "the largest wins" agree there).  The
+    # The second marker lies four columns beside the first: the discs overlap, and the overlap goes to 5 (over 2) or to 8 (had 8 stayed).
+    r3, c3 = np.array([r[0]] * 3, np.int32), np.array([cc[0], cc[0] + 4, cc[0]], np.int32)
+    l3 = np.array([8, 5, 2], np.int32)
+    want = ref.watershed_from_markers(c['mask'], r3, c3, l3)
+    assert not np.array_equal(want, ref.watershed_from_markers(c['mask'], r3[:2], c3[:2], l3[:2]))      # 8 on the shared pixel moves the line
+    assert np.array_equal(gpu.marker_watershed(c['mask'], r3, c3, l3), want)
     assert gpu.marker_watershed(c['mask'], [], [], []).max() == 0            # no marker: nothing is flooded
 
 

@@ -1,0 +1,310 @@
+"""The stages of NuSeT's marker watershed without a GPU: ``watershed_ref.stages`` (what tests/test_gpu_watershed_stages.py holds the
+device to, stage by stage) against a second, brute-force distance and a second fill on every case of tests/watershed_stage_cases.py;
+its ``out`` against ``watershed_from_markers`` on every committed case of tests/watershed_cases.py; the cases against what their
+names promise; and a list of MUTANTS - wrong restatements of one stage, each a slip a kernel could make - with the two facts that
+justify the stage comparison: every mutant shows in a stage product of a new case, and most of them pass the old comparison of the
+final ``mask * (lab != 0)`` on some committed case whose stage products they do change."""
+import os
+import sys
+
+import numpy as np
+import pytest
+from scipy import ndimage as ndi
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, HERE)
+import watershed_cases as old_cases          # noqa: E402
+import watershed_ref as ref                  # noqa: E402
+import watershed_stage_cases as cases        # noqa: E402
+
+from ecseg_amd import _lib                   # noqa: E402
+
+CASES = cases.all_cases()
+NAMES = [c['name'] for c in CASES]
+PRODUCTS = ref.STAGE_ORDER[:-1]              # rw, filled, d2, lab
+
+
+def _args(c):
+    return c['mask'], c['rows'], c['cols'], c['labels']
+
+
+def _old_marker_cases(subset):
+    """The committed cases of tests/watershed_cases.py that reach the watershed, as stage cases (their marker list is the restatement's)."""
+    src = old_cases.fixed_cases() + [old_cases.random_case(s) for s in range(12)] if subset else old_cases.all_cases()
+    out = []
+    for c in src:
+        mk = ref.marker_list(c['scores'], c['proposals'], c['mask'], c['min_score'])
+        if mk is not None:
+            out.append(dict(name=c['name'], mask=c['mask'], rows=mk[0], cols=mk[1], labels=mk[2]))
+    return out
+
+
+@pytest.fixture(scope='module')
+def want():
+    """``stages`` of every new case, computed once, with the flood's line pixels."""
+    out = []
+    for c in CASES:
+        lines = []
+        st = ref.stages(*_args(c), flood_fn=lambda m, rw, d2: ref.flood(m, rw, d2, lines=lines))
+        st['lines'] = lines
+        out.append(st)
+    return out
+
+
+def test_entry_points_are_declared_and_exported():
+    hdr = open(os.path.join(HERE, '..', 'include', 'ecseg_hip.h')).read()
+    assert 'still 5 - additive: ecseg_marker_watershed_stages_debug' in hdr and '#define ECSEG_ABI_VERSION 5' in hdr and _lib.ABI_VERSION == 5
+    for name, method in (('ecseg_marker_watershed_stages_debug', 'marker_watershed_stages'),
+                         ('ecseg_marker_watershed_batch_stages_debug', 'marker_watershed_batch_stages')):
+        assert name in _lib.EXPORTS and hasattr(_lib.Handle, method)
+
+
+# ---- a second fill, by labels: the mutants of the fill are this function with one argument changed ---------------------------------
+def fill_by_labels(mask, structure=None, last_row=True, last_col=True):
+    """The mask plus the background components (``structure``: None = 4-connected) with no pixel on the border."""
+    m = np.asarray(mask) != 0
+    H, W = m.shape
+    lab, n = ndi.label(~m, structure=structure)
+    edge = np.zeros((H, W), bool)
+    edge[0, :] = edge[:, 0] = True
+    if last_row:
+        edge[H - 1, :] = True
+    if last_col:
+        edge[:, W - 1] = True
+    open_ = np.zeros(n + 1, bool)
+    open_[lab[edge]] = True
+    open_[0] = True                                          # (label 0 is the mask itself)
+    return m | ~open_[lab]
+
+
+@pytest.mark.parametrize('k', range(len(CASES)), ids=NAMES)
+def test_stages_tie_to_the_second_distance_and_fill(want, k):
+    c, st = CASES[k], want[k]
+    m = c['mask'] != 0
+    assert [st[key].dtype for key in ref.STAGE_ORDER] == [np.int32, np.uint8, np.int32, np.int32, np.int32]
+    assert np.array_equal(st['filled'], fill_by_labels(c['mask']))
+    brute = ref.squared_edt_brute(st['filled'])
+    assert np.array_equal(brute, ref.squared_distance(c['mask']))            # on every pixel, the filled holes too
+    assert np.array_equal(st['d2'], brute * m)
+    assert not st['rw'][~m].any() and not st['lab'][~m].any() and (st['filled'][m] == 1).all()
+    assert np.array_equal(st['out'], ref.watershed_from_markers(*_args(c)))
+    kept = np.zeros(m.shape, bool)                           # lab is rw grown: a marker pixel keeps its label, line or not
+    kept[st['rw'] != 0] = True
+    assert np.array_equal(st['lab'][kept], st['rw'][kept])
+    for r, cc in st['lines']:
+        assert st['lab'][r, cc] == st['rw'][r, cc]           # a line pixel holds 0 unless it was a marker pixel
+
+
+def test_stages_out_equals_watershed_from_markers_on_the_committed_cases():
+    old = _old_marker_cases(subset=False)
+    assert len(old) >= 60
+    for c in old:
+        assert np.array_equal(ref.stages(*_args(c))['out'], ref.watershed_from_markers(*_args(c))), c['name']
+
+
+def test_cases_cover_what_they_name(want):
+    g = lambda name: (CASES[NAMES.index(name)], want[NAMES.index(name)])
+    shapes = {c['mask'].shape for c in CASES}
+    assert set(cases.EXTENTS) <= shapes and {255, 256, 257} <= {h * w for h, w in shapes}
+    assert min(min(s) for s in shapes) == 1 and max(max(s) for s in shapes) <= 257 and sum(h * w > 10000 for h, w in shapes) == 1
+    assert len(cases.SEEDS) == 48 and all(max(c['mask'].shape) <= 96 for c in CASES[-48:])
+    c, st = g('all_ones')
+    assert st['filled'].all() and st['d2'][0, 0] == 1 and st['d2'][8, 69] == 81 + 69 * 69      # the distance to (-1, 0)
+    c, st = g('all_zeros')
+    assert not st['filled'].any() and not st['rw'].any() and not st['lab'].any()
+    c, st = g('zero_column_63')                              # columns without a zero on both sides, in both blocks of the column pass
+    assert st['d2'][3, 0] == 63 * 63 and st['d2'][3, 129] == 66 * 66 and st['d2'][0, 64] == 1
+    c, st = g('zero_near_in_the_column_far_in_the_row')
+    assert st['d2'][20, 5] == 9 and st['d2'][20, 59] == 1
+    c, st = g('zero_near_in_the_row_far_in_the_column')
+    assert st['d2'][5, 20] == 4 and st['d2'][34, 20] == 1
+    c, st = g('single_zero_middle')
+    assert not c['mask'].all() and st['filled'].all() and st['d2'][4, 34] == 25 + 34 * 34 and st['d2'][4, 35] == 0
+    c, st = g('single_zero_top_right')
+    assert st['d2'][8, 0] == 64 + 69 * 69
+    c, st = g('hole_closed')
+    assert st['filled'][6, 8] == 1 and c['mask'][6, 8] == 0 and st['d2'][6, 8] == 0
+    c, st = g('hole_open_to_the_border')
+    assert st['filled'][4, 9] == 0
+    c, st = g('hole_closed_only_across_a_diagonal')
+    assert st['filled'][2, 2] == 1 and st['filled'][4, 4] == 1 and st['filled'][1, 1] == 0
+    assert fill_by_labels(c['mask'], structure=ref.FULL8)[4, 4] == 0
+    for name, open_px, hole_px in (('background_touching_the_last_row_only', (11, 5), (4, 9)),
+                                   ('background_touching_the_last_column_only', (4, 13), (8, 3)),
+                                   ('background_in_the_last_pixel_only', (11, 13), (5, 5))):
+        c, st = g(name)
+        assert c['mask'][0, :].all() and c['mask'][:, 0].all() and c['mask'][open_px] == 0 and c['mask'][hole_px] == 0
+        assert st['filled'][open_px] == 0 and st['filled'][hole_px] == 1
+    c, st = g('markers_on_the_background')
+    assert not c['mask'][c['rows'], c['cols']].any() and set(np.unique(st['rw'])) == {0, 1, 2, 4}     # label 3 is too far
+    c, st = g('overlapping_discs_larger_label_first')
+    assert st['rw'][5, 6] == 9 and st['rw'][5, 10] == 4
+    c, st = g('one_pixel_twice_smaller_label_last')
+    assert st['rw'][5, 5] == 2 and 7 not in st['rw']
+    c, st = g('one_pixel_three_times')
+    assert st['rw'][5, 5] == 1 and 8 not in st['rw'] and 3 not in st['rw']
+    c, st = g('labels_up_to_int32_max')
+    assert st['lab'].max() == cases.INT32_MAX and (st['lab'] == cases.INT32_MAX - 1).any()
+    c, st = g('every_foreground_pixel_a_marker')
+    assert np.array_equal(st['rw'] != 0, c['mask'] != 0) and np.array_equal(st['lab'], st['rw'])
+    c, st = g('no_marker')
+    assert not st['lab'].any() and not st['out'].any() and st['d2'].any()
+    c, st = g('plateau_strip')
+    assert set(np.unique(st['d2'])) == {0, 1} and (st['rw'] != 0).sum() > 30
+    c, st = g('marker_pixels_become_lines')
+    marker_lines = [p for p in st['lines'] if st['rw'][p]]
+    assert marker_lines and all(st['lab'][p] != 0 and st['out'][p] == 1 for p in marker_lines)
+    assert any(st['lab'][p] == 0 for p in st['lines'])
+    c, st = g('component_no_marker_reaches')
+    assert c['mask'][5, 23] == 1 and not st['lab'][3:9, 20:27].any() and st['lab'][16, 20] == 3
+
+
+# ---- the mutants --------------------------------------------------------------------------------------------------------------
+def _dilate(offsets):
+    def fn(markers):
+        H, W = markers.shape
+        pad = np.zeros((H + 6, W + 6), markers.dtype)
+        pad[3:-3, 3:-3] = markers
+        out = np.zeros_like(markers)
+        for dy, dx in offsets:
+            np.maximum(out, pad[3 + dy:3 + dy + H, 3 + dx:3 + dx + W], out=out)
+        return out
+    return fn
+
+
+def _largest_index(mask, rows, cols, labels, **kw):
+    """The dilation takes the largest LIST INDEX under the disc, then looks its label up."""
+    idx = ref.dilate_disk3(ref.marker_image(np.asarray(mask).shape, rows, cols, np.arange(1, len(rows) + 1)))
+    lut = np.concatenate([[0], np.asarray(labels, np.int64)])
+    return S(mask, rows, cols, labels, marker_fn=lambda *a: idx, dilate_fn=lambda i: lut[i], **kw)
+
+
+def _first_entry_wins(shape, rows, cols, labels):
+    return ref.marker_image(shape, rows[::-1], cols[::-1], labels[::-1])
+
+
+def _edt_row_search_cut(filled):
+    """The column pass, then a row minimum that looks no further than 63 columns to either side."""
+    f = np.asarray(filled) != 0
+    H, W = f.shape
+    INF = 1 << 30
+    g = np.full((H, W), INF, np.int64)
+    for x in range(W):
+        zy = np.nonzero(~f[:, x])[0]
+        if zy.size:
+            g[:, x] = np.abs(np.arange(H)[:, None] - zy[None, :]).min(axis=1)
+    if not (~f).any():
+        return ref.squared_edt(filled)
+    out = np.full((H, W), 0x7fffffff, np.int64)
+    for dx in range(max(-63, 1 - W), min(63, W - 1) + 1):
+        src = g[:, max(0, dx):W + min(0, dx)]
+        dst = out[:, max(0, -dx):W - max(0, dx)]
+        np.minimum(dst, np.where(src < INF, src * src + dx * dx, 0x7fffffff), out=dst)
+    return out
+
+
+def _edt_no_zero_transposed(filled):
+    f = np.asarray(filled) != 0
+    if f.all():
+        yy, xx = np.mgrid[:f.shape[0], :f.shape[1]].astype(np.int64)
+        return yy ** 2 + (xx + 1) ** 2                       # the distance to (0, -1)
+    return ref.squared_edt(filled)
+
+
+class _HeapRightOnTies(ref._Heap):
+    def pop(self):
+        a = self.a
+        top = a[0]
+        last = a.pop()
+        if a:
+            a[0] = last
+            i, n = 0, len(a)
+            while True:
+                l, r, s = 2 * i + 1, 2 * i + 2, i
+                if l >= n:
+                    break
+                if a[l][:2] < a[i][:2]:
+                    s = l
+                if r < n and a[r][:2] < a[i][:2] and a[r][:2] <= a[l][:2]:
+                    s = r
+                if s == i:
+                    break
+                a[i], a[s] = a[s], a[i]
+                i = s
+        return top
+
+
+def _flood_line_loses_label(mask, rw, d2):
+    lines = []
+    lab = ref.flood(mask, rw, d2, lines=lines)
+    for p in lines:
+        lab[p] = 0
+    return lab
+
+
+_FLOODS = {}
+
+
+def _flood_once(mask, rw, d2):
+    """``ref.flood``, remembered by its inputs: a mutant of an earlier stage that changes neither rw nor d2 on the mask floods nothing anew."""
+    m = np.asarray(mask) != 0
+    key = (m.shape, m.tobytes(), (rw * m).astype(np.int64).tobytes(), (d2 * m).astype(np.int64).tobytes())
+    if key not in _FLOODS:
+        _FLOODS[key] = ref.flood(mask, rw, d2)
+    return _FLOODS[key].copy()
+
+
+def S(*a, **kw):
+    kw.setdefault('flood_fn', _flood_once)
+    return ref.stages(*a, **kw)
+
+
+MUTANTS = [
+    ('dilation with dy^2 + dx^2 <= 8', lambda *a: S(*a, dilate_fn=_dilate([o for o in ref.DISK3 if o[0] ** 2 + o[1] ** 2 <= 8]))),
+    ('dilation by a 5 x 5 square', lambda *a: S(*a, dilate_fn=_dilate([(dy, dx) for dy in range(-2, 3) for dx in range(-2, 3)]))),
+    ('the largest list index, not the largest label', _largest_index),
+    ('the first entry wins on a shared pixel', lambda *a: S(*a, marker_fn=_first_entry_wins)),
+    ('rw not masked', lambda *a: S(*a, mask_rw=False)),
+    ('holes filled with an 8-connected background', lambda *a: S(*a, fill_fn=lambda m: fill_by_labels(m, structure=ref.FULL8))),
+    ('the border marking skips the last row', lambda *a: S(*a, fill_fn=lambda m: fill_by_labels(m, last_row=False))),
+    ('the border marking skips the last column', lambda *a: S(*a, fill_fn=lambda m: fill_by_labels(m, last_col=False))),
+    ('row search cut off at 64 columns', lambda *a: S(*a, edt_fn=_edt_row_search_cut)),
+    ('d2 without the fill', lambda *a: S(*a, edt_fn=lambda filled: ref.squared_edt(a[0]))),
+    ('no zero: the distance to (0, -1)', lambda *a: S(*a, edt_fn=_edt_no_zero_transposed)),
+    ('pop prefers the right child on a tie', lambda *a: S(*a, flood_fn=lambda m, rw, d2: ref.flood(m, rw, d2, heap=_HeapRightOnTies))),
+    ('another neighbour order', lambda *a: S(*a, flood_fn=lambda m, rw, d2: ref.flood(m, rw, d2, neighbours=((0, -1), (-1, 0), (0, 1), (1, 0))))),
+    ('a line pixel loses its marker label', lambda *a: S(*a, flood_fn=_flood_line_loses_label)),
+]
+
+
+def _caught(mutant, case_list, truths):
+    """Per case: (a stage product differs, the final out differs)."""
+    res = []
+    for c, t in zip(case_list, truths):
+        got = mutant(*_args(c))
+        res.append((any(not np.array_equal(got[key], t[key]) for key in PRODUCTS), not np.array_equal(got['out'], t['out'])))
+    return res
+
+
+def test_mutants_show_in_the_stages_and_hide_in_the_final_output(want):
+    """Every mutant differs from ``stages`` in a stage product of a new case; at least half of them leave the final ``out`` of a
+    committed tests/watershed_cases.py case as it is while changing one of that case's stage products - the old comparison (the 28
+    fixed cases and seeds 0 .. 11, those with markers) cannot see them there."""
+    old = _old_marker_cases(subset=True)
+    old_truth = [S(*_args(c)) for c in old]
+    rows, hidden = [], 0
+    for name, mutant in MUTANTS:
+        new = _caught(mutant, CASES, want)
+        com = _caught(mutant, old, old_truth)
+        row = dict(name=name, new_stage=sum(s for s, _ in new), new_out=sum(o for _, o in new), old_stage=sum(s for s, _ in com),
+                   old_out=sum(o for _, o in com), old_hidden=sum(s and not o for s, o in com))
+        rows.append(row)
+        hidden += row['old_hidden'] > 0
+    print('\n%-50s | new cases (%d): stages  out | committed cases (%d): stages  out  stage-only' % ('mutant', len(CASES), len(old)))
+    for r in rows:
+        print('%-50s | %21d %4d | %28d %4d %11d' % (r['name'], r['new_stage'], r['new_out'], r['old_stage'], r['old_out'], r['old_hidden']))
+    assert len(MUTANTS) == 14 and len(old) >= 30
+    for r in rows:
+        assert r['new_stage'] > 0, 'no new case shows: ' + r['name']
+        assert r['new_stage'] >= r['new_out'] and r['old_stage'] >= r['old_out']       # out is a function of the stage products
+    assert 2 * hidden >= len(MUTANTS), '%d of %d mutants hide behind the final output of a committed case' % (hidden, len(MUTANTS))

@@ -82,12 +82,35 @@ def dilate_disk3(markers):
     return out
 
 
-def squared_distance(mask):
-    """d^2 of ``distance_transform_edt(binary_fill_holes(mask))`` as int64.  A filled mask without a zero pixel gets scipy's answer,
-    the distance to (-1, 0)."""
-    filled = ndi.binary_fill_holes(np.asarray(mask) != 0)
-    d = ndi.distance_transform_edt(filled)
+def fill_holes(mask):
+    """``binary_fill_holes`` with its default structure: the background components that do not reach the border, 4-connected, are set."""
+    return ndi.binary_fill_holes(np.asarray(mask) != 0)
+
+
+def squared_edt(filled):
+    """d^2 of ``distance_transform_edt`` as int64.  An image without a zero pixel gets scipy's answer, the distance to (-1, 0)."""
+    d = ndi.distance_transform_edt(np.asarray(filled) != 0)
     return np.rint(d * d).astype(np.int64)
+
+
+def squared_distance(mask):
+    """d^2 of ``distance_transform_edt(binary_fill_holes(mask))`` as int64."""
+    return squared_edt(fill_holes(mask))
+
+
+def squared_edt_brute(filled):
+    """``squared_edt`` a second time with nothing shared: per pixel the minimum of dy^2 + dx^2 over every zero pixel, in integers, no
+    scipy.  O(pixels x zeros): for small images.  Without a zero, (row + 1)^2 + column^2: scipy's documented distance to (-1, 0)."""
+    f = np.asarray(filled) != 0
+    H, W = f.shape
+    yy, xx = np.mgrid[:H, :W].astype(np.int64)
+    zy, zx = (v.astype(np.int64) for v in np.nonzero(~f))
+    if zy.size == 0:
+        return (yy + 1) ** 2 + xx ** 2
+    out = np.empty((H, W), np.int64)
+    for y in range(H):                                       # a row at a time: (W, zeros) values
+        out[y] = ((y - zy[None, :]) ** 2 + (xx[y][:, None] - zx[None, :]) ** 2).min(axis=1)
+    return out
 
 
 class _Heap:
@@ -131,13 +154,14 @@ class _Heap:
         return top
 
 
-def flood(mask, markers_rw, d2):
+def flood(mask, markers_rw, d2, heap=_Heap, neighbours=NEIGHBOURS, lines=None):
     """The watershed with lines on one binary heap over the whole image: int64 labels, 0 on lines (a marker pixel that becomes a line
-    keeps its label), outside the mask and where no marker reaches."""
+    keeps its label), outside the mask and where no marker reaches.  ``lines``: a list that receives the (row, column) of every line
+    pixel in the order they are found.  ``heap`` and ``neighbours`` are what tests/test_watershed_stages.py swaps for wrong ones."""
     m = (np.asarray(mask) != 0).copy()
     H, W = m.shape
     out = (markers_rw * m).astype(np.int64)
-    hp = _Heap()
+    hp = heap()
     for r, c in zip(*np.nonzero(out)):
         hp.push((-int(d2[r, c]), 0, int(r), int(c), int(r), int(c)))
     age = 0
@@ -145,13 +169,15 @@ def flood(mask, markers_rw, d2):
         _, _, r, c, sr, sc = hp.pop()
         if out[r, c] and (r, c) != (sr, sc):
             continue
-        labs = set(int(out[r + dy, c + dx]) for dy, dx in NEIGHBOURS
+        labs = set(int(out[r + dy, c + dx]) for dy, dx in neighbours
                    if 0 <= r + dy < H and 0 <= c + dx < W and m[r + dy, c + dx] and out[r + dy, c + dx])
         if len(labs) > 1:
             m[r, c] = False
+            if lines is not None:
+                lines.append((r, c))
             continue
         out[r, c] = out[sr, sc]
-        for dy, dx in NEIGHBOURS:
+        for dy, dx in neighbours:
             y, x = r + dy, c + dx
             if 0 <= y < H and 0 <= x < W and m[y, x] and not out[y, x]:
                 age += 1
@@ -165,6 +191,28 @@ def watershed_from_markers(mask, rows, cols, labels, flood_fn=flood):
     rw = dilate_disk3(marker_image(mask.shape, rows, cols, labels))
     lab = flood_fn(mask, rw, squared_distance(mask))
     return (mask.astype(np.int64) * (lab != 0)).astype(np.int32)
+
+
+def stages(mask, rows, cols, labels, marker_fn=marker_image, dilate_fn=dilate_disk3, mask_rw=True, fill_fn=fill_holes, edt_fn=squared_edt,
+           flood_fn=flood):
+    """``watershed_from_markers`` with everything on the way, as the device keeps it (ecseg_marker_watershed_stages_debug):
+    rw int32 = markers_rw * mask; filled uint8 0 / 1; d2 int32 = the squared distance on the mask's pixels and 0 off the mask (the flood
+    reads it nowhere else; ``squared_edt_brute(filled)`` says what the filled holes would hold); lab int32 = the flood's labels; out
+    int32 = ``pred_mask * contour``.  The keyword arguments are the stages themselves: tests/test_watershed_stages.py swaps one for a
+    wrong one and asks who notices."""
+    mask = np.asarray(mask)
+    m = mask != 0
+    rw = dilate_fn(marker_fn(mask.shape, rows, cols, labels))
+    if mask_rw:
+        rw = rw * m
+    filled = fill_fn(mask)
+    d2 = edt_fn(filled) * m
+    lab = flood_fn(mask, rw, d2)
+    out = (mask.astype(np.int64) * (lab != 0)).astype(np.int32)
+    return dict(rw=rw.astype(np.int32), filled=filled.astype(np.uint8), d2=d2.astype(np.int32), lab=lab.astype(np.int32), out=out)
+
+
+STAGE_ORDER = ('rw', 'filled', 'd2', 'lab', 'out')
 
 
 def watershed(scores, proposals, mask, min_score, flood_fn=flood):
