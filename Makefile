@@ -37,6 +37,15 @@ asan_tiff_decode:
 	    ecseg_amd/csrc/host_codec.cpp tools/asan/tiff_decode_fuzz.cpp -o /tmp/ecseg_tiff_decode_fuzz
 	/tmp/ecseg_tiff_decode_fuzz
 
+# and for its Deflate strips: the per-strip routine (csrc/tiff_inflate_strip.h) compiled for the host, lanes as a loop, against the
+# host reader's rule made of the same zlib calls, on built-in streams, seeded valid streams and seeded mutations;
+# tests/test_tiff_inflate.py builds and runs it on the tests' corpus too
+.PHONY: asan_tiff_inflate
+asan_tiff_inflate:
+	g++ -std=c++17 -O1 -g -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=all \
+	    tools/asan/tiff_inflate_fuzz.cpp -lz -o /tmp/ecseg_tiff_inflate_fuzz
+	/tmp/ecseg_tiff_inflate_fuzz
+
 # and for the batched reader: the layout function (csrc/tiff_decode_batch.h) and the batched strip walk over packed batches with
 # corrupt and truncated files; tests/test_tiff_decode_batch.py builds and runs it
 .PHONY: asan_tiff_decode_batch

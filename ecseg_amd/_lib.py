@@ -1,5 +1,6 @@
 """ctypes binding of libecseg_hip.so (include/ecseg_hip.h).  There is no CPU fallback: when the library is missing
 or no MI355X is visible, every entry point raises."""
+import contextlib
 import ctypes as C
 import os
 import time
@@ -25,6 +26,7 @@ EXPORTS = [
     'ecseg_png_labels_encode', 'ecseg_meta_segment_files', 'ecseg_get_file_timings', 'ecseg_png_labels_stream_size',
     'ecseg_ccl_pass_debug', 'ecseg_meta_inference_stages_debug',
     'ecseg_tiff_decode_batch', 'ecseg_tiff_decode_batch_bytes', 'ecseg_tiff_decode_batch_routes', 'ecseg_tiff_decode_batch_counts',
+    'ecseg_tiff_decode_routes_ex', 'ecseg_tiff_decode_batch_routes_ex', 'ecseg_tiff_decode_batch_counts_ex', 'ecseg_tiff_decode_batch_bytes_ex',
     'ecseg_meta_segment_tiffs', 'ecseg_meta_segment_tiffs_files', 'ecseg_prefetch_tiffs', 'ecseg_get_read_timings',
     'ecseg_png_channel_bound', 'ecseg_png_channel_encode', 'ecseg_overlay_files',
     'ecseg_tiff_encode_batch', 'ecseg_tiff_encode_batch_bytes', 'ecseg_fish_render_tiff_batch',
@@ -158,6 +160,10 @@ def load_library():
     lib.ecseg_tiff_decode_batch_bytes.argtypes = [vp, C.c_longlong, vp, i32]; lib.ecseg_tiff_decode_batch_bytes.restype = C.c_longlong
     lib.ecseg_tiff_decode_batch_routes.argtypes = [vp, C.c_longlong, vp, i32]
     lib.ecseg_tiff_decode_batch_counts.argtypes = [vp, C.c_longlong]
+    lib.ecseg_tiff_decode_routes_ex.argtypes = [vp, C.c_longlong, i32]
+    lib.ecseg_tiff_decode_batch_routes_ex.argtypes = [vp, C.c_longlong, vp, i32, i32]
+    lib.ecseg_tiff_decode_batch_counts_ex.argtypes = [vp, C.c_longlong, i32]
+    lib.ecseg_tiff_decode_batch_bytes_ex.argtypes = [vp, C.c_longlong, vp, i32, i32]; lib.ecseg_tiff_decode_batch_bytes_ex.restype = C.c_longlong
     lib.ecseg_min_cut.argtypes = [vp, vp, C.c_longlong, vp, i32, i32, vp, vp]
     lib.ecseg_nuset_forward.argtypes = [vp, vp, i32, i32, i32, i32, vp]
     lib.ecseg_rpn_proposals.argtypes = [vp, vp, vp, i32, i32, i32, vp, i32, i32, i32, C.c_float, i32, i32, C.POINTER(C.c_int32), vp, vp, vp]
@@ -327,6 +333,8 @@ class Handle:
 
     def set_option(self, key, value):
         self._check(self.lib.ecseg_set_option(self.h, key.encode(), int(value)), 'ecseg_set_option(%s)' % key)
+        if key == 'tiff_deflate_on_device':  # the mirror the ``deflate`` arguments of tiff_decode / tiff_decode_many restore from
+            self.tiff_deflate_on_device = bool(value)
         if key == 'images_per_group':        # the same knob as set_images_per_group: keep the mirror the OOM retry restores from
             self.images_per_group = int(value)
 
@@ -945,10 +953,29 @@ class Handle:
         self._check(self.lib.ecseg_tiff_encode(self.h, _ptr(im), H, W, spp, int(bool(invert)), _ptr(out), cap, C.byref(n)), 'ecseg_tiff_encode')
         return out[:n.value].tobytes()
 
-    def tiff_decode(self, data):
+    @contextlib.contextmanager
+    def _deflate_option(self, deflate):
+        """The handle option ``tiff_deflate_on_device`` set to ``deflate`` for one call (None: left as it is)."""
+        before = getattr(self, 'tiff_deflate_on_device', False)
+        if deflate is None or bool(deflate) == before:
+            yield
+            return
+        self.set_option('tiff_deflate_on_device', int(bool(deflate)))
+        try:
+            yield
+        finally:
+            self.set_option('tiff_deflate_on_device', int(before))
+
+    def tiff_decode(self, data, deflate=None):
         """The bytes of a TIFF file -> what ``image_io.read_tiff`` returns for that file, (H, W) or (H, W, spp) uint8 / uint16, with
         every strip decoded on the device (ecseg_tiff_decode); None for a file that is left to the host readers (ECSEG_E_UNSUPPORTED:
-        tiles, BigTIFF, PackBits, Deflate).  Whether a file is worth sending here is ``image_io.imread``'s question (ecseg_tiff_decode_routes).  A corrupt file raises, with code -1."""
+        tiles, BigTIFF, PackBits, Deflate).  Whether a file is worth sending here is ``image_io.imread``'s question (ecseg_tiff_decode_routes).  A corrupt file raises, with code -1.
+        ``deflate``: True / False: the call runs with the handle option ``tiff_deflate_on_device`` on / off - on, Deflate strips
+        (compression 8 and 32946) are decoded too, and such a file is an array or an error, not None; None: as the option stands."""
+        with self._deflate_option(deflate):
+            return self._tiff_decode(data)
+
+    def _tiff_decode(self, data):
         buf = _file_u8(data)
         H, W, spp, bits = C.c_int(), C.c_int(), C.c_int(), C.c_int()
         shape = (C.byref(H), C.byref(W), C.byref(spp), C.byref(bits))
@@ -977,13 +1004,17 @@ class Handle:
                                                      _ptr(offs), _ptr(shapes), _ptr(status)), 'ecseg_tiff_decode_batch')
         return shapes, status
 
-    def tiff_decode_many(self, datas, budget_bytes=8 << 30):
+    def tiff_decode_many(self, datas, budget_bytes=8 << 30, deflate=None):
         """``tiff_decode`` over a list of files at once (ecseg_tiff_decode_batch: a wave per strip, the strips of all files side by side).
         -> a list with, per file, the array ``tiff_decode`` returns for it alone, None where it returns None, or the error it raises -
         returned in its place, not raised (``segment_many``'s rule), so that one bad file costs the others nothing.  The files are packed
         back to back (``pack_file_images``) and go in one call while the sum of what ecseg_tiff_decode_batch_bytes says each needs
         stays within ``budget_bytes`` of device scratch, else in several calls over consecutive files; a file that exceeds the budget
-        alone goes alone."""
+        alone goes alone.  ``deflate``: as in ``tiff_decode``."""
+        with self._deflate_option(deflate):
+            return self._tiff_decode_many(datas, budget_bytes)
+
+    def _tiff_decode_many(self, datas, budget_bytes):
         out = [None] * len(datas)
         todo = []                                              # (position, bytes as uint8)
         for k, data in enumerate(datas):
@@ -996,7 +1027,8 @@ class Handle:
             return out
         buf, ranges = pack_file_images([b for _, b in todo])     # packed once: every call reads its files through its rows of the table
         # what each file needs alone, asked once per file: their sum is at least what a call over them needs (every slot rounds up alone)
-        needs = [self.lib.ecseg_tiff_decode_batch_bytes(_ptr(buf), buf.size, _ptr(np.ascontiguousarray(ranges[k:k + 1])), 1) for k in range(len(todo))]
+        deflate = int(getattr(self, 'tiff_deflate_on_device', False))
+        needs = [self.lib.ecseg_tiff_decode_batch_bytes_ex(_ptr(buf), buf.size, _ptr(np.ascontiguousarray(ranges[k:k + 1])), 1, deflate) for k in range(len(todo))]
         chunks, lo, held = [], 0, 0
         for hi, need in enumerate(needs):
             if hi > lo and (need < 0 or held < 0 or held + need > budget_bytes):

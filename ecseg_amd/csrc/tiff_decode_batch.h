@@ -18,6 +18,11 @@
 
 namespace ecseg {
 
+// The codec of a file's strips.  TD_RAW and TD_LZW strips are tiffb_unstrip_kernel's, TD_DEFLATE strips tiffb_inflate_kernel's; each
+// kernel answers TD_OTHER_KERNEL (no status word) for a strip of the other.
+enum : uint8_t { TD_RAW = 0, TD_LZW = 1, TD_DEFLATE = 2 };
+constexpr uint32_t TD_OTHER_KERNEL = 2;
+
 struct TdFile {
     uint64_t file_off;       // of the file image in the packed upload
     uint64_t n_bytes;
@@ -28,7 +33,7 @@ struct TdFile {
     uint32_t H, rps, W, spp, bps;
     uint32_t first_strip;    // global index of strip 0 (grid x of tiffb_unstrip_kernel); the file has ceil(H / rps) strips
     uint32_t first_row;      // global index of row 0 (grid x of tiffb_unpredict_kernel); the file has H rows
-    uint8_t lzw, swap, predictor, in_batch;      // LZW or uncompressed strips; 16-bit samples in the other byte order; horizontal predictor; 0: a file of zero strips
+    uint8_t codec, swap, predictor, in_batch;    // TD_RAW / TD_LZW / TD_DEFLATE strips; 16-bit samples in the other byte order; horizontal predictor; 0: a file of zero strips
     uint32_t pad;
 };
 static_assert(sizeof(TdFile) == 80, "the device table is an array of 80-byte rows, copied as it is");
@@ -37,7 +42,8 @@ static_assert(sizeof(TdFile) == 80, "the device table is an array of 80-byte row
 struct TdFileIn {
     uint64_t src_off = 0, n_bytes = 0, dst_off = 0;
     uint32_t n_table = 0, H = 0, W = 0, spp = 1, bps = 1, rps = 1;
-    bool lzw = false, swap = false, predictor = false;
+    uint8_t codec = TD_RAW;
+    bool swap = false, predictor = false;
     bool in_batch = false;   // false: the file takes no part (zero strips, zero rows, nothing uploaded for it)
 };
 
@@ -48,6 +54,7 @@ struct TdBatchLayout {
     uint64_t table_words = 0;                    // uint32_t of all strip tables
     uint64_t n_strips = 0, n_rows = 0;           // the two grids
     bool any_u8_predictor = false, any_u16_pass = false;     // which tiffb_unpredict_kernel launches the batch needs
+    bool any_deflate = false;                    // whether it needs tiffb_inflate_kernel
 };
 
 constexpr uint64_t TD_BATCH_MAX_GRID = (1ull << 31) - 1;     // grid dimension x
@@ -84,13 +91,14 @@ inline std::string td_batch_layout(const std::vector<TdFileIn>& in, TdBatchLayou
         t.file_off = f.src_off - L.src_base; t.n_bytes = f.n_bytes; t.raster_off = f.dst_off - L.dst_base;
         t.line = (uint64_t)f.W * f.spp * f.bps;
         t.n_table = f.n_table; t.H = f.H; t.rps = f.rps; t.W = f.W; t.spp = f.spp; t.bps = f.bps;
-        t.lzw = f.lzw; t.swap = f.swap && f.bps == 2; t.predictor = f.predictor;
+        t.codec = f.codec; t.swap = f.swap && f.bps == 2; t.predictor = f.predictor;
         L.table_words += 2ull * f.n_table;
         L.n_strips += td_file_strips(t);
         L.n_rows += f.H;
         if (L.n_strips > TD_BATCH_MAX_GRID || L.n_rows > TD_BATCH_MAX_GRID) return "the batch holds 2^31 strips or rows, or more";
         L.any_u16_pass = L.any_u16_pass || (t.bps == 2 && (t.swap || t.predictor));
         L.any_u8_predictor = L.any_u8_predictor || (t.bps == 1 && t.predictor);
+        L.any_deflate = L.any_deflate || t.codec == TD_DEFLATE;
     }
     return std::string();
 }

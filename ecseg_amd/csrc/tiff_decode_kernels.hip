@@ -10,12 +10,15 @@
 // td_strip finds the strip's bytes in the file and clamps them to the file; one status word per strip (0, or 1: corrupt stream /
 // offset behind the file).  A strip the tables do not have is zero-filled.  One launch serves LZW and uncompressed files mixed; the
 // strips of different files share nothing, which is where a batch of files of few strips finds its parallelism.
+// tiffb_inflate_kernel: the same grid for the strips of Deflate files (ti_inflate_strip, tiff_inflate_strip.h), launched only for a
+// batch that holds one; each of the two kernels leaves the other's strips at once.
 // tiffb_unpredict_kernel: one wave per row, after all strips: 16-bit samples of a big-endian file are swapped to native order, then
 // the horizontal predictor is undone per sample channel (stride spp) as an inclusive wave scan over 64 samples with a carry
 // into the next 64, modulo 2^8 or 2^16 (td_unpredict_row).
 // tiffb_status_kernel: the strip words folded into one word per file.
 #include "common.h"
 #include "tiff_decode_strip.h"
+#include "tiff_inflate_strip.h"
 
 namespace ecseg {
 
@@ -53,7 +56,16 @@ __global__ __launch_bounds__(64) void tiffb_unstrip_kernel(const TdFile* __restr
                                                            const uint32_t* __restrict__ tables, uint8_t* rasters, uint32_t* __restrict__ status) {
     __shared__ TdLds L;
     const uint32_t st = tdb_unstrip(tab, n_files, files, tables, rasters, blockIdx.x, L);
-    if (threadIdx.x == 0) status[blockIdx.x] = st;
+    if (threadIdx.x == 0 && st != TD_OTHER_KERNEL) status[blockIdx.x] = st;
+}
+
+// The same grid for the Deflate strips (ti_inflate_strip, tiff_inflate_strip.h): a workgroup whose strip is the kernel's above
+// returns at once, as that kernel's do here.  The two write disjoint status words and disjoint rows of the rasters.
+__global__ __launch_bounds__(64) void tiffb_inflate_kernel(const TdFile* __restrict__ tab, uint32_t n_files, const uint8_t* __restrict__ files,
+                                                           const uint32_t* __restrict__ tables, uint8_t* rasters, uint32_t* __restrict__ status) {
+    __shared__ TiLds L;
+    const uint32_t st = tdb_inflate(tab, n_files, files, tables, rasters, blockIdx.x, L);
+    if (threadIdx.x == 0 && st != TD_OTHER_KERNEL) status[blockIdx.x] = st;
 }
 
 // Grid x is the global row; files of the other sample size, and files with neither swap nor predictor, return at once.
@@ -80,6 +92,7 @@ hipError_t run_tiff_decode_batch(const TiffDecodeBatchBufs& b, const TdBatchLayo
     hipError_t e = hipMemsetAsync(b.file_status, 0, (size_t)n * sizeof(uint32_t), s);
     if (e != hipSuccess || ns == 0) return e;
     hipLaunchKernelGGL(tiffb_unstrip_kernel, dim3(ns), dim3(64), 0, s, b.tab, n, b.files, b.tables, b.rasters, b.strip_status);
+    if (L.any_deflate) hipLaunchKernelGGL(tiffb_inflate_kernel, dim3(ns), dim3(64), 0, s, b.tab, n, b.files, b.tables, b.rasters, b.strip_status);
     if (L.any_u16_pass) hipLaunchKernelGGL(tiffb_unpredict_kernel<uint16_t>, dim3(nr), dim3(64), 0, s, b.tab, n, b.rasters);
     if (L.any_u8_predictor) hipLaunchKernelGGL(tiffb_unpredict_kernel<uint8_t>, dim3(nr), dim3(64), 0, s, b.tab, n, b.rasters);
     hipLaunchKernelGGL(tiffb_status_kernel, dim3((ns + 255) / 256), dim3(256), 0, s, b.tab, n, b.strip_status, ns, b.file_status);

@@ -176,16 +176,17 @@ TD_FN uint32_t td_find_file(const TdFile* tab, uint32_t n, uint32_t idx, bool ro
 }
 
 // Global strip `strip` of a batch, by one wave: td_lzw_strip or td_raw_strip on the strip's file.  Returns its status word (0, or 1:
-// corrupt stream / offset behind the file), the same in every lane.
+// corrupt stream / offset behind the file), the same in every lane; TD_OTHER_KERNEL for a Deflate strip (tdb_inflate, tiff_inflate_strip.h).
 TD_FN uint32_t tdb_unstrip(const TdFile* tab, uint32_t n_files, const uint8_t* files, const uint32_t* tables, uint8_t* rasters, uint32_t strip,
                            TdLds& L) {
     const TdFile& f = tab[td_first(td_find_file(tab, n_files, strip, false))];
+    if (f.codec == TD_DEFLATE) return TD_OTHER_KERNEL;
     const uint32_t k = strip - f.first_strip;
     if (!f.in_batch || (unsigned long long)k * f.rps >= f.H) return 0u;      // (the grid has the strips of the table: never)
     const uint32_t* offs = tables + f.table_off;
     const TdStrip t = td_strip(k, files + f.file_off, f.n_bytes, offs, offs + f.n_table, f.n_table, f.H, f.line, f.rps, rasters + f.raster_off);
     uint32_t st = 0;
-    if (f.lzw) st = td_lzw_strip(t.src, t.have, t.dst, t.want, L);           // (have == 0: nothing is read, the strip is zeros)
+    if (f.codec == TD_LZW) st = td_lzw_strip(t.src, t.have, t.dst, t.want, L);           // (have == 0: nothing is read, the strip is zeros)
     else td_raw_strip(t, 64u);
     return t.behind_file ? 1u : st;
 }

@@ -24,19 +24,33 @@ int parse_tiff(const uint8_t* buf, size_t n, TiffInfo* t);
 // decode at once.  The threshold is the measurement of DESIGN.md 5.9 (tools/time_tiff_decode.py, a 1040 x 1392 RGB scene): the
 // device call is faster than ecseg_tiff_read at 1040 strips (3.8 against 11.2 ms) and slower at 208 (14.0 against 11.1 ms), at 70, at
 // 17 and at 1; 1040 is the smallest count measured at which it wins.  Uncompressed strips lose on the device (6.9 against 1.3 ms:
-// the copies to and from the device cost more than the host's one memcpy) and Deflate has no device decoder: both stay on the host.
+// the copies to and from the device cost more than the host's one memcpy): they stay on the host.
+//   Deflate strips (compression 8 and 32946; tiffb_inflate_kernel) count only for a caller that asks (`deflate`: the handle option
+// tiff_deflate_on_device is on, ecseg_tiff_decode_routes_ex) and only from the thresholds below on, which are the Deflate tables of
+// DESIGN.md 5.9 (tools/time_tiff_decode.py --deflate): the smallest measured strip counts at which the device call's maximum is
+// below ecseg_tiff_read's minimum (TIFF_DEFLATE_NEVER would say that no measured cell wins: then only an explicit ecseg_tiff_decode /
+// ecseg_tiff_decode_batch call decodes a Deflate file on the device).  Measured 2026-10-20 on the 1040 x 1392 RGB scene, zlib level 6:
+// a single file wins at 1040 strips (4.73 ms, at most 5.01, against at least 15.66 of the host) and loses at 208 (14.48 against 14.15)
+// and at 70 (42.56 against 14.18); of the sets, those of 70, 140 and 208 strips lose and every measured set from 280 strips up wins
+// (280: four files of 70 strips, at most 51.29 ms against at least 54.92), the stat_fish pairs (1248 strips per image) included.
 constexpr size_t TIFF_DEVICE_MIN_STRIPS = 1040;
-inline bool tiff_goes_to_device(const TiffInfo& t) {
-    if (t.comp != 5 || t.rps == 0) return false;
+constexpr size_t TIFF_DEFLATE_NEVER = ~(size_t)0;
+constexpr size_t TIFF_DEFLATE_DEVICE_MIN_STRIPS = 1040;
+constexpr size_t TIFF_DEFLATE_BATCH_DEVICE_MIN_STRIPS = 280;
+inline bool tiff_is_deflate(const TiffInfo& t) { return t.comp == 8 || t.comp == 32946; }
+inline bool tiff_goes_to_device(const TiffInfo& t, bool deflate = false) {
+    const bool defl = deflate && tiff_is_deflate(t);
+    if ((t.comp != 5 && !defl) || t.rps == 0) return false;
     const size_t nstrips = ((size_t)t.H + t.rps - 1) / t.rps;
-    return nstrips >= TIFF_DEVICE_MIN_STRIPS && t.off.size() >= nstrips;
+    return nstrips >= (defl ? TIFF_DEFLATE_DEVICE_MIN_STRIPS : TIFF_DEVICE_MIN_STRIPS) && t.off.size() >= nstrips;
 }
 
 // The routing rule for a set of files that would go in one ecseg_tiff_decode_batch call, the only place that decides it
 // (ecseg_tiff_decode_batch_routes asks it for image_io.imread_many).  The strips of different files decode side by side as the strips
 // of one file do, so what counts is their sum: the set goes when the LZW strips of its files - those ecseg_tiff_decode accepts,
-// whatever their own strip count - are at least TIFF_BATCH_DEVICE_MIN_STRIPS together.  Uncompressed and Deflate files are never
-// counted (and never sent: tiff_batch_counts is false for them), for the reasons above.  The measurement is the batch table of
+// whatever their own strip count - are at least TIFF_BATCH_DEVICE_MIN_STRIPS together.  Uncompressed files are never counted (and
+// never sent: tiff_batch_counts is false for them), for the reasons above; Deflate files are counted only with `deflate`, their
+// strips are summed on their own against TIFF_DEFLATE_BATCH_DEVICE_MIN_STRIPS, and the set goes when either sum reaches its threshold.  The measurement is the batch table of
 // DESIGN.md 5.9 (tools/time_tiff_decode.py --batch: 1 to 32 files of the 1040 x 1392 RGB scene at 1, 5 and 15 rows per strip, and the
 // stat_fish pair): every measured set of 1040 strips or more is read faster through the device than by ecseg_tiff_read on one core
 // (the batch's maximum below the host's minimum), at each of the three plans; so is every measured set from 416 strips up, and the
@@ -46,17 +60,19 @@ inline bool tiff_goes_to_device(const TiffInfo& t) {
 // ecseg_tiff_decode accepts.
 constexpr size_t TIFF_BATCH_DEVICE_MIN_STRIPS = 1040;
 constexpr unsigned long long TIFF_BATCH_DEVICE_MAX_STRIP_BYTES = 15ull * 1392 * 3;
-inline bool tiff_batch_counts(const TiffInfo& t) {
-    if (t.comp != 5 || t.rps == 0 || t.H == 0) return false;
+inline bool tiff_batch_counts(const TiffInfo& t, bool deflate = false) {
+    const bool defl = deflate && tiff_is_deflate(t) && TIFF_DEFLATE_BATCH_DEVICE_MIN_STRIPS != TIFF_DEFLATE_NEVER;
+    if ((t.comp != 5 && !defl) || t.rps == 0 || t.H == 0) return false;
     const size_t nstrips = ((size_t)t.H + t.rps - 1) / t.rps;
     return t.off.size() >= nstrips &&                        // (a strip table shorter than the image stays on the host, as in the single-file rule)
            (unsigned long long)(t.rps < t.H ? t.rps : t.H) * t.W * t.spp * (t.bits / 8) <= TIFF_BATCH_DEVICE_MAX_STRIP_BYTES;
 }
-inline bool tiff_batch_goes_to_device(const TiffInfo* const* files, size_t n) {
-    size_t strips = 0;
+inline bool tiff_batch_goes_to_device(const TiffInfo* const* files, size_t n, bool deflate = false) {
+    size_t strips = 0, deflate_strips = 0;
     for (size_t i = 0; i < n; ++i)
-        if (tiff_batch_counts(*files[i])) strips += ((size_t)files[i]->H + files[i]->rps - 1) / files[i]->rps;
-    return strips >= TIFF_BATCH_DEVICE_MIN_STRIPS;
+        if (tiff_batch_counts(*files[i], deflate))
+            (tiff_is_deflate(*files[i]) ? deflate_strips : strips) += ((size_t)files[i]->H + files[i]->rps - 1) / files[i]->rps;
+    return strips >= TIFF_BATCH_DEVICE_MIN_STRIPS || deflate_strips >= TIFF_DEFLATE_BATCH_DEVICE_MIN_STRIPS;
 }
 
 }  // namespace ecseg

@@ -224,17 +224,23 @@ def image_shape(path):
     return read_tiff(path).shape
 
 
-def tiff_goes_to_device(data):
-    """The routing rule of the device reader (csrc/tiff_parse.h, the one place that states it) on the bytes of a file."""
+def tiff_goes_to_device(data, deflate=False):
+    """The routing rule of the device reader (csrc/tiff_parse.h, the one place that states it) on the bytes of a file.  ``deflate``:
+    Deflate files count too, from their own measured threshold on (ecseg_tiff_decode_routes_ex)."""
     buf = np.frombuffer(data, np.uint8)
-    return bool(buf.size) and load_library().ecseg_tiff_decode_routes(buf.ctypes.data_as(C.c_void_p), buf.size) == 1
+    if not buf.size:
+        return False
+    if deflate:
+        return load_library().ecseg_tiff_decode_routes_ex(buf.ctypes.data_as(C.c_void_p), buf.size, 1) == 1
+    return load_library().ecseg_tiff_decode_routes(buf.ctypes.data_as(C.c_void_p), buf.size) == 1
 
 
-def imread(path, handle=None):
+def imread(path, handle=None, deflate=False):
     """``skimage.io.imread`` stand-in for the inputs ``get_imgs`` globs (``*.tif`` and ``*.npy``, src/utils.py:105-110).
     ``handle``: anything with ``Handle.tiff_decode``: a ``.tif`` that the routing rule sends to the device (ecseg_tiff_decode_routes:
     LZW files of many strips) is decoded there, and by the readers of this module when that returns None (a layout it leaves to them)
-    or finds the file corrupt or unreadable, so that the error raised is theirs."""
+    or finds the file corrupt or unreadable, so that the error raised is theirs.  ``deflate``: the rule is asked with Deflate files
+    counting, and the handle decodes such a file (``Handle.tiff_decode(data, deflate=True)``)."""
     if str(path).lower().endswith('.npy'):
         return np.load(path)
     if handle is not None and hasattr(handle, 'tiff_decode') and str(path).lower().endswith(('.tif', '.tiff')):
@@ -242,7 +248,10 @@ def imread(path, handle=None):
         try:
             with open(path, 'rb') as f:
                 data = f.read()
-            if tiff_goes_to_device(data):
+            if deflate:
+                if tiff_goes_to_device(data, deflate=True):
+                    a = handle.tiff_decode(data, deflate=True)
+            elif tiff_goes_to_device(data):
                 a = handle.tiff_decode(data)
         except OSError:
             pass
@@ -254,17 +263,19 @@ def imread(path, handle=None):
     return read_tiff(path)
 
 
-def tiff_batch_goes_to_device(datas):
+def tiff_batch_goes_to_device(datas, deflate=False):
     """The routing rule for a set of files (csrc/tiff_parse.h, the one place that states it) on their bytes -> (whether the set goes to
-    the device in one ``Handle.tiff_decode_many``, per file whether the rule counts it: the files that are sent when it goes)."""
+    the device in one ``Handle.tiff_decode_many``, per file whether the rule counts it: the files that are sent when it goes).
+    ``deflate``: Deflate files count too, from their own measured threshold on (the ``_ex`` functions)."""
     lib = load_library()
     bufs = [d if isinstance(d, np.ndarray) else np.frombuffer(d, np.uint8) for d in datas]
-    counts = [bool(b.size) and lib.ecseg_tiff_decode_batch_counts(b.ctypes.data_as(C.c_void_p), b.size) == 1 for b in bufs]
+    deflate = int(bool(deflate))
+    counts = [bool(b.size) and lib.ecseg_tiff_decode_batch_counts_ex(b.ctypes.data_as(C.c_void_p), b.size, deflate) == 1 for b in bufs]
     sent = [b for b, c in zip(bufs, counts) if c]
     if not sent:
         return False, counts
     buf, ranges = pack_file_images(sent)                     # (no copy where the files lie in one buffer, as imread_many reads them)
-    goes = lib.ecseg_tiff_decode_batch_routes(buf.ctypes.data_as(C.c_void_p), buf.size, ranges.ctypes.data_as(C.c_void_p), len(ranges)) == 1
+    goes = lib.ecseg_tiff_decode_batch_routes_ex(buf.ctypes.data_as(C.c_void_p), buf.size, ranges.ctypes.data_as(C.c_void_p), len(ranges), deflate) == 1
     return goes, counts
 
 
@@ -282,12 +293,13 @@ def tiff_shape(data):
     return int(t[257][0]), int(t[256][0]), int(t.get(277, (1,))[0]), int(t.get(258, (1,))[0])
 
 
-def imread_many(paths, handle=None):
+def imread_many(paths, handle=None, deflate=False):
     """``imread`` over a list of paths -> a list with, per path, the array ``imread(path)`` returns or the exception it raises, in its
     place.  ``handle``: anything with ``Handle.tiff_decode_many``: the ``.tif`` / ``.tiff`` files the routing rule for a set counts
     (ecseg_tiff_decode_batch_routes: LZW files, whatever their strip count) are decoded in one call when together they are worth it;
     every other file, and every file that call answers with None or an error, is read by ``imread(path)``, so that the samples and
-    the errors are always its own."""
+    the errors are always its own.  ``deflate``: Deflate files count in the rule and are decoded by the call
+    (``Handle.tiff_decode_many(datas, deflate=True)``)."""
     out = [None] * len(paths)
     if handle is not None and hasattr(handle, 'tiff_decode_many'):
         tiffs = [(k, str(path)) for k, path in enumerate(paths) if str(path).lower().endswith(('.tif', '.tiff'))]
@@ -309,10 +321,11 @@ def imread_many(paths, handle=None):
                 continue
             held.append((k, pool[at:at + got]))
             at += n
-        goes, counts = tiff_batch_goes_to_device([d for _, d in held])
+        goes, counts = tiff_batch_goes_to_device([d for _, d in held], deflate=True) if deflate else tiff_batch_goes_to_device([d for _, d in held])
         if goes:
             sent = [e for e, c in zip(held, counts) if c]
-            for (k, _), a in zip(sent, handle.tiff_decode_many([d for _, d in sent])):
+            many = handle.tiff_decode_many([d for _, d in sent], deflate=True) if deflate else handle.tiff_decode_many([d for _, d in sent])
+            for (k, _), a in zip(sent, many):
                 if isinstance(a, np.ndarray):
                     out[k] = a
     for k, path in enumerate(paths):

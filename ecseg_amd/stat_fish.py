@@ -223,16 +223,23 @@ def render(img, channels, thresholded, boundaries):
     return original, with_segmentation(original, boundaries, 1), np.stack(lsq[::-1], axis=-1)
 
 
-def read_image(path, handle, max_probes=2, tiff_read_on_device=False, pre=None):
+def read_image(path, handle, max_probes=2, tiff_read_on_device=False, pre=None, tiff_read_deflate=False):
     """-> ((H, W, C) uint8 image, its (blue, green, red[, aqua]) channel indices) (src/stat_fish.py:206-212).  C is 3, or 4 for a
     four-channel ``.npy`` when ``max_probes`` (the entries of ``color_sensitivity``) is at least 3.  ``tiff_read_on_device``: a TIFF's
     strips are decoded by ``handle.tiff_decode`` (``image_io.imread(path, handle=handle)``).  ``pre``: what ``image_io.imread_many``
-    returned for the file, an array or the exception, when it was read ahead with its chunk (config key ``tiff_read_batch``)."""
+    returned for the file, an array or the exception, when it was read ahead with its chunk (config key ``tiff_read_batch``).
+    ``tiff_read_deflate`` (the config key, with ``tiff_read_on_device``): Deflate files count for the device reader too
+    (``image_io.imread(path, handle=handle, deflate=True)``)."""
     from . import image_io
     try:
         if isinstance(pre, Exception):
             raise pre
-        I = pre if pre is not None else image_io.imread(path, handle=handle if tiff_read_on_device else None)
+        if pre is not None:
+            I = pre
+        elif tiff_read_on_device and tiff_read_deflate:
+            I = image_io.imread(path, handle=handle, deflate=True)
+        else:
+            I = image_io.imread(path, handle=handle if tiff_read_on_device else None)
     except Exception as e:
         raise ImageError('cannot be read (%s)' % e)
     is_npy = path.lower().endswith('.npy')
@@ -261,16 +268,21 @@ def read_image(path, handle, max_probes=2, tiff_read_on_device=False, pre=None):
     return np.ascontiguousarray(I), (2, 1, 0)
 
 
-def read_mask(path, handle=None, pre=None):
+def read_mask(path, handle=None, pre=None, tiff_read_deflate=False):
     """``handle``: the mask's strips are decoded by ``handle.tiff_decode`` (config key ``tiff_read_on_device``).  ``pre``: as
-    ``read_image``'s."""
+    ``read_image``'s, and so is ``tiff_read_deflate``."""
     from . import image_io
     if not os.path.exists(path):
         raise ImageError('has no nucleus mask %s' % path)
     try:
         if isinstance(pre, Exception):
             raise pre
-        m = pre if pre is not None else image_io.imread(path, handle=handle)
+        if pre is not None:
+            m = pre
+        elif handle is not None and tiff_read_deflate:
+            m = image_io.imread(path, handle=handle, deflate=True)
+        else:
+            m = image_io.imread(path, handle=handle)
     except Exception as e:
         raise ImageError('nucleus mask %s cannot be read (%s)' % (path, e))
     if m.ndim == 3 and m.shape[2] == 1:
@@ -281,7 +293,7 @@ def read_mask(path, handle=None, pre=None):
 
 
 def process_image(path, mask_path, out_root, params, scale, handle, stats=None, use_min_cut=False, segment=None, tiff_on_device=False,
-                  tiff_read_on_device=False, pre_read=None, pending=None):
+                  tiff_read_on_device=False, pre_read=None, pending=None, tiff_read_deflate=False):
     """One image of src/stat_fish.py:199-308 -> (CSV rows, the scale that was used); the rows of a four-channel image carry the aqua
     fields of ``csv_columns(3)``, and ``stats['probes']`` becomes 3 once such an image was seen (it may have no nucleus and no row).  The three colour files come from ``handle.fish_render`` when the handle has it, else from
     ``render``, which writes the same bytes.  ``use_min_cut`` (:221-224): the label map comes
@@ -291,7 +303,7 @@ def process_image(path, mask_path, out_root, params, scale, handle, stats=None, 
     ``handle.fish_render_tiff``, which renders them there too, the mask and the min-cut picture by ``handle.tiff_encode`` - and
     reaches the disk as the file image these return; the bytes are those of the host writers.  ``tiff_read_on_device`` (the config key
     of that name): the image and the mask are read with ``handle.tiff_decode`` where the device reader takes the file; the samples are
-    those of the host readers.  ``pre_read`` (config key ``tiff_read_batch``): ``(image, mask)`` as ``image_io.imread_many`` returned them
+    those of the host readers; ``tiff_read_deflate`` (the config key of that name): Deflate files count for it too.  ``pre_read`` (config key ``tiff_read_batch``): ``(image, mask)`` as ``image_io.imread_many`` returned them
     for ``path`` and ``mask_path`` - an array, the exception, or None for "read it here" - when the files were read ahead with their chunk.
     ``pending`` (config key ``tiff_write_batch`` above 1, with ``tiff_on_device``): a list; instead of rendering and writing its TIFF
     files the image appends its pending TIFF work to it - the render inputs, the mask, the optional min-cut picture, the file names
@@ -304,9 +316,9 @@ def process_image(path, mask_path, out_root, params, scale, handle, stats=None, 
     t0 = time.perf_counter()
     img_name = os.path.basename(path)[:-4]
     pre_image, pre_mask = pre_read if pre_read is not None else (None, None)
-    I, channels = read_image(path, handle, len(params['color_sensitivity']), tiff_read_on_device, pre_image)
+    I, channels = read_image(path, handle, len(params['color_sensitivity']), tiff_read_on_device, pre_image, tiff_read_deflate)
     blue = channels[0]
-    mask = read_mask(mask_path, handle if tiff_read_on_device else None, pre_mask) if segment is None else segment(I[:, :, blue])
+    mask = read_mask(mask_path, handle if tiff_read_on_device else None, pre_mask, tiff_read_deflate) if segment is None else segment(I[:, :, blue])
     imheight, imwidth = mask.shape
     I = np.ascontiguousarray(I[:imheight, :imwidth])
     mask = np.ascontiguousarray(mask[:I.shape[0], :I.shape[1]])
@@ -559,6 +571,11 @@ def main(argv=None, handle=None):
         if read_batch > 1 and handle is not None and not hasattr(handle, 'tiff_decode_many'):
             raise ConfigError('tiff_read_batch: %d needs the batched device TIFF reader (tiff_decode_many), which the handle in use does not '
                               'have; only tiff_read_batch: 1 works on it' % read_batch)
+        read_deflate = var.get('tiff_read_deflate', False)
+        if not isinstance(read_deflate, bool):
+            raise ConfigError('tiff_read_deflate must be true or false (true, with tiff_read_on_device: Deflate input TIFFs count for the device reader too)')
+        if not tiff_read_on_device:
+            read_deflate = False                             # the key belongs to the device reader
         write_batch = var.get('tiff_write_batch', 1)
         if isinstance(write_batch, bool) or not isinstance(write_batch, int) or write_batch < 1:
             raise ConfigError('tiff_write_batch must be a positive integer (how many images have their TIFF files encoded in one call of the '
@@ -606,7 +623,7 @@ def main(argv=None, handle=None):
         chunk = image_paths[k:k + read_batch]
         files = chunk + ([mask_of(p) for p in chunk if os.path.exists(mask_of(p))] if segmenter is None else [])
         t0 = time.perf_counter()
-        got = dict(zip(files, image_io.imread_many(files, handle=handle)))
+        got = dict(zip(files, image_io.imread_many(files, handle=handle, deflate=True) if read_deflate else image_io.imread_many(files, handle=handle)))
         seen['read'] = seen.get('read', 0.0) + time.perf_counter() - t0
         for p in chunk:
             ahead[p] = (got[p], got.get(mask_of(p)) if segmenter is None else None)
@@ -656,7 +673,7 @@ def main(argv=None, handle=None):
                 for k, p in enumerate(chunk, at):
                     try:
                         read_ahead(k)
-                        I, channels = read_image(p, handle, len(params['color_sensitivity']), tiff_read_on_device, ahead.get(p, (None, None))[0])
+                        I, channels = read_image(p, handle, len(params['color_sensitivity']), tiff_read_on_device, ahead.get(p, (None, None))[0], read_deflate)
                         blues.append((p, np.ascontiguousarray(I[:, :, channels[0]])))
                     except ImageError as e:
                         hooks[p] = handed_in(e)              # (process_image meets and reports it at the image's turn)
@@ -671,7 +688,8 @@ def main(argv=None, handle=None):
                         read_ahead(k)
                     img_rows, scale = process_image(p, mask_of(p), out_root, params, scale, handle,
                                                      stats=seen, use_min_cut=use_min_cut, segment=hooks.get(p), tiff_on_device=tiff_on_device,
-                                                     tiff_read_on_device=tiff_read_on_device, pre_read=ahead.pop(p, None), pending=pending)
+                                                     tiff_read_on_device=tiff_read_on_device, pre_read=ahead.pop(p, None), pending=pending,
+                                                     tiff_read_deflate=read_deflate)
                     rows += img_rows
                 except ImageError as e:
                     print(p, '-', e)

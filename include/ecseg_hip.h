@@ -67,6 +67,9 @@ extern "C" {
  * without a host round trip; nothing existing changed.) */
 /* (still 5 - additive: ecseg_marker_watershed_stages_debug and ecseg_marker_watershed_batch_stages_debug, the marker watershed with its
  * stage products (rw, filled, d2, lab) read back, for the tests of its kernels; nothing existing changed.) */
+/* (still 5 - additive: option "tiff_deflate_on_device" with ecseg_tiff_decode_routes_ex, ecseg_tiff_decode_batch_routes_ex,
+ * ecseg_tiff_decode_batch_counts_ex and ecseg_tiff_decode_batch_bytes_ex, Deflate strips decoded on the device behind an option that
+ * is off by default; nothing existing changed.) */
 #define ECSEG_ABI_VERSION 5
 
 #define ECSEG_OK             0
@@ -222,7 +225,9 @@ int ecseg_set_images_per_group(ecseg_ctx* h, int n);
  * the half-empty last round of workgroups of the deep layers (one image: 11.3 -> 10.4 ms); 1..8: that many lanes; results are
  * bit-identical for every value), "blocking_wait" (1 (default): the wait for a launch group sleeps on an event created
  * with hipEventBlockingSync; 0: hipStreamSynchronize), "min_cut_lds_pixels" (0 .. ECSEG_MIN_CUT_LDS_PIXELS (default): windows of
- * ecseg_min_cut with more pixels than this keep their state in global memory instead of LDS; the results do not depend on it). */
+ * ecseg_min_cut with more pixels than this keep their state in global memory instead of LDS; the results do not depend on it),
+ * "tiff_deflate_on_device" (0 (default): ecseg_tiff_decode and ecseg_tiff_decode_batch leave Deflate files to the host,
+ * ECSEG_E_UNSUPPORTED; 1: they decode them on the device - see "TIFF files decoded on the device" below). */
 int ecseg_set_option(ecseg_ctx* h, const char* key, int value);
 
 /* ---- meta_preprocess (src/image_tools.py:86-101) ---------------------------------------------------------- */
@@ -509,8 +514,8 @@ int ecseg_fish_render_tiff_batch(ecseg_ctx* h, int n_images, const uint8_t* cons
  * ecseg_tiff_info plus ecseg_tiff_read return for the same bytes - ECSEG_OK, the shape in *H, *W, *samples_per_pixel,
  * *bits_per_sample and the samples in dst as native-endian (H, W, spp), strips that end early or are missing zero-filled - or
  * ECSEG_E_INVALID (not a TIFF, a corrupt IFD, a strip offset behind the file, a corrupt LZW stream in any strip: dst is not
- * written).  ECSEG_E_UNSUPPORTED: everything ecseg_tiff_info leaves to the Python reader, and Deflate strips, which stay on the
- * host (also strips of 2 GiB or more); the shape is reported then too
+ * written).  ECSEG_E_UNSUPPORTED: everything ecseg_tiff_info leaves to the Python reader, and Deflate strips unless the handle
+ * option "tiff_deflate_on_device" is on (below; also strips of 2 GiB or more); the shape is reported then too
  * when the file has one.  dst == NULL: only the shape (and the ECSEG_E_UNSUPPORTED verdict).  dst_bytes below H * W * spp *
  * bits / 8: ECSEG_E_INVALID with nothing written.  file: n_bytes of host memory, uploaded by the call; one synchronous call,
  * scratch (file image, strip tables, raster, status words) from the handle's call arena; device time of the kernels in
@@ -552,6 +557,22 @@ long long ecseg_tiff_decode_batch_bytes(const uint8_t* files, long long files_by
  * is the batch table of DESIGN.md 5.9.  No device work. */
 int ecseg_tiff_decode_batch_routes(const uint8_t* files, long long files_bytes, const int64_t* file_ranges, int n_files);
 int ecseg_tiff_decode_batch_counts(const uint8_t* file, long long n_bytes);
+/* Deflate strips (compression 8, and 32946 of older writers) on the device, all opt-in.  ecseg_set_option(h, "tiff_deflate_on_device",
+ * 1) (default 0): ecseg_tiff_decode and ecseg_tiff_decode_batch on that handle take such files - one wave per strip in a kernel of
+ * its own beside the LZW one (csrc/tiff_inflate_strip.h: each strip a zlib stream of its own, matches copied in the raster, Adler-32
+ * checked), mixed freely with LZW and uncompressed files in a batch - and return ECSEG_OK or ECSEG_E_INVALID for them where they
+ * returned ECSEG_E_UNSUPPORTED, by the host reader's rules (ecseg_tiff_read: a short stream zero-filled, a long one cut, every zlib
+ * data error corrupt; a stream that ends before the strip is full and before its own end is corrupt, as uncompress of zlib 1.2.9 and
+ * later has it).  Tiled, PackBits and BigTIFF files stay ECSEG_E_UNSUPPORTED; ecseg_meta_segment_tiffs does not read the option.
+ *   The four functions above that take no handle answer as before; these take the switch as `deflate` (0: the same answers).  With
+ * it a Deflate file counts from its own thresholds on (csrc/tiff_parse.h, the Deflate tables of DESIGN.md 5.9: a single file from
+ * 1040 strips, a set from 280 Deflate strips together, the smallest measured counts at which the device call's maximum is below
+ * ecseg_tiff_read's minimum; strips that decode to more than 62640 bytes are not counted, nothing was measured there).  ecseg_tiff_decode_batch_bytes_ex: the arena bytes with Deflate files taken (the
+ * Deflate kernel keeps its tables in LDS and needs nothing more from the arena than an LZW file of the same tags). */
+int ecseg_tiff_decode_routes_ex(const uint8_t* file, long long n_bytes, int deflate);
+int ecseg_tiff_decode_batch_routes_ex(const uint8_t* files, long long files_bytes, const int64_t* file_ranges, int n_files, int deflate);
+int ecseg_tiff_decode_batch_counts_ex(const uint8_t* file, long long n_bytes, int deflate);
+long long ecseg_tiff_decode_batch_bytes_ex(const uint8_t* files, long long files_bytes, const int64_t* file_ranges, int n_files, int deflate);
 
 /* ---- label PNG files encoded on the device ----------------------------------------------------------------------------------- */
 /* The file ecseg_png_write_labels would write for each of n_img label images, byte for byte (signature, IHDR, one IDAT, IEND), as

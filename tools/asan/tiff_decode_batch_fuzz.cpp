@@ -41,7 +41,7 @@ static File make_file(bool in_batch) {
     d.W = 1 + rnd() % (rnd() % 4 == 0 ? 300 : 20);
     d.H = 1 + rnd() % 12;
     d.rps = rnd() % 3 == 0 ? d.H : 1 + rnd() % d.H;
-    d.lzw = rnd() % 4 != 0;
+    d.codec = rnd() % 4 != 0 ? TD_LZW : TD_RAW;
     d.swap = d.bps == 2 && rnd() % 2;
     d.predictor = rnd() % 2;
     const uint32_t line = d.W * d.spp * d.bps, nstrips = (d.H + d.rps - 1) / d.rps;
@@ -52,7 +52,7 @@ static File make_file(bool in_batch) {
         std::vector<uint8_t> raw(n + 1), enc(2 * n + 64);
         for (uint32_t i = 0; i < n; ++i) raw[i] = kind == 0 ? (uint8_t)rnd() : kind == 1 ? (uint8_t)((i / 5) & 3) : (uint8_t)0;
         long long m = n;
-        if (d.lzw) {
+        if (d.codec == TD_LZW) {
             m = ecseg_lzw_encode(raw.data(), n, enc.data(), (long long)enc.size());
             if (m < 0) { std::printf("encode failed\n"); std::exit(1); }
         } else {
@@ -90,7 +90,7 @@ static int print_layouts(const char* path) {
             }
             TdFileIn d;
             d.src_off = a; d.n_bytes = b; d.dst_off = c; d.n_table = v[0]; d.H = v[1]; d.W = v[2]; d.spp = v[3]; d.bps = v[4]; d.rps = v[5];
-            d.lzw = v[6]; d.swap = v[7]; d.predictor = v[8]; d.in_batch = v[9];
+            d.codec = (uint8_t)v[6]; d.swap = v[7]; d.predictor = v[8]; d.in_batch = v[9];
             in.push_back(d);
             continue;
         }
@@ -182,7 +182,7 @@ int main(int argc, char** argv) {
                     if (off > t.n_bytes) bad_strip = true;
                     else {
                         const uint64_t have = cnt < t.n_bytes - off ? cnt : t.n_bytes - off;
-                        if (t.lzw) {
+                        if (t.codec == TD_LZW) {
                             std::unique_ptr<uint8_t[]> src(new uint8_t[have]), tmp(new uint8_t[want + 1]);
                             std::memcpy(src.get(), fs[i].image.data() + off, have);
                             const long long r = ecseg_lzw_decode(src.get(), (long long)have, tmp.get(), (long long)want);

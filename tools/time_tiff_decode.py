@@ -2,6 +2,7 @@
 
     python tools/time_tiff_decode.py [--passes 5] [--limit 120]
     python tools/time_tiff_decode.py --batch [--passes 5] [--limit 300] [--ks 1,2,4,8,16,32]
+    python tools/time_tiff_decode.py --deflate [--batch] ...
 
 A 1040 x 1392 RGB scene of the stat_fish generator (tests/stat_fish_cases.py ``full_size_scene``) is written with LZW and the
 horizontal predictor at 1, 5, 15, 64 and 1040 rows per strip, and once uncompressed.  Per file: the host reader from the page
@@ -20,6 +21,13 @@ questions of the routing rule, one Handle.tiff_decode_many - with only the rule'
 verdict is reported beside the times) - one warm-up and --passes passes each, median, minimum
 and maximum.  A cell counts as a win only when the batch's maximum is below the host's minimum; the last line lists the cells that
 win, and nothing is claimed between cells.
+
+--deflate: the same two tables for Deflate strips (compression 8, zlib level 6, horizontal predictor; the device decodes them with
+the handle option tiff_deflate_on_device, ``Handle.tiff_decode(data, deflate=True)`` / ``imread_many(..., deflate=True)``): single
+files at 1, 5 and 15 rows per strip - 15 rows are 62640 decoded bytes, the strip plan of about 64 KiB that tifffile writes - and
+batches of them and of the stat_fish pair (the mask a Deflate file of 208 strips).  The host side is ecseg_tiff_read, which inflates
+with zlib on one thread.  A single file wins, too, only where the device call's maximum is below the host's minimum; the Deflate
+thresholds of csrc/tiff_parse.h are the smallest strip counts that win (none: the rules never send a Deflate file on their own).
 """
 import argparse
 import json
@@ -29,6 +37,7 @@ import subprocess
 import sys
 import tempfile
 import time
+import zlib
 
 import numpy as np
 
@@ -38,7 +47,7 @@ sys.path.insert(0, os.path.join(ROOT, 'tests'))
 ROWS = (1, 5, 15, 64, 1040)
 
 
-def write_files(folder):
+def write_files(folder, deflate=False):
     import stat_fish_cases as cases
     import ctypes as C
     import tiff_decode_cases as dc
@@ -58,8 +67,19 @@ def write_files(folder):
         assert m > 0
         return dst[:m].tobytes()
     for rps in ROWS:
+        if deflate:
+            if rps <= 15:
+                strips = [zlib.compress(pred[r:r + rps].tobytes(), 6) for r in range(0, H, rps)]
+                names['zip_rps%d' % rps] = dc.tiff_file(strips, H, W, rps, spp=3, predictor=2, compression=8)
+            continue
         strips = [encode(pred[r:r + rps]) for r in range(0, H, rps)]
         names['lzw_rps%d' % rps] = dc.tiff_file(strips, H, W, rps, spp=3, predictor=2)
+    if deflate:
+        for name, data in names.items():
+            with open(os.path.join(folder, name + '.tif'), 'wb') as f:
+                f.write(data)
+        np.save(os.path.join(folder, 'pixels.npy'), img)
+        return list(names)
     names['raw'] = dc.tiff_file([flat.tobytes()], H, W, H, spp=3, compression=1)
     for name, data in names.items():
         with open(os.path.join(folder, name + '.tif'), 'wb') as f:
@@ -72,7 +92,7 @@ def stats(ms):
     return dict(median=statistics.median(ms), min=min(ms), max=max(ms))
 
 
-def one(path, passes):
+def one(path, passes, deflate=False):
     """The child: one file on the host reader and on the device -> one JSON line."""
     from ecseg_amd import image_io
     from ecseg_amd._lib import Handle
@@ -90,7 +110,7 @@ def one(path, passes):
     call, kern = [], []
     for rep in range(passes + 1):
         t0 = time.perf_counter()
-        a = gpu.tiff_decode(data)
+        a = gpu.tiff_decode(data, deflate=True) if deflate else gpu.tiff_decode(data)
         if a is None:
             out['device'] = 'a layout the device reader leaves to the host'
             break
@@ -100,6 +120,7 @@ def one(path, passes):
     else:
         assert np.array_equal(a, want)
         out.update(device_call_ms=stats(call), device_kernel_ms=stats(kern))
+        out['wins'] = out['device_call_ms']['max'] < out['host_read_ms']['min']
     gpu.close()
     print(json.dumps(out), flush=True)
 
@@ -107,7 +128,7 @@ def one(path, passes):
 BATCH_PLANS = ('rps1', 'rps5', 'rps15', 'pair')
 
 
-def write_batch(folder, plan, k):
+def write_batch(folder, plan, k, deflate=False):
     """k scenes of seeds 100 .. 100 + k - 1 at the plan's rows per strip ('pair': 1, each with its mask as write_tiff_gray8 writes
     it) -> the paths."""
     import ctypes as C
@@ -126,6 +147,9 @@ def write_batch(folder, plan, k):
         pred[:, 3:] = flat[:, 3:] - flat[:, :-3]
         strips = []
         for r in range(0, H, rps):
+            if deflate:
+                strips.append(zlib.compress(pred[r:r + rps].tobytes(), 6))
+                continue
             src = np.ascontiguousarray(pred[r:r + rps]).reshape(-1)
             dst = np.empty(2 * src.size + 64, np.uint8)
             m = lib.ecseg_lzw_encode(src.ctypes.data_as(C.c_void_p), src.size, dst.ctypes.data_as(C.c_void_p), dst.size)
@@ -133,21 +157,26 @@ def write_batch(folder, plan, k):
             strips.append(dst[:m].tobytes())
         paths.append(os.path.join(folder, 'scene_%02d.tif' % j))
         with open(paths[-1], 'wb') as f:
-            f.write(dc.tiff_file(strips, H, W, rps, spp=3, predictor=2))
+            f.write(dc.tiff_file(strips, H, W, rps, spp=3, predictor=2, compression=8 if deflate else 5))
         if plan == 'pair':
             paths.append(os.path.join(folder, 'mask_%02d.tif' % j))
+            if deflate:                                      # the mask at write_tiff_gray8's 5 rows per strip: 208 Deflate strips
+                m = (np.asarray(seg) > 0).astype(np.uint8) * np.uint8(255)
+                with open(paths[-1], 'wb') as f:
+                    f.write(dc.tiff_file([zlib.compress(m[r:r + 5].tobytes(), 6) for r in range(0, H, 5)], H, W, 5, compression=8))
+                continue
             image_io.write_tiff_gray8(paths[-1], (np.asarray(seg) > 0).astype(np.uint8) * np.uint8(255))
     return paths
 
 
-def batch_one(plan, k, passes):
+def batch_one(plan, k, passes, deflate=False):
     """The child: one (plan, k) cell on the host reader and through imread_many -> one JSON line."""
     from ecseg_amd import image_io
     from ecseg_amd._lib import Handle
     with tempfile.TemporaryDirectory() as tmp:
-        paths = write_batch(tmp, plan, k)
+        paths = write_batch(tmp, plan, k, deflate)
         datas = [open(p, 'rb').read() for p in paths]
-        goes, counts = image_io.tiff_batch_goes_to_device(datas)
+        goes, counts = image_io.tiff_batch_goes_to_device(datas, deflate=deflate)
         host = []
         for rep in range(passes + 1):
             t0 = time.perf_counter()
@@ -157,11 +186,13 @@ def batch_one(plan, k, passes):
         out = dict(plan=plan, k=k, files=len(paths), bytes=sum(len(d) for d in datas), rule_sends_the_set=bool(goes), host_read_ms=stats(host))
         rule = image_io.tiff_batch_goes_to_device                # the measurement sends every set: the rule's questions are asked and
         image_io.tiff_batch_goes_to_device = lambda datas: (True, rule(datas)[1])       # timed as ever, only the verdict is replaced
+        if deflate:                                              # (Deflate files: every file counts too, where the rule counts none)
+            image_io.tiff_batch_goes_to_device = lambda datas, deflate=False: (rule(datas, deflate=deflate) and True, [True] * len(datas))
         gpu = Handle(0)
         call = []
         for rep in range(passes + 1):
             t0 = time.perf_counter()
-            got = image_io.imread_many(paths, handle=gpu)
+            got = image_io.imread_many(paths, handle=gpu, deflate=True) if deflate else image_io.imread_many(paths, handle=gpu)
             if rep:
                 call.append((time.perf_counter() - t0) * 1e3)
         assert all(isinstance(g, np.ndarray) and g.dtype == w.dtype and np.array_equal(g, w) for g, w in zip(got, want))
@@ -177,7 +208,8 @@ def batch_main(a):
         for k in a.ks:
             cell = dict(plan=plan, k=k)
             try:
-                r = subprocess.run([sys.executable, os.path.abspath(__file__), '--batch-one', '%s:%d' % (plan, k), '--passes', str(a.passes)],
+                r = subprocess.run([sys.executable, os.path.abspath(__file__), '--batch-one', '%s:%d' % (plan, k), '--passes', str(a.passes)] +
+                                   (['--deflate'] if a.deflate else []),
                                    capture_output=True, text=True, timeout=a.limit)
             except subprocess.TimeoutExpired:
                 print(json.dumps(dict(cell, device='ended at the time limit of %g s' % a.limit)), flush=True)
@@ -197,21 +229,23 @@ def main():
     ap.add_argument('--limit', type=float, default=120.0)
     ap.add_argument('--one')
     ap.add_argument('--batch', action='store_true')
+    ap.add_argument('--deflate', action='store_true')
     ap.add_argument('--batch-one')
     ap.add_argument('--ks', type=lambda v: [int(x) for x in v.split(',')], default=[1, 2, 4, 8, 16, 32])
     a = ap.parse_args()
     if a.one:
-        return one(a.one, a.passes)
+        return one(a.one, a.passes, a.deflate)
     if a.batch_one:
         plan, k = a.batch_one.split(':')
-        return batch_one(plan, int(k), a.passes)
+        return batch_one(plan, int(k), a.passes, a.deflate)
     if a.batch:
         return batch_main(a)
     rows = []
     with tempfile.TemporaryDirectory() as tmp:
-        for name in write_files(tmp):
+        for name in write_files(tmp, a.deflate):
             try:
-                r = subprocess.run([sys.executable, os.path.abspath(__file__), '--one', os.path.join(tmp, name + '.tif'), '--passes', str(a.passes)],
+                r = subprocess.run([sys.executable, os.path.abspath(__file__), '--one', os.path.join(tmp, name + '.tif'), '--passes', str(a.passes)] +
+                                   (['--deflate'] if a.deflate else []),
                                    capture_output=True, text=True, timeout=a.limit)
             except subprocess.TimeoutExpired:
                 print(json.dumps(dict(file=name + '.tif', device='ended at the time limit of %g s' % a.limit)), flush=True)
@@ -222,6 +256,9 @@ def main():
             line = r.stdout.strip().splitlines()[-1]
             print(line, flush=True)
             rows.append(json.loads(line))
+    if a.deflate:
+        print(json.dumps(dict(strip_counts_where_the_device_maximum_is_below_the_host_minimum=sorted(-(-1040 // int(r['file'][7:-4])) for r in rows if r.get('wins')))))
+        return
     faster = [(-(-1040 // int(r['file'][7:-4])), r) for r in rows if r['file'].startswith('lzw_') and 'device_call_ms' in r and
               r['device_call_ms']['median'] < r['host_read_ms']['median']]
     print(json.dumps(dict(smallest_strip_count_with_the_device_call_faster=min((n for n, _ in faster), default=None))))
