@@ -82,5 +82,15 @@ asan_iseg_classify:
 	    tools/asan/iseg_classify_check.cpp -o $(ISEG_CHECK)
 	$(ISEG_CHECK)
 
+# and for interseg.batch: the planning header of ecseg_interseg_batch (csrc/iseg_batch.h) - table, groups, capacities, crop windows
+# and chunk runs - over layouts with gaps, reversed order, zero-nucleus images and capacities one short;
+# tests/test_interseg_batch.py builds and runs it.  ISEG_BATCH_CHECK: where the program is put
+ISEG_BATCH_CHECK ?= /tmp/ecseg_iseg_batch_check
+.PHONY: asan_iseg_batch
+asan_iseg_batch:
+	g++ -std=c++17 -O1 -g -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=all \
+	    tools/asan/iseg_batch_check.cpp -o $(ISEG_BATCH_CHECK)
+	$(ISEG_BATCH_CHECK)
+
 clean:
 	rm -rf __pycache__ ecseg_amd/csrc/*.o ecseg_amd/libecseg_*.so

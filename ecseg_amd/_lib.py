@@ -32,6 +32,7 @@ EXPORTS = [
     'ecseg_tiff_encode_batch', 'ecseg_tiff_encode_batch_bytes', 'ecseg_fish_render_tiff_batch',
     'ecseg_classify_nucleus_crops', 'ecseg_iseg_classifier_inputs_debug',
     'ecseg_marker_watershed_stages_debug', 'ecseg_marker_watershed_batch_stages_debug',
+    'ecseg_interseg_batch',
 ]
 
 
@@ -143,6 +144,7 @@ def load_library():
     lib.ecseg_nucleus_crops.argtypes = [vp, vp, i32, vp, vp, vp]
     lib.ecseg_classify_nucleus_crops.argtypes = [vp, vp, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp]
     lib.ecseg_iseg_classifier_inputs_debug.argtypes = [vp, vp, i32, vp, vp, i32, vp, i32, vp, vp]
+    lib.ecseg_interseg_batch.argtypes = [vp, vp, vp, vp, C.c_longlong, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.ecseg_fish_distances.argtypes = [vp, vp, i32, i32, u8p, i32, i32, i32, i32, vp, C.POINTER(C.c_int32)]
     lib.ecseg_fish_spots.argtypes = [vp, vp, i32, i32, u8p, i32, vp, i32, vp, i32, C.c_double, vp, i32, i32, i32, vp, vp, vp,
                                      C.POINTER(C.c_int32)]
@@ -842,6 +844,76 @@ class Handle:
                     'ecseg_classify_nucleus_crops')
         out = (mx, pi, ri.view(bool), pc, rc.view(bool))
         return out + (crops,) if want_crops else out
+
+    ISEG_OK, ISEG_INSTANCE_IDS, ISEG_RECORDS_OVERFLOW, ISEG_CROPS_OVERFLOW = 0, 1, 2, 3       # ECSEG_ISEG_* of the header
+
+    def interseg_batch_packed(self, packed, table, fish_index, model_i, model_c, record_capacity, crop_capacity):
+        """ecseg_interseg_batch as the header states it: a uint8 buffer, its (n, 8) int64 table (image offset, H, W, C, segmentation
+        offset, h, w, run_c) and the two capacities -> (out int32 (n, 8), records int64 (record_capacity, 8), and per crop
+        (crop_capacity entries each) crop_region int32, channel_max int32 (., 3), pred_i float32 (., 3), ran_i bool, pred_c float32,
+        ran_c bool).  ``interseg_many`` packs, sizes and unpacks for its caller."""
+        buf = _u8(packed).reshape(-1)
+        tab = np.ascontiguousarray(table, np.int64).reshape(-1, 8)
+        rcap, ccap = int(record_capacity), int(crop_capacity)
+        hi = getattr(model_i, 'handle', model_i)
+        hc = getattr(model_c, 'handle', model_c)
+        out = np.zeros((len(tab), 8), np.int32)
+        rec = np.zeros((max(rcap, 1), 8), np.int64)
+        region, mx = np.zeros(max(ccap, 1), np.int32), np.zeros((max(ccap, 1), 3), np.int32)
+        pi, pc = np.zeros((max(ccap, 1), 3), np.float32), np.zeros(max(ccap, 1), np.float32)
+        ri, rc = np.zeros(max(ccap, 1), np.uint8), np.zeros(max(ccap, 1), np.uint8)
+        self._check(self.lib.ecseg_interseg_batch(self.h, hi.h, hc.h if hc is not None else None, _ptr(buf), buf.size, _ptr(tab), len(tab),
+                                                  int(fish_index), rcap, ccap, _ptr(out), _ptr(rec), _ptr(region), _ptr(mx), _ptr(pi), _ptr(ri),
+                                                  _ptr(pc), _ptr(rc)), 'ecseg_interseg_batch')
+        return out, rec[:rcap], region[:ccap], mx[:ccap], pi[:ccap], ri[:ccap].view(bool), pc[:ccap], rc[:ccap].view(bool)
+
+    def interseg_many(self, images, segs, fish_index, quality_pass, model_i, model_c=None, record_capacity=None, crop_capacity=None):
+        """``nuclei_regions`` + the crop windows of ``interseg.region_rows`` + ``classify_nucleus_crops`` for a list of images in one
+        device call (ecseg_interseg_batch).  ``images``: (H, W, C >= 3) uint8 each; ``segs``: their (h, w) uint8 masks, not larger than
+        their image; ``quality_pass``: one bool per image, ecSeg-c applies to an image only where it is true (and ``model_c`` is given).
+        Returns one entry per image: ``(records int64 (n, 8), (owner int64, pred_i float32 (N, 3), ran_i bool, pred_c float32, ran_c
+        bool))`` with N the image's crops and ``owner`` their regions, or the ``EcsegError`` (code -1) ``nuclei_regions`` raises for
+        that image alone - an instance-id map.  ``record_capacity`` / ``crop_capacity``: room for the first call (default 1024 records
+        and 512 crops per image); the images reported as not fitting go again, together, with the room they asked for."""
+        n = len(images)
+        if not (len(segs) == n == len(quality_pass)):
+            raise ValueError('interseg_many takes one segmentation and one quality_pass flag per image')
+        ims = [_u8(a) for a in images]
+        sgs = [_u8(a) for a in segs]
+        for im, sg in zip(ims, sgs):
+            if im.ndim != 3 or sg.ndim != 2:
+                raise ValueError('interseg_many takes (H, W, C) images and (h, w) masks')
+        results = [None] * n
+        todo = list(range(n))
+        rcap = int(record_capacity) if record_capacity is not None else 1024 * n
+        ccap = int(crop_capacity) if crop_capacity is not None else 512 * n
+        while todo:
+            parts, tab, off = [], np.zeros((len(todo), 8), np.int64), 0
+            for j, i in enumerate(todo):
+                im, sg = ims[i], sgs[i]
+                tab[j] = (off, im.shape[0], im.shape[1], im.shape[2], off + im.size, sg.shape[0], sg.shape[1], int(bool(quality_pass[i])))
+                parts += [im.reshape(-1), sg.reshape(-1)]
+                off += im.size + sg.size
+            out, rec, region, _, pi, ri, pc, rc = self.interseg_batch_packed(np.concatenate(parts), tab, fish_index, model_i, model_c, rcap, ccap)
+            again, need_r, need_c = [], 0, 0
+            for j, i in enumerate(todo):
+                st, nr, r0, ncr, c0, vmin, vmax = (int(v) for v in out[j, :7])
+                if st == self.ISEG_INSTANCE_IDS:
+                    e = EcsegError('ecseg_nuclei_regions failed (-1): segmentation holds the non-zero values %d .. %d: only 0 / non-zero '
+                                   'nucleus masks are supported, not instance-id maps' % (vmin, vmax))
+                    e.code = -1
+                    results[i] = e
+                elif st == self.ISEG_OK:
+                    sl = slice(c0, c0 + ncr)
+                    results[i] = (rec[r0:r0 + nr].copy(), (region[sl].astype(np.int64), pi[sl].copy(), ri[sl].copy(), pc[sl].copy(), rc[sl].copy()))
+                else:
+                    again.append(i)
+                    need_r += nr
+                    need_c += max(ncr, 512)                   # (-1: not counted yet, the next round says)
+            if again and len(again) == len(todo) and need_r <= rcap and need_c <= ccap:
+                raise EcsegError('ecseg_interseg_batch: image %d fits neither %d records nor %d crops' % (again[0], rcap, ccap))
+            todo, rcap, ccap = again, max(rcap, need_r), max(ccap, need_c)
+        return results
 
     def iseg_classifier_inputs(self, crops, channel_max, sel_i, sel_c):
         """The input kernel of ``classify_nucleus_crops`` alone, for its tests (ecseg_iseg_classifier_inputs_debug): uint8 (k, 256, 256, 3)

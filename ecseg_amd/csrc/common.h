@@ -5,6 +5,7 @@
 
 #include "../../include/ecseg_hip.h"
 #include "scratch.h"
+#include "iseg_batch.h"
 #include "tiff_decode_batch.h"
 #include "tiff_encode_batch.h"
 #include "tiff_frame.h"
@@ -313,6 +314,30 @@ inline ClassifyBufs classify_bufs(Carver& c, int n) {
     b.crop = crop_bufs(c, n); b.sel_i = c.take<int32_t>((size_t)n); b.sel_c = c.take<int32_t>((size_t)n);
     return b;
 }
+// Device buffers of ecseg_interseg_batch for one group of n images padded to Hm x Wm (iseg_batch.h, whose iseg_batch_bytes restates
+// this layout's size): the group's bytes of the packed buffer, the table and the plan; mask, label map and region index of every
+// padded pixel with the scan blocks; the counters misc (4) and imisc (n, 4); cap records' accumulators, boxes and records; one
+// classifier chunk with the batch's own descriptors.
+struct IsegBatchBufs {
+    uint8_t* packed; IsegImage* tab; int32_t* plan; uint8_t* mask; int32_t* lab; int32_t* rid; int32_t* blk; int32_t* misc; int32_t* imisc;
+    unsigned long long* acc; int32_t* bb; int64_t* rec; int32_t* desc; ClassifyBufs cls; int cap;
+};
+inline IsegBatchBufs iseg_batch_bufs(Carver& c, int n, int Hm, int Wm, size_t span, int cap) {
+    const size_t px = (size_t)n * Hm * Wm, r = (size_t)cap;
+    IsegBatchBufs b;
+    b.packed = c.take<uint8_t>(span); b.tab = c.take<IsegImage>((size_t)n); b.plan = c.take<int32_t>((size_t)n * ISEG_PLAN);
+    b.mask = c.take<uint8_t>(px); b.lab = c.take<int32_t>(px); b.rid = c.take<int32_t>(px); b.blk = c.take<int32_t>((px + 1023) / 1024);
+    b.misc = c.take<int32_t>(4); b.imisc = c.take<int32_t>((size_t)n * 4);
+    b.acc = c.take<unsigned long long>(r * 4); b.bb = c.take<int32_t>(r * 4); b.rec = c.take<int64_t>(r * 8);
+    b.desc = c.take<int32_t>((size_t)ISEG_CHUNK * ISEG_DESC); b.cls = classify_bufs(c, ISEG_CHUNK);
+    b.cap = cap;
+    return b;
+}
+// The group's tab and packed bytes are on the device: pads and labels the masks, numbers the regions per image, hands the cap records
+// out (plan, misc[3] = records taken) and writes them; imisc[i][1..2]: image i's value range, as misc[1..2] of run_nuclei_regions.
+hipError_t run_iseg_batch_regions(int n, int Hm, int Wm, int ch0, const IsegBatchBufs& b, PostWorkspace& ws, hipStream_t s);
+// b.desc: n <= ISEG_CHUNK crops (image, region, y0, x0, h, w) -> b.cls.crop.crops / max, as run_nucleus_crops
+hipError_t run_iseg_batch_crops(int Hm, int Wm, const IsegBatchBufs& b, int n, const int order[3], hipStream_t s);
 // crops: (k, 256, 256, 3) uint8 with chmax (k, 3); sel_i / sel_c: n_i / n_c crop indices in [0, k), in any order, repeats allowed.
 // out_i (n_i, 256, 256, 1) float32 = (float) of channel 0 of crop sel_i[j]; out_c (n_c, 256, 256, 3) float32 = preprocess_ecseg_c of
 // crop sel_c[j] (iseg_c_value with the crop's own maxima).  Both 16-byte aligned; either list may be empty (its pointers unused).

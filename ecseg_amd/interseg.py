@@ -6,7 +6,9 @@
 one sigmoid unit) run batched through the same plan interpreter and HIP kernels as the metaseg U-Net, and the per-nucleus
 decision logic of src/interseg.py:131-190 is applied to their outputs (``classify_crops``).  One key of its own:
 ``classify_on_device`` (false; true: one ``Handle.classify_nucleus_crops`` call per image builds the crops, writes both classifiers'
-inputs from them on the device and runs the plans - no crop crosses the bus; the same CSV).
+inputs from them on the device and runs the plans - no crop crosses the bus; the same CSV).  With it, ``batch: k`` (1): the sorted
+images go k at a time, their files read side by side on host threads and their nuclei through ONE ``Handle.interseg_many`` call
+(``process_chunk``); the same CSV, messages and exit code.
 """
 import csv
 import os
@@ -213,23 +215,47 @@ def _load_image(p, seg_path):
     return I, seg
 
 
-def process_image(p, handle, ecseg_i_model, ecseg_c_model, fish_index, quality_pass, stats=None, classify_on_device=False):
-    """CSV rows of one image (src/interseg.py:105-235): [name, nucleus_center, interSeg_label, (ecSeg-c_label,) ecSeg-i_label].
-    ``classify_on_device`` (the config key): one ``handle.classify_nucleus_crops`` call takes the crop descriptors and returns the
-    classifiers' outputs - the crops never reach the host; the same rows."""
-    import time
-    from . import image_tools
+def _stem_and_segmentation(p):
     path_split = os.path.split(p)
     stem = path_split[1][:-4]
-    seg_path = os.path.join(path_split[0], 'annotated', stem, stem + '_segmentation.tif')
-    t0 = time.perf_counter()
-    I, seg = _load_image(p, seg_path)
+    return stem, os.path.join(path_split[0], 'annotated', stem, stem + '_segmentation.tif')
+
+
+def _device_inputs(I, seg, seg_path, handle):
+    """What ``_load_image`` read, as the device calls take it: both uint8, C-contiguous."""
+    from . import image_tools
     I = np.ascontiguousarray(image_tools.u16_to_u8(I, handle=handle))
     seg = np.ascontiguousarray(seg)
     if seg.dtype != np.uint8:                                       # a 16-bit / bool mask: the device call takes uint8
         if len(np.unique(seg[seg != 0])) > 1:
             raise ImageError('segmentation %s holds several non-zero values: only 0 / non-zero nucleus masks are supported' % seg_path)
         seg = (seg != 0).astype(np.uint8) * np.uint8(255)
+    return I, seg
+
+
+def _csv_rows(stem, centers, low, owner, crop_rows, has_c):
+    """The CSV rows of one image from its regions' centres and gate flags and its crops' rows (``owner``: the region of every crop)."""
+    by_region = {}
+    for k, r in zip(owner.tolist(), crop_rows):
+        by_region.setdefault(k, []).append(r)
+    rows = []
+    for k in range(len(centers)):
+        if low[k]:
+            rows.append([stem, centers[k], LOW_TRGT] + ([LOW_TRGT] if has_c else []) + [LOW_TRGT])
+            continue
+        for r in by_region.get(k, []):
+            rows.append([stem, centers[k], r['interSeg_label']] + ([r['ecSeg-c_label']] if has_c else []) + [r['ecSeg-i_label']])
+    return rows
+
+
+def process_image(p, handle, ecseg_i_model, ecseg_c_model, fish_index, quality_pass, stats=None, classify_on_device=False):
+    """CSV rows of one image (src/interseg.py:105-235): [name, nucleus_center, interSeg_label, (ecSeg-c_label,) ecSeg-i_label].
+    ``classify_on_device`` (the config key): one ``handle.classify_nucleus_crops`` call takes the crop descriptors and returns the
+    classifiers' outputs - the crops never reach the host; the same rows."""
+    import time
+    stem, seg_path = _stem_and_segmentation(p)
+    t0 = time.perf_counter()
+    I, seg = _device_inputs(*_load_image(p, seg_path), seg_path, handle)
     t1 = time.perf_counter()
     has_c = ecseg_c_model is not None
     crop_rows = []
@@ -255,22 +281,61 @@ def process_image(p, handle, ecseg_i_model, ecseg_c_model, fish_index, quality_p
             sl = slice(b0, b0 + CROP_BATCH)
             crop_rows += classify_crops(ecseg_i_model, crops[sl], ecseg_c_model, quality_pass, from_patches=tiled[sl], channel_max=cmax[sl])
     t3 = time.perf_counter()
-    by_region = {}
-    for k, r in zip(owner.tolist(), crop_rows):
-        by_region.setdefault(k, []).append(r)
-    rows = []
-    for k in range(len(centers)):
-        if low[k]:
-            rows.append([stem, centers[k], LOW_TRGT] + ([LOW_TRGT] if has_c else []) + [LOW_TRGT])
-            continue
-        for r in by_region.get(k, []):
-            rows.append([stem, centers[k], r['interSeg_label']] + ([r['ecSeg-c_label']] if has_c else []) + [r['ecSeg-i_label']])
+    rows = _csv_rows(stem, centers, low, owner, crop_rows, has_c)
     if stats is not None:
         for key, v in (('read', t1 - t0), ('device_crops', t2 - t1), ('classifiers', t3 - t2), ('rows', time.perf_counter() - t3)):
             stats[key] = stats.get(key, 0.0) + v
         stats['crops'] = stats.get('crops', 0) + len(desc)
         stats['nuclei'] = stats.get('nuclei', 0) + len(centers)
     return rows
+
+
+def process_chunk(paths, quality, handle, ecseg_i_model, ecseg_c_model, fish_index, pool, stats=None):
+    """``process_image`` for the images of one chunk (config key ``batch``, with ``classify_on_device``): the files are read side by
+    side on ``pool``, then ONE ``handle.interseg_many`` call takes every image that could be read.  ``quality``: per image its
+    ``quality_pass`` flag, or the ``ImageError`` the quality score raised.  Returns per image its CSV rows or its ``ImageError``: what
+    fails one image leaves the others alone."""
+    import time
+    has_c = ecseg_c_model is not None
+    names = [_stem_and_segmentation(p) for p in paths]
+    t0 = time.perf_counter()
+
+    def load(k):
+        if isinstance(quality[k], ImageError):
+            return quality[k]
+        try:
+            return _load_image(paths[k], names[k][1])
+        except ImageError as e:
+            return e
+    out = list(pool.map(load, range(len(paths))))
+    live = []
+    for k, item in enumerate(out):
+        if not isinstance(item, ImageError):
+            try:
+                live.append((k,) + _device_inputs(item[0], item[1], names[k][1], handle))
+            except ImageError as e:
+                out[k] = e
+    t1 = time.perf_counter()
+    results = handle.interseg_many([I for _, I, _ in live], [seg for _, _, seg in live], fish_index, [bool(quality[k]) for k, _, _ in live],
+                                   ecseg_i_model, ecseg_c_model) if live else []
+    t2 = time.perf_counter()
+    for (k, _, _), res in zip(live, results):
+        if isinstance(res, Exception):
+            if getattr(res, 'code', None) != -1:
+                raise res
+            out[k] = ImageError(str(res))
+            continue
+        rec, (owner, pred_i, ran_i, pred_c, ran_c) = res
+        centers, low = region_rows(rec)[:2]
+        crop_rows = rows_from_predictions(has_c, bool(quality[k]), ran_i, pred_i, ran_c, pred_c)
+        out[k] = _csv_rows(names[k][0], centers, low, np.asarray(owner, np.int64), crop_rows, has_c)
+        if stats is not None:
+            stats['crops'] = stats.get('crops', 0) + len(owner)
+            stats['nuclei'] = stats.get('nuclei', 0) + len(centers)
+    if stats is not None:
+        for key, v in (('read', t1 - t0), ('device', t2 - t1), ('rows', time.perf_counter() - t2)):
+            stats[key] = stats.get(key, 0.0) + v
+    return out
 
 
 def csv_columns(has_centromeric_probe):
@@ -298,6 +363,12 @@ def main(argv=None):
     if not isinstance(classify_on_device, bool):
         print("interseg.classify_on_device must be true or false (true: the nucleus crops go through the classifiers without leaving the device). Exiting...")
         sys.exit(2)
+    batch = var.get('batch', 1)
+    if isinstance(batch, bool) or not isinstance(batch, int) or batch < 1:
+        print("interseg.batch must be a positive integer (how many images share one device call, with classify_on_device: true; 1: one by one). Exiting...")
+        sys.exit(2)
+    if not classify_on_device:
+        batch = 1                                            # (as tiff_read_batch without its parent key)
     fish_index = 1 if fish_color == 'green' else 0
     os.makedirs(os.path.join(inpath, 'annotated'), exist_ok=True)
 
@@ -313,6 +384,9 @@ def main(argv=None):
     if classify_on_device and not hasattr(handle, 'classify_nucleus_crops'):
         print("interseg.classify_on_device: true needs the device classifier path (classify_nucleus_crops), which the handle in use does not have. Exiting...")
         sys.exit(2)
+    if batch > 1 and not hasattr(handle, 'interseg_many'):
+        print("interseg.batch: %d needs the batched device path (interseg_many), which the handle in use does not have; only batch: 1 works on it. Exiting..." % batch)
+        sys.exit(2)
     table, table_error = None, None
     if has_centromeric_probe:
         # the reference reads the table even without a centromeric probe, where it is never used (src/interseg.py:101)
@@ -321,23 +395,45 @@ def main(argv=None):
         except (OSError, ValueError) as e:
             table_error = 'annotated/stat_fish_lsq.csv cannot be read (%s): run stat_fish first' % e
 
-    rows, failed = [], []
-    for p in image_paths:
-        path_split = os.path.split(p)
-        print("Processing image: ", p)
+    def quality_of(p):
+        if not has_centromeric_probe:
+            return True
+        if table_error:
+            raise ImageError(table_error)
         try:
-            quality_pass = True
-            if has_centromeric_probe:
-                if table_error:
-                    raise ImageError(table_error)
-                try:
-                    quality_pass = bool(quality_score(table, path_split[1][:-4], ['red', 'green'][1 - fish_index]) <= 3)
-                except ValueError as e:
-                    raise ImageError(str(e))
-            rows += process_image(p, handle, ecseg_i_model, ecseg_c_model, fish_index, quality_pass, classify_on_device=classify_on_device)
-        except ImageError as e:
-            print(p, '-', e)
-            failed.append((p, str(e)))
+            return bool(quality_score(table, os.path.split(p)[1][:-4], ['red', 'green'][1 - fish_index]) <= 3)
+        except ValueError as e:
+            raise ImageError(str(e))
+
+    rows, failed = [], []
+    if batch == 1:
+        for p in image_paths:
+            print("Processing image: ", p)
+            try:
+                rows += process_image(p, handle, ecseg_i_model, ecseg_c_model, fish_index, quality_of(p), classify_on_device=classify_on_device)
+            except ImageError as e:
+                print(p, '-', e)
+                failed.append((p, str(e)))
+    else:
+        from concurrent.futures import ThreadPoolExecutor
+        from .utils import default_io_threads
+        with ThreadPoolExecutor(default_io_threads()) as pool:
+            for c0 in range(0, len(image_paths), batch):
+                chunk = image_paths[c0:c0 + batch]
+                quality = []
+                for p in chunk:
+                    try:
+                        quality.append(quality_of(p))
+                    except ImageError as e:
+                        quality.append(e)
+                results = process_chunk(chunk, quality, handle, ecseg_i_model, ecseg_c_model, fish_index, pool)
+                for p, res in zip(chunk, results):               # the lines of batch: 1, in its order
+                    print("Processing image: ", p)
+                    if isinstance(res, ImageError):
+                        print(p, '-', res)
+                        failed.append((p, str(res)))
+                    else:
+                        rows += res
     with open(os.path.join(inpath, 'interphase_prediction_%s.csv' % fish_color), 'w') as f:
         f.write(csvio.csv_text(csv_columns(has_centromeric_probe), rows))
     if failed:

@@ -70,6 +70,8 @@ extern "C" {
 /* (still 5 - additive: option "tiff_deflate_on_device" with ecseg_tiff_decode_routes_ex, ecseg_tiff_decode_batch_routes_ex,
  * ecseg_tiff_decode_batch_counts_ex and ecseg_tiff_decode_batch_bytes_ex, Deflate strips decoded on the device behind an option that
  * is off by default; nothing existing changed.) */
+/* (still 5 - additive: ecseg_interseg_batch, the regions, crops and classifiers of many interSeg images in one call; nothing existing
+ * changed.  The number stays where every additive entry above left it: a caller of version 5 runs unchanged.) */
 #define ECSEG_ABI_VERSION 5
 
 #define ECSEG_OK             0
@@ -384,6 +386,44 @@ int ecseg_classify_nucleus_crops(ecseg_ctx* h, ecseg_ctx* model_i, ecseg_ctx* mo
  * float32, what ecseg_classify_nucleus_crops would write into the two plans' inputs.  Device time in ECSEG_T_TILE. */
 int ecseg_iseg_classifier_inputs_debug(ecseg_ctx* h, const uint8_t* crops, int k, const int32_t* channel_max, const int32_t* sel_i,
                                        int n_i, const int32_t* sel_c, int n_c, float* out_i, float* out_c);
+/* ecseg_nuclei_regions, the crop windows of src/interseg.py:150-154,190-194 and ecseg_classify_nucleus_crops for n_images images in
+ * ONE call: per image exactly the records and the classifier outputs those calls give for it alone.
+ * packed: packed_bytes bytes holding, per image, the uint8 image (H, W, C), C >= 3, and its uint8 segmentation (h, w), h <= H,
+ * w <= W (16-bit images are converted by the caller, as for ecseg_nuclei_regions).  images: n_images x 8 int64 rows
+ * (image offset, H, W, C, segmentation offset, h, w, run_c).  The 2 n_images rasters lie in the order image 0, segmentation 0,
+ * image 1, ...: each starts at or after the end of the one in front (ecseg_marker_watershed_batch's rule: back to back, gaps allowed,
+ * no overlap).  run_c: 1 where ecSeg-c applies to that image (a passed quality score); ignored when model_c is NULL.  fish_index 0 / 1:
+ * the channel the gate sums, and the crops' channels are (fish_index, 1 - fish_index, 2).  h, model_i, model_c: as
+ * ecseg_classify_nucleus_crops; the region map ecseg_nuclei_regions left on h is not touched.
+ * out: n_images x 8 int32 rows
+ *   [0] status: ECSEG_ISEG_OK; ECSEG_ISEG_INSTANCE_IDS - two different non-zero values, [5] the smallest and [6] the largest (the
+ *       refusal of ecseg_nuclei_regions, for this image only); ECSEG_ISEG_RECORDS_OVERFLOW / ECSEG_ISEG_CROPS_OVERFLOW - its
+ *       records / crops do not fit what is left of record_capacity / crop_capacity
+ *   [1] its regions   [2] its first record in `records`, -1 unless OK or CROPS_OVERFLOW   [3] its crops, -1 where they were not
+ *   counted   [4] its first crop in the per-crop arrays, -1 unless OK   [7] 0.
+ * Capacities are handed out in image order and nothing is ever truncated: an image whose regions do not fit takes no record and
+ * the images behind it go on (one whose regions fit takes their room whatever its status becomes); the same for the crops of the
+ * images that are OK so far.  Call again for the reported images with [1] / [3] entries of room.
+ * records (record_capacity x 8 int64): the layout of ecseg_nuclei_regions, region indices restart at 0 per image.  Per crop, in
+ * image order, then region order, then window order (crop_capacity entries each): crop_region (its region), channel_max (x 3),
+ * ran_i, pred_i (x 3), ran_c, pred_c (may be NULL without model_c) as ecseg_classify_nucleus_crops writes them.  The classifier
+ * chunks of 256 crops are filled across image boundaries.
+ * One synchronous call, scratch from the call arena: the masks are padded to the largest (h, w) of the call and labelled as one
+ * same-shape batch, 9 bytes per padded pixel besides the rasters and one chunk of crops; above 8 GiB, or 2^31 padded pixels, the
+ * call runs consecutive images in several groups (the classifier chunks are then filled per group).  Device time as
+ * ecseg_classify_nucleus_crops, the labelling and statistics in ECSEG_T_COUNT too.  ECSEG_E_INVALID: a null pointer that is
+ * needed, n_images outside 0 .. ECSEG_INTERSEG_BATCH_MAX_IMAGES, a negative capacity, fish_index not 0 / 1, a row with an extent
+ * < 1, C outside 3 .. 256, a segmentation larger than its image, 2^31 pixels or more, run_c not 0 / 1, a raster that overlaps the
+ * one in front or leaves packed (the message names the image), and the model errors of ecseg_classify_nucleus_crops. */
+#define ECSEG_INTERSEG_BATCH_MAX_IMAGES 1024
+#define ECSEG_ISEG_OK               0
+#define ECSEG_ISEG_INSTANCE_IDS     1
+#define ECSEG_ISEG_RECORDS_OVERFLOW 2
+#define ECSEG_ISEG_CROPS_OVERFLOW   3
+int ecseg_interseg_batch(ecseg_ctx* h, ecseg_ctx* model_i, ecseg_ctx* model_c, const uint8_t* packed, long long packed_bytes,
+                         const int64_t* images, int n_images, int fish_index, int record_capacity, int crop_capacity, int32_t* out,
+                         int64_t* records, int32_t* crop_region, int32_t* channel_max, float* pred_i, uint8_t* ran_i, float* pred_c,
+                         uint8_t* ran_c);
 
 /* ---- fish_distance_calculation: per-nucleus FISH - centromere distances (src/fish_distance_calculation.py:16-46) --------- */
 /* Replaces, for ONE image, the loop over regionprops(segmentation) (:19), the gate on lsq channels 0 and 1 (:21), the spot

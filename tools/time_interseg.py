@@ -3,6 +3,10 @@
     python tools/time_interseg.py [--images 16] [--nuclei 40] [--height 1040] [--width 1392] [--cpu-workers 16]
     python tools/time_interseg.py --classify-on-device off|on|alternate     # the classifier stage with interseg.classify_on_device
                                                                             # off / on (alternate: off, on, off, on in one process)
+    python tools/time_interseg.py --classify-on-device on --batch 8 alternate   # `make interseg` end to end over a folder of files, file
+                                                                            # reads included, interseg.batch 1, 8, 1, 8: a child process per visit
+
+Without --batch nothing is read from a file: the images are arrays in memory, so the read stage is in none of those figures.
 
 Device side: per image ``Handle.nuclei_regions`` + ``Handle.nucleus_crops`` (regions + crops), the two classifiers
 (tests/golden/interseg_synth.h5 and ecseg_c_synth.h5, batched) and the host work around them (region rows, decisions).
@@ -164,8 +168,78 @@ def classify_report(a):
     print(json.dumps(out))
 
 
+def batch_visit(a):
+    """One mode visit of --batch, in a process of its own: ``interseg.main``'s loop (files read from the folder, device calls, rows)
+    over the folder with ``classify_on_device`` on and ``batch`` = a.batch_visit; a warm-up pass, then 3 timed passes.  One JSON line."""
+    from concurrent.futures import ThreadPoolExecutor
+
+    from ecseg_amd import hdf5_min, interseg, utils
+    from ecseg_amd.model import MetasegModel
+    g = os.path.join(ROOT, 'tests', 'golden')
+    mi = MetasegModel(*hdf5_min.load_keras_h5(os.path.join(g, 'interseg_synth.h5')))
+    mc = MetasegModel(*hdf5_min.load_keras_h5(os.path.join(g, 'ecseg_c_synth.h5')))
+    h, k = mi.handle, a.batch_visit
+    paths = utils.get_imgs(a.folder)
+
+    def one_pass(pool):
+        st, rows = {}, 0
+        t0 = time.perf_counter()
+        if k == 1:
+            for p in paths:
+                rows += len(interseg.process_image(p, h, mi, mc, 0, True, stats=st, classify_on_device=True))
+            st['device'] = st.pop('device_crops') + st.pop('classifiers')
+        else:
+            for c0 in range(0, len(paths), k):
+                for r in interseg.process_chunk(paths[c0:c0 + k], [True] * len(paths[c0:c0 + k]), h, mi, mc, 0, pool, stats=st):
+                    rows += len(r)
+        return time.perf_counter() - t0, st, rows
+    with ThreadPoolExecutor(utils.default_io_threads()) as pool:
+        one_pass(pool)
+        runs = [one_pass(pool) for _ in range(3)]
+    rates = [len(paths) / r[0] for r in runs]
+    print(json.dumps({'batch': k, 'images': len(paths), 'rows': runs[-1][2], 'io_threads': utils.default_io_threads(),
+                      'images_per_s': {'median': round(float(np.median(rates)), 3), 'min': round(min(rates), 3), 'max': round(max(rates), 3)},
+                      'stage_s_per_pass': {key: round(float(np.median([r[1][key] for r in runs])), 4) for key in ('read', 'device', 'rows')}}))
+
+
+def batch_report(a):
+    """--batch K [alternate]: the synthetic images written once as the files ``make interseg`` reads (RGB TIFFs and their
+    annotated/<name>/<name>_segmentation.tif), then ``batch`` 1, K, 1, K (alternate) or K alone, every visit a child process under its
+    own time limit.  Prints one JSON line with the visits in order."""
+    import subprocess
+    import tempfile
+
+    from ecseg_amd import image_io
+    with tempfile.TemporaryDirectory() as folder:
+        for j in range(a.images):
+            seg, img = synth_image(1000 + j, a.height, a.width, a.nuclei)
+            name = 'img%03d' % j
+            os.makedirs(os.path.join(folder, 'annotated', name))
+            image_io.write_tiff_rgb8(os.path.join(folder, name + '.tif'), img)
+            image_io.write_tiff_gray8(os.path.join(folder, 'annotated', name, name + '_segmentation.tif'), seg)
+        visits = [1, a.batch, 1, a.batch] if a.mode == 'alternate' else [a.batch]
+        out = {'images': a.images, 'shape': [a.height, a.width], 'visits': []}
+        for k in visits:
+            cmd = [sys.executable, os.path.abspath(__file__), '--batch-visit', str(k), '--folder', folder]
+            try:
+                res = subprocess.run(cmd, capture_output=True, text=True, timeout=a.visit_timeout)
+            except subprocess.TimeoutExpired:
+                out['visits'].append({'batch': k, 'error': 'no result within %d s' % a.visit_timeout})
+                break                                                       # nothing more is started behind a visit that hung
+            if res.returncode != 0:
+                out['visits'].append({'batch': k, 'error': 'exit %d: %s' % (res.returncode, res.stderr[-500:])})
+                break
+            out['visits'].append(json.loads(res.stdout.strip().splitlines()[-1]))
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument('--batch', type=int, default=None, help='time `make interseg` end to end (file reads included) with interseg.batch 1 and this value')
+    ap.add_argument('mode', nargs='?', choices=['alternate'], default=None, help='with --batch: batch 1, K, 1, K instead of K alone')
+    ap.add_argument('--visit-timeout', type=int, default=240, help='with --batch: seconds a mode visit may take')
+    ap.add_argument('--batch-visit', type=int, default=None, help=argparse.SUPPRESS)
+    ap.add_argument('--folder', default=None, help=argparse.SUPPRESS)
     ap.add_argument('--images', type=int, default=16)
     ap.add_argument('--nuclei', type=int, default=40)
     ap.add_argument('--height', type=int, default=1040)
@@ -175,6 +249,10 @@ def main():
     ap.add_argument('--classify-on-device', choices=['off', 'on', 'alternate'], default=None,
                     help='time the classifier stage of `make interseg` with interseg.classify_on_device off, on, or off, on, off, on over the same images')
     a = ap.parse_args()
+    if a.batch_visit:
+        return batch_visit(a)
+    if a.batch:
+        return batch_report(a)
     if a.classify_on_device:
         return classify_report(a)
     from ecseg_amd import hdf5_min, interseg
