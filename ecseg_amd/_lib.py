@@ -33,6 +33,7 @@ EXPORTS = [
     'ecseg_classify_nucleus_crops', 'ecseg_iseg_classifier_inputs_debug',
     'ecseg_marker_watershed_stages_debug', 'ecseg_marker_watershed_batch_stages_debug',
     'ecseg_interseg_batch',
+    'ecseg_stitch_stages_debug', 'ecseg_preprocess_stages_debug', 'ecseg_otsu_debug',
 ]
 
 
@@ -131,6 +132,9 @@ def load_library():
     lib.ecseg_host_alloc.argtypes = [vp, C.c_size_t, C.POINTER(vp)]
     lib.ecseg_host_free.argtypes = [vp, vp]
     lib.ecseg_stitch_argmax.argtypes = [vp, vp, i32, i32, i32, vp]
+    lib.ecseg_stitch_stages_debug.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp]
+    lib.ecseg_preprocess_stages_debug.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp]
+    lib.ecseg_otsu_debug.argtypes = [vp, vp, i32, vp, vp, vp]
     lib.ecseg_meta_inference.argtypes = [vp, u8p, i32, i32, i32, vp, vp]
     lib.ecseg_meta_inference_dev.argtypes = [vp, u8p, i32, i32, i32, vp, vp]
     lib.ecseg_meta_inference_stages_debug.argtypes = [vp, u8p, i32, i32, i32, i32, i32, vp, vp]
@@ -662,6 +666,44 @@ class Handle:
         out = np.empty((n_img, H, W), np.uint8)
         self._check(self.lib.ecseg_stitch_argmax(self.h, _ptr(p), n_img, H, W, _ptr(out)), 'ecseg_stitch_argmax')
         return out
+
+    def stitch_stages(self, probs, n_img, H, W):
+        """Test-only (ecseg_stitch_stages_debug): (n_img * n_patches, 256, 256, cs >= 4) float32 patch predictions, the whole batch in
+        one launch -> dict: ``labels`` (n_img, H, W) uint8, ``tie_risk`` (n_img) int32, ``probs`` (n_img, H, W, 4) float32."""
+        p = np.ascontiguousarray(probs, np.float32)
+        if p.ndim != 4 or p.shape[1:3] != (256, 256) or (n_img and p.shape[0] % n_img):
+            raise ValueError('probs must be (n_img * n_patches, 256, 256, channels), got %s' % (p.shape,))
+        res = dict(labels=np.empty((n_img, H, W), np.uint8), tie_risk=np.empty(n_img, np.int32), probs=np.empty((n_img, H, W, 4), np.float32))
+        self._check(self.lib.ecseg_stitch_stages_debug(self.h, _ptr(p), p.shape[3], n_img, H, W, _ptr(res['labels']), _ptr(res['tie_risk']),
+                                                       _ptr(res['probs'])), 'ecseg_stitch_stages_debug')
+        return res
+
+    def preprocess_stages(self, imgs):
+        """Test-only (ecseg_preprocess_stages_debug): ``preprocess`` with what it leaves on the way -> dict: ``hist`` (n, 256) uint32,
+        ``threshold`` (n) int32, ``inverted`` (n) int32, ``gray`` (n, H, W) uint8."""
+        a = np.ascontiguousarray(imgs)
+        if a.dtype not in (np.uint8, np.uint16):
+            raise TypeError('meta_preprocess takes uint8 or uint16 images, got %s' % a.dtype)
+        if a.ndim == 3:
+            a = a[..., None]
+        n, H, W, Cc = a.shape
+        res = dict(hist=np.empty((n, 256), np.uint32), threshold=np.empty(n, np.int32), inverted=np.empty(n, np.int32),
+                   gray=np.empty((n, H, W), np.uint8))
+        self._check(self.lib.ecseg_preprocess_stages_debug(self.h, _ptr(a), n, H, W, Cc, a.dtype.itemsize, _ptr(res['hist']),
+                                                           _ptr(res['threshold']), _ptr(res['inverted']), _ptr(res['gray'])),
+                    'ecseg_preprocess_stages_debug')
+        return res
+
+    def otsu(self, hists, px):
+        """Test-only (ecseg_otsu_debug): (n, 256) histograms with their pixel counts (n), each the sum of its histogram ->
+        (threshold (n) int32, inverted (n) int32) of the Otsu kernel alone."""
+        hs = np.ascontiguousarray(hists, np.uint32)
+        p = np.ascontiguousarray(px, np.int64)
+        if hs.ndim != 2 or hs.shape[1] != 256 or p.shape != (hs.shape[0],):
+            raise ValueError('hists must be (n, 256) and px (n), got %s and %s' % (hs.shape, p.shape))
+        thr, inv = np.empty(len(hs), np.int32), np.empty(len(hs), np.int32)
+        self._check(self.lib.ecseg_otsu_debug(self.h, _ptr(hs), len(hs), _ptr(p), _ptr(thr), _ptr(inv)), 'ecseg_otsu_debug')
+        return thr, inv
 
     def meta_inference(self, labels):
         a = _u8(labels)

@@ -267,8 +267,11 @@ hipError_t run_count_hsr(PostWorkspace& ws, const uint8_t* chrom, const uint8_t*
 hipError_t run_overlay(PostWorkspace& ws, uint8_t* labels, const uint8_t* rgb, int n_img, int H, int W, int C,
                        int sens, int hsr_thr, long long* out_dev, hipStream_t s);
 hipError_t launch_u16_to_u8(const uint16_t* in, uint8_t* out, size_t count, hipStream_t s);
+// hist_ws: n_img * 256 counters, left holding the histograms; threshold (may be null): Otsu's threshold per image
 hipError_t run_preprocess(const void* img, int n_img, int H, int W, int C, int bps, uint8_t* gray, int32_t* inverted,
-                          uint32_t* hist_ws, hipStream_t s);
+                          uint32_t* hist_ws, hipStream_t s, int32_t* threshold = nullptr);
+// Otsu and the "> 50 % white" decision alone on given histograms (n_img, 256); px_img (required): the sum of each; threshold may be null
+hipError_t launch_otsu_decide(const uint32_t* hist, int n_img, const long long* px_img, int32_t* inverted, int32_t* threshold, hipStream_t s);
 
 // ---- launchers implemented in interseg_kernels.hip (the file-level driver of src/interseg.py) ------------------------------
 // What ecseg_nuclei_regions leaves for ecseg_nucleus_crops: the region label map (H, W) and the first H rows of the image.

@@ -1,5 +1,5 @@
 // The one-call drivers of the clean-up and counting kernels (ccl_kernels.hip, meta_inference_kernels.hip, overlay_kernels.hip, stitch_preprocess_kernels.hip): each uploads its inputs, runs its kernels on the main
-// stream and downloads the results (u16_to_u8, stitch_argmax, meta_inference, the counts, one labelling pass alone, overlay).
+// stream and downloads the results (u16_to_u8, stitch_argmax, the stitch / preprocess / Otsu stages for the tests, meta_inference, the counts, one labelling pass alone, overlay).
 #include "driver_util.h"
 
 using namespace ecseg;
@@ -39,6 +39,87 @@ int ecseg_stitch_argmax(ecseg_ctx* h, const float* probs, int n_img, int H, int 
     HIP_TRY(h, hipMemcpyAsync(labels_raw, h->d_raw, px * n_img, hipMemcpyDeviceToHost, s));
     HIP_TRY(h, hipStreamSynchronize(s));
     return ECSEG_OK;
+}
+
+// Test-only: launch_stitch_argmax with its tie counters and launch_stitch_probs over the WHOLE batch, one launch each (segment_dev
+// stitches launch group by launch group), patches with any channel stride; every output may be null.
+int ecseg_stitch_stages_debug(ecseg_ctx* h, const float* probs, int chan_stride, int n_img, int H, int W, uint8_t* labels, int32_t* tie_risk,
+                              float* probs_out) {
+    DRIVER_OPEN(h);
+    if (n_img < 0 || chan_stride < 4 || (n_img > 0 && !probs)) return fail(h, ECSEG_E_INVALID, "stitch_stages: bad arguments");
+    if (n_img == 0) return ECSEG_OK;
+    USE_DEVICE(h);
+    StitchPlan* sp = nullptr;
+    int rc;
+    if ((rc = get_stitch(h, H, W, &sp))) return rc;
+    const size_t px = (size_t)H * W, nfl = (size_t)n_img * sp->n_pos * 65536 * chan_stride;
+    if ((rc = h->d_probs_in.ensure(h, nfl))) return rc;
+    if ((rc = h->d_raw.ensure(h, px * n_img))) return rc;
+    if ((rc = h->d_tie.ensure(h, (size_t)n_img))) return rc;
+    if ((rc = h->d_tie_sh.ensure(h, (size_t)n_img * G_SHARDS * G_STRIDE))) return rc;
+    if (probs_out && (rc = h->d_sprobs.ensure(h, px * n_img * 4))) return rc;
+    hipStream_t s = h->stream;
+    HIP_TRY(h, hipMemcpyAsync(h->d_probs_in, probs, nfl * sizeof(float), hipMemcpyHostToDevice, s));
+    HIP_TRY(h, launch_stitch_argmax(h->d_probs_in, chan_stride, sp->map_dev, n_img, sp->n_pos, H, W, h->d_raw, s, h->d_tie, h->d_tie_sh));
+    if (probs_out) HIP_TRY(h, launch_stitch_probs(h->d_probs_in, chan_stride, sp->map_dev, n_img, sp->n_pos, H, W, h->d_sprobs, s));
+    if (labels) HIP_TRY(h, hipMemcpyAsync(labels, h->d_raw, px * n_img, hipMemcpyDeviceToHost, s));
+    if (tie_risk) HIP_TRY(h, hipMemcpyAsync(tie_risk, h->d_tie, (size_t)n_img * 4, hipMemcpyDeviceToHost, s));
+    if (probs_out) HIP_TRY(h, hipMemcpyAsync(probs_out, h->d_sprobs, px * n_img * 4 * sizeof(float), hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    return ECSEG_OK;                                         // (untimed: stage_ms keeps the call before's)
+}
+
+// Test-only: run_preprocess as ecseg_preprocess runs it, with the histograms and Otsu's thresholds it leaves on the way; every output
+// may be null.
+int ecseg_preprocess_stages_debug(ecseg_ctx* h, const void* img, int n_img, int H, int W, int C, int bps, uint32_t* hist, int32_t* threshold,
+                                  int32_t* inverted, uint8_t* gray) {
+    DRIVER_OPEN(h);
+    if (n_img < 0 || H <= 0 || W <= 0 || (C != 1 && C != 3 && C != 4) || (bps != 1 && bps != 2) || (n_img > 0 && !img))
+        return fail(h, ECSEG_E_INVALID, "preprocess_stages: bad arguments");
+    if (n_img == 0) return ECSEG_OK;
+    USE_DEVICE(h);
+    const size_t px = (size_t)H * W, tot = px * n_img, in_bytes = tot * C * bps;
+    int rc;
+    if ((rc = h->d_aux8.ensure(h, in_bytes))) return rc;
+    if ((rc = h->d_gray.ensure(h, tot))) return rc;
+    if ((rc = h->d_i32.ensure(h, (size_t)2 * n_img))) return rc;       // the inverted flags, then the thresholds
+    if ((rc = h->d_hist.ensure(h, (size_t)n_img * 256))) return rc;
+    hipStream_t s = h->stream;
+    HIP_TRY(h, hipMemcpyAsync(h->d_aux8, img, in_bytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(h, run_preprocess(h->d_aux8, n_img, H, W, C, bps, h->d_gray, h->d_i32, h->d_hist, s, h->d_i32 + n_img));
+    if (hist) HIP_TRY(h, hipMemcpyAsync(hist, h->d_hist, (size_t)n_img * 256 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    if (threshold) HIP_TRY(h, hipMemcpyAsync(threshold, h->d_i32 + n_img, (size_t)n_img * 4, hipMemcpyDeviceToHost, s));
+    if (inverted) HIP_TRY(h, hipMemcpyAsync(inverted, h->d_i32, (size_t)n_img * 4, hipMemcpyDeviceToHost, s));
+    if (gray) HIP_TRY(h, hipMemcpyAsync(gray, h->d_gray, tot, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    return ECSEG_OK;                                         // (untimed)
+}
+
+// Test-only: otsu_decide_kernel alone on the caller's histograms, each with its own pixel count (which must be its sum).
+int ecseg_otsu_debug(ecseg_ctx* h, const uint32_t* hist, int n_img, const int64_t* px, int32_t* threshold, int32_t* inverted) {
+    DRIVER_OPEN(h);
+    if (n_img < 0 || (n_img > 0 && (!hist || !px))) return fail(h, ECSEG_E_INVALID, "otsu_debug: bad arguments");
+    for (int i = 0; i < n_img; ++i) {
+        unsigned long long sum = 0;
+        for (int b = 0; b < 256; ++b) sum += hist[(size_t)i * 256 + b];
+        if (px[i] < 1 || px[i] > 0x7fffffffll || (unsigned long long)px[i] != sum)
+            return fail(h, ECSEG_E_INVALID, "otsu_debug: px of histogram " + std::to_string(i) + " is not its sum, or outside 1 .. 2^31 - 1");
+    }
+    if (n_img == 0) return ECSEG_OK;
+    USE_DEVICE(h);
+    int rc;
+    if ((rc = h->d_hist.ensure(h, (size_t)n_img * 256))) return rc;
+    if ((rc = h->d_i64.ensure(h, (size_t)n_img))) return rc;
+    if ((rc = h->d_i32.ensure(h, (size_t)2 * n_img))) return rc;       // the inverted flags, then the thresholds
+    static_assert(sizeof(long long) == sizeof(int64_t), "px goes up as it is");
+    hipStream_t s = h->stream;
+    HIP_TRY(h, hipMemcpyAsync(h->d_hist, hist, (size_t)n_img * 256 * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(h->d_i64, px, (size_t)n_img * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(h, launch_otsu_decide(h->d_hist, n_img, h->d_i64, h->d_i32, h->d_i32 + n_img, s));
+    if (threshold) HIP_TRY(h, hipMemcpyAsync(threshold, h->d_i32 + n_img, (size_t)n_img * 4, hipMemcpyDeviceToHost, s));
+    if (inverted) HIP_TRY(h, hipMemcpyAsync(inverted, h->d_i32, (size_t)n_img * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    return ECSEG_OK;                                         // (untimed)
 }
 
 int ecseg_meta_inference_dev(ecseg_ctx* h, const uint8_t* in, int n_img, int H, int W, uint8_t* out, int32_t* n_ec) {

@@ -144,11 +144,17 @@ __global__ __launch_bounds__(256) void hist256_kernel(const uint8_t* __restrict_
     if (h[threadIdx.x]) atomicAdd(hist + (size_t)im * 256 + threadIdx.x, h[threadIdx.x]);
 }
 
-// Otsu threshold (OpenCV getThreshVal_Otsu_8u restated) + the "> 50 % white" decision; one thread per image
-__global__ void otsu_decide_kernel(const uint32_t* __restrict__ hist, int n_img, size_t px, int32_t* __restrict__ inverted) {
+// Otsu threshold (OpenCV getThreshVal_Otsu_8u restated) + the "> 50 % white" decision; one thread per image.  px_img (may be null:
+// every image has px_all pixels, as in the product): the pixel count of each image, the sum of its histogram; threshold (may be null)
+__global__ void otsu_decide_kernel(const uint32_t* __restrict__ hist, int n_img, size_t px_all, const long long* __restrict__ px_img,
+                                   int32_t* __restrict__ inverted, int32_t* __restrict__ threshold) {
+    // every a * b + c below rounds twice, as in OpenCV's build and in oracle/preprocess.py: contracted into fused multiply-adds
+    // (q1 + h * scale, mu1 + i * p_i, mu - q1 * mu1) the last bit of sigma changes, and with it the winner of two near-equal maxima
+#pragma clang fp contract(off)
     const int im = blockIdx.x * blockDim.x + threadIdx.x;
     if (im >= n_img) return;
     const uint32_t* h = hist + (size_t)im * 256;
+    const size_t px = px_img ? (size_t)px_img[im] : px_all;
     const double scale = 1.0 / (double)px;
     double mu = 0.0;
     for (int i = 0; i < 256; ++i) mu += (double)i * (double)h[i];
@@ -170,6 +176,14 @@ __global__ void otsu_decide_kernel(const uint32_t* __restrict__ hist, int n_img,
     unsigned long long white = 0;
     for (int i = max_val + 1; i < 256; ++i) white += h[i];
     inverted[im] = ((double)white > (double)px * 0.5) ? 1 : 0;
+    if (threshold) threshold[im] = max_val;
+}
+
+hipError_t launch_otsu_decide(const uint32_t* hist, int n_img, const long long* px_img, int32_t* inverted, int32_t* threshold, hipStream_t s) {
+    if (n_img <= 0) return hipSuccess;
+    if (!px_img) return hipErrorInvalidValue;                // (no count for all images here: 1 / 0 otherwise)
+    hipLaunchKernelGGL(otsu_decide_kernel, dim3((n_img + 63) / 64), dim3(64), 0, s, hist, n_img, (size_t)0, px_img, inverted, threshold);
+    return hipGetLastError();
 }
 
 __global__ __launch_bounds__(256) void invert_kernel(uint8_t* __restrict__ gray, const int32_t* __restrict__ inverted,
@@ -180,7 +194,7 @@ __global__ __launch_bounds__(256) void invert_kernel(uint8_t* __restrict__ gray,
 }
 
 hipError_t run_preprocess(const void* img, int n_img, int H, int W, int C, int bps, uint8_t* gray, int32_t* inverted,
-                          uint32_t* hist_ws, hipStream_t s) {
+                          uint32_t* hist_ws, hipStream_t s, int32_t* threshold) {
     if (n_img <= 0) return hipSuccess;
     const size_t px = (size_t)H * W, total = px * n_img;
     const unsigned pg = px_grid(total);
@@ -190,7 +204,7 @@ hipError_t run_preprocess(const void* img, int n_img, int H, int W, int C, int b
     if (e != hipSuccess) return e;
     const int bpi = 64;
     hipLaunchKernelGGL(hist256_kernel, dim3(n_img * bpi), dim3(256), 0, s, gray, px, hist_ws, bpi);
-    hipLaunchKernelGGL(otsu_decide_kernel, dim3((n_img + 63) / 64), dim3(64), 0, s, hist_ws, n_img, px, inverted);
+    hipLaunchKernelGGL(otsu_decide_kernel, dim3((n_img + 63) / 64), dim3(64), 0, s, hist_ws, n_img, px, (const long long*)nullptr, inverted, threshold);
     hipLaunchKernelGGL(invert_kernel, dim3(pg), dim3(256), 0, s, gray, inverted, px, total);
     return hipGetLastError();
 }

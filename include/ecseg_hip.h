@@ -72,6 +72,9 @@ extern "C" {
  * is off by default; nothing existing changed.) */
 /* (still 5 - additive: ecseg_interseg_batch, the regions, crops and classifiers of many interSeg images in one call; nothing existing
  * changed.  The number stays where every additive entry above left it: a caller of version 5 runs unchanged.) */
+/* (still 5 - additive: ecseg_stitch_stages_debug, ecseg_preprocess_stages_debug and ecseg_otsu_debug, the stitch with its tie-risk count
+ * over a whole batch in one launch, meta_preprocess with its histograms and thresholds, and Otsu alone on given histograms, for the
+ * tests of csrc/stitch_preprocess_kernels.hip; nothing existing changed.) */
 #define ECSEG_ABI_VERSION 5
 
 #define ECSEG_OK             0
@@ -271,6 +274,23 @@ int ecseg_u16_to_u8(ecseg_ctx* h, const uint16_t* in, long long count, uint8_t* 
 /* ---- stitched probabilities -> labels only (src/utils.py:116-118), for parity of the tail in isolation ---- */
 /* probs: (n_img * n_patches, 256, 256, 4) float32 patch predictions in reference patch order. */
 int ecseg_stitch_argmax(ecseg_ctx* h, const float* probs, int n_img, int H, int W, uint8_t* labels_raw);
+/* Test-only: the stitch kernels over the whole batch, one launch each (the pipeline stitches one launch group at a time, so only here
+ * does a thread's grid-stride walk reach a second image once n_img * H * W passes 16384 workgroups of 256 pixels).  probs:
+ * (n_img * n_patches, 256, 256, chan_stride) float32, chan_stride >= 4, channels 4 .. chan_stride - 1 never read.  Every output may
+ * be NULL: labels (n_img, H, W) uint8, the quantised first-maximum argmax; tie_risk (n_img) int32, as ecseg_segment_images_ex counts
+ * it (written pixels whose two largest quantised values differ by at most 1); probs_out (n_img, H, W, 4) float32, the stitched
+ * probabilities, 0 where the stitch writes nothing.  ECSEG_E_INVALID: chan_stride < 4, a NULL probs, an image below 256 x 256. */
+int ecseg_stitch_stages_debug(ecseg_ctx* h, const float* probs, int chan_stride, int n_img, int H, int W, uint8_t* labels, int32_t* tie_risk,
+                              float* probs_out);
+/* Test-only: ecseg_preprocess with what it leaves on the way.  img, n_img, H, W, C, bytes_per_sample as there.  Every output may be
+ * NULL: hist (n_img, 256) uint32, the histogram of the 8-bit image before the inversion; threshold (n_img) int32, Otsu's threshold;
+ * inverted (n_img) int32; gray (n_img, H, W) uint8 as ecseg_preprocess returns it. */
+int ecseg_preprocess_stages_debug(ecseg_ctx* h, const void* img, int n_img, int H, int W, int C, int bytes_per_sample, uint32_t* hist,
+                                  int32_t* threshold, int32_t* inverted, uint8_t* gray);
+/* Test-only: the Otsu kernel of ecseg_preprocess alone on given histograms.  hist: (n_img, 256) uint32; px: (n_img) int64, the pixel
+ * count of each image - it must be the sum of its histogram and lie in 1 .. 2^31 - 1, anything else is ECSEG_E_INVALID.  threshold,
+ * inverted (n_img) int32, either may be NULL: Otsu's threshold and the "more than half of the pixels lie above it" flag. */
+int ecseg_otsu_debug(ecseg_ctx* h, const uint32_t* hist, int n_img, const int64_t* px, int32_t* threshold, int32_t* inverted);
 
 /* ---- meta_inference(I) (src/image_tools.py:15-84) + count_cc(I==3)[0] on given label images -------------- */
 int ecseg_meta_inference(ecseg_ctx* h, const uint8_t* labels_in, int n_img, int H, int W,
