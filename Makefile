@@ -92,5 +92,15 @@ asan_iseg_batch:
 	    tools/asan/iseg_batch_check.cpp -o $(ISEG_BATCH_CHECK)
 	$(ISEG_BATCH_CHECK)
 
+# and for stat_fish.batch: the layout header of ecseg_stat_fish_batch (csrc/fish_batch.h) - rasters, typed arrays by element, padded
+# planes, the arena and its restated byte count - over seeded chunks, reversed order, mixed C and K, zero-nucleus images and capacities
+# one short; tests/test_stat_fish_batch.py builds and runs it.  FISH_BATCH_CHECK: where the program is put
+FISH_BATCH_CHECK ?= /tmp/ecseg_fish_batch_check
+.PHONY: asan_fish_batch
+asan_fish_batch:
+	g++ -std=c++17 -O1 -g -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=all \
+	    tools/asan/fish_batch_check.cpp -o $(FISH_BATCH_CHECK)
+	$(FISH_BATCH_CHECK)
+
 clean:
 	rm -rf __pycache__ ecseg_amd/csrc/*.o ecseg_amd/libecseg_*.so

@@ -34,6 +34,7 @@ EXPORTS = [
     'ecseg_marker_watershed_stages_debug', 'ecseg_marker_watershed_batch_stages_debug',
     'ecseg_interseg_batch',
     'ecseg_stitch_stages_debug', 'ecseg_preprocess_stages_debug', 'ecseg_otsu_debug',
+    'ecseg_stat_fish_batch', 'ecseg_stat_fish_batch_bytes',
 ]
 
 
@@ -160,6 +161,9 @@ def load_library():
     lib.ecseg_tiff_encode_batch_bytes.argtypes = [vp, i32]; lib.ecseg_tiff_encode_batch_bytes.restype = C.c_longlong
     lib.ecseg_fish_render_tiff_batch.argtypes = [vp, i32, C.POINTER(vp), vp, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp,
                                                  C.c_longlong, vp]
+    lib.ecseg_stat_fish_batch.argtypes = [vp, i32, C.POINTER(vp), vp, vp, C.POINTER(vp), C.POINTER(vp), vp, C.POINTER(vp), vp, vp, vp, i32,
+                                          C.POINTER(vp), C.POINTER(vp), i32, vp, vp, vp, vp, C.c_longlong, vp, vp, vp]
+    lib.ecseg_stat_fish_batch_bytes.argtypes = [i32, vp, vp, vp, i32]; lib.ecseg_stat_fish_batch_bytes.restype = C.c_longlong
     lib.ecseg_tiff_decode.argtypes = [vp, vp, C.c_longlong, vp, C.c_longlong, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
     lib.ecseg_tiff_decode_routes.argtypes = [vp, C.c_longlong]
     lib.ecseg_tiff_decode_batch.argtypes = [vp, vp, C.c_longlong, vp, i32, vp, C.c_longlong, vp, vp, vp]
@@ -1308,6 +1312,148 @@ class Handle:
             for i, c in enumerate(chunk):
                 have = (True, True, True, c[4] is not None, c[5] is not None)
                 out.append(tuple(files[o:o + k].tobytes() if h else None for (o, k), h in zip(ranges[i].tolist(), have)))
+        return out
+
+    # ---- stat_fish.batch: mask to file images of k images per call ------------------------------------------
+    STAT_FISH_ITEM_KEYS = ('img', 'channels', 'mask', 'labels', 'weights', 'normal_threshold', 'intensity_thresholds', 'min_cc_size',
+                           'mask_file', 'picture')
+
+    @classmethod
+    def _stat_fish_item(cls, item):
+        """One item of ``stat_fish_many`` checked and made contiguous -> the tuple ``stat_fish_packed`` takes, or raises."""
+        unknown = set(item) - set(cls.STAT_FISH_ITEM_KEYS)
+        if unknown:
+            raise ValueError('stat_fish_many: unknown item keys %s' % sorted(unknown))
+        im = _u8(item['img'])
+        if im.ndim != 3 or im.shape[2] not in (3, 4) or not im.size:
+            raise ValueError('stat_fish_many takes non-empty (H, W, 3) or (H, W, 4) uint8 images')
+        H, W, Cn = im.shape
+        ch = np.ascontiguousarray(item['channels'], np.int32).reshape(-1)
+        if len(ch) != Cn:
+            raise ValueError('stat_fish_many takes one channel index per image channel (blue, green, red[, aqua])')
+        mask, labels = item.get('mask'), item.get('labels')
+        if (mask is None) == (labels is None):
+            raise ValueError('stat_fish_many takes exactly one of mask and labels per image')
+        if mask is not None:
+            mask = _u8(mask)
+            if mask.shape != (H, W):
+                raise ValueError('stat_fish_many takes an (H, W) uint8 mask of the image\'s extent')
+        else:
+            labels = np.ascontiguousarray(labels)
+            if labels.dtype != np.int32:
+                if labels.dtype.kind not in 'iu' or (labels.size and (int(labels.max()) > 2 ** 31 - 1 or int(labels.min()) < -2 ** 31)):
+                    raise ValueError('stat_fish_many takes integer labels that fit int32')
+                labels = labels.astype(np.int32)
+            if labels.shape != (H, W):
+                raise ValueError('stat_fish_many takes an (H, W) label map of the image\'s extent')
+        w = np.ascontiguousarray(item['weights'], np.float64)
+        if w.ndim != 2 or w.shape[0] != w.shape[1] or not w.size:
+            raise ValueError('stat_fish_many takes a square K x K kernel')
+        ithr = np.ascontiguousarray(item['intensity_thresholds'], np.float64).reshape(-1)
+        if len(ithr) != Cn - 1:
+            raise ValueError('stat_fish_many takes one intensity threshold per probe channel (C - 1 of them)')
+        mask_file, picture = item.get('mask_file'), item.get('picture')
+        if mask_file is True:
+            if mask is None:
+                raise ValueError('stat_fish_many: mask_file=True needs a mask')
+            mask_file = mask
+        elif mask_file is not None:
+            mask_file = _u8(mask_file)
+        picture = None if picture is None else _u8(picture)
+        if (mask_file is not None and mask_file.shape != (H, W)) or (picture is not None and picture.shape != (H, W, 3)):
+            raise ValueError('stat_fish_many takes an (H, W) mask file raster and an (H, W, 3) picture of the image\'s extent, or None')
+        return (im, np.concatenate([ch, np.zeros(4 - len(ch), np.int32)]), mask, labels, w, float(item['normal_threshold']),
+                np.concatenate([ithr, np.zeros(3 - len(ithr))]), int(item['min_cc_size']), mask_file, picture)
+
+    def _stat_fish_tables(self, chunk):
+        shapes = np.array([c[0].shape for c in chunk], np.int32).reshape(-1, 3)
+        ks = np.array([c[4].shape[0] for c in chunk], np.int32)
+        flags = np.array([(c[3] is not None) | ((c[8] is not None) << 1) | ((c[8] is not None and c[8] is c[2]) << 2) | ((c[9] is not None) << 3)
+                          for c in chunk], np.int32)
+        return shapes, ks, flags
+
+    def stat_fish_batch_bytes(self, chunk, record_capacity):
+        """Device scratch one ``stat_fish_packed`` call over these prepared items needs (ecseg_stat_fish_batch_bytes; -1: refused)."""
+        shapes, ks, flags = self._stat_fish_tables(chunk)
+        return self.lib.ecseg_stat_fish_batch_bytes(len(chunk), _ptr(shapes), _ptr(ks), _ptr(flags), int(record_capacity))
+
+    def stat_fish_packed(self, chunk, line_thickness, record_capacity, out_capacity=None, want_masks=False, poison=None):
+        """ecseg_stat_fish_batch as it is over prepared items (``_stat_fish_item``) -> dict: ``n_cells`` (n,) int32, ``ranks`` int32 (the
+        images' maps back to back), ``records`` int64 (record_capacity, 24), ``out`` uint8 with ``ranges`` (n, 5, 2), and with
+        ``want_masks`` ``thresholded`` and ``boundaries`` (uint8, back to back).  ``out_capacity``: bytes of ``out`` (default: the sum of
+        ecseg_tiff_encode_bound).  ``poison``: a byte every output buffer is filled with before the call (tests)."""
+        n = len(chunk)
+        shapes, ks, _ = self._stat_fish_tables(chunk)
+        chans = np.ascontiguousarray(np.stack([c[1] for c in chunk]), np.int32) if n else np.zeros((0, 4), np.int32)
+        ptrs = lambda col: (C.c_void_p * max(n, 1))(*[None if c[col] is None else c[col].ctypes.data for c in chunk])
+        normal = np.array([c[5] for c in chunk], np.float64)
+        ithr = np.ascontiguousarray(np.stack([c[6] for c in chunk]), np.float64) if n else np.zeros((0, 3))
+        min_cc = np.array([c[7] for c in chunk], np.int32)
+        px = [int(c[0].shape[0]) * int(c[0].shape[1]) for c in chunk]
+        if out_capacity is None:
+            out_capacity = 0
+            for c in chunk:
+                H, W = c[0].shape[:2]
+                out_capacity += 3 * self.lib.ecseg_tiff_encode_bound(H, W, 3) + (self.lib.ecseg_tiff_encode_bound(H, W, 1) if c[8] is not None else 0) + \
+                    (self.lib.ecseg_tiff_encode_bound(H, W, 3) if c[9] is not None else 0)
+            if out_capacity < 0:
+                raise ValueError('stat_fish_many: an image that cannot be written as a TIFF')
+        cap = int(record_capacity)
+        def new(shape, dt):
+            a = np.empty(shape, dt)
+            if poison is not None:
+                a.view(np.uint8)[...] = poison
+            return a
+        res = dict(n_cells=new((max(n, 1),), np.int32), ranks=new((max(sum(px), 1),), np.int32), records=new((max(cap, 1), self.FISH_SPOT_INT64), np.int64),
+                   out=new((max(int(out_capacity), 1),), np.uint8), ranges=new((max(n, 1), 5, 2), np.int64))
+        if want_masks:
+            res['thresholded'] = new((max(sum(p * (c[0].shape[2] - 1) for p, c in zip(px, chunk)), 1),), np.uint8)
+            res['boundaries'] = new((max(sum(px), 1),), np.uint8)
+        self._check(self.lib.ecseg_stat_fish_batch(self.h, n, ptrs(0), _ptr(shapes), _ptr(chans), ptrs(2), ptrs(3), _ptr(ks), ptrs(4), _ptr(normal),
+                                                   _ptr(ithr), _ptr(min_cc), int(line_thickness), ptrs(8), ptrs(9), cap, _ptr(res['ranks']),
+                                                   _ptr(res['records']), _ptr(res['n_cells']), _ptr(res['out']), int(out_capacity), _ptr(res['ranges']),
+                                                   _ptr(res.get('thresholded')), _ptr(res.get('boundaries'))), 'ecseg_stat_fish_batch')
+        res['n_cells'] = res['n_cells'][:n]
+        res['ranges'] = res['ranges'][:n]
+        return res
+
+    def stat_fish_many(self, items, line_thickness, record_capacity=4096, budget_bytes=8 << 30, want_masks=False):
+        """stat_fish from the mask to the file images for a list of images (ecseg_stat_fish_batch): per item what ``ccl_labels`` ->
+        ``fish_spots`` -> ``fish_render_tiff_many`` give, in one device call per chunk.  An item is a dict: ``img`` (H, W, C) uint8,
+        C = 3 or 4; ``channels`` its (blue, green, red[, aqua]) indices; exactly one of ``mask`` ((H, W) uint8, non-zero = nucleus,
+        labelled 8-connected on the device) and ``labels`` ((H, W) integer map, used as given); ``weights`` (K x K float64),
+        ``normal_threshold``, ``intensity_thresholds`` (C - 1), ``min_cc_size``; optional ``mask_file`` (an (H, W) uint8 raster, or True
+        for the mask itself) and ``picture`` ((H, W, 3) uint8), encoded beside the three colour files.
+        -> per item ``(ranks, records, files)``: the (H, W) int32 dense ranks (0 background, 1 .. n in ascending label order), the
+        (n, 24) int64 records of ``fish_spots`` and the tuple (original, with_segmentation, lsq, mask file or None, picture or None) of
+        ``bytes``; with ``want_masks`` a fourth and fifth entry, ``fish_spots``' thresholded and boundaries.  An item that fails
+        validation has its exception in its place and takes no part; the others are unaffected.  ``record_capacity`` is grown and the
+        call repeated once when the chunk holds more cells.  The list goes in one call while ecseg_stat_fish_batch_bytes stays within
+        ``budget_bytes``, else in consecutive calls (an item above the budget alone goes alone); the returned list is the same."""
+        out = [None] * len(items)
+        good = []
+        for k, item in enumerate(items):
+            try:
+                good.append((k, self._stat_fish_item(item)))
+            except (ValueError, TypeError, KeyError) as e:
+                out[k] = e
+        needs = [self.stat_fish_batch_bytes([c], 0) for _, c in good]
+        for lo, hi in self._split_by_budget(needs, budget_bytes):
+            chunk = [c for _, c in good[lo:hi]]
+            res = self.stat_fish_packed(chunk, line_thickness, record_capacity, want_masks=want_masks)
+            total = int(res['n_cells'].sum())
+            if total > record_capacity:                      # the counts alone came back: once more with room for them
+                res = self.stat_fish_packed(chunk, line_thickness, total, want_masks=want_masks)
+            p0 = r0 = t0 = 0
+            for (k, _), c, n, rng in zip(good[lo:hi], chunk, res['n_cells'].tolist(), res['ranges'].tolist()):
+                H, W, Cn = c[0].shape
+                have = (True, True, True, c[8] is not None, c[9] is not None)
+                files = tuple(res['out'][o:o + m].tobytes() if hv else None for (o, m), hv in zip(rng, have))
+                entry = (res['ranks'][p0:p0 + H * W].reshape(H, W).copy(), res['records'][r0:r0 + n].copy(), files)
+                if want_masks:
+                    entry += (res['thresholded'][t0:t0 + H * W * (Cn - 1)].reshape(H, W, Cn - 1).copy(), res['boundaries'][p0:p0 + H * W].reshape(H, W).copy())
+                out[k] = entry
+                p0 += H * W; r0 += n; t0 += H * W * (Cn - 1)
         return out
 
     # ---- min-cut splitter -------------------------------------------------------------------------------

@@ -159,19 +159,16 @@ __device__ __forceinline__ void uf_unite_back(int32_t* par, int p, int y, int x,
     }
 }
 
-// Plane blockIdx.y of par / sz (px entries each): parent = root for every keyed pixel, sz[root] = pixels of the component.
-// cnt (may be null; one plane only): [0] += components, [1] += keyed pixels.
-static __global__ __launch_bounds__(256) void uf_size_kernel(int px, int32_t* par_all, int32_t* __restrict__ sz_all,
-                                                             int32_t* __restrict__ cnt) {
-    const unsigned pu = blockIdx.x * 256u + threadIdx.x;     // px < 2^31: no wrap
+// Pixel pu of one plane of par / sz (px entries each): parent = root for a keyed pixel, sz[root] = pixels of the component.
+// cnt (may be null): [0] += components, [1] += keyed pixels.  Call it with whole waves (the counters are summed by ballot).
+__device__ __forceinline__ void uf_size_pixel(int px, int32_t* par, int32_t* __restrict__ sz, int32_t* __restrict__ cnt, unsigned pu) {
     const int p = (int)pu;
-    int32_t* par = par_all + (size_t)blockIdx.y * (size_t)px;
     bool keyed = false, is_root = false;
     if (pu < (unsigned)px && uf_load(par, p) >= 0) {
         keyed = true;
         const int root = uf_find(par, p);
         __hip_atomic_store(par + p, root, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // a shortcut inside the same tree
-        atomicAdd(sz_all + (size_t)blockIdx.y * (size_t)px + root, 1);
+        atomicAdd(sz + root, 1);
         is_root = root == p;
     }
     if (cnt) {                                               // one atomic per wave and counter
@@ -181,6 +178,25 @@ static __global__ __launch_bounds__(256) void uf_size_kernel(int px, int32_t* pa
             if (nk) atomicAdd(cnt + 1, nk);
         }
     }
+}
+
+// Plane blockIdx.y of par / sz (px entries each); cnt: one plane only.
+static __global__ __launch_bounds__(256) void uf_size_kernel(int px, int32_t* par_all, int32_t* __restrict__ sz_all,
+                                                             int32_t* __restrict__ cnt) {
+    const size_t o = (size_t)blockIdx.y * (size_t)px;
+    uf_size_pixel(px, par_all + o, sz_all + o, cnt, blockIdx.x * 256u + threadIdx.x);   // px < 2^31: no wrap
+}
+
+// ---- the dense cell index -------------------------------------------------------------------------------------------------
+// Pixel p of a label map of px pixels: flag[label - 1] = 1 for a label that occurs; *bad = 1 when a label exceeds px (the caller
+// refuses the map).  An exclusive scan over flag then gives every label its dense ascending cell index.
+__device__ __forceinline__ void cell_mark_pixel(const int32_t* __restrict__ L, int px, int32_t* __restrict__ flag, int32_t* __restrict__ bad,
+                                                unsigned p) {
+    if (p >= (unsigned)px) return;
+    const int l = L[p];
+    if (l <= 0) return;
+    if (l > px) { *bad = 1; return; }
+    flag[l - 1] = 1;
 }
 
 }  // namespace ecseg

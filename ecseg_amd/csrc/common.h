@@ -6,6 +6,7 @@
 #include "../../include/ecseg_hip.h"
 #include "scratch.h"
 #include "iseg_batch.h"
+#include "fish_batch.h"
 #include "tiff_decode_batch.h"
 #include "tiff_encode_batch.h"
 #include "tiff_frame.h"
@@ -336,6 +337,11 @@ inline IsegBatchBufs iseg_batch_bufs(Carver& c, int n, int Hm, int Wm, size_t sp
     b.cap = cap;
     return b;
 }
+// The opening of a chunk of masks of different extents, shared by ecseg_interseg_batch and ecseg_stat_fish_batch: mask (n, Hm, Wm) =
+// the segmentation of tab[i] (seg_off, h, w; bytes of `packed`) in the top left corner, background elsewhere; lab = its 8-connected
+// labels (run_ccl_labels: 1 + the raster index, in the padded plane, of the component's first pixel).  n * Hm * Wm < 2^31.
+hipError_t run_pad_label_masks(const uint8_t* packed, const IsegImage* tab, int n, int Hm, int Wm, uint8_t* mask, int32_t* lab, PostWorkspace& ws,
+                               hipStream_t s);
 // The group's tab and packed bytes are on the device: pads and labels the masks, numbers the regions per image, hands the cap records
 // out (plan, misc[3] = records taken) and writes them; imisc[i][1..2]: image i's value range, as misc[1..2] of run_nuclei_regions.
 hipError_t run_iseg_batch_regions(int n, int Hm, int Wm, int ch0, const IsegBatchBufs& b, PostWorkspace& ws, hipStream_t s);
@@ -400,6 +406,15 @@ inline FishSpotBufs fishspot_bufs(Carver& c, const CellIndexBufs& cells, int H, 
 // n records of ecseg_fish_spots.  img: (H, W, C) uint8; ch: the np probe channels; wts: K x K float64 on the device.
 hipError_t run_fishspot(int32_t* labels, const uint8_t* img, int H, int W, int C, int np, const int ch[3], const double* wts, int K,
                         double normal_thr, const double ithr[3], int min_cc, int line_t, int n, const FishSpotBufs& b, hipStream_t s);
+
+// A chunk of images (ecseg_stat_fish_batch; layout, table and buffers in fish_batch.h).  b.work holds the rasters, b.tab the rows,
+// b.ptab the padded images' rows, b.w the weights, and the given label maps lie in b.lab.  run_fishspot_batch_open labels the masks,
+// builds the dense cell index of every image with one scan and leaves per image its cells and first record in the rows and in b.plan
+// ((n + 1, 2) int32: cells, 1 = a label above H * W; the last pair: the chunk's cells).  run_fishspot_batch, once the caller has
+// read the plan and laid out c for `cells`: run_fishspot for every image, one launch per stage; b.lab becomes the ranks.
+hipError_t run_fishspot_batch_open(const FsBatchLayout& L, const FsBatchBufs& b, PostWorkspace& ws, hipStream_t s);
+hipError_t run_fishspot_batch(const FsBatchLayout& L, const FsBatchBufs& b, const FsBatchCellBufs& c, int cells, int max_cells, int line_t,
+                              hipStream_t s);
 
 // Device buffers of ecseg_fish_render for one H x W image of C channels: the inputs img (C bytes per pixel), thr (C - 1) and bnd
 // (1), and the three (H, W, 3) outputs orig, seg and lsq.

@@ -1,5 +1,7 @@
 // The FISH drivers: the per-nucleus distances (fishdist_kernels.hip), stat_fish's spots and its three colour files
 // (fishspot_kernels.hip; as TIFF files through tiff_collect of drivers_files.hip) and the min-cut tasks (mincut_kernels.hip).
+#include <algorithm>
+
 #include "driver_util.h"
 
 using namespace ecseg;
@@ -252,6 +254,162 @@ int ecseg_fish_render_tiff_batch(ecseg_ctx* h, int n_images, const uint8_t* cons
             q[1] = at[i].has[k] ? ranges[2 * f + 1] : 0;
             f += at[i].has[k];
         }
+    return ECSEG_OK;
+}
+
+// ---- stat_fish.batch: mask to file images for a chunk of images in one call (layout: fish_batch.h) ---------------------------------
+}  // extern "C"
+
+// What ecseg_stat_fish_batch and ecseg_stat_fish_batch_bytes plan alike: the chunk's layout and, over its encoded rasters, the
+// batched encoder's.  Empty string, or what is wrong.
+struct FsBatchPlan { FsBatchLayout L; TeBatchLayout T; };
+static std::string fs_batch_plan(const std::vector<FsImageIn>& in, FsBatchPlan& p) {
+    std::string bad = fs_batch_layout(in, p.L);
+    if (!bad.empty()) return bad;
+    std::vector<TeFileIn> files;
+    bad = tiff_encode_batch_plan(p.L.files.data(), (int)(p.L.files.size() / 5), (long long)p.L.work, files);
+    if (bad.empty()) bad = te_batch_layout(files, p.T);
+    return bad;
+}
+
+extern "C" {
+
+long long ecseg_stat_fish_batch_bytes(int n_images, const int32_t* shapes, const int32_t* kernel_sizes, const int32_t* flags,
+                                      int record_capacity) {
+    if (n_images == 0) return 0;
+    if (n_images < 0 || !shapes || !kernel_sizes || !flags || record_capacity < 0) return -1;
+    std::vector<FsImageIn> in((size_t)n_images);
+    for (size_t i = 0; i < in.size(); ++i) {
+        in[i].H = shapes[3 * i]; in[i].W = shapes[3 * i + 1]; in[i].C = shapes[3 * i + 2]; in[i].K = kernel_sizes[i];
+        in[i].given_labels = flags[i] & 1; in[i].mask_file = flags[i] & 2; in[i].mask_is_file = flags[i] & 4; in[i].picture = flags[i] & 8;
+    }
+    FsBatchPlan p;
+    if (!fs_batch_plan(in, p).empty()) return -1;
+    Carver c, cells;
+    (void)fs_batch_bufs(c, p.L);
+    (void)tiff_encode_batch_bufs(c, p.T, false);
+    (void)fs_batch_cell_bufs(cells, (size_t)record_capacity);
+    return (long long)(c.used + cells.used);
+}
+
+int ecseg_stat_fish_batch(ecseg_ctx* h, int n_images, const uint8_t* const* imgs, const int32_t* shapes, const int32_t* channels,
+                          const uint8_t* const* masks, const int32_t* const* labels, const int32_t* kernel_sizes,
+                          const double* const* weights, const double* normal_thresholds, const double* intensity_thresholds,
+                          const int32_t* min_cc_sizes, int line_thickness, const uint8_t* const* mask_files,
+                          const uint8_t* const* pictures, int record_capacity, int32_t* ranks, int64_t* records, int32_t* n_cells,
+                          uint8_t* out, long long out_cap, int64_t* out_ranges, uint8_t* thresholded_debug, uint8_t* boundaries_debug) {
+    DRIVER_OPEN(h);
+    static_assert(FSB_MAX_IMAGES == ECSEG_STAT_FISH_BATCH_MAX_IMAGES && FSB_MAX_KERNEL == ECSEG_FISH_SPOT_MAX_KERNEL, "fish_batch.h and the header disagree");
+    const std::string me = "stat_fish_batch: ";
+    if (n_images < 0 || out_cap < 0 || record_capacity < 0 || (record_capacity > 0 && !records) ||
+        (n_images > 0 && (!imgs || !shapes || !channels || (!masks && !labels) || !kernel_sizes || !weights || !normal_thresholds ||
+                          !intensity_thresholds || !min_cc_sizes || !ranks || !n_cells || !out || !out_ranges)))
+        return fail(h, ECSEG_E_INVALID, me + "bad arguments");
+    if (line_thickness < 1 || line_thickness > ECSEG_FISH_SPOT_MAX_LINE)
+        return fail(h, ECSEG_E_INVALID, me + "line_thickness must be between 1 and " + std::to_string(ECSEG_FISH_SPOT_MAX_LINE));
+    clear_timings(h);
+    if (n_images == 0) return ECSEG_OK;
+    if (n_images > FSB_MAX_IMAGES) return fail(h, ECSEG_E_INVALID, me + "more than " + std::to_string(FSB_MAX_IMAGES) + " images");
+    const size_t n = (size_t)n_images;
+    std::vector<FsImageIn> in(n);
+    for (size_t i = 0; i < n; ++i) {
+        const std::string who = me + "image " + std::to_string(i) + ": ";
+        const bool has_mask = masks && masks[i], has_labels = labels && labels[i];
+        if (!imgs[i] || !weights[i]) return fail(h, ECSEG_E_INVALID, who + "bad arguments (no image or no weights)");
+        if (has_mask == has_labels) return fail(h, ECSEG_E_INVALID, who + "exactly one of the mask and the label map must be given");
+        const int C = shapes[3 * i + 2];
+        if (C < 3 || C > 4) return fail(h, ECSEG_E_INVALID, who + "the image must have 3 or 4 channels, not " + std::to_string(C));
+        for (int j = 0; j < C; ++j)
+            if (channels[4 * i + j] < 0 || channels[4 * i + j] >= C)
+                return fail(h, ECSEG_E_INVALID, who + "channel index out of range (the image has " + std::to_string(C) + " channels)");
+        FsImageIn& f = in[i];
+        f.H = shapes[3 * i]; f.W = shapes[3 * i + 1]; f.C = C; f.K = kernel_sizes[i];
+        f.given_labels = has_labels; f.mask_file = mask_files && mask_files[i]; f.picture = pictures && pictures[i];
+        f.mask_is_file = f.mask_file && has_mask && mask_files[i] == masks[i];
+    }
+    FsBatchPlan p;
+    const std::string bad = fs_batch_plan(in, p);
+    if (!bad.empty()) return fail(h, ECSEG_E_INVALID, me + bad);
+    FsBatchLayout& L = p.L;
+    for (size_t i = 0; i < n; ++i) {
+        FsImage& t = L.tab[i];
+        for (int j = 0; j < 4; ++j) t.ch[j] = j < t.C ? channels[4 * i + j] : 0;
+        for (int j = 0; j < 3; ++j) t.ithr[j] = j < t.np ? intensity_thresholds[3 * i + j] : 0.0;
+        t.normal_thr = normal_thresholds[i]; t.min_cc = min_cc_sizes[i];
+        n_cells[i] = 0;
+    }
+    {
+        Carver measure;
+        (void)fs_batch_bufs(measure, L);
+        if ((long long)measure.used != fs_batch_bytes(L)) return fail(h, ECSEG_E_INVALID, me + "fs_batch_bytes does not restate fs_batch_bufs");
+    }
+    USE_DEVICE(h);
+    int rc;
+    FsBatchBufs b{};
+    TiffEncodeBatchBufs t{};
+    if (L.n_pad > 0 && (rc = ensure_post(h, L.n_pad, (size_t)L.Hm * L.Wm))) return rc;
+    if ((rc = lay_out(h, h->call_arena, [&](Carver& c) { b = fs_batch_bufs(c, L); t = tiff_encode_batch_bufs(c, p.T, false); }))) return rc;
+    t.src = b.work + p.T.src_base;                           // (the table's offsets count from the first encoded raster)
+    hipStream_t s = h->stream;
+    const std::vector<IsegImage> ptab = fs_batch_pad_table(L);
+    for (size_t i = 0; i < n; ++i) {
+        const FsImage& r = L.tab[i];
+        const size_t px = (size_t)r.H * r.W;
+        HIP_TRY(h, hipMemcpyAsync(b.work + r.img, imgs[i], px * r.C, hipMemcpyHostToDevice, s));
+        HIP_TRY(h, hipMemcpyAsync(b.w + r.w, weights[i], (size_t)r.K * r.K * sizeof(double), hipMemcpyHostToDevice, s));
+        if (in[i].given_labels) HIP_TRY(h, hipMemcpyAsync(b.lab + r.lab, labels[i], px * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        else HIP_TRY(h, hipMemcpyAsync(b.work + r.msk, masks[i], px, hipMemcpyHostToDevice, s));
+        if (in[i].mask_file && !in[i].mask_is_file) HIP_TRY(h, hipMemcpyAsync(b.work + r.file[3], mask_files[i], px, hipMemcpyHostToDevice, s));
+        if (in[i].picture) HIP_TRY(h, hipMemcpyAsync(b.work + r.file[4], pictures[i], px * 3, hipMemcpyHostToDevice, s));
+    }
+    HIP_TRY(h, hipMemcpyAsync(b.tab, L.tab.data(), n * sizeof(FsImage), hipMemcpyHostToDevice, s));
+    if (!ptab.empty()) HIP_TRY(h, hipMemcpyAsync(b.ptab, ptab.data(), ptab.size() * sizeof(IsegImage), hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(t.tab, p.T.tab.data(), p.T.tab.size() * sizeof(TeFile), hipMemcpyHostToDevice, s));
+    TIMED(h, s, 0, 1, HIP_TRY(h, run_fishspot_batch_open(L, b, h->ws, s)));
+    std::vector<int32_t> plan((n + 1) * 2);
+    HIP_TRY(h, hipMemcpyAsync(plan.data(), b.plan, plan.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));   // every image's cells in one copy
+    WAIT_SET(h, s, 0, 1);
+    int max_cells = 0;
+    for (size_t i = 0; i < n; ++i) {
+        if (plan[2 * i + 1])
+            return fail(h, ECSEG_E_INVALID, me + "image " + std::to_string(i) + ": the label map holds a label larger than H * W = " +
+                                                std::to_string((long long)L.tab[i].H * L.tab[i].W) + " (renumber the labels by rank first)");
+        n_cells[i] = plan[2 * i];
+        max_cells = std::max(max_cells, plan[2 * i]);
+    }
+    const int cells = plan[2 * n];
+    if (cells > record_capacity) return ECSEG_OK;           // the counts alone: the caller comes back with a larger buffer
+    FsBatchCellBufs c{};
+    if ((rc = lay_out(h, h->count_arena, [&](Carver& cv) { c = fs_batch_cell_bufs(cv, (size_t)cells); }))) return rc;
+    TIMED(h, s, 2, 3,
+          HIP_TRY(h, run_fishspot_batch(L, b, c, cells, max_cells, line_thickness, s));
+          for (size_t i = 0; i < n; ++i) {
+              const FsImage& r = L.tab[i];
+              const FishRenderBufs fr{b.work + r.img, b.work + r.thr, b.work + r.bnd, b.work + r.file[0], b.work + r.file[1], b.work + r.file[2]};
+              HIP_TRY(h, run_fish_render(r.H, r.W, r.C, r.ch, fr, s));
+          }
+          HIP_TRY(h, run_tiff_encode_batch(t, p.T, s)));
+    std::vector<int64_t> ranges(2 * p.T.tab.size());
+    if ((rc = tiff_batch_collect(h, "stat_fish_batch", p.T, t, out, out_cap, ranges.data()))) return rc;   // (waits for the stream; too small: nothing written)
+    timed_add(h, 2, 3);
+    HIP_TRY(h, hipMemcpyAsync(ranks, b.lab, L.px * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    if (cells > 0) HIP_TRY(h, hipMemcpyAsync(records, c.rec, (size_t)cells * ECSEG_FISH_SPOT_INT64 * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    size_t f = 0, thr_at = 0, bnd_at = 0;
+    for (size_t i = 0; i < n; ++i) {
+        const FsImage& r = L.tab[i];
+        const size_t px = (size_t)r.H * r.W;
+        if (thresholded_debug) HIP_TRY(h, hipMemcpyAsync(thresholded_debug + thr_at, b.work + r.thr, px * r.np, hipMemcpyDeviceToHost, s));
+        if (boundaries_debug) HIP_TRY(h, hipMemcpyAsync(boundaries_debug + bnd_at, b.work + r.bnd, px, hipMemcpyDeviceToHost, s));
+        thr_at += px * r.np; bnd_at += px;
+        for (int k = 0; k < FSB_FILES; ++k) {
+            int64_t* q = out_ranges + 2 * (FSB_FILES * i + k);
+            const bool has = r.file[k] >= 0;
+            q[0] = has ? ranges[2 * f] : 0;
+            q[1] = has ? ranges[2 * f + 1] : 0;
+            f += has;
+        }
+    }
+    HIP_TRY(h, hipStreamSynchronize(s));
     return ECSEG_OK;
 }
 

@@ -34,12 +34,7 @@ static constexpr int FD_TILE = 1024;             // centromere pixels per LDS ti
 // flag[label - 1] = 1 for every label that occurs; misc[3] = 1 when a label exceeds px (the caller refuses the map)
 __global__ __launch_bounds__(256) void fd_mark_kernel(const int32_t* __restrict__ L, int px, int32_t* __restrict__ flag,
                                                       int32_t* __restrict__ misc) {
-    const unsigned p = blockIdx.x * 256u + threadIdx.x;     // px < 2^31: no wrap
-    if (p >= (unsigned)px) return;
-    const int l = L[p];
-    if (l <= 0) return;
-    if (l > px) { misc[3] = 1; return; }
-    flag[l - 1] = 1;
+    cell_mark_pixel(L, px, flag, misc + 3, blockIdx.x * 256u + threadIdx.x);     // px < 2^31: no wrap
 }
 
 // acc: per cell (area, FISH pixels, centromere pixels, bits) uint32; bits: 1 = channel 0 non-zero somewhere in the cell,

@@ -43,9 +43,13 @@ static constexpr int FS_SLOTS = 4;                           // union-find slots
 struct FsChannels { int c[3]; };
 struct FsThresholds { double t[3]; };
 
+// Every stage is stated once, as a __device__ function of the thread's index over ONE image's buffers (the block index is
+// blockIdx.x in both forms).  The fs_* kernels run it on the image of ecseg_fish_spots; the fsb_* kernels (further down) run it on
+// image blockIdx.y of a chunk, whose buffers they find through the FsImage table (fish_batch.h).
+
 // mx[j] = max over the image of channel ch.c[j]
-__global__ __launch_bounds__(256) void fs_channel_max_kernel(const uint8_t* __restrict__ img, int px, int C, int np, FsChannels ch,
-                                                             int32_t* __restrict__ mx) {
+__device__ __forceinline__ void fs_channel_max_body(const uint8_t* __restrict__ img, int px, int C, int np, const FsChannels& ch,
+                                                    int32_t* __restrict__ mx) {
     int m[3] = {0, 0, 0};
     for (unsigned p = blockIdx.x * 256u + threadIdx.x; p < (unsigned)px; p += gridDim.x * 256u) {
         const uint8_t* q = img + (size_t)p * C;
@@ -60,12 +64,17 @@ __global__ __launch_bounds__(256) void fs_channel_max_kernel(const uint8_t* __re
         if ((threadIdx.x & 63) == 0 && j < np && m[j] > 0) atomicMax(mx + j, m[j]);
     }
 }
+__global__ __launch_bounds__(256) void fs_channel_max_kernel(const uint8_t* __restrict__ img, int px, int C, int np, FsChannels ch,
+                                                             int32_t* __restrict__ mx) {
+    fs_channel_max_body(img, px, C, np, ch, mx);
+}
 
 // acc: per cell 12 uint64: area, sum of rows, sum of columns, then per probe sum / count / maximum of the non-zero raw pixels.
-// val[cell] = the cell's label value.  L is relabelled in place to cell + 1.
-__global__ __launch_bounds__(256) void fs_cell_stats_kernel(int32_t* __restrict__ L, const int32_t* __restrict__ rid,
-                                                            const uint8_t* __restrict__ img, int H, int W, int C, int np, FsChannels ch,
-                                                            u64* __restrict__ acc, int32_t* __restrict__ val) {
+// val[cell] = the cell's label value.  L is relabelled in place to cell + 1.  rid gives cell0 + cell (cell0: the cells of the images
+// in front, 0 for an image alone); acc and val are indexed by that sum.
+__device__ __forceinline__ void fs_cell_stats_body(int32_t* __restrict__ L, const int32_t* __restrict__ rid, const uint8_t* __restrict__ img,
+                                                   int H, int W, int C, int np, const FsChannels& ch, int cell0, u64* __restrict__ acc,
+                                                   int32_t* __restrict__ val) {
     const int lane = threadIdx.x & 63;
     const StatTile tile = stat_tile(W);
     for (int r = 0; r < CELL_ROWS_PER_WAVE; ++r) {
@@ -78,7 +87,7 @@ __global__ __launch_bounds__(256) void fs_cell_stats_kernel(int32_t* __restrict_
             l = L[p];
             if (l > 0) {
                 reg = rid[l - 1];
-                L[p] = reg + 1;
+                L[p] = reg - cell0 + 1;
                 const uint8_t* q = img + p * C;
 #pragma unroll
                 for (int j = 0; j < 3; ++j)
@@ -123,18 +132,26 @@ __global__ __launch_bounds__(256) void fs_cell_stats_kernel(int32_t* __restrict_
         });
     }
 }
+__global__ __launch_bounds__(256) void fs_cell_stats_kernel(int32_t* __restrict__ L, const int32_t* __restrict__ rid,
+                                                            const uint8_t* __restrict__ img, int H, int W, int C, int np, FsChannels ch,
+                                                            u64* __restrict__ acc, int32_t* __restrict__ val) {
+    fs_cell_stats_body(L, rid, img, H, W, C, np, ch, 0, acc, val);
+}
 
-// L: cell + 1 per pixel (0 background).  thr (H, W, np) uint8 0 / 255; par: np planes of H * W parents (pixel | -1).
-__global__ __launch_bounds__(256) void fs_threshold_kernel(const int32_t* __restrict__ L, const uint8_t* __restrict__ img, int H, int W, int C,
-                                                           int np, FsChannels ch, const double* __restrict__ wts, int K, double normal_thr,
-                                                           FsThresholds ithr, const int32_t* __restrict__ mx, uint8_t* __restrict__ thr,
-                                                           int32_t* __restrict__ par) {
+// L: cell + 1 per pixel (0 background).  thr (H, W, np) uint8 0 / 255; par: np planes of H * W parents (pixel | -1).  The LDS
+// (FS_KMAX * FS_KMAX weights and the FS_HALO_H x FS_HALO_W halo tile) is sized for the largest K, whatever this image's is.
+// A tile below the image (a chunk's grid is the largest image's) returns before the first barrier, the whole workgroup together.
+__device__ __forceinline__ void fs_threshold_body(const int32_t* __restrict__ L, const uint8_t* __restrict__ img, int H, int W, int C, int np,
+                                                  const FsChannels& ch, const double* __restrict__ wts, int K, double normal_thr,
+                                                  const FsThresholds& ithr, const int32_t* __restrict__ mx, uint8_t* __restrict__ thr,
+                                                  int32_t* __restrict__ par) {
     __shared__ double s_w[FS_KMAX * FS_KMAX];
     __shared__ uint8_t s_t[FS_HALO_H * FS_HALO_W];
     const int t = threadIdx.x, lx = t & 63, ly = t >> 6;
     const int r = K >> 1, hw = FS_TW + K - 1, hh = FS_TH + K - 1;
     const unsigned tiles_x = ((unsigned)W + FS_TW - 1) / FS_TW;
     const int x0 = (int)(blockIdx.x % tiles_x) * FS_TW, y0 = (int)(blockIdx.x / tiles_x) * FS_TH;
+    if (y0 >= H) return;
     for (int i = t; i < K * K; i += 256) s_w[i] = wts[i];
     const size_t px = (size_t)H * W;
     for (int j = 0; j < np; ++j) {
@@ -172,27 +189,36 @@ __global__ __launch_bounds__(256) void fs_threshold_kernel(const int32_t* __rest
         }
     }
 }
+__global__ __launch_bounds__(256) void fs_threshold_kernel(const int32_t* __restrict__ L, const uint8_t* __restrict__ img, int H, int W, int C,
+                                                           int np, FsChannels ch, const double* __restrict__ wts, int K, double normal_thr,
+                                                           FsThresholds ithr, const int32_t* __restrict__ mx, uint8_t* __restrict__ thr,
+                                                           int32_t* __restrict__ par) {
+    fs_threshold_body(L, img, H, W, C, np, ch, wts, K, normal_thr, ithr, mx, thr, par);
+}
 
-// slot blockIdx.y: unite every mask pixel with its W / N neighbour when that is a mask pixel of the same cell
-__global__ __launch_bounds__(256) void fs_unite_kernel(const int32_t* __restrict__ L, int H, int W, int32_t* par_all) {
+// one plane of parents: unite every mask pixel with its W / N neighbour when that is a mask pixel of the same cell
+__device__ __forceinline__ void fs_unite_body(const int32_t* __restrict__ L, int H, int W, int32_t* par) {
     const unsigned pu = blockIdx.x * 256u + threadIdx.x;    // H * W < 2^31: no wrap
     if (pu >= (unsigned)(H * W)) return;
     const int p = (int)pu;
-    int32_t* par = par_all + (size_t)blockIdx.y * ((size_t)H * W);
     if (uf_load(par, p) < 0) return;
     const int cell = L[p];
     const int y = p / W, x = p - y * W;
     uf_unite_back(par, p, y, x, W, 0, [&](int q) { return L[q] == cell; });
 }
+// slot blockIdx.y
+__global__ __launch_bounds__(256) void fs_unite_kernel(const int32_t* __restrict__ L, int H, int W, int32_t* par_all) {
+    fs_unite_body(L, H, W, par_all + (size_t)blockIdx.y * ((size_t)H * W));
+}
 
-// slot = slot0 + blockIdx.y.  Components below min_cc: cleared from thr when thr != null (probes), else just not counted (the pair).
+// One slot.  Components below min_cc: cleared from thr when thr != null (probes), else just not counted (the pair).
 // cnt: per cell FS_SLOTS x (pixels, components) uint32.
-__global__ __launch_bounds__(256) void fs_finalize_kernel(const int32_t* __restrict__ L, int px, int np, int slot0, int min_cc,
-                                                          const int32_t* __restrict__ par_all, const int32_t* __restrict__ sz_all,
-                                                          uint8_t* __restrict__ thr, unsigned* __restrict__ cnt) {
+__device__ __forceinline__ void fs_finalize_body(const int32_t* __restrict__ L, int px, int np, int slot, int min_cc,
+                                                 const int32_t* __restrict__ par_all, const int32_t* __restrict__ sz_all,
+                                                 uint8_t* __restrict__ thr, unsigned* __restrict__ cnt) {
     const unsigned pu = blockIdx.x * 256u + threadIdx.x;
     if (pu >= (unsigned)px) return;
-    const int p = (int)pu, slot = slot0 + (int)blockIdx.y;
+    const int p = (int)pu;
     const int32_t* par = par_all + (size_t)slot * (size_t)px;
     const int q = par[p];
     if (q < 0) return;
@@ -205,18 +231,27 @@ __global__ __launch_bounds__(256) void fs_finalize_kernel(const int32_t* __restr
     atomicAdd(c, 1u);
     if (root == p) atomicAdd(c + 1, 1u);
 }
+// slot = slot0 + blockIdx.y
+__global__ __launch_bounds__(256) void fs_finalize_kernel(const int32_t* __restrict__ L, int px, int np, int slot0, int min_cc,
+                                                          const int32_t* __restrict__ par_all, const int32_t* __restrict__ sz_all,
+                                                          uint8_t* __restrict__ thr, unsigned* __restrict__ cnt) {
+    fs_finalize_body(L, px, np, slot0 + (int)blockIdx.y, min_cc, par_all, sz_all, thr, cnt);
+}
 
 // parents of the pair slot: the pixel itself where the cleaned masks of probes 0 and 1 are both set
-__global__ __launch_bounds__(256) void fs_pair_init_kernel(const uint8_t* __restrict__ thr, int px, int np, int32_t* __restrict__ par) {
+__device__ __forceinline__ void fs_pair_init_body(const uint8_t* __restrict__ thr, int px, int np, int32_t* __restrict__ par) {
     const unsigned p = blockIdx.x * 256u + threadIdx.x;
     if (p >= (unsigned)px) return;
     const uint8_t* q = thr + (size_t)p * np;
     par[p] = (q[0] && q[1]) ? (int)p : -1;
 }
+__global__ __launch_bounds__(256) void fs_pair_init_kernel(const uint8_t* __restrict__ thr, int px, int np, int32_t* __restrict__ par) {
+    fs_pair_init_body(thr, px, np, par);
+}
 
 // b = 255 where sum L[y][x-t+1..x] != sum L[y][x+1..x+t] or the same along y (taps outside the image are 0): the "SAME" padding
 // of an even kernel, t - 1 before and t after.  Ranks are < 2^31 and t <= 16; the sums are 64-bit.
-__global__ __launch_bounds__(256) void fs_boundary_kernel(const int32_t* __restrict__ L, int H, int W, int t, uint8_t* __restrict__ out) {
+__device__ __forceinline__ void fs_boundary_body(const int32_t* __restrict__ L, int H, int W, int t, uint8_t* __restrict__ out) {
     const unsigned pu = blockIdx.x * 256u + threadIdx.x;
     if (pu >= (unsigned)(H * W)) return;
     const int p = (int)pu, y = p / W, x = p - y * W;
@@ -229,10 +264,13 @@ __global__ __launch_bounds__(256) void fs_boundary_kernel(const int32_t* __restr
     }
     out[p] = (h != 0 || v != 0) ? 255 : 0;
 }
+__global__ __launch_bounds__(256) void fs_boundary_kernel(const int32_t* __restrict__ L, int H, int W, int t, uint8_t* __restrict__ out) {
+    fs_boundary_body(L, H, W, t, out);
+}
 
 // rec (n, ECSEG_FISH_SPOT_INT64) int64: see ecseg_fish_spots
-__global__ __launch_bounds__(256) void fs_records_kernel(const u64* __restrict__ acc, const unsigned* __restrict__ cnt,
-                                                         const int32_t* __restrict__ val, int n, int np, int64_t* __restrict__ rec) {
+__device__ __forceinline__ void fs_records_body(const u64* __restrict__ acc, const unsigned* __restrict__ cnt, const int32_t* __restrict__ val,
+                                                int n, int np, int64_t* __restrict__ rec) {
     const unsigned cell = blockIdx.x * 256u + threadIdx.x;
     if (cell >= (unsigned)n) return;
     const u64* a = acc + (size_t)cell * 12;
@@ -251,6 +289,95 @@ __global__ __launch_bounds__(256) void fs_records_kernel(const u64* __restrict__
     o[19] = np >= 2 ? c[6] : 0;
     o[20] = np >= 2 ? c[7] : 0;
     o[21] = o[22] = o[23] = 0;
+}
+__global__ __launch_bounds__(256) void fs_records_kernel(const u64* __restrict__ acc, const unsigned* __restrict__ cnt,
+                                                         const int32_t* __restrict__ val, int n, int np, int64_t* __restrict__ rec) {
+    fs_records_body(acc, cnt, val, n, np, rec);
+}
+
+// ---- a chunk of images (ecseg_stat_fish_batch; layout in fish_batch.h) ---------------------------------------------------------
+// blockIdx.y = the image, blockIdx.x = a block of the largest image's grid: a block past its image's extent returns at once (every
+// body above begins with that test).  Where a stage runs per union-find slot, blockIdx.z is the slot.  Everything an image owns is
+// found through its row: pointers move, the values (parents, labels, ranks) stay indices inside the image.
+struct FsbView {
+    uint8_t* work; FsImage* tab; int32_t* lab; int32_t* rid; int32_t* par; int32_t* sz; int32_t* mx; const double* w;
+    u64* acc; unsigned* cnt; int32_t* val; int64_t* rec;
+};
+__device__ __forceinline__ FsChannels fsb_probes(const FsImage& t) { return FsChannels{{t.ch[1], t.ch[2], t.ch[3]}}; }
+
+// the labels of the padded planes into the packed label maps: 1 + the raster index of the first pixel, counted in the image's own
+// width as ecseg_ccl_labels counts it
+__global__ __launch_bounds__(256) void fsb_unpad_kernel(FsbView v, const int32_t* __restrict__ plab, int Wm) {
+    const FsImage& t = v.tab[blockIdx.y];
+    const unsigned p = blockIdx.x * 256u + threadIdx.x;
+    if (t.pad < 0 || p >= (unsigned)(t.H * t.W)) return;
+    const int y = (int)(p / (unsigned)t.W), x = (int)p - y * t.W;
+    int l = plab[(size_t)t.pad + (size_t)y * Wm + x];
+    if (l > 0) { const int r = l - 1, ry = r / Wm; l = 1 + ry * t.W + (r - ry * Wm); }
+    v.lab[(size_t)t.lab + p] = l;
+}
+// plan (n + 1, 2): [i][1] = 1 when image i holds a label above its pixel count
+__global__ __launch_bounds__(256) void fsb_mark_kernel(FsbView v, int32_t* __restrict__ plan) {
+    const FsImage& t = v.tab[blockIdx.y];
+    cell_mark_pixel(v.lab + t.lab, t.H * t.W, v.rid + t.lab, plan + 2 * (size_t)blockIdx.y + 1, blockIdx.x * 256u + threadIdx.x);
+}
+// After the scan over the whole rid: rid[row.lab] is the number of cells in front of image i, the next image's (or the total) ends it.
+__global__ __launch_bounds__(256) void fsb_plan_kernel(FsbView v, int n, const int32_t* __restrict__ total, int32_t* __restrict__ plan) {
+    const int i = (int)(blockIdx.x * 256u + threadIdx.x);
+    if (i > n) return;
+    if (i == n) { plan[2 * (size_t)n] = *total; plan[2 * (size_t)n + 1] = 0; return; }
+    const int base = v.rid[v.tab[i].lab], next = i + 1 < n ? v.rid[v.tab[i + 1].lab] : *total;
+    v.tab[i].rec0 = base; v.tab[i].n_cells = next - base;
+    plan[2 * (size_t)i] = next - base;
+}
+__global__ __launch_bounds__(256) void fsb_channel_max_kernel(FsbView v) {
+    const FsImage& t = v.tab[blockIdx.y];
+    fs_channel_max_body(v.work + t.img, t.H * t.W, t.C, t.np, fsb_probes(t), v.mx + 4 * (size_t)blockIdx.y);
+}
+__global__ __launch_bounds__(256) void fsb_cell_stats_kernel(FsbView v) {
+    const FsImage& t = v.tab[blockIdx.y];
+    fs_cell_stats_body(v.lab + t.lab, v.rid + t.lab, v.work + t.img, t.H, t.W, t.C, t.np, fsb_probes(t), t.rec0, v.acc, v.val);
+}
+__global__ __launch_bounds__(256) void fsb_threshold_kernel(FsbView v) {
+    const FsImage& t = v.tab[blockIdx.y];
+    fs_threshold_body(v.lab + t.lab, v.work + t.img, t.H, t.W, t.C, t.np, fsb_probes(t), v.w + t.w, t.K, t.normal_thr,
+                      FsThresholds{{t.ithr[0], t.ithr[1], t.ithr[2]}}, v.mx + 4 * (size_t)blockIdx.y, v.work + t.thr, v.par + 4 * t.lab);
+}
+// slot = slot0 + blockIdx.z while it is a probe of the image (slot0 = FS_SLOTS - 1: the pair, for images of two probes or more)
+__device__ __forceinline__ bool fsb_slot_live(const FsImage& t, int slot) { return slot == FS_SLOTS - 1 ? t.np >= 2 : slot < t.np; }
+__global__ __launch_bounds__(256) void fsb_unite_kernel(FsbView v, int slot0) {
+    const FsImage& t = v.tab[blockIdx.y];
+    const int slot = slot0 + (int)blockIdx.z;
+    if (!fsb_slot_live(t, slot)) return;
+    fs_unite_body(v.lab + t.lab, t.H, t.W, v.par + 4 * t.lab + (size_t)slot * ((size_t)t.H * t.W));
+}
+__global__ __launch_bounds__(256) void fsb_size_kernel(FsbView v, int slot0) {
+    const FsImage& t = v.tab[blockIdx.y];
+    const int slot = slot0 + (int)blockIdx.z, px = t.H * t.W;
+    if (!fsb_slot_live(t, slot)) return;
+    const size_t o = 4 * (size_t)t.lab + (size_t)slot * (size_t)px;
+    uf_size_pixel(px, v.par + o, v.sz + o, static_cast<int32_t*>(nullptr), blockIdx.x * 256u + threadIdx.x);
+}
+__global__ __launch_bounds__(256) void fsb_finalize_kernel(FsbView v, int slot0) {
+    const FsImage& t = v.tab[blockIdx.y];
+    const int slot = slot0 + (int)blockIdx.z;
+    if (!fsb_slot_live(t, slot)) return;
+    fs_finalize_body(v.lab + t.lab, t.H * t.W, t.np, slot, t.min_cc, v.par + 4 * t.lab, v.sz + 4 * t.lab,
+                     slot == FS_SLOTS - 1 ? static_cast<uint8_t*>(nullptr) : v.work + t.thr, v.cnt + (size_t)t.rec0 * FS_SLOTS * 2);
+}
+__global__ __launch_bounds__(256) void fsb_pair_init_kernel(FsbView v) {
+    const FsImage& t = v.tab[blockIdx.y];
+    if (t.np < 2) return;
+    fs_pair_init_body(v.work + t.thr, t.H * t.W, t.np, v.par + 4 * t.lab + (size_t)(FS_SLOTS - 1) * ((size_t)t.H * t.W));
+}
+__global__ __launch_bounds__(256) void fsb_boundary_kernel(FsbView v, int line_t) {
+    const FsImage& t = v.tab[blockIdx.y];
+    fs_boundary_body(v.lab + t.lab, t.H, t.W, line_t, v.work + t.bnd);
+}
+__global__ __launch_bounds__(256) void fsb_records_kernel(FsbView v) {
+    const FsImage& t = v.tab[blockIdx.y];
+    fs_records_body(v.acc + (size_t)t.rec0 * 12, v.cnt + (size_t)t.rec0 * FS_SLOTS * 2, v.val + t.rec0, t.n_cells, t.np,
+                    v.rec + (size_t)t.rec0 * ECSEG_FISH_SPOT_INT64);
 }
 
 // ---- ecseg_fish_render ---------------------------------------------------------------------------------------------------
@@ -384,6 +511,54 @@ hipError_t run_fishspot(int32_t* labels, const uint8_t* img, int H, int W, int C
     }
     hipLaunchKernelGGL(fs_boundary_kernel, dim3(gpx), dim3(256), 0, s, labels, H, W, line_t, b.bnd);
     hipLaunchKernelGGL(fs_records_kernel, dim3(((unsigned)n + 255u) / 256u), dim3(256), 0, s, b.acc, b.cnt, b.val, n, np, b.rec);
+    return hipGetLastError();
+}
+
+// The opening of a chunk, up to the plan: the masks labelled (padded, 8-connected) and brought into the packed label maps beside the
+// given ones, every label marked, one scan over the chunk, and per image its cells and its first record (b.plan, the rows).
+hipError_t run_fishspot_batch_open(const FsBatchLayout& L, const FsBatchBufs& b, PostWorkspace& ws, hipStream_t s) {
+    const unsigned n = (unsigned)L.tab.size(), gpx = ((unsigned)L.max_px + 255u) / 256u;
+    const FsbView v{b.work, b.tab, b.lab, b.rid, b.par, b.sz, b.mx, b.w, nullptr, nullptr, nullptr, nullptr};
+    hipError_t e;
+    if ((e = hipMemsetAsync(b.rid, 0, L.px * sizeof(int32_t), s)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(b.plan, 0, ((size_t)n + 1) * 2 * sizeof(int32_t), s)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(b.total, 0, 4 * sizeof(int32_t), s)) != hipSuccess) return e;
+    if (L.n_pad > 0) {
+        if ((e = run_pad_label_masks(b.work, b.ptab, L.n_pad, L.Hm, L.Wm, b.pmask, b.plab, ws, s)) != hipSuccess) return e;
+        hipLaunchKernelGGL(fsb_unpad_kernel, dim3(gpx, n), dim3(256), 0, s, v, b.plab, L.Wm);
+    }
+    hipLaunchKernelGGL(fsb_mark_kernel, dim3(gpx, n), dim3(256), 0, s, v, b.plan);
+    exclusive_scan(LoadStrided{b.rid, 1}, (int)L.px, b.blk, b.rid, b.total, s);
+    hipLaunchKernelGGL(fsb_plan_kernel, dim3(n / 256u + 1u), dim3(256), 0, s, v, (int)n, b.total, b.plan);
+    return hipGetLastError();
+}
+
+// The rest: what run_fishspot does for one image, one launch per stage for the chunk.  cells: the chunk's cells (> 0: c is laid out);
+// max_cells: the most of one image.
+hipError_t run_fishspot_batch(const FsBatchLayout& L, const FsBatchBufs& b, const FsBatchCellBufs& c, int cells, int max_cells, int line_t,
+                              hipStream_t s) {
+    const unsigned n = (unsigned)L.tab.size(), gpx = ((unsigned)L.max_px + 255u) / 256u;
+    const FsbView v{b.work, b.tab, b.lab, b.rid, b.par, b.sz, b.mx, b.w, c.acc, c.cnt, c.val, c.rec};
+    hipError_t e;
+    if ((e = hipMemsetAsync(b.mx, 0, (size_t)n * 4 * sizeof(int32_t), s)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(b.sz, 0, L.px * FS_SLOTS * sizeof(int32_t), s)) != hipSuccess) return e;
+    if (cells > 0) {
+        if ((e = hipMemsetAsync(c.acc, 0, (size_t)cells * 12 * sizeof(u64), s)) != hipSuccess) return e;
+        if ((e = hipMemsetAsync(c.cnt, 0, (size_t)cells * FS_SLOTS * 2 * sizeof(unsigned), s)) != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(fsb_channel_max_kernel, dim3(gpx < 2048u ? gpx : 2048u, n), dim3(256), 0, s, v);
+    hipLaunchKernelGGL(fsb_cell_stats_kernel, dim3(stat_tiles(L.max_H, L.max_W), n), dim3(256), 0, s, v);
+    const unsigned thr_tiles = (((unsigned)L.max_W + FS_TW - 1) / FS_TW) * (((unsigned)L.max_H + FS_TH - 1) / FS_TH);
+    hipLaunchKernelGGL(fsb_threshold_kernel, dim3(thr_tiles, n), dim3(256), 0, s, v);
+    hipLaunchKernelGGL(fsb_unite_kernel, dim3(gpx, n, FS_SLOTS - 1), dim3(256), 0, s, v, 0);
+    hipLaunchKernelGGL(fsb_size_kernel, dim3(gpx, n, FS_SLOTS - 1), dim3(256), 0, s, v, 0);
+    hipLaunchKernelGGL(fsb_finalize_kernel, dim3(gpx, n, FS_SLOTS - 1), dim3(256), 0, s, v, 0);
+    hipLaunchKernelGGL(fsb_pair_init_kernel, dim3(gpx, n), dim3(256), 0, s, v);
+    hipLaunchKernelGGL(fsb_unite_kernel, dim3(gpx, n, 1), dim3(256), 0, s, v, FS_SLOTS - 1);
+    hipLaunchKernelGGL(fsb_size_kernel, dim3(gpx, n, 1), dim3(256), 0, s, v, FS_SLOTS - 1);
+    hipLaunchKernelGGL(fsb_finalize_kernel, dim3(gpx, n, 1), dim3(256), 0, s, v, FS_SLOTS - 1);
+    hipLaunchKernelGGL(fsb_boundary_kernel, dim3(gpx, n), dim3(256), 0, s, v, line_t);
+    if (max_cells > 0) hipLaunchKernelGGL(fsb_records_kernel, dim3(((unsigned)max_cells + 255u) / 256u, n), dim3(256), 0, s, v);
     return hipGetLastError();
 }
 

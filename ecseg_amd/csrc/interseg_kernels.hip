@@ -282,6 +282,13 @@ hipError_t run_nucleus_crops(const int32_t* labels, const uint8_t* img, int W, i
     return hipGetLastError();
 }
 
+hipError_t run_pad_label_masks(const uint8_t* packed, const IsegImage* tab, int n, int Hm, int Wm, uint8_t* mask, int32_t* lab, PostWorkspace& ws,
+                               hipStream_t s) {
+    const unsigned pad_x = (unsigned)std::min<size_t>(((size_t)Hm * Wm + 255) / 256, 4096);
+    hipLaunchKernelGGL(iseg_pad_masks_kernel, dim3(pad_x, (unsigned)n), dim3(256), 0, s, packed, tab, Hm, Wm, mask);
+    return run_ccl_labels(ws, mask, n, Hm, Wm, 8, lab, s);
+}
+
 hipError_t run_iseg_batch_regions(int n, int Hm, int Wm, int ch0, const IsegBatchBufs& b, PostWorkspace& ws, hipStream_t s) {
     const int px = Hm * Wm;                                  // n * px < 2^31 (iseg_batch_groups)
     hipError_t e;
@@ -289,9 +296,7 @@ hipError_t run_iseg_batch_regions(int n, int Hm, int Wm, int ch0, const IsegBatc
     if ((e = hipMemsetAsync(b.imisc, 0, (size_t)n * 4 * sizeof(int32_t), s)) != hipSuccess) return e;
     if (b.cap > 0 && (e = hipMemsetAsync(b.acc, 0, (size_t)b.cap * 4 * sizeof(u64), s)) != hipSuccess) return e;
     if (b.cap > 0 && (e = hipMemsetAsync(b.bb, 0x7f, (size_t)b.cap * 4 * sizeof(int32_t), s)) != hipSuccess) return e;
-    const unsigned pad_x = (unsigned)std::min<size_t>(((size_t)px + 255) / 256, 4096);
-    hipLaunchKernelGGL(iseg_pad_masks_kernel, dim3(pad_x, (unsigned)n), dim3(256), 0, s, b.packed, b.tab, Hm, Wm, b.mask);
-    if ((e = run_ccl_labels(ws, b.mask, n, Hm, Wm, 8, b.lab, s)) != hipSuccess) return e;
+    if ((e = run_pad_label_masks(b.packed, b.tab, n, Hm, Wm, b.mask, b.lab, ws, s)) != hipSuccess) return e;
     exclusive_scan(LoadRootFlagBatch{b.lab, (unsigned)px}, n * px, b.blk, b.rid, b.misc, s);
     hipLaunchKernelGGL(iseg_batch_plan_kernel, dim3(1), dim3(64), 0, s, b.rid, b.misc, n, px, b.cap, b.plan);
     hipLaunchKernelGGL(iseg_region_stats_batch_kernel, dim3(stat_tiles(Hm, Wm), (unsigned)n), dim3(256), 0, s, b.lab, b.rid, b.mask, b.packed,

@@ -393,6 +393,64 @@ def process_image(path, mask_path, out_root, params, scale, handle, stats=None, 
     return rows_from_records(img_name, rec, len(probes)), scale
 
 
+def prepare_image(path, mask_path, out_root, params, scale, handle, stats=None, use_min_cut=False, segment=None, tiff_read_on_device=False,
+                  pre_read=None, tiff_read_deflate=False):
+    """The front half of ``process_image`` for ``stat_fish.batch`` above 1 -> (the image's share of a chunk, the scale that was used):
+    the image and its mask are read (or segmented), the min-cut splitter runs when it is on, and the image's own parameters are worked
+    out - with ``scale: auto`` from the areas of a regions-only ``fish_spots`` call, as ``process_image`` does.  Nothing is labelled,
+    measured, rendered or written here: ``main`` hands the ``item`` of k images to one ``handle.stat_fish_many`` call.  Arguments and
+    failures (``ImageError``) are ``process_image``'s.  A pending image holds its image, its mask (or label map) and the optional
+    min-cut picture until its chunk runs: 3 + 1 bytes per pixel, 5.8 MB at 1040 x 1392 x 3 (4 more bytes per pixel with
+    ``use_min_cut``, whose label map is int32, and 3 more for its picture)."""
+    import time
+    t0 = time.perf_counter()
+    img_name = os.path.basename(path)[:-4]
+    pre_image, pre_mask = pre_read if pre_read is not None else (None, None)
+    I, channels = read_image(path, handle, len(params['color_sensitivity']), tiff_read_on_device, pre_image, tiff_read_deflate)
+    mask = read_mask(mask_path, handle if tiff_read_on_device else None, pre_mask, tiff_read_deflate) if segment is None else segment(I[:, :, channels[0]])
+    imheight, imwidth = mask.shape
+    I = np.ascontiguousarray(I[:imheight, :imwidth])
+    mask = np.ascontiguousarray(mask[:I.shape[0], :I.shape[1]])
+    if mask.size == 0:
+        raise ImageError('is empty')
+    t1 = time.perf_counter()
+    probes = list(channels[1:])
+    labels = visualization = None
+    off = ([[0.0]], float('inf'), [float('inf')] * len(probes), 1)
+    try:
+        if use_min_cut:
+            from .min_cut import binary_seg_to_instance_min_cut
+            labels, visualization = binary_seg_to_instance_min_cut(mask, params['flow_limit'], params['cell_size_threshold_coeff'], handle=handle)
+        if scale == 'auto':                                  # the areas come first: the weights depend on them
+            rec, _, _ = handle.fish_spots(labels if use_min_cut else handle.ccl_labels(mask, 8), I, probes, off[0], off[1], off[2], off[3],
+                                          params['line_thickness'])
+            scale = get_scale(rec[:, 1], params['target_median_nuclei_size'])
+    except Exception as e:
+        if getattr(e, 'code', None) == -1:
+            raise ImageError(str(e))
+        raise
+    stdev, min_cc, shape = derived_parameters(scale, params)
+    if isinstance(stdev, float) and math.isnan(stdev):
+        weights, normal, ithr, min_cc_used = off
+    else:
+        if shape[0] != shape[1] or shape[0] > MAX_KERNEL or shape[0] < 1:
+            raise ImageError('needs a %s Gaussian kernel: the device takes square kernels up to %d x %d' % (shape, MAX_KERNEL, MAX_KERNEL))
+        weights, normal, ithr, min_cc_used = gaussian_proj_kernel(shape, stdev), params['normal_threshold'], params['color_sensitivity'][:len(probes)], min_cc
+    item = dict(img=I, channels=channels, weights=weights, normal_threshold=normal, intensity_thresholds=ithr, min_cc_size=min_cc_used)
+    if use_min_cut:
+        item.update(labels=labels, mask_file=mask)
+        if visualization is not None:
+            item['picture'] = np.ascontiguousarray(visualization[..., ::-1])
+    else:
+        item.update(mask=mask, mask_file=True)
+    names = [img_name + '_original.tif', img_name + '_original_with_segmentation.tif', lsq_name(img_name, params, stdev, min_cc),
+             img_name + '_segmentation.tif', img_name + '_segmentation_corrected_min_cut.tif']
+    if stats is not None:
+        for key, v in (('read', t1 - t0), ('device', time.perf_counter() - t1)):
+            stats[key] = stats.get(key, 0.0) + v
+    return dict(path=path, name=img_name, folder=os.path.join(out_root, img_name), names=names, item=item, probes=len(probes)), scale
+
+
 def load_params():
     """DEFAULT_PARAMS overridden by a src/stat_fish_params.yaml in the working directory -> (params, path of that file or None)."""
     import yaml
@@ -520,7 +578,12 @@ def main(argv=None, handle=None):
     ``handle.fish_render_tiff_many`` call - ``process_image`` hands its TIFF work back (its docstring says what an image holds until
     then) and the files are written every k such images and at the end.  The files, their names, the CSV and the messages are those of
     k = 1.  An image's CSV rows are added once its files are on disk; where such a call or a write fails, every image of that chunk is
-    reported as not processed (exit code 1, no rows), the other chunks are unaffected, and an image that failed earlier is in no chunk."""
+    reported as not processed (exit code 1, no rows), the other chunks are unaffected, and an image that failed earlier is in no chunk.
+
+    ``batch: k`` (with ``tiff_on_device: true``; default 1; above 1 ``tiff_write_batch`` is ignored): the images are read and prepared
+    one by one (``prepare_image``) and k of them are labelled, measured, rendered and encoded by one ``handle.stat_fish_many`` call,
+    which returns the dense ranks (the ``.npy``), the records and the file images.  Files, names, CSV, messages and exit code are those
+    of k = 1; a chunk whose call fails reports each of its images, by the rule above."""
     import yaml
     from . import csvio
     from .utils import get_imgs
@@ -582,6 +645,17 @@ def main(argv=None, handle=None):
                               'device TIFF encoder; 1: one by one)')
         if not tiff_on_device:
             write_batch = 1                                  # the key belongs to the device encoder
+        fish_batch = var.get('batch', 1)
+        if isinstance(fish_batch, bool) or not isinstance(fish_batch, int) or fish_batch < 1:
+            raise ConfigError('batch must be a positive integer (how many images are labelled, measured, rendered and encoded in one device '
+                              'call; 1: one by one)')
+        if not tiff_on_device:
+            fish_batch = 1                                   # the key belongs to the device encoder: the chunk's files are encoded in its call
+        if fish_batch > 1:
+            write_batch = 1                                  # ... and there is nothing left for tiff_write_batch to batch
+            if handle is not None and not hasattr(handle, 'stat_fish_many'):
+                raise ConfigError('batch: %d needs the batched stat_fish call (stat_fish_many), which the handle in use does not have; only '
+                                  'batch: 1 works on it' % fish_batch)
         if write_batch > 1 and handle is not None and not all(hasattr(handle, m) for m in ('tiff_encode_many', 'fish_render_tiff_many')):
             raise ConfigError('tiff_write_batch: %d needs the batched device TIFF encoder (tiff_encode_many, fish_render_tiff_many), which the '
                               'handle in use does not have; only tiff_write_batch: 1 works on it' % write_batch)
@@ -662,6 +736,48 @@ def main(argv=None, handle=None):
             rows.extend(w['rows'])
             seen['nuclei'] = seen.get('nuclei', 0) + w['nuclei']
             seen['probes'] = max(seen.get('probes', len(PROBE_NAMES)), w['probes'])
+    held = []                                                # stat_fish.batch: the images prepared for the next stat_fish_many call
+
+    def run_chunk():                                         # one device call for the held images, then their files and rows; a failed call is every such image's
+        if not held:
+            return
+        import time
+        from . import image_io
+        t0 = time.perf_counter()
+        chunk = list(held)
+        del held[:]
+        try:
+            results = handle.stat_fish_many([w['item'] for w in chunk], params['line_thickness'])
+            t1 = time.perf_counter()
+            seen['device'] = seen.get('device', 0.0) + t1 - t0
+            for w, res in zip(chunk, results):
+                if isinstance(res, Exception):               # the binding refused this image alone
+                    print(w['path'], '-', res)
+                    failed.append((w['path'], str(res)))
+                    continue
+                ranks, rec, files = res
+                os.makedirs(w['folder'], exist_ok=True)
+                image_io.write_npy_int64(os.path.join(w['folder'], w['name'] + '__segmentation_min_cut.npy'), ranks)
+                for name, data in zip(w['names'], files):
+                    if data is not None:
+                        image_io.write_file_image(os.path.join(w['folder'], name), data)
+                w['rows'], w['nuclei'] = rows_from_records(w['name'], rec, w['probes']), len(rec)
+            seen['write'] = seen.get('write', 0.0) + time.perf_counter() - t1
+        except Exception as e:
+            if getattr(e, 'code', None) != -1 and not isinstance(e, OSError):
+                raise
+            for w in chunk:
+                if 'rows' in w:
+                    del w['rows']
+                if not any(w['path'] == f[0] for f in failed):
+                    print(w['path'], '-', 'its chunk could not be processed (%s)' % e)
+                    failed.append((w['path'], 'its chunk could not be processed (%s)' % e))
+            return
+        for w in chunk:
+            if 'rows' in w:
+                rows.extend(w['rows'])
+                seen['nuclei'] = seen.get('nuclei', 0) + w['nuclei']
+                seen['probes'] = max(seen.get('probes', len(PROBE_NAMES)), w['probes'])
     try:
         for at in range(0, len(image_paths), batch):
             chunk = image_paths[at:at + batch]
@@ -686,6 +802,14 @@ def main(argv=None, handle=None):
                 try:
                     if p not in ahead:
                         read_ahead(k)
+                    if fish_batch > 1:
+                        work, scale = prepare_image(p, mask_of(p), out_root, params, scale, handle, stats=seen, use_min_cut=use_min_cut,
+                                                    segment=hooks.get(p), tiff_read_on_device=tiff_read_on_device, pre_read=ahead.pop(p, None),
+                                                    tiff_read_deflate=read_deflate)
+                        held.append(work)
+                        if len(held) >= fish_batch:
+                            run_chunk()
+                        continue
                     img_rows, scale = process_image(p, mask_of(p), out_root, params, scale, handle,
                                                      stats=seen, use_min_cut=use_min_cut, segment=hooks.get(p), tiff_on_device=tiff_on_device,
                                                      tiff_read_on_device=tiff_read_on_device, pre_read=ahead.pop(p, None), pending=pending,
@@ -697,6 +821,7 @@ def main(argv=None, handle=None):
                 if pending is not None and len(pending) >= write_batch:
                     flush()
         flush()
+        run_chunk()
     finally:
         if own:
             handle.close()

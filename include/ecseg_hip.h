@@ -75,6 +75,8 @@ extern "C" {
 /* (still 5 - additive: ecseg_stitch_stages_debug, ecseg_preprocess_stages_debug and ecseg_otsu_debug, the stitch with its tie-risk count
  * over a whole batch in one launch, meta_preprocess with its histograms and thresholds, and Otsu alone on given histograms, for the
  * tests of csrc/stitch_preprocess_kernels.hip; nothing existing changed.) */
+/* (still 5 - additive: ecseg_stat_fish_batch and ecseg_stat_fish_batch_bytes, the labelling, spot statistics, colour files and TIFF
+ * encode of many stat_fish images in one call; nothing existing changed.) */
 #define ECSEG_ABI_VERSION 5
 
 #define ECSEG_OK             0
@@ -567,6 +569,42 @@ int ecseg_fish_render_tiff_batch(ecseg_ctx* h, int n_images, const uint8_t* cons
                                  const int32_t* channels /* [n][4] */, const uint8_t* const* thresholded, const uint8_t* const* boundaries,
                                  const uint8_t* const* masks, const uint8_t* const* pictures, uint8_t* out, long long out_cap,
                                  int64_t* out_ranges /* [n][5][2] offset, n_bytes */);
+
+/* stat_fish from the nucleus mask to the file images for n_images images in ONE call (config key stat_fish.batch): per image what
+ * ecseg_ccl_labels(mask, 8) -> ecseg_fish_spots -> ecseg_fish_render_tiff_batch give, with every raster uploaded once and nothing
+ * brought back that the caller does not write to disk.  imgs[i] (H, W, C) uint8, C = 3 or 4, shapes and channels as
+ * ecseg_fish_render_tiff_batch takes them; the probes of image i are channels[i][1 .. C - 1] (green, red[, aqua]).  Exactly one of
+ * masks[i] ((H, W) uint8, non-zero = nucleus, labelled 8-connected on the device) and labels[i] ((H, W) int32, used as given: <= 0
+ * background, cells need not be connected, no label above H * W) is non-null.  Per image its own ecseg_fish_spots parameters:
+ * kernel_sizes[i] = K, weights[i] (K x K float64), normal_thresholds[i], intensity_thresholds[3 i .. 3 i + 2] (the first C - 1 are
+ * read), min_cc_sizes[i]; line_thickness is one for the call.  mask_files / pictures (either may be NULL, and so may any entry): the
+ * (H, W) raster of _segmentation.tif and the (H, W, 3) min-cut picture, encoded beside the three rendered files; where mask_files[i]
+ * is the pointer masks[i] the mask is uploaded once.
+ *   ranks: int32, the images' (H, W) maps back to back: 0 background, else 1 + the cell's index in ascending label order (what
+ * ecseg_fish_spots' records[.][0] numbers).  records: ECSEG_FISH_SPOT_INT64 int64 per cell as ecseg_fish_spots writes them, the images
+ * back to back; n_cells[i]: the cells of image i.  out, out_cap, out_ranges: as ecseg_fish_render_tiff_batch returns them.
+ * thresholded_debug / boundaries_debug (tests; may be NULL): ecseg_fish_spots' thresholded ((H, W, C - 1)) and boundaries ((H, W)) of
+ * the images back to back - otherwise they never leave the device.
+ *   record_capacity: room of `records` in cells, for the whole chunk.  When the chunk holds more, the call returns ECSEG_OK with every
+ * n_cells[i] set and nothing else written (ecseg_fish_spots' rule): come back with a larger buffer.  out_cap too small is
+ * ECSEG_E_INVALID with no output but n_cells written.  An image without a nucleus has zero ranks, no record and files rendered from
+ * all-zero masks.  ECSEG_E_INVALID: what the single calls refuse, the message naming the image ("image i: ..."); more than
+ * ECSEG_STAT_FISH_BATCH_MAX_IMAGES images; a chunk of 2^31 pixels or more (also counted with every mask padded to the largest one).
+ * n_images == 0 is ECSEG_OK and does nothing.  No result depends on the order of the atomics: two calls give identical bytes.  One
+ * synchronous call; scratch from the handle's call arena and, for what the cell count sizes, its count arena
+ * (ecseg_stat_fish_batch_bytes says how much); device time of all kernels in ECSEG_T_COUNT. */
+#define ECSEG_STAT_FISH_BATCH_MAX_IMAGES 8192
+int ecseg_stat_fish_batch(ecseg_ctx* h, int n_images, const uint8_t* const* imgs, const int32_t* shapes /* [n][3] H, W, C */,
+                          const int32_t* channels /* [n][4] */, const uint8_t* const* masks, const int32_t* const* labels,
+                          const int32_t* kernel_sizes, const double* const* weights, const double* normal_thresholds,
+                          const double* intensity_thresholds /* [n][3] */, const int32_t* min_cc_sizes, int line_thickness,
+                          const uint8_t* const* mask_files, const uint8_t* const* pictures, int record_capacity, int32_t* ranks,
+                          int64_t* records, int32_t* n_cells, uint8_t* out, long long out_cap, int64_t* out_ranges /* [n][5][2] */,
+                          uint8_t* thresholded_debug, uint8_t* boundaries_debug);
+/* Bytes of device scratch such a call needs (both arenas), or -1 for a chunk it refuses.  flags[i]: bit 0 the image comes with given
+ * labels (else a mask), bit 1 it has a mask file, bit 2 that file is the mask itself, bit 3 it has a picture.  No device work. */
+long long ecseg_stat_fish_batch_bytes(int n_images, const int32_t* shapes, const int32_t* kernel_sizes, const int32_t* flags,
+                                      int record_capacity);
 
 /* ---- TIFF files decoded on the device ---------------------------------------------------------------------------------------- */
 /* skimage.io.imread of a baseline TIFF (src/utils.py:110) from a file image in memory, with every strip decoded on the device

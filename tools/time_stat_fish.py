@@ -1,7 +1,7 @@
 """Timing of ``make stat_fish`` on synthetic full-size scenes.
 
     python tools/time_stat_fish.py [--images 16] [--reps 5] [--cpu-workers 16] [--channels 4] [--main-passes 3]
-                                   [--tiff-on-device off|on|alternate] [--tiff-read-on-device off|on|alternate] [--tiff-read-batch K] [--tiff-write-batch K] [--no-cpu-baseline]
+                                   [--tiff-on-device off|on|alternate] [--tiff-read-on-device off|on|alternate] [--tiff-read-batch K] [--tiff-write-batch K] [--batch K] [--no-cpu-baseline]
 
 Per 1040 x 1392 scene with 300 nuclei (tests/stat_fish_cases.py ``full_size_scene``) it reports
   * device milliseconds per image of ecseg_fish_spots (ECSEG_T_COUNT: the kernels alone), of the nucleus labelling in front of
@@ -18,6 +18,9 @@ Per 1040 x 1392 scene with 300 nuclei (tests/stat_fish_cases.py ``full_size_scen
     stage of ``process_image`` per image is reported beside the write stage;
   * with ``--tiff-read-batch K`` (K above 1) ``tiff_read_on_device: true`` holds throughout and ``tiff_read_batch`` 1 and K alternate,
     twice (``main_by_read_batch``); the read stage then includes the chunks that ``main()`` reads ahead;
+  * with ``--batch K`` (K above 1) ``tiff_on_device: true`` holds throughout - and the read keys as given - and ``stat_fish.batch`` 1 and K
+    alternate, twice (``main_by_batch``): images/s, the read / device / write stage per image and ``encode_kernel_ms_per_image``, which
+    then is ECSEG_T_COUNT of every encoding or chunk call (``stat_fish_many`` holds labelling, spots, render and encode) per image;
   * with ``--tiff-write-batch K`` (K above 1) ``tiff_on_device: true`` holds throughout - and the read keys as given, ``--tiff-read-batch``
     as a fixed value - and ``tiff_write_batch`` 1 and K alternate, twice (``main_by_write_batch``); the write stage then includes the
     chunks that ``main()`` writes, and ``encode_kernel_ms_per_image`` is ECSEG_T_COUNT of the encoding calls (``fish_render_tiff`` and
@@ -64,6 +67,7 @@ def main():
     ap.add_argument('--tiff-read-on-device', choices=('off', 'on', 'alternate'), default='off')
     ap.add_argument('--tiff-read-batch', type=int, default=1, help='with --tiff-read-on-device on: tiff_read_batch 1 and this value alternate, twice')
     ap.add_argument('--tiff-write-batch', type=int, default=1, help='with tiff_on_device on: tiff_write_batch 1 and this value alternate, twice')
+    ap.add_argument('--batch', type=int, default=1, help='with tiff_on_device on: stat_fish.batch 1 and this value alternate, twice')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     a = ap.parse_args()
     import yaml
@@ -141,15 +145,21 @@ def main():
             seen['stats'] = kw['stats']
             return process_image(*args, **kw)
 
+        prepare_image = stat_fish.prepare_image
+
+        def spy_prepare(*args, **kw):
+            seen['stats'] = kw['stats']
+            return prepare_image(*args, **kw)
+
         encode_ms = []
-        for name in ('fish_render_tiff', 'tiff_encode', 'fish_render_tiff_many'):     # ECSEG_T_COUNT of every encoding call of main()
+        for name in ('fish_render_tiff', 'tiff_encode', 'fish_render_tiff_many', 'stat_fish_many'):     # ECSEG_T_COUNT of every encoding call of main()
             def timed(*args, _call=getattr(gpu, name), **kw):
                 r = _call(*args, **kw)
                 encode_ms.append(gpu.timings()['count'])
                 return r
             setattr(gpu, name, timed)
 
-        def passes(key, read_key=False, read_batch=1, write_batch=1):
+        def passes(key, read_key=False, read_batch=1, write_batch=1, fish_batch=1):
             """One warm-up pass (arenas, page cache) and --main-passes timed ones -> images/s of each, write stage ms per image."""
             cfg = {'stat_fish': {'inpath': inp, 'scale': 1, 'use_min_cut': False, 'nuclei_size_T': 5000}}
             if key:
@@ -160,9 +170,11 @@ def main():
                 cfg['stat_fish']['tiff_read_batch'] = read_batch
             if write_batch > 1:
                 cfg['stat_fish']['tiff_write_batch'] = write_batch
+            if fish_batch > 1:
+                cfg['stat_fish']['batch'] = fish_batch
             with open(os.path.join(tmp, 'config.yaml'), 'w') as f:
                 yaml.safe_dump(cfg, f)
-            rates, writes, stage_reads, encodes = [], [], [], []
+            rates, writes, stage_reads, encodes, devices = [], [], [], [], []
             for rep in range(a.main_passes + 1):
                 t0 = time.perf_counter()
                 del encode_ms[:]
@@ -172,18 +184,31 @@ def main():
                     writes.append(seen['stats']['write'] * 1e3 / a.images)
                     stage_reads.append(seen['stats']['read'] * 1e3 / a.images)
                     encodes.append(sum(encode_ms) / a.images)
+                    devices.append(seen['stats'].get('device', 0.0) * 1e3 / a.images)
                 seen.clear()
-            return rates, writes, stage_reads, encodes
+            return rates, writes, stage_reads, encodes, devices
 
-        def summary(rates, writes, stage_reads, encodes):
+        def summary(rates, writes, stage_reads, encodes, devices):
             return dict(main_images_per_s=statistics.median(rates), main_images_per_s_min=min(rates), main_images_per_s_max=max(rates),
                         write_stage_ms_per_image=statistics.median(writes), read_stage_ms_per_image=statistics.median(stage_reads),
-                        encode_kernel_ms_per_image=statistics.median(encodes))
+                        encode_kernel_ms_per_image=statistics.median(encodes), encode_kernel_ms_per_image_min=min(encodes),
+                        encode_kernel_ms_per_image_max=max(encodes), device_stage_ms_per_image=statistics.median(devices))
         cwd = os.getcwd()
         os.chdir(tmp)
         stat_fish.process_image = spy
+        stat_fish.prepare_image = spy_prepare
         try:
-            if a.tiff_write_batch > 1:                            # tiff_on_device on throughout, tiff_write_batch 1 and K alternating, twice
+            if a.batch > 1:                                       # tiff_on_device on throughout, stat_fish.batch 1 and K alternating, twice
+                r_on = a.tiff_read_on_device == 'on'
+                rb = a.tiff_read_batch if r_on else 1
+                out['main_by_batch'] = [dict(tiff_on_device=True, tiff_read_on_device=r_on, tiff_read_batch=rb, batch=k, **summary(*passes(True, r_on, rb, 1, k)))
+                                        for k in (1, a.batch, 1, a.batch)]
+                ones = [r for r in out['main_by_batch'] if r['batch'] == 1]
+                many = [r for r in out['main_by_batch'] if r['batch'] > 1]
+                out['max_1_below_min_k'] = max(r['main_images_per_s_max'] for r in ones) < min(r['main_images_per_s_min'] for r in many)
+                out['max_k_below_min_1'] = max(r['main_images_per_s_max'] for r in many) < min(r['main_images_per_s_min'] for r in ones)
+                out.update(ones[0])
+            elif a.tiff_write_batch > 1:                            # tiff_on_device on throughout, tiff_write_batch 1 and K alternating, twice
                 r_on = a.tiff_read_on_device == 'on'
                 out['main_by_write_batch'] = [dict(tiff_on_device=True, tiff_read_on_device=r_on, tiff_read_batch=a.tiff_read_batch if r_on else 1,
                                                    tiff_write_batch=k, **summary(*passes(True, r_on, a.tiff_read_batch if r_on else 1, k)))
@@ -220,6 +245,7 @@ def main():
                            **summary(*passes(a.tiff_on_device == 'on', a.tiff_read_on_device == 'on')))
         finally:
             stat_fish.process_image = process_image
+            stat_fish.prepare_image = prepare_image
             os.chdir(cwd)
     gpu.close()
     if a.no_cpu_baseline:
