@@ -102,5 +102,15 @@ asan_fish_batch:
 	    tools/asan/fish_batch_check.cpp -o $(FISH_BATCH_CHECK)
 	$(FISH_BATCH_CHECK)
 
+# and for ecseg_min_cut_regions: the layout header (csrc/mincut_regions.h) - selection, windows, centre records, capacities and the
+# arena - over seeded label lists, zero regions and capacities one short; tests/test_min_cut_regions.py builds and runs it.
+# MIN_CUT_REGIONS_CHECK: where the program is put
+MIN_CUT_REGIONS_CHECK ?= /tmp/ecseg_min_cut_regions_check
+.PHONY: asan_min_cut_regions
+asan_min_cut_regions:
+	g++ -std=c++17 -O1 -g -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=all \
+	    tools/asan/min_cut_regions_check.cpp -o $(MIN_CUT_REGIONS_CHECK)
+	$(MIN_CUT_REGIONS_CHECK)
+
 clean:
 	rm -rf __pycache__ ecseg_amd/csrc/*.o ecseg_amd/libecseg_*.so

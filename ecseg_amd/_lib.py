@@ -35,6 +35,7 @@ EXPORTS = [
     'ecseg_interseg_batch',
     'ecseg_stitch_stages_debug', 'ecseg_preprocess_stages_debug', 'ecseg_otsu_debug',
     'ecseg_stat_fish_batch', 'ecseg_stat_fish_batch_bytes',
+    'ecseg_min_cut_regions',
 ]
 
 
@@ -175,6 +176,7 @@ def load_library():
     lib.ecseg_tiff_decode_batch_counts_ex.argtypes = [vp, C.c_longlong, i32]
     lib.ecseg_tiff_decode_batch_bytes_ex.argtypes = [vp, C.c_longlong, vp, i32, i32]; lib.ecseg_tiff_decode_batch_bytes_ex.restype = C.c_longlong
     lib.ecseg_min_cut.argtypes = [vp, vp, C.c_longlong, vp, i32, i32, vp, vp]
+    lib.ecseg_min_cut_regions.argtypes = [vp, vp, i32, i32, C.c_double, i32, i32, i32, C.c_longlong, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.ecseg_nuset_forward.argtypes = [vp, vp, i32, i32, i32, i32, vp]
     lib.ecseg_rpn_proposals.argtypes = [vp, vp, vp, i32, i32, i32, vp, i32, i32, i32, C.c_float, i32, i32, C.POINTER(C.c_int32), vp, vp, vp]
     lib.ecseg_rpn_proposals_last.argtypes = [vp, i32, vp, i32, i32, i32, C.c_float, i32, i32, C.POINTER(C.c_int32), vp, vp, vp]
@@ -1479,6 +1481,43 @@ class Handle:
         self._check(self.lib.ecseg_min_cut(self.h, _ptr(packed), packed.size, _ptr(desc), len(wins), int(dist), _ptr(side), _ptr(flow)),
                     'ecseg_min_cut')
         return [side[offs[k]:offs[k + 1]].reshape(w.shape) for k, w in enumerate(wins)], flow
+
+    def min_cut_regions_raw(self, mask, coeff, min_rad, region_capacity, center_capacity, window_capacity):
+        """One ecseg_min_cut_regions call with the given capacities -> (labels, (n_cells, n_regions, n_centers, window_pixels),
+        regions, centers, windows, comp): the four buffers as allocated, preset to -1 / 255, untouched when a capacity is short."""
+        m = _u8(mask)
+        if m.ndim != 2:
+            raise ValueError('min_cut_regions takes a 2-D mask')
+        H, W = m.shape
+        labels = np.empty((H, W), np.int32)
+        regions = np.full((int(region_capacity), 8), -1, np.int32)
+        centers = np.full((int(center_capacity), 8), -1, np.int32)
+        windows = np.full(int(window_capacity), 255, np.uint8)
+        comp = np.full(int(window_capacity), -1, np.int32)
+        counts = np.zeros(3, np.int32)
+        wpx = C.c_longlong(0)
+        self._check(self.lib.ecseg_min_cut_regions(self.h, _ptr(m), H, W, float(coeff), int(min_rad), regions.shape[0], centers.shape[0],
+                                                   windows.size, _ptr(labels), _ptr(counts[0:]), _ptr(regions), _ptr(counts[1:]), _ptr(centers),
+                                                   _ptr(counts[2:]), _ptr(windows), _ptr(comp), C.byref(wpx)), 'ecseg_min_cut_regions')
+        return labels, (int(counts[0]), int(counts[1]), int(counts[2]), int(wpx.value)), regions, centers, windows, comp
+
+    def min_cut_regions(self, mask, coeff, min_rad=10):
+        """What binary_seg_to_instance_min_cut needs before its first max-flow, in one device call (ecseg_min_cut_regions; the records
+        are in include/ecseg_hip.h) -> (labels (H, W) int32, regions (n, 8) int32, centers (m, 8) int32, windows, comp): ``windows``
+        and ``comp`` hold one (h, w) array per region.  The capacities are guessed and grown by one repeat call."""
+        m = _u8(mask)
+        caps = getattr(self, '_mcr_caps', (64, 256, 1 << 18))
+        got = self.min_cut_regions_raw(m, coeff, min_rad, *caps)
+        _, n_reg, n_cen, wpx = got[1]
+        if n_reg > caps[0] or n_cen > caps[1] or wpx > caps[2]:
+            caps = (max(caps[0], n_reg), max(caps[1], n_cen), max(caps[2], wpx))
+            got = self.min_cut_regions_raw(m, coeff, min_rad, *caps)
+        self._mcr_caps = caps                                # the next image of a folder is alike: one call then
+        labels, _, regions, centers, windows, comp = got
+        regions, centers = regions[:n_reg], centers[:n_cen]
+        wins = [windows[r[5]:r[5] + r[3] * r[4]].reshape(r[3], r[4]) for r in regions]
+        comps = [comp[r[5]:r[5] + r[3] * r[4]].reshape(r[3], r[4]) for r in regions]
+        return labels, regions, centers, wins, comps
 
     # ---- NuSeT's network stage ---------------------------------------------------------------------------
     RPN_MAX_CANDIDATES = 1 << 22   # ECSEG_RPN_MAX_CANDIDATES

@@ -7,6 +7,7 @@
 #include "scratch.h"
 #include "iseg_batch.h"
 #include "fish_batch.h"
+#include "mincut_regions.h"
 #include "tiff_decode_batch.h"
 #include "tiff_encode_batch.h"
 #include "tiff_frame.h"
@@ -560,6 +561,18 @@ inline MinCutBufs mincut_bufs(Carver& c, size_t mask_bytes, int n_tasks, size_t 
 // n_global: how many tasks have soff >= 0 (a kernel without tasks is not launched).
 hipError_t run_mincut(const uint8_t* masks, const int32_t* desc, const long long* soff, int n_tasks, int n_global, int d, uint8_t* scratch,
                       uint8_t* side, int32_t* flow, hipStream_t s);
+
+// ---- launchers implemented in mincut_centers_kernels.hip (src/max_flow_binary_mask.py:143-216; layout: mincut_regions.h) ------
+// (the device buffers McrOpenBufs and McrRegionBufs are laid out in mincut_regions.h)
+// b.mask on the device, H * W < 2^31 -> b.lab = run_ccl_labels' 4-connected labels, b.rid[p] = roots in front of pixel p,
+// b.misc[0] = the number of labels.
+hipError_t run_mcr_label(PostWorkspace& ws, int H, int W, const McrOpenBufs& b, hipStream_t s);
+// n = b.misc[0] > 0 -> b.lab renumbered 1..n in raster order of first pixels; stats (n, 5): area, first and last row, first and last column
+hipError_t run_mcr_stats(int H, int W, int n, const McrOpenBufs& b, int32_t* stats, hipStream_t s);
+// b.regions (label, r0, c0, h, w, window offset) and b.slot in place -> b.windows, b.comp (numbered 1.. per region), b.counts,
+// b.first, *b.total and the centre records; n_lds: how many regions mcr_in_lds admits (a kernel without regions is not launched).
+hipError_t run_mcr_centers(const int32_t* labels, int W, int n_regions, int n_lds, int min_rad, int lds_pixels, const McrRegionBufs& b,
+                           hipStream_t s);
 
 // ---- launchers implemented in nuset_kernels.hip (src/utils.py:53, src/model_layers/rpn_proposal.py) ---------------------------
 // mask (h * w uint8) = argmax over the 2 channels of `logits`, a tie giving 0.

@@ -172,6 +172,7 @@ struct ecseg_ctx : ecseg::DevMem {
     uint32_t* pre_file_status = nullptr;   // in pre_arena: read by the call that takes the rasters, after ev_pre
     int tiff_deflate_on_device = 0;   // ecseg_tiff_decode and ecseg_tiff_decode_batch take Deflate strips (tiffb_inflate_kernel); 0: they are ECSEG_E_UNSUPPORTED
     int min_cut_lds_pixels = ECSEG_MIN_CUT_LDS_PIXELS;   // windows above this many pixels keep their state in global memory (tests lower it)
+    int min_cut_centers_lds_pixels = ECSEG_MIN_CUT_CENTERS_LDS_PIXELS;   // ecseg_min_cut_regions: crops above this many pixels keep their state in global memory (tests lower it)
     ecseg::PostWorkspace ws{};       // carved from post_arena
     ecseg::RegionMapBufs iseg{};     // carved from keep_arena
     int iseg_H = 0, iseg_W = 0, iseg_img_w = 0, iseg_C = 0, iseg_n = -1;   // iseg_n < 0: no region map on the handle

@@ -466,4 +466,84 @@ int ecseg_min_cut(ecseg_ctx* h, const uint8_t* masks, long long mask_bytes, cons
     return ECSEG_OK;
 }
 
+// ---- the min-cut splitter before its first max-flow: labels, selection, windows and centres (src/max_flow_binary_mask.py:143-216) ----
+int ecseg_min_cut_regions(ecseg_ctx* h, const uint8_t* mask, int H, int W, double coeff, int min_rad, int region_capacity,
+                          int center_capacity, long long window_capacity, int32_t* labels, int32_t* n_cells, int32_t* regions,
+                          int32_t* n_regions, int32_t* centers, int32_t* n_centers, uint8_t* windows, int32_t* comp, long long* window_pixels) {
+    DRIVER_OPEN(h);
+    static_assert(MCR_LDS_PIXELS == ECSEG_MIN_CUT_CENTERS_LDS_PIXELS && MCR_MAX_PIXELS == ECSEG_MIN_CUT_MAX_PIXELS &&
+                  MCR_MAX_BYTES == ECSEG_MIN_CUT_MAX_BYTES, "mincut_regions.h and the header disagree");
+    const std::string me = "min_cut_regions: ";
+    if (n_cells) *n_cells = 0;
+    if (n_regions) *n_regions = 0;
+    if (n_centers) *n_centers = 0;
+    if (window_pixels) *window_pixels = 0;
+    if (!mask || !labels || !n_cells || !n_regions || !n_centers || !window_pixels || region_capacity < 0 || center_capacity < 0 ||
+        window_capacity < 0 || (region_capacity > 0 && !regions) || (center_capacity > 0 && !centers) || (window_capacity > 0 && (!windows || !comp)))
+        return fail(h, ECSEG_E_INVALID, me + "bad arguments");
+    if (H < 1 || W < 1) return fail(h, ECSEG_E_INVALID, me + "H and W must be at least 1");
+    if (!px_below_2_31(H, W)) return fail(h, ECSEG_E_INVALID, me + "image too large (H * W must be below 2^31)");
+    if (min_rad < 0) return fail(h, ECSEG_E_INVALID, me + "min_rad must not be negative");
+    if (!(coeff - coeff == 0.0)) return fail(h, ECSEG_E_INVALID, me + "coeff must be finite");
+    USE_DEVICE(h);
+    const size_t px = (size_t)H * W;
+    int rc;
+    McrOpenBufs o{};
+    if ((rc = ensure_post(h, 1, px))) return rc;
+    if ((rc = lay_out(h, h->call_arena, [&](Carver& c) { o = mcr_open_bufs(c, H, W); }))) return rc;
+    hipStream_t s = h->stream;
+    clear_timings(h);
+    HIP_TRY(h, hipMemcpyAsync(o.mask, mask, px, hipMemcpyHostToDevice, s));
+    TIMED(h, s, 0, 1, HIP_TRY(h, run_mcr_label(h->ws, H, W, o, s)));
+    int32_t n = 0;
+    HIP_TRY(h, hipMemcpyAsync(&n, o.misc, sizeof(n), hipMemcpyDeviceToHost, s));
+    WAIT_SET(h, s, 0, 1);
+    *n_cells = n;
+    if (n == 0) {                                            // an empty mask: no label, no region
+        std::fill(labels, labels + px, (int32_t)0);
+        return ECSEG_OK;
+    }
+    // the areas and boxes are sized by the number of labels, which is known only now
+    int32_t* d_stats = nullptr;
+    if ((rc = lay_out(h, h->count_arena, [&](Carver& c) { d_stats = c.take<int32_t>((size_t)n * 5); }))) return rc;
+    TIMED(h, s, 2, 3, HIP_TRY(h, run_mcr_stats(H, W, n, o, d_stats, s)));
+    std::vector<int32_t> stats((size_t)n * 5);
+    HIP_TRY(h, hipMemcpyAsync(stats.data(), d_stats, stats.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipMemcpyAsync(labels, o.lab, px * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    WAIT_ADD(h, s, 2, 3);
+    McrPlan P;
+    const std::string bad = mcr_plan(stats.data(), n, coeff, h->min_cut_centers_lds_pixels, P);
+    if (!bad.empty()) return fail(h, ECSEG_E_INVALID, me + bad);
+    *n_regions = P.n_regions;
+    *window_pixels = P.window_pixels;
+    if (P.n_regions == 0) return ECSEG_OK;
+    // a region's accumulators: at most one 8-connected component per 2 x 2 block of its interior
+    std::vector<int32_t> slot((size_t)P.n_regions);
+    size_t slots = 0;
+    for (int i = 0; i < P.n_regions; ++i) {
+        const int rh = P.regions[(size_t)i * MCR_REC + 3], rw = P.regions[(size_t)i * MCR_REC + 4];
+        slot[(size_t)i] = (int32_t)slots;
+        slots += mcr_center_bound(rh, rw);
+    }
+    McrRegionBufs b{};                                       // (the statistics are on the host: their arena is laid out anew)
+    if ((rc = lay_out(h, h->count_arena, [&](Carver& c) { b = mcr_region_bufs(c, P.n_regions, (size_t)P.window_pixels, slots); }))) return rc;
+    HIP_TRY(h, hipMemcpyAsync(b.regions, P.regions.data(), P.regions.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(b.slot, slot.data(), slot.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    TIMED(h, s, 0, 1, HIP_TRY(h, run_mcr_centers(o.lab, W, P.n_regions, P.n_lds, min_rad, h->min_cut_centers_lds_pixels, b, s)));
+    std::vector<int32_t> counts((size_t)P.n_regions);
+    HIP_TRY(h, hipMemcpyAsync(counts.data(), b.counts, counts.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    WAIT_ADD(h, s, 0, 1);
+    const long long nc = mcr_place_centers(P, counts.data());
+    if (nc < 0 || nc > (long long)slots) return fail(h, ECSEG_E_INVALID, me + "the component counts leave their bound");
+    *n_centers = (int32_t)nc;
+    if (!mcr_fits(P.n_regions, nc, P.window_pixels, region_capacity, center_capacity, window_capacity))
+        return ECSEG_OK;                                     // the counts alone: the caller comes back with larger buffers
+    std::copy(P.regions.begin(), P.regions.end(), regions);
+    if (nc > 0) HIP_TRY(h, hipMemcpyAsync(centers, b.centers, (size_t)nc * MCR_REC * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipMemcpyAsync(windows, b.windows, (size_t)P.window_pixels, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipMemcpyAsync(comp, b.comp, (size_t)P.window_pixels * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    return ECSEG_OK;
+}
+
 }  // extern "C"

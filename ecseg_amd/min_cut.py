@@ -157,7 +157,29 @@ def label_colors(labels, mask, seed=1):
     return np.dstack([r, g, b]).astype(np.uint8)
 
 
-def binary_seg_to_instance_min_cut(segmented_cells, flow_limit, cell_size_threshold_coeff, seed=1, handle=None, stats=None):
+def device_regions(handle, seg, coeff, rng, min_rad=10):
+    """The labelling, the selection and ``get_centers`` of every selected region from ONE ``handle.min_cut_regions`` call ->
+    (labels, [(label, box, mask, centers)] for the regions with two or more centres).  The host walks the records in region order
+    and component order; a component whose rounded centroid is off the mask ([3] == 0) takes ``rng.randint(area)`` and that entry
+    of the component's pixels in raster order (:148-150), so the draws come in the reference's order."""
+    labels, regions, centers, windows, comps = handle.min_cut_regions((np.asarray(seg) != 0).astype(np.uint8), coeff, min_rad)
+    out = []
+    for i, reg in enumerate(np.asarray(regions).tolist()):
+        k, r0, c0, h, w, _, first, count = reg
+        cs = []
+        for j, rec in enumerate(np.asarray(centers[first:first + count]).tolist()):
+            row, col = rec[1], rec[2]
+            if not rec[3]:
+                pick = np.flatnonzero(np.asarray(comps[i]).reshape(-1) == j + 1)[rng.randint(rec[4])]
+                row, col = divmod(int(pick), w)
+            cs.append((int(row), int(col)))
+        if len(cs) > 1:
+            out.append((k, (slice(r0, r0 + h), slice(c0, c0 + w)), np.asarray(windows[i]), cs))
+    return np.asarray(labels), out
+
+
+def binary_seg_to_instance_min_cut(segmented_cells, flow_limit, cell_size_threshold_coeff, seed=1, handle=None, stats=None,
+                                   regions_on_device=False):
     """src/max_flow_binary_mask.py:202-233 -> (labels int32 (H, W), visualization uint8 (H, W, 3)).
     Base labelling (:204): 4-connected (``connectivity=1``), numbered 1..n in raster order of the first pixel -
     ``handle.ccl_labels(mask, 4)`` renumbered by rank.  Regions with area > coeff * median(area) (:205-206,214) are cut where
@@ -166,7 +188,8 @@ def binary_seg_to_instance_min_cut(segmented_cells, flow_limit, cell_size_thresh
     ``num_cells + 1``, ``+ 2``, ... in region order, then cell order (:220-225).  One ``RandomState(seed)`` per call stands for
     ``np.random.seed(seed)`` (:203).  ``handle``: anything with ``ccl_labels`` and ``min_cut`` (a ``_lib.Handle``); ``stats``: a dict
     that receives the time of the centre finding ('centers', seconds), the device calls ('calls', 'tasks') and their kernel time
-    ('kernel_ms')."""
+    ('kernel_ms').  ``regions_on_device``: everything before the first ``min_cut`` call comes from one
+    ``handle.min_cut_regions`` call (``device_regions``); 'centers' is then the wall time of that call plus the record walk."""
     import time
     from scipy import ndimage
     if handle is None:
@@ -176,31 +199,41 @@ def binary_seg_to_instance_min_cut(segmented_cells, flow_limit, cell_size_thresh
         raise ValueError('binary_seg_to_instance_min_cut takes a 2-D mask')
     distance = flow_distance(flow_limit)
     rng = np.random.RandomState(seed)
-    raw = np.asarray(handle.ccl_labels((seg != 0).astype(np.uint8) * np.uint8(255), 4))
-    values = np.unique(raw[raw > 0])
-    labels = np.where(raw > 0, np.searchsorted(values, raw) + 1, 0).astype(np.int32)
-    num_cells = len(values)
-    if num_cells == 0:
-        return labels, label_colors(labels, seg, seed)
-    areas = np.bincount(labels.reshape(-1), minlength=num_cells + 1)[1:]
-    expected = np.median(areas)
-    boxes = ndimage.find_objects(labels)
-    t0 = time.perf_counter()
-    items, owners = [], []
-    for k in range(1, num_cells + 1):
-        if areas[k - 1] > cell_size_threshold_coeff * expected:
-            mask = (labels[boxes[k - 1]] == k).astype(np.uint8)
-            centers = get_centers(mask, rng=rng)
-            if len(centers) > 1:
-                items.append((mask, centers))
-                owners.append(k)
+    if regions_on_device:
+        t0 = time.perf_counter()
+        labels, found = device_regions(handle, seg, cell_size_threshold_coeff, rng)
+        num_cells = int(labels.max()) if labels.size else 0
+        if num_cells == 0:
+            return labels, label_colors(labels, seg, seed)
+        boxes = {k: box for k, box, _, _ in found}
+        items = [(mask, centers) for _, _, mask, centers in found]
+        owners = [k for k, _, _, _ in found]
+    else:
+        raw = np.asarray(handle.ccl_labels((seg != 0).astype(np.uint8) * np.uint8(255), 4))
+        values = np.unique(raw[raw > 0])
+        labels = np.where(raw > 0, np.searchsorted(values, raw) + 1, 0).astype(np.int32)
+        num_cells = len(values)
+        if num_cells == 0:
+            return labels, label_colors(labels, seg, seed)
+        areas = np.bincount(labels.reshape(-1), minlength=num_cells + 1)[1:]
+        expected = np.median(areas)
+        boxes = dict(enumerate(ndimage.find_objects(labels), start=1))
+        t0 = time.perf_counter()
+        items, owners = [], []
+        for k in range(1, num_cells + 1):
+            if areas[k - 1] > cell_size_threshold_coeff * expected:
+                mask = (labels[boxes[k]] == k).astype(np.uint8)
+                centers = get_centers(mask, rng=rng)
+                if len(centers) > 1:
+                    items.append((mask, centers))
+                    owners.append(k)
     if stats is not None:
         stats['centers'] = stats.get('centers', 0.0) + time.perf_counter() - t0
         stats['regions'] = stats.get('regions', 0) + len(items)
     out = labels.copy()
     for k, cells in zip(owners, segment_many(items, distance, handle, stats=stats)):
-        view = out[boxes[k - 1]]
-        view[labels[boxes[k - 1]] == k] = 0
+        view = out[boxes[k]]
+        view[labels[boxes[k]] == k] = 0
         for i, cell in enumerate(cells):
             if i:
                 num_cells += 1

@@ -293,7 +293,7 @@ def read_mask(path, handle=None, pre=None, tiff_read_deflate=False):
 
 
 def process_image(path, mask_path, out_root, params, scale, handle, stats=None, use_min_cut=False, segment=None, tiff_on_device=False,
-                  tiff_read_on_device=False, pre_read=None, pending=None, tiff_read_deflate=False):
+                  tiff_read_on_device=False, pre_read=None, pending=None, tiff_read_deflate=False, min_cut_regions_on_device=False):
     """One image of src/stat_fish.py:199-308 -> (CSV rows, the scale that was used); the rows of a four-channel image carry the aqua
     fields of ``csv_columns(3)``, and ``stats['probes']`` becomes 3 once such an image was seen (it may have no nucleus and no row).  The three colour files come from ``handle.fish_render`` when the handle has it, else from
     ``render``, which writes the same bytes.  ``use_min_cut`` (:221-224): the label map comes
@@ -310,7 +310,8 @@ def process_image(path, mask_path, out_root, params, scale, handle, stats=None, 
     and its CSV rows - and returns no rows: ``main`` writes the files of k such images through one ``handle.fish_render_tiff_many``
     call and adds the rows once they are on disk.  The ``.npy`` file is written here as always.  A pending image holds its image,
     thresholded masks, boundaries and mask until then, 3 + 2 + 1 + 1 bytes per pixel: about 10.1 MB at 1040 x 1392 x 3 (8.7 MB without
-    the mask; another 4.3 MB with the min-cut picture)."""
+    the mask; another 4.3 MB with the min-cut picture).  ``min_cut_regions_on_device`` (the config key of that name, with
+    ``use_min_cut``): the splitter's labelling, selection and centres come from one ``handle.min_cut_regions`` call; same labels."""
     import time
     from . import image_io
     t0 = time.perf_counter()
@@ -331,7 +332,8 @@ def process_image(path, mask_path, out_root, params, scale, handle, stats=None, 
     try:
         if use_min_cut:
             from .min_cut import binary_seg_to_instance_min_cut
-            labels, visualization = binary_seg_to_instance_min_cut(mask, params['flow_limit'], params['cell_size_threshold_coeff'], handle=handle)
+            labels, visualization = binary_seg_to_instance_min_cut(mask, params['flow_limit'], params['cell_size_threshold_coeff'], handle=handle,
+                                                                   regions_on_device=min_cut_regions_on_device)
         else:
             labels = handle.ccl_labels(mask, 8)
         off = ([[0.0]], float('inf'), [float('inf')] * len(probes), 1)     # a call for the regions alone
@@ -394,7 +396,7 @@ def process_image(path, mask_path, out_root, params, scale, handle, stats=None, 
 
 
 def prepare_image(path, mask_path, out_root, params, scale, handle, stats=None, use_min_cut=False, segment=None, tiff_read_on_device=False,
-                  pre_read=None, tiff_read_deflate=False):
+                  pre_read=None, tiff_read_deflate=False, min_cut_regions_on_device=False):
     """The front half of ``process_image`` for ``stat_fish.batch`` above 1 -> (the image's share of a chunk, the scale that was used):
     the image and its mask are read (or segmented), the min-cut splitter runs when it is on, and the image's own parameters are worked
     out - with ``scale: auto`` from the areas of a regions-only ``fish_spots`` call, as ``process_image`` does.  Nothing is labelled,
@@ -420,7 +422,8 @@ def prepare_image(path, mask_path, out_root, params, scale, handle, stats=None, 
     try:
         if use_min_cut:
             from .min_cut import binary_seg_to_instance_min_cut
-            labels, visualization = binary_seg_to_instance_min_cut(mask, params['flow_limit'], params['cell_size_threshold_coeff'], handle=handle)
+            labels, visualization = binary_seg_to_instance_min_cut(mask, params['flow_limit'], params['cell_size_threshold_coeff'], handle=handle,
+                                                                   regions_on_device=min_cut_regions_on_device)
         if scale == 'auto':                                  # the areas come first: the weights depend on them
             rec, _, _ = handle.fish_spots(labels if use_min_cut else handle.ccl_labels(mask, 8), I, probes, off[0], off[1], off[2], off[3],
                                           params['line_thickness'])
@@ -602,6 +605,14 @@ def main(argv=None, handle=None):
         if use_min_cut and handle is not None and not hasattr(handle, 'min_cut'):
             raise ConfigError('use_min_cut: True needs the min-cut splitter (src/max_flow_binary_mask.py), whose device call the handle in use '
                               'does not have: set use_min_cut: False in config.yaml')
+        regions_on_device = var.get('min_cut_regions_on_device', False)
+        if not isinstance(regions_on_device, bool):
+            raise ConfigError('min_cut_regions_on_device must be true or false (true, with use_min_cut: the labelling, the selection and the '
+                              'centres of the min-cut splitter come from one device call)')
+        regions_on_device = regions_on_device and use_min_cut        # ignored without the splitter
+        if regions_on_device and handle is not None and not hasattr(handle, 'min_cut_regions'):
+            raise ConfigError('min_cut_regions_on_device: true needs the device call min_cut_regions, which the handle in use does not have; '
+                              'only min_cut_regions_on_device: false works on it')
         scale = var['scale']
         if scale != 'auto' and (isinstance(scale, bool) or not isinstance(scale, (int, float)) or not scale > 0 or math.isinf(scale)):
             raise ConfigError('scale must be a positive number or "auto"')
@@ -805,7 +816,7 @@ def main(argv=None, handle=None):
                     if fish_batch > 1:
                         work, scale = prepare_image(p, mask_of(p), out_root, params, scale, handle, stats=seen, use_min_cut=use_min_cut,
                                                     segment=hooks.get(p), tiff_read_on_device=tiff_read_on_device, pre_read=ahead.pop(p, None),
-                                                    tiff_read_deflate=read_deflate)
+                                                    tiff_read_deflate=read_deflate, min_cut_regions_on_device=regions_on_device)
                         held.append(work)
                         if len(held) >= fish_batch:
                             run_chunk()
@@ -813,7 +824,7 @@ def main(argv=None, handle=None):
                     img_rows, scale = process_image(p, mask_of(p), out_root, params, scale, handle,
                                                      stats=seen, use_min_cut=use_min_cut, segment=hooks.get(p), tiff_on_device=tiff_on_device,
                                                      tiff_read_on_device=tiff_read_on_device, pre_read=ahead.pop(p, None), pending=pending,
-                                                     tiff_read_deflate=read_deflate)
+                                                     tiff_read_deflate=read_deflate, min_cut_regions_on_device=regions_on_device)
                     rows += img_rows
                 except ImageError as e:
                     print(p, '-', e)

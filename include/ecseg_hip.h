@@ -233,6 +233,7 @@ int ecseg_set_images_per_group(ecseg_ctx* h, int n);
  * bit-identical for every value), "blocking_wait" (1 (default): the wait for a launch group sleeps on an event created
  * with hipEventBlockingSync; 0: hipStreamSynchronize), "min_cut_lds_pixels" (0 .. ECSEG_MIN_CUT_LDS_PIXELS (default): windows of
  * ecseg_min_cut with more pixels than this keep their state in global memory instead of LDS; the results do not depend on it),
+ * "min_cut_centers_lds_pixels" (0 .. ECSEG_MIN_CUT_CENTERS_LDS_PIXELS (default): the same for the crops of ecseg_min_cut_regions),
  * "tiff_deflate_on_device" (0 (default): ecseg_tiff_decode and ecseg_tiff_decode_batch leave Deflate files to the host,
  * ECSEG_E_UNSUPPORTED; 1: they decode them on the device - see "TIFF files decoded on the device" below). */
 int ecseg_set_option(ecseg_ctx* h, const char* key, int value);
@@ -777,6 +778,36 @@ int ecseg_prefetch_tiffs(ecseg_ctx* h, const uint8_t* files, long long files_byt
 #define ECSEG_MIN_CUT_LDS_PIXELS 10240
 int ecseg_min_cut(ecseg_ctx* h, const uint8_t* masks, long long mask_bytes, const int32_t* tasks, int n_tasks, int dist, uint8_t* side,
                   int32_t* flow);
+
+/* ---- the min-cut nucleus splitter before its first max-flow (src/max_flow_binary_mask.py:143-216) ---------------------------- */
+/* Replaces, for ONE image, label(mask, connectivity=1) (:204), the areas, their median and the selection (:205-206,214), the
+ * bounding-box crops (:212,215) and get_centers + binary_img_to_centers on every selected crop (:143-199, percentile 0).
+ * mask: (H, W) uint8, != 0 is foreground.  labels (H, W) int32: the 4-connected components numbered 1..n in raster order of each
+ * component's first pixel, 0 background; *n_cells = n.  Selected: the labels with (double)area > coeff * np.median(areas), strictly,
+ * in ascending label order; *n_regions their count.  Per selected region i:
+ *   regions (region_capacity x 8 int32): [0] label  [1] r0  [2] c0  [3] h  [4] w (its bounding box)  [5] offset of its window
+ *     [6] index of its first centre record  [7] number of centre components;
+ *   windows: the crop labels[box] == label as uint8 0 / 1, row-major, the crops back to back - the layout ecseg_min_cut takes for
+ *     `masks`; *window_pixels their total size; comp (int32, laid out as windows): the 8-connected components of the centre pixels,
+ *     numbered 1.. in raster order of first pixels, 0 elsewhere;
+ *   centers (center_capacity x 8 int32), by region, then component: [0] region index  [1] row  [2] column (the component's centroid
+ *     rounded half to even, crop coordinates)  [3] 1 if the window is non-zero there, else 0 (the caller then draws a pixel of the
+ *     component, :148-150)  [4] area  [5] raster index of the component's first pixel in the crop  [6] 0  [7] 0.
+ * Centre pixels of an h x w crop: with d the exact city-block distance to the nearest zero pixel of the crop itself (2^30 everywhere
+ * when it has none) and the candidates the interior pixels with d > min_rad that are not below any of their eight neighbours, the
+ * interior pixels with d >= max(min over the candidates of d, min_rad); none without a candidate or when h < 3 or w < 3.
+ * When region_capacity < *n_regions, center_capacity < *n_centers or window_capacity < *window_pixels, labels and the three counts
+ * are still written and regions, centers, windows and comp are not touched: call again with larger buffers (as ecseg_fish_spots).
+ * One synchronous call, scratch from the handle's arenas, device time of the kernels in ECSEG_T_COUNT; integer work throughout: two
+ * calls give identical bytes.  ECSEG_E_INVALID: a null pointer, a negative capacity, H or W < 1, H * W >= 2^31, min_rad < 0, coeff
+ * not finite, a selected region whose crop exceeds ECSEG_MIN_CUT_MAX_PIXELS (the message names the label) or windows of more than
+ * ECSEG_MIN_CUT_MAX_BYTES in all - ecseg_min_cut would refuse those anyway.  Crops of up to ECSEG_MIN_CUT_CENTERS_LDS_PIXELS pixels
+ * (whose rows, padded to an odd stride, fit 10240 cells) keep their state in LDS, larger ones in their own part of comp. */
+#define ECSEG_MIN_CUT_CENTERS_LDS_PIXELS 8192
+int ecseg_min_cut_regions(ecseg_ctx* h, const uint8_t* mask, int H, int W, double coeff, int min_rad, int region_capacity,
+                          int center_capacity, long long window_capacity, int32_t* labels, int32_t* n_cells, int32_t* regions,
+                          int32_t* n_regions, int32_t* centers, int32_t* n_centers, uint8_t* windows, int32_t* comp,
+                          long long* window_pixels);
 
 /* ---- NuSeT's network stage (src/utils.py:35-103): the U-Net mask and the RPN proposal layer ------------------------------ */
 /* Runs the loaded plan on ONE whole image and writes pred_masks (:53): x is the normalised (H, W) float32 image, the plan's input

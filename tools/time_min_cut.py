@@ -10,6 +10,14 @@ and max over --reps passes after a warm-up pass,
 and, as the baseline, the scipy restatement tests/min_cut_ref.py ``instance_min_cut`` of the same scenes on one core and on a pool
 of --cpu-workers processes (seconds per image = wall time / scenes).  The labels of the device path are compared with the
 restatement's on every scene.  Prints one JSON line.
+
+    python tools/time_min_cut.py --regions-on-device off|on|alternate [--passes 3] [--leg-timeout 300]
+
+times the whole ``binary_seg_to_instance_min_cut`` on the same scene with ``regions_on_device`` off, on, or - ``alternate`` - in the
+legs off, on, off, on of one session: every leg is a child process under its own time limit, does one warm-up pass and then
+--passes passes, and reports median (min - max) of the whole function, the 'centers' share (with the key on: the one device call
+plus the record walk) and ECSEG_T_COUNT of ecseg_min_cut_regions.  The project's rule: the key is a gain only where the slowest
+pass with it on is faster than the fastest pass with it off; the line says so in ``gain``.
 """
 import argparse
 import json
@@ -40,12 +48,73 @@ def _mmm(values):
     return {'median': statistics.median(values), 'min': min(values), 'max': max(values)}
 
 
+def _leg(on, passes):
+    """One leg in this process -> dict for the parent."""
+    import min_cut_cases as cases
+    from ecseg_amd import min_cut as mc
+    from ecseg_amd._lib import Handle
+    gpu = Handle(0)
+    mask = cases.big_scene(0)
+    whole, centers, call_ms = [], [], []
+    for rep in range(passes + 1):
+        stats = {}
+        t0 = time.perf_counter()
+        labels, _ = mc.binary_seg_to_instance_min_cut(mask, 60, 1.25, handle=gpu, stats=stats, regions_on_device=on)
+        if rep:
+            whole.append((time.perf_counter() - t0) * 1e3)
+            centers.append(stats['centers'] * 1e3)
+    if on:
+        for _ in range(passes):
+            gpu.min_cut_regions((mask != 0).astype(np.uint8), 1.25)
+            call_ms.append(float(gpu.timings()['count']))
+    out = {'on': on, 'whole_function_ms': _mmm(whole), 'centers_ms': _mmm(centers), 'cells': int(labels.max()),
+           'labels_sha': __import__('hashlib').sha256(np.ascontiguousarray(labels).tobytes()).hexdigest()}
+    if call_ms:
+        out['min_cut_regions_kernel_ms'] = _mmm(call_ms)
+    gpu.close()
+    return out
+
+
+def _legs(mode, passes, limit):
+    import subprocess
+    order = {'off': [False], 'on': [True], 'alternate': [False, True, False, True]}[mode]
+    legs = []
+    for on in order:                                         # a fresh child per leg, each under its own time limit
+        cmd = [sys.executable, os.path.abspath(__file__), '--leg', 'on' if on else 'off', '--passes', str(passes)]
+        try:
+            got = subprocess.run(cmd, capture_output=True, text=True, timeout=limit)
+        except subprocess.TimeoutExpired:
+            print(json.dumps({'error': 'leg %s ran into its time limit of %d s' % ('on' if on else 'off', limit), 'legs': legs}), flush=True)
+            return 1
+        if got.returncode != 0:
+            print(json.dumps({'error': 'leg failed', 'stderr': got.stderr[-2000:], 'legs': legs}), flush=True)
+            return 1
+        legs.append(json.loads(got.stdout.strip().splitlines()[-1]))
+    out = {'mode': mode, 'passes': passes, 'legs': legs, 'labels_equal': len({leg['labels_sha'] for leg in legs}) == 1}
+    offs = [leg['whole_function_ms'] for leg in legs if not leg['on']]
+    ons = [leg['whole_function_ms'] for leg in legs if leg['on']]
+    if offs and ons:
+        out['fastest_off_ms'], out['slowest_on_ms'] = min(v['min'] for v in offs), max(v['max'] for v in ons)
+        out['gain'] = out['slowest_on_ms'] < out['fastest_off_ms']
+    print(json.dumps(out), flush=True)
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--reps', type=int, default=7)
     ap.add_argument('--cpu-workers', type=int, default=16)
     ap.add_argument('--scenes', type=int, default=16)
+    ap.add_argument('--regions-on-device', choices=['off', 'on', 'alternate'])
+    ap.add_argument('--passes', type=int, default=3)
+    ap.add_argument('--leg-timeout', type=int, default=300)
+    ap.add_argument('--leg', choices=['off', 'on'], help=argparse.SUPPRESS)
     a = ap.parse_args()
+    if a.leg:
+        print(json.dumps(_leg(a.leg == 'on', a.passes)), flush=True)
+        return
+    if a.regions_on_device:
+        sys.exit(_legs(a.regions_on_device, a.passes, a.leg_timeout))
     import min_cut_cases as cases
     from ecseg_amd import min_cut as mc
     from ecseg_amd._lib import Handle
