@@ -36,6 +36,7 @@ EXPORTS = [
     'ecseg_stitch_stages_debug', 'ecseg_preprocess_stages_debug', 'ecseg_otsu_debug',
     'ecseg_stat_fish_batch', 'ecseg_stat_fish_batch_bytes',
     'ecseg_min_cut_regions',
+    'ecseg_scratch_fill_debug',
 ]
 
 
@@ -143,6 +144,7 @@ def load_library():
     lib.ecseg_count_cc.argtypes = [vp, u8p, i32, i32, i32, vp, vp]
     lib.ecseg_ccl_labels.argtypes = [vp, u8p, i32, i32, i32, i32, vp]
     lib.ecseg_ccl_pass_debug.argtypes = [vp, u8p, u8p, i32, i32, i32, C.POINTER(CclPassDesc), C.POINTER(CclPassOut)]
+    lib.ecseg_scratch_fill_debug.argtypes = [vp, i32]
     lib.ecseg_count_colocalization.argtypes = [vp, u8p, u8p, i32, i32, i32, vp]
     lib.ecseg_count_hsr.argtypes = [vp, u8p, u8p, i32, i32, i32, i32, vp]
     lib.ecseg_overlay.argtypes = [vp, u8p, u8p, i32, i32, i32, i32, i32, i32, vp]
@@ -801,6 +803,12 @@ class Handle:
                     list1=[l1[i, :max(0, min(cap, int(cnt[i, 7])))].copy() for i in range(n)],
                     list2=[l2[i, :max(0, min(cap, int(cnt[i, 8])))].copy() for i in range(n)])
         return bufs
+
+    def scratch_fill_debug(self, byte):
+        """Test-only (ecseg_scratch_fill_debug): fills the whole capacity of every scratch arena of the handle with ``byte`` (0 .. 255),
+        between two waits for the handle's streams.  The region map of ``nuclei_regions``, what was sent or decoded ahead and the
+        clean-up workspace's layout are withdrawn; every driver must answer afterwards as on a fresh handle."""
+        self._check(self.lib.ecseg_scratch_fill_debug(self.h, int(byte)), 'ecseg_scratch_fill_debug')
 
     def count_colocalization(self, ob1, ob2):
         a, single = self._stack(ob1)

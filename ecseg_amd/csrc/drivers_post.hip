@@ -299,6 +299,36 @@ int ecseg_ccl_pass_debug(ecseg_ctx* h, const uint8_t* key_img, const uint8_t* au
     return ECSEG_OK;
 }
 
+// Test-only: every scratch arena of ctx.h filled with `byte` over its whole capacity (not the last layout's extent), between two waits
+// for every stream of the handle.  Nothing grows or is freed.  The slots that are meant to outlive their call are withdrawn the way
+// their owners do it, so that no later call reads the fill as state:
+//   keep_arena  iseg (ecseg_nuclei_regions -> ecseg_nucleus_crops, ecseg_classify_nucleus_crops): iseg_n = -1, "no region map";
+//   pre_arena   the decode-ahead's file images, tables and status words (pre_file_status): DRIVER_OPEN drops what was sent ahead
+//               (pre_tiffs.files = null, without which no call takes the rasters; pre_plan and pre_read_ms keep their values unread);
+//   post_arena  ws: only its layout outlives a call, never its contents; dropped, so the next ensure_post lays it out for its own need.
+// call_arena and count_arena carry nothing: the cell index a FISH driver leaves in call_arena is rebuilt by the call that comes back.
+int ecseg_scratch_fill_debug(ecseg_ctx* h, int byte) {
+    DRIVER_OPEN(h);
+    if (byte < 0 || byte > 255) return fail(h, ECSEG_E_INVALID, "scratch_fill_debug: byte must be 0 .. 255");
+    USE_DEVICE(h);
+    auto wait_all = [&]() -> hipError_t {
+        hipError_t e;
+        if ((e = hipStreamSynchronize(h->stream)) != hipSuccess) return e;
+        if ((e = hipStreamSynchronize(h->stream2)) != hipSuccess) return e;
+        if (h->stream_in && (e = hipStreamSynchronize(h->stream_in)) != hipSuccess) return e;
+        for (hipStream_t ls : h->lane_streams) if ((e = hipStreamSynchronize(ls)) != hipSuccess) return e;
+        return hipSuccess;
+    };
+    HIP_TRY(h, wait_all());
+    h->iseg_n = -1; h->iseg = RegionMapBufs{};
+    h->pre_file_status = nullptr;
+    h->ws = PostWorkspace{};
+    for (DevBuf<uint8_t>* a : {&h->post_arena, &h->call_arena, &h->count_arena, &h->keep_arena, &h->pre_arena})
+        if (a->p && a->cap) HIP_TRY(h, hipMemsetAsync(a->p, byte, a->cap, h->stream));
+    HIP_TRY(h, wait_all());
+    return ECSEG_OK;                                         // (untimed: stage_ms keeps the call before's)
+}
+
 int ecseg_overlay(ecseg_ctx* h, const uint8_t* labels, const uint8_t* rgb, int n_img, int H, int W, int C, int sens, int hsr_thr,
                   int64_t* out) {
     DRIVER_OPEN(h);

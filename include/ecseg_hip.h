@@ -77,6 +77,8 @@ extern "C" {
  * tests of csrc/stitch_preprocess_kernels.hip; nothing existing changed.) */
 /* (still 5 - additive: ecseg_stat_fish_batch and ecseg_stat_fish_batch_bytes, the labelling, spot statistics, colour files and TIFF
  * encode of many stat_fish images in one call; nothing existing changed.) */
+/* (still 5 - additive: ecseg_scratch_fill_debug, every scratch arena of the handle filled with one byte, for the tests that hold each
+ * driver to its answer whatever an earlier call left there; nothing existing changed.) */
 #define ECSEG_ABI_VERSION 5
 
 #define ECSEG_OK             0
@@ -342,6 +344,12 @@ typedef struct ecseg_ccl_pass_out {
 } ecseg_ccl_pass_out;
 int ecseg_ccl_pass_debug(ecseg_ctx* h, const uint8_t* key_img, const uint8_t* aux_img, int n_img, int H, int W,
                          const ecseg_ccl_pass_desc* pass, const ecseg_ccl_pass_out* out);
+/* Test-only: waits for the handle's streams, fills the whole present capacity of every scratch arena of the drivers with `byte`
+ * (0 .. 255) and waits again.  No arena grows, shrinks or is freed.  What a call leaves in an arena for a later one is withdrawn as
+ * its owner withdraws it: the region map of ecseg_nuclei_regions (ecseg_nucleus_crops then fails with "no region map on the
+ * handle"), whatever was sent or decoded ahead for the next ecseg_meta_segment call, and the layout of the clean-up workspace, which
+ * the next call that needs it makes anew.  Every driver must answer afterwards as on a fresh handle. */
+int ecseg_scratch_fill_debug(ecseg_ctx* h, int byte);
 /* count_colocalization (:126-134) */
 int ecseg_count_colocalization(ecseg_ctx* h, const uint8_t* ob1, const uint8_t* ob2, int n_img, int H, int W,
                                int32_t* n_out);

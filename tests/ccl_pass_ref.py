@@ -163,3 +163,53 @@ def tile_owner_counts(img, lut, conn):
         for tx in range(nx):
             out[ty, tx] = len(components(np.asarray(img)[ty * TILE_H:(ty + 1) * TILE_H, tx * TILE_W:(tx + 1) * TILE_W], lut, conn)[1])
     return out
+
+
+# ---- the comparison of one device call with the reference (tests/test_gpu_ccl_pass.py, tests/test_gpu_scratch.py) ----
+def check_queries(got, labs, aux, mode, queries, what):
+    for i, lab in enumerate(labs):
+        flags = lab.flags(mode.aux_mode, mode.aux_c, None if aux is None else aux[i])
+        want = [lab.query(flags, qk, qn) for qk, qn in queries]
+        assert got['cnt'][i, :len(queries)].tolist() == want, (what, i, queries)
+
+
+def check_pass(got, imgs, aux, mode, labs, queries, what):
+    """Everything one ``Handle.ccl_pass`` call exported (``got``) against the Labellings ``labs`` of its images, image by image."""
+    full = allow_full_effective(mode.conn, mode.stat, mode.need, mode.count_only, mode.allow_full)
+    for i, lab in enumerate(labs):
+        w = (what, i)
+        px = imgs[i].size
+        idx = np.arange(px)
+        assert np.array_equal(got['tile_any'][i], tile_model(keys_of(imgs[i], mode.lut), full)), w
+        root = got['root'][i].ravel()
+        zero = np.zeros(imgs[i].shape, np.int64)
+        if mode.count_only:
+            # no resolved roots: the pixels counted as roots are exactly the components' first pixels
+            assert np.array_equal(np.flatnonzero(root >= 0), np.sort(lab.root)), w
+            assert np.array_equal(root[root >= 0], idx[root >= 0]) and root.min(initial=-1) >= -1, w
+            flags = None
+            for k in ('area', 'sumy', 'sumx', 'flag'):
+                assert not got[k][i].any(), (w, k)
+        else:
+            assert np.array_equal(got['root'][i], lab.root_px), w
+            keyed = root >= 0
+            assert np.array_equal(root[root[keyed]], root[keyed]) and (root[keyed] <= idx[keyed]).all(), w
+            flags = lab.flags(mode.aux_mode, mode.aux_c, None if aux is None else aux[i])
+            if mode.aux_mode == AUX_NONE:
+                assert not flags.any()
+            assert np.array_equal(got['flag'][i], lab.at_roots(flags, np.uint32)), w
+            assert np.array_equal(got['area'][i], lab.at_roots(lab.area, np.uint32) if mode.stat & STAT_AREA else zero), w
+            assert np.array_equal(got['sumy'][i], lab.at_roots(lab.sumy, np.uint64) if mode.stat & STAT_SUMS else zero), w
+            assert np.array_equal(got['sumx'][i], lab.at_roots(lab.sumx, np.uint64) if mode.stat & STAT_SUMS else zero), w
+        if mode.need & NEED_NCOMP:
+            assert got['ncomp'][i].tolist() == lab.ncomp.tolist(), w
+        if mode.need & NEED_NPX:
+            assert got['npx'][i].tolist() == lab.npx.tolist(), w
+        if mode.need & NEED_LAST:
+            assert got['last_root'][i] == lab.last_root, w
+        if mode.need & NEED_LISTS:
+            for k, want in (('1', lab.list1), ('2', lab.list2)):
+                lst = np.sort(got['list' + k][i])
+                assert got['nlist' + k][i] == len(want) and np.array_equal(lst, want) and len(np.unique(lst)) == len(lst), (w, k)
+    if queries:
+        check_queries(got, labs, aux, mode, queries, what)

@@ -82,13 +82,18 @@ def _noise_without_runs(H, W, rng):
     return np.cumsum(rng.integers(1, 256, n)).astype(np.uint8)
 
 
-def _fish(H, W, rng):
-    """clip(N(20, 8)) noise plus bright dots, as the stream of such samples"""
+def fish_raster(H, W, rng):
+    """clip(N(20, 8)) noise plus bright dots: an (H, W) uint8 channel (shared with tests/test_gpu_scratch.py)"""
     v = np.clip(rng.normal(20, 8, (H, W)), 0, 255).astype(np.uint8)
     for _ in range(max(1, H * W // 400)):
         y, x = int(rng.integers(0, H)), int(rng.integers(0, W))
         v[y:y + 2, x:x + 2] = 230
-    return stream_of(v, False).ravel()
+    return v
+
+
+def _fish(H, W, rng):
+    """``fish_raster`` as the stream of its samples"""
+    return stream_of(fish_raster(H, W, rng), False).ravel()
 
 
 def _speckle(H, W, rng):

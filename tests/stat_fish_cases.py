@@ -160,3 +160,30 @@ def full_size_scene(seed=1):
             img[y0:y1, x0:x1, c] += rng.uniform(60, 200) * np.exp(-((yy[y0:y1] - cy) ** 2 + (xx[:, x0:x1] - cx) ** 2) / (2 * s * s))
     img = np.clip(np.rint(img), 0, 255).astype(np.uint8)
     return img, (seg != 0).astype(np.uint8) * np.uint8(255)
+
+
+def make_item(seed, size, K, C, source, min_cc=None, picture=False, mask_file=True):
+    """A seeded scene of tests/stat_fish_cases.py as an item of ``stat_fish_many``.  source: 'mask' (the scene's cells as a 0 / 255
+    mask), 'labels' (its label map as given), 'background', 'foreground' (all-zero / all-255 masks)."""
+    case = scene(seed, size=size, K=K, n_probe=2)
+    rng = np.random.default_rng(seed + 77)
+    H, W = size
+    img = case['img']
+    if img.shape[2] != C:                                    # the scene drew its own channel count: cut or add the aqua channel
+        img = np.ascontiguousarray(img[..., :3]) if C == 3 else np.dstack([img, rng.integers(0, 200, (H, W, 1)).astype(np.uint8)])
+    probes = list(case['probes']) + ([3] if C == 4 else [])
+    blue = [c for c in range(C) if c not in probes][0]
+    item = dict(img=np.ascontiguousarray(img), channels=[blue] + probes, weights=NAN1 if K == 1 else case['weights'],
+                normal_threshold=case['normal'], intensity_thresholds=list(case['ithr']) + ([55.0] if C == 4 else []),
+                min_cc_size=case['min_cc'] if min_cc is None else min_cc)
+    seg = case['seg']
+    if source == 'labels':
+        item['labels'] = seg
+    else:
+        mask = {'mask': (seg != 0), 'background': np.zeros((H, W), bool), 'foreground': np.ones((H, W), bool)}[source]
+        item['mask'] = mask.astype(np.uint8) * np.uint8(255)
+        if mask_file:
+            item['mask_file'] = True
+    if picture:
+        item['picture'] = rng.integers(0, 256, (H, W, 3)).astype(np.uint8)
+    return item

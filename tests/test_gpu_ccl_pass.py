@@ -36,53 +36,7 @@ def _run(gpu, imgs, aux, mode, queries=()):
                         allow_full=mode.allow_full, queries=queries)
 
 
-def _check_queries(got, labs, aux, mode, queries, what):
-    for i, lab in enumerate(labs):
-        flags = lab.flags(mode.aux_mode, mode.aux_c, None if aux is None else aux[i])
-        want = [lab.query(flags, qk, qn) for qk, qn in queries]
-        assert got['cnt'][i, :len(queries)].tolist() == want, (what, i, queries)
-
-
-def _check(got, imgs, aux, mode, labs, queries, what):
-    """Everything one call exported, image by image."""
-    full = ref.allow_full_effective(mode.conn, mode.stat, mode.need, mode.count_only, mode.allow_full)
-    for i, lab in enumerate(labs):
-        w = (what, i)
-        px = imgs[i].size
-        idx = np.arange(px)
-        assert np.array_equal(got['tile_any'][i], ref.tile_model(ref.keys_of(imgs[i], mode.lut), full)), w
-        root = got['root'][i].ravel()
-        zero = np.zeros(imgs[i].shape, np.int64)
-        if mode.count_only:
-            # no resolved roots: the pixels counted as roots are exactly the components' first pixels
-            assert np.array_equal(np.flatnonzero(root >= 0), np.sort(lab.root)), w
-            assert np.array_equal(root[root >= 0], idx[root >= 0]) and root.min(initial=-1) >= -1, w
-            flags = None
-            for k in ('area', 'sumy', 'sumx', 'flag'):
-                assert not got[k][i].any(), (w, k)
-        else:
-            assert np.array_equal(got['root'][i], lab.root_px), w
-            keyed = root >= 0
-            assert np.array_equal(root[root[keyed]], root[keyed]) and (root[keyed] <= idx[keyed]).all(), w
-            flags = lab.flags(mode.aux_mode, mode.aux_c, None if aux is None else aux[i])
-            if mode.aux_mode == ref.AUX_NONE:
-                assert not flags.any()
-            assert np.array_equal(got['flag'][i], lab.at_roots(flags, np.uint32)), w
-            assert np.array_equal(got['area'][i], lab.at_roots(lab.area, np.uint32) if mode.stat & ref.STAT_AREA else zero), w
-            assert np.array_equal(got['sumy'][i], lab.at_roots(lab.sumy, np.uint64) if mode.stat & ref.STAT_SUMS else zero), w
-            assert np.array_equal(got['sumx'][i], lab.at_roots(lab.sumx, np.uint64) if mode.stat & ref.STAT_SUMS else zero), w
-        if mode.need & ref.NEED_NCOMP:
-            assert got['ncomp'][i].tolist() == lab.ncomp.tolist(), w
-        if mode.need & ref.NEED_NPX:
-            assert got['npx'][i].tolist() == lab.npx.tolist(), w
-        if mode.need & ref.NEED_LAST:
-            assert got['last_root'][i] == lab.last_root, w
-        if mode.need & ref.NEED_LISTS:
-            for k, want in (('1', lab.list1), ('2', lab.list2)):
-                lst = np.sort(got['list' + k][i])
-                assert got['nlist' + k][i] == len(want) and np.array_equal(lst, want) and len(np.unique(lst)) == len(lst), (w, k)
-    if queries:
-        _check_queries(got, labs, aux, mode, queries, what)
+_check_queries, _check = ref.check_queries, ref.check_pass     # (shared with tests/test_gpu_scratch.py)
 
 
 def _hold(gpu, mode, ci):

@@ -31,21 +31,7 @@ def model16(gpu):
     return MetasegModel(cfg, synth.unet_weights(cfg, seed=0), handle=gpu)
 
 
-def tiff_of(img, rps, compression=5, predictor=1, big_endian=False):
-    """the file of (H, W[, C]) uint8 / uint16 samples under a plan, built with tests/tiff_decode_cases.py"""
-    H, W = img.shape[:2]
-    a = img.reshape(H, W, -1)
-    if predictor == 2:
-        d = a.copy()
-        d[:, 1:] = a[:, 1:] - a[:, :-1]
-        a = d
-    if a.dtype == np.uint16:
-        a = a.astype('>u2' if big_endian else '<u2')
-    rows = a.reshape(H, -1)
-    strips = [rows[r:r + rps].tobytes() for r in range(0, H, rps)]
-    if compression == 5:
-        strips = [tc.pack(tc.lzw_codes(s)) for s in strips]
-    return tc.tiff_file(strips, H, W, rps, spp=a.shape[2], bits=8 * img.dtype.itemsize, compression=compression, predictor=predictor, big_endian=big_endian)
+tiff_of = tc.file_of                         # (shared with tests/test_gpu_scratch.py)
 
 
 def _samples(seed, H, W, spp, bits, bright=False):

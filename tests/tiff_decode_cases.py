@@ -184,3 +184,20 @@ def strips_of(data):
             break
         out.append((data[o:o + min(c, len(data) - o)], rows * line))
     return out
+
+
+def file_of(img, rps, compression=5, predictor=1, big_endian=False):
+    """the file of (H, W[, C]) uint8 / uint16 samples under a plan, strips by ``lzw_codes`` / ``pack``, the file by ``tiff_file``"""
+    H, W = img.shape[:2]
+    a = img.reshape(H, W, -1)
+    if predictor == 2:
+        d = a.copy()
+        d[:, 1:] = a[:, 1:] - a[:, :-1]
+        a = d
+    if a.dtype == np.uint16:
+        a = a.astype('>u2' if big_endian else '<u2')
+    rows = a.reshape(H, -1)
+    strips = [rows[r:r + rps].tobytes() for r in range(0, H, rps)]
+    if compression == 5:
+        strips = [pack(lzw_codes(s)) for s in strips]
+    return tiff_file(strips, H, W, rps, spp=a.shape[2], bits=8 * img.dtype.itemsize, compression=compression, predictor=predictor, big_endian=big_endian)
