@@ -54,6 +54,16 @@ asan_tiff_decode_batch:
 	    ecseg_amd/csrc/host_codec.cpp tools/asan/tiff_decode_batch_fuzz.cpp -o /tmp/ecseg_tiff_decode_batch_fuzz
 	/tmp/ecseg_tiff_decode_batch_fuzz
 
+# and for its tiled files (option tiff_tiled_on_device): the tile-table parse, tile_place (csrc/tiff_parse.h), the layout with staging
+# slots and the staging -> raster walk of tiffb_untile_kernel (csrc/tiff_untile.h) compiled for the host, lanes as a loop, against a
+# naive untile; tests/test_tiff_tiles.py builds and runs it.  TIFF_TILES_CHECK: where the program is put
+TIFF_TILES_CHECK ?= /tmp/ecseg_tiff_tiles_check
+.PHONY: asan_tiff_tiles
+asan_tiff_tiles:
+	g++ -std=c++17 -O1 -g -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=all \
+	    ecseg_amd/csrc/host_codec.cpp ecseg_amd/csrc/host_io.cpp tools/asan/tiff_tiles_check.cpp -lz -o $(TIFF_TILES_CHECK)
+	$(TIFF_TILES_CHECK)
+
 # and for the batched writer: the layout function (csrc/tiff_encode_batch.h) over seeded file lists and the strip routine of the
 # encode kernels (csrc/tiff_encode_strip.h) compiled for the host, lanes as a loop, against the host encoder;
 # tests/test_tiff_encode_batch.py builds and runs it

@@ -361,7 +361,7 @@ int entry_values(const Reader& r, size_t e, std::vector<uint32_t>* out) {
 
 // ECSEG_OK, ECSEG_E_UNSUPPORTED (a valid layout this reader leaves to the Python one) or ECSEG_E_INVALID (corrupt); TiffInfo and
 // the declaration are in tiff_parse.h, for the device reader's driver
-int ecseg::parse_tiff(const uint8_t* buf, size_t n, TiffInfo* t) {
+int ecseg::parse_tiff(const uint8_t* buf, size_t n, TiffInfo* t, bool take_tiles) {
     if (n < 8) return ECSEG_E_INVALID;
     if (buf[0] == 'I' && buf[1] == 'I') t->le = true;
     else if (buf[0] == 'M' && buf[1] == 'M') t->le = false;
@@ -374,15 +374,23 @@ int ecseg::parse_tiff(const uint8_t* buf, size_t n, TiffInfo* t) {
     if (!r.ok(ifd, 2)) return ECSEG_E_INVALID;
     const uint32_t ne = r.u16(ifd);
     if (!r.ok(ifd + 2, (size_t)ne * 12)) return ECSEG_E_INVALID;
-    bool have_w = false, have_h = false, tiled = false;
-    std::vector<uint32_t> v;
+    bool have_w = false, have_h = false, tiled = false, have_th = false, tile_tags_ok = true;
+    std::vector<uint32_t> v, tile_off, tile_cnt;
     for (uint32_t i = 0; i < ne; ++i) {
         const size_t e = ifd + 2 + (size_t)i * 12;
         const uint32_t tag = r.u16(e);
         const bool wanted = tag == 256 || tag == 257 || tag == 258 || tag == 259 || tag == 273 || tag == 277 || tag == 278 ||
-                            tag == 279 || tag == 284 || tag == 317 || tag == 339 || tag == 322;
+                            tag == 279 || tag == 284 || tag == 317 || tag == 339 || tag == 322 || (take_tiles && tag >= 323 && tag <= 325);
         if (!wanted) continue;
-        if (tag == 322) { tiled = true; continue; }
+        if (tag == 322) tiled = true;
+        if (tag >= 322 && tag <= 325) {                      // the tile tags: read for a caller that takes tiles, and never the reason a file of strips is refused
+            if (!take_tiles) continue;
+            if (entry_values(r, e, &v) != ECSEG_OK || v.empty()) { tile_tags_ok = false; continue; }
+            if (tag == 322) t->tw = v[0];
+            else if (tag == 323) { t->th = v[0]; have_th = true; }
+            else (tag == 324 ? tile_off : tile_cnt) = v;
+            continue;
+        }
         if (const int rc = entry_values(r, e, &v)) return rc;
         if (v.empty()) return ECSEG_E_INVALID;
         switch (tag) {
@@ -401,9 +409,19 @@ int ecseg::parse_tiff(const uint8_t* buf, size_t n, TiffInfo* t) {
     }
     if (!have_w || !have_h || t->W == 0 || t->H == 0 || t->spp == 0 || t->W > (1u << 20) || t->H > (1u << 20) || t->spp > 16)
         return ECSEG_E_INVALID;
-    if (tiled || (t->bits != 8 && t->bits != 16) || t->fmt != 1 || (t->planar != 1 && t->spp > 1) ||
+    if ((tiled && !take_tiles) || (t->bits != 8 && t->bits != 16) || t->fmt != 1 || (t->planar != 1 && t->spp > 1) ||
         (t->comp != 1 && t->comp != 5 && t->comp != 8 && t->comp != 32946) || (t->pred != 1 && t->pred != 2))
         return ECSEG_E_UNSUPPORTED;
+    if (tiled) {                                             // (take_tiles) the rule of tiff_parse.h; everything else is the Python reader's
+        if (!tile_tags_ok || !have_th || t->tw == 0 || t->th == 0 || t->tw % 16 || t->th % 16 || t->tw > TIFF_TILE_MAX_EXTENT || t->th > TIFF_TILE_MAX_EXTENT ||
+            !t->off.empty() || !t->cnt.empty())
+            return ECSEG_E_UNSUPPORTED;
+        const size_t n_tiles = (size_t)((t->H + t->th - 1) / t->th) * ((t->W + t->tw - 1) / t->tw);
+        if (tile_off.size() < n_tiles || tile_cnt.size() < n_tiles) return ECSEG_E_UNSUPPORTED;
+        t->off = tile_off; t->cnt = tile_cnt; t->rps = t->H;
+        return ECSEG_OK;
+    }
+    t->tw = t->th = 0;                                       // (TileLength and the tables without TileWidth: strips)
     if (t->off.empty()) return ECSEG_E_INVALID;
     if (t->cnt.empty()) {
         if (t->off.size() != 1 || t->off[0] > n) return ECSEG_E_INVALID;

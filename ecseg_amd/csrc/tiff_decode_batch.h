@@ -34,9 +34,19 @@ struct TdFile {
     uint32_t first_strip;    // global index of strip 0 (grid x of tiffb_unstrip_kernel); the file has ceil(H / rps) strips
     uint32_t first_row;      // global index of row 0 (grid x of tiffb_unpredict_kernel); the file has H rows
     uint8_t codec, swap, predictor, in_batch;    // TD_RAW / TD_LZW / TD_DEFLATE strips; 16-bit samples in the other byte order; horizontal predictor; 0: a file of zero strips
-    uint32_t pad;
+    uint32_t tiles;          // 0: strips; else 1 + the file's row of the tiled-file table (then n_table is its tile count, rps its tile length)
 };
 static_assert(sizeof(TdFile) == 80, "the device table is an array of 80-byte rows, copied as it is");
+
+// A tiled file: the tile grid, where its staging slots lie (tile k at stage_off + k * th * tw * spp * bps; unused for TD_RAW), and the
+// global index of its first row of tiles (grid x of tiffb_untile_kernel; the file has `down` of them).
+struct TdTiles {
+    uint64_t stage_off;
+    uint32_t file;           // its row of the file table
+    uint32_t tw, th, across, down;
+    uint32_t first_trow;
+};
+static_assert(sizeof(TdTiles) == 32, "the tiled-file table is an array of 32-byte rows, copied as it is");
 
 // What the layout is made from, per file: the tags (parse_tiff), where the caller keeps the file and wants the raster.
 struct TdFileIn {
@@ -44,6 +54,7 @@ struct TdFileIn {
     uint32_t n_table = 0, H = 0, W = 0, spp = 1, bps = 1, rps = 1;
     uint8_t codec = TD_RAW;
     bool swap = false, predictor = false;
+    uint32_t tw = 0, th = 0; // a tiled file's tile extents (0: strips); n_table is then at least its tile count
     bool in_batch = false;   // false: the file takes no part (zero strips, zero rows, nothing uploaded for it)
 };
 
@@ -55,11 +66,13 @@ struct TdBatchLayout {
     uint64_t n_strips = 0, n_rows = 0;           // the two grids
     bool any_u8_predictor = false, any_u16_pass = false;     // which tiffb_unpredict_kernel launches the batch needs
     bool any_deflate = false;                    // whether it needs tiffb_inflate_kernel
+    std::vector<TdTiles> tiles;                  // one row per tiled file that takes part (empty: no tiffb_untile_kernel, no staging)
+    uint64_t stage_bytes = 0, n_trows = 0;       // the staging slots of all compressed tiles; the rows of tiles (the grid of tiffb_untile_kernel)
 };
 
 constexpr uint64_t TD_BATCH_MAX_GRID = (1ull << 31) - 1;     // grid dimension x
 
-inline uint64_t td_file_strips(const TdFile& f) { return f.in_batch ? ((uint64_t)f.H + f.rps - 1) / f.rps : 0; }
+inline uint64_t td_file_strips(const TdFile& f) { return !f.in_batch ? 0 : f.tiles ? f.n_table : ((uint64_t)f.H + f.rps - 1) / f.rps; }
 inline uint64_t td_file_raster_bytes(const TdFile& f) { return f.in_batch ? f.line * f.H : 0; }
 
 // Empty string, or what is wrong: a 16-bit raster at an odd offset, or more strips or rows than a grid has.  The caller has made
@@ -92,26 +105,41 @@ inline std::string td_batch_layout(const std::vector<TdFileIn>& in, TdBatchLayou
         t.line = (uint64_t)f.W * f.spp * f.bps;
         t.n_table = f.n_table; t.H = f.H; t.rps = f.rps; t.W = f.W; t.spp = f.spp; t.bps = f.bps;
         t.codec = f.codec; t.swap = f.swap && f.bps == 2; t.predictor = f.predictor;
-        L.table_words += 2ull * f.n_table;
+        if (f.tw) {                                          // tiles: the table holds the image's tiles and no more; compressed ones get a slot each
+            TdTiles tt{L.stage_bytes, (uint32_t)i, f.tw, f.th, (f.W + f.tw - 1) / f.tw, (f.H + f.th - 1) / f.th, (uint32_t)L.n_trows};
+            const uint64_t n_tiles = (uint64_t)tt.across * tt.down;
+            if (n_tiles > f.n_table || n_tiles > TD_BATCH_MAX_GRID) return "file " + std::to_string(i) + ": a tile table shorter than the image";
+            t.n_table = (uint32_t)n_tiles; t.rps = f.th; t.tiles = (uint32_t)L.tiles.size() + 1;
+            if (f.codec != TD_RAW) L.stage_bytes += n_tiles * f.th * f.tw * f.spp * f.bps;
+            L.n_trows += tt.down;
+            L.tiles.push_back(tt);
+        }
+        L.table_words += 2ull * t.n_table;
         L.n_strips += td_file_strips(t);
         L.n_rows += f.H;
         if (L.n_strips > TD_BATCH_MAX_GRID || L.n_rows > TD_BATCH_MAX_GRID) return "the batch holds 2^31 strips or rows, or more";
-        L.any_u16_pass = L.any_u16_pass || (t.bps == 2 && (t.swap || t.predictor));
-        L.any_u8_predictor = L.any_u8_predictor || (t.bps == 1 && t.predictor);
+        L.any_u16_pass = L.any_u16_pass || (!t.tiles && t.bps == 2 && (t.swap || t.predictor));      // (tiffb_untile_kernel does both for a tiled file)
+        L.any_u8_predictor = L.any_u8_predictor || (!t.tiles && t.bps == 1 && t.predictor);
         L.any_deflate = L.any_deflate || t.codec == TD_DEFLATE;
     }
     return std::string();
 }
 
-// Device buffers of one batch: the table, the file images, the strip tables, the rasters, one status word per strip and one per file.
+// Device buffers of one batch: the table, the file images, the strip tables, the rasters, one status word per strip and one per file;
+// for a batch with tiled files, behind them, the tiled-file table and the staging slots.
 // `rasters`: where the caller's destination lies on the device already (the input slots of ecseg_meta_segment_tiffs): the rasters are
 // written there, from dst_base on, and the arena holds none.
-struct TiffDecodeBatchBufs { TdFile* tab; uint8_t* files; uint32_t* tables; uint8_t* rasters; uint32_t* strip_status; uint32_t* file_status; };
+struct TiffDecodeBatchBufs {
+    TdFile* tab; uint8_t* files; uint32_t* tables; uint8_t* rasters; uint32_t* strip_status; uint32_t* file_status;
+    TdTiles* tiles; uint8_t* staging;
+};
 inline TiffDecodeBatchBufs tiff_decode_batch_bufs(Carver& c, const TdBatchLayout& L, uint8_t* rasters = nullptr) {
     TiffDecodeBatchBufs b;
     b.tab = c.take<TdFile>(L.tab.size()); b.files = c.take<uint8_t>((size_t)L.src_span); b.tables = c.take<uint32_t>((size_t)L.table_words);
     b.rasters = rasters ? rasters + L.dst_base : c.take<uint8_t>((size_t)L.dst_span); b.strip_status = c.take<uint32_t>((size_t)L.n_strips);
     b.file_status = c.take<uint32_t>(L.tab.size());
+    b.tiles = nullptr; b.staging = nullptr;
+    if (!L.tiles.empty()) { b.tiles = c.take<TdTiles>(L.tiles.size()); b.staging = c.take<uint8_t>((size_t)L.stage_bytes); }
     return b;
 }
 

@@ -15,10 +15,16 @@
 // tiffb_unpredict_kernel: one wave per row, after all strips: 16-bit samples of a big-endian file are swapped to native order, then
 // the horizontal predictor is undone per sample channel (stride spp) as an inclusive wave scan over 64 samples with a carry
 // into the next 64, modulo 2^8 or 2^16 (td_unpredict_row).
+// tiffb_untile_kernel: only for a batch with tiled files (the handle option tiff_tiled_on_device), after the two strip kernels, in
+// which a tile is a strip of the grid whose stream decodes into its staging slot.  Grid x is the row of tiles counted over the tiled
+// files (TdTiles), grid y splits the rows of the tiles among TD_UNTILE_PARTS waves; a wave puts whole raster rows in their place:
+// byte order, the predictor along each tile row, the padding of edge tiles dropped (tiff_untile.h).  The row kernel above leaves
+// tiled files alone.
 // tiffb_status_kernel: the strip words folded into one word per file.
 #include "common.h"
 #include "tiff_decode_strip.h"
 #include "tiff_inflate_strip.h"
+#include "tiff_untile.h"
 
 namespace ecseg {
 
@@ -53,18 +59,20 @@ __device__ __forceinline__ void td_unpredict_row(T* __restrict__ q, uint32_t W, 
 
 // ---- the kernels: the pointers come from the table (tiff_decode_batch.h), the work is td_unpredict_row and tiff_decode_strip.h ----
 __global__ __launch_bounds__(64) void tiffb_unstrip_kernel(const TdFile* __restrict__ tab, uint32_t n_files, const uint8_t* __restrict__ files,
-                                                           const uint32_t* __restrict__ tables, uint8_t* rasters, uint32_t* __restrict__ status) {
+                                                           const uint32_t* __restrict__ tables, uint8_t* rasters, uint32_t* __restrict__ status,
+                                                           const TdTiles* __restrict__ tiles, uint8_t* staging) {
     __shared__ TdLds L;
-    const uint32_t st = tdb_unstrip(tab, n_files, files, tables, rasters, blockIdx.x, L);
+    const uint32_t st = tdb_unstrip(tab, n_files, files, tables, rasters, blockIdx.x, L, tiles, staging);
     if (threadIdx.x == 0 && st != TD_OTHER_KERNEL) status[blockIdx.x] = st;
 }
 
 // The same grid for the Deflate strips (ti_inflate_strip, tiff_inflate_strip.h): a workgroup whose strip is the kernel's above
 // returns at once, as that kernel's do here.  The two write disjoint status words and disjoint rows of the rasters.
 __global__ __launch_bounds__(64) void tiffb_inflate_kernel(const TdFile* __restrict__ tab, uint32_t n_files, const uint8_t* __restrict__ files,
-                                                           const uint32_t* __restrict__ tables, uint8_t* rasters, uint32_t* __restrict__ status) {
+                                                           const uint32_t* __restrict__ tables, uint8_t* rasters, uint32_t* __restrict__ status,
+                                                           const TdTiles* __restrict__ tiles, uint8_t* staging) {
     __shared__ TiLds L;
-    const uint32_t st = tdb_inflate(tab, n_files, files, tables, rasters, blockIdx.x, L);
+    const uint32_t st = tdb_inflate(tab, n_files, files, tables, rasters, blockIdx.x, L, tiles, staging);
     if (threadIdx.x == 0 && st != TD_OTHER_KERNEL) status[blockIdx.x] = st;
 }
 
@@ -73,8 +81,16 @@ template <typename T>
 __global__ __launch_bounds__(64) void tiffb_unpredict_kernel(const TdFile* __restrict__ tab, uint32_t n_files, uint8_t* rasters) {
     const TdFile& f = tab[td_first(td_find_file(tab, n_files, blockIdx.x, true))];
     const uint32_t row = blockIdx.x - f.first_row;
-    if (!f.in_batch || row >= f.H || f.bps != sizeof(T) || !(f.swap || f.predictor)) return;
+    if (!f.in_batch || f.tiles || row >= f.H || f.bps != sizeof(T) || !(f.swap || f.predictor)) return;
     td_unpredict_row(reinterpret_cast<T*>(rasters + f.raster_off + (size_t)row * f.line), f.W, f.spp, f.swap, f.predictor);
+}
+
+// Grid x is the global row of tiles, grid y the part of its rows (tdb_untile, tiff_untile.h).
+constexpr uint32_t TD_UNTILE_PARTS = 8;
+__global__ __launch_bounds__(64) void tiffb_untile_kernel(const TdFile* __restrict__ tab, const TdTiles* __restrict__ tiles, uint32_t n_tiled,
+                                                          const uint8_t* __restrict__ files, const uint32_t* __restrict__ tables,
+                                                          const uint8_t* __restrict__ staging, uint8_t* rasters) {
+    tdb_untile(tab, tiles, n_tiled, files, tables, staging, rasters, blockIdx.x, blockIdx.y, TD_UNTILE_PARTS);
 }
 
 // One thread per strip: a strip that is not clean marks its file, and no other.  file_status is zero before.
@@ -91,8 +107,12 @@ hipError_t run_tiff_decode_batch(const TiffDecodeBatchBufs& b, const TdBatchLayo
     const uint32_t n = (uint32_t)L.tab.size(), ns = (uint32_t)L.n_strips, nr = (uint32_t)L.n_rows;
     hipError_t e = hipMemsetAsync(b.file_status, 0, (size_t)n * sizeof(uint32_t), s);
     if (e != hipSuccess || ns == 0) return e;
-    hipLaunchKernelGGL(tiffb_unstrip_kernel, dim3(ns), dim3(64), 0, s, b.tab, n, b.files, b.tables, b.rasters, b.strip_status);
-    if (L.any_deflate) hipLaunchKernelGGL(tiffb_inflate_kernel, dim3(ns), dim3(64), 0, s, b.tab, n, b.files, b.tables, b.rasters, b.strip_status);
+    hipLaunchKernelGGL(tiffb_unstrip_kernel, dim3(ns), dim3(64), 0, s, b.tab, n, b.files, b.tables, b.rasters, b.strip_status, b.tiles, b.staging);
+    if (L.any_deflate)
+        hipLaunchKernelGGL(tiffb_inflate_kernel, dim3(ns), dim3(64), 0, s, b.tab, n, b.files, b.tables, b.rasters, b.strip_status, b.tiles, b.staging);
+    if (!L.tiles.empty())
+        hipLaunchKernelGGL(tiffb_untile_kernel, dim3((uint32_t)L.n_trows, TD_UNTILE_PARTS), dim3(64), 0, s, b.tab, b.tiles, (uint32_t)L.tiles.size(), b.files,
+                           b.tables, b.staging, b.rasters);
     if (L.any_u16_pass) hipLaunchKernelGGL(tiffb_unpredict_kernel<uint16_t>, dim3(nr), dim3(64), 0, s, b.tab, n, b.rasters);
     if (L.any_u8_predictor) hipLaunchKernelGGL(tiffb_unpredict_kernel<uint8_t>, dim3(nr), dim3(64), 0, s, b.tab, n, b.rasters);
     hipLaunchKernelGGL(tiffb_status_kernel, dim3((ns + 255) / 256), dim3(256), 0, s, b.tab, n, b.strip_status, ns, b.file_status);

@@ -155,6 +155,21 @@ TD_FN TdStrip td_strip(uint32_t strip, const uint8_t* file, unsigned long long n
     return t;
 }
 
+// Tile k of a tiled file: its stream in the file and, for a compressed tile, its staging slot.  The stream is clamped to the file as
+// the Python reader's slice buf[off:off + cnt] is - an offset behind the file is an empty stream, not an error of its own: an LZW or
+// uncompressed tile of no bytes is zeros, a Deflate one a short stream.
+TD_FN uint32_t td_tile_stream(uint32_t k, const TdFile& f, const uint32_t* tables, unsigned long long* at) {
+    const unsigned long long off = tables[f.table_off + k], cnt = tables[f.table_off + f.n_table + k];
+    *at = off < f.n_bytes ? off : f.n_bytes;
+    return (uint32_t)(cnt < f.n_bytes - *at ? cnt : f.n_bytes - *at);        // (below 2^32: the counts are 32-bit)
+}
+TD_FN TdStrip td_tile(uint32_t k, const TdFile& f, const TdTiles& tt, const uint8_t* files, const uint32_t* tables, uint8_t* staging) {
+    const unsigned long long tile_bytes = (unsigned long long)tt.th * tt.tw * f.spp * f.bps;      // (below 2^31: the driver refuses larger tiles)
+    unsigned long long at = 0;
+    const uint32_t have = td_tile_stream(k, f, tables, &at);
+    return TdStrip{files + f.file_off + at, staging + tt.stage_off + k * tile_bytes, have, (uint32_t)tile_bytes, true, false};
+}
+
 // An uncompressed strip: a clamped copy and the zero fill, by `nlanes` lanes (the threads of the workgroup).
 TD_FN void td_raw_strip(const TdStrip& t, uint32_t nlanes) {
     const uint32_t got = t.have < t.want ? t.have : t.want;
@@ -177,11 +192,17 @@ TD_FN uint32_t td_find_file(const TdFile* tab, uint32_t n, uint32_t idx, bool ro
 
 // Global strip `strip` of a batch, by one wave: td_lzw_strip or td_raw_strip on the strip's file.  Returns its status word (0, or 1:
 // corrupt stream / offset behind the file), the same in every lane; TD_OTHER_KERNEL for a Deflate strip (tdb_inflate, tiff_inflate_strip.h).
+// tiles, staging: the tiled-file table and the staging slots of a batch that has tiled files (else no row of tab points there).
 TD_FN uint32_t tdb_unstrip(const TdFile* tab, uint32_t n_files, const uint8_t* files, const uint32_t* tables, uint8_t* rasters, uint32_t strip,
-                           TdLds& L) {
+                           TdLds& L, const TdTiles* tiles = nullptr, uint8_t* staging = nullptr) {
     const TdFile& f = tab[td_first(td_find_file(tab, n_files, strip, false))];
     if (f.codec == TD_DEFLATE) return TD_OTHER_KERNEL;
     const uint32_t k = strip - f.first_strip;
+    if (f.tiles) {                                           // a tile: an LZW stream into its slot; an uncompressed one is tiffb_untile_kernel's alone
+        if (!f.in_batch || k >= f.n_table || f.codec != TD_LZW) return 0u;
+        const TdStrip t = td_tile(k, f, tiles[f.tiles - 1], files, tables, staging);
+        return td_lzw_strip(t.src, t.have, t.dst, t.want, L);
+    }
     if (!f.in_batch || (unsigned long long)k * f.rps >= f.H) return 0u;      // (the grid has the strips of the table: never)
     const uint32_t* offs = tables + f.table_off;
     const TdStrip t = td_strip(k, files + f.file_off, f.n_bytes, offs, offs + f.n_table, f.n_table, f.H, f.line, f.rps, rasters + f.raster_off);

@@ -377,10 +377,15 @@ TD_FN uint32_t ti_inflate_strip(const uint8_t* src, uint32_t have, uint8_t* dst,
 // behind the file), the same in every lane; TD_OTHER_KERNEL for a strip of tdb_unstrip's.  A strip the tables do not have is
 // zero-filled; one they have is a stream, and an empty stream is corrupt.
 TD_FN uint32_t tdb_inflate(const TdFile* tab, uint32_t n_files, const uint8_t* files, const uint32_t* tables, uint8_t* rasters, uint32_t strip,
-                           TiLds& L) {
+                           TiLds& L, const TdTiles* tiles = nullptr, uint8_t* staging = nullptr) {
     const TdFile& f = tab[td_first(td_find_file(tab, n_files, strip, false))];
     if (f.codec != TD_DEFLATE) return TD_OTHER_KERNEL;
     const uint32_t k = strip - f.first_strip;
+    if (f.tiles) {                                           // a tile: its zlib stream into its slot (td_tile: an offset behind the file is a short stream)
+        if (!f.in_batch || k >= f.n_table) return 0u;
+        const TdStrip t = td_tile(k, f, tiles[f.tiles - 1], files, tables, staging);
+        return ti_inflate_strip(t.src, t.have, t.dst, t.want, L);
+    }
     if (!f.in_batch || (unsigned long long)k * f.rps >= f.H) return 0u;      // (the grid has the strips of the table: never)
     const uint32_t* offs = tables + f.table_off;
     const TdStrip t = td_strip(k, files + f.file_off, f.n_bytes, offs, offs + f.n_table, f.n_table, f.H, f.line, f.rps, rasters + f.raster_off);

@@ -11,12 +11,40 @@ namespace ecseg {
 
 struct TiffInfo {
     uint32_t W = 0, H = 0, bits = 8, spp = 1, comp = 1, planar = 1, pred = 1, fmt = 1, rps = 0;
+    uint32_t tw = 0, th = 0;         // a tiled file's TileWidth and TileLength (0: strips); off and cnt are then its tile tables
     std::vector<uint32_t> off, cnt;
     bool le = true;
 };
 
-// ECSEG_OK, ECSEG_E_UNSUPPORTED (a valid layout this reader leaves to the Python one) or ECSEG_E_INVALID (corrupt)
-int parse_tiff(const uint8_t* buf, size_t n, TiffInfo* t);
+// ECSEG_OK, ECSEG_E_UNSUPPORTED (a valid layout this reader leaves to the Python one) or ECSEG_E_INVALID (corrupt).
+// tiled == false: a file with TileWidth (tag 322) is ECSEG_E_UNSUPPORTED and its tile tags are not read.  tiled == true (the device
+// reader with the option tiff_tiled_on_device): tags 322 to 325 are read and the file is taken (t->tw != 0) when both tile extents are
+// positive multiples of 16 of at most TIFF_TILE_MAX_EXTENT, it has no strip tags, and both tile tables have an entry for each of its
+// ceil(H / th) * ceil(W / tw) tiles; sample size, format, planarity, compression and predictor are held to the rules of strips.  Every
+// other tiled file stays ECSEG_E_UNSUPPORTED.
+constexpr uint32_t TIFF_TILE_MAX_EXTENT = 1u << 20;
+int parse_tiff(const uint8_t* buf, size_t n, TiffInfo* t, bool tiled = false);
+
+// Where row r of tile `tile` of a tiled image goes: tiles lie row-major, `across` = ceil(W / tw) per row of tiles, and those on the
+// right and bottom edges are padded to the full tile.  -> the raster row, the first pixel column, and of the tile row's tw * px bytes
+// how many are kept (those of pixels inside the image) and how many are dropped as padding; a row below the image keeps nothing.  One
+// plain function for tiffb_untile_kernel and for the host check (tools/asan/tiff_tiles_check.cpp).  H, W, tw, th at most 2^20, px the
+// bytes of a pixel.
+struct TileGeom { uint32_t H, W, th, tw, px; };
+struct TilePlace { uint32_t row, col, keep, drop; };
+#ifdef __HIPCC__
+__host__ __device__
+#endif
+inline TilePlace tile_place(const TileGeom& g, uint32_t tile, uint32_t r) {
+    const uint32_t across = (g.W + g.tw - 1) / g.tw, ty = tile / across, tx = tile - ty * across;
+    TilePlace p;
+    p.row = ty * g.th + r;
+    p.col = tx * g.tw;
+    const uint32_t cols = g.W - p.col < g.tw ? g.W - p.col : g.tw;           // (col < W: tx < across)
+    p.keep = (r < g.th && p.row < g.H) ? cols * g.px : 0u;
+    p.drop = g.tw * g.px - p.keep;
+    return p;
+}
 
 // The routing rule of the device reader, the only place that decides whether a file goes to the device (ecseg_tiff_decode_routes
 // asks it for image_io.imread; ecseg_tiff_decode itself decodes whatever it is given).  A strip is one serial LZW stream on one
@@ -33,12 +61,25 @@ int parse_tiff(const uint8_t* buf, size_t n, TiffInfo* t);
 // a single file wins at 1040 strips (4.73 ms, at most 5.01, against at least 15.66 of the host) and loses at 208 (14.48 against 14.15)
 // and at 70 (42.56 against 14.18); of the sets, those of 70, 140 and 208 strips lose and every measured set from 280 strips up wins
 // (280: four files of 70 strips, at most 51.29 ms against at least 54.92), the stat_fish pairs (1248 strips per image) included.
+//   Tiled files (TiffInfo::tw != 0; tiffb_untile_kernel) count only for a caller that asks (`tiled`: the handle option
+// tiff_tiled_on_device is on, the _ex2 functions) and only from a measured tile count on.  The table of DESIGN.md 5.9
+// (tools/time_tiff_decode.py --tiled) is NOT MEASURED yet: both thresholds are TIFF_TILED_NEVER, the rule answers 0 for every tiled
+// file and set, and only an explicit ecseg_tiff_decode / ecseg_tiff_decode_batch call decodes one on the device.
 constexpr size_t TIFF_DEVICE_MIN_STRIPS = 1040;
+constexpr size_t TIFF_TILED_NEVER = ~(size_t)0;
+constexpr size_t TIFF_TILED_DEVICE_MIN_TILES = TIFF_TILED_NEVER;
+constexpr size_t TIFF_TILED_BATCH_DEVICE_MIN_TILES = TIFF_TILED_NEVER;
+inline size_t tiff_tile_count(const TiffInfo& t) { return t.tw ? (size_t)((t.H + t.th - 1) / t.th) * ((t.W + t.tw - 1) / t.tw) : 0; }
+inline bool tiff_tiled_counts(const TiffInfo& t, bool deflate, bool tiled, size_t threshold) {
+    return tiled && threshold != TIFF_TILED_NEVER && (t.comp == 5 || (deflate && (t.comp == 8 || t.comp == 32946))) &&
+           t.off.size() >= tiff_tile_count(t) && t.cnt.size() >= tiff_tile_count(t);
+}
 constexpr size_t TIFF_DEFLATE_NEVER = ~(size_t)0;
 constexpr size_t TIFF_DEFLATE_DEVICE_MIN_STRIPS = 1040;
 constexpr size_t TIFF_DEFLATE_BATCH_DEVICE_MIN_STRIPS = 280;
 inline bool tiff_is_deflate(const TiffInfo& t) { return t.comp == 8 || t.comp == 32946; }
-inline bool tiff_goes_to_device(const TiffInfo& t, bool deflate = false) {
+inline bool tiff_goes_to_device(const TiffInfo& t, bool deflate = false, bool tiled = false) {
+    if (t.tw) return tiff_tiled_counts(t, deflate, tiled, TIFF_TILED_DEVICE_MIN_TILES) && tiff_tile_count(t) >= TIFF_TILED_DEVICE_MIN_TILES;
     const bool defl = deflate && tiff_is_deflate(t);
     if ((t.comp != 5 && !defl) || t.rps == 0) return false;
     const size_t nstrips = ((size_t)t.H + t.rps - 1) / t.rps;
@@ -60,19 +101,24 @@ inline bool tiff_goes_to_device(const TiffInfo& t, bool deflate = false) {
 // ecseg_tiff_decode accepts.
 constexpr size_t TIFF_BATCH_DEVICE_MIN_STRIPS = 1040;
 constexpr unsigned long long TIFF_BATCH_DEVICE_MAX_STRIP_BYTES = 15ull * 1392 * 3;
-inline bool tiff_batch_counts(const TiffInfo& t, bool deflate = false) {
+inline bool tiff_batch_counts(const TiffInfo& t, bool deflate = false, bool tiled = false) {
+    if (t.tw) return tiff_tiled_counts(t, deflate, tiled, TIFF_TILED_BATCH_DEVICE_MIN_TILES);
     const bool defl = deflate && tiff_is_deflate(t) && TIFF_DEFLATE_BATCH_DEVICE_MIN_STRIPS != TIFF_DEFLATE_NEVER;
     if ((t.comp != 5 && !defl) || t.rps == 0 || t.H == 0) return false;
     const size_t nstrips = ((size_t)t.H + t.rps - 1) / t.rps;
     return t.off.size() >= nstrips &&                        // (a strip table shorter than the image stays on the host, as in the single-file rule)
            (unsigned long long)(t.rps < t.H ? t.rps : t.H) * t.W * t.spp * (t.bits / 8) <= TIFF_BATCH_DEVICE_MAX_STRIP_BYTES;
 }
-inline bool tiff_batch_goes_to_device(const TiffInfo* const* files, size_t n, bool deflate = false) {
-    size_t strips = 0, deflate_strips = 0;
-    for (size_t i = 0; i < n; ++i)
-        if (tiff_batch_counts(*files[i], deflate))
-            (tiff_is_deflate(*files[i]) ? deflate_strips : strips) += ((size_t)files[i]->H + files[i]->rps - 1) / files[i]->rps;
-    return strips >= TIFF_BATCH_DEVICE_MIN_STRIPS || deflate_strips >= TIFF_DEFLATE_BATCH_DEVICE_MIN_STRIPS;
+// Tiled files (with `tiled`) are summed by tiles, on their own, against TIFF_TILED_BATCH_DEVICE_MIN_TILES.
+inline bool tiff_batch_goes_to_device(const TiffInfo* const* files, size_t n, bool deflate = false, bool tiled = false) {
+    size_t strips = 0, deflate_strips = 0, tiles = 0;
+    for (size_t i = 0; i < n; ++i) {
+        if (!tiff_batch_counts(*files[i], deflate, tiled)) continue;
+        if (files[i]->tw) tiles += tiff_tile_count(*files[i]);
+        else (tiff_is_deflate(*files[i]) ? deflate_strips : strips) += ((size_t)files[i]->H + files[i]->rps - 1) / files[i]->rps;
+    }
+    return strips >= TIFF_BATCH_DEVICE_MIN_STRIPS || deflate_strips >= TIFF_DEFLATE_BATCH_DEVICE_MIN_STRIPS ||
+           (TIFF_TILED_BATCH_DEVICE_MIN_TILES != TIFF_TILED_NEVER && tiles >= TIFF_TILED_BATCH_DEVICE_MIN_TILES);
 }
 
 }  // namespace ecseg

@@ -224,12 +224,15 @@ def image_shape(path):
     return read_tiff(path).shape
 
 
-def tiff_goes_to_device(data, deflate=False):
+def tiff_goes_to_device(data, deflate=False, tiled=False):
     """The routing rule of the device reader (csrc/tiff_parse.h, the one place that states it) on the bytes of a file.  ``deflate``:
-    Deflate files count too, from their own measured threshold on (ecseg_tiff_decode_routes_ex)."""
+    Deflate files count too, from their own measured threshold on (ecseg_tiff_decode_routes_ex).  ``tiled``: so do tiled files, from a
+    measured tile count on (ecseg_tiff_decode_routes_ex2)."""
     buf = np.frombuffer(data, np.uint8)
     if not buf.size:
         return False
+    if tiled:
+        return load_library().ecseg_tiff_decode_routes_ex2(buf.ctypes.data_as(C.c_void_p), buf.size, int(bool(deflate)), 1) == 1
     if deflate:
         return load_library().ecseg_tiff_decode_routes_ex(buf.ctypes.data_as(C.c_void_p), buf.size, 1) == 1
     return load_library().ecseg_tiff_decode_routes(buf.ctypes.data_as(C.c_void_p), buf.size) == 1
@@ -240,7 +243,9 @@ def imread(path, handle=None, deflate=False):
     ``handle``: anything with ``Handle.tiff_decode``: a ``.tif`` that the routing rule sends to the device (ecseg_tiff_decode_routes:
     LZW files of many strips) is decoded there, and by the readers of this module when that returns None (a layout it leaves to them)
     or finds the file corrupt or unreadable, so that the error raised is theirs.  ``deflate``: the rule is asked with Deflate files
-    counting, and the handle decodes such a file (``Handle.tiff_decode(data, deflate=True)``)."""
+    counting, and the handle decodes such a file (``Handle.tiff_decode(data, deflate=True)``).  A handle with the option
+    ``tiff_tiled_on_device`` on (its attribute of that name) takes tiled files: the rule is asked with them counting
+    (ecseg_tiff_decode_routes_ex2)."""
     if str(path).lower().endswith('.npy'):
         return np.load(path)
     if handle is not None and hasattr(handle, 'tiff_decode') and str(path).lower().endswith(('.tif', '.tiff')):
@@ -248,7 +253,10 @@ def imread(path, handle=None, deflate=False):
         try:
             with open(path, 'rb') as f:
                 data = f.read()
-            if deflate:
+            if getattr(handle, 'tiff_tiled_on_device', False):
+                if tiff_goes_to_device(data, deflate=deflate, tiled=True):
+                    a = handle.tiff_decode(data, deflate=True) if deflate else handle.tiff_decode(data)
+            elif deflate:
                 if tiff_goes_to_device(data, deflate=True):
                     a = handle.tiff_decode(data, deflate=True)
             elif tiff_goes_to_device(data):
@@ -263,13 +271,22 @@ def imread(path, handle=None, deflate=False):
     return read_tiff(path)
 
 
-def tiff_batch_goes_to_device(datas, deflate=False):
+def tiff_batch_goes_to_device(datas, deflate=False, tiled=False):
     """The routing rule for a set of files (csrc/tiff_parse.h, the one place that states it) on their bytes -> (whether the set goes to
     the device in one ``Handle.tiff_decode_many``, per file whether the rule counts it: the files that are sent when it goes).
-    ``deflate``: Deflate files count too, from their own measured threshold on (the ``_ex`` functions)."""
+    ``deflate``: Deflate files count too, from their own measured threshold on (the ``_ex`` functions).  ``tiled``: so do tiled files
+    (the ``_ex2`` functions)."""
     lib = load_library()
     bufs = [d if isinstance(d, np.ndarray) else np.frombuffer(d, np.uint8) for d in datas]
-    deflate = int(bool(deflate))
+    deflate, tiled = int(bool(deflate)), int(bool(tiled))
+    if tiled:
+        counts = [bool(b.size) and lib.ecseg_tiff_decode_batch_counts_ex2(b.ctypes.data_as(C.c_void_p), b.size, deflate, 1) == 1 for b in bufs]
+        sent = [b for b, c in zip(bufs, counts) if c]
+        if not sent:
+            return False, counts
+        buf, ranges = pack_file_images(sent)
+        return lib.ecseg_tiff_decode_batch_routes_ex2(buf.ctypes.data_as(C.c_void_p), buf.size, ranges.ctypes.data_as(C.c_void_p), len(ranges), deflate,
+                                                      1) == 1, counts
     counts = [bool(b.size) and lib.ecseg_tiff_decode_batch_counts_ex(b.ctypes.data_as(C.c_void_p), b.size, deflate) == 1 for b in bufs]
     sent = [b for b, c in zip(bufs, counts) if c]
     if not sent:
@@ -299,7 +316,7 @@ def imread_many(paths, handle=None, deflate=False):
     (ecseg_tiff_decode_batch_routes: LZW files, whatever their strip count) are decoded in one call when together they are worth it;
     every other file, and every file that call answers with None or an error, is read by ``imread(path)``, so that the samples and
     the errors are always its own.  ``deflate``: Deflate files count in the rule and are decoded by the call
-    (``Handle.tiff_decode_many(datas, deflate=True)``)."""
+    (``Handle.tiff_decode_many(datas, deflate=True)``).  A handle with the option ``tiff_tiled_on_device`` on: as in ``imread``."""
     out = [None] * len(paths)
     if handle is not None and hasattr(handle, 'tiff_decode_many'):
         tiffs = [(k, str(path)) for k, path in enumerate(paths) if str(path).lower().endswith(('.tif', '.tiff'))]
@@ -321,7 +338,10 @@ def imread_many(paths, handle=None, deflate=False):
                 continue
             held.append((k, pool[at:at + got]))
             at += n
-        goes, counts = tiff_batch_goes_to_device([d for _, d in held], deflate=True) if deflate else tiff_batch_goes_to_device([d for _, d in held])
+        if getattr(handle, 'tiff_tiled_on_device', False):   # (the handle option: tiled files count in the rule, and the call takes them)
+            goes, counts = tiff_batch_goes_to_device([d for _, d in held], deflate=deflate, tiled=True)
+        else:
+            goes, counts = tiff_batch_goes_to_device([d for _, d in held], deflate=True) if deflate else tiff_batch_goes_to_device([d for _, d in held])
         if goes:
             sent = [e for e, c in zip(held, counts) if c]
             many = handle.tiff_decode_many([d for _, d in sent], deflate=True) if deflate else handle.tiff_decode_many([d for _, d in sent])

@@ -70,6 +70,9 @@ extern "C" {
 /* (still 5 - additive: option "tiff_deflate_on_device" with ecseg_tiff_decode_routes_ex, ecseg_tiff_decode_batch_routes_ex,
  * ecseg_tiff_decode_batch_counts_ex and ecseg_tiff_decode_batch_bytes_ex, Deflate strips decoded on the device behind an option that
  * is off by default; nothing existing changed.) */
+/* (still 5 - additive: option "tiff_tiled_on_device" with ecseg_tiff_decode_routes_ex2, ecseg_tiff_decode_batch_routes_ex2,
+ * ecseg_tiff_decode_batch_counts_ex2 and ecseg_tiff_decode_batch_bytes_ex2, tiled TIFF files decoded on the device behind an option
+ * that is off by default; nothing existing changed.) */
 /* (still 5 - additive: ecseg_interseg_batch, the regions, crops and classifiers of many interSeg images in one call; nothing existing
  * changed.  The number stays where every additive entry above left it: a caller of version 5 runs unchanged.) */
 /* (still 5 - additive: ecseg_stitch_stages_debug, ecseg_preprocess_stages_debug and ecseg_otsu_debug, the stitch with its tie-risk count
@@ -237,7 +240,9 @@ int ecseg_set_images_per_group(ecseg_ctx* h, int n);
  * ecseg_min_cut with more pixels than this keep their state in global memory instead of LDS; the results do not depend on it),
  * "min_cut_centers_lds_pixels" (0 .. ECSEG_MIN_CUT_CENTERS_LDS_PIXELS (default): the same for the crops of ecseg_min_cut_regions),
  * "tiff_deflate_on_device" (0 (default): ecseg_tiff_decode and ecseg_tiff_decode_batch leave Deflate files to the host,
- * ECSEG_E_UNSUPPORTED; 1: they decode them on the device - see "TIFF files decoded on the device" below). */
+ * ECSEG_E_UNSUPPORTED; 1: they decode them on the device - see "TIFF files decoded on the device" below), "tiff_tiled_on_device"
+ * (0 (default): the two leave tiled files to the Python reader, ECSEG_E_UNSUPPORTED without a shape; 1: they decode them on the
+ * device - the same section). */
 int ecseg_set_option(ecseg_ctx* h, const char* key, int value);
 
 /* ---- meta_preprocess (src/image_tools.py:86-101) ---------------------------------------------------------- */
@@ -670,7 +675,8 @@ int ecseg_tiff_decode_batch_counts(const uint8_t* file, long long n_bytes);
  * checked), mixed freely with LZW and uncompressed files in a batch - and return ECSEG_OK or ECSEG_E_INVALID for them where they
  * returned ECSEG_E_UNSUPPORTED, by the host reader's rules (ecseg_tiff_read: a short stream zero-filled, a long one cut, every zlib
  * data error corrupt; a stream that ends before the strip is full and before its own end is corrupt, as uncompress of zlib 1.2.9 and
- * later has it).  Tiled, PackBits and BigTIFF files stay ECSEG_E_UNSUPPORTED; ecseg_meta_segment_tiffs does not read the option.
+ * later has it).  PackBits and BigTIFF files stay ECSEG_E_UNSUPPORTED, and so do tiled files without the option below;
+ * ecseg_meta_segment_tiffs does not read the option.
  *   The four functions above that take no handle answer as before; these take the switch as `deflate` (0: the same answers).  With
  * it a Deflate file counts from its own thresholds on (csrc/tiff_parse.h, the Deflate tables of DESIGN.md 5.9: a single file from
  * 1040 strips, a set from 280 Deflate strips together, the smallest measured counts at which the device call's maximum is below
@@ -680,6 +686,32 @@ int ecseg_tiff_decode_routes_ex(const uint8_t* file, long long n_bytes, int defl
 int ecseg_tiff_decode_batch_routes_ex(const uint8_t* files, long long files_bytes, const int64_t* file_ranges, int n_files, int deflate);
 int ecseg_tiff_decode_batch_counts_ex(const uint8_t* file, long long n_bytes, int deflate);
 long long ecseg_tiff_decode_batch_bytes_ex(const uint8_t* files, long long files_bytes, const int64_t* file_ranges, int n_files, int deflate);
+/* Tiled files (TileWidth, TileLength, TileOffsets, TileByteCounts: tags 322 to 325; what Bio-Formats / OME-TIFF, QuPath, libvips and
+ * tifffile with tile= write) on the device, all opt-in.  ecseg_set_option(h, "tiff_tiled_on_device", 1) (default 0): ecseg_tiff_decode
+ * and ecseg_tiff_decode_batch on that handle take a tiled file whose tile extents are positive multiples of 16 (of at most 2^20),
+ * chunky (or one sample per pixel), 8 or 16 unsigned bits, uncompressed or LZW - Deflate with "tiff_deflate_on_device" on as well -,
+ * predictor 1 or 2, without strip tags, with a tile table entry for each of its ceil(H / TileLength) * ceil(W / TileWidth) tiles and
+ * tiles below 2 GiB.  Every other tiled file stays ECSEG_E_UNSUPPORTED (BigTIFF, PackBits tiles, planar RGB, float samples, a short
+ * tile table, strip and tile tags together), as does every tiled file with the option off.  A tile is a strip of the batch grid - a
+ * wave per tile, beside the strips of other files in the same launch - whose stream decodes into a staging slot of one tile in the
+ * call arena; tiffb_untile_kernel (csrc/tiff_untile.h) then puts every tile row in its place in the raster: byte order, the horizontal
+ * predictor restarting at each tile's first column, the padding of right and bottom edge tiles dropped.  Uncompressed tiles have no
+ * slot and are placed from the file image.
+ *   The oracle is the Python reader (image_io.read_tiff), the one reader of tiled files so far: ECSEG_OK with its samples, or
+ * ECSEG_E_INVALID where it raises on a tile's stream (a corrupt LZW stream; a Deflate stream that is corrupt, cut short or empty).
+ * Like that reader's slice, a tile's bytes are clamped to the file: an offset behind the file or a count that leaves it is a shorter
+ * or empty stream - zeros for an LZW or uncompressed tile, ECSEG_E_INVALID for a Deflate one - not an error of its own.  (One
+ * difference remains, in the inflate routine shared with strips: a Deflate stream that gave the whole tile and ends inside its
+ * trailer is taken, where zlib.decompress refuses it.)  ecseg_meta_segment_tiffs does not read the option.
+ *   The handle-free functions get the switch as `tiled` beside `deflate` (both 0: the answers of the functions without a suffix).
+ * A tiled file counts in the two routing rules only from a measured tile count on (csrc/tiff_parse.h; tools/time_tiff_decode.py
+ * --tiled).  That table is NOT MEASURED yet: the rules answer 0 for every tiled file and every set of them, and only
+ * an explicit ecseg_tiff_decode / ecseg_tiff_decode_batch call decodes one on the device.  ecseg_tiff_decode_batch_bytes_ex2: the
+ * arena bytes with tiled files taken - the staging slots of their compressed tiles and a 32-byte table row per tiled file on top. */
+int ecseg_tiff_decode_routes_ex2(const uint8_t* file, long long n_bytes, int deflate, int tiled);
+int ecseg_tiff_decode_batch_routes_ex2(const uint8_t* files, long long files_bytes, const int64_t* file_ranges, int n_files, int deflate, int tiled);
+int ecseg_tiff_decode_batch_counts_ex2(const uint8_t* file, long long n_bytes, int deflate, int tiled);
+long long ecseg_tiff_decode_batch_bytes_ex2(const uint8_t* files, long long files_bytes, const int64_t* file_ranges, int n_files, int deflate, int tiled);
 
 /* ---- label PNG files encoded on the device ----------------------------------------------------------------------------------- */
 /* The file ecseg_png_write_labels would write for each of n_img label images, byte for byte (signature, IHDR, one IDAT, IEND), as

@@ -3,6 +3,7 @@
     python tools/time_tiff_decode.py [--passes 5] [--limit 120]
     python tools/time_tiff_decode.py --batch [--passes 5] [--limit 300] [--ks 1,2,4,8,16,32]
     python tools/time_tiff_decode.py --deflate [--batch] ...
+    python tools/time_tiff_decode.py --tiled [--batch] [--deflate] ...
 
 A 1040 x 1392 RGB scene of the stat_fish generator (tests/stat_fish_cases.py ``full_size_scene``) is written with LZW and the
 horizontal predictor at 1, 5, 15, 64 and 1040 rows per strip, and once uncompressed.  Per file: the host reader from the page
@@ -28,6 +29,15 @@ files at 1, 5 and 15 rows per strip - 15 rows are 62640 decoded bytes, the strip
 batches of them and of the stat_fish pair (the mask a Deflate file of 208 strips).  The host side is ecseg_tiff_read, which inflates
 with zlib on one thread.  A single file wins, too, only where the device call's maximum is below the host's minimum; the Deflate
 thresholds of csrc/tiff_parse.h are the smallest strip counts that win (none: the rules never send a Deflate file on their own).
+
+--tiled: the table for tiled files (handle option tiff_tiled_on_device; tiffb_untile_kernel): the same scene written by the tests' tile
+writer (tests/tiff_tiles_cases.py) with square tiles of 16, 64, 256 and 512 pixels, LZW with the horizontal predictor, and with --deflate
+zlib level 6 instead.  The yardstick is what reads such a file today, ``image_io.imread(path)`` without a handle (the pure-Python
+reader, tile after tile); the device side is ``Handle.tiff_decode`` with the option on - with --batch ``imread_many`` over k = --ks such
+scenes with only the rule's verdict replaced.  Every cell is a child process of its own under --limit seconds; median (min - max); a
+cell wins only where the device's maximum is below the host's minimum, and the thresholds of csrc/tiff_parse.h
+(TIFF_TILED_DEVICE_MIN_TILES, TIFF_TILED_BATCH_DEVICE_MIN_TILES) are the smallest measured tile counts that win - a tile size that was
+not measured is never counted.
 """
 import argparse
 import json
@@ -202,6 +212,77 @@ def batch_one(plan, k, passes, deflate=False):
     print(json.dumps(out), flush=True)
 
 
+TILE_SIZES = (16, 64, 256, 512)
+
+
+def write_tiled(folder, tile, seed, deflate):
+    import stat_fish_cases as cases
+    import tiff_tiles_cases as tc
+    img, _ = cases.full_size_scene(seed)
+    path = os.path.join(folder, 'tile%d_%s_%d.tif' % (tile, 'zip' if deflate else 'lzw', seed))
+    with open(path, 'wb') as f:
+        f.write(tc.tiled_tiff(np.ascontiguousarray(img), tile, tile, 8 if deflate else 5, 2))
+    return path, -(-img.shape[0] // tile) * -(-img.shape[1] // tile)
+
+
+def tiled_one(tile, k, passes, deflate, batch):
+    """The child: k scenes at one tile size, read by image_io.imread without a handle and on the device -> one JSON line."""
+    from ecseg_amd import image_io
+    from ecseg_amd._lib import Handle
+    with tempfile.TemporaryDirectory() as tmp:
+        written = [write_tiled(tmp, tile, 100 + j, deflate) for j in range(k)]
+        paths, tiles = [p for p, _ in written], sum(n for _, n in written)
+        datas = [open(p, 'rb').read() for p in paths]
+        host = []
+        for rep in range(passes + 1):
+            t0 = time.perf_counter()
+            want = [image_io.imread(p) for p in paths]
+            if rep:
+                host.append((time.perf_counter() - t0) * 1e3)
+        gpu = Handle(0)
+        gpu.set_option('tiff_tiled_on_device', 1)
+        gpu.set_option('tiff_deflate_on_device', int(deflate))
+        if batch:
+            goes, _ = image_io.tiff_batch_goes_to_device(datas, deflate=deflate, tiled=True)
+            rule = image_io.tiff_batch_goes_to_device            # the rule's questions are asked and timed, only the verdict is replaced
+            image_io.tiff_batch_goes_to_device = lambda datas, deflate=False, tiled=False: (rule(datas, deflate=deflate, tiled=tiled) and True, [True] * len(datas))
+        else:
+            goes = image_io.tiff_goes_to_device(datas[0], deflate=deflate, tiled=True)
+        call, kern = [], []
+        for rep in range(passes + 1):
+            t0 = time.perf_counter()
+            got = image_io.imread_many(paths, handle=gpu, deflate=deflate) if batch else [gpu.tiff_decode(datas[0])]
+            if rep:
+                call.append((time.perf_counter() - t0) * 1e3)
+                kern.append(gpu.timings()['count'])
+        assert all(isinstance(g, np.ndarray) and g.dtype == w.dtype and np.array_equal(g, w) for g, w in zip(got, want))
+        out = dict(tile=tile, k=k, tiles=tiles, codec='zip' if deflate else 'lzw', bytes=sum(len(d) for d in datas), rule_sends_it=bool(goes),
+                   host_imread_ms=stats(host), device_call_ms=stats(call), device_kernel_ms=stats(kern))
+        out['wins'] = out['device_call_ms']['max'] < out['host_imread_ms']['min']
+        gpu.close()
+    print(json.dumps(out), flush=True)
+
+
+def tiled_main(a):
+    rows = []
+    for tile in TILE_SIZES:
+        for k in (a.ks if a.batch else [1]):
+            cell = dict(tile=tile, k=k)
+            try:
+                r = subprocess.run([sys.executable, os.path.abspath(__file__), '--tiled-one', '%d:%d' % (tile, k), '--passes', str(a.passes)] +
+                                   (['--deflate'] if a.deflate else []) + (['--batch'] if a.batch else []), capture_output=True, text=True, timeout=a.limit)
+            except subprocess.TimeoutExpired:
+                print(json.dumps(dict(cell, device='ended at the time limit of %g s' % a.limit)), flush=True)
+                return                                       # a hung device run: nothing more is started on the device
+            if r.returncode != 0:
+                print(json.dumps(dict(cell, failed=r.returncode, stderr=r.stderr[-2000:])), flush=True)
+                return
+            line = r.stdout.strip().splitlines()[-1]
+            print(line, flush=True)
+            rows.append(json.loads(line))
+    print(json.dumps(dict(cells_where_the_device_maximum_is_below_the_host_minimum=[[r['tile'], r['k'], r['tiles']] for r in rows if r['wins']])))
+
+
 def batch_main(a):
     rows = []
     for plan in BATCH_PLANS:
@@ -231,8 +312,15 @@ def main():
     ap.add_argument('--batch', action='store_true')
     ap.add_argument('--deflate', action='store_true')
     ap.add_argument('--batch-one')
+    ap.add_argument('--tiled', action='store_true')
+    ap.add_argument('--tiled-one')
     ap.add_argument('--ks', type=lambda v: [int(x) for x in v.split(',')], default=[1, 2, 4, 8, 16, 32])
     a = ap.parse_args()
+    if a.tiled_one:
+        tile, k = a.tiled_one.split(':')
+        return tiled_one(int(tile), int(k), a.passes, a.deflate, a.batch)
+    if a.tiled:
+        return tiled_main(a)
     if a.one:
         return one(a.one, a.passes, a.deflate)
     if a.batch_one:
