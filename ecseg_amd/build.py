@@ -6,7 +6,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(HERE, 'libecseg_hip.so')
-SOURCES = ['api.hip', 'filter_layout.hip', 'model_load.hip', 'plan_run.hip', 'segment.hip', 'drivers_post.hip', 'drivers_interseg.hip', 'drivers_fish.hip', 'drivers_files.hip', 'drivers_nuset.hip','unet_kernels.hip', 'layer_kernels.hip', 'wino4_kernel.hip', 'wino4s_kernel.hip', 'wino4r_kernel.hip', 'convs_kernel.hip', 'wino16_kernel.hip', 'ccl_kernels.hip', 'meta_inference_kernels.hip', 'overlay_kernels.hip', 'stitch_preprocess_kernels.hip', 'interseg_kernels.hip', 'iseg_classify_kernels.hip', 'fishdist_kernels.hip', 'fishspot_kernels.hip', 'mincut_kernels.hip', 'mincut_centers_kernels.hip', 'nuset_kernels.hip', 'watershed_kernels.hip', 'rescale_kernels.hip', 'tiff_kernels.hip', 'tiff_decode_kernels.hip', 'png_kernels.hip', 'png_gray_kernels.hip', 'host_codec.cpp', 'host_io.cpp', 'comm.hip']
+SOURCES = ['api.hip', 'filter_layout.hip', 'model_load.hip', 'plan_run.hip', 'segment.hip', 'drivers_post.hip', 'drivers_interseg.hip', 'drivers_fish.hip', 'drivers_files.hip', 'drivers_nuset.hip', 'conv_mfma_kernel.hip', 'wino2_kernel.hip', 'conv_direct_kernels.hip', 'layer_kernels.hip', 'wino4_kernel.hip', 'wino4s_kernel.hip', 'wino4r_kernel.hip', 'convs_kernel.hip', 'wino16_kernel.hip', 'ccl_kernels.hip', 'meta_inference_kernels.hip', 'overlay_kernels.hip', 'stitch_preprocess_kernels.hip', 'interseg_kernels.hip', 'iseg_classify_kernels.hip', 'fishdist_kernels.hip', 'fishspot_kernels.hip', 'mincut_kernels.hip', 'mincut_centers_kernels.hip', 'nuset_kernels.hip', 'watershed_kernels.hip', 'rescale_kernels.hip', 'tiff_kernels.hip', 'tiff_decode_kernels.hip', 'png_kernels.hip', 'png_gray_kernels.hip', 'host_codec.cpp', 'host_io.cpp', 'comm.hip']
 # packed f32 VALU ops stall the SIMD beside MFMAs: keep the transform arithmetic of the Winograd kernels scalar
 EXTRA_FLAGS = {'wino4_kernel.hip': ['-fno-slp-vectorize'], 'wino4s_kernel.hip': ['-fno-slp-vectorize'], 'wino4r_kernel.hip': ['-fno-slp-vectorize']}
 # the proposal layer restates TensorFlow's float32 arithmetic op by op: a * b + c must round twice there

@@ -91,14 +91,27 @@ constexpr double W4_PA = ECSEG_W4_PA, W4_PB = ECSEG_W4_PB;
 inline long wt_chunk_pitch(int np_total) { return (long)2 * np_total * 4 + 32; }
 inline long wt_tap_pitch(int np_total, int chunks) { return wt_chunk_pitch(np_total) * chunks + 96; }
 
-// ---- launchers implemented in unet_kernels.hip --------------------------------------------------------------
+// Blocks of 256 threads for a grid-stride kernel over `total` work items: never 0, capped at 65536 * 16
+inline unsigned grid_for(size_t total) {
+    size_t b = (total + 255) / 256;
+    if (b > 65536 * 16) b = 65536 * 16;
+    return (unsigned)(b ? b : 1);
+}
+
+// ---- conv_mfma_kernel.hip: implicit-GEMM convolutions on the fp32 matrix cores ---------------------------------
 hipError_t launch_conv_mfma(const ConvParams& p, hipStream_t s);
 bool       conv_mfma_supported(const ConvParams& p);
 int        conv_mfma_ntile(int cout);   // N tile (32 | 64 | 128) used for a given Cout
-// Winograd F(2x2,3x3) variant for 3x3 / stride 1 / pad 1 convolutions; p.wt = 16 transformed taps, p.coutp padded to
-// conv_wino_ntile()
+// Conv2D with any taps / stride / dilation on the matrix cores; p.wt = relayout_conv image, p.coutp padded to conv_mfma_ntile()
+hipError_t launch_conv_mfma_tap(const ConvParams& p, int dilation, hipStream_t s);
+bool       conv_mfma_tap_supported(const ConvParams& p);
+
+// ---- wino2_kernel.hip: Winograd F(2x2,3x3) for 3x3 / stride 1 / pad 1 convolutions; p.wt = 16 transformed taps, p.coutp padded
+// ---- to conv_wino_ntile() --------------------------------------------------------------------------------------
 hipError_t launch_conv_wino(const ConvParams& p, hipStream_t s);
 int        conv_wino_ntile(int cout);
+
+// ---- the other matrix-core convolutions, one file each -----------------------------------------------------------
 // Winograd F(2x2,3x3) for 16 / 32 input and output channels on 16x16x4 MFMAs (wino16_kernel.hip); p.wt = image written by
 // relayout_wino16 (filter_layout.hip)
 hipError_t launch_conv_wino16(const ConvParams& p, hipStream_t s);
@@ -127,41 +140,37 @@ bool       convs_supported(const ConvParams& p);
 size_t     convs_image_bytes(int cin, int np);
 hipError_t launch_convs_filter(const float* wt_fp32, void* dst, int cin, int np, hipStream_t s);
 
+// ---- conv_direct_kernels.hip: convolutions off the matrix cores ------------------------------------------------------
 hipError_t launch_conv_small_cin(const TView& in, const TView& out, const float* w_hwio, const float* bias, int n,
                                  int R, int S, int pad_top, int pad_left, int act, float alpha, hipStream_t s);
 hipError_t launch_conv_head(const TView& in, const TView& out, const float* w_io, const float* bias, int n, int act,
                             float alpha, hipStream_t s);
-hipError_t launch_conv_generic(const TView& in, const TView& out, const float* w_hwio, const float* bias, int n,
-                               int R, int S, int stride, int pad_top, int pad_left, int act, float alpha, hipStream_t s);
+// scalar kernel: vertical / horizontal stride and dilation rate may differ (dilation rates below 1 count as 1)
+hipError_t launch_conv_generic(const TView& in, const TView& out, const float* w_hwio, const float* bias, int n, int R, int S,
+                               int stride, int stride_x, int dilation, int dilation_x, int pad_top, int pad_left, int act, float alpha,
+                               hipStream_t s);
 hipError_t launch_convt_generic(const TView& in, const TView& out, const float* w_hwoi, const float* bias, int n,
                                 int R, int S, int stride, int crop_top, int crop_left, int act, float alpha,
                                 hipStream_t s);
+// DepthwiseConv2D: kernel (kh, kw, cin, mult), output channel = input channel * mult + j
+hipError_t launch_dwconv(const TView& in, const TView& out, const float* w, const float* bias, int n, int kh, int kw, int stride,
+                         int dilation, int pad_top, int pad_left, int mult, int act, float alpha, hipStream_t s);
+
+// ---- layer_kernels.hip: everything that is not a convolution -----------------------------------------------------
 hipError_t launch_maxpool(const TView& in, const TView& out, int n, int kh, int kw, int stride, int mode, hipStream_t s);
+hipError_t launch_pool_pad(const TView& in, const TView& out, int n, int kh, int kw, int stride, int pad_top, int pad_left, int mode,
+                           hipStream_t s);
 hipError_t launch_global_pool(const TView& in, const TView& out, int n, int mode, hipStream_t s);
 hipError_t launch_upsample(const TView& in, const TView& out, int n, int factor, int mode, hipStream_t s);
 hipError_t launch_affine(const TView& in, const TView& out, const float* scale, const float* shift, int n, int act,
                          float alpha, hipStream_t s);
-hipError_t launch_add(const TView& a, const TView& b, const TView& out, int n, int act, float alpha, hipStream_t s);
-hipError_t launch_copy(const TView& in, const TView& out, int n, int off_y, int off_x, hipStream_t s);
-hipError_t launch_softmax(const TView& in, const TView& out, int n, hipStream_t s);
-hipError_t launch_u8_to_f32(const uint8_t* in, float* out, size_t count, hipStream_t s);
-
-// ---- launchers implemented in layer_kernels.hip (the wider Keras vocabulary) -------------------------------------
-// Conv2D with any taps / stride / dilation on the matrix cores; p.wt = relayout_conv image, p.coutp padded to conv_mfma_ntile()
-hipError_t launch_conv_mfma_tap(const ConvParams& p, int dilation, hipStream_t s);
-bool       conv_mfma_tap_supported(const ConvParams& p);
-hipError_t launch_conv_generic_dil(const TView& in, const TView& out, const float* w_hwio, const float* bias, int n, int R, int S,
-                                   int stride, int stride_x, int dilation, int dilation_x, int pad_top, int pad_left, int act, float alpha,
-                                   hipStream_t s);       // scalar kernel: vertical / horizontal stride and dilation rate may differ
-// DepthwiseConv2D: kernel (kh, kw, cin, mult), output channel = input channel * mult + j
-hipError_t launch_dwconv(const TView& in, const TView& out, const float* w, const float* bias, int n, int kh, int kw, int stride,
-                         int dilation, int pad_top, int pad_left, int mult, int act, float alpha, hipStream_t s);
 // y = act(a (+) b), mode = ECSEG_BIN_*, extents of 1 broadcast
 hipError_t launch_binary(const TView& a, const TView& b, const TView& out, int n, int mode, int act, float alpha, hipStream_t s);
 hipError_t launch_prelu(const TView& in, const TView& out, const float* slope, int n, int per_element, hipStream_t s);
 hipError_t launch_layernorm(const TView& in, const TView& out, const float* gamma, const float* beta, int n, float eps, hipStream_t s);
-hipError_t launch_pool_pad(const TView& in, const TView& out, int n, int kh, int kw, int stride, int pad_top, int pad_left, int mode,
-                           hipStream_t s);
+hipError_t launch_copy(const TView& in, const TView& out, int n, int off_y, int off_x, hipStream_t s);
+hipError_t launch_softmax(const TView& in, const TView& out, int n, hipStream_t s);
+hipError_t launch_u8_to_f32(const uint8_t* in, float* out, size_t count, hipStream_t s);
 // im2patches_overlap on the device: (n_img, H, W) uint8 -> (n_img * n_pos, 256, 256, 1) float32
 hipError_t launch_tile_patches(const uint8_t* gray, int n_img, int H, int W, const int32_t* pos_yx, int n_pos,
                                float* out, hipStream_t s);

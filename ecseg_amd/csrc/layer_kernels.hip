@@ -1,328 +1,200 @@
-// Kernels of the wider Keras layer vocabulary (round 5): whatever metaseg.h5 / interseg_models/* turn out to contain
-// must load (reference src/utils.py:27-33, src/interseg.py:96-98 call tf.keras.models.load_model on an unknown file).
-//
-//   conv_mfma_tap_kernel   Conv2D with ANY taps / stride / dilation_rate on the fp32 matrix cores (implicit GEMM, the tile of
-//                          every tap staged on its own - dilated taps share no halo worth keeping)
-//   dwconv_kernel          DepthwiseConv2D / the depthwise half of SeparableConv2D / Conv2D(groups = Cin): HBM-bound,
-//                          16-byte channel-quad accesses, LDS-staged halo
-//   binary_kernel          Add / Multiply / Subtract / Maximum / Minimum with broadcasting (squeeze-and-excite x * s)
-//   prelu_kernel, layernorm_kernel, pool_pad_kernel ('same' pooling)
-// NHWC float32 views everywhere (common.h: TView).
+// Every plan-interpreter kernel that is not a convolution, for gfx950 (MI355X): pooling ('valid', 'same', global), up-sampling,
+// affine / activation, binary ops with broadcasting (Add / Multiply / Subtract / Maximum / Minimum), PReLU, LayerNormalization,
+// pad / crop / copy, softmax, and the input side (u8_to_f32, tile_patches).  NHWC float32 views (common.h: TView).
 #include "common.h"
 #include "device_util.h"
 
 namespace ecseg {
 
 // ------------------------------------------------------------------------------------------------------------
-// Implicit-GEMM convolution, tap by tap.  Workgroup = 128 output pixels (TH x TW tile of one patch) x BN output channels,
-// as conv_mfma_kernel (unet_kernels.hip), but the K loop walks (tap, group of KCH 8-channel chunks) and stages, per step,
-// the 128 input pixels THAT tap reads: pixel (oy * stride - pad + r * dil, ox * stride - pad + s * dil).  With a dilation
-// rate of 6 - 18 (ASPP heads) the union of the taps' footprints is (TH + 2 dil) x (TW + 2 dil) pixels of which every tap
-// uses 128: a shared halo would not fit LDS and would be read once per tap anyway.  Input re-reads (R * S times) are served
-// by L2; the MFMA work per staged byte equals the 1x1 kernel's.
-//
-//   M = output pixels (lane & 31 -> pixel of the wave's 32-pixel strip), N = output channels, K = (tap, input channel);
-//   one MFMA (v_mfma_f32_32x32x2_f32) consumes channels {e, 4 + e} of a chunk, so one ds_read_b128 per operand feeds four.
-// LDS: As[kc][half][128 pixels][4 ch], Bs[kc][half][BN][4 ch]; global filter layout = relayout_conv (filter_layout.hip):
-// wt[tap][chunk][half][N padded][4].
+// Element-wise / resampling kernels (HBM-bound; float4 fast path when every view is 16-byte aligned)
 // ------------------------------------------------------------------------------------------------------------
-template <int NT, int TW>
-__global__ __launch_bounds__(256) void conv_mfma_tap_kernel(ConvParams p, int tiles_x, int tiles_y, int nblk_n, int dil) {
-    constexpr int KCH = 4;
-    constexpr int BN = NT * 32;
-    constexpr int B_PER_T = (2 * BN * KCH) / 256;            // = NT
+__device__ __forceinline__ bool view_vec4(const TView& v) {
+    return (v.c % 4 == 0) && (v.cs % 4 == 0) && ((((uintptr_t)v.p) & 15) == 0);
+}
 
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    f32x4* As = reinterpret_cast<f32x4*>(smem);              // [KCH][2][128]
-    f32x4* Bs = As + KCH * 2 * 128;                          // [KCH][2][BN]
-
-    const int tid = threadIdx.x;
-    unsigned bid = xcd_remap(blockIdx.x, gridDim.x);
-    const int nb = bid % nblk_n; bid /= nblk_n;
-    const int tx0 = (bid % tiles_x) * TW; bid /= tiles_x;
-    const int ty0 = (bid % tiles_y) * (128 / TW); bid /= tiles_y;
-    const int img = bid;
-    const int n0 = nb * BN;
-    const int Hin = p.in.h, Win = p.in.w, Cin = p.in.c;
-    const int st = p.stride > 0 ? p.stride : 1;
-    const size_t in_img = (size_t)img * Hin * Win * p.in.cs;
-
-    // this thread's A piece: pixel a_pix of the tile, channel half a_h, for every one of the KCH chunks of a step
-    const int a_pix = tid >> 1, a_h = tid & 1;
-    const int a_iy0 = (ty0 + a_pix / TW) * st - p.pad_top, a_ix0 = (tx0 + a_pix % TW) * st - p.pad_left;
-    const size_t chunk_stride = (size_t)p.wt_chunk_stride, tap_stride = (size_t)p.wt_tap_stride;
-    // B pieces: q = tid + k * 256 over [kc][half][BN]
-    const int ngrp = (p.cin_chunks + KCH - 1) / KCH;
-    const int nsteps = p.R * p.S * ngrp;
-
-    f32x4 a_reg[KCH], b_reg[B_PER_T];
-    auto load_step = [&](int step) {
-        const int tap = step / ngrp, grp = step - tap * ngrp;
-        const int r = tap / p.S, s = tap - r * p.S;
-        const int iy = a_iy0 + r * dil, ix = a_ix0 + s * dil;
-        const bool inside = iy >= 0 && iy < Hin && ix >= 0 && ix < Win;
-        const float* ap = p.in.p + in_img + ((size_t)(inside ? iy : 0) * Win + (inside ? ix : 0)) * p.in.cs + a_h * 4;
+// MaxPooling2D (mode 0) / AveragePooling2D (mode 1), 'valid'
+template <bool VEC>
+__global__ __launch_bounds__(256) void maxpool_kernel(TView in, TView out, size_t total, int kh, int kw, int stride, int mode) {
+    constexpr int V = VEC ? 4 : 1;
+    const int cq = out.c / V;
+    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x) {
+        const int c = (int)(t % cq) * V;
+        size_t pix = t / cq;
+        const int ox = (int)(pix % out.w); pix /= out.w;
+        const int oy = (int)(pix % out.h);
+        const size_t img = pix / out.h;
+        float m[V];
 #pragma unroll
-        for (int kc = 0; kc < KCH; ++kc) {
-            const int ch = (grp * KCH + kc) * 8 + a_h * 4;
-            f32x4 v = {0.f, 0.f, 0.f, 0.f};
-            if (inside && ch < Cin) v = *reinterpret_cast<const f32x4*>(ap + (grp * KCH + kc) * 8);
-            a_reg[kc] = v;
-        }
+        for (int e = 0; e < V; ++e) m[e] = mode ? 0.f : -INFINITY;
+        for (int r = 0; r < kh; ++r)
+            for (int s = 0; s < kw; ++s) {
+                const float* ip = in.p + ((img * in.h + (oy * stride + r)) * in.w + (ox * stride + s)) * in.cs + c;
+                if (VEC) {
+                    const f32x4 v = *reinterpret_cast<const f32x4*>(ip);
 #pragma unroll
-        for (int k = 0; k < B_PER_T; ++k) {
-            const int q = tid + k * 256;
-            const int kc = q / (2 * BN), rem = q - kc * 2 * BN;
-            const int h = rem / BN, j = rem - h * BN;
-            const int chunk = grp * KCH + kc;
-            f32x4 v = {0.f, 0.f, 0.f, 0.f};
-            if (chunk < p.cin_chunks)
-                v = *reinterpret_cast<const f32x4*>(p.wt + tap * tap_stride + chunk * chunk_stride + ((size_t)h * p.coutp + n0 + j) * 4);
-            b_reg[k] = v;
-        }
-    };
-    auto store_step = [&]() {
-#pragma unroll
-        for (int kc = 0; kc < KCH; ++kc) As[(kc * 2 + a_h) * 128 + a_pix] = a_reg[kc];
-#pragma unroll
-        for (int k = 0; k < B_PER_T; ++k) Bs[tid + k * 256] = b_reg[k];
-    };
-
-    const int lane = tid & 63, wave = tid >> 6;
-    const int li = lane & 31, lh = lane >> 5;
-    const f32x4* Ap = As + lh * 128 + wave * 32 + li;        // (row-major TH x TW tile: pixel index = wave * 32 + li for both tile shapes)
-    const f32x4* Bp = Bs + lh * BN + li;
-
-    f32x16 acc[NT];
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[nt][e] = 0.f;
-
-    load_step(0);
-    for (int step = 0; step < nsteps; ++step) {
-        store_step();
-        __syncthreads();
-        if (step + 1 < nsteps) load_step(step + 1);
-        const int grp = step % ngrp;
-        const int live = min(KCH, p.cin_chunks - grp * KCH);   // chunks of this step that exist (uniform)
-#pragma unroll
-        for (int kc = 0; kc < KCH; ++kc) {
-            if (kc < live) {
-                const f32x4 a = Ap[kc * 2 * 128];
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt) {
-                    const f32x4 b = Bp[kc * 2 * BN + nt * 32];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) acc[nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[e], b[e], acc[nt], 0, 0, 0);
+                    for (int e = 0; e < V; ++e) m[e] = mode ? m[e] + v[e] : fmaxf(m[e], v[e]);
+                } else {
+                    m[0] = mode ? m[0] + ip[0] : fmaxf(m[0], ip[0]);
                 }
             }
+        if (mode) {
+            const float inv = 1.f / (float)(kh * kw);
+#pragma unroll
+            for (int e = 0; e < V; ++e) m[e] *= inv;
         }
-        __syncthreads();
-    }
-
-    // output stage: every wave turns its 32 x 32 accumulator tile around through a private 4-KB LDS tile so that a lane
-    // finishes 4 consecutive channels of one pixel (bias, activation, one 16-byte store)
-    const int Hout = p.out.h, Wout = p.out.w, Cout = p.out.c;
-    float* Xs = reinterpret_cast<float*>(smem) + wave * 1024;
-    const bool vec_ok = (p.out.cs % 4 == 0) && (Cout % 4 == 0) && ((reinterpret_cast<uintptr_t>(p.out.p) & 15) == 0);
-    const int quad = lane & 7;
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) {
-        const int co = n0 + nt * 32 + 4 * quad;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) Xs[((e & 3) + 8 * (e >> 2) + 4 * lh) * 32 + li] = acc[nt][e];
-        f32x4 bv = {0.f, 0.f, 0.f, 0.f};
-        if (p.bias != nullptr) {
-#pragma unroll
-            for (int c = 0; c < 4; ++c) if (co + c < Cout) bv[c] = p.bias[co + c];
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int row = (lane >> 3) + 8 * r;               // pixel inside the wave's 32-pixel strip
-            f32x4 v = *reinterpret_cast<const f32x4*>(Xs + row * 32 + 4 * quad) + bv;
-            v = apply_act4(v, p.act, p.alpha);
-            const int pix = wave * 32 + row;
-            const int oy = ty0 + pix / TW, ox = tx0 + pix % TW;
-            if (oy < Hout && ox < Wout) {
-                float* o = p.out.p + (((size_t)img * Hout + oy) * Wout + ox) * p.out.cs + co;
-                if (vec_ok && co + 3 < Cout) *reinterpret_cast<f32x4*>(o) = v;
-                else {
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) if (co + c < Cout) o[c] = v[c];
-                }
-            }
+        float* op = out.p + ((img * out.h + oy) * out.w + ox) * out.cs + c;
+        if (VEC) {
+            f32x4 o; o[0] = m[0]; o[1] = m[V > 1 ? 1 : 0]; o[2] = m[V > 2 ? 2 : 0]; o[3] = m[V > 3 ? 3 : 0];
+            *reinterpret_cast<f32x4*>(op) = o;
+        } else {
+            op[0] = m[0];
         }
     }
 }
 
-bool conv_mfma_tap_supported(const ConvParams& p) {
-    return (p.in.cs % 4 == 0) && (p.in.c % 4 == 0) && ((((uintptr_t)p.in.p) & 15) == 0) && p.in.c >= 8 && p.R >= 1 && p.S >= 1;
-}
-
-template <int NT, int TW>
-static hipError_t launch_conv_mfma_tap_t(const ConvParams& p, int dil, hipStream_t s) {
-    constexpr int TH = 128 / TW, BN = NT * 32;
-    const int tiles_x = (p.out.w + TW - 1) / TW, tiles_y = (p.out.h + TH - 1) / TH;
-    const int nblk_n = p.coutp / BN;
-    size_t lds = (size_t)4 * (2 * 128 + 2 * BN) * 16;
-    if (lds < 4 * 4096) lds = 4 * 4096;
-    const size_t grid = (size_t)p.n * tiles_x * tiles_y * nblk_n;
-    if (grid == 0) return hipSuccess;
-    if (grid > 0x7fffffffull) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((conv_mfma_tap_kernel<NT, TW>), dim3((unsigned)grid), dim3(256), lds, s, p, tiles_x, tiles_y, nblk_n, dil);
+hipError_t launch_maxpool(const TView& in, const TView& out, int n, int kh, int kw, int stride, int mode, hipStream_t s) {
+    const bool vec = (in.c % 4 == 0) && (in.cs % 4 == 0) && (out.cs % 4 == 0) && ((((uintptr_t)in.p) | ((uintptr_t)out.p)) & 15) == 0;
+    const size_t total = (size_t)n * out.h * out.w * (vec ? out.c / 4 : out.c);
+    if (!total) return hipSuccess;
+    if (vec) hipLaunchKernelGGL(maxpool_kernel<true>, dim3(grid_for(total)), dim3(256), 0, s, in, out, total, kh, kw, stride, mode);
+    else hipLaunchKernelGGL(maxpool_kernel<false>, dim3(grid_for(total)), dim3(256), 0, s, in, out, total, kh, kw, stride, mode);
     return hipGetLastError();
 }
 
-hipError_t launch_conv_mfma_tap(const ConvParams& p, int dil, hipStream_t s) {
-    if (dil < 1) dil = 1;
-    const int bn = conv_mfma_ntile(p.out.c);
-    if (p.coutp % bn != 0) return hipErrorInvalidValue;
-    const bool wide = p.out.w >= 32;
-    if (bn == 128) return wide ? launch_conv_mfma_tap_t<4, 32>(p, dil, s) : launch_conv_mfma_tap_t<4, 16>(p, dil, s);
-    if (bn == 64) return wide ? launch_conv_mfma_tap_t<2, 32>(p, dil, s) : launch_conv_mfma_tap_t<2, 16>(p, dil, s);
-    return wide ? launch_conv_mfma_tap_t<1, 32>(p, dil, s) : launch_conv_mfma_tap_t<1, 16>(p, dil, s);
-}
-
-// ------------------------------------------------------------------------------------------------------------
-// DepthwiseConv2D (depth multiplier 1, channels % 4 == 0): HBM-bound - every input value is used kh * kw times by
-// neighbouring outputs of ITS channel only, so the work is one pass over the tensor if the halo is kept on chip.
-// Workgroup = DW_TY x DW_TX output pixels x CQ channel quads (<= 64 channels): the input halo of the tile is staged in
-// LDS with 16-byte loads (consecutive lanes = consecutive channel quads of a pixel: 256 contiguous bytes per pixel at 64
-// channels), every work item then reads its kh * kw taps from LDS (consecutive lanes = consecutive 16-byte slots:
-// conflict-free) and writes 4 channels with one 16-byte store.  Filter [tap][channel] (Keras' (kh, kw, cin, 1)) in LDS too.
-// LDS == false: the same arithmetic straight from global memory (L2), for halos that do not fit 64 KB.
-// ------------------------------------------------------------------------------------------------------------
-constexpr int DW_TY = 8, DW_TX = 8;
-
-template <bool LDS>
-__global__ __launch_bounds__(256) void dwconv_kernel(TView in, TView out, const float* __restrict__ w, const float* __restrict__ bias,
-                                                     int kh, int kw, int stride, int dil, int pad_top, int pad_left, int act,
-                                                     float alpha, int tiles_x, int tiles_y, int cq, int nblk_c) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int tid = threadIdx.x;
-    unsigned bid = blockIdx.x;
-    const int cb = bid % nblk_c; bid /= nblk_c;
-    const int bx = bid % tiles_x; bid /= tiles_x;
-    const int by = bid % tiles_y; bid /= tiles_y;
-    const size_t img = bid;
-    const int q0 = cb * cq;                                   // first channel quad of this workgroup
-    const int nq = min(cq, in.c / 4 - q0);
-    const int oy0 = by * DW_TY, ox0 = bx * DW_TX;
-    const int hh = (DW_TY - 1) * stride + (kh - 1) * dil + 1, hw = (DW_TX - 1) * stride + (kw - 1) * dil + 1;
-    const int iy0 = oy0 * stride - pad_top, ix0 = ox0 * stride - pad_left;
-    f32x4* Hs = reinterpret_cast<f32x4*>(smem);              // [hh][hw][cq]
-    f32x4* Ws = Hs + (LDS ? hh * hw * cq : 0);               // [kh * kw][cq]
-    const float* ip = in.p + img * (size_t)in.h * in.w * in.cs + q0 * 4;
-    for (int t = tid; t < kh * kw * cq; t += 256) {
-        const int tap = t / cq, q = t - tap * cq;
-        f32x4 v = {0.f, 0.f, 0.f, 0.f};
-        if (q < nq) v = *reinterpret_cast<const f32x4*>(w + (size_t)tap * in.c + (q0 + q) * 4);
-        Ws[t] = v;
-    }
-    if (LDS) {
-        for (int t = tid; t < hh * hw * cq; t += 256) {
-            const int q = t % cq, pix = t / cq;
-            const int hy = pix / hw, hx = pix - hy * hw;
-            const int iy = iy0 + hy, ix = ix0 + hx;
-            f32x4 v = {0.f, 0.f, 0.f, 0.f};
-            if (q < nq && iy >= 0 && iy < in.h && ix >= 0 && ix < in.w)
-                v = *reinterpret_cast<const f32x4*>(ip + ((size_t)iy * in.w + ix) * in.cs + q * 4);
-            Hs[t] = v;
-        }
-    }
-    __syncthreads();
-    for (int t = tid; t < DW_TY * DW_TX * cq; t += 256) {
-        const int q = t % cq, pix = t / cq;
-        const int py = pix / DW_TX, px = pix - py * DW_TX;
-        const int oy = oy0 + py, ox = ox0 + px;
-        if (q >= nq || oy >= out.h || ox >= out.w) continue;
-        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-        if (bias != nullptr) acc = *reinterpret_cast<const f32x4*>(bias + (q0 + q) * 4);
-        for (int r = 0; r < kh; ++r)
-            for (int s = 0; s < kw; ++s) {
-                f32x4 v;
-                if (LDS) v = Hs[((py * stride + r * dil) * hw + px * stride + s * dil) * cq + q];
-                else {
-                    const int iy = iy0 + py * stride + r * dil, ix = ix0 + px * stride + s * dil;
-                    v = f32x4{0.f, 0.f, 0.f, 0.f};
-                    if (iy >= 0 && iy < in.h && ix >= 0 && ix < in.w) v = *reinterpret_cast<const f32x4*>(ip + ((size_t)iy * in.w + ix) * in.cs + q * 4);
-                }
-                const f32x4 k4 = Ws[(r * kw + s) * cq + q];
-#pragma unroll
-                for (int c = 0; c < 4; ++c) acc[c] = fmaf(v[c], k4[c], acc[c]);
-            }
-        acc = apply_act_ext4(acc, act, alpha);
-        *reinterpret_cast<f32x4*>(out.p + ((img * out.h + oy) * out.w + ox) * out.cs + (q0 + q) * 4) = acc;
-    }
-}
-
-// Any depth multiplier / channel count / alignment: thread = (output pixel, output channel); kernel (kh, kw, cin, mult)
-__global__ __launch_bounds__(256) void dwconv_generic_kernel(TView in, TView out, const float* __restrict__ w, const float* __restrict__ bias,
-                                                             size_t total, int kh, int kw, int stride, int dil, int pad_top, int pad_left,
-                                                             int mult, int act, float alpha) {
+// MaxPooling2D / AveragePooling2D with padding='same': the window starts (pad_top, pad_left) before the input; the maximum
+// and the average run over the pixels that lie inside it (TensorFlow's average excludes the padding from the divisor)
+__global__ __launch_bounds__(256) void pool_pad_kernel(TView in, TView out, size_t total, int kh, int kw, int stride, int pad_top,
+                                                       int pad_left, int mode) {
     for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x) {
-        const int co = (int)(t % out.c);
+        const int c = (int)(t % out.c);
         size_t pix = t / out.c;
         const int ox = (int)(pix % out.w); pix /= out.w;
         const int oy = (int)(pix % out.h);
         const size_t img = pix / out.h;
-        const int ci = co / mult;
-        float acc = bias ? bias[co] : 0.f;
+        float m = mode ? 0.f : -INFINITY;
+        int cnt = 0;
         for (int r = 0; r < kh; ++r) {
-            const int iy = oy * stride - pad_top + r * dil;
+            const int iy = oy * stride - pad_top + r;
             if (iy < 0 || iy >= in.h) continue;
             for (int s = 0; s < kw; ++s) {
-                const int ix = ox * stride - pad_left + s * dil;
+                const int ix = ox * stride - pad_left + s;
                 if (ix < 0 || ix >= in.w) continue;
-                acc = fmaf(in.p[((img * in.h + iy) * in.w + ix) * in.cs + ci], w[(size_t)(r * kw + s) * out.c + co], acc);
+                const float v = in.p[((img * in.h + iy) * in.w + ix) * in.cs + c];
+                m = mode ? m + v : fmaxf(m, v);
+                ++cnt;
             }
         }
-        out.p[((img * out.h + oy) * out.w + ox) * out.cs + co] = apply_act_ext(acc, act, alpha);
+        if (mode) m = cnt ? m / (float)cnt : 0.f;
+        out.p[((img * out.h + oy) * out.w + ox) * out.cs + c] = m;
     }
 }
 
-static unsigned lk_grid_for(size_t total) {
-    size_t b = (total + 255) / 256;
-    if (b > 65536 * 16) b = 65536 * 16;
-    return (unsigned)(b ? b : 1);
+hipError_t launch_pool_pad(const TView& in, const TView& out, int n, int kh, int kw, int stride, int pad_top, int pad_left, int mode,
+                           hipStream_t s) {
+    const size_t total = (size_t)n * out.h * out.w * out.c;
+    if (!total) return hipSuccess;
+    hipLaunchKernelGGL(pool_pad_kernel, dim3(grid_for(total)), dim3(256), 0, s, in, out, total, kh, kw, stride, pad_top, pad_left, mode);
+    return hipGetLastError();
 }
 
-hipError_t launch_dwconv(const TView& in, const TView& out, const float* w, const float* bias, int n, int kh, int kw, int stride,
-                         int dil, int pad_top, int pad_left, int mult, int act, float alpha, hipStream_t s) {
+// GlobalAveragePooling2D (mode 1) / GlobalMaxPooling2D (mode 0): workgroup = (patch, 64 channels); lane = channel
+// (coalesced 256-B rows), the four waves split the pixels and meet in LDS.  Fixed summation order: run-to-run identical.
+__global__ __launch_bounds__(256) void global_pool_kernel(TView in, TView out, int mode) {
+    __shared__ float part[4][64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int c = blockIdx.x * 64 + lane;
+    const size_t img = blockIdx.y;
+    const int npx = in.h * in.w;
+    float acc = mode ? 0.f : -INFINITY;
+    if (c < in.c) {
+        const float* ip = in.p + img * (size_t)npx * in.cs + c;
+        for (int q = wave; q < npx; q += 4) {
+            const float v = ip[(size_t)q * in.cs];
+            acc = mode ? acc + v : fmaxf(acc, v);
+        }
+    }
+    part[wave][lane] = acc;
+    __syncthreads();
+    if (wave == 0 && c < in.c) {
+        float r = part[0][lane];
+#pragma unroll
+        for (int k = 1; k < 4; ++k) r = mode ? r + part[k][lane] : fmaxf(r, part[k][lane]);
+        if (mode) r *= 1.f / (float)npx;
+        out.p[img * (size_t)out.cs + c] = r;
+    }
+}
+
+hipError_t launch_global_pool(const TView& in, const TView& out, int n, int mode, hipStream_t s) {
     if (n <= 0) return hipSuccess;
-    if (dil < 1) dil = 1;
-    const bool vec = mult == 1 && in.c % 4 == 0 && in.cs % 4 == 0 && out.cs % 4 == 0 && out.c == in.c &&
-                     ((((uintptr_t)in.p) | ((uintptr_t)out.p)) & 15) == 0 && (bias == nullptr || (((uintptr_t)bias) & 15) == 0) &&
-                     (((uintptr_t)w) & 15) == 0;
-    if (!vec) {
-        const size_t total = (size_t)n * out.h * out.w * out.c;
-        if (!total) return hipSuccess;
-        hipLaunchKernelGGL(dwconv_generic_kernel, dim3(lk_grid_for(total)), dim3(256), 0, s, in, out, w, bias, total, kh, kw, stride, dil,
-                           pad_top, pad_left, mult, act, alpha);
-        return hipGetLastError();
+    hipLaunchKernelGGL(global_pool_kernel, dim3((unsigned)((in.c + 63) / 64), (unsigned)n), dim3(256), 0, s, in, out, mode);
+    return hipGetLastError();
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void upsample_kernel(TView in, TView out, size_t total, int f, int mode) {
+    constexpr int V = VEC ? 4 : 1;
+    const int cq = out.c / V;
+    const float inv = 1.f / (float)f;
+    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x) {
+        const int c = (int)(t % cq) * V;
+        size_t pix = t / cq;
+        const int ox = (int)(pix % out.w); pix /= out.w;
+        const int oy = (int)(pix % out.h);
+        const size_t img = pix / out.h;
+        float o[V];
+        if (mode == 0) {
+            const float* ip = in.p + ((img * in.h + oy / f) * in.w + ox / f) * in.cs + c;
+#pragma unroll
+            for (int e = 0; e < V; ++e) o[e] = ip[e];
+        } else {
+            // half-pixel centres: src = (dst + 0.5) / f - 0.5, edges clamped
+            const float sy = ((float)oy + 0.5f) * inv - 0.5f, sx = ((float)ox + 0.5f) * inv - 0.5f;
+            const float fy = floorf(sy), fx = floorf(sx);
+            const int y0 = max((int)fy, 0), y1 = min((int)ceilf(sy), in.h - 1);
+            const int x0 = max((int)fx, 0), x1 = min((int)ceilf(sx), in.w - 1);
+            const float ly = sy - fy, lx = sx - fx;
+            const float* r0 = in.p + (img * in.h + y0) * (size_t)in.w * in.cs + c;
+            const float* r1 = in.p + (img * in.h + min(y1, in.h - 1)) * (size_t)in.w * in.cs + c;
+#pragma unroll
+            for (int e = 0; e < V; ++e) {
+                const float tl = r0[(size_t)x0 * in.cs + e], tr = r0[(size_t)x1 * in.cs + e];
+                const float bl = r1[(size_t)x0 * in.cs + e], br = r1[(size_t)x1 * in.cs + e];
+                const float top = tl + (tr - tl) * lx, bot = bl + (br - bl) * lx;
+                o[e] = top + (bot - top) * ly;
+            }
+        }
+        float* op = out.p + ((img * out.h + oy) * out.w + ox) * out.cs + c;
+#pragma unroll
+        for (int e = 0; e < V; ++e) op[e] = o[e];
     }
-    const int quads = in.c / 4;
-    const int cq = quads < 16 ? quads : 16;
-    const int nblk_c = (quads + cq - 1) / cq;
-    const int tiles_x = (out.w + DW_TX - 1) / DW_TX, tiles_y = (out.h + DW_TY - 1) / DW_TY;
-    const size_t grid = (size_t)n * tiles_x * tiles_y * nblk_c;
-    if (grid == 0) return hipSuccess;
-    if (grid > 0x7fffffffull) return hipErrorInvalidValue;
-    const size_t hh = (size_t)(DW_TY - 1) * stride + (size_t)(kh - 1) * dil + 1, hw = (size_t)(DW_TX - 1) * stride + (size_t)(kw - 1) * dil + 1;
-    const size_t halo = hh * hw * cq * 16, wbytes = (size_t)kh * kw * cq * 16;
-    if (wbytes > 60000) {                                       // (a > 60 x 60-tap depthwise kernel)
-        const size_t total = (size_t)n * out.h * out.w * out.c;
-        hipLaunchKernelGGL(dwconv_generic_kernel, dim3(lk_grid_for(total)), dim3(256), 0, s, in, out, w, bias, total, kh, kw, stride, dil,
-                           pad_top, pad_left, mult, act, alpha);
-        return hipGetLastError();
+}
+
+hipError_t launch_upsample(const TView& in, const TView& out, int n, int factor, int mode, hipStream_t s) {
+    const bool vec = (in.c % 4 == 0);
+    const size_t total = (size_t)n * out.h * out.w * (vec ? out.c / 4 : out.c);
+    if (!total) return hipSuccess;
+    if (vec) hipLaunchKernelGGL(upsample_kernel<true>, dim3(grid_for(total)), dim3(256), 0, s, in, out, total, factor, mode);
+    else hipLaunchKernelGGL(upsample_kernel<false>, dim3(grid_for(total)), dim3(256), 0, s, in, out, total, factor, mode);
+    return hipGetLastError();
+}
+
+__global__ __launch_bounds__(256) void affine_kernel(TView in, TView out, const float* __restrict__ scale,
+                                                     const float* __restrict__ shift, size_t total, int act, float alpha) {
+    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x) {
+        const int c = (int)(t % out.c);
+        const size_t pix = t / out.c;
+        float v = in.p[pix * in.cs + c];
+        if (scale) v = v * scale[c] + shift[c];
+        out.p[pix * out.cs + c] = apply_act_ext(v, act, alpha);
     }
-    if (halo + wbytes <= 64 * 1024)
-        hipLaunchKernelGGL(dwconv_kernel<true>, dim3((unsigned)grid), dim3(256), halo + wbytes, s, in, out, w, bias, kh, kw, stride, dil,
-                           pad_top, pad_left, act, alpha, tiles_x, tiles_y, cq, nblk_c);
-    else
-        hipLaunchKernelGGL(dwconv_kernel<false>, dim3((unsigned)grid), dim3(256), wbytes, s, in, out, w, bias, kh, kw, stride, dil,
-                           pad_top, pad_left, act, alpha, tiles_x, tiles_y, cq, nblk_c);
+}
+
+hipError_t launch_affine(const TView& in, const TView& out, const float* scale, const float* shift, int n, int act,
+                         float alpha, hipStream_t s) {
+    const size_t total = (size_t)n * out.h * out.w * out.c;
+    if (!total) return hipSuccess;
+    hipLaunchKernelGGL(affine_kernel, dim3(grid_for(total)), dim3(256), 0, s, in, out, scale, shift, total, act, alpha);
     return hipGetLastError();
 }
 
@@ -369,8 +241,8 @@ hipError_t launch_binary(const TView& a, const TView& b, const TView& out, int n
     const bool vec = v4(a) && v4(b) && v4(out);
     const size_t total = (size_t)n * out.h * out.w * (vec ? out.c / 4 : out.c);
     if (!total) return hipSuccess;
-    if (vec) hipLaunchKernelGGL(binary_kernel<true>, dim3(lk_grid_for(total)), dim3(256), 0, s, a, b, out, total, mode, act, alpha);
-    else hipLaunchKernelGGL(binary_kernel<false>, dim3(lk_grid_for(total)), dim3(256), 0, s, a, b, out, total, mode, act, alpha);
+    if (vec) hipLaunchKernelGGL(binary_kernel<true>, dim3(grid_for(total)), dim3(256), 0, s, a, b, out, total, mode, act, alpha);
+    else hipLaunchKernelGGL(binary_kernel<false>, dim3(grid_for(total)), dim3(256), 0, s, a, b, out, total, mode, act, alpha);
     return hipGetLastError();
 }
 
@@ -389,7 +261,7 @@ __global__ __launch_bounds__(256) void prelu_kernel(TView in, TView out, const f
 hipError_t launch_prelu(const TView& in, const TView& out, const float* slope, int n, int per_element, hipStream_t s) {
     const size_t total = (size_t)n * out.h * out.w * out.c;
     if (!total) return hipSuccess;
-    hipLaunchKernelGGL(prelu_kernel, dim3(lk_grid_for(total)), dim3(256), 0, s, in, out, slope, total, per_element);
+    hipLaunchKernelGGL(prelu_kernel, dim3(grid_for(total)), dim3(256), 0, s, in, out, slope, total, per_element);
     return hipGetLastError();
 }
 
@@ -441,75 +313,76 @@ hipError_t launch_layernorm(const TView& in, const TView& out, const float* gamm
     return hipGetLastError();
 }
 
-// MaxPooling2D / AveragePooling2D with padding='same': the window starts (pad_top, pad_left) before the input; the maximum
-// and the average run over the pixels that lie inside it (TensorFlow's average excludes the padding from the divisor)
-__global__ __launch_bounds__(256) void pool_pad_kernel(TView in, TView out, size_t total, int kh, int kw, int stride, int pad_top,
-                                                       int pad_left, int mode) {
+// y[oy][ox] = x[oy - off_y][ox - off_x] or 0 outside: ZeroPadding2D (off > 0), Cropping2D (off < 0), plain copy (0)
+__global__ __launch_bounds__(256) void copy_kernel(TView in, TView out, size_t total, int off_y, int off_x) {
     for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x) {
         const int c = (int)(t % out.c);
         size_t pix = t / out.c;
         const int ox = (int)(pix % out.w); pix /= out.w;
         const int oy = (int)(pix % out.h);
         const size_t img = pix / out.h;
-        float m = mode ? 0.f : -INFINITY;
-        int cnt = 0;
-        for (int r = 0; r < kh; ++r) {
-            const int iy = oy * stride - pad_top + r;
-            if (iy < 0 || iy >= in.h) continue;
-            for (int s = 0; s < kw; ++s) {
-                const int ix = ox * stride - pad_left + s;
-                if (ix < 0 || ix >= in.w) continue;
-                const float v = in.p[((img * in.h + iy) * in.w + ix) * in.cs + c];
-                m = mode ? m + v : fmaxf(m, v);
-                ++cnt;
-            }
-        }
-        if (mode) m = cnt ? m / (float)cnt : 0.f;
-        out.p[((img * out.h + oy) * out.w + ox) * out.cs + c] = m;
+        const int iy = oy - off_y, ix = ox - off_x;
+        float v = 0.f;
+        if (iy >= 0 && iy < in.h && ix >= 0 && ix < in.w) v = in.p[((img * in.h + iy) * in.w + ix) * in.cs + c];
+        out.p[((img * out.h + oy) * out.w + ox) * out.cs + c] = v;
     }
 }
 
-hipError_t launch_pool_pad(const TView& in, const TView& out, int n, int kh, int kw, int stride, int pad_top, int pad_left, int mode,
-                           hipStream_t s) {
+hipError_t launch_copy(const TView& in, const TView& out, int n, int off_y, int off_x, hipStream_t s) {
     const size_t total = (size_t)n * out.h * out.w * out.c;
     if (!total) return hipSuccess;
-    hipLaunchKernelGGL(pool_pad_kernel, dim3(lk_grid_for(total)), dim3(256), 0, s, in, out, total, kh, kw, stride, pad_top, pad_left, mode);
+    hipLaunchKernelGGL(copy_kernel, dim3(grid_for(total)), dim3(256), 0, s, in, out, total, off_y, off_x);
     return hipGetLastError();
 }
 
-// conv_generic_kernel (unet_kernels.hip) with dilation rates and per-axis strides: the scalar fall-back of dilated layers the MFMA kernel does
-// not take (Cin % 4 != 0, unaligned views) and of every layer with ANISOTROPIC strides / dilation rates (round 6)
-__global__ __launch_bounds__(256) void conv_generic_dil_kernel(TView in, TView out, const float* __restrict__ w, const float* __restrict__ bias,
-                                                               size_t total, int R, int S, int stride, int stride_x, int dil, int dil_x, int pad_top, int pad_left,
-                                                               int act, float alpha) {
-    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x) {
-        const int co = (int)(t % out.c);
-        size_t pix = t / out.c;
-        const int ox = (int)(pix % out.w); pix /= out.w;
-        const int oy = (int)(pix % out.h);
-        const size_t img = pix / out.h;
-        float acc = bias ? bias[co] : 0.f;
-        for (int r = 0; r < R; ++r) {
-            const int iy = oy * stride - pad_top + r * dil;
-            if (iy < 0 || iy >= in.h) continue;
-            for (int s = 0; s < S; ++s) {
-                const int ix = ox * stride_x - pad_left + s * dil_x;
-                if (ix < 0 || ix >= in.w) continue;
-                const float* ip = in.p + ((img * in.h + iy) * in.w + ix) * in.cs;
-                const float* wp = w + (size_t)(r * S + s) * in.c * out.c + co;
-                for (int ci = 0; ci < in.c; ++ci) acc = fmaf(ip[ci], wp[(size_t)ci * out.c], acc);
-            }
-        }
-        out.p[((img * out.h + oy) * out.w + ox) * out.cs + co] = apply_act(acc, act, alpha);
+__global__ __launch_bounds__(256) void softmax_kernel(TView in, TView out, size_t npix) {
+    for (size_t pix = (size_t)blockIdx.x * blockDim.x + threadIdx.x; pix < npix; pix += (size_t)gridDim.x * blockDim.x) {
+        const float* ip = in.p + pix * in.cs;
+        float* op = out.p + pix * out.cs;
+        float m = ip[0];
+        for (int c = 1; c < in.c; ++c) m = fmaxf(m, ip[c]);
+        float sum = 0.f;
+        for (int c = 0; c < in.c; ++c) sum += expf(ip[c] - m);
+        for (int c = 0; c < in.c; ++c) op[c] = expf(ip[c] - m) / sum;
     }
 }
 
-hipError_t launch_conv_generic_dil(const TView& in, const TView& out, const float* w, const float* bias, int n, int R, int S, int stride, int stride_x,
-                                   int dil, int dil_x, int pad_top, int pad_left, int act, float alpha, hipStream_t s) {
-    const size_t total = (size_t)n * out.h * out.w * out.c;
+hipError_t launch_softmax(const TView& in, const TView& out, int n, hipStream_t s) {
+    const size_t npix = (size_t)n * out.h * out.w;
+    if (!npix) return hipSuccess;
+    hipLaunchKernelGGL(softmax_kernel, dim3(grid_for(npix)), dim3(256), 0, s, in, out, npix);
+    return hipGetLastError();
+}
+
+__global__ __launch_bounds__(256) void u8_to_f32_kernel(const uint8_t* __restrict__ in, float* __restrict__ out, size_t count) {
+    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < count; t += (size_t)gridDim.x * blockDim.x)
+        out[t] = (float)in[t];
+}
+
+hipError_t launch_u8_to_f32(const uint8_t* in, float* out, size_t count, hipStream_t s) {
+    if (!count) return hipSuccess;
+    hipLaunchKernelGGL(u8_to_f32_kernel, dim3(grid_for(count)), dim3(256), 0, s, in, out, count);
+    return hipGetLastError();
+}
+
+// im2patches_overlap (reference src/image_tools.py:181-184): patch k of image i = gray[i, y0:y0+256, x0:x0+256]
+__global__ __launch_bounds__(256) void tile_patches_kernel(const uint8_t* __restrict__ gray, int H, int W,
+                                                           const int32_t* __restrict__ pos, int n_pos,
+                                                           float* __restrict__ out, size_t total) {
+    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x) {
+        const int x = (int)(t & 255), y = (int)((t >> 8) & 255);
+        const size_t pk = t >> 16;
+        const int k = (int)(pk % n_pos);
+        const size_t img = pk / n_pos;
+        out[t] = (float)gray[(img * H + pos[2 * k] + y) * W + pos[2 * k + 1] + x];
+    }
+}
+
+hipError_t launch_tile_patches(const uint8_t* gray, int n_img, int H, int W, const int32_t* pos_yx, int n_pos, float* out,
+                               hipStream_t s) {
+    const size_t total = (size_t)n_img * n_pos * 65536;
     if (!total) return hipSuccess;
-    hipLaunchKernelGGL(conv_generic_dil_kernel, dim3(lk_grid_for(total)), dim3(256), 0, s, in, out, w, bias, total, R, S, stride, stride_x,
-                       dil < 1 ? 1 : dil, dil_x < 1 ? 1 : dil_x, pad_top, pad_left, act, alpha);
+    hipLaunchKernelGGL(tile_patches_kernel, dim3(grid_for(total)), dim3(256), 0, s, gray, H, W, pos_yx, n_pos, out, total);
     return hipGetLastError();
 }
 

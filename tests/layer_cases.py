@@ -218,6 +218,51 @@ def merge_cases():
     return out
 
 
+# ---- Add of two same-shape inputs, bit for bit -----------------------------------------------------------------------------
+# (a, b) pairs that meet in one element: signed zeros, values that cancel to 0, large values (a finite sum, an overflow), infinities
+# beside finite values and beside their own sign.  No inf + -inf (NaN) and no denormals.
+ADD_EXACT_PAIRS = ((0.0, 0.0), (-0.0, -0.0), (0.0, -0.0), (-0.0, 0.0), (1.5, -1.5), (-2.75e-3, 2.75e-3), (1e38, 1e38), (3e38, 3e38),
+                   (-3e38, -3e38), (3e38, -3e38), (1e30, 1.0), (np.inf, 1.0), (-np.inf, -1.0), (np.inf, np.inf), (-np.inf, -np.inf),
+                   (np.inf, -3e38), (1.0, np.inf))
+
+
+def add_exact_case(C, view=False, N=2, H=5, W=7):
+    """Add([a, b]) with a = the input (or an exact copy of it) and b = the input moved down a row (``_shifted``), so element
+    (y, x, c) adds x[y] and x[y - 1], and row 0 adds +0.  Rows 1 and 0 of image 0 hold ``ADD_EXACT_PAIRS``, over and over; the
+    rest is random.  ``view``: a is the member at channel offset 2 of a 12-channel Concatenate - stride and channel count are
+    multiples of 4 and only the pointer is not 16-byte aligned; the members beside it are channel selections of the input
+    clipped to [0, 1] (finite, so that their one-hot products are)."""
+    name = 'add_exact_c%d%s' % (C, '_view' if view else '')
+    x = _f32(_rng(name).normal(size=(N, H, W, C)))
+    pairs = np.array(ADD_EXACT_PAIRS, np.float32)
+    idx = np.arange(W * C) % len(pairs)
+    x[0, 1] = pairs[idx, 0].reshape(W, C)
+    x[0, 0] = pairs[idx, 1].reshape(W, C)
+    layers, weights, a = [_in(H, W, C)], {}, 'in'
+    if view:
+        layers.append(_L('ReLU', 'f', ['in'], max_value=1.0, negative_slope=0.0, threshold=0.0))
+        (Ls, ws), (Lt, wt) = _onehot('s', 'f', C, [0, 1]), _onehot('t', 'f', C, [3, 2])
+        layers.extend([Ls, _L('ZeroPadding2D', 'a', ['in'], padding=[[0, 0], [0, 0]]), Lt, _L('Concatenate', 'cat1', ['s', 'a', 't'], axis=-1)])
+        weights.update(ws, **wt)
+        a = 'a'
+    layers.extend(_shifted('b'))
+    layers.append(_L('Add', 'op', [a, 'b']))
+    # vector: launch_binary's test - every view of the op has all channels, a multiple of 4 of them, and is 16-byte aligned
+    return _case(name, 'add_exact', layers, weights, x, dict(op='add_exact', vector=C % 4 == 0 and not view, view=view))
+
+
+def add_exact_operands(case):
+    """-> (a, b) float32, the two operands of the case's Add as the layers above make them."""
+    a = case['x']
+    b = np.zeros_like(a)
+    b[:, 1:] = a[:, :-1]
+    return a, b
+
+
+def add_exact_cases():
+    return [add_exact_case(8), add_exact_case(6), add_exact_case(8, view=True)]
+
+
 # ---- PReLU -----------------------------------------------------------------------------------------------------------
 PRELU_SHARED = (None, [1], [2], [3], [1, 2], [1, 3], [2, 3], [1, 2, 3])
 

@@ -1,6 +1,7 @@
 """Every non-convolution layer kernel ALONE against tests/layer_ref.py's float64 restatement, element by element, on the cases of
-tests/layer_cases.py (maxpool / pool_pad / global_pool / upsample / affine / add / binary / prelu / copy / layernorm /
-softmax kernels and the activation codes of device_util.h).  tests/test_layers_ref.py ties layer_ref to the float64 oracle.
+tests/layer_cases.py (the maxpool / pool_pad / global_pool / upsample / affine / binary / prelu / copy / layernorm / softmax
+kernels of csrc/layer_kernels.hip and the activation codes of device_util.h).  tests/test_layers_ref.py ties layer_ref to the
+float64 oracle.  Every Add of a plan runs on binary_kernel: test_add_of_two_inputs_is_exact holds it to numpy's float32 sum, bit for bit.
 
 Bounds.  u = 2^-24 is the relative error of one correctly rounded float32 operation (half an ulp), so a library function
 with an error ceiling of k ulp contributes 2k u.  Every bound but round1's is |got - want64| <= n_ops * u * mag * SECOND + floor, with
@@ -205,3 +206,34 @@ def test_layer_kernels_against_float64(gpu, group):
         for fn, (v, r) in sorted(stats['ulp'].items()):
             print('  %-15s %-21.2f %-22s %.3f' % (fn, v, '0.5' if fn == 'leaky_relu' else ('%.1f' % (ACT_OPS[fn] / 2.0)) if fn in ACT_OPS else 'per element', r))
     assert not bad, '\n'.join(bad)
+
+
+@pytest.mark.parametrize('act', ('linear', 'relu'))
+@pytest.mark.parametrize('case', layer_cases.add_exact_cases(), ids=lambda c: c['name'])
+def test_add_of_two_inputs_is_exact(gpu, case, act):
+    """Add of two same-shape inputs = numpy.float32(a) + numpy.float32(b), then the op's own activation (linear | ReLU: v > 0 ? v : +0),
+    bit for bit, on both branches of launch_binary: 16 bytes per lane (C = 8), one float per lane because C % 4 != 0 (C = 6), and one
+    float per lane because an operand's pointer is not 16-byte aligned (C = 8 at channel offset 2 of a 12-channel buffer)."""
+    a, b = layer_cases.add_exact_operands(case)
+    with np.errstate(over='ignore'):
+        want = a + b
+    assert want.dtype == np.float32 and not np.isnan(want).any()
+    assert np.isinf(want).any() and (want == 0).any() and np.signbit(want[want == 0]).any()      # the hand-picked pairs are in
+    if act == 'relu':
+        want = np.where(want > 0, want, np.float32(0.0))
+    plan = keras_plan.build_plan(case['cfg'], case['weights'])
+    adds = [o for o in plan.ops if o['op'] == keras_plan.OP_ADD]
+    assert len(adds) == 1 and adds[0]['mode'] == 0 and adds[0]['act'] == 0
+    views = [plan.tensors[adds[0][k]] for k in ('in0', 'in1', 'out')]
+    assert all((t['h'], t['w'], t['c']) == want.shape[1:] for t in views)
+    # the case takes the branch it is meant for: launch_binary's test on the views, and for the view case the pointer alone decides
+    assert all(t['c'] % 4 == 0 and t['c_stride'] % 4 == 0 and t['c_offset'] % 4 == 0 for t in views) == case['kind']['vector']
+    if case['kind']['view']:
+        assert all(t['c'] % 4 == 0 and t['c_stride'] % 4 == 0 for t in views) and [t['c_offset'] % 4 for t in views] == [2, 0, 0]
+    adds[0]['act'] = keras_plan.ACT[act]                      # the activation of the ADD op itself (ecseg_op_desc.act), inside binary_kernel
+    gpu.load_plan(plan)
+    got = gpu.forward_patches(case['x'])
+    assert got.shape == want.shape and got.dtype == np.float32
+    differ = got.view(np.uint32) != want.view(np.uint32)
+    i = np.unravel_index(np.argmax(differ), differ.shape)
+    assert not differ.any(), '%d of %d differ, first at %s: %r + %r = %r, expected %r' % (differ.sum(), differ.size, i, a[i], b[i], got[i], want[i])
