@@ -46,6 +46,14 @@ asan_tiff_inflate:
 	    tools/asan/tiff_inflate_fuzz.cpp -lz -o /tmp/ecseg_tiff_inflate_fuzz
 	/tmp/ecseg_tiff_inflate_fuzz
 
+# and for its PackBits strips (csrc/tiff_packbits_strip.h, the body of tiffb_packbits_kernel): seeded valid, truncated and overlong
+# streams against a plain byte loop that restates image_io._packbits_decode; tests/test_tiff_packbits.py builds and runs it
+.PHONY: asan_tiff_packbits
+asan_tiff_packbits:
+	g++ -std=c++17 -O1 -g -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=all \
+	    tools/asan/tiff_packbits_fuzz.cpp -o /tmp/ecseg_tiff_packbits_fuzz
+	/tmp/ecseg_tiff_packbits_fuzz
+
 # and for the batched reader: the layout function (csrc/tiff_decode_batch.h) and the batched strip walk over packed batches with
 # corrupt and truncated files; tests/test_tiff_decode_batch.py builds and runs it
 .PHONY: asan_tiff_decode_batch

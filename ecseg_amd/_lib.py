@@ -28,6 +28,7 @@ EXPORTS = [
     'ecseg_tiff_decode_batch', 'ecseg_tiff_decode_batch_bytes', 'ecseg_tiff_decode_batch_routes', 'ecseg_tiff_decode_batch_counts',
     'ecseg_tiff_decode_routes_ex', 'ecseg_tiff_decode_batch_routes_ex', 'ecseg_tiff_decode_batch_counts_ex', 'ecseg_tiff_decode_batch_bytes_ex',
     'ecseg_tiff_decode_routes_ex2', 'ecseg_tiff_decode_batch_routes_ex2', 'ecseg_tiff_decode_batch_counts_ex2', 'ecseg_tiff_decode_batch_bytes_ex2',
+    'ecseg_tiff_decode_routes_ex3', 'ecseg_tiff_decode_batch_routes_ex3', 'ecseg_tiff_decode_batch_counts_ex3', 'ecseg_tiff_decode_batch_bytes_ex3',
     'ecseg_meta_segment_tiffs', 'ecseg_meta_segment_tiffs_files', 'ecseg_prefetch_tiffs', 'ecseg_get_read_timings',
     'ecseg_png_channel_bound', 'ecseg_png_channel_encode', 'ecseg_overlay_files',
     'ecseg_tiff_encode_batch', 'ecseg_tiff_encode_batch_bytes', 'ecseg_fish_render_tiff_batch',
@@ -182,6 +183,10 @@ def load_library():
     lib.ecseg_tiff_decode_batch_routes_ex2.argtypes = [vp, C.c_longlong, vp, i32, i32, i32]
     lib.ecseg_tiff_decode_batch_counts_ex2.argtypes = [vp, C.c_longlong, i32, i32]
     lib.ecseg_tiff_decode_batch_bytes_ex2.argtypes = [vp, C.c_longlong, vp, i32, i32, i32]; lib.ecseg_tiff_decode_batch_bytes_ex2.restype = C.c_longlong
+    lib.ecseg_tiff_decode_routes_ex3.argtypes = [vp, C.c_longlong, i32, i32, i32]
+    lib.ecseg_tiff_decode_batch_routes_ex3.argtypes = [vp, C.c_longlong, vp, i32, i32, i32, i32]
+    lib.ecseg_tiff_decode_batch_counts_ex3.argtypes = [vp, C.c_longlong, i32, i32, i32]
+    lib.ecseg_tiff_decode_batch_bytes_ex3.argtypes = [vp, C.c_longlong, vp, i32, i32, i32, i32]; lib.ecseg_tiff_decode_batch_bytes_ex3.restype = C.c_longlong
     lib.ecseg_min_cut.argtypes = [vp, vp, C.c_longlong, vp, i32, i32, vp, vp]
     lib.ecseg_min_cut_regions.argtypes = [vp, vp, i32, i32, C.c_double, i32, i32, i32, C.c_longlong, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.ecseg_nuset_forward.argtypes = [vp, vp, i32, i32, i32, i32, vp]
@@ -356,6 +361,8 @@ class Handle:
             self.tiff_deflate_on_device = bool(value)
         if key == 'tiff_tiled_on_device':    # the mirror image_io.imread / imread_many and tiff_decode_many read: tiled files are taken
             self.tiff_tiled_on_device = bool(value)
+        if key == 'tiff_packbits_on_device': # the same for PackBits files
+            self.tiff_packbits_on_device = bool(value)
         if key == 'images_per_group':        # the same knob as set_images_per_group: keep the mirror the OOM retry restores from
             self.images_per_group = int(value)
 
@@ -1104,7 +1111,7 @@ class Handle:
     def tiff_decode(self, data, deflate=None):
         """The bytes of a TIFF file -> what ``image_io.read_tiff`` returns for that file, (H, W) or (H, W, spp) uint8 / uint16, with
         every strip decoded on the device (ecseg_tiff_decode); None for a file that is left to the host readers (ECSEG_E_UNSUPPORTED:
-        BigTIFF, PackBits, Deflate, and tiles unless the handle option ``tiff_tiled_on_device`` is on).  Whether a file is worth sending here is ``image_io.imread``'s question (ecseg_tiff_decode_routes).  A corrupt file raises, with code -1.
+        BigTIFF, Deflate, and tiles or PackBits unless the handle option ``tiff_tiled_on_device`` / ``tiff_packbits_on_device`` is on).  Whether a file is worth sending here is ``image_io.imread``'s question (ecseg_tiff_decode_routes).  A corrupt file raises, with code -1.
         ``deflate``: True / False: the call runs with the handle option ``tiff_deflate_on_device`` on / off - on, Deflate strips
         (compression 8 and 32946) are decoded too, and such a file is an array or an error, not None; None: as the option stands."""
         with self._deflate_option(deflate):
@@ -1163,7 +1170,8 @@ class Handle:
         buf, ranges = pack_file_images([b for _, b in todo])     # packed once: every call reads its files through its rows of the table
         # what each file needs alone, asked once per file: their sum is at least what a call over them needs (every slot rounds up alone)
         deflate, tiled = int(getattr(self, 'tiff_deflate_on_device', False)), int(getattr(self, 'tiff_tiled_on_device', False))
-        needs = [self.lib.ecseg_tiff_decode_batch_bytes_ex2(_ptr(buf), buf.size, _ptr(np.ascontiguousarray(ranges[k:k + 1])), 1, deflate, tiled)
+        packbits = int(getattr(self, 'tiff_packbits_on_device', False))
+        needs = [self.lib.ecseg_tiff_decode_batch_bytes_ex3(_ptr(buf), buf.size, _ptr(np.ascontiguousarray(ranges[k:k + 1])), 1, deflate, tiled, packbits)
                  for k in range(len(todo))]
         chunks, lo, held = [], 0, 0
         for hi, need in enumerate(needs):

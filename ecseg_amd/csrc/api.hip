@@ -137,6 +137,7 @@ int ecseg_set_option(ecseg_ctx* h, const char* key, int value) {
     else if (k == "lane_auto_windows" && value >= 0) h->lane_auto_windows = value;
     else if (k == "tiff_deflate_on_device") h->tiff_deflate_on_device = value != 0;
     else if (k == "tiff_tiled_on_device") h->tiff_tiled_on_device = value != 0;
+    else if (k == "tiff_packbits_on_device") h->tiff_packbits_on_device = value != 0;
     else if (k == "min_cut_lds_pixels" && value >= 0 && value <= ECSEG_MIN_CUT_LDS_PIXELS) h->min_cut_lds_pixels = value;   // 0: every window in global memory
     else if (k == "min_cut_centers_lds_pixels" && value >= 0 && value <= ECSEG_MIN_CUT_CENTERS_LDS_PIXELS) h->min_cut_centers_lds_pixels = value;   // 0: every crop in global memory
     else return fail(h, ECSEG_E_INVALID, "unknown option or bad value: " + k);

@@ -361,7 +361,7 @@ int entry_values(const Reader& r, size_t e, std::vector<uint32_t>* out) {
 
 // ECSEG_OK, ECSEG_E_UNSUPPORTED (a valid layout this reader leaves to the Python one) or ECSEG_E_INVALID (corrupt); TiffInfo and
 // the declaration are in tiff_parse.h, for the device reader's driver
-int ecseg::parse_tiff(const uint8_t* buf, size_t n, TiffInfo* t, bool take_tiles) {
+int ecseg::parse_tiff(const uint8_t* buf, size_t n, TiffInfo* t, bool take_tiles, bool take_packbits) {
     if (n < 8) return ECSEG_E_INVALID;
     if (buf[0] == 'I' && buf[1] == 'I') t->le = true;
     else if (buf[0] == 'M' && buf[1] == 'M') t->le = false;
@@ -410,7 +410,7 @@ int ecseg::parse_tiff(const uint8_t* buf, size_t n, TiffInfo* t, bool take_tiles
     if (!have_w || !have_h || t->W == 0 || t->H == 0 || t->spp == 0 || t->W > (1u << 20) || t->H > (1u << 20) || t->spp > 16)
         return ECSEG_E_INVALID;
     if ((tiled && !take_tiles) || (t->bits != 8 && t->bits != 16) || t->fmt != 1 || (t->planar != 1 && t->spp > 1) ||
-        (t->comp != 1 && t->comp != 5 && t->comp != 8 && t->comp != 32946) || (t->pred != 1 && t->pred != 2))
+        (t->comp != 1 && t->comp != 5 && t->comp != 8 && t->comp != 32946 && !(take_packbits && t->comp == 32773)) || (t->pred != 1 && t->pred != 2))
         return ECSEG_E_UNSUPPORTED;
     if (tiled) {                                             // (take_tiles) the rule of tiff_parse.h; everything else is the Python reader's
         if (!tile_tags_ok || !have_th || t->tw == 0 || t->th == 0 || t->tw % 16 || t->th % 16 || t->tw > TIFF_TILE_MAX_EXTENT || t->th > TIFF_TILE_MAX_EXTENT ||

@@ -18,9 +18,9 @@
 
 namespace ecseg {
 
-// The codec of a file's strips.  TD_RAW and TD_LZW strips are tiffb_unstrip_kernel's, TD_DEFLATE strips tiffb_inflate_kernel's; each
-// kernel answers TD_OTHER_KERNEL (no status word) for a strip of the other.
-enum : uint8_t { TD_RAW = 0, TD_LZW = 1, TD_DEFLATE = 2 };
+// The codec of a file's strips.  TD_RAW and TD_LZW strips are tiffb_unstrip_kernel's, TD_DEFLATE strips tiffb_inflate_kernel's,
+// TD_PACKBITS strips tiffb_packbits_kernel's; each kernel answers TD_OTHER_KERNEL (no status word) for a strip of another.
+enum : uint8_t { TD_RAW = 0, TD_LZW = 1, TD_DEFLATE = 2, TD_PACKBITS = 3 };
 constexpr uint32_t TD_OTHER_KERNEL = 2;
 
 struct TdFile {
@@ -33,7 +33,7 @@ struct TdFile {
     uint32_t H, rps, W, spp, bps;
     uint32_t first_strip;    // global index of strip 0 (grid x of tiffb_unstrip_kernel); the file has ceil(H / rps) strips
     uint32_t first_row;      // global index of row 0 (grid x of tiffb_unpredict_kernel); the file has H rows
-    uint8_t codec, swap, predictor, in_batch;    // TD_RAW / TD_LZW / TD_DEFLATE strips; 16-bit samples in the other byte order; horizontal predictor; 0: a file of zero strips
+    uint8_t codec, swap, predictor, in_batch;    // TD_RAW / TD_LZW / TD_DEFLATE / TD_PACKBITS strips; 16-bit samples in the other byte order; horizontal predictor; 0: a file of zero strips
     uint32_t tiles;          // 0: strips; else 1 + the file's row of the tiled-file table (then n_table is its tile count, rps its tile length)
 };
 static_assert(sizeof(TdFile) == 80, "the device table is an array of 80-byte rows, copied as it is");
@@ -66,6 +66,7 @@ struct TdBatchLayout {
     uint64_t n_strips = 0, n_rows = 0;           // the two grids
     bool any_u8_predictor = false, any_u16_pass = false;     // which tiffb_unpredict_kernel launches the batch needs
     bool any_deflate = false;                    // whether it needs tiffb_inflate_kernel
+    bool any_packbits = false;                   // whether it needs tiffb_packbits_kernel
     std::vector<TdTiles> tiles;                  // one row per tiled file that takes part (empty: no tiffb_untile_kernel, no staging)
     uint64_t stage_bytes = 0, n_trows = 0;       // the staging slots of all compressed tiles; the rows of tiles (the grid of tiffb_untile_kernel)
 };
@@ -121,6 +122,7 @@ inline std::string td_batch_layout(const std::vector<TdFileIn>& in, TdBatchLayou
         L.any_u16_pass = L.any_u16_pass || (!t.tiles && t.bps == 2 && (t.swap || t.predictor));      // (tiffb_untile_kernel does both for a tiled file)
         L.any_u8_predictor = L.any_u8_predictor || (!t.tiles && t.bps == 1 && t.predictor);
         L.any_deflate = L.any_deflate || t.codec == TD_DEFLATE;
+        L.any_packbits = L.any_packbits || t.codec == TD_PACKBITS;
     }
     return std::string();
 }

@@ -12,10 +12,12 @@
 // strips of different files share nothing, which is where a batch of files of few strips finds its parallelism.
 // tiffb_inflate_kernel: the same grid for the strips of Deflate files (ti_inflate_strip, tiff_inflate_strip.h), launched only for a
 // batch that holds one; each of the two kernels leaves the other's strips at once.
+// tiffb_packbits_kernel: the same grid once more for the strips of PackBits files (tp_packbits_strip, tiff_packbits_strip.h: the
+// header walk in every lane, the bytes of a run written by the lanes), launched only for a batch that holds one.
 // tiffb_unpredict_kernel: one wave per row, after all strips: 16-bit samples of a big-endian file are swapped to native order, then
 // the horizontal predictor is undone per sample channel (stride spp) as an inclusive wave scan over 64 samples with a carry
 // into the next 64, modulo 2^8 or 2^16 (td_unpredict_row).
-// tiffb_untile_kernel: only for a batch with tiled files (the handle option tiff_tiled_on_device), after the two strip kernels, in
+// tiffb_untile_kernel: only for a batch with tiled files (the handle option tiff_tiled_on_device), after the strip kernels, in
 // which a tile is a strip of the grid whose stream decodes into its staging slot.  Grid x is the row of tiles counted over the tiled
 // files (TdTiles), grid y splits the rows of the tiles among TD_UNTILE_PARTS waves; a wave puts whole raster rows in their place:
 // byte order, the predictor along each tile row, the padding of edge tiles dropped (tiff_untile.h).  The row kernel above leaves
@@ -24,6 +26,7 @@
 #include "common.h"
 #include "tiff_decode_strip.h"
 #include "tiff_inflate_strip.h"
+#include "tiff_packbits_strip.h"
 #include "tiff_untile.h"
 
 namespace ecseg {
@@ -76,6 +79,15 @@ __global__ __launch_bounds__(64) void tiffb_inflate_kernel(const TdFile* __restr
     if (threadIdx.x == 0 && st != TD_OTHER_KERNEL) status[blockIdx.x] = st;
 }
 
+// And for the PackBits strips (tp_packbits_strip, tiff_packbits_strip.h), under the same rule.
+__global__ __launch_bounds__(64) void tiffb_packbits_kernel(const TdFile* __restrict__ tab, uint32_t n_files, const uint8_t* __restrict__ files,
+                                                            const uint32_t* __restrict__ tables, uint8_t* rasters, uint32_t* __restrict__ status,
+                                                            const TdTiles* __restrict__ tiles, uint8_t* staging) {
+    __shared__ TpLds L;
+    const uint32_t st = tdb_packbits(tab, n_files, files, tables, rasters, blockIdx.x, L, tiles, staging);
+    if (threadIdx.x == 0 && st != TD_OTHER_KERNEL) status[blockIdx.x] = st;
+}
+
 // Grid x is the global row; files of the other sample size, and files with neither swap nor predictor, return at once.
 template <typename T>
 __global__ __launch_bounds__(64) void tiffb_unpredict_kernel(const TdFile* __restrict__ tab, uint32_t n_files, uint8_t* rasters) {
@@ -110,6 +122,8 @@ hipError_t run_tiff_decode_batch(const TiffDecodeBatchBufs& b, const TdBatchLayo
     hipLaunchKernelGGL(tiffb_unstrip_kernel, dim3(ns), dim3(64), 0, s, b.tab, n, b.files, b.tables, b.rasters, b.strip_status, b.tiles, b.staging);
     if (L.any_deflate)
         hipLaunchKernelGGL(tiffb_inflate_kernel, dim3(ns), dim3(64), 0, s, b.tab, n, b.files, b.tables, b.rasters, b.strip_status, b.tiles, b.staging);
+    if (L.any_packbits)
+        hipLaunchKernelGGL(tiffb_packbits_kernel, dim3(ns), dim3(64), 0, s, b.tab, n, b.files, b.tables, b.rasters, b.strip_status, b.tiles, b.staging);
     if (!L.tiles.empty())
         hipLaunchKernelGGL(tiffb_untile_kernel, dim3((uint32_t)L.n_trows, TD_UNTILE_PARTS), dim3(64), 0, s, b.tab, b.tiles, (uint32_t)L.tiles.size(), b.files,
                            b.tables, b.staging, b.rasters);

@@ -191,12 +191,13 @@ TD_FN uint32_t td_find_file(const TdFile* tab, uint32_t n, uint32_t idx, bool ro
 }
 
 // Global strip `strip` of a batch, by one wave: td_lzw_strip or td_raw_strip on the strip's file.  Returns its status word (0, or 1:
-// corrupt stream / offset behind the file), the same in every lane; TD_OTHER_KERNEL for a Deflate strip (tdb_inflate, tiff_inflate_strip.h).
+// corrupt stream / offset behind the file), the same in every lane; TD_OTHER_KERNEL for a Deflate strip (tdb_inflate, tiff_inflate_strip.h)
+// and for a PackBits strip (tdb_packbits, tiff_packbits_strip.h).
 // tiles, staging: the tiled-file table and the staging slots of a batch that has tiled files (else no row of tab points there).
 TD_FN uint32_t tdb_unstrip(const TdFile* tab, uint32_t n_files, const uint8_t* files, const uint32_t* tables, uint8_t* rasters, uint32_t strip,
                            TdLds& L, const TdTiles* tiles = nullptr, uint8_t* staging = nullptr) {
     const TdFile& f = tab[td_first(td_find_file(tab, n_files, strip, false))];
-    if (f.codec == TD_DEFLATE) return TD_OTHER_KERNEL;
+    if (f.codec == TD_DEFLATE || f.codec == TD_PACKBITS) return TD_OTHER_KERNEL;
     const uint32_t k = strip - f.first_strip;
     if (f.tiles) {                                           // a tile: an LZW stream into its slot; an uncompressed one is tiffb_untile_kernel's alone
         if (!f.in_batch || k >= f.n_table || f.codec != TD_LZW) return 0u;

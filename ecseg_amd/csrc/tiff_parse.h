@@ -22,8 +22,10 @@ struct TiffInfo {
 // positive multiples of 16 of at most TIFF_TILE_MAX_EXTENT, it has no strip tags, and both tile tables have an entry for each of its
 // ceil(H / th) * ceil(W / tw) tiles; sample size, format, planarity, compression and predictor are held to the rules of strips.  Every
 // other tiled file stays ECSEG_E_UNSUPPORTED.
+// packbits == false: a PackBits file (compression 32773) is ECSEG_E_UNSUPPORTED, as it is for the host reader.  packbits == true
+// (the device reader with the option tiff_packbits_on_device): it is taken, held to every other rule of strips and of tiles.
 constexpr uint32_t TIFF_TILE_MAX_EXTENT = 1u << 20;
-int parse_tiff(const uint8_t* buf, size_t n, TiffInfo* t, bool tiled = false);
+int parse_tiff(const uint8_t* buf, size_t n, TiffInfo* t, bool tiled = false, bool packbits = false);
 
 // Where row r of tile `tile` of a tiled image goes: tiles lie row-major, `across` = ceil(W / tw) per row of tiles, and those on the
 // right and bottom edges are padded to the full tile.  -> the raster row, the first pixel column, and of the tile row's tw * px bytes
@@ -65,6 +67,9 @@ inline TilePlace tile_place(const TileGeom& g, uint32_t tile, uint32_t r) {
 // tiff_tiled_on_device is on, the _ex2 functions) and only from a measured tile count on.  The table of DESIGN.md 5.9
 // (tools/time_tiff_decode.py --tiled) is NOT MEASURED yet: both thresholds are TIFF_TILED_NEVER, the rule answers 0 for every tiled
 // file and set, and only an explicit ecseg_tiff_decode / ecseg_tiff_decode_batch call decodes one on the device.
+//   PackBits files (compression 32773; tiffb_packbits_kernel) parse only for a caller that asks (the handle option
+// tiff_packbits_on_device, the _ex3 functions) and have no table at all (tools/time_tiff_decode.py --packbits is NOT MEASURED): no
+// rule here names their compression, so they count in none, strips or tiles, and only an explicit call decodes one on the device.
 constexpr size_t TIFF_DEVICE_MIN_STRIPS = 1040;
 constexpr size_t TIFF_TILED_NEVER = ~(size_t)0;
 constexpr size_t TIFF_TILED_DEVICE_MIN_TILES = TIFF_TILED_NEVER;

@@ -224,13 +224,16 @@ def image_shape(path):
     return read_tiff(path).shape
 
 
-def tiff_goes_to_device(data, deflate=False, tiled=False):
+def tiff_goes_to_device(data, deflate=False, tiled=False, packbits=False):
     """The routing rule of the device reader (csrc/tiff_parse.h, the one place that states it) on the bytes of a file.  ``deflate``:
     Deflate files count too, from their own measured threshold on (ecseg_tiff_decode_routes_ex).  ``tiled``: so do tiled files, from a
-    measured tile count on (ecseg_tiff_decode_routes_ex2)."""
+    measured tile count on (ecseg_tiff_decode_routes_ex2).  ``packbits``: PackBits files parse (ecseg_tiff_decode_routes_ex3); they
+    have no measured table and count in no rule."""
     buf = np.frombuffer(data, np.uint8)
     if not buf.size:
         return False
+    if packbits:
+        return load_library().ecseg_tiff_decode_routes_ex3(buf.ctypes.data_as(C.c_void_p), buf.size, int(bool(deflate)), int(bool(tiled)), 1) == 1
     if tiled:
         return load_library().ecseg_tiff_decode_routes_ex2(buf.ctypes.data_as(C.c_void_p), buf.size, int(bool(deflate)), 1) == 1
     if deflate:
@@ -245,7 +248,8 @@ def imread(path, handle=None, deflate=False):
     or finds the file corrupt or unreadable, so that the error raised is theirs.  ``deflate``: the rule is asked with Deflate files
     counting, and the handle decodes such a file (``Handle.tiff_decode(data, deflate=True)``).  A handle with the option
     ``tiff_tiled_on_device`` on (its attribute of that name) takes tiled files: the rule is asked with them counting
-    (ecseg_tiff_decode_routes_ex2)."""
+    (ecseg_tiff_decode_routes_ex2); one with ``tiff_packbits_on_device`` on takes PackBits files, and the rule is asked with that
+    flag too (ecseg_tiff_decode_routes_ex3)."""
     if str(path).lower().endswith('.npy'):
         return np.load(path)
     if handle is not None and hasattr(handle, 'tiff_decode') and str(path).lower().endswith(('.tif', '.tiff')):
@@ -253,7 +257,10 @@ def imread(path, handle=None, deflate=False):
         try:
             with open(path, 'rb') as f:
                 data = f.read()
-            if getattr(handle, 'tiff_tiled_on_device', False):
+            if getattr(handle, 'tiff_packbits_on_device', False):
+                if tiff_goes_to_device(data, deflate=deflate, tiled=bool(getattr(handle, 'tiff_tiled_on_device', False)), packbits=True):
+                    a = handle.tiff_decode(data, deflate=True) if deflate else handle.tiff_decode(data)
+            elif getattr(handle, 'tiff_tiled_on_device', False):
                 if tiff_goes_to_device(data, deflate=deflate, tiled=True):
                     a = handle.tiff_decode(data, deflate=True) if deflate else handle.tiff_decode(data)
             elif deflate:
@@ -271,14 +278,22 @@ def imread(path, handle=None, deflate=False):
     return read_tiff(path)
 
 
-def tiff_batch_goes_to_device(datas, deflate=False, tiled=False):
+def tiff_batch_goes_to_device(datas, deflate=False, tiled=False, packbits=False):
     """The routing rule for a set of files (csrc/tiff_parse.h, the one place that states it) on their bytes -> (whether the set goes to
     the device in one ``Handle.tiff_decode_many``, per file whether the rule counts it: the files that are sent when it goes).
     ``deflate``: Deflate files count too, from their own measured threshold on (the ``_ex`` functions).  ``tiled``: so do tiled files
-    (the ``_ex2`` functions)."""
+    (the ``_ex2`` functions).  ``packbits``: PackBits files parse and count in no rule (the ``_ex3`` functions)."""
     lib = load_library()
     bufs = [d if isinstance(d, np.ndarray) else np.frombuffer(d, np.uint8) for d in datas]
     deflate, tiled = int(bool(deflate)), int(bool(tiled))
+    if packbits:
+        counts = [bool(b.size) and lib.ecseg_tiff_decode_batch_counts_ex3(b.ctypes.data_as(C.c_void_p), b.size, deflate, tiled, 1) == 1 for b in bufs]
+        sent = [b for b, c in zip(bufs, counts) if c]
+        if not sent:
+            return False, counts
+        buf, ranges = pack_file_images(sent)
+        return lib.ecseg_tiff_decode_batch_routes_ex3(buf.ctypes.data_as(C.c_void_p), buf.size, ranges.ctypes.data_as(C.c_void_p), len(ranges), deflate,
+                                                      tiled, 1) == 1, counts
     if tiled:
         counts = [bool(b.size) and lib.ecseg_tiff_decode_batch_counts_ex2(b.ctypes.data_as(C.c_void_p), b.size, deflate, 1) == 1 for b in bufs]
         sent = [b for b, c in zip(bufs, counts) if c]
@@ -296,10 +311,16 @@ def tiff_batch_goes_to_device(datas, deflate=False, tiled=False):
     return goes, counts
 
 
-def tiff_batch_counts(data):
+def tiff_batch_counts(data, deflate=False, tiled=False, packbits=False):
     """Whether the rule for a set counts this file (ecseg_tiff_decode_batch_counts: an LZW file that ecseg_tiff_decode accepts), on its
-    bytes as a uint8 array.  Touches no handle: `make metaseg`'s reader threads ask it."""
-    return bool(data.size) and load_library().ecseg_tiff_decode_batch_counts(data.ctypes.data_as(C.c_void_p), data.size) == 1
+    bytes as a uint8 array.  Touches no handle: `make metaseg`'s reader threads ask it.  The three switches: those of the ``_ex3``
+    function (all off: the function without a suffix)."""
+    if not data.size:
+        return False
+    if deflate or tiled or packbits:
+        return load_library().ecseg_tiff_decode_batch_counts_ex3(data.ctypes.data_as(C.c_void_p), data.size, int(bool(deflate)), int(bool(tiled)),
+                                                                 int(bool(packbits))) == 1
+    return load_library().ecseg_tiff_decode_batch_counts(data.ctypes.data_as(C.c_void_p), data.size) == 1
 
 
 def tiff_shape(data):
@@ -316,7 +337,8 @@ def imread_many(paths, handle=None, deflate=False):
     (ecseg_tiff_decode_batch_routes: LZW files, whatever their strip count) are decoded in one call when together they are worth it;
     every other file, and every file that call answers with None or an error, is read by ``imread(path)``, so that the samples and
     the errors are always its own.  ``deflate``: Deflate files count in the rule and are decoded by the call
-    (``Handle.tiff_decode_many(datas, deflate=True)``).  A handle with the option ``tiff_tiled_on_device`` on: as in ``imread``."""
+    (``Handle.tiff_decode_many(datas, deflate=True)``).  A handle with the option ``tiff_tiled_on_device`` or
+    ``tiff_packbits_on_device`` on: as in ``imread``."""
     out = [None] * len(paths)
     if handle is not None and hasattr(handle, 'tiff_decode_many'):
         tiffs = [(k, str(path)) for k, path in enumerate(paths) if str(path).lower().endswith(('.tif', '.tiff'))]
@@ -338,7 +360,10 @@ def imread_many(paths, handle=None, deflate=False):
                 continue
             held.append((k, pool[at:at + got]))
             at += n
-        if getattr(handle, 'tiff_tiled_on_device', False):   # (the handle option: tiled files count in the rule, and the call takes them)
+        if getattr(handle, 'tiff_packbits_on_device', False):    # (the handle option: PackBits files parse, and the call takes them)
+            goes, counts = tiff_batch_goes_to_device([d for _, d in held], deflate=deflate, tiled=bool(getattr(handle, 'tiff_tiled_on_device', False)),
+                                                     packbits=True)
+        elif getattr(handle, 'tiff_tiled_on_device', False):   # (the handle option: tiled files count in the rule, and the call takes them)
             goes, counts = tiff_batch_goes_to_device([d for _, d in held], deflate=deflate, tiled=True)
         else:
             goes, counts = tiff_batch_goes_to_device([d for _, d in held], deflate=True) if deflate else tiff_batch_goes_to_device([d for _, d in held])

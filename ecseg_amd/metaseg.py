@@ -17,7 +17,12 @@ put the bytes on disk - the same bytes; a file the device did not produce is wri
 only reads the bytes of a ``.tif`` file, and a batch of LZW files that the routing rule for a set accepts
 (ecseg_tiff_decode_batch_routes) is decoded on the GPU straight into the batch of the device call that segments it - the same
 samples; ``.npy`` inputs, Deflate, PackBits, tiled, planar and uncompressed files, sets the rule refuses and every file the device
-leaves to the host are read by the host reader as before; not with ``emit_probs``, whose device call takes decoded images).
+leaves to the host are read by the host reader as before; not with ``emit_probs``, whose device call takes decoded images),
+``tiff_read_deflate`` / ``tiff_read_tiled`` / ``tiff_read_packbits`` (false; with ``tiff_read_on_device``, ignored without: Deflate /
+tiled / PackBits input TIFFs count for the device reader too - the handle options ``tiff_deflate_on_device`` / ``tiff_tiled_on_device``
+/ ``tiff_packbits_on_device`` are on for the run and the routing rule is asked with the switch.  Deflate files count from their
+measured thresholds on, a set from 280 Deflate strips; tiled and PackBits files have no measured table, so the rule counts none and
+they stay with the Python reader - the same samples either way).
 """
 import concurrent.futures as cf
 import json
@@ -91,11 +96,17 @@ class _TiffBatch:
         return _TiffBatch(self.datas[sl], self.tshape, self.status[sl])
 
 
-def _tiff_file(p):
-    """-> _TiffFile when the rule for a set counts the file (an LZW file ecseg_tiff_decode accepts), else None: the host reader's"""
+def _tiff_kinds(device_tiffs):
+    """``device_tiffs`` of the readers -> (deflate, tiled, packbits): the config keys tiff_read_deflate / _tiled / _packbits"""
+    return tuple(device_tiffs) if isinstance(device_tiffs, tuple) else (False, False, False)
+
+
+def _tiff_file(p, kinds=(False, False, False)):
+    """-> _TiffFile when the rule for a set counts the file (an LZW file ecseg_tiff_decode accepts; with ``kinds``, what the rule counts
+    with those switches: Deflate files - tiled and PackBits files have no measured table, so none of them), else None: the host reader's"""
     try:
         data = np.fromfile(p, np.uint8)
-        if not image_io.tiff_batch_counts(data):
+        if not (image_io.tiff_batch_counts(data, *kinds) if any(kinds) else image_io.tiff_batch_counts(data)):
             return None
         return _TiffFile(p, data, image_io.tiff_shape(data))
     except Exception:
@@ -108,7 +119,7 @@ def _read(p, resume=False, device_tiffs=False):
         if done is not None:
             return done
     if device_tiffs and str(p).lower().endswith(('.tif', '.tiff')):
-        f = _tiff_file(p)
+        f = _tiff_file(p, _tiff_kinds(device_tiffs))
         if f is not None:
             return f
     img = image_io.imread(p)
@@ -379,12 +390,21 @@ def _segment_isolating(model, imgs, log, emit_probs=False, outs=None, files=None
 
 
 def run(inpath, model, image_paths, rank=0, world=1, batch_images=8, io_threads=None, log=print, stats=None, resume=False,
-        emit_probs=False, pinned_mb=2048, pinned_min_images=None, files_on_device=False, tiff_read_on_device=False):
+        emit_probs=False, pinned_mb=2048, pinned_min_images=None, files_on_device=False, tiff_read_on_device=False, tiff_read_deflate=False,
+        tiff_read_tiled=False, tiff_read_packbits=False):
     """Segment this rank's shard; returns records (one row per image of the WHOLE job after the all-gather).
     ``tiff_read_on_device``: LZW ``.tif`` inputs are decoded by the device call of their batch (host path only with ``emit_probs``:
-    the key is then without effect)."""
-    if tiff_read_on_device and not all(hasattr(m.handle, 'meta_segment_tiffs') for m in (model if isinstance(model, (list, tuple)) else [model])):
+    the key is then without effect).  ``tiff_read_deflate`` / ``tiff_read_tiled`` / ``tiff_read_packbits`` (with it; ignored
+    without): the handle options ``tiff_deflate_on_device`` / ``tiff_tiled_on_device`` / ``tiff_packbits_on_device`` are on for the
+    run and the routing rule is asked with the switch - Deflate files count from their measured thresholds on; tiled and PackBits
+    files have no measured table, count in no rule and stay with the Python reader."""
+    handles = [m.handle for m in (model if isinstance(model, (list, tuple)) else [model])]
+    if tiff_read_on_device and not all(hasattr(h, 'meta_segment_tiffs') for h in handles):
         raise ValueError('tiff_read_on_device needs the device TIFF reader (meta_segment_tiffs), which the handle in use does not have')
+    kinds = tuple(bool(k) and bool(tiff_read_on_device) and not emit_probs for k in (tiff_read_deflate, tiff_read_tiled, tiff_read_packbits))
+    if any(kinds) and not all(hasattr(h, 'set_option') for h in handles):
+        raise ValueError('tiff_read_deflate / tiff_read_tiled / tiff_read_packbits need a handle with options (set_option), which the handle in use '
+                         'does not have')
     if files_on_device and not all(hasattr(m.handle, 'meta_segment_files') for m in (model if isinstance(model, (list, tuple)) else [model])):
         raise ValueError('files_on_device needs the device file coders (meta_segment_files), which the handle in use does not have')
     start, stop, per = dist.shard_bounds(len(image_paths), rank, world)
@@ -406,10 +426,17 @@ def run(inpath, model, image_paths, rank=0, world=1, batch_images=8, io_threads=
     # (page-locking pays after ~5 uses of a buffer: not for a handful of images; pinned_min_images overrides the threshold)
     if pinned_mb > 0 and len(mine) >= (4 * batch_images if pinned_min_images is None else pinned_min_images):
         pool.start()
+    options = ('tiff_deflate_on_device', 'tiff_tiled_on_device', 'tiff_packbits_on_device')
+    turned_on = [(h, key) for h in handles for key, on in zip(options, kinds) if on and not getattr(h, key, False)]
     try:
+        for h, key in turned_on:
+            h.set_option(key, 1)                             # meta_segment_tiffs and prefetch_tiffs read them off the handle
         return _run_threads(model, mine, start, per, rank, world, batch_images, io_threads, window, pending_writes, n_ec,
-                            status, log, stats, resume, tie, emit_probs, pool, files_on_device, tiff_read_on_device and not emit_probs)
+                            status, log, stats, resume, tie, emit_probs, pool, files_on_device,
+                            (kinds if any(kinds) else True) if tiff_read_on_device and not emit_probs else False)
     finally:
+        for h, key in turned_on:
+            h.set_option(key, 0)                             # a handle goes back as it came
         pool.stop()
         sys.setswitchinterval(old_switch)
 
@@ -613,7 +640,10 @@ def _run_threads(model, mine, start, per, rank, world, batch_images, io_threads,
             """the batches of a group of _TiffFile: one of files where the rule for a set sends them, else one of images read by the host"""
             t0 = time.perf_counter()
             files = [f for _, f in group]
-            if image_io.tiff_batch_goes_to_device([f.data for f in files])[0]:
+            kinds = _tiff_kinds(device_tiffs)
+            goes = image_io.tiff_batch_goes_to_device([f.data for f in files], *kinds) if any(kinds) else \
+                image_io.tiff_batch_goes_to_device([f.data for f in files])
+            if goes[0]:
                 total, most = sum(f.data.size for f in files), max(f.data.size for f in files)
                 buf = pool.get(total, max(len(group), batch_images) * most)
                 flat, datas, at = buf if buf is not None else np.empty(total, np.uint8), [], 0
@@ -822,6 +852,15 @@ def main(argv=None):
     if not isinstance(tiff_read_on_device, bool):
         print("metaseg.tiff_read_on_device must be true or false (true: LZW input TIFFs are decoded on the device, into the batch). Exiting...")
         sys.exit(2)
+    read_kinds = {}
+    for key, what in (('tiff_read_deflate', 'Deflate'), ('tiff_read_tiled', 'tiled'), ('tiff_read_packbits', 'PackBits')):
+        read_kinds[key] = var.get(key, False)
+        if not isinstance(read_kinds[key], bool):
+            print("metaseg.%s must be true or false (true, with tiff_read_on_device: %s input TIFFs count for the device reader too). Exiting..."
+                  % (key, what))
+            sys.exit(2)
+        if not tiff_read_on_device:
+            read_kinds[key] = False                          # the key belongs to the device reader
     for sub in ('dapi', 'labels'):
         os.makedirs(os.path.join(inpath, sub), exist_ok=True)
 
@@ -855,13 +894,17 @@ def main(argv=None):
     if tiff_read_on_device and not all(hasattr(m.handle, 'meta_segment_tiffs') for m in models):
         print("metaseg.tiff_read_on_device: true needs the device TIFF reader (meta_segment_tiffs), which the handle in use does not have. Exiting...")
         sys.exit(2)
+    if any(read_kinds.values()) and not all(hasattr(m.handle, 'set_option') for m in models):
+        print("metaseg.%s: true needs a handle with options (set_option), which the handle in use does not have. Exiting..."
+              % [k for k, v in read_kinds.items() if v][0])
+        sys.exit(2)
     image_paths = get_imgs(inpath)
     print("Reading from: ", inpath)
     t0 = time.perf_counter()
     stats = {}
     rec = run(inpath, models if workers > 1 else model, image_paths, rank, world, batch_images=int(var.get('batch_images', 8)),
               io_threads=var.get('io_threads'), stats=stats, resume=bool(var.get('resume', False)), emit_probs=emit_probs,
-              pinned_mb=int(var.get('pinned_mb', 2048)), files_on_device=files_on_device, tiff_read_on_device=tiff_read_on_device)
+              pinned_mb=int(var.get('pinned_mb', 2048)), files_on_device=files_on_device, tiff_read_on_device=tiff_read_on_device, **read_kinds)
     failed = finish(inpath, image_paths, rec, rank, seconds=time.perf_counter() - t0, gpu_seconds=stats.get('gpu_seconds', 0.0))
     if native:
         dist.native_close(os.environ['ECSEG_RDZV'], rank)          # (the all-gather was the last thing every rank waited for)

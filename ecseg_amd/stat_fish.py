@@ -658,6 +658,14 @@ def main(argv=None, handle=None):
         if read_tiled and handle is not None and not hasattr(handle, 'set_option'):
             raise ConfigError('tiff_read_tiled: true needs a handle with options (set_option), which the handle in use does not have; only '
                               'tiff_read_tiled: false works on it')
+        read_packbits = var.get('tiff_read_packbits', False)
+        if not isinstance(read_packbits, bool):
+            raise ConfigError('tiff_read_packbits must be true or false (true, with tiff_read_on_device: PackBits input TIFFs count for the device reader too)')
+        if not tiff_read_on_device:
+            read_packbits = False                            # the key belongs to the device reader
+        if read_packbits and handle is not None and not hasattr(handle, 'set_option'):
+            raise ConfigError('tiff_read_packbits: true needs a handle with options (set_option), which the handle in use does not have; only '
+                              'tiff_read_packbits: false works on it')
         write_batch = var.get('tiff_write_batch', 1)
         if isinstance(write_batch, bool) or not isinstance(write_batch, int) or write_batch < 1:
             raise ConfigError('tiff_write_batch must be a positive integer (how many images have their TIFF files encoded in one call of the '
@@ -707,6 +715,9 @@ def main(argv=None, handle=None):
     tiled_before = bool(getattr(handle, 'tiff_tiled_on_device', False))
     if read_tiled and not tiled_before:
         handle.set_option('tiff_tiled_on_device', 1)         # image_io.imread / imread_many read it off the handle
+    packbits_before = bool(getattr(handle, 'tiff_packbits_on_device', False))
+    if read_packbits and not packbits_before:
+        handle.set_option('tiff_packbits_on_device', 1)      # (the same)
     rows, failed, seen = [], [], {}
     mask_of = lambda p: os.path.join(masks, os.path.basename(p)[:-4] + '.tif')
     ahead = {}                                               # tiff_read_batch: image path -> (image, mask) read with its chunk, until the image is done
@@ -847,8 +858,11 @@ def main(argv=None, handle=None):
     finally:
         if own:
             handle.close()
-        elif read_tiled and not tiled_before:
-            handle.set_option('tiff_tiled_on_device', 0)     # a handle that was handed in goes back as it came
+        else:
+            if read_tiled and not tiled_before:
+                handle.set_option('tiff_tiled_on_device', 0)     # a handle that was handed in goes back as it came
+            if read_packbits and not packbits_before:
+                handle.set_option('tiff_packbits_on_device', 0)
     with open(os.path.join(out_root, 'stat_fish_lsq.csv'), 'w') as f:
         n_probe = seen.get('probes', len(PROBE_NAMES))
         f.write(csvio.csv_text(csv_columns(n_probe), widen_rows(rows) if n_probe == 3 else rows))

@@ -73,6 +73,10 @@ extern "C" {
 /* (still 5 - additive: option "tiff_tiled_on_device" with ecseg_tiff_decode_routes_ex2, ecseg_tiff_decode_batch_routes_ex2,
  * ecseg_tiff_decode_batch_counts_ex2 and ecseg_tiff_decode_batch_bytes_ex2, tiled TIFF files decoded on the device behind an option
  * that is off by default; nothing existing changed.) */
+/* (still 5 - additive: option "tiff_packbits_on_device" with ecseg_tiff_decode_routes_ex3, ecseg_tiff_decode_batch_routes_ex3,
+ * ecseg_tiff_decode_batch_counts_ex3 and ecseg_tiff_decode_batch_bytes_ex3, PackBits files decoded on the device behind an option that
+ * is off by default; ecseg_meta_segment_tiffs, ecseg_meta_segment_tiffs_files and ecseg_prefetch_tiffs read the three tiff_*_on_device
+ * options of their handle; with every option at its default nothing changed.) */
 /* (still 5 - additive: ecseg_interseg_batch, the regions, crops and classifiers of many interSeg images in one call; nothing existing
  * changed.  The number stays where every additive entry above left it: a caller of version 5 runs unchanged.) */
 /* (still 5 - additive: ecseg_stitch_stages_debug, ecseg_preprocess_stages_debug and ecseg_otsu_debug, the stitch with its tie-risk count
@@ -242,7 +246,8 @@ int ecseg_set_images_per_group(ecseg_ctx* h, int n);
  * "tiff_deflate_on_device" (0 (default): ecseg_tiff_decode and ecseg_tiff_decode_batch leave Deflate files to the host,
  * ECSEG_E_UNSUPPORTED; 1: they decode them on the device - see "TIFF files decoded on the device" below), "tiff_tiled_on_device"
  * (0 (default): the two leave tiled files to the Python reader, ECSEG_E_UNSUPPORTED without a shape; 1: they decode them on the
- * device - the same section). */
+ * device - the same section), "tiff_packbits_on_device" (0 (default): the two leave PackBits files to the Python reader,
+ * ECSEG_E_UNSUPPORTED without a shape; 1: they decode them on the device - the same section). */
 int ecseg_set_option(ecseg_ctx* h, const char* key, int value);
 
 /* ---- meta_preprocess (src/image_tools.py:86-101) ---------------------------------------------------------- */
@@ -675,8 +680,8 @@ int ecseg_tiff_decode_batch_counts(const uint8_t* file, long long n_bytes);
  * checked), mixed freely with LZW and uncompressed files in a batch - and return ECSEG_OK or ECSEG_E_INVALID for them where they
  * returned ECSEG_E_UNSUPPORTED, by the host reader's rules (ecseg_tiff_read: a short stream zero-filled, a long one cut, every zlib
  * data error corrupt; a stream that ends before the strip is full and before its own end is corrupt, as uncompress of zlib 1.2.9 and
- * later has it).  PackBits and BigTIFF files stay ECSEG_E_UNSUPPORTED, and so do tiled files without the option below;
- * ecseg_meta_segment_tiffs does not read the option.
+ * later has it).  BigTIFF files stay ECSEG_E_UNSUPPORTED, and so do tiled and PackBits files without the options below;
+ * ecseg_meta_segment_tiffs reads the option off its handle as the two do.
  *   The four functions above that take no handle answer as before; these take the switch as `deflate` (0: the same answers).  With
  * it a Deflate file counts from its own thresholds on (csrc/tiff_parse.h, the Deflate tables of DESIGN.md 5.9: a single file from
  * 1040 strips, a set from 280 Deflate strips together, the smallest measured counts at which the device call's maximum is below
@@ -691,7 +696,7 @@ long long ecseg_tiff_decode_batch_bytes_ex(const uint8_t* files, long long files
  * and ecseg_tiff_decode_batch on that handle take a tiled file whose tile extents are positive multiples of 16 (of at most 2^20),
  * chunky (or one sample per pixel), 8 or 16 unsigned bits, uncompressed or LZW - Deflate with "tiff_deflate_on_device" on as well -,
  * predictor 1 or 2, without strip tags, with a tile table entry for each of its ceil(H / TileLength) * ceil(W / TileWidth) tiles and
- * tiles below 2 GiB.  Every other tiled file stays ECSEG_E_UNSUPPORTED (BigTIFF, PackBits tiles, planar RGB, float samples, a short
+ * tiles below 2 GiB.  Every other tiled file stays ECSEG_E_UNSUPPORTED (BigTIFF, PackBits tiles without "tiff_packbits_on_device", planar RGB, float samples, a short
  * tile table, strip and tile tags together), as does every tiled file with the option off.  A tile is a strip of the batch grid - a
  * wave per tile, beside the strips of other files in the same launch - whose stream decodes into a staging slot of one tile in the
  * call arena; tiffb_untile_kernel (csrc/tiff_untile.h) then puts every tile row in its place in the raster: byte order, the horizontal
@@ -702,7 +707,7 @@ long long ecseg_tiff_decode_batch_bytes_ex(const uint8_t* files, long long files
  * Like that reader's slice, a tile's bytes are clamped to the file: an offset behind the file or a count that leaves it is a shorter
  * or empty stream - zeros for an LZW or uncompressed tile, ECSEG_E_INVALID for a Deflate one - not an error of its own.  (One
  * difference remains, in the inflate routine shared with strips: a Deflate stream that gave the whole tile and ends inside its
- * trailer is taken, where zlib.decompress refuses it.)  ecseg_meta_segment_tiffs does not read the option.
+ * trailer is taken, where zlib.decompress refuses it.)  ecseg_meta_segment_tiffs reads the option off its handle as the two do.
  *   The handle-free functions get the switch as `tiled` beside `deflate` (both 0: the answers of the functions without a suffix).
  * A tiled file counts in the two routing rules only from a measured tile count on (csrc/tiff_parse.h; tools/time_tiff_decode.py
  * --tiled).  That table is NOT MEASURED yet: the rules answer 0 for every tiled file and every set of them, and only
@@ -712,6 +717,27 @@ int ecseg_tiff_decode_routes_ex2(const uint8_t* file, long long n_bytes, int def
 int ecseg_tiff_decode_batch_routes_ex2(const uint8_t* files, long long files_bytes, const int64_t* file_ranges, int n_files, int deflate, int tiled);
 int ecseg_tiff_decode_batch_counts_ex2(const uint8_t* file, long long n_bytes, int deflate, int tiled);
 long long ecseg_tiff_decode_batch_bytes_ex2(const uint8_t* files, long long files_bytes, const int64_t* file_ranges, int n_files, int deflate, int tiled);
+/* PackBits files (compression 32773: older ImageJ and Photoshop exports) on the device, opt-in.  ecseg_set_option(h,
+ * "tiff_packbits_on_device", 1) (default 0): ecseg_tiff_decode and ecseg_tiff_decode_batch on that handle take such a file, strips
+ * or - with "tiff_tiled_on_device" on as well - tiles, held to every other rule of the readers above: a wave per strip or tile in a
+ * kernel of its own beside the LZW and Deflate ones (tiffb_packbits_kernel; csrc/tiff_packbits_strip.h: the header walk in every
+ * lane, the up to 128 bytes of a run written by the lanes), byte order and predictor by the code that serves the other codecs, a
+ * tile through its staging slot and tiffb_untile_kernel.  With the option off every PackBits file is ECSEG_E_UNSUPPORTED without a
+ * shape, as before.
+ *   The oracle is the Python reader (image_io.read_tiff with _packbits_decode), the one reader of PackBits files: header h < 128:
+ * h + 1 literal bytes; h > 128: the next byte 257 - h times; 128: nothing.  That decoder raises for no stream - one that ends early
+ * gives what it has and zeros behind, a run that would pass the strip's end is cut there, bytes left over are not looked at - so no
+ * PackBits stream is ECSEG_E_INVALID; a strip that starts behind the end of the file is, as for every codec.
+ *   The handle-free functions get the switch as `packbits` beside `deflate` and `tiled` (all 0: the answers of the functions without
+ * a suffix).  No table of tools/time_tiff_decode.py --packbits is measured: with the switch a PackBits file parses,
+ * and it counts in no routing rule, strips or tiles; only an explicit call decodes one on the device.
+ * ecseg_tiff_decode_batch_bytes_ex3: the arena bytes with PackBits files taken (what an LZW file of the same tags needs). */
+int ecseg_tiff_decode_routes_ex3(const uint8_t* file, long long n_bytes, int deflate, int tiled, int packbits);
+int ecseg_tiff_decode_batch_routes_ex3(const uint8_t* files, long long files_bytes, const int64_t* file_ranges, int n_files, int deflate, int tiled,
+                                       int packbits);
+int ecseg_tiff_decode_batch_counts_ex3(const uint8_t* file, long long n_bytes, int deflate, int tiled, int packbits);
+long long ecseg_tiff_decode_batch_bytes_ex3(const uint8_t* files, long long files_bytes, const int64_t* file_ranges, int n_files, int deflate, int tiled,
+                                            int packbits);
 
 /* ---- label PNG files encoded on the device ----------------------------------------------------------------------------------- */
 /* The file ecseg_png_write_labels would write for each of n_img label images, byte for byte (signature, IHDR, one IDAT, IEND), as
@@ -764,11 +790,14 @@ int ecseg_get_file_timings(ecseg_ctx* h, float* ms_out /* [2] */);
 /* ecseg_meta_segment with the input files themselves as its input: the packed file table of ecseg_tiff_decode_batch (files, files_bytes,
  * file_ranges, n_files) and the batch's common shape.  The strips of every file decode on the device, a wave per strip, straight into
  * the call's input buffer (raster i at i * H * W * C * bytes_per_sample); pre-processing, U-Net, clean-up and count run behind them as
- * in ecseg_meta_segment, and the host decodes nothing.  status[i] is what ecseg_tiff_decode returns for file i alone (ECSEG_OK,
- * ECSEG_E_INVALID, ECSEG_E_UNSUPPORTED); a file that decodes but whose H, W, samples per pixel or bits are not the call's has
+ * in ecseg_meta_segment, and the host decodes nothing.  status[i] is what ecseg_tiff_decode returns for file i alone ON THIS HANDLE
+ * (ECSEG_OK, ECSEG_E_INVALID, ECSEG_E_UNSUPPORTED): the options "tiff_deflate_on_device", "tiff_tiled_on_device" and
+ * "tiff_packbits_on_device" are read as ecseg_tiff_decode reads them - all 0 (the default): LZW and uncompressed strips alone, every
+ * other file ECSEG_E_UNSUPPORTED; on: Deflate strips, tiles and PackBits files decode into the same slots, by the same kernels.  A file that decodes but whose H, W, samples per pixel or bits are not the call's has
  * ECSEG_E_INVALID.  An image whose status is not ECSEG_OK is the all-zero image - its input slot is cleared on the device before the
  * pre-processing, so that nothing of an earlier call reaches an output -, its n_ec is -1 and (_files) its two file lengths are 0;
- * every other image has exactly what ecseg_meta_segment gives for the samples ecseg_tiff_read returns, byte for byte.  The call
+ * every other image has exactly what ecseg_meta_segment gives for the samples image_io.read_tiff returns (ecseg_tiff_read's, where
+ * that reader takes the file), byte for byte.  The call
  * returns ECSEG_OK when it ran, whatever the status words say.  ECSEG_E_INVALID: the argument errors of ecseg_meta_segment and of
  * ecseg_tiff_decode_batch (a null table, a range that overlaps the one in front or leaves the files), 65536 images or more, 2^31
  * strips or rows or more.  ecseg_meta_segment_tiffs_files: the same with the two file tables, the capacity protocol and the timings
@@ -785,8 +814,10 @@ int ecseg_get_read_timings(ecseg_ctx* h, float* ms_out /* [1] */);
 /* The analogue of ecseg_prefetch_input: names the files of the ecseg_meta_segment_tiffs[_files] call AFTER the coming one, as that call
  * will pass them (page-locked memory, unchanged until then).  The coming ecseg_meta_segment_tiffs[_files] call uploads them on the
  * input stream and decodes them there into the spare input buffer, under its own kernels; the call after it recognises them by
- * (pointer, bytes, ranges, n, shape) and skips upload and decode.  Any other call on the handle withdraws them, as does files == null
- * or n_files == 0.  Results are those of calls without it. */
+ * (pointer, bytes, ranges, n, shape) and the state of the three tiff_*_on_device options under which they were decoded, and skips
+ * upload and decode.  Any other call on the handle withdraws them, as does files == null or n_files == 0, and so does a change of one
+ * of those options in between: the call then decodes its files itself, under the options as they stand.  Results are those of calls
+ * without it. */
 int ecseg_prefetch_tiffs(ecseg_ctx* h, const uint8_t* files, long long files_bytes, const int64_t* file_ranges, int n_files, int H, int W, int C,
                          int bytes_per_sample);
 

@@ -11,6 +11,8 @@ milliseconds per image of the two file coders, and ``verdict`` = the minimum on 
 ``--tiff-read-on-device``: the same for the config key ``tiff_read_on_device`` (batches of LZW input files decoded on the device, into the
 U-Net's batch); ``alternate`` alternates this key with ``--files-on-device`` held at off or on, ``verdict`` is then this key's, and
 every pass reports ``tiff_device_images`` and the decode's device milliseconds per image (``device_ms_per_image['tiff_decode']``).
+``--input-compression deflate``: the input files are written with Adobe Deflate, and a pass with ``tiff_read_on_device`` on has
+``tiff_read_deflate`` on beside it, so that ``--tiff-read-on-device alternate`` compares the host reader and the device on a Deflate folder.
 """
 import argparse
 import json
@@ -46,7 +48,9 @@ def main():
     ap.add_argument('--keep', default=None)
     ap.add_argument('--workers', type=int, default=1, help='handles (device threads) on the GPU: config key device_workers')
     ap.add_argument('--pinned-mb', type=int, default=2048, help='page-locked host memory for the batch buffers (config key pinned_mb; 0: none)')
-    ap.add_argument('--input-compression', default='tiff_lzw', choices=('tiff_lzw', 'raw'), help='compression of the generated input TIFFs (raw = uncompressed, as many microscopes write them)')
+    ap.add_argument('--input-compression', default='tiff_lzw', choices=('tiff_lzw', 'raw', 'deflate'),
+                    help='compression of the generated input TIFFs (raw = uncompressed, as many microscopes write them; deflate: Adobe Deflate, and '
+                         'the config key tiff_read_deflate goes with tiff_read_on_device, so that --tiff-read-on-device alternate runs on a Deflate folder)')
     ap.add_argument('--weights', default='random', choices=('random', 'smooth'),
                     help="random: seeded random weights (speckled labels: the slowest case for the label PNG coder); smooth: the fitted base-16 "
                          "stand-in for a trained model (tests/golden/smooth_b16_f16.npz: blobs, as real label maps)")
@@ -78,7 +82,7 @@ def main():
             os.unlink(os.path.join(inp, f))
     for i in range(0 if have else a.n):
         img = np.roll(base[i % 8], (31 * (i // 8), 17 * (i // 8)), axis=(0, 1))
-        Image.fromarray(img).save(os.path.join(inp, 'img%04d.tif' % i), compression=a.input_compression)
+        Image.fromarray(img).save(os.path.join(inp, 'img%04d.tif' % i), compression='tiff_adobe_deflate' if a.input_compression == 'deflate' else a.input_compression)
     t_gen = time.perf_counter() - t0
     in_bytes = sum(os.path.getsize(os.path.join(inp, f)) for f in os.listdir(inp))
     if a.weights == 'smooth':
@@ -116,7 +120,7 @@ def main():
             st = {}
             c0, t0 = cgroup_cpu(), time.perf_counter()
             r = metaseg.run(inp, [model] + extra if extra else model, utils.get_imgs(inp), batch_images=a.batch, io_threads=a.io_threads,
-                            log=lambda *x: None, stats=st, pinned_mb=a.pinned_mb, files_on_device=key, tiff_read_on_device=tkey)
+                            log=lambda *x: None, stats=st, pinned_mb=a.pinned_mb, files_on_device=key, tiff_read_on_device=tkey, tiff_read_deflate=bool(tkey) and a.input_compression == 'deflate')
             return r, time.perf_counter() - t0, c0, cgroup_cpu(), st
 
         by_key = []
@@ -124,7 +128,7 @@ def main():
         for key, tkey in [(k, t) for k in values[a.files_on_device] for t in values[a.tiff_read_on_device]]:
             if key or tkey:                                  # (the file coders' and the decoder's arenas and page-locked buffers: first use is not the rate)
                 metaseg.run(warm, model, utils.get_imgs(warm), batch_images=a.batch, log=lambda *x: None, pinned_mb=a.pinned_mb,
-                            pinned_min_images=0, files_on_device=key, tiff_read_on_device=tkey)
+                            pinned_min_images=0, files_on_device=key, tiff_read_on_device=tkey, tiff_read_deflate=bool(tkey) and a.input_compression == 'deflate')
             rec, dt, cg0, cg1, stats = one_pass(key, tkey)
             by_key.append({'files_on_device': key, 'tiff_read_on_device': tkey, 'tiff_device_images': stats.get('tiff_device_images', 0), 'seconds': round(dt, 3), 'images_per_s': round(a.n / dt, 2),
                            'cpu_ms_per_image': None if not (cg0 and cg1) else round(1e3 * (cg1['usage_s'] - cg0['usage_s']) / a.n, 2),
@@ -149,7 +153,7 @@ def main():
     print(json.dumps({'files_on_device': a.files_on_device, 'tiff_read_on_device': a.tiff_read_on_device, 'verdict_on': judged, 'main_by_key': by_key,
                       'verdict': None if not (offs and ons) else {'off_max': max(offs), 'on_min': min(ons), 'on_wins': min(ons) > max(offs)},
                       'what': '`make metaseg` loop: %d RGB %s TIFF files (1040x1392) -> dapi/*.tif, labels/*.png, labels/*.npy (int64), records'
-                              % (a.n, 'LZW' if a.input_compression == 'tiff_lzw' else 'uncompressed'), 'images': a.n, 'unet_base': a.base, 'weights': a.weights, 'batch_images': a.batch, 'device_workers': a.workers, 'pinned_mb': a.pinned_mb,
+                              % (a.n, {'tiff_lzw': 'LZW', 'deflate': 'Deflate'}.get(a.input_compression, 'uncompressed')), 'images': a.n, 'unet_base': a.base, 'weights': a.weights, 'batch_images': a.batch, 'device_workers': a.workers, 'pinned_mb': a.pinned_mb,
                       'pinned_pool': stats.get('pinned_pool'), 'warmup': 'one full batch per handle' if a.warm_full else 'one image',
                       'io_threads': a.io_threads or 'default', 'cpu_count': os.cpu_count(),
                       'seconds': round(dt, 3), 'images_per_s': round(a.n / dt, 2),

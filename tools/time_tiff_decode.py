@@ -4,6 +4,7 @@
     python tools/time_tiff_decode.py --batch [--passes 5] [--limit 300] [--ks 1,2,4,8,16,32]
     python tools/time_tiff_decode.py --deflate [--batch] ...
     python tools/time_tiff_decode.py --tiled [--batch] [--deflate] ...
+    python tools/time_tiff_decode.py --packbits [--batch] ...
 
 A 1040 x 1392 RGB scene of the stat_fish generator (tests/stat_fish_cases.py ``full_size_scene``) is written with LZW and the
 horizontal predictor at 1, 5, 15, 64 and 1040 rows per strip, and once uncompressed.  Per file: the host reader from the page
@@ -38,6 +39,12 @@ scenes with only the rule's verdict replaced.  Every cell is a child process of 
 cell wins only where the device's maximum is below the host's minimum, and the thresholds of csrc/tiff_parse.h
 (TIFF_TILED_DEVICE_MIN_TILES, TIFF_TILED_BATCH_DEVICE_MIN_TILES) are the smallest measured tile counts that win - a tile size that was
 not measured is never counted.
+
+--packbits: the table for PackBits strips (compression 32773; handle option tiff_packbits_on_device; tiffb_packbits_kernel): the same
+scene written by the tests' PackBits writer (tests/tiff_packbits_cases.py) at 1, 5 and 15 rows per strip with the horizontal
+predictor, the same shape of table as --deflate: ``image_io.imread(path)`` without a handle (the Python reader, the only host reader of
+PackBits) against ``Handle.tiff_decode`` with the option on - with --batch ``imread_many`` over k = --ks such scenes with only the
+rule's verdict replaced.  No rule of csrc/tiff_parse.h counts a PackBits file until this table is measured.
 """
 import argparse
 import json
@@ -283,6 +290,74 @@ def tiled_main(a):
     print(json.dumps(dict(cells_where_the_device_maximum_is_below_the_host_minimum=[[r['tile'], r['k'], r['tiles']] for r in rows if r['wins']])))
 
 
+PACKBITS_ROWS = (1, 5, 15)                                   # rows per strip: the plans of the LZW tables
+
+
+def packbits_one(rps, k, passes, batch):
+    """The child: k scenes as PackBits strips at one plan (horizontal predictor), read by image_io.imread without a handle - the Python
+    reader, the only host reader of PackBits - and on the device (handle option tiff_packbits_on_device) -> one JSON line."""
+    import stat_fish_cases as cases
+    import tiff_packbits_cases as pc
+    from ecseg_amd import image_io
+    from ecseg_amd._lib import Handle
+    with tempfile.TemporaryDirectory() as tmp:
+        paths = []
+        for j in range(k):
+            img, _ = cases.full_size_scene(100 + j)
+            paths.append(os.path.join(tmp, 'packbits%d_%d.tif' % (rps, j)))
+            with open(paths[-1], 'wb') as f:
+                f.write(pc.strip_file(np.ascontiguousarray(img), rps, predictor=2))
+        datas = [open(p, 'rb').read() for p in paths]
+        strips = k * -(-img.shape[0] // rps)
+        host = []
+        for rep in range(passes + 1):
+            t0 = time.perf_counter()
+            want = [image_io.imread(p) for p in paths]
+            if rep:
+                host.append((time.perf_counter() - t0) * 1e3)
+        gpu = Handle(0)
+        gpu.set_option('tiff_packbits_on_device', 1)
+        if batch:
+            goes, _ = image_io.tiff_batch_goes_to_device(datas, packbits=True)
+            rule = image_io.tiff_batch_goes_to_device            # the rule's questions are asked and timed, only the verdict is replaced
+            image_io.tiff_batch_goes_to_device = lambda datas, **kw: (rule(datas, **kw) and True, [True] * len(datas))
+        else:
+            goes = image_io.tiff_goes_to_device(datas[0], packbits=True)
+        call, kern = [], []
+        for rep in range(passes + 1):
+            t0 = time.perf_counter()
+            got = image_io.imread_many(paths, handle=gpu) if batch else [gpu.tiff_decode(datas[0])]
+            if rep:
+                call.append((time.perf_counter() - t0) * 1e3)
+                kern.append(gpu.timings()['count'])
+        assert all(isinstance(g, np.ndarray) and g.dtype == w.dtype and np.array_equal(g, w) for g, w in zip(got, want))
+        out = dict(rows_per_strip=rps, k=k, strips=strips, codec='packbits', bytes=sum(len(d) for d in datas), rule_sends_it=bool(goes),
+                   host_imread_ms=stats(host), device_call_ms=stats(call), device_kernel_ms=stats(kern))
+        out['wins'] = out['device_call_ms']['max'] < out['host_imread_ms']['min']
+        gpu.close()
+    print(json.dumps(out), flush=True)
+
+
+def packbits_main(a):
+    rows = []
+    for rps in PACKBITS_ROWS:
+        for k in (a.ks if a.batch else [1]):
+            cell = dict(rows_per_strip=rps, k=k)
+            try:
+                r = subprocess.run([sys.executable, os.path.abspath(__file__), '--packbits-one', '%d:%d' % (rps, k), '--passes', str(a.passes)] +
+                                   (['--batch'] if a.batch else []), capture_output=True, text=True, timeout=a.limit)
+            except subprocess.TimeoutExpired:
+                print(json.dumps(dict(cell, device='ended at the time limit of %g s' % a.limit)), flush=True)
+                return                                       # a hung device run: nothing more is started on the device
+            if r.returncode != 0:
+                print(json.dumps(dict(cell, failed=r.returncode, stderr=r.stderr[-2000:])), flush=True)
+                return
+            line = r.stdout.strip().splitlines()[-1]
+            print(line, flush=True)
+            rows.append(json.loads(line))
+    print(json.dumps(dict(cells_where_the_device_maximum_is_below_the_host_minimum=[[r['rows_per_strip'], r['k'], r['strips']] for r in rows if r['wins']])))
+
+
 def batch_main(a):
     rows = []
     for plan in BATCH_PLANS:
@@ -314,6 +389,8 @@ def main():
     ap.add_argument('--batch-one')
     ap.add_argument('--tiled', action='store_true')
     ap.add_argument('--tiled-one')
+    ap.add_argument('--packbits', action='store_true')
+    ap.add_argument('--packbits-one')
     ap.add_argument('--ks', type=lambda v: [int(x) for x in v.split(',')], default=[1, 2, 4, 8, 16, 32])
     a = ap.parse_args()
     if a.tiled_one:
@@ -321,6 +398,11 @@ def main():
         return tiled_one(int(tile), int(k), a.passes, a.deflate, a.batch)
     if a.tiled:
         return tiled_main(a)
+    if a.packbits_one:
+        rps, k = a.packbits_one.split(':')
+        return packbits_one(int(rps), int(k), a.passes, a.batch)
+    if a.packbits:
+        return packbits_main(a)
     if a.one:
         return one(a.one, a.passes, a.deflate)
     if a.batch_one:
