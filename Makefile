@@ -130,5 +130,15 @@ asan_min_cut_regions:
 	    tools/asan/min_cut_regions_check.cpp -o $(MIN_CUT_REGIONS_CHECK)
 	$(MIN_CUT_REGIONS_CHECK)
 
+# and for fish_distance_calculation.batch: the layout header of ecseg_fish_distances_batch (csrc/fishdist_batch.h) - the global pixel
+# axis, the runs of tiles and blocks with their lookup, the two-part buffer, the groups and the limits - over seeded shape lists with
+# extents of 1 and ragged tiles; tests/test_fish_distance_batch.py builds and runs it.  FISHDIST_BATCH_CHECK: where the program is put
+FISHDIST_BATCH_CHECK ?= /tmp/ecseg_fishdist_batch_check
+.PHONY: asan_fishdist_batch
+asan_fishdist_batch:
+	g++ -std=c++17 -O1 -g -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=all \
+	    tools/asan/fishdist_batch_check.cpp -o $(FISHDIST_BATCH_CHECK)
+	$(FISHDIST_BATCH_CHECK)
+
 clean:
 	rm -rf __pycache__ ecseg_amd/csrc/*.o ecseg_amd/libecseg_*.so

@@ -39,6 +39,7 @@ EXPORTS = [
     'ecseg_stat_fish_batch', 'ecseg_stat_fish_batch_bytes',
     'ecseg_min_cut_regions',
     'ecseg_scratch_fill_debug',
+    'ecseg_fish_distances_batch',
 ]
 
 
@@ -156,6 +157,7 @@ def load_library():
     lib.ecseg_iseg_classifier_inputs_debug.argtypes = [vp, vp, i32, vp, vp, i32, vp, i32, vp, vp]
     lib.ecseg_interseg_batch.argtypes = [vp, vp, vp, vp, C.c_longlong, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.ecseg_fish_distances.argtypes = [vp, vp, i32, i32, u8p, i32, i32, i32, i32, vp, C.POINTER(C.c_int32)]
+    lib.ecseg_fish_distances_batch.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(vp), vp, i32, i32, i32, vp, vp, vp]
     lib.ecseg_fish_spots.argtypes = [vp, vp, i32, i32, u8p, i32, vp, i32, vp, i32, C.c_double, vp, i32, i32, i32, vp, vp, vp,
                                      C.POINTER(C.c_int32)]
     lib.ecseg_fish_render.argtypes = [vp, u8p, i32, i32, i32, vp, u8p, i32, u8p, vp, vp, vp]
@@ -1022,6 +1024,64 @@ class Handle:
             if n.value <= cap:
                 return rec[:n.value]
             cap = n.value
+
+    FISH_DISTANCES_BATCH_MAX_IMAGES = 8192
+
+    def fish_distances_batch_raw(self, labels, lsqs, fish_channel, centromere_channel, record_capacity):
+        """ecseg_fish_distances_batch as it is: contiguous (H, W) int32 label maps and (H, W, C) uint8 images -> (records int64
+        (record_capacity, 8) - written only when the chunk's cells fit -, n_cells (n,) int32, status (n,) int32)."""
+        n = len(labels)
+        shapes = np.zeros((max(n, 1), 3), np.int32)
+        for i, im in enumerate(lsqs):
+            shapes[i] = im.shape
+        cap = int(record_capacity)
+        rec = np.zeros((max(cap, 1), 8), np.int64)
+        n_cells, status = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
+        lp = (C.c_void_p * max(n, 1))(*[a.ctypes.data for a in labels])
+        ip = (C.c_void_p * max(n, 1))(*[a.ctypes.data for a in lsqs])
+        self._check(self.lib.ecseg_fish_distances_batch(self.h, n, lp, ip, _ptr(shapes), int(fish_channel), int(centromere_channel), cap,
+                                                        _ptr(rec), _ptr(n_cells), _ptr(status)), 'ecseg_fish_distances_batch')
+        return rec[:cap], n_cells[:n], status[:n]
+
+    def fish_distances_many(self, labels, lsqs, fish_channel, centromere_channel, record_capacity=4096):
+        """``fish_distances`` for a list of images of any extents in one device call (ecseg_fish_distances_batch).  Returns one entry
+        per image: the int64 (n_cells, 8) records ``fish_distances`` returns, or the ``EcsegError`` (code -1) it raises for that image
+        alone - a label above H * W.  The error is returned, not raised: the other images of the chunk keep their answers.
+        ``record_capacity``: room for the records of the whole chunk on the first call; a chunk holding more goes once more with the
+        room it reported.  Lists longer than ``FISH_DISTANCES_BATCH_MAX_IMAGES`` go in several calls."""
+        if len(labels) != len(lsqs):
+            raise ValueError('fish_distances_many takes one lsq image per label map')
+        labs, ims = [], []
+        for lab, im in zip(labels, lsqs):
+            lab = np.ascontiguousarray(lab)
+            if lab.dtype != np.int32:
+                if lab.dtype.kind not in 'iu' or (lab.size and (int(lab.max()) > 2 ** 31 - 1 or int(lab.min()) < -2 ** 31)):
+                    raise ValueError('fish_distances_many takes integer labels that fit int32')
+                lab = lab.astype(np.int32)
+            im = _u8(im)
+            if lab.ndim != 2 or im.ndim != 3 or im.shape[:2] != lab.shape:
+                raise ValueError('fish_distances_many takes (H, W) label maps and (H, W, C) images of the same extent')
+            labs.append(lab)
+            ims.append(im)
+        out = []
+        for i0 in range(0, len(labs), self.FISH_DISTANCES_BATCH_MAX_IMAGES):
+            sl = slice(i0, i0 + self.FISH_DISTANCES_BATCH_MAX_IMAGES)
+            cap = int(record_capacity)
+            rec, n_cells, status = self.fish_distances_batch_raw(labs[sl], ims[sl], fish_channel, centromere_channel, cap)
+            if int(n_cells.sum()) > cap:
+                cap = int(n_cells.sum())
+                rec, n_cells, status = self.fish_distances_batch_raw(labs[sl], ims[sl], fish_channel, centromere_channel, cap)
+            at = 0
+            for lab, k, st in zip(labs[sl], n_cells.tolist(), status.tolist()):
+                if st != 0:
+                    e = EcsegError('ecseg_fish_distances failed (%d): fish_distances: the label map holds a label larger than H * W = %d '
+                                   '(renumber the labels by rank first)' % (st, lab.size))
+                    e.code = st
+                    out.append(e)
+                else:
+                    out.append(rec[at:at + k].copy())
+                at += k
+        return out
 
     # ---- stat_fish -------------------------------------------------------------------------------------
     FISH_SPOT_INT64 = 24

@@ -49,6 +49,12 @@ __device__ __forceinline__ StatTile stat_tile(int W) {
     return StatTile{xb, xb + (threadIdx.x & 63u),
                     (int)(blockIdx.x / tiles_x) * (4 * CELL_ROWS_PER_WAVE) + (int)(threadIdx.x >> 6) * CELL_ROWS_PER_WAVE};
 }
+// ... and of tile `tile` of an image that shares its grid with others (fishdist_batch.h: the workgroup looks its image up first)
+__device__ __forceinline__ StatTile stat_tile_at(unsigned tile, int W) {
+    const unsigned tiles_x = ((unsigned)W + 63u) / 64u;
+    const unsigned xb = (tile % tiles_x) * 64u;
+    return StatTile{xb, xb + (threadIdx.x & 63u), (int)(tile / tiles_x) * (4 * CELL_ROWS_PER_WAVE) + (int)(threadIdx.x >> 6) * CELL_ROWS_PER_WAVE};
+}
 inline unsigned stat_tiles(int H, int W) {
     return (((unsigned)W + 63u) / 64u) * (((unsigned)H + 4 * CELL_ROWS_PER_WAVE - 1) / (4 * CELL_ROWS_PER_WAVE));
 }

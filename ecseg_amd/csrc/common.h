@@ -7,6 +7,7 @@
 #include "scratch.h"
 #include "iseg_batch.h"
 #include "fish_batch.h"
+#include "fishdist_batch.h"
 #include "mincut_regions.h"
 #include "tiff_decode_batch.h"
 #include "tiff_encode_batch.h"
@@ -396,6 +397,14 @@ inline FishDistBufs fishdist_bufs(Carver& c, const CellIndexBufs& cells, int H, 
 // of ecseg_fish_distances to rec.  lsq: (H, W, C) uint8; fi / ci: FISH and centromere channel.
 hipError_t run_fishdist_records(int32_t* labels, const uint8_t* lsq, int H, int W, int C, int fi, int ci, int n, const FishDistBufs& b,
                                 hipStream_t s);
+
+// A chunk of images (ecseg_fish_distances_batch; layout, table and buffers in fishdist_batch.h).  b.lab holds the label maps and b.lsq
+// the rasters where the table has them, b.tab the rows.  run_fishdist_batch_open builds the dense cell index of every image with one
+// scan and leaves b.plan ((n + 1, 2) int32: per image its first cell and 1 = a label above H * W, such an image holding no cell; the
+// last pair: the chunk's cells).  run_fishdist_batch_records, once the caller has carved c for those cells (partials = cells *
+// fishdist_slices(cells)), relabels b.lab in place and writes the records of all images back to back to c.rec.
+hipError_t run_fishdist_batch_open(const FdbLayout& L, const FdbPixelBufs& b, hipStream_t s);
+hipError_t run_fishdist_batch_records(const FdbLayout& L, const FdbPixelBufs& b, const FdbCellBufs& c, int cells, int fi, int ci, hipStream_t s);
 
 // ---- launcher implemented in fishspot_kernels.hip (src/stat_fish.py:73-107,134-142,226-300) ---------------------------------
 // Device buffers of one H x W image with np probes: rid as run_dense_cells left it, mx, the outputs thr (one plane per probe) and

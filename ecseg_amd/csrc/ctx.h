@@ -115,6 +115,7 @@ struct DevMem {
     DevBuf<uint8_t> call_arena;   // everything a driver can size before its first launch
     DevBuf<uint8_t> count_arena;  // the FISH drivers: what is sized by the cell count, read back while call_arena is in use
     DevBuf<uint8_t> keep_arena;   // `iseg`, left by ecseg_nuclei_regions for ecseg_nucleus_crops: no other driver touches it
+    DevBuf<uint8_t> fishdist_batch_buf;   // ecseg_fish_distances_batch alone: carved by the driver itself in two parts (fishdist_batch.h), grow-only
     DevBuf<uint8_t> pre_arena;    // ecseg_prefetch_tiffs: the decode-ahead's file images, tables and status words; they outlive the call that launched it, which call_arena does not
 };
 

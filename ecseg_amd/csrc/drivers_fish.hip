@@ -45,6 +45,58 @@ static int fish_render_check(ecseg_ctx* h, const uint8_t* img, int H, int W, int
     return ECSEG_OK;
 }
 
+// One group of ecseg_fish_distances_batch: consecutive images of the chunk that share one pass over the driver's own scratch buffer
+// (fishdist_batch.h).  The buffer is carved in two parts with the arenas' three steps - measure, ensure, place - written out here:
+// it is no arena of ctx.h and joins none of their rows.
+struct FdbRun { FdbLayout L; FdbPixelBufs b; std::vector<int32_t> plan; int cells = 0; };
+
+// The first part: measured TOGETHER with the most the second part can need (the buffer must not grow while the first part is in
+// use), grown if need be, placed; then the uploads, the dense cell index of the whole group and the plan on the host.
+static int fdb_open_group(ecseg_ctx* h, const int32_t* const* labels, const uint8_t* const* lsqs, const int32_t* shapes, FdbGroup g, int capacity,
+                          FdbRun& r) {
+    const std::string me = "fish_distances_batch: ";
+    const std::string bad = fdb_layout(shapes, g.first, g.n, r.L);
+    if (!bad.empty()) return fail(h, ECSEG_E_INVALID, me + bad);
+    const size_t n = (size_t)g.n, bound = (size_t)fdb_cell_bound(r.L.px, capacity);
+    Carver measure;
+    (void)fdb_pixel_bufs(measure, r.L);
+    if ((long long)measure.used != fdb_pixel_bytes(r.L)) return fail(h, ECSEG_E_INVALID, me + "fdb_pixel_bytes does not restate fdb_pixel_bufs");
+    (void)fdb_cell_bufs(measure, bound, bound + FDB_SLICE_BUDGET);
+    if ((long long)measure.used != fdb_group_bytes(r.L, capacity)) return fail(h, ECSEG_E_INVALID, me + "fdb_group_bytes does not restate the two parts");
+    if (int rc = h->fishdist_batch_buf.ensure(h, measure.used)) return rc;
+    Carver place(h->fishdist_batch_buf.p);
+    r.b = fdb_pixel_bufs(place, r.L);
+    hipStream_t s = h->stream;
+    for (size_t k = 0; k < n; ++k) {
+        const FdbImage& t = r.L.tab[k];
+        const size_t px = (size_t)t.H * t.W;
+        HIP_TRY(h, hipMemcpyAsync(r.b.lab + t.px0, labels[(size_t)g.first + k], px * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        HIP_TRY(h, hipMemcpyAsync(r.b.lsq + t.lsq0, lsqs[(size_t)g.first + k], px * t.C, hipMemcpyHostToDevice, s));
+    }
+    HIP_TRY(h, hipMemcpyAsync(r.b.tab, r.L.tab.data(), n * sizeof(FdbImage), hipMemcpyHostToDevice, s));
+    TIMED(h, s, 0, 1, HIP_TRY(h, run_fishdist_batch_open(r.L, r.b, s)));
+    r.plan.assign((n + 1) * 2, 0);
+    HIP_TRY(h, hipMemcpyAsync(r.plan.data(), r.b.plan, r.plan.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));   // every image's cells in one copy
+    WAIT_ADD(h, s, 0, 1);
+    r.cells = r.plan[2 * n];
+    return ECSEG_OK;
+}
+
+// The second part, carved behind the first now that the group's cells are known, and the group's records at `records`
+static int fdb_finish_group(ecseg_ctx* h, const FdbRun& r, int fi, int ci, int64_t* records) {
+    if (r.cells == 0) return ECSEG_OK;
+    const size_t cells = (size_t)r.cells;
+    Carver place(h->fishdist_batch_buf.p);
+    (void)fdb_pixel_bufs(place, r.L);
+    const FdbCellBufs c = fdb_cell_bufs(place, cells, cells * (size_t)fishdist_slices(r.cells));
+    if (place.used > h->fishdist_batch_buf.cap) return fail(h, ECSEG_E_INVALID, "fish_distances_batch: the second part leaves the measured buffer");
+    hipStream_t s = h->stream;
+    TIMED(h, s, 2, 3, HIP_TRY(h, run_fishdist_batch_records(r.L, r.b, c, r.cells, fi, ci, s)));
+    HIP_TRY(h, hipMemcpyAsync(records, c.rec, cells * 8 * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    WAIT_ADD(h, s, 2, 3);
+    return ECSEG_OK;
+}
+
 extern "C" {
 
 // ---- fish_distance_calculation (src/fish_distance_calculation.py:16-46) ---------------------------------------------------
@@ -72,6 +124,54 @@ int ecseg_fish_distances(ecseg_ctx* h, const int32_t* labels, int H, int W, cons
     TIMED(h, s, 2, 3, HIP_TRY(h, run_fishdist_records(cells.lab, cells.img, H, W, C, fish_channel, centromere_channel, n, b, s)));
     HIP_TRY(h, hipMemcpyAsync(records, b.rec, (size_t)n * 8 * sizeof(int64_t), hipMemcpyDeviceToHost, s));
     WAIT_ADD(h, s, 2, 3);
+    return ECSEG_OK;
+}
+
+
+// ---- fish_distance_calculation.batch: the same for a chunk of images in one call (layout: fishdist_batch.h) ----------------------
+int ecseg_fish_distances_batch(ecseg_ctx* h, int n_images, const int32_t* const* labels, const uint8_t* const* lsqs, const int32_t* shapes,
+                               int fish_channel, int centromere_channel, int record_capacity, int64_t* records, int32_t* n_cells,
+                               int32_t* status) {
+    DRIVER_OPEN(h);
+    static_assert(FDB_MAX_IMAGES == ECSEG_FISH_DISTANCES_BATCH_MAX_IMAGES, "fishdist_batch.h and the header disagree");
+    const std::string me = "fish_distances_batch: ";
+    if (n_images < 0 || record_capacity < 0 || (record_capacity > 0 && !records) || (n_images > 0 && (!labels || !lsqs || !shapes || !n_cells || !status)))
+        return fail(h, ECSEG_E_INVALID, me + "bad arguments");
+    clear_timings(h);
+    if (n_images == 0) return ECSEG_OK;
+    if (n_images > FDB_MAX_IMAGES) return fail(h, ECSEG_E_INVALID, me + "more than " + std::to_string(FDB_MAX_IMAGES) + " images");
+    FdbRun run;
+    const std::string bad = fdb_layout(shapes, 0, n_images, run.L);          // the limits of the whole chunk
+    if (!bad.empty()) return fail(h, ECSEG_E_INVALID, me + bad);
+    for (int i = 0; i < n_images; ++i) {
+        const std::string who = me + "image " + std::to_string(i) + ": ";
+        const int C = shapes[3 * (size_t)i + 2];
+        if (!labels[i] || !lsqs[i]) return fail(h, ECSEG_E_INVALID, who + "bad arguments (no label map or no lsq image)");
+        if (fish_channel < 0 || fish_channel >= C || centromere_channel < 0 || centromere_channel >= C)
+            return fail(h, ECSEG_E_INVALID, who + "channel out of range (the lsq image has " + std::to_string(C) + " channels)");
+        n_cells[i] = 0;
+        status[i] = ECSEG_OK;
+    }
+    const std::vector<FdbGroup> groups = fdb_groups(shapes, n_images, record_capacity);
+    USE_DEVICE(h);
+    int rc;
+    // the counts first: of the only group on its way, of several groups in a pass of their own (nothing is written above the capacity)
+    long long total = 0;
+    for (const FdbGroup& g : groups) {
+        if ((rc = fdb_open_group(h, labels, lsqs, shapes, g, record_capacity, run))) return rc;
+        for (int k = 0; k < g.n; ++k) {
+            n_cells[g.first + k] = run.plan[2 * (size_t)k + 2] - run.plan[2 * (size_t)k];
+            status[g.first + k] = run.plan[2 * (size_t)k + 1] ? ECSEG_E_INVALID : ECSEG_OK;
+        }
+        total += run.cells;
+    }
+    if (total > record_capacity) return ECSEG_OK;            // the counts alone: the caller comes back with a larger buffer
+    long long at = 0;
+    for (const FdbGroup& g : groups) {
+        if (groups.size() > 1 && (rc = fdb_open_group(h, labels, lsqs, shapes, g, record_capacity, run))) return rc;
+        if ((rc = fdb_finish_group(h, run, fish_channel, centromere_channel, records + at * 8))) return rc;
+        at += run.cells;
+    }
     return ECSEG_OK;
 }
 

@@ -306,7 +306,7 @@ int ecseg_ccl_pass_debug(ecseg_ctx* h, const uint8_t* key_img, const uint8_t* au
 //   pre_arena   the decode-ahead's file images, tables and status words (pre_file_status): DRIVER_OPEN drops what was sent ahead
 //               (pre_tiffs.files = null, without which no call takes the rasters; pre_plan and pre_read_ms keep their values unread);
 //   post_arena  ws: only its layout outlives a call, never its contents; dropped, so the next ensure_post lays it out for its own need.
-// call_arena and count_arena carry nothing: the cell index a FISH driver leaves in call_arena is rebuilt by the call that comes back.
+// call_arena, count_arena and ecseg_fish_distances_batch's own buffer carry nothing: the cell index a FISH driver leaves in call_arena is rebuilt by the call that comes back.
 int ecseg_scratch_fill_debug(ecseg_ctx* h, int byte) {
     DRIVER_OPEN(h);
     if (byte < 0 || byte > 255) return fail(h, ECSEG_E_INVALID, "scratch_fill_debug: byte must be 0 .. 255");
@@ -323,7 +323,7 @@ int ecseg_scratch_fill_debug(ecseg_ctx* h, int byte) {
     h->iseg_n = -1; h->iseg = RegionMapBufs{};
     h->pre_file_status = nullptr;
     h->ws = PostWorkspace{};
-    for (DevBuf<uint8_t>* a : {&h->post_arena, &h->call_arena, &h->count_arena, &h->keep_arena, &h->pre_arena})
+    for (DevBuf<uint8_t>* a : {&h->post_arena, &h->call_arena, &h->count_arena, &h->keep_arena, &h->pre_arena, &h->fishdist_batch_buf})
         if (a->p && a->cap) HIP_TRY(h, hipMemsetAsync(a->p, byte, a->cap, h->stream));
     HIP_TRY(h, wait_all());
     return ECSEG_OK;                                         // (untimed: stage_ms keeps the call before's)

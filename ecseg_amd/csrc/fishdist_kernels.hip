@@ -240,4 +240,228 @@ hipError_t run_fishdist_records(int32_t* labels, const uint8_t* lsq, int H, int 
     return hipGetLastError();
 }
 
+// ---- a chunk of images in one pass (ecseg_fish_distances_batch; the layout and the lookups: fishdist_batch.h) ------------------------
+// The same five steps over the chunk's global pixel axis.  A workgroup of a per-pixel kernel is one 256-pixel block of ONE image, a
+// workgroup of the statistics kernel one tile of one image; both look their image up in the table first.  Cells are numbered over the
+// whole chunk, ascending by (image, label), so acc, val, off, cur, the lists, the partials and the records are those of the single
+// image with "the image" read as "the chunk", and the fold (fd_records_kernel) is the single image's.
+static_assert(FDB_TILE_W == 64 && FDB_TILE_H == 4 * CELL_ROWS_PER_WAVE, "fishdist_batch.h restates the statistics tile of cell_util.h");
+
+// flag[px0 + label - 1] = 1 for every label of image i that occurs; status[i] = 1 when one of its labels exceeds its H * W
+__global__ __launch_bounds__(256) void fdb_mark_kernel(const int32_t* __restrict__ L, const FdbImage* __restrict__ tab, int n,
+                                                       int32_t* __restrict__ flag, int32_t* __restrict__ status) {
+    const int i = fdb_find(tab, n, false, blockIdx.x);
+    const FdbImage im = tab[i];
+    cell_mark_pixel(L + im.px0, im.H * im.W, flag + im.px0, status + i, (blockIdx.x - (unsigned)im.blk0) * 256u + threadIdx.x);
+}
+
+// A refused image holds no cell: its share of the flag space is cleared before the scan (a no-op for every other image)
+__global__ __launch_bounds__(256) void fdb_void_refused_kernel(const FdbImage* __restrict__ tab, int n, const int32_t* __restrict__ status,
+                                                               int32_t* __restrict__ flag) {
+    const int i = fdb_find(tab, n, false, blockIdx.x);
+    if (!status[i]) return;
+    const FdbImage im = tab[i];
+    const unsigned p = (blockIdx.x - (unsigned)im.blk0) * 256u + threadIdx.x;
+    if (p < (unsigned)(im.H * im.W)) flag[im.px0 + p] = 0;
+}
+
+// plan (n + 1, 2): per image the cells in front of it (rid at its first pixel) and its status word; the last pair: the chunk's cells
+__global__ __launch_bounds__(256) void fdb_plan_kernel(const int32_t* __restrict__ rid, const FdbImage* __restrict__ tab, int n,
+                                                       const int32_t* __restrict__ status, const int32_t* __restrict__ misc,
+                                                       int32_t* __restrict__ plan) {
+    const unsigned i = blockIdx.x * 256u + threadIdx.x;
+    if (i > (unsigned)n) return;
+    plan[2 * i] = i < (unsigned)n ? rid[tab[i].px0] : misc[0];
+    plan[2 * i + 1] = i < (unsigned)n ? status[i] : 0;
+}
+
+// fd_cell_stats_kernel on tile blockIdx.x of the chunk: L, rid and par are indexed on the global pixel axis, the tile walks local rows
+// and columns; cimg[cell] = the cell's image.  The same label value in two images is two keys (the scan numbered them apart).
+__global__ __launch_bounds__(256) void fdb_cell_stats_kernel(int32_t* __restrict__ L, const int32_t* __restrict__ rid,
+                                                             const uint8_t* __restrict__ lsq, const FdbImage* __restrict__ tab, int n,
+                                                             const int32_t* __restrict__ status, int fi, int ci, unsigned* __restrict__ acc,
+                                                             int32_t* __restrict__ val, int32_t* __restrict__ cimg, int32_t* __restrict__ par) {
+    __shared__ int s_key[CELL_SLOTS], s_val[CELL_SLOTS];
+    __shared__ unsigned s_acc[4][CELL_SLOTS];
+    __shared__ int s_img;
+    const int t = threadIdx.x, lane = t & 63;
+    if (t < CELL_SLOTS) {
+        s_key[t] = -1;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) s_acc[j][t] = 0;
+    }
+    if (t == 0) s_img = fdb_find(tab, n, true, blockIdx.x);  // once per workgroup
+    __syncthreads();
+    const int img = s_img;
+    if (status[img]) return;                                 // block-uniform: a refused image is not touched
+    const FdbImage im = tab[img];
+    const int H = im.H, W = im.W, C = im.C;
+    const StatTile tile = stat_tile_at(blockIdx.x - (unsigned)im.tile0, W);
+    for (int r = 0; r < CELL_ROWS_PER_WAVE; ++r) {
+        const int y = tile.ybeg + r;
+        if (y >= H) break;                                   // wave-uniform
+        int reg = -1, l = 0;
+        bool f = false, c = false, g0 = false, g1 = false;
+        if (tile.x < (unsigned)W) {
+            const size_t p = (size_t)y * W + tile.x, gp = (size_t)im.px0 + p;
+            l = L[gp];
+            if (l > 0) {                                     // l <= H * W: the mark kernel has seen every pixel of this image
+                reg = rid[im.px0 + l - 1];
+                L[gp] = reg + 1;
+                const uint8_t* q = lsq + im.lsq0 + p * C;
+                f = q[fi] != 0; c = q[ci] != 0; g0 = q[0] != 0; g1 = q[1] != 0;
+            }
+            par[gp] = f ? (int)gp : -1;
+        }
+        wave_key_groups(reg, [&](int key, bool mine, u64 m, int leader) {
+            const unsigned cnt = (unsigned)__popcll(m);
+            const unsigned nf = (unsigned)__popcll(__ballot(mine && f)), nc = (unsigned)__popcll(__ballot(mine && c));
+            const unsigned bits = (__ballot(mine && g0) ? 1u : 0u) | (__ballot(mine && g1) ? 2u : 0u) | (__ballot(mine && f && c) ? 4u : 0u);
+            if (lane != leader) return;
+            const int found = lds_key_claim(s_key, key);
+            if (found >= 0) {
+                s_val[found] = l;                            // every writer of a slot stores the same label
+                atomicAdd(&s_acc[0][found], cnt); atomicAdd(&s_acc[1][found], nf); atomicAdd(&s_acc[2][found], nc);
+                atomicOr(&s_acc[3][found], bits);
+            } else {                                         // more than 64 cells in one 64 x 32 tile: straight to the cell
+                unsigned* a = acc + (size_t)key * 4;
+                atomicAdd(a + 0, cnt); atomicAdd(a + 1, nf); atomicAdd(a + 2, nc); atomicOr(a + 3, bits);
+                val[key] = l; cimg[key] = img;
+            }
+        });
+    }
+    __syncthreads();
+    if (t < CELL_SLOTS && s_key[t] >= 0) {
+        const int k = s_key[t];
+        unsigned* a = acc + (size_t)k * 4;
+        atomicAdd(a + 0, s_acc[0][t]); atomicAdd(a + 1, s_acc[1][t]); atomicAdd(a + 2, s_acc[2][t]); atomicOr(a + 3, s_acc[3][t]);
+        val[k] = s_val[t]; cimg[k] = img;
+    }
+}
+
+// fd_fill_unite_kernel on block blockIdx.x of the chunk.  The parents are global pixel indices, row and column local: a pixel with
+// x > 0 has its W neighbour, and one with y > 0 its N, NW and NE neighbours, in its own image, so uf_unite_back never sees a pixel of
+// the image in front - also where that image has the same width and its last row lies one "row" above.  The lists store local (y, x).
+__global__ __launch_bounds__(256) void fdb_fill_unite_kernel(const int32_t* __restrict__ L, const uint8_t* __restrict__ lsq,
+                                                             const FdbImage* __restrict__ tab, int n, const int32_t* __restrict__ status,
+                                                             int fi, int ci, int cells, const int32_t* __restrict__ off,
+                                                             int32_t* __restrict__ cur, int2* __restrict__ flist, int2* __restrict__ clist,
+                                                             int32_t* par) {
+    const int img = fdb_find(tab, n, false, blockIdx.x);
+    if (status[img]) return;
+    const FdbImage im = tab[img];
+    const unsigned pu = (blockIdx.x - (unsigned)im.blk0) * 256u + threadIdx.x;   // H * W < 2^31: no wrap
+    if (pu >= (unsigned)(im.H * im.W)) return;
+    const int gp = im.px0 + (int)pu;                         // the chunk holds fewer than 2^31 pixels
+    const int cell = L[gp];
+    if (cell <= 0) return;
+    const uint8_t* q = lsq + im.lsq0 + (size_t)pu * im.C;
+    const bool f = q[fi] != 0, c = q[ci] != 0;
+    const int y = (int)pu / im.W, x = (int)pu - y * im.W;
+    if (c) clist[off[cells + cell - 1] + atomicAdd(cur + cells + cell - 1, 1)] = make_int2(y, x);
+    if (!f) return;
+    flist[off[cell - 1] + atomicAdd(cur + cell - 1, 1)] = make_int2(y, x);
+    uf_unite_back(par, gp, y, x, im.W, 1, [&](int nb) { return L[nb] == cell; });
+}
+
+// fd_distance_kernel over all cells of the chunk: the root count turns a FISH pixel's local (y, x) back into its global index with the
+// first pixel and the width of the cell's image.
+template <typename T>
+__global__ __launch_bounds__(256) void fdb_distance_kernel(const unsigned* __restrict__ acc, const int32_t* __restrict__ off,
+                                                           const int2* __restrict__ flist, const int2* __restrict__ clist,
+                                                           const int32_t* __restrict__ par, const int32_t* __restrict__ cimg,
+                                                           const FdbImage* __restrict__ tab, int n, int S, u64* __restrict__ pbest,
+                                                           int32_t* __restrict__ proots) {
+    __shared__ int2 s_c[FD_TILE];
+    __shared__ int s_roots[4];
+    __shared__ T s_best[4];
+    const int cell = blockIdx.x, slice = blockIdx.y, t = threadIdx.x;
+    const unsigned* a = acc + (size_t)cell * 4;
+    const int nf = (int)a[1], nc = (int)a[2];
+    const unsigned bits = a[3];
+    const size_t slot = (size_t)cell * S + slice;
+    if ((long long)slice * 256 >= nf) {                      // block-uniform: nothing of the list falls into this slice
+        if (t == 0) { pbest[slot] = ~0ull; proots[slot] = 0; }
+        return;
+    }
+    const FdbImage im = tab[cimg[cell]];                     // (a cell with a FISH pixel has been seen by the statistics kernel)
+    const int2* fl = flist + off[cell];
+    const int2* cl = clist + off[n + cell];
+    const long long step = (long long)S * 256;
+    int roots = 0;
+    for (long long i = (long long)slice * 256 + t; i < nf; i += step) {
+        const int2 f = fl[i];
+        const int p = im.px0 + f.x * im.W + f.y;
+        roots += par[p] == p;
+    }
+    T best = ~(T)0;
+    if (nc > 0 && !(bits & 4u)) {
+        for (int c0 = 0; c0 < nc; c0 += FD_TILE) {
+            const int m = min(FD_TILE, nc - c0);
+            __syncthreads();
+            for (int j = t; j < m; j += 256) s_c[j] = cl[c0 + j];
+            __syncthreads();
+            for (long long i = (long long)slice * 256 + t; i < nf; i += step) {
+                const int2 f = fl[i];
+#pragma unroll 4
+                for (int j = 0; j < m; ++j) {
+                    const int2 c = s_c[j];
+                    const T d = fd_sq<T>(f.x - c.x) + fd_sq<T>(f.y - c.y);
+                    best = d < best ? d : best;
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        roots += __shfl_xor(roots, d);
+        const T o = __shfl_xor(best, d);
+        best = o < best ? o : best;
+    }
+    if ((t & 63) == 0) { s_roots[t >> 6] = roots; s_best[t >> 6] = best; }
+    __syncthreads();
+    if (t == 0) {
+#pragma unroll
+        for (int w = 1; w < 4; ++w) { roots += s_roots[w]; best = s_best[w] < best ? s_best[w] : best; }
+        pbest[slot] = best == ~(T)0 ? ~0ull : (u64)best;
+        proots[slot] = roots;
+    }
+}
+
+hipError_t run_fishdist_batch_open(const FdbLayout& L, const FdbPixelBufs& b, hipStream_t s) {
+    const int n = (int)L.tab.size(), px = (int)L.px;
+    hipError_t e;
+    if ((e = hipMemsetAsync(b.misc, 0, 4 * sizeof(int32_t), s)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(b.status, 0, (size_t)n * sizeof(int32_t), s)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(b.rid, 0, (size_t)px * sizeof(int32_t), s)) != hipSuccess) return e;
+    hipLaunchKernelGGL(fdb_mark_kernel, dim3(L.blocks), dim3(256), 0, s, b.lab, b.tab, n, b.rid, b.status);
+    hipLaunchKernelGGL(fdb_void_refused_kernel, dim3(L.blocks), dim3(256), 0, s, b.tab, n, b.status, b.rid);
+    exclusive_scan(LoadStrided{b.rid, 1}, px, b.blk, b.rid, b.misc, s);
+    hipLaunchKernelGGL(fdb_plan_kernel, dim3(((unsigned)n + 256u) / 256u), dim3(256), 0, s, b.rid, b.tab, n, b.status, b.misc, b.plan);
+    return hipGetLastError();
+}
+
+hipError_t run_fishdist_batch_records(const FdbLayout& L, const FdbPixelBufs& b, const FdbCellBufs& c, int cells, int fi, int ci, hipStream_t s) {
+    if (cells <= 0) return hipSuccess;
+    const int n = (int)L.tab.size();
+    int2* flist = reinterpret_cast<int2*>(b.flist);
+    int2* clist = reinterpret_cast<int2*>(b.clist);
+    hipError_t e;
+    if ((e = hipMemsetAsync(c.acc, 0, (size_t)cells * 4 * sizeof(unsigned), s)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(c.cur, 0, (size_t)cells * 2 * sizeof(int32_t), s)) != hipSuccess) return e;
+    hipLaunchKernelGGL(fdb_cell_stats_kernel, dim3(L.tiles), dim3(256), 0, s, b.lab, b.rid, b.lsq, b.tab, n, b.status, fi, ci, c.acc, c.val, c.img, b.par);
+    exclusive_scan(LoadStrided{reinterpret_cast<const int32_t*>(c.acc) + 1, 4}, cells, b.blk, c.off, b.misc + 1, s);
+    exclusive_scan(LoadStrided{reinterpret_cast<const int32_t*>(c.acc) + 2, 4}, cells, b.blk, c.off + cells, b.misc + 2, s);
+    hipLaunchKernelGGL(fdb_fill_unite_kernel, dim3(L.blocks), dim3(256), 0, s, b.lab, b.lsq, b.tab, n, b.status, fi, ci, cells, c.off, c.cur, flist,
+                       clist, b.par);
+    const int S = fishdist_slices(cells);
+    const dim3 g((unsigned)cells, (unsigned)S);
+    if (L.max_extent <= 32768)
+        hipLaunchKernelGGL(fdb_distance_kernel<unsigned>, g, dim3(256), 0, s, c.acc, c.off, flist, clist, b.par, c.img, b.tab, cells, S, c.pbest, c.proots);
+    else
+        hipLaunchKernelGGL(fdb_distance_kernel<u64>, g, dim3(256), 0, s, c.acc, c.off, flist, clist, b.par, c.img, b.tab, cells, S, c.pbest, c.proots);
+    hipLaunchKernelGGL(fd_records_kernel, dim3(((unsigned)cells + 255u) / 256u), dim3(256), 0, s, c.acc, c.val, cells, S, c.pbest, c.proots, c.rec);
+    return hipGetLastError();
+}
+
 }  // namespace ecseg

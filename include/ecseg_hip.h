@@ -86,6 +86,8 @@ extern "C" {
  * encode of many stat_fish images in one call; nothing existing changed.) */
 /* (still 5 - additive: ecseg_scratch_fill_debug, every scratch arena of the handle filled with one byte, for the tests that hold each
  * driver to its answer whatever an earlier call left there; nothing existing changed.) */
+/* (still 5 - additive: ecseg_fish_distances_batch, the per-nucleus records of fish_distance_calculation for many images in one call;
+ * nothing existing changed.) */
 #define ECSEG_ABI_VERSION 5
 
 #define ECSEG_OK             0
@@ -485,6 +487,28 @@ int ecseg_interseg_batch(ecseg_ctx* h, ecseg_ctx* model_i, ecseg_ctx* model_c, c
  * 0 .. C - 1, H * W >= 2^31, H * W * C >= 2^40.  The distance search is brute force (FISH x centromere pixels per cell). */
 int ecseg_fish_distances(ecseg_ctx* h, const int32_t* labels, int H, int W, const uint8_t* lsq, int C, int fish_channel,
                          int centromere_channel, int capacity, int64_t* records, int32_t* n_cells);
+
+/* The same for n_images images in ONE call (config key fish_distance_calculation.batch).  Image i has shapes[3 i ..] = H, W, C of its
+ * own, labels[i] ((H, W) int32) and lsqs[i] ((H, W, C) uint8) as ecseg_fish_distances takes them; fish_channel and centromere_channel
+ * apply to every image.  On the device the images' pixels lie back to back on one pixel axis (csrc/fishdist_batch.h): one scan numbers
+ * the cells of the whole chunk, ascending by (image, label) - the same label value in two images is two cells - and no connected
+ * component, list or distance reaches across the seam between two images.
+ *   n_cells[i]: the different labels > 0 of image i.  records: 8 int64 per cell as ecseg_fish_distances writes them, the images back to
+ * back in call order.  status[i]: ECSEG_OK, or ECSEG_E_INVALID for an image holding a label above its H * W: that image has n_cells[i]
+ * = 0 and no record and disturbs no other image (the call itself returns ECSEG_OK).  record_capacity: room of `records` in cells, for
+ * the whole chunk; when the chunk holds more, the call returns ECSEG_OK with every n_cells[i] and status[i] set and nothing else
+ * written (ecseg_fish_distances' rule): come back with a larger buffer.  Every field is a sum, an OR, a minimum or a root count, so no
+ * byte depends on the order of the atomics: the records equal those of n_images single calls, and two calls give identical bytes.
+ *   ECSEG_E_INVALID, the message naming the image ("image i: ..."): what the single call refuses (no pointer, H or W below 1, C < 2, a
+ * channel outside 0 .. C - 1, H * W >= 2^31, H * W * C >= 2^40); also more than ECSEG_FISH_DISTANCES_BATCH_MAX_IMAGES images, a chunk
+ * of 2^31 pixels or more, or of 2^40 lsq bytes or more.  n_images == 0 is ECSEG_OK and does nothing.  One synchronous call; a chunk
+ * whose scratch would pass 8 GiB runs its consecutive images in several groups.  The scratch is one grow-only buffer of the driver's
+ * own on the handle (none of the arenas; a region map left by ecseg_nuclei_regions stays valid), freed with the handle; device time
+ * of all kernels in ECSEG_T_COUNT. */
+#define ECSEG_FISH_DISTANCES_BATCH_MAX_IMAGES 8192
+int ecseg_fish_distances_batch(ecseg_ctx* h, int n_images, const int32_t* const* labels, const uint8_t* const* lsqs,
+                               const int32_t* shapes /* [n][3] H, W, C */, int fish_channel, int centromere_channel, int record_capacity,
+                               int64_t* records, int32_t* n_cells, int32_t* status);
 
 /* ---- stat_fish behind nuclei_segment: per-nucleus FISH spot statistics (src/stat_fish.py:73-107,134-142,226-300) ----------- */
 /* Replaces, for ONE image, get_thresholded (:73-88, the two TensorFlow convolutions included), the loop over

@@ -11,6 +11,13 @@ Per 1040 x 1392 scene with a few hundred nuclei it reports
   * the same scenes through the CPU baselines tests/fish_distance_ref.py ``loop`` (the reference's per-pixel loop) and
     ``records`` (vectorised numpy) on a pool of --cpu-workers processes.
 Prints one JSON line.
+
+    python tools/time_fish_distance.py --batch 8 alternate [--images 32] [--io-threads N]
+
+``alternate`` runs ``main()`` over one such folder with ``batch`` 1, k, 1, k: per leg one warm-up pass and three timed passes, and
+prints one JSON line with, per leg, the images per second of every pass (median, min, max) and the seconds each pass spent reading
+(at ``batch`` above 1: waiting for the reader threads), in the device call with what prepares it, and on the rows.  By the project's
+rule ``batch: k`` is a gain only where the minimum of its legs lies above the maximum of the ``batch: 1`` legs.
 """
 import argparse
 import json
@@ -73,8 +80,74 @@ def _stats(xs):
     return {'median': round(statistics.median(xs), 4), 'min': round(min(xs), 4), 'max': round(max(xs), 4)}
 
 
+def write_folder(inp, data):
+    """the scenes as stat_fish leaves them under ``inp``"""
+    from PIL import Image
+
+    from ecseg_amd import image_io
+    for k, (lsq, seg) in enumerate(data):
+        name = 'img_%03d' % k
+        d = os.path.join(inp, 'annotated', name)
+        os.makedirs(d)
+        image_io.write_tiff_gray8(os.path.join(inp, name + '.tif'), np.zeros((4, 4), np.uint8))
+        np.save(os.path.join(d, name + '__segmentation_min_cut.npy'), seg)
+        Image.fromarray(lsq).save(os.path.join(d, name + '_lsq_t.tif'), compression='tiff_lzw')
+
+
+def alternate(a):
+    """``main()`` with batch 1, k, 1, k over one folder -> the JSON line of the module docstring"""
+    import yaml
+
+    from ecseg_amd import fish_distance_calculation as fdc
+    from ecseg_amd._lib import Handle
+    data = [synth_scene(2000 + k, a.height, a.width, a.nuclei) for k in range(a.images)]
+    out = {'images': a.images, 'shape': [a.height, a.width], 'batch': a.batch, 'passes_per_leg': 3, 'legs': []}
+    h = Handle(0)
+    with tempfile.TemporaryDirectory() as tmp:
+        inp = os.path.join(tmp, 'in')
+        write_folder(inp, data)
+        cwd = os.getcwd()
+        os.chdir(tmp)
+        devnull = open(os.devnull, 'w')
+        try:
+            csvs = []
+            for k in (1, a.batch, 1, a.batch):
+                var = {'inpath': inp, 'centromere_probe_color': 'green', 'fish_probe_color': 'red', 'max_centromeric_spots': 3, 'batch': k}
+                if a.io_threads:
+                    var['io_threads'] = a.io_threads
+                with open('config.yaml', 'w') as f:
+                    yaml.safe_dump({'fish_distance_calculation': var}, f)
+                rates, parts = [], []
+                for rep in range(4):                           # one warm-up pass, three timed
+                    stats = {}
+                    stdout, sys.stdout = sys.stdout, devnull
+                    try:
+                        t0 = time.perf_counter()
+                        fdc.main([], handle=h, stats=stats)
+                        dt = time.perf_counter() - t0
+                    finally:
+                        sys.stdout = stdout
+                    if rep:
+                        rates.append(a.images / dt)
+                        parts.append({key: round(stats.get(key, 0.0), 4) for key in ('read_s', 'device_s', 'rows_s')})
+                csvs.append(open(os.path.join(inp, 'centromere_distances.csv')).read())
+                out['legs'].append({'batch': k, 'images_per_s': _stats(rates), 'passes': parts})
+            out['csv_rows'] = csvs[0].count('\n') - 1
+            out['same_csv'] = all(c == csvs[0] for c in csvs)
+        finally:
+            os.chdir(cwd)
+    h.close()
+    one = [leg['images_per_s'] for leg in out['legs'] if leg['batch'] == 1]
+    many = [leg['images_per_s'] for leg in out['legs'] if leg['batch'] != 1]
+    out['gain'] = bool(many) and min(m['min'] for m in many) > max(o['max'] for o in one)
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument('mode', nargs='?', choices=['alternate'], help='alternate: main() with batch 1, k, 1, k (needs --batch k)')
+    ap.add_argument('--batch', type=int, default=0)
+    ap.add_argument('--io-threads', type=int, default=0)
     ap.add_argument('--images', type=int, default=16)
     ap.add_argument('--nuclei', type=int, default=300)
     ap.add_argument('--height', type=int, default=1040)
@@ -83,11 +156,13 @@ def main():
     ap.add_argument('--cpu-workers', type=int, default=16)
     ap.add_argument('--no-cpu', action='store_true')
     a = ap.parse_args()
+    if a.mode == 'alternate':
+        if a.batch < 2:
+            ap.error('alternate needs --batch k with k above 1')
+        return alternate(a)
     import yaml
-    from PIL import Image
 
     from ecseg_amd import fish_distance_calculation as fdc
-    from ecseg_amd import image_io
     from ecseg_amd._lib import Handle
     jobs = [(2000 + k, a.height, a.width, a.nuclei) for k in range(a.images)]
     data = [synth_scene(*j) for j in jobs]
@@ -112,13 +187,7 @@ def main():
            'device_ms_per_image': _stats(dev), 'call_ms_per_image': _stats(wall)}
     with tempfile.TemporaryDirectory() as tmp:
         inp = os.path.join(tmp, 'in')
-        for k, (lsq, seg) in enumerate(data):
-            name = 'img_%03d' % k
-            d = os.path.join(inp, 'annotated', name)
-            os.makedirs(d)
-            image_io.write_tiff_gray8(os.path.join(inp, name + '.tif'), np.zeros((4, 4), np.uint8))
-            np.save(os.path.join(d, name + '__segmentation_min_cut.npy'), seg)
-            Image.fromarray(lsq).save(os.path.join(d, name + '_lsq_t.tif'), compression='tiff_lzw')
+        write_folder(inp, data)
         reads = []
         for rep in range(a.reps + 1):
             t0 = time.perf_counter()
