@@ -26,9 +26,6 @@ EXPORTS = [
     'ecseg_png_labels_encode', 'ecseg_meta_segment_files', 'ecseg_get_file_timings', 'ecseg_png_labels_stream_size',
     'ecseg_ccl_pass_debug', 'ecseg_meta_inference_stages_debug',
     'ecseg_tiff_decode_batch', 'ecseg_tiff_decode_batch_bytes', 'ecseg_tiff_decode_batch_routes', 'ecseg_tiff_decode_batch_counts',
-    'ecseg_tiff_decode_routes_ex', 'ecseg_tiff_decode_batch_routes_ex', 'ecseg_tiff_decode_batch_counts_ex', 'ecseg_tiff_decode_batch_bytes_ex',
-    'ecseg_tiff_decode_routes_ex2', 'ecseg_tiff_decode_batch_routes_ex2', 'ecseg_tiff_decode_batch_counts_ex2', 'ecseg_tiff_decode_batch_bytes_ex2',
-    'ecseg_tiff_decode_routes_ex3', 'ecseg_tiff_decode_batch_routes_ex3', 'ecseg_tiff_decode_batch_counts_ex3', 'ecseg_tiff_decode_batch_bytes_ex3',
     'ecseg_meta_segment_tiffs', 'ecseg_meta_segment_tiffs_files', 'ecseg_prefetch_tiffs', 'ecseg_get_read_timings',
     'ecseg_png_channel_bound', 'ecseg_png_channel_encode', 'ecseg_overlay_files',
     'ecseg_tiff_encode_batch', 'ecseg_tiff_encode_batch_bytes', 'ecseg_fish_render_tiff_batch',
@@ -51,7 +48,39 @@ class EcsegError(RuntimeError):
 E_HIP = -2
 E_NOMEM = -4
 E_UNSUPPORTED, E_IO = -5, -6
-ABI_VERSION = 5           # ECSEG_ABI_VERSION of include/ecseg_hip.h this binding was written for
+ABI_VERSION = 6           # ECSEG_ABI_VERSION of include/ecseg_hip.h this binding was written for
+TIFF_DEFLATE, TIFF_TILED, TIFF_PACKBITS = 1, 2, 4     # ECSEG_TIFF_* of the header: the kinds of file a TIFF decoder takes beside LZW and uncompressed strips
+TIFF_OPTIONS = (('deflate', 'tiff_deflate_on_device', TIFF_DEFLATE), ('tiled', 'tiff_tiled_on_device', TIFF_TILED),
+                ('packbits', 'tiff_packbits_on_device', TIFF_PACKBITS))   # (keyword, handle option and mirror attribute, bit)
+
+
+def tiff_kinds(deflate=False, tiled=False, packbits=False):
+    """The kinds word of the handle-free routing functions (ecseg_tiff_decode_routes and the three beside it) from three switches."""
+    return (TIFF_DEFLATE if deflate else 0) | (TIFF_TILED if tiled else 0) | (TIFF_PACKBITS if packbits else 0)
+
+
+def handle_tiff_kinds(handle):
+    """The kinds word of anything that stands in for a ``Handle``: its ``tiff_kinds``, or the three mirror attributes where it has only those."""
+    kinds = getattr(handle, 'tiff_kinds', None)
+    return tiff_kinds(*(getattr(handle, key, False) for _, key, _ in TIFF_OPTIONS)) if kinds is None else int(kinds)
+
+
+@contextlib.contextmanager
+def tiff_options(handle, deflate=None, tiled=None, packbits=None):
+    """The handle options ``tiff_deflate_on_device`` / ``tiff_tiled_on_device`` / ``tiff_packbits_on_device`` set to the given values
+    for the body (None: left alone, and ``set_option`` is not needed).  An option that already stands as asked is not touched; each
+    one that was changed is put back on the way out, also when the body raises.  ``Handle.tiff_options`` is this function."""
+    changed = []
+    try:
+        for (_, key, _), value in zip(TIFF_OPTIONS, (deflate, tiled, packbits)):
+            before = bool(getattr(handle, key, False))
+            if value is not None and bool(value) != before:
+                handle.set_option(key, int(bool(value)))
+                changed.append((key, before))
+        yield
+    finally:
+        for key, before in changed:
+            handle.set_option(key, int(before))
 
 
 class TensorDesc(C.Structure):
@@ -172,23 +201,11 @@ def load_library():
                                           C.POINTER(vp), C.POINTER(vp), i32, vp, vp, vp, vp, C.c_longlong, vp, vp, vp]
     lib.ecseg_stat_fish_batch_bytes.argtypes = [i32, vp, vp, vp, i32]; lib.ecseg_stat_fish_batch_bytes.restype = C.c_longlong
     lib.ecseg_tiff_decode.argtypes = [vp, vp, C.c_longlong, vp, C.c_longlong, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
-    lib.ecseg_tiff_decode_routes.argtypes = [vp, C.c_longlong]
+    lib.ecseg_tiff_decode_routes.argtypes = [vp, C.c_longlong, C.c_uint]
     lib.ecseg_tiff_decode_batch.argtypes = [vp, vp, C.c_longlong, vp, i32, vp, C.c_longlong, vp, vp, vp]
-    lib.ecseg_tiff_decode_batch_bytes.argtypes = [vp, C.c_longlong, vp, i32]; lib.ecseg_tiff_decode_batch_bytes.restype = C.c_longlong
-    lib.ecseg_tiff_decode_batch_routes.argtypes = [vp, C.c_longlong, vp, i32]
-    lib.ecseg_tiff_decode_batch_counts.argtypes = [vp, C.c_longlong]
-    lib.ecseg_tiff_decode_routes_ex.argtypes = [vp, C.c_longlong, i32]
-    lib.ecseg_tiff_decode_batch_routes_ex.argtypes = [vp, C.c_longlong, vp, i32, i32]
-    lib.ecseg_tiff_decode_batch_counts_ex.argtypes = [vp, C.c_longlong, i32]
-    lib.ecseg_tiff_decode_batch_bytes_ex.argtypes = [vp, C.c_longlong, vp, i32, i32]; lib.ecseg_tiff_decode_batch_bytes_ex.restype = C.c_longlong
-    lib.ecseg_tiff_decode_routes_ex2.argtypes = [vp, C.c_longlong, i32, i32]
-    lib.ecseg_tiff_decode_batch_routes_ex2.argtypes = [vp, C.c_longlong, vp, i32, i32, i32]
-    lib.ecseg_tiff_decode_batch_counts_ex2.argtypes = [vp, C.c_longlong, i32, i32]
-    lib.ecseg_tiff_decode_batch_bytes_ex2.argtypes = [vp, C.c_longlong, vp, i32, i32, i32]; lib.ecseg_tiff_decode_batch_bytes_ex2.restype = C.c_longlong
-    lib.ecseg_tiff_decode_routes_ex3.argtypes = [vp, C.c_longlong, i32, i32, i32]
-    lib.ecseg_tiff_decode_batch_routes_ex3.argtypes = [vp, C.c_longlong, vp, i32, i32, i32, i32]
-    lib.ecseg_tiff_decode_batch_counts_ex3.argtypes = [vp, C.c_longlong, i32, i32, i32]
-    lib.ecseg_tiff_decode_batch_bytes_ex3.argtypes = [vp, C.c_longlong, vp, i32, i32, i32, i32]; lib.ecseg_tiff_decode_batch_bytes_ex3.restype = C.c_longlong
+    lib.ecseg_tiff_decode_batch_bytes.argtypes = [vp, C.c_longlong, vp, i32, C.c_uint]; lib.ecseg_tiff_decode_batch_bytes.restype = C.c_longlong
+    lib.ecseg_tiff_decode_batch_routes.argtypes = [vp, C.c_longlong, vp, i32, C.c_uint]
+    lib.ecseg_tiff_decode_batch_counts.argtypes = [vp, C.c_longlong, C.c_uint]
     lib.ecseg_min_cut.argtypes = [vp, vp, C.c_longlong, vp, i32, i32, vp, vp]
     lib.ecseg_min_cut_regions.argtypes = [vp, vp, i32, i32, C.c_double, i32, i32, i32, C.c_longlong, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.ecseg_nuset_forward.argtypes = [vp, vp, i32, i32, i32, i32, vp]
@@ -302,6 +319,8 @@ class Handle:
         self.images_per_group = 0          # 0: automatic (ecseg_set_images_per_group)
         self.native_seconds = 0.0          # time spent inside ecseg_meta_segment (stage report of `make metaseg`)
         self._pinned = {}                  # page-locked host buffers of host_empty: array address -> allocation
+        # mirrors of the three tiff_*_on_device options (set_option keeps them): what tiff_options restores from and tiff_kinds reads
+        self.tiff_deflate_on_device = self.tiff_tiled_on_device = self.tiff_packbits_on_device = False
 
     def close(self):
         if getattr(self, 'h', None):
@@ -359,12 +378,8 @@ class Handle:
 
     def set_option(self, key, value):
         self._check(self.lib.ecseg_set_option(self.h, key.encode(), int(value)), 'ecseg_set_option(%s)' % key)
-        if key == 'tiff_deflate_on_device':  # the mirror the ``deflate`` arguments of tiff_decode / tiff_decode_many restore from
-            self.tiff_deflate_on_device = bool(value)
-        if key == 'tiff_tiled_on_device':    # the mirror image_io.imread / imread_many and tiff_decode_many read: tiled files are taken
-            self.tiff_tiled_on_device = bool(value)
-        if key == 'tiff_packbits_on_device': # the same for PackBits files
-            self.tiff_packbits_on_device = bool(value)
+        if key in ('tiff_deflate_on_device', 'tiff_tiled_on_device', 'tiff_packbits_on_device'):
+            setattr(self, key, bool(value))
         if key == 'images_per_group':        # the same knob as set_images_per_group: keep the mirror the OOM retry restores from
             self.images_per_group = int(value)
 
@@ -1155,18 +1170,12 @@ class Handle:
         self._check(self.lib.ecseg_tiff_encode(self.h, _ptr(im), H, W, spp, int(bool(invert)), _ptr(out), cap, C.byref(n)), 'ecseg_tiff_encode')
         return out[:n.value].tobytes()
 
-    @contextlib.contextmanager
-    def _deflate_option(self, deflate):
-        """The handle option ``tiff_deflate_on_device`` set to ``deflate`` for one call (None: left as it is)."""
-        before = getattr(self, 'tiff_deflate_on_device', False)
-        if deflate is None or bool(deflate) == before:
-            yield
-            return
-        self.set_option('tiff_deflate_on_device', int(bool(deflate)))
-        try:
-            yield
-        finally:
-            self.set_option('tiff_deflate_on_device', int(before))
+    tiff_options = tiff_options
+
+    @property
+    def tiff_kinds(self):
+        """The kinds of file ``tiff_decode`` and ``tiff_decode_many`` take now, as the word of the routing functions."""
+        return tiff_kinds(self.tiff_deflate_on_device, self.tiff_tiled_on_device, self.tiff_packbits_on_device)
 
     def tiff_decode(self, data, deflate=None):
         """The bytes of a TIFF file -> what ``image_io.read_tiff`` returns for that file, (H, W) or (H, W, spp) uint8 / uint16, with
@@ -1174,7 +1183,7 @@ class Handle:
         BigTIFF, Deflate, and tiles or PackBits unless the handle option ``tiff_tiled_on_device`` / ``tiff_packbits_on_device`` is on).  Whether a file is worth sending here is ``image_io.imread``'s question (ecseg_tiff_decode_routes).  A corrupt file raises, with code -1.
         ``deflate``: True / False: the call runs with the handle option ``tiff_deflate_on_device`` on / off - on, Deflate strips
         (compression 8 and 32946) are decoded too, and such a file is an array or an error, not None; None: as the option stands."""
-        with self._deflate_option(deflate):
+        with self.tiff_options(deflate=deflate):
             return self._tiff_decode(data)
 
     def _tiff_decode(self, data):
@@ -1213,7 +1222,7 @@ class Handle:
         back to back (``pack_file_images``) and go in one call while the sum of what ecseg_tiff_decode_batch_bytes says each needs
         stays within ``budget_bytes`` of device scratch, else in several calls over consecutive files; a file that exceeds the budget
         alone goes alone.  ``deflate``: as in ``tiff_decode``."""
-        with self._deflate_option(deflate):
+        with self.tiff_options(deflate=deflate):
             return self._tiff_decode_many(datas, budget_bytes)
 
     def _tiff_decode_many(self, datas, budget_bytes):
@@ -1229,9 +1238,7 @@ class Handle:
             return out
         buf, ranges = pack_file_images([b for _, b in todo])     # packed once: every call reads its files through its rows of the table
         # what each file needs alone, asked once per file: their sum is at least what a call over them needs (every slot rounds up alone)
-        deflate, tiled = int(getattr(self, 'tiff_deflate_on_device', False)), int(getattr(self, 'tiff_tiled_on_device', False))
-        packbits = int(getattr(self, 'tiff_packbits_on_device', False))
-        needs = [self.lib.ecseg_tiff_decode_batch_bytes_ex3(_ptr(buf), buf.size, _ptr(np.ascontiguousarray(ranges[k:k + 1])), 1, deflate, tiled, packbits)
+        needs = [self.lib.ecseg_tiff_decode_batch_bytes(_ptr(buf), buf.size, _ptr(np.ascontiguousarray(ranges[k:k + 1])), 1, self.tiff_kinds)
                  for k in range(len(todo))]
         chunks, lo, held = [], 0, 0
         for hi, need in enumerate(needs):

@@ -22,6 +22,9 @@ int check_model(ecseg_ctx* h) {
     return ECSEG_OK;
 }
 
+// The three tiff_*_on_device options are a bit each of the handle's kinds word.
+static void set_tiff_kind(ecseg_ctx* h, unsigned bit, int on) { h->tiff_kinds = on ? h->tiff_kinds | bit : h->tiff_kinds & ~bit; }
+
 }  // namespace ecseg
 
 using namespace ecseg;
@@ -135,9 +138,9 @@ int ecseg_set_option(ecseg_ctx* h, const char* key, int value) {
     else if (k == "crop_mask") h->crop_mask = value != 0;
     else if (k == "unet_lanes" && value >= 0 && value <= 8) h->unet_lanes = value;   // 0: automatic
     else if (k == "lane_auto_windows" && value >= 0) h->lane_auto_windows = value;
-    else if (k == "tiff_deflate_on_device") h->tiff_deflate_on_device = value != 0;
-    else if (k == "tiff_tiled_on_device") h->tiff_tiled_on_device = value != 0;
-    else if (k == "tiff_packbits_on_device") h->tiff_packbits_on_device = value != 0;
+    else if (k == "tiff_deflate_on_device") set_tiff_kind(h, ECSEG_TIFF_DEFLATE, value);
+    else if (k == "tiff_tiled_on_device") set_tiff_kind(h, ECSEG_TIFF_TILED, value);
+    else if (k == "tiff_packbits_on_device") set_tiff_kind(h, ECSEG_TIFF_PACKBITS, value);
     else if (k == "min_cut_lds_pixels" && value >= 0 && value <= ECSEG_MIN_CUT_LDS_PIXELS) h->min_cut_lds_pixels = value;   // 0: every window in global memory
     else if (k == "min_cut_centers_lds_pixels" && value >= 0 && value <= ECSEG_MIN_CUT_CENTERS_LDS_PIXELS) h->min_cut_centers_lds_pixels = value;   // 0: every crop in global memory
     else return fail(h, ECSEG_E_INVALID, "unknown option or bad value: " + k);

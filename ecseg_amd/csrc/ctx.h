@@ -123,7 +123,7 @@ struct DevMem {
 // recognises them by, what the host made of every file, and the layout with raster i at i * H * W * C * bytes_per_sample.
 struct TiffsKey {
     const uint8_t* files = nullptr; long long bytes = 0; int n = 0, H = 0, W = 0, C = 0, bps = 0;
-    int opts = 0;                    // tiff_decode_opts(h) when the set was planned: which kinds of file the handle took then
+    unsigned opts = 0;               // h->tiff_kinds when the set was planned: which kinds of file the handle took then
     std::vector<int64_t> ranges;
     bool same_set(const TiffsKey& o) const {
         return files && files == o.files && bytes == o.bytes && n == o.n && H == o.H && W == o.W && C == o.C && bps == o.bps && ranges == o.ranges;
@@ -173,9 +173,10 @@ struct ecseg_ctx : ecseg::DevMem {
     ecseg::TiffsKey pre_tiffs;       // what d_pre holds decoded (files == nullptr: nothing), with pre_plan and the status words at pre_file_status
     ecseg::TiffsPlan pre_plan;
     uint32_t* pre_file_status = nullptr;   // in pre_arena: read by the call that takes the rasters, after ev_pre
-    int tiff_tiled_on_device = 0;     // ecseg_tiff_decode and ecseg_tiff_decode_batch take tiled files (tiffb_untile_kernel); 0: they are ECSEG_E_UNSUPPORTED
-    int tiff_deflate_on_device = 0;   // ecseg_tiff_decode and ecseg_tiff_decode_batch take Deflate strips (tiffb_inflate_kernel); 0: they are ECSEG_E_UNSUPPORTED
-    int tiff_packbits_on_device = 0;  // ecseg_tiff_decode and ecseg_tiff_decode_batch take PackBits files (tiffb_packbits_kernel); 0: they are ECSEG_E_UNSUPPORTED
+    // ECSEG_TIFF_* bits, set and cleared by the options tiff_deflate_on_device / tiff_tiled_on_device / tiff_packbits_on_device: ecseg_tiff_decode,
+    // ecseg_tiff_decode_batch and ecseg_meta_segment_tiffs take Deflate strips (tiffb_inflate_kernel) / tiled files (tiffb_untile_kernel) /
+    // PackBits files (tiffb_packbits_kernel); a kind whose bit is clear is ECSEG_E_UNSUPPORTED
+    unsigned tiff_kinds = 0;
     int min_cut_lds_pixels = ECSEG_MIN_CUT_LDS_PIXELS;   // windows above this many pixels keep their state in global memory (tests lower it)
     int min_cut_centers_lds_pixels = ECSEG_MIN_CUT_CENTERS_LDS_PIXELS;   // ecseg_min_cut_regions: crops above this many pixels keep their state in global memory (tests lower it)
     ecseg::PostWorkspace ws{};       // carved from post_arena
@@ -279,12 +280,11 @@ int png_gray_encode(ecseg_ctx* h, const char* who, const GraySource& src, int n_
 
 // The files of a batch as ecseg_tiff_decode judges each alone: info[i] and status[i] (with_strips: the file is to be decoded, not only
 // measured), and the rows of the layout for the files that are ECSEG_OK (dst_offsets may be null: the rasters back to back, 16-bit
-// ones on even offsets).  deflate: Deflate files are taken (the handle option tiff_deflate_on_device), else they are ECSEG_E_UNSUPPORTED;
-// tiled: so are tiled files (tiff_tiled_on_device); packbits: so are PackBits files (tiff_packbits_on_device).
+// ones on even offsets).  kinds (ECSEG_TIFF_*, a handle's tiff_kinds): the Deflate, tiled and PackBits files whose bit is set are taken,
+// the others are ECSEG_E_UNSUPPORTED.
 // Empty string, or which argument is wrong.
 std::string tiff_batch_plan(const uint8_t* files, long long files_bytes, const int64_t* ranges, int n_files, const int64_t* dst_offsets,
-                            bool with_strips, std::vector<TiffInfo>& info, std::vector<int>& status, std::vector<TdFileIn>& in, bool deflate = false,
-                            bool tiled = false, bool packbits = false);
+                            bool with_strips, std::vector<TiffInfo>& info, std::vector<int>& status, std::vector<TdFileIn>& in, unsigned kinds);
 // The rest of the way, one statement for ecseg_tiff_decode (a batch of one), ecseg_tiff_decode_batch and ecseg_meta_segment_tiffs:
 // p.tables from the files' parsed tags and p.L; then, with the buffers of tiff_decode_batch_bufs(p.L), the upload of the file span,
 // the table and the tables and the decode on stream s, the kernels between events e0 and e1.  p and the caller's files are read until

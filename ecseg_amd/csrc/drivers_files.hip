@@ -235,20 +235,19 @@ static int tiff_strips_in_file(const TiffInfo& t, size_t n, std::string& why) {
 
 // What ecseg_tiff_decode makes of a file before any device work, for itself and for every file of a batch: the tags in t, *parsed
 // (the file has a shape), and ECSEG_OK or the status with its reason.  with_strips: the file is to be decoded, not only measured.
-// deflate: Deflate strips are taken (the handle option tiff_deflate_on_device); without it they are the host reader's.  tiled: tiled
-// files are taken by the rule of parse_tiff (tiff_tiled_on_device); without it they are ECSEG_E_UNSUPPORTED and have no shape, as ever.
-// packbits: so are PackBits files (tiff_packbits_on_device), under the same words.
-static int tiff_decode_verdict(const uint8_t* file, size_t n, bool with_strips, bool deflate, bool tiled, bool packbits, TiffInfo& t, bool* parsed,
-                               std::string& why) {
+// kinds (ECSEG_TIFF_*): with ECSEG_TIFF_DEFLATE Deflate strips are taken (the handle option tiff_deflate_on_device); without it they are
+// the host reader's.  With ECSEG_TIFF_TILED tiled files are taken by the rule of parse_tiff (tiff_tiled_on_device); without it they are
+// ECSEG_E_UNSUPPORTED and have no shape, as ever.  ECSEG_TIFF_PACKBITS: so are PackBits files (tiff_packbits_on_device), under the same words.
+static int tiff_decode_verdict(const uint8_t* file, size_t n, bool with_strips, unsigned kinds, TiffInfo& t, bool* parsed, std::string& why) {
     t = TiffInfo();
-    int rc = parse_tiff(file, n, &t, tiled, packbits);
+    int rc = parse_tiff(file, n, &t, kinds);
     *parsed = rc == ECSEG_OK;
     if (rc != ECSEG_OK) {
         why = rc == ECSEG_E_UNSUPPORTED ? "a layout the native readers leave to the Python reader" : "not a TIFF file, or a corrupt one";
         return rc;
     }
     const unsigned long long bpp = t.bits / 8, line = (unsigned long long)t.W * t.spp * bpp, total = line * t.H;
-    if (tiff_is_deflate(t) && !deflate) { why = "Deflate strips are decoded by the host reader (option tiff_deflate_on_device: 0)"; return ECSEG_E_UNSUPPORTED; }
+    if (tiff_is_deflate(t) && !(kinds & ECSEG_TIFF_DEFLATE)) { why = "Deflate strips are decoded by the host reader (option tiff_deflate_on_device: 0)"; return ECSEG_E_UNSUPPORTED; }
     if (t.tw && (unsigned long long)t.tw * t.th * t.spp * bpp >= (1ull << 31)) { why = "tiles of 2 GiB or more"; return ECSEG_E_UNSUPPORTED; }
     if ((!t.tw && (unsigned long long)t.rps * line >= (1ull << 31)) || total >= (1ull << 40)) {
         why = "strips of 2 GiB or more, or an image of 1 TiB or more";
@@ -270,8 +269,7 @@ static TdFileIn td_file_in(const TiffInfo& t, size_t src_off, size_t n) {
 
 // The files of a batch as ecseg_tiff_decode judges each alone (ctx.h says what comes back).
 std::string ecseg::tiff_batch_plan(const uint8_t* files, long long files_bytes, const int64_t* ranges, int n_files, const int64_t* dst_offsets,
-                                   bool with_strips, std::vector<TiffInfo>& info, std::vector<int>& status, std::vector<TdFileIn>& in, bool deflate,
-                                   bool tiled, bool packbits) {
+                                   bool with_strips, std::vector<TiffInfo>& info, std::vector<int>& status, std::vector<TdFileIn>& in, unsigned kinds) {
     info.assign((size_t)n_files, TiffInfo()); status.assign((size_t)n_files, ECSEG_OK); in.assign((size_t)n_files, TdFileIn());
     long long end = 0;
     for (int i = 0; i < n_files; ++i) {                      // the geometry first: nothing is read through a bad range
@@ -286,7 +284,7 @@ std::string ecseg::tiff_batch_plan(const uint8_t* files, long long files_bytes, 
         const size_t off = (size_t)ranges[2 * (size_t)i], nb = (size_t)ranges[2 * (size_t)i + 1];
         TiffInfo& t = info[(size_t)i];
         bool parsed = false;
-        status[(size_t)i] = tiff_decode_verdict(files + off, nb, with_strips, deflate, tiled, packbits, t, &parsed, why);
+        status[(size_t)i] = tiff_decode_verdict(files + off, nb, with_strips, kinds, t, &parsed, why);
         if (!parsed) t.H = t.W = 0;                          // (no shape to report)
         if (status[(size_t)i] != ECSEG_OK) continue;
         TdFileIn& f = in[(size_t)i] = td_file_in(t, off, nb);
@@ -392,16 +390,13 @@ int ecseg_tiff_encode_batch(ecseg_ctx* h, const uint8_t* rasters, long long rast
 }
 
 // ---- TIFF files decoded on the device -------------------------------------------------------------------------------------------
-int ecseg_tiff_decode_routes_ex3(const uint8_t* file, long long n_bytes, int deflate, int tiled, int packbits) {
+// (the four handle-free questions: a word with a bit outside the three ECSEG_TIFF_* is a bad argument)
+static bool tiff_kinds_ok(unsigned kinds) { return !(kinds & ~(ECSEG_TIFF_DEFLATE | ECSEG_TIFF_TILED | ECSEG_TIFF_PACKBITS)); }
+
+int ecseg_tiff_decode_routes(const uint8_t* file, long long n_bytes, unsigned kinds) {
     TiffInfo t;
-    return file && n_bytes >= 0 && parse_tiff(file, (size_t)n_bytes, &t, tiled != 0, packbits != 0) == ECSEG_OK &&
-                   tiff_goes_to_device(t, deflate != 0, tiled != 0) ? 1 : 0;
+    return file && n_bytes >= 0 && tiff_kinds_ok(kinds) && parse_tiff(file, (size_t)n_bytes, &t, kinds) == ECSEG_OK && tiff_goes_to_device(t, kinds) ? 1 : 0;
 }
-int ecseg_tiff_decode_routes_ex2(const uint8_t* file, long long n_bytes, int deflate, int tiled) {
-    return ecseg_tiff_decode_routes_ex3(file, n_bytes, deflate, tiled, 0);
-}
-int ecseg_tiff_decode_routes_ex(const uint8_t* file, long long n_bytes, int deflate) { return ecseg_tiff_decode_routes_ex2(file, n_bytes, deflate, 0); }
-int ecseg_tiff_decode_routes(const uint8_t* file, long long n_bytes) { return ecseg_tiff_decode_routes_ex(file, n_bytes, 0); }
 
 int ecseg_tiff_decode(ecseg_ctx* h, const uint8_t* file, long long n_bytes, void* dst, long long dst_bytes, int* H, int* W, int* samples_per_pixel,
                       int* bits_per_sample) {
@@ -413,7 +408,7 @@ int ecseg_tiff_decode(ecseg_ctx* h, const uint8_t* file, long long n_bytes, void
     std::string why;
     const size_t n = (size_t)n_bytes;
     bool parsed = false;
-    int rc = tiff_decode_verdict(file, n, false, h->tiff_deflate_on_device != 0, h->tiff_tiled_on_device != 0, h->tiff_packbits_on_device != 0, t, &parsed, why);
+    int rc = tiff_decode_verdict(file, n, false, h->tiff_kinds, t, &parsed, why);
     if (parsed) { *H = (int)t.H; *W = (int)t.W; *samples_per_pixel = (int)t.spp; *bits_per_sample = (int)t.bits; }
     if (rc != ECSEG_OK) return fail(h, rc, "tiff_decode: " + why);
     const unsigned long long bpp = t.bits / 8, line = (unsigned long long)t.W * t.spp * bpp, total = line * t.H;
@@ -446,63 +441,37 @@ int ecseg_tiff_decode(ecseg_ctx* h, const uint8_t* file, long long n_bytes, void
 }
 
 // ---- the same over a batch of files: every strip of every file is a wave of one launch ----------------------------------------------
-int ecseg_tiff_decode_batch_counts_ex3(const uint8_t* file, long long n_bytes, int deflate, int tiled, int packbits) {
+int ecseg_tiff_decode_batch_counts(const uint8_t* file, long long n_bytes, unsigned kinds) {
     TiffInfo t;
     std::string why;
     bool parsed = false;
-    return file && n_bytes >= 0 && tiff_decode_verdict(file, (size_t)n_bytes, true, deflate != 0, tiled != 0, packbits != 0, t, &parsed, why) == ECSEG_OK &&
-                   tiff_batch_counts(t, deflate != 0, tiled != 0) ? 1 : 0;
+    return file && n_bytes >= 0 && tiff_kinds_ok(kinds) && tiff_decode_verdict(file, (size_t)n_bytes, true, kinds, t, &parsed, why) == ECSEG_OK &&
+                   tiff_batch_counts(t, kinds) ? 1 : 0;
 }
-int ecseg_tiff_decode_batch_counts_ex2(const uint8_t* file, long long n_bytes, int deflate, int tiled) {
-    return ecseg_tiff_decode_batch_counts_ex3(file, n_bytes, deflate, tiled, 0);
-}
-int ecseg_tiff_decode_batch_counts_ex(const uint8_t* file, long long n_bytes, int deflate) {
-    return ecseg_tiff_decode_batch_counts_ex2(file, n_bytes, deflate, 0);
-}
-int ecseg_tiff_decode_batch_counts(const uint8_t* file, long long n_bytes) { return ecseg_tiff_decode_batch_counts_ex(file, n_bytes, 0); }
 
-int ecseg_tiff_decode_batch_routes_ex3(const uint8_t* files, long long files_bytes, const int64_t* file_ranges, int n_files, int deflate, int tiled,
-                                       int packbits) {
-    if (n_files <= 0 || !files || !file_ranges || files_bytes < 0) return 0;
+int ecseg_tiff_decode_batch_routes(const uint8_t* files, long long files_bytes, const int64_t* file_ranges, int n_files, unsigned kinds) {
+    if (n_files <= 0 || !files || !file_ranges || files_bytes < 0 || !tiff_kinds_ok(kinds)) return 0;
     std::vector<TiffInfo> info; std::vector<int> status; std::vector<TdFileIn> in;
-    if (!tiff_batch_plan(files, files_bytes, file_ranges, n_files, nullptr, true, info, status, in, deflate != 0, tiled != 0, packbits != 0).empty()) return 0;
+    if (!tiff_batch_plan(files, files_bytes, file_ranges, n_files, nullptr, true, info, status, in, kinds).empty()) return 0;
     std::vector<const TiffInfo*> ok;
     for (int i = 0; i < n_files; ++i) if (status[(size_t)i] == ECSEG_OK) ok.push_back(&info[(size_t)i]);
-    return tiff_batch_goes_to_device(ok.data(), ok.size(), deflate != 0, tiled != 0) ? 1 : 0;
-}
-int ecseg_tiff_decode_batch_routes_ex2(const uint8_t* files, long long files_bytes, const int64_t* file_ranges, int n_files, int deflate, int tiled) {
-    return ecseg_tiff_decode_batch_routes_ex3(files, files_bytes, file_ranges, n_files, deflate, tiled, 0);
-}
-int ecseg_tiff_decode_batch_routes_ex(const uint8_t* files, long long files_bytes, const int64_t* file_ranges, int n_files, int deflate) {
-    return ecseg_tiff_decode_batch_routes_ex2(files, files_bytes, file_ranges, n_files, deflate, 0);
-}
-int ecseg_tiff_decode_batch_routes(const uint8_t* files, long long files_bytes, const int64_t* file_ranges, int n_files) {
-    return ecseg_tiff_decode_batch_routes_ex(files, files_bytes, file_ranges, n_files, 0);
+    return tiff_batch_goes_to_device(ok.data(), ok.size(), kinds) ? 1 : 0;
 }
 
 // (The Deflate kernel keeps its tables in LDS and takes nothing from the arena: a Deflate file needs what an LZW file of its tags needs.
 // A tiled file needs its row of the tiled-file table and the staging slots of its compressed tiles on top: tiff_decode_batch_bufs.
 // The PackBits kernel stages its stream in LDS: a PackBits file needs what an LZW file of its tags needs.)
-long long ecseg_tiff_decode_batch_bytes_ex3(const uint8_t* files, long long files_bytes, const int64_t* file_ranges, int n_files, int deflate, int tiled,
-                                            int packbits) {
+long long ecseg_tiff_decode_batch_bytes(const uint8_t* files, long long files_bytes, const int64_t* file_ranges, int n_files, unsigned kinds) {
+    if (!tiff_kinds_ok(kinds)) return -1;
     if (n_files == 0) return 0;
     if (n_files < 0 || !files || !file_ranges || files_bytes < 0) return -1;
     std::vector<TiffInfo> info; std::vector<int> status; std::vector<TdFileIn> in;
-    if (!tiff_batch_plan(files, files_bytes, file_ranges, n_files, nullptr, true, info, status, in, deflate != 0, tiled != 0, packbits != 0).empty()) return -1;
+    if (!tiff_batch_plan(files, files_bytes, file_ranges, n_files, nullptr, true, info, status, in, kinds).empty()) return -1;
     TdBatchLayout L;
     if (!td_batch_layout(in, L).empty()) return -1;
     Carver c;
     (void)tiff_decode_batch_bufs(c, L);
     return (long long)c.used;
-}
-long long ecseg_tiff_decode_batch_bytes_ex2(const uint8_t* files, long long files_bytes, const int64_t* file_ranges, int n_files, int deflate, int tiled) {
-    return ecseg_tiff_decode_batch_bytes_ex3(files, files_bytes, file_ranges, n_files, deflate, tiled, 0);
-}
-long long ecseg_tiff_decode_batch_bytes_ex(const uint8_t* files, long long files_bytes, const int64_t* file_ranges, int n_files, int deflate) {
-    return ecseg_tiff_decode_batch_bytes_ex2(files, files_bytes, file_ranges, n_files, deflate, 0);
-}
-long long ecseg_tiff_decode_batch_bytes(const uint8_t* files, long long files_bytes, const int64_t* file_ranges, int n_files) {
-    return ecseg_tiff_decode_batch_bytes_ex(files, files_bytes, file_ranges, n_files, 0);
 }
 
 int ecseg_tiff_decode_batch(ecseg_ctx* h, const uint8_t* files, long long files_bytes, const int64_t* file_ranges, int n_files, void* dst,
@@ -520,7 +489,7 @@ int ecseg_tiff_decode_batch(ecseg_ctx* h, const uint8_t* files, long long files_
     std::vector<int>& verdict = p.verdict;
     TdBatchLayout& L = p.L;
     std::string bad = tiff_batch_plan(files, files_bytes, file_ranges, n_files, dst ? dst_offsets : nullptr, dst != nullptr, info, verdict, in,
-                                      h->tiff_deflate_on_device != 0, h->tiff_tiled_on_device != 0, h->tiff_packbits_on_device != 0);
+                                      h->tiff_kinds);
     if (!bad.empty()) return fail(h, ECSEG_E_INVALID, me + bad);
     if (dst) {                                               // every raster inside the destination and clear of the others
         std::vector<std::pair<uint64_t, uint64_t>> spans;   // (offset, end) of the files that are decoded

@@ -361,7 +361,8 @@ int entry_values(const Reader& r, size_t e, std::vector<uint32_t>* out) {
 
 // ECSEG_OK, ECSEG_E_UNSUPPORTED (a valid layout this reader leaves to the Python one) or ECSEG_E_INVALID (corrupt); TiffInfo and
 // the declaration are in tiff_parse.h, for the device reader's driver
-int ecseg::parse_tiff(const uint8_t* buf, size_t n, TiffInfo* t, bool take_tiles, bool take_packbits) {
+int ecseg::parse_tiff(const uint8_t* buf, size_t n, TiffInfo* t, unsigned kinds) {
+    const bool take_tiles = kinds & ECSEG_TIFF_TILED, take_packbits = kinds & ECSEG_TIFF_PACKBITS;
     if (n < 8) return ECSEG_E_INVALID;
     if (buf[0] == 'I' && buf[1] == 'I') t->le = true;
     else if (buf[0] == 'M' && buf[1] == 'M') t->le = false;

@@ -315,19 +315,13 @@ struct MetaFiles { uint8_t* const* dapi; long long dapi_cap; long long* dapi_byt
 // slots (raster i at i * H * W * C * bps of d_aux8, or of d_pre for the call after: ecseg_prefetch_tiffs), and the host never sees a sample.
 struct MetaTiffs { const uint8_t* files; long long files_bytes; const int64_t* ranges; int32_t* status; };
 
-// The kinds of file the handle's decoders take, as one word: what a set decoded ahead was planned under (TiffsKey::opts).
-static int tiff_decode_opts(const ecseg_ctx* h) {
-    return (h->tiff_deflate_on_device ? 1 : 0) | (h->tiff_tiled_on_device ? 2 : 0) | (h->tiff_packbits_on_device ? 4 : 0);
-}
-
-// What the host makes of the files of one such call: every file judged as ecseg_tiff_decode judges it alone on this handle (its three
-// tiff_*_on_device options), a file of another shape than the call's refused, the rest laid out on the slots.  ECSEG_OK, or the
+// What the host makes of the files of one such call: every file judged as ecseg_tiff_decode judges it alone on this handle (its
+// tiff_kinds), a file of another shape than the call's refused, the rest laid out on the slots.  ECSEG_OK, or the
 // argument error.
 static int tiffs_plan(ecseg_ctx* h, const uint8_t* files, long long files_bytes, const int64_t* ranges, int n, int H, int W, int C, int bps, TiffsPlan& p) {
     const std::string me = "meta_segment_tiffs: ";
     std::vector<TiffInfo> info; std::vector<TdFileIn> in;
-    std::string bad = tiff_batch_plan(files, files_bytes, ranges, n, nullptr, true, info, p.verdict, in, h->tiff_deflate_on_device != 0,
-                                      h->tiff_tiled_on_device != 0, h->tiff_packbits_on_device != 0);
+    std::string bad = tiff_batch_plan(files, files_bytes, ranges, n, nullptr, true, info, p.verdict, in, h->tiff_kinds);
     if (!bad.empty()) return fail(h, ECSEG_E_INVALID, me + bad);
     const uint64_t slot = (uint64_t)H * W * C * bps;
     for (size_t i = 0; i < (size_t)n; ++i) {
@@ -366,7 +360,7 @@ static int meta_segment_run(ecseg_ctx* h, const void* img, int n_img, int H, int
     if (tiffs) {
         me.files = tiffs->files; me.bytes = tiffs->files_bytes; me.n = n_img; me.H = H; me.W = W; me.C = C; me.bps = bps;
         me.ranges.assign(tiffs->ranges, tiffs->ranges + 2 * (size_t)n_img);
-        me.opts = tiff_decode_opts(h);                     // (a set decoded ahead under other options is not this call's: withdrawn below)
+        me.opts = h->tiff_kinds;                     // (a set decoded ahead under other options is not this call's: withdrawn below)
         if (h->next_tiffs.same_set(me)) h->next_tiffs.files = nullptr;     // (registered for a call that never came: it names THIS call's files)
         ahead = h->pre_tiffs.same(me) && h->d_pre && h->pre_file_status;
         h->pre_tiffs.files = nullptr;                      // (files decoded ahead are for the very next call or for nobody)
@@ -462,7 +456,7 @@ static int meta_segment_run(ecseg_ctx* h, const void* img, int n_img, int H, int
             if ((rc = tiff_batch_launch(h, nx.files, h->pre_plan, ab, h->stream_in, h->ev_read[2], h->ev_read[3]))) return rc;
             HIP_TRY(h, hipEventRecord(h->ev_pre, h->stream_in));
             h->pre_file_status = ab.file_status;
-            nx.opts = tiff_decode_opts(h);                 // (what pre_plan was made under)
+            nx.opts = h->tiff_kinds;                 // (what pre_plan was made under)
             std::swap(h->pre_tiffs, nx);
             sent_tiffs = true;
         } else {

@@ -15,7 +15,7 @@ import zlib
 
 import numpy as np
 
-from ._lib import E_IO, E_UNSUPPORTED, load_library, pack_file_images
+from ._lib import E_IO, E_UNSUPPORTED, TIFF_OPTIONS, handle_tiff_kinds, load_library, pack_file_images, tiff_kinds
 
 # class k -> RGBA of ListedColormap(['#386cb0', '#ffff99', '#7fc97f', '#f0027f']) with vmin=0, vmax=4
 # (reference src/metaseg.py:47,52)
@@ -225,20 +225,19 @@ def image_shape(path):
 
 
 def tiff_goes_to_device(data, deflate=False, tiled=False, packbits=False):
-    """The routing rule of the device reader (csrc/tiff_parse.h, the one place that states it) on the bytes of a file.  ``deflate``:
-    Deflate files count too, from their own measured threshold on (ecseg_tiff_decode_routes_ex).  ``tiled``: so do tiled files, from a
-    measured tile count on (ecseg_tiff_decode_routes_ex2).  ``packbits``: PackBits files parse (ecseg_tiff_decode_routes_ex3); they
-    have no measured table and count in no rule."""
+    """The routing rule of the device reader (csrc/tiff_parse.h, the one place that states it) on the bytes of a file
+    (ecseg_tiff_decode_routes with the kinds word of the three switches).  ``deflate``: Deflate files count too, from their own measured
+    threshold on.  ``tiled``: so do tiled files, from a measured tile count on.  ``packbits``: PackBits files parse; they have no
+    measured table and count in no rule."""
     buf = np.frombuffer(data, np.uint8)
-    if not buf.size:
-        return False
-    if packbits:
-        return load_library().ecseg_tiff_decode_routes_ex3(buf.ctypes.data_as(C.c_void_p), buf.size, int(bool(deflate)), int(bool(tiled)), 1) == 1
-    if tiled:
-        return load_library().ecseg_tiff_decode_routes_ex2(buf.ctypes.data_as(C.c_void_p), buf.size, int(bool(deflate)), 1) == 1
-    if deflate:
-        return load_library().ecseg_tiff_decode_routes_ex(buf.ctypes.data_as(C.c_void_p), buf.size, 1) == 1
-    return load_library().ecseg_tiff_decode_routes(buf.ctypes.data_as(C.c_void_p), buf.size) == 1
+    return bool(buf.size) and load_library().ecseg_tiff_decode_routes(buf.ctypes.data_as(C.c_void_p), buf.size, tiff_kinds(deflate, tiled, packbits)) == 1
+
+
+def _switches(handle, deflate):
+    """The keywords the routing rules are asked with for this handle: ``deflate`` from the caller, the rest from the handle's kinds
+    word; only those that are on (a rule that stands in for ours may know none of the others)."""
+    kinds = tiff_kinds(deflate) | handle_tiff_kinds(handle)
+    return {name: True for name, _, bit in TIFF_OPTIONS if kinds & bit}
 
 
 def imread(path, handle=None, deflate=False):
@@ -247,9 +246,8 @@ def imread(path, handle=None, deflate=False):
     LZW files of many strips) is decoded there, and by the readers of this module when that returns None (a layout it leaves to them)
     or finds the file corrupt or unreadable, so that the error raised is theirs.  ``deflate``: the rule is asked with Deflate files
     counting, and the handle decodes such a file (``Handle.tiff_decode(data, deflate=True)``).  A handle with the option
-    ``tiff_tiled_on_device`` on (its attribute of that name) takes tiled files: the rule is asked with them counting
-    (ecseg_tiff_decode_routes_ex2); one with ``tiff_packbits_on_device`` on takes PackBits files, and the rule is asked with that
-    flag too (ecseg_tiff_decode_routes_ex3)."""
+    ``tiff_tiled_on_device`` or ``tiff_packbits_on_device`` on (its ``tiff_kinds``, or its attributes of those names) takes tiled /
+    PackBits files: the rule is asked with those kinds too."""
     if str(path).lower().endswith('.npy'):
         return np.load(path)
     if handle is not None and hasattr(handle, 'tiff_decode') and str(path).lower().endswith(('.tif', '.tiff')):
@@ -257,17 +255,8 @@ def imread(path, handle=None, deflate=False):
         try:
             with open(path, 'rb') as f:
                 data = f.read()
-            if getattr(handle, 'tiff_packbits_on_device', False):
-                if tiff_goes_to_device(data, deflate=deflate, tiled=bool(getattr(handle, 'tiff_tiled_on_device', False)), packbits=True):
-                    a = handle.tiff_decode(data, deflate=True) if deflate else handle.tiff_decode(data)
-            elif getattr(handle, 'tiff_tiled_on_device', False):
-                if tiff_goes_to_device(data, deflate=deflate, tiled=True):
-                    a = handle.tiff_decode(data, deflate=True) if deflate else handle.tiff_decode(data)
-            elif deflate:
-                if tiff_goes_to_device(data, deflate=True):
-                    a = handle.tiff_decode(data, deflate=True)
-            elif tiff_goes_to_device(data):
-                a = handle.tiff_decode(data)
+            if tiff_goes_to_device(data, **_switches(handle, deflate)):
+                a = handle.tiff_decode(data, deflate=True) if deflate else handle.tiff_decode(data)
         except OSError:
             pass
         except RuntimeError as e:
@@ -281,46 +270,23 @@ def imread(path, handle=None, deflate=False):
 def tiff_batch_goes_to_device(datas, deflate=False, tiled=False, packbits=False):
     """The routing rule for a set of files (csrc/tiff_parse.h, the one place that states it) on their bytes -> (whether the set goes to
     the device in one ``Handle.tiff_decode_many``, per file whether the rule counts it: the files that are sent when it goes).
-    ``deflate``: Deflate files count too, from their own measured threshold on (the ``_ex`` functions).  ``tiled``: so do tiled files
-    (the ``_ex2`` functions).  ``packbits``: PackBits files parse and count in no rule (the ``_ex3`` functions)."""
-    lib = load_library()
+    ``deflate``: Deflate files count too, from their own measured threshold on.  ``tiled``: so do tiled files.  ``packbits``: PackBits
+    files parse and count in no rule."""
+    lib, kinds = load_library(), tiff_kinds(deflate, tiled, packbits)
     bufs = [d if isinstance(d, np.ndarray) else np.frombuffer(d, np.uint8) for d in datas]
-    deflate, tiled = int(bool(deflate)), int(bool(tiled))
-    if packbits:
-        counts = [bool(b.size) and lib.ecseg_tiff_decode_batch_counts_ex3(b.ctypes.data_as(C.c_void_p), b.size, deflate, tiled, 1) == 1 for b in bufs]
-        sent = [b for b, c in zip(bufs, counts) if c]
-        if not sent:
-            return False, counts
-        buf, ranges = pack_file_images(sent)
-        return lib.ecseg_tiff_decode_batch_routes_ex3(buf.ctypes.data_as(C.c_void_p), buf.size, ranges.ctypes.data_as(C.c_void_p), len(ranges), deflate,
-                                                      tiled, 1) == 1, counts
-    if tiled:
-        counts = [bool(b.size) and lib.ecseg_tiff_decode_batch_counts_ex2(b.ctypes.data_as(C.c_void_p), b.size, deflate, 1) == 1 for b in bufs]
-        sent = [b for b, c in zip(bufs, counts) if c]
-        if not sent:
-            return False, counts
-        buf, ranges = pack_file_images(sent)
-        return lib.ecseg_tiff_decode_batch_routes_ex2(buf.ctypes.data_as(C.c_void_p), buf.size, ranges.ctypes.data_as(C.c_void_p), len(ranges), deflate,
-                                                      1) == 1, counts
-    counts = [bool(b.size) and lib.ecseg_tiff_decode_batch_counts_ex(b.ctypes.data_as(C.c_void_p), b.size, deflate) == 1 for b in bufs]
+    counts = [bool(b.size) and lib.ecseg_tiff_decode_batch_counts(b.ctypes.data_as(C.c_void_p), b.size, kinds) == 1 for b in bufs]
     sent = [b for b, c in zip(bufs, counts) if c]
     if not sent:
         return False, counts
     buf, ranges = pack_file_images(sent)                     # (no copy where the files lie in one buffer, as imread_many reads them)
-    goes = lib.ecseg_tiff_decode_batch_routes_ex(buf.ctypes.data_as(C.c_void_p), buf.size, ranges.ctypes.data_as(C.c_void_p), len(ranges), deflate) == 1
-    return goes, counts
+    return lib.ecseg_tiff_decode_batch_routes(buf.ctypes.data_as(C.c_void_p), buf.size, ranges.ctypes.data_as(C.c_void_p), len(ranges), kinds) == 1, counts
 
 
 def tiff_batch_counts(data, deflate=False, tiled=False, packbits=False):
-    """Whether the rule for a set counts this file (ecseg_tiff_decode_batch_counts: an LZW file that ecseg_tiff_decode accepts), on its
-    bytes as a uint8 array.  Touches no handle: `make metaseg`'s reader threads ask it.  The three switches: those of the ``_ex3``
-    function (all off: the function without a suffix)."""
-    if not data.size:
-        return False
-    if deflate or tiled or packbits:
-        return load_library().ecseg_tiff_decode_batch_counts_ex3(data.ctypes.data_as(C.c_void_p), data.size, int(bool(deflate)), int(bool(tiled)),
-                                                                 int(bool(packbits))) == 1
-    return load_library().ecseg_tiff_decode_batch_counts(data.ctypes.data_as(C.c_void_p), data.size) == 1
+    """Whether the rule for a set counts this file (ecseg_tiff_decode_batch_counts: an LZW file that ecseg_tiff_decode accepts, and
+    with a switch the files of that kind the rule counts), on its bytes as a uint8 array.  Touches no handle: `make metaseg`'s reader
+    threads ask it."""
+    return bool(data.size) and load_library().ecseg_tiff_decode_batch_counts(data.ctypes.data_as(C.c_void_p), data.size, tiff_kinds(deflate, tiled, packbits)) == 1
 
 
 def tiff_shape(data):
@@ -360,13 +326,7 @@ def imread_many(paths, handle=None, deflate=False):
                 continue
             held.append((k, pool[at:at + got]))
             at += n
-        if getattr(handle, 'tiff_packbits_on_device', False):    # (the handle option: PackBits files parse, and the call takes them)
-            goes, counts = tiff_batch_goes_to_device([d for _, d in held], deflate=deflate, tiled=bool(getattr(handle, 'tiff_tiled_on_device', False)),
-                                                     packbits=True)
-        elif getattr(handle, 'tiff_tiled_on_device', False):   # (the handle option: tiled files count in the rule, and the call takes them)
-            goes, counts = tiff_batch_goes_to_device([d for _, d in held], deflate=deflate, tiled=True)
-        else:
-            goes, counts = tiff_batch_goes_to_device([d for _, d in held], deflate=True) if deflate else tiff_batch_goes_to_device([d for _, d in held])
+        goes, counts = tiff_batch_goes_to_device([d for _, d in held], **_switches(handle, deflate))
         if goes:
             sent = [e for e, c in zip(held, counts) if c]
             many = handle.tiff_decode_many([d for _, d in sent], deflate=True) if deflate else handle.tiff_decode_many([d for _, d in sent])

@@ -25,6 +25,7 @@ measured thresholds on, a set from 280 Deflate strips; tiled and PackBits files 
 they stay with the Python reader - the same samples either way).
 """
 import concurrent.futures as cf
+import contextlib
 import json
 import os
 import queue
@@ -37,7 +38,7 @@ import numpy as np
 import yaml
 
 from . import csvio, dist, image_io
-from ._lib import E_HIP, E_NOMEM, EcsegError
+from ._lib import E_HIP, E_NOMEM, EcsegError, tiff_options
 from .utils import default_io_threads, get_imgs, load_model, save_img, tune_host_allocator
 
 MODEL_NAME = 'metaseg.h5'
@@ -426,17 +427,14 @@ def run(inpath, model, image_paths, rank=0, world=1, batch_images=8, io_threads=
     # (page-locking pays after ~5 uses of a buffer: not for a handful of images; pinned_min_images overrides the threshold)
     if pinned_mb > 0 and len(mine) >= (4 * batch_images if pinned_min_images is None else pinned_min_images):
         pool.start()
-    options = ('tiff_deflate_on_device', 'tiff_tiled_on_device', 'tiff_packbits_on_device')
-    turned_on = [(h, key) for h in handles for key, on in zip(options, kinds) if on and not getattr(h, key, False)]
     try:
-        for h, key in turned_on:
-            h.set_option(key, 1)                             # meta_segment_tiffs and prefetch_tiffs read them off the handle
-        return _run_threads(model, mine, start, per, rank, world, batch_images, io_threads, window, pending_writes, n_ec,
-                            status, log, stats, resume, tie, emit_probs, pool, files_on_device,
-                            (kinds if any(kinds) else True) if tiff_read_on_device and not emit_probs else False)
+        with contextlib.ExitStack() as options:              # meta_segment_tiffs and prefetch_tiffs read them off the handle; a handle goes back as it came
+            for h in handles:
+                options.enter_context(tiff_options(h, *(on or None for on in kinds)))
+            return _run_threads(model, mine, start, per, rank, world, batch_images, io_threads, window, pending_writes, n_ec,
+                                status, log, stats, resume, tie, emit_probs, pool, files_on_device,
+                                (kinds if any(kinds) else True) if tiff_read_on_device and not emit_probs else False)
     finally:
-        for h, key in turned_on:
-            h.set_option(key, 0)                             # a handle goes back as it came
         pool.stop()
         sys.setswitchinterval(old_switch)
 

@@ -56,6 +56,7 @@ A side effect on the process: ``main`` calls ``keep_freed_memory`` (glibc's ``ma
 image are recycled for the next instead of going back to the kernel between the device calls; ``ECSEG_MALLOC_DEFAULT=1`` switches
 that off.
 """
+import contextlib
 import datetime
 import math
 import os
@@ -712,12 +713,9 @@ def main(argv=None, handle=None):
         from ._lib import Handle
         handle = Handle(0)
     keep_freed_memory()
-    tiled_before = bool(getattr(handle, 'tiff_tiled_on_device', False))
-    if read_tiled and not tiled_before:
-        handle.set_option('tiff_tiled_on_device', 1)         # image_io.imread / imread_many read it off the handle
-    packbits_before = bool(getattr(handle, 'tiff_packbits_on_device', False))
-    if read_packbits and not packbits_before:
-        handle.set_option('tiff_packbits_on_device', 1)      # (the same)
+    from ._lib import tiff_options
+    options = contextlib.ExitStack()                         # image_io.imread / imread_many read the two options off the handle
+    options.enter_context(tiff_options(handle, tiled=read_tiled or None, packbits=read_packbits or None))
     rows, failed, seen = [], [], {}
     mask_of = lambda p: os.path.join(masks, os.path.basename(p)[:-4] + '.tif')
     ahead = {}                                               # tiff_read_batch: image path -> (image, mask) read with its chunk, until the image is done
@@ -856,13 +854,9 @@ def main(argv=None, handle=None):
         flush()
         run_chunk()
     finally:
+        options.close()                                      # a handle that was handed in goes back as it came
         if own:
             handle.close()
-        else:
-            if read_tiled and not tiled_before:
-                handle.set_option('tiff_tiled_on_device', 0)     # a handle that was handed in goes back as it came
-            if read_packbits and not packbits_before:
-                handle.set_option('tiff_packbits_on_device', 0)
     with open(os.path.join(out_root, 'stat_fish_lsq.csv'), 'w') as f:
         n_probe = seen.get('probes', len(PROBE_NAMES))
         f.write(csvio.csv_text(csv_columns(n_probe), widen_rows(rows) if n_probe == 3 else rows))

@@ -88,7 +88,12 @@ extern "C" {
  * driver to its answer whatever an earlier call left there; nothing existing changed.) */
 /* (still 5 - additive: ecseg_fish_distances_batch, the per-nucleus records of fish_distance_calculation for many images in one call;
  * nothing existing changed.) */
-#define ECSEG_ABI_VERSION 5
+/* 6: the kinds word.  ecseg_tiff_decode_routes, ecseg_tiff_decode_batch_routes, ecseg_tiff_decode_batch_counts and
+ * ecseg_tiff_decode_batch_bytes take a last argument `unsigned kinds` (ECSEG_TIFF_DEFLATE | ECSEG_TIFF_TILED | ECSEG_TIFF_PACKBITS; 0: the
+ * answers they gave without it) and replace their twelve copies with the suffixes _ex (deflate), _ex2 (deflate, tiled) and _ex3
+ * (deflate, tiled, packbits), which are gone: _exN(..., d, t, p) is now (..., d * ECSEG_TIFF_DEFLATE | t * ECSEG_TIFF_TILED |
+ * p * ECSEG_TIFF_PACKBITS).  The three tiff_*_on_device options and every other entry point are as they were. */
+#define ECSEG_ABI_VERSION 6
 
 #define ECSEG_OK             0
 #define ECSEG_E_INVALID     -1   /* bad argument / shape / plan */
@@ -655,19 +660,14 @@ long long ecseg_stat_fish_batch_bytes(int n_images, const int32_t* shapes, const
  * ecseg_tiff_info plus ecseg_tiff_read return for the same bytes - ECSEG_OK, the shape in *H, *W, *samples_per_pixel,
  * *bits_per_sample and the samples in dst as native-endian (H, W, spp), strips that end early or are missing zero-filled - or
  * ECSEG_E_INVALID (not a TIFF, a corrupt IFD, a strip offset behind the file, a corrupt LZW stream in any strip: dst is not
- * written).  ECSEG_E_UNSUPPORTED: everything ecseg_tiff_info leaves to the Python reader, and Deflate strips unless the handle
- * option "tiff_deflate_on_device" is on (below; also strips of 2 GiB or more); the shape is reported then too
+ * written).  ECSEG_E_UNSUPPORTED: everything ecseg_tiff_info leaves to the Python reader, and Deflate strips, tiles and PackBits files unless the
+ * handle option of their kind is on (the section below; also strips of 2 GiB or more); the shape is reported then too
  * when the file has one.  dst == NULL: only the shape (and the ECSEG_E_UNSUPPORTED verdict).  dst_bytes below H * W * spp *
  * bits / 8: ECSEG_E_INVALID with nothing written.  file: n_bytes of host memory, uploaded by the call; one synchronous call,
  * scratch (file image, strip tables, raster, status words) from the handle's call arena; device time of the kernels in
  * ECSEG_T_COUNT. */
 int ecseg_tiff_decode(ecseg_ctx* h, const uint8_t* file, long long n_bytes, void* dst, long long dst_bytes,
                       int* H, int* W, int* samples_per_pixel, int* bits_per_sample);
-/* The one rule that says whether a file is worth sending to ecseg_tiff_decode (image_io.imread(path, handle) asks it): 1 for an
- * LZW file of at least 1040 strips, 0 for everything else, unreadable files included.  A strip is one serial stream on one wave,
- * so the device is faster than a host core only where many strips decode at once; the measurement behind the threshold is in
- * DESIGN.md 5.9.  No device work. */
-int ecseg_tiff_decode_routes(const uint8_t* file, long long n_bytes);
 /* ecseg_tiff_decode over n_files files in one call (csrc/tiff_decode_kernels.hip, the tiffb_* kernels): the strips of all files are
  * one grid, a wave per strip, so files of few strips find in each other the parallelism one of them lacks.  files: files_bytes of
  * host memory; file i is bytes [file_ranges[2 i], file_ranges[2 i] + file_ranges[2 i + 1]) of it, the ranges in ascending order
@@ -686,82 +686,78 @@ int ecseg_tiff_decode_routes(const uint8_t* file, long long n_bytes);
 int ecseg_tiff_decode_batch(ecseg_ctx* h, const uint8_t* files, long long files_bytes, const int64_t* file_ranges /* [n][2] offset, n_bytes */,
                             int n_files, void* dst, long long dst_bytes, const int64_t* dst_offsets /* [n] */,
                             int32_t* shapes /* [n][4] H, W, spp, bits */, int32_t* status /* [n] */);
-/* The bytes of the call arena ecseg_tiff_decode_batch needs for these files with their rasters back to back (16-bit ones on even
- * offsets), for a caller that splits a large set into several calls; -1 for bad arguments, 0 for no files.  No device work. */
-long long ecseg_tiff_decode_batch_bytes(const uint8_t* files, long long files_bytes, const int64_t* file_ranges, int n_files);
-/* The one rule that says whether a set of files is worth sending to ecseg_tiff_decode_batch (image_io.imread_many asks it): 1 when
- * the LZW strips of the files ecseg_tiff_decode accepts, whatever their own strip count, are at least 1040 together; uncompressed
- * and Deflate files are never counted, nor files whose strips decode to more than 62640 bytes (nothing was measured there) or whose
- * strip table is shorter than the image (as in the single-file rule).  0 for
- * everything else, bad arguments included.  ecseg_tiff_decode_batch_counts: 1 for a
- * file that the rule counts - the files of a set that goes which are sent -, 0 for any other.  The measurement behind the threshold
- * is the batch table of DESIGN.md 5.9.  No device work. */
-int ecseg_tiff_decode_batch_routes(const uint8_t* files, long long files_bytes, const int64_t* file_ranges, int n_files);
-int ecseg_tiff_decode_batch_counts(const uint8_t* file, long long n_bytes);
-/* Deflate strips (compression 8, and 32946 of older writers) on the device, all opt-in.  ecseg_set_option(h, "tiff_deflate_on_device",
- * 1) (default 0): ecseg_tiff_decode and ecseg_tiff_decode_batch on that handle take such files - one wave per strip in a kernel of
- * its own beside the LZW one (csrc/tiff_inflate_strip.h: each strip a zlib stream of its own, matches copied in the raster, Adler-32
- * checked), mixed freely with LZW and uncompressed files in a batch - and return ECSEG_OK or ECSEG_E_INVALID for them where they
- * returned ECSEG_E_UNSUPPORTED, by the host reader's rules (ecseg_tiff_read: a short stream zero-filled, a long one cut, every zlib
- * data error corrupt; a stream that ends before the strip is full and before its own end is corrupt, as uncompress of zlib 1.2.9 and
- * later has it).  BigTIFF files stay ECSEG_E_UNSUPPORTED, and so do tiled and PackBits files without the options below;
- * ecseg_meta_segment_tiffs reads the option off its handle as the two do.
- *   The four functions above that take no handle answer as before; these take the switch as `deflate` (0: the same answers).  With
- * it a Deflate file counts from its own thresholds on (csrc/tiff_parse.h, the Deflate tables of DESIGN.md 5.9: a single file from
- * 1040 strips, a set from 280 Deflate strips together, the smallest measured counts at which the device call's maximum is below
- * ecseg_tiff_read's minimum; strips that decode to more than 62640 bytes are not counted, nothing was measured there).  ecseg_tiff_decode_batch_bytes_ex: the arena bytes with Deflate files taken (the
- * Deflate kernel keeps its tables in LDS and needs nothing more from the arena than an LZW file of the same tags). */
-int ecseg_tiff_decode_routes_ex(const uint8_t* file, long long n_bytes, int deflate);
-int ecseg_tiff_decode_batch_routes_ex(const uint8_t* files, long long files_bytes, const int64_t* file_ranges, int n_files, int deflate);
-int ecseg_tiff_decode_batch_counts_ex(const uint8_t* file, long long n_bytes, int deflate);
-long long ecseg_tiff_decode_batch_bytes_ex(const uint8_t* files, long long files_bytes, const int64_t* file_ranges, int n_files, int deflate);
-/* Tiled files (TileWidth, TileLength, TileOffsets, TileByteCounts: tags 322 to 325; what Bio-Formats / OME-TIFF, QuPath, libvips and
- * tifffile with tile= write) on the device, all opt-in.  ecseg_set_option(h, "tiff_tiled_on_device", 1) (default 0): ecseg_tiff_decode
- * and ecseg_tiff_decode_batch on that handle take a tiled file whose tile extents are positive multiples of 16 (of at most 2^20),
- * chunky (or one sample per pixel), 8 or 16 unsigned bits, uncompressed or LZW - Deflate with "tiff_deflate_on_device" on as well -,
- * predictor 1 or 2, without strip tags, with a tile table entry for each of its ceil(H / TileLength) * ceil(W / TileWidth) tiles and
- * tiles below 2 GiB.  Every other tiled file stays ECSEG_E_UNSUPPORTED (BigTIFF, PackBits tiles without "tiff_packbits_on_device", planar RGB, float samples, a short
- * tile table, strip and tile tags together), as does every tiled file with the option off.  A tile is a strip of the batch grid - a
- * wave per tile, beside the strips of other files in the same launch - whose stream decodes into a staging slot of one tile in the
- * call arena; tiffb_untile_kernel (csrc/tiff_untile.h) then puts every tile row in its place in the raster: byte order, the horizontal
- * predictor restarting at each tile's first column, the padding of right and bottom edge tiles dropped.  Uncompressed tiles have no
- * slot and are placed from the file image.
- *   The oracle is the Python reader (image_io.read_tiff), the one reader of tiled files so far: ECSEG_OK with its samples, or
- * ECSEG_E_INVALID where it raises on a tile's stream (a corrupt LZW stream; a Deflate stream that is corrupt, cut short or empty).
- * Like that reader's slice, a tile's bytes are clamped to the file: an offset behind the file or a count that leaves it is a shorter
- * or empty stream - zeros for an LZW or uncompressed tile, ECSEG_E_INVALID for a Deflate one - not an error of its own.  (One
- * difference remains, in the inflate routine shared with strips: a Deflate stream that gave the whole tile and ends inside its
- * trailer is taken, where zlib.decompress refuses it.)  ecseg_meta_segment_tiffs reads the option off its handle as the two do.
- *   The handle-free functions get the switch as `tiled` beside `deflate` (both 0: the answers of the functions without a suffix).
- * A tiled file counts in the two routing rules only from a measured tile count on (csrc/tiff_parse.h; tools/time_tiff_decode.py
- * --tiled).  That table is NOT MEASURED yet: the rules answer 0 for every tiled file and every set of them, and only
- * an explicit ecseg_tiff_decode / ecseg_tiff_decode_batch call decodes one on the device.  ecseg_tiff_decode_batch_bytes_ex2: the
- * arena bytes with tiled files taken - the staging slots of their compressed tiles and a 32-byte table row per tiled file on top. */
-int ecseg_tiff_decode_routes_ex2(const uint8_t* file, long long n_bytes, int deflate, int tiled);
-int ecseg_tiff_decode_batch_routes_ex2(const uint8_t* files, long long files_bytes, const int64_t* file_ranges, int n_files, int deflate, int tiled);
-int ecseg_tiff_decode_batch_counts_ex2(const uint8_t* file, long long n_bytes, int deflate, int tiled);
-long long ecseg_tiff_decode_batch_bytes_ex2(const uint8_t* files, long long files_bytes, const int64_t* file_ranges, int n_files, int deflate, int tiled);
-/* PackBits files (compression 32773: older ImageJ and Photoshop exports) on the device, opt-in.  ecseg_set_option(h,
- * "tiff_packbits_on_device", 1) (default 0): ecseg_tiff_decode and ecseg_tiff_decode_batch on that handle take such a file, strips
- * or - with "tiff_tiled_on_device" on as well - tiles, held to every other rule of the readers above: a wave per strip or tile in a
- * kernel of its own beside the LZW and Deflate ones (tiffb_packbits_kernel; csrc/tiff_packbits_strip.h: the header walk in every
- * lane, the up to 128 bytes of a run written by the lanes), byte order and predictor by the code that serves the other codecs, a
- * tile through its staging slot and tiffb_untile_kernel.  With the option off every PackBits file is ECSEG_E_UNSUPPORTED without a
- * shape, as before.
- *   The oracle is the Python reader (image_io.read_tiff with _packbits_decode), the one reader of PackBits files: header h < 128:
- * h + 1 literal bytes; h > 128: the next byte 257 - h times; 128: nothing.  That decoder raises for no stream - one that ends early
- * gives what it has and zeros behind, a run that would pass the strip's end is cut there, bytes left over are not looked at - so no
- * PackBits stream is ECSEG_E_INVALID; a strip that starts behind the end of the file is, as for every codec.
- *   The handle-free functions get the switch as `packbits` beside `deflate` and `tiled` (all 0: the answers of the functions without
- * a suffix).  No table of tools/time_tiff_decode.py --packbits is measured: with the switch a PackBits file parses,
- * and it counts in no routing rule, strips or tiles; only an explicit call decodes one on the device.
- * ecseg_tiff_decode_batch_bytes_ex3: the arena bytes with PackBits files taken (what an LZW file of the same tags needs). */
-int ecseg_tiff_decode_routes_ex3(const uint8_t* file, long long n_bytes, int deflate, int tiled, int packbits);
-int ecseg_tiff_decode_batch_routes_ex3(const uint8_t* files, long long files_bytes, const int64_t* file_ranges, int n_files, int deflate, int tiled,
-                                       int packbits);
-int ecseg_tiff_decode_batch_counts_ex3(const uint8_t* file, long long n_bytes, int deflate, int tiled, int packbits);
-long long ecseg_tiff_decode_batch_bytes_ex3(const uint8_t* files, long long files_bytes, const int64_t* file_ranges, int n_files, int deflate, int tiled,
-                                            int packbits);
+
+/* ---- which files are worth sending: four questions without a handle, and the kinds of file a decoder takes -------------------------- */
+/* A word of these bits says which kinds of file are taken beside LZW and uncompressed strips.  A handle keeps one, all bits clear by
+ * default, set and cleared by ecseg_set_option(h, "tiff_deflate_on_device" / "tiff_tiled_on_device" / "tiff_packbits_on_device", 0 or 1):
+ * ecseg_tiff_decode and ecseg_tiff_decode_batch on that handle take the kinds whose bit is set and answer ECSEG_E_UNSUPPORTED for the
+ * others, and ecseg_meta_segment_tiffs reads the word off its handle as the two do.  The four functions at the end of this section take
+ * no handle and get the word as their last argument, `kinds`; 0 gives the answers for LZW and uncompressed strips alone, and a bit
+ * outside the three is a bad argument.  BigTIFF files stay ECSEG_E_UNSUPPORTED under every word. */
+#define ECSEG_TIFF_DEFLATE  1u
+#define ECSEG_TIFF_TILED    2u
+#define ECSEG_TIFF_PACKBITS 4u
+/* The rule for one file, ecseg_tiff_decode_routes (image_io.imread(path, handle) asks it): 1 for an LZW file of at least 1040 strips,
+ * 0 for everything else, unreadable files and bad arguments included.  A strip is one serial stream on one wave, so the device is
+ * faster than a host core only where many strips decode at once; the measurement behind the threshold is in DESIGN.md 5.9.
+ *   The rule for a set of files that would go in one ecseg_tiff_decode_batch call, ecseg_tiff_decode_batch_routes
+ * (image_io.imread_many asks it): 1 when the LZW strips of the files ecseg_tiff_decode accepts, whatever their own strip count, are at
+ * least 1040 together; uncompressed files are never counted, nor - under any word - files whose strips decode to more than 62640
+ * bytes (nothing was measured there) or whose strip table is shorter than the image (as in the single-file rule).  0 for everything
+ * else, bad arguments included.  ecseg_tiff_decode_batch_counts: 1 for a file that the rule counts - the files of a set that goes
+ * which are sent -, 0 for any other.  The measurement behind the threshold is the batch table of DESIGN.md 5.9.
+ *   ecseg_tiff_decode_batch_bytes: the bytes of the call arena ecseg_tiff_decode_batch needs for these files, as a handle with this
+ * word takes them, with their rasters back to back (16-bit ones on even offsets), for a caller that splits a large set into several
+ * calls; -1 for bad arguments, 0 for no files.  A file the word does not take is left out and needs nothing.
+ *   None of the four does device work.  What each kind adds:
+ *
+ * ECSEG_TIFF_DEFLATE - Deflate strips (compression 8, and 32946 of older writers), option "tiff_deflate_on_device".  Accepted: such
+ * files, one wave per strip in a kernel of its own beside the LZW one (csrc/tiff_inflate_strip.h: each strip a zlib stream of its own,
+ * matches copied in the raster, Adler-32 checked), mixed freely with LZW and uncompressed files in a batch; they return ECSEG_OK or
+ * ECSEG_E_INVALID where they returned ECSEG_E_UNSUPPORTED.  The oracle is the host reader (ecseg_tiff_read): a short stream
+ * zero-filled, a long one cut, every zlib data error corrupt; a stream that ends before the strip is full and before its own end is
+ * corrupt, as uncompress of zlib 1.2.9 and later has it.  Routing: with the bit a Deflate file counts from its own thresholds on
+ * (csrc/tiff_parse.h, the Deflate tables of DESIGN.md 5.9: a single file from 1040 strips, a set from 280 Deflate strips together,
+ * summed apart from the LZW strips - the smallest measured counts at which the device call's maximum is below ecseg_tiff_read's
+ * minimum); without it a Deflate file is never counted.  Arena: the Deflate kernel keeps its tables in LDS and needs nothing more
+ * than an LZW file of the same tags.
+ *
+ * ECSEG_TIFF_TILED - tiled files (TileWidth, TileLength, TileOffsets, TileByteCounts: tags 322 to 325; what Bio-Formats / OME-TIFF,
+ * QuPath, libvips and tifffile with tile= write), option "tiff_tiled_on_device".  Accepted: a tiled file whose tile extents are
+ * positive multiples of 16 (of at most 2^20), chunky (or one sample per pixel), 8 or 16 unsigned bits, uncompressed or LZW - Deflate
+ * with ECSEG_TIFF_DEFLATE as well, PackBits with ECSEG_TIFF_PACKBITS as well -, predictor 1 or 2, without strip tags, with a tile table
+ * entry for each of its ceil(H / TileLength) * ceil(W / TileWidth) tiles and tiles below 2 GiB.  Every other tiled file stays
+ * ECSEG_E_UNSUPPORTED (BigTIFF, PackBits tiles without ECSEG_TIFF_PACKBITS, planar RGB, float samples, a short tile table, strip and
+ * tile tags together), as does every tiled file without the bit - without a shape.  A tile is a strip of the batch grid - a wave per
+ * tile, beside the strips of other files in the same launch - whose stream decodes into a staging slot of one tile in the call arena;
+ * tiffb_untile_kernel (csrc/tiff_untile.h) then puts every tile row in its place in the raster: byte order, the horizontal predictor
+ * restarting at each tile's first column, the padding of right and bottom edge tiles dropped.  Uncompressed tiles have no slot and
+ * are placed from the file image.  The oracle is the Python reader (image_io.read_tiff), the one reader of tiled files so far:
+ * ECSEG_OK with its samples, or ECSEG_E_INVALID where it raises on a tile's stream (a corrupt LZW stream; a Deflate stream that is
+ * corrupt, cut short or empty).  Like that reader's slice, a tile's bytes are clamped to the file: an offset behind the file or a
+ * count that leaves it is a shorter or empty stream - zeros for an LZW or uncompressed tile, ECSEG_E_INVALID for a Deflate one - not
+ * an error of its own.  (One difference remains, in the inflate routine shared with strips: a Deflate stream that gave the whole tile
+ * and ends inside its trailer is taken, where zlib.decompress refuses it.)  Routing: a tiled file counts in the two rules only from a
+ * measured tile count on (csrc/tiff_parse.h; tools/time_tiff_decode.py --tiled).  That table is NOT MEASURED yet: the
+ * rules answer 0 for every tiled file and every set of them, and only an explicit ecseg_tiff_decode / ecseg_tiff_decode_batch call
+ * decodes one on the device.  Arena: the staging slots of a file's compressed tiles and a 32-byte table row per tiled file on top.
+ *
+ * ECSEG_TIFF_PACKBITS - PackBits files (compression 32773: older ImageJ and Photoshop exports), option "tiff_packbits_on_device".
+ * Accepted: such a file, strips or - with ECSEG_TIFF_TILED as well - tiles, held to every other rule of the readers above: a wave per
+ * strip or tile in a kernel of its own beside the LZW and Deflate ones (tiffb_packbits_kernel; csrc/tiff_packbits_strip.h: the header
+ * walk in every lane, the up to 128 bytes of a run written by the lanes), byte order and predictor by the code that serves the other
+ * codecs, a tile through its staging slot and tiffb_untile_kernel.  Without the bit every PackBits file is ECSEG_E_UNSUPPORTED
+ * without a shape.  The oracle is the Python reader (image_io.read_tiff with _packbits_decode), the one reader of PackBits files:
+ * header h < 128: h + 1 literal bytes; h > 128: the next byte 257 - h times; 128: nothing.  That decoder raises for no stream - one
+ * that ends early gives what it has and zeros behind, a run that would pass the strip's end is cut there, bytes left over are not
+ * looked at - so no PackBits stream is ECSEG_E_INVALID; a strip that starts behind the end of the file is, as for every codec.
+ * Routing: no table of tools/time_tiff_decode.py --packbits is measured (NOT MEASURED): with the bit a PackBits file
+ * parses, and it counts in no routing rule, strips or tiles; only an explicit call decodes one on the device.  Arena: what an LZW
+ * file of the same tags needs. */
+int ecseg_tiff_decode_routes(const uint8_t* file, long long n_bytes, unsigned kinds);
+int ecseg_tiff_decode_batch_counts(const uint8_t* file, long long n_bytes, unsigned kinds);
+int ecseg_tiff_decode_batch_routes(const uint8_t* files, long long files_bytes, const int64_t* file_ranges, int n_files, unsigned kinds);
+long long ecseg_tiff_decode_batch_bytes(const uint8_t* files, long long files_bytes, const int64_t* file_ranges, int n_files, unsigned kinds);
 
 /* ---- label PNG files encoded on the device ----------------------------------------------------------------------------------- */
 /* The file ecseg_png_write_labels would write for each of n_img label images, byte for byte (signature, IHDR, one IDAT, IEND), as

@@ -312,7 +312,7 @@ def test_entry_point_is_declared_and_exported():
     from ecseg_amd._lib import ABI_VERSION, EXPORTS, LIB_PATH
     header = open(os.path.join(ROOT, 'include', 'ecseg_hip.h')).read()
     assert re.search(r'\becseg_fish_distances\s*\(', header) and 'ecseg_fish_distances' in EXPORTS
-    assert ABI_VERSION == 5 and '#define ECSEG_ABI_VERSION 5' in header
+    assert ABI_VERSION == 6 and '#define ECSEG_ABI_VERSION 6' in header
     from ecseg_amd import build
     assert 'fishdist_kernels.hip' in build.SOURCES
     if os.path.exists(LIB_PATH):

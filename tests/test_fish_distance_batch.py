@@ -117,7 +117,7 @@ def test_a_folder_without_images_and_one_of_a_single_image(tmp_path, monkeypatch
 def test_the_header_the_binding_and_the_documents_name_the_feature():
     header = open(os.path.join(ROOT, 'include', 'ecseg_hip.h')).read()
     assert re.search(r'\becseg_fish_distances_batch\s*\(', header) and 'ECSEG_FISH_DISTANCES_BATCH_MAX_IMAGES' in header
-    assert 'still 5 - additive: ecseg_fish_distances_batch' in header and '#define ECSEG_ABI_VERSION 5' in header
+    assert 'still 5 - additive: ecseg_fish_distances_batch' in header and '#define ECSEG_ABI_VERSION 6' in header
     assert 'ecseg_fish_distances_batch' in _lib.EXPORTS and hasattr(_lib.Handle, 'fish_distances_many')
     assert _lib.Handle.FISH_DISTANCES_BATCH_MAX_IMAGES == int(re.search(r'#define ECSEG_FISH_DISTANCES_BATCH_MAX_IMAGES (\d+)', header).group(1))
     binding = open(os.path.join(ROOT, 'ecseg_amd', '_lib.py')).read()

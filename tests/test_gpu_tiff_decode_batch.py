@@ -315,7 +315,7 @@ def test_a_lowered_budget_splits_the_batch_into_several_calls(gpu, pool, monkeyp
     assert calls == [len(batch)]
     del calls[:]
     buf, tab = _packed(datas)
-    need = load_library().ecseg_tiff_decode_batch_bytes(buf.ctypes.data_as(C.c_void_p), buf.size, tab.ctypes.data_as(C.c_void_p), len(tab))
+    need = load_library().ecseg_tiff_decode_batch_bytes(buf.ctypes.data_as(C.c_void_p), buf.size, tab.ctypes.data_as(C.c_void_p), len(tab), 0)
     assert need > 6 * 256
     split = gpu.tiff_decode_many(datas, budget_bytes=need // 3)
     assert len(calls) >= 3 and sum(calls) == len(batch), calls

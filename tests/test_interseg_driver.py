@@ -196,7 +196,7 @@ def test_new_entry_points_are_declared_and_exported():
     header = open(os.path.join(ROOT, 'include', 'ecseg_hip.h')).read()
     for name in ('ecseg_nuclei_regions', 'ecseg_nucleus_crops'):
         assert re.search(r'\b%s\s*\(' % name, header) and name in EXPORTS
-    assert ABI_VERSION == 5
+    assert ABI_VERSION == 6
 
 
 def test_csv_columns_and_text():

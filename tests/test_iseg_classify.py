@@ -251,7 +251,7 @@ def test_the_documents_the_header_and_the_binding_name_the_feature():
     header = open(os.path.join(ROOT, 'include', 'ecseg_hip.h')).read()
     for name in ('ecseg_classify_nucleus_crops', 'ecseg_iseg_classifier_inputs_debug'):
         assert re.search(r'\b%s\s*\(' % name, header) and name in EXPORTS
-    assert ABI_VERSION == 5 and hasattr(Handle, 'classify_nucleus_crops')
+    assert ABI_VERSION == 6 and hasattr(Handle, 'classify_nucleus_crops')
     assert re.search(r'^  # classify_on_device: true', open(os.path.join(ROOT, 'config.yaml')).read(), re.M)
     assert yaml.safe_load(open(os.path.join(ROOT, 'config.yaml')))['interseg'].get('classify_on_device', False) is False
     for doc in ('README.md', 'DESIGN.md', 'INTEGRATION.md'):

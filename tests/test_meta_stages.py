@@ -18,7 +18,7 @@ from oracle import postproc          # noqa: E402
 def test_entry_point_is_registered_as_an_addition_to_abi_5():
     from ecseg_amd import _lib
     hdr = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'include', 'ecseg_hip.h')).read()
-    assert 'still 5 - additive: ecseg_meta_inference_stages_debug' in hdr and '#define ECSEG_ABI_VERSION 5' in hdr and _lib.ABI_VERSION == 5
+    assert 'still 5 - additive: ecseg_meta_inference_stages_debug' in hdr and '#define ECSEG_ABI_VERSION 6' in hdr and _lib.ABI_VERSION == 6
     assert 'ecseg_meta_inference_stages_debug' in _lib.EXPORTS and hasattr(_lib.Handle, 'meta_inference_stages')
 
 

@@ -271,12 +271,12 @@ def test_bad_splitter_parameters(tmp_path, monkeypatch, capsys, text, key):
 def test_header_export_and_defaults():
     header = open(os.path.join(ROOT, 'include', 'ecseg_hip.h')).read()
     assert 'int ecseg_min_cut(ecseg_ctx* h, const uint8_t* masks, long long mask_bytes, const int32_t* tasks, int n_tasks, int dist' in header
-    assert '#define ECSEG_ABI_VERSION 5' in header.replace('  ', ' ') or 'ECSEG_ABI_VERSION' in header
+    assert '#define ECSEG_ABI_VERSION 6' in header.replace('  ', ' ') or 'ECSEG_ABI_VERSION' in header
     for line in ('the source ball wins', 'capacity 2 into t', 'Nothing leaves t', 's has no arcs except to its ball'):
         assert line in header
     assert '#define ECSEG_MIN_CUT_MAX_DIST   %d' % _lib.Handle.MIN_CUT_MAX_DIST in header
     assert '#define ECSEG_MIN_CUT_LDS_PIXELS %d' % _lib.Handle.MIN_CUT_LDS_PIXELS in header
-    assert 'ecseg_min_cut' in _lib.EXPORTS and _lib.ABI_VERSION == 5 and hasattr(_lib.Handle, 'min_cut')
+    assert 'ecseg_min_cut' in _lib.EXPORTS and _lib.ABI_VERSION == 6 and hasattr(_lib.Handle, 'min_cut')
     assert sf.DEFAULT_PARAMS['flow_limit'] == 60 and sf.DEFAULT_PARAMS['cell_size_threshold_coeff'] == 1.25
     assert sf.MAX_DIST == _lib.Handle.MIN_CUT_MAX_DIST
     assert yaml.safe_load(open(os.path.join(ROOT, 'config.yaml')))['stat_fish']['use_min_cut'] is False

@@ -386,7 +386,7 @@ def test_header_binding_and_build_agree():
     assert 'int ecseg_rpn_proposals_last(ecseg_ctx* h, int A, const double* ref_anchors, int stride, int im_h, int im_w, float nms_threshold,' in header
     assert '#define ECSEG_RPN_MAX_PRE_NMS    %d' % _lib.Handle.RPN_MAX_PRE_NMS in header
     assert '#define ECSEG_RPN_MAX_CANDIDATES (1 << 22)' in header and _lib.Handle.RPN_MAX_CANDIDATES == 1 << 22
-    assert '#define ECSEG_ABI_VERSION 5' in header.replace('  ', ' ') and _lib.ABI_VERSION == 5
+    assert '#define ECSEG_ABI_VERSION 6' in header.replace('  ', ' ') and _lib.ABI_VERSION == 6
     for name in ('ecseg_nuset_forward', 'ecseg_rpn_proposals', 'ecseg_rpn_proposals_last'):
         assert name in _lib.EXPORTS
     for name in ('nuset_forward', 'rpn_proposals', 'rpn_proposals_last'):

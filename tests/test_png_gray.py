@@ -36,7 +36,7 @@ def test_header_binding_and_documents_name_the_new_symbols():
     assert ('int ecseg_png_channel_encode(ecseg_ctx* h, const uint8_t* pixels /* (n_img,H,W,C) host */, int n_img, int H, int W, int C, int channel, int invert,\n'
             '                             uint8_t* const* files, long long file_cap, long long* file_bytes);') in hdr
     assert 'int ecseg_overlay_files(ecseg_ctx* h, const uint8_t* labels, const void* img, int n_img, int H, int W, int C, int bytes_per_sample /* 1 | 2 */,' in hdr
-    assert 'still 5 - additive: ecseg_png_channel_encode' in hdr and '#define ECSEG_ABI_VERSION 5' in hdr and _lib.ABI_VERSION == 5
+    assert 'still 5 - additive: ecseg_png_channel_encode' in hdr and '#define ECSEG_ABI_VERSION 6' in hdr and _lib.ABI_VERSION == 6
     assert 'still 5 - additive: ecseg_png_labels_encode' in hdr                               # the earlier lines stay
     lib = _lib.load_library()
     for name in ('ecseg_png_channel_bound', 'ecseg_png_channel_encode', 'ecseg_overlay_files'):

@@ -319,8 +319,8 @@ def test_fish_distance_calculation_reads_what_the_run_leaves(tmp_path, monkeypat
 def test_header_binding_and_documents_of_the_new_symbol():
     hdr = open(os.path.join(ROOT, 'include', 'ecseg_hip.h')).read()
     assert 'int ecseg_fish_render(ecseg_ctx* h, const uint8_t* img, int H, int W, int C, const int32_t* channels' in hdr
-    assert 'still 5 - additive: ecseg_fish_render' in hdr and '#define ECSEG_ABI_VERSION 5' in hdr
-    assert 'ecseg_fish_render' in _lib.EXPORTS and hasattr(_lib.Handle, 'fish_render') and _lib.ABI_VERSION == 5
+    assert 'still 5 - additive: ecseg_fish_render' in hdr and '#define ECSEG_ABI_VERSION 6' in hdr
+    assert 'ecseg_fish_render' in _lib.EXPORTS and hasattr(_lib.Handle, 'fish_render') and _lib.ABI_VERSION == 6
     assert hasattr(_lib.load_library(), 'ecseg_fish_render')
     assert 'fs_render_kernel' in open(os.path.join(ROOT, 'ecseg_amd', 'csrc', 'fishspot_kernels.hip')).read()
     for doc in ('README.md', 'DESIGN.md'):

@@ -151,7 +151,7 @@ def test_the_header_the_binding_and_the_documents_name_the_feature():
     header = open(os.path.join(ROOT, 'include', 'ecseg_hip.h')).read()
     for name in ('ecseg_stat_fish_batch(', 'ecseg_stat_fish_batch_bytes(', 'ECSEG_STAT_FISH_BATCH_MAX_IMAGES'):
         assert name in header
-    assert '#define ECSEG_ABI_VERSION 5' in header
+    assert '#define ECSEG_ABI_VERSION 6' in header
     assert {'ecseg_stat_fish_batch', 'ecseg_stat_fish_batch_bytes'} <= set(_lib.EXPORTS) and hasattr(_lib.Handle, 'stat_fish_many')
     assert '# batch: 8' in open(os.path.join(ROOT, 'config.yaml')).read()
     for doc in ('README.md', 'DESIGN.md'):

@@ -26,7 +26,7 @@ PRE_NAMES = [c['name'] for c in PRE_CASES]
 
 def test_entry_points_are_declared_and_exported():
     hdr = open(os.path.join(HERE, '..', 'include', 'ecseg_hip.h')).read()
-    assert 'still 5 - additive: ecseg_stitch_stages_debug' in hdr and '#define ECSEG_ABI_VERSION 5' in hdr and _lib.ABI_VERSION == 5
+    assert 'still 5 - additive: ecseg_stitch_stages_debug' in hdr and '#define ECSEG_ABI_VERSION 6' in hdr and _lib.ABI_VERSION == 6
     for name, method in (('ecseg_stitch_stages_debug', 'stitch_stages'), ('ecseg_preprocess_stages_debug', 'preprocess_stages'),
                          ('ecseg_otsu_debug', 'otsu')):
         assert name in _lib.EXPORTS and name in hdr and hasattr(_lib.Handle, method)

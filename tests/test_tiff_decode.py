@@ -25,8 +25,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_header_binding_and_documents_name_the_new_symbol():
     hdr = open(os.path.join(ROOT, 'include', 'ecseg_hip.h')).read()
     assert 'int ecseg_tiff_decode(ecseg_ctx* h, const uint8_t* file, long long n_bytes, void* dst, long long dst_bytes,' in hdr
-    assert 'int* H, int* W, int* samples_per_pixel, int* bits_per_sample);' in hdr and 'int ecseg_tiff_decode_routes(const uint8_t* file, long long n_bytes);' in hdr
-    assert 'still 5 - additive: ecseg_tiff_decode' in hdr and '#define ECSEG_ABI_VERSION 5' in hdr and _lib.ABI_VERSION == 5
+    assert 'int* H, int* W, int* samples_per_pixel, int* bits_per_sample);' in hdr and 'int ecseg_tiff_decode_routes(const uint8_t* file, long long n_bytes, unsigned kinds);' in hdr
+    assert 'still 5 - additive: ecseg_tiff_decode' in hdr and '#define ECSEG_ABI_VERSION 6' in hdr and _lib.ABI_VERSION == 6
     assert 'still 5 - additive: ecseg_tiff_encode_bound' in hdr                 # the earlier lines stay
     assert 'skimage.io.imread' in hdr.split('int ecseg_tiff_decode(')[0][-2500:] and 'src/utils.py:110' in hdr.split('int ecseg_tiff_decode(')[0][-2500:]
     lib = _lib.load_library()

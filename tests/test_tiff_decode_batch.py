@@ -24,9 +24,9 @@ def test_header_binding_and_documents_name_the_new_symbols():
     assert ('int ecseg_tiff_decode_batch(ecseg_ctx* h, const uint8_t* files, long long files_bytes, const int64_t* file_ranges /* [n][2] offset, n_bytes */,\n'
             '                            int n_files, void* dst, long long dst_bytes, const int64_t* dst_offsets /* [n] */,\n'
             '                            int32_t* shapes /* [n][4] H, W, spp, bits */, int32_t* status /* [n] */);') in hdr
-    assert 'long long ecseg_tiff_decode_batch_bytes(const uint8_t* files, long long files_bytes, const int64_t* file_ranges, int n_files);' in hdr
-    assert 'int ecseg_tiff_decode_batch_routes(const uint8_t* files, long long files_bytes, const int64_t* file_ranges, int n_files);' in hdr
-    assert 'still 5 - additive: ecseg_tiff_decode_batch' in hdr and '#define ECSEG_ABI_VERSION 5' in hdr and _lib.ABI_VERSION == 5
+    assert 'long long ecseg_tiff_decode_batch_bytes(const uint8_t* files, long long files_bytes, const int64_t* file_ranges, int n_files, unsigned kinds);' in hdr
+    assert 'int ecseg_tiff_decode_batch_routes(const uint8_t* files, long long files_bytes, const int64_t* file_ranges, int n_files, unsigned kinds);' in hdr
+    assert 'still 5 - additive: ecseg_tiff_decode_batch' in hdr and '#define ECSEG_ABI_VERSION 6' in hdr and _lib.ABI_VERSION == 6
     assert 'still 5 - additive: ecseg_tiff_decode and ecseg_tiff_decode_routes' in hdr          # the earlier lines stay
     lib = _lib.load_library()
     for name in ('ecseg_tiff_decode_batch', 'ecseg_tiff_decode_batch_bytes', 'ecseg_tiff_decode_batch_routes', 'ecseg_tiff_decode_batch_counts'):
@@ -206,12 +206,12 @@ def test_the_routing_rule_on_synthetic_file_sets():
     lib = _lib.load_library()
     buf = np.frombuffer(f208, np.uint8)
     tab = np.array([[0, buf.size + 1]], np.int64)
-    assert lib.ecseg_tiff_decode_batch_routes(buf.ctypes.data, buf.size, tab.ctypes.data, 1) == 0
-    assert lib.ecseg_tiff_decode_batch_routes(buf.ctypes.data, buf.size, tab.ctypes.data, 0) == 0
-    assert lib.ecseg_tiff_decode_batch_bytes(buf.ctypes.data, buf.size, tab.ctypes.data, 1) == -1
-    assert lib.ecseg_tiff_decode_batch_bytes(buf.ctypes.data, buf.size, tab.ctypes.data, 0) == 0
+    assert lib.ecseg_tiff_decode_batch_routes(buf.ctypes.data, buf.size, tab.ctypes.data, 1, 0) == 0
+    assert lib.ecseg_tiff_decode_batch_routes(buf.ctypes.data, buf.size, tab.ctypes.data, 0, 0) == 0
+    assert lib.ecseg_tiff_decode_batch_bytes(buf.ctypes.data, buf.size, tab.ctypes.data, 1, 0) == -1
+    assert lib.ecseg_tiff_decode_batch_bytes(buf.ctypes.data, buf.size, tab.ctypes.data, 0, 0) == 0
     tab[0, 1] = buf.size
-    assert lib.ecseg_tiff_decode_batch_bytes(buf.ctypes.data, buf.size, tab.ctypes.data, 1) >= buf.size + 208 * 8
+    assert lib.ecseg_tiff_decode_batch_bytes(buf.ctypes.data, buf.size, tab.ctypes.data, 1, 0) >= buf.size + 208 * 8
 
 
 def test_file_images_that_lie_in_one_buffer_are_packed_without_a_copy():

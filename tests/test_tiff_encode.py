@@ -86,7 +86,7 @@ def test_header_binding_and_documents_of_the_new_symbols():
     assert 'long long ecseg_tiff_encode_bound(int H, int W, int spp);' in hdr
     assert 'int ecseg_tiff_encode(ecseg_ctx* h, const uint8_t* img, int H, int W, int spp, int invert, uint8_t* out' in hdr
     assert 'int ecseg_fish_render_tiff(ecseg_ctx* h, const uint8_t* img, int H, int W, int C, const int32_t* channels' in hdr
-    assert 'still 5 - additive: ecseg_tiff_encode_bound' in hdr and '#define ECSEG_ABI_VERSION 5' in hdr and _lib.ABI_VERSION == 5
+    assert 'still 5 - additive: ecseg_tiff_encode_bound' in hdr and '#define ECSEG_ABI_VERSION 6' in hdr and _lib.ABI_VERSION == 6
     lib = _lib.load_library()
     for name in ('ecseg_tiff_encode_bound', 'ecseg_tiff_encode', 'ecseg_fish_render_tiff'):
         assert name in _lib.EXPORTS and hasattr(lib, name), name

@@ -36,7 +36,7 @@ def test_header_binding_and_documents_name_the_new_symbols():
             '                            int n_files, uint8_t* out, long long out_cap, int64_t* out_ranges /* [n][2] offset, n_bytes */);') in hdr
     assert 'long long ecseg_tiff_encode_batch_bytes(const int64_t* files, int n_files);' in hdr
     assert 'int ecseg_fish_render_tiff_batch(ecseg_ctx* h, int n_images, const uint8_t* const* imgs, const int32_t* shapes' in hdr
-    assert 'still 5 - additive: ecseg_tiff_encode_batch' in hdr and '#define ECSEG_ABI_VERSION 5' in hdr and _lib.ABI_VERSION == 5
+    assert 'still 5 - additive: ecseg_tiff_encode_batch' in hdr and '#define ECSEG_ABI_VERSION 6' in hdr and _lib.ABI_VERSION == 6
     assert 'still 5 - additive: ecseg_tiff_encode_bound' in hdr                 # the earlier lines stay
     lib = _lib.load_library()
     for name in ('ecseg_tiff_encode_batch', 'ecseg_tiff_encode_batch_bytes', 'ecseg_fish_render_tiff_batch'):

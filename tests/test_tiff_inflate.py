@@ -3,6 +3,7 @@
 class of tests/tiff_inflate_cases.py, and the per-strip routine of tiffb_inflate_kernel (ti_inflate_strip) compiled for the host
 under ASan + UBSan against the host rule on that corpus."""
 import os
+import re
 import shutil
 import struct
 import subprocess
@@ -21,7 +22,8 @@ from ecseg_amd import _lib, image_io         # noqa: E402
 from ecseg_amd import stat_fish as sf        # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW = ('ecseg_tiff_decode_routes_ex', 'ecseg_tiff_decode_batch_routes_ex', 'ecseg_tiff_decode_batch_counts_ex', 'ecseg_tiff_decode_batch_bytes_ex')
+NEW = ('ecseg_tiff_decode_routes', 'ecseg_tiff_decode_batch_routes', 'ecseg_tiff_decode_batch_counts', 'ecseg_tiff_decode_batch_bytes')
+DEFINES = [('ECSEG_TIFF_DEFLATE', '1'), ('ECSEG_TIFF_TILED', '2'), ('ECSEG_TIFF_PACKBITS', '4')]      # re.findall(r'#define (ECSEG_TIFF_\w+)\s+(\d+)u', header)
 
 
 def test_header_binding_and_documents_name_the_option_and_the_new_symbols():
@@ -29,7 +31,8 @@ def test_header_binding_and_documents_name_the_option_and_the_new_symbols():
     lib = _lib.load_library()
     for name in NEW:
         assert name + '(' in hdr and name in _lib.EXPORTS and hasattr(lib, name), name
-    assert 'still 5 - additive: option "tiff_deflate_on_device"' in hdr and '#define ECSEG_ABI_VERSION 5' in hdr
+    assert re.findall(r'#define (ECSEG_TIFF_\w+)\s+(\d+)u', hdr) == DEFINES and not [n for n in _lib.EXPORTS if n.startswith('ecseg_tiff_decode') and '_ex' in n]
+    assert 'still 5 - additive: option "tiff_deflate_on_device"' in hdr and '#define ECSEG_ABI_VERSION 6' in hdr
     for doc in ('DESIGN.md', 'README.md', 'INTEGRATION.md'):
         text = open(os.path.join(ROOT, doc)).read()
         assert 'tiff_deflate_on_device' in text and 'tiff_read_deflate' in text, doc
@@ -153,13 +156,11 @@ def test_the_flagged_routing_functions_answer_as_the_old_ones_with_the_flag_off_
         for n in (1, 208, 1040, 3000):
             one = np.frombuffer(_file_of_strips(n, comp), np.uint8)
             buf, ranges = _lib.pack_file_images([one, one])
-            old = (lib.ecseg_tiff_decode_routes(_ptr(one), one.size), lib.ecseg_tiff_decode_batch_counts(_ptr(one), one.size),
-                   lib.ecseg_tiff_decode_batch_routes(_ptr(buf), buf.size, _ptr(ranges), 2))
-            off = (lib.ecseg_tiff_decode_routes_ex(_ptr(one), one.size, 0), lib.ecseg_tiff_decode_batch_counts_ex(_ptr(one), one.size, 0),
-                   lib.ecseg_tiff_decode_batch_routes_ex(_ptr(buf), buf.size, _ptr(ranges), 2, 0))
-            on = (lib.ecseg_tiff_decode_routes_ex(_ptr(one), one.size, 1), lib.ecseg_tiff_decode_batch_counts_ex(_ptr(one), one.size, 1),
-                  lib.ecseg_tiff_decode_batch_routes_ex(_ptr(buf), buf.size, _ptr(ranges), 2, 1))
-            assert old == off, (comp, n)
+            answers = lambda kinds: (lib.ecseg_tiff_decode_routes(_ptr(one), one.size, kinds), lib.ecseg_tiff_decode_batch_counts(_ptr(one), one.size, kinds),
+                                     lib.ecseg_tiff_decode_batch_routes(_ptr(buf), buf.size, _ptr(ranges), 2, kinds))
+            old, on = answers(0), answers(_lib.TIFF_DEFLATE)
+            for more in (_lib.TIFF_TILED, _lib.TIFF_PACKBITS, _lib.TIFF_TILED | _lib.TIFF_PACKBITS):     # a file of strips: the other two kinds change nothing
+                assert answers(more) == old and answers(_lib.TIFF_DEFLATE | more) == on, (comp, n, more)
             assert image_io.tiff_goes_to_device(one.tobytes()) == bool(old[0]) and image_io.tiff_goes_to_device(one.tobytes(), deflate=True) == bool(on[0])
             if comp in (1, 5):
                 assert on == old, (comp, n)
@@ -170,11 +171,12 @@ def test_the_flagged_routing_functions_answer_as_the_old_ones_with_the_flag_off_
             # the arena: nothing for a Deflate file without the flag (it is left out), with it what an LZW file of the same tags needs
             lzw = np.frombuffer(_file_of_strips(n, 5), np.uint8)
             r1 = np.array([[0, one.size]], np.int64)
-            assert lib.ecseg_tiff_decode_batch_bytes_ex(_ptr(one), one.size, _ptr(r1), 1, 0) == lib.ecseg_tiff_decode_batch_bytes(_ptr(one), one.size, _ptr(r1), 1)
-            need = lib.ecseg_tiff_decode_batch_bytes_ex(_ptr(one), one.size, _ptr(r1), 1, 1)
+            assert lib.ecseg_tiff_decode_batch_bytes(_ptr(one), one.size, _ptr(r1), 1, _lib.TIFF_TILED | _lib.TIFF_PACKBITS) == lib.ecseg_tiff_decode_batch_bytes(_ptr(one), one.size, _ptr(r1), 1, 0) == 6 * 256
+            need = lib.ecseg_tiff_decode_batch_bytes(_ptr(one), one.size, _ptr(r1), 1, _lib.TIFF_DEFLATE)
+            assert need == lib.ecseg_tiff_decode_batch_bytes(_ptr(one), one.size, _ptr(r1), 1, 7)
             slot = lambda v: (v + 255) // 256 * 256
             r2 = np.array([[0, lzw.size]], np.int64)
-            assert need - slot(one.size) == lib.ecseg_tiff_decode_batch_bytes(_ptr(lzw), lzw.size, _ptr(r2), 1) - slot(lzw.size) > 0
+            assert need - slot(one.size) == lib.ecseg_tiff_decode_batch_bytes(_ptr(lzw), lzw.size, _ptr(r2), 1, 0) - slot(lzw.size) > 0
 
 
 # ---- make stat_fish: the key ---------------------------------------------------------------------------------------------------------

@@ -5,6 +5,7 @@ program that walks tile_place, the tile-table parse and the staging -> raster co
 import base64
 import json
 import os
+import re
 import shutil
 import subprocess
 import sys
@@ -28,21 +29,24 @@ def _ptr(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
-def _answers(lib, data, deflate, tiled, two=True):
-    """(routes, counts, set routes, arena bytes of the file alone) of the handle-free functions with the two switches."""
+def _answers(lib, data, deflate, tiled, packbits=0):
+    """(routes, counts, set routes, arena bytes of the file alone) of the handle-free functions with the word of the switches."""
     one = np.frombuffer(data, np.uint8)
     buf, ranges = _lib.pack_file_images([one, one])
     r1 = np.array([[0, one.size]], np.int64)
-    return (lib.ecseg_tiff_decode_routes_ex2(_ptr(one), one.size, deflate, tiled), lib.ecseg_tiff_decode_batch_counts_ex2(_ptr(one), one.size, deflate, tiled),
-            lib.ecseg_tiff_decode_batch_routes_ex2(_ptr(buf), buf.size, _ptr(ranges), 2, deflate, tiled),
-            lib.ecseg_tiff_decode_batch_bytes_ex2(_ptr(one), one.size, _ptr(r1), 1, deflate, tiled))
+    kinds = _lib.tiff_kinds(deflate, tiled, packbits)
+    return (lib.ecseg_tiff_decode_routes(_ptr(one), one.size, kinds), lib.ecseg_tiff_decode_batch_counts(_ptr(one), one.size, kinds),
+            lib.ecseg_tiff_decode_batch_routes(_ptr(buf), buf.size, _ptr(ranges), 2, kinds),
+            lib.ecseg_tiff_decode_batch_bytes(_ptr(one), one.size, _ptr(r1), 1, kinds))
 
 
 def test_header_binding_and_documents_name_the_option_and_the_new_symbols():
     hdr = open(os.path.join(ROOT, 'include', 'ecseg_hip.h')).read()
-    for name in ('ecseg_tiff_decode_routes_ex2', 'ecseg_tiff_decode_batch_routes_ex2', 'ecseg_tiff_decode_batch_counts_ex2', 'ecseg_tiff_decode_batch_bytes_ex2'):
-        assert name in hdr and name in _lib.EXPORTS, name
-    assert 'still 5 - additive: option "tiff_tiled_on_device"' in hdr and '#define ECSEG_ABI_VERSION 5' in hdr
+    for name in ('ecseg_tiff_decode_routes', 'ecseg_tiff_decode_batch_routes', 'ecseg_tiff_decode_batch_counts', 'ecseg_tiff_decode_batch_bytes'):
+        assert name + '(' in hdr and name in _lib.EXPORTS, name
+    assert re.findall(r'#define (ECSEG_TIFF_\w+)\s+(\d+)u', hdr) == [('ECSEG_TIFF_DEFLATE', '1'), ('ECSEG_TIFF_TILED', '2'), ('ECSEG_TIFF_PACKBITS', '4')]
+    assert not [n for n in _lib.EXPORTS if n.startswith('ecseg_tiff_decode') and '_ex' in n]
+    assert 'still 5 - additive: option "tiff_tiled_on_device"' in hdr and '#define ECSEG_ABI_VERSION 6' in hdr
     for doc in ('README.md', 'DESIGN.md', 'config.yaml'):
         text = open(os.path.join(ROOT, doc)).read()
         assert 'tiff_read_tiled' in text, doc
@@ -95,7 +99,7 @@ def test_the_python_reader_on_the_damaged_files_is_the_verdict_the_device_tests_
 
 
 def test_the_parser_takes_tiled_files_only_with_the_switch_and_leaves_the_rest_to_the_python_reader():
-    """Through ecseg_tiff_decode_batch_bytes_ex2, which is -1 only for bad arguments and else what the accepted files need: a file the
+    """Through ecseg_tiff_decode_batch_bytes, which is -1 only for bad arguments and else what the accepted files need: a file the
     parser refuses needs the empty arena, an accepted one its staging slots on top."""
     lib = _lib.load_library()
     empty = None
@@ -104,8 +108,8 @@ def test_the_parser_takes_tiled_files_only_with_the_switch_and_leaves_the_rest_t
         off = _answers(lib, data, 0, 0)
         one = np.frombuffer(data, np.uint8)
         r1 = np.array([[0, one.size]], np.int64)
-        assert off[3] == lib.ecseg_tiff_decode_batch_bytes(_ptr(one), one.size, _ptr(r1), 1) == _answers(lib, data, 1, 0)[3], name
-        assert off[:3] == (0, 0, 0) and lib.ecseg_tiff_decode_routes(_ptr(one), one.size) == 0, name
+        assert off[3] == lib.ecseg_tiff_decode_batch_bytes(_ptr(one), one.size, _ptr(r1), 1, 0) == _answers(lib, data, 1, 0)[3], name
+        assert off[:3] == (0, 0, 0) and lib.ecseg_tiff_decode_routes(_ptr(one), one.size, 0) == 0, name
         empty = off[3] if empty is None else empty
         assert off[3] == empty == 6 * 256, 'a tiled file is left out without the switch: six empty slots'
         ext = [int(v) for v in name.split('_')[1].split('x') + name.split('_')[2][1:].split('x')]
@@ -140,15 +144,12 @@ def test_the_rule_functions_answer_as_before_with_the_switch_off_and_by_the_meas
     for name, b64 in files.items():                                    # strips, and the two tifffile-written tiled files
         data = base64.b64decode(b64)
         one = np.frombuffer(data, np.uint8)
-        buf, ranges = _lib.pack_file_images([one, one])
-        r1 = np.array([[0, one.size]], np.int64)
         for deflate in (0, 1):
-            old = (lib.ecseg_tiff_decode_routes_ex(_ptr(one), one.size, deflate), lib.ecseg_tiff_decode_batch_counts_ex(_ptr(one), one.size, deflate),
-                   lib.ecseg_tiff_decode_batch_routes_ex(_ptr(buf), buf.size, _ptr(ranges), 2, deflate),
-                   lib.ecseg_tiff_decode_batch_bytes_ex(_ptr(one), one.size, _ptr(r1), 1, deflate))
-            assert _answers(lib, data, deflate, 0) == old, (name, deflate)
-            if 'tiled' not in name:
+            old = _answers(lib, data, deflate, 0)
+            if 'tiled' not in name:                                    # a file of strips: TILED in the word changes none of the four answers,
                 assert _answers(lib, data, deflate, 1) == old, (name, deflate)
+                part = slice(3) if 'packbits' in name else slice(4)   # nor does PACKBITS, but for the arena of a PackBits file: it then parses
+                assert _answers(lib, data, deflate, 0, 1)[part] == old[part] == _answers(lib, data, deflate, 1, 1)[part], (name, deflate)
     big = tc.pixels('rgb8', 160, 1392)                                 # 870 tiles of 16 x 16
     for comp in (1, 5, 8):
         data = tc.tiled_tiff(big, 16, 16, comp, 2)

@@ -53,7 +53,7 @@ def want():
 
 def test_entry_points_are_declared_and_exported():
     hdr = open(os.path.join(HERE, '..', 'include', 'ecseg_hip.h')).read()
-    assert 'still 5 - additive: ecseg_marker_watershed_stages_debug' in hdr and '#define ECSEG_ABI_VERSION 5' in hdr and _lib.ABI_VERSION == 5
+    assert 'still 5 - additive: ecseg_marker_watershed_stages_debug' in hdr and '#define ECSEG_ABI_VERSION 6' in hdr and _lib.ABI_VERSION == 6
     for name, method in (('ecseg_marker_watershed_stages_debug', 'marker_watershed_stages'),
                          ('ecseg_marker_watershed_batch_stages_debug', 'marker_watershed_batch_stages')):
         assert name in _lib.EXPORTS and hasattr(_lib.Handle, method)

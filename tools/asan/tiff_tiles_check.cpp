@@ -161,7 +161,7 @@ int main() {
             const File& f = fs.back();
             TiffInfo t, t0;
             if (parse_tiff(f.image.data(), f.image.size(), &t0) != -5) { std::printf("round %d: a tiled file passes the parser without the switch\n", round); return 1; }
-            const int rc = parse_tiff(f.image.data(), f.image.size(), &t, true);
+            const int rc = parse_tiff(f.image.data(), f.image.size(), &t, ECSEG_TIFF_TILED);
             if (rc != (f.cut_table ? -5 : 0)) { std::printf("round %d: file %d: the parser says %d (table cut: %d)\n", round, i, rc, (int)f.cut_table); return 1; }
             TdFileIn d;
             src += rnd() % 3 == 0 ? rnd() % 40 : 0;
@@ -238,7 +238,7 @@ int main() {
                             : ((size_t)f.image[4] << 24) | ((size_t)f.image[5] << 16) | ((size_t)f.image[6] << 8) | f.image[7];
     const size_t tw_value = ifd + 2 + 12 * 7 + 8 + (f.le ? 0 : 3);           // the low byte of TileWidth, the eighth entry
     f.image[tw_value] = (uint8_t)(f.image[tw_value] + 8);
-    if (parse_tiff(f.image.data(), f.image.size(), &t, true) != -5) { std::printf("a tile width that is no multiple of 16 passes the parser\n"); return 1; }
+    if (parse_tiff(f.image.data(), f.image.size(), &t, ECSEG_TIFF_TILED) != -5) { std::printf("a tile width that is no multiple of 16 passes the parser\n"); return 1; }
     std::printf("tiff_tiles_check ok: %lld files, %lld tiles, %lld files refused for a short table\n", files, tiles, refused);
     return 0;
 }
